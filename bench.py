@@ -2,7 +2,7 @@
 """bench.py — the hot path of BASELINE.json on MI355X.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload importance|smc_lgssm|smc_hmm]
-                  [--rng philox|threefry] [--no-cpu-baseline] [--no-extra]
+                  [--rng philox|threefry] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-extra]]
 
 A "step" is one pass of the hot path over one batch of synthetic input, inputs resident in HBM:
   importance (default, BASELINE configs[1]): ImportanceK on the 10-latent Gaussian model, 1e6 particles per
@@ -11,11 +11,19 @@ A "step" is one pass of the hot path over one batch of synthetic input, inputs r
   smc_lgssm (configs[2]): bootstrap SMC, T=100, ONE filter of 1e6 particles.  value = particle-steps/s.
   smc_hmm   (configs[4]): 256-state HMM, T=500, ONE filter of 1e6 particles.
 
-Protocol: W untimed warm-up steps, then a block of EXACTLY K steps bracketed by barrier + synchronize on both
-sides (max over ranks).  A K-step block of a 18 us step is far too short to carry a number, so the block is
-repeated (each repetition bracketed the same way) until at least 50 ms and 5 blocks have been timed; `value`
-and `ms_per_step` are the MEDIAN block, `timed_blocks` / `block_ms_{min,median,max}` report the rest.  The
-dominant kernel is sampled with HIP events on the launch stream over all timed blocks (>= 20 samples; median).
+Protocol: W untimed warm-up steps (one process: followed by SETTLE_S seconds more of untimed steps, for the clocks to
+settle), then ONE block of EXACTLY K steps bracketed by barrier + synchronize on both sides (max over ranks); `value` and `ms_per_step`
+come from that block.  The dominant kernel is sampled with HIP
+events on the launch stream inside the block (median).
+
+A plain run measures the headline and prints the line, nothing else.  `--full` adds everything else the line used to
+carry: the other BASELINE configs and variants as `extra` / `configs` entries (each a median over repeated timed
+blocks), the CPU baselines, and the unabridged detail file ($GJX_BENCH_DETAIL).  `--no-extra` / `--no-cpu-baseline`
+leave parts of that out.
+
+`--dump-outputs DIR` (one GPU, importance or smc_*): after the timed block, the arrays the last timed step computed go
+to DIR/<name>.npy (float32 per-particle columns, float64 scalars), at most DUMP_MAX_BYTES in all: a larger output is
+cut to a fixed seeded sample of particles (`sample_index.npy`).  Inputs are seeded, so two builds compare 1:1.
 
 `--gpus N` with N > 1: launched by `torch.distributed.run` (RANK / WORLD_SIZE in the environment) this process
 is one rank; launched plainly it is the PARENT, which starts N rank processes before any GPU call, never touches
@@ -58,9 +66,16 @@ def parse():
     p.add_argument("--fast-math", action="store_true", help="importance / scan: the opt-in hardware-transcendental plan (profiling passes)")
     p.add_argument("--rng", default="philox", choices=["philox", "threefry"])
     p.add_argument("--particles", type=int, default=N_PER_GPU, help="particles per GPU")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-extra", action="store_true")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true", help="also the extra configs, the CPU baselines and the detail file")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    p.add_argument("--no-extra", action="store_true", help="--full without the extra configs")
+    p.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.gpus != 1 or FORCE_DIST or args.workload not in ("importance", "smc_lgssm", "smc_hmm")):
+        p.error("--dump-outputs: one GPU and --workload importance|smc_lgssm|smc_hmm")
+    return args
 
 
 FORCE_DIST = bool(os.environ.get("GJX_BENCH_FORCE_DIST"))  # exercise the N>1 code path with one rank
@@ -194,9 +209,57 @@ def timed_blocks(run_block, world, min_s=MIN_TIMED_S, min_blocks=5, max_blocks=2
 timed_blocks.last_reps = 1
 
 
-def block_stats(blocks):
+def timed_block(run_block, world):
+    """The headline's protocol: ONE bracket (barrier + synchronize on both sides, its duration the max over ranks) around
+    ONE call of `run_block()`, which runs exactly the K steps.  Returns the seconds and the block's result."""
+    barrier_sync(world)
+    t0 = time.perf_counter()
+    out = run_block()
+    barrier_sync(world)
+    return max_over_ranks(time.perf_counter() - t0, world), out
+
+
+SETTLE_S = 0.2
+
+
+def settle(run):
+    """Untimed `run()`s for SETTLE_S seconds, after the W warm-up steps: the device's clocks settle over the first tens of
+    milliseconds under load, and the headline's ONE timed block must not start before.  One process only (the
+    ranks of a group must make the same calls)."""
+    import torch
+
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < SETTLE_S:
+        run()
+        torch.cuda.synchronize()
+
+
+def block_stats(blocks, reps=None):
     return {"timed_blocks": len(blocks), "block_ms_min": min(blocks) * 1e3, "block_ms_median": statistics.median(blocks) * 1e3,
-            "block_ms_max": max(blocks) * 1e3, "blocks_per_bracket": timed_blocks.last_reps}
+            "block_ms_max": max(blocks) * 1e3, "blocks_per_bracket": timed_blocks.last_reps if reps is None else reps}
+
+
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(path, columns, scalars):
+    """`columns`: name -> tensor [..., n] (one value per particle, last axis), written as float32; `scalars`: name -> float,
+    written as float64.  Over DUMP_MAX_BYTES the columns keep a fixed seeded sample of particles (sorted; `sample_index`)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    n = next(iter(columns.values())).shape[-1]
+    per_particle = sum(4 * (t.numel() // n) for t in columns.values())
+    budget = DUMP_MAX_BYTES - 256 * (len(columns) + len(scalars) + 1)  # (.npy headers)
+    idx = None
+    if per_particle * n > budget:
+        idx = np.sort(np.random.default_rng(0).choice(n, budget // (per_particle + 8), replace=False))
+        np.save(os.path.join(path, "sample_index.npy"), idx.astype(np.float64))
+    for name, t in columns.items():
+        a = t.detach().cpu().numpy().astype(np.float32)
+        np.save(os.path.join(path, f"{name}.npy"), a if idx is None else a[..., idx])
+    for name, v in scalars.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.asarray([v], dtype=np.float64))
 
 
 def pmc_traffic(pattern: str, pick):
@@ -218,7 +281,10 @@ def pmc_traffic(pattern: str, pick):
 # ImportanceK (BASELINE configs[1])
 # ------------------------------------------------------------------------------------------------------------
 def bench_importance(args, ops, rank, world, launch_passes=None, rng=None, steps=None, warmup=None, ramp=True,
-                     min_s=MIN_TIMED_S, fast_math=False):
+                     min_s=MIN_TIMED_S, fast_math=False, exact=False, dump_dir=None):
+    """`exact`: the headline protocol (ONE timed block of `steps` passes); else a median over repeated blocks."""
+    import torch
+
     from genjax._amd import workloads as W
     from genjax._amd.ops import HipEvent
 
@@ -303,6 +369,8 @@ def bench_importance(args, ops, rank, world, launch_passes=None, rng=None, steps
     if ramp:
         run_steps(max(0, RAMP_PASSES - warmup), False)
     run_steps(warmup, False)
+    if exact and not sharded:
+        settle(lambda: run_steps(LAUNCH, False))
     # An event record is a barrier packet in the HIP queue; a back-to-back pair with nothing in between measures
     # that fixed cost, which is subtracted from the kernel intervals.
     cal = [(HipEvent(), HipEvent()) for _ in range(16)]
@@ -311,8 +379,20 @@ def bench_importance(args, ops, rank, world, launch_passes=None, rng=None, steps
         b.record(ops.stream())
     barrier_sync(world)
     ev_overhead_ms = statistics.median(a.elapsed_ms(b) for a, b in cal)
-    blocks, (e, q) = timed_blocks(lambda: run_steps(steps, True), world, min_s=min_s)  # each block: EXACTLY `steps` passes
-    dt = statistics.median(blocks)
+    if exact:
+        dt, (e, q) = timed_block(lambda: run_steps(steps, True), world)
+        blocks = [dt]
+    else:
+        blocks, (e, q) = timed_blocks(lambda: run_steps(steps, True), world, min_s=min_s)  # each block: EXACTLY `steps` passes
+        dt = statistics.median(blocks)
+    if dump_dir:
+        # the last step: the last pass of the last fold batch, at its position in that batch's last launch
+        last = (steps - 1) % BATCH
+        p = last % LAUNCH
+        dump_outputs(dump_dir, {"values": torch.stack([v[p, :n] for v in prep.values_all]), "score": prep.score_all[p, :n],
+                                "logw": prep.logw_all[p, :n]},
+                     {"log_z": ops.log_z_from_rows(prep.e_all[last:last + 1], prep.q_all[last:last + 1], total_particles),
+                      "lse": float(prep.lse_all[last])})
     # the dominant kernel: launches of `c` passes each; full launches (c == LAUNCH) define the quoted duration
     full = [(a, b, c) for a, b, c in samples if c == min(LAUNCH, steps)] or samples
     raw = sorted(a.elapsed_ms(b) for a, b, _ in full)
@@ -357,18 +437,20 @@ def bench_importance(args, ops, rank, world, launch_passes=None, rng=None, steps
     if pmc_insts:
         res["roofline"]["pmc_instructions_per_pass"] = {
             k: pmc_insts[k] for k in ("SQ_INSTS_VALU", "SQ_INSTS_VALU_TRANS_F32", "SQ_INSTS_SALU", "SQ_INSTS_VMEM", "SQ_WAVES") if k in pmc_insts}
-    res.update(block_stats(blocks))
+    res.update(block_stats(blocks, 1 if exact else None))
     return res, wl
 
 
 # ------------------------------------------------------------------------------------------------------------
 # bootstrap SMC (BASELINE configs[2], [4]; sharded: configs[3])
 # ------------------------------------------------------------------------------------------------------------
-def bench_smc_sharded(args, ops, rank, world, kind):
+def bench_smc_sharded(args, ops, rank, world, kind, steps=None, warmup=None):
     """BASELINE configs[3] (and its HMM sibling): the filter sharded over the ranks, 1e6 particles per GPU.  Driver: the
     library's own (`gjx_smc_sharded_run_*` over a `gjx_comm` RCCL communicator: per step ONE launch, the all-gather of
     the tile records, the grouped send/recv of the ancestor shuffle — no interpreter between the launches);
-    GJX_BENCH_PY_COMM=1 selects the Python `torch.distributed` loop instead (the same protocol, 2-3x the host time)."""
+    GJX_BENCH_PY_COMM=1 selects the Python `torch.distributed` loop instead (the same protocol, 2-3x the host time).
+    `steps` (the headline): `warmup` more untimed runs, then ONE timed block of exactly `steps` runs; a timed step is one
+    whole T-step run, and `ms_per_step` its time (without `steps`: the time of one SMC step, run / T)."""
     from genjax._amd import dist as gdist
 
     impl = 1 if args.rng == "philox" else 0
@@ -421,6 +503,8 @@ def bench_smc_sharded(args, ops, rank, world, kind):
         why = " | ".join(reasons) if transport == "rccl" else None
         if transport == "rccl" and (want == "peers" or REHEARSE):
             raise RuntimeError("the peer transport did not validate: " + str(why))
+    for _ in range(warmup if steps is not None else 0):
+        run()
     if smc is not None:
         smc.received = 0
     runs = [0]
@@ -429,13 +513,18 @@ def bench_smc_sharded(args, ops, rank, world, kind):
         runs[0] += 1
         return run()
 
-    blocks, r = timed_blocks(one_run, world, min_s=0.08, min_blocks=20, max_blocks=60)
-    dt = statistics.median(blocks)
+    if steps is not None:
+        t, r = timed_block(lambda: [one_run() for _ in range(steps)][-1], world)
+        blocks, dt = [t], t / steps
+    else:
+        blocks, r = timed_blocks(one_run, world, min_s=0.08, min_blocks=20, max_blocks=60)
+        dt = statistics.median(blocks)  # one run
     per_step_ms = dt * 1e3 / T
     achieved = BYTES_SMC_PER_PARTICLE_STEP * n / (per_step_ms * 1e-3) / 1e9
     res = {
         "metric": "particle-steps/sec, bootstrap SMC (1e6 particles per GPU)",
-        "value": n_total * T / dt, "unit": "particle-steps/s", "ms_per_step": per_step_ms,
+        # the headline's timed step is one whole run (as in bench_smc); the `extra` entry keeps its time per SMC step
+        "value": n_total * T / dt, "unit": "particle-steps/s", "ms_per_step": dt * 1e3 if steps is not None else per_step_ms,
         "config": {"workload": f"bootstrap SMC {kind} T={T} N={n_total} sharded x{world} (BASELINE configs[3] at world=8)",
                    "rng": args.rng, "shuffle": exchange,
                    "parallelism": (f"particle-sharded x{world}, peer transport: per step 1 step launch reading remote windows in place + 1 signal launch; no collective"
@@ -450,7 +539,7 @@ def bench_smc_sharded(args, ops, rank, world, kind):
         "log_z": r["log_z"], "log_z_exact": r["log_z_exact"],
         "bracket": {"empty_ms": empty_bracket_s(world) * 1e3, "min_ms": BRACKET_MIN_S * 1e3},
     }
-    res.update(block_stats(blocks))
+    res.update(block_stats(blocks, 1 if steps is not None else None))
     return res
 
 
@@ -650,10 +739,12 @@ def bench_sharded_rank0_virtual(args, ops, world=8, steps=40):
     return out
 
 
-def bench_smc(args, ops, kind, filters=1, min_s=0.08, variant=None, T=None):
+def bench_smc(args, ops, kind, filters=1, min_s=0.08, variant=None, T=None, steps=None, warmup=None, dump_dir=None):
     """Single device: `filters` independent filters (seeds s, s+1, ...) step in the same launches; filters=1 is
     the literal BASELINE config.  A "step" of the protocol here is one whole T-step filter run (one enqueue).
-    `variant`: extra keywords of the workload (ess_threshold, another model / observation sequence)."""
+    `variant`: extra keywords of the workload (ess_threshold, another model / observation sequence).
+    `steps` (the headline): `warmup` untimed runs, then ONE timed block of exactly `steps` runs; else ~50 ms of untimed
+    runs and a median over repeated one-run blocks."""
     import torch
 
     from genjax._amd import workloads as W
@@ -667,13 +758,18 @@ def bench_smc(args, ops, kind, filters=1, min_s=0.08, variant=None, T=None):
         kw.update(variant)
     wl = W.LgssmSMC(ops, impl, 1, n, T, **kw) if kind == "smc_lgssm" else W.HmmSMC(ops, impl, 2, n, T, **kw)
     g0 = ops.smc_run_graph_stats()  # (r04: from the second run of a shape on, a one-filter run is one replayed hipGraph)
-    # warm-up long enough for the clock ramp (see bench_importance): ~50 ms of the same launches
-    t0 = time.perf_counter()
-    out = wl.run()
-    torch.cuda.synchronize()
-    while time.perf_counter() - t0 < 0.05:
+    if steps is not None:
+        for _ in range(warmup):
+            wl.run()
+        settle(wl.run)
+    else:
+        # warm-up long enough for the clock ramp (see bench_importance): ~50 ms of the same launches
+        t0 = time.perf_counter()
         out = wl.run()
         torch.cuda.synchronize()
+        while time.perf_counter() - t0 < 0.05:
+            out = wl.run()
+            torch.cuda.synchronize()
     evs = []
 
     def one_run():
@@ -684,10 +780,17 @@ def bench_smc(args, ops, kind, filters=1, min_s=0.08, variant=None, T=None):
         evs.append((e0, e1))
         return o
 
-    blocks, out = timed_blocks(one_run, 1, min_s=min_s, min_blocks=20, max_blocks=60)
+    if steps is not None:
+        t, out = timed_block(lambda: [one_run() for _ in range(steps)][-1], 1)
+        blocks, reps, dt = [t], 1, t / steps
+    else:
+        blocks, out = timed_blocks(one_run, 1, min_s=min_s, min_blocks=20, max_blocks=60)
+        reps, dt = None, statistics.median(blocks)
     r = wl.result(out)
+    if dump_dir:
+        dump_outputs(dump_dir, {"state": r["state"], "logw": r["logw"]},
+                     {"log_z": r["log_z"]} if filters == 1 else {f"log_z_{f}": z for f, z in enumerate(r["log_z"])})
     dev_ms = statistics.median(a.elapsed_ms(b) for a, b in evs)
-    dt = statistics.median(blocks)
     per_step_ms = dev_ms / T
     achieved = BYTES_SMC_PER_PARTICLE_STEP * n * filters / (per_step_ms * 1e-3) / 1e9
     log_z = r["log_z"][0] if filters > 1 else r["log_z"]
@@ -717,7 +820,7 @@ def bench_smc(args, ops, kind, filters=1, min_s=0.08, variant=None, T=None):
         fl = r["resampled"] if filters == 1 else r["resampled"][0]
         res["resampling_steps"] = int(fl.sum())
         res["steps"] = T
-    res.update(block_stats(blocks))
+    res.update(block_stats(blocks, reps))
     g1 = ops.smc_run_graph_stats()
     res["config"]["launch_form"] = (
         f"whole run replayed as ONE hipGraph ({g1['replays'] - g0['replays']} of this entry's runs; keys, observations and model "
@@ -1290,11 +1393,12 @@ def run_rank(args):
                       else bench_scan_hmm(args, ops))
         return
     if args.workload == "importance":
-        res, _ = bench_importance(args, ops, rank, world, fast_math=args.fast_math)
+        res, _ = bench_importance(args, ops, rank, world, fast_math=args.fast_math, exact=True, dump_dir=args.dump_outputs)
     elif sharded:
-        res = bench_smc_sharded(args, ops, rank, world, args.workload)
+        res = bench_smc_sharded(args, ops, rank, world, args.workload, steps=args.steps, warmup=args.warmup)
     else:
-        res, smc_gpu = bench_smc(args, ops, args.workload, filters=int(os.environ.get("GJX_BENCH_FILTERS", "1")))
+        res, smc_gpu = bench_smc(args, ops, args.workload, filters=int(os.environ.get("GJX_BENCH_FILTERS", "1")),
+                                 steps=args.steps, warmup=args.warmup, dump_dir=args.dump_outputs)
     extra = {}
     out = None
     if rank == 0:
@@ -1306,9 +1410,9 @@ def run_rank(args):
         }
         out.update(res)
         out["log_z_abs_err_vs_exact"] = abs(out["log_z"] - out["log_z_exact"])
-        out["statistic"] = "median over timed_blocks repetitions of the K-step block"
+        out["statistic"] = "one timed block of exactly K steps"
     guard = None
-    if not args.no_extra and args.workload == "importance":
+    if args.full and not args.no_extra and args.workload == "importance":
         if sharded:
             # BASELINE configs[3]: the LGSSM filter with 1e6 particles per GPU, sharded (every rank takes part).  The
             # headline above is already measured: a rank that never comes back from the exchange must not cost the line.
@@ -1393,7 +1497,7 @@ def run_rank(args):
             except Exception as ex:  # reported, never silently dropped
                 extra["importance_fast_math"] = {"error": f"{type(ex).__name__}: {ex}"}
     if rank == 0:
-        if not args.no_cpu_baseline:  # (r04: N > 1 lines carry it too — rank 0's host cores, the same bounded sample)
+        if args.full and not args.no_cpu_baseline:  # (r04: N > 1 lines carry it too — rank 0's host cores, the same bounded sample)
             if args.workload == "importance":
                 # (N > 1: the CPU sample is ONE GPU's share, 1e6 particles — its log Z is not the job's, so nothing is compared)
                 out["cpu_baseline"] = cpu_baseline_importance(args, out["log_z"] if world == 1 else None)
@@ -1401,7 +1505,8 @@ def run_rank(args):
             else:
                 out["cpu_baseline"] = cpu_baseline_smc(args, args.workload, smc_gpu)
         if guard is None or guard.claim_line():
-            write_detail(out, extra)
+            if args.full:
+                write_detail(out, extra)
             emit_line(compact_line(out, extra, args))
     if sharded:
         import torch.distributed as dist

@@ -11,7 +11,7 @@ rm -rf "$OUT" && mkdir -p "$OUT"
 # Timing runs use bench.py's defaults (2048-pass clock ramp + 64 warm-up + 1024 timed passes, 8 passes per launch):
 # the timed region is the LAST 128 importance launches of the trace.  Counter runs need no steady clocks: 48 timed + 8
 # warm-up passes without the ramp, so every launch covers exactly 8 passes and a run makes 56 passes.
-BENCH="python3 bench.py"
+BENCH="python3 bench.py --full"
 PMCBENCH="python3 bench.py --steps 48 --warmup 8 --no-cpu-baseline --no-extra"
 export GJX_BENCH_RAMP=2048
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- $BENCH > "$OUT/bench_under_rocprof.log" 2>&1 || exit 1

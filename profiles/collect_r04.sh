@@ -9,7 +9,7 @@ OUT=gpurun_out/profiles_$TAG
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 rm -rf "$OUT" && mkdir -p "$OUT"
 # 1. the driver's command under the kernel trace (every kernel of the bench line, extras included)
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_under_rocprof.json" 2> "$OUT/bench_under_rocprof.err" || exit 1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_under_rocprof.json" 2> "$OUT/bench_under_rocprof.err" || exit 1
 echo "trace done"
 # 1b. r04 (VERDICT r03 hygiene): a kernel trace PER WORKLOAD, so that every `configs` entry has its own rows (the one-filter LGSSM
 # row of the whole-run trace mixes the normal and the collapsing-weights runs)
@@ -54,7 +54,7 @@ bash tools/pmc_samplers.sh > "$OUT/pmc_samplers.txt" 2>&1 || echo "pmc_samplers 
 [ -f genjax-chi_amd/lib/libgjx_hip_prof.so ] && bash tools/pmc_phases.sh lgssm > "$OUT/pmc_phases.txt" 2>&1
 unset GJX_BENCH_RAMP GJX_BENCH_MIN_S GJX_BENCH_LAUNCH
 # 3. the plain bench line of the same build
-GJX_BENCH_DETAIL="$OUT/bench_detail.json" timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 > "$OUT/bench_plain.json" 2> "$OUT/bench_plain.err" || exit 1
+GJX_BENCH_DETAIL="$OUT/bench_detail.json" timeout -k 10 400 python3 bench.py --full --steps 20 --warmup 5 > "$OUT/bench_plain.json" 2> "$OUT/bench_plain.err" || exit 1
 python3 profiles/summarize_r04.py "$TAG" "$OUT" > "$OUT/summarize.log" 2>&1 || { tail -20 "$OUT/summarize.log"; exit 1; }
 # keep the summaries; drop the raw per-dispatch CSVs (large)
 mkdir -p "$OUT/summary" && cp profiles/${TAG}_* "$OUT/summary/" 2>/dev/null

@@ -289,12 +289,16 @@ def test_bench_two_rank_line_rehearsal():
     env = dict(os.environ, GJX_BENCH_REHEARSE="1", HSA_ENABLE_IPC_MODE_LEGACY="0", GJX_BENCH_BRACKET_MIN_S="0.002")
     env.pop("RANK", None); env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "smc_lgssm", "--steps", "2",
-                        "--warmup", "1", "--particles", "200000"], env=env, capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--particles", "200000", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["scaling"] == "weak"
+    # one timed block of the 2 runs; a timed step is one whole run of T = 100 steps over both ranks' whole tiles
+    n_total, T = 2 * -(-200000 // 1024) * 1024, 100
+    assert d["timed_blocks"] == 1 and abs(d["block_ms_median"] / d["ms_per_step"] - 2) < 1e-9
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 / (n_total * T) - 1) < 1e-9
     assert d["config"]["transport"].startswith("peers"), d["config"]
     assert "roofline" in d and d.get("cpu_baseline") and d["cpu_baseline"]["value"] > 0
     assert abs(d["log_z"] - d["log_z_exact"]) < 1.0
