@@ -1272,9 +1272,7 @@ struct ResampleArgs {
   TileEss* ess_out = nullptr;           // GLOBAL, likewise (adaptive filters)
   int scan_max = kScanMax;              // rounds of the window scan (test knob: 0 = every output tile takes the per-slot search)
   int debug_stop = 0;                   // profiling builds only (-DGJX_PROFILE_HOOKS, GJX_SMC_DEBUG_STOP): leave the kernel after phase k
-  int xcd_map = 1;                      // contiguous output tiles per XCD (GJX_SMC_XCD_MAP=0: plain order)
   int wt_stores = 0;                    // write-through stores of the step's output columns (store16_out)
-  int wave_route = 1;                   // populations of up to kWave * 4 tiles: every WAVE merges the records itself (GJX_SMC_WAVE_ROUTE=0: LDS route)
   PeerMap pm;                           // r04: the source population is distributed over peers (PEERS instantiations only)
 };
 
@@ -1569,7 +1567,7 @@ GJX_DEV void policy_store_quad(Policy& P, int64_t jq, int64_t out_lo, const uint
 // in the write-back at the kernel's end (the next step's workgroups, on any XCD, read them from memory either way).
 // Measured (r03), one filter of 1e6 particles: LGSSM step 13.17 -> 12.59 us, HMM 13.73 -> 13.22; with 16 filters per launch
 // the write-back wins (127 vs 132 us: the next step finds part of its input in the L2s), so the host sets `wt` for
-// one-filter launches only (ResampleArgs::wt_stores; GJX_SMC_WT=0|1 forces it).
+// one-filter launches only (ResampleArgs::wt_stores).
 GJX_DEV void store16_out(void* p, uint4 v, bool wt) {
 #if defined(__HIP_DEVICE_COMPILE__)
   if (wt) {
@@ -1827,7 +1825,7 @@ GJX_DEV void resample_body_impl(const ResampleArgs& A, Policy& P) {
   auto src_qw = [&](uint64_t i) -> const uint32_t* { return PEERS ? peer_ptr(qw_all + i, sh_delta[(uint32_t)(i >> 10) / tpr]) : qw_all + i; };
   GJX_DBG_STOP(A, 15);  // (profiling: the launch / dispatch floor)
   const bool adaptive = ADAPTIVE && A.ess_thr > 0.0;
-  if (A.xcd_map) {
+  {
     // XCD-aware tile order: workgroups are dealt to the 8 XCDs round-robin, and neighbouring output tiles read
     // overlapping source windows — give every XCD a CONTIGUOUS range of output tiles so that the overlap is served by its
     // own L2 instead of a second trip to memory (a bijection on the launch's tiles: same results)
@@ -1858,7 +1856,7 @@ GJX_DEV void resample_body_impl(const ResampleArgs& A, Policy& P) {
   constexpr int kC = kMaxLdsTiles / kBlock;  // tiles per thread of the in-kernel merge
   const bool grouped = LDSP && A.groups != nullptr;  // (launch-uniform)
   constexpr bool lds_prefix = LDSP;               // (true for the LDS, the wave and the grouped route)
-  const bool wave_route = lds_prefix && !grouped && A.wave_route != 0 && A.ntiles <= (uint64_t)(kWave * kC);  // (launch-uniform)
+  const bool wave_route = lds_prefix && !grouped && A.ntiles <= (uint64_t)(kWave * kC);  // (launch-uniform)
   const uint64_t ngroups = grouped ? (A.ntiles + kGroupTiles - 1) / kGroupTiles : 0;  // <= kMaxGroups = kBlock: one per thread
   // the tiles whose prefix will live in LDS: [k_base, k_base + nrange).  Grouped route: SPECULATIVELY the four groups around
   // the output tile's own position (ancestors stay near their slots unless the weights are very uneven), so that the tile
@@ -2355,8 +2353,8 @@ GJX_DEV void resample_args_anchor(const ResampleArgs& A) {
 #if defined(__HIP_DEVICE_COMPILE__)
   asm volatile("" ::"s"(A.qw), "s"(A.recs), "s"(A.subs), "s"(A.n), "s"(A.ntiles), "s"(A.n_out), "s"(A.out_lo), "s"(A.out_hi));
   asm volatile("" ::"s"(A.u0), "s"(A.e_out), "s"(A.q_out), "s"(A.prefix), "s"(A.groups), "s"(A.fb.n_filters), "s"(A.ess_thr));
-  asm volatile("" ::"s"(A.qw_out), "s"(A.logw_out), "s"(A.recs_out), "s"(A.subs_out), "s"(A.scan_max), "s"(A.xcd_map),
-               "s"(A.wt_stores), "s"(A.wave_route), "s"(A.resampled_out));
+  asm volatile("" ::"s"(A.qw_out), "s"(A.logw_out), "s"(A.recs_out), "s"(A.subs_out), "s"(A.scan_max), "s"(A.wt_stores),
+               "s"(A.resampled_out));
 #endif
 }
 template <int IMPL, class Policy, bool ADAPTIVE = true, bool PEERS = false>

@@ -980,13 +980,12 @@ __global__ __launch_bounds__(kBlock) void k_group_records(const TileRec* recs, c
     if (tid == 0) groups[g].e = e;
   }
 }
-// Which route a population beyond kMaxLdsTiles takes (resample_body): group records (default) or the precomputed global
-// prefix (GJX_SMC_BIG_ROUTE=prefix: the r03 route, kept for A/B and for populations beyond kMaxGroups groups).  `scratch`:
-// the caller's u64[prefix_words(ntiles)].  -> true: A.groups is set and the group launch is enqueued.
+// Which route a population beyond kMaxLdsTiles takes (resample_body): group records whenever they fit, else the
+// precomputed global prefix (the r03 route: populations beyond kMaxGroups groups).  `scratch`: the caller's
+// u64[prefix_words(ntiles)].  -> true: A.groups is set and the group launch is enqueued.
 static bool launch_group_records(ResampleArgs& A, uint64_t* scratch, hipStream_t st) {
-  static const bool allow = [] { const char* e = std::getenv("GJX_SMC_BIG_ROUTE"); return !(e && e[0] == 'p'); }();
   const uint64_t ng = (A.ntiles + kGroupTiles - 1) / kGroupTiles;
-  if (!allow || !scratch || ng > (uint64_t)kMaxGroups || (((uintptr_t)scratch) & 15) != 0 ||
+  if (!scratch || ng > (uint64_t)kMaxGroups || (((uintptr_t)scratch) & 15) != 0 ||
       ng * sizeof(GroupRec) > prefix_words(A.ntiles) * sizeof(uint64_t))
     return false;
   GroupRec* groups = reinterpret_cast<GroupRec*>(scratch);
@@ -2005,12 +2004,10 @@ static void cat_tables_prepare(CSite* sites, int n, std::vector<void*>* owned) {
     uint2* ent = nullptr;
     uint4* guide4 = nullptr;
     // buckets per row: finer than the categories (so that a bucket rarely holds more than two), within a table of a few MB
-    // that the L2s keep (GJX_CAT_GUIDE_BITS: tuning knob)
-    static const int gknob = [] { const char* e = std::getenv("GJX_CAT_GUIDE_BITS"); return e ? atoi(e) : 0; }();
+    // that the L2s keep
     int gbits = 8;
     while ((1 << gbits) < 4 * st.n_cat && gbits < 11) ++gbits;
     while (gbits > 8 && (sizeof(uint4) << gbits) * rows > ((size_t)2 << 20)) --gbits;
-    if (gknob >= 4 && gknob <= 16) gbits = gknob;
     if (hipMalloc(&ent, sizeof(uint2) * rows * (size_t)st.n_cat) != hipSuccess || hipMalloc(&guide4, (sizeof(uint4) << gbits) * rows) != hipSuccess) {
       (void)hipGetLastError();
       if (ent) (void)hipFree(ent);
@@ -2298,10 +2295,7 @@ static int jit_form_pref() {  // GJX_JIT_FORM = one | pair | quad (test / tuning
   const char* e = std::getenv("GJX_JIT_FORM");
   if (e && !strcmp(e, "one")) return 1;
   if (e && !strcmp(e, "pair")) return 2;
-  if (e && !strcmp(e, "quad")) return 4;
-  const char* old = std::getenv("GJX_JIT_PAIRED");  // 0: always the one-particle-per-lane form
-  if (old && old[0] == '0') return 1;
-  return 4;  // measured (tools/ab_importance.py, 1e6 particles): quad 13.1 / pair 13.6 / one 28.3 us per pass at 8 passes per launch
+  return 4;  // quad; measured (tools/ab_importance.py, 1e6 particles): quad 13.1 / pair 13.6 / one 28.3 us per pass at 8 passes per launch
 }
 int gjx_plan_specialized_source(const gjx_plan* p, int impl, char* buf, size_t buf_len, size_t* needed) {
   if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
@@ -2372,10 +2366,9 @@ static gjx_jit::Compiled& plan_compiled(gjx_plan* mp, const gjx_keys* pk, int la
       // The kernels are bound by dependency latency, not by issue slots (a wave64 VALU instruction issues in ~2.4
       // cycles, tools/microbench/valu_rate.hip): a sixth wave per SIMD (<= 80 VGPRs) is worth 2-3 % on the paired
       // form as long as the allocator gets there with (next to) no spilling; otherwise the unconstrained build is kept.
-      const char* e = std::getenv("GJX_JIT_MIN_WAVES");  // test knob: force the hint (0 = none)
-      const int hint = e ? atoi(e) : (P == 2 ? 6 : 0);
+      const int hint = P == 2 ? 6 : 0;
       bool ok = gjx_jit::compile(make(hint), pk->impl, &c);
-      if (ok && !e && hint > 0) {
+      if (ok && hint > 0) {
         int scratch = 0;
         const hipError_t qe = hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, c.fn);
         if (qe != hipSuccess) (void)hipGetLastError();  // a failed query must not surface as a launch error later
@@ -2479,12 +2472,7 @@ static int importance_launch(const gjx_plan* p, const gjx_keys* pk, int32_t n_pa
       PlanParams prm = p->prm;
       PlanTables tabs = c.tabs;
       void* args[] = {&k, &cols, &score, &logw, &nn, &max_partials, &row_e, &row_s, &tail, &bt, &prm, &tabs};
-      uint64_t rows = ((uint64_t)n_pass * nrows_of(n) + c.rows_per_block - 1) / c.rows_per_block;
-      static const uint64_t grid_cap = [] {
-        const char* e = std::getenv("GJX_IMPORTANCE_GRID");
-        return e ? (uint64_t)strtoull(e, nullptr, 10) : 0ull;
-      }();
-      if (grid_cap && rows > grid_cap) rows = grid_cap;  // the kernel strides over rows
+      const uint64_t rows = ((uint64_t)n_pass * nrows_of(n) + c.rows_per_block - 1) / c.rows_per_block;
       if (hipModuleLaunchKernel(c.fn, (unsigned)(rows > 0x7fffffffull ? 0x7fffffffull : rows), 1, 1, (unsigned)c.block, 1, 1, 0,
                                 S(s), args, nullptr) != hipSuccess)
         return GJX_ERR_LAUNCH;
@@ -2941,10 +2929,7 @@ static int smc_resample_args(const gjx_smc_config* cfg, int t, const gjx_smc_pop
   static const int dbg_stop = [] { const char* e = std::getenv("GJX_SMC_DEBUG_STOP"); return e ? atoi(e) : 0; }();
   A.debug_stop = dbg_stop;
 #endif
-  static const int xcd_map = [] { const char* e = std::getenv("GJX_SMC_XCD_MAP"); return e ? atoi(e) : 1; }();
-  A.xcd_map = xcd_map;
-  static const int wt_knob = [] { const char* e = std::getenv("GJX_SMC_WT"); return e ? atoi(e) : -1; }();
-  A.wt_stores = wt_knob >= 0 ? wt_knob : (ctx.fb.n_filters > 1 ? 0 : 1);  // (measured: store16_out, gjx_device.hpp)
+  A.wt_stores = ctx.fb.n_filters > 1 ? 0 : 1;  // (measured: store16_out, gjx_device.hpp)
   // The merged prefix by ONE small launch (a workgroup per filter) instead of in every workgroup: required beyond
   // kMaxLdsTiles, and worth it from a few filters per launch (the whole-run drivers provide prev->prefix then), where its
   // ~4 us are shared by all filters while every one of the F x tiles workgroups saves the merge of its filter's records.
@@ -2952,10 +2937,8 @@ static int smc_resample_args(const gjx_smc_config* cfg, int t, const gjx_smc_pop
     if (!peers_ok(cfg) || ctx.fb.n_filters > 1) return GJX_ERR_INVALID;
     A.pm = peer_map_of(cfg->peers, cfg->n_total);
   }
-  static const int wave_route = [] { const char* e = std::getenv("GJX_SMC_WAVE_ROUTE"); return e ? atoi(e) : 1; }();
-  A.wave_route = wave_route;
   // (r04: filters of up to 256 tiles merge their records inside every wave — no prefix launch even for a batch of filters)
-  const bool in_wave = wave_route != 0 && A.ntiles <= (uint64_t)(kWave * (kMaxLdsTiles / kBlock));
+  const bool in_wave = A.ntiles <= (uint64_t)(kWave * (kMaxLdsTiles / kBlock));
   if (A.ntiles > (uint64_t)kMaxLdsTiles || (ctx.fb.n_filters > 1 && prev->prefix && !in_wave)) {
     if (ctx.fb.n_filters > 1 && A.ntiles > (uint64_t)kMaxLdsTiles) return GJX_ERR_UNSUPPORTED;
     const unsigned nf = ctx.fb.n_filters > 1 ? ctx.fb.n_filters : 1u;
@@ -3117,11 +3100,10 @@ int gjx_smc_peer_signal(const gjx_smc_peers* peers, const gjx_tile_rec* recs, co
   return launch_status();
 }
 int gjx_smc_peer_signal_fused(const gjx_smc_config* cfg) {
-  // (the group-record route: one filter beyond kMaxLdsTiles tiles, within kMaxGroups groups, not switched off)
+  // (the group-record route: one filter beyond kMaxLdsTiles tiles, within kMaxGroups groups)
   if (!cfg || !cfg->peers || cfg->n_filters > 1) return 0;
-  static const bool allow = [] { const char* e = std::getenv("GJX_SMC_BIG_ROUTE"); return !(e && e[0] == 'p'); }();
   const uint64_t nt = ntiles_of(cfg->n_total);
-  return allow && nt > (uint64_t)kMaxLdsTiles && (nt + kGroupTiles - 1) / kGroupTiles <= (uint64_t)kMaxGroups ? 1 : 0;
+  return nt > (uint64_t)kMaxLdsTiles && (nt + kGroupTiles - 1) / kGroupTiles <= (uint64_t)kMaxGroups ? 1 : 0;
 }
 int gjx_smc_peer_wait(const gjx_smc_peers* peers, uint64_t value, gjx_stream s) {
   if (!peers_desc_ok(peers)) return GJX_ERR_INVALID;
@@ -3153,6 +3135,8 @@ struct RunCommon {
   int last = 0;
   FilterBatch fb;
 };
+// filters per launch from which the merge of the tile records is a launch of its own (k_scan_records; smc_resample_args)
+constexpr unsigned kPrefixFilters = 4;
 static int run_common_init(const gjx_smc_config* cfg, Carver& cv, RunCommon& rc, int n_state, void* const* state_out,
                            float* logw_out, gjx_stream s, bool clear_flags = true) {
   const uint64_t N = cfg->n_total;
@@ -3175,11 +3159,7 @@ static int run_common_init(const gjx_smc_config* cfg, Carver& cv, RunCommon& rc,
     rc.pop[i].recs = reinterpret_cast<gjx_tile_rec*>(cv.take<TileRec>((size_t)rc.F * rc.nt));
     rc.pop[i].subs = reinterpret_cast<gjx_tile_sub*>(cv.take<TileSub>((size_t)rc.F * rc.nt));
     rc.pop[i].ess = rc.adaptive ? reinterpret_cast<gjx_tile_ess*>(cv.take<TileEss>((size_t)rc.F * rc.nt)) : nullptr;
-    static const unsigned prefix_filters = [] {
-      const char* e = std::getenv("GJX_SMC_PREFIX_FILTERS");  // tuning knob: filters per launch from which the merge is a launch of its own
-      return e ? (unsigned)atoi(e) : 4u;
-    }();
-    rc.pop[i].prefix = (rc.nt > (uint64_t)kMaxLdsTiles || rc.F >= prefix_filters) ? cv.take<uint64_t>((size_t)rc.F * prefix_words(rc.nt)) : nullptr;
+    rc.pop[i].prefix = (rc.nt > (uint64_t)kMaxLdsTiles || rc.F >= kPrefixFilters) ? cv.take<uint64_t>((size_t)rc.F * prefix_words(rc.nt)) : nullptr;
   }
   // log-weights: an adaptive filter carries them from step to step; otherwise only the last step's are stored
   rc.logw_final = logw_out;
@@ -3322,8 +3302,7 @@ int gjx_scan_run(gjx_scan_plan* p, const gjx_scan_io* io, gjx_stream s) {
     uintptr_t al = (uintptr_t)io->logw | (uintptr_t)io->score | (uintptr_t)(4 * io->col_stride) | (uintptr_t)(4 * io->n);
     for (int c = 0; c < io->n_value_cols; ++c) al |= (uintptr_t)io->value_cols[c];
     for (int d = 0; d < p->n_state; ++d) al |= io->carry_out ? (uintptr_t)io->carry_out[d] : 0;
-    static const bool allow = [] { const char* e = std::getenv("GJX_SCAN_QUAD"); return !(e && e[0] == '0'); }();
-    quad = allow && impl == 1 && pk->mode == 1 && pk->parent_lane == 0 && (pk->first & 1) == 0 && (al & 15) == 0;
+    quad = impl == 1 && pk->mode == 1 && pk->parent_lane == 0 && (pk->first & 1) == 0 && (al & 15) == 0;
   }
   gjx_jit::Compiled& c = p->jit[quad ? 2 : impl];
   if (c.state == 0) {

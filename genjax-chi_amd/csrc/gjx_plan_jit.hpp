@@ -465,34 +465,19 @@ inline void emit_prelude(std::ostringstream& o, bool fast_math = false, bool bm_
   // (resource anchored 1 GiB below the first lane's address; every lane of the wave reads the same table, so all offsets
   // are in range) the scan of the 256-state HMM runs 4.02 -> 2.39 ms per 5e8 particle-steps against the same load as
   // global_load_dwordx4; the sc0 / sc1 bits make no further difference, a non-temporal global load is 2x slower and an
-  // agent-scope pair of 8-byte loads is even (profiles/r04_ab/README.md).  GJX_GUIDE_LOAD=global keeps the old form for A/B.
-  {
-    const char* gl = std::getenv("GJX_GUIDE_LOAD");
-    if (gl && !strcmp(gl, "global"))
-      o << "__device__ __forceinline__ uint4 jguide_load(const uint4* p){ return *p; }\n";
-    else
-      o << "typedef unsigned jv4u_t __attribute__((ext_vector_type(4)));\n__device__ __forceinline__ uint4 jguide_load(const uint4* p){ const uint64_t a=(uint64_t)(uintptr_t)p; const uint64_t first=((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a>>32))<<32)|(uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a); const uint64_t base=first-(1ull<<30); __amdgpu_buffer_rsrc_t rs=__builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)base,0,0x7fffffff,0x00020000); const jv4u_t v=__builtin_amdgcn_raw_buffer_load_b128(rs,(int)(uint32_t)(a-base),0,0); return make_uint4(v[0],v[1],v[2],v[3]); }\n";
-  }
+  // agent-scope pair of 8-byte loads is even (profiles/r04_ab/README.md).
+  o << "typedef unsigned jv4u_t __attribute__((ext_vector_type(4)));\n__device__ __forceinline__ uint4 jguide_load(const uint4* p){ const uint64_t a=(uint64_t)(uintptr_t)p; const uint64_t first=((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a>>32))<<32)|(uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a); const uint64_t base=first-(1ull<<30); __amdgpu_buffer_rsrc_t rs=__builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)base,0,0x7fffffff,0x00020000); const jv4u_t v=__builtin_amdgcn_raw_buffer_load_b128(rs,(int)(uint32_t)(a-base),0,0); return make_uint4(v[0],v[1],v[2],v[3]); }\n";
   o << "__device__ __forceinline__ int32_t jcat_invcdf_gb(const uint4* guide, const uint2* ent, uint32_t K, uint32_t bits, int sh, uint32_t& lpb){ const uint4 g=jguide_load(guide+(bits>>sh)); const uint32_t c0=g.y&511u, c1=(g.y>>9)&511u; if (bits<=g.x){ lpb=g.z; return (int32_t)c0; } if (!(g.y>>18)){ lpb=g.w; return (int32_t)c1; } const uint64_t thr=((uint64_t)bits*(uint64_t)ent[K-1].x)>>32; uint32_t c=c1; uint2 e=ent[c]; while (c<K-1 && (uint64_t)e.x<=thr){ ++c; e=ent[c]; } lpb=e.y; return (int32_t)c; }\n";
   o << "template <int IMPL> __device__ __forceinline__ int32_t jcat_gumbel(const float* l, uint32_t K, const Stream<IMPL>& st){ int32_t best=0; float bv=-__builtin_inff(); for(uint32_t c=0;c<K;++c){ const float v = l[c] + gumbel_from_bits(st.bits32(c)); if (v>bv || c==0){ bv=v; best=(int32_t)c; } } return best; }\n";
 }
 
-// Write-through (sc1) column stores in the quad kernels when a launch holds ONE pass (store16_out, gjx_device.hpp): the
-// kernel's end no longer waits for the write-back of its 48 MB — 4.94e10 -> 5.47e10 particles/s at one pass per launch;
-// with many passes per launch the write-back overlaps the following passes and plain stores are 1 % faster, hence the
-// run-time flag.  GJX_JIT_WT=0: plain stores always.
-inline bool wt_stores_knob() {
-  const char* e = std::getenv("GJX_JIT_WT");
-  return !(e && e[0] == '0');
-}
 // The sites of a lane that owns NP whole PAIRS of adjacent particles (suffixes A, B [, C, D]) under PHILOX: one cipher
 // block per pair and two draws (pk0 / pk1: the cipher key; pair0 [, pair1]: the pairs' counter words — defined by the
 // caller), one Box-Muller transform per pair and Normal site, every stored column one vector store at `store_at`.
-// GJX_JIT_GAMMA_MULTI=0: every particle of a lane loops over its own rejection attempts (the r01-r03 form; A/B knob)
-inline bool gamma_multi_knob() {
-  const char* e = std::getenv("GJX_JIT_GAMMA_MULTI");
-  return !(e && e[0] == '0');
-}
+// The quad kernels store write-through (sc1) when a launch holds ONE pass (store16_out, gjx_device.hpp): the kernel's end
+// no longer waits for the write-back of its 48 MB — 4.94e10 -> 5.47e10 particles/s at one pass per launch; with many
+// passes per launch the write-back overlaps the following passes and plain stores are 1 % faster, hence the run-time flag
+// `wt_one_pass`.
 template <class CSiteT, class CArgT>
 inline void emit_pair_lane_sites(std::ostringstream& o, std::vector<SiteEmitter<CSiteT, CArgT>>& em, const CSiteT* sites, int n_sites,
                                  int NP, const std::string& ind, const std::string& store_at) {
@@ -534,7 +519,7 @@ int cur_pair_blk = -1;
         em[2 * pi].tail(q, "zc" + Z);
         em[2 * pi + 1].tail(q, "zs" + Z);
       }
-    } else if (!st.observed && (st.dist == GJX_DIST_GAMMA || st.dist == GJX_DIST_BETA) && gamma_multi_knob()) {
+    } else if (!st.observed && (st.dist == GJX_DIST_GAMMA || st.dist == GJX_DIST_BETA)) {
       // the lane's P particles draw their gammas TOGETHER (gjx_device.hpp std_gamma_multi: the first attempts straight-line,
       // the retries in one shared loop): the same values as P std_gamma calls, fewer divergent wave-trips
       const std::string I = std::to_string(em[0].impl), PS = std::to_string(P);
@@ -570,13 +555,11 @@ int cur_pair_blk = -1;
       std::string vals;
       for (int u = 0; u < P; ++u)
         vals += (u ? ", " : "") + (isint ? "(uint32_t)vi" + Q + sfx[u] : "f2u(vf" + Q + sfx[u] + ")");
-      o << "#ifndef GJX_EXP_NO_VALUE_STORES\n";
-      if (P == 4 && wt_stores_knob())
+      if (P == 4)
         o << ind << "store16_out(reinterpret_cast<uint32_t*>(cols.out[" << st.out_col << "]) + " << store_at << ", make_uint4(" << vals << "), wt_one_pass);\n";
       else
-      o << ind << "*reinterpret_cast<uint" << P << "*>(reinterpret_cast<uint32_t*>(cols.out[" << st.out_col << "]) + " << store_at << ") = make_uint" << P
-        << "(" << vals << ");\n";
-      o << "#endif\n";
+        o << ind << "*reinterpret_cast<uint" << P << "*>(reinterpret_cast<uint32_t*>(cols.out[" << st.out_col << "]) + " << store_at << ") = make_uint" << P
+          << "(" << vals << ");\n";
     }
   }
 }
@@ -625,8 +608,7 @@ struct Gen {
     // the fused tail in one trip of loads instead of 8 by a single wave (host-API call 52.5 -> 47.6 us at 1e6 particles)
     bool any_col = false;
     for (int q = 0; q < n_sites; ++q) any_col = any_col || sites[q].out_col >= 0;
-    int R = (NP == 2 && !any_col) ? 4 : 1;
-    if (const char* e = std::getenv("GJX_JIT_PAIR_ROWS")) R = atoi(e) == 2 ? 2 : (atoi(e) == 4 ? 4 : 1);
+    const int R = (NP == 2 && !any_col) ? 4 : 1;
     block = lanes_per_row * R;
     rows_per_block = R;
     const int waves_per_row = lanes_per_row / 64;  // 2 (pairs) or 1 (quads)
@@ -683,18 +665,16 @@ struct Gen {
     o << "      const uint64_t pair0 = (lnA - 1u) >> 1;\n";
     if (NP == 2) o << "      const uint64_t pair1 = pair0 + 1u;\n";
     emit_pair_lane_sites<CSiteT, CArgT>(o, em, sites, n_sites, NP, "      ", "po + iA");
-    {
+    if (P == 4) {
+      std::string wb, sb;
+      for (int u = 0; u < P; ++u) { wb += (u ? ", f2u(w" : "f2u(w") + std::string(sfx[u]) + ")"; sb += (u ? ", f2u(sc" : "f2u(sc") + std::string(sfx[u]) + ")"; }
+      o << "      if (logw) store16_out(logw + po + iA, make_uint4(" << wb << "), wt_one_pass);\n";
+      o << "      if (score) store16_out(score + po + iA, make_uint4(" << sb << "), wt_one_pass);\n";
+    } else {
       std::string ws, ss;
       for (int u = 0; u < P; ++u) { ws += (u ? ", w" : "w") + std::string(sfx[u]); ss += (u ? ", sc" : "sc") + std::string(sfx[u]); }
-      if (P == 4 && wt_stores_knob()) {
-        std::string wb, sb;
-        for (int u = 0; u < P; ++u) { wb += (u ? ", f2u(w" : "f2u(w") + std::string(sfx[u]) + ")"; sb += (u ? ", f2u(sc" : "f2u(sc") + std::string(sfx[u]) + ")"; }
-        o << "      if (logw) store16_out(logw + po + iA, make_uint4(" << wb << "), wt_one_pass);\n";
-        o << "      if (score) store16_out(score + po + iA, make_uint4(" << sb << "), wt_one_pass);\n";
-      } else {
       o << "      if (logw) *reinterpret_cast<float" << P << "*>(logw + po + iA) = make_float" << P << "(" << ws << ");\n";
       o << "      if (score) *reinterpret_cast<float" << P << "*>(score + po + iA) = make_float" << P << "(" << ss << ");\n";
-      }
     }
     o << "    }\n";
     o << "    if (max_partials || row_e) {\n";
