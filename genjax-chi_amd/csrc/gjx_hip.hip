@@ -4066,3 +4066,71 @@ int gjx_smc_sharded_run_plan(gjx_comm* c, const gjx_smc_config* cfg, gjx_smc_pla
 }
 
 }  // extern "C"
+
+// =====================================================================================================================
+// Trajectory trace-back over a recorded filter history (include/gjx_paths.h; kernel in gjx_paths.hpp)
+// =====================================================================================================================
+#include "gjx_paths.hpp"
+
+namespace {
+inline uint64_t paths_chunks(uint64_t m) { return (m + kPathsChunk - 1) / kPathsChunk; }
+inline bool paths_size_ok(uint64_t v) { return v >= 1 && v < (1ull << 31); }
+}  // namespace
+
+extern "C" {
+
+int gjx_paths_version(int* major, int* minor) {
+  if (major) *major = GJX_PATHS_VERSION_MAJOR;
+  if (minor) *minor = GJX_PATHS_VERSION_MINOR;
+  return GJX_OK;
+}
+size_t gjx_paths_workspace_bytes(int32_t n_steps, uint64_t m, int32_t n_cols) {
+  if (n_steps < 1 || !paths_size_ok(m) || n_cols < 0 || n_cols > GJX_PATHS_MAX_COLS) return 0;
+  return (size_t)n_steps * (size_t)(2 * n_cols + 1) * (size_t)paths_chunks(m) * sizeof(uint64_t);
+}
+int gjx_paths_trace(const gjx_paths_io* io, void* ws, size_t ws_bytes, gjx_stream s) {
+  if (!io || io->n_steps < 1 || !paths_size_ok(io->n) || !paths_size_ok(io->m) || io->n_cols < 0 || io->n_cols > GJX_PATHS_MAX_COLS)
+    return GJX_ERR_INVALID;
+  const int T = io->n_steps, nc = io->n_cols;
+  if ((T > 1 && (!io->ancestors || io->anc_stride < io->n)) || (!io->leaves && io->m != io->n)) return GJX_ERR_INVALID;
+  // (rows are addressed as t * stride in 64 bits: T < 2^31 rows of a stride below 2^32 elements cannot wrap)
+  if (io->anc_stride >= (1ull << 32) || io->lineage_stride >= (1ull << 32)) return GJX_ERR_INVALID;
+  bool any_out = io->lineage_out || io->unique_out;
+  if (io->lineage_out && io->lineage_stride < io->m) return GJX_ERR_INVALID;
+  PathsArgs A{};
+  for (int c = 0; c < nc; ++c) {
+    if (!io->cols[c] || io->col_stride[c] < io->n || io->col_stride[c] >= (1ull << 32)) return GJX_ERR_INVALID;
+    if (io->paths_out[c] && (io->paths_stride[c] < io->m || io->paths_stride[c] >= (1ull << 32))) return GJX_ERR_INVALID;
+    any_out = any_out || io->paths_out[c];
+    A.cols[c] = reinterpret_cast<const uint32_t*>(io->cols[c]);
+    A.col_stride[c] = io->col_stride[c];
+    A.paths_out[c] = reinterpret_cast<uint32_t*>(io->paths_out[c]);
+    A.paths_stride[c] = io->paths_stride[c];
+    if (io->col_is_f32[c]) A.f32_mask |= 1u << c;
+  }
+  if ((io->sum_out || io->sumsq_out) && nc > 0) any_out = true;
+  if (!any_out) return GJX_ERR_INVALID;
+  if (io->unique_out && !(io->flags & GJX_PATHS_LEAVES_ORDERED)) return GJX_ERR_INVALID;
+  const bool stats = io->unique_out || ((io->sum_out || io->sumsq_out) && nc > 0);
+  if (stats) {
+    if (!io->ticket || ((uintptr_t)ws & 7) != 0) return GJX_ERR_INVALID;
+    if (!ws || ws_bytes < gjx_paths_workspace_bytes(T, io->m, nc)) return GJX_ERR_WORKSPACE;
+  }
+  A.T = T; A.n_cols = nc;
+  A.n = (uint32_t)io->n; A.m = (uint32_t)io->m;
+  A.n_chunks = (uint32_t)paths_chunks(io->m);
+  A.anc = io->ancestors; A.anc_stride = io->anc_stride;
+  A.leaves = io->leaves;
+  A.lin_out = io->lineage_out; A.lin_stride = io->lineage_stride;
+  A.sum_out = nc > 0 ? io->sum_out : nullptr; A.sumsq_out = nc > 0 ? io->sumsq_out : nullptr;
+  A.unique_out = io->unique_out;
+  A.partials = reinterpret_cast<uint64_t*>(ws);
+  A.ticket = io->ticket;
+  unsigned grid = A.n_chunks < kPathsMaxGrid ? A.n_chunks : kPathsMaxGrid;
+  if (io->max_workgroups && grid > io->max_workgroups) grid = io->max_workgroups;
+  if (stats) k_paths_trace<true><<<grid, kBlock, 0, S(s)>>>(A);
+  else k_paths_trace<false><<<grid, kBlock, 0, S(s)>>>(A);
+  return launch_status();
+}
+
+}  // extern "C"

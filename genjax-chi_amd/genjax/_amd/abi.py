@@ -44,6 +44,8 @@ MAP_EXP, MAP_LOG, MAP_DIV, MAP_RDIV, MAP_SQRT, MAP_ABS = range(6)
 MAX_EXPR_OPS, MAX_EXPR_DEPTH = 32, 8
 MAX_PARAMS = 64
 SMC_MAX_STATE, SMC_MAX_OBS = 4, 8
+PATHS_MAX_COLS = SMC_MAX_STATE + 1  # gjx_paths.h: GJX_PATHS_MAX_COLS
+PATHS_LEAVES_ORDERED = 1  # gjx_paths.h: GJX_PATHS_LEAVES_ORDERED
 OP_LOGSUMEXP, OP_CATEGORICAL_INDEX, OP_RESAMPLE, OP_SMC = range(4)
 MAX_SITES = 64
 PLAN_FAST_MATH = 1  # gjx.h: GJX_PLAN_FAST_MATH
@@ -53,6 +55,15 @@ class GjxError(RuntimeError):
     def __init__(self, fn: str, code: int):
         super().__init__(f"{fn} failed: {STATUS.get(code, code)}")
         self.code = code
+
+
+class PathsUnavailable(GjxError):
+    """An entry point of include/gjx_paths.h called on a library that does not export it (GJX_ERR_UNSUPPORTED)."""
+
+    def __init__(self, fn: str, backend: str):
+        RuntimeError.__init__(self, f"{fn}: the library '{backend}' does not implement include/gjx_paths.h "
+                                    "(libgjx_hip.so does; the trace-back kernel has no CPU restatement)")
+        self.code = -2
 
 
 class Keys(C.Structure):
@@ -422,7 +433,43 @@ PROTOTYPES = {
     "gjx_hmm_prepare": (C.c_int, [C.POINTER(Hmm), _P, _P, _P]),
 }
 
+class PathsIO(C.Structure):
+    """gjx_paths_io (include/gjx_paths.h): a trajectory trace-back over a recorded filter history."""
+    _fields_ = [
+        ("n_steps", C.c_int32),
+        ("n_cols", C.c_int32),
+        ("n", C.c_uint64),
+        ("m", C.c_uint64),
+        ("ancestors", C.c_void_p),
+        ("anc_stride", C.c_uint64),
+        ("leaves", C.c_void_p),
+        ("cols", C.c_void_p * PATHS_MAX_COLS),
+        ("col_stride", C.c_uint64 * PATHS_MAX_COLS),
+        ("col_is_f32", C.c_int32 * PATHS_MAX_COLS),
+        ("lineage_out", C.c_void_p),
+        ("lineage_stride", C.c_uint64),
+        ("paths_out", C.c_void_p * PATHS_MAX_COLS),
+        ("paths_stride", C.c_uint64 * PATHS_MAX_COLS),
+        ("sum_out", C.c_void_p),
+        ("sumsq_out", C.c_void_p),
+        ("unique_out", C.c_void_p),
+        ("ticket", C.c_void_p),
+        ("flags", C.c_uint32),
+        ("max_workgroups", C.c_uint32),
+    ]
+
+
+# include/gjx_paths.h: a SECOND header with a version of its own — exported by libgjx_hip.so only and bound if present
+# (GjxLib); PROTOTYPES above stays exactly the symbol set of gjx.h, which the CPU oracle restates.
+PATHS_PROTOTYPES = {
+    "gjx_paths_version": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gjx_paths_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_uint64, C.c_int32]),
+    "gjx_paths_trace": (C.c_int, [C.POINTER(PathsIO), _P, C.c_size_t, _P]),
+}
+PATHS_ABI_VERSION = (0, 1)
+
 _NO_STATUS = {
+    "gjx_paths_workspace_bytes",
     "gjx_backend_name",
     "gjx_workspace_bytes",
     "gjx_frac_bits",
@@ -477,8 +524,25 @@ class GjxLib:
         self.call("gjx_version", C.byref(major), C.byref(minor))
         self.version = (major.value, minor.value)
         self.name = self._gjx_backend_name().decode()
+        # include/gjx_paths.h: bound if the library has it (libgjx_hip.so does, the oracle library does not)
+        self.has_paths = hasattr(self._dll, "gjx_paths_version")
+        if self.has_paths:
+            vfn = self._dll.gjx_paths_version
+            vfn.restype, vfn.argtypes = PATHS_PROTOTYPES["gjx_paths_version"]
+            vfn(C.byref(major), C.byref(minor))
+            if (major.value, minor.value) != PATHS_ABI_VERSION:
+                raise AbiVersionMismatch(
+                    f"{path} implements gjx_paths.h {major.value}.{minor.value}; these bindings are written for "
+                    f"{PATHS_ABI_VERSION[0]}.{PATHS_ABI_VERSION[1]}: rebuild the library from this tree")
+            for name, (res, args) in PATHS_PROTOTYPES.items():
+                fn = getattr(self._dll, name)
+                fn.restype = res
+                fn.argtypes = args
+                setattr(self, "_" + name, fn)
 
     def call(self, name: str, *args):
+        if name in PATHS_PROTOTYPES and not self.has_paths:
+            raise PathsUnavailable(name, self.name)
         rc = getattr(self, "_" + name)(*args)
         if name not in _NO_STATUS and rc != GJX_OK:
             raise GjxError(name, rc)

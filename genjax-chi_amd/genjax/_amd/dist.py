@@ -546,7 +546,8 @@ class ShardedSMC:
                            packing or a count exchange); volume ~ the rank's own block, independent of the
                            number of ranks; costs one device->host read of the ranges per step;
       exchange="allgather" every rank receives the whole population (no host sync; volume grows with ranks).
-    Either way particles, ancestors and log Z are bit-identical to the single-device filter."""
+    Either way particles, ancestors and log Z are bit-identical to the single-device filter.
+    The sharded drivers do not record the per-step state history (`BootstrapSMC(record_history=True)` is one device)."""
 
     def __init__(self, ops: Ops, kind: str, impl: int, seed: int, n_total: int, T: int, rank: int, world: int,
                  record_ancestors: bool = False, exchange: str = "ranges", comm=None, poison: bool = False,

@@ -443,6 +443,59 @@ class Ops:
         self.lib.call("gjx_gather_cols", C.c_void_p(ancestors.data_ptr()), n_out, src, dst, len(cols), self.stream())
         return outs
 
+    # ---- trajectory trace-back over a recorded history (include/gjx_paths.h) ----------------------
+    def paths_trace(self, ancestors: torch.Tensor, cols: list, leaves: torch.Tensor | None = None, *, lineage: bool = True,
+                    paths: bool = True, sums: bool = False, unique: bool = False, leaves_ordered: bool = False,
+                    max_workgroups: int = 0) -> dict:
+        """gjx_paths_trace, ONE launch: `ancestors` int32 [T, n] and every 4-byte column of `cols` [T, n] may be row-strided
+        views (`[:, :n]` of a padded buffer); `leaves` int32[m] or None (identity, m = n).  -> dict(lineage int32[T, m],
+        paths [col dtype [T, m]], sum / sumsq float64[len(cols), T] (rows of int32 columns are 0), unique int64[T]), each
+        None unless asked for.  `unique` needs non-decreasing leaves, declared with `leaves_ordered` (identity leaves are).
+        Raises abi.PathsUnavailable on a library without include/gjx_paths.h (the CPU oracle)."""
+        if not self.lib.has_paths:
+            raise abi.PathsUnavailable("gjx_paths_trace", self.lib.name)
+        if ancestors.dim() != 2 or ancestors.dtype != torch.int32 or ancestors.stride(1) != 1 or ancestors.device.type != self.device_type:
+            raise ValueError("paths_trace: ancestors must be an int32 [T, n] device tensor with contiguous rows")
+        T, n = ancestors.shape
+        if len(cols) > abi.PATHS_MAX_COLS:
+            raise ValueError(f"paths_trace: at most {abi.PATHS_MAX_COLS} columns")
+        m = n if leaves is None else leaves.numel()
+        io = abi.PathsIO()
+        io.n_steps, io.n_cols, io.n, io.m = T, len(cols), n, m
+        io.ancestors, io.anc_stride = ancestors.data_ptr(), ancestors.stride(0) if T > 1 else n
+        if leaves is not None:
+            io.leaves = self._chk(leaves, torch.int32, name="leaves").value
+        out = dict(lineage=None, paths=None, sum=None, sumsq=None, unique=None)
+        if lineage:
+            out["lineage"] = self.empty((T, m), torch.int32)
+            io.lineage_out, io.lineage_stride = out["lineage"].data_ptr(), m
+        if paths:
+            out["paths"] = []
+        for c, col in enumerate(cols):
+            if col.shape != (T, n) or col.element_size() != 4 or col.stride(1) != 1 or col.device.type != self.device_type:
+                raise ValueError("paths_trace: columns must be 4-byte [T, n] device tensors with contiguous rows")
+            io.cols[c], io.col_stride[c] = col.data_ptr(), col.stride(0) if T > 1 else n
+            io.col_is_f32[c] = 1 if col.dtype == torch.float32 else 0
+            if paths:
+                o = self.empty((T, m), col.dtype)
+                out["paths"].append(o)
+                io.paths_out[c], io.paths_stride[c] = o.data_ptr(), m
+        ws, nb = None, 0
+        if (sums and cols) or unique:
+            if sums and cols:
+                out["sum"], out["sumsq"] = self.empty((len(cols), T), torch.float64), self.empty((len(cols), T), torch.float64)
+                io.sum_out, io.sumsq_out = out["sum"].data_ptr(), out["sumsq"].data_ptr()
+            if unique:
+                out["unique"] = self.empty(T, torch.int64)
+                io.unique_out = out["unique"].data_ptr()
+            nb = int(self.lib.call("gjx_paths_workspace_bytes", T, m, len(cols)))
+            ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=self._alloc_device)  # (per call: see workspace())
+            io.ticket = self.tickets().data_ptr()  # word 0 of the stream's zeroed ticket words: left zero by every launch
+        io.flags = abi.PATHS_LEAVES_ORDERED if (leaves_ordered or leaves is None) else 0
+        io.max_workgroups = int(max_workgroups)
+        self.lib.call("gjx_paths_trace", C.byref(io), self._p(ws), nb, self.stream())
+        return out
+
     # ---- fused SMC --------------------------------------------------------------------------------
     def _smc_cfg(self, impl, n_total, first, n_local, step_keys, resample_keys, ess_threshold: float = 0.0):
         """`step_keys` / `resample_keys`: [T, 2] for one filter, [F, T, 2] for F filters stepping in the same
