@@ -29,6 +29,7 @@ import torch
 
 from . import abi, prng, workloads as W
 from .ops import Ops
+from .smc_models import HmmFilter, LgssmFilter, PlanFilter
 
 
 def _dist():
@@ -559,7 +560,7 @@ class ShardedSMC:
             raise ValueError(f"n_total must be a multiple of world*{tile}")
         if kind not in ("lgssm", "hmm", "plan") or exchange not in ("ranges", "allgather"):
             raise ValueError("kind: lgssm | hmm | plan; exchange: ranges | allgather")
-        self.ops, self.kind, self.impl, self.T, self.rank, self.world = ops, kind, impl, T, rank, world
+        self.ops, self.impl, self.T, self.rank, self.world = ops, impl, T, rank, world
         self.exchange, self.poison = exchange, poison
         self.comm = comm if comm is not None else TorchComm(rank, world)
         self.n_total, self.n_local = n_total, n_total // world
@@ -569,37 +570,28 @@ class ShardedSMC:
         # from the all-gathered exact ESS sums, and a step that keeps its particles exchanges nothing
         self.cfg = ops.smc_config(impl, n_total, self.first, self.n_local, sk, rk, ess_threshold)
         dev = ops.device()
-        if kind == "lgssm":
-            self.y = W.lgssm_data(T) if y is None else y
-            self.model = W.lgssm_model() if lgssm is None else lgssm
-            self.log_z_exact = W.lgssm_exact_log_z(self.y) if lgssm is None else float("nan")
-            sdt = torch.float32
+        if kind == "lgssm":  # (the one place that tells the kinds apart: everything below drives the bound model)
+            y = W.lgssm_data(T) if y is None else y
+            self.model = LgssmFilter(ops, W.lgssm_model() if lgssm is None else lgssm, y)
+            self.log_z_exact = W.lgssm_exact_log_z(y) if lgssm is None else float("nan")
         elif kind == "plan":
-            import numpy as np
-
-            self.plan = plan
-            self.y = np.asarray(obs, dtype=np.float32).reshape(T, -1)
-            self.log_z_exact = float("nan")
-            sdt = torch.float32
+            self.model, self.log_z_exact = PlanFilter(ops, plan, obs), float("nan")
         else:
-            trans, obs = W.hmm_tables(n_states)
-            self.k = trans.shape[0]
-            self.init = W.HMM["init_state"] % self.k
-            self.y = W.hmm_data(T, n_states)
-            self.log_z_exact = W.hmm_exact_log_z(self.y, n_states)
-            self.model = ops.hmm_model(self.k, self.init, torch.from_numpy(trans).to(dev).contiguous(),
-                                       torch.from_numpy(obs).to(dev).contiguous())
-            self.trans_alias, self.obs_logp = ops.hmm_prepare_model(self.model)
-            sdt = torch.int32
+            trans, obs_l = W.hmm_tables(n_states)
+            k = trans.shape[0]
+            y = W.hmm_data(T, n_states)
+            self.log_z_exact = W.hmm_exact_log_z(y, n_states)
+            self.model = HmmFilter(ops, k, W.HMM["init_state"] % k, torch.from_numpy(trans).to(dev).contiguous(),
+                                   torch.from_numpy(obs_l).to(dev).contiguous(), y)
         # global-size buffers: a rank's own block is always current, remote ranges are filled on demand
-        self.n_cols = plan.n_state if kind == "plan" else 1
+        sdts = self.model.state_dtypes
         self.adaptive = bool(self.cfg._adaptive)
         # `arena` (PeerArena): the peer transport — the populations live in the rank's arena, at the same offsets on every rank
         self.arena = arena
         if arena is not None:
-            self.pop = arena.pops(ops, n_total, [sdt] * self.n_cols, self.adaptive)
+            self.pop = arena.pops(ops, n_total, sdts, self.adaptive)
         else:
-            self.pop = [ops.smc_pop(n_total, [sdt] * self.n_cols, self.adaptive) for _ in range(2)]
+            self.pop = [ops.smc_pop(n_total, sdts, self.adaptive) for _ in range(2)]
         for p_ in self.pop:
             for c in [*p_.state, p_.qw, p_.logw]:
                 c.zero_()
@@ -621,12 +613,7 @@ class ShardedSMC:
         out = self.pop[cur].struct(self.first, with_logw=keep_logw)
         prev = self.pop[prv].struct() if t else None
         pe, pq = (self.out_e[t - 1:t], self.out_q[t - 1:t]) if t else (None, None)
-        if self.kind == "plan":
-            self.ops.smc_plan_step(self.cfg, self.plan, t, self.y[t], prev, out, pe, pq, anc)
-        elif self.kind == "lgssm":
-            self.ops.smc_lgssm_step(self.cfg, self.model, t, float(self.y[t]), prev, out, pe, pq, anc)
-        else:
-            self.ops.smc_hmm_step(self.cfg, self.model, t, int(self.y[t]), prev, out, self.trans_alias, self.obs_logp, pe, pq, anc)
+        self.model.step(self.cfg, t, prev, out, pe, pq, anc)
 
     def _shuffle(self, cur: int):
         """Make the source ranges of the next resampling present on every rank."""
@@ -679,7 +666,7 @@ class ShardedSMC:
         lo, hi = self.first, self.first + self.n_local
         last = self.pop[(self.T - 1) & 1]
         final = [c[lo:hi] for c in last.state]
-        return dict(out_e=self.out_e, out_q=self.out_q, state=final[0] if self.n_cols == 1 else final,
+        return dict(out_e=self.out_e, out_q=self.out_q, state=final[0] if len(final) == 1 else final,
                     logw=last.logw[lo:hi], ancestors=self.ancestors,
                     log_z=ops.log_z_from_pairs(self.out_e, self.out_q, self.n_total, self.cfg._flags),
                     resampled=self.cfg._flags, log_z_exact=self.log_z_exact, received=self.received)
@@ -688,10 +675,6 @@ class ShardedSMC:
         """The same filter driven from C (`gjx_smc_sharded_run_*`): the per-step launch, the all-gather of the records
         and the ancestor shuffle without the interpreter in between.  Same results as `run()` bit for bit."""
         import ctypes as C
-
-        import numpy as np
-
-        from . import abi
 
         ops = self.ops
         if self.poison and self.arena is None:  # tests: whatever a rank never receives must never be read
@@ -710,18 +693,7 @@ class ShardedSMC:
         recv = C.c_uint64(0)
         io.received = C.pointer(recv)
         try:
-            if self.kind == "lgssm":
-                y = np.ascontiguousarray(np.asarray(self.y, dtype=np.float32))
-                ops.lib.call("gjx_smc_sharded_run_lgssm", comm.handle, C.byref(self.cfg), C.byref(self.model),
-                             C.c_void_p(y.ctypes.data), C.byref(io), ops.stream())
-            elif self.kind == "hmm":
-                y = np.ascontiguousarray(np.asarray(self.y, dtype=np.int32))
-                ops.lib.call("gjx_smc_sharded_run_hmm", comm.handle, C.byref(self.cfg), C.byref(self.model),
-                             C.c_void_p(y.ctypes.data), ops._p(self.trans_alias), ops._p(self.obs_logp), C.byref(io), ops.stream())
-            else:
-                y = np.ascontiguousarray(np.asarray(self.y, dtype=np.float32))
-                ops.lib.call("gjx_smc_sharded_run_plan", comm.handle, C.byref(self.cfg), self.plan.handle,
-                             C.c_void_p(y.ctypes.data) if y.size else None, C.byref(io), ops.stream())
+            self.model.sharded_run(comm, self.cfg, io)
         finally:
             self.received = int(recv.value)
         if self.arena is not None:

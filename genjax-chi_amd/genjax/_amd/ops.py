@@ -16,6 +16,7 @@ import torch
 
 from . import abi
 from .abi import GjxLib, Keys, F32
+from .smc_models import HmmFilter, LgssmFilter, PlanFilter
 
 
 @dataclass(frozen=True)
@@ -497,10 +498,11 @@ class Ops:
         return out
 
     # ---- fused SMC --------------------------------------------------------------------------------
-    def _smc_cfg(self, impl, n_total, first, n_local, step_keys, resample_keys, ess_threshold: float = 0.0):
-        """`step_keys` / `resample_keys`: [T, 2] for one filter, [F, T, 2] for F filters stepping in the same
-        launches (gjx_smc_config.n_filters).  `ess_threshold` in (0, 1): ESS-adaptive resampling — the config then
-        carries a device int32[T] / [F, T] `cfg._flags` (1 where a step began with a resampling)."""
+    def smc_config(self, impl, n_total, first, n_local, step_keys, resample_keys, ess_threshold: float = 0.0):
+        """Config of a whole-run call or of the step-level entry points (`first`, `n_local`: a rank's own block).
+        `step_keys` / `resample_keys`: [T, 2] for one filter, [F, T, 2] for F filters stepping in the same launches
+        (gjx_smc_config.n_filters; whole-run calls only).  `ess_threshold` in (0, 1): ESS-adaptive resampling — the config
+        then carries a device int32[T] / [F, T] `cfg._flags` (1 where a step began with a resampling)."""
         import numpy as np
 
         sk = np.ascontiguousarray(np.asarray(step_keys, dtype=np.uint32))
@@ -522,52 +524,45 @@ class Ops:
             cfg.resampled_out = cfg._flags.data_ptr()
         return cfg
 
-    def _smc_buffers(self, cfg, n, state_dtype, want_ancestors):
-        """Outputs of a whole-run call: one filter -> [T], [n]; F filters -> [F, T], [F, stride] (views [:, :n])."""
+    def _smc_buffers(self, cfg, n, model, want_ancestors):
+        """Outputs and scratch of a whole-run call as `model.run` takes them: one filter -> [T], [n], ancestors [T, n]; F
+        filters -> [F, T], [F, stride] (views [:, :n]), [T, F, stride].  (Keep the ORDER of the allocations: the replayed
+        run graph is keyed on the addresses, which the caching allocator hands back to the next run in this order.)"""
         F, T = cfg._filters, cfg.n_steps
-        if F == 1:
-            return (self.empty(T, torch.int32), self.empty(T, torch.int64), self.empty(n, state_dtype),
-                    self.empty(n, torch.float32), self.empty((T, n), torch.int32) if want_ancestors else None,
-                    self.workspace(abi.OP_SMC, n))
-        stride = cfg.filter_stride
-        ws_one = int(self.lib.call("gjx_workspace_bytes", abi.OP_SMC, n))
-        ws = torch.empty(F * ws_one, dtype=torch.uint8, device=self._alloc_device)  # (per call: see workspace())
-        return (self.empty((F, T), torch.int32), self.empty((F, T), torch.int64), self.empty((F, stride), state_dtype),
-                self.empty((F, stride), torch.float32),
-                self.empty((T, F, stride), torch.int32) if want_ancestors else None, (ws, F * ws_one))
+        lead, row = ((), n) if F == 1 else ((F,), cfg.filter_stride)
+        out_e, out_q = self.empty((*lead, T), torch.int32), self.empty((*lead, T), torch.int64)
+        states = [self.empty((*lead, row), dt) for dt in model.state_dtypes]
+        logw = self.empty((*lead, row), torch.float32)
+        anc = self.empty((T, *lead, row), torch.int32) if want_ancestors else None
+        if F > 1 and model.workspace_per_filter:
+            nb = F * int(self.lib.call("gjx_workspace_bytes", abi.OP_SMC, n))
+            ws = torch.empty(nb, dtype=torch.uint8, device=self._alloc_device)  # (per call: see workspace())
+        else:
+            ws, nb = self.workspace(abi.OP_SMC, F * row)
+        return out_e, out_q, states, logw, anc, ws, nb
+
+    def _smc_run(self, model, impl, n, step_keys, resample_keys, want_ancestors=False, ess_threshold: float = 0.0,
+                 want_flags: bool = True, columns: bool = True):
+        """The whole-run call of a bound filter model (smc_models.py) -> (out_e, out_q, state columns, logw, ancestors,
+        resampled flags or None).  `columns` False: the one state column itself."""
+        cfg = self.smc_config(impl, n, 0, n, step_keys, resample_keys, ess_threshold)
+        assert model.T == cfg.n_steps
+        outputs = self._smc_buffers(cfg, n, model, want_ancestors)
+        model.run(cfg, outputs)
+        out_e, out_q, states, logw, anc = outputs[:5]
+        out = (out_e, out_q, states if columns else states[0], logw, anc)
+        return (*out, cfg._flags) if want_flags else out
 
     def smc_run_lgssm(self, impl, n, step_keys, resample_keys, model: abi.Lgssm, y, want_ancestors=False,
                       ess_threshold: float = 0.0, want_flags: bool = False):
         """-> (out_e, out_q, state, logw, ancestors[, resampled flags or None])."""
-        import numpy as np
-
-        cfg = self._smc_cfg(impl, n, 0, n, step_keys, resample_keys, ess_threshold)
-        yh = np.ascontiguousarray(np.asarray(y, dtype=np.float32))
-        assert yh.size == cfg.n_steps
-        out_e, out_q, state, logw, anc, (ws, nb) = self._smc_buffers(cfg, n, torch.float32, want_ancestors)
-        self.lib.call("gjx_smc_run_lgssm", C.byref(cfg), C.byref(model), C.c_void_p(yh.ctypes.data),
-                      C.c_void_p(out_e.data_ptr()), C.c_void_p(out_q.data_ptr()), C.c_void_p(state.data_ptr()),
-                      C.c_void_p(logw.data_ptr()), C.c_void_p(anc.data_ptr()) if anc is not None else None,
-                      C.c_void_p(ws.data_ptr()), nb, self.stream())
-        return (out_e, out_q, state, logw, anc, cfg._flags) if want_flags else (out_e, out_q, state, logw, anc)
+        return self._smc_run(LgssmFilter(self, model, y), impl, n, step_keys, resample_keys, want_ancestors, ess_threshold,
+                             want_flags, columns=False)
 
     def smc_run_hmm(self, impl, n, step_keys, resample_keys, n_states, init_state, trans_logits, obs_logits, y,
                     want_ancestors=False, ess_threshold: float = 0.0, want_flags: bool = False):
-        import numpy as np
-
-        cfg = self._smc_cfg(impl, n, 0, n, step_keys, resample_keys, ess_threshold)
-        yh = np.ascontiguousarray(np.asarray(y, dtype=np.int32))
-        assert yh.size == cfg.n_steps
-        mdl = abi.Hmm()
-        mdl.n_states, mdl.init_state = n_states, init_state
-        mdl.trans_logits = self._chk(trans_logits, torch.float32, n_states * n_states).value
-        mdl.obs_logits = self._chk(obs_logits, torch.float32, n_states * n_states).value
-        out_e, out_q, state, logw, anc, (ws, nb) = self._smc_buffers(cfg, n, torch.int32, want_ancestors)
-        self.lib.call("gjx_smc_run_hmm", C.byref(cfg), C.byref(mdl), C.c_void_p(yh.ctypes.data),
-                      C.c_void_p(out_e.data_ptr()), C.c_void_p(out_q.data_ptr()), C.c_void_p(state.data_ptr()),
-                      C.c_void_p(logw.data_ptr()), C.c_void_p(anc.data_ptr()) if anc is not None else None,
-                      C.c_void_p(ws.data_ptr()), nb, self.stream())
-        return (out_e, out_q, state, logw, anc, cfg._flags) if want_flags else (out_e, out_q, state, logw, anc)
+        return self._smc_run(HmmFilter(self, n_states, init_state, trans_logits, obs_logits, y), impl, n, step_keys,
+                             resample_keys, want_ancestors, ess_threshold, want_flags, columns=False)
 
     def hmm_model(self, n_states: int, init_state: int, trans_logits: torch.Tensor, obs_logits: torch.Tensor) -> abi.Hmm:
         mdl = abi.Hmm()
@@ -684,29 +679,10 @@ class Ops:
         """`step_keys` / `resample_keys` [T, 2]: one filter -> (e [T], q [T], state columns [n], logw [n], ancestors
         [T, n]); [F, T, 2]: F filters (same observations, own keys) stepping in the same launches -> ([F, T], [F, T],
         columns [F, stride], [F, stride], [T, F, stride]), filter f equal to its own single run bit for bit."""
-        import numpy as np
-
-        cfg = self._smc_cfg(impl, n, 0, n, step_keys, resample_keys, ess_threshold)
-        T, F = cfg.n_steps, cfg._filters
-        oh = np.ascontiguousarray(np.asarray(obs, dtype=np.float32).reshape(T, max(plan.n_obs, 1))[:, :plan.n_obs])
-        stride = cfg.filter_stride if F > 1 else n
-        shape = (lambda *tail: (F, *tail)) if F > 1 else (lambda *tail: tail)
-        out_e, out_q = self.empty(shape(T), torch.int32), self.empty(shape(T), torch.int64)
-        states = [self.empty(shape(stride), torch.float32) for _ in range(plan.n_state)]
-        sp = (C.c_void_p * plan.n_state)(*[t.data_ptr() for t in states])
-        logw = self.empty(shape(stride), torch.float32)
-        anc = self.empty((T, F, stride) if F > 1 else (T, n), torch.int32) if want_ancestors else None
-        ws, nb = self.workspace(abi.OP_SMC, F * stride)
-        self.lib.call("gjx_smc_run_plan", C.byref(cfg), plan.handle, C.c_void_p(oh.ctypes.data) if plan.n_obs else None,
-                      self._p(out_e), self._p(out_q), sp, self._p(logw), self._p(anc), C.c_void_p(ws.data_ptr()), nb,
-                      self.stream())
-        return (out_e, out_q, states, logw, anc, cfg._flags) if want_flags else (out_e, out_q, states, logw, anc)
+        return self._smc_run(PlanFilter(self, plan, obs), impl, n, step_keys, resample_keys, want_ancestors,
+                             ess_threshold, want_flags)
 
     # ---- step-level SMC pieces (multi-device driver: dist.py) -----------------------------------
-    def smc_config(self, impl, n_total, first, n_local, step_keys, resample_keys, ess_threshold: float = 0.0):
-        """Step-level config (one filter)."""
-        return self._smc_cfg(impl, n_total, first, n_local, step_keys, resample_keys, ess_threshold)
-
     @staticmethod
     def _p(t):
         return None if t is None else C.c_void_p(t.data_ptr())

@@ -1,10 +1,13 @@
-"""Bootstrap SMC on the fused state-space kernels (`gjx_smc_run_lgssm` / `gjx_smc_run_hmm`).
+"""Bootstrap SMC on the fused state-space kernels (`gjx_smc_run_*` / `gjx_smc_*_step`: the hand-written
+linear-Gaussian model and discrete HMM, and the generated plan of a user-written `StateSpaceModel`).
 
 The reference's SMC module has no resampling step or SMC loop; the north star
 asks for bootstrap SMC with systematic resampling and an ancestor gather.  This is that driver:
 one call enqueues the whole T-step filter — per step one fused resample+gather+propagate+weight
-kernel and one tile-sum kernel — with no host synchronisation.  The model classes are the
-fixed-structure equivalents of the `@scan`/`@gen` kernels
+kernel and one tile-sum kernel — with no host synchronisation.  `_bind_model` turns a model class into
+the bound filter model (smc_models.py) that the whole-run call and the stepwise history filter run; it is
+the only place here that tells the kinds apart.  The model classes are the fixed-structure equivalents of
+the `@scan`/`@gen` kernels
 
     x' = normal(a * x, q) @ "x";  normal(x', r) @ "y"                  (LinearGaussianSSM)
     z' = categorical(T[z, :]) @ "z";  categorical(O[z', :]) @ "x"      (DiscreteHMM, exact_testbed.py:62-68)
@@ -20,7 +23,9 @@ import torch
 from . import abi, prng
 from .choicemap import ChoiceMap
 from .runtime import get_ops, use_ops
+from .smc_models import HmmFilter, LgssmFilter, PlanFilter
 from .smc_plan import StateSpaceModel, build_smc_plan, observation_matrix
+from .workloads import smc_key_schedule
 
 
 @dataclass(frozen=True)
@@ -80,7 +85,7 @@ class SMCResult:
             raise ValueError("n_paths needs a key: without one there is exactly one path per final particle")
         out = ops.paths_trace(self.ancestors, cols, leaves, sums=True, unique=True, leaves_ordered=True)
         paths = out["paths"]
-        return Trajectories(paths[0] if n_state == 1 else tuple(paths[:n_state]), out["lineage"], out["unique"],
+        return Trajectories(_columns(paths[:n_state]), out["lineage"], out["unique"],
                             None if key is not None else self.log_weights,
                             paths[n_state] if with_log_weights else None, out["sum"][:n_state], out["sumsq"][:n_state],
                             [c.dtype == torch.float32 for c in cols[:n_state]])
@@ -120,42 +125,53 @@ class Trajectories:
         return self._pick(self._moments()[1])
 
 
-def run_with_history(ops, model, observations, n: int, key: prng.PRNGKey, ess_threshold: float = 0.0, plan=None) -> SMCResult:
+def _columns(cols):
+    """State columns as results carry them: the tensor itself for one column, a tuple for a multi-component carry."""
+    return cols[0] if len(cols) == 1 else tuple(cols)
+
+
+def _build_plan(ops, model: StateSpaceModel, observations: ChoiceMap):
+    """-> (SmcPlan, observation matrix [T, n_obs]) of a user-written model and its observed sequences."""
+    addrs = [a for a, _ in observations.leaves()]
+    with use_ops(ops):
+        plan, _ = build_smc_plan(model, addrs)
+    return plan, observation_matrix(observations, addrs)
+
+
+def _bind_model(ops, model, observations, plan=None):
+    """The model bound to `ops` (smc_models.py) that every driver below runs; the uploads of a fixed model happen here,
+    per call.  `observations`: as for BootstrapSMC.  `plan`: what `_build_plan` returned for a StateSpaceModel earlier."""
+    if isinstance(model, LinearGaussianSSM):
+        return LgssmFilter(ops, abi.Lgssm(model.x0_loc, model.x0_scale, model.a, model.q, model.r), observations)
+    if isinstance(model, DiscreteHMM):
+        dev = ops.device()
+        tl = torch.as_tensor(model.trans_logits, dtype=torch.float32).to(dev).contiguous()
+        ol = torch.as_tensor(model.obs_logits, dtype=torch.float32).to(dev).contiguous()
+        return HmmFilter(ops, int(tl.shape[0]), int(model.init_state), tl, ol, observations)
+    if isinstance(model, StateSpaceModel):
+        plan, obs = plan or _build_plan(ops, model, observations)
+        return PlanFilter(ops, plan, obs)
+    raise TypeError(f"no fused SMC kernel for {type(model).__name__}")
+
+
+def run_with_history(ops, model, observations, n: int, key: prng.PRNGKey, ess_threshold: float = 0.0) -> SMCResult:
     """The bootstrap filter of `BootstrapSMC.run`, driven STEP BY STEP through `ops` so that every step's population stays:
     step t writes its state columns and log-weights into row t of `[T, stride]` buffers and step t + 1 reads them there — the
     history costs no copy and no kernel of its own.  The per-step scratch (fixed-point weights, tile records) ping-pongs
     between two populations.  Rows have a stride of whole tiles (16-byte aligned rows whatever n is: the steps' 16-byte
     stores stay 16-byte stores and inside their row).  Every field the whole-run call also returns is bit-equal to it.
-    `observations`: as for BootstrapSMC.  `plan`: (SmcPlan, n_state, observation matrix) of a StateSpaceModel built earlier.
-    One filter on one device: filter batches (`run_many`) and the sharded drivers do not record history."""
-    n = int(n)
-    dev = ops.device()
-    hmm_tables = None
-    if isinstance(model, LinearGaussianSSM):
-        y = np.asarray(observations).astype(np.float32)
-        mdl, sdt, n_state = abi.Lgssm(model.x0_loc, model.x0_scale, model.a, model.q, model.r), torch.float32, 1
-    elif isinstance(model, DiscreteHMM):
-        y = np.asarray(observations).astype(np.int32)
-        tl = torch.as_tensor(model.trans_logits, dtype=torch.float32).to(dev).contiguous()
-        ol = torch.as_tensor(model.obs_logits, dtype=torch.float32).to(dev).contiguous()
-        mdl, sdt, n_state = ops.hmm_model(int(tl.shape[0]), int(model.init_state), tl, ol), torch.int32, 1
-        hmm_tables = ops.hmm_prepare_model(mdl)
-    elif isinstance(model, StateSpaceModel):
-        if plan is None:
-            addrs = [a for a, _ in observations.leaves()]
-            with use_ops(ops):
-                pl, n_state = build_smc_plan(model, addrs)
-            plan = (pl, n_state, observation_matrix(observations, addrs))
-        mdl, n_state, y = plan
-        sdt = torch.float32
-    else:
-        raise TypeError(f"no fused SMC kernel for {type(model).__name__}")
-    T = len(y)
+    `observations`: as for BootstrapSMC.  One filter on one device: filter batches (`run_many`) and the sharded drivers do not record history."""
+    return _history_run(ops, _bind_model(ops, model, observations), n, key, ess_threshold)
+
+
+def _history_run(ops, model, n: int, key: prng.PRNGKey, ess_threshold: float) -> SMCResult:
+    """`run_with_history` of a bound model."""
+    n, T = int(n), model.T
     sk, rk = smc_key_schedule(key, T)
     cfg = ops.smc_config(key.impl, n, 0, n, sk, rk, ess_threshold)
     stride = ops.num_tiles(n) * ops.tile
     # each buffer once, uninitialised: 4 T stride bytes per column
-    hist = [ops.empty((T, stride), sdt) for _ in range(n_state)]
+    hist = [ops.empty((T, stride), dt) for dt in model.state_dtypes]
     lw = ops.empty((T, stride), torch.float32)
     anc = ops.empty((T, stride), torch.int32)
     out_e, out_q = ops.empty(T, torch.int32), ops.empty(T, torch.int64)
@@ -163,35 +179,29 @@ def run_with_history(ops, model, observations, n: int, key: prng.PRNGKey, ess_th
     structs = []
     for t in range(T):  # the population of step t: scratch of parity t, state / log-weights in row t
         p = pops[t & 1].struct()
-        for k in range(n_state):
-            p.state[k] = hist[k][t].data_ptr()
+        for k, h in enumerate(hist):
+            p.state[k] = h[t].data_ptr()
         p.logw = lw[t].data_ptr()
         structs.append(p)
     # (views made once, outside the loop of launches: the loop is host-bound)
     anc_rows, e_rows, q_rows = anc.unbind(0), out_e.split(1), out_q.split(1)
-    for t in range(T):
-        prev = structs[t - 1] if t else None
-        pe, pq = (e_rows[t - 1], q_rows[t - 1]) if t else (None, None)
-        if isinstance(model, LinearGaussianSSM):
-            ops.smc_lgssm_step(cfg, mdl, t, float(y[t]), prev, structs[t], pe, pq, anc_rows[t])
-        elif isinstance(model, DiscreteHMM):
-            ops.smc_hmm_step(cfg, mdl, t, int(y[t]), prev, structs[t], hmm_tables[0], hmm_tables[1], pe, pq, anc_rows[t])
-        else:
-            ops.smc_plan_step(cfg, mdl, t, y[t], prev, structs[t], pe, pq, anc_rows[t])
+    model.step(cfg, 0, None, structs[0], None, None, anc_rows[0])
+    for t in range(1, T):
+        model.step(cfg, t, structs[t - 1], structs[t], e_rows[t - 1], q_rows[t - 1], anc_rows[t])
     ops.smc_finish(cfg, pops[(T - 1) & 1].recs, e_rows[T - 1], q_rows[T - 1])
     cols = [h[:, :n] for h in hist]
-    history = cols[0] if n_state == 1 else tuple(cols)
-    last = cols[0][T - 1] if n_state == 1 else tuple(c[T - 1] for c in cols)
     flags = cfg._flags
-    return SMCResult(ops.log_z_from_pairs(out_e, out_q, n, flags), out_e, out_q, last, lw[T - 1, :n], anc[:, :n], flags,
-                     history, lw[:, :n])
+    return SMCResult(ops.log_z_from_pairs(out_e, out_q, n, flags), out_e, out_q, _columns([c[T - 1] for c in cols]),
+                     lw[T - 1, :n], anc[:, :n], flags, _columns(cols), lw[:, :n])
 
 
-def smc_key_schedule(key: prng.PRNGKey, T: int):
-    """step t propagates with fold_in(key, 2t) and resamples with fold_in(key, 2t+1) (fresh lane-0 keys;
-    for threefry the same words as split(key, 2T)[2t], [2t+1])."""
-    w = prng.fold_words(key, 2 * T)
-    return w[0::2].copy(), w[1::2].copy()
+def _result(ops, n: int, out, f: int | None = None) -> SMCResult:
+    """One filter's result from what the whole-run call returned (Ops._smc_run); `f`: filter f of an `[F, stride]` batch."""
+    step_e, step_q, states, logw, anc, flags = out
+    if f is not None:
+        step_e, step_q, states, logw = step_e[f], step_q[f], [c[f, :n] for c in states], logw[f, :n]
+        anc, flags = None if anc is None else anc[:, f, :n], None if flags is None else flags[f]
+    return SMCResult(ops.log_z_from_pairs(step_e, step_q, n, flags), step_e, step_q, _columns(states), logw, anc, flags)
 
 
 class BootstrapSMC:
@@ -209,80 +219,45 @@ class BootstrapSMC:
         self.model, self.n, self.record_ancestors = model, int(n_particles), record_ancestors
         self.record_history = bool(record_history)
         self.ess_threshold = float(ess_threshold)
-        self._plan = None
-        if isinstance(model, StateSpaceModel):
-            if not isinstance(observations, ChoiceMap):
-                raise TypeError("observations for a StateSpaceModel are a ChoiceMap of length-T sequences")
-            self._obs_chm = observations
-            self.observations = None
-        else:
-            self.observations = np.asarray(observations)
+        self._plan = None  # (SmcPlan, observation matrix) of a StateSpaceModel, built at the first run
+        if isinstance(model, StateSpaceModel) and not isinstance(observations, ChoiceMap):
+            raise TypeError("observations for a StateSpaceModel are a ChoiceMap of length-T sequences")
+        self.observations = observations if isinstance(observations, ChoiceMap) else np.asarray(observations)
 
     def get_num_particles(self):
         return self.n
 
+    def _bind(self, ops):
+        """The filter model bound to `ops`: per call for a fixed model (its tensors may change between runs); the plan and
+        the observation matrix of a StateSpaceModel are built once and kept."""
+        if isinstance(self.model, StateSpaceModel) and self._plan is None:
+            self._plan = _build_plan(ops, self.model, self.observations)
+        return _bind_model(ops, self.model, self.observations, self._plan)
+
     def run(self, key: prng.PRNGKey) -> SMCResult:
         ops = get_ops()
+        model = self._bind(ops)
         if self.record_history:
-            if isinstance(self.model, StateSpaceModel):
-                if self._plan is None:
-                    self._obs_addrs = [a for a, _ in self._obs_chm.leaves()]
-                    self._plan, self._n_state = build_smc_plan(self.model, self._obs_addrs)
-                    self._obs = observation_matrix(self._obs_chm, self._obs_addrs)
-                return run_with_history(ops, self.model, None, self.n, key, self.ess_threshold,
-                                        plan=(self._plan, self._n_state, self._obs))
-            return run_with_history(ops, self.model, self.observations, self.n, key, self.ess_threshold)
-        if self.observations is not None:
-            T = len(self.observations)
-            sk, rk = smc_key_schedule(key, T)
-        if isinstance(self.model, LinearGaussianSSM):
-            m = self.model
-            out = ops.smc_run_lgssm(key.impl, self.n, sk, rk, abi.Lgssm(m.x0_loc, m.x0_scale, m.a, m.q, m.r),
-                                    self.observations.astype(np.float32), self.record_ancestors,
-                                    ess_threshold=self.ess_threshold, want_flags=True)
-        elif isinstance(self.model, DiscreteHMM):
-            m = self.model
-            dev = ops.device()
-            tl = torch.as_tensor(m.trans_logits, dtype=torch.float32).to(dev).contiguous()
-            ol = torch.as_tensor(m.obs_logits, dtype=torch.float32).to(dev).contiguous()
-            out = ops.smc_run_hmm(key.impl, self.n, sk, rk, int(tl.shape[0]), int(m.init_state), tl, ol,
-                                  self.observations.astype(np.int32), self.record_ancestors,
-                                  ess_threshold=self.ess_threshold, want_flags=True)
-        elif isinstance(self.model, StateSpaceModel):
-            if self._plan is None:
-                self._obs_addrs = [a for a, _ in self._obs_chm.leaves()]
-                self._plan, self._n_state = build_smc_plan(self.model, self._obs_addrs)
-                self._obs = observation_matrix(self._obs_chm, self._obs_addrs)
-            T = self._obs.shape[0]
-            sk, rk = smc_key_schedule(key, T)
-            om, oq, states, logw, anc, fl = ops.smc_run_plan(self._plan, key.impl, self.n, sk, rk, self._obs,
-                                                             self.record_ancestors, ess_threshold=self.ess_threshold,
-                                                             want_flags=True)
-            out = (om, oq, states[0] if self._n_state == 1 else tuple(states), logw, anc, fl)
-        else:
-            raise TypeError(f"no fused SMC kernel for {type(self.model).__name__}")
-        step_e, step_q, state, logw, anc, flags = out
-        return SMCResult(ops.log_z_from_pairs(step_e, step_q, self.n, flags), step_e, step_q, state, logw, anc, flags)
+            return _history_run(ops, model, self.n, key, self.ess_threshold)
+        sk, rk = smc_key_schedule(key, model.T)
+        return _result(ops, self.n, ops._smc_run(model, key.impl, self.n, sk, rk, self.record_ancestors, self.ess_threshold))
 
     def run_many(self, keys) -> list:
         """`vmap(self.run)(keys)`: one independent filter per key.  Up to 16 filters step in the same kernel launches
         (`gjx_smc_config.n_filters`: a 1e6-particle step alone is under one round of an MI355X), for the hand-written
         models and for generated ones alike; element b equals `self.run(keys[b])` bit for bit."""
         keys = list(keys)
-        if self.record_history or not isinstance(self.model, (LinearGaussianSSM, DiscreteHMM, StateSpaceModel)) or len(keys) < 2:
+        if self.record_history or len(keys) < 2:
             return [self.run(k) for k in keys]
         ops, out = get_ops(), []
-        if isinstance(self.model, StateSpaceModel) and self._plan is None:
-            self.run(keys[0])  # builds the plan and the observation matrix
-        T = len(self.observations) if self.observations is not None else self._obs.shape[0]
-        ess = dict(ess_threshold=self.ess_threshold, want_flags=True)
+        model = self._bind(ops)
         for lo in range(0, len(keys), 16):
             chunk = keys[lo:lo + 16]
             if len(chunk) == 1:
                 out.append(self.run(chunk[0]))
                 continue
             try:
-                out.extend(self._run_chunk(ops, chunk, T, ess))
+                out.extend(self._run_chunk(ops, chunk, model.T, model))
             except abi.GjxError as e:
                 # populations too large for a filter batch (more than 2048 tiles per filter, or a workspace the
                 # device cannot hold): the documented contract is "element b equals self.run(keys[b])" — run them so
@@ -291,36 +266,11 @@ class BootstrapSMC:
                 out.extend(self.run(k) for k in chunk)
         return out
 
-    def _run_chunk(self, ops, chunk, T, ess) -> list:
-        out = []
+    def _run_chunk(self, ops, chunk, T, model) -> list:
         pairs = [smc_key_schedule(k, T) for k in chunk]
         sk, rk = np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
-        m, impl = self.model, chunk[0].impl
-        if isinstance(m, StateSpaceModel):
-            om, oq, states, logw, anc, fl = ops.smc_run_plan(self._plan, impl, self.n, sk, rk, self._obs,
-                                                             self.record_ancestors, **ess)
-            for f in range(len(chunk)):
-                cols = [c[f, :self.n] for c in states]
-                ff = None if fl is None else fl[f]
-                out.append(SMCResult(ops.log_z_from_pairs(om[f], oq[f], self.n, ff), om[f], oq[f],
-                                     cols[0] if self._n_state == 1 else tuple(cols), logw[f, :self.n],
-                                     None if anc is None else anc[:, f, :self.n], ff))
-            return out
-        if isinstance(m, LinearGaussianSSM):
-            res = ops.smc_run_lgssm(impl, self.n, sk, rk, abi.Lgssm(m.x0_loc, m.x0_scale, m.a, m.q, m.r),
-                                    self.observations.astype(np.float32), self.record_ancestors, **ess)
-        else:
-            dev = ops.device()
-            tl = torch.as_tensor(m.trans_logits, dtype=torch.float32).to(dev).contiguous()
-            ol = torch.as_tensor(m.obs_logits, dtype=torch.float32).to(dev).contiguous()
-            res = ops.smc_run_hmm(impl, self.n, sk, rk, int(tl.shape[0]), int(m.init_state), tl, ol,
-                                  self.observations.astype(np.int32), self.record_ancestors, **ess)
-        step_e, step_q, state, logw, anc, fl = res
-        for f in range(len(chunk)):
-            ff = None if fl is None else fl[f]
-            out.append(SMCResult(ops.log_z_from_pairs(step_e[f], step_q[f], self.n, ff), step_e[f], step_q[f],
-                                 state[f, :self.n], logw[f, :self.n], None if anc is None else anc[:, f, :self.n], ff))
-        return out
+        out = ops._smc_run(model, chunk[0].impl, self.n, sk, rk, self.record_ancestors, self.ess_threshold)
+        return [_result(ops, self.n, out, f) for f in range(len(chunk))]
 
     def log_marginal_likelihood_estimate(self, key: prng.PRNGKey) -> float:
         return self.run(key).log_marginal_likelihood

@@ -112,3 +112,24 @@ def test_smoothing_means_match_the_rts_smoother(oracle_ops):
     # bit-reproducible: the figures recorded when this check was specified
     assert np.allclose(z, [-1.22, 0.85, 0.72, 0.48, 0.77, -0.95, -1.94, -0.00], atol=0.006)
     assert uniq0 == 27787
+
+
+def test_run_many_builds_the_plan_without_running_a_filter(oracle_ops):
+    """`run_many` on a fresh StateSpaceModel filter: the plan comes from its builder, not from a filter that is run and
+    thrown away — three keys are ONE `gjx_smc_run_plan` call (one batch), and element b still equals `run(keys[b])`."""
+    model, obs = P.model_and_obs("ssm2")
+    keys = [genjax.random.key(s) for s in (3, 8, 9)]
+    calls, call = [], oracle_ops.lib.call
+    oracle_ops.lib.call = lambda name, *a: (calls.append(name), call(name, *a))[1]
+    try:
+        with use_ops(oracle_ops):
+            alg = BootstrapSMC(model, obs, 2000, record_ancestors=True)
+            many = alg.run_many(keys)
+    finally:
+        del oracle_ops.lib.call
+    assert calls.count("gjx_smc_run_plan") == 1 and calls.count("gjx_smc_plan_create") == 1
+    with use_ops(oracle_ops):
+        for k, m in zip(keys, many):
+            one = alg.run(k)
+            assert torch.equal(m.step_q, one.step_q) and torch.equal(m.ancestors, one.ancestors) and _eq(m.particles, one.particles)
+            assert m.log_marginal_likelihood == one.log_marginal_likelihood
