@@ -1592,6 +1592,35 @@ GJX_DEV void store16_out(void* p, uint4 v, bool wt) {
 #endif
   *reinterpret_cast<uint4*>(p) = v;
 }
+// The same store with the address in two parts: a WAVE-UNIFORM base (scalar registers) and the lane's byte offset (one
+// 32-bit register shared by every column a lane stores).  store16_out takes a per-lane 64-bit address: twelve columns kept
+// twelve address pairs alive across the importance kernel's row loop (24 VGPRs).  Here the plain store is
+// `global_store_dwordx4 voff, data, s[base]` and the write-through one takes the base itself into its descriptor.
+GJX_DEV void store16_at(void* ubase, uint32_t lane_bytes, uint4 v, bool wt) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (wt) {
+    typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
+    v4u_t x;
+    x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+    __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(ubase, 0, 0x7fffffff, 0x00020000);
+    __builtin_amdgcn_raw_buffer_store_b128(x, rs, (int)lane_bytes, 0, 16 /* sc1 */);
+    return;
+  }
+#endif
+  *reinterpret_cast<uint4*>(reinterpret_cast<char*>(ubase) + lane_bytes) = v;
+}
+// Ends the compiler's freedom to postpone an accumulator's update: the two running sums are needed HERE, as one register
+// pair.  Without it the generated importance kernels compute every site's log-density where the totals are stored, at the
+// end of the row, and keep all sampled values alive until then (40 VGPRs in the 10-latent quad kernel).  No instruction;
+// the pair keeps the packed-f32 forms of the adds and of the log-densities that feed them.
+typedef float pin2_t __attribute__((ext_vector_type(2)));
+GJX_DEV pin2_t pinned2(float a, float b) {  // (by value: through references the packed forms are lost)
+  pin2_t t = {a, b};
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(t));
+#endif
+  return t;
+}
 
 // ---- emission: the fixed-point weights and the record of the tile a workgroup has just produced -------------------
 // w[r], ok[r]: the log-weights of the thread's four consecutive slots (tile offset 4 tid + r) and whether the slot

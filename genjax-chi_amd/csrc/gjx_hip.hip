@@ -2047,6 +2047,8 @@ struct gjx_plan {
   // specialised kernels, built on first use: [0] THREEFRY, [1] PHILOX one particle per lane, [2] PHILOX pairs
   // (two adjacent particles per lane), [3] PHILOX quads (four per lane: one wave per 256-particle row)
   gjx_jit::Compiled jit[4];
+  gjx_jit::Compiled jit_tail[4];  // the same forms WITH the fused fold (gjx_jit::Gen::fused_tail): built on the first launch
+                                  // that passes a gjx_lse_out, so the default launches do not carry the fold's registers
   std::vector<void*> dev_owned;  // per-row tables of categorical sites (specialised kernels)
   std::mutex jit_mu;
   ExprStore expr;      // GJX_ARG_EXPR programs (host; read by the code generator)
@@ -2297,13 +2299,27 @@ static int jit_form_pref() {  // GJX_JIT_FORM = one | pair | quad (test / tuning
   if (e && !strcmp(e, "pair")) return 2;
   return 4;  // quad; measured (tools/ab_importance.py, 1e6 particles): quad 13.1 / pair 13.6 / one 28.3 us per pass at 8 passes per launch
 }
+// The waves-per-SIMD hint of a form (P particles per lane).  The kernels are bound by dependency latency, not by issue
+// slots (a wave64 VALU instruction issues in ~2.4 cycles, tools/microbench/valu_rate.hip), so resident waves are what
+// pays, and a SIMD's 512 VGPRs are shared in granules of 8: <= 128 registers is 4 waves, <= 96 5, <= 80 6, <= 72 7, <= 64 8
+// (allocated registers: the code object's .vgpr_count; a rocprofv3 trace's VGPR column is half of it).
+//  * pairs: hint 6 (<= 80 VGPRs); the 10-latent kernel takes 49 under it.
+//  * quads: none.  The 10-latent kernel allocates 68 VGPRs unhinted, no scratch: 7 waves.  Hint 7 gives 70 registers and
+//    28 more instructions, hint 8 64 registers, 8 B of scratch and 105 more instructions (profiles/occupancy_summary.md;
+//    tools/ab_waves_hint.py measures them against each other through GJX_JIT_DEFINE=GJX_WAVES_HINT=<k>).
+// A hinted build that spills more than 32 B is replaced by the unhinted one (plan_compiled).
+static int jit_waves_hint(int P) { return P == 2 ? 6 : 0; }
 int gjx_plan_specialized_source(const gjx_plan* p, int impl, char* buf, size_t buf_len, size_t* needed) {
+  const bool fused_tail = (impl & GJX_SOURCE_FUSED_TAIL) != 0;
+  impl &= ~GJX_SOURCE_FUSED_TAIL;
   if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
   gjx_jit::Gen<CSite, CArg> g;
   g.impl = impl; g.sites = p->host; g.n_sites = p->n_sites; g.laned = impl == 1 && jit_form_pref() >= 2;
   g.sc = p->scopes.n_scopes > 0 ? &p->scopes : nullptr;
   g.pairs_per_lane = jit_form_pref() == 4 ? 2 : 1;  // (GJX_JIT_FORM picks the PHILOX form shown)
   g.fast_math = (p->flags & GJX_PLAN_FAST_MATH) != 0;
+  g.fused_tail = fused_tail;
+  g.min_waves = g.laned ? jit_waves_hint(2 * g.pairs_per_lane) : 0;  // the kernel that ships
   gjx_jit::TableScope ts;
   const std::string src = g.run();
   if (needed) *needed = src.size() + 1;
@@ -2316,12 +2332,16 @@ int gjx_plan_specialized_source(const gjx_plan* p, int impl, char* buf, size_t b
 }
 
 int gjx_plan_compile_check(const gjx_plan* p, int impl) {
+  const bool fused_tail = (impl & GJX_SOURCE_FUSED_TAIL) != 0;
+  impl &= ~GJX_SOURCE_FUSED_TAIL;
   if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
   for (int form = 0; form <= 2 * impl; ++form) {  // PHILOX: one particle per lane, pairs, quads
     gjx_jit::Gen<CSite, CArg> g;
     g.impl = impl; g.sites = p->host; g.n_sites = p->n_sites; g.laned = form != 0; g.pairs_per_lane = form == 2 ? 2 : 1;
     g.sc = p->scopes.n_scopes > 0 ? &p->scopes : nullptr;
     g.fast_math = (p->flags & GJX_PLAN_FAST_MATH) != 0;
+    g.fused_tail = fused_tail;
+    g.min_waves = jit_waves_hint(2 * form);
     gjx_jit::TableScope ts;
     if (!gjx_jit::compile_only(g.run())) return GJX_ERR_UNSUPPORTED;
   }
@@ -2331,6 +2351,7 @@ int gjx_plan_destroy(gjx_plan* p) {
   if (!p) return GJX_OK;
   if (p->dev) (void)hipFree(p->dev);
   for (auto& c : p->jit) gjx_jit::release(&c);  // the modules stay cached (bounded, LRU) for plans of the same structure
+  for (auto& c : p->jit_tail) gjx_jit::release(&c);
   free_owned(p->dev_owned);
   delete p;
   return GJX_OK;
@@ -2338,14 +2359,15 @@ int gjx_plan_destroy(gjx_plan* p) {
 
 // The hiprtc-specialised kernel of a plan for this key form (compiled and loaded on first use).
 // `lane_particles`: how many adjacent particles a lane may own given n and the alignment of the output buffers (1, 2, 4).
-static gjx_jit::Compiled& plan_compiled(gjx_plan* mp, const gjx_keys* pk, int lane_particles) {
+// `fused_tail`: the variant that folds the row sums inside the launch (launches that pass a gjx_lse_out).
+static gjx_jit::Compiled& plan_compiled(gjx_plan* mp, const gjx_keys* pk, int lane_particles, bool fused_tail = false) {
   // PHILOX children of a lane-0 key share one cipher key, and an even first index keeps particle pairs
   // (2i, 2i+1) together: the paired / quad kernel forms (gjx_plan_jit.hpp)
   const bool pairable = pk->impl == 1 && pk->mode == 1 && pk->parent_lane == 0 && (pk->first & 1) == 0;
   int P = pairable ? (lane_particles < jit_form_pref() ? lane_particles : jit_form_pref()) : 1;
   if (P == 3) P = 2;
   const bool laned = P >= 2;
-  gjx_jit::Compiled& c = mp->jit[P == 4 ? 3 : (laned ? 2 : pk->impl)];
+  gjx_jit::Compiled& c = (fused_tail ? mp->jit_tail : mp->jit)[P == 4 ? 3 : (laned ? 2 : pk->impl)];
   if (c.state == 0) {
     std::lock_guard<std::mutex> lock(mp->jit_mu);
     if (c.state == 0) {
@@ -2356,6 +2378,7 @@ static gjx_jit::Compiled& plan_compiled(gjx_plan* mp, const gjx_keys* pk, int la
         g.sc = mp->scopes.n_scopes > 0 ? &mp->scopes : nullptr;
         g.fast_math = (mp->flags & GJX_PLAN_FAST_MATH) != 0;
         g.min_waves = min_waves;
+        g.fused_tail = fused_tail;
         gjx_jit::TableScope ts;  // the source numbers the plan's device tables; the addresses travel as a kernel argument
         std::string src = g.run();
         c.block = g.block;
@@ -2363,11 +2386,15 @@ static gjx_jit::Compiled& plan_compiled(gjx_plan* mp, const gjx_keys* pk, int la
         c.tabs = ts.reg.tables();
         return src;
       };
-      // The kernels are bound by dependency latency, not by issue slots (a wave64 VALU instruction issues in ~2.4
-      // cycles, tools/microbench/valu_rate.hip): a sixth wave per SIMD (<= 80 VGPRs) is worth 2-3 % on the paired
-      // form as long as the allocator gets there with (next to) no spilling; otherwise the unconstrained build is kept.
-      const int hint = P == 2 ? 6 : 0;
+      // (jit_waves_hint has the register counts and the waves per SIMD that follow from them.)  The hint is kept as long
+      // as the allocator gets there with (next to) no spilling; otherwise the unconstrained build is used.
+      const int hint = laned ? jit_waves_hint(P) : 0;
       bool ok = gjx_jit::compile(make(hint), pk->impl, &c);
+      if (ok && std::getenv("GJX_PLAN_JIT_VERBOSE")) {  // what the loaded code object allocates (the VGPR column of a rocprofv3 kernel trace is HALF of this)
+        int regs = 0;
+        if (hipFuncGetAttribute(&regs, HIP_FUNC_ATTRIBUTE_NUM_REGS, c.fn) != hipSuccess) (void)hipGetLastError();
+        fprintf(stderr, "gjx jit: %d particle(s) per lane%s: %d registers per lane\n", P, fused_tail ? ", fused tail" : "", regs);
+      }
       if (ok && hint > 0) {
         int scratch = 0;
         const hipError_t qe = hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, c.fn);
@@ -2456,7 +2483,7 @@ static int importance_launch(const gjx_plan* p, const gjx_keys* pk, int32_t n_pa
     uintptr_t al = (uintptr_t)logw | (uintptr_t)score | (uintptr_t)(4 * pass_stride) | (uintptr_t)(4 * n);
     for (int c = 0; c < n_value_cols; ++c) al |= (uintptr_t)value_cols[c];
     const int lane_particles = (al & 15) == 0 ? 4 : ((al & 7) == 0 ? 2 : 1);
-    gjx_jit::Compiled& c = plan_compiled(const_cast<gjx_plan*>(p), pk, lane_particles);
+    gjx_jit::Compiled& c = plan_compiled(const_cast<gjx_plan*>(p), pk, lane_particles, lse != nullptr);
     if (c.state != 1 && (!jit_fallback_allowed() || p->has_expr || p->scopes.n_scopes > 0)) return GJX_ERR_JIT;  // loud: never a silent 7x slower route
     if (c.state == 1) {
       uint64_t nn = n;
@@ -3206,6 +3233,7 @@ struct gjx_scan_plan {
   CSite step[GJX_MAX_SITES];
   CArg next_state[GJX_SMC_MAX_STATE];
   gjx_jit::Compiled jit[3];  // THREEFRY, PHILOX one particle per lane, PHILOX four per lane (GenScan::quad)
+  gjx_jit::Compiled jit_tail[3];  // the same with the fused fold (GenScan::fused_tail): launches that pass a gjx_lse_out
   gjx_jit::ScopeInfo scopes;  // nested calls inside the step kernel (gjx_scan_plan_create_scoped)
   std::vector<void*> dev_owned;  // per-row tables of categorical sites
   std::mutex mu;
@@ -3249,17 +3277,19 @@ int gjx_scan_plan_create_scoped(const gjx_scan_model* m, const gjx_scope* scopes
 int gjx_scan_plan_destroy(gjx_scan_plan* p) {
   if (!p) return GJX_OK;
   for (auto& c : p->jit) gjx_jit::release(&c);
+  for (auto& c : p->jit_tail) gjx_jit::release(&c);
   free_owned(p->dev_owned);
   delete p;
   return GJX_OK;
 }
 static std::string scan_plan_source(const gjx_scan_plan* plan, int impl, const char** kname = nullptr, PlanTables* tabs = nullptr,
-                                    bool quad = false, int* block = nullptr) {
+                                    bool quad = false, int* block = nullptr, bool fused_tail = false) {
   gjx_jit::TableScope ts;
   gjx_jit::GenScan<CSite, CArg> g;
   g.impl = impl; g.sites = plan->step; g.n_sites = plan->n_step; g.next_state = plan->next_state;
   g.n_state = plan->n_state; g.n_obs = plan->n_obs; g.fast_math = (plan->flags & GJX_PLAN_FAST_MATH) != 0;
   g.quad = quad;
+  g.fused_tail = fused_tail;
   g.sc = plan->scopes.n_scopes > 0 ? &plan->scopes : nullptr;
   if (kname) *kname = g.kname();
   std::string src = g.run();
@@ -3268,10 +3298,12 @@ static std::string scan_plan_source(const gjx_scan_plan* plan, int impl, const c
   return src;
 }
 int gjx_scan_plan_compile_check(const gjx_scan_plan* p, int impl) {
+  const bool ft = (impl & GJX_SOURCE_FUSED_TAIL) != 0;  // (the variant with the in-launch fold, as gjx_plan_compile_check)
+  impl &= ~GJX_SOURCE_FUSED_TAIL;
   if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
-  if (std::getenv("GJX_PLAN_JIT_DUMP")) fprintf(stderr, "%s\n", scan_plan_source(p, impl).c_str());
-  if (impl == 1 && !gjx_jit::compile_only(scan_plan_source(p, impl, nullptr, nullptr, true))) return GJX_ERR_UNSUPPORTED;
-  return gjx_jit::compile_only(scan_plan_source(p, impl)) ? GJX_OK : GJX_ERR_UNSUPPORTED;
+  if (std::getenv("GJX_PLAN_JIT_DUMP")) fprintf(stderr, "%s\n", scan_plan_source(p, impl, nullptr, nullptr, false, nullptr, ft).c_str());
+  if (impl == 1 && !gjx_jit::compile_only(scan_plan_source(p, impl, nullptr, nullptr, true, nullptr, ft))) return GJX_ERR_UNSUPPORTED;
+  return gjx_jit::compile_only(scan_plan_source(p, impl, nullptr, nullptr, false, nullptr, ft)) ? GJX_OK : GJX_ERR_UNSUPPORTED;
 }
 int gjx_scan_run(gjx_scan_plan* p, const gjx_scan_io* io, gjx_stream s) {
   if (!p || !io || !keys_ok(io->particle_keys) || io->particle_keys->has_fold || !io->logw || io->n_steps < 1 ||
@@ -3304,14 +3336,15 @@ int gjx_scan_run(gjx_scan_plan* p, const gjx_scan_io* io, gjx_stream s) {
     for (int d = 0; d < p->n_state; ++d) al |= io->carry_out ? (uintptr_t)io->carry_out[d] : 0;
     quad = impl == 1 && pk->mode == 1 && pk->parent_lane == 0 && (pk->first & 1) == 0 && (al & 15) == 0;
   }
-  gjx_jit::Compiled& c = p->jit[quad ? 2 : impl];
+  const bool fused_tail = io->lse != nullptr;  // the in-launch fold: a variant of its own, built when first asked for
+  gjx_jit::Compiled& c = (fused_tail ? p->jit_tail : p->jit)[quad ? 2 : impl];
   if (c.state == 0) {
     std::lock_guard<std::mutex> lock(p->mu);
     if (c.state == 0) {
       cat_tables_prepare(p->step, p->n_step, &p->dev_owned);
       const char* kname = nullptr;
       int block = 256;
-      const std::string src = scan_plan_source(p, impl, &kname, &c.tabs, quad, &block);
+      const std::string src = scan_plan_source(p, impl, &kname, &c.tabs, quad, &block, fused_tail);
       c.block = block;
       if (std::getenv("GJX_PLAN_JIT_DUMP")) fprintf(stderr, "%s\n", src.c_str());
       c.state = gjx_jit::compile(src, impl, &c, kname) ? 1 : -1;

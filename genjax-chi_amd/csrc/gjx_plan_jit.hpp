@@ -338,6 +338,7 @@ struct SiteEmitter {
   // Part 2 of site q: the sampled value (Normal sites take their standard normal from `eps`: an expression
   // or, empty, this particle's own derivation), the log-density, the accumulators and the stored column.
   bool presampled = false;  // tail(): a Gamma / Beta site's value vf<q> has been defined by the caller
+  bool defer_acc = false;   // tail(): only the sampled value; the caller accumulates lp_of(q)
   void tail(int q, const std::string& eps = "") {
     const CSiteT& st = sites[q];
     const std::string I = std::to_string(impl), Q = std::to_string(q) + sfx, K = key_of(q);
@@ -384,6 +385,22 @@ struct SiteEmitter {
           }
       }
     }
+    if (defer_acc) return;  // (the caller adds lp_of(q) to the accumulators itself: emit_pair_lane_sites)
+    const std::string lp = lp_of(q);
+    const std::string v = (isint ? "vi" : "vf") + Q;
+    const std::string aw = acc("w", scope_of(q)), as = acc("sc", scope_of(q));
+    o << ind << "{ const float lp = " << lp << "; " << as << " = " << as << " + lp;"
+      << (st.observed ? " " + aw + " = " + aw + " + lp;" : "") << " }\n";
+    if ((mode == 0 || mode == 2) && st.out_col >= 0 && store_values)
+      o << ind << "reinterpret_cast<uint32_t*>(cols.out[" << st.out_col << "])[" << (mode == 2 ? "oi" : "i") << sfx << "] = "
+        << (isint ? "(uint32_t)" + v : "f2u(" + v + ")") << ";\n";
+  }
+  // the log-density of site q at its value, as an expression over the names head() and tail() have defined
+  std::string lp_of(int q) const {
+    const CSiteT& st = sites[q];
+    const std::string Q = std::to_string(q) + sfx;
+    const std::string row = "row" + Q;
+    const bool isint = is_int(st);
     std::string lp;
     const std::string v = (isint ? "vi" : "vf") + Q;
     // hoisted per-site constants: literals (pre == 1) or derived from the launch's parameters (pre == 2)
@@ -425,12 +442,7 @@ struct SiteEmitter {
     const bool all_const = st.observed && st.obs.kind == GJX_ARG_CONST && is_const(st.a0) &&
                            (st.dist == GJX_DIST_BERNOULLI || st.dist == GJX_DIST_CATEGORICAL || is_const(st.a1));
     if (all_const) lp = "opq(" + lp + ")";
-    const std::string aw = acc("w", scope_of(q)), as = acc("sc", scope_of(q));
-    o << ind << "{ const float lp = " << lp << "; " << as << " = " << as << " + lp;"
-      << (st.observed ? " " + aw + " = " + aw + " + lp;" : "") << " }\n";
-    if ((mode == 0 || mode == 2) && st.out_col >= 0 && store_values)
-      o << ind << "reinterpret_cast<uint32_t*>(cols.out[" << st.out_col << "])[" << (mode == 2 ? "oi" : "i") << sfx << "] = "
-        << (isint ? "(uint32_t)" + v : "f2u(" + v + ")") << ";\n";
+    return lp;
   }
 
   // a callee's weight and score are ITS totals, added to the caller's when the call returns (static.py:374-380: the
@@ -480,12 +492,18 @@ inline void emit_prelude(std::ostringstream& o, bool fast_math = false, bool bm_
 // `wt_one_pass`.
 template <class CSiteT, class CArgT>
 inline void emit_pair_lane_sites(std::ostringstream& o, std::vector<SiteEmitter<CSiteT, CArgT>>& em, const CSiteT* sites, int n_sites,
-                                 int NP, const std::string& ind, const std::string& store_at) {
+                                 int NP, const std::string& ind, const std::string& store_at, const std::string& sc_guard = "",
+                                 const std::string& ubase = "", const std::string& lane_bytes = "") {
   const char* sfx[4] = {"A", "B", "C", "D"};
   const int P = 2 * NP;
 int cur_pair_blk = -1;
   for (int q = 0; q < n_sites; ++q) {
     const CSiteT& st = sites[q];
+    // `sc_guard` (the importance kernels: the name of the score pointer): the lane's weights and scores are brought up to
+    // date AT the site, pair by pair (gjx_device.hpp pinned2), the scores only where the launch stores them — so w and sc
+    // are the only values that live from one site to the next.  (A callee's sites keep the plain per-particle form.)
+    const bool pinned = !sc_guard.empty() && em[0].scope_of(q) == 0;
+    for (int u = 0; u < P; ++u) em[u].defer_acc = pinned;
     for (int u = 0; u < P; ++u) em[u].head(q);
     const std::string Q = std::to_string(q);
     if (!st.observed && em[0].one_word(st) && em[0].scope_of(q) == 0) {  // (a callee's sites: every particle's own lone key)
@@ -549,13 +567,40 @@ int cur_pair_blk = -1;
     } else {
       for (int u = 0; u < P; ++u) em[u].tail(q);
     }
+    if (pinned) {
+      auto pins = [&](const char* base) {
+        std::string t;
+        for (int pi = 0; pi < NP; ++pi) {
+          const std::string a = std::string(base) + sfx[2 * pi], b = std::string(base) + sfx[2 * pi + 1];
+          t += " { const pin2_t t = pinned2(" + a + ", " + b + "); " + a + " = t[0]; " + b + " = t[1]; }";
+        }
+        return t;
+      };
+      if (st.observed) {  // the log-density enters the weight (always needed) and the score
+        for (int u = 0; u < P; ++u) o << ind << "const float lp" << Q << sfx[u] << " = " << em[u].lp_of(q) << ";\n";
+        o << ind;
+        for (int u = 0; u < P; ++u) o << "w" << sfx[u] << " = w" << sfx[u] << " + lp" << Q << sfx[u] << "; ";
+        o << pins("w") << "\n";
+        o << ind << "if (" << sc_guard << ") { ";
+        for (int u = 0; u < P; ++u) o << "sc" << sfx[u] << " = sc" << sfx[u] << " + lp" << Q << sfx[u] << "; ";
+        o << pins("sc") << " }\n";
+      } else {  // a latent site's log-density is part of the score alone
+        o << ind << "if (" << sc_guard << ") {\n";
+        for (int u = 0; u < P; ++u)
+          o << ind << "  { const float lp = " << em[u].lp_of(q) << "; sc" << sfx[u] << " = sc" << sfx[u] << " + lp; }\n";
+        o << ind << " " << pins("sc") << "\n" << ind << "}\n";
+      }
+      for (int u = 0; u < P; ++u) em[u].defer_acc = false;
+    }
     for (int u = 0; u < P; ++u) em[u].close_scopes(q + 1);
     if (st.out_col >= 0) {  // the lane's particles are adjacent in the column: one 8- / 16-byte store per lane
       const bool isint = SiteEmitter<CSiteT, CArgT>::is_int(st);
       std::string vals;
       for (int u = 0; u < P; ++u)
         vals += (u ? ", " : "") + (isint ? "(uint32_t)vi" + Q + sfx[u] : "f2u(vf" + Q + sfx[u] + ")");
-      if (P == 4)
+      if (P == 4 && !ubase.empty())  // (wave-uniform base + the lane's byte offset: gjx_device.hpp store16_at)
+        o << ind << "store16_at(reinterpret_cast<uint32_t*>(cols.out[" << st.out_col << "]) + " << ubase << ", " << lane_bytes << ", make_uint4(" << vals << "), wt_one_pass);\n";
+      else if (P == 4)
         o << ind << "store16_out(reinterpret_cast<uint32_t*>(cols.out[" << st.out_col << "]) + " << store_at << ", make_uint4(" << vals << "), wt_one_pass);\n";
       else
         o << ind << "*reinterpret_cast<uint" << P << "*>(reinterpret_cast<uint32_t*>(cols.out[" << st.out_col << "]) + " << store_at << ") = make_uint" << P
@@ -577,6 +622,9 @@ struct Gen {
   const CSiteT* sites;
   int n_sites;
   int min_waves = 0;  // __launch_bounds__ waves-per-SIMD hint (0 = none)
+  bool fused_tail = false;  // the kernel folds the row sums itself (gjx_device.hpp lse_tail; launches that pass a gjx_lse_out).
+                            // A variant of its own: inlined into every kernel, the fold cost 22 VGPRs — one wave per SIMD —
+                            // on launches that never enter it (132 -> 110 in the 10-latent quad kernel)
   int block = 256;    // threads per workgroup of the generated kernel
   int rows_per_block = 1;
   bool laned = false; // the paired form (see above)
@@ -598,6 +646,17 @@ struct Gen {
       if (!sites[q].observed && sites[q].dist == GJX_DIST_NORMAL) return true;
     return false;
   }
+  // the waves-per-SIMD hint is a macro with the plan's choice as its default (0 = none), so that
+  // GJX_JIT_DEFINE=GJX_WAVES_HINT=<k> builds the same kernel under another hint for an A/B (tools/ab_waves_hint.py)
+  std::string bounds(int threads) const { return "__launch_bounds__(" + std::to_string(threads) + ", GJX_WAVES_HINT)"; }
+  void emit_hint_default() { o << "#ifndef GJX_WAVES_HINT\n#define GJX_WAVES_HINT " << (min_waves > 0 ? min_waves : 0) << "\n#endif\n"; }
+  // the row sums of a kernel without the fused fold are read by a later launch: plain stores
+  const char* tail_scope() const { return fused_tail ? "tail.tickets != nullptr" : "false"; }
+  void emit_tail() {
+    o << "  }\n";
+    if (fused_tail) o << "  if (row_e) lse_tail(row_e, row_s, (n + 255) / 256, tail);\n";
+    o << "}\n";
+  }
 
   std::string run_paired() {
     // NP pairs of adjacent particles per lane; a 256-particle row is 128 / NP lanes.  R rows per workgroup.
@@ -612,15 +671,19 @@ struct Gen {
     block = lanes_per_row * R;
     rows_per_block = R;
     const int waves_per_row = lanes_per_row / 64;  // 2 (pairs) or 1 (quads)
+    // the quad form's stores: one wave-uniform base per column and row (scalar registers) plus ONE per-lane byte offset
+    // (gjx_device.hpp store16_at); the four-row workgroup of the estimate-only kernel has no block-uniform row
+    const bool ubase = NP == 2 && R == 1;
     emit_prelude(o, fast_math, bm_lds());
-    o << "extern \"C\" __global__ __launch_bounds__(" << block << (min_waves > 0 ? ", " + std::to_string(min_waves) : std::string())
-      << ") void " << kname() << signature();
+    emit_hint_default();
+    o << "extern \"C\" __global__ " << bounds(block) << " void " << kname() << signature();
     if (waves_per_row > 1) o << "  __shared__ float sh_red[" << waves_per_row * R << "];\n  __shared__ uint64_t sh_sum[" << waves_per_row * R << "];\n";
     if (R == 1) o << "  const int wv = threadIdx.x >> 6, pr = 0, tr = threadIdx.x;  // (block-uniform row: the cipher key stays scalar)\n";
     else o << "  const int wv = threadIdx.x >> 6, pr = threadIdx.x / " << lanes_per_row << ", tr = threadIdx.x % " << lanes_per_row << ";\n";
     o << "  (void)wv;\n";
     // the kernel's scalar arguments in ONE round of loads (gjx_device.hpp: resample_args_anchor has the measurement)
-    o << "  asm volatile(\"\" :: \"s\"(n), \"s\"(score), \"s\"(logw), \"s\"(max_partials), \"s\"(row_e), \"s\"(row_s), \"s\"(bt.n_pass), \"s\"(bt.rows_per_pass), \"s\"(bt.pass_stride), \"s\"(bt.row_stride), \"s\"(ks.first), \"s\"(ks.parent.k0), \"s\"(ks.parent.k1), \"s\"(tail.tickets));\n";
+    o << "  asm volatile(\"\" :: \"s\"(n), \"s\"(score), \"s\"(logw), \"s\"(max_partials), \"s\"(row_e), \"s\"(row_s), \"s\"(bt.n_pass), \"s\"(bt.rows_per_pass), \"s\"(bt.pass_stride), \"s\"(bt.row_stride), \"s\"(ks.first), \"s\"(ks.parent.k0), \"s\"(ks.parent.k1)"
+      << (fused_tail ? ", \"s\"(tail.tickets)" : "") << ");\n";
     {
       bool seen[64] = {};  // ... and the value columns this plan stores (RunCols::out has 64)
       for (int q = 0; q < n_sites; ++q)
@@ -646,6 +709,9 @@ struct Gen {
     for (int u = 1; u < P; ++u) o << "    const uint64_t i" << sfx[u] << " = iA + " << u << ";\n";
     // n is a multiple of P in this form (checked by the host): all particles of a lane exist or none
     o << "    const bool ok = live_row && iA < n;\n";
+    // (the lane's offset is made opaque per row: folded into the columns' bases it would be hoisted out of the row loop
+    // as one 64-bit address pair per column)
+    if (ubase) o << "    const uint64_t ub = po + row * 256;\n    uint32_t lb = 16u * (uint32_t)tr;\n    asm volatile(\"\" : \"+v\"(lb));\n";
     for (int u = 0; u < P; ++u) o << "    const uint64_t li" << sfx[u] << " = i" << sfx[u] << "; (void)li" << sfx[u] << ";\n";
     for (int u = 0; u < P; ++u) o << "    float w" << sfx[u] << " = 0.0f, sc" << sfx[u] << " = 0.0f;\n";
     o << "    if (ok) {\n";
@@ -664,8 +730,13 @@ struct Gen {
     for (int u = 0; u < P; ++u) em[u].emit_scope_keys();
     o << "      const uint64_t pair0 = (lnA - 1u) >> 1;\n";
     if (NP == 2) o << "      const uint64_t pair1 = pair0 + 1u;\n";
-    emit_pair_lane_sites<CSiteT, CArgT>(o, em, sites, n_sites, NP, "      ", "po + iA");
-    if (P == 4) {
+    emit_pair_lane_sites<CSiteT, CArgT>(o, em, sites, n_sites, NP, "      ", "po + iA", "score", ubase ? "ub" : "", "lb");
+    if (ubase) {
+      std::string wb, sb;
+      for (int u = 0; u < P; ++u) { wb += (u ? ", f2u(w" : "f2u(w") + std::string(sfx[u]) + ")"; sb += (u ? ", f2u(sc" : "f2u(sc") + std::string(sfx[u]) + ")"; }
+      o << "      if (logw) store16_at(logw + ub, lb, make_uint4(" << wb << "), wt_one_pass);\n";
+      o << "      if (score) store16_at(score + ub, lb, make_uint4(" << sb << "), wt_one_pass);\n";
+    } else if (P == 4) {
       std::string wb, sb;
       for (int u = 0; u < P; ++u) { wb += (u ? ", f2u(w" : "f2u(w") + std::string(sfx[u]) + ")"; sb += (u ? ", f2u(sc" : "f2u(sc") + std::string(sfx[u]) + ")"; }
       o << "      if (logw) store16_out(logw + po + iA, make_uint4(" << wb << "), wt_one_pass);\n";
@@ -700,9 +771,9 @@ struct Gen {
       o << "        __syncthreads();\n        if ((threadIdx.x & 63) == 0) sh_sum[wv] = sb;\n        __syncthreads();\n";
       o << "        sb = sh_sum[2 * pr] + sh_sum[2 * pr + 1];\n";
     }
-    o << "        if (tr == 0 && live_row) lse_store_row(row_e, row_s, ro + row, eb, sb, tail.tickets != nullptr);\n";
+    o << "        if (tr == 0 && live_row) lse_store_row(row_e, row_s, ro + row, eb, sb, " << tail_scope() << ");\n";
     o << "      }\n    }\n";
-    o << "  }\n  if (row_e) lse_tail(row_e, row_s, (n + 255) / 256, tail);\n}\n";
+    emit_tail();
     return o.str();
   }
 
@@ -710,10 +781,10 @@ struct Gen {
     if (laned && impl == 1) return run_paired();
     const std::string I = std::to_string(impl);
     emit_prelude(o, fast_math, bm_lds());
+    emit_hint_default();
     // One workgroup per 256-particle row (grid-stride): short blocks keep every SIMD's wave slots
     // full even at 1e6 particles (15 rows per lane), where a 4-row block would serialise its rows.
-    o << "extern \"C\" __global__ __launch_bounds__(256" << (min_waves > 0 ? ", " + std::to_string(min_waves) : std::string())
-      << ") void " << kname() << signature();
+    o << "extern \"C\" __global__ " << bounds(256) << " void " << kname() << signature();
     o << "  __shared__ float sh_red[4];\n  __shared__ uint64_t sh_sum[4];\n";
     if (bm_lds()) o << "  bm_stage();\n";
     o << "  const uint64_t rows_all = (uint64_t)bt.n_pass * bt.rows_per_pass;\n";
@@ -741,9 +812,9 @@ struct Gen {
     o << "      if (row_e) {\n";
     o << "        const int32_t eb = row_anchor(bm);\n";
     o << "        const uint64_t sb = block_sum(live ? rowfix(tmax, eb) : 0, sh_sum);\n";
-    o << "        if (threadIdx.x == 0) lse_store_row(row_e, row_s, ro + row, eb, sb, tail.tickets != nullptr);\n";
+    o << "        if (threadIdx.x == 0) lse_store_row(row_e, row_s, ro + row, eb, sb, " << tail_scope() << ");\n";
     o << "      }\n    }\n";
-    o << "  }\n  if (row_e) lse_tail(row_e, row_s, (n + 255) / 256, tail);\n}\n";
+    emit_tail();
     return o.str();
   }
 };
@@ -766,6 +837,14 @@ struct GenScan {
                       // lane's two pairs share their cipher blocks and Box-Muller transforms exactly as in the importance
                       // kernel's quad form; row statistics are wave reductions, every store is 16 bytes per lane.
   int block = 256;
+  bool fused_tail = false;  // as Gen::fused_tail: the in-launch fold of the row sums is a variant of its own (inlined, it took
+                            // the one-particle-per-lane LGSSM kernel from 64 to 133 VGPRs, 7 -> 3 waves per SIMD)
+  const char* tail_scope() const { return fused_tail ? "tail.tickets != nullptr" : "false"; }
+  void emit_tail() {
+    o << "  }\n";
+    if (fused_tail) o << "  if (row_e) lse_tail(row_e, row_s, (n + 255) / 256, tail);\n";
+    o << "}\n";
+  }
   const char* kname() const { return impl == 0 ? "gjx_scan_kernel_threefry" : "gjx_scan_kernel_philox"; }
   // PHILOX Normal sites draw through the Box-Muller tables: this source's kernels stage them in LDS (gjx_device.hpp bm_stage)
   bool bm_lds() const {
@@ -832,9 +911,9 @@ struct GenScan {
     o << "      if (row_e) {\n";
     o << "        const int32_t eb = row_anchor(bm);\n";
     o << "        const uint64_t sb = wave_sum(ok ? (rowfix(wtA, eb) + rowfix(wtB, eb) + rowfix(wtC, eb) + rowfix(wtD, eb)) : 0);\n";
-    o << "        if (threadIdx.x == 0) lse_store_row(row_e, row_s, row, eb, sb, tail.tickets != nullptr);\n";
+    o << "        if (threadIdx.x == 0) lse_store_row(row_e, row_s, row, eb, sb, " << tail_scope() << ");\n";
     o << "      }\n    }\n";
-    o << "  }\n  if (row_e) lse_tail(row_e, row_s, (n + 255) / 256, tail);\n}\n";
+    emit_tail();
     return o.str();
   }
   std::string run() {
@@ -875,9 +954,9 @@ struct GenScan {
     o << "      if (row_e) {\n";
     o << "        const int32_t eb = row_anchor(bm);\n";
     o << "        const uint64_t sb = block_sum(live ? rowfix(tmax, eb) : 0, sh_sum);\n";
-    o << "        if (threadIdx.x == 0) lse_store_row(row_e, row_s, row, eb, sb, tail.tickets != nullptr);\n";
+    o << "        if (threadIdx.x == 0) lse_store_row(row_e, row_s, row, eb, sb, " << tail_scope() << ");\n";
     o << "      }\n    }\n";
-    o << "  }\n  if (row_e) lse_tail(row_e, row_s, (n + 255) / 256, tail);\n}\n";
+    emit_tail();
     return o.str();
   }
 };
@@ -1074,7 +1153,7 @@ struct Compiled {
   int state = 0;  // 0 untried, 1 ready, -1 failed
   int block = 256;  // threads per workgroup of the compiled kernel
   int rows_per_block = 1;  // 256-particle rows per workgroup
-  std::string key;  // the source this slot holds a reference on (module cache)
+  std::string key;  // the module-cache entry this slot holds a reference on (ModuleCache::key_of the source)
   gjx::PlanTables tabs;  // the device tables of THIS plan, in the order the source numbers them (kernel argument)
 };
 
@@ -1328,10 +1407,21 @@ struct ModuleCache {
     static ModuleCache c;
     return c;
   }
-  // -> the loaded module of `src` with one more reference, or nullptr (compile / load failure, logged)
-  hipModule_t acquire(const std::string& src) {
+  // The key of a source: the source itself and, where the A/B knobs add compiler options (GJX_JIT_DEFINE, GJX_JIT_OPTS),
+  // those options — the same text compiled under another define is another module.
+  static std::string key_of(const std::string& src) {
+    const std::vector<std::string> opts = compile_options();
+    std::string key = src;
+    for (size_t k = 4; k < opts.size(); ++k) key += "\n// " + opts[k];  // (the four fixed options come first)
+    return key;
+  }
+  // -> the loaded module of `src` with one more reference, or nullptr (compile / load failure, logged); `key_out`: what
+  // release() takes
+  hipModule_t acquire(const std::string& src, std::string* key_out) {
+    const std::string key = key_of(src);
+    *key_out = key;
     std::lock_guard<std::mutex> lock(mu);
-    auto it = map.find(src);
+    auto it = map.find(key);
     if (it == map.end()) {
       std::string code;
       if (!compile_to_code(src, &code)) return nullptr;
@@ -1343,7 +1433,7 @@ struct ModuleCache {
         return nullptr;
       }
       ++compiles;
-      it = map.emplace(src, Entry{mod, 1, ++clock}).first;  // referenced before anything is evicted
+      it = map.emplace(key, Entry{mod, 1, ++clock}).first;  // referenced before anything is evicted
       evict_locked();
       return mod;
     }
@@ -1351,10 +1441,10 @@ struct ModuleCache {
     it->second.tick = ++clock;
     return it->second.mod;
   }
-  void release(const std::string& src) {
-    if (src.empty()) return;
+  void release(const std::string& key) {
+    if (key.empty()) return;
     std::lock_guard<std::mutex> lock(mu);
-    auto it = map.find(src);
+    auto it = map.find(key);
     if (it != map.end() && it->second.refs > 0) it->second.refs--;
     evict_locked();
   }
@@ -1381,9 +1471,10 @@ inline void release(Compiled* c) {
 }
 inline bool compile(const std::string& src, int impl, Compiled* out, const char* kernel = nullptr) {
   release(out);  // (a slot that is being rebuilt, e.g. without the occupancy hint)
-  hipModule_t mod = ModuleCache::get().acquire(src);
+  std::string key;
+  hipModule_t mod = ModuleCache::get().acquire(src, &key);
   if (!mod) return false;
-  out->key = src;
+  out->key = key;
   hipFunction_t fn = nullptr;
   const hipError_t ge =
       hipModuleGetFunction(&fn, mod, kernel ? kernel : (impl == 0 ? "gjx_plan_kernel_threefry" : "gjx_plan_kernel_philox"));
@@ -1409,9 +1500,10 @@ inline void release_smc(CompiledSmc* c) {
   c->step = c->step_adaptive = c->init = nullptr;
 }
 inline bool compile_smc(const std::string& src, CompiledSmc* out) {
-  hipModule_t mod = ModuleCache::get().acquire(src);
+  std::string key;
+  hipModule_t mod = ModuleCache::get().acquire(src, &key);
   if (!mod) return false;
-  out->key = src;
+  out->key = key;
   if (hipModuleGetFunction(&out->step, mod, "gjx_smc_step_kernel") != hipSuccess ||
       hipModuleGetFunction(&out->step_adaptive, mod, "gjx_smc_step_kernel_adaptive") != hipSuccess ||
       hipModuleGetFunction(&out->init, mod, "gjx_smc_init_kernel") != hipSuccess) {

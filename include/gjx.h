@@ -281,7 +281,11 @@ int gjx_plan_set_params(gjx_plan* p, const float* params /*host*/, int n_params)
  * straight-line gfx950 kernel — the same device functions in the same order, constants folded —
  * and compiled with hiprtc; GJX_PLAN_JIT=0 keeps the table-interpreter kernel.  Diagnostics:
  * the generated HIP source (buf nullable; *needed = bytes incl. NUL) and an offline compile check
- * (needs no GPU).  The oracle build returns GJX_ERR_UNSUPPORTED for both. */
+ * (needs no GPU).  The oracle build returns GJX_ERR_UNSUPPORTED for both.
+ * A plan's importance kernel exists in two variants: the default one, and one that also folds the row sums inside
+ * the launch (built on the first launch that passes a gjx_lse_out).  Both diagnostics show / check the default
+ * variant; `impl | GJX_SOURCE_FUSED_TAIL` asks for the other. */
+#define GJX_SOURCE_FUSED_TAIL 0x100
 int gjx_plan_specialized_source(const gjx_plan* p, int impl, char* buf, size_t buf_len, size_t* needed);
 /* Build (hiprtc) and load now the kernel gjx_importance_run would build on its first launch with
  * this key form, so that no launch pays the ~0.2 s compilation.  Optional; the oracle build returns

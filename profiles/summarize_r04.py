@@ -74,7 +74,7 @@ with open(os.path.join(here, f"{tag}_summary.md"), "w") as f:
     f.write("| kernel | calls | avg ns | min ns | max ns | % |\n|---|---|---|---|---|---|\n")
     for r in stats:
         f.write(f"| `{r['Name'][:90]}` | {r['Calls']} | {float(r['AverageNs']):.0f} | {r['MinNs']} | {r['MaxNs']} | {r['Percentage']} |\n")
-    f.write("\n## per (kernel, grid): the launch shapes the bench line quotes\n\n| kernel | grid (threads) | VGPR | SGPR | launches | avg ns | median ns | min ns |\n|---|---|---|---|---|---|---|---|\n")
+    f.write("\n## per (kernel, grid): the launch shapes the bench line quotes\n\n| kernel | grid (threads) | VGPR (trace column: HALF the allocation on gfx950) | SGPR | launches | avg ns | median ns | min ns |\n|---|---|---|---|---|---|---|---|\n")
     for (name, grid, vg, sg), ts in sorted(by.items(), key=lambda kv: -sum(kv[1])):
         if len(ts) < 3:
             continue
