@@ -8,6 +8,7 @@
 // bits.  No entry point allocates, frees or synchronises (graph-capturable), except plan
 // create/destroy.
 #include "../../include/gjx.h"
+#include "../../include/gjx_guided.h"
 #include "gjx_device.hpp"
 
 #include <hip/hip_runtime.h>
@@ -1992,7 +1993,7 @@ static void cat_tables_prepare(CSite* sites, int n, std::vector<void*>* owned) {
     const size_t rows = (size_t)st.n_rows;
     const unsigned grid = ((unsigned)rows + 63) / 64;
     // (one thread per row: rows are few — a transition / emission matrix — and this runs once per plan)
-    if (st.observed && st.obs.kind != GJX_ARG_INPUT) {  // the value is launch-uniform: the transposed log-probabilities only
+    if (!gjx_jit::sampled_mode(st.observed) && st.obs.kind != GJX_ARG_INPUT) {  // never drawn here (observed: a launch-uniform value; guided: its partner's): the transposed log-probabilities only
       float* lt = nullptr;
       if (hipMalloc(&lt, sizeof(float) * rows * (size_t)st.n_cat) != hipSuccess) { (void)hipGetLastError(); continue; }
       k_cat_prepare<<<grid, 64>>>(st.logits, (uint32_t)rows, (uint32_t)st.n_cat, nullptr, nullptr, lt, 0);
@@ -2106,12 +2107,17 @@ static bool arg_ok(const gjx_arg& a, int s, int n_state = -1, int n_obs = -1, bo
 static CArg carg(const gjx_arg& a) { return CArg{a.kind, a.ref, 0, a.ref, a.scale, a.offset, a.table}; }
 
 // Validate one site and convert it (hoisting per-site constants with the same spec functions).
+// `allow_guided`: the tables of gjx_smc_plan_create_guided, where `observed` may also be GJX_SITE_PROPOSED / GJX_SITE_GUIDED
+// (include/gjx_guided.h); every other creator refuses observed > 1 (it used to read it as "observed").
 static bool convert_site(const gjx_site& st, int s, CSite& c, int n_state = -1, int n_obs = -1,
-                         bool allow_state = false) {
+                         bool allow_state = false, bool allow_guided = false) {
+  if (st.observed > (allow_guided ? GJX_SITE_GUIDED : 1)) return false;
   bool ok = st.dist >= 0 && st.dist <= GJX_DIST_CATEGORICAL && arg_ok(st.arg[0], s, n_state, n_obs, allow_state);
   const bool two_args = st.dist != GJX_DIST_BERNOULLI && st.dist != GJX_DIST_CATEGORICAL;
   if (ok && two_args) ok = arg_ok(st.arg[1], s, n_state, n_obs, allow_state);
-  if (ok && st.observed) {
+  if (ok && st.observed == GJX_SITE_GUIDED) {  // (that the partner is a PROPOSED site of the same kind: smc_guided_pairs_ok)
+    ok = st.obs.kind == GJX_ARG_SITE && st.obs.ref >= 0 && st.obs.ref < s && st.obs.scale == 1.0f && st.obs.offset == 0.0f;
+  } else if (ok && st.observed && st.observed != GJX_SITE_PROPOSED) {
     if (n_state < 0) ok = st.obs.kind == GJX_ARG_CONST || (st.obs.kind == GJX_ARG_INPUT && st.obs.ref >= 0 && st.obs.ref < 16) ||
                           (st.obs.kind == GJX_ARG_PARAM && st.obs.ref >= 0 && st.obs.ref < GJX_MAX_PARAMS);
     else ok = st.obs.kind == GJX_ARG_CONST || (st.obs.kind == GJX_ARG_OBS && st.obs.ref >= 0 && st.obs.ref < n_obs);
@@ -3385,11 +3391,25 @@ struct gjx_smc_plan {
   ExprStore init_expr, step_expr;  // GJX_ARG_EXPR programs of the two tables
   StateExprStore init_state_expr, next_state_expr;
   gjx_jit::ScopeInfo init_scopes, step_scopes;        // nested calls (gjx_smc_plan_create_scoped): generated kernels only
+  bool guided = false;                                // proposed / guided sites (gjx_guided.h): generated kernels only
   bool has_expr = false;                              // any program?  Then the filter runs as generated kernels only
   CSite* dev_init = nullptr; CSite* dev_step = nullptr;  // the interpreter's device copies of the tables (made on first use)
 };
 
-int gjx_smc_plan_create(const gjx_smc_model* m, gjx_smc_plan** out) {
+// every PROPOSED site of a table has exactly one GUIDED partner, of its own kind (integer- or float-valued)
+static bool smc_guided_pairs_ok(const CSite* sites, int n) {
+  int refs[GJX_MAX_SITES] = {};
+  for (int q = 0; q < n; ++q) {
+    if (sites[q].observed != GJX_SITE_GUIDED) continue;
+    const CSite& pr = sites[sites[q].obs.ref_site];
+    if (pr.observed != GJX_SITE_PROPOSED || (pr.dist >= GJX_DIST_BERNOULLI) != (sites[q].dist >= GJX_DIST_BERNOULLI)) return false;
+    refs[sites[q].obs.ref_site]++;
+  }
+  for (int q = 0; q < n; ++q)
+    if (sites[q].observed == GJX_SITE_PROPOSED && refs[q] != 1) return false;
+  return true;
+}
+static int smc_plan_create_impl(const gjx_smc_model* m, gjx_smc_plan** out, bool allow_guided) {
   if (!m || !out || m->n_state < 1 || m->n_state > GJX_SMC_MAX_STATE || m->n_obs < 0 || m->n_obs > GJX_SMC_MAX_OBS ||
       !m->init_sites || !m->step_sites || m->n_init_sites <= 0 || m->n_init_sites > GJX_MAX_SITES ||
       m->n_step_sites <= 0 || m->n_step_sites > GJX_MAX_SITES)
@@ -3398,8 +3418,13 @@ int gjx_smc_plan_create(const gjx_smc_model* m, gjx_smc_plan** out) {
   if (!p) return GJX_ERR_LAUNCH;
   p->n_state = m->n_state; p->n_obs = m->n_obs; p->n_init = m->n_init_sites; p->n_step = m->n_step_sites;
   bool ok = true;
-  for (int s = 0; ok && s < p->n_init; ++s) ok = convert_site(m->init_sites[s], s, p->init[s], m->n_state, m->n_obs, false);
-  for (int s = 0; ok && s < p->n_step; ++s) ok = convert_site(m->step_sites[s], s, p->step[s], m->n_state, m->n_obs, true);
+  for (int s = 0; ok && s < p->n_init; ++s) ok = convert_site(m->init_sites[s], s, p->init[s], m->n_state, m->n_obs, false, allow_guided);
+  for (int s = 0; ok && s < p->n_step; ++s) ok = convert_site(m->step_sites[s], s, p->step[s], m->n_state, m->n_obs, true, allow_guided);
+  if (ok && allow_guided) {
+    ok = smc_guided_pairs_ok(p->init, p->n_init) && smc_guided_pairs_ok(p->step, p->n_step);
+    for (int s = 0; s < p->n_init; ++s) p->guided = p->guided || p->init[s].observed > 1;
+    for (int s = 0; s < p->n_step; ++s) p->guided = p->guided || p->step[s].observed > 1;
+  }
   for (int k = 0; ok && k < p->n_state; ++k) {
     ok = arg_ok(m->init_state[k], p->n_init, m->n_state, m->n_obs, false) && m->init_state[k].kind != GJX_ARG_TABLE &&
          arg_ok(m->next_state[k], p->n_step, m->n_state, m->n_obs, true) && m->next_state[k].kind != GJX_ARG_TABLE;
@@ -3417,6 +3442,13 @@ int gjx_smc_plan_create(const gjx_smc_model* m, gjx_smc_plan** out) {
   for (int k = 0; k < p->n_state; ++k)
     p->has_expr = p->has_expr || p->init_state[k].kind == GJX_ARG_EXPR || p->next_state[k].kind == GJX_ARG_EXPR;
   *out = p;
+  return GJX_OK;
+}
+int gjx_smc_plan_create(const gjx_smc_model* m, gjx_smc_plan** out) { return smc_plan_create_impl(m, out, false); }
+int gjx_smc_plan_create_guided(const gjx_smc_model* m, gjx_smc_plan** out) { return smc_plan_create_impl(m, out, true); }
+int gjx_guided_version(int* major, int* minor) {
+  if (major) *major = GJX_GUIDED_VERSION_MAJOR;
+  if (minor) *minor = GJX_GUIDED_VERSION_MINOR;
   return GJX_OK;
 }
 int gjx_smc_plan_create_scoped(const gjx_smc_model* m, const gjx_scope* init_scopes, int n_init_scopes,
@@ -3476,6 +3508,17 @@ static std::string smc_plan_source(const gjx_smc_plan* plan, int impl, PlanTable
   if (tabs) *tabs = ts.reg.tables();
   return src;
 }
+int gjx_smc_plan_source(const gjx_smc_plan* p, int impl, char* buf, size_t buf_len, size_t* needed) {
+  if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
+  const std::string src = smc_plan_source(p, impl);
+  if (needed) *needed = src.size() + 1;
+  if (buf && buf_len > 0) {
+    const size_t k = src.size() < buf_len - 1 ? src.size() : buf_len - 1;
+    memcpy(buf, src.data(), k);
+    buf[k] = 0;
+  }
+  return GJX_OK;
+}
 int gjx_smc_plan_compile_check(const gjx_smc_plan* p, int impl) {
   if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
   if (std::getenv("GJX_PLAN_JIT_DUMP")) fprintf(stderr, "%s\n", smc_plan_source(p, impl).c_str());
@@ -3524,7 +3567,7 @@ static int smc_plan_route(gjx_smc_plan* plan, int impl, gjx_jit::CompiledSmc** c
   if (peers) return gjx_jit::enabled() ? GJX_ERR_JIT : GJX_ERR_UNSUPPORTED;  // (the table-walking policy has no peer form)
   const bool off = !gjx_jit::enabled();
   if (!off && !jit_fallback_allowed()) return GJX_ERR_JIT;  // loud: never a silent slower route
-  if (plan->has_expr || plan->init_scopes.n_scopes > 0 || plan->step_scopes.n_scopes > 0) return off ? GJX_ERR_UNSUPPORTED : GJX_ERR_JIT;
+  if (plan->has_expr || plan->guided || plan->init_scopes.n_scopes > 0 || plan->step_scopes.n_scopes > 0) return off ? GJX_ERR_UNSUPPORTED : GJX_ERR_JIT;
   return smc_plan_interp_tables(plan);
 }
 static int smc_plan_step(const gjx_smc_config* cfg, gjx_smc_plan* plan, gjx_jit::CompiledSmc* cp, int t,

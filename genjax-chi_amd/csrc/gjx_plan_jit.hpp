@@ -94,6 +94,9 @@ inline std::string plit(const void* p) { return plit_as("float", p); }
 // from the scopes' ranges: every `@` site and every call takes the next counter of the scope it sits in (THREEFRY: the
 // 1-based counter over all of them; PHILOX: the 0-based index among those that consume randomness — unobserved sites and
 // calls), a callee numbers its own sites afresh under fold_in(caller's key, the call's counter).
+// gjx_site.observed (include/gjx.h: 0 latent, 1 observed; include/gjx_guided.h: 2 proposed, 3 guided): does the site
+// consume randomness?  Latent and proposed sites do — same draw numbering, same quad blocks.
+inline bool sampled_mode(int observed) { return observed == 0 || observed == GJX_SITE_PROPOSED; }
 struct ScopeInfo {
   int n_scopes = 0;
   int site_scope[GJX_MAX_SITES];
@@ -132,7 +135,7 @@ inline bool derive_scopes(const gjx_site* sites, int n_sites, const gjx_scope* s
     out.site_scope[q] = fr[depth - 1].id;
     out.fold_t[q] = fr[depth - 1].ct++;
     out.fold_p[q] = fr[depth - 1].dr;
-    if (!sites[q].observed) fr[depth - 1].dr++;
+    if (sampled_mode(sites[q].observed)) fr[depth - 1].dr++;
   }
   return next == n_sc;
 }
@@ -163,6 +166,9 @@ struct SiteEmitter {
   }
 
   static bool is_int(const CSiteT& s) { return s.dist >= GJX_DIST_BERNOULLI; }
+  static bool sampled(const CSiteT& s) { return sampled_mode(s.observed); }  // consumes randomness (latent or proposed)
+  static bool proposed(const CSiteT& s) { return s.observed == GJX_SITE_PROPOSED; }
+  static bool guided(const CSiteT& s) { return s.observed == GJX_SITE_GUIDED; }
   std::string nm(const char* base, int q) const { return std::string(base) + std::to_string(q) + sfx; }
   std::string val_f32(int site) const { return is_int(sites[site]) ? "(float)" + nm("vi", site) : nm("vf", site); }
   std::string val_i32(int site) const {
@@ -233,12 +239,12 @@ struct SiteEmitter {
   // does any site draw (and so need the per-particle key)?
   bool needs_pk() const {
     for (int q = 0; q < n_sites; ++q)
-      if (!sites[q].observed) return true;
+      if (sampled(sites[q])) return true;
     return false;
   }
   bool needs_stream_key() const {
     for (int q = 0; q < n_sites; ++q)
-      if (!sites[q].observed && !one_word(sites[q])) return true;
+      if (sampled(sites[q]) && !one_word(sites[q])) return true;
     return false;
   }
   // fold of site q: THREEFRY the 1-based site counter; PHILOX the 0-based index among the sampled sites
@@ -246,7 +252,7 @@ struct SiteEmitter {
     if (sc) return impl == 0 ? sc->fold_t[q] : sc->fold_p[q];
     if (impl == 0) return (uint32_t)(q + 1);
     uint32_t d = 0;
-    for (int p = 0; p < q; ++p) d += sites[p].observed ? 0u : 1u;
+    for (int p = 0; p < q; ++p) d += sampled(sites[p]) ? 1u : 0u;
     return d;
   }
   bool one_word(const CSiteT& st) const {
@@ -263,7 +269,7 @@ struct SiteEmitter {
     const CSiteT& st = sites[q];
     const std::string Q = std::to_string(q) + sfx;
     const uint32_t fold = fold_of(q);
-    o << ind << "// site " << q << sfx << " dist " << st.dist << (st.observed ? " observed" : " latent") << "\n";
+    o << ind << "// site " << q << sfx << " dist " << st.dist << (guided(st) ? " guided" : proposed(st) ? " proposed" : st.observed ? " observed" : " latent") << "\n";
     if (st.dist == GJX_DIST_CATEGORICAL) {
       std::string rr;
       if (st.a0.kind == GJX_ARG_SITE) rr = val_i32(st.a0.ref_site);
@@ -313,7 +319,12 @@ struct SiteEmitter {
       o << ind << "const float a0_" << Q << " = " << carg(st.a0, 0) << ";\n";
       if (st.dist != GJX_DIST_BERNOULLI) o << ind << "const float a1_" << Q << " = " << carg(st.a1, 1) << ";\n";
     }
-    if (st.observed) {
+    if (guided(st)) {  // the value its partner (an earlier proposed site) drew
+      if (is_int(st)) o << ind << "const int32_t vi" << Q << " = " << val_i32(st.obs.ref_site) << ";\n";
+      else o << ind << "const float vf" << Q << " = " << val_f32(st.obs.ref_site) << ";\n";
+      return;
+    }
+    if (st.observed == 1) {
       std::string ov;
       if (st.obs.kind == GJX_ARG_CONST) {
         const float v = st.obs.offset;
@@ -346,7 +357,7 @@ struct SiteEmitter {
     const std::string row = "row" + Q;
     const bool isint = is_int(st);
     // (presampled: the pair / quad forms draw the gammas of a lane's particles together — std_gamma_multi — and define vf<q> themselves)
-    if (!st.observed && !(presampled && (st.dist == GJX_DIST_GAMMA || st.dist == GJX_DIST_BETA))) {
+    if (sampled(st) && !(presampled && (st.dist == GJX_DIST_GAMMA || st.dist == GJX_DIST_BETA))) {
       switch (st.dist) {
         case GJX_DIST_NORMAL: {
           std::string e = eps;
@@ -389,8 +400,15 @@ struct SiteEmitter {
     const std::string lp = lp_of(q);
     const std::string v = (isint ? "vi" : "vf") + Q;
     const std::string aw = acc("w", scope_of(q)), as = acc("sc", scope_of(q));
-    o << ind << "{ const float lp = " << lp << "; " << as << " = " << as << " + lp;"
-      << (st.observed ? " " + aw + " = " + aw + " + lp;" : "") << " }\n";
+    if (proposed(st)) {  // q's log-density enters nothing here: its guided partner adds lp - lq at ITS position
+      o << ind << "const float lq" << Q << " = " << lp << ";\n";
+    } else if (guided(st)) {  // the difference first (a proposal equal to the model's site cancels exactly), then the sum
+      o << ind << "{ const float lp = " << lp << "; " << as << " = " << as << " + lp; const float d = lp - " << nm("lq", st.obs.ref_site)
+        << "; " << aw << " = " << aw << " + d; }\n";
+    } else {
+      o << ind << "{ const float lp = " << lp << "; " << as << " = " << as << " + lp;"
+        << (st.observed ? " " + aw + " = " + aw + " + lp;" : "") << " }\n";
+    }
     if ((mode == 0 || mode == 2) && st.out_col >= 0 && store_values)
       o << ind << "reinterpret_cast<uint32_t*>(cols.out[" << st.out_col << "])[" << (mode == 2 ? "oi" : "i") << sfx << "] = "
         << (isint ? "(uint32_t)" + v : "f2u(" + v + ")") << ";\n";
@@ -421,7 +439,7 @@ struct SiteEmitter {
         break;
       case GJX_DIST_BERNOULLI: lp = "logpdf_bernoulli(" + v + " != 0, a0_" + Q + ")"; break;
       default:
-        if (st.cat_ent && !st.observed && st.cat_mode != 0)
+        if (st.cat_ent && sampled(st) && st.cat_mode != 0)
           lp = "u2f(lpb" + Q + ")";  // a drawn category is in range
         else
           lp = "((" + v + " < 0 || " + v + " >= " + std::to_string(st.n_cat) + ") ? -__builtin_inff() : " +
@@ -439,7 +457,7 @@ struct SiteEmitter {
         if (ops[k].op >= GJX_EXPR_SITE && ops[k].op <= GJX_EXPR_OBS) return false;
       return true;
     };
-    const bool all_const = st.observed && st.obs.kind == GJX_ARG_CONST && is_const(st.a0) &&
+    const bool all_const = st.observed == 1 && st.obs.kind == GJX_ARG_CONST && is_const(st.a0) &&
                            (st.dist == GJX_DIST_BERNOULLI || st.dist == GJX_DIST_CATEGORICAL || is_const(st.a1));
     if (all_const) lp = "opq(" + lp + ")";
     return lp;
@@ -990,7 +1008,7 @@ struct GenSmc {
     SiteEmitter<CSiteT, CArgT> e{const_cast<std::ostringstream&>(o), impl, 1, sites, n_sites, "", ""};
     e.sc = sc;
     for (int q = 0; q < n_sites; ++q)
-      if (!sites[q].observed && e.one_word(sites[q]) && e.scope_of(q) == 0) ++n;
+      if (e.sampled(sites[q]) && e.one_word(sites[q]) && e.scope_of(q) == 0) ++n;
     return n;
   }
   void emit_prefetch(const CSiteT* sites, int n_sites, const ScopeInfo* sc) {
@@ -1000,7 +1018,7 @@ struct GenSmc {
     int i = 0;
     for (int q = 0; q < n_sites; ++q) {
       const CSiteT& st = sites[q];
-      if (st.observed || !e.one_word(st) || e.scope_of(q) != 0) continue;
+      if (!e.sampled(st) || !e.one_word(st) || e.scope_of(q) != 0) continue;
       o << "    philox4x32(a.step_key.k0, a.step_key.k1, (uint32_t)g, (uint32_t)(g >> 32), " << e.fold_of(q) << "u, kTagQuad, pf_w[" << i
         << "][0], pf_w[" << i << "][1], pf_w[" << i << "][2], pf_w[" << i << "][3]);\n";
       if (st.dist == GJX_DIST_NORMAL) {
@@ -1033,7 +1051,7 @@ struct GenSmc {
       const CSiteT& st = sites[q];
       const std::string Q = std::to_string(q);
       for (int u = 0; u < 4; ++u) em[u].head(q);
-      const bool drawn = !st.observed && em[0].one_word(st) && em[0].scope_of(q) == 0;  // (a callee's sites: their own lone keys)
+      const bool drawn = em[0].sampled(st) && em[0].one_word(st) && em[0].scope_of(q) == 0;  // (a callee's sites: their own lone keys)
       const bool normal = drawn && st.dist == GJX_DIST_NORMAL;
       if (drawn && prefetched) {  // (computed by prefetch(): the same block, the same transforms)
         for (int u = 0; u < 4; ++u) o << "    const uint32_t bits" << Q << sf[u] << " = pf_w[" << pf_i << "][" << u << "]; (void)bits" << Q << sf[u] << ";\n";

@@ -66,6 +66,15 @@ class PathsUnavailable(GjxError):
         self.code = -2
 
 
+class GuidedUnavailable(GjxError):
+    """An entry point of include/gjx_guided.h called on a library that does not export it (GJX_ERR_UNSUPPORTED)."""
+
+    def __init__(self, fn: str, backend: str):
+        RuntimeError.__init__(self, f"{fn}: the library '{backend}' does not implement include/gjx_guided.h "
+                                    "(libgjx_hip.so does; the CPU oracle knows no proposed / guided sites and would misread their tables)")
+        self.code = -2
+
+
 class Keys(C.Structure):
     _fields_ = [
         ("impl", C.c_int32),
@@ -468,6 +477,15 @@ PATHS_PROTOTYPES = {
 }
 PATHS_ABI_VERSION = (0, 1)
 
+# include/gjx_guided.h: a THIRD header, same arrangement — guided particle filters (proposed / guided site modes)
+SITE_PROPOSED, SITE_GUIDED = 2, 3  # gjx_guided.h: GJX_SITE_PROPOSED / GJX_SITE_GUIDED (values of Site.observed)
+GUIDED_PROTOTYPES = {
+    "gjx_guided_version": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gjx_smc_plan_create_guided": (C.c_int, [C.POINTER(SmcModel), C.POINTER(_P)]),
+    "gjx_smc_plan_source": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+}
+GUIDED_ABI_VERSION = (0, 1)
+
 _NO_STATUS = {
     "gjx_paths_workspace_bytes",
     "gjx_backend_name",
@@ -540,9 +558,27 @@ class GjxLib:
                 fn.argtypes = args
                 setattr(self, "_" + name, fn)
 
+        # include/gjx_guided.h: likewise
+        self.has_guided = hasattr(self._dll, "gjx_guided_version")
+        if self.has_guided:
+            vfn = self._dll.gjx_guided_version
+            vfn.restype, vfn.argtypes = GUIDED_PROTOTYPES["gjx_guided_version"]
+            vfn(C.byref(major), C.byref(minor))
+            if (major.value, minor.value) != GUIDED_ABI_VERSION:
+                raise AbiVersionMismatch(
+                    f"{path} implements gjx_guided.h {major.value}.{minor.value}; these bindings are written for "
+                    f"{GUIDED_ABI_VERSION[0]}.{GUIDED_ABI_VERSION[1]}: rebuild the library from this tree")
+            for name, (res, args) in GUIDED_PROTOTYPES.items():
+                fn = getattr(self._dll, name)
+                fn.restype = res
+                fn.argtypes = args
+                setattr(self, "_" + name, fn)
+
     def call(self, name: str, *args):
         if name in PATHS_PROTOTYPES and not self.has_paths:
             raise PathsUnavailable(name, self.name)
+        if name in GUIDED_PROTOTYPES and not self.has_guided:
+            raise GuidedUnavailable(name, self.name)
         rc = getattr(self, "_" + name)(*args)
         if name not in _NO_STATUS and rc != GJX_OK:
             raise GjxError(name, rc)

@@ -585,7 +585,14 @@ class Ops:
         return cdf.view(n_states, -1), logp
 
     # ---- bootstrap SMC for a user model (init + step site tables) --------------------------------
-    def smc_plan_create(self, init_sites, step_sites, init_state, next_state, n_obs: int, init_scopes=(), step_scopes=()) -> "SmcPlan":
+    def smc_plan_create(self, init_sites, step_sites, init_state, next_state, n_obs: int, init_scopes=(), step_scopes=(),
+                        guided: bool = False) -> "SmcPlan":
+        """`guided`: the tables may hold proposed / guided sites (include/gjx_guided.h: gjx_smc_plan_create_guided; raises
+        abi.GuidedUnavailable on a library without that header — the CPU oracle)."""
+        if guided and not self.lib.has_guided:
+            raise abi.GuidedUnavailable("gjx_smc_plan_create_guided", self.lib.name)
+        if guided and (init_scopes or step_scopes):
+            raise ValueError("a guided plan has flat bodies (gjx_smc_plan_create_guided takes no scopes)")
         m = abi.SmcModel()
         ia = (abi.Site * len(init_sites))(*init_sites)
         sa = (abi.Site * len(step_sites))(*step_sites)
@@ -596,7 +603,9 @@ class Ops:
             m.next_state[k] = a
         m.n_state, m.n_obs = len(next_state), n_obs
         handle = C.c_void_p()
-        if init_scopes or step_scopes:  # nested `@gen` calls inside init / step
+        if guided:
+            self.lib.call("gjx_smc_plan_create_guided", C.byref(m), C.byref(handle))
+        elif init_scopes or step_scopes:  # nested `@gen` calls inside init / step
             si = (abi.Scope * max(1, len(init_scopes)))(*[abi.Scope(*k) for k in init_scopes])
             ss = (abi.Scope * max(1, len(step_scopes)))(*[abi.Scope(*k) for k in step_scopes])
             self.lib.call("gjx_smc_plan_create_scoped", C.byref(m), si, len(init_scopes), ss, len(step_scopes), C.byref(handle))
@@ -815,6 +824,17 @@ class SmcPopulation:
 class SmcPlan:
     def __init__(self, ops: "Ops", handle, n_state: int, n_obs: int):
         self.ops, self.handle, self.n_state, self.n_obs = ops, handle, n_state, n_obs
+
+    def compile_check(self, impl: int) -> int:
+        return self.ops.lib._gjx_smc_plan_compile_check(self.handle, impl)
+
+    def source(self, impl: int) -> str:
+        """The HIP source of the plan's generated kernels (include/gjx_guided.h: gjx_smc_plan_source)."""
+        need = C.c_size_t()
+        self.ops.lib.call("gjx_smc_plan_source", self.handle, impl, None, 0, C.byref(need))
+        buf = C.create_string_buffer(need.value)
+        self.ops.lib.call("gjx_smc_plan_source", self.handle, impl, buf, need.value, None)
+        return buf.value.decode()
 
     def __del__(self):
         try:

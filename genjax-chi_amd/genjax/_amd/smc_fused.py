@@ -24,7 +24,7 @@ from . import abi, prng
 from .choicemap import ChoiceMap
 from .runtime import get_ops, use_ops
 from .smc_models import HmmFilter, LgssmFilter, PlanFilter
-from .smc_plan import StateSpaceModel, build_smc_plan, observation_matrix
+from .smc_plan import StateSpaceModel, build_guided_plan, build_smc_plan, observation_matrix
 from .workloads import smc_key_schedule
 
 
@@ -274,3 +274,42 @@ class BootstrapSMC:
 
     def log_marginal_likelihood_estimate(self, key: prng.PRNGKey) -> float:
         return self.run(key).log_marginal_likelihood
+
+
+class GuidedSMC(BootstrapSMC):
+    """Particle filter of a `StateSpaceModel` whose latent sites are drawn from USER PROPOSALS instead of the model's own
+    transition (a bootstrap filter collapses when the observations are sharp against the transition noise):
+
+        @gen
+        def track_q(carry, y):               # (the carry as `step` receives it, this step's observations)
+            normal(c1 * carry + c2 * y, s) @ "x"
+
+        GuidedSMC(StateSpaceModel(init, step), C["y"].set(ys), n, step_proposal=track_q).run(key)
+
+    `y` is a scalar when one address is observed and a tuple in the order of the observation ChoiceMap's leaves when several
+    are; a proposal's return value is ignored.  A proposal site is paired with the model's body-level latent site of the
+    same address: the model's site takes the proposed value and the step's weight is multiplied by p(x_t | x_{t-1}) /
+    q(x_t | x_{t-1}, y_t).  Model latents without a partner keep being drawn from the model.  Without
+    `init_proposal(y)` step 0 is the bootstrap filter's.  `PlanUnsupported` (naming the address): a proposal site without
+    a model partner or on an observed address, an integer-valued site paired with a float-valued one, a nested `@gen`
+    call inside a proposal or in the model's bodies.
+
+    Everything else is `BootstrapSMC`: the lowering gives an ordinary generated plan, so `run`, `run_many`, `ess_threshold`,
+    `record_history`, `SMCResult.trajectories` and one-launch-per-step / graph replay work unchanged.  The two site modes
+    exist in libgjx_hip.so only (include/gjx_guided.h): on other libraries `abi.GuidedUnavailable`.  Guided plans in the
+    sharded drivers (`ShardedSMC`) are out of scope: nothing there has been run or tested with them."""
+
+    def __init__(self, model: StateSpaceModel, observations, n_particles: int, step_proposal, init_proposal=None,
+                 record_ancestors: bool = False, ess_threshold: float = 0.0, record_history: bool = False):
+        if not isinstance(model, StateSpaceModel):
+            raise TypeError("GuidedSMC guides a StateSpaceModel (the hand-written models have no proposal sites)")
+        super().__init__(model, observations, n_particles, record_ancestors, ess_threshold, record_history)
+        self.step_proposal, self.init_proposal = step_proposal, init_proposal
+
+    def _bind(self, ops):
+        if self._plan is None:
+            addrs = [a for a, _ in self.observations.leaves()]
+            with use_ops(ops):
+                plan, _ = build_guided_plan(self.model, addrs, self.step_proposal, self.init_proposal)
+            self._plan = (plan, observation_matrix(self.observations, addrs))
+        return PlanFilter(ops, *self._plan)

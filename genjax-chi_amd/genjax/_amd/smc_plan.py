@@ -31,7 +31,7 @@ import torch
 from . import abi
 from .choicemap import ChoiceMap
 from .lang import GenerativeFunction, StaticGenerativeFunction
-from .plan import PlanTracer, PlanUnsupported, Sym, _Table
+from .plan import PlanTracer, PlanUnsupported, Sym, _IntSym, _Table
 from .runtime import get_ops
 
 
@@ -120,6 +120,119 @@ def build_smc_plan(model: StateSpaceModel, obs_addrs: list[tuple]):
     plan = get_ops().smc_plan_create(ti.sites, ts.sites, init_state, next_state, len(obs_addrs),
                                      init_scopes=[tuple(k) for k in ti.scopes], step_scopes=[tuple(k) for k in ts.scopes])
     plan._keep = (ti.keep, ts.keep)  # constant tables the site tables point into
+    return plan, len(init_state)
+
+
+class _GuidedTracer(_SmcTracer):
+    """One tracer and ONE site table for a proposal and the model body it guides.  The proposal is traced first: its sites
+    take table positions 0 .. n_q - 1 as PROPOSED sites (sampled like latent ones; their log-density is kept).  The model
+    body is then traced into the same table: at the address of a proposed site it emits a GUIDED site that points at its
+    partner, and the value the body sees from there on is the partner's value."""
+
+    def __init__(self, obs_index: dict):
+        super().__init__(obs_index)
+        self.in_proposal = False
+        self.proposed: dict = {}  # address -> table index of the proposal's site, until the model's site has taken it
+
+    def run_proposal(self, proposal, args):
+        self.in_proposal = True
+        try:
+            self.run(proposal.source, args)  # (the proposal's return value is ignored)
+        finally:
+            self.in_proposal = False
+        self.traces = {}  # the model body uses the same addresses again
+        self.items = []
+
+    def unpaired(self) -> list:
+        return list(self.proposed)
+
+    def _call(self, addr, gen_fn, args):
+        if self.in_proposal:
+            raise PlanUnsupported(f"nested `@gen` call at address {addr!r} inside a proposal: proposals are flat bodies of distribution sites")
+        a = addr if isinstance(addr, tuple) else (addr,)
+        inside = [k for k in self.proposed if k[:len(self.prefix + a)] == self.prefix + a]
+        if inside:
+            raise PlanUnsupported(f"the proposal's site {_show(inside[0])} pairs with a model site inside the callee at {addr!r}: "
+                                  "only body-level latent sites can be guided")
+        raise PlanUnsupported(f"nested `@gen` call at address {addr!r} in a body of a guided model: guided plans have flat bodies "
+                              "(a site inside a callee cannot be guided)")
+
+    def handle_trace(self, addr, gen_fn, args):
+        from .lang import Distribution
+
+        if not isinstance(gen_fn, Distribution):
+            return self._call(addr, gen_fn, args)
+        key = self.prefix + (addr if isinstance(addr, tuple) else (addr,))
+        if self.in_proposal:
+            if key in self.obs_index:
+                raise PlanUnsupported(f"the proposal draws the OBSERVED address {_show(key)}: only latent sites can be proposed")
+            out = super().handle_trace(addr, gen_fn, args)
+            self.sites[-1].observed = abi.SITE_PROPOSED
+            self.proposed[key] = len(self.sites) - 1
+            return out
+        if key not in self.proposed:
+            return super().handle_trace(addr, gen_fn, args)
+        partner = self.proposed.pop(key)
+        super().handle_trace(addr, gen_fn, args)  # the model's own site: its distribution and arguments
+        site, me = self.sites[-1], len(self.sites) - 1
+        if self.meta[me]["is_int"] != self.meta[partner]["is_int"]:
+            raise PlanUnsupported(f"address {_show(key)}: the proposal's site is "
+                                  f"{'integer' if self.meta[partner]['is_int'] else 'float'}-valued and the model's is "
+                                  f"{'integer' if self.meta[me]['is_int'] else 'float'}-valued")
+        site.observed = abi.SITE_GUIDED
+        site.obs = abi.Arg(abi.ARG_SITE, partner, 1.0, 0.0, None)
+        return _IntSym(self, ("site", partner)) if self.meta[partner]["is_int"] else Sym(self, ("site", partner))
+
+
+def _show(key: tuple) -> str:
+    return repr(key[0] if len(key) == 1 else key)
+
+
+def build_guided_plan(model: StateSpaceModel, obs_addrs: list[tuple], step_proposal, init_proposal=None):
+    """-> (SmcPlan, n_state) of the guided filter: `build_smc_plan` with `step_proposal(carry, y)` (and, if given,
+    `init_proposal(y)`) traced in front of the model's bodies.  `y`: this step's observation (a tuple in the order of
+    `obs_addrs` when several addresses are observed).  Raises abi.GuidedUnavailable on a library without
+    include/gjx_guided.h."""
+    gens = [model.init, model.step, step_proposal] + ([init_proposal] if init_proposal is not None else [])
+    if not all(isinstance(g, StaticGenerativeFunction) for g in gens):
+        raise TypeError("GuidedSMC needs `@gen` functions for the model and the proposals")
+    if len(obs_addrs) > abi.SMC_MAX_OBS:
+        raise PlanUnsupported(f"at most {abi.SMC_MAX_OBS} observed addresses per step")
+    ops = get_ops()
+    if not ops.lib.has_guided:  # (before any table is built: the oracle would misread the two site modes)
+        raise abi.GuidedUnavailable("gjx_smc_plan_create_guided", ops.lib.name)
+    obs_index = {a: k for k, a in enumerate(obs_addrs)}
+
+    def obs_arg(tr):
+        ys = tuple(Sym(tr, ("obs", k)) for k in range(len(obs_addrs)))
+        return ys[0] if len(ys) == 1 else ys
+
+    def close(tr, what):
+        if tr.unpaired():
+            raise PlanUnsupported(f"the {what} proposal's site {_show(tr.unpaired()[0])} has no partner: "
+                                  "the model has no body-level latent site at that address")
+
+    ti = _GuidedTracer(obs_index)
+    if init_proposal is not None:
+        ti.run_proposal(init_proposal, (obs_arg(ti),))
+    init_ret = ti.run(model.init.source, ())
+    close(ti, "init")
+    init_state = _state_args(ti, init_ret, None)
+    ts = _GuidedTracer(obs_index)
+    carry = tuple(Sym(ts, ("state", k)) for k in range(len(init_state)))
+    carry_arg = carry[0] if len(carry) == 1 else carry
+    ts.run_proposal(step_proposal, (carry_arg, obs_arg(ts)))
+    step_ret = ts.run(model.step.source, (carry_arg,))
+    close(ts, "step")
+    next_state = _state_args(ts, step_ret, len(init_state))
+    seen = {m["path"] for m in ti.meta + ts.meta}
+    missing = [a for a in obs_addrs if a not in seen]
+    if missing:
+        raise ValueError(f"observed addresses not visited by the model: {missing}")
+    plan = ops.smc_plan_create(ti.sites, ts.sites, init_state, next_state, len(obs_addrs), guided=True)
+    plan._keep = (ti.keep, ts.keep)
+    plan._tables = (ti.sites, ts.sites)  # the lowered tables (tests and tools read the modes / references from them)
+    plan._state_args = (init_state, next_state)
     return plan, len(init_state)
 
 
