@@ -1508,6 +1508,38 @@ struct PlanPolicyArgs {
   int32_t wt;  // write-through stores of the state / ancestor columns (store16_out; the host sets it for one-filter launches)
 };
 
+// Kernel argument block of one backward-simulation step (include/gjx_backsim.h; the kernels are generated from the
+// transition table, gjx_plan_jit.hpp GenBacksim).  Rows are those of step t; `best` holds one packed running maximum per
+// trajectory, (order-preserving bits of v) << 32 | ~i: a 64-bit unsigned maximum is the first maximiser.
+struct BacksimArgs {
+  const uint32_t* col[4];       // state columns, row t
+  const uint32_t* col_next[4];  // ... row t + 1 (unused by the last step's kernel)
+  const float* lw;              // log-weights, row t
+  const unsigned long long* best_next;  // [m] the winners of step t + 1
+  unsigned long long* best;             // [m] zero before the launch
+  float obs[8];                 // observation row t + 1
+  Key kt;                       // fold_in(key, t): lane 0
+  uint32_t n, m;
+  uint32_t i32_mask;            // bit c: column c holds int32
+  uint32_t vec2;                // every row base above is 8-byte aligned: a lane's two candidates are one load
+  uint32_t chunk;               // candidates per work item (a multiple of 512)
+  uint32_t n_chunks;
+};
+constexpr int kBacksimBlock = 4;  // trajectories a work item walks together over its chunk of candidates
+// v -> a word whose unsigned order is the order `>` gives floats: -0 counts as +0; a NaN — only the value of candidate 0
+// ever stays in a running maximum as one (`v > best || i == 0`) — is above everything.
+GJX_HD unsigned long long backsim_pack(float v, uint32_t i) {
+  uint32_t u = f2u(v);
+  u = u == 0x80000000u ? 0u : u;
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  u = v == v ? u : 0xffffffffu;
+  return ((unsigned long long)u << 32) | (uint32_t)~i;
+}
+GJX_HD uint32_t backsim_index(unsigned long long w, uint32_t n) {  // always a valid index
+  const uint32_t i = ~(uint32_t)w;
+  return i < n ? i : n - 1u;
+}
+
 template <int N>
 struct IntC {
   static constexpr int value = N;

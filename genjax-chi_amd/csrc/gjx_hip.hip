@@ -9,6 +9,7 @@
 // create/destroy.
 #include "../../include/gjx.h"
 #include "../../include/gjx_guided.h"
+#include "../../include/gjx_backsim.h"
 #include "gjx_device.hpp"
 
 #include <hip/hip_runtime.h>
@@ -2109,8 +2110,10 @@ static CArg carg(const gjx_arg& a) { return CArg{a.kind, a.ref, 0, a.ref, a.scal
 // Validate one site and convert it (hoisting per-site constants with the same spec functions).
 // `allow_guided`: the tables of gjx_smc_plan_create_guided, where `observed` may also be GJX_SITE_PROPOSED / GJX_SITE_GUIDED
 // (include/gjx_guided.h); every other creator refuses observed > 1 (it used to read it as "observed").
+// `allow_next`: the tables of gjx_backsim_plan_create, where `obs` may also be {GJX_ARG_NEXT, a carry component, 1, 0}
+// (include/gjx_backsim.h); arg_ok knows no such kind, so it is refused everywhere else.
 static bool convert_site(const gjx_site& st, int s, CSite& c, int n_state = -1, int n_obs = -1,
-                         bool allow_state = false, bool allow_guided = false) {
+                         bool allow_state = false, bool allow_guided = false, bool allow_next = false) {
   if (st.observed > (allow_guided ? GJX_SITE_GUIDED : 1)) return false;
   bool ok = st.dist >= 0 && st.dist <= GJX_DIST_CATEGORICAL && arg_ok(st.arg[0], s, n_state, n_obs, allow_state);
   const bool two_args = st.dist != GJX_DIST_BERNOULLI && st.dist != GJX_DIST_CATEGORICAL;
@@ -2120,7 +2123,9 @@ static bool convert_site(const gjx_site& st, int s, CSite& c, int n_state = -1, 
   } else if (ok && st.observed && st.observed != GJX_SITE_PROPOSED) {
     if (n_state < 0) ok = st.obs.kind == GJX_ARG_CONST || (st.obs.kind == GJX_ARG_INPUT && st.obs.ref >= 0 && st.obs.ref < 16) ||
                           (st.obs.kind == GJX_ARG_PARAM && st.obs.ref >= 0 && st.obs.ref < GJX_MAX_PARAMS);
-    else ok = st.obs.kind == GJX_ARG_CONST || (st.obs.kind == GJX_ARG_OBS && st.obs.ref >= 0 && st.obs.ref < n_obs);
+    else ok = st.obs.kind == GJX_ARG_CONST || (st.obs.kind == GJX_ARG_OBS && st.obs.ref >= 0 && st.obs.ref < n_obs) ||
+              (allow_next && st.obs.kind == GJX_ARG_NEXT && st.obs.ref >= 0 && st.obs.ref < n_state && st.obs.scale == 1.0f &&
+               st.obs.offset == 0.0f);
   }
   if (ok && st.dist == GJX_DIST_CATEGORICAL)
     ok = st.logits && st.n_cat > 0 && st.n_rows > 0 && (st.cat_mode == 0 || st.cat_mode == 1) && st.arg[0].kind != GJX_ARG_EXPR;
@@ -4206,6 +4211,217 @@ int gjx_paths_trace(const gjx_paths_io* io, void* ws, size_t ws_bytes, gjx_strea
   if (io->max_workgroups && grid > io->max_workgroups) grid = io->max_workgroups;
   if (stats) k_paths_trace<true><<<grid, kBlock, 0, S(s)>>>(A);
   else k_paths_trace<false><<<grid, kBlock, 0, S(s)>>>(A);
+  return launch_status();
+}
+
+}  // extern "C"
+
+// =====================================================================================================================
+// Backward-simulation smoothing over a recorded filter history (include/gjx_backsim.h; kernels generated by
+// gjx_plan_jit.hpp GenBacksim)
+// =====================================================================================================================
+struct gjx_backsim_plan {
+  int n_sites, n_state, n_obs;
+  CSite sites[GJX_MAX_SITES];
+  ExprStore expr;  // GJX_ARG_EXPR programs of the table
+  std::vector<void*> dev_owned;  // per-row tables of categorical sites
+  std::mutex mu;
+  struct Kernels {
+    hipFunction_t step = nullptr, last = nullptr;
+    int state = 0;  // 0 untried, 1 ready, -1 failed
+    std::string key;
+    gjx::PlanTables tabs;
+  } jit[2];
+  bool tables_ready = false;
+};
+
+namespace {
+constexpr uint32_t kBacksimLaneCands = 2;                       // adjacent candidates per lane
+constexpr uint32_t kBacksimTrip = kBlock * kBacksimLaneCands;   // candidates a workgroup covers per trip
+constexpr uint32_t kBacksimChunk = 8 * kBacksimTrip;            // candidates per work item
+constexpr unsigned kBacksimMaxGrid = 256 * 16;
+
+inline bool backsim_size_ok(uint64_t v) { return v >= 1 && v < (1ull << 31); }
+
+std::string backsim_source(const gjx_backsim_plan* p, int impl, PlanTables* tabs = nullptr) {
+  gjx_jit::TableScope ts;
+  gjx_jit::GenBacksim<CSite, CArg> g;
+  g.impl = impl; g.sites = p->sites; g.n_sites = p->n_sites; g.n_state = p->n_state;
+  std::string src = g.run();
+  if (tabs) *tabs = ts.reg.tables();
+  return src;
+}
+
+gjx_backsim_plan::Kernels* backsim_compiled(gjx_backsim_plan* p, int impl) {
+  gjx_backsim_plan::Kernels& c = p->jit[impl];
+  if (c.state == 0) {
+    std::lock_guard<std::mutex> lock(p->mu);
+    if (c.state == 0) {
+      if (!p->tables_ready) {  // (the derived tables: once per plan, a GPU is present by now)
+        cat_tables_prepare(p->sites, p->n_sites, &p->dev_owned);
+        p->tables_ready = true;
+      }
+      hipModule_t mod = gjx_jit::ModuleCache::get().acquire(backsim_source(p, impl, &c.tabs), &c.key);
+      bool ok = mod != nullptr;
+      if (ok && (hipModuleGetFunction(&c.step, mod, "gjx_backsim_step_kernel") != hipSuccess ||
+                 hipModuleGetFunction(&c.last, mod, "gjx_backsim_last_kernel") != hipSuccess)) {
+        (void)hipGetLastError();
+        fprintf(stderr, "[gjx] hipModuleGetFunction failed for a generated backward-simulation kernel\n");
+        gjx_jit::ModuleCache::get().release(c.key);
+        c.key.clear();
+        ok = false;
+      }
+      c.state = ok ? 1 : -1;
+    }
+  }
+  return c.state == 1 ? &c : nullptr;
+}
+
+struct BacksimFinishArgs {
+  const unsigned long long* best;  // [T, m]
+  const uint32_t* col[GJX_SMC_MAX_STATE];
+  uint64_t col_stride[GJX_SMC_MAX_STATE];
+  uint32_t* paths[GJX_SMC_MAX_STATE];
+  uint64_t paths_stride[GJX_SMC_MAX_STATE];
+  int32_t* lineage;
+  uint64_t lineage_stride;
+  uint32_t T, n, m, n_cols;
+};
+// lineage[t][j] = the winner of (t, j); path_c[t][j] = col_c[t][winner], copied as 32 bits
+__global__ __launch_bounds__(kBlock) void k_backsim_finish(BacksimFinishArgs a) {
+  const uint64_t total = (uint64_t)a.T * a.m;
+  for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < total; k += (uint64_t)gridDim.x * kBlock) {
+    const uint32_t t = (uint32_t)(k / a.m), j = (uint32_t)(k - (uint64_t)t * a.m);
+    const uint32_t w = backsim_index(a.best[k], a.n);
+    if (a.lineage) a.lineage[(uint64_t)t * a.lineage_stride + j] = (int32_t)w;
+    for (uint32_t c = 0; c < a.n_cols; ++c)
+      if (a.paths[c]) a.paths[c][(uint64_t)t * a.paths_stride[c] + j] = a.col[c][(uint64_t)t * a.col_stride[c] + w];
+  }
+}
+}  // namespace
+
+extern "C" {
+
+int gjx_backsim_version(int* major, int* minor) {
+  if (major) *major = GJX_BACKSIM_VERSION_MAJOR;
+  if (minor) *minor = GJX_BACKSIM_VERSION_MINOR;
+  return GJX_OK;
+}
+int gjx_backsim_plan_create(const gjx_site* sites, int n_sites, int n_state, int n_obs, uint32_t flags,
+                            gjx_backsim_plan** out) {
+  if (!sites || !out || n_sites < 1 || n_sites > GJX_MAX_SITES || n_state < 1 || n_state > GJX_SMC_MAX_STATE || n_obs < 0 ||
+      n_obs > GJX_SMC_MAX_OBS || flags != 0u)
+    return GJX_ERR_INVALID;
+  gjx_backsim_plan* p = new (std::nothrow) gjx_backsim_plan;
+  if (!p) return GJX_ERR_LAUNCH;
+  p->n_sites = n_sites; p->n_state = n_state; p->n_obs = n_obs;
+  bool ok = true;
+  for (int s = 0; ok && s < n_sites; ++s)
+    ok = sites[s].observed == 1 && convert_site(sites[s], s, p->sites[s], n_state, n_obs, true, false, true);
+  if (!ok) {
+    delete p;
+    return GJX_ERR_INVALID;
+  }
+  expr_adopt(p->sites, n_sites, &p->expr);
+  *out = p;
+  return GJX_OK;
+}
+int gjx_backsim_plan_destroy(gjx_backsim_plan* p) {
+  if (!p) return GJX_OK;
+  for (auto& c : p->jit) gjx_jit::ModuleCache::get().release(c.key);
+  free_owned(p->dev_owned);
+  delete p;
+  return GJX_OK;
+}
+int gjx_backsim_plan_source(const gjx_backsim_plan* p, int impl, char* buf, size_t buf_len, size_t* needed) {
+  if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
+  const std::string src = backsim_source(p, impl);
+  if (needed) *needed = src.size() + 1;
+  if (buf && buf_len > 0) {
+    const size_t k = src.size() < buf_len - 1 ? src.size() : buf_len - 1;
+    memcpy(buf, src.data(), k);
+    buf[k] = 0;
+  }
+  return GJX_OK;
+}
+int gjx_backsim_plan_compile_check(const gjx_backsim_plan* p, int impl) {
+  if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
+  return gjx_jit::compile_only(backsim_source(p, impl)) ? GJX_OK : GJX_ERR_UNSUPPORTED;
+}
+size_t gjx_backsim_workspace_bytes(int32_t n_steps, uint64_t m) {
+  if (n_steps < 1 || !backsim_size_ok(m)) return 0;
+  return (size_t)n_steps * (size_t)m * sizeof(unsigned long long);
+}
+int gjx_backsim_run(gjx_backsim_plan* p, const gjx_backsim_io* io, void* ws, size_t ws_bytes, gjx_stream s) {
+  if (!p || !io || io->n_steps < 1 || !backsim_size_ok(io->n) || !backsim_size_ok(io->m) || (io->impl != 0 && io->impl != 1) ||
+      (io->impl == 0 && io->key_lane != 0))
+    return GJX_ERR_INVALID;
+  const uint32_t T = (uint32_t)io->n_steps, n = (uint32_t)io->n, m = (uint32_t)io->m;
+  if (!io->logw || io->logw_stride < io->n || io->logw_stride >= (1ull << 32) || (p->n_obs > 0 && !io->obs)) return GJX_ERR_INVALID;
+  bool any_out = io->lineage_out != nullptr;
+  if (io->lineage_out && (io->lineage_stride < io->m || io->lineage_stride >= (1ull << 32))) return GJX_ERR_INVALID;
+  BacksimFinishArgs F{};
+  uint32_t i32_mask = 0;
+  for (int c = 0; c < p->n_state; ++c) {
+    if (!io->cols[c] || io->col_stride[c] < io->n || io->col_stride[c] >= (1ull << 32)) return GJX_ERR_INVALID;
+    if (io->paths_out[c] && (io->paths_stride[c] < io->m || io->paths_stride[c] >= (1ull << 32))) return GJX_ERR_INVALID;
+    any_out = any_out || io->paths_out[c];
+    F.col[c] = reinterpret_cast<const uint32_t*>(io->cols[c]);
+    F.col_stride[c] = io->col_stride[c];
+    F.paths[c] = reinterpret_cast<uint32_t*>(io->paths_out[c]);
+    F.paths_stride[c] = io->paths_stride[c];
+    if (io->col_is_i32[c]) i32_mask |= 1u << c;
+  }
+  if (!any_out || ((uintptr_t)ws & 7) != 0) return GJX_ERR_INVALID;
+  if (!ws || ws_bytes < gjx_backsim_workspace_bytes(io->n_steps, io->m)) return GJX_ERR_WORKSPACE;
+  if (!gjx_jit::enabled()) return GJX_ERR_UNSUPPORTED;  // generated kernels only, as guided plans
+  gjx_backsim_plan::Kernels* k = backsim_compiled(p, io->impl);
+  if (!k) return GJX_ERR_JIT;
+
+  unsigned long long* best = reinterpret_cast<unsigned long long*>(ws);
+  if (hipMemsetAsync(best, 0, (size_t)T * m * sizeof(unsigned long long), S(s)) != hipSuccess) return GJX_ERR_LAUNCH;
+  const Key key{io->key[0], io->key[1], (uint32_t)io->key_lane, (uint32_t)(io->key_lane >> 32)};
+  const uint32_t n_chunks = (n + kBacksimChunk - 1) / kBacksimChunk;
+  const uint64_t items = (uint64_t)((m + kBacksimBlock - 1) / kBacksimBlock) * n_chunks;
+  unsigned grid = (unsigned)(items < kBacksimMaxGrid ? items : kBacksimMaxGrid);
+  if (io->max_workgroups && grid > io->max_workgroups) grid = io->max_workgroups;
+  for (uint32_t t = T; t-- > 0;) {
+    BacksimArgs A;
+    memset(&A, 0, sizeof A);
+    const bool last = t == T - 1;
+    uintptr_t al = 0;
+    for (int c = 0; c < p->n_state; ++c) {
+      A.col[c] = F.col[c] + (uint64_t)t * F.col_stride[c];
+      A.col_next[c] = last ? nullptr : F.col[c] + (uint64_t)(t + 1) * F.col_stride[c];
+      al |= (uintptr_t)A.col[c];
+    }
+    A.lw = io->logw + (uint64_t)t * io->logw_stride;
+    al |= (uintptr_t)A.lw;
+    A.best_next = last ? nullptr : best + (uint64_t)(t + 1) * m;
+    A.best = best + (uint64_t)t * m;
+    if (!last)
+      for (int c = 0; c < p->n_obs; ++c) A.obs[c] = io->obs[(size_t)(t + 1) * (size_t)p->n_obs + c];
+    A.kt = io->impl == 0 ? fold_in<0>(key, t) : fold_in<1>(key, t);
+    A.n = n; A.m = m;
+    A.i32_mask = i32_mask;
+    A.vec2 = (al & 7) == 0 ? 1u : 0u;
+    A.chunk = kBacksimChunk;
+    A.n_chunks = n_chunks;
+    PlanTables tabs = k->tabs;
+    void* args[] = {&A, &tabs};
+    if (hipModuleLaunchKernel(last ? k->last : k->step, grid, 1, 1, kBlock, 1, 1, 0, S(s), args, nullptr) != hipSuccess) {
+      (void)hipGetLastError();
+      return GJX_ERR_LAUNCH;
+    }
+  }
+  F.best = best;
+  F.lineage = io->lineage_out;
+  F.lineage_stride = io->lineage_stride;
+  F.T = T; F.n = n; F.m = m; F.n_cols = (uint32_t)p->n_state;
+  const uint64_t fb = ((uint64_t)T * m + kBlock - 1) / kBlock;
+  unsigned fgrid = (unsigned)(fb < 4096 ? fb : 4096);
+  if (io->max_workgroups && fgrid > io->max_workgroups) fgrid = io->max_workgroups;
+  k_backsim_finish<<<fgrid, kBlock, 0, S(s)>>>(F);
   return launch_status();
 }
 

@@ -332,6 +332,7 @@ struct SiteEmitter {
         ov = in_support ? flit(v) : flit_opaque(v);
       }
       else if (st.obs.kind == GJX_ARG_OBS) ov = "a.obs[" + std::to_string(st.obs.ref) + "]";
+      else if (st.obs.kind == GJX_ARG_NEXT) ov = "nx_" + std::to_string(st.obs.ref);  // (transition tables: gjx_backsim.h)
       else if (st.obs.kind == GJX_ARG_PARAM) ov = arg(st.obs);
       else ov = "cols.in[" + std::to_string(st.obs.ref) + "][li" + sfx + "]";
       if (is_int(st)) o << ind << "const int32_t vi" << Q << " = (int32_t)__builtin_rintf(" << ov << ");\n";
@@ -1161,6 +1162,96 @@ struct GenSmc {
       o << "          if (a.anc_out) a.anc_out[loc + u] = (int32_t)j;\n        }\n    }\n  }\n";
     }
     o << "  emit_init_tile(wq, okq, em, loc, first_slot / kTile + ltile);\n}\n";
+    return o.str();
+  }
+};
+
+// The kernels of a backward-simulation plan (include/gjx_backsim.h).  The transition table becomes ONE device function,
+// trans_lp(state of candidate i, next state of trajectory j) -> the f32 sum of the table's log-densities, emitted by
+// SiteEmitter exactly as an SMC step's weight is (mode 1: st_<k>, a.obs[]; nx_<c> for GJX_ARG_NEXT).  Around it:
+//   lanes over candidates, two adjacent ones per lane (8-byte loads of state and log-weight, once per work item);
+//   a work item = kBacksimBlock trajectories x one chunk of candidates: the trajectories' keys and next-state values are
+//   wave-uniform (scalar registers), each lane keeps (best value, best index) per trajectory and candidate order is
+//   ascending inside a lane, so `v > best || i == 0` is the oracle's own scan there;
+//   at the end of the item one DPP wave maximum per trajectory over the packed word (gjx_device.hpp backsim_pack) and one
+//   64-bit atomic maximum per wave and trajectory: order-free and exact.
+// A trajectory index past m is clamped to m - 1: its (identical) maxima change nothing.
+template <class CSiteT, class CArgT>
+struct GenBacksim {
+  std::ostringstream o;
+  int impl;
+  const CSiteT* sites;
+  int n_sites;
+  int n_state;
+
+  std::string run() {
+    const std::string I = std::to_string(impl);
+    emit_prelude(o);
+    std::string st_params, st_args_a, st_args_b, nx_params, nx_args;
+    for (int k = 0; k < n_state; ++k) {
+      const std::string K = std::to_string(k);
+      st_params += ", float st_" + K;
+      nx_params += ", float nx_" + K;
+      st_args_a += ", sa[" + K + "]";
+      st_args_b += ", sb[" + K + "]";
+      nx_args += ", nx[u][" + K + "]";
+    }
+    o << "__device__ __forceinline__ float trans_lp(const BacksimArgs& a, const PlanTables& tabs" << st_params << nx_params << ") {\n";
+    for (int k = 0; k < n_state; ++k) o << "  (void)st_" << k << "; (void)nx_" << k << ";\n";
+    o << "  float w = 0.0f, sc = 0.0f;\n";
+    SiteEmitter<CSiteT, CArgT> e{o, impl, 1, sites, n_sites, "  ", ""};
+    e.run();
+    o << "  (void)sc;\n  return w;\n}\n";
+    o << "constexpr int D = " << n_state << ", JB = kBacksimBlock;\n";
+    o << "__device__ __forceinline__ float bs_col(uint32_t bits, bool is_i32) { return is_i32 ? (float)(int32_t)bits : u2f(bits); }\n";
+    o << "template <bool LAST>\n__device__ __forceinline__ void backsim_body(const BacksimArgs& a, const PlanTables& tabs) {\n";
+    o << "  const uint32_t n = a.n, m = a.m;\n";
+    o << "  const uint32_t n_tb = (m + JB - 1) / JB;\n";
+    o << "  const uint64_t items = (uint64_t)n_tb * a.n_chunks;\n";
+    o << "  for (uint64_t it = blockIdx.x; it < items; it += gridDim.x) {\n";
+    o << "    const uint32_t tb = (uint32_t)(it / a.n_chunks), cc = (uint32_t)(it - (uint64_t)tb * a.n_chunks);\n";
+    o << "    Key tk[JB];\n    float nx[JB][D];\n    uint32_t tj[JB];\n";
+    o << "#pragma unroll\n    for (int u = 0; u < JB; ++u) {\n";
+    o << "      const uint32_t j = tb * JB + u < m ? tb * JB + u : m - 1u;\n";
+    o << "      tj[u] = j;\n      tk[u] = split_at<" << I << ">(a.kt, (uint64_t)j);\n";
+    o << "      for (int c = 0; c < D; ++c) nx[u][c] = 0.0f;\n";
+    o << "      if (!LAST) {\n        const uint32_t w = backsim_index(a.best_next[j], n);\n";
+    o << "        for (int c = 0; c < D; ++c) nx[u][c] = bs_col(a.col_next[c][w], (a.i32_mask >> c) & 1u);\n      }\n";
+    o << "    }\n";
+    o << "    float bv[JB];\n    uint32_t bi[JB];\n";
+    o << "#pragma unroll\n    for (int u = 0; u < JB; ++u) { bv[u] = -__builtin_inff(); bi[u] = 0x7fffffffu; }\n";
+    o << "    const uint64_t c0 = (uint64_t)cc * a.chunk;\n";
+    o << "    const uint64_t c1 = c0 + a.chunk < n ? c0 + a.chunk : n;\n";
+    o << "    for (uint64_t i64 = c0 + 2u * threadIdx.x; i64 < c1; i64 += 2u * blockDim.x) {\n";
+    o << "      const uint32_t i = (uint32_t)i64;\n";
+    o << "      const bool hasb = i + 1u < n;\n";
+    o << "      float sa[D], sb[D], lwa, lwb;\n";
+    o << "      if (a.vec2 && hasb) {\n";
+    o << "        const uint2 l2 = *reinterpret_cast<const uint2*>(a.lw + i);\n        lwa = u2f(l2.x); lwb = u2f(l2.y);\n";
+    o << "        for (int c = 0; c < D; ++c) {\n          const uint2 v2 = *reinterpret_cast<const uint2*>(a.col[c] + i);\n";
+    o << "          sa[c] = bs_col(v2.x, (a.i32_mask >> c) & 1u); sb[c] = bs_col(v2.y, (a.i32_mask >> c) & 1u);\n        }\n";
+    o << "      } else {\n";
+    o << "        lwa = a.lw[i]; lwb = hasb ? a.lw[i + 1u] : -__builtin_inff();\n";
+    o << "        for (int c = 0; c < D; ++c) {\n          sa[c] = bs_col(a.col[c][i], (a.i32_mask >> c) & 1u);\n";
+    o << "          sb[c] = hasb ? bs_col(a.col[c][i + 1u], (a.i32_mask >> c) & 1u) : sa[c];\n        }\n";
+    o << "      }\n";
+    o << "      const bool first = i == 0u;\n";
+    o << "#pragma unroll\n      for (int u = 0; u < JB; ++u) {\n";
+    o << "        const Stream<" << I << "> ds(tk[u], false, 0u);\n";
+    o << "        const float la = LAST ? lwa : lwa + trans_lp(a, tabs" << st_args_a << nx_args << ");\n";
+    o << "        const float lb = LAST ? lwb : lwb + trans_lp(a, tabs" << st_args_b << nx_args << ");\n";
+    o << "        const float va = la + gumbel_from_bits(ds.bits32(i));\n";
+    o << "        const float vb = lb + gumbel_from_bits(ds.bits32(i + 1u));\n";
+    o << "        if (va > bv[u] || first) { bv[u] = va; bi[u] = i; }\n";
+    o << "        if (hasb && vb > bv[u]) { bv[u] = vb; bi[u] = i + 1u; }\n";
+    o << "      }\n    }\n";
+    o << "#pragma unroll\n    for (int u = 0; u < JB; ++u) {\n";
+    o << "      const unsigned long long w = wave_last_u64(wave_scan_u64(backsim_pack(bv[u], bi[u]), 0ull,\n";
+    o << "          [](uint64_t x, uint64_t y) { return x > y ? x : y; }));\n";
+    o << "      if ((threadIdx.x & 63u) == 0u) atomicMax(a.best + tj[u], w);\n";
+    o << "    }\n  }\n}\n";
+    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_backsim_step_kernel(BacksimArgs a, PlanTables tabs) { backsim_body<false>(a, tabs); }\n";
+    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_backsim_last_kernel(BacksimArgs a, PlanTables tabs) { backsim_body<true>(a, tabs); }\n";
     return o.str();
   }
 };

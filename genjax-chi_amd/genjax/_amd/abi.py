@@ -75,6 +75,15 @@ class GuidedUnavailable(GjxError):
         self.code = -2
 
 
+class BacksimUnavailable(GjxError):
+    """An entry point of include/gjx_backsim.h called on a library that does not export it (GJX_ERR_UNSUPPORTED)."""
+
+    def __init__(self, fn: str, backend: str):
+        RuntimeError.__init__(self, f"{fn}: the library '{backend}' does not implement include/gjx_backsim.h "
+                                    "(libgjx_hip.so does; backward simulation runs as generated HIP kernels only)")
+        self.code = -2
+
+
 class Keys(C.Structure):
     _fields_ = [
         ("impl", C.c_int32),
@@ -486,7 +495,46 @@ GUIDED_PROTOTYPES = {
 }
 GUIDED_ABI_VERSION = (0, 1)
 
+# include/gjx_backsim.h: a FOURTH header, same arrangement — backward-simulation smoothing over a recorded history
+ARG_NEXT = 8  # gjx_backsim.h: GJX_ARG_NEXT (Arg.kind, in Site.obs of a transition table)
+
+
+class BacksimIO(C.Structure):
+    """gjx_backsim_io (include/gjx_backsim.h)."""
+    _fields_ = [
+        ("n_steps", C.c_int32),
+        ("impl", C.c_int32),
+        ("n", C.c_uint64),
+        ("m", C.c_uint64),
+        ("key", C.c_uint32 * 2),
+        ("key_lane", C.c_uint64),
+        ("cols", C.c_void_p * SMC_MAX_STATE),
+        ("col_stride", C.c_uint64 * SMC_MAX_STATE),
+        ("col_is_i32", C.c_int32 * SMC_MAX_STATE),
+        ("logw", C.c_void_p),
+        ("logw_stride", C.c_uint64),
+        ("obs", C.c_void_p),
+        ("lineage_out", C.c_void_p),
+        ("lineage_stride", C.c_uint64),
+        ("paths_out", C.c_void_p * SMC_MAX_STATE),
+        ("paths_stride", C.c_uint64 * SMC_MAX_STATE),
+        ("max_workgroups", C.c_uint32),
+    ]
+
+
+BACKSIM_PROTOTYPES = {
+    "gjx_backsim_version": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gjx_backsim_plan_create": (C.c_int, [C.POINTER(Site), C.c_int, C.c_int, C.c_int, C.c_uint32, C.POINTER(_P)]),
+    "gjx_backsim_plan_destroy": (C.c_int, [_P]),
+    "gjx_backsim_plan_source": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gjx_backsim_plan_compile_check": (C.c_int, [_P, C.c_int]),
+    "gjx_backsim_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_uint64]),
+    "gjx_backsim_run": (C.c_int, [_P, C.POINTER(BacksimIO), _P, C.c_size_t, _P]),
+}
+BACKSIM_ABI_VERSION = (0, 1)
+
 _NO_STATUS = {
+    "gjx_backsim_workspace_bytes",
     "gjx_paths_workspace_bytes",
     "gjx_backend_name",
     "gjx_workspace_bytes",
@@ -574,7 +622,25 @@ class GjxLib:
                 fn.argtypes = args
                 setattr(self, "_" + name, fn)
 
+        # include/gjx_backsim.h: likewise
+        self.has_backsim = hasattr(self._dll, "gjx_backsim_version")
+        if self.has_backsim:
+            vfn = self._dll.gjx_backsim_version
+            vfn.restype, vfn.argtypes = BACKSIM_PROTOTYPES["gjx_backsim_version"]
+            vfn(C.byref(major), C.byref(minor))
+            if (major.value, minor.value) != BACKSIM_ABI_VERSION:
+                raise AbiVersionMismatch(
+                    f"{path} implements gjx_backsim.h {major.value}.{minor.value}; these bindings are written for "
+                    f"{BACKSIM_ABI_VERSION[0]}.{BACKSIM_ABI_VERSION[1]}: rebuild the library from this tree")
+            for name, (res, args) in BACKSIM_PROTOTYPES.items():
+                fn = getattr(self._dll, name)
+                fn.restype = res
+                fn.argtypes = args
+                setattr(self, "_" + name, fn)
+
     def call(self, name: str, *args):
+        if name in BACKSIM_PROTOTYPES and not self.has_backsim:
+            raise BacksimUnavailable(name, self.name)
         if name in PATHS_PROTOTYPES and not self.has_paths:
             raise PathsUnavailable(name, self.name)
         if name in GUIDED_PROTOTYPES and not self.has_guided:

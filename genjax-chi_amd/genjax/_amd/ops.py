@@ -497,6 +497,64 @@ class Ops:
         self.lib.call("gjx_paths_trace", C.byref(io), self._p(ws), nb, self.stream())
         return out
 
+    # ---- backward-simulation smoothing over a recorded history (include/gjx_backsim.h) -------------
+    def backsim_plan_create(self, table) -> "BacksimPlan":
+        """`table`: a smc_plan.TransitionTable.  Raises abi.BacksimUnavailable on a library without include/gjx_backsim.h
+        (the CPU oracle), before any table it would misread is handed over."""
+        if not self.lib.has_backsim:
+            raise abi.BacksimUnavailable("gjx_backsim_plan_create", self.lib.name)
+        arr = (abi.Site * max(1, len(table.sites)))(*table.sites)
+        handle = C.c_void_p()
+        self.lib.call("gjx_backsim_plan_create", arr, len(table.sites), table.n_state, table.n_obs, 0, C.byref(handle))
+        plan = BacksimPlan(self, handle, table.n_state, table.n_obs)
+        plan._keep = table.keep  # device tables the plan's sites point into
+        return plan
+
+    def backsim_run(self, plan: "BacksimPlan", key, cols: list, logw: torch.Tensor, obs, m: int, *, lineage: bool = True,
+                    paths: bool = True, max_workgroups: int = 0) -> dict:
+        """gjx_backsim_run: ONE call enqueues the backward pass over the history `cols` (4-byte [T, n] columns, float32 or
+        int32) / `logw` f32[T, n] — row-strided views (`[:, :n]` of a padded buffer) are taken as they are — for `m`
+        trajectories under the scalar `key` (a prng.PRNGKey).  `obs`: host [T, n_obs] observation rows (None for a plan
+        without).  -> dict(lineage int32[T, m], paths [col dtype [T, m]]), each None unless asked for."""
+        import numpy as np
+
+        if not self.lib.has_backsim:
+            raise abi.BacksimUnavailable("gjx_backsim_run", self.lib.name)
+        if len(cols) != plan.n_state:
+            raise ValueError(f"backsim_run: the plan has {plan.n_state} state columns, got {len(cols)}")
+        if logw.dim() != 2 or logw.dtype != torch.float32 or logw.stride(1) != 1 or logw.device.type != self.device_type:
+            raise ValueError("backsim_run: logw must be a float32 [T, n] device tensor with contiguous rows")
+        T, n = logw.shape
+        io = abi.BacksimIO()
+        io.n_steps, io.impl, io.n, io.m = T, key.impl, n, int(m)
+        io.key[0], io.key[1], io.key_lane = key.k0, key.k1, key.lane
+        io.logw, io.logw_stride = logw.data_ptr(), logw.stride(0) if T > 1 else n
+        out = dict(lineage=None, paths=None)
+        if lineage:
+            out["lineage"] = self.empty((T, m), torch.int32)
+            io.lineage_out, io.lineage_stride = out["lineage"].data_ptr(), m
+        if paths:
+            out["paths"] = []
+        for c, col in enumerate(cols):
+            if (col.shape != (T, n) or col.dtype not in (torch.float32, torch.int32) or col.stride(1) != 1
+                    or col.device.type != self.device_type):
+                raise ValueError("backsim_run: columns must be float32 / int32 [T, n] device tensors with contiguous rows")
+            io.cols[c], io.col_stride[c] = col.data_ptr(), col.stride(0) if T > 1 else n
+            io.col_is_i32[c] = 1 if col.dtype == torch.int32 else 0
+            if paths:
+                o = self.empty((T, m), col.dtype)
+                out["paths"].append(o)
+                io.paths_out[c], io.paths_stride[c] = o.data_ptr(), m
+        y = None
+        if plan.n_obs:
+            y = np.ascontiguousarray(np.asarray(obs, dtype=np.float32).reshape(T, -1)[:, :plan.n_obs])
+            io.obs = y.ctypes.data
+        nb = int(self.lib.call("gjx_backsim_workspace_bytes", T, int(m)))
+        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=self._alloc_device)  # (per call: see workspace())
+        io.max_workgroups = int(max_workgroups)
+        self.lib.call("gjx_backsim_run", plan.handle, C.byref(io), self._p(ws), nb, self.stream())
+        return out
+
     # ---- fused SMC --------------------------------------------------------------------------------
     def smc_config(self, impl, n_total, first, n_local, step_keys, resample_keys, ess_threshold: float = 0.0):
         """Config of a whole-run call or of the step-level entry points (`first`, `n_local`: a rank's own block).
@@ -840,6 +898,31 @@ class SmcPlan:
         try:
             if self.handle:
                 self.ops.lib.call("gjx_smc_plan_destroy", self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+class BacksimPlan:
+    """A gjx_backsim_plan (include/gjx_backsim.h): the generated kernels of one transition table."""
+
+    def __init__(self, ops: "Ops", handle, n_state: int, n_obs: int):
+        self.ops, self.handle, self.n_state, self.n_obs = ops, handle, n_state, n_obs
+
+    def compile_check(self, impl: int) -> int:
+        return self.ops.lib._gjx_backsim_plan_compile_check(self.handle, impl)
+
+    def source(self, impl: int) -> str:
+        need = C.c_size_t()
+        self.ops.lib.call("gjx_backsim_plan_source", self.handle, impl, None, 0, C.byref(need))
+        buf = C.create_string_buffer(need.value)
+        self.ops.lib.call("gjx_backsim_plan_source", self.handle, impl, buf, need.value, None)
+        return buf.value.decode()
+
+    def __del__(self):
+        try:
+            if self.handle:
+                self.ops.lib.call("gjx_backsim_plan_destroy", self.handle)
                 self.handle = None
         except Exception:
             pass

@@ -130,9 +130,13 @@ def _columns(cols):
     return cols[0] if len(cols) == 1 else tuple(cols)
 
 
+def _obs_addrs(observations: ChoiceMap) -> list:
+    return [a for a, _ in observations.leaves()]
+
+
 def _build_plan(ops, model: StateSpaceModel, observations: ChoiceMap):
     """-> (SmcPlan, observation matrix [T, n_obs]) of a user-written model and its observed sequences."""
-    addrs = [a for a, _ in observations.leaves()]
+    addrs = _obs_addrs(observations)
     with use_ops(ops):
         plan, _ = build_smc_plan(model, addrs)
     return plan, observation_matrix(observations, addrs)
@@ -150,7 +154,7 @@ def _bind_model(ops, model, observations, plan=None):
         return HmmFilter(ops, int(tl.shape[0]), int(model.init_state), tl, ol, observations)
     if isinstance(model, StateSpaceModel):
         plan, obs = plan or _build_plan(ops, model, observations)
-        return PlanFilter(ops, plan, obs)
+        return PlanFilter(ops, plan, obs, source=(model, _obs_addrs(observations)))
     raise TypeError(f"no fused SMC kernel for {type(model).__name__}")
 
 
@@ -220,6 +224,7 @@ class BootstrapSMC:
         self.record_history = bool(record_history)
         self.ess_threshold = float(ess_threshold)
         self._plan = None  # (SmcPlan, observation matrix) of a StateSpaceModel, built at the first run
+        self._transition = None  # (BacksimPlan, observation rows) of `backward_simulate`, built at its first call
         if isinstance(model, StateSpaceModel) and not isinstance(observations, ChoiceMap):
             raise TypeError("observations for a StateSpaceModel are a ChoiceMap of length-T sequences")
         self.observations = observations if isinstance(observations, ChoiceMap) else np.asarray(observations)
@@ -241,6 +246,39 @@ class BootstrapSMC:
             return _history_run(ops, model, self.n, key, self.ess_threshold)
         sk, rk = smc_key_schedule(key, model.T)
         return _result(ops, self.n, ops._smc_run(model, key.impl, self.n, sk, rk, self.record_ancestors, self.ess_threshold))
+
+    def backward_simulate(self, result: SMCResult, key: prng.PRNGKey, n_paths: int, max_workgroups: int = 0) -> "Trajectories":
+        """Backward-simulation smoothing: `n_paths` trajectories x_0:T-1, each drawn afresh from the recorded
+        populations of `result` (a `record_history=True` run of THIS filter) — x_T-1 from the final weights, then x_t from
+        all n particles of step t with weights w_t^i f(x_t+1 | x_t^i) — in one library call of T + 1 stream-ordered launches
+        (gjx_backsim_run; no [n_paths, n] array exists anywhere).  Unlike `SMCResult.trajectories` it does not follow the
+        genealogy, so early steps keep as many distinct particles as the weights allow.  Equally weighted paths:
+        `mean()` / `var()` are smoothing moments; the lineage rows are not ordered.
+
+        The transition density is the model's own (`GuidedSMC`: the underlying StateSpaceModel's; proposals play no part).
+        `PlanUnsupported` when the carry is not exactly the step's latent draws (a degenerate transition);
+        `abi.BacksimUnavailable` on a library without include/gjx_backsim.h; `ValueError` without recorded history."""
+        if result.history is None or result.log_weight_history is None:
+            raise ValueError("backward_simulate() needs the per-step states: run the filter with BootstrapSMC(..., record_history=True)")
+        ops = get_ops()
+        if not ops.lib.has_backsim:
+            raise abi.BacksimUnavailable("gjx_backsim_run", ops.lib.name)
+        if self._transition is None:
+            table, obs = self._bind(ops).transition_table()
+            self._transition = (ops.backsim_plan_create(table), obs)
+        plan, obs = self._transition
+        cols = list(result.history) if isinstance(result.history, tuple) else [result.history]
+        m = int(n_paths)
+        out = ops.backsim_run(plan, key, cols, result.log_weight_history, obs, m, max_workgroups=max_workgroups)
+        paths, lin = out["paths"], out["lineage"]
+        # float64 moments and distinct counts from the returned columns (T m elements: small against the n m T pass)
+        is_f32 = [c.dtype == torch.float32 for c in paths]
+        zero = torch.zeros(lin.shape[0], dtype=torch.float64, device=lin.device)
+        sums = torch.stack([p.double().sum(1) if f else zero for p, f in zip(paths, is_f32)])
+        sumsq = torch.stack([(p.double() * p.double()).sum(1) if f else zero for p, f in zip(paths, is_f32)])
+        srt = lin.sort(dim=1).values
+        unique = 1 + (srt[:, 1:] != srt[:, :-1]).sum(1)
+        return Trajectories(_columns(paths), lin, unique.to(torch.int64), None, None, sums, sumsq, is_f32)
 
     def run_many(self, keys) -> list:
         """`vmap(self.run)(keys)`: one independent filter per key.  Up to 16 filters step in the same kernel launches
@@ -312,4 +350,4 @@ class GuidedSMC(BootstrapSMC):
             with use_ops(ops):
                 plan, _ = build_guided_plan(self.model, addrs, self.step_proposal, self.init_proposal)
             self._plan = (plan, observation_matrix(self.observations, addrs))
-        return PlanFilter(ops, *self._plan)
+        return PlanFilter(ops, *self._plan, source=(self.model, _obs_addrs(self.observations)))

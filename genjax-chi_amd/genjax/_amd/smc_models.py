@@ -6,7 +6,9 @@ filters of dist.py) are written once against `state_dtypes`, `y` (host observati
 
     run(cfg, outputs)                                     gjx_smc_run_*            (outputs: Ops._smc_buffers)
     step(cfg, t, prev, out, prev_e, prev_q, ancestors)    gjx_smc_*_step
-    sharded_run(comm, cfg, io)                            gjx_smc_sharded_run_*"""
+    sharded_run(comm, cfg, io)                            gjx_smc_sharded_run_*
+    transition_table()                                    f(x_t+1 | x_t) as a site table (include/gjx_backsim.h;
+                                                          smc_plan.TransitionTable) and the observation rows that go with it"""
 
 from __future__ import annotations
 
@@ -36,6 +38,17 @@ class LgssmFilter:
 
     def step(self, cfg, t, prev, out, prev_e, prev_q, ancestors):
         self.ops.smc_lgssm_step(cfg, self.model, t, float(self.y[t]), prev, out, prev_e, prev_q, ancestors)
+
+    def transition_table(self):
+        """`normal(a * x, q) @ "x"` constrained to the next state: what a user-written LGSSM lowers to."""
+        from .smc_plan import TransitionTable
+
+        site = abi.Site()
+        site.dist, site.observed, site.out_col = abi.DIST_NORMAL, 1, -1
+        site.arg[0] = abi.Arg(abi.ARG_STATE, 0, self.model.a, 0.0, None)
+        site.arg[1] = abi.Arg(abi.ARG_CONST, 0, 0.0, self.model.q, None)
+        site.obs = abi.Arg(abi.ARG_NEXT, 0, 1.0, 0.0, None)
+        return TransitionTable([site], 1, 0), None
 
     def sharded_run(self, comm, cfg, io):
         self.ops.lib.call("gjx_smc_sharded_run_lgssm", comm.handle, C.byref(cfg), C.byref(self.model),
@@ -68,6 +81,20 @@ class HmmFilter:
         alias, logp = self.tables
         self.ops.smc_hmm_step(cfg, self.model, t, int(self.y[t]), prev, out, alias, logp, prev_e, prev_q, ancestors)
 
+    def transition_table(self):
+        """`categorical(logits=T[z]) @ "z"` constrained to the next state: row = the state, value = the next one (the generated
+        kernel reads the transposed log-probability table the plan machinery derives for such a site)."""
+        from .smc_plan import TransitionTable
+
+        K = int(self.model.n_states)
+        site = abi.Site()
+        site.dist, site.observed, site.out_col = abi.DIST_CATEGORICAL, 1, -1
+        site.n_cat, site.n_rows, site.cat_mode = K, K, 0
+        site.arg[0] = abi.Arg(abi.ARG_STATE, 0, 1.0, 0.0, None)
+        site.obs = abi.Arg(abi.ARG_NEXT, 0, 1.0, 0.0, None)
+        site.logits = self.model.trans_logits
+        return TransitionTable([site], 1, 0, (self.model,)), None
+
     def sharded_run(self, comm, cfg, io):
         o = self.ops
         alias, logp = self.tables
@@ -78,9 +105,11 @@ class HmmFilter:
 class PlanFilter:
     workspace_per_filter = False  # F filters in one call: one workspace of F * stride particles
 
-    def __init__(self, ops, plan, obs):
-        """`plan`: an SmcPlan (Ops.smc_plan_create); `obs`: the [T, n_obs] observation constants ([T] for a plan without)."""
+    def __init__(self, ops, plan, obs, source=None):
+        """`plan`: an SmcPlan (Ops.smc_plan_create); `obs`: the [T, n_obs] observation constants ([T] for a plan without);
+        `source`: (StateSpaceModel, observed addresses) the plan was lowered from — what `transition_table` lowers again."""
         self.ops, self.plan, self.state_dtypes = ops, plan, [torch.float32] * plan.n_state
+        self.source = source
         self.y = np.ascontiguousarray(np.asarray(obs, dtype=np.float32).reshape(-1, max(plan.n_obs, 1))[:, :plan.n_obs])
         self.T = len(self.y)
         self._obs = C.c_void_p(self.y.ctypes.data) if plan.n_obs else None
@@ -94,6 +123,15 @@ class PlanFilter:
 
     def step(self, cfg, t, prev, out, prev_e, prev_q, ancestors):
         self.ops.smc_plan_step(cfg, self.plan, t, self.y[t], prev, out, prev_e, prev_q, ancestors)
+
+    def transition_table(self):
+        from .runtime import use_ops
+        from .smc_plan import build_transition_table
+
+        if self.source is None:
+            raise ValueError("this plan filter was not bound from a StateSpaceModel: no transition to lower")
+        with use_ops(self.ops):
+            return build_transition_table(*self.source), (self.y if self.plan.n_obs else None)
 
     def sharded_run(self, comm, cfg, io):
         self.ops.lib.call("gjx_smc_sharded_run_plan", comm.handle, C.byref(cfg), self.plan.handle, self._obs, C.byref(io),

@@ -236,6 +236,97 @@ def build_guided_plan(model: StateSpaceModel, obs_addrs: list[tuple], step_propo
     return plan, len(init_state)
 
 
+# ---- the transition table of a backward-simulation smoother (include/gjx_backsim.h) --------------------------------
+@dataclass
+class TransitionTable:
+    """f(x_{t+1} | x_t) of a state-space model as a site table: every site constrained — a latent site of the step to
+    "next-state component c" (`abi.ARG_NEXT`), an observed one to its observation.  `Ops.backsim_plan_create` takes it."""
+    sites: list  # [abi.Site]
+    n_state: int
+    n_obs: int
+    keep: tuple = ()  # device tensors and expression programs the sites point into
+
+
+class _TransitionTracer(_SmcTracer):
+    """The model's `step` alone, flat: a site inside a callee has no carry component of its own."""
+
+    def _call(self, addr, gen_fn, args):
+        raise PlanUnsupported(f"nested `@gen` call at address {addr!r} in `step`: backward simulation needs the transition density "
+                              "of a flat body (every latent site a carry component)")
+
+
+def _reads_state(tracer, a: abi.Arg) -> bool:
+    if a.kind == abi.ARG_STATE:
+        return True
+    return a.kind == abi.ARG_EXPR and any(op == abi.EXPR_STATE for op, _, _ in tracer.expr_progs[a.table])
+
+
+def _renumbered(tracer, a: abi.Arg, new_index: dict, keep: list) -> abi.Arg:
+    """`a` with its site references moved to the positions of the shortened table."""
+    if a.kind in (abi.ARG_SITE, abi.ARG_TABLE):
+        return abi.Arg(a.kind, new_index[a.ref], a.scale, a.offset, a.table)
+    if a.kind == abi.ARG_EXPR:
+        prog = [(op, new_index[ref] if op == abi.EXPR_SITE else ref, val) for op, ref, val in tracer.expr_progs[a.table]]
+        return abi.expr_arg(prog, keep)
+    return a
+
+
+def build_transition_table(model: StateSpaceModel, obs_addrs: list[tuple]) -> TransitionTable:
+    """The transition density of `model.step` over the CARRY, as backward simulation needs it: defined only when the carry
+    IS the step's latent draws — every returned component a plain reference to a body-level latent site, every latent site
+    returned exactly once, no nested calls.  The table is the step's sites with each latent site constrained to its
+    next-state component; observed sites stay only if an argument reads the old state (one that depends on the new state
+    alone is the same for every candidate and is dropped).  Anything else: `PlanUnsupported`, naming the address or the
+    component."""
+    if not isinstance(model.init, StaticGenerativeFunction) or not isinstance(model.step, StaticGenerativeFunction):
+        raise TypeError("StateSpaceModel needs `@gen` functions")
+    if len(obs_addrs) > abi.SMC_MAX_OBS:
+        raise PlanUnsupported(f"at most {abi.SMC_MAX_OBS} observed addresses per step")
+    obs_index = {a: k for k, a in enumerate(obs_addrs)}
+    # (the carry's length is that of what `init` returns, as in build_smc_plan; the table comes from `step` alone)
+    ti = _SmcTracer(obs_index)
+    n_state = len(_state_args(ti, ti.run(model.init.source, ()), None))
+    tr = _TransitionTracer(obs_index)
+    carry = tuple(Sym(tr, ("state", k)) for k in range(n_state))
+    ret = tr.run(model.step.source, (carry[0],) if n_state == 1 else (carry,))
+    vals = ret if isinstance(ret, (tuple, list)) else (ret,)
+    if len(vals) != n_state:
+        raise PlanUnsupported("init and step must return carries of the same length")
+    component_of: dict = {}  # latent site -> the carry component that returns it
+    for c, v in enumerate(vals):
+        plain = (isinstance(v, Sym) and v.src[0] == "site" and v.scale == 1.0 and v.offset == 0.0
+                 and not v.has_mul and not v.has_add and tr.sites[v.src[1]].observed == 0)
+        if not plain:
+            raise PlanUnsupported(f"carry component {c} of `step` is an expression, not one of the step's latent draws: the "
+                                  "transition is degenerate (it has no density over the carry), so backward simulation is "
+                                  "undefined for this model")
+        q = v.src[1]
+        if q in component_of:
+            raise PlanUnsupported(f"the latent site {_show(tr.meta[q]['path'])} is returned twice (carry components "
+                                  f"{component_of[q]} and {c}): the transition is degenerate")
+        component_of[q] = c
+    for q, site in enumerate(tr.sites):
+        if site.observed == 0 and q not in component_of:
+            raise PlanUnsupported(f"the latent site {_show(tr.meta[q]['path'])} is not returned in the carry: the transition "
+                                  "density over the carry would need it integrated out")
+    kept = [q for q, site in enumerate(tr.sites)
+            if site.observed == 0 or _reads_state(tr, site.arg[0]) or (site.dist != abi.DIST_BERNOULLI and site.dist != abi.DIST_CATEGORICAL
+                                                                    and _reads_state(tr, site.arg[1]))]
+    new_index = {q: k for k, q in enumerate(kept)}
+    keep: list = list(tr.keep)
+    sites = []
+    for q in kept:
+        site = abi.Site.from_buffer_copy(tr.sites[q])
+        for k in range(2):
+            site.arg[k] = _renumbered(tr, tr.sites[q].arg[k], new_index, keep)
+        if site.observed == 0:
+            site.observed = 1
+            site.obs = abi.Arg(abi.ARG_NEXT, component_of[q], 1.0, 0.0, None)
+        site.out_col = -1
+        sites.append(site)
+    return TransitionTable(sites, n_state, len(obs_addrs), tuple(keep))
+
+
 def observation_matrix(observations, obs_addrs: list[tuple]) -> np.ndarray:
     """[T, n_obs] float32 from a ChoiceMap whose observed leaves are length-T vectors."""
     cols = []
