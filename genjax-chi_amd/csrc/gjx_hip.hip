@@ -1811,13 +1811,25 @@ __global__ __launch_bounds__(kBlock) void k_map_f32(const float* x, float c, flo
 // ================================================================================================
 // C-ABI
 // ================================================================================================
-extern "C" {
-
-int gjx_version(int* major, int* minor) {
-  if (major) *major = GJX_VERSION_MAJOR;
-  if (minor) *minor = GJX_VERSION_MINOR;
+// the *_source entry points: `src` into the caller's buffer (truncated to it), its full size with the NUL into `needed`
+static int copy_source_out(const std::string& src, char* buf, size_t buf_len, size_t* needed) {
+  if (needed) *needed = src.size() + 1;
+  if (buf && buf_len > 0) {
+    const size_t k = src.size() < buf_len - 1 ? src.size() : buf_len - 1;
+    memcpy(buf, src.data(), k);
+    buf[k] = 0;
+  }
   return GJX_OK;
 }
+// the *_version entry points
+static int version_out(int* major, int* minor, int maj, int min) {
+  if (major) *major = maj;
+  if (minor) *minor = min;
+  return GJX_OK;
+}
+extern "C" {
+
+int gjx_version(int* major, int* minor) { return version_out(major, minor, GJX_VERSION_MAJOR, GJX_VERSION_MINOR); }
 const char* gjx_backend_name(void) { return "hip-gfx950"; }
 int gjx_frac_bits(uint64_t n_total) { return frac_bits(n_total); }
 uint64_t gjx_smc_tile(void) { return kTile; }
@@ -2028,6 +2040,24 @@ static void cat_tables_prepare(CSite* sites, int n, std::vector<void*>* owned) {
 static void free_owned(std::vector<void*>& owned) {
   for (void* p : owned) (void)hipFree(p);
   owned.clear();
+}
+// Compile on first use, once per slot: under the plan's lock, the derived tables of the plan's site tables (a GPU is present
+// by now; sites that have theirs are skipped), then `build` -> ready or failed.  -> the slot is ready.
+struct SiteTable {
+  CSite* sites;
+  int n;
+};
+extern "C++" template <class Build>
+static bool compiled_once(std::mutex& mu, gjx_jit::Module& c, std::initializer_list<SiteTable> tables, std::vector<void*>* owned,
+                          Build build) {
+  if (c.state == 0) {
+    std::lock_guard<std::mutex> lock(mu);
+    if (c.state == 0) {
+      for (const SiteTable& t : tables) cat_tables_prepare(t.sites, t.n, owned);
+      c.state = build() ? 1 : -1;
+    }
+  }
+  return c.state == 1;
 }
 
 // A plan's own copy of the programs of one site table (the caller's arrays need not outlive plan creation; only the
@@ -2320,39 +2350,32 @@ static int jit_form_pref() {  // GJX_JIT_FORM = one | pair | quad (test / tuning
 //    tools/ab_waves_hint.py measures them against each other through GJX_JIT_DEFINE=GJX_WAVES_HINT=<k>).
 // A hinted build that spills more than 32 B is replaced by the unhinted one (plan_compiled).
 static int jit_waves_hint(int P) { return P == 2 ? 6 : 0; }
+// The importance generator of a plan.  `form`: particles per lane, 1, 2 (pairs) or 4 (quads); above 1 is PHILOX only.
+static void plan_gen_setup(gjx_jit::Gen<CSite, CArg>& g, const gjx_plan* p, int impl, int form, bool fused_tail, int min_waves) {
+  g.impl = impl; g.sites = p->host; g.n_sites = p->n_sites; g.laned = form >= 2; g.pairs_per_lane = form == 4 ? 2 : 1;
+  g.sc = p->scopes.n_scopes > 0 ? &p->scopes : nullptr;
+  g.fast_math = (p->flags & GJX_PLAN_FAST_MATH) != 0;
+  g.fused_tail = fused_tail;
+  g.min_waves = min_waves;
+}
 int gjx_plan_specialized_source(const gjx_plan* p, int impl, char* buf, size_t buf_len, size_t* needed) {
   const bool fused_tail = (impl & GJX_SOURCE_FUSED_TAIL) != 0;
   impl &= ~GJX_SOURCE_FUSED_TAIL;
   if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
+  const int form = impl == 1 ? jit_form_pref() : 1;  // (GJX_JIT_FORM picks the PHILOX form shown)
   gjx_jit::Gen<CSite, CArg> g;
-  g.impl = impl; g.sites = p->host; g.n_sites = p->n_sites; g.laned = impl == 1 && jit_form_pref() >= 2;
-  g.sc = p->scopes.n_scopes > 0 ? &p->scopes : nullptr;
-  g.pairs_per_lane = jit_form_pref() == 4 ? 2 : 1;  // (GJX_JIT_FORM picks the PHILOX form shown)
-  g.fast_math = (p->flags & GJX_PLAN_FAST_MATH) != 0;
-  g.fused_tail = fused_tail;
-  g.min_waves = g.laned ? jit_waves_hint(2 * g.pairs_per_lane) : 0;  // the kernel that ships
+  plan_gen_setup(g, p, impl, form, fused_tail, jit_waves_hint(form));  // the kernel that ships
   gjx_jit::TableScope ts;
-  const std::string src = g.run();
-  if (needed) *needed = src.size() + 1;
-  if (buf && buf_len > 0) {
-    const size_t k = src.size() < buf_len - 1 ? src.size() : buf_len - 1;
-    memcpy(buf, src.data(), k);
-    buf[k] = 0;
-  }
-  return GJX_OK;
+  return copy_source_out(g.run(), buf, buf_len, needed);
 }
 
 int gjx_plan_compile_check(const gjx_plan* p, int impl) {
   const bool fused_tail = (impl & GJX_SOURCE_FUSED_TAIL) != 0;
   impl &= ~GJX_SOURCE_FUSED_TAIL;
   if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
-  for (int form = 0; form <= 2 * impl; ++form) {  // PHILOX: one particle per lane, pairs, quads
+  for (int form = 1; form <= (impl == 1 ? 4 : 1); form *= 2) {  // PHILOX: one particle per lane, pairs, quads
     gjx_jit::Gen<CSite, CArg> g;
-    g.impl = impl; g.sites = p->host; g.n_sites = p->n_sites; g.laned = form != 0; g.pairs_per_lane = form == 2 ? 2 : 1;
-    g.sc = p->scopes.n_scopes > 0 ? &p->scopes : nullptr;
-    g.fast_math = (p->flags & GJX_PLAN_FAST_MATH) != 0;
-    g.fused_tail = fused_tail;
-    g.min_waves = jit_waves_hint(2 * form);
+    plan_gen_setup(g, p, impl, form, fused_tail, jit_waves_hint(form));
     gjx_jit::TableScope ts;
     if (!gjx_jit::compile_only(g.run())) return GJX_ERR_UNSUPPORTED;
   }
@@ -2361,8 +2384,8 @@ int gjx_plan_compile_check(const gjx_plan* p, int impl) {
 int gjx_plan_destroy(gjx_plan* p) {
   if (!p) return GJX_OK;
   if (p->dev) (void)hipFree(p->dev);
-  for (auto& c : p->jit) gjx_jit::release(&c);  // the modules stay cached (bounded, LRU) for plans of the same structure
-  for (auto& c : p->jit_tail) gjx_jit::release(&c);
+  for (auto& c : p->jit) c.release();  // the modules stay cached (bounded, LRU) for plans of the same structure
+  for (auto& c : p->jit_tail) c.release();
   free_owned(p->dev_owned);
   delete p;
   return GJX_OK;
@@ -2379,51 +2402,43 @@ static gjx_jit::Compiled& plan_compiled(gjx_plan* mp, const gjx_keys* pk, int la
   if (P == 3) P = 2;
   const bool laned = P >= 2;
   gjx_jit::Compiled& c = (fused_tail ? mp->jit_tail : mp->jit)[P == 4 ? 3 : (laned ? 2 : pk->impl)];
-  if (c.state == 0) {
-    std::lock_guard<std::mutex> lock(mp->jit_mu);
-    if (c.state == 0) {
-      cat_tables_prepare(mp->host, mp->n_sites, &mp->dev_owned);
-      auto make = [&](int min_waves) {
-        gjx_jit::Gen<CSite, CArg> g;
-        g.impl = pk->impl; g.sites = mp->host; g.n_sites = mp->n_sites; g.laned = laned; g.pairs_per_lane = P == 4 ? 2 : 1;
-        g.sc = mp->scopes.n_scopes > 0 ? &mp->scopes : nullptr;
-        g.fast_math = (mp->flags & GJX_PLAN_FAST_MATH) != 0;
-        g.min_waves = min_waves;
-        g.fused_tail = fused_tail;
-        gjx_jit::TableScope ts;  // the source numbers the plan's device tables; the addresses travel as a kernel argument
-        std::string src = g.run();
-        c.block = g.block;
-        c.rows_per_block = g.rows_per_block;
-        c.tabs = ts.reg.tables();
-        return src;
-      };
-      // (jit_waves_hint has the register counts and the waves per SIMD that follow from them.)  The hint is kept as long
-      // as the allocator gets there with (next to) no spilling; otherwise the unconstrained build is used.
-      const int hint = laned ? jit_waves_hint(P) : 0;
-      bool ok = gjx_jit::compile(make(hint), pk->impl, &c);
-      if (ok && std::getenv("GJX_PLAN_JIT_VERBOSE")) {  // what the loaded code object allocates (the VGPR column of a rocprofv3 kernel trace is HALF of this)
-        int regs = 0;
-        if (hipFuncGetAttribute(&regs, HIP_FUNC_ATTRIBUTE_NUM_REGS, c.fn) != hipSuccess) (void)hipGetLastError();
-        fprintf(stderr, "gjx jit: %d particle(s) per lane%s: %d registers per lane\n", P, fused_tail ? ", fused tail" : "", regs);
-      }
-      if (ok && hint > 0) {
-        int scratch = 0;
-        const hipError_t qe = hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, c.fn);
-        if (qe != hipSuccess) (void)hipGetLastError();  // a failed query must not surface as a launch error later
-        if (std::getenv("GJX_PLAN_JIT_VERBOSE")) fprintf(stderr, "gjx jit: waves-per-SIMD hint %d: query %d, scratch %d B\n", hint, (int)qe, scratch);
-        if (qe != hipSuccess || scratch > 32) {  // (a couple of spilled words cost less than the lost wave)
-          ok = gjx_jit::compile(make(0), pk->impl, &c);  // (releases the hinted module: it stays cached, unreferenced)
-        }
-      }
-      if (!ok) {
-        (void)hipGetLastError();
-        fprintf(stderr, "[gjx] plan specialisation FAILED (hiprtc compile or module load; impl %d, %d particle(s) per lane). "
-                        "gjx_importance_run returns GJX_ERR_JIT; set GJX_PLAN_JIT_VERBOSE=1 for the compiler log, GJX_PLAN_JIT=0 "
-                        "or GJX_PLAN_JIT_FALLBACK=1 to run the (7x slower) table interpreter instead.\n", pk->impl, P);
-      }
-      c.state = ok ? 1 : -1;
+  compiled_once(mp->jit_mu, c, {{mp->host, mp->n_sites}}, &mp->dev_owned, [&] {
+    auto build = [&](int min_waves) {
+      gjx_jit::Gen<CSite, CArg> g;
+      plan_gen_setup(g, mp, pk->impl, P, fused_tail, min_waves);
+      gjx_jit::TableScope ts;  // the source numbers the plan's device tables; the addresses travel as a kernel argument
+      const std::string src = g.run();
+      c.block = g.block;
+      c.rows_per_block = g.rows_per_block;
+      c.tabs = ts.reg.tables();
+      return c.load(src, {g.kname()}, {&c.fn});
+    };
+    // (jit_waves_hint has the register counts and the waves per SIMD that follow from them.)  The hint is kept as long
+    // as the allocator gets there with (next to) no spilling; otherwise the unconstrained build is used.
+    const int hint = laned ? jit_waves_hint(P) : 0;
+    bool ok = build(hint);
+    if (ok && std::getenv("GJX_PLAN_JIT_VERBOSE")) {  // what the loaded code object allocates (the VGPR column of a rocprofv3 kernel trace is HALF of this)
+      int regs = 0;
+      if (hipFuncGetAttribute(&regs, HIP_FUNC_ATTRIBUTE_NUM_REGS, c.fn) != hipSuccess) (void)hipGetLastError();
+      fprintf(stderr, "gjx jit: %d particle(s) per lane%s: %d registers per lane\n", P, fused_tail ? ", fused tail" : "", regs);
     }
-  }
+    if (ok && hint > 0) {
+      int scratch = 0;
+      const hipError_t qe = hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, c.fn);
+      if (qe != hipSuccess) (void)hipGetLastError();  // a failed query must not surface as a launch error later
+      if (std::getenv("GJX_PLAN_JIT_VERBOSE")) fprintf(stderr, "gjx jit: waves-per-SIMD hint %d: query %d, scratch %d B\n", hint, (int)qe, scratch);
+      if (qe != hipSuccess || scratch > 32) {  // (a couple of spilled words cost less than the lost wave)
+        ok = build(0);  // (releases the hinted module: it stays cached, unreferenced)
+      }
+    }
+    if (!ok) {
+      (void)hipGetLastError();
+      fprintf(stderr, "[gjx] plan specialisation FAILED (hiprtc compile or module load; impl %d, %d particle(s) per lane). "
+                      "gjx_importance_run returns GJX_ERR_JIT; set GJX_PLAN_JIT_VERBOSE=1 for the compiler log, GJX_PLAN_JIT=0 "
+                      "or GJX_PLAN_JIT_FALLBACK=1 to run the (7x slower) table interpreter instead.\n", pk->impl, P);
+    }
+    return ok;
+  });
   return c;
 }
 static bool jit_fallback_allowed() {
@@ -3287,8 +3302,8 @@ int gjx_scan_plan_create_scoped(const gjx_scan_model* m, const gjx_scope* scopes
 }
 int gjx_scan_plan_destroy(gjx_scan_plan* p) {
   if (!p) return GJX_OK;
-  for (auto& c : p->jit) gjx_jit::release(&c);
-  for (auto& c : p->jit_tail) gjx_jit::release(&c);
+  for (auto& c : p->jit) c.release();
+  for (auto& c : p->jit_tail) c.release();
   free_owned(p->dev_owned);
   delete p;
   return GJX_OK;
@@ -3349,19 +3364,13 @@ int gjx_scan_run(gjx_scan_plan* p, const gjx_scan_io* io, gjx_stream s) {
   }
   const bool fused_tail = io->lse != nullptr;  // the in-launch fold: a variant of its own, built when first asked for
   gjx_jit::Compiled& c = (fused_tail ? p->jit_tail : p->jit)[quad ? 2 : impl];
-  if (c.state == 0) {
-    std::lock_guard<std::mutex> lock(p->mu);
-    if (c.state == 0) {
-      cat_tables_prepare(p->step, p->n_step, &p->dev_owned);
-      const char* kname = nullptr;
-      int block = 256;
-      const std::string src = scan_plan_source(p, impl, &kname, &c.tabs, quad, &block, fused_tail);
-      c.block = block;
-      if (std::getenv("GJX_PLAN_JIT_DUMP")) fprintf(stderr, "%s\n", src.c_str());
-      c.state = gjx_jit::compile(src, impl, &c, kname) ? 1 : -1;
-    }
-  }
-  if (c.state != 1) return GJX_ERR_JIT;
+  const bool ready = compiled_once(p->mu, c, {{p->step, p->n_step}}, &p->dev_owned, [&] {
+    const char* kname = nullptr;
+    const std::string src = scan_plan_source(p, impl, &kname, &c.tabs, quad, &c.block, fused_tail);
+    if (std::getenv("GJX_PLAN_JIT_DUMP")) fprintf(stderr, "%s\n", src.c_str());
+    return c.load(src, {kname}, {&c.fn});
+  });
+  if (!ready) return GJX_ERR_JIT;
   KeySrc k = key_src(io->particle_keys);
   ScanArgs sa;
   memset(&sa, 0, sizeof sa);
@@ -3451,11 +3460,7 @@ static int smc_plan_create_impl(const gjx_smc_model* m, gjx_smc_plan** out, bool
 }
 int gjx_smc_plan_create(const gjx_smc_model* m, gjx_smc_plan** out) { return smc_plan_create_impl(m, out, false); }
 int gjx_smc_plan_create_guided(const gjx_smc_model* m, gjx_smc_plan** out) { return smc_plan_create_impl(m, out, true); }
-int gjx_guided_version(int* major, int* minor) {
-  if (major) *major = GJX_GUIDED_VERSION_MAJOR;
-  if (minor) *minor = GJX_GUIDED_VERSION_MINOR;
-  return GJX_OK;
-}
+int gjx_guided_version(int* major, int* minor) { return version_out(major, minor, GJX_GUIDED_VERSION_MAJOR, GJX_GUIDED_VERSION_MINOR); }
 int gjx_smc_plan_create_scoped(const gjx_smc_model* m, const gjx_scope* init_scopes, int n_init_scopes,
                                const gjx_scope* step_scopes, int n_step_scopes, gjx_smc_plan** out) {
   gjx_smc_plan* p = nullptr;
@@ -3471,8 +3476,8 @@ int gjx_smc_plan_create_scoped(const gjx_smc_model* m, const gjx_scope* init_sco
 }
 int gjx_smc_plan_destroy(gjx_smc_plan* p) {
   if (!p) return GJX_OK;
-  for (auto& c : p->jit) gjx_jit::release_smc(&c);  // compiled modules are owned by the process-wide (bounded) cache
-  for (auto& c : p->jit_peers) gjx_jit::release_smc(&c);
+  for (auto& c : p->jit) c.release();  // compiled modules are owned by the process-wide (bounded) cache
+  for (auto& c : p->jit_peers) c.release();
   free_owned(p->dev_owned);
   if (p->dev_init) (void)hipFree(p->dev_init);
   if (p->dev_step) (void)hipFree(p->dev_step);
@@ -3515,14 +3520,7 @@ static std::string smc_plan_source(const gjx_smc_plan* plan, int impl, PlanTable
 }
 int gjx_smc_plan_source(const gjx_smc_plan* p, int impl, char* buf, size_t buf_len, size_t* needed) {
   if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
-  const std::string src = smc_plan_source(p, impl);
-  if (needed) *needed = src.size() + 1;
-  if (buf && buf_len > 0) {
-    const size_t k = src.size() < buf_len - 1 ? src.size() : buf_len - 1;
-    memcpy(buf, src.data(), k);
-    buf[k] = 0;
-  }
-  return GJX_OK;
+  return copy_source_out(smc_plan_source(p, impl), buf, buf_len, needed);
 }
 int gjx_smc_plan_compile_check(const gjx_smc_plan* p, int impl) {
   if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
@@ -3548,17 +3546,11 @@ static int smc_plan_interp_tables(gjx_smc_plan* plan) {
 static gjx_jit::CompiledSmc* smc_plan_compiled(gjx_smc_plan* plan, int impl, bool peers = false) {
   if (!gjx_jit::enabled()) return nullptr;  // (GJX_PLAN_JIT=0: the table-walking policy, smc_plan_route)
   gjx_jit::CompiledSmc& c = peers ? plan->jit_peers[impl] : plan->jit[impl];
-  if (c.state == 0) {
-    std::lock_guard<std::mutex> lock(plan->mu);
-    if (c.state == 0) {
-      if (plan->jit[impl].state == 0 && plan->jit_peers[impl].state == 0) {  // (the derived tables: once per plan)
-        cat_tables_prepare(plan->init, plan->n_init, &plan->dev_owned);
-        cat_tables_prepare(plan->step, plan->n_step, &plan->dev_owned);
-      }
-      c.state = gjx_jit::compile_smc(smc_plan_source(plan, impl, &c.tabs, peers), &c) ? 1 : -1;
-    }
-  }
-  return c.state == 1 ? &c : nullptr;
+  const bool ready = compiled_once(plan->mu, c, {{plan->init, plan->n_init}, {plan->step, plan->n_step}}, &plan->dev_owned, [&] {
+    return c.load(smc_plan_source(plan, impl, &c.tabs, peers), {"gjx_smc_step_kernel", "gjx_smc_step_kernel_adaptive", "gjx_smc_init_kernel"},
+                  {&c.step, &c.step_adaptive, &c.init});
+  });
+  return ready ? &c : nullptr;
 }
 
 // One step of a plan-driven filter: the generated init kernel (t == 0) or the generated policy inside the fused
@@ -3643,37 +3635,6 @@ int gjx_smc_plan_step(const gjx_smc_config* cfg, gjx_smc_plan* plan, int t, cons
   return smc_plan_step(cfg, plan, c, t, obs_t, prev, out, prev_e_out, prev_q_out, ancestors_out, s, StepCtx{});
 }
 
-int gjx_smc_run_plan(const gjx_smc_config* cfg, gjx_smc_plan* plan, const float* obs_host, int32_t* out_e,
-                     uint64_t* out_q, float* const* state_out, float* logw_out, int32_t* ancestors_out,
-                     void* ws, size_t ws_bytes, gjx_stream s) {
-  if (!cfg_ok(cfg) || cfg->first_slot != 0 || cfg->n_local != cfg->n_total || !plan || !out_e || !out_q ||
-      !state_out || !logw_out || (plan->n_obs > 0 && !obs_host))
-    return GJX_ERR_INVALID;
-  gjx_jit::CompiledSmc* cp = nullptr;
-  const int route = smc_plan_route(plan, cfg->impl, &cp);
-  if (route) return route;
-  const int D = plan->n_state, T = cfg->n_steps;
-  void* st[GJX_SMC_MAX_STATE];
-  for (int k = 0; k < D; ++k) {
-    if (!state_out[k]) return GJX_ERR_INVALID;
-    st[k] = state_out[k];
-  }
-  // several filters per launch (as in smc_run): filter f's particles lie f * stride further in every array
-  Carver cv{(char*)ws, ws ? ws_bytes : 0};
-  RunCommon rc;
-  int r = run_common_init(cfg, cv, rc, D, st, logw_out, s);
-  if (r) return r;
-  for (int t = 0; t < T; ++t) {
-    gjx_smc_pop out;
-    StepCtx ctx = run_step_ctx(cfg, rc, t, &out);
-    r = smc_plan_step(cfg, plan, cp, t, plan->n_obs ? obs_host + (size_t)t * (size_t)plan->n_obs : nullptr,
-                      &rc.pop[(t & 1) ^ 1], &out, t ? out_e + (t - 1) : nullptr, t ? out_q + (t - 1) : nullptr,
-                      ancestors_out ? ancestors_out + (size_t)t * rc.F * rc.stride : nullptr, s, ctx);
-    if (r) return r;
-  }
-  return run_finish(cfg, rc, out_e, out_q, s);
-}
-
 }  // extern "C"
 
 // ---- r04: a whole run as ONE hipGraph, replayed -------------------------------------------------------------------------------
@@ -3734,19 +3695,20 @@ struct RunGraphs {
 };
 
 template <class Step>
-static int smc_run(const gjx_smc_config* cfg, const void* model, int32_t* out_e, uint64_t* out_q,
-                   void* state_out, float* logw_out, int32_t* ancestors_out, void* ws,
+static int smc_run(const gjx_smc_config* cfg, const void* model, int32_t* out_e, uint64_t* out_q, int n_state,
+                   void* const* state_out, float* logw_out, int32_t* ancestors_out, void* ws,
                    size_t ws_bytes, gjx_stream s, Step step, const RunGraphInfo* gi = nullptr) {
   if (!cfg_ok(cfg) || cfg->first_slot != 0 || cfg->n_local != cfg->n_total || !model || !out_e ||
-      !out_q || !state_out || !logw_out)
+      !out_q || !logw_out)
     return GJX_ERR_INVALID;
+  for (int k = 0; k < n_state; ++k)
+    if (!state_out[k]) return GJX_ERR_INVALID;
   const int T = cfg->n_steps;
   // the T launches of the run on stream `st`; sp / rp: the device parameter block of a replayed run (or null)
   auto run_loop = [&](gjx_stream st, const StepParams* sp, const float* rp) -> int {
     Carver cv{(char*)ws, ws ? ws_bytes : 0};
     RunCommon rc;
-    void* stt[1] = {state_out};
-    int r = run_common_init(cfg, cv, rc, 1, stt, logw_out, st, sp == nullptr);  // (a replayed run clears the flags in front of the graph)
+    int r = run_common_init(cfg, cv, rc, n_state, state_out, logw_out, st, sp == nullptr);  // (a replayed run clears the flags in front of the graph)
     for (int t = 0; t < T && !r; ++t) {
       int32_t* anc_t = ancestors_out ? ancestors_out + (size_t)t * rc.F * rc.stride : nullptr;
       gjx_smc_pop out;
@@ -3754,7 +3716,7 @@ static int smc_run(const gjx_smc_config* cfg, const void* model, int32_t* out_e,
       if (sp) { ctx.sp = sp + t; ctx.rp = rp; }
 #ifdef GJX_PROFILE_HOOKS
       static const bool dbg_fixed = std::getenv("GJX_SMC_DEBUG_FIXED") != nullptr;  // profiling: every step reads step 0's population
-      if (dbg_fixed && t > 0) {
+      if (gi && dbg_fixed && t > 0) {  // (the fixed models: their runs alone describe themselves with a RunGraphInfo)
         out = rc.pop[1];
         if (!rc.adaptive) out.logw = nullptr;
         r = step(t, &rc.pop[0], &out, out_e + (t - 1), out_q + (t - 1), anc_t, ctx, st);
@@ -3772,7 +3734,7 @@ static int smc_run(const gjx_smc_config* cfg, const void* model, int32_t* out_e,
     std::lock_guard<std::mutex> lock(G.mu);
     uint64_t key[20] = {(uint64_t)gi->kind, cfg->n_total, (uint64_t)T, (uint64_t)cfg->impl, (uint64_t)f2u(cfg->ess_threshold),
                         (uint64_t)(uintptr_t)cfg->resampled_out, (uint64_t)(uintptr_t)out_e, (uint64_t)(uintptr_t)out_q,
-                        (uint64_t)(uintptr_t)state_out, (uint64_t)(uintptr_t)logw_out, (uint64_t)(uintptr_t)ancestors_out,
+                        (uint64_t)(uintptr_t)state_out[0], (uint64_t)(uintptr_t)logw_out, (uint64_t)(uintptr_t)ancestors_out,
                         (uint64_t)(uintptr_t)ws, (uint64_t)ws_bytes, gi->extra[0], gi->extra[1], gi->extra[2], gi->extra[3], 0, 0, 0};
     RunGraphEntry* e = nullptr;
     for (auto& x : G.entries)
@@ -3874,7 +3836,8 @@ int gjx_smc_run_lgssm(const gjx_smc_config* cfg, const gjx_lgssm* model, const f
     memcpy(gi.rp, rp, sizeof rp);
     gi.n_rp = 6;
   }
-  return smc_run(cfg, model, out_e, out_q, state_out, logw_out, ancestors_out, ws, ws_bytes, s, step, model ? &gi : nullptr);
+  void* st[1] = {state_out};
+  return smc_run(cfg, model, out_e, out_q, 1, st, logw_out, ancestors_out, ws, ws_bytes, s, step, model ? &gi : nullptr);
 }
 
 int gjx_smc_run_hmm(const gjx_smc_config* cfg, const gjx_hmm* model, const int32_t* y_host,
@@ -3907,7 +3870,27 @@ int gjx_smc_run_hmm(const gjx_smc_config* cfg, const gjx_hmm* model, const int32
   gi.extra[0] = (uint64_t)model->n_states; gi.extra[1] = (uint64_t)(uint32_t)model->init_state;
   bool ys_ok = cfg && cfg->n_steps > 0;
   for (int t = 0; ys_ok && t < cfg->n_steps; ++t) ys_ok = y_host[t] >= 0 && y_host[t] < model->n_states;
-  return smc_run(cfg, model, out_e, out_q, state_out, logw_out, ancestors_out, ws, head_bytes, s, step, ys_ok ? &gi : nullptr);
+  void* st[1] = {state_out};
+  return smc_run(cfg, model, out_e, out_q, 1, st, logw_out, ancestors_out, ws, head_bytes, s, step, ys_ok ? &gi : nullptr);
+}
+
+int gjx_smc_run_plan(const gjx_smc_config* cfg, gjx_smc_plan* plan, const float* obs_host, int32_t* out_e,
+                     uint64_t* out_q, float* const* state_out, float* logw_out, int32_t* ancestors_out,
+                     void* ws, size_t ws_bytes, gjx_stream s) {
+  if (!cfg_ok(cfg) || cfg->first_slot != 0 || cfg->n_local != cfg->n_total || !plan || !out_e || !out_q ||
+      !state_out || !logw_out || (plan->n_obs > 0 && !obs_host))
+    return GJX_ERR_INVALID;
+  gjx_jit::CompiledSmc* cp = nullptr;
+  const int route = smc_plan_route(plan, cfg->impl, &cp);
+  if (route) return route;
+  void* st[GJX_SMC_MAX_STATE];
+  for (int k = 0; k < plan->n_state; ++k) st[k] = state_out[k];
+  auto step = [&](int t, const gjx_smc_pop* prev, const gjx_smc_pop* out, int32_t* pe, uint64_t* pq, int32_t* anc,
+                  const StepCtx& ctx, gjx_stream stm) {
+    return smc_plan_step(cfg, plan, cp, t, plan->n_obs ? obs_host + (size_t)t * (size_t)plan->n_obs : nullptr, prev, out, pe, pq, anc,
+                         stm, ctx);
+  };
+  return smc_run(cfg, plan, out_e, out_q, plan->n_state, st, logw_out, ancestors_out, ws, ws_bytes, s, step);  // (no graph)
 }
 
 }  // extern "C"
@@ -4160,11 +4143,7 @@ inline bool paths_size_ok(uint64_t v) { return v >= 1 && v < (1ull << 31); }
 
 extern "C" {
 
-int gjx_paths_version(int* major, int* minor) {
-  if (major) *major = GJX_PATHS_VERSION_MAJOR;
-  if (minor) *minor = GJX_PATHS_VERSION_MINOR;
-  return GJX_OK;
-}
+int gjx_paths_version(int* major, int* minor) { return version_out(major, minor, GJX_PATHS_VERSION_MAJOR, GJX_PATHS_VERSION_MINOR); }
 size_t gjx_paths_workspace_bytes(int32_t n_steps, uint64_t m, int32_t n_cols) {
   if (n_steps < 1 || !paths_size_ok(m) || n_cols < 0 || n_cols > GJX_PATHS_MAX_COLS) return 0;
   return (size_t)n_steps * (size_t)(2 * n_cols + 1) * (size_t)paths_chunks(m) * sizeof(uint64_t);
@@ -4226,13 +4205,7 @@ struct gjx_backsim_plan {
   ExprStore expr;  // GJX_ARG_EXPR programs of the table
   std::vector<void*> dev_owned;  // per-row tables of categorical sites
   std::mutex mu;
-  struct Kernels {
-    hipFunction_t step = nullptr, last = nullptr;
-    int state = 0;  // 0 untried, 1 ready, -1 failed
-    std::string key;
-    gjx::PlanTables tabs;
-  } jit[2];
-  bool tables_ready = false;
+  gjx_jit::CompiledBacksim jit[2];
 };
 
 namespace {
@@ -4252,29 +4225,12 @@ std::string backsim_source(const gjx_backsim_plan* p, int impl, PlanTables* tabs
   return src;
 }
 
-gjx_backsim_plan::Kernels* backsim_compiled(gjx_backsim_plan* p, int impl) {
-  gjx_backsim_plan::Kernels& c = p->jit[impl];
-  if (c.state == 0) {
-    std::lock_guard<std::mutex> lock(p->mu);
-    if (c.state == 0) {
-      if (!p->tables_ready) {  // (the derived tables: once per plan, a GPU is present by now)
-        cat_tables_prepare(p->sites, p->n_sites, &p->dev_owned);
-        p->tables_ready = true;
-      }
-      hipModule_t mod = gjx_jit::ModuleCache::get().acquire(backsim_source(p, impl, &c.tabs), &c.key);
-      bool ok = mod != nullptr;
-      if (ok && (hipModuleGetFunction(&c.step, mod, "gjx_backsim_step_kernel") != hipSuccess ||
-                 hipModuleGetFunction(&c.last, mod, "gjx_backsim_last_kernel") != hipSuccess)) {
-        (void)hipGetLastError();
-        fprintf(stderr, "[gjx] hipModuleGetFunction failed for a generated backward-simulation kernel\n");
-        gjx_jit::ModuleCache::get().release(c.key);
-        c.key.clear();
-        ok = false;
-      }
-      c.state = ok ? 1 : -1;
-    }
-  }
-  return c.state == 1 ? &c : nullptr;
+gjx_jit::CompiledBacksim* backsim_compiled(gjx_backsim_plan* p, int impl) {
+  gjx_jit::CompiledBacksim& c = p->jit[impl];
+  const bool ready = compiled_once(p->mu, c, {{p->sites, p->n_sites}}, &p->dev_owned, [&] {
+    return c.load(backsim_source(p, impl, &c.tabs), {"gjx_backsim_step_kernel", "gjx_backsim_last_kernel"}, {&c.step, &c.last});
+  });
+  return ready ? &c : nullptr;
 }
 
 struct BacksimFinishArgs {
@@ -4302,11 +4258,7 @@ __global__ __launch_bounds__(kBlock) void k_backsim_finish(BacksimFinishArgs a) 
 
 extern "C" {
 
-int gjx_backsim_version(int* major, int* minor) {
-  if (major) *major = GJX_BACKSIM_VERSION_MAJOR;
-  if (minor) *minor = GJX_BACKSIM_VERSION_MINOR;
-  return GJX_OK;
-}
+int gjx_backsim_version(int* major, int* minor) { return version_out(major, minor, GJX_BACKSIM_VERSION_MAJOR, GJX_BACKSIM_VERSION_MINOR); }
 int gjx_backsim_plan_create(const gjx_site* sites, int n_sites, int n_state, int n_obs, uint32_t flags,
                             gjx_backsim_plan** out) {
   if (!sites || !out || n_sites < 1 || n_sites > GJX_MAX_SITES || n_state < 1 || n_state > GJX_SMC_MAX_STATE || n_obs < 0 ||
@@ -4328,21 +4280,14 @@ int gjx_backsim_plan_create(const gjx_site* sites, int n_sites, int n_state, int
 }
 int gjx_backsim_plan_destroy(gjx_backsim_plan* p) {
   if (!p) return GJX_OK;
-  for (auto& c : p->jit) gjx_jit::ModuleCache::get().release(c.key);
+  for (auto& c : p->jit) c.release();
   free_owned(p->dev_owned);
   delete p;
   return GJX_OK;
 }
 int gjx_backsim_plan_source(const gjx_backsim_plan* p, int impl, char* buf, size_t buf_len, size_t* needed) {
   if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
-  const std::string src = backsim_source(p, impl);
-  if (needed) *needed = src.size() + 1;
-  if (buf && buf_len > 0) {
-    const size_t k = src.size() < buf_len - 1 ? src.size() : buf_len - 1;
-    memcpy(buf, src.data(), k);
-    buf[k] = 0;
-  }
-  return GJX_OK;
+  return copy_source_out(backsim_source(p, impl), buf, buf_len, needed);
 }
 int gjx_backsim_plan_compile_check(const gjx_backsim_plan* p, int impl) {
   if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
@@ -4375,7 +4320,7 @@ int gjx_backsim_run(gjx_backsim_plan* p, const gjx_backsim_io* io, void* ws, siz
   if (!any_out || ((uintptr_t)ws & 7) != 0) return GJX_ERR_INVALID;
   if (!ws || ws_bytes < gjx_backsim_workspace_bytes(io->n_steps, io->m)) return GJX_ERR_WORKSPACE;
   if (!gjx_jit::enabled()) return GJX_ERR_UNSUPPORTED;  // generated kernels only, as guided plans
-  gjx_backsim_plan::Kernels* k = backsim_compiled(p, io->impl);
+  gjx_jit::CompiledBacksim* k = backsim_compiled(p, io->impl);
   if (!k) return GJX_ERR_JIT;
 
   unsigned long long* best = reinterpret_cast<unsigned long long*>(ws);

@@ -14,6 +14,7 @@
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
 #include <mutex>
 #include <sstream>
 #include <string>
@@ -1256,16 +1257,6 @@ struct GenBacksim {
   }
 };
 
-struct Compiled {
-  hipModule_t mod = nullptr;
-  hipFunction_t fn = nullptr;
-  int state = 0;  // 0 untried, 1 ready, -1 failed
-  int block = 256;  // threads per workgroup of the compiled kernel
-  int rows_per_block = 1;  // 256-particle rows per workgroup
-  std::string key;  // the module-cache entry this slot holds a reference on (ModuleCache::key_of the source)
-  gjx::PlanTables tabs;  // the device tables of THIS plan, in the order the source numbers them (kernel argument)
-};
-
 inline bool enabled() {
   const char* e = std::getenv("GJX_PLAN_JIT");
   return !(e && e[0] == '0');
@@ -1572,56 +1563,49 @@ struct ModuleCache {
     }
   }
 };
-inline void release(Compiled* c) {
-  ModuleCache::get().release(c->key);
-  c->key.clear();
-  c->fn = nullptr;
-  c->mod = nullptr;
-}
-inline bool compile(const std::string& src, int impl, Compiled* out, const char* kernel = nullptr) {
-  release(out);  // (a slot that is being rebuilt, e.g. without the occupancy hint)
-  std::string key;
-  hipModule_t mod = ModuleCache::get().acquire(src, &key);
-  if (!mod) return false;
-  out->key = key;
-  hipFunction_t fn = nullptr;
-  const hipError_t ge =
-      hipModuleGetFunction(&fn, mod, kernel ? kernel : (impl == 0 ? "gjx_plan_kernel_threefry" : "gjx_plan_kernel_philox"));
-  if (ge != hipSuccess) {
-    (void)hipGetLastError();
-    std::fprintf(stderr, "[gjx] hipModuleGetFunction failed for a specialised plan kernel: %s\n", hipGetErrorString(ge));
-    release(out);
-    return false;
-  }
-  out->mod = nullptr;  // owned by the cache
-  out->fn = fn;
-  return true;
-}
-struct CompiledSmc {
-  hipFunction_t step = nullptr, step_adaptive = nullptr, init = nullptr;
+
+// One slot of a plan: a reference on the cached module of one generated source, and the plan's device tables as that
+// source numbers them.  The plan kinds derive from it and add the function handles of their kernels.
+struct Module {
   int state = 0;  // 0 untried, 1 ready, -1 failed
-  std::string key;
-  gjx::PlanTables tabs;  // the device tables of THIS plan (kernel argument of both kernels)
-};
-inline void release_smc(CompiledSmc* c) {
-  ModuleCache::get().release(c->key);
-  c->key.clear();
-  c->step = c->step_adaptive = c->init = nullptr;
-}
-inline bool compile_smc(const std::string& src, CompiledSmc* out) {
-  std::string key;
-  hipModule_t mod = ModuleCache::get().acquire(src, &key);
-  if (!mod) return false;
-  out->key = key;
-  if (hipModuleGetFunction(&out->step, mod, "gjx_smc_step_kernel") != hipSuccess ||
-      hipModuleGetFunction(&out->step_adaptive, mod, "gjx_smc_step_kernel_adaptive") != hipSuccess ||
-      hipModuleGetFunction(&out->init, mod, "gjx_smc_init_kernel") != hipSuccess) {
-    (void)hipGetLastError();
-    std::fprintf(stderr, "[gjx] hipModuleGetFunction failed for a generated SMC kernel\n");
-    release_smc(out);
-    return false;
+  std::string key;  // the module-cache entry this slot holds a reference on (ModuleCache::key_of the source)
+  gjx::PlanTables tabs;  // the device tables of THIS plan, in the order the source numbers them (kernel argument)
+
+  void release() {
+    ModuleCache::get().release(key);
+    key.clear();
   }
-  return true;
-}
+  // The module of `src` (compiled, or shared with plans of the same structure) and its kernels `names` into `fns`.  A slot
+  // that is being rebuilt (e.g. without the occupancy hint) lets go of its module first.
+  bool load(const std::string& src, std::initializer_list<const char*> names, std::initializer_list<hipFunction_t*> fns) {
+    release();
+    std::string k;
+    hipModule_t mod = ModuleCache::get().acquire(src, &k);
+    if (!mod) return false;
+    key = k;
+    auto fn = fns.begin();
+    for (const char* name : names) {
+      const hipError_t ge = hipModuleGetFunction(*fn++, mod, name);
+      if (ge == hipSuccess) continue;
+      (void)hipGetLastError();
+      std::fprintf(stderr, "[gjx] hipModuleGetFunction failed for the generated kernel %s: %s\n", name, hipGetErrorString(ge));
+      for (hipFunction_t* f : fns) *f = nullptr;
+      release();
+      return false;
+    }
+    return true;
+  }
+};
+struct Compiled : Module {  // an importance or scan kernel
+  hipFunction_t fn = nullptr;
+  int block = 256;  // threads per workgroup of the compiled kernel
+  int rows_per_block = 1;  // 256-particle rows per workgroup
+};
+struct CompiledSmc : Module {  // the kernels of a filter (bootstrap or guided)
+  hipFunction_t step = nullptr, step_adaptive = nullptr, init = nullptr;
+};
+struct CompiledBacksim : Module {  // the two kernels of a backward pass
+  hipFunction_t step = nullptr, last = nullptr;
+};
 
 }  // namespace gjx_jit

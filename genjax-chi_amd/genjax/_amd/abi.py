@@ -9,6 +9,7 @@ tensors; the product never does.)
 
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 
@@ -57,31 +58,26 @@ class GjxError(RuntimeError):
         self.code = code
 
 
-class PathsUnavailable(GjxError):
-    """An entry point of include/gjx_paths.h called on a library that does not export it (GJX_ERR_UNSUPPORTED)."""
+class HeaderUnavailable(GjxError):
+    """An entry point of an optional header called on a library that does not export it (GJX_ERR_UNSUPPORTED)."""
+    header = why = ""
 
     def __init__(self, fn: str, backend: str):
-        RuntimeError.__init__(self, f"{fn}: the library '{backend}' does not implement include/gjx_paths.h "
-                                    "(libgjx_hip.so does; the trace-back kernel has no CPU restatement)")
+        RuntimeError.__init__(self, f"{fn}: the library '{backend}' does not implement include/{self.header} "
+                                    f"(libgjx_hip.so does; {self.why})")
         self.code = -2
 
 
-class GuidedUnavailable(GjxError):
-    """An entry point of include/gjx_guided.h called on a library that does not export it (GJX_ERR_UNSUPPORTED)."""
-
-    def __init__(self, fn: str, backend: str):
-        RuntimeError.__init__(self, f"{fn}: the library '{backend}' does not implement include/gjx_guided.h "
-                                    "(libgjx_hip.so does; the CPU oracle knows no proposed / guided sites and would misread their tables)")
-        self.code = -2
+class PathsUnavailable(HeaderUnavailable):
+    header, why = "gjx_paths.h", "the trace-back kernel has no CPU restatement"
 
 
-class BacksimUnavailable(GjxError):
-    """An entry point of include/gjx_backsim.h called on a library that does not export it (GJX_ERR_UNSUPPORTED)."""
+class GuidedUnavailable(HeaderUnavailable):
+    header, why = "gjx_guided.h", "the CPU oracle knows no proposed / guided sites and would misread their tables"
 
-    def __init__(self, fn: str, backend: str):
-        RuntimeError.__init__(self, f"{fn}: the library '{backend}' does not implement include/gjx_backsim.h "
-                                    "(libgjx_hip.so does; backward simulation runs as generated HIP kernels only)")
-        self.code = -2
+
+class BacksimUnavailable(HeaderUnavailable):
+    header, why = "gjx_backsim.h", "backward simulation runs as generated HIP kernels only"
 
 
 class Keys(C.Structure):
@@ -533,6 +529,20 @@ BACKSIM_PROTOTYPES = {
 }
 BACKSIM_ABI_VERSION = (0, 1)
 
+# The optional headers, in the order they are bound: every one is exported by libgjx_hip.so only and bound if present.
+class Header(collections.namedtuple("Header", "key header version_fn prototypes version_name unavailable")):
+    @property
+    def version(self):  # the (major, minor) these bindings are written for: the module constant as it is when a library loads
+        return globals()[self.version_name]
+
+
+OPTIONAL_HEADERS = {h.key: h for h in (
+    Header("paths", "gjx_paths.h", "gjx_paths_version", PATHS_PROTOTYPES, "PATHS_ABI_VERSION", PathsUnavailable),
+    Header("guided", "gjx_guided.h", "gjx_guided_version", GUIDED_PROTOTYPES, "GUIDED_ABI_VERSION", GuidedUnavailable),
+    Header("backsim", "gjx_backsim.h", "gjx_backsim_version", BACKSIM_PROTOTYPES, "BACKSIM_ABI_VERSION", BacksimUnavailable),
+)}
+_HEADER_OF = {name: h for h in OPTIONAL_HEADERS.values() for name in h.prototypes}  # entry point -> its optional header
+
 _NO_STATUS = {
     "gjx_backsim_workspace_bytes",
     "gjx_paths_workspace_bytes",
@@ -560,6 +570,9 @@ class AbiVersionMismatch(RuntimeError):
     pass
 
 
+_CORE_HEADER = Header("core", "gjx.h", "gjx_version", PROTOTYPES, "ABI_VERSION", None)
+
+
 class GjxLib:
     """A loaded implementation of include/gjx.h.  `device_type` is the torch device type whose
     memory the library's "dev" pointers refer to ("cuda" for libgjx_hip.so)."""
@@ -570,81 +583,44 @@ class GjxLib:
         self.path = path
         self.device_type = device_type
         self._dll = C.CDLL(path)
-        # the version FIRST (gjx_version exists in every build): a library of another minor may lack newer symbols, and the
-        # useful error is "wrong version", not "missing symbol"
-        vfn = self._dll.gjx_version
-        vfn.restype, vfn.argtypes = PROTOTYPES["gjx_version"]
+        # gjx.h, then every optional header the library has (libgjx_hip.so all of them, the oracle library none).  The version
+        # FIRST (gjx_version exists in every build): a library of another minor may lack newer symbols, and the useful error
+        # is "wrong version", not "missing symbol"
+        self.has = {}
         major, minor = C.c_int(-1), C.c_int(-1)
-        vfn(C.byref(major), C.byref(minor))
-        if (major.value, minor.value) != ABI_VERSION:
-            raise AbiVersionMismatch(
-                f"{path} implements gjx.h {major.value}.{minor.value}; these bindings are written for "
-                f"{ABI_VERSION[0]}.{ABI_VERSION[1]} (struct layouts and the sampling spec differ between minors): rebuild the "
-                "library from this tree, or run the other library with its own tree's bindings")
-        for name, (res, args) in PROTOTYPES.items():
-            fn = getattr(self._dll, name)  # AttributeError => ABI symbol missing: fail loudly
-            fn.restype = res
-            fn.argtypes = args
-            setattr(self, "_" + name, fn)
-        major, minor = C.c_int(), C.c_int()
-        self.call("gjx_version", C.byref(major), C.byref(minor))
-        self.version = (major.value, minor.value)
+        for h in (_CORE_HEADER, *OPTIONAL_HEADERS.values()):
+            if h is not _CORE_HEADER:
+                self.has[h.key] = hasattr(self._dll, h.version_fn)
+                setattr(self, "has_" + h.key, self.has[h.key])
+                if not self.has[h.key]:
+                    continue
+            vfn = getattr(self._dll, h.version_fn)
+            vfn.restype, vfn.argtypes = h.prototypes[h.version_fn]
+            vfn(C.byref(major), C.byref(minor))
+            if (major.value, minor.value) != h.version:
+                raise AbiVersionMismatch(
+                    f"{path} implements {h.header} {major.value}.{minor.value}; these bindings are written for "
+                    f"{h.version[0]}.{h.version[1]}" + (
+                        " (struct layouts and the sampling spec differ between minors): rebuild the library from this tree, or "
+                        "run the other library with its own tree's bindings" if h is _CORE_HEADER
+                        else ": rebuild the library from this tree"))
+            for name, (res, args) in h.prototypes.items():
+                fn = getattr(self._dll, name)  # AttributeError => ABI symbol missing: fail loudly
+                fn.restype = res
+                fn.argtypes = args
+                setattr(self, "_" + name, fn)
+        self.version = _CORE_HEADER.version  # (checked above)
         self.name = self._gjx_backend_name().decode()
-        # include/gjx_paths.h: bound if the library has it (libgjx_hip.so does, the oracle library does not)
-        self.has_paths = hasattr(self._dll, "gjx_paths_version")
-        if self.has_paths:
-            vfn = self._dll.gjx_paths_version
-            vfn.restype, vfn.argtypes = PATHS_PROTOTYPES["gjx_paths_version"]
-            vfn(C.byref(major), C.byref(minor))
-            if (major.value, minor.value) != PATHS_ABI_VERSION:
-                raise AbiVersionMismatch(
-                    f"{path} implements gjx_paths.h {major.value}.{minor.value}; these bindings are written for "
-                    f"{PATHS_ABI_VERSION[0]}.{PATHS_ABI_VERSION[1]}: rebuild the library from this tree")
-            for name, (res, args) in PATHS_PROTOTYPES.items():
-                fn = getattr(self._dll, name)
-                fn.restype = res
-                fn.argtypes = args
-                setattr(self, "_" + name, fn)
 
-        # include/gjx_guided.h: likewise
-        self.has_guided = hasattr(self._dll, "gjx_guided_version")
-        if self.has_guided:
-            vfn = self._dll.gjx_guided_version
-            vfn.restype, vfn.argtypes = GUIDED_PROTOTYPES["gjx_guided_version"]
-            vfn(C.byref(major), C.byref(minor))
-            if (major.value, minor.value) != GUIDED_ABI_VERSION:
-                raise AbiVersionMismatch(
-                    f"{path} implements gjx_guided.h {major.value}.{minor.value}; these bindings are written for "
-                    f"{GUIDED_ABI_VERSION[0]}.{GUIDED_ABI_VERSION[1]}: rebuild the library from this tree")
-            for name, (res, args) in GUIDED_PROTOTYPES.items():
-                fn = getattr(self._dll, name)
-                fn.restype = res
-                fn.argtypes = args
-                setattr(self, "_" + name, fn)
-
-        # include/gjx_backsim.h: likewise
-        self.has_backsim = hasattr(self._dll, "gjx_backsim_version")
-        if self.has_backsim:
-            vfn = self._dll.gjx_backsim_version
-            vfn.restype, vfn.argtypes = BACKSIM_PROTOTYPES["gjx_backsim_version"]
-            vfn(C.byref(major), C.byref(minor))
-            if (major.value, minor.value) != BACKSIM_ABI_VERSION:
-                raise AbiVersionMismatch(
-                    f"{path} implements gjx_backsim.h {major.value}.{minor.value}; these bindings are written for "
-                    f"{BACKSIM_ABI_VERSION[0]}.{BACKSIM_ABI_VERSION[1]}: rebuild the library from this tree")
-            for name, (res, args) in BACKSIM_PROTOTYPES.items():
-                fn = getattr(self._dll, name)
-                fn.restype = res
-                fn.argtypes = args
-                setattr(self, "_" + name, fn)
+    def require(self, key: str, fn_name: str):
+        """Raise the header's *Unavailable, naming `fn_name`, on a library without the optional header `key`."""
+        if not self.has[key]:
+            raise OPTIONAL_HEADERS[key].unavailable(fn_name, self.name)
 
     def call(self, name: str, *args):
-        if name in BACKSIM_PROTOTYPES and not self.has_backsim:
-            raise BacksimUnavailable(name, self.name)
-        if name in PATHS_PROTOTYPES and not self.has_paths:
-            raise PathsUnavailable(name, self.name)
-        if name in GUIDED_PROTOTYPES and not self.has_guided:
-            raise GuidedUnavailable(name, self.name)
+        h = _HEADER_OF.get(name)
+        if h is not None and not self.has[h.key]:
+            raise h.unavailable(name, self.name)
         rc = getattr(self, "_" + name)(*args)
         if name not in _NO_STATUS and rc != GJX_OK:
             raise GjxError(name, rc)

@@ -444,6 +444,25 @@ class Ops:
         self.lib.call("gjx_gather_cols", C.c_void_p(ancestors.data_ptr()), n_out, src, dst, len(cols), self.stream())
         return outs
 
+    def _history_io(self, io, cols, T, n, m, lineage, paths, dtype_ok, is_dtype, dtype, error):
+        """The columns of a recorded history in a PathsIO / BacksimIO: the [T, n] inputs `cols` (row-strided views are taken
+        as they are; `dtype_ok(col)` else ValueError(`error`); `is_dtype[c]` = 1 where column c is `dtype`) and the [T, m]
+        outputs asked for -> (lineage int32[T, m] or None, paths [col dtype [T, m]] or None)."""
+        lin, outs = None, [] if paths else None
+        if lineage:
+            lin = self.empty((T, m), torch.int32)
+            io.lineage_out, io.lineage_stride = lin.data_ptr(), m
+        for c, col in enumerate(cols):
+            if col.shape != (T, n) or not dtype_ok(col) or col.stride(1) != 1 or col.device.type != self.device_type:
+                raise ValueError(error)
+            io.cols[c], io.col_stride[c] = col.data_ptr(), col.stride(0) if T > 1 else n
+            is_dtype[c] = 1 if col.dtype == dtype else 0
+            if paths:
+                o = self.empty((T, m), col.dtype)
+                outs.append(o)
+                io.paths_out[c], io.paths_stride[c] = o.data_ptr(), m
+        return lin, outs
+
     # ---- trajectory trace-back over a recorded history (include/gjx_paths.h) ----------------------
     def paths_trace(self, ancestors: torch.Tensor, cols: list, leaves: torch.Tensor | None = None, *, lineage: bool = True,
                     paths: bool = True, sums: bool = False, unique: bool = False, leaves_ordered: bool = False,
@@ -453,8 +472,7 @@ class Ops:
         paths [col dtype [T, m]], sum / sumsq float64[len(cols), T] (rows of int32 columns are 0), unique int64[T]), each
         None unless asked for.  `unique` needs non-decreasing leaves, declared with `leaves_ordered` (identity leaves are).
         Raises abi.PathsUnavailable on a library without include/gjx_paths.h (the CPU oracle)."""
-        if not self.lib.has_paths:
-            raise abi.PathsUnavailable("gjx_paths_trace", self.lib.name)
+        self.lib.require("paths", "gjx_paths_trace")
         if ancestors.dim() != 2 or ancestors.dtype != torch.int32 or ancestors.stride(1) != 1 or ancestors.device.type != self.device_type:
             raise ValueError("paths_trace: ancestors must be an int32 [T, n] device tensor with contiguous rows")
         T, n = ancestors.shape
@@ -467,20 +485,9 @@ class Ops:
         if leaves is not None:
             io.leaves = self._chk(leaves, torch.int32, name="leaves").value
         out = dict(lineage=None, paths=None, sum=None, sumsq=None, unique=None)
-        if lineage:
-            out["lineage"] = self.empty((T, m), torch.int32)
-            io.lineage_out, io.lineage_stride = out["lineage"].data_ptr(), m
-        if paths:
-            out["paths"] = []
-        for c, col in enumerate(cols):
-            if col.shape != (T, n) or col.element_size() != 4 or col.stride(1) != 1 or col.device.type != self.device_type:
-                raise ValueError("paths_trace: columns must be 4-byte [T, n] device tensors with contiguous rows")
-            io.cols[c], io.col_stride[c] = col.data_ptr(), col.stride(0) if T > 1 else n
-            io.col_is_f32[c] = 1 if col.dtype == torch.float32 else 0
-            if paths:
-                o = self.empty((T, m), col.dtype)
-                out["paths"].append(o)
-                io.paths_out[c], io.paths_stride[c] = o.data_ptr(), m
+        out["lineage"], out["paths"] = self._history_io(
+            io, cols, T, n, m, lineage, paths, lambda col: col.element_size() == 4, io.col_is_f32, torch.float32,
+            "paths_trace: columns must be 4-byte [T, n] device tensors with contiguous rows")
         ws, nb = None, 0
         if (sums and cols) or unique:
             if sums and cols:
@@ -501,8 +508,7 @@ class Ops:
     def backsim_plan_create(self, table) -> "BacksimPlan":
         """`table`: a smc_plan.TransitionTable.  Raises abi.BacksimUnavailable on a library without include/gjx_backsim.h
         (the CPU oracle), before any table it would misread is handed over."""
-        if not self.lib.has_backsim:
-            raise abi.BacksimUnavailable("gjx_backsim_plan_create", self.lib.name)
+        self.lib.require("backsim", "gjx_backsim_plan_create")
         arr = (abi.Site * max(1, len(table.sites)))(*table.sites)
         handle = C.c_void_p()
         self.lib.call("gjx_backsim_plan_create", arr, len(table.sites), table.n_state, table.n_obs, 0, C.byref(handle))
@@ -518,8 +524,7 @@ class Ops:
         without).  -> dict(lineage int32[T, m], paths [col dtype [T, m]]), each None unless asked for."""
         import numpy as np
 
-        if not self.lib.has_backsim:
-            raise abi.BacksimUnavailable("gjx_backsim_run", self.lib.name)
+        self.lib.require("backsim", "gjx_backsim_run")
         if len(cols) != plan.n_state:
             raise ValueError(f"backsim_run: the plan has {plan.n_state} state columns, got {len(cols)}")
         if logw.dim() != 2 or logw.dtype != torch.float32 or logw.stride(1) != 1 or logw.device.type != self.device_type:
@@ -529,22 +534,9 @@ class Ops:
         io.n_steps, io.impl, io.n, io.m = T, key.impl, n, int(m)
         io.key[0], io.key[1], io.key_lane = key.k0, key.k1, key.lane
         io.logw, io.logw_stride = logw.data_ptr(), logw.stride(0) if T > 1 else n
-        out = dict(lineage=None, paths=None)
-        if lineage:
-            out["lineage"] = self.empty((T, m), torch.int32)
-            io.lineage_out, io.lineage_stride = out["lineage"].data_ptr(), m
-        if paths:
-            out["paths"] = []
-        for c, col in enumerate(cols):
-            if (col.shape != (T, n) or col.dtype not in (torch.float32, torch.int32) or col.stride(1) != 1
-                    or col.device.type != self.device_type):
-                raise ValueError("backsim_run: columns must be float32 / int32 [T, n] device tensors with contiguous rows")
-            io.cols[c], io.col_stride[c] = col.data_ptr(), col.stride(0) if T > 1 else n
-            io.col_is_i32[c] = 1 if col.dtype == torch.int32 else 0
-            if paths:
-                o = self.empty((T, m), col.dtype)
-                out["paths"].append(o)
-                io.paths_out[c], io.paths_stride[c] = o.data_ptr(), m
+        out = dict(zip(("lineage", "paths"), self._history_io(
+            io, cols, T, n, m, lineage, paths, lambda col: col.dtype in (torch.float32, torch.int32), io.col_is_i32, torch.int32,
+            "backsim_run: columns must be float32 / int32 [T, n] device tensors with contiguous rows")))
         y = None
         if plan.n_obs:
             y = np.ascontiguousarray(np.asarray(obs, dtype=np.float32).reshape(T, -1)[:, :plan.n_obs])
@@ -647,8 +639,8 @@ class Ops:
                         guided: bool = False) -> "SmcPlan":
         """`guided`: the tables may hold proposed / guided sites (include/gjx_guided.h: gjx_smc_plan_create_guided; raises
         abi.GuidedUnavailable on a library without that header — the CPU oracle)."""
-        if guided and not self.lib.has_guided:
-            raise abi.GuidedUnavailable("gjx_smc_plan_create_guided", self.lib.name)
+        if guided:
+            self.lib.require("guided", "gjx_smc_plan_create_guided")
         if guided and (init_scopes or step_scopes):
             raise ValueError("a guided plan has flat bodies (gjx_smc_plan_create_guided takes no scopes)")
         m = abi.SmcModel()

@@ -261,8 +261,7 @@ class BootstrapSMC:
         if result.history is None or result.log_weight_history is None:
             raise ValueError("backward_simulate() needs the per-step states: run the filter with BootstrapSMC(..., record_history=True)")
         ops = get_ops()
-        if not ops.lib.has_backsim:
-            raise abi.BacksimUnavailable("gjx_backsim_run", ops.lib.name)
+        ops.lib.require("backsim", "gjx_backsim_run")
         if self._transition is None:
             table, obs = self._bind(ops).transition_table()
             self._transition = (ops.backsim_plan_create(table), obs)

@@ -199,8 +199,7 @@ def build_guided_plan(model: StateSpaceModel, obs_addrs: list[tuple], step_propo
     if len(obs_addrs) > abi.SMC_MAX_OBS:
         raise PlanUnsupported(f"at most {abi.SMC_MAX_OBS} observed addresses per step")
     ops = get_ops()
-    if not ops.lib.has_guided:  # (before any table is built: the oracle would misread the two site modes)
-        raise abi.GuidedUnavailable("gjx_smc_plan_create_guided", ops.lib.name)
+    ops.lib.require("guided", "gjx_smc_plan_create_guided")  # (before any table is built: the oracle would misread the two site modes)
     obs_index = {a: k for k, a in enumerate(obs_addrs)}
 
     def obs_arg(tr):

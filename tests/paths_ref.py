@@ -1,10 +1,11 @@
 """Shared by the history / trace-back tests (CPU and GPU): the filters of the test grid, the numpy reference of
-include/gjx_paths.h, and a float64 Kalman + RTS smoother for the benchmark LGSSM."""
+include/gjx_paths.h, and the check of smoothing means against the exact smoother (backsim_ref.lgssm_rts)."""
 
 import numpy as np
 import torch
 
 import genjax
+from backsim_ref import lgssm_rts
 from genjax import ChoiceMapBuilder as C, gen, normal
 from genjax._amd import workloads as W
 from genjax._amd.smc_fused import DiscreteHMM, LinearGaussianSSM, StateSpaceModel
@@ -63,28 +64,6 @@ def trace_ref(anc, cols, leaves, n: int):
     return lin.astype(np.int32), paths, unique
 
 
-def rts_smoother_mean(y):
-    """E[x_t | y_0:T-1] of workloads.LGSSM in float64: Kalman filter forward, Rauch-Tung-Striebel backward."""
-    L = W.LGSSM
-    a, q2, r2 = L["a"], L["q"] ** 2, L["r"] ** 2
-    y = np.asarray(y, dtype=np.float64)
-    T = len(y)
-    mf, pf, mp, pp = np.empty(T), np.empty(T), np.empty(T), np.empty(T)
-    m, p = L["x0_loc"], L["x0_scale"] ** 2
-    for t in range(T):
-        if t:
-            m, p = a * m, a * a * p + q2
-        mp[t], pp[t] = m, p
-        k = p / (p + r2)
-        m, p = m + k * (y[t] - m), (1 - k) * p
-        mf[t], pf[t] = m, p
-    ms = mf.copy()
-    for t in range(T - 2, -1, -1):
-        g = pf[t] * a / pp[t + 1]
-        ms[t] = mf[t] + g * (ms[t + 1] - mp[t + 1])
-    return ms
-
-
 STAT_N, STAT_R, STAT_T = 200_000, 16, 8
 
 
@@ -97,7 +76,7 @@ def check_smoothing_means(means):
     deviation over the runs / sqrt(R)) of the exact smoother, at every t.  -> the z scores."""
     means = np.asarray(means, dtype=np.float64)
     R = means.shape[0]
-    exact = rts_smoother_mean(W.lgssm_data(STAT_T))
+    exact = lgssm_rts(W.lgssm_data(STAT_T))[0]  # E[x_t | y_0:T-1]
     se = means.std(axis=0, ddof=1) / np.sqrt(R)
     z = (means.mean(axis=0) - exact) / se
     print("smoothing z scores:", np.round(z, 2), "standard errors:", se)

@@ -4,9 +4,7 @@ generated kernels compiled for gfx950 offline (libgjx_hip.so loaded without a de
 tests/backsim_ref.py held against exact smoothers."""
 
 import ctypes as C
-import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -17,36 +15,15 @@ import backsim_ref as B
 import genjax
 from genjax import ChoiceMapBuilder as Cm, gen, normal
 from genjax._amd import abi, workloads as W
-from genjax._amd.abi import GjxError, GjxLib
-from genjax._amd.ops import Ops
+from genjax._amd.abi import GjxError
 from genjax._amd.plan import PlanUnsupported
 from genjax._amd.runtime import use_ops
 from genjax._amd.smc_models import HmmFilter, LgssmFilter
 from genjax._amd.smc_plan import build_smc_plan, build_transition_table
 from genjax.inference.smc import BootstrapSMC, DiscreteHMM, LinearGaussianSSM, StateSpaceModel
+from offline import kernel_notes, llvm_tool, ops  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB_DIR = os.path.join(ROOT, "genjax-chi_amd", "lib")
-HIP_LIB = os.path.join(LIB_DIR, "libgjx_hip.so")
-JITC = os.path.join(LIB_DIR, "gjx_jitc")
-DEVICE_HDR = os.path.join(ROOT, "genjax-chi_amd", "csrc", "gjx_device.hpp")
-OPTIONS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"]  # gjx_plan_jit.hpp compile_options()
 Y = [("y",)]
-
-
-@pytest.fixture(scope="module")
-def ops():
-    if not os.path.exists(HIP_LIB) or not os.path.exists(JITC):
-        import __graft_entry__ as g
-
-        g.build()
-    return Ops(GjxLib(HIP_LIB, "cuda"))  # no compute calls below: plans are host objects
-
-
-def _symbols(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return set(re.findall(r"\b(gjx_[a-z0-9_]+)\s*\(", txt))
 
 
 def _table(ops, model, addrs=Y):
@@ -54,27 +31,7 @@ def _table(ops, model, addrs=Y):
         return build_transition_table(StateSpaceModel(*model), addrs)
 
 
-# ---- the header ------------------------------------------------------------------------------------------------------
-def test_fourth_header_is_exported_by_the_hip_library_only(ops, oracle_ops):
-    syms = _symbols("gjx_backsim.h")
-    assert syms == set(abi.BACKSIM_PROTOTYPES) == {
-        "gjx_backsim_version", "gjx_backsim_plan_create", "gjx_backsim_plan_destroy", "gjx_backsim_plan_source",
-        "gjx_backsim_plan_compile_check", "gjx_backsim_workspace_bytes", "gjx_backsim_run"}
-    for other in ("gjx.h", "gjx_paths.h", "gjx_guided.h"):
-        assert not (syms & _symbols(other))
-    assert not (syms & set(abi.PROTOTYPES))
-    for name in syms:
-        assert hasattr(ops.lib._dll, name) and not hasattr(oracle_ops.lib._dll, name), name
-    assert ops.lib.has_backsim and not oracle_ops.lib.has_backsim
-    major, minor = C.c_int(-1), C.c_int(-1)
-    ops.lib.call("gjx_backsim_version", C.byref(major), C.byref(minor))
-    assert (major.value, minor.value) == abi.BACKSIM_ABI_VERSION
-    hdr = open(os.path.join(ROOT, "include", "gjx_backsim.h")).read()
-    assert f"GJX_BACKSIM_VERSION_MAJOR {major.value}" in hdr and f"GJX_BACKSIM_VERSION_MINOR {minor.value}" in hdr
-    assert f"GJX_ARG_NEXT {abi.ARG_NEXT}" in hdr
-    assert ops.lib.call("gjx_backsim_workspace_bytes", 100, 1024) == 100 * 1024 * 8
-
-
+# ---- the header (that it is exported by the HIP library only: test_paths_abi.py, with the other optional headers) ---------
 def test_oracle_bound_ops_raise_unavailable(oracle_ops):
     y = W.lgssm_data(6)
     alg = BootstrapSMC(LinearGaussianSSM(), y, 512, record_history=True)
@@ -297,36 +254,13 @@ def test_the_creators_of_gjx_h_reject_the_new_kind(ops, oracle_ops):
 
 
 # ---- offline compilation -----------------------------------------------------------------------------------------------
-def _readelf():
-    for cand in ("/opt/rocm/llvm/bin/llvm-readelf", "/opt/rocm/lib/llvm/bin/llvm-readelf"):
-        if os.path.exists(cand):
-            return cand
-    return shutil.which("llvm-readelf")
-
-
-def _objdump():
-    for cand in ("/opt/rocm/llvm/bin/llvm-objdump", "/opt/rocm/lib/llvm/bin/llvm-objdump"):
-        if os.path.exists(cand):
-            return cand
-    return shutil.which("llvm-objdump")
-
-
-def _compile(src, tmp_path, name):
-    fsrc, fout, flog = (str(tmp_path / f"{name}.{ext}") for ext in ("hip", "co", "log"))
-    with open(fsrc, "w") as f:
-        f.write(src)
-    r = subprocess.run([JITC, fsrc, DEVICE_HDR, fout, flog, *OPTIONS], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.returncode, open(flog).read() if os.path.exists(flog) else r.stderr)
-    return fout
-
-
 def inner_loop_instructions(code_object, kernel="gjx_backsim_step_kernel"):
     """Lane-instructions per candidate-trajectory PAIR, counted from the disassembly: the candidate loop is the smallest
     backward branch of the kernel whose body holds the cipher's multiplies; one trip serves 2 candidates x kBacksimBlock
     trajectories.  Every instruction of the body is counted once, the rarely taken special-case blocks of the spec's
     logarithm included: an upper bound on what a trip issues.  -> dict(per_pair, valu, mad_u64 (the cipher's multiplies),
     salu, memory, pairs), or None without llvm-objdump."""
-    dump = _objdump()
+    dump = llvm_tool("llvm-objdump")
     if dump is None:
         return None
     txt = subprocess.run([dump, "-d", "--no-show-raw-insn", code_object], capture_output=True, text=True, timeout=120).stdout
@@ -373,21 +307,12 @@ def test_generated_kernels_compile_offline(ops, oracle_ops, tmp_path):
 
 
 def test_philox_lgssm_kernel_occupancy_and_inner_loop(ops, tmp_path):
-    readelf = _readelf()
-    if readelf is None:
-        pytest.skip("llvm-readelf is not installed")
     plan = ops.backsim_plan_create(_table(ops, B.lgssm_model()))
-    co = _compile(plan.source(1), tmp_path, "backsim_lgssm")
-    notes = subprocess.run([readelf, "--notes", co], capture_output=True, text=True, timeout=60).stdout
-    metas = {}
-    for name, blob in re.findall(r"\.name:\s+(gjx_backsim_\w+_kernel)\n(.*?)(?=\.name:|\Z)", notes, flags=re.S):
-        metas[name] = {k: int(v) for k, v in re.findall(r"\.(vgpr_count|agpr_count|private_segment_fixed_size|sgpr_count):\s+(\d+)", blob)}
-    if "gjx_backsim_step_kernel" not in metas or len(metas["gjx_backsim_step_kernel"]) < 3:  # (field order differs between toolchains)
-        allv = {k: [int(v) for v in re.findall(rf"\.{k}:\s+(\d+)", notes)] for k in ("vgpr_count", "agpr_count", "private_segment_fixed_size")}
-        metas = {"gjx_backsim_step_kernel": {k: max(v) for k, v in allv.items()}}
-    meta = metas["gjx_backsim_step_kernel"]
+    metas = kernel_notes(plan.source(1), tmp_path, "backsim_lgssm")
+    co = str(tmp_path / "backsim_lgssm.co")
     print("PHILOX LGSSM backward-simulation step kernel:", metas)
-    assert "gjx_backsim_step_kernel" in notes and "gjx_backsim_last_kernel" in notes
+    assert "gjx_backsim_step_kernel" in metas and "gjx_backsim_last_kernel" in metas
+    meta = metas["gjx_backsim_step_kernel"]
     assert meta["private_segment_fixed_size"] == 0 and meta["agpr_count"] == 0, meta
     assert meta["vgpr_count"] <= 128, meta  # four waves per SIMD of 512 registers
     loop = inner_loop_instructions(co)

@@ -4,10 +4,7 @@ creators' validation, and the generated kernels compiled for gfx950 offline (lib
 test_plan_specialization.py does)."""
 
 import ctypes as C
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 import torch
@@ -16,36 +13,15 @@ import genjax
 import guided_ref as G
 from genjax import ChoiceMapBuilder as Cm, flip, gen, normal
 from genjax._amd import abi
-from genjax._amd.abi import GjxError, GjxLib
-from genjax._amd.ops import Ops
+from genjax._amd.abi import GjxError
 from genjax._amd.plan import PlanUnsupported
 from genjax._amd.runtime import use_ops
 from genjax._amd.smc_plan import build_guided_plan, build_smc_plan
 from genjax.inference.smc import GuidedSMC, StateSpaceModel
+from offline import kernel_notes, ops  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB_DIR = os.path.join(ROOT, "genjax-chi_amd", "lib")
-HIP_LIB = os.path.join(LIB_DIR, "libgjx_hip.so")
-JITC = os.path.join(LIB_DIR, "gjx_jitc")
-DEVICE_HDR = os.path.join(ROOT, "genjax-chi_amd", "csrc", "gjx_device.hpp")
-OPTIONS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"]  # gjx_plan_jit.hpp compile_options()
 R = 0.05
 Y = [("y",)]
-
-
-@pytest.fixture(scope="module")
-def ops():
-    if not os.path.exists(HIP_LIB) or not os.path.exists(JITC):
-        import __graft_entry__ as g
-
-        g.build()
-    return Ops(GjxLib(HIP_LIB, "cuda"))  # no compute calls below: plans are host objects
-
-
-def _symbols(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return set(re.findall(r"\b(gjx_[a-z0-9_]+)\s*\(", txt))
 
 
 def _lgssm_guided(ops, with_init=True):
@@ -55,22 +31,7 @@ def _lgssm_guided(ops, with_init=True):
         return build_guided_plan(StateSpaceModel(init, step), Y, tq, sq if with_init else None)[0]
 
 
-# ---- the header ------------------------------------------------------------------------------------------------------
-def test_third_header_is_exported_by_the_hip_library_only(ops, oracle_ops):
-    guided = _symbols("gjx_guided.h")
-    assert guided == set(abi.GUIDED_PROTOTYPES) == {"gjx_guided_version", "gjx_smc_plan_create_guided", "gjx_smc_plan_source"}
-    assert not (guided & _symbols("gjx.h")) and not (guided & set(abi.PROTOTYPES)) and not (guided & _symbols("gjx_paths.h"))
-    for name in guided:
-        assert hasattr(ops.lib._dll, name) and not hasattr(oracle_ops.lib._dll, name), name
-    assert ops.lib.has_guided and not oracle_ops.lib.has_guided
-    major, minor = C.c_int(-1), C.c_int(-1)
-    ops.lib.call("gjx_guided_version", C.byref(major), C.byref(minor))
-    assert (major.value, minor.value) == abi.GUIDED_ABI_VERSION
-    hdr = open(os.path.join(ROOT, "include", "gjx_guided.h")).read()
-    assert f"GJX_GUIDED_VERSION_MAJOR {major.value}" in hdr and f"GJX_GUIDED_VERSION_MINOR {minor.value}" in hdr
-    assert f"GJX_SITE_PROPOSED {abi.SITE_PROPOSED}" in hdr and f"GJX_SITE_GUIDED {abi.SITE_GUIDED}" in hdr
-
-
+# ---- the header (that it is exported by the HIP library only: test_paths_abi.py, with the other optional headers) ---------
 def test_oracle_bound_ops_refuse_guided_filters(oracle_ops):
     init, step = G.lgssm_model(R)
     tq, sq, _ = G.lgssm_optimal(R)
@@ -343,39 +304,14 @@ def test_guided_plans_compile_for_both_generators(ops, impl):
         assert "philox4x32(" not in quad  # (nothing is drawn twice: the guided site draws nothing)
 
 
-def _readelf():
-    for cand in ("/opt/rocm/llvm/bin/llvm-readelf", "/opt/rocm/lib/llvm/bin/llvm-readelf"):
-        if os.path.exists(cand):
-            return cand
-    return shutil.which("llvm-readelf")
-
-
-def _kernel_notes(src, tmp_path, name):
-    """As test_importance_occupancy.kernel_notes, per kernel of a generated SMC source: {kernel: {field: int}}."""
-    readelf = _readelf()
-    if readelf is None:
-        pytest.skip("llvm-readelf is not installed")
-    fsrc, fout, flog = (str(tmp_path / f"{name}.{ext}") for ext in ("hip", "co", "log"))
-    with open(fsrc, "w") as f:
-        f.write(src)
-    r = subprocess.run([JITC, fsrc, DEVICE_HDR, fout, flog, *OPTIONS], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.returncode, open(flog).read() if os.path.exists(flog) else r.stderr)
-    notes = subprocess.run([readelf, "--notes", fout], capture_output=True, text=True, timeout=60).stdout
-    out = {}
-    for blk in notes.split("- .agpr_count")[1:]:
-        kname = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        out[kname] = {k: int(v) for k, v in re.findall(r"\.(vgpr_count|private_segment_fixed_size|sgpr_count):\s+(\d+)", blk)}
-    return out
-
-
 def test_guided_step_kernel_has_no_scratch(ops, tmp_path):
     """The PHILOX step kernel of the guided LGSSM (quad form: lq of four slots lives from the proposal to its partner)
     against the bootstrap plan of the same model; figures in profiles/guided_summary.md."""
     init, step = G.lgssm_model(R)
     with use_ops(ops):
         boot = build_smc_plan(StateSpaceModel(init, step), Y)[0]
-    guided = _kernel_notes(_plans(ops)["lgssm"].source(1), tmp_path, "guided")
-    plain = _kernel_notes(boot.source(1), tmp_path, "bootstrap")
+    guided = kernel_notes(_plans(ops)["lgssm"].source(1), tmp_path, "guided")
+    plain = kernel_notes(boot.source(1), tmp_path, "bootstrap")
     for k in ("gjx_smc_step_kernel", "gjx_smc_step_kernel_adaptive", "gjx_smc_init_kernel"):
         print(f"{k}: guided {guided[k]}  bootstrap {plain[k]}")
     assert guided["gjx_smc_step_kernel"]["private_segment_fixed_size"] == 0

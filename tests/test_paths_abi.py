@@ -1,49 +1,60 @@
-"""include/gjx_paths.h: a second header next to gjx.h.  libgjx_hip.so exports it, the ctypes table covers it, gjx.h
-and the oracle library know nothing of it, and host-side validation refuses bad calls before any launch (no GPU
-needed for any of this)."""
+"""The optional headers next to gjx.h (gjx_paths.h, gjx_guided.h, gjx_backsim.h): libgjx_hip.so exports them, the ctypes
+tables cover them, gjx.h and the oracle library know nothing of them.  And include/gjx_paths.h itself: host-side validation
+refuses bad calls before any launch (no GPU needed for any of this)."""
 
 import ctypes as C
 import os
-import re
 
 import pytest
 import torch
 
 from genjax._amd import abi
-from genjax._amd.abi import GjxError, GjxLib
+from genjax._amd.abi import GjxError
 from genjax._amd.ops import Ops
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIP_LIB = os.path.join(ROOT, "genjax-chi_amd", "lib", "libgjx_hip.so")
-
-
-def _symbols(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return set(re.findall(r"\b(gjx_[a-z0-9_]+)\s*\(", txt))
+from offline import ROOT, header_symbols, ops  # noqa: F401
 
 
 @pytest.fixture(scope="module")
-def hip_lib():
-    if not os.path.exists(HIP_LIB):
-        import __graft_entry__ as g
-
-        g.build()
-    return GjxLib(HIP_LIB, "cuda")  # loading needs no GPU
+def hip_lib(ops):
+    return ops.lib
 
 
-def test_tables_match_the_headers(hip_lib):
-    paths = _symbols("gjx_paths.h")
-    assert paths == set(abi.PATHS_PROTOTYPES) == {"gjx_paths_version", "gjx_paths_workspace_bytes", "gjx_paths_trace"}
-    assert not (paths & _symbols("gjx.h")) and not (paths & set(abi.PROTOTYPES))
-    for name in paths:
-        assert hasattr(hip_lib._dll, name), name
-    assert hip_lib.has_paths
+# per optional header: the symbols it declares, and the constants the binding restates as the header's text has them
+HEADERS = dict(
+    paths=({"gjx_paths_version", "gjx_paths_workspace_bytes", "gjx_paths_trace"},
+           ["GJX_PATHS_MAX_COLS (GJX_SMC_MAX_STATE + 1)", f"GJX_PATHS_LEAVES_ORDERED {abi.PATHS_LEAVES_ORDERED}u"]),
+    guided=({"gjx_guided_version", "gjx_smc_plan_create_guided", "gjx_smc_plan_source"},
+            [f"GJX_SITE_PROPOSED {abi.SITE_PROPOSED}", f"GJX_SITE_GUIDED {abi.SITE_GUIDED}"]),
+    backsim=({"gjx_backsim_version", "gjx_backsim_plan_create", "gjx_backsim_plan_destroy", "gjx_backsim_plan_source",
+              "gjx_backsim_plan_compile_check", "gjx_backsim_workspace_bytes", "gjx_backsim_run"},
+             [f"GJX_ARG_NEXT {abi.ARG_NEXT}"]))
+
+
+@pytest.mark.parametrize("key", list(abi.OPTIONAL_HEADERS))
+def test_optional_header_is_exported_by_the_hip_library_only(hip_lib, oracle_ops, key):
+    h = abi.OPTIONAL_HEADERS[key]
+    symbols, constants = HEADERS[key]
+    syms = header_symbols(h.header)
+    assert syms == set(h.prototypes) == symbols and h.version_fn in syms
+    assert h.prototypes is getattr(abi, f"{key.upper()}_PROTOTYPES") and h.version == getattr(abi, f"{key.upper()}_ABI_VERSION")
+    assert not (syms & header_symbols("gjx.h")) and not (syms & set(abi.PROTOTYPES))
+    for other in abi.OPTIONAL_HEADERS.values():
+        if other is not h:
+            assert not (syms & header_symbols(other.header)) and not (syms & set(other.prototypes))
+    for name in syms:
+        assert hasattr(hip_lib._dll, name) and not hasattr(oracle_ops.lib._dll, name), name
+    assert getattr(hip_lib, f"has_{key}") and not getattr(oracle_ops.lib, f"has_{key}")
     major, minor = C.c_int(-1), C.c_int(-1)
-    hip_lib.call("gjx_paths_version", C.byref(major), C.byref(minor))
-    assert (major.value, minor.value) == abi.PATHS_ABI_VERSION
-    hdr = open(os.path.join(ROOT, "include", "gjx_paths.h")).read()
-    assert f"GJX_PATHS_VERSION_MAJOR {major.value}" in hdr and f"GJX_PATHS_VERSION_MINOR {minor.value}" in hdr
+    hip_lib.call(h.version_fn, C.byref(major), C.byref(minor))
+    assert (major.value, minor.value) == h.version
+    hdr = open(os.path.join(ROOT, "include", h.header)).read()
+    up = key.upper()
+    assert f"GJX_{up}_VERSION_MAJOR {major.value}" in hdr and f"GJX_{up}_VERSION_MINOR {minor.value}" in hdr
+    for text in constants:
+        assert text in hdr, text
+    assert abi.PATHS_MAX_COLS == abi.SMC_MAX_STATE + 1
+    if key == "backsim":
+        assert hip_lib.call("gjx_backsim_workspace_bytes", 100, 1024) == 100 * 1024 * 8
 
 
 def test_oracle_loads_without_them_and_says_so(oracle_ops):

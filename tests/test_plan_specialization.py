@@ -2,34 +2,12 @@
 compiles for gfx950 (hiprtc cross-compiles offline), for both RNG schemes and for plans touching
 every distribution / argument kind."""
 
-import ctypes as C
 import os
 
 import pytest
 
 from genjax._amd import abi, workloads as W
-from genjax._amd.abi import GjxLib
-from genjax._amd.ops import Ops
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIP_LIB = os.path.join(ROOT, "genjax-chi_amd", "lib", "libgjx_hip.so")
-
-
-@pytest.fixture(scope="module")
-def hip_lib_nogpu():
-    if not os.path.exists(HIP_LIB):
-        import __graft_entry__ as g
-
-        g.build()
-    return Ops(GjxLib(HIP_LIB, "cuda"))  # no compute calls below: plans are host objects
-
-
-def source_of(ops, plan, impl):
-    need = C.c_size_t()
-    ops.lib.call("gjx_plan_specialized_source", plan.handle, impl, None, 0, C.byref(need))
-    buf = C.create_string_buffer(need.value)
-    ops.lib.call("gjx_plan_specialized_source", plan.handle, impl, buf, need.value, None)
-    return buf.value.decode()
+from offline import HIP_LIB, ROOT, importance_source as source_of, ops as hip_lib_nogpu  # noqa: F401
 
 
 @pytest.mark.parametrize("impl", [0, 1])
