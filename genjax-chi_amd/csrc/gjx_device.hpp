@@ -1540,6 +1540,26 @@ GJX_HD uint32_t backsim_index(unsigned long long w, uint32_t n) {  // always a v
   return i < n ? i : n - 1u;
 }
 
+// Kernel argument block of one step of the MCMC backward sampler (include/gjx_backmove.h; the kernels are generated from
+// the transition table, gjx_plan_jit.hpp GenBackmove).  Rows are those of step t.
+struct BackmoveArgs {
+  const uint32_t* col[4];       // state columns, row t
+  const uint32_t* col_next[4];  // ... row t + 1 (unused by the last step's kernel)
+  uint32_t* path[4];            // path values, row t (each nullable)
+  const uint64_t* cdf;          // [n] inclusive fixed-point CDF of lw[t] (null where the step draws nothing)
+  const int32_t* anc_next;      // ancestors, row t + 1
+  const int32_t* lin_next;      // [m] lineage, row t + 1
+  int32_t* lin;                 // [m] lineage, row t
+  float obs[8];                 // observation row t + 1
+  Key pk, ak;                   // fold_in(k_t, 0) proposals, fold_in(k_t, 1) acceptance: lane 0
+  uint32_t n, m;
+  uint32_t n_moves;
+  uint32_t i32_mask;            // bit c: column c holds int32
+  uint32_t coarse;              // != 0: two-level search, the tile ends of the CDF staged in LDS (n <= kBackmoveLdsTiles tiles)
+};
+constexpr uint32_t kBackmoveTile = 1024;      // CDF entries per coarse-level entry (8 KB: at most 10 dependent reads inside)
+constexpr uint32_t kBackmoveLdsTiles = 2048;  // 16 KB of LDS: populations up to 2^21 take the two-level search
+
 template <int N>
 struct IntC {
   static constexpr int value = N;

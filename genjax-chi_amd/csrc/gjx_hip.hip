@@ -10,6 +10,7 @@
 #include "../../include/gjx.h"
 #include "../../include/gjx_guided.h"
 #include "../../include/gjx_backsim.h"
+#include "../../include/gjx_backmove.h"
 #include "gjx_device.hpp"
 
 #include <hip/hip_runtime.h>
@@ -4206,6 +4207,7 @@ struct gjx_backsim_plan {
   std::vector<void*> dev_owned;  // per-row tables of categorical sites
   std::mutex mu;
   gjx_jit::CompiledBacksim jit[2];
+  gjx_jit::CompiledBacksim move_jit[2];  // the MCMC move kernels of the same table (include/gjx_backmove.h)
 };
 
 namespace {
@@ -4281,6 +4283,7 @@ int gjx_backsim_plan_create(const gjx_site* sites, int n_sites, int n_state, int
 int gjx_backsim_plan_destroy(gjx_backsim_plan* p) {
   if (!p) return GJX_OK;
   for (auto& c : p->jit) c.release();
+  for (auto& c : p->move_jit) c.release();
   free_owned(p->dev_owned);
   delete p;
   return GJX_OK;
@@ -4367,6 +4370,153 @@ int gjx_backsim_run(gjx_backsim_plan* p, const gjx_backsim_io* io, void* ws, siz
   unsigned fgrid = (unsigned)(fb < 4096 ? fb : 4096);
   if (io->max_workgroups && fgrid > io->max_workgroups) fgrid = io->max_workgroups;
   k_backsim_finish<<<fgrid, kBlock, 0, S(s)>>>(F);
+  return launch_status();
+}
+
+}  // extern "C"
+
+// =====================================================================================================================
+// MCMC backward simulation on a backward-simulation plan (include/gjx_backmove.h; kernels generated by gjx_plan_jit.hpp
+// GenBackmove)
+// =====================================================================================================================
+namespace {
+constexpr unsigned kBackmoveMaxGrid = 256 * 8;  // workgroups of 256 paths, grid-stride beyond (the LDS stage is per workgroup)
+
+std::string backmove_source(const gjx_backsim_plan* p, int impl, PlanTables* tabs = nullptr) {
+  gjx_jit::TableScope ts;
+  gjx_jit::GenBackmove<CSite, CArg> g;
+  g.impl = impl; g.sites = p->sites; g.n_sites = p->n_sites; g.n_state = p->n_state;
+  std::string src = g.run();
+  if (tabs) *tabs = ts.reg.tables();
+  return src;
+}
+
+gjx_jit::CompiledBacksim* backmove_compiled(gjx_backsim_plan* p, int impl) {
+  gjx_jit::CompiledBacksim& c = p->move_jit[impl];
+  const bool ready = compiled_once(p->mu, c, {{p->sites, p->n_sites}}, &p->dev_owned, [&] {
+    return c.load(backmove_source(p, impl, &c.tabs), {"gjx_backmove_step_kernel", "gjx_backmove_last_kernel"}, {&c.step, &c.last});
+  });
+  return ready ? &c : nullptr;
+}
+
+// The scratch of a run, carved in one order by the size function and the driver: the front half of a multinomial
+// resampling (weights_prepare: tile maxima, tile masses, the maximum), the CDF, and the lineage rows of a call without
+// lineage_out.
+struct BackmoveScratch {
+  float* mp;
+  uint64_t* tiles;
+  float* mx;
+  uint64_t* cdf;
+  int32_t* lineage;
+};
+bool backmove_carve(Carver& cv, uint32_t T, uint64_t n, uint64_t m, BackmoveScratch* out) {
+  const uint64_t nt = ntiles_of(n);
+  out->mp = cv.take<float>(nt);
+  out->tiles = cv.take<uint64_t>(nt);
+  out->mx = cv.take<float>(1);
+  out->cdf = cv.take<uint64_t>(n);
+  out->lineage = cv.take<int32_t>((size_t)T * m);
+  return cv.ok;
+}
+
+// test / measurement knob, read at every call: GJX_BACKMOVE_SEARCH=plain sends every search through the one-level halving of
+// the whole CDF (the same indices either way)
+bool backmove_coarse_knob() {
+  const char* e = std::getenv("GJX_BACKMOVE_SEARCH");
+  return !(e && e[0] == 'p');
+}
+}  // namespace
+
+extern "C" {
+
+int gjx_backmove_version(int* major, int* minor) { return version_out(major, minor, GJX_BACKMOVE_VERSION_MAJOR, GJX_BACKMOVE_VERSION_MINOR); }
+int gjx_backmove_plan_source(const gjx_backsim_plan* p, int impl, char* buf, size_t buf_len, size_t* needed) {
+  if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
+  return copy_source_out(backmove_source(p, impl), buf, buf_len, needed);
+}
+int gjx_backmove_plan_compile_check(const gjx_backsim_plan* p, int impl) {
+  if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
+  return gjx_jit::compile_only(backmove_source(p, impl)) ? GJX_OK : GJX_ERR_UNSUPPORTED;
+}
+size_t gjx_backmove_workspace_bytes(int32_t n_steps, uint64_t n, uint64_t m) {
+  if (n_steps < 1 || !backsim_size_ok(n) || !backsim_size_ok(m)) return 0;
+  Carver cv{nullptr, ~(size_t)0};
+  BackmoveScratch sc;
+  (void)backmove_carve(cv, (uint32_t)n_steps, n, m, &sc);
+  return ~(size_t)0 - cv.left;
+}
+int gjx_backmove_run(gjx_backsim_plan* p, const gjx_backmove_io* io, void* ws, size_t ws_bytes, gjx_stream s) {
+  if (!p || !io || io->n_steps < 1 || !backsim_size_ok(io->n) || !backsim_size_ok(io->m) || (io->impl != 0 && io->impl != 1) ||
+      (io->impl == 0 && io->key_lane != 0) || io->n_moves < 0 || io->n_moves > GJX_BACKMOVE_MAX_MOVES)
+    return GJX_ERR_INVALID;
+  const uint32_t T = (uint32_t)io->n_steps, n = (uint32_t)io->n, m = (uint32_t)io->m, K = (uint32_t)io->n_moves;
+  if ((uint64_t)m * (K ? K : 1u) >= (1ull << 31)) return GJX_ERR_INVALID;
+  if (!io->logw || io->logw_stride < io->n || io->logw_stride >= (1ull << 32) || (p->n_obs > 0 && !io->obs)) return GJX_ERR_INVALID;
+  if (!io->ancestors || io->anc_stride < io->n || io->anc_stride >= (1ull << 32)) return GJX_ERR_INVALID;
+  bool any_out = io->lineage_out != nullptr;
+  if (io->lineage_out && (io->lineage_stride < io->m || io->lineage_stride >= (1ull << 32))) return GJX_ERR_INVALID;
+  uint32_t i32_mask = 0;
+  for (int c = 0; c < p->n_state; ++c) {
+    if (!io->cols[c] || io->col_stride[c] < io->n || io->col_stride[c] >= (1ull << 32)) return GJX_ERR_INVALID;
+    if (io->paths_out[c] && (io->paths_stride[c] < io->m || io->paths_stride[c] >= (1ull << 32))) return GJX_ERR_INVALID;
+    any_out = any_out || io->paths_out[c];
+    if (io->col_is_i32[c]) i32_mask |= 1u << c;
+  }
+  if (!any_out || ((uintptr_t)ws & 7) != 0) return GJX_ERR_INVALID;
+  if (!ws || ws_bytes < gjx_backmove_workspace_bytes(io->n_steps, io->n, io->m)) return GJX_ERR_WORKSPACE;
+  if (!gjx_jit::enabled()) return GJX_ERR_UNSUPPORTED;  // generated kernels only, as gjx_backsim_run
+  gjx_jit::CompiledBacksim* k = backmove_compiled(p, io->impl);
+  if (!k) return GJX_ERR_JIT;
+
+  Carver cv{(char*)ws, ws_bytes};
+  BackmoveScratch sc;
+  if (!backmove_carve(cv, T, n, m, &sc)) return GJX_ERR_WORKSPACE;
+  int32_t* lin = io->lineage_out ? io->lineage_out : sc.lineage;
+  const uint64_t lin_stride = io->lineage_out ? io->lineage_stride : m;
+  const Key key{io->key[0], io->key[1], (uint32_t)io->key_lane, (uint32_t)(io->key_lane >> 32)};
+  const uint64_t nt = ntiles_of(n);
+  const uint32_t coarse = backmove_coarse_knob() && nt <= kBackmoveLdsTiles ? 1u : 0u;
+  const uint64_t wg = ((uint64_t)m + kBlock - 1) / kBlock;
+  unsigned grid = (unsigned)(wg < kBackmoveMaxGrid ? wg : kBackmoveMaxGrid);
+  if (io->max_workgroups && grid > io->max_workgroups) grid = io->max_workgroups;
+  for (uint32_t t = T; t-- > 0;) {
+    const bool last = t == T - 1;
+    BackmoveArgs A;
+    memset(&A, 0, sizeof A);
+    if (last || K > 0) {  // the CDF of lw[t], as gjx_resample_multinomial builds it
+      const float* lw = io->logw + (uint64_t)t * io->logw_stride;
+      Carver step_cv{(char*)ws, ws_bytes};  // the same buffers every step (backmove_carve's order: stream order makes the reuse safe)
+      float* mx;
+      uint64_t* tiles;
+      if (weights_prepare(lw, n, step_cv, &mx, &tiles, S(s)) != GJX_OK) return GJX_ERR_WORKSPACE;
+      k_cdf<<<(unsigned)nt, kBlock, 0, S(s)>>>(lw, n, mx, tiles, nt, frac_bits(n), sc.cdf);
+      A.cdf = sc.cdf;
+    }
+    for (int c = 0; c < p->n_state; ++c) {
+      const uint32_t* col = reinterpret_cast<const uint32_t*>(io->cols[c]);
+      A.col[c] = col + (uint64_t)t * io->col_stride[c];
+      A.col_next[c] = last ? nullptr : col + (uint64_t)(t + 1) * io->col_stride[c];
+      A.path[c] = io->paths_out[c] ? reinterpret_cast<uint32_t*>(io->paths_out[c]) + (uint64_t)t * io->paths_stride[c] : nullptr;
+    }
+    A.anc_next = last ? nullptr : io->ancestors + (uint64_t)(t + 1) * io->anc_stride;
+    A.lin_next = last ? nullptr : lin + (uint64_t)(t + 1) * lin_stride;
+    A.lin = lin + (uint64_t)t * lin_stride;
+    if (!last)
+      for (int c = 0; c < p->n_obs; ++c) A.obs[c] = io->obs[(size_t)(t + 1) * (size_t)p->n_obs + c];
+    const Key kt = io->impl == 0 ? fold_in<0>(key, t) : fold_in<1>(key, t);
+    A.pk = io->impl == 0 ? fold_in<0>(kt, 0u) : fold_in<1>(kt, 0u);
+    A.ak = io->impl == 0 ? fold_in<0>(kt, 1u) : fold_in<1>(kt, 1u);
+    A.n = n; A.m = m;
+    A.n_moves = K;
+    A.i32_mask = i32_mask;
+    A.coarse = coarse;
+    PlanTables tabs = k->tabs;
+    void* args[] = {&A, &tabs};
+    if (hipModuleLaunchKernel(last ? k->last : k->step, grid, 1, 1, kBlock, 1, 1, 0, S(s), args, nullptr) != hipSuccess) {
+      (void)hipGetLastError();
+      return GJX_ERR_LAUNCH;
+    }
+  }
   return launch_status();
 }
 

@@ -1257,6 +1257,106 @@ struct GenBacksim {
   }
 };
 
+// The kernels of the MCMC backward sampler (include/gjx_backmove.h) over the SAME transition table: trans_lp is emitted as
+// GenBacksim emits it, around it a LATENCY kernel — one lane per path, and per move a CDF search (dependent reads), a random
+// gather of the proposal's state and one transition density.  None of that depends on the chain's state, so a path's moves
+// are issued in blocks of 4 / 2 / 1 INDEPENDENT chains (bm_moves<B>: the B searches advance in lockstep, one load each per
+// round, a wave-uniform trip count — a finished search repeats its last read and changes nothing); only the B
+// compare-and-select steps at the end of a block are serial.
+//   search   bm_search returns cdf_upper_bound's index (gjx_hip.hip): the same halving of [lo, hi], run ceil(log2(size))
+//            times.  Two levels when a.coarse: the CDF's tile ends (entry 1024 k + 1023, the last one for the ragged tile)
+//            staged in LDS once per workgroup, then at most 10 rounds inside one 8 KB tile.  The CDF is non-decreasing, so
+//            the first entry above thr lies in the first tile whose END is above thr (the last tile if none is).
+//   keys     a.pk / a.ak have lane 0: under PHILOX the cipher key of every proposal and every uniform is wave-uniform.
+template <class CSiteT, class CArgT>
+struct GenBackmove {
+  std::ostringstream o;
+  int impl;
+  const CSiteT* sites;
+  int n_sites;
+  int n_state;
+
+  std::string run() {
+    const std::string I = std::to_string(impl);
+    emit_prelude(o);
+    std::string st_params, nx_params, st_args, nx_args;
+    for (int k = 0; k < n_state; ++k) {
+      const std::string K = std::to_string(k);
+      st_params += ", float st_" + K;
+      nx_params += ", float nx_" + K;
+      st_args += ", st[" + K + "]";
+      nx_args += ", nx[" + K + "]";
+    }
+    o << "__device__ __forceinline__ float trans_lp(const BackmoveArgs& a, const PlanTables& tabs" << st_params << nx_params << ") {\n";
+    for (int k = 0; k < n_state; ++k) o << "  (void)st_" << k << "; (void)nx_" << k << ";\n";
+    o << "  float w = 0.0f, sc = 0.0f;\n";
+    SiteEmitter<CSiteT, CArgT> e{o, impl, 1, sites, n_sites, "  ", ""};
+    e.run();
+    o << "  (void)sc;\n  return w;\n}\n";
+    o << "constexpr int D = " << n_state << ";\n";
+    o << "__device__ __forceinline__ float bm_col(uint32_t bits, bool is_i32) { return is_i32 ? (float)(int32_t)bits : u2f(bits); }\n";
+    o << "__device__ __forceinline__ float bm_score(const BackmoveArgs& a, const PlanTables& tabs, uint32_t i, const float (&nx)[D]) {\n";
+    o << "  float st[D];\n  for (int c = 0; c < D; ++c) st[c] = bm_col(a.col[c][i], (a.i32_mask >> c) & 1u);\n";
+    o << "  return trans_lp(a, tabs" << st_args << nx_args << ");\n}\n";
+    o << "__device__ __forceinline__ int bm_steps(uint32_t size) { return size > 1u ? 32 - __builtin_clz(size - 1u) : 0; }\n";
+    o << "template <int B>\n__device__ __forceinline__ void bm_search(const uint64_t* c, uint32_t (&lo)[B], uint32_t (&hi)[B], const uint64_t (&thr)[B], int steps) {\n";
+    o << "  for (int it = 0; it < steps; ++it) {\n    uint32_t mid[B];\n    uint64_t v[B];\n";
+    o << "#pragma unroll\n    for (int u = 0; u < B; ++u) { mid[u] = lo[u] + ((hi[u] - lo[u]) >> 1); v[u] = c[mid[u]]; }\n";
+    o << "#pragma unroll\n    for (int u = 0; u < B; ++u)\n      if (lo[u] < hi[u]) { if (v[u] > thr[u]) hi[u] = mid[u]; else lo[u] = mid[u] + 1u; }\n";
+    o << "  }\n}\n";
+    o << "__device__ __forceinline__ uint32_t bm_tile_end(uint32_t k, uint32_t n) { const uint32_t e = (k + 1u) * kBackmoveTile; return (e < n ? e : n) - 1u; }\n";
+    o << "__device__ __forceinline__ void bm_stage(const BackmoveArgs& a, uint64_t* ends) {\n";
+    o << "  const uint32_t nt = (a.n + kBackmoveTile - 1u) / kBackmoveTile;\n";
+    o << "  for (uint32_t k = threadIdx.x; k < nt; k += blockDim.x) ends[k] = a.cdf[bm_tile_end(k, a.n)];\n  __syncthreads();\n}\n";
+    // elements e[u] of the multinomial draw under a.pk: out[u] = the first i with cdf[i] > mulhi64(bits64(e[u]), Q)
+    o << "template <int B>\n__device__ __forceinline__ void bm_draw(const BackmoveArgs& a, const uint64_t* ends, uint64_t Q, const uint32_t (&e)[B], uint32_t (&out)[B]) {\n";
+    o << "  const Stream<" << I << "> ps(a.pk, false, 0u);\n  const uint32_t n = a.n;\n  uint64_t thr[B];\n  uint32_t hi[B];\n";
+    o << "#pragma unroll\n  for (int u = 0; u < B; ++u) { thr[u] = __umul64hi(ps.bits64(e[u]), Q); out[u] = 0u; }\n";
+    o << "  if (a.coarse) {\n    const uint32_t nt = (n + kBackmoveTile - 1u) / kBackmoveTile;\n";
+    o << "#pragma unroll\n    for (int u = 0; u < B; ++u) hi[u] = nt - 1u;\n";
+    o << "    bm_search<B>(ends, out, hi, thr, bm_steps(nt));\n";
+    o << "#pragma unroll\n    for (int u = 0; u < B; ++u) { hi[u] = bm_tile_end(out[u], n); out[u] *= kBackmoveTile; }\n";
+    o << "    bm_search<B>(a.cdf, out, hi, thr, bm_steps(n < kBackmoveTile ? n : kBackmoveTile));\n";
+    o << "  } else {\n";
+    o << "#pragma unroll\n    for (int u = 0; u < B; ++u) hi[u] = n - 1u;\n";
+    o << "    bm_search<B>(a.cdf, out, hi, thr, bm_steps(n));\n  }\n}\n";
+    // moves r0 .. r0 + B - 1 of path j
+    o << "template <int B>\n__device__ __forceinline__ void bm_moves(const BackmoveArgs& a, const PlanTables& tabs, const uint64_t* ends, uint64_t Q, uint32_t j, uint32_t r0,\n";
+    o << "                                         const float (&nx)[D], uint32_t& cur, float& s_cur) {\n";
+    o << "  uint32_t e[B], pr[B];\n  float sp[B], lg[B];\n";
+    o << "#pragma unroll\n  for (int u = 0; u < B; ++u) e[u] = (r0 + (uint32_t)u) * a.m + j;\n";
+    o << "  bm_draw<B>(a, ends, Q, e, pr);\n";
+    o << "#pragma unroll\n  for (int u = 0; u < B; ++u) {\n    sp[u] = bm_score(a, tabs, pr[u], nx);\n";
+    o << "    const Stream<" << I << "> as(split_at<" << I << ">(a.ak, (uint64_t)e[u]), false, 0u);\n";
+    o << "    lg[u] = m_log(uniform01(as.bits32(0u)));\n  }\n";
+    o << "#pragma unroll\n  for (int u = 0; u < B; ++u) {\n    const float d = sp[u] - s_cur;\n";
+    o << "    if (d >= 0.0f || lg[u] < d) { cur = pr[u]; s_cur = sp[u]; }\n  }\n}\n";
+    o << "__device__ __forceinline__ void bm_store(const BackmoveArgs& a, uint32_t j, uint32_t i) {\n  a.lin[j] = (int32_t)i;\n";
+    o << "  for (int c = 0; c < D; ++c)\n    if (a.path[c]) a.path[c][j] = a.col[c][i];\n}\n";
+    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_backmove_step_kernel(BackmoveArgs a, PlanTables tabs) {\n";
+    o << "  __shared__ uint64_t sh_ends[kBackmoveLdsTiles];\n";
+    o << "  const uint32_t n = a.n, m = a.m, K = a.n_moves;\n  uint64_t Q = 0;\n";
+    o << "  if (K) {\n    Q = a.cdf[n - 1u];\n    if (a.coarse) bm_stage(a, sh_ends);\n  }\n";
+    o << "  for (uint64_t j64 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j64 < m; j64 += (uint64_t)gridDim.x * blockDim.x) {\n";
+    o << "    const uint32_t j = (uint32_t)j64;\n";
+    o << "    uint32_t nxt = (uint32_t)a.lin_next[j];\n    nxt = nxt < n ? nxt : n - 1u;\n";
+    o << "    float nx[D];\n    for (int c = 0; c < D; ++c) nx[c] = bm_col(a.col_next[c][nxt], (a.i32_mask >> c) & 1u);\n";
+    o << "    uint32_t cur = (uint32_t)a.anc_next[nxt];\n    cur = cur < n ? cur : n - 1u;\n";
+    o << "    if (K) {\n      float s_cur = bm_score(a, tabs, cur, nx);\n      uint32_t r = 0;\n";
+    o << "      for (; r + 4u <= K; r += 4u) bm_moves<4>(a, tabs, sh_ends, Q, j, r, nx, cur, s_cur);\n";
+    o << "      if (K - r >= 2u) { bm_moves<2>(a, tabs, sh_ends, Q, j, r, nx, cur, s_cur); r += 2u; }\n";
+    o << "      if (K - r >= 1u) bm_moves<1>(a, tabs, sh_ends, Q, j, r, nx, cur, s_cur);\n    }\n";
+    o << "    bm_store(a, j, cur);\n  }\n}\n";
+    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_backmove_last_kernel(BackmoveArgs a, PlanTables tabs) {\n";
+    o << "  __shared__ uint64_t sh_ends[kBackmoveLdsTiles];\n  (void)tabs;\n";
+    o << "  const uint64_t Q = a.cdf[a.n - 1u];\n  if (a.coarse) bm_stage(a, sh_ends);\n";
+    o << "  for (uint64_t j64 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j64 < a.m; j64 += (uint64_t)gridDim.x * blockDim.x) {\n";
+    o << "    const uint32_t e[1] = {(uint32_t)j64};\n    uint32_t i[1];\n    bm_draw<1>(a, sh_ends, Q, e, i);\n";
+    o << "    bm_store(a, e[0], i[0]);\n  }\n}\n";
+    return o.str();
+  }
+};
+
 inline bool enabled() {
   const char* e = std::getenv("GJX_PLAN_JIT");
   return !(e && e[0] == '0');

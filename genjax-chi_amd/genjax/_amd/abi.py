@@ -80,6 +80,10 @@ class BacksimUnavailable(HeaderUnavailable):
     header, why = "gjx_backsim.h", "backward simulation runs as generated HIP kernels only"
 
 
+class BackmoveUnavailable(HeaderUnavailable):
+    header, why = "gjx_backmove.h", "the MCMC backward moves run as generated HIP kernels only"
+
+
 class Keys(C.Structure):
     _fields_ = [
         ("impl", C.c_int32),
@@ -529,6 +533,28 @@ BACKSIM_PROTOTYPES = {
 }
 BACKSIM_ABI_VERSION = (0, 1)
 
+
+# include/gjx_backmove.h: a FIFTH header, same arrangement — MCMC backward simulation (K Metropolis-Hastings moves per path
+# and step, cost independent of n) on an existing gjx_backsim_plan
+class BackmoveIO(C.Structure):
+    """gjx_backmove_io (include/gjx_backmove.h): the fields of gjx_backsim_io, then ancestors / anc_stride / n_moves."""
+    _fields_ = BacksimIO._fields_ + [
+        ("ancestors", C.c_void_p),
+        ("anc_stride", C.c_uint64),
+        ("n_moves", C.c_int32),
+    ]
+
+
+BACKMOVE_PROTOTYPES = {
+    "gjx_backmove_version": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gjx_backmove_plan_source": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gjx_backmove_plan_compile_check": (C.c_int, [_P, C.c_int]),
+    "gjx_backmove_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_uint64, C.c_uint64]),
+    "gjx_backmove_run": (C.c_int, [_P, C.POINTER(BackmoveIO), _P, C.c_size_t, _P]),
+}
+BACKMOVE_ABI_VERSION = (0, 1)
+BACKMOVE_MAX_MOVES = 256  # gjx_backmove.h: GJX_BACKMOVE_MAX_MOVES
+
 # The optional headers, in the order they are bound: every one is exported by libgjx_hip.so only and bound if present.
 class Header(collections.namedtuple("Header", "key header version_fn prototypes version_name unavailable")):
     @property
@@ -541,9 +567,22 @@ OPTIONAL_HEADERS = {h.key: h for h in (
     Header("guided", "gjx_guided.h", "gjx_guided_version", GUIDED_PROTOTYPES, "GUIDED_ABI_VERSION", GuidedUnavailable),
     Header("backsim", "gjx_backsim.h", "gjx_backsim_version", BACKSIM_PROTOTYPES, "BACKSIM_ABI_VERSION", BacksimUnavailable),
 )}
-_HEADER_OF = {name: h for h in OPTIONAL_HEADERS.values() for name in h.prototypes}  # entry point -> its optional header
+# Headers that build on an optional header's objects (gjx_backmove.h works on a gjx_backsim_plan): the same tuples, bound
+# after OPTIONAL_HEADERS and looked up with them everywhere.
+EXTENSION_HEADERS = {h.key: h for h in (
+    Header("backmove", "gjx_backmove.h", "gjx_backmove_version", BACKMOVE_PROTOTYPES, "BACKMOVE_ABI_VERSION", BackmoveUnavailable),
+)}
+
+
+def all_optional_headers():
+    """Every header next to gjx.h, in binding order: OPTIONAL_HEADERS, then EXTENSION_HEADERS."""
+    return (*OPTIONAL_HEADERS.values(), *EXTENSION_HEADERS.values())
+
+
+_HEADER_OF = {name: h for h in all_optional_headers() for name in h.prototypes}  # entry point -> its optional header
 
 _NO_STATUS = {
+    "gjx_backmove_workspace_bytes",
     "gjx_backsim_workspace_bytes",
     "gjx_paths_workspace_bytes",
     "gjx_backend_name",
@@ -588,7 +627,7 @@ class GjxLib:
         # is "wrong version", not "missing symbol"
         self.has = {}
         major, minor = C.c_int(-1), C.c_int(-1)
-        for h in (_CORE_HEADER, *OPTIONAL_HEADERS.values()):
+        for h in (_CORE_HEADER, *all_optional_headers()):
             if h is not _CORE_HEADER:
                 self.has[h.key] = hasattr(self._dll, h.version_fn)
                 setattr(self, "has_" + h.key, self.has[h.key])
@@ -615,7 +654,7 @@ class GjxLib:
     def require(self, key: str, fn_name: str):
         """Raise the header's *Unavailable, naming `fn_name`, on a library without the optional header `key`."""
         if not self.has[key]:
-            raise OPTIONAL_HEADERS[key].unavailable(fn_name, self.name)
+            raise (OPTIONAL_HEADERS.get(key) or EXTENSION_HEADERS[key]).unavailable(fn_name, self.name)
 
     def call(self, name: str, *args):
         h = _HEADER_OF.get(name)

@@ -522,29 +522,58 @@ class Ops:
         int32) / `logw` f32[T, n] — row-strided views (`[:, :n]` of a padded buffer) are taken as they are — for `m`
         trajectories under the scalar `key` (a prng.PRNGKey).  `obs`: host [T, n_obs] observation rows (None for a plan
         without).  -> dict(lineage int32[T, m], paths [col dtype [T, m]]), each None unless asked for."""
+        self.lib.require("backsim", "gjx_backsim_run")
+        io = abi.BacksimIO()
+        out, T, keep = self._backsim_io(io, "backsim_run", plan, key, cols, logw, obs, m, lineage, paths, max_workgroups)
+        nb = int(self.lib.call("gjx_backsim_workspace_bytes", T, int(m)))
+        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=self._alloc_device)  # (per call: see workspace())
+        self.lib.call("gjx_backsim_run", plan.handle, C.byref(io), self._p(ws), nb, self.stream())
+        return out
+
+    def _backsim_io(self, io, name, plan, key, cols, logw, obs, m, lineage, paths, max_workgroups):
+        """The fields gjx_backsim_io and gjx_backmove_io share -> (the output dict, T, the host observation rows `io` points
+        into: keep them alive over the call)."""
         import numpy as np
 
-        self.lib.require("backsim", "gjx_backsim_run")
         if len(cols) != plan.n_state:
-            raise ValueError(f"backsim_run: the plan has {plan.n_state} state columns, got {len(cols)}")
+            raise ValueError(f"{name}: the plan has {plan.n_state} state columns, got {len(cols)}")
         if logw.dim() != 2 or logw.dtype != torch.float32 or logw.stride(1) != 1 or logw.device.type != self.device_type:
-            raise ValueError("backsim_run: logw must be a float32 [T, n] device tensor with contiguous rows")
+            raise ValueError(f"{name}: logw must be a float32 [T, n] device tensor with contiguous rows")
         T, n = logw.shape
-        io = abi.BacksimIO()
         io.n_steps, io.impl, io.n, io.m = T, key.impl, n, int(m)
         io.key[0], io.key[1], io.key_lane = key.k0, key.k1, key.lane
         io.logw, io.logw_stride = logw.data_ptr(), logw.stride(0) if T > 1 else n
         out = dict(zip(("lineage", "paths"), self._history_io(
             io, cols, T, n, m, lineage, paths, lambda col: col.dtype in (torch.float32, torch.int32), io.col_is_i32, torch.int32,
-            "backsim_run: columns must be float32 / int32 [T, n] device tensors with contiguous rows")))
+            f"{name}: columns must be float32 / int32 [T, n] device tensors with contiguous rows")))
         y = None
         if plan.n_obs:
             y = np.ascontiguousarray(np.asarray(obs, dtype=np.float32).reshape(T, -1)[:, :plan.n_obs])
             io.obs = y.ctypes.data
-        nb = int(self.lib.call("gjx_backsim_workspace_bytes", T, int(m)))
-        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=self._alloc_device)  # (per call: see workspace())
         io.max_workgroups = int(max_workgroups)
-        self.lib.call("gjx_backsim_run", plan.handle, C.byref(io), self._p(ws), nb, self.stream())
+        return out, T, y
+
+    # ---- MCMC backward simulation: K Metropolis-Hastings moves per path and step (include/gjx_backmove.h) ----------
+    def backmove_run(self, plan: "BacksimPlan", key, cols: list, logw: torch.Tensor, ancestors: torch.Tensor, obs, m: int,
+                     n_moves: int, *, lineage: bool = True, paths: bool = True, max_workgroups: int = 0) -> dict:
+        """gjx_backmove_run: ONE call enqueues the backward pass of `m` paths over the history `cols` / `logw` (as backsim_run
+        takes them) and the filter's `ancestors` int32 [T, n]: every path starts a step at its genealogical ancestor and makes
+        `n_moves` (0 .. 256) Metropolis-Hastings moves proposed from that step's filter weights — m n_moves (T - 1)
+        transition densities whatever n is; 0 moves is trace-back from multinomial leaves.
+        -> dict(lineage int32[T, m], paths [col dtype [T, m]]), each None unless asked for.  Raises abi.BackmoveUnavailable
+        on a library without include/gjx_backmove.h (the CPU oracle)."""
+        self.lib.require("backmove", "gjx_backmove_run")
+        if ancestors.dim() != 2 or ancestors.dtype != torch.int32 or ancestors.stride(1) != 1 or ancestors.device.type != self.device_type:
+            raise ValueError("backmove_run: ancestors must be an int32 [T, n] device tensor with contiguous rows")
+        io = abi.BackmoveIO()
+        out, T, keep = self._backsim_io(io, "backmove_run", plan, key, cols, logw, obs, m, lineage, paths, max_workgroups)
+        if tuple(ancestors.shape) != tuple(logw.shape):
+            raise ValueError("backmove_run: ancestors and logw must have the same [T, n] shape")
+        io.ancestors, io.anc_stride = ancestors.data_ptr(), ancestors.stride(0) if T > 1 else ancestors.shape[1]
+        io.n_moves = int(n_moves)
+        nb = int(self.lib.call("gjx_backmove_workspace_bytes", T, logw.shape[1], int(m)))
+        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=self._alloc_device)  # (per call: see workspace())
+        self.lib.call("gjx_backmove_run", plan.handle, C.byref(io), self._p(ws), nb, self.stream())
         return out
 
     # ---- fused SMC --------------------------------------------------------------------------------
@@ -909,6 +938,18 @@ class BacksimPlan:
         self.ops.lib.call("gjx_backsim_plan_source", self.handle, impl, None, 0, C.byref(need))
         buf = C.create_string_buffer(need.value)
         self.ops.lib.call("gjx_backsim_plan_source", self.handle, impl, buf, need.value, None)
+        return buf.value.decode()
+
+    def move_compile_check(self, impl: int) -> int:
+        """gjx_backmove_plan_compile_check: the MCMC move kernels of the same table (include/gjx_backmove.h)."""
+        self.ops.lib.require("backmove", "gjx_backmove_plan_compile_check")
+        return self.ops.lib._gjx_backmove_plan_compile_check(self.handle, impl)
+
+    def move_source(self, impl: int) -> str:
+        need = C.c_size_t()
+        self.ops.lib.call("gjx_backmove_plan_source", self.handle, impl, None, 0, C.byref(need))
+        buf = C.create_string_buffer(need.value)
+        self.ops.lib.call("gjx_backmove_plan_source", self.handle, impl, buf, need.value, None)
         return buf.value.decode()
 
     def __del__(self):

@@ -247,7 +247,8 @@ class BootstrapSMC:
         sk, rk = smc_key_schedule(key, model.T)
         return _result(ops, self.n, ops._smc_run(model, key.impl, self.n, sk, rk, self.record_ancestors, self.ess_threshold))
 
-    def backward_simulate(self, result: SMCResult, key: prng.PRNGKey, n_paths: int, max_workgroups: int = 0) -> "Trajectories":
+    def backward_simulate(self, result: SMCResult, key: prng.PRNGKey, n_paths: int, max_workgroups: int = 0,
+                          n_moves: int | None = None) -> "Trajectories":
         """Backward-simulation smoothing: `n_paths` trajectories x_0:T-1, each drawn afresh from the recorded
         populations of `result` (a `record_history=True` run of THIS filter) — x_T-1 from the final weights, then x_t from
         all n particles of step t with weights w_t^i f(x_t+1 | x_t^i) — in one library call of T + 1 stream-ordered launches
@@ -257,10 +258,24 @@ class BootstrapSMC:
 
         The transition density is the model's own (`GuidedSMC`: the underlying StateSpaceModel's; proposals play no part).
         `PlanUnsupported` when the carry is not exactly the step's latent draws (a degenerate transition);
-        `abi.BacksimUnavailable` on a library without include/gjx_backsim.h; `ValueError` without recorded history."""
+        `abi.BacksimUnavailable` on a library without include/gjx_backsim.h; `ValueError` without recorded history.
+
+        `n_moves=K` (an int, 0 .. 256) selects the MCMC backward sampler instead (Bunch & Godsill 2013): every
+        path starts a step at its genealogical ancestor and makes K Metropolis-Hastings moves proposed from that step's
+        filter weights (gjx_backmove_run) — n_paths K (T - 1) transition densities whatever n is, so it runs at the filter's
+        own size; K = 0 is trace-back from multinomial leaves, and a few moves already undo the genealogy's collapse.  It
+        reads `result.ancestors` (`ValueError` without); `abi.BackmoveUnavailable` on a library without
+        include/gjx_backmove.h.  `n_moves=None`: the exact method above."""
         if result.history is None or result.log_weight_history is None:
             raise ValueError("backward_simulate() needs the per-step states: run the filter with BootstrapSMC(..., record_history=True)")
+        if n_moves is not None:
+            if isinstance(n_moves, bool) or not isinstance(n_moves, (int, np.integer)) or not 0 <= int(n_moves) <= abi.BACKMOVE_MAX_MOVES:
+                raise ValueError(f"backward_simulate(): n_moves must be None or an int in 0 .. {abi.BACKMOVE_MAX_MOVES}, got {n_moves!r}")
+            if result.ancestors is None:
+                raise ValueError("backward_simulate(n_moves=...) starts every path at its genealogical ancestor: the result has no ancestor table")
         ops = get_ops()
+        if n_moves is not None:
+            ops.lib.require("backmove", "gjx_backmove_run")
         ops.lib.require("backsim", "gjx_backsim_run")
         if self._transition is None:
             table, obs = self._bind(ops).transition_table()
@@ -268,7 +283,11 @@ class BootstrapSMC:
         plan, obs = self._transition
         cols = list(result.history) if isinstance(result.history, tuple) else [result.history]
         m = int(n_paths)
-        out = ops.backsim_run(plan, key, cols, result.log_weight_history, obs, m, max_workgroups=max_workgroups)
+        if n_moves is None:
+            out = ops.backsim_run(plan, key, cols, result.log_weight_history, obs, m, max_workgroups=max_workgroups)
+        else:
+            out = ops.backmove_run(plan, key, cols, result.log_weight_history, result.ancestors, obs, m, int(n_moves),
+                                   max_workgroups=max_workgroups)
         paths, lin = out["paths"], out["lineage"]
         # float64 moments and distinct counts from the returned columns (T m elements: small against the n m T pass)
         is_f32 = [c.dtype == torch.float32 for c in paths]
