@@ -2082,6 +2082,8 @@ struct gjx_plan {
   gjx_jit::Compiled jit[4];
   gjx_jit::Compiled jit_tail[4];  // the same forms WITH the fused fold (gjx_jit::Gen::fused_tail): built on the first launch
                                   // that passes a gjx_lse_out, so the default launches do not carry the fold's registers
+  gjx_jit::Compiled jit_wt[2];  // the quad form with WRITE-THROUGH stores (gjx_jit::Gen::wt_stores), [1] with the fused fold:
+                                // built on the first launch of a single pass (the other forms have one kind of store)
   std::vector<void*> dev_owned;  // per-row tables of categorical sites (specialised kernels)
   std::mutex jit_mu;
   ExprStore expr;      // GJX_ARG_EXPR programs (host; read by the code generator)
@@ -2341,44 +2343,44 @@ static int jit_form_pref() {  // GJX_JIT_FORM = one | pair | quad (test / tuning
   if (e && !strcmp(e, "pair")) return 2;
   return 4;  // quad; measured (tools/ab_importance.py, 1e6 particles): quad 13.1 / pair 13.6 / one 28.3 us per pass at 8 passes per launch
 }
-// The waves-per-SIMD hint of a form (P particles per lane).  The kernels are bound by dependency latency, not by issue
-// slots (a wave64 VALU instruction issues in ~2.4 cycles, tools/microbench/valu_rate.hip), so resident waves are what
-// pays, and a SIMD's 512 VGPRs are shared in granules of 8: <= 128 registers is 4 waves, <= 96 5, <= 80 6, <= 72 7, <= 64 8
-// (allocated registers: the code object's .vgpr_count; a rocprofv3 trace's VGPR column is half of it).
+// The waves-per-SIMD hint of a form (P particles per lane).  A SIMD's 512 VGPRs are shared in granules of 8: <= 128
+// registers is 4 waves, <= 96 5, <= 80 6, <= 72 7, <= 64 8 (allocated registers: the code object's .vgpr_count; a rocprofv3
+// trace's VGPR column is half of it).
 //  * pairs: hint 6 (<= 80 VGPRs); the 10-latent kernel takes 49 under it.
-//  * quads: none.  The 10-latent kernel allocates 68 VGPRs unhinted, no scratch: 7 waves.  Hint 7 gives 70 registers and
-//    28 more instructions, hint 8 64 registers, 8 B of scratch and 105 more instructions (profiles/occupancy_summary.md;
-//    tools/ab_waves_hint.py measures them against each other through GJX_JIT_DEFINE=GJX_WAVES_HINT=<k>).
+//  * quads: none.  Built without SLP vectorisation (gjx_plan_jit.hpp compile_options) the 10-latent kernel allocates 62
+//    VGPRs unhinted, no scratch: 8 waves (with SLP: 67 / 68, 7 waves; profiles/issue_cost_summary.md has both measured;
+//    tools/ab_waves_hint.py measures hints against each other through GJX_JIT_DEFINE=GJX_WAVES_HINT=<k>).
 // A hinted build that spills more than 32 B is replaced by the unhinted one (plan_compiled).
 static int jit_waves_hint(int P) { return P == 2 ? 6 : 0; }
 // The importance generator of a plan.  `form`: particles per lane, 1, 2 (pairs) or 4 (quads); above 1 is PHILOX only.
-static void plan_gen_setup(gjx_jit::Gen<CSite, CArg>& g, const gjx_plan* p, int impl, int form, bool fused_tail, int min_waves) {
+static void plan_gen_setup(gjx_jit::Gen<CSite, CArg>& g, const gjx_plan* p, int impl, int form, bool fused_tail, bool wt_stores, int min_waves) {
   g.impl = impl; g.sites = p->host; g.n_sites = p->n_sites; g.laned = form >= 2; g.pairs_per_lane = form == 4 ? 2 : 1;
   g.sc = p->scopes.n_scopes > 0 ? &p->scopes : nullptr;
   g.fast_math = (p->flags & GJX_PLAN_FAST_MATH) != 0;
   g.fused_tail = fused_tail;
+  g.wt_stores = wt_stores;
   g.min_waves = min_waves;
 }
 int gjx_plan_specialized_source(const gjx_plan* p, int impl, char* buf, size_t buf_len, size_t* needed) {
-  const bool fused_tail = (impl & GJX_SOURCE_FUSED_TAIL) != 0;
-  impl &= ~GJX_SOURCE_FUSED_TAIL;
+  const bool fused_tail = (impl & GJX_SOURCE_FUSED_TAIL) != 0, wt_stores = (impl & GJX_SOURCE_WT_STORES) != 0;
+  impl &= ~(GJX_SOURCE_FUSED_TAIL | GJX_SOURCE_WT_STORES);
   if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
   const int form = impl == 1 ? jit_form_pref() : 1;  // (GJX_JIT_FORM picks the PHILOX form shown)
   gjx_jit::Gen<CSite, CArg> g;
-  plan_gen_setup(g, p, impl, form, fused_tail, jit_waves_hint(form));  // the kernel that ships
+  plan_gen_setup(g, p, impl, form, fused_tail, wt_stores, jit_waves_hint(form));  // the kernel that ships
   gjx_jit::TableScope ts;
   return copy_source_out(g.run(), buf, buf_len, needed);
 }
 
 int gjx_plan_compile_check(const gjx_plan* p, int impl) {
-  const bool fused_tail = (impl & GJX_SOURCE_FUSED_TAIL) != 0;
-  impl &= ~GJX_SOURCE_FUSED_TAIL;
+  const bool fused_tail = (impl & GJX_SOURCE_FUSED_TAIL) != 0, wt_stores = (impl & GJX_SOURCE_WT_STORES) != 0;
+  impl &= ~(GJX_SOURCE_FUSED_TAIL | GJX_SOURCE_WT_STORES);
   if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
   for (int form = 1; form <= (impl == 1 ? 4 : 1); form *= 2) {  // PHILOX: one particle per lane, pairs, quads
     gjx_jit::Gen<CSite, CArg> g;
-    plan_gen_setup(g, p, impl, form, fused_tail, jit_waves_hint(form));
+    plan_gen_setup(g, p, impl, form, fused_tail, wt_stores && form == 4, jit_waves_hint(form));
     gjx_jit::TableScope ts;
-    if (!gjx_jit::compile_only(g.run())) return GJX_ERR_UNSUPPORTED;
+    if (!gjx_jit::compile_only(g.run(), gjx_jit::PlanKind::importance)) return GJX_ERR_UNSUPPORTED;
   }
   return GJX_OK;
 }
@@ -2387,6 +2389,7 @@ int gjx_plan_destroy(gjx_plan* p) {
   if (p->dev) (void)hipFree(p->dev);
   for (auto& c : p->jit) c.release();  // the modules stay cached (bounded, LRU) for plans of the same structure
   for (auto& c : p->jit_tail) c.release();
+  for (auto& c : p->jit_wt) c.release();
   free_owned(p->dev_owned);
   delete p;
   return GJX_OK;
@@ -2395,24 +2398,26 @@ int gjx_plan_destroy(gjx_plan* p) {
 // The hiprtc-specialised kernel of a plan for this key form (compiled and loaded on first use).
 // `lane_particles`: how many adjacent particles a lane may own given n and the alignment of the output buffers (1, 2, 4).
 // `fused_tail`: the variant that folds the row sums inside the launch (launches that pass a gjx_lse_out).
-static gjx_jit::Compiled& plan_compiled(gjx_plan* mp, const gjx_keys* pk, int lane_particles, bool fused_tail = false) {
+// `one_pass`: a launch of a single pass; the quad form then stores write-through (gjx_jit::Gen::wt_stores).
+static gjx_jit::Compiled& plan_compiled(gjx_plan* mp, const gjx_keys* pk, int lane_particles, bool fused_tail = false, bool one_pass = false) {
   // PHILOX children of a lane-0 key share one cipher key, and an even first index keeps particle pairs
   // (2i, 2i+1) together: the paired / quad kernel forms (gjx_plan_jit.hpp)
   const bool pairable = pk->impl == 1 && pk->mode == 1 && pk->parent_lane == 0 && (pk->first & 1) == 0;
   int P = pairable ? (lane_particles < jit_form_pref() ? lane_particles : jit_form_pref()) : 1;
   if (P == 3) P = 2;
   const bool laned = P >= 2;
-  gjx_jit::Compiled& c = (fused_tail ? mp->jit_tail : mp->jit)[P == 4 ? 3 : (laned ? 2 : pk->impl)];
+  const bool wt_stores = one_pass && P == 4;
+  gjx_jit::Compiled& c = wt_stores ? mp->jit_wt[fused_tail ? 1 : 0] : (fused_tail ? mp->jit_tail : mp->jit)[P == 4 ? 3 : (laned ? 2 : pk->impl)];
   compiled_once(mp->jit_mu, c, {{mp->host, mp->n_sites}}, &mp->dev_owned, [&] {
     auto build = [&](int min_waves) {
       gjx_jit::Gen<CSite, CArg> g;
-      plan_gen_setup(g, mp, pk->impl, P, fused_tail, min_waves);
+      plan_gen_setup(g, mp, pk->impl, P, fused_tail, wt_stores, min_waves);
       gjx_jit::TableScope ts;  // the source numbers the plan's device tables; the addresses travel as a kernel argument
       const std::string src = g.run();
       c.block = g.block;
       c.rows_per_block = g.rows_per_block;
       c.tabs = ts.reg.tables();
-      return c.load(src, {g.kname()}, {&c.fn});
+      return c.load(src, gjx_jit::PlanKind::importance, {g.kname()}, {&c.fn});
     };
     // (jit_waves_hint has the register counts and the waves per SIMD that follow from them.)  The hint is kept as long
     // as the allocator gets there with (next to) no spilling; otherwise the unconstrained build is used.
@@ -2421,7 +2426,7 @@ static gjx_jit::Compiled& plan_compiled(gjx_plan* mp, const gjx_keys* pk, int la
     if (ok && std::getenv("GJX_PLAN_JIT_VERBOSE")) {  // what the loaded code object allocates (the VGPR column of a rocprofv3 kernel trace is HALF of this)
       int regs = 0;
       if (hipFuncGetAttribute(&regs, HIP_FUNC_ATTRIBUTE_NUM_REGS, c.fn) != hipSuccess) (void)hipGetLastError();
-      fprintf(stderr, "gjx jit: %d particle(s) per lane%s: %d registers per lane\n", P, fused_tail ? ", fused tail" : "", regs);
+      fprintf(stderr, "gjx jit: %d particle(s) per lane%s%s: %d registers per lane\n", P, fused_tail ? ", fused tail" : "", wt_stores ? ", write-through stores" : "", regs);
     }
     if (ok && hint > 0) {
       int scratch = 0;
@@ -2456,6 +2461,7 @@ int gjx_plan_prepare(gjx_plan* p, const gjx_keys* pk) {
   bool ok = plan_compiled(p, pk, 1).state == 1;
   ok = plan_compiled(p, pk, 2).state == 1 && ok;
   ok = plan_compiled(p, pk, 4).state == 1 && ok;
+  ok = plan_compiled(p, pk, 4, false, true).state == 1 && ok;  // (a single-pass launch: the quad form's other kind of store)
   if (ok) return GJX_OK;
   return jit_fallback_allowed() && !p->has_expr ? plan_device_table(p) : GJX_ERR_JIT;
 }
@@ -2510,7 +2516,7 @@ static int importance_launch(const gjx_plan* p, const gjx_keys* pk, int32_t n_pa
     uintptr_t al = (uintptr_t)logw | (uintptr_t)score | (uintptr_t)(4 * pass_stride) | (uintptr_t)(4 * n);
     for (int c = 0; c < n_value_cols; ++c) al |= (uintptr_t)value_cols[c];
     const int lane_particles = (al & 15) == 0 ? 4 : ((al & 7) == 0 ? 2 : 1);
-    gjx_jit::Compiled& c = plan_compiled(const_cast<gjx_plan*>(p), pk, lane_particles, lse != nullptr);
+    gjx_jit::Compiled& c = plan_compiled(const_cast<gjx_plan*>(p), pk, lane_particles, lse != nullptr, n_pass <= 1);
     if (c.state != 1 && (!jit_fallback_allowed() || p->has_expr || p->scopes.n_scopes > 0)) return GJX_ERR_JIT;  // loud: never a silent 7x slower route
     if (c.state == 1) {
       uint64_t nn = n;
@@ -3329,8 +3335,8 @@ int gjx_scan_plan_compile_check(const gjx_scan_plan* p, int impl) {
   impl &= ~GJX_SOURCE_FUSED_TAIL;
   if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
   if (std::getenv("GJX_PLAN_JIT_DUMP")) fprintf(stderr, "%s\n", scan_plan_source(p, impl, nullptr, nullptr, false, nullptr, ft).c_str());
-  if (impl == 1 && !gjx_jit::compile_only(scan_plan_source(p, impl, nullptr, nullptr, true, nullptr, ft))) return GJX_ERR_UNSUPPORTED;
-  return gjx_jit::compile_only(scan_plan_source(p, impl, nullptr, nullptr, false, nullptr, ft)) ? GJX_OK : GJX_ERR_UNSUPPORTED;
+  if (impl == 1 && !gjx_jit::compile_only(scan_plan_source(p, impl, nullptr, nullptr, true, nullptr, ft), gjx_jit::PlanKind::scan)) return GJX_ERR_UNSUPPORTED;
+  return gjx_jit::compile_only(scan_plan_source(p, impl, nullptr, nullptr, false, nullptr, ft), gjx_jit::PlanKind::scan) ? GJX_OK : GJX_ERR_UNSUPPORTED;
 }
 int gjx_scan_run(gjx_scan_plan* p, const gjx_scan_io* io, gjx_stream s) {
   if (!p || !io || !keys_ok(io->particle_keys) || io->particle_keys->has_fold || !io->logw || io->n_steps < 1 ||
@@ -3369,7 +3375,7 @@ int gjx_scan_run(gjx_scan_plan* p, const gjx_scan_io* io, gjx_stream s) {
     const char* kname = nullptr;
     const std::string src = scan_plan_source(p, impl, &kname, &c.tabs, quad, &c.block, fused_tail);
     if (std::getenv("GJX_PLAN_JIT_DUMP")) fprintf(stderr, "%s\n", src.c_str());
-    return c.load(src, {kname}, {&c.fn});
+    return c.load(src, gjx_jit::PlanKind::scan, {kname}, {&c.fn});
   });
   if (!ready) return GJX_ERR_JIT;
   KeySrc k = key_src(io->particle_keys);
@@ -3487,7 +3493,7 @@ int gjx_smc_plan_destroy(gjx_smc_plan* p) {
 }
 int gjx_jit_compile_source(const char* source) {
   if (!source) return GJX_ERR_INVALID;
-  return gjx_jit::compile_only(source) ? GJX_OK : GJX_ERR_JIT;
+  return gjx_jit::compile_only(source, gjx_jit::PlanKind::smc /* (no options of its own: the base list) */) ? GJX_OK : GJX_ERR_JIT;
 }
 int gjx_jit_stats(uint64_t* compiles, uint64_t* cached_modules, uint64_t* evictions) {
   gjx_jit::ModuleCache& mc = gjx_jit::ModuleCache::get();
@@ -3526,7 +3532,7 @@ int gjx_smc_plan_source(const gjx_smc_plan* p, int impl, char* buf, size_t buf_l
 int gjx_smc_plan_compile_check(const gjx_smc_plan* p, int impl) {
   if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
   if (std::getenv("GJX_PLAN_JIT_DUMP")) fprintf(stderr, "%s\n", smc_plan_source(p, impl).c_str());
-  return gjx_jit::compile_only(smc_plan_source(p, impl)) ? GJX_OK : GJX_ERR_UNSUPPORTED;
+  return gjx_jit::compile_only(smc_plan_source(p, impl), gjx_jit::PlanKind::smc) ? GJX_OK : GJX_ERR_UNSUPPORTED;
 }
 
 // The interpreter's device copies of the site tables (GJX_PLAN_JIT=0 / a failed compilation with the fallback allowed).
@@ -3548,7 +3554,7 @@ static gjx_jit::CompiledSmc* smc_plan_compiled(gjx_smc_plan* plan, int impl, boo
   if (!gjx_jit::enabled()) return nullptr;  // (GJX_PLAN_JIT=0: the table-walking policy, smc_plan_route)
   gjx_jit::CompiledSmc& c = peers ? plan->jit_peers[impl] : plan->jit[impl];
   const bool ready = compiled_once(plan->mu, c, {{plan->init, plan->n_init}, {plan->step, plan->n_step}}, &plan->dev_owned, [&] {
-    return c.load(smc_plan_source(plan, impl, &c.tabs, peers), {"gjx_smc_step_kernel", "gjx_smc_step_kernel_adaptive", "gjx_smc_init_kernel"},
+    return c.load(smc_plan_source(plan, impl, &c.tabs, peers), gjx_jit::PlanKind::smc, {"gjx_smc_step_kernel", "gjx_smc_step_kernel_adaptive", "gjx_smc_init_kernel"},
                   {&c.step, &c.step_adaptive, &c.init});
   });
   return ready ? &c : nullptr;
@@ -4230,7 +4236,7 @@ std::string backsim_source(const gjx_backsim_plan* p, int impl, PlanTables* tabs
 gjx_jit::CompiledBacksim* backsim_compiled(gjx_backsim_plan* p, int impl) {
   gjx_jit::CompiledBacksim& c = p->jit[impl];
   const bool ready = compiled_once(p->mu, c, {{p->sites, p->n_sites}}, &p->dev_owned, [&] {
-    return c.load(backsim_source(p, impl, &c.tabs), {"gjx_backsim_step_kernel", "gjx_backsim_last_kernel"}, {&c.step, &c.last});
+    return c.load(backsim_source(p, impl, &c.tabs), gjx_jit::PlanKind::backsim, {"gjx_backsim_step_kernel", "gjx_backsim_last_kernel"}, {&c.step, &c.last});
   });
   return ready ? &c : nullptr;
 }
@@ -4294,7 +4300,7 @@ int gjx_backsim_plan_source(const gjx_backsim_plan* p, int impl, char* buf, size
 }
 int gjx_backsim_plan_compile_check(const gjx_backsim_plan* p, int impl) {
   if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
-  return gjx_jit::compile_only(backsim_source(p, impl)) ? GJX_OK : GJX_ERR_UNSUPPORTED;
+  return gjx_jit::compile_only(backsim_source(p, impl), gjx_jit::PlanKind::backsim) ? GJX_OK : GJX_ERR_UNSUPPORTED;
 }
 size_t gjx_backsim_workspace_bytes(int32_t n_steps, uint64_t m) {
   if (n_steps < 1 || !backsim_size_ok(m)) return 0;
@@ -4394,7 +4400,7 @@ std::string backmove_source(const gjx_backsim_plan* p, int impl, PlanTables* tab
 gjx_jit::CompiledBacksim* backmove_compiled(gjx_backsim_plan* p, int impl) {
   gjx_jit::CompiledBacksim& c = p->move_jit[impl];
   const bool ready = compiled_once(p->mu, c, {{p->sites, p->n_sites}}, &p->dev_owned, [&] {
-    return c.load(backmove_source(p, impl, &c.tabs), {"gjx_backmove_step_kernel", "gjx_backmove_last_kernel"}, {&c.step, &c.last});
+    return c.load(backmove_source(p, impl, &c.tabs), gjx_jit::PlanKind::backsim, {"gjx_backmove_step_kernel", "gjx_backmove_last_kernel"}, {&c.step, &c.last});
   });
   return ready ? &c : nullptr;
 }
@@ -4436,7 +4442,7 @@ int gjx_backmove_plan_source(const gjx_backsim_plan* p, int impl, char* buf, siz
 }
 int gjx_backmove_plan_compile_check(const gjx_backsim_plan* p, int impl) {
   if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
-  return gjx_jit::compile_only(backmove_source(p, impl)) ? GJX_OK : GJX_ERR_UNSUPPORTED;
+  return gjx_jit::compile_only(backmove_source(p, impl), gjx_jit::PlanKind::backsim) ? GJX_OK : GJX_ERR_UNSUPPORTED;
 }
 size_t gjx_backmove_workspace_bytes(int32_t n_steps, uint64_t n, uint64_t m) {
   if (n_steps < 1 || !backsim_size_ok(n) || !backsim_size_ok(m)) return 0;

@@ -508,8 +508,8 @@ inline void emit_prelude(std::ostringstream& o, bool fast_math = false, bool bm_
 // caller), one Box-Muller transform per pair and Normal site, every stored column one vector store at `store_at`.
 // The quad kernels store write-through (sc1) when a launch holds ONE pass (store16_out, gjx_device.hpp): the kernel's end
 // no longer waits for the write-back of its 48 MB — 4.94e10 -> 5.47e10 particles/s at one pass per launch; with many
-// passes per launch the write-back overlaps the following passes and plain stores are 1 % faster, hence the run-time flag
-// `wt_one_pass`.
+// passes per launch the write-back overlaps the following passes and plain stores are 1 % faster, hence the two source
+// variants (Gen::wt_stores: `wt_one_pass` is a constant of the generated source).
 template <class CSiteT, class CArgT>
 inline void emit_pair_lane_sites(std::ostringstream& o, std::vector<SiteEmitter<CSiteT, CArgT>>& em, const CSiteT* sites, int n_sites,
                                  int NP, const std::string& ind, const std::string& store_at, const std::string& sc_guard = "",
@@ -645,6 +645,9 @@ struct Gen {
   bool fused_tail = false;  // the kernel folds the row sums itself (gjx_device.hpp lse_tail; launches that pass a gjx_lse_out).
                             // A variant of its own: inlined into every kernel, the fold cost 22 VGPRs — one wave per SIMD —
                             // on launches that never enter it (132 -> 110 in the 10-latent quad kernel)
+  bool wt_stores = false;  // the quad form's 16-byte stores are write-through (launches of ONE pass) instead of plain.  A variant
+                           // of its own: as a run-time flag every store was a uniform branch pair (88 scalar instructions per
+                           // row of the 10-latent kernel) and a basic block of its own
   int block = 256;    // threads per workgroup of the generated kernel
   int rows_per_block = 1;
   bool laned = false; // the paired form (see above)
@@ -714,7 +717,7 @@ struct Gen {
     }
     if (bm_lds()) o << "  bm_stage();\n";
     o << "  const uint64_t rows_all = (uint64_t)bt.n_pass * bt.rows_per_pass;\n";
-    o << "  const bool wt_one_pass = bt.n_pass <= 1u; (void)wt_one_pass;\n";
+    o << "  const bool wt_one_pass = " << (wt_stores ? "true" : "false") << "; (void)wt_one_pass;  // (Gen::wt_stores)\n";
     o << "  for (uint64_t g0 = (uint64_t)blockIdx.x * " << R << "; g0 < rows_all; g0 += (uint64_t)gridDim.x * " << R << ") {\n";
     o << "    const uint64_t gr = g0 + pr;\n";
     o << "    const uint32_t pass = (uint32_t)(gr / bt.rows_per_pass);\n";
@@ -1401,11 +1404,24 @@ inline bool read_file(const std::string& path, std::string* out) {
   std::fclose(f);
   return true;
 }
-inline std::vector<std::string> compile_options() {
+// The plan kinds that generate kernels.  Each has its own compiler option list (compile_options).
+enum class PlanKind { importance, scan, smc, backsim };
+// The options of one plan kind: four fixed ones, then the kind's own, then the A/B knobs (a later option wins).
+//  * importance: -fno-slp-vectorize.  The SLP vectoriser turns pairs of f32 operations into v_pk_* forms, which issue no
+//    faster per flop than two scalar ones (tools/README.md) but cost v_mov shuffles to build register pairs and hazard wait
+//    states between dependent packed instructions.  Without it the 10-latent quad kernel has 303 more vector instructions,
+//    1.5 % fewer priced issue cycles (tools/price_kernel.py), a third of the wait states and 62 instead of 67 VGPRs: 8 waves
+//    per SIMD; measured 11.9 -> 10.9 us per pass (profiles/issue_cost_summary.md).
+//  * scan: nothing of its own.  The scan kernels share emit_pair_lane_sites, but the LGSSM quad kernel prices at 1337.0
+//    cycles per row and step with SLP and 1345.6 without (56 / 50 VGPRs: eight waves per SIMD either way).
+//  * smc, backsim: nothing of their own (not priced).
+inline std::vector<std::string> compile_options(PlanKind kind) {
   std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"};
+  if (kind == PlanKind::importance) opts.push_back("-fno-slp-vectorize");
   // GJX_JIT_DEFINE=NAME[=VALUE]: one extra -D for the generated kernel (A/B knob for device-header variants)
   if (const char* d = std::getenv("GJX_JIT_DEFINE")) opts.push_back(std::string("-D") + d);
-  // GJX_JIT_OPTS="opt opt ...": extra compiler options for the generated kernel (scheduling experiments)
+  // GJX_JIT_OPTS="opt opt ...": extra compiler options for the generated kernel (scheduling experiments; -fslp-vectorize
+  // gives an importance kernel its former option list back)
   if (const char* e = std::getenv("GJX_JIT_OPTS")) {
     std::istringstream is(e);
     for (std::string t; is >> t;) opts.push_back(t);
@@ -1469,7 +1485,7 @@ inline std::vector<char*> child_environ() {
   return env;
 }
 // -> 1 compiled, 0 compilation failed or the child died (logged), -1 the child could not be started
-inline int compile_in_child(const std::string& src, std::string* code) {
+inline int compile_in_child(const std::string& src, std::string* code, PlanKind kind) {
   const std::string helper = jitc_path();
   if (helper.empty()) return -1;
   static std::mutex mu;  // compilations are serialised by the module cache's lock anyway
@@ -1481,7 +1497,7 @@ inline int compile_in_child(const std::string& src, std::string* code) {
   const std::string stem = dir + "/k" + std::to_string(++serial);
   const std::string fsrc = stem + ".hip", fhdr = dir + "/gjx_device.hpp", fout = stem + ".co", flog = stem + ".log";
   if (!write_file(fsrc, src.data(), src.size())) return -1;
-  const std::vector<std::string> opts = compile_options();
+  const std::vector<std::string> opts = compile_options(kind);
   std::vector<char*> argv = {const_cast<char*>(helper.c_str()), const_cast<char*>(fsrc.c_str()), const_cast<char*>(fhdr.c_str()),
                              const_cast<char*>(fout.c_str()), const_cast<char*>(flog.c_str())};
   for (const std::string& o : opts) argv.push_back(const_cast<char*>(o.c_str()));
@@ -1523,7 +1539,7 @@ inline int compile_in_child(const std::string& src, std::string* code) {
 }
 
 // Compile `src` for gfx950; on success `code` holds the code object.
-inline bool compile_to_code(const std::string& src, std::string* code) {
+inline bool compile_to_code(const std::string& src, std::string* code, PlanKind kind) {
   // GJX_PLAN_JIT_DUMP_FILE=path: the source about to be compiled (overwritten per compilation: after a compiler crash the
   // file holds the offending kernel)
   if (const char* f = std::getenv("GJX_PLAN_JIT_DUMP_FILE")) {
@@ -1534,7 +1550,7 @@ inline bool compile_to_code(const std::string& src, std::string* code) {
   }
   const char* inproc = std::getenv("GJX_JIT_INPROC");
   if (!(inproc && inproc[0] == '1')) {
-    const int r = compile_in_child(src, code);
+    const int r = compile_in_child(src, code, kind);
     if (r >= 0) return r == 1;
     routes().spawn_failures++;
     // no silent change of route: a caller that accepts the compiler inside its own address space says so
@@ -1555,7 +1571,7 @@ inline bool compile_to_code(const std::string& src, std::string* code) {
   const char* hn[] = {"gjx_device.hpp"};
   const char* hs[] = {kDeviceHeader};
   if (hiprtcCreateProgram(&prog, src.c_str(), "gjx_plan.hip", 1, hs, hn) != HIPRTC_SUCCESS) return false;
-  const std::vector<std::string> extra = compile_options();
+  const std::vector<std::string> extra = compile_options(kind);
   std::vector<const char*> opts;
   for (const std::string& t : extra) opts.push_back(t.c_str());
   const hiprtcResult r = hiprtcCompileProgram(prog, (int)opts.size(), opts.data());
@@ -1579,9 +1595,9 @@ inline bool compile_to_code(const std::string& src, std::string* code) {
   routes().inproc++;
   return true;
 }
-inline bool compile_only(const std::string& src) {
+inline bool compile_only(const std::string& src, PlanKind kind) {
   std::string code;
-  return compile_to_code(src, &code) && !code.empty();
+  return compile_to_code(src, &code, kind) && !code.empty();
 }
 
 // The module cache.  Identical sources (same model structure) share one loaded module process-wide, so re-creating a
@@ -1607,24 +1623,24 @@ struct ModuleCache {
     static ModuleCache c;
     return c;
   }
-  // The key of a source: the source itself and, where the A/B knobs add compiler options (GJX_JIT_DEFINE, GJX_JIT_OPTS),
-  // those options — the same text compiled under another define is another module.
-  static std::string key_of(const std::string& src) {
-    const std::vector<std::string> opts = compile_options();
+  // The key of a source: the source itself and the compiler options beyond the four fixed ones (the plan kind's own and
+  // the A/B knobs GJX_JIT_DEFINE, GJX_JIT_OPTS) — the same text compiled under another option is another module.
+  static std::string key_of(const std::string& src, PlanKind kind) {
+    const std::vector<std::string> opts = compile_options(kind);
     std::string key = src;
     for (size_t k = 4; k < opts.size(); ++k) key += "\n// " + opts[k];  // (the four fixed options come first)
     return key;
   }
   // -> the loaded module of `src` with one more reference, or nullptr (compile / load failure, logged); `key_out`: what
   // release() takes
-  hipModule_t acquire(const std::string& src, std::string* key_out) {
-    const std::string key = key_of(src);
+  hipModule_t acquire(const std::string& src, PlanKind kind, std::string* key_out) {
+    const std::string key = key_of(src, kind);
     *key_out = key;
     std::lock_guard<std::mutex> lock(mu);
     auto it = map.find(key);
     if (it == map.end()) {
       std::string code;
-      if (!compile_to_code(src, &code)) return nullptr;
+      if (!compile_to_code(src, &code, kind)) return nullptr;
       hipModule_t mod = nullptr;
       const hipError_t le = hipModuleLoadData(&mod, code.data());
       if (le != hipSuccess) {
@@ -1677,10 +1693,10 @@ struct Module {
   }
   // The module of `src` (compiled, or shared with plans of the same structure) and its kernels `names` into `fns`.  A slot
   // that is being rebuilt (e.g. without the occupancy hint) lets go of its module first.
-  bool load(const std::string& src, std::initializer_list<const char*> names, std::initializer_list<hipFunction_t*> fns) {
+  bool load(const std::string& src, PlanKind kind, std::initializer_list<const char*> names, std::initializer_list<hipFunction_t*> fns) {
     release();
     std::string k;
-    hipModule_t mod = ModuleCache::get().acquire(src, &k);
+    hipModule_t mod = ModuleCache::get().acquire(src, kind, &k);
     if (!mod) return false;
     key = k;
     auto fn = fns.begin();

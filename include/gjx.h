@@ -284,8 +284,12 @@ int gjx_plan_set_params(gjx_plan* p, const float* params /*host*/, int n_params)
  * (needs no GPU).  The oracle build returns GJX_ERR_UNSUPPORTED for both.
  * A plan's importance kernel exists in two variants: the default one, and one that also folds the row sums inside
  * the launch (built on the first launch that passes a gjx_lse_out).  Both diagnostics show / check the default
- * variant; `impl | GJX_SOURCE_FUSED_TAIL` asks for the other. */
+ * variant; `impl | GJX_SOURCE_FUSED_TAIL` asks for the other.
+ * The kind of store is a variant too, of the four-particles-per-lane form: plain stores by default (launches of
+ * several passes: the write-back overlaps the following passes), write-through stores for a launch of ONE pass (built
+ * on the first such launch, or by gjx_plan_prepare).  `impl | GJX_SOURCE_WT_STORES` asks for the write-through variant; the flags combine. */
 #define GJX_SOURCE_FUSED_TAIL 0x100
+#define GJX_SOURCE_WT_STORES 0x200
 int gjx_plan_specialized_source(const gjx_plan* p, int impl, char* buf, size_t buf_len, size_t* needed);
 /* Build (hiprtc) and load now the kernel gjx_importance_run would build on its first launch with
  * this key form, so that no launch pays the ~0.2 s compilation.  Optional; the oracle build returns

@@ -9,6 +9,8 @@ __global__ __launch_bounds__(256) void k_rate(float* out, int iters, long long* 
   uint32_t w[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) { v[k] = threadIdx.x * 0.001f + k; w[k] = threadIdx.x * 2654435761u + k; }
+  float sel_lo = iters * 0.000125f, sel_hi = iters * 0.00075f;  // (run-time values either side of the threshold: nothing folds)
+  asm volatile("" : "+v"(sel_lo), "+v"(sel_hi));
   const long long t0 = clock64();
   for (int i = 0; i < iters; ++i) {
 #pragma unroll
@@ -18,6 +20,9 @@ __global__ __launch_bounds__(256) void k_rate(float* out, int iters, long long* 
       if (KIND == 2) { const uint64_t p = (uint64_t)w[k] * 0xD2511F53u; w[k] = (uint32_t)(p >> 32) ^ (uint32_t)p; }  // v_mad_u64_u32 + xor
       if (KIND == 3) v[k] = __builtin_amdgcn_sqrtf(v[k]) + 1.5f;                        // v_sqrt_f32 + add
       if (KIND == 4) v[k] = v[k] > 2.0f ? v[k] - 1.0f : v[k] + 0.75f;                   // cmp + sub + add + cndmask
+      if (KIND == 5) asm volatile("v_xor_b32 %0, %0, %1" : "+v"(w[k]) : "v"(w[(k + 1) & 7]));  // v_xor_b32 alone (no v_xor3 folding)
+      if (KIND == 6) v[k] = v[k] > 2.0f ? sel_lo : sel_hi;                              // v_cmp_lt_f32 + v_cndmask_b32 (mask through VCC / an SGPR pair)
+      if (KIND == 8) { v[k] = (float)w[k]; w[k] = __float_as_uint(v[k]) + 3u; }         // v_cvt_f32_u32 + add
       if (KIND == 7) { uint64_t t = ((uint64_t)w[k] << 32) | w[(k + 1) & 7]; t += 0x123456789ull * (k + 1); w[k] = (uint32_t)(t >> 32) ^ (uint32_t)t; }  // 64-bit add + xor
     }
   }
@@ -43,29 +48,56 @@ void run(const char* name, int ops_per_iter, float* out, long long* clk) {
          winstr / (ms * 1e-3), 1024.0 * 2.4e9 / (winstr / (ms * 1e-3)), c);
 }
 typedef float float2v __attribute__((ext_vector_type(2)));
+// CHAINS independent chains of packed multiplies per lane, 8 instructions per iteration either way: CHAINS = 8 never waits
+// on its own result; CHAINS = 1 is ONE dependent chain (each v_pk_mul_f32 reads the pair the one before wrote) — the case
+// that draws the hazard wait states, hidden only by the SIMD's other waves
+template <int CHAINS>
 __global__ __launch_bounds__(256) void k_pk(float* out, int iters) {
-  float2v v[8];
+  float2v v[CHAINS];
 #pragma unroll
-  for (int k = 0; k < 8; ++k) v[k] = float2v{threadIdx.x * 0.001f + k, threadIdx.x * 0.002f + k};
+  for (int k = 0; k < CHAINS; ++k) v[k] = float2v{threadIdx.x * 0.001f + k, threadIdx.x * 0.002f + k};
   for (int i = 0; i < iters; ++i) {
 #pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = v[k] * float2v{1.0001f, 0.9999f};  // v_pk_mul_f32
+    for (int k = 0; k < 8; ++k) v[k % CHAINS] = v[k % CHAINS] * float2v{1.0001f, 0.9999f};  // v_pk_mul_f32
   }
   float s = 0;
 #pragma unroll
-  for (int k = 0; k < 8; ++k) s += v[k].x + v[k].y;
+  for (int k = 0; k < CHAINS; ++k) s += v[k].x + v[k].y;
   if (s == -1.0f) out[blockIdx.x] = s;
 }
-void run_pk(float* out, long long*) {
+// 8 fmas per iteration and, with LDS = 1, one 8-byte LDS read (ds_read_b64) whose index comes from the value read before:
+// what a table lookup costs next to vector work (the Box-Muller tables of the importance kernels are two such reads per
+// transform).  Reported per iteration; the difference to LDS = 0 is the read's share of the issue time.
+template <int LDS>
+__global__ __launch_bounds__(256) void k_lds(float* out, int iters) {
+  __shared__ uint2 tab[256];
+  tab[threadIdx.x] = make_uint2(threadIdx.x * 2654435761u, threadIdx.x + 1u);
+  __syncthreads();
+  float v[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) v[k] = threadIdx.x * 0.001f + k;
+  uint32_t idx = threadIdx.x, acc = 0;
+  for (int i = 0; i < iters; ++i) {
+    if (LDS) { const uint2 e = tab[idx & 255u]; idx = e.x >> 7; acc ^= e.y; }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(v[k]) : "v"(1.0001f), "v"(0.5f));  // (kept unpacked)
+  }
+  float s = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) s += v[k];
+  if (s == -1.0f || acc == 0x12345u) out[blockIdx.x] = s + (float)idx;
+}
+template <class K>
+void run_plain(const char* name, K kernel, double instr_per_iter, float* out) {
   hipEvent_t a, b; hipEventCreate(&a); hipEventCreate(&b);
   const int iters = 4000, grid = 256 * 8 * 4;
-  hipLaunchKernelGGL(k_pk, dim3(grid), dim3(256), 0, 0, out, iters);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, 0, out, iters);
   hipEventRecord(a);
-  hipLaunchKernelGGL(k_pk, dim3(grid), dim3(256), 0, 0, out, iters);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, 0, out, iters);
   hipEventRecord(b); hipEventSynchronize(b);
   float ms; hipEventElapsedTime(&ms, a, b);
-  const double winstr = (double)grid * 4 * iters * 8.0;
-  printf("%-28s %.3f ms  %.3e wave-instr/s  (= %.2f cycles per wave-instr per SIMD at 2.4 GHz)\n", "pk_mul_f32", ms, winstr / (ms * 1e-3),
+  const double winstr = (double)grid * 4 * iters * instr_per_iter;
+  printf("%-28s %.3f ms  %.3e wave-instr/s  (= %.2f cycles per wave-instr per SIMD at 2.4 GHz)\n", name, ms, winstr / (ms * 1e-3),
          1024.0 * 2.4e9 / (winstr / (ms * 1e-3)));
 }
 int main() {
@@ -76,6 +108,12 @@ int main() {
   run<3>("sqrt_f32+add", 2, out, clk);
   run<4>("cmp+sub+add+cndmask", 4, out, clk);
   run<7>("add_u64+xor", 2, out, clk);
-  run_pk(out, clk);
+  run<5>("xor_b32", 1, out, clk);
+  run<6>("cmp+cndmask (vcc)", 2, out, clk);
+  run<8>("cvt_f32_u32+add", 2, out, clk);
+  run_plain("pk_mul_f32, 8 chains", k_pk<8>, 8.0, out);
+  run_plain("pk_mul_f32, 1 dependent chain", k_pk<1>, 8.0, out);
+  run_plain("8 fma (per iteration)", k_lds<0>, 1.0, out);
+  run_plain("8 fma + ds_read_b64 (per iteration)", k_lds<1>, 1.0, out);
   return 0;
 }
