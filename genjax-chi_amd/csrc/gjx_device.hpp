@@ -1584,6 +1584,14 @@ template <class Policy>
 GJX_DEV auto policy_set_peers(Policy& P, const int64_t* pd, uint32_t tpr, int) -> decltype(P.set_peers(pd, tpr), void()) { P.set_peers(pd, tpr); }
 template <class Policy>
 GJX_DEV void policy_set_peers(Policy&, const int64_t*, uint32_t, long) {}
+// load_params (the generated policy of a PARAMETERISED plan, include/gjx_smc_params.h): the workgroup's filter is known —
+// the policy reads that filter's row of launch parameters into its members.  The row's address is the kernel argument plus
+// block-index arithmetic and the table is read-only for the launch, so these are scalar loads issued once, in front of
+// the step's first stores, and the values live in scalar registers.  Policies without parameters have no such member.
+template <class Policy>
+GJX_DEV auto policy_load_params(Policy& P, uint32_t f, int) -> decltype(P.load_params(f), void()) { P.load_params(f); }
+template <class Policy>
+GJX_DEV void policy_load_params(Policy&, uint32_t, long) {}
 // a 4-byte element of a source column: index i of the GLOBAL population, read from its owner's arena
 template <bool PEERS, class T>
 GJX_DEV T src_load(const T* base, uint32_t i, const int64_t* pd, uint32_t tpr) {
@@ -1880,8 +1888,10 @@ GJX_DEV void resample_body_impl(const ResampleArgs& A, Policy& P) {
   TileEss* ess_out = A.ess_out;
   const uint64_t* prefix = LDSP ? nullptr : A.prefix;
   double u0 = A.sp ? A.sp->u0 : A.u0;
+  uint32_t filter = 0;
   if (A.fb.n_filters > 1) {
     const uint32_t f = (uint32_t)(b / A.fb.tiles);
+    filter = f;
     b -= (uint64_t)f * A.fb.tiles;
     qw_all += (uint64_t)f * A.fb.stride;
     if (lw_all) lw_all += (uint64_t)f * A.fb.stride;
@@ -1900,6 +1910,7 @@ GJX_DEV void resample_body_impl(const ResampleArgs& A, Policy& P) {
     u0 = A.fb.u0[f];
     P.select_filter((uint64_t)f * A.fb.stride, A.fb.step_key[f]);
   }
+  policy_load_params(P, filter, 0);
   const uint32_t tpr = PEERS ? A.pm.tiles_per_rank : 1u;
   // where tile k of the source population lives (its owner's arena when the population is distributed)
   auto src_subs = [&](uint64_t k) -> const TileSub* { return PEERS ? peer_ptr(subs + k, sh_delta[(uint32_t)k / tpr]) : subs + k; };

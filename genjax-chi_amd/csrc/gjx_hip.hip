@@ -11,6 +11,7 @@
 #include "../../include/gjx_guided.h"
 #include "../../include/gjx_backsim.h"
 #include "../../include/gjx_backmove.h"
+#include "../../include/gjx_smc_params.h"
 #include "gjx_device.hpp"
 
 #include <hip/hip_runtime.h>
@@ -2094,7 +2095,7 @@ struct gjx_plan {
 
 // GJX_ARG_EXPR (gjx.h): a postfix program as a distribution argument.  Well-formed: at most GJX_MAX_EXPR_OPS entries,
 // operands in range for the plan kind, the stack never deeper than 8, exactly one value left.
-static bool expr_ok(const gjx_arg& a, int s, int n_state, int n_obs, bool allow_state) {
+static bool expr_ok(const gjx_arg& a, int s, int n_state, int n_obs, bool allow_state, bool allow_param = false) {
   const gjx_expr_op* ops = reinterpret_cast<const gjx_expr_op*>(a.table);
   if (!ops || a.ref < 1 || a.ref > GJX_MAX_EXPR_OPS) return false;
   int depth = 0;
@@ -2104,7 +2105,7 @@ static bool expr_ok(const gjx_arg& a, int s, int n_state, int n_obs, bool allow_
       case GJX_EXPR_CONST: ++depth; break;
       case GJX_EXPR_SITE: if (r < 0 || r >= s) return false; ++depth; break;
       case GJX_EXPR_INPUT: if (n_state >= 0 || r < 0 || r >= 16) return false; ++depth; break;
-      case GJX_EXPR_PARAM: if (n_state >= 0 || r < 0 || r >= GJX_MAX_PARAMS) return false; ++depth; break;
+      case GJX_EXPR_PARAM: if ((n_state >= 0 && !allow_param) || r < 0 || r >= GJX_MAX_PARAMS) return false; ++depth; break;
       case GJX_EXPR_STATE: if (n_state < 0 || !allow_state || r < 0 || r >= n_state) return false; ++depth; break;
       case GJX_EXPR_OBS: if (n_state < 0 || r < 0 || r >= n_obs) return false; ++depth; break;
       case GJX_EXPR_ADD: case GJX_EXPR_SUB: case GJX_EXPR_MUL: case GJX_EXPR_DIV: case GJX_EXPR_MAX: case GJX_EXPR_MIN:
@@ -2124,17 +2125,18 @@ static bool expr_ok(const gjx_arg& a, int s, int n_state, int n_obs, bool allow_
   return depth == 1;
 }
 
-// Argument validity.  n_state / n_obs > -1 switch on the SMC-plan kinds (STATE only if allow_state).
-static bool arg_ok(const gjx_arg& a, int s, int n_state = -1, int n_obs = -1, bool allow_state = false) {
+// Argument validity.  n_state / n_obs > -1 switch on the SMC-plan kinds (STATE only if allow_state; PARAM only if
+// allow_param: the tables of gjx_smc_plan_create_params, include/gjx_smc_params.h).
+static bool arg_ok(const gjx_arg& a, int s, int n_state = -1, int n_obs = -1, bool allow_state = false, bool allow_param = false) {
   switch (a.kind) {
-    case GJX_ARG_EXPR: return expr_ok(a, s, n_state, n_obs, allow_state);
+    case GJX_ARG_EXPR: return expr_ok(a, s, n_state, n_obs, allow_state, allow_param);
     case GJX_ARG_CONST: return true;
     case GJX_ARG_SITE: return a.ref >= 0 && a.ref < s;
     case GJX_ARG_INPUT: return n_state < 0 && a.ref >= 0 && a.ref < 16;
     case GJX_ARG_TABLE: return a.ref >= 0 && a.ref < s && a.table != nullptr;
     case GJX_ARG_STATE: return allow_state && a.ref >= 0 && a.ref < n_state;
     case GJX_ARG_OBS: return n_obs >= 0 && a.ref >= 0 && a.ref < n_obs;
-    case GJX_ARG_PARAM: return n_state < 0 && a.ref >= 0 && a.ref < GJX_MAX_PARAMS;
+    case GJX_ARG_PARAM: return (n_state < 0 || allow_param) && a.ref >= 0 && a.ref < GJX_MAX_PARAMS;
     default: return false;
   }
 }
@@ -2146,17 +2148,18 @@ static CArg carg(const gjx_arg& a) { return CArg{a.kind, a.ref, 0, a.ref, a.scal
 // `allow_next`: the tables of gjx_backsim_plan_create, where `obs` may also be {GJX_ARG_NEXT, a carry component, 1, 0}
 // (include/gjx_backsim.h); arg_ok knows no such kind, so it is refused everywhere else.
 static bool convert_site(const gjx_site& st, int s, CSite& c, int n_state = -1, int n_obs = -1,
-                         bool allow_state = false, bool allow_guided = false, bool allow_next = false) {
+                         bool allow_state = false, bool allow_guided = false, bool allow_next = false, bool allow_param = false) {
   if (st.observed > (allow_guided ? GJX_SITE_GUIDED : 1)) return false;
-  bool ok = st.dist >= 0 && st.dist <= GJX_DIST_CATEGORICAL && arg_ok(st.arg[0], s, n_state, n_obs, allow_state);
+  bool ok = st.dist >= 0 && st.dist <= GJX_DIST_CATEGORICAL && arg_ok(st.arg[0], s, n_state, n_obs, allow_state, allow_param);
   const bool two_args = st.dist != GJX_DIST_BERNOULLI && st.dist != GJX_DIST_CATEGORICAL;
-  if (ok && two_args) ok = arg_ok(st.arg[1], s, n_state, n_obs, allow_state);
+  if (ok && two_args) ok = arg_ok(st.arg[1], s, n_state, n_obs, allow_state, allow_param);
   if (ok && st.observed == GJX_SITE_GUIDED) {  // (that the partner is a PROPOSED site of the same kind: smc_guided_pairs_ok)
     ok = st.obs.kind == GJX_ARG_SITE && st.obs.ref >= 0 && st.obs.ref < s && st.obs.scale == 1.0f && st.obs.offset == 0.0f;
   } else if (ok && st.observed && st.observed != GJX_SITE_PROPOSED) {
     if (n_state < 0) ok = st.obs.kind == GJX_ARG_CONST || (st.obs.kind == GJX_ARG_INPUT && st.obs.ref >= 0 && st.obs.ref < 16) ||
                           (st.obs.kind == GJX_ARG_PARAM && st.obs.ref >= 0 && st.obs.ref < GJX_MAX_PARAMS);
     else ok = st.obs.kind == GJX_ARG_CONST || (st.obs.kind == GJX_ARG_OBS && st.obs.ref >= 0 && st.obs.ref < n_obs) ||
+              (allow_param && st.obs.kind == GJX_ARG_PARAM && st.obs.ref >= 0 && st.obs.ref < GJX_MAX_PARAMS) ||
               (allow_next && st.obs.kind == GJX_ARG_NEXT && st.obs.ref >= 0 && st.obs.ref < n_state && st.obs.scale == 1.0f &&
                st.obs.offset == 0.0f);
   }
@@ -3415,6 +3418,19 @@ struct gjx_smc_plan {
   bool guided = false;                                // proposed / guided sites (gjx_guided.h): generated kernels only
   bool has_expr = false;                              // any program?  Then the filter runs as generated kernels only
   CSite* dev_init = nullptr; CSite* dev_step = nullptr;  // the interpreter's device copies of the tables (made on first use)
+  // include/gjx_smc_params.h (n_params > 0: a parameterised plan, generated kernels only)
+  int n_params = 0;
+  int n_rows = 0;             // rows of the last gjx_smc_plan_set_params (0: none yet)
+  std::vector<float> rows;    // [n_rows][row_len()]: the caller's values, then the derived constants of init's and step's sites
+  float* dev_rows = nullptr;  // f32[kMaxFilters][row_len()], read by the generated kernels
+  // pinned staging of an upload (one row per filter), used in turn: the copy never waits on the host for the stream, and a
+  // slot is written again only when the copy that read it has run (its event; four runs back: it returns at once)
+  static constexpr int kStage = 4;
+  float* stage[kStage] = {};
+  hipEvent_t stage_ev[kStage] = {};
+  int stage_next = 0;
+  bool rows_dirty = false;    // set_params since the last upload (gjx_smc_plan_step uploads then, and at every step 0)
+  int row_len() const { return n_params + 2 * (n_init + n_step); }
 };
 
 // every PROPOSED site of a table has exactly one GUIDED partner, of its own kind (integer- or float-valued)
@@ -3430,7 +3446,8 @@ static bool smc_guided_pairs_ok(const CSite* sites, int n) {
     if (sites[q].observed == GJX_SITE_PROPOSED && refs[q] != 1) return false;
   return true;
 }
-static int smc_plan_create_impl(const gjx_smc_model* m, gjx_smc_plan** out, bool allow_guided) {
+static int smc_plan_create_impl(const gjx_smc_model* m, gjx_smc_plan** out, bool allow_guided, int n_params = 0) {
+  const bool ap = n_params > 0;
   if (!m || !out || m->n_state < 1 || m->n_state > GJX_SMC_MAX_STATE || m->n_obs < 0 || m->n_obs > GJX_SMC_MAX_OBS ||
       !m->init_sites || !m->step_sites || m->n_init_sites <= 0 || m->n_init_sites > GJX_MAX_SITES ||
       m->n_step_sites <= 0 || m->n_step_sites > GJX_MAX_SITES)
@@ -3439,16 +3456,16 @@ static int smc_plan_create_impl(const gjx_smc_model* m, gjx_smc_plan** out, bool
   if (!p) return GJX_ERR_LAUNCH;
   p->n_state = m->n_state; p->n_obs = m->n_obs; p->n_init = m->n_init_sites; p->n_step = m->n_step_sites;
   bool ok = true;
-  for (int s = 0; ok && s < p->n_init; ++s) ok = convert_site(m->init_sites[s], s, p->init[s], m->n_state, m->n_obs, false, allow_guided);
-  for (int s = 0; ok && s < p->n_step; ++s) ok = convert_site(m->step_sites[s], s, p->step[s], m->n_state, m->n_obs, true, allow_guided);
+  for (int s = 0; ok && s < p->n_init; ++s) ok = convert_site(m->init_sites[s], s, p->init[s], m->n_state, m->n_obs, false, allow_guided, false, ap);
+  for (int s = 0; ok && s < p->n_step; ++s) ok = convert_site(m->step_sites[s], s, p->step[s], m->n_state, m->n_obs, true, allow_guided, false, ap);
   if (ok && allow_guided) {
     ok = smc_guided_pairs_ok(p->init, p->n_init) && smc_guided_pairs_ok(p->step, p->n_step);
     for (int s = 0; s < p->n_init; ++s) p->guided = p->guided || p->init[s].observed > 1;
     for (int s = 0; s < p->n_step; ++s) p->guided = p->guided || p->step[s].observed > 1;
   }
   for (int k = 0; ok && k < p->n_state; ++k) {
-    ok = arg_ok(m->init_state[k], p->n_init, m->n_state, m->n_obs, false) && m->init_state[k].kind != GJX_ARG_TABLE &&
-         arg_ok(m->next_state[k], p->n_step, m->n_state, m->n_obs, true) && m->next_state[k].kind != GJX_ARG_TABLE;
+    ok = arg_ok(m->init_state[k], p->n_init, m->n_state, m->n_obs, false, ap) && m->init_state[k].kind != GJX_ARG_TABLE &&
+         arg_ok(m->next_state[k], p->n_step, m->n_state, m->n_obs, true, ap) && m->next_state[k].kind != GJX_ARG_TABLE;
     p->init_state[k] = carg(m->init_state[k]);
     p->next_state[k] = carg(m->next_state[k]);
   }
@@ -3462,6 +3479,25 @@ static int smc_plan_create_impl(const gjx_smc_model* m, gjx_smc_plan** out, bool
   state_expr_adopt(p->next_state, p->n_state, &p->next_state_expr);
   for (int k = 0; k < p->n_state; ++k)
     p->has_expr = p->has_expr || p->init_state[k].kind == GJX_ARG_EXPR || p->next_state[k].kind == GJX_ARG_EXPR;
+  if (ap) {  // every referenced slot lies inside the row
+    int mx = expr_max_ref(p->init, p->n_init, GJX_EXPR_PARAM);
+    if (expr_max_ref(p->step, p->n_step, GJX_EXPR_PARAM) > mx) mx = expr_max_ref(p->step, p->n_step, GJX_EXPR_PARAM);
+    auto see = [&](const CArg& a) {
+      if (a.kind == GJX_ARG_PARAM && a.ref > mx) mx = a.ref;
+      if (a.kind != GJX_ARG_EXPR) return;
+      const gjx_expr_op* ops = reinterpret_cast<const gjx_expr_op*>(a.table);
+      for (int i = 0; i < a.ref; ++i)
+        if (ops[i].op == GJX_EXPR_PARAM && ops[i].ref > mx) mx = ops[i].ref;
+    };
+    for (int s = 0; s < p->n_init; ++s) { see(p->init[s].a0); see(p->init[s].a1); if (p->init[s].observed == 1) see(p->init[s].obs); }
+    for (int s = 0; s < p->n_step; ++s) { see(p->step[s].a0); see(p->step[s].a1); if (p->step[s].observed == 1) see(p->step[s].obs); }
+    for (int k = 0; k < p->n_state; ++k) { see(p->init_state[k]); see(p->next_state[k]); }
+    if (mx >= n_params) {
+      delete p;
+      return GJX_ERR_INVALID;
+    }
+    p->n_params = n_params;
+  }
   *out = p;
   return GJX_OK;
 }
@@ -3481,8 +3517,108 @@ int gjx_smc_plan_create_scoped(const gjx_smc_model* m, const gjx_scope* init_sco
   *out = p;
   return GJX_OK;
 }
+// ---- parameterised plans (include/gjx_smc_params.h) ---------------------------------------------------------------------
+int gjx_smc_params_version(int* major, int* minor) { return version_out(major, minor, GJX_SMC_PARAMS_VERSION_MAJOR, GJX_SMC_PARAMS_VERSION_MINOR); }
+int gjx_smc_plan_create_params(const gjx_smc_model* m, const gjx_scope* init_scopes, int n_init_scopes,
+                               const gjx_scope* step_scopes, int n_step_scopes, int n_params, gjx_smc_plan** out) {
+  if (n_params < 1 || n_params > GJX_MAX_PARAMS) return GJX_ERR_INVALID;
+  gjx_smc_plan* p = nullptr;
+  const int rc = smc_plan_create_impl(m, &p, true, n_params);
+  if (rc) return rc;
+  if ((p->guided && (n_init_scopes || n_step_scopes)) ||  // (guided plans have flat bodies)
+      !gjx_jit::derive_scopes(m->init_sites, m->n_init_sites, init_scopes, n_init_scopes, p->init_scopes) ||
+      !gjx_jit::derive_scopes(m->step_sites, m->n_step_sites, step_scopes, n_step_scopes, p->step_scopes)) {
+    gjx_smc_plan_destroy(p);
+    return GJX_ERR_INVALID;
+  }
+  *out = p;
+  return GJX_OK;
+}
+// The rows and, per row, the constants of the sites whose arguments are constants or parameters (convert_site: pre == 2)
+// — the spec functions gjx_plan_set_params uses, on the host: IEEE-exact ops give the bits a constant's would have.
+int gjx_smc_plan_set_params(gjx_smc_plan* p, const float* rows, int n_rows) {
+  if (!p || p->n_params < 1 || !rows || n_rows < 1 || n_rows > GJX_SMC_PARAMS_MAX_ROWS) return GJX_ERR_INVALID;
+  const int L = p->row_len(), P = p->n_params;
+  std::lock_guard<std::mutex> lock(p->mu);
+  p->rows.assign((size_t)n_rows * (size_t)L, 0.0f);
+  for (int r = 0; r < n_rows; ++r) {
+    float* row = p->rows.data() + (size_t)r * (size_t)L;
+    memcpy(row, rows + (size_t)r * (size_t)P, sizeof(float) * (size_t)P);
+    auto val = [&](const CArg& a) {  // CONST or PARAM, as the generated source reads it (gjx_plan_jit.hpp SiteEmitter::arg)
+      if (a.kind == GJX_ARG_CONST) return a.offset;
+      if (a.scale == 1.0f && a.offset == 0.0f) return row[a.ref];
+      const float t = a.scale * row[a.ref];
+      return t + a.offset;
+    };
+    auto derive = [&](const CSite* sites, int n, float* d) {
+      for (int q = 0; q < n; ++q) {
+        const CSite& c = sites[q];
+        if (c.pre != 2) continue;
+        if (c.dist == GJX_DIST_NORMAL) {
+          d[2 * q] = normal_rs(val(c.a1));
+          d[2 * q + 1] = normal_lognorm(val(c.a1));
+        } else if (c.dist == GJX_DIST_GAMMA) {
+          d[2 * q + 1] = gamma_lognorm(val(c.a0), val(c.a1));
+        } else {
+          d[2 * q + 1] = beta_lbeta(val(c.a0), val(c.a1));
+        }
+      }
+    };
+    derive(p->init, p->n_init, row + P);
+    derive(p->step, p->n_step, row + P + 2 * p->n_init);
+  }
+  p->n_rows = n_rows;
+  p->rows_dirty = true;
+  return GJX_OK;
+}
+// The rows of a launch of F filters, one per filter, copied to the plan's device table on the caller's stream from pinned
+// staging: asynchronous for the host.  Stream order puts the copy behind the launches of an earlier run and in front of
+// this run's.  (The table and the staging are made at the first upload: a plan is a host object until it runs.)
+static void smc_plan_free_rows(gjx_smc_plan* p) {
+  for (int i = 0; i < gjx_smc_plan::kStage; ++i) {
+    if (p->stage_ev[i]) (void)hipEventDestroy(p->stage_ev[i]);
+    if (p->stage[i]) (void)hipHostFree(p->stage[i]);
+    p->stage_ev[i] = nullptr;
+    p->stage[i] = nullptr;
+  }
+  if (p->dev_rows) (void)hipFree(p->dev_rows);
+  p->dev_rows = nullptr;
+}
+static int smc_plan_upload_rows(gjx_smc_plan* p, int F, gjx_stream s) {
+  std::lock_guard<std::mutex> lock(p->mu);
+  if (p->n_rows < 1 || (p->n_rows != 1 && p->n_rows != F) || F > kMaxFilters) return GJX_ERR_INVALID;
+  const size_t L = (size_t)p->row_len();
+  const size_t table_bytes = sizeof(float) * L * (size_t)kMaxFilters;
+  if (!p->dev_rows) {
+    bool ok = hipMalloc((void**)&p->dev_rows, table_bytes) == hipSuccess;
+    for (int i = 0; ok && i < gjx_smc_plan::kStage; ++i)
+      ok = hipHostMalloc((void**)&p->stage[i], table_bytes, hipHostMallocDefault) == hipSuccess &&
+           hipEventCreateWithFlags(&p->stage_ev[i], hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+      (void)hipGetLastError();
+      smc_plan_free_rows(p);
+      return GJX_ERR_LAUNCH;
+    }
+  }
+  const int slot = p->stage_next;
+  p->stage_next = (slot + 1) % gjx_smc_plan::kStage;
+  if (hipEventSynchronize(p->stage_ev[slot]) != hipSuccess) {  // (never recorded: success at once)
+    (void)hipGetLastError();
+    return GJX_ERR_LAUNCH;
+  }
+  for (int f = 0; f < F; ++f)
+    memcpy(p->stage[slot] + (size_t)f * L, p->rows.data() + (p->n_rows == 1 ? 0 : (size_t)f * L), sizeof(float) * L);
+  if (hipMemcpyAsync(p->dev_rows, p->stage[slot], sizeof(float) * L * (size_t)F, hipMemcpyHostToDevice, S(s)) != hipSuccess ||
+      hipEventRecord(p->stage_ev[slot], S(s)) != hipSuccess) {
+    (void)hipGetLastError();
+    return GJX_ERR_LAUNCH;
+  }
+  p->rows_dirty = false;
+  return GJX_OK;
+}
 int gjx_smc_plan_destroy(gjx_smc_plan* p) {
   if (!p) return GJX_OK;
+  smc_plan_free_rows(p);
   for (auto& c : p->jit) c.release();  // compiled modules are owned by the process-wide (bounded) cache
   for (auto& c : p->jit_peers) c.release();
   free_owned(p->dev_owned);
@@ -3521,6 +3657,7 @@ static std::string smc_plan_source(const gjx_smc_plan* plan, int impl, PlanTable
   g.n_step = plan->n_step; g.init_state = plan->init_state; g.next_state = plan->next_state; g.n_state = plan->n_state;
   g.sc_init = plan->init_scopes.n_scopes > 0 ? &plan->init_scopes : nullptr;
   g.sc_step = plan->step_scopes.n_scopes > 0 ? &plan->step_scopes : nullptr;
+  g.n_params = plan->n_params;
   std::string src = g.run();
   if (tabs) *tabs = ts.reg.tables();
   return src;
@@ -3571,7 +3708,7 @@ static int smc_plan_route(gjx_smc_plan* plan, int impl, gjx_jit::CompiledSmc** c
   if (peers) return gjx_jit::enabled() ? GJX_ERR_JIT : GJX_ERR_UNSUPPORTED;  // (the table-walking policy has no peer form)
   const bool off = !gjx_jit::enabled();
   if (!off && !jit_fallback_allowed()) return GJX_ERR_JIT;  // loud: never a silent slower route
-  if (plan->has_expr || plan->guided || plan->init_scopes.n_scopes > 0 || plan->step_scopes.n_scopes > 0) return off ? GJX_ERR_UNSUPPORTED : GJX_ERR_JIT;
+  if (plan->has_expr || plan->guided || plan->n_params > 0 || plan->init_scopes.n_scopes > 0 || plan->step_scopes.n_scopes > 0) return off ? GJX_ERR_UNSUPPORTED : GJX_ERR_JIT;
   return smc_plan_interp_tables(plan);
 }
 static int smc_plan_step(const gjx_smc_config* cfg, gjx_smc_plan* plan, gjx_jit::CompiledSmc* cp, int t,
@@ -3610,7 +3747,8 @@ static int smc_plan_step(const gjx_smc_config* cfg, gjx_smc_plan* plan, gjx_jit:
       return launch_status();
     }
     PlanTables tabs = cp->tabs;
-    void* args[] = {&PA, &first, &nl, &em, &fb, &tabs};
+    const float* prm_rows = plan->dev_rows;  // (the generated kernels of a parameterised plan take it as their last argument)
+    void* args[] = {&PA, &first, &nl, &em, &fb, &tabs, &prm_rows};
     if (hipModuleLaunchKernel(cp->init, ntl * nf, 1, 1, kBlock, 1, 1, 0, S(s), args, nullptr) != hipSuccess) return GJX_ERR_LAUNCH;
     return launch_status();
   }
@@ -3624,7 +3762,8 @@ static int smc_plan_step(const gjx_smc_config* cfg, gjx_smc_plan* plan, gjx_jit:
     return launch_status();
   }
   PlanTables tabs = cp->tabs;
-  void* args[] = {&A, &PA, &tabs};
+  const float* prm_rows = plan->dev_rows;
+  void* args[] = {&A, &PA, &tabs, &prm_rows};
   if (hipModuleLaunchKernel(ad ? cp->step_adaptive : cp->step, ntl * nf, 1, 1, kBlock, 1, 1, 0, S(s), args, nullptr) != hipSuccess) return GJX_ERR_LAUNCH;
   return launch_status();
 }
@@ -3635,6 +3774,15 @@ int gjx_smc_plan_step(const gjx_smc_config* cfg, gjx_smc_plan* plan, int t, cons
   if (!cfg_ok(cfg) || !plan || t < 0 || t >= cfg->n_steps || !out || (t > 0 && !prev) || (plan->n_obs > 0 && !obs_t) ||
       cfg->n_filters > 1)
     return GJX_ERR_INVALID;
+  if (plan->n_params > 0) {  // include/gjx_smc_params.h: one filter on one device, row 0
+    if (cfg->peers || cfg->first_slot != 0 || cfg->n_local != cfg->n_total) return GJX_ERR_UNSUPPORTED;
+    if (plan->n_rows < 1) return GJX_ERR_INVALID;
+    if (!gjx_jit::enabled()) return GJX_ERR_UNSUPPORTED;
+    if (t == 0 || plan->rows_dirty || !plan->dev_rows) {
+      const int up = smc_plan_upload_rows(plan, 1, s);
+      if (up) return up;
+    }
+  }
   gjx_jit::CompiledSmc* c = nullptr;
   // (the peer transport: steps t >= 1 run the peer form of the generated kernels; step 0 reads no source population)
   const int route = smc_plan_route(plan, cfg->impl, &c, cfg->peers != nullptr && t > 0);
@@ -3887,9 +4035,18 @@ int gjx_smc_run_plan(const gjx_smc_config* cfg, gjx_smc_plan* plan, const float*
   if (!cfg_ok(cfg) || cfg->first_slot != 0 || cfg->n_local != cfg->n_total || !plan || !out_e || !out_q ||
       !state_out || !logw_out || (plan->n_obs > 0 && !obs_host))
     return GJX_ERR_INVALID;
+  if (plan->n_params > 0) {
+    if (cfg->peers) return GJX_ERR_UNSUPPORTED;
+    const int F = cfg->n_filters > 1 ? cfg->n_filters : 1;
+    if (plan->n_rows < 1 || (plan->n_rows != 1 && plan->n_rows != F)) return GJX_ERR_INVALID;  // (no rows yet; rows for another bank)
+  }
   gjx_jit::CompiledSmc* cp = nullptr;
   const int route = smc_plan_route(plan, cfg->impl, &cp);
   if (route) return route;
+  if (plan->n_params > 0) {  // this run's rows, once, in front of its first launch
+    const int up = smc_plan_upload_rows(plan, cfg->n_filters > 1 ? cfg->n_filters : 1, s);
+    if (up) return up;
+  }
   void* st[GJX_SMC_MAX_STATE];
   for (int k = 0; k < plan->n_state; ++k) st[k] = state_out[k];
   auto step = [&](int t, const gjx_smc_pop* prev, const gjx_smc_pop* out, int32_t* pe, uint64_t* pq, int32_t* anc,
@@ -4133,6 +4290,7 @@ int gjx_smc_sharded_run_hmm(gjx_comm* c, const gjx_smc_config* cfg, const gjx_hm
 int gjx_smc_sharded_run_plan(gjx_comm* c, const gjx_smc_config* cfg, gjx_smc_plan* plan, const float* obs_host,
                              const gjx_sharded_io* io, gjx_stream s) {
   if (!c || !c->t || !plan) return GJX_ERR_INVALID;
+  if (plan->n_params > 0) return GJX_ERR_UNSUPPORTED;  // (include/gjx_smc_params.h: out of scope)
   return gjx_sharded::run_plan(*c->t, cfg, plan, plan->n_state, plan->n_obs, obs_host, io, s);
 }
 

@@ -183,7 +183,11 @@ struct SiteEmitter {
         return "((" + flit(a.scale) + " * cols.in[" + std::to_string(a.ref) + "][li" + sfx + "]) + " + flit(a.offset) + ")";
       case GJX_ARG_STATE: return "((" + flit(a.scale) + " * st_" + std::to_string(a.ref) + sfx + ") + " + flit(a.offset) + ")";
       case GJX_ARG_OBS: return "((" + flit(a.scale) + " * a.obs[" + std::to_string(a.ref) + "]) + " + flit(a.offset) + ")";
-      case GJX_ARG_PARAM: return "((" + flit(a.scale) + " * prm.p[" + std::to_string(a.ref) + "]) + " + flit(a.offset) + ")";
+      case GJX_ARG_PARAM:
+        // (an SMC plan's parameter as it stands is the row's value itself: no multiply by 1, no add of 0 — a uniform value
+        // stays in its scalar register — and what gjx_smc_plan_set_params derives the site's constants from)
+        if (mode == 1 && a.scale == 1.0f && a.offset == 0.0f) return "prm.p[" + std::to_string(a.ref) + "]";
+        return "((" + flit(a.scale) + " * prm.p[" + std::to_string(a.ref) + "]) + " + flit(a.offset) + ")";
       case GJX_ARG_EXPR: {
         // the postfix program as ONE parenthesised f32 expression: every operator rounds once, in program order (the
         // translation unit is compiled with -ffp-contract=off: no fusion, no re-association)
@@ -1000,6 +1004,21 @@ struct GenSmc {
   const ScopeInfo* sc_init = nullptr;  // nested calls inside init / step (null: flat bodies)
   const ScopeInfo* sc_step = nullptr;
   bool peers = false;  // r04: the step kernels of the peer transport (the source population lives in the peers' arenas)
+  // include/gjx_smc_params.h: > 0 — the bodies read `prm.p[slot]` / `prm.d[2 site (+ 1)]` from the workgroup's filter's row
+  // of the plan's device table, f32[filters][row_len()]: the caller's parameters, then the derived constants of the init
+  // table's sites, then those of the step table's.  Both kernels take the table as one more argument
+  // (`const float* __restrict__`: read-only for the launch) and copy the entries their body names into members at entry,
+  // where the filter is known: a compile-time offset from a workgroup-uniform base each, so scalar loads into scalar
+  // registers (entries no body names are never loaded).  0: the source is the plain plan's, byte for byte.
+  int n_params = 0;
+  int row_len() const { return n_params + 2 * (n_init + n_step); }
+  void emit_prm_struct(const char* name, int n_sites, int d_off) {
+    o << "struct " << name << " {\n  float p[" << n_params << "], d[" << 2 * n_sites << "];\n";
+    o << "  __device__ __forceinline__ void load(const float* __restrict__ rows, uint32_t f) {\n";
+    o << "    const float* __restrict__ row = rows + (size_t)f * " << row_len() << "u;\n";
+    o << "#pragma unroll\n    for (int k = 0; k < " << n_params << "; ++k) p[k] = row[k];\n";
+    o << "#pragma unroll\n    for (int k = 0; k < " << 2 * n_sites << "; ++k) d[k] = row[" << d_off << " + k];\n  }\n};\n";
+  }
 
   // PHILOX: the four consecutive slots jq .. jq+3 of a lane (jq a multiple of 4) walked together.  One-word draw
   // number f of the quad is ONE block, PH(ctr = (g_lo, g_hi, f, 'Q'), key = step key), g = jq / 4, slot u taking
@@ -1101,10 +1120,15 @@ struct GenSmc {
     es.sc = sc_step;
     ei.sc = sc_init;
     // ---- step policy
+    if (n_params > 0) emit_prm_struct("GenStepPrm", n_step, n_params + 2 * n_init);
     o << "struct GenPolicy {\n  static constexpr bool kEmit = true;\n  static constexpr bool kPeers = " << (peers ? "true" : "false") << ";\n  PlanPolicyArgs a;\n  PlanTables tabs;\n";
     o << "  const int64_t* pd = nullptr;\n  uint32_t tpr = 1;\n";
     o << "  __device__ __forceinline__ void set_peers(const int64_t* d, uint32_t t) { pd = d; tpr = t; }\n";
     o << "  struct Out { float s[" << D << "]; };\n";
+    if (n_params > 0) {
+      o << "  GenStepPrm prm;\n  const float* __restrict__ prm_rows = nullptr;\n";
+      o << "  __device__ __forceinline__ void load_params(uint32_t f) { prm.load(prm_rows, f); }\n";
+    }
     o << "  __device__ __forceinline__ void select_filter(uint64_t off, Key k) {\n";
     o << "    for (int c = 0; c < " << D << "; ++c) { a.prev_state[c] += off; a.state_out[c] += off; }\n";
     o << "    if (a.anc_out) a.anc_out += off; a.step_key = k;\n  }\n";
@@ -1130,28 +1154,34 @@ struct GenSmc {
     o << "      return;\n    }\n";
     o << "    for (int u = 0; u < 4; ++u) if (ok[u]) store(jq + u, out_lo, anc[u], o[u]);\n  }\n};\n";
     // two instantiations, as for the hand-written filters: the every-step form carries no ESS decision / keep-your-particle path
-    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_smc_step_kernel(ResampleArgs A, PlanPolicyArgs PA, PlanTables T) {\n";
-    o << "  GenPolicy P;\n  P.a = PA;\n  P.tabs = T;\n  resample_body<" << I << ", GenPolicy, false, GenPolicy::kPeers>(A, P);\n}\n";
-    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_smc_step_kernel_adaptive(ResampleArgs A, PlanPolicyArgs PA, PlanTables T) {\n";
-    o << "  GenPolicy P;\n  P.a = PA;\n  P.tabs = T;\n  resample_body<" << I << ", GenPolicy, true, GenPolicy::kPeers>(A, P);\n}\n";
+    const std::string PRM_ARG = n_params > 0 ? ", const float* __restrict__ prm_rows" : "", PRM_SET = n_params > 0 ? "  P.prm_rows = prm_rows;\n" : "";
+    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_smc_step_kernel(ResampleArgs A, PlanPolicyArgs PA, PlanTables T" << PRM_ARG << ") {\n";
+    o << "  GenPolicy P;\n  P.a = PA;\n  P.tabs = T;\n" << PRM_SET << "  resample_body<" << I << ", GenPolicy, false, GenPolicy::kPeers>(A, P);\n}\n";
+    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_smc_step_kernel_adaptive(ResampleArgs A, PlanPolicyArgs PA, PlanTables T" << PRM_ARG << ") {\n";
+    o << "  GenPolicy P;\n  P.a = PA;\n  P.tabs = T;\n" << PRM_SET << "  resample_body<" << I << ", GenPolicy, true, GenPolicy::kPeers>(A, P);\n}\n";
     // ---- init kernel: one workgroup per LOCAL tile, like k_lgssm_init
+    if (n_params > 0) emit_prm_struct("GenInitPrm", n_init, n_params);
     if (impl == 1) {
       o << "struct GenInitOut { float s[" << D << "]; };\n";
-      o << "__device__ __forceinline__ void init_quad(const PlanPolicyArgs& a, const PlanTables& tabs, int64_t jq, GenInitOut (&out)[4], float (&wq)[4]) {\n";
+      o << "__device__ __forceinline__ void init_quad(const PlanPolicyArgs& a, const PlanTables& tabs, " << (n_params > 0 ? "const GenInitPrm& prm, " : "")
+        << "int64_t jq, GenInitOut (&out)[4], float (&wq)[4]) {\n";
       emit_quad_body(init_sites, n_init, init_state, false);
       o << "}\n";
     }
-    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_smc_init_kernel(PlanPolicyArgs a, uint64_t first_slot, uint64_t n_local, EmitOut em, FilterBatch fb, PlanTables tabs) {\n";
+    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_smc_init_kernel(PlanPolicyArgs a, uint64_t first_slot, uint64_t n_local, EmitOut em, FilterBatch fb, PlanTables tabs" << PRM_ARG << ") {\n";
     o << "  uint64_t ltile = blockIdx.x;\n";
+    if (n_params > 0) o << "  uint32_t filter = 0;\n";
     o << "  if (fb.n_filters > 1) {  // several filters per launch: tile of filter f, its key, its outputs\n";
     o << "    const uint32_t f = (uint32_t)(ltile / fb.tiles);\n    ltile -= (uint64_t)f * fb.tiles;\n    a.step_key = fb.step_key[f];\n";
+    if (n_params > 0) o << "    filter = f;\n";
     o << "    for (int k = 0; k < " << D << "; ++k) a.state_out[k] += (uint64_t)f * fb.stride;\n";
     o << "    if (a.anc_out) a.anc_out += (uint64_t)f * fb.stride;\n    select_filter_emit(em, fb, f);\n  }\n";
+    if (n_params > 0) o << "  GenInitPrm prm;\n  prm.load(prm_rows, filter);  // (this filter's row: scalar loads, in front of every store)\n";
     o << "  const uint64_t loc = ltile * kTile + 4 * (uint64_t)threadIdx.x;\n  const uint64_t gq = first_slot + loc;\n";
     o << "  float wq[4];\n  bool okq[4];\n  for (int u = 0; u < 4; ++u) okq[u] = loc + u < n_local;\n";
     if (impl == 1) {  // four consecutive slots per lane, one cipher block per one-word draw of the quad
       o << "  {\n    const int64_t jq = (int64_t)gq;\n    GenInitOut out[4];\n";
-      o << "    init_quad(a, tabs, jq, out, wq);\n";
+      o << "    init_quad(a, tabs, " << (n_params > 0 ? "prm, " : "") << "jq, out, wq);\n";
       o << "    for (int u = 0; u < 4; ++u) {\n      if (okq[u]) {\n";
       for (int k = 0; k < n_state; ++k) o << "        a.state_out[" << k << "][loc + u] = out[u].s[" << k << "];\n";
       o << "        if (a.anc_out) a.anc_out[loc + u] = (int32_t)(gq + u);\n      }\n    }\n  }\n";

@@ -84,6 +84,10 @@ class BackmoveUnavailable(HeaderUnavailable):
     header, why = "gjx_backmove.h", "the MCMC backward moves run as generated HIP kernels only"
 
 
+class SmcParamsUnavailable(HeaderUnavailable):
+    header, why = "gjx_smc_params.h", "parameterised filters run as generated HIP kernels only"
+
+
 class Keys(C.Structure):
     _fields_ = [
         ("impl", C.c_int32),
@@ -555,6 +559,17 @@ BACKMOVE_PROTOTYPES = {
 BACKMOVE_ABI_VERSION = (0, 1)
 BACKMOVE_MAX_MOVES = 256  # gjx_backmove.h: GJX_BACKMOVE_MAX_MOVES
 
+# include/gjx_smc_params.h: a SIXTH header, same arrangement — parameterised state-space models (one parameter row per
+# filter of a launch) as plain gjx_smc_plan objects
+SMC_PARAMS_PROTOTYPES = {
+    "gjx_smc_params_version": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gjx_smc_plan_create_params": (C.c_int, [C.POINTER(SmcModel), C.POINTER(Scope), C.c_int, C.POINTER(Scope), C.c_int, C.c_int,
+                                             C.POINTER(_P)]),
+    "gjx_smc_plan_set_params": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int]),
+}
+SMC_PARAMS_ABI_VERSION = (0, 1)
+SMC_PARAMS_MAX_ROWS = 16  # gjx_smc_params.h: GJX_SMC_PARAMS_MAX_ROWS
+
 # The optional headers, in the order they are bound: every one is exported by libgjx_hip.so only and bound if present.
 class Header(collections.namedtuple("Header", "key header version_fn prototypes version_name unavailable")):
     @property
@@ -572,11 +587,18 @@ OPTIONAL_HEADERS = {h.key: h for h in (
 EXTENSION_HEADERS = {h.key: h for h in (
     Header("backmove", "gjx_backmove.h", "gjx_backmove_version", BACKMOVE_PROTOTYPES, "BACKMOVE_ABI_VERSION", BackmoveUnavailable),
 )}
+# Headers that add creators / setters for the objects of gjx.h itself (gjx_smc_params.h makes and configures a
+# gjx_smc_plan).  A table of its own for the reason EXTENSION_HEADERS is one: the suites of the earlier headers pin the
+# contents of the two tables above; bound after them and looked up with them everywhere.
+PLAN_HEADERS = {h.key: h for h in (
+    Header("smc_params", "gjx_smc_params.h", "gjx_smc_params_version", SMC_PARAMS_PROTOTYPES, "SMC_PARAMS_ABI_VERSION",
+           SmcParamsUnavailable),
+)}
 
 
 def all_optional_headers():
-    """Every header next to gjx.h, in binding order: OPTIONAL_HEADERS, then EXTENSION_HEADERS."""
-    return (*OPTIONAL_HEADERS.values(), *EXTENSION_HEADERS.values())
+    """Every header next to gjx.h, in binding order: OPTIONAL_HEADERS, then EXTENSION_HEADERS, then PLAN_HEADERS."""
+    return (*OPTIONAL_HEADERS.values(), *EXTENSION_HEADERS.values(), *PLAN_HEADERS.values())
 
 
 _HEADER_OF = {name: h for h in all_optional_headers() for name in h.prototypes}  # entry point -> its optional header
@@ -654,7 +676,7 @@ class GjxLib:
     def require(self, key: str, fn_name: str):
         """Raise the header's *Unavailable, naming `fn_name`, on a library without the optional header `key`."""
         if not self.has[key]:
-            raise (OPTIONAL_HEADERS.get(key) or EXTENSION_HEADERS[key]).unavailable(fn_name, self.name)
+            raise next(h for h in all_optional_headers() if h.key == key).unavailable(fn_name, self.name)
 
     def call(self, name: str, *args):
         h = _HEADER_OF.get(name)

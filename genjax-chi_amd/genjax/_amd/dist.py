@@ -555,6 +555,11 @@ class ShardedSMC:
                  n_states=None, lgssm=None, y=None, plan=None, obs=None, ess_threshold: float = 0.0, arena=None):
         """`lgssm` (abi.Lgssm) / `y`: another linear-Gaussian model and observation sequence than the benchmark's.
         kind "plan": a generated filter — `plan` from `ops.smc_plan_create`, `obs` [T, n_obs]."""
+        if kind == "plan" and getattr(plan, "n_params", 0):
+            from .plan import PlanUnsupported
+
+            raise PlanUnsupported("ShardedSMC: a parameterised plan (StateSpaceModel(..., params=...)) runs on one device; "
+                                  "build the model at a fixed θ to shard it")
         tile = ops.tile
         if n_total % (world * tile) != 0:
             raise ValueError(f"n_total must be a multiple of world*{tile}")

@@ -665,9 +665,14 @@ class Ops:
 
     # ---- bootstrap SMC for a user model (init + step site tables) --------------------------------
     def smc_plan_create(self, init_sites, step_sites, init_state, next_state, n_obs: int, init_scopes=(), step_scopes=(),
-                        guided: bool = False) -> "SmcPlan":
+                        guided: bool = False, n_params: int = 0) -> "SmcPlan":
         """`guided`: the tables may hold proposed / guided sites (include/gjx_guided.h: gjx_smc_plan_create_guided; raises
-        abi.GuidedUnavailable on a library without that header — the CPU oracle)."""
+        abi.GuidedUnavailable on a library without that header — the CPU oracle).
+        `n_params` > 0: a parameterised plan (include/gjx_smc_params.h: gjx_smc_plan_create_params; ARG_PARAM arguments and
+        EXPR_PARAM leaves read a row of `n_params` launch parameters, set with `SmcPlan.set_params`; raises
+        abi.SmcParamsUnavailable on a library without that header)."""
+        if n_params:
+            self.lib.require("smc_params", "gjx_smc_plan_create_params")
         if guided:
             self.lib.require("guided", "gjx_smc_plan_create_guided")
         if guided and (init_scopes or step_scopes):
@@ -682,6 +687,12 @@ class Ops:
             m.next_state[k] = a
         m.n_state, m.n_obs = len(next_state), n_obs
         handle = C.c_void_p()
+        if n_params:
+            si = (abi.Scope * len(init_scopes))(*[abi.Scope(*k) for k in init_scopes]) if init_scopes else None
+            ss = (abi.Scope * len(step_scopes))(*[abi.Scope(*k) for k in step_scopes]) if step_scopes else None
+            self.lib.call("gjx_smc_plan_create_params", C.byref(m), si, len(init_scopes), ss, len(step_scopes), int(n_params),
+                          C.byref(handle))
+            return SmcPlan(self, handle, len(next_state), n_obs, int(n_params))
         if guided:
             self.lib.call("gjx_smc_plan_create_guided", C.byref(m), C.byref(handle))
         elif init_scopes or step_scopes:  # nested `@gen` calls inside init / step
@@ -901,8 +912,19 @@ class SmcPopulation:
 
 
 class SmcPlan:
-    def __init__(self, ops: "Ops", handle, n_state: int, n_obs: int):
-        self.ops, self.handle, self.n_state, self.n_obs = ops, handle, n_state, n_obs
+    def __init__(self, ops: "Ops", handle, n_state: int, n_obs: int, n_params: int = 0):
+        self.ops, self.handle, self.n_state, self.n_obs, self.n_params = ops, handle, n_state, n_obs, n_params
+
+    def set_params(self, rows):
+        """gjx_smc_plan_set_params (include/gjx_smc_params.h): `rows` f32[n_params] — one row for every filter of the launches
+        that follow — or f32[F, n_params], one per filter of a run of F filters.  Copied by the library."""
+        import numpy as np
+
+        r = np.ascontiguousarray(np.asarray(rows, dtype=np.float32))
+        r = r.reshape(1, -1) if r.ndim == 1 else r
+        if r.ndim != 2 or r.shape[1] != self.n_params:
+            raise ValueError(f"set_params: rows of {self.n_params} values expected, got an array of shape {tuple(r.shape)}")
+        self.ops.lib.call("gjx_smc_plan_set_params", self.handle, r.ctypes.data_as(C.POINTER(C.c_float)), int(r.shape[0]))
 
     def compile_check(self, impl: int) -> int:
         return self.ops.lib._gjx_smc_plan_compile_check(self.handle, impl)

@@ -444,13 +444,26 @@ class ParamVal:
     concrete value and does its arithmetic on the host with the operands' own types — exactly what the per-site column
     path would compute — but reaches the kernel as a PARAMETER, so its value is not part of the kernel's source.
     Anything that would turn it into structure (a comparison, `float()`, an index, mixing with a traced site value)
-    raises `PlanUnsupported`; the body is then traced again with plain constants."""
+    raises `PlanUnsupported`; the body is then traced again with plain constants.
 
-    __slots__ = ("value", "slot")
+    A parameter of a parameterised state-space model (smc_plan.py: `StateSpaceModel(..., params=...)`) also carries its
+    DERIVATION — a closure `theta -> value` that its arithmetic methods compose — and the declared parameter's `name`:
+    the slot row of another theta is then computed without tracing the body again, and a misuse names the parameter."""
 
-    def __init__(self, value):
+    __slots__ = ("value", "slot", "deriv", "name")
+
+    def __init__(self, value, deriv=None, name=None):
         # (a tensor does its host arithmetic as a site value does on the per-site path: lang.SpecTensor)
-        self.value, self.slot = _spec_wrap(value), None
+        self.value, self.slot, self.deriv, self.name = _spec_wrap(value), None, deriv, name
+
+    def _derived(self, value, fn, *operands):
+        """The result of host arithmetic `fn` over `operands` (ParamVals and numbers): its value, and — if any operand has a
+        derivation — the composed one."""
+        named = [x for x in operands if isinstance(x, ParamVal) and x.deriv is not None]
+        if not named:
+            return ParamVal(value)
+        parts = [(x.deriv if isinstance(x, ParamVal) and x.deriv is not None else (lambda th, c=ParamVal._v(x): c)) for x in operands]
+        return ParamVal(value, lambda th: fn(*[d(th) for d in parts]), named[0].name)
 
     @staticmethod
     def _v(x):
@@ -465,7 +478,9 @@ class ParamVal:
             o = ParamVal._v(other)
             if o is None:
                 return NotImplemented  # (a traced value: its reflected method builds the expression)
-            return ParamVal(op(o, self.value) if swap else op(self.value, o))
+            if swap:
+                return self._derived(op(o, self.value), op, other, self)
+            return self._derived(op(self.value, o), op, self, other)
 
         return f
 
@@ -477,24 +492,34 @@ class ParamVal:
     del _bin
 
     def __neg__(self):
-        return ParamVal(-self.value)
+        return self._derived(-self.value, lambda a: -a, self)
 
     def __abs__(self):
-        return ParamVal(abs(self.value))
+        return self._derived(abs(self.value), abs, self)
+
+    def _structure(self) -> str:
+        if self.name is None:
+            return "a launch parameter used as structure"
+        return (f"the model parameter {self.name!r} used as structure (a comparison, float(), an index, an integer argument of "
+                "a distribution): its value would become part of the kernel; build the model at a fixed value instead")
 
     def _no(self, *a, **k):
-        raise PlanUnsupported("a launch parameter used as structure")
+        raise PlanUnsupported(self._structure())
 
     __bool__ = __float__ = __int__ = __index__ = __lt__ = __le__ = __gt__ = __ge__ = __len__ = __iter__ = _no
     __array__ = __floordiv__ = __rfloordiv__ = __mod__ = __rmod__ = _no
     __hash__ = object.__hash__
 
     def __eq__(self, other):
-        raise PlanUnsupported("a launch parameter used as structure")
+        raise PlanUnsupported(self._structure())
+
+    __ne__ = __eq__
 
     @classmethod
     def __torch_function__(cls, func, types, args=(), kwargs=None):
-        raise PlanUnsupported(f"torch.{getattr(func, '__name__', func)} on a launch parameter")
+        named = next((a.name for a in args if isinstance(a, ParamVal) and a.name is not None), None)
+        raise PlanUnsupported(f"torch.{getattr(func, '__name__', func)} on " +
+                              ("a launch parameter" if named is None else f"the model parameter {named!r}"))
 
 
 class _Table:
@@ -629,6 +654,8 @@ class PlanTracer(_Handler):
             is_int = True
         elif isinstance(gen_fn, Categorical):
             kind, v = args[0] if isinstance(args[0], tuple) else ("logits", args[0])
+            if isinstance(v, ParamVal) and v.name is not None:
+                raise PlanUnsupported(v._structure())
             if isinstance(v, (Sym, _Table, ParamVal)):
                 raise PlanUnsupported("data-dependent categorical parameters")
             site.dist = abi.DIST_CATEGORICAL

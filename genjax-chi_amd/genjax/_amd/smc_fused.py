@@ -134,11 +134,12 @@ def _obs_addrs(observations: ChoiceMap) -> list:
     return [a for a, _ in observations.leaves()]
 
 
-def _build_plan(ops, model: StateSpaceModel, observations: ChoiceMap):
-    """-> (SmcPlan, observation matrix [T, n_obs]) of a user-written model and its observed sequences."""
+def _build_plan(ops, model: StateSpaceModel, observations: ChoiceMap, theta=None):
+    """-> (SmcPlan, observation matrix [T, n_obs]) of a user-written model and its observed sequences.  `theta`: where a
+    model with parameters is traced (smc_plan.build_smc_plan)."""
     addrs = _obs_addrs(observations)
     with use_ops(ops):
-        plan, _ = build_smc_plan(model, addrs)
+        plan, _ = build_smc_plan(model, addrs, theta)
     return plan, observation_matrix(observations, addrs)
 
 
@@ -214,8 +215,12 @@ class BootstrapSMC:
     resamplings the log-weights accumulate (gjx.h: gjx_smc_config.ess_threshold)."""
 
     def __init__(self, model, observations, n_particles: int, record_ancestors: bool = False, ess_threshold: float = 0.0,
-                 record_history: bool = False):
-        """`record_history`: `run()` also returns every step's particles and log-weights (`SMCResult.history`,
+                 record_history: bool = False, params=None):
+        """`params`: the default parameter row theta of a `StateSpaceModel(..., params=names)` (a sequence in declaration
+        order); `run(key, params=...)` / `run_many(keys, params=...)` take a row (or one per key) for that call.  The plan
+        is compiled once, whatever theta is; a row is rounded to f32 and that is what the filter runs.
+
+        `record_history`: `run()` also returns every step's particles and log-weights (`SMCResult.history`,
         `.log_weight_history`; the ancestor table is then always recorded) — what `SMCResult.trajectories` traces back.
         Memory: 4 T n bytes per state column, the log-weights and the ancestors (T=100, n=1e6: 0.4 GB each).  Such a run
         is a stream of per-step launches (`run_with_history`), bit-equal to the default whole-run call in everything both
@@ -225,6 +230,12 @@ class BootstrapSMC:
         self.ess_threshold = float(ess_threshold)
         self._plan = None  # (SmcPlan, observation matrix) of a StateSpaceModel, built at the first run
         self._transition = None  # (BacksimPlan, observation rows) of `backward_simulate`, built at its first call
+        self.params = None if params is None else np.asarray(params, dtype=np.float64).reshape(-1)
+        self._parameterised = isinstance(model, StateSpaceModel) and bool(model.params)
+        if params is not None and not self._parameterised:
+            raise ValueError("params=... needs a StateSpaceModel that declares parameters (StateSpaceModel(init, step, params=(...)))")
+        if self.params is not None and len(self.params) != len(model.params):
+            raise ValueError(f"the model declares {len(model.params)} parameters {model.params}, got {len(self.params)} values")
         if isinstance(model, StateSpaceModel) and not isinstance(observations, ChoiceMap):
             raise TypeError("observations for a StateSpaceModel are a ChoiceMap of length-T sequences")
         self.observations = observations if isinstance(observations, ChoiceMap) else np.asarray(observations)
@@ -232,16 +243,41 @@ class BootstrapSMC:
     def get_num_particles(self):
         return self.n
 
-    def _bind(self, ops):
+    def _bind(self, ops, theta=None):
         """The filter model bound to `ops`: per call for a fixed model (its tensors may change between runs); the plan and
-        the observation matrix of a StateSpaceModel are built once and kept."""
+        the observation matrix of a StateSpaceModel are built once and kept (`theta`: where a model with parameters is
+        traced that once)."""
         if isinstance(self.model, StateSpaceModel) and self._plan is None:
-            self._plan = _build_plan(ops, self.model, self.observations)
+            self._plan = _build_plan(ops, self.model, self.observations, theta)
         return _bind_model(ops, self.model, self.observations, self._plan)
 
-    def run(self, key: prng.PRNGKey) -> SMCResult:
+    def _thetas(self, params, n_keys: int | None = None):
+        """The theta rows of a call, f64[1 or n_keys, P] (None for a model without parameters): `params`, else the default."""
+        if not self._parameterised:
+            if params is not None:
+                raise ValueError("params=... needs a StateSpaceModel that declares parameters")
+            return None
+        th = self.params if params is None else np.asarray(params, dtype=np.float64)
+        if th is None:
+            raise ValueError(f"the model declares the parameters {self.model.params}: pass params=... to the filter or to this call")
+        P = len(self.model.params)
+        th = th.reshape(1, -1) if th.ndim < 2 else th
+        if th.ndim != 2 or th.shape[1] != P or th.shape[0] not in ((1,) if n_keys is None else (1, n_keys)):
+            raise ValueError(f"params: one row of {P} values" + ("" if n_keys is None else f", or an array [{n_keys}, {P}] (one row per key)")
+                             + f"; got shape {tuple(np.shape(params if params is not None else self.params))}")
+        return th
+
+    def _set_rows(self, model, thetas):
+        """The slot rows of `thetas` (smc_plan.ParamSpace: theta, then the values the bodies derive from it on the host) into
+        the plan, for the launches that follow."""
+        if thetas is not None:
+            model.plan.set_params(model.plan._space.rows(thetas))
+
+    def run(self, key: prng.PRNGKey, params=None) -> SMCResult:
         ops = get_ops()
-        model = self._bind(ops)
+        thetas = self._thetas(params)
+        model = self._bind(ops, None if thetas is None else thetas[0])
+        self._set_rows(model, thetas)
         if self.record_history:
             return _history_run(ops, model, self.n, key, self.ess_threshold)
         sk, rk = smc_key_schedule(key, model.T)
@@ -266,6 +302,11 @@ class BootstrapSMC:
         own size; K = 0 is trace-back from multinomial leaves, and a few moves already undo the genealogy's collapse.  It
         reads `result.ancestors` (`ValueError` without); `abi.BackmoveUnavailable` on a library without
         include/gjx_backmove.h.  `n_moves=None`: the exact method above."""
+        if self._parameterised:
+            from .plan import PlanUnsupported
+
+            raise PlanUnsupported(f"backward_simulate() of a model with parameters {self.model.params}: transition tables hold "
+                                  "constants only — build the model at a fixed θ to smooth")
         if result.history is None or result.log_weight_history is None:
             raise ValueError("backward_simulate() needs the per-step states: run the filter with BootstrapSMC(..., record_history=True)")
         if n_moves is not None:
@@ -298,29 +339,39 @@ class BootstrapSMC:
         unique = 1 + (srt[:, 1:] != srt[:, :-1]).sum(1)
         return Trajectories(_columns(paths), lin, unique.to(torch.int64), None, None, sums, sumsq, is_f32)
 
-    def run_many(self, keys) -> list:
+    def run_many(self, keys, params=None) -> list:
         """`vmap(self.run)(keys)`: one independent filter per key.  Up to 16 filters step in the same kernel launches
         (`gjx_smc_config.n_filters`: a 1e6-particle step alone is under one round of an MI355X), for the hand-written
-        models and for generated ones alike; element b equals `self.run(keys[b])` bit for bit."""
+        models and for generated ones alike; element b equals `self.run(keys[b])` bit for bit.
+        `params` (a model with parameters): one theta row for every key, or an array [len(keys), P] with one row per key —
+        a BANK of filters, filter b at theta_b in the same launches; element b equals `self.run(keys[b], params=rows[b])`."""
         keys = list(keys)
+        thetas = self._thetas(params, len(keys))
+        row = (lambda b: None) if thetas is None else (lambda b: thetas[b if len(thetas) > 1 else 0])
         if self.record_history or len(keys) < 2:
-            return [self.run(k) for k in keys]
+            return [self.run(k, row(b)) for b, k in enumerate(keys)]
         ops, out = get_ops(), []
-        model = self._bind(ops)
+        model = self._bind(ops, row(0))
         for lo in range(0, len(keys), 16):
             chunk = keys[lo:lo + 16]
             if len(chunk) == 1:
-                out.append(self.run(chunk[0]))
+                out.append(self.run(chunk[0], row(lo)))
                 continue
             try:
+                self._set_rows(model, None if thetas is None else (thetas if len(thetas) == 1 else thetas[lo:lo + 16]))
                 out.extend(self._run_chunk(ops, chunk, model.T, model))
             except abi.GjxError as e:
                 # populations too large for a filter batch (more than 2048 tiles per filter, or a workspace the
                 # device cannot hold): the documented contract is "element b equals self.run(keys[b])" — run them so
                 if e.code not in (-2, -3):  # GJX_ERR_UNSUPPORTED, GJX_ERR_WORKSPACE
                     raise
-                out.extend(self.run(k) for k in chunk)
+                out.extend(self.run(k, row(lo + b)) for b, k in enumerate(chunk))
         return out
+
+    def log_marginal_likelihoods(self, keys, params=None) -> np.ndarray:
+        """float64[len(keys)]: the log-marginal-likelihood estimate of every filter of `run_many(keys, params)` — with one
+        theta row per key, up to 16 points of a likelihood surface per launch."""
+        return np.asarray([r.log_marginal_likelihood for r in self.run_many(keys, params)], dtype=np.float64)
 
     def _run_chunk(self, ops, chunk, T, model) -> list:
         pairs = [smc_key_schedule(k, T) for k in chunk]
@@ -328,8 +379,8 @@ class BootstrapSMC:
         out = ops._smc_run(model, chunk[0].impl, self.n, sk, rk, self.record_ancestors, self.ess_threshold)
         return [_result(ops, self.n, out, f) for f in range(len(chunk))]
 
-    def log_marginal_likelihood_estimate(self, key: prng.PRNGKey) -> float:
-        return self.run(key).log_marginal_likelihood
+    def log_marginal_likelihood_estimate(self, key: prng.PRNGKey, params=None) -> float:
+        return self.run(key, params).log_marginal_likelihood
 
 
 class GuidedSMC(BootstrapSMC):
@@ -356,16 +407,86 @@ class GuidedSMC(BootstrapSMC):
     sharded drivers (`ShardedSMC`) are out of scope: nothing there has been run or tested with them."""
 
     def __init__(self, model: StateSpaceModel, observations, n_particles: int, step_proposal, init_proposal=None,
-                 record_ancestors: bool = False, ess_threshold: float = 0.0, record_history: bool = False):
+                 record_ancestors: bool = False, ess_threshold: float = 0.0, record_history: bool = False, params=None):
+        """A model with parameters (`StateSpaceModel(..., params=...)`): the proposals take theta last,
+        `step_proposal(carry, y, theta)` and `init_proposal(y, theta)`; `params` as for BootstrapSMC."""
         if not isinstance(model, StateSpaceModel):
             raise TypeError("GuidedSMC guides a StateSpaceModel (the hand-written models have no proposal sites)")
-        super().__init__(model, observations, n_particles, record_ancestors, ess_threshold, record_history)
+        super().__init__(model, observations, n_particles, record_ancestors, ess_threshold, record_history, params)
         self.step_proposal, self.init_proposal = step_proposal, init_proposal
 
-    def _bind(self, ops):
+    def _bind(self, ops, theta=None):
         if self._plan is None:
             addrs = [a for a, _ in self.observations.leaves()]
             with use_ops(ops):
-                plan, _ = build_guided_plan(self.model, addrs, self.step_proposal, self.init_proposal)
+                plan, _ = build_guided_plan(self.model, addrs, self.step_proposal, self.init_proposal, theta)
             self._plan = (plan, observation_matrix(self.observations, addrs))
         return PlanFilter(ops, *self._plan, source=(self.model, _obs_addrs(self.observations)))
+
+
+class ParticleMH:
+    """Particle-marginal Metropolis-Hastings over the parameters of a `StateSpaceModel(..., params=...)`: `n_chains`
+    (<= 16) independent random-walk chains whose particle filters step as ONE filter bank — one `run_many` per iteration,
+    the proposal of chain c in row c — so an iteration costs the launches of a single filter run.
+
+        pmmh = ParticleMH(BootstrapSMC(model, obs, n, params=theta0), log_prior, step_scale=0.15, n_chains=8)
+        samples, log_likelihood, accepted = pmmh.run(key, theta0, n_iters)
+
+    `log_prior(theta row f32[P]) -> float` (-inf outside the support); `step_scale`: a number or a length-P sequence.
+    `run` returns `samples float64[n_iters + 1, C, P]`, `log_likelihood float64[n_iters + 1, C]` (the estimate the chain
+    holds) and `accepted bool[n_iters, C]`.  Fully specified, so a run can be replayed:
+
+      rng = np.random.default_rng([k0, k1]) (the key's two words); the filter key of iteration i (0: the initial state)
+      and chain c is fold_in(fold_in(key, i), c); per iteration z = rng.standard_normal((C, P)), then u = rng.random(C);
+      the proposal is theta + step_scale * z rounded to f32 and stored as such (the stored theta is what the filter ran);
+      accept iff log(u) < (ll' + lp') - (ll + lp).  A proposal with log_prior == -inf is rejected: its bank row runs the
+      chain's CURRENT theta and the result is discarded — no value outside the support (a negative scale) ever reaches a
+      kernel and the launch shape never changes.
+
+    `log_likelihood=` (a callable `rows f32[C, P] -> float64[C]`) replaces the bank (`smc` may then be None): the tests
+    that run without a GPU drive the sampler with an exact likelihood through it."""
+
+    def __init__(self, smc, log_prior, step_scale, n_chains: int = 8, log_likelihood=None):
+        if not 1 <= int(n_chains) <= 16:
+            raise ValueError("ParticleMH: n_chains in 1 .. 16 (the filters of one launch)")
+        if log_likelihood is None:
+            if not isinstance(smc, BootstrapSMC) or not smc._parameterised:
+                raise TypeError("ParticleMH needs a BootstrapSMC / GuidedSMC over a StateSpaceModel(..., params=...), or log_likelihood=")
+            if smc.record_history:
+                raise ValueError("ParticleMH: a record_history filter runs one filter at a time; build the filter without it")
+        self.smc, self.log_prior, self.n_chains, self.log_likelihood = smc, log_prior, int(n_chains), log_likelihood
+        self.step_scale = np.asarray(step_scale, dtype=np.float64)
+
+    def _bank(self, key: prng.PRNGKey, i: int, rows: np.ndarray) -> np.ndarray:
+        if self.log_likelihood is not None:
+            return np.asarray(self.log_likelihood(rows), dtype=np.float64).reshape(self.n_chains)
+        ki = prng.fold_in(key, i)
+        return self.smc.log_marginal_likelihoods([prng.fold_in(ki, c) for c in range(self.n_chains)], rows)
+
+    def run(self, key: prng.PRNGKey, theta0, n_iters: int):
+        C = self.n_chains
+        theta0 = np.asarray(theta0, dtype=np.float32).reshape(-1)
+        P = theta0.size
+        lp0 = float(self.log_prior(theta0))
+        if not np.isfinite(lp0):
+            raise ValueError("ParticleMH.run: log_prior(theta0) must be finite")
+        rng = np.random.default_rng([key.k0, key.k1])
+        theta = np.tile(theta0, (C, 1))  # f32[C, P]: what the filters ran
+        lp = np.full(C, lp0, dtype=np.float64)
+        ll = self._bank(key, 0, theta)
+        samples = np.empty((n_iters + 1, C, P), dtype=np.float64)
+        lls = np.empty((n_iters + 1, C), dtype=np.float64)
+        accepted = np.zeros((n_iters, C), dtype=bool)
+        samples[0], lls[0] = theta, ll
+        for i in range(1, n_iters + 1):
+            z = rng.standard_normal((C, P))
+            u = rng.random(C)
+            prop = (theta.astype(np.float64) + self.step_scale * z).astype(np.float32)
+            lp_new = np.asarray([float(self.log_prior(prop[c])) for c in range(C)], dtype=np.float64)
+            live = lp_new > -np.inf
+            ll_new = self._bank(key, i, np.where(live[:, None], prop, theta))
+            acc = live & (np.log(u) < (ll_new + lp_new) - (ll + lp))
+            theta = np.where(acc[:, None], prop, theta)
+            ll, lp = np.where(acc, ll_new, ll), np.where(acc, lp_new, lp)
+            samples[i], lls[i], accepted[i - 1] = theta, ll, acc
+        return samples, lls, accepted

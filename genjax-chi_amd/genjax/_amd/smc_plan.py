@@ -19,11 +19,20 @@ Both bodies are run once with symbolic values (the same tracer as `plan.py`): th
 observations become observed sites whose values are this step's observation constants
 (`GJX_ARG_OBS`), and the returned carry becomes the next state expressions.  `gjx_smc_plan_create`
 + `gjx_smc_run_plan` then generate and run one fused resample+propagate+weight kernel per step.
-The same restrictions as for importance plans apply (supported distributions, affine arguments)."""
+The same restrictions as for importance plans apply (supported distributions, affine arguments).
+
+A model that declares PARAMETERS, `StateSpaceModel(init, step, params=("a", "q", "r"))`, has bodies `init(theta)` and
+`step(carry, theta)` (`theta`: a tuple in declaration order) and lowers to a parameterised plan (include/gjx_smc_params.h):
+its kernels hold no value of theta, read a row of launch parameters instead, and up to 16 filters of one launch take a
+row each (`BootstrapSMC.run_many(keys, params=rows)`).  The semantics are `plan.ParamVal`'s: arithmetic among parameters
+and numbers happens on the HOST, per row, in the operands' own Python types — what the same number written as a literal
+in the body would have gone through, hence bit-equal to it — and every distinct result that reaches a site argument, an
+observed value, a carry expression or a postfix program is one SLOT of the row: slots 0 .. P-1 are theta itself, derived
+ones follow in first-use order (`ParamSpace`).  `a * x` with a traced `x` is a postfix program with a parameter leaf."""
 
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
 import torch
@@ -31,25 +40,93 @@ import torch
 from . import abi
 from .choicemap import ChoiceMap
 from .lang import GenerativeFunction, StaticGenerativeFunction
-from .plan import PlanTracer, PlanUnsupported, Sym, _IntSym, _Table
+from .plan import ParamVal, PlanTracer, PlanUnsupported, Sym, _IntSym, _Table
 from .runtime import get_ops
 
 
 @dataclass(frozen=True)
 class StateSpaceModel:
     """x_0 ~ init();  x_t ~ step(x_{t-1}).  `init` takes no arguments and returns the first carry;
-    `step` takes the carry (a scalar or a tuple of up to 4 scalars) and returns the next one."""
+    `step` takes the carry (a scalar or a tuple of up to 4 scalars) and returns the next one.
+    `params`: names of the model's scalar parameters; the bodies are then `init(theta)` and `step(carry, theta)` with
+    `theta` a tuple in this order (a GuidedSMC's proposals: `step_proposal(carry, y, theta)`, `init_proposal(y, theta)`)."""
 
     init: GenerativeFunction
     step: GenerativeFunction
+    params: tuple = ()
+
+    def __post_init__(self):
+        names = (self.params,) if isinstance(self.params, str) else tuple(self.params)
+        if len(set(names)) != len(names) or not all(isinstance(k, str) for k in names):
+            raise ValueError("StateSpaceModel(params=...): distinct parameter names")
+        if len(names) > abi.MAX_PARAMS:
+            raise ValueError(f"StateSpaceModel(params=...): at most {abi.MAX_PARAMS} parameters")
+        object.__setattr__(self, "params", names)
+
+
+class ParamSpace:
+    """The row of a parameterised plan: slots 0 .. P-1 are theta, then one slot per derived value in first-use order,
+    shared by the tracers of init, step and the proposals.  `row(theta)` evaluates every slot's derivation."""
+
+    def __init__(self, names: tuple, theta):
+        theta = [float(np.float32(v)) for v in np.asarray(theta, dtype=np.float64).reshape(-1)]
+        if len(theta) != len(names):
+            raise ValueError(f"the model declares {len(names)} parameters {names}, got {len(theta)} values")
+        self.names = names
+        self.theta = tuple(ParamVal(v, (lambda th, k=k: th[k]), name) for k, (v, name) in enumerate(zip(theta, names)))
+        self.derivs = [t.deriv for t in self.theta]
+        self.values = list(theta)
+        for k, t in enumerate(self.theta):
+            t.slot = k
+
+    def slot(self, pv: ParamVal) -> int:
+        if pv.slot is None:
+            if pv.deriv is None:
+                raise PlanUnsupported("a launch parameter that is not derived from the model's parameters")
+            if len(self.derivs) >= abi.MAX_PARAMS:
+                raise PlanUnsupported(f"too many parameter slots (theta and values derived from it: at most {abi.MAX_PARAMS})")
+            self.derivs.append(pv.deriv)
+            self.values.append(_f32_of(pv.value))
+            pv.slot = len(self.derivs) - 1
+        return pv.slot
+
+    @property
+    def n_slots(self) -> int:
+        return len(self.derivs)
+
+    def row(self, theta) -> np.ndarray:
+        """f32[n_slots] for one theta (rounded to f32 first: the stored theta is what the filter runs)."""
+        th = tuple(float(np.float32(v)) for v in np.asarray(theta, dtype=np.float64).reshape(-1))
+        if len(th) != len(self.names):
+            raise ValueError(f"the model declares {len(self.names)} parameters {self.names}, got {len(th)} values")
+        return np.asarray([_f32_of(d(th)) for d in self.derivs], dtype=np.float32)
+
+    def rows(self, thetas) -> np.ndarray:
+        th = np.asarray(thetas, dtype=np.float64)
+        th = th.reshape(1, -1) if th.ndim < 2 else th
+        return np.stack([self.row(t) for t in th])
+
+
+def _f32_of(v) -> float:
+    return float(torch.as_tensor(float(v) if not isinstance(v, torch.Tensor) else v, dtype=torch.float32))
 
 
 class _SmcTracer(PlanTracer):
     """PlanTracer whose observed sites read per-step observation constants."""
 
-    def __init__(self, obs_index: dict):
-        super().__init__(ChoiceMap.empty(), 1, use_params=False)
+    def __init__(self, obs_index: dict, space: ParamSpace | None = None):
+        super().__init__(ChoiceMap.empty(), 1, use_params=space is not None)
         self.obs_index = obs_index  # full address (the calls' addresses, then the site's) -> observation column
+        self.space = space  # a parameterised model's slots (shared by its tracers)
+
+    def param_slot(self, pv: ParamVal) -> int:
+        if self.space is None:
+            raise PlanUnsupported("a launch parameter in a model that declares none")
+        return self.space.slot(pv)
+
+    def theta_args(self) -> tuple:
+        """What the bodies of a parameterised model take after their own arguments."""
+        return () if self.space is None else (self.space.theta,)
 
     def _arg(self, v) -> abi.Arg:
         if isinstance(v, Sym) and v.src[0] == "state":
@@ -71,7 +148,11 @@ class _SmcTracer(PlanTracer):
         if isinstance(gen_fn, Distribution) and key in self.obs_index:
             # constrain with a placeholder, then point the site's observed value at the obs vector
             self.constraint = ChoiceMap.entry(0.0, *local)
-            out = super().handle_trace(addr, gen_fn, args)
+            up, self.use_params = self.use_params, False  # (the placeholder is no launch parameter)
+            try:
+                out = super().handle_trace(addr, gen_fn, args)
+            finally:
+                self.use_params = up
             k = self.obs_index[key]
             self.sites[-1].obs = abi.Arg(abi.ARG_OBS, k, 1.0, 0.0, None)
             self.constraint = ChoiceMap.empty()
@@ -98,29 +179,48 @@ def _state_args(tracer: _SmcTracer, ret, n_expected: int | None):
     return out
 
 
-def build_smc_plan(model: StateSpaceModel, obs_addrs: list[tuple]):
+def build_smc_plan(model: StateSpaceModel, obs_addrs: list[tuple], theta=None):
     """-> (SmcPlan, n_state).  obs_addrs: addresses (tuples) observed at every step, in the column
-    order of the observation matrix."""
+    order of the observation matrix.  `theta`: for a model with parameters, the values the bodies are traced at (any
+    point of the parameter space: the plan's structure does not depend on it); the plan then carries `_space`
+    (ParamSpace) and takes rows through `SmcPlan.set_params`."""
     if not isinstance(model.init, StaticGenerativeFunction) or not isinstance(model.step, StaticGenerativeFunction):
         raise TypeError("StateSpaceModel needs `@gen` functions")
     if len(obs_addrs) > abi.SMC_MAX_OBS:
         raise PlanUnsupported(f"at most {abi.SMC_MAX_OBS} observed addresses per step")
     obs_index = {a: k for k, a in enumerate(obs_addrs)}
-    ti = _SmcTracer(obs_index)
-    init_ret = ti.run(model.init.source, ())
+    space = _param_space(model, theta)
+    if space is not None:
+        get_ops().lib.require("smc_params", "gjx_smc_plan_create_params")  # (before any table is built)
+    ti = _SmcTracer(obs_index, space)
+    init_ret = ti.run(model.init.source, ti.theta_args())
     init_state = _state_args(ti, init_ret, None)
-    ts = _SmcTracer(obs_index)
+    ts = _SmcTracer(obs_index, space)
     carry = tuple(Sym(ts, ("state", k)) for k in range(len(init_state)))
-    step_ret = ts.run(model.step.source, (carry[0],) if len(carry) == 1 else (carry,))
+    step_ret = ts.run(model.step.source, ((carry[0],) if len(carry) == 1 else (carry,)) + ts.theta_args())
     next_state = _state_args(ts, step_ret, len(init_state))
     seen = {m["path"] for m in ti.meta + ts.meta}
     missing = [a for a in obs_addrs if a not in seen]
     if missing:
         raise ValueError(f"observed addresses not visited by the model: {missing}")
     plan = get_ops().smc_plan_create(ti.sites, ts.sites, init_state, next_state, len(obs_addrs),
-                                     init_scopes=[tuple(k) for k in ti.scopes], step_scopes=[tuple(k) for k in ts.scopes])
+                                     init_scopes=[tuple(k) for k in ti.scopes], step_scopes=[tuple(k) for k in ts.scopes],
+                                     n_params=space.n_slots if space is not None else 0)
     plan._keep = (ti.keep, ts.keep)  # constant tables the site tables point into
+    plan._space = space
+    plan._tables = (ti.sites, ts.sites)
+    plan._state_args = (init_state, next_state)
     return plan, len(init_state)
+
+
+def _param_space(model: StateSpaceModel, theta) -> ParamSpace | None:
+    if not model.params:
+        if theta is not None:
+            raise ValueError("params were given for a StateSpaceModel that declares none (StateSpaceModel(init, step, params=(...)))")
+        return None
+    if theta is None:
+        raise ValueError(f"the model declares the parameters {model.params}: pass their values (params=...)")
+    return ParamSpace(model.params, theta)
 
 
 class _GuidedTracer(_SmcTracer):
@@ -129,8 +229,8 @@ class _GuidedTracer(_SmcTracer):
     body is then traced into the same table: at the address of a proposed site it emits a GUIDED site that points at its
     partner, and the value the body sees from there on is the partner's value."""
 
-    def __init__(self, obs_index: dict):
-        super().__init__(obs_index)
+    def __init__(self, obs_index: dict, space=None):
+        super().__init__(obs_index, space)
         self.in_proposal = False
         self.proposed: dict = {}  # address -> table index of the proposal's site, until the model's site has taken it
 
@@ -188,7 +288,7 @@ def _show(key: tuple) -> str:
     return repr(key[0] if len(key) == 1 else key)
 
 
-def build_guided_plan(model: StateSpaceModel, obs_addrs: list[tuple], step_proposal, init_proposal=None):
+def build_guided_plan(model: StateSpaceModel, obs_addrs: list[tuple], step_proposal, init_proposal=None, theta=None):
     """-> (SmcPlan, n_state) of the guided filter: `build_smc_plan` with `step_proposal(carry, y)` (and, if given,
     `init_proposal(y)`) traced in front of the model's bodies.  `y`: this step's observation (a tuple in the order of
     `obs_addrs` when several addresses are observed).  Raises abi.GuidedUnavailable on a library without
@@ -201,6 +301,9 @@ def build_guided_plan(model: StateSpaceModel, obs_addrs: list[tuple], step_propo
     ops = get_ops()
     ops.lib.require("guided", "gjx_smc_plan_create_guided")  # (before any table is built: the oracle would misread the two site modes)
     obs_index = {a: k for k, a in enumerate(obs_addrs)}
+    space = _param_space(model, theta)  # (a parameterised model: every body and proposal takes `theta` last)
+    if space is not None:
+        ops.lib.require("smc_params", "gjx_smc_plan_create_params")
 
     def obs_arg(tr):
         ys = tuple(Sym(tr, ("obs", k)) for k in range(len(obs_addrs)))
@@ -211,25 +314,27 @@ def build_guided_plan(model: StateSpaceModel, obs_addrs: list[tuple], step_propo
             raise PlanUnsupported(f"the {what} proposal's site {_show(tr.unpaired()[0])} has no partner: "
                                   "the model has no body-level latent site at that address")
 
-    ti = _GuidedTracer(obs_index)
+    ti = _GuidedTracer(obs_index, space)
     if init_proposal is not None:
-        ti.run_proposal(init_proposal, (obs_arg(ti),))
-    init_ret = ti.run(model.init.source, ())
+        ti.run_proposal(init_proposal, (obs_arg(ti),) + ti.theta_args())
+    init_ret = ti.run(model.init.source, ti.theta_args())
     close(ti, "init")
     init_state = _state_args(ti, init_ret, None)
-    ts = _GuidedTracer(obs_index)
+    ts = _GuidedTracer(obs_index, space)
     carry = tuple(Sym(ts, ("state", k)) for k in range(len(init_state)))
     carry_arg = carry[0] if len(carry) == 1 else carry
-    ts.run_proposal(step_proposal, (carry_arg, obs_arg(ts)))
-    step_ret = ts.run(model.step.source, (carry_arg,))
+    ts.run_proposal(step_proposal, (carry_arg, obs_arg(ts)) + ts.theta_args())
+    step_ret = ts.run(model.step.source, (carry_arg,) + ts.theta_args())
     close(ts, "step")
     next_state = _state_args(ts, step_ret, len(init_state))
     seen = {m["path"] for m in ti.meta + ts.meta}
     missing = [a for a in obs_addrs if a not in seen]
     if missing:
         raise ValueError(f"observed addresses not visited by the model: {missing}")
-    plan = ops.smc_plan_create(ti.sites, ts.sites, init_state, next_state, len(obs_addrs), guided=True)
+    plan = ops.smc_plan_create(ti.sites, ts.sites, init_state, next_state, len(obs_addrs), guided=True,
+                               n_params=space.n_slots if space is not None else 0)
     plan._keep = (ti.keep, ts.keep)
+    plan._space = space
     plan._tables = (ti.sites, ts.sites)  # the lowered tables (tests and tools read the modes / references from them)
     plan._state_args = (init_state, next_state)
     return plan, len(init_state)
@@ -281,6 +386,9 @@ def build_transition_table(model: StateSpaceModel, obs_addrs: list[tuple]) -> Tr
         raise TypeError("StateSpaceModel needs `@gen` functions")
     if len(obs_addrs) > abi.SMC_MAX_OBS:
         raise PlanUnsupported(f"at most {abi.SMC_MAX_OBS} observed addresses per step")
+    if model.params:
+        raise PlanUnsupported(f"backward simulation of a model with parameters {model.params}: transition tables hold constants "
+                              "only — build the model at a fixed θ to smooth")
     obs_index = {a: k for k, a in enumerate(obs_addrs)}
     # (the carry's length is that of what `init` returns, as in build_smc_plan; the table comes from `step` alone)
     ti = _SmcTracer(obs_index)
