@@ -439,17 +439,15 @@ GJX_HD float e_min(float a, float b) { return (a != a) ? a : ((b != b) ? b : (a 
 // 1e-5 relative of the reference on a path WITHOUT resampling, so an importance plan may trade the bit-exact
 // polynomials for the hardware transcendentals (v_log_f32 / v_exp_f32 / v_sqrt_f32 / v_sin_f32 / v_cos_f32: ~1 ulp,
 // an 8-cycle issue each against 24-40 dependent fma's) wherever the result is a CONTINUOUS function of its input: the
-// Box-Muller transform of Normal sites, the transcendental terms of log-densities, and the row-anchored weight sums.
+// Box-Muller transform of Normal sites and the row-anchored weight sums.  The logs inside log-densities keep m_log (xlogy below).
 // Everything that DECIDES something (rejection tests of the gamma sampler, categorical CDFs, Bernoulli thresholds,
 // resampling weights) keeps the exact functions, so a fast plan draws the same particles as the exact plan up to
-// rounding.  d_log / d_exp are the density-side functions; the exact build maps them to m_log / m_exp.
+// rounding.  d_exp is the weight-side function; the exact build maps it to m_exp.
 #if defined(GJX_FAST_MATH) && defined(__HIP_DEVICE_COMPILE__)
 #define GJX_FAST_MATH_DEVICE 1
-GJX_HD float d_log(float x) { return __builtin_amdgcn_logf(x) * 0.69314718055994531f; }
 GJX_HD float d_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }
 GJX_HD float d_exp_core(float x) { return d_exp(x); }
 #else
-GJX_HD float d_log(float x) { return m_log(x); }
 GJX_HD float d_exp(float x) { return m_exp(x); }
 GJX_HD float d_exp_core(float x) { return m_exp_core(x); }
 #endif
@@ -744,7 +742,7 @@ GJX_HD float smc_slot_normal(Key step_key, uint64_t j) {  // one slot on its own
 
 // --- log-densities (TFP formulas).  The *_pre forms take the per-site constants a plan hoists.
 GJX_HD float normal_rs(float scale) { return 1.0f / scale; }
-GJX_HD float normal_lognorm(float scale) { return 0.91893853320467f + d_log(scale); }
+GJX_HD float normal_lognorm(float scale) { return 0.91893853320467f + m_log(scale); }  // (m_log in fast-math plans too: xlogy below)
 GJX_HD float logpdf_normal_pre(float x, float loc, float rs, float lognorm) {
   const float d = x * rs - loc * rs;
   return (-0.5f * d) * d - lognorm;
@@ -752,7 +750,10 @@ GJX_HD float logpdf_normal_pre(float x, float loc, float rs, float lognorm) {
 GJX_HD float logpdf_normal(float x, float loc, float scale) {
   return logpdf_normal_pre(x, loc, normal_rs(scale), normal_lognorm(scale));
 }
-GJX_HD float xlogy(float a, float y) { return a == 0.0f ? 0.0f : a * d_log(y); }
+// (m_log also in fast-math plans, for every log inside a log-density: a score is a sum whose terms cancel — a coefficient
+// shape - 1 of up to 1e4 multiplied the hardware log's last bit into 2 % of a score of 0.046 — and the hardware log flushes a
+// subnormal draw to log 0 = -inf where the density is finite.  Literal scales and shapes are hoisted on the host anyway.)
+GJX_HD float xlogy(float a, float y) { return a == 0.0f ? 0.0f : a * m_log(y); }
 GJX_HD float gamma_lognorm(float conc, float rate) { return m_lgamma(conc) - conc * m_log(rate); }
 GJX_HD float logpdf_gamma_pre(float x, float conc, float rate, float lognorm) {
   return (xlogy(conc - 1.0f, x) - rate * x) - lognorm;
@@ -767,12 +768,12 @@ GJX_HD float logpdf_beta_pre(float x, float a, float b, float lbeta) {
 GJX_HD float logpdf_beta(float x, float a, float b) {
   return logpdf_beta_pre(x, a, b, beta_lbeta(a, b));
 }
-GJX_HD float logpdf_bernoulli(bool e, float p) { return e ? d_log(p) : d_log(1.0f - p); }
+GJX_HD float logpdf_bernoulli(bool e, float p) { return e ? m_log(p) : m_log(1.0f - p); }  // (p may be a subnormal Beta draw: as xlogy)
 
 // --- Marsaglia-Tsang Gamma(conc, 1).  Attempt a of gamma `which` uses sub-stream 1 + 2a + which
 // (w0 -> normal, w1 -> uniform); the conc<1 boost uniform is word `which` of sub-stream 0.
 template <int IMPL>
-GJX_DEV float std_gamma(const Stream<IMPL>& st, int which, float conc) {
+GJX_DEV float gamma_dv(const Stream<IMPL>& st, int which, float conc) {  // d * v of the accepted attempt
   const bool boost = conc < 1.0f;
   const float a = boost ? conc + 1.0f : conc;
   const float d = a - 0.33333334f;
@@ -791,14 +792,57 @@ GJX_DEV float std_gamma(const Stream<IMPL>& st, int which, float conc) {
     rhs = rhs + d * m_log(v);
     if (m_log(u) < rhs) break;
   }
-  float g = d * v;
-  if (boost) {
-    uint32_t w0, w1;
-    st.words(0u, w0, w1);
-    const float ub = uniform01(which ? w1 : w0);
-    g = g * m_exp(m_log(ub) / conc);
-  }
+  return d * v;
+}
+template <int IMPL>
+GJX_DEV float gamma_boost_log(const Stream<IMPL>& st, int which, float conc) {  // log(u_boost) / conc, conc < 1
+  uint32_t w0, w1;
+  st.words(0u, w0, w1);
+  const float ub = uniform01(which ? w1 : w0);
+  return m_log(ub) / conc;
+}
+template <int IMPL>
+GJX_DEV float std_gamma(const Stream<IMPL>& st, int which, float conc) {
+  float g = gamma_dv<IMPL>(st, which, conc);
+  if (conc < 1.0f) g = g * m_exp(gamma_boost_log<IMPL>(st, which, conc));
   return g;
+}
+// log of the same draw, from the same sub-streams: finite (or -inf for a boost uniform of 0) where the draw itself flushes to 0
+template <int IMPL>
+GJX_DEV float std_gamma_log(const Stream<IMPL>& st, int which, float conc) {
+  float l = m_log(gamma_dv<IMPL>(st, which, conc));
+  if (conc < 1.0f) l = l + gamma_boost_log<IMPL>(st, which, conc);
+  return l;
+}
+
+// --- Beta(a, b) from its two gammas: g1 / (g1 + g2) wherever that ratio is sound: a shape >= 1 (its gamma never
+// leaves the normal range, and the other one's underflow then rounds the ratio to the 0 or 1 it is next to), or both gammas
+// normal f32 numbers.  With BOTH shapes below 1 the boost u^(1/conc) flushes gammas to 0 (42 % of them at conc = 0.01): 0 / 0 was
+// NaN (17.8 % of the draws of Beta(0.01, 0.01)), and 0 / tiny was 0 where the true ratio is an ordinary number.  There the ratio
+// is taken in log space, 1 / (1 + exp(l2 - l1)) with l = log(d v) + log(u_boost) / conc of each gamma, from the same
+// sub-streams (the attempt loops run again: the branch is rare, the common path pays the compares): in [0, 1], never NaN for
+// shapes that are normal positive f32 numbers.  Shapes outside the domain (NaN, <= 0, subnormal: 1 / conc overflows) keep the
+// ratio's own result.  The exact functions on both paths: a
+// fast-math plan draws the same value.
+template <int IMPL>
+__device__ __noinline__ float beta_from_logs(const Stream<IMPL> st, float a, float b) {  // (out of line: rare, and one copy per module)
+  float l[2];
+#pragma nounroll
+  for (int which = 0; which < 2; ++which) l[which] = std_gamma_log<IMPL>(st, which, which ? b : a);
+  const float l1 = l[0], l2 = l[1];
+  if (l1 == l2) return 0.5f;  // (also both -inf)
+  const float dl = l2 - l1;
+  if (dl > 0.0f) {
+    const float e = m_exp(-dl);
+    return e / (1.0f + e);
+  }
+  return 1.0f / (1.0f + m_exp(dl));
+}
+template <int IMPL>
+GJX_DEV float beta_from_gammas(const Stream<IMPL>& st, float a, float b, float g1, float g2) {
+  if (!(a < 1.0f && b < 1.0f) || (g1 >= 1.17549435e-38f && g2 >= 1.17549435e-38f)) return g1 / (g1 + g2);
+  if (!(a >= 1.17549435e-38f && b >= 1.17549435e-38f)) return g1 / (g1 + g2);  // NaN, <= 0, subnormal: outside the domain
+  return beta_from_logs<IMPL>(st, a, b);
 }
 
 // r04: the same draws for the P particles of a lane (the pair / quad forms of the generated kernels), scheduled for the

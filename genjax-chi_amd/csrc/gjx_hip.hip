@@ -177,7 +177,7 @@ __global__ __launch_bounds__(kBlock) void k_sample_beta(KeySrc ks, Opnd a_, Opnd
     const float a = a_.at(i), b = b_.at(i);
     const float g1 = std_gamma<IMPL>(st, 0, a);
     const float g2 = std_gamma<IMPL>(st, 1, b);
-    const float v = g1 / (g1 + g2);
+    const float v = beta_from_gammas<IMPL>(st, a, b, g1, g2);
     val[i] = v;
     if (score) score[i] = logpdf_beta(v, a, b);
   }
@@ -401,7 +401,7 @@ __global__ __launch_bounds__(kBlock) void k_importance(const CSite* __restrict__
             const Stream<IMPL> strm(pkey[r], true, fold);
             const float g1 = std_gamma<IMPL>(strm, 0, a0[r]);
             const float g2 = std_gamma<IMPL>(strm, 1, a1[r]);
-            vf[r] = g1 / (g1 + g2);
+            vf[r] = beta_from_gammas<IMPL>(strm, a0[r], a1[r], g1, g2);
           } else if ((MASK & (1 << GJX_DIST_CATEGORICAL)) && dist == GJX_DIST_CATEGORICAL) {
             if (st.cat_mode == 0) {
               const Stream<IMPL> strm(pkey[r], true, fold);
@@ -1632,7 +1632,7 @@ GJX_DEV float interp_walk(const InterpTable& T, const float* obs, Key step_key, 
           const Stream<IMPL> strm(pkey, true, fold);
           const float g1 = std_gamma<IMPL>(strm, 0, a0);
           const float g2 = std_gamma<IMPL>(strm, 1, a1);
-          vf = g1 / (g1 + g2);
+          vf = beta_from_gammas<IMPL>(strm, a0, a1, g1, g2);
           break;
         }
         default:

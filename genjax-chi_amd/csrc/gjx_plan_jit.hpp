@@ -352,6 +352,12 @@ struct SiteEmitter {
     }
   }
 
+  // A Beta site with a literal shape that is not below 1: beta_from_gammas (gjx_device.hpp) is its first line, the bare ratio; the
+  // source says so and the log-space branch is not compiled in.
+  static bool beta_plain_ratio(const CSiteT& st) {
+    return (st.a0.kind == GJX_ARG_CONST && !(st.a0.offset < 1.0f)) || (st.a1.kind == GJX_ARG_CONST && !(st.a1.offset < 1.0f));
+  }
+
   // Part 2 of site q: the sampled value (Normal sites take their standard normal from `eps`: an expression
   // or, empty, this particle's own derivation), the log-density, the accumulators and the stored column.
   bool presampled = false;  // tail(): a Gamma / Beta site's value vf<q> has been defined by the caller
@@ -385,7 +391,10 @@ struct SiteEmitter {
           o << ind << "const Stream<" << I << "> strm" << Q << "(" << K << ", true, " << fold << "u);\n";
           o << ind << "const float g1_" << Q << " = std_gamma<" << I << ">(strm" << Q << ", 0, a0_" << Q << ");\n";
           o << ind << "const float g2_" << Q << " = std_gamma<" << I << ">(strm" << Q << ", 1, a1_" << Q << ");\n";
-          o << ind << "const float vf" << Q << " = g1_" << Q << " / (g1_" << Q << " + g2_" << Q << ");\n";
+          if (beta_plain_ratio(st))
+            o << ind << "const float vf" << Q << " = g1_" << Q << " / (g1_" << Q << " + g2_" << Q << ");\n";
+          else
+            o << ind << "const float vf" << Q << " = beta_from_gammas<" << I << ">(strm" << Q << ", a0_" << Q << ", a1_" << Q << ", g1_" << Q << ", g2_" << Q << ");\n";
           break;
         default:
           if (st.cat_mode == 0) {
@@ -492,7 +501,7 @@ struct SiteEmitter {
 // bm_lds: the kernels of this source stage the Box-Muller tables in LDS (each calls bm_stage() at entry; gjx_device.hpp)
 inline void emit_prelude(std::ostringstream& o, bool fast_math = false, bool bm_lds = false) {
   if (bm_lds) o << "#define GJX_BM_LDS 1\n";
-  if (fast_math) o << "#define GJX_FAST_MATH 1\n";  // gjx.h GJX_PLAN_FAST_MATH: hardware transcendentals (gjx_device.hpp d_log / d_exp / bm_pair)
+  if (fast_math) o << "#define GJX_FAST_MATH 1\n";  // gjx.h GJX_PLAN_FAST_MATH: hardware transcendentals (gjx_device.hpp d_exp / bm_pair)
   o << "#include \"gjx_device.hpp\"\nusing namespace gjx;\n";
   o << "__device__ __forceinline__ float jrow_max(const float* l, uint32_t K){ float m=l[0]; for(uint32_t c=1;c<K;++c) m = l[c]>m?l[c]:m; return m; }\n";
   o << "__device__ __forceinline__ float jrow_lse(const float* l, uint32_t K){ const float m=jrow_max(l,K); float acc=0.0f; for(uint32_t c=0;c<K;++c) acc = acc + m_exp(l[c]-m); return m + m_log(acc); }\n";
@@ -582,8 +591,11 @@ int cur_pair_blk = -1;
       for (int u = 0; u < P; ++u) {
         if (st.dist == GJX_DIST_GAMMA)
           o << ind << "const float vf" << Q << sfx[u] << " = vg0_" << Q << "[" << u << "] / a1_" << Q << sfx[u] << ";\n";
-        else
+        else if (em[0].beta_plain_ratio(st))
           o << ind << "const float vf" << Q << sfx[u] << " = vg0_" << Q << "[" << u << "] / (vg0_" << Q << "[" << u << "] + vg1_" << Q << "[" << u << "]);\n";
+        else
+          o << ind << "const float vf" << Q << sfx[u] << " = beta_from_gammas<" << I << ">(Stream<" << I << ">(" << em[u].key_of(q) << ", true, " << fold
+            << "u), a0_" << Q << sfx[u] << ", a1_" << Q << sfx[u] << ", vg0_" << Q << "[" << u << "], vg1_" << Q << "[" << u << "]);\n";
         em[u].presampled = true;
         em[u].tail(q);
         em[u].presampled = false;

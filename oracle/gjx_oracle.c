@@ -209,7 +209,7 @@ int gjx_sample_logpdf_beta(const gjx_keys* k, gjx_f32 a_, gjx_f32 b_, float* val
     float a = OPND(a_, i), b = OPND(b_, i);
     float g1 = o_std_gamma(&st, 0, a);
     float g2 = o_std_gamma(&st, 1, b);
-    float v = g1 / (g1 + g2);
+    float v = o_beta_from_gammas(&st, a, b, g1, g2);
     value_out[i] = v;
     if (score_out) score_out[i] = o_logpdf_beta(v, a, b);
   }
@@ -617,7 +617,7 @@ static void site_walk(const gjx_site* sites, int n_sites, const walk_ctx* c, sit
                     : c->pair_normals ? o_site_normal(&strm) : o_std_normal(bits0);
           float t = a1 * eps; v.f = a0 + t; break; }
         case GJX_DIST_GAMMA: v.f = o_std_gamma(&strm, 0, a0) / a1; break;
-        case GJX_DIST_BETA: { float g1 = o_std_gamma(&strm, 0, a0), g2 = o_std_gamma(&strm, 1, a1); v.f = g1 / (g1 + g2); break; }
+        case GJX_DIST_BETA: { float g1 = o_std_gamma(&strm, 0, a0), g2 = o_std_gamma(&strm, 1, a1); v.f = o_beta_from_gammas(&strm, a0, a1, g1, g2); break; }
         case GJX_DIST_BERNOULLI: v.i = o_uniform01(bits0) < a0; break;
         default: v.i = st->cat_mode == 0 ? cat_gumbel(row, (uint32_t)st->n_cat, &strm)
                                          : cat_invcdf(row, (uint32_t)st->n_cat, bits0);

@@ -503,7 +503,7 @@ static inline float o_logpdf_bernoulli(int e, float p) {
 /* Marsaglia & Tsang (2000) Gamma(conc, 1) on sub-streams of `key`: attempt a of gamma `which`
  * (0/1; Beta draws two) uses words(sub = 1 + 2a + which): w0 -> normal, w1 -> uniform.  The
  * conc < 1 boost uniform is word `which` of sub 0.  At most 64 attempts (then accept). */
-static inline float o_std_gamma(const o_stream* st, int which, float conc) {
+static inline float o_gamma_dv(const o_stream* st, int which, float conc) { /* d * v of the accepted attempt */
   int boost = conc < 1.0f;
   float a = boost ? conc + 1.0f : conc;
   float d = a - 0.33333334f;
@@ -522,14 +522,43 @@ static inline float o_std_gamma(const o_stream* st, int which, float conc) {
     rhs = rhs + d * o_log(v);
     if (o_log(u) < rhs) break;
   }
-  float g = d * v;
-  if (boost) {
-    uint32_t w0, w1;
-    o_words(st, 0u, &w0, &w1);
-    float ub = o_uniform01(which ? w1 : w0);
-    g = g * o_exp(o_log(ub) / conc);
-  }
+  return d * v;
+}
+static inline float o_gamma_boost_log(const o_stream* st, int which, float conc) { /* log(u_boost) / conc, conc < 1 */
+  uint32_t w0, w1;
+  o_words(st, 0u, &w0, &w1);
+  float ub = o_uniform01(which ? w1 : w0);
+  return o_log(ub) / conc;
+}
+static inline float o_std_gamma(const o_stream* st, int which, float conc) {
+  float g = o_gamma_dv(st, which, conc);
+  if (conc < 1.0f) g = g * o_exp(o_gamma_boost_log(st, which, conc));
   return g;
+}
+/* log of the same draw, from the same sub-streams: finite (or -inf for a boost uniform of 0) where the draw itself flushes to 0 */
+static inline float o_std_gamma_log(const o_stream* st, int which, float conc) {
+  float l = o_log(o_gamma_dv(st, which, conc));
+  if (conc < 1.0f) l = l + o_gamma_boost_log(st, which, conc);
+  return l;
+}
+
+/* Beta(a, b) from its two gammas: g1 / (g1 + g2) wherever that ratio is sound: a shape >= 1 (its gamma never
+ * leaves the normal range, and the other one's underflow then rounds the ratio to the 0 or 1 it is next to), or both gammas
+ * normal f32 numbers.  With BOTH shapes below 1 the boost u^(1/conc) flushes gammas to 0 (42 % of them at conc = 0.01): 0 / 0 was
+ * NaN (17.8 % of the draws of Beta(0.01, 0.01)), and 0 / tiny was 0 where the true ratio is an ordinary number.  There the ratio
+ * is taken in log space, 1 / (1 + exp(l2 - l1)) with l = log(d v) + log(u_boost) / conc of each gamma, from the same
+ * sub-streams: in [0, 1], never NaN for shapes that are normal positive f32 numbers.  Shapes outside the domain (NaN, <= 0, subnormal: 1 / conc overflows) keep the ratio's own result. */
+static inline float o_beta_from_gammas(const o_stream* st, float a, float b, float g1, float g2) {
+  if (!(a < 1.0f && b < 1.0f) || (g1 >= 1.17549435e-38f && g2 >= 1.17549435e-38f)) return g1 / (g1 + g2);
+  if (!(a >= 1.17549435e-38f && b >= 1.17549435e-38f)) return g1 / (g1 + g2); /* NaN, <= 0, subnormal: outside the domain */
+  float l1 = o_std_gamma_log(st, 0, a), l2 = o_std_gamma_log(st, 1, b);
+  if (l1 == l2) return 0.5f; /* (also both -inf) */
+  float dl = l2 - l1;
+  if (dl > 0.0f) {
+    float e = o_exp(-dl);
+    return e / (1.0f + e);
+  }
+  return 1.0f / (1.0f + o_exp(dl));
 }
 
 /* ---------------- fixed-point weights ------------------------------------ */

@@ -6,6 +6,8 @@ SURVEY F6, and its tests hold no random golden vectors):
   rng_kat.json        Random123 known-answer vectors for Threefry2x32-20 / Philox4x32-10
                       (Salmon et al. SC'11 distribution, kat_vectors) — literals below.
   logpdf_scipy.json   scipy.stats float64 log-densities on a fixed grid.
+  logpdf_wide.json    the same over the whole parameter range (tests/dist_range_ref.py: shapes 0.01 .. 1e4, the
+                      quantiles 1e-6 .. 1 - 1e-6 rounded to f32, the support's edges, the smallest f32 numbers).
   reference_kat.json  closed-form answers the reference's own tests assert
                       (tests/inference/test_smc.py:32-87, tests/generative_functions/
                       test_static_gen_fn.py:317-318, README.md:121-123 analytic means).
@@ -62,6 +64,11 @@ dump("logpdf_scipy.json", {
     "bernoulli": [{"x": e, "p": p, "logpdf": float(math.log(p if e else 1 - p))} for e in (0, 1) for p in (0.1, 0.5, 0.7)],
     "categorical": [{"logits": [-0.3, -0.5], "logpdf": [-0.59813887, -0.79813887]}],
 })
+
+sys.path.insert(0, os.path.dirname(HERE))
+import dist_range_ref  # noqa: E402
+
+dump("logpdf_wide.json", dist_range_ref.density_cases())
 
 dump("reference_kat.json", {
     "flip_flip_trivial_logZ": math.log(0.7),
