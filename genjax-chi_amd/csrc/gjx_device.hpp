@@ -1551,6 +1551,15 @@ struct PlanPolicyArgs {
   float obs[8];
   int32_t wt;  // write-through stores of the state / ancestor columns (store16_out; the host sets it for one-filter launches)
 };
+// The retained path of a conditional step (include/gjx_csmc.h), an argument of the conditional kernels only: slot `slot`
+// (= n - 1) takes path[k][t] as the value of the sampled site that is carry component k.  Only the lane that owns the slot
+// reads the path.
+struct CsmcRet {
+  const float* path[4];
+  int64_t slot;
+  int32_t t;
+  int32_t pad;
+};
 
 // Kernel argument block of one backward-simulation step (include/gjx_backsim.h; the kernels are generated from the
 // transition table, gjx_plan_jit.hpp GenBacksim).  Rows are those of step t; `best` holds one packed running maximum per
@@ -1882,7 +1891,10 @@ GJX_DEV void wave_lds_fence() {
 // LDSP: the merged prefix of the source tiles lives in LDS (the LDS, wave and grouped routes: A.prefix == nullptr) — a
 // compile-time fact inside the body, so that every read of it is an LDS read (as a run-time choice between LDS and the prefix
 // array in memory the reads were flat loads through a selected pointer).
-template <int IMPL, class Policy, bool ADAPTIVE, bool PEERS, bool LDSP>
+// COND (include/gjx_csmc.h: the conditional step): the launch serves n_out + 1 slots — the comb's n_out teeth
+// and slot n_out, which keeps source particle n_out (= n - 1, the retained particle) whatever the weights are.  The comb sees
+// the slots below n_out only; a workgroup whose tile starts at n_out holds nothing but the retained slot and searches nothing.
+template <int IMPL, class Policy, bool ADAPTIVE, bool PEERS, bool LDSP, bool COND = false>
 GJX_DEV void resample_body_impl(const ResampleArgs& A, Policy& P) {
   constexpr int kW = kBlock / kWave;
   constexpr int kSrc = 8;                        // sources per lane and round of the window scan
@@ -1974,6 +1986,7 @@ GJX_DEV void resample_body_impl(const ResampleArgs& A, Policy& P) {
   const int64_t j1 = j0 + (int64_t)kTile < A.out_hi ? j0 + (int64_t)kTile : A.out_hi;
   const int64_t jq = j0 + (int64_t)kPer * tid;
   const int32_t n_out = (int32_t)A.n_out;
+  const int64_t j1c = COND && j1 > (int64_t)n_out ? (int64_t)n_out : j1;  // the end of the workgroup's COMB slots (j1 unless COND)
 
   // ---- the source records (issued first; the policy's ancestor-independent work runs under their latency) --------
   // Three routes to the merged prefix of the source tiles' masses (launch-uniform):
@@ -2235,6 +2248,11 @@ GJX_DEV void resample_body_impl(const ResampleArgs& A, Policy& P) {
       anc[r] = (uint32_t)(g < A.n ? g : A.n - 1);
     }
     __syncthreads();
+  } else if (COND && j0 >= (int64_t)n_out) {
+    // ---- a tile that holds only the retained slot: no tooth of the comb falls here (workgroup-uniform) ----------------
+#pragma unroll
+    for (int r = 0; r < kPer; ++r) anc[r] = (uint32_t)n_out;
+    __syncthreads();
   } else {
     const double scale = (double)A.n_out / (double)tot;
     auto nlo_of = [&](uint64_t k) -> int32_t { return comb_tile(pre_at(k), scale, u0, n_out); };  // teeth below the START of tile k
@@ -2356,19 +2374,19 @@ GJX_DEV void resample_body_impl(const ResampleArgs& A, Policy& P) {
         double c = (double)c_start;
         int32_t start = comb_in_tile(c, scale_t, tb, nhi, n_out);  // (the tile's start for its first source: c == 0)
         n_end = i0 + kSrc >= tend ? nhi : comb_in_tile((double)(c_start + own), scale_t, tb, nhi, n_out);
-        if (n_end > start && n_end > j0 && start < j1) {  // the lane's sources own a tooth of this tile's slots
+        if (n_end > start && n_end > j0 && start < j1c) {  // the lane's sources own a tooth of this tile's slots
           const uint32_t id_base = (uint32_t)(i0 - i_base) + 1u;
 #pragma unroll
           for (int r = 0; r < kSrc; ++r) {
             c += (double)q[r];
             const int32_t nr = r == kSrc - 1 ? n_end : (i0 + r + 1 >= tend ? nhi : comb_in_tile(c, scale_t, tb, nhi, n_out));
-            if (nr > start && nr > j0 && start < j1) marks[(start > j0 ? start : (int32_t)j0) - (int32_t)j0] = id_base + (uint32_t)r;
+            if (nr > start && nr > j0 && start < j1c) marks[(start > j0 ? start : (int32_t)j0) - (int32_t)j0] = id_base + (uint32_t)r;
             start = nr;
           }
         }
       }
       // the window reaches the end of the workgroup's slots?  (two flags by round parity: a wave may be one barrier ahead)
-      if (tid == kScanLanes - 1) sh_cov[rounds & 1] = n_end >= j1 ? 1u : 0u;
+      if (tid == kScanLanes - 1) sh_cov[rounds & 1] = n_end >= j1c ? 1u : 0u;
       __syncthreads();
       covered = sh_cov[rounds & 1] != 0;
     }
@@ -2396,6 +2414,10 @@ GJX_DEV void resample_body_impl(const ResampleArgs& A, Policy& P) {
 #pragma unroll 1
       for (int r = 0; r < kPer; ++r) {
         const int64_t j = jq + r;
+        if (COND && j >= (int64_t)n_out) {  // (the retained slot and the lanes beyond it: no tooth to search for)
+          anc[r] = (uint32_t)n_out;
+          continue;
+        }
         uint64_t k, pk;   // the slot's source tile, the mass before it
         int dk;           // ... its shift
         int32_t nhi;      // ... teeth below its end
@@ -2464,6 +2486,10 @@ GJX_DEV void resample_body_impl(const ResampleArgs& A, Policy& P) {
     }
   }
 
+  if (COND) {  // the retained slot keeps the retained particle — after a resampling and on the zero-mass path alike
+#pragma unroll
+    for (int r = 0; r < kPer; ++r) anc[r] = jq + r == (int64_t)n_out ? (uint32_t)n_out : anc[r];
+  }
   GJX_DBG_STOP(A, 4, if (anc[0] == 0xffffffffu) marks[0] = anc[1] + anc[2] + anc[3]);
   typename Policy::Out out[kPer];
   float w[kPer];
@@ -2493,7 +2519,7 @@ GJX_DEV void resample_args_anchor(const ResampleArgs& A) {
                "s"(A.resampled_out));
 #endif
 }
-template <int IMPL, class Policy, bool ADAPTIVE = true, bool PEERS = false>
+template <int IMPL, class Policy, bool ADAPTIVE = true, bool PEERS = false, bool COND = false>
 GJX_DEV void resample_body(const ResampleArgs& A, Policy& P) {
 #ifndef GJX_NO_ARGS_ANCHOR   // (A/B builds: profiles/r04_ab/README.md; anchoring the policy's members as well measured even)
   resample_args_anchor(A);
@@ -2503,8 +2529,8 @@ GJX_DEV void resample_body(const ResampleArgs& A, Policy& P) {
     asm volatile("" ::"s"(A.lw), "s"(A.ess), "s"(A.ess_out));
 #endif
   }
-  if (A.prefix == nullptr) resample_body_impl<IMPL, Policy, ADAPTIVE, PEERS, true>(A, P);  // (launch-uniform)
-  else resample_body_impl<IMPL, Policy, ADAPTIVE, PEERS, false>(A, P);
+  if (A.prefix == nullptr) resample_body_impl<IMPL, Policy, ADAPTIVE, PEERS, true, COND>(A, P);  // (launch-uniform)
+  else resample_body_impl<IMPL, Policy, ADAPTIVE, PEERS, false, COND>(A, P);
 }
 
 }  // namespace gjx

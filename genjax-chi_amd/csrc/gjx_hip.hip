@@ -12,6 +12,7 @@
 #include "../../include/gjx_backsim.h"
 #include "../../include/gjx_backmove.h"
 #include "../../include/gjx_smc_params.h"
+#include "../../include/gjx_csmc.h"
 #include "gjx_device.hpp"
 
 #include <hip/hip_runtime.h>
@@ -3410,6 +3411,7 @@ struct gjx_smc_plan {
   CArg init_state[GJX_SMC_MAX_STATE], next_state[GJX_SMC_MAX_STATE];
   gjx_jit::CompiledSmc jit[2];
   gjx_jit::CompiledSmc jit_peers[2];  // r04: the step kernels of the peer transport (compiled on first use)
+  gjx_jit::CompiledSmc jit_cond[2];   // include/gjx_csmc.h: the conditional kernels (step, init), compiled on first use
   std::vector<void*> dev_owned;  // per-row tables of categorical sites
   std::mutex mu;
   ExprStore init_expr, step_expr;  // GJX_ARG_EXPR programs of the two tables
@@ -3621,6 +3623,7 @@ int gjx_smc_plan_destroy(gjx_smc_plan* p) {
   smc_plan_free_rows(p);
   for (auto& c : p->jit) c.release();  // compiled modules are owned by the process-wide (bounded) cache
   for (auto& c : p->jit_peers) c.release();
+  for (auto& c : p->jit_cond) c.release();
   free_owned(p->dev_owned);
   if (p->dev_init) (void)hipFree(p->dev_init);
   if (p->dev_step) (void)hipFree(p->dev_step);
@@ -3649,10 +3652,15 @@ int gjx_jit_routes(uint64_t* child_compiles, uint64_t* inproc_compiles, uint64_t
   return GJX_OK;
 }
 
-static std::string smc_plan_source(const gjx_smc_plan* plan, int impl, PlanTables* tabs = nullptr, bool peers = false) {
+static std::string smc_plan_source(const gjx_smc_plan* plan, int impl, PlanTables* tabs = nullptr, bool peers = false, bool cond = false) {
   gjx_jit::TableScope ts;
   gjx_jit::GenSmc<CSite, CArg> g;
   g.peers = peers;
+  if (cond) {  // (include/gjx_csmc.h; the caller has checked the plan: csmc_plan_status)
+    g.cond = true;
+    (void)g.csmc_components(plan->init, plan->n_init, plan->init_state, plan->n_state, g.ret_init);
+    (void)g.csmc_components(plan->step, plan->n_step, plan->next_state, plan->n_state, g.ret_step);
+  }
   g.impl = impl; g.init_sites = plan->init; g.n_init = plan->n_init; g.step_sites = plan->step;
   g.n_step = plan->n_step; g.init_state = plan->init_state; g.next_state = plan->next_state; g.n_state = plan->n_state;
   g.sc_init = plan->init_scopes.n_scopes > 0 ? &plan->init_scopes : nullptr;
@@ -3713,7 +3721,10 @@ static int smc_plan_route(gjx_smc_plan* plan, int impl, gjx_jit::CompiledSmc** c
 }
 static int smc_plan_step(const gjx_smc_config* cfg, gjx_smc_plan* plan, gjx_jit::CompiledSmc* cp, int t,
                          const float* obs_t, const gjx_smc_pop* prev, const gjx_smc_pop* out, int32_t* prev_e_out,
-                         uint64_t* prev_q_out, int32_t* ancestors_out, gjx_stream s, const StepCtx& ctx) {
+                         uint64_t* prev_q_out, int32_t* ancestors_out, gjx_stream s, const StepCtx& ctx,
+                         const CsmcRet* ret = nullptr) {
+  // `ret` (include/gjx_csmc.h): `cp` holds the plan's CONDITIONAL kernels — they take *ret as their last argument and the
+  // comb has n - 1 teeth (the launch still serves all n slots)
   const bool ad = cfg_adaptive(cfg);
   const uint64_t nt = ntiles_of(cfg->n_total);
   if (!pop_ok(out, plan->n_state, ad, false, nt) ||
@@ -3748,7 +3759,9 @@ static int smc_plan_step(const gjx_smc_config* cfg, gjx_smc_plan* plan, gjx_jit:
     }
     PlanTables tabs = cp->tabs;
     const float* prm_rows = plan->dev_rows;  // (the generated kernels of a parameterised plan take it as their last argument)
-    void* args[] = {&PA, &first, &nl, &em, &fb, &tabs, &prm_rows};
+    CsmcRet R = ret ? *ret : CsmcRet{};
+    void* args[] = {&PA, &first, &nl, &em, &fb, &tabs, &prm_rows, &R};
+    if (ret && plan->n_params == 0) args[6] = &R;  // (... the conditional kernels the path, behind it)
     if (hipModuleLaunchKernel(cp->init, ntl * nf, 1, 1, kBlock, 1, 1, 0, S(s), args, nullptr) != hipSuccess) return GJX_ERR_LAUNCH;
     return launch_status();
   }
@@ -3756,6 +3769,7 @@ static int smc_plan_step(const gjx_smc_config* cfg, gjx_smc_plan* plan, gjx_jit:
   int rc = smc_resample_args(cfg, t, prev, out, prev_e_out, prev_q_out, ctx, s, &A);
   if (rc) return rc;
   PA.wt = A.wt_stores;
+  if (ret) A.n_out = cfg->n_total - 1;  // the comb's teeth: slots 0 .. n - 2 (out_hi stays n: the retained slot is served too)
   if (!cp) {
     if (cfg->impl == 0) k_smc_interp_step<0><<<ntl * nf, kBlock, 0, S(s)>>>(A, PA, IT);
     else k_smc_interp_step<1><<<ntl * nf, kBlock, 0, S(s)>>>(A, PA, IT);
@@ -3763,7 +3777,9 @@ static int smc_plan_step(const gjx_smc_config* cfg, gjx_smc_plan* plan, gjx_jit:
   }
   PlanTables tabs = cp->tabs;
   const float* prm_rows = plan->dev_rows;
-  void* args[] = {&A, &PA, &tabs, &prm_rows};
+  CsmcRet R = ret ? *ret : CsmcRet{};
+  void* args[] = {&A, &PA, &tabs, &prm_rows, &R};
+  if (ret && plan->n_params == 0) args[3] = &R;
   if (hipModuleLaunchKernel(ad ? cp->step_adaptive : cp->step, ntl * nf, 1, 1, kBlock, 1, 1, 0, S(s), args, nullptr) != hipSuccess) return GJX_ERR_LAUNCH;
   return launch_status();
 }
@@ -3788,6 +3804,68 @@ int gjx_smc_plan_step(const gjx_smc_config* cfg, gjx_smc_plan* plan, int t, cons
   const int route = smc_plan_route(plan, cfg->impl, &c, cfg->peers != nullptr && t > 0);
   if (route) return route;
   return smc_plan_step(cfg, plan, c, t, obs_t, prev, out, prev_e_out, prev_q_out, ancestors_out, s, StepCtx{});
+}
+
+// ---- include/gjx_csmc.h: the conditional step ------------------------------------------------------------------------------
+int gjx_csmc_version(int* major, int* minor) { return version_out(major, minor, GJX_CSMC_VERSION_MAJOR, GJX_CSMC_VERSION_MINOR); }
+// flat bodies, and the model condition: every sampled site is exactly one carry component and the other way round
+static int csmc_plan_status(const gjx_smc_plan* p) {
+  if (p->init_scopes.n_scopes > 0 || p->step_scopes.n_scopes > 0) return GJX_ERR_UNSUPPORTED;
+  int comp[GJX_MAX_SITES];
+  if (!gjx_jit::GenSmc<CSite, CArg>::csmc_components(p->init, p->n_init, p->init_state, p->n_state, comp) ||
+      !gjx_jit::GenSmc<CSite, CArg>::csmc_components(p->step, p->n_step, p->next_state, p->n_state, comp))
+    return GJX_ERR_INVALID;
+  return GJX_OK;
+}
+int gjx_csmc_plan_source(const gjx_smc_plan* p, int impl, char* buf, size_t buf_len, size_t* needed) {
+  if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
+  const int st = csmc_plan_status(p);
+  if (st) return st;
+  return copy_source_out(smc_plan_source(p, impl, nullptr, false, true), buf, buf_len, needed);
+}
+int gjx_csmc_plan_compile_check(const gjx_smc_plan* p, int impl) {
+  if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
+  const int st = csmc_plan_status(p);
+  if (st) return st;
+  return gjx_jit::compile_only(smc_plan_source(p, impl, nullptr, false, true), gjx_jit::PlanKind::smc) ? GJX_OK : GJX_ERR_UNSUPPORTED;
+}
+int gjx_smc_plan_step_conditional(const gjx_smc_config* cfg, gjx_smc_plan* plan, int t, const float* obs_t, const gjx_smc_pop* prev,
+                                  const gjx_smc_pop* out, int32_t* prev_e_out, uint64_t* prev_q_out, int32_t* ancestors_out,
+                                  const gjx_csmc_path* retained, gjx_stream s) {
+  if (!cfg_ok(cfg) || !plan || t < 0 || t >= cfg->n_steps || !out || (t > 0 && !prev) || (plan->n_obs > 0 && !obs_t) ||
+      !retained || cfg->n_total < 2)
+    return GJX_ERR_INVALID;
+  for (int k = 0; k < plan->n_state; ++k)
+    if (!retained->path[k]) return GJX_ERR_INVALID;
+  if (cfg->n_filters > 1 || cfg_adaptive(cfg) || cfg->peers || cfg->first_slot != 0 || cfg->n_local != cfg->n_total)
+    return GJX_ERR_UNSUPPORTED;
+  const int st = csmc_plan_status(plan);
+  if (st) return st;
+  if (!gjx_jit::enabled()) return GJX_ERR_UNSUPPORTED;
+  if (plan->n_params > 0) {  // include/gjx_smc_params.h: row 0, as gjx_smc_plan_step
+    if (plan->n_rows < 1) return GJX_ERR_INVALID;
+    if (t == 0 || plan->rows_dirty || !plan->dev_rows) {
+      const int up = smc_plan_upload_rows(plan, 1, s);
+      if (up) return up;
+    }
+  }
+  // (the populations are checked before anything is compiled, as on the unconditional route)
+  const uint64_t nt = ntiles_of(cfg->n_total);
+  if (!pop_ok(out, plan->n_state, false, false, nt) || (t > 0 && (!pop_ok(prev, plan->n_state, false, true, nt) || prev->recs == out->recs)))
+    return GJX_ERR_INVALID;
+  const int impl = cfg->impl;
+  gjx_jit::CompiledSmc& c = plan->jit_cond[impl];
+  const bool ready = compiled_once(plan->mu, c, {{plan->init, plan->n_init}, {plan->step, plan->n_step}}, &plan->dev_owned, [&] {
+    return c.load(smc_plan_source(plan, impl, &c.tabs, false, true), gjx_jit::PlanKind::smc,
+                  {"gjx_smc_step_kernel_conditional", "gjx_smc_init_kernel_conditional"}, {&c.step, &c.init});
+  });
+  if (!ready) return GJX_ERR_JIT;  // (loud: a conditional step has no other route)
+  CsmcRet R;
+  memset(&R, 0, sizeof(R));
+  for (int k = 0; k < plan->n_state; ++k) R.path[k] = retained->path[k];
+  R.slot = (int64_t)cfg->n_total - 1;
+  R.t = t;
+  return smc_plan_step(cfg, plan, &c, t, obs_t, prev, out, prev_e_out, prev_q_out, ancestors_out, s, StepCtx{}, &R);
 }
 
 }  // extern "C"

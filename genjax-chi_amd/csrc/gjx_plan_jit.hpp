@@ -153,6 +153,11 @@ struct SiteEmitter {
   bool store_values = true;  // false: the caller stores (the paired kernel writes both particles at once)
   bool ext_bits = false;     // true: the caller defines bits<q><sfx> of one-word draws (SMC quads share a block)
   const ScopeInfo* sc = nullptr;  // nested calls: per-site key scope and fold (null: a flat body, the implicit numbering)
+  // include/gjx_csmc.h (the conditional kernels only): ret_comp[q] >= 0 — sampled site q is carry component ret_comp[q]; its
+  // draw is made as ever (named vd<q> / vj<q>) and its VALUE is `rsel<sfx> ? rv_<k> : the draw`: a select in front of every
+  // log-density that reads it.  null: the source of the unconditional kernels, byte for byte.
+  const int* ret_comp = nullptr;
+  bool retained(int q) const { return ret_comp && ret_comp[q] >= 0 && sampled(sites[q]); }
 
   int scope_of(int q) const { return sc ? sc->site_scope[q] : 0; }
   std::string key_of_scope(int k) const { return k == 0 ? "pkey" + sfx : "skey" + std::to_string(k) + sfx; }
@@ -368,6 +373,7 @@ struct SiteEmitter {
     const uint32_t fold = fold_of(q);
     const std::string row = "row" + Q;
     const bool isint = is_int(st);
+    const std::string VF = (retained(q) ? "vd" : "vf") + Q, VI = (retained(q) ? "vj" : "vi") + Q;  // what the draw defines
     // (presampled: the pair / quad forms draw the gammas of a lane's particles together — std_gamma_multi — and define vf<q> themselves)
     if (sampled(st) && !(presampled && (st.dist == GJX_DIST_GAMMA || st.dist == GJX_DIST_BETA))) {
       switch (st.dist) {
@@ -377,38 +383,45 @@ struct SiteEmitter {
             e = pairs_normals() ? "site_normal<1>(Stream<1>(" + K + ", true, " + std::to_string(fold) + "u))"
                                 : "std_normal(bits" + Q + ")";
           o << ind << "const float t" << Q << " = a1_" << Q << " * " << e << ";\n";
-          o << ind << "const float vf" << Q << " = a0_" << Q << " + t" << Q << ";\n";
+          o << ind << "const float " << VF << " = a0_" << Q << " + t" << Q << ";\n";
           break;
         }
         case GJX_DIST_BERNOULLI:
-          o << ind << "const int32_t vi" << Q << " = uniform01(bits" << Q << ") < a0_" << Q << " ? 1 : 0;\n";
+          o << ind << "const int32_t " << VI << " = uniform01(bits" << Q << ") < a0_" << Q << " ? 1 : 0;\n";
           break;
         case GJX_DIST_GAMMA:
           o << ind << "const Stream<" << I << "> strm" << Q << "(" << K << ", true, " << fold << "u);\n";
-          o << ind << "const float vf" << Q << " = std_gamma<" << I << ">(strm" << Q << ", 0, a0_" << Q << ") / a1_" << Q << ";\n";
+          o << ind << "const float " << VF << " = std_gamma<" << I << ">(strm" << Q << ", 0, a0_" << Q << ") / a1_" << Q << ";\n";
           break;
         case GJX_DIST_BETA:
           o << ind << "const Stream<" << I << "> strm" << Q << "(" << K << ", true, " << fold << "u);\n";
           o << ind << "const float g1_" << Q << " = std_gamma<" << I << ">(strm" << Q << ", 0, a0_" << Q << ");\n";
           o << ind << "const float g2_" << Q << " = std_gamma<" << I << ">(strm" << Q << ", 1, a1_" << Q << ");\n";
           if (beta_plain_ratio(st))
-            o << ind << "const float vf" << Q << " = g1_" << Q << " / (g1_" << Q << " + g2_" << Q << ");\n";
+            o << ind << "const float " << VF << " = g1_" << Q << " / (g1_" << Q << " + g2_" << Q << ");\n";
           else
-            o << ind << "const float vf" << Q << " = beta_from_gammas<" << I << ">(strm" << Q << ", a0_" << Q << ", a1_" << Q << ", g1_" << Q << ", g2_" << Q << ");\n";
+            o << ind << "const float " << VF << " = beta_from_gammas<" << I << ">(strm" << Q << ", a0_" << Q << ", a1_" << Q << ", g1_" << Q << ", g2_" << Q << ");\n";
           break;
         default:
           if (st.cat_mode == 0) {
             o << ind << "const Stream<" << I << "> strm" << Q << "(" << K << ", true, " << fold << "u);\n";
-            o << ind << "const int32_t vi" << Q << " = jcat_gumbel<" << I << ">(" << row << ", " << st.n_cat << "u, strm" << Q << ");\n";
+            o << ind << "const int32_t " << VI << " = jcat_gumbel<" << I << ">(" << row << ", " << st.n_cat << "u, strm" << Q << ");\n";
           } else if (st.cat_ent) {  // the row's prepared {CDF, log-probability} entries, entered at the guide of the draw's
                                     // top byte (same integers as the two-pass walk: the same category); the entry the walk
                                     // ends on carries the log-density
             o << ind << "uint32_t lpb" << Q << ";\n";
-            o << ind << "const int32_t vi" << Q << " = jcat_invcdf_gb(" << plit_as("uint4", st.cat_guide4) << " + ((size_t)rr" << Q << " << " << st.cat_gbits << "), "
+            o << ind << "const int32_t " << VI << " = jcat_invcdf_gb(" << plit_as("uint4", st.cat_guide4) << " + ((size_t)rr" << Q << " << " << st.cat_gbits << "), "
               << plit_as("uint2", st.cat_ent) << " + (size_t)rr" << Q << " * " << st.n_cat << ", " << st.n_cat << "u, bits" << Q << ", " << (32 - st.cat_gbits) << ", lpb" << Q << ");\n";
           } else {
-            o << ind << "const int32_t vi" << Q << " = jcat_invcdf(" << row << ", " << st.n_cat << "u, bits" << Q << ");\n";
+            o << ind << "const int32_t " << VI << " = jcat_invcdf(" << row << ", " << st.n_cat << "u, bits" << Q << ");\n";
           }
+      }
+      if (retained(q)) {  // (the state column's f32 value, converted as val_i32 converts one)
+        const std::string rv = "rv_" + std::to_string(ret_comp[q]);
+        // (clamped to +-2^30 first, a NaN to -2^30: the conversion is defined for every f32, and whatever is not a
+        // category of the site is outside its support — log-density -inf — as for an observed value)
+        if (isint) o << ind << "const int32_t vi" << Q << " = rsel" << sfx << " ? (int32_t)__builtin_rintf(__builtin_fminf(__builtin_fmaxf(" << rv << ", -1073741824.0f), 1073741824.0f)) : " << VI << ";\n";
+        else o << ind << "const float vf" << Q << " = rsel" << sfx << " ? " << rv << " : " << VF << ";\n";
       }
     }
     if (defer_acc) return;  // (the caller adds lp_of(q) to the accumulators itself: emit_pair_lane_sites)
@@ -454,13 +467,14 @@ struct SiteEmitter {
         break;
       case GJX_DIST_BERNOULLI: lp = "logpdf_bernoulli(" + v + " != 0, a0_" + Q + ")"; break;
       default:
-        if (st.cat_ent && sampled(st) && st.cat_mode != 0)
+        const bool lpb_drawn = st.cat_ent && sampled(st) && st.cat_mode != 0;
+        if (lpb_drawn && !retained(q))
           lp = "u2f(lpb" + Q + ")";  // a drawn category is in range
         else
-          lp = "((" + v + " < 0 || " + v + " >= " + std::to_string(st.n_cat) + ") ? -__builtin_inff() : " +
+          lp = std::string(lpb_drawn ? "(!rsel" + sfx + " ? u2f(lpb" + Q + ") : " : "") + "((" + v + " < 0 || " + v + " >= " + std::to_string(st.n_cat) + ") ? -__builtin_inff() : " +
                (st.cat_logp_t ? plit(st.cat_logp_t) + "[(size_t)" + v + " * " + std::to_string(st.n_rows) + " + rr" + Q + "]"
                 : st.cat_ent ? "u2f(" + plit_as("uint2", st.cat_ent) + "[(size_t)rr" + Q + " * " + std::to_string(st.n_cat) + " + " + v + "].y)"
-                             : row + "[" + v + "] - jrow_lse(" + row + ", " + std::to_string(st.n_cat) + "u)") + ")";
+                             : row + "[" + v + "] - jrow_lse(" + row + ", " + std::to_string(st.n_cat) + "u)") + ")" + (lpb_drawn ? ")" : "");
     }
     // an observed site whose arguments and value are ALL compile-time constants has a compile-time log-density: opaque, so
     // that no overflow of valid constants (-inf, +inf) becomes a constant log-weight either
@@ -1024,6 +1038,34 @@ struct GenSmc {
   // registers (entries no body names are never loaded).  0: the source is the plain plan's, byte for byte.
   int n_params = 0;
   int row_len() const { return n_params + 2 * (n_init + n_step); }
+  // include/gjx_csmc.h: the CONDITIONAL kernels, a source of their own (gjx_smc_step_kernel_conditional,
+  // gjx_smc_init_kernel_conditional: one more argument, CsmcRet).  The policy is GenPolicy plus one select per sampled site:
+  // the slot CsmcRet names takes the retained value as the site's value — after the draw (consumed as ever: no draw is
+  // renumbered) and in front of every log-density that reads it.  The lane that owns the slot loads the path's values; no
+  // other lane, so no other workgroup, reads them.  false: today's source, byte for byte.
+  bool cond = false;
+  int ret_init[GJX_MAX_SITES], ret_step[GJX_MAX_SITES];  // csmc_components of the two bodies
+  // The model condition: every sampled site of a body is, by itself, exactly one carry component ({GJX_ARG_SITE, s, 1, 0})
+  // and every carry component is such a site.  comp[q] = the component of site q, or -1.
+  static bool csmc_components(const CSiteT* sites, int n_sites, const CArgT* state, int n_state, int* comp) {
+    for (int q = 0; q < n_sites; ++q) comp[q] = -1;
+    for (int k = 0; k < n_state; ++k) {
+      const CArgT& a = state[k];
+      if (a.kind != GJX_ARG_SITE || a.scale != 1.0f || a.offset != 0.0f || a.ref_site < 0 || a.ref_site >= n_sites) return false;
+      if (!sampled_mode(sites[a.ref_site].observed) || comp[a.ref_site] >= 0) return false;
+      comp[a.ref_site] = k;
+    }
+    for (int q = 0; q < n_sites; ++q)
+      if (sampled_mode(sites[q].observed) && comp[q] < 0) return false;
+    return true;
+  }
+  // the retained values of a lane (`own`: does it hold the slot?) and, per slot of the lane, whether it is the slot
+  void emit_ret_values(const char* ind, const std::string& own) {
+    for (int k = 0; k < n_state; ++k) o << ind << "float rv_" << k << " = 0.0f;\n";
+    o << ind << "if (" << own << ") {\n";
+    for (int k = 0; k < n_state; ++k) o << ind << "  rv_" << k << " = ret.path[" << k << "][ret.t];\n";
+    o << ind << "}\n";
+  }
   void emit_prm_struct(const char* name, int n_sites, int d_off) {
     o << "struct " << name << " {\n  float p[" << n_params << "], d[" << 2 * n_sites << "];\n";
     o << "  __device__ __forceinline__ void load(const float* __restrict__ rows, uint32_t f) {\n";
@@ -1076,6 +1118,13 @@ struct GenSmc {
       em.back().sc = sc;
     }
     o << "    const uint64_t g = (uint64_t)jq >> 2;\n";
+    if (cond) {  // (the retained slot may be any word of its quad)
+      for (int u = 0; u < 4; ++u) {
+        em[u].ret_comp = step ? ret_step : ret_init;
+        o << "    const bool rsel" << sf[u] << " = jq + " << u << " == ret.slot;\n";
+      }
+      emit_ret_values("    ", "(uint64_t)(ret.slot - jq) < 4u");
+    }
     for (int u = 0; u < 4; ++u) {
       if (step)
         for (int k = 0; k < n_state; ++k) o << "    const float st_" << k << sf[u] << " = src_load<kPeers>(a.prev_state[" << k << "], src[" << u << "], pd, tpr);\n";
@@ -1131,10 +1180,13 @@ struct GenSmc {
     SiteEmitter<CSiteT, CArgT> ei{o, impl, 1, init_sites, n_init, "        "};
     es.sc = sc_step;
     ei.sc = sc_init;
+    if (cond) { es.ret_comp = ret_step; ei.ret_comp = ret_init; }
+    const std::string RET_ARG = cond ? ", CsmcRet ret" : "";
     // ---- step policy
     if (n_params > 0) emit_prm_struct("GenStepPrm", n_step, n_params + 2 * n_init);
     o << "struct GenPolicy {\n  static constexpr bool kEmit = true;\n  static constexpr bool kPeers = " << (peers ? "true" : "false") << ";\n  PlanPolicyArgs a;\n  PlanTables tabs;\n";
     o << "  const int64_t* pd = nullptr;\n  uint32_t tpr = 1;\n";
+    if (cond) o << "  CsmcRet ret;\n";
     o << "  __device__ __forceinline__ void set_peers(const int64_t* d, uint32_t t) { pd = d; tpr = t; }\n";
     o << "  struct Out { float s[" << D << "]; };\n";
     if (n_params > 0) {
@@ -1148,6 +1200,10 @@ struct GenSmc {
     for (int k = 0; k < n_state; ++k) o << "    const float st_" << k << " = src_load<kPeers>(a.prev_state[" << k << "], src_global, pd, tpr);\n";
     if (es.needs_pk() || sc_step) o << "    const Key pkey = slot_key<" << I << ">(a.step_key, (uint64_t)j);\n";
     o << "    float w = 0.0f, sc = 0.0f;\n";
+    if (cond) {
+      o << "    const bool rsel = j == ret.slot;\n";
+      emit_ret_values("    ", "rsel");
+    }
     es.run();
     for (int k = 0; k < n_state; ++k) o << "    out.s[" << k << "] = " << es.arg(next_state[k]) << ";\n";
     o << "    (void)sc;\n    return w;\n  }\n";
@@ -1167,20 +1223,25 @@ struct GenSmc {
     o << "    for (int u = 0; u < 4; ++u) if (ok[u]) store(jq + u, out_lo, anc[u], o[u]);\n  }\n};\n";
     // two instantiations, as for the hand-written filters: the every-step form carries no ESS decision / keep-your-particle path
     const std::string PRM_ARG = n_params > 0 ? ", const float* __restrict__ prm_rows" : "", PRM_SET = n_params > 0 ? "  P.prm_rows = prm_rows;\n" : "";
+    if (cond) {  // (every-step, one device: no adaptive and no peer form)
+      o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_smc_step_kernel_conditional(ResampleArgs A, PlanPolicyArgs PA, PlanTables T" << PRM_ARG << RET_ARG << ") {\n";
+      o << "  GenPolicy P;\n  P.a = PA;\n  P.tabs = T;\n  P.ret = ret;\n" << PRM_SET << "  resample_body<" << I << ", GenPolicy, false, false, true>(A, P);\n}\n";
+    } else {
     o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_smc_step_kernel(ResampleArgs A, PlanPolicyArgs PA, PlanTables T" << PRM_ARG << ") {\n";
     o << "  GenPolicy P;\n  P.a = PA;\n  P.tabs = T;\n" << PRM_SET << "  resample_body<" << I << ", GenPolicy, false, GenPolicy::kPeers>(A, P);\n}\n";
     o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_smc_step_kernel_adaptive(ResampleArgs A, PlanPolicyArgs PA, PlanTables T" << PRM_ARG << ") {\n";
     o << "  GenPolicy P;\n  P.a = PA;\n  P.tabs = T;\n" << PRM_SET << "  resample_body<" << I << ", GenPolicy, true, GenPolicy::kPeers>(A, P);\n}\n";
+    }
     // ---- init kernel: one workgroup per LOCAL tile, like k_lgssm_init
     if (n_params > 0) emit_prm_struct("GenInitPrm", n_init, n_params);
     if (impl == 1) {
       o << "struct GenInitOut { float s[" << D << "]; };\n";
       o << "__device__ __forceinline__ void init_quad(const PlanPolicyArgs& a, const PlanTables& tabs, " << (n_params > 0 ? "const GenInitPrm& prm, " : "")
-        << "int64_t jq, GenInitOut (&out)[4], float (&wq)[4]) {\n";
+        << "int64_t jq, GenInitOut (&out)[4], float (&wq)[4]" << (cond ? ", const CsmcRet& ret" : "") << ") {\n";
       emit_quad_body(init_sites, n_init, init_state, false);
       o << "}\n";
     }
-    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_smc_init_kernel(PlanPolicyArgs a, uint64_t first_slot, uint64_t n_local, EmitOut em, FilterBatch fb, PlanTables tabs" << PRM_ARG << ") {\n";
+    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_smc_init_kernel" << (cond ? "_conditional" : "") << "(PlanPolicyArgs a, uint64_t first_slot, uint64_t n_local, EmitOut em, FilterBatch fb, PlanTables tabs" << PRM_ARG << RET_ARG << ") {\n";
     o << "  uint64_t ltile = blockIdx.x;\n";
     if (n_params > 0) o << "  uint32_t filter = 0;\n";
     o << "  if (fb.n_filters > 1) {  // several filters per launch: tile of filter f, its key, its outputs\n";
@@ -1193,7 +1254,7 @@ struct GenSmc {
     o << "  float wq[4];\n  bool okq[4];\n  for (int u = 0; u < 4; ++u) okq[u] = loc + u < n_local;\n";
     if (impl == 1) {  // four consecutive slots per lane, one cipher block per one-word draw of the quad
       o << "  {\n    const int64_t jq = (int64_t)gq;\n    GenInitOut out[4];\n";
-      o << "    init_quad(a, tabs, " << (n_params > 0 ? "prm, " : "") << "jq, out, wq);\n";
+      o << "    init_quad(a, tabs, " << (n_params > 0 ? "prm, " : "") << "jq, out, wq" << (cond ? ", ret" : "") << ");\n";
       o << "    for (int u = 0; u < 4; ++u) {\n      if (okq[u]) {\n";
       for (int k = 0; k < n_state; ++k) o << "        a.state_out[" << k << "][loc + u] = out[u].s[" << k << "];\n";
       o << "        if (a.anc_out) a.anc_out[loc + u] = (int32_t)(gq + u);\n      }\n    }\n  }\n";
@@ -1201,6 +1262,10 @@ struct GenSmc {
       o << "  for (int u = 0; u < 4; ++u) {\n    const uint64_t j = gq + u;\n    wq[u] = 0.0f;\n    {\n";
       if (ei.needs_pk() || sc_init) o << "        const Key pkey = slot_key<" << I << ">(a.step_key, j);\n";
       o << "        float w = 0.0f, sc = 0.0f;\n";
+      if (cond) {
+        o << "        const bool rsel = (int64_t)j == ret.slot;\n";
+        emit_ret_values("        ", "rsel");
+      }
       ei.run();
       for (int k = 0; k < n_state; ++k) o << "        const float ns_" << k << " = " << ei.arg(init_state[k]) << ";\n";
       o << "        (void)sc;\n        wq[u] = w;\n        if (okq[u]) {\n";

@@ -88,6 +88,10 @@ class SmcParamsUnavailable(HeaderUnavailable):
     header, why = "gjx_smc_params.h", "parameterised filters run as generated HIP kernels only"
 
 
+class CsmcUnavailable(HeaderUnavailable):
+    header, why = "gjx_csmc.h", "the conditional step runs as generated HIP kernels only"
+
+
 class Keys(C.Structure):
     _fields_ = [
         ("impl", C.c_int32),
@@ -570,6 +574,21 @@ SMC_PARAMS_PROTOTYPES = {
 SMC_PARAMS_ABI_VERSION = (0, 1)
 SMC_PARAMS_MAX_ROWS = 16  # gjx_smc_params.h: GJX_SMC_PARAMS_MAX_ROWS
 
+# include/gjx_csmc.h: a SEVENTH header, same arrangement — the conditional step (slot n - 1 retained) of a gjx_smc_plan
+class CsmcPath(C.Structure):
+    """gjx_csmc_path (include/gjx_csmc.h): one device f32[T] per state component."""
+    _fields_ = [("path", C.c_void_p * SMC_MAX_STATE)]
+
+
+CSMC_PROTOTYPES = {
+    "gjx_csmc_version": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gjx_smc_plan_step_conditional": (C.c_int, [C.POINTER(SmcConfig), _P, C.c_int, _P, C.POINTER(SmcPop), C.POINTER(SmcPop), _P, _P, _P,
+                                                C.POINTER(CsmcPath), _P]),
+    "gjx_csmc_plan_source": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gjx_csmc_plan_compile_check": (C.c_int, [_P, C.c_int]),
+}
+CSMC_ABI_VERSION = (0, 1)
+
 # The optional headers, in the order they are bound: every one is exported by libgjx_hip.so only and bound if present.
 class Header(collections.namedtuple("Header", "key header version_fn prototypes version_name unavailable")):
     @property
@@ -593,6 +612,7 @@ EXTENSION_HEADERS = {h.key: h for h in (
 PLAN_HEADERS = {h.key: h for h in (
     Header("smc_params", "gjx_smc_params.h", "gjx_smc_params_version", SMC_PARAMS_PROTOTYPES, "SMC_PARAMS_ABI_VERSION",
            SmcParamsUnavailable),
+    Header("csmc", "gjx_csmc.h", "gjx_csmc_version", CSMC_PROTOTYPES, "CSMC_ABI_VERSION", CsmcUnavailable),
 )}
 
 

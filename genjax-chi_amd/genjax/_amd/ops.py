@@ -813,6 +813,25 @@ class Ops:
                       C.byref(prev) if prev is not None else None, C.byref(out), self._p(prev_e_out), self._p(prev_q_out),
                       self._p(ancestors_out), self.stream())
 
+    def csmc_path(self, cols: list) -> abi.CsmcPath:
+        """gjx_csmc_path over `cols`: one contiguous f32[T] device tensor per state component (kept alive by the struct)."""
+        p = abi.CsmcPath()
+        for k, c in enumerate(cols):
+            p.path[k] = self._chk(c, torch.float32, name="retained").value
+        p._keep = list(cols)
+        return p
+
+    def smc_plan_step_conditional(self, cfg, plan: "SmcPlan", t: int, obs_t, prev, out, retained: abi.CsmcPath, prev_e_out=None,
+                                  prev_q_out=None, ancestors_out=None):
+        """gjx_smc_plan_step_conditional (include/gjx_csmc.h): `smc_plan_step` with slot n - 1 retained at `retained`
+        (`csmc_path`).  Raises abi.CsmcUnavailable on a library without that header."""
+        import numpy as np
+
+        oh = np.ascontiguousarray(np.asarray(obs_t, dtype=np.float32).reshape(-1)[:plan.n_obs])
+        self.lib.call("gjx_smc_plan_step_conditional", C.byref(cfg), plan.handle, t, C.c_void_p(oh.ctypes.data) if plan.n_obs else None,
+                      C.byref(prev) if prev is not None else None, C.byref(out), self._p(prev_e_out), self._p(prev_q_out),
+                      self._p(ancestors_out), C.byref(retained), self.stream())
+
     def smc_records_pack(self, cfg, world: int, unpack: bool, recs, ess, stage):
         """gjx_smc_records_pack: a rank's records + ESS sums <-> its slot of the one-message staging buffer."""
         self.lib.call("gjx_smc_records_pack", C.byref(cfg), int(world), 1 if unpack else 0, self._p(recs), self._p(ess),
@@ -935,6 +954,19 @@ class SmcPlan:
         self.ops.lib.call("gjx_smc_plan_source", self.handle, impl, None, 0, C.byref(need))
         buf = C.create_string_buffer(need.value)
         self.ops.lib.call("gjx_smc_plan_source", self.handle, impl, buf, need.value, None)
+        return buf.value.decode()
+
+    def csmc_compile_check(self, impl: int) -> int:
+        """gjx_csmc_plan_compile_check (include/gjx_csmc.h): the status, not raised."""
+        self.ops.lib.require("csmc", "gjx_csmc_plan_compile_check")
+        return self.ops.lib._gjx_csmc_plan_compile_check(self.handle, impl)
+
+    def csmc_source(self, impl: int) -> str:
+        """The HIP source of the plan's CONDITIONAL kernels (include/gjx_csmc.h: gjx_csmc_plan_source)."""
+        need = C.c_size_t()
+        self.ops.lib.call("gjx_csmc_plan_source", self.handle, impl, None, 0, C.byref(need))
+        buf = C.create_string_buffer(need.value)
+        self.ops.lib.call("gjx_csmc_plan_source", self.handle, impl, buf, need.value, None)
         return buf.value.decode()
 
     def __del__(self):

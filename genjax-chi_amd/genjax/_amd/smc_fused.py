@@ -24,7 +24,7 @@ from . import abi, prng
 from .choicemap import ChoiceMap
 from .runtime import get_ops, use_ops
 from .smc_models import HmmFilter, LgssmFilter, PlanFilter
-from .smc_plan import StateSpaceModel, build_guided_plan, build_smc_plan, observation_matrix
+from .smc_plan import StateSpaceModel, build_guided_plan, build_smc_plan, check_conditional, observation_matrix
 from .workloads import smc_key_schedule
 
 
@@ -169,9 +169,12 @@ def run_with_history(ops, model, observations, n: int, key: prng.PRNGKey, ess_th
     return _history_run(ops, _bind_model(ops, model, observations), n, key, ess_threshold)
 
 
-def _history_run(ops, model, n: int, key: prng.PRNGKey, ess_threshold: float) -> SMCResult:
-    """`run_with_history` of a bound model."""
+def _history_run(ops, model, n: int, key: prng.PRNGKey, ess_threshold: float, retained=None, log_z: bool = True) -> SMCResult:
+    """`run_with_history` of a bound model.  `retained` (an abi.CsmcPath, plan filters only): every step is the conditional
+    step (include/gjx_csmc.h) — slot n - 1 carries that path through the run.  `log_z=False`: `log_marginal_likelihood`
+    stays None — its float64 sum is formed on the host, the one host read of a run."""
     n, T = int(n), model.T
+    how = {} if retained is None else {"retained": retained}
     sk, rk = smc_key_schedule(key, T)
     cfg = ops.smc_config(key.impl, n, 0, n, sk, rk, ess_threshold)
     stride = ops.num_tiles(n) * ops.tile
@@ -190,13 +193,13 @@ def _history_run(ops, model, n: int, key: prng.PRNGKey, ess_threshold: float) ->
         structs.append(p)
     # (views made once, outside the loop of launches: the loop is host-bound)
     anc_rows, e_rows, q_rows = anc.unbind(0), out_e.split(1), out_q.split(1)
-    model.step(cfg, 0, None, structs[0], None, None, anc_rows[0])
+    model.step(cfg, 0, None, structs[0], None, None, anc_rows[0], **how)
     for t in range(1, T):
-        model.step(cfg, t, structs[t - 1], structs[t], e_rows[t - 1], q_rows[t - 1], anc_rows[t])
+        model.step(cfg, t, structs[t - 1], structs[t], e_rows[t - 1], q_rows[t - 1], anc_rows[t], **how)
     ops.smc_finish(cfg, pops[(T - 1) & 1].recs, e_rows[T - 1], q_rows[T - 1])
     cols = [h[:, :n] for h in hist]
     flags = cfg._flags
-    return SMCResult(ops.log_z_from_pairs(out_e, out_q, n, flags), out_e, out_q, _columns([c[T - 1] for c in cols]),
+    return SMCResult(ops.log_z_from_pairs(out_e, out_q, n, flags) if log_z else None, out_e, out_q, _columns([c[T - 1] for c in cols]),
                      lw[T - 1, :n], anc[:, :n], flags, _columns(cols), lw[:, :n])
 
 
@@ -273,13 +276,59 @@ class BootstrapSMC:
         if thetas is not None:
             model.plan.set_params(model.plan._space.rows(thetas))
 
-    def run(self, key: prng.PRNGKey, params=None) -> SMCResult:
+    def _check_conditional(self, ops):
+        """What `run(retained=...)` asks of the filter itself, before anything is bound."""
+        if not isinstance(self.model, StateSpaceModel):
+            raise ValueError(f"run(retained=...): the conditional filter runs generated plans only — {type(self.model).__name__} is "
+                             "a fixed model: write it as a StateSpaceModel")
+        if not self.record_history:
+            raise ValueError("run(retained=...) needs the per-step states: build the filter with record_history=True")
+        if 0.0 < self.ess_threshold < 1.0:
+            raise ValueError("run(retained=...): ESS-adaptive conditional filters are out of scope (ess_threshold must be 0)")
+        if self.n < 2:
+            raise ValueError("run(retained=...): at least 2 particles (the last slot is the retained one)")
+        ops.lib.require("csmc", "gjx_smc_plan_step_conditional")
+
+    def _retained_columns(self, ops, model, retained) -> list:
+        """`retained` as the conditional step takes it: one contiguous f32[T] device tensor per carry component."""
+        check_conditional(model.plan)
+        cols = list(retained) if isinstance(retained, (tuple, list)) else [retained]
+        if len(cols) != model.plan.n_state:
+            raise ValueError(f"run(retained=...): the carry has {model.plan.n_state} component(s), got {len(cols)} path column(s)")
+        out = []
+        for k, c in enumerate(cols):
+            c = torch.as_tensor(c)
+            if c.numel() != model.T or c.dim() > 2 or (c.dim() == 2 and c.shape[0] != model.T):
+                raise ValueError(f"run(retained=...): component {k} must be a path of T = {model.T} values ([T], or a [T, 1] column "
+                                 f"of a Trajectories), got shape {tuple(c.shape)}")
+            out.append(c.to(device=ops.device(), dtype=torch.float32).reshape(-1).contiguous())
+        return out
+
+    def run(self, key: prng.PRNGKey, params=None, retained=None) -> SMCResult:
+        """`retained`: a path x*_0:T-1 — a tensor [T], or a tuple of them for a multi-component carry (a column of a
+        `Trajectories` with one path qualifies) — makes the run a CONDITIONAL particle filter: the last
+        particle, slot n - 1, carries x* at every step and is its own ancestor; slots 0 .. n - 2 are resampled by a comb of
+        n - 1 teeth over all n particles.  An ordinary `SMCResult` (`trajectories`, `backward_simulate` work on it
+        unchanged).  Needs `record_history=True`, a `StateSpaceModel` whose sampled sites are exactly its carry components
+        (`PlanUnsupported` otherwise) and `ess_threshold == 0`."""
+        return self._run(key, params, retained)
+
+    def _run(self, key: prng.PRNGKey, params=None, retained=None, log_z: bool = True) -> SMCResult:
+        """`run`; `log_z=False` (ParticleGibbs' sweeps and the timing tools, record_history filters only): the float64 sum of
+        log Z is not formed — it is the one host read of a stepwise run — and `log_marginal_likelihood` is None; `step_e` /
+        `step_q` hold the exact pairs on the device."""
         ops = get_ops()
+        if retained is not None:
+            self._check_conditional(ops)
         thetas = self._thetas(params)
         model = self._bind(ops, None if thetas is None else thetas[0])
+        if retained is not None:
+            path = ops.csmc_path(self._retained_columns(ops, model, retained))
+            self._set_rows(model, thetas)
+            return _history_run(ops, model, self.n, key, 0.0, path, log_z)
         self._set_rows(model, thetas)
         if self.record_history:
-            return _history_run(ops, model, self.n, key, self.ess_threshold)
+            return _history_run(ops, model, self.n, key, self.ess_threshold, log_z=log_z)
         sk, rk = smc_key_schedule(key, model.T)
         return _result(ops, self.n, ops._smc_run(model, key.impl, self.n, sk, rk, self.record_ancestors, self.ess_threshold))
 
@@ -339,12 +388,14 @@ class BootstrapSMC:
         unique = 1 + (srt[:, 1:] != srt[:, :-1]).sum(1)
         return Trajectories(_columns(paths), lin, unique.to(torch.int64), None, None, sums, sumsq, is_f32)
 
-    def run_many(self, keys, params=None) -> list:
+    def run_many(self, keys, params=None, retained=None) -> list:
         """`vmap(self.run)(keys)`: one independent filter per key.  Up to 16 filters step in the same kernel launches
         (`gjx_smc_config.n_filters`: a 1e6-particle step alone is under one round of an MI355X), for the hand-written
         models and for generated ones alike; element b equals `self.run(keys[b])` bit for bit.
         `params` (a model with parameters): one theta row for every key, or an array [len(keys), P] with one row per key —
         a BANK of filters, filter b at theta_b in the same launches; element b equals `self.run(keys[b], params=rows[b])`."""
+        if retained is not None:
+            raise ValueError("run_many(retained=...): conditional filters run one at a time — call run(key, retained=...) per key")
         keys = list(keys)
         thetas = self._thetas(params, len(keys))
         row = (lambda b: None) if thetas is None else (lambda b: thetas[b if len(thetas) > 1 else 0])
@@ -490,3 +541,90 @@ class ParticleMH:
             ll, lp = np.where(acc, ll_new, ll), np.where(acc, lp_new, lp)
             samples[i], lls[i], accepted[i - 1] = theta, ll, acc
         return samples, lls, accepted
+
+
+@dataclass
+class ParticleGibbsResult:
+    paths: torch.Tensor | tuple  # f32[n_sweeps, T] (a tuple of columns for a multi-component carry): the path after every sweep
+    thetas: np.ndarray | None  # float64[n_sweeps, P]: the parameter row after every sweep (a model with parameters)
+
+
+class ParticleGibbs:
+    """Particle Gibbs (Andrieu, Doucet & Holenstein 2010) on the conditional filter: every sweep runs `smc` with the current
+    path retained in its last slot (`run(key, retained=path)`), draws ONE final particle by its weight and takes that
+    particle's path as the new one.  It needs no more than a handful of particles (>= 2) to keep moving where PMMH stalls.
+
+    How exact it is (profiles/csmc_summary.md): the free slots are resampled by a systematic comb in FIXED slot
+    order, under which a free slot's ancestor does not have the weights as its marginal law, and the sweep relabels the path
+    it selected as the last slot.  With `refresh="trace"` the chain's stationary law is therefore close to, not exactly,
+    p(x_0:T-1 | y, theta): a float64 restatement of the sampler measures smoothing means off by about 0.02 posterior
+    standard deviations at n = 4 .. 8 on the linear-Gaussian model (multinomial resampling of the free slots: none).
+    `refresh="backward"` draws the path from the recorded populations without following the slots' genealogy; prefer it
+    where that matters.
+
+        pg = ParticleGibbs(BootstrapSMC(model, obs, 8, record_history=True), refresh="trace")
+        paths = pg.run(key, n_sweeps=2000).paths            # [n_sweeps, T]
+
+    `refresh="trace"`: the drawn leaf is traced back through the ancestor table (gjx_paths_trace, one launch);
+    `refresh="backward"`: the path is drawn afresh by backward simulation over the recorded populations
+    (`backward_simulate(..., n_paths=1)`: particle Gibbs with backward simulation, which mixes over early steps even with
+    very few particles) — not available for a model with parameters (`PlanUnsupported`: transition tables hold constants).
+    `param_update(key, path, theta) -> theta`: the user's Gibbs / Metropolis update of theta given the path, run on the
+    host between sweeps; its result (rounded to f32 by the filter) is the next sweep's row.
+
+    Fully specified, so a run can be replayed sweep by sweep: with k_s = fold_in(key, s), the filter of sweep s runs under
+    fold_in(k_s, 0), the leaf is `categorical_index(fold_in(k_s, 1), final log-weights)` (a Gumbel-max draw by the
+    weights — not a fixed slot of a systematic comb, which is not distributed by the weights), the backward pass runs
+    under fold_in(k_s, 2) (it draws its own leaf from the final weights) and `param_update` gets fold_in(k_s, 3).  Sweep 0
+    is an UNCONDITIONAL run when `init` is None.  The path stays on the device from sweep to sweep: no host read happens
+    inside a sweep unless `param_update` makes one."""
+
+    def __init__(self, smc: BootstrapSMC, refresh: str = "trace", param_update=None):
+        if not isinstance(smc, BootstrapSMC) or not isinstance(smc.model, StateSpaceModel):
+            raise TypeError("ParticleGibbs needs a BootstrapSMC / GuidedSMC over a StateSpaceModel (a fixed model: write it as a StateSpaceModel)")
+        if refresh not in ("trace", "backward"):
+            raise ValueError(f"ParticleGibbs: refresh is 'trace' or 'backward', got {refresh!r}")
+        if not smc.record_history:
+            raise ValueError("ParticleGibbs needs the per-step states: build the filter with record_history=True")
+        if 0.0 < smc.ess_threshold < 1.0:
+            raise ValueError("ParticleGibbs: ESS-adaptive conditional filters are out of scope (ess_threshold must be 0)")
+        if refresh == "backward" and smc._parameterised:
+            from .plan import PlanUnsupported
+
+            raise PlanUnsupported(f"ParticleGibbs(refresh='backward') of a model with parameters {smc.model.params}: transition "
+                                  "tables hold constants only — use refresh='trace'")
+        if param_update is not None and not smc._parameterised:
+            raise ValueError("ParticleGibbs(param_update=...) needs a StateSpaceModel that declares parameters")
+        self.smc, self.refresh, self.param_update = smc, refresh, param_update
+
+    def sweep(self, k_s: prng.PRNGKey, path, theta=None):
+        """One sweep under its key k_s = fold_in(key, s) -> the new path, a list of contiguous f32[T] device tensors.
+        `path`: the retained path (None: an unconditional run)."""
+        ops = get_ops()
+        res = self.smc._run(prng.fold_in(k_s, 0), theta, None if path is None else tuple(path), log_z=False)
+        if self.refresh == "backward":
+            new = self.smc.backward_simulate(res, prng.fold_in(k_s, 2), 1).paths
+            return [c.reshape(-1).contiguous() for c in (new if isinstance(new, tuple) else (new,))]
+        leaf = ops.categorical_index(prng.fold_in(k_s, 1).literal(), res.log_weights.contiguous()).to(torch.int32)
+        cols = list(res.history) if isinstance(res.history, tuple) else [res.history]
+        out = ops.paths_trace(res.ancestors, cols, leaf, lineage=False)
+        return [c.reshape(-1).contiguous() for c in out["paths"]]
+
+    def run(self, key: prng.PRNGKey, n_sweeps: int, init=None, params=None) -> ParticleGibbsResult:
+        """`init`: the first retained path (as `run(retained=...)` takes it); None: sweep 0 is an unconditional run.
+        `params`: the first parameter row of a model with parameters (default: the filter's)."""
+        thetas = self.smc._thetas(params)
+        theta = None if thetas is None else np.asarray(thetas[0], dtype=np.float32).astype(np.float64)
+        path = None if init is None else (list(init) if isinstance(init, (tuple, list)) else [init])
+        kept, rows = [], []
+        for s in range(int(n_sweeps)):
+            k_s = prng.fold_in(key, s)
+            path = self.sweep(k_s, path, theta)
+            if self.param_update is not None:
+                new = self.param_update(prng.fold_in(k_s, 3), _columns(path), theta.copy())
+                theta = np.asarray(new, dtype=np.float32).astype(np.float64).reshape(-1)
+            kept.append(path)
+            if theta is not None:
+                rows.append(theta.copy())
+        paths = _columns([torch.stack([p[k] for p in kept]) for k in range(len(kept[0]))]) if kept else None
+        return ParticleGibbsResult(paths, np.stack(rows) if rows else None)

@@ -121,7 +121,11 @@ class PlanFilter:
         o.lib.call("gjx_smc_run_plan", C.byref(cfg), self.plan.handle, self._obs, o._p(out_e), o._p(out_q), cols,
                    o._p(logw), o._p(anc), o._p(ws), nb, o.stream())
 
-    def step(self, cfg, t, prev, out, prev_e, prev_q, ancestors):
+    def step(self, cfg, t, prev, out, prev_e, prev_q, ancestors, retained=None):
+        """`retained` (an abi.CsmcPath): the conditional step (include/gjx_csmc.h) — slot n - 1 keeps that path."""
+        if retained is not None:
+            self.ops.smc_plan_step_conditional(cfg, self.plan, t, self.y[t], prev, out, retained, prev_e, prev_q, ancestors)
+            return
         self.ops.smc_plan_step(cfg, self.plan, t, self.y[t], prev, out, prev_e, prev_q, ancestors)
 
     def transition_table(self):

@@ -210,7 +210,33 @@ def build_smc_plan(model: StateSpaceModel, obs_addrs: list[tuple], theta=None):
     plan._space = space
     plan._tables = (ti.sites, ts.sites)
     plan._state_args = (init_state, next_state)
+    plan._nested = bool(ti.scopes or ts.scopes)
     return plan, len(init_state)
+
+
+def check_conditional(plan) -> None:
+    """The model condition of the conditional step (include/gjx_csmc.h) on a lowered plan: flat bodies, and
+    in both of them every sampled site (latent or proposed) is, by itself, exactly one carry component and every carry
+    component is such a site — the rule `build_transition_table` enforces for backward simulation.  `PlanUnsupported`."""
+    if getattr(plan, "_nested", False):
+        raise PlanUnsupported("a retained path in a model with nested `@gen` calls: the conditional step needs flat bodies "
+                              "(every sampled site a carry component)")
+    for body, sites, state in zip(("init", "step"), plan._tables, plan._state_args):
+        component_of: dict = {}
+        for c, a in enumerate(state):
+            plain = (a.kind == abi.ARG_SITE and a.scale == 1.0 and a.offset == 0.0 and 0 <= a.ref < len(sites)
+                     and sites[a.ref].observed in (0, abi.SITE_PROPOSED))
+            if not plain:
+                raise PlanUnsupported(f"carry component {c} of `{body}` is not one of the body's sampled sites by itself: a retained "
+                                      "path does not determine the step (the conditional filter needs every carry component to be "
+                                      "a latent draw)")
+            if a.ref in component_of:
+                raise PlanUnsupported(f"site {a.ref} of `{body}` is returned twice (carry components {component_of[a.ref]} and {c})")
+            component_of[a.ref] = c
+        for q, site in enumerate(sites):
+            if site.observed in (0, abi.SITE_PROPOSED) and q not in component_of:
+                raise PlanUnsupported(f"the latent site {q} of `{body}` is not returned in the carry: a retained path does not "
+                                      "determine it (the conditional filter needs every sampled site to be a carry component)")
 
 
 def _param_space(model: StateSpaceModel, theta) -> ParamSpace | None:
@@ -337,6 +363,7 @@ def build_guided_plan(model: StateSpaceModel, obs_addrs: list[tuple], step_propo
     plan._space = space
     plan._tables = (ti.sites, ts.sites)  # the lowered tables (tests and tools read the modes / references from them)
     plan._state_args = (init_state, next_state)
+    plan._nested = False
     return plan, len(init_state)
 
 

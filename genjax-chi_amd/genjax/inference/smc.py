@@ -4,8 +4,9 @@ Importance, ImportanceK, SMCAlgorithm), plus what the north star adds on top of 
 
 from .._amd.inference import (ChangeTarget, Importance, ImportanceK, ParticleCollection, SMCAlgorithm,
                               stack_to_first_dim)
-from .._amd.smc_fused import (BootstrapSMC, DiscreteHMM, GuidedSMC, LinearGaussianSSM, ParticleMH, SMCResult,
-                              StateSpaceModel, Trajectories)
+from .._amd.smc_fused import (BootstrapSMC, DiscreteHMM, GuidedSMC, LinearGaussianSSM, ParticleGibbs, ParticleGibbsResult,
+                              ParticleMH, SMCResult, StateSpaceModel, Trajectories)
 
 __all__ = ["ChangeTarget", "Importance", "ImportanceK", "SMCAlgorithm", "ParticleCollection", "BootstrapSMC", "GuidedSMC",
-           "LinearGaussianSSM", "DiscreteHMM", "StateSpaceModel", "SMCResult", "Trajectories", "stack_to_first_dim", "ParticleMH"]
+           "LinearGaussianSSM", "DiscreteHMM", "StateSpaceModel", "SMCResult", "Trajectories", "stack_to_first_dim", "ParticleMH",
+           "ParticleGibbs", "ParticleGibbsResult"]
