@@ -68,14 +68,26 @@ GJX_HD void threefry2x32(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uin
   o1 = x1;
 }
 
+// a ^ b ^ c.  gfx950 has a three-input bitwise instruction (v_bitop3_b32, truth table 0x96; the third source may be a scalar
+// register: the round key), which the compiler does not form from an XOR chain by itself: it emits two v_xor_b32.  Host code
+// and other architectures keep the chain, and so does -DGJX_PHILOX_PLAIN_XOR (the A/B and pricing escape:
+// GJX_JIT_DEFINE=GJX_PHILOX_PLAIN_XOR for the generated kernels).  The same bits either way.
+GJX_HD uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
+#if defined(__HIP_DEVICE_COMPILE__) && defined(__gfx950__) && !defined(GJX_PHILOX_PLAIN_XOR)
+  return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+#else
+  return a ^ b ^ c;
+#endif
+}
+
 GJX_HD void philox4x32(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2,
                        uint32_t c3, uint32_t& o0, uint32_t& o1, uint32_t& o2, uint32_t& o3) {
 #pragma unroll
   for (int r = 0; r < 10; ++r) {
     const uint64_t p0 = (uint64_t)0xD2511F53u * c0;  // v_mad_u64_u32: hi and lo in one op
     const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    const uint32_t n0 = xor3((uint32_t)(p1 >> 32), c1, k0);
+    const uint32_t n2 = xor3((uint32_t)(p0 >> 32), c3, k1);
     c1 = (uint32_t)p1;
     c3 = (uint32_t)p0;
     c0 = n0;

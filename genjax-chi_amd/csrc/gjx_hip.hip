@@ -13,6 +13,11 @@
 #include "../../include/gjx_backmove.h"
 #include "../../include/gjx_smc_params.h"
 #include "../../include/gjx_csmc.h"
+// The library's own kernels keep the Philox round's plain XOR chain (gjx_device.hpp xor3): with v_bitop3_b32 the one-filter
+// LGSSM step measured 0.5 % slower (8.96e10 against 9.01e10 particle-steps/s, three alternating runs each, parent's range
+// 0.1 %), while the generated kernels, which include the header on their own, gain 6 % (importance) and 12 % (LGSSM scan);
+// profiles/philox_xor3_summary.md.
+#define GJX_PHILOX_PLAIN_XOR 1
 #include "gjx_device.hpp"
 
 #include <hip/hip_runtime.h>
@@ -2351,9 +2356,11 @@ static int jit_form_pref() {  // GJX_JIT_FORM = one | pair | quad (test / tuning
 // registers is 4 waves, <= 96 5, <= 80 6, <= 72 7, <= 64 8 (allocated registers: the code object's .vgpr_count; a rocprofv3
 // trace's VGPR column is half of it).
 //  * pairs: hint 6 (<= 80 VGPRs); the 10-latent kernel takes 49 under it.
-//  * quads: none.  Built without SLP vectorisation (gjx_plan_jit.hpp compile_options) the 10-latent kernel allocates 62
-//    VGPRs unhinted, no scratch: 8 waves (with SLP: 67 / 68, 7 waves; profiles/issue_cost_summary.md has both measured;
-//    tools/ab_waves_hint.py measures hints against each other through GJX_JIT_DEFINE=GJX_WAVES_HINT=<k>).
+//  * quads: none.  Built without SLP vectorisation (gjx_plan_jit.hpp compile_options) the 10-latent kernel allocates 64
+//    VGPRs unhinted, no scratch: 8 waves (62 with the Philox round's plain XOR chain; with SLP: 67 / 68, 7 waves;
+//    profiles/issue_cost_summary.md and profiles/philox_xor3_summary.md have them measured; hint 8 reaches 64 too but caps
+//    the scalar registers at 78 and prices 1.8 % higher; tools/ab_waves_hint.py measures hints against each other through
+//    GJX_JIT_DEFINE=GJX_WAVES_HINT=<k>).
 // A hinted build that spills more than 32 B is replaced by the unhinted one (plan_compiled).
 static int jit_waves_hint(int P) { return P == 2 ? 6 : 0; }
 // The importance generator of a plan.  `form`: particles per lane, 1, 2 (pairs) or 4 (quads); above 1 is PHILOX only.

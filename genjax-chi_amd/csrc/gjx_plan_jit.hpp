@@ -812,7 +812,12 @@ struct Gen {
       o << "      __syncthreads();\n      if ((threadIdx.x & 63) == 0) sh_red[wv] = bm;\n      __syncthreads();\n";
       o << "      bm = sh_red[2 * pr] > sh_red[2 * pr + 1] ? sh_red[2 * pr] : sh_red[2 * pr + 1];\n";
     }
-    o << "      if (max_partials && tr == 0 && live_row) max_partials[ro + row] = bm;\n";
+    // the row's writer lane.  The one-row quad form asks the row's own opaque lane offset: `tr == 0` is hoisted out of the row
+    // loop as a lane mask that lives in a scalar-register pair, and with the cipher's round keys held in scalar registers
+    // (v_bitop3_b32 reads them in place, gjx_device.hpp xor3) the allocator spilled that pair to a 65th VGPR — one more than
+    // eight waves per SIMD allow.  One v_cmp per row instead.
+    const char* lane0 = ubase ? "lb == 0u" : "tr == 0";
+    o << "      if (max_partials && " << lane0 << " && live_row) max_partials[ro + row] = bm;\n";
     o << "      if (row_e) {\n";
     o << "        const int32_t eb = row_anchor(bm);\n";
     {
@@ -824,7 +829,7 @@ struct Gen {
       o << "        __syncthreads();\n        if ((threadIdx.x & 63) == 0) sh_sum[wv] = sb;\n        __syncthreads();\n";
       o << "        sb = sh_sum[2 * pr] + sh_sum[2 * pr + 1];\n";
     }
-    o << "        if (tr == 0 && live_row) lse_store_row(row_e, row_s, ro + row, eb, sb, " << tail_scope() << ");\n";
+    o << "        if (" << lane0 << " && live_row) lse_store_row(row_e, row_s, ro + row, eb, sb, " << tail_scope() << ");\n";
     o << "      }\n    }\n";
     emit_tail();
     return o.str();

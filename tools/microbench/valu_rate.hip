@@ -9,6 +9,7 @@ __global__ __launch_bounds__(256) void k_rate(float* out, int iters, long long* 
   uint32_t w[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) { v[k] = threadIdx.x * 0.001f + k; w[k] = threadIdx.x * 2654435761u + k; }
+  uint32_t sk = (uint32_t)iters * 0x9E3779B9u;  // a wave-uniform round key: it lives in a scalar register
   float sel_lo = iters * 0.000125f, sel_hi = iters * 0.00075f;  // (run-time values either side of the threshold: nothing folds)
   asm volatile("" : "+v"(sel_lo), "+v"(sel_hi));
   const long long t0 = clock64();
@@ -23,8 +24,18 @@ __global__ __launch_bounds__(256) void k_rate(float* out, int iters, long long* 
       if (KIND == 5) asm volatile("v_xor_b32 %0, %0, %1" : "+v"(w[k]) : "v"(w[(k + 1) & 7]));  // v_xor_b32 alone (no v_xor3 folding)
       if (KIND == 6) v[k] = v[k] > 2.0f ? sel_lo : sel_hi;                              // v_cmp_lt_f32 + v_cndmask_b32 (mask through VCC / an SGPR pair)
       if (KIND == 8) { v[k] = (float)w[k]; w[k] = __float_as_uint(v[k]) + 3u; }         // v_cvt_f32_u32 + add
+      // the Philox round's three-input XOR (hi ^ c1 ^ round key, the key scalar) as ONE v_bitop3_b32 and as the v_xor_b32 pair
+      if (KIND == 9) asm volatile("v_bitop3_b32 %0, %0, %1, %2 bitop3:0x96" : "+v"(w[k]) : "v"(w[(k + 1) & 7]), "s"(sk));
+      if (KIND == 10) asm volatile("v_xor_b32 %0, %0, %1\n\tv_xor_b32 %0, %2, %0" : "+v"(w[k]) : "v"(w[(k + 1) & 7]), "s"(sk));
+      // ... and in the round's own pattern (multiply, XOR3 of its two words with the key, multiply, ...)
+      if (KIND == 11 || KIND == 12) {
+        const uint64_t p = (uint64_t)0xD2511F53u * w[k];  // v_mad_u64_u32
+        if (KIND == 11) asm volatile("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(w[k]) : "v"((uint32_t)(p >> 32)), "v"((uint32_t)p), "s"(sk));
+        else asm volatile("v_xor_b32 %0, %1, %2\n\tv_xor_b32 %0, %3, %0" : "=&v"(w[k]) : "v"((uint32_t)(p >> 32)), "v"((uint32_t)p), "s"(sk));
+      }
       if (KIND == 7) { uint64_t t = ((uint64_t)w[k] << 32) | w[(k + 1) & 7]; t += 0x123456789ull * (k + 1); w[k] = (uint32_t)(t >> 32) ^ (uint32_t)t; }  // 64-bit add + xor
     }
+    if (KIND >= 9) sk += 0x9E3779B9u;  // (the key schedule: scalar, beside the vector issue)
   }
   const long long t1 = clock64();
   float s = 0; uint32_t x = 0;
@@ -111,6 +122,10 @@ int main() {
   run<5>("xor_b32", 1, out, clk);
   run<6>("cmp+cndmask (vcc)", 2, out, clk);
   run<8>("cvt_f32_u32+add", 2, out, clk);
+  run<9>("bitop3_b32 (v, v, s)", 1, out, clk);
+  run<10>("xor_b32 pair (v, v, s)", 2, out, clk);
+  run<11>("mad_u64_u32+bitop3_b32", 2, out, clk);
+  run<12>("mad_u64_u32+xor_b32 pair", 3, out, clk);
   run_plain("pk_mul_f32, 8 chains", k_pk<8>, 8.0, out);
   run_plain("pk_mul_f32, 1 dependent chain", k_pk<1>, 8.0, out);
   run_plain("8 fma (per iteration)", k_lds<0>, 1.0, out);

@@ -22,13 +22,16 @@ import subprocess
 import sys
 
 # cycles per wave64 instruction per SIMD (tools/README.md has the measurements)
-RATES = {"simple": 2.4, "multiply": 5.5, "transcendental": 8.0, "packed": 4.2, "wait_states": 1.0, "scalar": 0.0, "lds": 0.0,
-         "memory": 0.0}
+# bitop3: v_bitop3_b32 issues at the packed instructions' rate, not at the simple one (4.26 measured with a scalar third source,
+# against 4.98 for the v_xor_b32 pair it replaces in the Philox round)
+RATES = {"simple": 2.4, "multiply": 5.5, "transcendental": 8.0, "packed": 4.2, "bitop3": 4.3, "wait_states": 1.0, "scalar": 0.0,
+         "lds": 0.0, "memory": 0.0}
 # class by mnemonic prefix, first match wins
 PREFIXES = [
     ("s_nop", "wait_states"),
     ("s_", "scalar"),
     ("v_pk_", "packed"),
+    ("v_bitop3", "bitop3"),
     ("v_mad_u64", "multiply"), ("v_mad_i64", "multiply"), ("v_mul_lo", "multiply"), ("v_mul_hi", "multiply"),
     ("v_sqrt", "transcendental"), ("v_rsq", "transcendental"), ("v_rcp", "transcendental"), ("v_log", "transcendental"),
     ("v_exp", "transcendental"), ("v_sin", "transcendental"), ("v_cos", "transcendental"),
@@ -36,7 +39,7 @@ PREFIXES = [
     ("ds_", "lds"),
     ("global_", "memory"), ("buffer_", "memory"), ("flat_", "memory"), ("scratch_", "memory"),
 ]
-CLASSES = ["simple", "multiply", "transcendental", "packed", "wait_states", "scalar", "lds", "memory"]
+CLASSES = ["simple", "multiply", "transcendental", "packed", "bitop3", "wait_states", "scalar", "lds", "memory"]
 
 
 def objdump():
@@ -146,7 +149,7 @@ def price(code_object, kernel=None):
             counts[cls] += 1
     cycles = {c: counts[c] * RATES[c] for c in CLASSES}
     return {"kernel": name, "loop_instructions": len(loop), "counts": counts, "s_nop_instructions": nops, "cycles": cycles,
-            "vector_instructions": sum(counts[c] for c in ("simple", "multiply", "transcendental", "packed")),
+            "vector_instructions": sum(counts[c] for c in ("simple", "multiply", "transcendental", "packed", "bitop3")),
             "priced_cycles": sum(cycles.values())}
 
 
