@@ -1625,6 +1625,26 @@ struct BackmoveArgs {
 constexpr uint32_t kBackmoveTile = 1024;      // CDF entries per coarse-level entry (8 KB: at most 10 dependent reads inside)
 constexpr uint32_t kBackmoveLdsTiles = 2048;  // 16 KB of LDS: populations up to 2^21 take the two-level search
 
+// Kernel argument block of the tempered move launch (include/gjx_temper.h; the kernel is generated from the site table,
+// gjx_plan_jit.hpp GenTemper).  By value: pointers, key, scales and beta live in scalar registers.
+constexpr int kTemperMaxLatents = 16;
+struct TemperArgs {
+  const float* x_in[kTemperMaxLatents];
+  float* x_out[kTemperMaxLatents];
+  const float* lp_in;
+  const float* ll_in;
+  float* lp_out;
+  float* ll_out;
+  const int32_t* anc;  // nullable: identity
+  int32_t* n_accept;   // nullable
+  Key key;
+  float scales[kTemperMaxLatents];
+  float beta;
+  uint32_t n;
+  uint32_t n_moves;
+  uint32_t recompute;
+};
+
 template <int N>
 struct IntC {
   static constexpr int value = N;

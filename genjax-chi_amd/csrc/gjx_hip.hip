@@ -13,6 +13,7 @@
 #include "../../include/gjx_backmove.h"
 #include "../../include/gjx_smc_params.h"
 #include "../../include/gjx_csmc.h"
+#include "../../include/gjx_temper.h"
 // The library's own kernels keep the Philox round's plain XOR chain (gjx_device.hpp xor3): with v_bitop3_b32 the one-filter
 // LGSSM step measured 0.5 % slower (8.96e10 against 9.01e10 particle-steps/s, three alternating runs each, parent's range
 // 0.1 %), while the generated kernels, which include the header on their own, gain 6 % (importance) and 12 % (LGSSM scan);
@@ -2306,27 +2307,30 @@ int gjx_plan_create_scoped(const gjx_site* sites, int n_sites, const gjx_scope* 
 
 // Launch parameters: the caller's values and the per-site constants that depend on them (the spec functions on the
 // host: IEEE-exact ops give the bits the device would compute per particle).
+static void plan_derive_params(PlanParams& prm, const CSite* sites, int n_sites) {
+  auto val = [&](const CArg& a) {  // CONST or PARAM
+    if (a.kind == GJX_ARG_CONST) return a.offset;
+    const float t = a.scale * prm.p[a.ref];
+    return t + a.offset;
+  };
+  for (int q = 0; q < n_sites; ++q) {
+    const CSite& c = sites[q];
+    if (c.pre != 2) continue;
+    if (c.dist == GJX_DIST_NORMAL) {
+      prm.d[2 * q] = normal_rs(val(c.a1));
+      prm.d[2 * q + 1] = normal_lognorm(val(c.a1));
+    } else if (c.dist == GJX_DIST_GAMMA) {
+      prm.d[2 * q + 1] = gamma_lognorm(val(c.a0), val(c.a1));
+    } else {
+      prm.d[2 * q + 1] = beta_lbeta(val(c.a0), val(c.a1));
+    }
+  }
+}
 int gjx_plan_set_params(gjx_plan* p, const float* params, int n_params) {
   if (!p || n_params < 0 || n_params > GJX_MAX_PARAMS || (n_params && !params) || n_params <= p->max_param) return GJX_ERR_INVALID;
   for (int k = 0; k < n_params; ++k) p->prm.p[k] = params[k];
   p->n_params = n_params;
-  auto val = [&](const CArg& a) {  // CONST or PARAM
-    if (a.kind == GJX_ARG_CONST) return a.offset;
-    const float t = a.scale * p->prm.p[a.ref];
-    return t + a.offset;
-  };
-  for (int q = 0; q < p->n_sites; ++q) {
-    const CSite& c = p->host[q];
-    if (c.pre != 2) continue;
-    if (c.dist == GJX_DIST_NORMAL) {
-      p->prm.d[2 * q] = normal_rs(val(c.a1));
-      p->prm.d[2 * q + 1] = normal_lognorm(val(c.a1));
-    } else if (c.dist == GJX_DIST_GAMMA) {
-      p->prm.d[2 * q + 1] = gamma_lognorm(val(c.a0), val(c.a1));
-    } else {
-      p->prm.d[2 * q + 1] = beta_lbeta(val(c.a0), val(c.a1));
-    }
-  }
+  plan_derive_params(p->prm, p->host, p->n_sites);
   return GJX_OK;
 }
 
@@ -4766,6 +4770,293 @@ int gjx_backmove_run(gjx_backsim_plan* p, const gjx_backmove_io* io, void* ws, s
       return GJX_ERR_LAUNCH;
     }
   }
+  return launch_status();
+}
+
+}  // extern "C"
+
+// =====================================================================================================================
+// Tempered SMC for static models (include/gjx_temper.h): the move kernel is generated from the site table
+// (gjx_plan_jit.hpp GenTemper); the ESS ladder is the fixed kernel below
+// =====================================================================================================================
+struct gjx_temper_plan {
+  int n_sites, n_latents;
+  int n_params;   // values set by gjx_temper_plan_set_params
+  int max_param;  // highest GJX_ARG_PARAM index the table reads (-1: none)
+  int max_input;  // highest input column it reads (-1: none)
+  PlanParams prm;
+  CSite sites[GJX_MAX_SITES];
+  ExprStore expr;
+  std::vector<void*> dev_owned;  // per-row tables of categorical (observed) sites
+  std::mutex mu;
+  gjx_jit::CompiledTemper jit[2];
+};
+
+namespace {
+constexpr unsigned kTemperMaxGrid = 256 * 16;  // workgroups of 256 particles, grid-stride beyond
+
+std::string temper_source(const gjx_temper_plan* p, int impl, PlanTables* tabs = nullptr) {
+  gjx_jit::TableScope ts;
+  gjx_jit::GenTemper<CSite, CArg> g;
+  g.impl = impl; g.sites = p->sites; g.n_sites = p->n_sites;
+  std::string src = g.run();
+  if (tabs) *tabs = ts.reg.tables();
+  return src;
+}
+
+gjx_jit::CompiledTemper* temper_compiled(gjx_temper_plan* p, int impl) {
+  gjx_jit::CompiledTemper& c = p->jit[impl];
+  const bool ready = compiled_once(p->mu, c, {{p->sites, p->n_sites}}, &p->dev_owned, [&] {
+    return c.load(temper_source(p, impl, &c.tabs), gjx_jit::PlanKind::temper, {"gjx_temper_move_kernel"}, {&c.move});
+  });
+  return ready ? &c : nullptr;
+}
+
+// ---- the ESS ladder -------------------------------------------------------------------------------------------------
+constexpr uint32_t kLadderMaxBlocks = 256;
+constexpr int kLadderChunk = 8;  // temperatures a pass over the block's entries serves: 16 float64 accumulators per lane
+struct LadderArgs {
+  const float* ll;
+  double* out;       // [2 G + 1]
+  uint32_t* ticket;  // zero between launches
+  float* mb;         // [W] block maxima
+  double* part;      // [W, G, 2] block sums
+  uint32_t n, per, G;
+  float delta[GJX_TEMPER_MAX_LADDER];
+};
+struct LadderScratch {
+  uint32_t* ticket;
+  float* mb;
+  double* part;
+};
+bool ladder_carve(Carver& cv, uint32_t W, uint32_t G, LadderScratch* out) {
+  out->ticket = cv.take<uint32_t>(2);
+  out->mb = cv.take<float>(W);
+  out->part = cv.take<double>((size_t)W * G * 2);
+  return cv.ok;
+}
+// the sum of v over the workgroup in a FIXED tree: a xor butterfly inside each wave (every lane ends with the same bits),
+// then the four waves in index order
+GJX_DEV double ladder_block_sum(double v, double* sh) {
+#pragma unroll
+  for (int m = 1; m < kWave; m <<= 1) v += __shfl_xor(v, m, kWave);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+__global__ __launch_bounds__(kBlock) void k_temper_ladder(LadderArgs a) {
+  __shared__ float sh_red[4];
+  __shared__ double sh_sum[4];
+  __shared__ uint32_t sh_last;
+  const uint32_t b = blockIdx.x, W = gridDim.x, G = a.G;
+  const uint64_t lo64 = (uint64_t)b * a.per;
+  const uint32_t lo = lo64 < a.n ? (uint32_t)lo64 : a.n;
+  const uint32_t hi = (uint64_t)lo + a.per < a.n ? lo + a.per : a.n;
+  const float ninf = -__builtin_inff();
+  float mx = ninf;
+  for (uint32_t i = lo + threadIdx.x; i < hi; i += kBlock) {
+    const float v = a.ll[i];
+    mx = v > mx ? v : mx;  // (a NaN is skipped)
+  }
+  const float mb = block_max(mx, sh_red);
+  for (uint32_t g0 = 0; g0 < G; g0 += kLadderChunk) {
+    double s1[kLadderChunk], s2[kLadderChunk];
+#pragma unroll
+    for (int u = 0; u < kLadderChunk; ++u) { s1[u] = 0.0; s2[u] = 0.0; }
+    if (mb > ninf) {
+      for (uint32_t i = lo + threadIdx.x; i < hi; i += kBlock) {
+        const float v = a.ll[i];
+        if (!(v > ninf)) continue;  // -inf, NaN: no contribution
+        const float c = v - mb;
+#pragma unroll
+        for (int u = 0; u < kLadderChunk; ++u) {
+          const float dl = g0 + u < G ? a.delta[g0 + u] : 0.0f;
+          const float t = dl * c;
+          const double e = (double)m_exp(t);
+          s1[u] += e;
+          s2[u] += e * e;
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kLadderChunk; ++u) {
+      const double t1 = ladder_block_sum(s1[u], sh_sum);
+      const double t2 = ladder_block_sum(s2[u], sh_sum);
+      if (threadIdx.x == 0 && g0 + u < G) {
+        a.part[((size_t)b * G + g0 + u) * 2] = t1;
+        a.part[((size_t)b * G + g0 + u) * 2 + 1] = t2;
+      }
+    }
+  }
+  // the ticket: the writer lane releases its stores with the add; the last arriver's workgroup acquires and folds
+  if (threadIdx.x == 0) {
+    a.mb[b] = mb;
+    sh_last = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == W - 1u ? 1u : 0u;
+  }
+  __syncthreads();
+  if (!sh_last) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  float M = ninf;
+  for (uint32_t k = 0; k < W; ++k) M = a.mb[k] > M ? a.mb[k] : M;
+  if (threadIdx.x < G) {
+    const uint32_t g = threadIdx.x;
+    const double dl = (double)a.delta[g];
+    double S1 = 0.0, S2 = 0.0;
+    if (M > ninf) {
+      for (uint32_t k = 0; k < W; ++k) {  // in index order
+        const float mk = a.mb[k];
+        if (!(mk > ninf)) continue;
+        const double f = exp(dl * ((double)mk - (double)M));
+        S1 += f * a.part[((size_t)k * G + g) * 2];
+        S2 += (f * f) * a.part[((size_t)k * G + g) * 2 + 1];
+      }
+    }
+    a.out[2 * g] = S1;
+    a.out[2 * g + 1] = S2;
+  }
+  if (threadIdx.x == 0) {
+    a.out[2 * G] = (double)M;
+    __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+}  // namespace
+
+extern "C" {
+
+int gjx_temper_version(int* major, int* minor) { return version_out(major, minor, GJX_TEMPER_VERSION_MAJOR, GJX_TEMPER_VERSION_MINOR); }
+int gjx_temper_plan_create(const gjx_site* sites, int n_sites, uint32_t flags, gjx_temper_plan** out) {
+  if (!sites || !out || n_sites < 1 || n_sites > GJX_MAX_SITES || flags != 0u) return GJX_ERR_INVALID;
+  gjx_temper_plan* p = new (std::nothrow) gjx_temper_plan;
+  if (!p) return GJX_ERR_LAUNCH;
+  p->n_sites = n_sites; p->n_latents = 0; p->n_params = 0; p->max_param = -1; p->max_input = -1;
+  memset(&p->prm, 0, sizeof p->prm);
+  int n_observed = 0;
+  bool ok = true;
+  for (int s = 0; ok && s < n_sites; ++s) {
+    CSite& c = p->sites[s];
+    ok = convert_site(sites[s], s, c);
+    if (!ok) break;
+    if (c.observed) ++n_observed;
+    else if (c.dist > GJX_DIST_BETA) ok = false;  // an integer-valued latent has no random-walk move
+    else ++p->n_latents;
+    for (const CArg* a : {&c.a0, &c.a1, &c.obs}) {
+      if (a == &c.obs && !c.observed) continue;
+      if (a->kind == GJX_ARG_PARAM && a->ref > p->max_param) p->max_param = a->ref;
+      if (a->kind == GJX_ARG_INPUT && a->ref > p->max_input) p->max_input = a->ref;
+    }
+  }
+  if (!ok || p->n_latents < 1 || p->n_latents > GJX_TEMPER_MAX_LATENTS || n_observed < 1) {
+    delete p;
+    return GJX_ERR_INVALID;
+  }
+  expr_adopt(p->sites, n_sites, &p->expr);
+  const int mp = expr_max_ref(p->sites, n_sites, GJX_EXPR_PARAM), mi = expr_max_ref(p->sites, n_sites, GJX_EXPR_INPUT);
+  if (mp > p->max_param) p->max_param = mp;
+  if (mi > p->max_input) p->max_input = mi;
+  *out = p;
+  return GJX_OK;
+}
+int gjx_temper_plan_destroy(gjx_temper_plan* p) {
+  if (!p) return GJX_OK;
+  for (auto& c : p->jit) c.release();
+  free_owned(p->dev_owned);
+  delete p;
+  return GJX_OK;
+}
+int gjx_temper_plan_set_params(gjx_temper_plan* p, const float* params, int n_params) {
+  if (!p || n_params < 0 || n_params > GJX_MAX_PARAMS || (n_params && !params) || n_params <= p->max_param) return GJX_ERR_INVALID;
+  for (int k = 0; k < n_params; ++k) p->prm.p[k] = params[k];
+  p->n_params = n_params;
+  plan_derive_params(p->prm, p->sites, p->n_sites);
+  return GJX_OK;
+}
+int gjx_temper_plan_n_latents(const gjx_temper_plan* p) { return p ? p->n_latents : GJX_ERR_INVALID; }
+int gjx_temper_plan_source(const gjx_temper_plan* p, int impl, char* buf, size_t buf_len, size_t* needed) {
+  if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
+  return copy_source_out(temper_source(p, impl), buf, buf_len, needed);
+}
+int gjx_temper_plan_compile_check(const gjx_temper_plan* p, int impl) {
+  if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
+  return gjx_jit::compile_only(temper_source(p, impl), gjx_jit::PlanKind::temper) ? GJX_OK : GJX_ERR_UNSUPPORTED;
+}
+int gjx_temper_move(gjx_temper_plan* p, const gjx_temper_io* io, gjx_stream s) {
+  if (!p || !io || io->n < 1 || io->n >= (1ull << 31) || (io->impl != 0 && io->impl != 1) || (io->impl == 0 && io->key_lane != 0) ||
+      io->n_moves < 0 || io->n_moves > GJX_TEMPER_MAX_MOVES)
+    return GJX_ERR_INVALID;
+  if (!io->lp_out || !io->ll_out || (!io->recompute && (!io->lp_in || !io->ll_in)) || (io->n_moves > 0 && !io->scales))
+    return GJX_ERR_INVALID;
+  if (io->n_input_cols < 0 || io->n_input_cols > 16 || io->n_input_cols <= p->max_input || (io->n_input_cols && !io->input_cols) ||
+      p->n_params <= p->max_param)
+    return GJX_ERR_INVALID;
+  TemperArgs A;
+  memset(&A, 0, sizeof A);
+  for (int l = 0; l < p->n_latents; ++l) {
+    if (!io->x_in[l] || !io->x_out[l]) return GJX_ERR_INVALID;
+    A.x_in[l] = io->x_in[l];
+    A.x_out[l] = io->x_out[l];
+    A.scales[l] = io->scales ? io->scales[l] : 0.0f;
+  }
+  RunCols cols;
+  memset(&cols, 0, sizeof cols);
+  for (int c = 0; c < io->n_input_cols; ++c) {
+    if (c <= p->max_input && !io->input_cols[c]) return GJX_ERR_INVALID;
+    cols.in[c] = io->input_cols[c];
+  }
+  if (!gjx_jit::enabled()) return GJX_ERR_UNSUPPORTED;  // a generated kernel only
+  gjx_jit::CompiledTemper* k = temper_compiled(p, io->impl);
+  if (!k) return GJX_ERR_JIT;
+  A.lp_in = io->lp_in; A.ll_in = io->ll_in; A.lp_out = io->lp_out; A.ll_out = io->ll_out;
+  A.anc = io->ancestors; A.n_accept = io->n_accept;
+  A.key = Key{io->key[0], io->key[1], (uint32_t)io->key_lane, (uint32_t)(io->key_lane >> 32)};
+  A.beta = io->beta;
+  A.n = (uint32_t)io->n;
+  A.n_moves = (uint32_t)io->n_moves;
+  A.recompute = io->recompute ? 1u : 0u;
+  const uint64_t wg = (io->n + kBlock - 1) / kBlock;
+  unsigned grid = (unsigned)(wg < kTemperMaxGrid ? wg : kTemperMaxGrid);
+  if (io->max_workgroups && grid > io->max_workgroups) grid = io->max_workgroups;
+  PlanParams prm = p->prm;
+  PlanTables tabs = k->tabs;
+  void* args[] = {&A, &cols, &prm, &tabs};
+  if (hipModuleLaunchKernel(k->move, grid, 1, 1, kBlock, 1, 1, 0, S(s), args, nullptr) != hipSuccess) {
+    (void)hipGetLastError();
+    return GJX_ERR_LAUNCH;
+  }
+  return launch_status();
+}
+
+uint32_t gjx_temper_ladder_blocks(uint64_t n) {
+  const uint64_t rows = nrows_of(n);
+  return (uint32_t)(rows < kLadderMaxBlocks ? rows : kLadderMaxBlocks);
+}
+size_t gjx_temper_ladder_workspace_bytes(uint64_t n, int32_t n_deltas) {
+  if (n < 1 || n >= (1ull << 31) || n_deltas < 1 || n_deltas > GJX_TEMPER_MAX_LADDER) return 0;
+  Carver cv{nullptr, ~(size_t)0};
+  LadderScratch sc;
+  (void)ladder_carve(cv, gjx_temper_ladder_blocks(n), (uint32_t)n_deltas, &sc);
+  return ~(size_t)0 - cv.left;
+}
+int gjx_temper_ess_ladder(const float* ll, uint64_t n, const float* deltas, int32_t n_deltas, double* out, void* ws, size_t ws_bytes,
+                          gjx_stream s) {
+  if (!ll || !deltas || !out || n < 1 || n >= (1ull << 31) || n_deltas < 1 || n_deltas > GJX_TEMPER_MAX_LADDER || ((uintptr_t)ws & 7) != 0)
+    return GJX_ERR_INVALID;
+  LadderArgs A;
+  memset(&A, 0, sizeof A);
+  for (int g = 0; g < n_deltas; ++g) {
+    if (!(deltas[g] >= 0.0f) || !(deltas[g] - deltas[g] == 0.0f)) return GJX_ERR_INVALID;
+    A.delta[g] = deltas[g];
+  }
+  if (!ws || ws_bytes < gjx_temper_ladder_workspace_bytes(n, n_deltas)) return GJX_ERR_WORKSPACE;
+  const uint32_t W = gjx_temper_ladder_blocks(n);
+  Carver cv{(char*)ws, ws_bytes};
+  LadderScratch sc;
+  if (!ladder_carve(cv, W, (uint32_t)n_deltas, &sc)) return GJX_ERR_WORKSPACE;
+  A.ll = ll; A.out = out; A.ticket = sc.ticket; A.mb = sc.mb; A.part = sc.part;
+  A.n = (uint32_t)n;
+  A.per = (uint32_t)((n + W - 1) / W);
+  A.G = (uint32_t)n_deltas;
+  k_temper_ladder<<<W, kBlock, 0, S(s)>>>(A);
   return launch_status();
 }
 

@@ -1472,6 +1472,97 @@ struct GenBackmove {
   }
 };
 
+// The move kernel of a tempered SMC sampler (include/gjx_temper.h) over a flat importance-style site table: one lane per
+// particle, the chain's state (L latent values, lp, ll) in registers, K Metropolis-Hastings sweeps in a run-time loop.
+//   assess   tm_assess is the table's walk by SiteEmitter (mode 0: parameters, input columns and postfix programs as in an
+//            importance kernel) over a COPY of the table in which every latent site is an observed one whose value is the
+//            function argument nx_<l> — the register the chain holds (the GJX_ARG_NEXT form of the transition tables).
+//            Nothing is drawn in it; the latent sites' log-densities go to lp (-inf outside a Gamma's / Beta's open support:
+//            the density formulas are TFP's and do not say so themselves — a Gamma(1, b) is finite below 0), the observed
+//            sites' to ll.
+//   propose  x'_l = x_l + scales[l] * site_normal(Stream(split_at(p_r, i), fold of latent l)): what k_sample_normal computes
+//            for the lazy children of p_r.  Under PHILOX latents 2 k and 2 k + 1 read the same pair block (one cipher
+//            call after common-subexpression elimination).
+//   keys     fold_in(key, r) and its two children are wave-uniform: three cipher blocks per sweep on the scalar side.
+// No LDS (the Box-Muller tables are read from the constant arrays: GJX_BM_LDS is not defined), no barrier.
+template <class CSiteT, class CArgT>
+struct GenTemper {
+  std::ostringstream o;
+  int impl;
+  const CSiteT* sites;
+  int n_sites;
+
+  std::string run() {
+    const std::string I = std::to_string(impl);
+    emit_prelude(o);
+    std::vector<CSiteT> tab(sites, sites + n_sites);
+    int L = 0;
+    for (int q = 0; q < n_sites; ++q) {
+      if (sites[q].observed) continue;
+      tab[q].observed = 1;
+      tab[q].obs = CArgT{};
+      tab[q].obs.kind = GJX_ARG_NEXT;
+      tab[q].obs.ref = L++;
+      tab[q].obs.scale = 1.0f;
+    }
+    auto list = [&](const std::string& pre) {  // pre0 pre1 ... pre<L-1>
+      std::string t;
+      for (int l = 0; l < L; ++l) t += pre + std::to_string(l);
+      return t;
+    };
+    o << "__device__ __forceinline__ void tm_assess(const RunCols& cols, const PlanParams& prm, const PlanTables& tabs, uint32_t li"
+      << list(", float nx_") << ", float& lp_out, float& ll_out) {\n";
+    o << "  (void)cols; (void)prm; (void)tabs; (void)li;\n  float lp = 0.0f, ll = 0.0f;\n";
+    SiteEmitter<CSiteT, CArgT> e{o, impl, 0, tab.data(), n_sites, "  ", ""};
+    for (int q = 0; q < n_sites; ++q) {
+      e.head(q);
+      if (sites[q].observed) {
+        o << "  ll = ll + " << e.lp_of(q) << ";\n";
+        continue;
+      }
+      // a latent outside its site's OPEN support (a NaN included) has log-density -inf, whatever the density formula gives there
+      const std::string v = e.nm("vf", q);
+      const std::string in = sites[q].dist == GJX_DIST_GAMMA ? "(" + v + " > 0.0f)"
+                             : sites[q].dist == GJX_DIST_BETA ? "(" + v + " > 0.0f && " + v + " < 1.0f)" : "";
+      if (in.empty()) o << "  lp = lp + " << e.lp_of(q) << ";\n";
+      else o << "  lp = lp + (" << in << " ? " << e.lp_of(q) << " : -__builtin_inff());\n";
+    }
+    o << "  lp_out = lp; ll_out = ll;\n}\n";
+    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_temper_move_kernel(TemperArgs a, RunCols cols, PlanParams prm, PlanTables tabs) {\n";
+    o << "  const uint32_t n = a.n;\n";
+    o << "  for (uint64_t i64 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i64 < n; i64 += (uint64_t)gridDim.x * blockDim.x) {\n";
+    o << "    const uint32_t i = (uint32_t)i64;\n";
+    o << "    uint32_t an = a.anc ? (uint32_t)a.anc[i] : i;\n    an = an < n ? an : n - 1u;\n";
+    for (int l = 0; l < L; ++l) o << "    float x" << l << " = a.x_in[" << l << "][an];\n";
+    o << "    float lp, ll;\n";
+    o << "    if (a.recompute) tm_assess(cols, prm, tabs, i" << list(", x") << ", lp, ll);\n";
+    o << "    else { lp = a.lp_in[an]; ll = a.ll_in[an]; }\n";
+    o << "    int32_t acc = 0;\n";
+    o << "    for (uint32_t r = 0; r < a.n_moves; ++r) {\n";
+    o << "      const Key kr = fold_in<" << I << ">(a.key, r);\n";
+    o << "      const Key pk = split_at<" << I << ">(fold_in<" << I << ">(kr, 0u), (uint64_t)i);\n";
+    o << "      const Key ak = split_at<" << I << ">(fold_in<" << I << ">(kr, 1u), (uint64_t)i);\n";
+    for (int l = 0; l < L; ++l) {
+      const uint32_t fold = impl == 0 ? (uint32_t)(l + 1) : (uint32_t)l;  // (SiteEmitter::fold_of for a table of L latents)
+      o << "      const float t" << l << " = a.scales[" << l << "] * site_normal<" << I << ">(Stream<" << I << ">(pk, true, " << fold << "u));\n";
+      o << "      const float y" << l << " = x" << l << " + t" << l << ";\n";
+    }
+    o << "      float lpn, lln;\n      tm_assess(cols, prm, tabs, i" << list(", y") << ", lpn, lln);\n";
+    o << "      const float bh = a.beta * ll;\n      const float h = lp + bh;\n";
+    o << "      const float bn = a.beta * lln;\n      const float hn = lpn + bn;\n";
+    o << "      const float d = hn - h;\n";
+    o << "      const float lg = m_log(uniform01(Stream<" << I << ">(ak, false, 0u).bits32(0u)));\n";
+    o << "      if (d >= 0.0f || lg < d) {";
+    for (int l = 0; l < L; ++l) o << " x" << l << " = y" << l << ";";
+    o << " lp = lpn; ll = lln; ++acc; }\n";
+    o << "    }\n";
+    for (int l = 0; l < L; ++l) o << "    a.x_out[" << l << "][i] = x" << l << ";\n";
+    o << "    a.lp_out[i] = lp;\n    a.ll_out[i] = ll;\n    if (a.n_accept) a.n_accept[i] = acc;\n";
+    o << "  }\n}\n";
+    return o.str();
+  }
+};
+
 inline bool enabled() {
   const char* e = std::getenv("GJX_PLAN_JIT");
   return !(e && e[0] == '0');
@@ -1517,7 +1608,7 @@ inline bool read_file(const std::string& path, std::string* out) {
   return true;
 }
 // The plan kinds that generate kernels.  Each has its own compiler option list (compile_options).
-enum class PlanKind { importance, scan, smc, backsim };
+enum class PlanKind { importance, scan, smc, backsim, temper };
 // The options of one plan kind: four fixed ones, then the kind's own, then the A/B knobs (a later option wins).
 //  * importance: -fno-slp-vectorize.  The SLP vectoriser turns pairs of f32 operations into v_pk_* forms, which issue no
 //    faster per flop than two scalar ones (tools/README.md) but cost v_mov shuffles to build register pairs and hazard wait
@@ -1527,6 +1618,7 @@ enum class PlanKind { importance, scan, smc, backsim };
 //  * scan: nothing of its own.  The scan kernels share emit_pair_lane_sites, but the LGSSM quad kernel prices at 1337.0
 //    cycles per row and step with SLP and 1345.6 without (56 / 50 VGPRs: eight waves per SIMD either way).
 //  * smc, backsim: nothing of their own (not priced).
+//  * temper: nothing of its own (not priced): one particle per lane, nothing for the SLP vectoriser to pair.
 inline std::vector<std::string> compile_options(PlanKind kind) {
   std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"};
   if (kind == PlanKind::importance) opts.push_back("-fno-slp-vectorize");
@@ -1834,6 +1926,9 @@ struct CompiledSmc : Module {  // the kernels of a filter (bootstrap or guided)
 };
 struct CompiledBacksim : Module {  // the two kernels of a backward pass
   hipFunction_t step = nullptr, last = nullptr;
+};
+struct CompiledTemper : Module {  // the move kernel of a tempered sampler
+  hipFunction_t move = nullptr;
 };
 
 }  // namespace gjx_jit

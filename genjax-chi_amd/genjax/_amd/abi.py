@@ -92,6 +92,10 @@ class CsmcUnavailable(HeaderUnavailable):
     header, why = "gjx_csmc.h", "the conditional step runs as generated HIP kernels only"
 
 
+class TemperUnavailable(HeaderUnavailable):
+    header, why = "gjx_temper.h", "the tempered move runs as a generated HIP kernel only"
+
+
 class Keys(C.Structure):
     _fields_ = [
         ("impl", C.c_int32),
@@ -589,6 +593,53 @@ CSMC_PROTOTYPES = {
 }
 CSMC_ABI_VERSION = (0, 1)
 
+# include/gjx_temper.h: an EIGHTH header, same arrangement — tempered SMC for static models: a plan kind of its own over a
+# flat importance-style site table, the fused resample-move launch and the one-launch ESS ladder
+TEMPER_MAX_LATENTS = 16  # gjx_temper.h: GJX_TEMPER_MAX_LATENTS
+TEMPER_MAX_MOVES = 256   # ... GJX_TEMPER_MAX_MOVES
+TEMPER_MAX_LADDER = 64   # ... GJX_TEMPER_MAX_LADDER
+
+
+class TemperIO(C.Structure):
+    """gjx_temper_io (include/gjx_temper.h)."""
+    _fields_ = [
+        ("impl", C.c_int32),
+        ("n_moves", C.c_int32),
+        ("recompute", C.c_int32),
+        ("beta", C.c_float),
+        ("n", C.c_uint64),
+        ("key", C.c_uint32 * 2),
+        ("key_lane", C.c_uint64),
+        ("x_in", C.c_void_p * TEMPER_MAX_LATENTS),
+        ("lp_in", C.c_void_p),
+        ("ll_in", C.c_void_p),
+        ("ancestors", C.c_void_p),
+        ("scales", C.POINTER(C.c_float)),
+        ("input_cols", C.POINTER(C.c_void_p)),
+        ("n_input_cols", C.c_int32),
+        ("x_out", C.c_void_p * TEMPER_MAX_LATENTS),
+        ("lp_out", C.c_void_p),
+        ("ll_out", C.c_void_p),
+        ("n_accept", C.c_void_p),
+        ("max_workgroups", C.c_uint32),
+    ]
+
+
+TEMPER_PROTOTYPES = {
+    "gjx_temper_version": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gjx_temper_plan_create": (C.c_int, [C.POINTER(Site), C.c_int, C.c_uint32, C.POINTER(_P)]),
+    "gjx_temper_plan_destroy": (C.c_int, [_P]),
+    "gjx_temper_plan_set_params": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int]),
+    "gjx_temper_plan_n_latents": (C.c_int, [_P]),
+    "gjx_temper_plan_source": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gjx_temper_plan_compile_check": (C.c_int, [_P, C.c_int]),
+    "gjx_temper_move": (C.c_int, [_P, C.POINTER(TemperIO), _P]),
+    "gjx_temper_ladder_blocks": (C.c_uint32, [C.c_uint64]),
+    "gjx_temper_ladder_workspace_bytes": (C.c_size_t, [C.c_uint64, C.c_int32]),
+    "gjx_temper_ess_ladder": (C.c_int, [_P, C.c_uint64, C.POINTER(C.c_float), C.c_int32, _P, _P, C.c_size_t, _P]),
+}
+TEMPER_ABI_VERSION = (0, 1)
+
 # The optional headers, in the order they are bound: every one is exported by libgjx_hip.so only and bound if present.
 class Header(collections.namedtuple("Header", "key header version_fn prototypes version_name unavailable")):
     @property
@@ -613,6 +664,7 @@ PLAN_HEADERS = {h.key: h for h in (
     Header("smc_params", "gjx_smc_params.h", "gjx_smc_params_version", SMC_PARAMS_PROTOTYPES, "SMC_PARAMS_ABI_VERSION",
            SmcParamsUnavailable),
     Header("csmc", "gjx_csmc.h", "gjx_csmc_version", CSMC_PROTOTYPES, "CSMC_ABI_VERSION", CsmcUnavailable),
+    Header("temper", "gjx_temper.h", "gjx_temper_version", TEMPER_PROTOTYPES, "TEMPER_ABI_VERSION", TemperUnavailable),
 )}
 
 
@@ -624,6 +676,9 @@ def all_optional_headers():
 _HEADER_OF = {name: h for h in all_optional_headers() for name in h.prototypes}  # entry point -> its optional header
 
 _NO_STATUS = {
+    "gjx_temper_plan_n_latents",
+    "gjx_temper_ladder_blocks",
+    "gjx_temper_ladder_workspace_bytes",
     "gjx_backmove_workspace_bytes",
     "gjx_backsim_workspace_bytes",
     "gjx_paths_workspace_bytes",

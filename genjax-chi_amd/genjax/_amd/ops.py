@@ -577,6 +577,79 @@ class Ops:
         return out
 
     # ---- fused SMC --------------------------------------------------------------------------------
+    # ---- tempered SMC for static models (include/gjx_temper.h) -----------------------------------------
+    def temper_plan_create(self, sites: list, keep=()) -> "TemperPlan":
+        """A gjx_temper_plan over a flat importance-style site table.  Raises abi.TemperUnavailable on a library without
+        include/gjx_temper.h (the CPU oracle)."""
+        self.lib.require("temper", "gjx_temper_plan_create")
+        arr = (abi.Site * max(1, len(sites)))(*sites)
+        handle = C.c_void_p()
+        self.lib.call("gjx_temper_plan_create", arr, len(sites), 0, C.byref(handle))
+        plan = TemperPlan(self, handle, int(self.lib.call("gjx_temper_plan_n_latents", handle)))
+        plan._keep = keep  # device tables and programs the sites point into
+        return plan
+
+    def temper_move(self, plan: "TemperPlan", key, x: list, lp, ll, beta: float, n_moves: int, scales=None, *, ancestors=None,
+                    recompute: bool = False, input_cols=(), want_accept: bool = True, max_workgroups: int = 0):
+        """gjx_temper_move: ONE launch — every particle loads its ancestor's latents `x` (L float32[n] columns) and
+        `lp` / `ll`, makes `n_moves` Metropolis-Hastings sweeps against prior * likelihood^beta under the scalar `key` (a
+        prng.PRNGKey) and writes fresh columns.  -> (x [L columns], lp, ll, n_accept int32[n] or None)."""
+        import numpy as np
+
+        self.lib.require("temper", "gjx_temper_move")
+        L, n = plan.n_latents, x[0].numel()
+        if len(x) != L:
+            raise ValueError(f"temper_move: the plan has {L} latents, got {len(x)} columns")
+        io = abi.TemperIO()
+        io.impl, io.n_moves, io.recompute, io.beta, io.n = key.impl, int(n_moves), 1 if recompute else 0, float(beta), n
+        io.key[0], io.key[1], io.key_lane = key.k0, key.k1, key.lane
+        block = self.empty_columns(n, [torch.float32] * (L + 2))
+        for l in range(L):
+            io.x_in[l] = self._chk(x[l], torch.float32, n, f"x[{l}]").value
+            io.x_out[l] = block[l].data_ptr()
+        if not recompute:
+            io.lp_in, io.ll_in = self._chk(lp, torch.float32, n, "lp").value, self._chk(ll, torch.float32, n, "ll").value
+        io.lp_out, io.ll_out = block[L].data_ptr(), block[L + 1].data_ptr()
+        if ancestors is not None:
+            io.ancestors = self._chk(ancestors, torch.int32, n, "ancestors").value
+        sc = None
+        if scales is not None:
+            sc = np.ascontiguousarray(np.asarray(scales, dtype=np.float32).reshape(-1))
+            if sc.size != L:
+                raise ValueError(f"temper_move: {L} scales expected, got {sc.size}")
+            io.scales = sc.ctypes.data_as(C.POINTER(C.c_float))
+        ins = (C.c_void_p * max(1, len(input_cols)))()
+        for i, t in enumerate(input_cols):
+            ins[i] = self._chk(t, torch.float32, n, f"input_cols[{i}]").value
+        io.input_cols, io.n_input_cols = ins, len(input_cols)
+        acc = self.empty(n, torch.int32) if want_accept else None
+        if acc is not None:
+            io.n_accept = acc.data_ptr()
+        io.max_workgroups = int(max_workgroups)
+        self.lib.call("gjx_temper_move", plan.handle, C.byref(io), self.stream())
+        return list(block[:L]), block[L], block[L + 1], acc
+
+    def temper_ladder_workspace(self, n: int) -> torch.Tensor:
+        """A zeroed workspace of gjx_temper_ess_ladder for populations of n and any ladder length (its ticket stays zero
+        from call to call: calls that share it must be stream-ordered)."""
+        self.lib.require("temper", "gjx_temper_ladder_workspace_bytes")
+        nb = int(self.lib.call("gjx_temper_ladder_workspace_bytes", int(n), abi.TEMPER_MAX_LADDER))
+        return torch.zeros(max(nb, 8), dtype=torch.uint8, device=self._alloc_device)
+
+    def temper_ess_ladder(self, ll: torch.Tensor, deltas, ws: torch.Tensor | None = None, out: torch.Tensor | None = None):
+        """gjx_temper_ess_ladder: ONE launch -> float64[2 G + 1] on the device: (S1_g, S2_g) of the increments
+        deltas[g] * ll for every g, then max(ll).  ESS_g = S1_g^2 / S2_g."""
+        import numpy as np
+
+        self.lib.require("temper", "gjx_temper_ess_ladder")
+        n = ll.numel()
+        d = np.ascontiguousarray(np.asarray(deltas, dtype=np.float32).reshape(-1))
+        ws = self.temper_ladder_workspace(n) if ws is None else ws
+        out = self.empty(2 * d.size + 1, torch.float64) if out is None else out
+        self.lib.call("gjx_temper_ess_ladder", self._chk(ll, torch.float32, n, "ll"), n, d.ctypes.data_as(C.POINTER(C.c_float)),
+                      int(d.size), self._p(out), self._p(ws), ws.numel(), self.stream())
+        return out
+
     def smc_config(self, impl, n_total, first, n_local, step_keys, resample_keys, ess_threshold: float = 0.0):
         """Config of a whole-run call or of the step-level entry points (`first`, `n_local`: a rank's own block).
         `step_keys` / `resample_keys`: [T, 2] for one filter, [F, T, 2] for F filters stepping in the same launches
@@ -1010,6 +1083,39 @@ class BacksimPlan:
         try:
             if self.handle:
                 self.ops.lib.call("gjx_backsim_plan_destroy", self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+class TemperPlan:
+    """A gjx_temper_plan (include/gjx_temper.h): the generated move kernel of one static model's site table."""
+
+    def __init__(self, ops: "Ops", handle, n_latents: int):
+        self.ops, self.handle, self.n_latents = ops, handle, n_latents
+
+    def set_params(self, values) -> "TemperPlan":
+        import numpy as np
+
+        v = np.ascontiguousarray(np.asarray(values, dtype=np.float32).reshape(-1))
+        self.ops.lib.call("gjx_temper_plan_set_params", self.handle,
+                          v.ctypes.data_as(C.POINTER(C.c_float)) if v.size else None, int(v.size))
+        return self
+
+    def compile_check(self, impl: int) -> int:
+        return self.ops.lib._gjx_temper_plan_compile_check(self.handle, impl)
+
+    def source(self, impl: int) -> str:
+        need = C.c_size_t()
+        self.ops.lib.call("gjx_temper_plan_source", self.handle, impl, None, 0, C.byref(need))
+        buf = C.create_string_buffer(need.value)
+        self.ops.lib.call("gjx_temper_plan_source", self.handle, impl, buf, need.value, None)
+        return buf.value.decode()
+
+    def __del__(self):
+        try:
+            if self.handle:
+                self.ops.lib.call("gjx_temper_plan_destroy", self.handle)
                 self.handle = None
         except Exception:
             pass

@@ -1,0 +1,296 @@
+"""Tempered SMC for static `@gen` models (include/gjx_temper.h).
+
+`TemperedSMC(target, n_particles)` walks a population from the prior of a static model to its posterior through the targets
+prior * likelihood^beta: every stage reweights by likelihood^(beta' - beta), resamples systematically and moves each particle
+with `n_moves` random-walk Metropolis-Hastings sweeps — the resampling gather and the sweeps are ONE launch
+(gjx_temper_move), and the next temperature is chosen from two one-launch ESS ladders (gjx_temper_ess_ladder) instead of a
+host bisection.  It needs no gradients and returns posterior samples AND log Z where the prior-proposal estimators
+(ImportanceK) have collapsed: a posterior much narrower than the prior."""
+
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+from . import abi, prng
+from .choicemap import ChoiceMap
+from .inference import ParticleCollection, SMCAlgorithm, Target
+from .lang import split
+from .plan import PlanTracer, PlanUnsupported, _make_plan, _needs_eager
+from .runtime import get_ops
+
+LADDER = 32  # candidates per ladder launch
+
+
+class _TemperTracer(PlanTracer):
+    """PlanTracer that names the address of whatever a tempered plan cannot hold."""
+
+    def _call(self, addr, gen_fn, args):
+        raise PlanUnsupported(f"TemperedSMC: nested generative function at address {addr!r}")
+
+    def handle_trace(self, addr, gen_fn, args):
+        try:
+            out = super().handle_trace(addr, gen_fn, args)
+        except PlanUnsupported as e:
+            if "at address" in str(e):
+                raise
+            raise PlanUnsupported(f"TemperedSMC: {e} at address {addr!r} (a vector-valued or otherwise unsupported site)") from None
+        m = self.meta[-1]
+        if m["obs"] is None and m["is_int"]:
+            raise PlanUnsupported(f"TemperedSMC: integer-valued latent at address {addr!r} (a random-walk move needs a float value)")
+        if self.inputs:
+            raise PlanUnsupported(f"TemperedSMC: per-particle column at address {addr!r}")
+        return out
+
+
+def lower(target: Target, n: int):
+    """-> the tracer of the target's body as a flat site table (the tracing ImportanceK uses), observations and scalar
+    arguments as launch parameters.  PlanUnsupported, naming the address, for what a tempered plan cannot hold."""
+    from .lang import StaticGenerativeFunction
+
+    if not isinstance(target.p, StaticGenerativeFunction):
+        raise PlanUnsupported("TemperedSMC: the target's model must be a static @gen function")
+    if any(_needs_eager(a) for a in target.args):
+        raise PlanUnsupported("TemperedSMC: the target's arguments need the per-site path")
+    constraint = target.constraint.merge(ChoiceMap.empty())
+    last = None
+    for use_params in (True, False):
+        tracer = _TemperTracer(constraint, n, use_params)
+        try:
+            tracer.run(target.p.source, tracer.wrap_args(target.args))
+        except PlanUnsupported as e:
+            if "at address" in str(e):
+                raise
+            last = e
+            continue
+        except Exception as e:  # symbolic values fed to code that expects tensors: retried with constants
+            last = PlanUnsupported(f"TemperedSMC: the body is not plan-able ({type(e).__name__}: {e})")
+            continue
+        addrs = [m["addr"] for m in tracer.meta]
+        if not any(m["obs"] is None for m in tracer.meta):
+            raise PlanUnsupported(f"TemperedSMC: no latent site among the addresses {addrs!r}")
+        if all(m["obs"] is None for m in tracer.meta):
+            raise PlanUnsupported(f"TemperedSMC: no observed site among the addresses {addrs!r}")
+        n_lat = sum(m["obs"] is None for m in tracer.meta)
+        if n_lat > abi.TEMPER_MAX_LATENTS:
+            raise PlanUnsupported(f"TemperedSMC: {n_lat} latents (at most {abi.TEMPER_MAX_LATENTS}); the last is at address "
+                                  f"{[m['addr'] for m in tracer.meta if m['obs'] is None][-1]!r}")
+        return tracer
+    raise last
+
+
+def ladder_deltas(beta: float, lo=None, hi=None):
+    """The candidates of one ladder launch, float32.  Coarse (lo is None): delta_j = (1 - beta) 2^-(G - 1 - j); fine:
+    delta_k = lo + (hi - lo) k / G."""
+    G = LADDER
+    if lo is None:
+        span = np.float32(np.float32(1.0) - np.float32(beta))
+        return (span * np.exp2(-np.arange(G - 1, -1, -1, dtype=np.float64))).astype(np.float32)
+    return (np.float64(lo) + (np.float64(hi) - np.float64(lo)) * np.arange(G, dtype=np.float64) / G).astype(np.float32)
+
+
+def ess_of(s1, s2):
+    s1, s2 = np.asarray(s1, dtype=np.float64), np.asarray(s2, dtype=np.float64)
+    return np.where(s2 > 0.0, s1 * s1 / np.where(s2 > 0.0, s2, 1.0), 0.0)
+
+
+def next_beta(beta: float, need: float, ess_fn):
+    """The schedule rule: the largest candidate step whose increment keeps ESS >= need, from a coarse
+    geometric ladder and a linear one between its bracketing candidates.  `ess_fn(deltas f32[G]) -> ESS float64[G]` is one
+    ladder launch.  -> (beta' as a float32 value, its ESS)."""
+    b = np.float32(beta)
+    coarse = ladder_deltas(beta)
+    ess = ess_fn(coarse)
+    if ess[-1] >= need:
+        return 1.0, float(ess[-1])
+    ok = np.nonzero(ess >= need)[0]
+    if ok.size == 0:
+        step, e = coarse[0], float(ess[0])
+    else:
+        j = int(ok[-1])
+        fine = ladder_deltas(beta, coarse[j], coarse[j + 1])
+        ess2 = ess_fn(fine)
+        ok2 = np.nonzero(ess2 >= need)[0]
+        k = int(ok2[-1]) if ok2.size else 0
+        step, e = fine[k], float(ess2[k])
+    nb = np.float32(b + np.float32(step))
+    if not nb > b:
+        nb = np.nextafter(b, np.float32(2.0))
+    return (1.0 if nb >= np.float32(1.0) else float(nb)), e
+
+
+class TemperedResult:
+    """What `TemperedSMC.run` returns.  `choices`: the final, equally weighted population's latent columns as a ChoiceMap;
+    `lp`, `ll`: its log-prior and log-likelihood columns (f32[n], on the device)."""
+
+    def __init__(self, log_marginal_likelihood, betas, ess, accept_rate, choices, lp, ll, columns):
+        self.log_marginal_likelihood, self.betas, self.ess, self.accept_rate = log_marginal_likelihood, betas, ess, accept_rate
+        self.choices, self.lp, self.ll, self.columns = choices, lp, ll, columns
+
+    def __repr__(self):
+        return (f"TemperedResult(log_marginal_likelihood={self.log_marginal_likelihood:.6f}, stages={len(self.betas) - 1}, "
+                f"n={self.lp.numel()})")
+
+
+class TemperedSMC(SMCAlgorithm):
+    """Adaptive tempered SMC sampler for a static target (Neal 2001; Del Moral, Doucet & Jasra 2006; the adaptive schedule
+    of Jasra et al. 2011).
+
+    `n_moves`: Metropolis-Hastings sweeps per stage; `ess_target`: the next temperature is the largest whose increment keeps
+    the effective sample size at `ess_target * n_particles`; `betas`: a FIXED increasing schedule ending at 1 instead;
+    `scale`: one proposal scale per latent (a number for all) instead of 2.38 / sqrt(L) times the weighted population
+    standard deviation.
+
+    The adaptive schedule depends on the particles, so the estimate of Z is consistent but NOT exactly unbiased (Beskos,
+    Jasra, Kantas & Thiery 2016); a fixed `betas=` keeps it unbiased.
+
+    Host reads per adaptive stage: the two ladders' results and the proposal scales — three (two at the last stage, where
+    the first ladder already reaches beta = 1; one fewer each with `scale=`; none with `betas=` and `scale=`) — and one at
+    the end of the run for the accumulated normalising constants and accept counts."""
+
+    def __init__(self, target: Target, n_particles: int, n_moves: int = 2, ess_target: float = 0.5, betas=None, scale=None):
+        if not isinstance(target, Target):
+            raise TypeError("TemperedSMC: target must be a Target")
+        self.target, self.n_particles, self.n_moves = target, int(n_particles), int(n_moves)
+        self.ess_target = float(ess_target)
+        if self.n_particles < 1 or not 0 <= self.n_moves <= abi.TEMPER_MAX_MOVES:
+            raise ValueError("TemperedSMC: n_particles >= 1 and 0 <= n_moves <= 256")
+        if not 0.0 < self.ess_target < 1.0:
+            raise ValueError("TemperedSMC: 0 < ess_target < 1")
+        self.betas = None
+        if betas is not None:
+            b = [float(np.float32(x)) for x in betas]
+            if b and b[0] == 0.0:
+                b = b[1:]
+            if not b or b[-1] != 1.0 or any(y <= x for x, y in zip([0.0] + b, b)):
+                raise ValueError("TemperedSMC: betas must increase strictly from above 0 to exactly 1")
+            self.betas = b
+        self.scale = scale
+        self._st = None
+
+    def get_num_particles(self):
+        return self.n_particles
+
+    def get_final_target(self):
+        return self.target
+
+    # -- lowering ----------------------------------------------------------------------------------------------------------
+    def _state(self):
+        ops = get_ops()
+        st = self._st
+        if st is not None and st["ops"] is ops:
+            return st
+        ops.lib.require("temper", "gjx_temper_plan_create")
+        tracer = lower(self.target, self.n_particles)
+        latents = [m for m in tracer.meta if m["obs"] is None]
+        tplan = ops.temper_plan_create(tracer.sites, keep=(tracer.keep, tracer))
+        st = self._st = dict(ops=ops, tracer=tracer, latents=latents, tplan=tplan, ws=None)
+        return st
+
+    def _scales(self, st):
+        L = len(st["latents"])
+        if self.scale is None:
+            return None
+        s = np.asarray(self.scale, dtype=np.float32).reshape(-1)
+        if s.size == 1:
+            s = np.repeat(s, L)
+        if s.size != L:
+            raise ValueError(f"TemperedSMC: scale must be one number or one per latent ({L})")
+        return s
+
+    @staticmethod
+    def population_scales(x: list, lw: torch.Tensor) -> torch.Tensor:
+        """2.38 / sqrt(L) times the weighted standard deviation of every latent column, float64 on the device, rounded to
+        float32 (f32[L], still on the device)."""
+        w = torch.softmax(lw.double(), dim=0)
+        cols = torch.stack([c.double() for c in x])
+        mean = (cols * w).sum(dim=1, keepdim=True)
+        var = (((cols - mean) ** 2) * w).sum(dim=1)
+        return (2.38 / math.sqrt(len(x)) * torch.sqrt(var)).to(torch.float32)
+
+    # -- the run ---------------------------------------------------------------------------------------------------------------
+    def run(self, key) -> TemperedResult:
+        """Stage 0 draws the population from the prior (the importance kernel) and fills lp / ll (one move launch with K = 0,
+        recompute); stage s >= 1 picks beta', reweights, resamples systematically under fold_in(fold_in(key, s), 0) and
+        moves under fold_in(fold_in(key, s), 1) — the last stage (beta' = 1) too, so the population returned is equally
+        weighted.  A function of `key` alone: two runs are bit-equal."""
+        st = self._state()
+        ops, tracer, tplan = st["ops"], st["tracer"], st["tplan"]
+        n, L, K = self.n_particles, len(st["latents"]), self.n_moves
+        plan = _make_plan(tracer)  # (sets the importance plan's launch parameters)
+        if tracer.params:
+            tplan.set_params(tracer.params)
+        dtypes = [torch.float32] * tracer.n_out
+        vals = ops.importance_run(plan, prng.split_lazy(prng.fold_in(key, 0), n), n, [], dtypes, want_score=False,
+                                  want_max_partials=False)[0]
+        x = [vals[m["out_col"]] for m in st["latents"]]
+        x, lp, ll, _ = ops.temper_move(tplan, key, x, None, None, 0.0, 0, None, recompute=True, want_accept=False)
+        if st["ws"] is None:
+            st["ws"] = ops.temper_ladder_workspace(n)
+        ws = st["ws"]
+        fixed_scales = self._scales(st)
+        need = self.ess_target * n
+
+        def ess_fn(deltas):
+            out = ops.temper_ess_ladder(ll, deltas, ws).cpu().numpy()  # (one host read)
+            return ess_of(out[0:-1:2], out[1:-1:2])
+
+        beta, betas, ess, pairs, accepts = 0.0, [0.0], [], [], []
+        s = 0
+        while beta < 1.0:
+            s += 1
+            ks = prng.fold_in(key, s)
+            if self.betas is not None:
+                nb = self.betas[s - 1]
+                out = ops.temper_ess_ladder(ll, [np.float32(nb) - np.float32(beta)], ws)
+                ess.append(out)  # (read at the end of the run)
+            else:
+                nb, e = next_beta(beta, need, ess_fn)
+                ess.append(e)
+            delta = float(np.float32(np.float32(nb) - np.float32(beta)))
+            lw = ll * delta  # f32: one rounding per particle
+            anc, e_s, q_s = ops.resample("systematic", prng.fold_in(ks, 0).literal(), lw)
+            sc = fixed_scales
+            if sc is None and K > 0:
+                sc = self.population_scales(x, lw).cpu().numpy()  # (one host read)
+            x, lp, ll, acc = ops.temper_move(tplan, prng.fold_in(ks, 1), x, lp, ll, nb, K, sc, ancestors=anc)
+            pairs.append((e_s, q_s))
+            accepts.append(acc.sum())
+            beta = nb
+            betas.append(nb)
+        # one host read for the whole run: the exact (e, q) pair of every stage, the accept counts, fixed-schedule ESS sums
+        e_all = torch.cat([p[0] for p in pairs]).cpu().numpy().astype(np.int64)
+        q_all = torch.cat([p[1] for p in pairs]).cpu().numpy().astype(np.int64)
+        acc_all = torch.stack(accepts).cpu().numpy()
+        log_z = 0.0
+        for e_s, q_s in zip(e_all, q_all):
+            if q_s <= 0:
+                log_z = float("-inf")
+                break
+            log_z += int(e_s) * math.log(2.0) + math.log(int(q_s)) - 30 * math.log(2.0) - math.log(n)
+        if self.betas is not None:
+            ess = [float(ess_of(o[0], o[1])) for o in torch.stack(ess).cpu().numpy()]
+        rate = [float(a) / (n * K) if K else 0.0 for a in acc_all]
+        choices = ChoiceMap.from_mapping([(m["addr"], c) for m, c in zip(st["latents"], x)])
+        return TemperedResult(float(log_z), betas, ess, rate, choices, lp, ll, x)
+
+    # -- the SMCAlgorithm interface --------------------------------------------------------------------------------------------
+    def run_smc(self, key) -> ParticleCollection:
+        """The final population as a ParticleCollection: traces through `Target.importance` with the latent columns as
+        constraints, every log-weight f32(log Z-hat), so that logsumexp - log n reproduces the estimate."""
+        res = self.run(key)
+        n = self.n_particles
+        sub_keys = split(prng.fold_in(key, 0x7fffffff), n)
+        trs, _ = self.target.importance(sub_keys, res.choices)  # (every site is constrained: the keys draw nothing)
+        lw = torch.full((n,), float(np.float32(res.log_marginal_likelihood)), dtype=torch.float32, device=res.lp.device)
+        out = ParticleCollection(trs, lw, True)
+        out.result = res
+        return out
+
+    def log_marginal_likelihood_estimate(self, key, target: Target | None = None):
+        if target is not None:
+            return super().log_marginal_likelihood_estimate(key, target)
+        res = self.run(key)
+        return torch.tensor(float(np.float32(res.log_marginal_likelihood)), dtype=torch.float32, device=res.lp.device)
