@@ -641,21 +641,43 @@ static const BmEnt g_bm_cs[256] = GJX_BM_CS_INIT;
 #if defined(GJX_BM_LDS) && defined(__HIP_DEVICE_COMPILE__)
 __shared__ BmEnt s_bm_lg[64];
 __shared__ BmEnt s_bm_cs[256];
-GJX_DEV void bm_stage() {  // every thread of the workgroup, before its first Normal site
+// GJX_BM_BLOCK: the workgroup's size, a constant of the generated source (64, 128 or 256; defined next to GJX_BM_LDS).  Read
+// from the dispatch packet instead (blockDim.x) it was a kernel-argument trip of its own in front of the table loads, whose
+// addresses it forms; known here, the loads issue unguarded (256 / GJX_BM_BLOCK per thread of the angle table, one of the
+// radius table by the first 64 threads) and there is no copy loop for sizes that are never generated.
+#ifndef GJX_BM_BLOCK
+#error "GJX_BM_LDS needs GJX_BM_BLOCK: the size of the workgroups that call bm_stage()"
+#endif
+// Staging has two halves.  bm_issue() loads the thread's table entries into registers: the loads depend on nothing but the
+// thread's index, so a kernel that calls it first has them in flight while its arguments arrive.  BmLoads::bm_stage() waits
+// for them, writes LDS and is the workgroup's barrier.  Issued behind the argument loads' wait instead, the table loads were
+// one more memory trip of every wave's entry (profiles/entry_chain_summary.md: 9.55e10 -> 9.65e10 particles/s).  Every
+// thread of the workgroup runs both halves, once, before its first Normal site; bm_stage() is the two in one call.
+struct BmLoads {
+  BmEnt c[256 / GJX_BM_BLOCK], l;
+  GJX_DEV void bm_stage() const {
+    constexpr int BD = GJX_BM_BLOCK, K = 256 / BD;
+    const uint32_t t = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < K; ++k) s_bm_cs[t + (uint32_t)(k * BD)] = c[k];
+    if (BD == 64 || t < 64u) s_bm_lg[t] = l;
+    __syncthreads();
+  }
+};
+GJX_DEV BmLoads bm_issue() {
   // (r04: every load of the thread issued before the first is waited for — as two copy loops a 64-thread workgroup went
-  // through FIVE dependent memory trips at kernel entry, load / wait / write each; workgroups have 64, 128 or 256 threads)
-  const uint32_t t = threadIdx.x, bd = blockDim.x;
-  BmEnt c[4], l{0u, 0u};
+  // through FIVE dependent memory trips at kernel entry, load / wait / write each)
+  constexpr int BD = GJX_BM_BLOCK, K = 256 / BD;
+  static_assert(BD == 64 || BD == 128 || BD == 256, "workgroups have 64, 128 or 256 threads");
+  const uint32_t t = threadIdx.x;
+  BmLoads r;
+  r.l = BmEnt{0u, 0u};
 #pragma unroll
-  for (int k = 0; k < 4; ++k) c[k] = t + (uint32_t)k * bd < 256u ? g_bm_cs[t + (uint32_t)k * bd] : BmEnt{0u, 0u};
-  if (t < 64u) l = g_bm_lg[t];
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    if (t + (uint32_t)k * bd < 256u) s_bm_cs[t + (uint32_t)k * bd] = c[k];
-  if (t < 64u) s_bm_lg[t] = l;
-  for (uint32_t i = t + 4u * bd; i < 256u; i += bd) s_bm_cs[i] = g_bm_cs[i];  // (workgroups below 64 threads: not generated)
-  __syncthreads();
+  for (int k = 0; k < K; ++k) r.c[k] = g_bm_cs[t + (uint32_t)(k * BD)];
+  if (BD == 64 || t < 64u) r.l = g_bm_lg[t];
+  return r;
 }
+GJX_DEV void bm_stage() { bm_issue().bm_stage(); }
 #define GJX_BM_LG s_bm_lg
 #define GJX_BM_CS s_bm_cs
 #else
@@ -1521,7 +1543,8 @@ GJX_DEV void lse_store_row(int32_t* row_e, uint64_t* row_s, uint64_t row, int32_
   }
 }
 // Called by every thread of every workgroup once, after its last lse_store_row.
-GJX_DEV void lse_tail(const int32_t* row_e, const uint64_t* row_s, uint64_t n_rows, const LseTail& t) {
+// `block`, `n_blocks`: the workgroup's linear id and the number of workgroups of the launch (its grid may have two dimensions).
+GJX_DEV void lse_tail(const int32_t* row_e, const uint64_t* row_s, uint64_t n_rows, const LseTail& t, uint32_t block, uint32_t n_blocks) {
   if (!t.tickets) return;
   __shared__ uint32_t sh_last;
   // every wave drains its own stores (a workgroup of several one-wave rows has a storing lane in each wave), then the
@@ -1529,12 +1552,12 @@ GJX_DEV void lse_tail(const int32_t* row_e, const uint64_t* row_s, uint64_t n_ro
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (threadIdx.x == 0) {
-    const uint32_t shard = blockIdx.x % kLseTicketShards;
-    const uint32_t in_shard = (gridDim.x - shard + kLseTicketShards - 1) / kLseTicketShards;
+    const uint32_t shard = block % kLseTicketShards;
+    const uint32_t in_shard = (n_blocks - shard + kLseTicketShards - 1) / kLseTicketShards;
     uint32_t last = 0;
     if (__hip_atomic_fetch_add(t.tickets + shard * kLseTicketStride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
         in_shard - 1) {
-      const uint32_t n_shards = gridDim.x < (uint32_t)kLseTicketShards ? gridDim.x : (uint32_t)kLseTicketShards;
+      const uint32_t n_shards = n_blocks < (uint32_t)kLseTicketShards ? n_blocks : (uint32_t)kLseTicketShards;
       last = __hip_atomic_fetch_add(t.tickets + kLseTicketShards * kLseTicketStride, 1u, __ATOMIC_RELAXED,
                                     __HIP_MEMORY_SCOPE_AGENT) ==
                      n_shards - 1

@@ -2547,8 +2547,10 @@ static int importance_launch(const gjx_plan* p, const gjx_keys* pk, int32_t n_pa
       PlanParams prm = p->prm;
       PlanTables tabs = c.tabs;
       void* args[] = {&k, &cols, &score, &logw, &nn, &max_partials, &row_e, &row_s, &tail, &bt, &prm, &tabs};
-      const uint64_t rows = ((uint64_t)n_pass * nrows_of(n) + c.rows_per_block - 1) / c.rows_per_block;
-      if (hipModuleLaunchKernel(c.fn, (unsigned)(rows > 0x7fffffffull ? 0x7fffffffull : rows), 1, 1, (unsigned)c.block, 1, 1, 0,
+      // grid (workgroups of a pass, passes): the kernel takes its pass from blockIdx.y and its row from blockIdx.x; the
+      // dispatcher hands workgroups out x fastest, i.e. pass after pass as the linear grid did
+      const uint64_t rows = (nrows_of(n) + c.rows_per_block - 1) / c.rows_per_block;
+      if (hipModuleLaunchKernel(c.fn, (unsigned)(rows > 0x7fffffffull ? 0x7fffffffull : rows), (unsigned)n_pass, 1, (unsigned)c.block, 1, 1, 0,
                                 S(s), args, nullptr) != hipSuccess)
         return GJX_ERR_LAUNCH;
       return launch_status();

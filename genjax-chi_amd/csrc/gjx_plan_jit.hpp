@@ -512,9 +512,10 @@ struct SiteEmitter {
   }
 };
 
-// bm_lds: the kernels of this source stage the Box-Muller tables in LDS (each calls bm_stage() at entry; gjx_device.hpp)
-inline void emit_prelude(std::ostringstream& o, bool fast_math = false, bool bm_lds = false) {
-  if (bm_lds) o << "#define GJX_BM_LDS 1\n";
+// bm_lds: the kernels of this source stage the Box-Muller tables in LDS (each calls bm_stage() at entry; gjx_device.hpp),
+// `block` threads per workgroup (a constant of the source: bm_stage forms its table addresses from it)
+inline void emit_prelude(std::ostringstream& o, bool fast_math = false, bool bm_lds = false, int block = 0) {
+  if (bm_lds) o << "#define GJX_BM_LDS 1\n#define GJX_BM_BLOCK " << block << "\n";
   if (fast_math) o << "#define GJX_FAST_MATH 1\n";  // gjx.h GJX_PLAN_FAST_MATH: hardware transcendentals (gjx_device.hpp d_exp / bm_pair)
   o << "#include \"gjx_device.hpp\"\nusing namespace gjx;\n";
   o << "__device__ __forceinline__ float jrow_max(const float* l, uint32_t K){ float m=l[0]; for(uint32_t c=1;c<K;++c) m = l[c]>m?l[c]:m; return m; }\n";
@@ -707,8 +708,17 @@ struct Gen {
   const char* tail_scope() const { return fused_tail ? "tail.tickets != nullptr" : "false"; }
   void emit_tail() {
     o << "  }\n";
-    if (fused_tail) o << "  if (row_e) lse_tail(row_e, row_s, (n + 255) / 256, tail);\n";
+    // (one ticket per workgroup of the two-dimensional grid: its linear id, x fastest, and the count of all of them)
+    if (fused_tail) o << "  if (row_e) lse_tail(row_e, row_s, (n + 255) / 256, tail, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);\n";
     o << "}\n";
+  }
+  // The grid is (rows of a pass / R, passes): a workgroup's pass is blockIdx.y and its first row blockIdx.x — known to the
+  // dispatcher, so the kernel divides nothing, and the address of the pass's parent key (bt.parent[pass], in the kernel
+  // argument block) is known at the first instruction: its load goes out with the other arguments'.  The loop over x is for
+  // rows beyond the grid limit (2^31 - 1 workgroups of 256 particles: dead at any size that fits in memory).
+  void emit_pass_key() {
+    o << "  const uint32_t pass = blockIdx.y, grid_x = gridDim.x;  // (pass < bt.n_pass <= kMaxPasses: the host launches n_pass rows of workgroups)\n";
+    o << "  const uint32_t bk0 = bt.parent[pass][0], bk1 = bt.parent[pass][1];\n";
   }
 
   std::string run_paired() {
@@ -727,15 +737,19 @@ struct Gen {
     // the quad form's stores: one wave-uniform base per column and row (scalar registers) plus ONE per-lane byte offset
     // (gjx_device.hpp store16_at); the four-row workgroup of the estimate-only kernel has no block-uniform row
     const bool ubase = NP == 2 && R == 1;
-    emit_prelude(o, fast_math, bm_lds());
+    emit_prelude(o, fast_math, bm_lds(), block);
     emit_hint_default();
     o << "extern \"C\" __global__ " << bounds(block) << " void " << kname() << signature();
     if (waves_per_row > 1) o << "  __shared__ float sh_red[" << waves_per_row * R << "];\n  __shared__ uint64_t sh_sum[" << waves_per_row * R << "];\n";
     if (R == 1) o << "  const int wv = threadIdx.x >> 6, pr = 0, tr = threadIdx.x;  // (block-uniform row: the cipher key stays scalar)\n";
     else o << "  const int wv = threadIdx.x >> 6, pr = threadIdx.x / " << lanes_per_row << ", tr = threadIdx.x % " << lanes_per_row << ";\n";
     o << "  (void)wv;\n";
-    // the kernel's scalar arguments in ONE round of loads (gjx_device.hpp: resample_args_anchor has the measurement)
-    o << "  asm volatile(\"\" :: \"s\"(n), \"s\"(score), \"s\"(logw), \"s\"(max_partials), \"s\"(row_e), \"s\"(row_s), \"s\"(bt.n_pass), \"s\"(bt.rows_per_pass), \"s\"(bt.pass_stride), \"s\"(bt.row_stride), \"s\"(ks.first), \"s\"(ks.parent.k0), \"s\"(ks.parent.k1)"
+    // the Box-Muller tables' loads first (they wait for no argument: gjx_device.hpp bm_issue), then the kernel's scalar
+    // arguments in ONE round of loads (gjx_device.hpp: resample_args_anchor has the measurement), the pass's parent key among
+    // them: one wait for both
+    if (bm_lds()) o << "  const BmLoads bm_loads = bm_issue();\n";
+    emit_pass_key();
+    o << "  asm volatile(\"\" :: \"s\"(n), \"s\"(score), \"s\"(logw), \"s\"(max_partials), \"s\"(row_e), \"s\"(row_s), \"s\"(bt.n_pass), \"s\"(bt.rows_per_pass), \"s\"(bt.pass_stride), \"s\"(bt.row_stride), \"s\"(ks.first), \"s\"(ks.parent.k0), \"s\"(ks.parent.k1), \"s\"(bk0), \"s\"(bk1), \"s\"(grid_x)"
       << (fused_tail ? ", \"s\"(tail.tickets)" : "") << ");\n";
     {
       bool seen[64] = {};  // ... and the value columns this plan stores (RunCols::out has 64)
@@ -745,17 +759,18 @@ struct Gen {
           o << "  asm volatile(\"\" :: \"s\"(cols.out[" << sites[q].out_col << "]));\n";
         }
     }
-    if (bm_lds()) o << "  bm_stage();\n";
-    o << "  const uint64_t rows_all = (uint64_t)bt.n_pass * bt.rows_per_pass;\n";
+    if (bm_lds()) o << "  bm_loads.bm_stage();\n";
     o << "  const bool wt_one_pass = " << (wt_stores ? "true" : "false") << "; (void)wt_one_pass;  // (Gen::wt_stores)\n";
-    o << "  for (uint64_t g0 = (uint64_t)blockIdx.x * " << R << "; g0 < rows_all; g0 += (uint64_t)gridDim.x * " << R << ") {\n";
-    o << "    const uint64_t gr = g0 + pr;\n";
-    o << "    const uint32_t pass = (uint32_t)(gr / bt.rows_per_pass);\n";
-    o << "    const uint64_t row = gr - (uint64_t)pass * bt.rows_per_pass;\n";
-    o << "    const bool live_row = gr < rows_all;\n";
-    o << "    const uint32_t pk0 = bt.n_pass > 1 ? bt.parent[pass < bt.n_pass ? pass : 0][0] : ks.parent.k0;\n";
-    o << "    const uint32_t pk1 = bt.n_pass > 1 ? bt.parent[pass < bt.n_pass ? pass : 0][1] : ks.parent.k1;\n";
-    o << "    const uint64_t po = (uint64_t)pass * bt.pass_stride, ro = (uint64_t)pass * bt.row_stride;  // this pass's outputs\n";
+    o << "  const uint32_t pk0 = bt.n_pass > 1 ? bk0 : ks.parent.k0, pk1 = bt.n_pass > 1 ? bk1 : ks.parent.k1;\n";
+    o << "  const uint64_t po = (uint64_t)pass * bt.pass_stride, ro = (uint64_t)pass * bt.row_stride;  // this pass's outputs\n";
+    o << "  for (uint64_t g0 = (uint64_t)blockIdx.x * " << R << "; g0 < bt.rows_per_pass; g0 += (uint64_t)grid_x * " << R << ") {\n";
+    o << "    const uint64_t row = g0 + pr;\n";
+    o << "    const bool live_row = row < bt.rows_per_pass;  // (the four-row workgroup: the dead rows at the end of a pass)\n";
+    // the row's index in the per-row arrays.  (The one-row quad form makes it opaque per row: folded into the three arrays'
+    // bases it is hoisted out of the row loop as an address pair and a stride pair each, and with the cipher's round keys in
+    // scalar registers that was more than fit — a pair spilled to VGPR lanes and read back for every row.)
+    o << "    uint64_t rrow = ro + row;\n";
+    if (NP == 2 && R == 1) o << "    asm volatile(\"\" : \"+s\"(rrow));\n";
     const char* sfx[4] = {"A", "B", "C", "D"};
     const int P = 2 * NP;  // particles per lane
     o << "    const uint64_t iA = row * 256 + " << P << " * (uint64_t)tr;\n";
@@ -817,7 +832,7 @@ struct Gen {
     // (v_bitop3_b32 reads them in place, gjx_device.hpp xor3) the allocator spilled that pair to a 65th VGPR — one more than
     // eight waves per SIMD allow.  One v_cmp per row instead.
     const char* lane0 = ubase ? "lb == 0u" : "tr == 0";
-    o << "      if (max_partials && " << lane0 << " && live_row) max_partials[ro + row] = bm;\n";
+    o << "      if (max_partials && " << lane0 << " && live_row) max_partials[rrow] = bm;\n";
     o << "      if (row_e) {\n";
     o << "        const int32_t eb = row_anchor(bm);\n";
     {
@@ -829,7 +844,7 @@ struct Gen {
       o << "        __syncthreads();\n        if ((threadIdx.x & 63) == 0) sh_sum[wv] = sb;\n        __syncthreads();\n";
       o << "        sb = sh_sum[2 * pr] + sh_sum[2 * pr + 1];\n";
     }
-    o << "        if (" << lane0 << " && live_row) lse_store_row(row_e, row_s, ro + row, eb, sb, " << tail_scope() << ");\n";
+    o << "        if (" << lane0 << " && live_row) lse_store_row(row_e, row_s, rrow, eb, sb, " << tail_scope() << ");\n";
     o << "      }\n    }\n";
     emit_tail();
     return o.str();
@@ -838,20 +853,19 @@ struct Gen {
   std::string run() {
     if (laned && impl == 1) return run_paired();
     const std::string I = std::to_string(impl);
-    emit_prelude(o, fast_math, bm_lds());
+    emit_prelude(o, fast_math, bm_lds(), 256);
     emit_hint_default();
     // One workgroup per 256-particle row (grid-stride): short blocks keep every SIMD's wave slots
     // full even at 1e6 particles (15 rows per lane), where a 4-row block would serialise its rows.
     o << "extern \"C\" __global__ " << bounds(256) << " void " << kname() << signature();
     o << "  __shared__ float sh_red[4];\n  __shared__ uint64_t sh_sum[4];\n";
+    emit_pass_key();
+    o << "  asm volatile(\"\" :: \"s\"(bk0), \"s\"(bk1), \"s\"(grid_x));\n";
     if (bm_lds()) o << "  bm_stage();\n";
-    o << "  const uint64_t rows_all = (uint64_t)bt.n_pass * bt.rows_per_pass;\n";
-    o << "  for (uint64_t gr = blockIdx.x; gr < rows_all; gr += gridDim.x) {\n";
-    o << "    const uint32_t pass = (uint32_t)(gr / bt.rows_per_pass);\n";
-    o << "    const uint64_t row = gr - (uint64_t)pass * bt.rows_per_pass;\n";
-    o << "    const uint64_t po = (uint64_t)pass * bt.pass_stride, ro = (uint64_t)pass * bt.row_stride;\n";
-    o << "    KeySrc kp = ks;\n";
-    o << "    if (bt.n_pass > 1) { kp.parent.k0 = bt.parent[pass][0]; kp.parent.k1 = bt.parent[pass][1]; }\n";
+    o << "  const uint64_t po = (uint64_t)pass * bt.pass_stride, ro = (uint64_t)pass * bt.row_stride;\n";
+    o << "  KeySrc kp = ks;\n";
+    o << "  if (bt.n_pass > 1) { kp.parent.k0 = bk0; kp.parent.k1 = bk1; }\n";
+    o << "  for (uint64_t row = blockIdx.x; row < bt.rows_per_pass; row += grid_x) {\n";
     o << "    float tmax = -__builtin_inff();\n    bool live = false;\n";
     o << "    {\n";
     o << "      const uint64_t li = row * 256 + threadIdx.x, i = po + li;\n";
@@ -900,7 +914,7 @@ struct GenScan {
   const char* tail_scope() const { return fused_tail ? "tail.tickets != nullptr" : "false"; }
   void emit_tail() {
     o << "  }\n";
-    if (fused_tail) o << "  if (row_e) lse_tail(row_e, row_s, (n + 255) / 256, tail);\n";
+    if (fused_tail) o << "  if (row_e) lse_tail(row_e, row_s, (n + 255) / 256, tail, blockIdx.x, gridDim.x);\n";
     o << "}\n";
   }
   const char* kname() const { return impl == 0 ? "gjx_scan_kernel_threefry" : "gjx_scan_kernel_philox"; }
@@ -915,7 +929,7 @@ struct GenScan {
     block = 64;
     const char* sfx[4] = {"A", "B", "C", "D"};
     const int P = 4;
-    emit_prelude(o, fast_math, bm_lds());
+    emit_prelude(o, fast_math, bm_lds(), block);
     o << "struct StepObs { const float* obs; };\n";
     o << "extern \"C\" __global__ __launch_bounds__(64) void " << kname()
       << "(KeySrc ks, RunCols cols, ScanArgs sa, float* score, float* logw, float* max_partials, int32_t* row_e, uint64_t* row_s, LseTail tail, PlanTables tabs) {\n";
@@ -977,7 +991,7 @@ struct GenScan {
   std::string run() {
     if (quad && impl == 1) return run_quad();
     const std::string I = std::to_string(impl);
-    emit_prelude(o, fast_math, bm_lds());
+    emit_prelude(o, fast_math, bm_lds(), 256);
     o << "struct StepObs { const float* obs; };\n";
     o << "extern \"C\" __global__ __launch_bounds__(256) void " << kname()
       << "(KeySrc ks, RunCols cols, ScanArgs sa, float* score, float* logw, float* max_partials, int32_t* row_e, uint64_t* row_s, LseTail tail, PlanTables tabs) {\n";

@@ -15,7 +15,7 @@ timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/
   || { echo "trace run failed"; tail -5 "$OUT/trace.log"; exit 1; }
 timeout -k 10 400 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d "$OUT/pmc1" -o p -- python bench.py > "$OUT/pmc1.log" 2>&1 \
   || { echo "counter run 1 failed"; tail -5 "$OUT/pmc1.log"; exit 1; }
-timeout -k 10 400 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAIT_INST_ANY --output-format csv -d "$OUT/pmc2" -o p -- python bench.py > "$OUT/pmc2.log" 2>&1 \
+timeout -k 10 400 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAIT_INST_ANY --output-format csv -d "$OUT/pmc2" -o p -- python bench.py > "$OUT/pmc2.log" 2>&1 \
   || { echo "counter run 2 failed"; tail -5 "$OUT/pmc2.log"; exit 1; }
 python3 profiles/summarize_occupancy.py "$TAG" "$OUT" "$OUT/summary.json" && cat "$OUT/summary.json"
 # the raw per-dispatch tables are large: the summary is what is kept

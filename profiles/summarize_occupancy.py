@@ -32,7 +32,9 @@ def newest(pattern):
 durs, vg = collections.defaultdict(list), {}
 for r in csv.DictReader(open(newest("trace/**/*kernel_trace.csv"))):
     if KERNEL in r["Kernel_Name"]:
-        g = int(r["Grid_Size_X"])
+        # (threads of the whole grid: an importance launch is (rows of a pass, passes) workgroups, so x alone is the same for
+        # launches of any number of passes; the counter tables' Grid_Size is the whole grid as well)
+        g = int(r["Grid_Size_X"]) * int(r.get("Grid_Size_Y") or 1) * int(r.get("Grid_Size_Z") or 1)
         durs[g].append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
         vg[g] = int(r["VGPR_Count"])
 grid = max(durs, key=lambda g: len(durs[g]))  # the timed launches (32 passes each)
@@ -65,6 +67,8 @@ if {"SQ_WAVES", "SQ_WAVE_CYCLES", "SQ_INSTS_VALU"} <= set(c):
     res["resident_waves_per_simd_average"] = 4.0 * c["SQ_WAVE_CYCLES"] / (cycles * N_SIMD)
     res["cycles_per_valu_instruction_per_simd"] = cycles * N_SIMD / c["SQ_INSTS_VALU"]
     res["valu_instructions_per_wave"] = c["SQ_INSTS_VALU"] / c["SQ_WAVES"]
+if {"SQ_WAVES", "SQ_INSTS_SALU"} <= set(c):
+    res["salu_instructions_per_wave"] = c["SQ_INSTS_SALU"] / c["SQ_WAVES"]
 if {"SQ_WAIT_INST_ANY", "SQ_WAVE_CYCLES"} <= set(c):
     res["waiting_fraction_of_wave_cycles"] = c["SQ_WAIT_INST_ANY"] / c["SQ_WAVE_CYCLES"]
 res["note"] = (f"durations from the trace run, counters from the counter runs (kernels serialised); cycles = duration x {CLOCK_HZ / 1e9} GHz; "
