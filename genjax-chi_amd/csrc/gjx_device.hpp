@@ -1016,6 +1016,86 @@ GJX_HD float gumbel_from_bits(uint32_t bits) {
   return -m_log(-m_log(u));
 }
 
+// ---- categorical sites of the generated kernels (gjx_plan_jit.hpp SiteEmitter calls these by name) ------------------
+#if defined(__HIP_DEVICE_COMPILE__)
+GJX_DEV float jrow_max(const float* l, uint32_t K) {
+  float m = l[0];
+  for (uint32_t c = 1; c < K; ++c) m = l[c] > m ? l[c] : m;
+  return m;
+}
+GJX_DEV float jrow_lse(const float* l, uint32_t K) {
+  const float m = jrow_max(l, K);
+  float acc = 0.0f;
+  for (uint32_t c = 0; c < K; ++c) acc = acc + m_exp(l[c] - m);
+  return m + m_log(acc);
+}
+// inverse CDF over the row's fixed-point weights: the first class whose running sum is above bits * Q / 2^32
+GJX_DEV int32_t jcat_invcdf(const float* l, uint32_t K, uint32_t bits) {
+  const float m = jrow_max(l, K);
+  uint64_t Q = 0;
+  for (uint32_t c = 0; c < K; ++c) Q += cat_fix(l[c], m);
+  const uint64_t thr = ((uint64_t)bits * Q) >> 32;
+  uint64_t C = 0;
+  for (uint32_t c = 0; c < K; ++c) {
+    C += cat_fix(l[c], m);
+    if (C > thr) return (int32_t)c;
+  }
+  return (int32_t)(K - 1);
+}
+// the guide bucket: one scattered 16-byte load per draw from a table of up to 2 MB (L2-resident).  As a BUFFER load
+// (resource anchored 1 GiB below the first lane's address; every lane of the wave reads the same table, so all offsets
+// are in range) the scan of the 256-state HMM runs 4.02 -> 2.39 ms per 5e8 particle-steps against the same load as
+// global_load_dwordx4; the sc0 / sc1 bits make no further difference, a non-temporal global load is 2x slower and an
+// agent-scope pair of 8-byte loads is even (profiles/r04_ab/README.md).
+typedef unsigned jv4u_t __attribute__((ext_vector_type(4)));
+GJX_DEV uint4 jguide_load(const uint4* p) {
+  const uint64_t a = (uint64_t)(uintptr_t)p;
+  const uint64_t first = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32)) << 32) |
+                         (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a);
+  const uint64_t base = first - (1ull << 30);
+  __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)base, 0, 0x7fffffff, 0x00020000);
+  const jv4u_t v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(uint32_t)(a - base), 0, 0);
+  return make_uint4(v[0], v[1], v[2], v[3]);
+}
+// ... through the guide: bucket bits >> sh names the first two candidate classes and their log-probability bits; a bucket
+// that spans more classes walks the (cumulative weight, log-probability bits) entries from the second candidate on
+GJX_DEV int32_t jcat_invcdf_gb(const uint4* guide, const uint2* ent, uint32_t K, uint32_t bits, int sh, uint32_t& lpb) {
+  const uint4 g = jguide_load(guide + (bits >> sh));
+  const uint32_t c0 = g.y & 511u, c1 = (g.y >> 9) & 511u;
+  if (bits <= g.x) {
+    lpb = g.z;
+    return (int32_t)c0;
+  }
+  if (!(g.y >> 18)) {
+    lpb = g.w;
+    return (int32_t)c1;
+  }
+  const uint64_t thr = ((uint64_t)bits * (uint64_t)ent[K - 1].x) >> 32;
+  uint32_t c = c1;
+  uint2 e = ent[c];
+  while (c < K - 1 && (uint64_t)e.x <= thr) {
+    ++c;
+    e = ent[c];
+  }
+  lpb = e.y;
+  return (int32_t)c;
+}
+// Gumbel-max over the row: class c perturbed by word c of the site's stream, the first maximiser wins
+template <int IMPL>
+GJX_DEV int32_t jcat_gumbel(const float* l, uint32_t K, const Stream<IMPL>& st) {
+  int32_t best = 0;
+  float bv = -__builtin_inff();
+  for (uint32_t c = 0; c < K; ++c) {
+    const float v = l[c] + gumbel_from_bits(st.bits32(c));
+    if (v > bv || c == 0) {
+      bv = v;
+      best = (int32_t)c;
+    }
+  }
+  return best;
+}
+#endif  // __HIP_DEVICE_COMPILE__
+
 // Systematic comb: number of teeth (j + u0), j in [0, n_out), strictly below mass C * scale.
 GJX_HD int64_t teeth_below(uint64_t C, double scale, double u0, int64_t n_out) {
   const double P = (double)C * scale;
@@ -1667,6 +1747,181 @@ struct TemperArgs {
   uint32_t n_moves;
   uint32_t recompute;
 };
+
+// ---- the fixed device code of the backward-simulation and backward-move kernels ---------------------------------------
+// What the site table decides reaches it as template arguments: the generator, the number of carry components D, and a
+// generated struct whose static member is the table's walk — Trans::trans_lp(a, tabs, st, nx), the f32 sum of the transition
+// table's log-densities from state st[D] to next state nx[D] (gjx_plan_jit.hpp emit_trans_struct).  The backward-simulation
+// entry points are one instantiation of backsim_body each; the backward-move kernels keep their loop over paths in the
+// generated source (GenBackmove says why) and call the backmove_* templates from it.
+#if defined(__HIP_DEVICE_COMPILE__)
+GJX_DEV float backsim_col(uint32_t bits, bool is_i32) { return is_i32 ? (float)(int32_t)bits : u2f(bits); }
+
+// One backward-simulation step.  Lanes over candidates, two adjacent ones per lane (8-byte loads of state and log-weight,
+// once per work item); a work item = kBacksimBlock trajectories x one chunk of candidates: the trajectories' keys and
+// next-state values are wave-uniform (scalar registers), each lane keeps (best value, best index) per trajectory and
+// candidate order is ascending inside a lane, so `v > best || i == 0` is the oracle's own scan there; at the end of the item
+// one DPP wave maximum per trajectory over the packed word (backsim_pack) and one 64-bit atomic maximum per wave and
+// trajectory: order-free and exact.  A trajectory index past m is clamped to m - 1: its (identical) maxima change nothing.
+// LAST: the final step has no next state — the candidates' log-weights alone.
+template <int IMPL, int D, class Trans, bool LAST>
+GJX_DEV void backsim_body(const BacksimArgs& a, const PlanTables& tabs) {
+  constexpr int JB = kBacksimBlock;
+  const uint32_t n = a.n, m = a.m;
+  const uint32_t n_tb = (m + JB - 1) / JB;
+  const uint64_t items = (uint64_t)n_tb * a.n_chunks;
+  for (uint64_t it = blockIdx.x; it < items; it += gridDim.x) {
+    const uint32_t tb = (uint32_t)(it / a.n_chunks), cc = (uint32_t)(it - (uint64_t)tb * a.n_chunks);
+    Key tk[JB];
+    float nx[JB][D];
+    uint32_t tj[JB];
+#pragma unroll
+    for (int u = 0; u < JB; ++u) {
+      const uint32_t j = tb * JB + u < m ? tb * JB + u : m - 1u;
+      tj[u] = j;
+      tk[u] = split_at<IMPL>(a.kt, (uint64_t)j);
+      for (int c = 0; c < D; ++c) nx[u][c] = 0.0f;
+      if (!LAST) {
+        const uint32_t w = backsim_index(a.best_next[j], n);
+        for (int c = 0; c < D; ++c) nx[u][c] = backsim_col(a.col_next[c][w], (a.i32_mask >> c) & 1u);
+      }
+    }
+    float bv[JB];
+    uint32_t bi[JB];
+#pragma unroll
+    for (int u = 0; u < JB; ++u) { bv[u] = -__builtin_inff(); bi[u] = 0x7fffffffu; }
+    const uint64_t c0 = (uint64_t)cc * a.chunk;
+    const uint64_t c1 = c0 + a.chunk < n ? c0 + a.chunk : n;
+    for (uint64_t i64 = c0 + 2u * threadIdx.x; i64 < c1; i64 += 2u * blockDim.x) {
+      const uint32_t i = (uint32_t)i64;
+      const bool hasb = i + 1u < n;
+      float sa[D], sb[D], lwa, lwb;
+      if (a.vec2 && hasb) {
+        const uint2 l2 = *reinterpret_cast<const uint2*>(a.lw + i);
+        lwa = u2f(l2.x); lwb = u2f(l2.y);
+        for (int c = 0; c < D; ++c) {
+          const uint2 v2 = *reinterpret_cast<const uint2*>(a.col[c] + i);
+          sa[c] = backsim_col(v2.x, (a.i32_mask >> c) & 1u); sb[c] = backsim_col(v2.y, (a.i32_mask >> c) & 1u);
+        }
+      } else {
+        lwa = a.lw[i]; lwb = hasb ? a.lw[i + 1u] : -__builtin_inff();
+        for (int c = 0; c < D; ++c) {
+          sa[c] = backsim_col(a.col[c][i], (a.i32_mask >> c) & 1u);
+          sb[c] = hasb ? backsim_col(a.col[c][i + 1u], (a.i32_mask >> c) & 1u) : sa[c];
+        }
+      }
+      const bool first = i == 0u;
+#pragma unroll
+      for (int u = 0; u < JB; ++u) {
+        const Stream<IMPL> ds(tk[u], false, 0u);
+        const float la = LAST ? lwa : lwa + Trans::trans_lp(a, tabs, sa, nx[u]);
+        const float lb = LAST ? lwb : lwb + Trans::trans_lp(a, tabs, sb, nx[u]);
+        const float va = la + gumbel_from_bits(ds.bits32(i));
+        const float vb = lb + gumbel_from_bits(ds.bits32(i + 1u));
+        if (va > bv[u] || first) { bv[u] = va; bi[u] = i; }
+        if (hasb && vb > bv[u]) { bv[u] = vb; bi[u] = i + 1u; }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < JB; ++u) {
+      const unsigned long long w = wave_last_u64(wave_scan_u64(backsim_pack(bv[u], bi[u]), 0ull,
+          [](uint64_t x, uint64_t y) { return x > y ? x : y; }));
+      if ((threadIdx.x & 63u) == 0u) atomicMax(a.best + tj[u], w);
+    }
+  }
+}
+
+// The MCMC backward sampler over the same transition table: a LATENCY kernel — one lane per path, and per move a CDF search
+// (dependent reads), a random gather of the proposal's state and one transition density.  None of that depends on the
+// chain's state, so a path's moves are issued in blocks of 4 / 2 / 1 INDEPENDENT chains (backmove_moves<B>: the B searches
+// advance in lockstep, one load each per round, a wave-uniform trip count — a finished search repeats its last read and
+// changes nothing); only the B compare-and-select steps at the end of a block are serial.
+//   search   backmove_search returns cdf_upper_bound's index (gjx_hip.hip): the same halving of [lo, hi], run
+//            ceil(log2(size)) times.  Two levels when a.coarse: the CDF's tile ends (entry 1024 k + 1023, the last one for
+//            the ragged tile) staged in LDS once per workgroup, then at most 10 rounds inside one 8 KB tile.  The CDF is
+//            non-decreasing, so the first entry above thr lies in the first tile whose END is above thr (the last tile if
+//            none is).
+//   keys     a.pk / a.ak have lane 0: under PHILOX the cipher key of every proposal and every uniform is wave-uniform.
+template <int D, class Trans>
+GJX_DEV float backmove_score(const BackmoveArgs& a, const PlanTables& tabs, uint32_t i, const float (&nx)[D]) {
+  float st[D];
+  for (int c = 0; c < D; ++c) st[c] = backsim_col(a.col[c][i], (a.i32_mask >> c) & 1u);
+  return Trans::trans_lp(a, tabs, st, nx);
+}
+GJX_DEV int backmove_steps(uint32_t size) { return size > 1u ? 32 - __builtin_clz(size - 1u) : 0; }
+template <int B>
+GJX_DEV void backmove_search(const uint64_t* c, uint32_t (&lo)[B], uint32_t (&hi)[B], const uint64_t (&thr)[B], int steps) {
+  for (int it = 0; it < steps; ++it) {
+    uint32_t mid[B];
+    uint64_t v[B];
+#pragma unroll
+    for (int u = 0; u < B; ++u) { mid[u] = lo[u] + ((hi[u] - lo[u]) >> 1); v[u] = c[mid[u]]; }
+#pragma unroll
+    for (int u = 0; u < B; ++u)
+      if (lo[u] < hi[u]) { if (v[u] > thr[u]) hi[u] = mid[u]; else lo[u] = mid[u] + 1u; }
+  }
+}
+GJX_DEV uint32_t backmove_tile_end(uint32_t k, uint32_t n) {
+  const uint32_t e = (k + 1u) * kBackmoveTile;
+  return (e < n ? e : n) - 1u;
+}
+// the CDF's tile ends into `ends` (LDS, kBackmoveLdsTiles entries); called by every thread of the workgroup
+GJX_DEV void backmove_stage(const BackmoveArgs& a, uint64_t* ends) {
+  const uint32_t nt = (a.n + kBackmoveTile - 1u) / kBackmoveTile;
+  for (uint32_t k = threadIdx.x; k < nt; k += blockDim.x) ends[k] = a.cdf[backmove_tile_end(k, a.n)];
+  __syncthreads();
+}
+// elements e[u] of the multinomial draw under a.pk: out[u] = the first i with cdf[i] > mulhi64(bits64(e[u]), Q)
+template <int IMPL, int B>
+GJX_DEV void backmove_draw(const BackmoveArgs& a, const uint64_t* ends, uint64_t Q, const uint32_t (&e)[B], uint32_t (&out)[B]) {
+  const Stream<IMPL> ps(a.pk, false, 0u);
+  const uint32_t n = a.n;
+  uint64_t thr[B];
+  uint32_t hi[B];
+#pragma unroll
+  for (int u = 0; u < B; ++u) { thr[u] = __umul64hi(ps.bits64(e[u]), Q); out[u] = 0u; }
+  if (a.coarse) {
+    const uint32_t nt = (n + kBackmoveTile - 1u) / kBackmoveTile;
+#pragma unroll
+    for (int u = 0; u < B; ++u) hi[u] = nt - 1u;
+    backmove_search<B>(ends, out, hi, thr, backmove_steps(nt));
+#pragma unroll
+    for (int u = 0; u < B; ++u) { hi[u] = backmove_tile_end(out[u], n); out[u] *= kBackmoveTile; }
+    backmove_search<B>(a.cdf, out, hi, thr, backmove_steps(n < kBackmoveTile ? n : kBackmoveTile));
+  } else {
+#pragma unroll
+    for (int u = 0; u < B; ++u) hi[u] = n - 1u;
+    backmove_search<B>(a.cdf, out, hi, thr, backmove_steps(n));
+  }
+}
+// moves r0 .. r0 + B - 1 of path j
+template <int IMPL, int D, class Trans, int B>
+GJX_DEV void backmove_moves(const BackmoveArgs& a, const PlanTables& tabs, const uint64_t* ends, uint64_t Q, uint32_t j, uint32_t r0,
+                            const float (&nx)[D], uint32_t& cur, float& s_cur) {
+  uint32_t e[B], pr[B];
+  float sp[B], lg[B];
+#pragma unroll
+  for (int u = 0; u < B; ++u) e[u] = (r0 + (uint32_t)u) * a.m + j;
+  backmove_draw<IMPL, B>(a, ends, Q, e, pr);
+#pragma unroll
+  for (int u = 0; u < B; ++u) {
+    sp[u] = backmove_score<D, Trans>(a, tabs, pr[u], nx);
+    const Stream<IMPL> as(split_at<IMPL>(a.ak, (uint64_t)e[u]), false, 0u);
+    lg[u] = m_log(uniform01(as.bits32(0u)));
+  }
+#pragma unroll
+  for (int u = 0; u < B; ++u) {
+    const float d = sp[u] - s_cur;
+    if (d >= 0.0f || lg[u] < d) { cur = pr[u]; s_cur = sp[u]; }
+  }
+}
+template <int D>
+GJX_DEV void backmove_store(const BackmoveArgs& a, uint32_t j, uint32_t i) {
+  a.lin[j] = (int32_t)i;
+  for (int c = 0; c < D; ++c)
+    if (a.path[c]) a.path[c][j] = a.col[c][i];
+}
+#endif  // __HIP_DEVICE_COMPILE__
 
 template <int N>
 struct IntC {

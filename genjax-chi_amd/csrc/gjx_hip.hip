@@ -34,6 +34,15 @@ namespace {
 
 inline int launch_status() { return hipGetLastError() == hipSuccess ? GJX_OK : GJX_ERR_LAUNCH; }
 inline hipStream_t S(gjx_stream s) { return reinterpret_cast<hipStream_t>(s); }
+// One launch of a generated kernel (a gx x gy grid of `block` threads).  A refused launch leaves its error with the runtime:
+// cleared here, or the next call's launch_status() would report it again.
+inline int launch_generated(hipFunction_t fn, uint64_t gx, unsigned gy, unsigned block, gjx_stream s, void** args) {
+  if (hipModuleLaunchKernel(fn, (unsigned)gx, gy, 1, block, 1, 1, 0, S(s), args, nullptr) != hipSuccess) {
+    (void)hipGetLastError();
+    return GJX_ERR_LAUNCH;
+  }
+  return launch_status();
+}
 inline uint64_t ntiles_of(uint64_t n) { return (n + kTile - 1) / kTile; }
 inline uint64_t nrows_of(uint64_t n) { return (n + kBlock - 1) / kBlock; }  // max-partial granularity
 inline unsigned grid_for(uint64_t n) {
@@ -2550,10 +2559,7 @@ static int importance_launch(const gjx_plan* p, const gjx_keys* pk, int32_t n_pa
       // grid (workgroups of a pass, passes): the kernel takes its pass from blockIdx.y and its row from blockIdx.x; the
       // dispatcher hands workgroups out x fastest, i.e. pass after pass as the linear grid did
       const uint64_t rows = (nrows_of(n) + c.rows_per_block - 1) / c.rows_per_block;
-      if (hipModuleLaunchKernel(c.fn, (unsigned)(rows > 0x7fffffffull ? 0x7fffffffull : rows), (unsigned)n_pass, 1, (unsigned)c.block, 1, 1, 0,
-                                S(s), args, nullptr) != hipSuccess)
-        return GJX_ERR_LAUNCH;
-      return launch_status();
+      return launch_generated(c.fn, rows > 0x7fffffffull ? 0x7fffffffull : rows, (unsigned)n_pass, (unsigned)c.block, s, args);
     }
   }
   if (p->has_expr || p->scopes.n_scopes > 0) return GJX_ERR_UNSUPPORTED;  // programs and nested calls are compiled, never interpreted
@@ -3334,7 +3340,6 @@ int gjx_scan_plan_destroy(gjx_scan_plan* p) {
 }
 static std::string scan_plan_source(const gjx_scan_plan* plan, int impl, const char** kname = nullptr, PlanTables* tabs = nullptr,
                                     bool quad = false, int* block = nullptr, bool fused_tail = false) {
-  gjx_jit::TableScope ts;
   gjx_jit::GenScan<CSite, CArg> g;
   g.impl = impl; g.sites = plan->step; g.n_sites = plan->n_step; g.next_state = plan->next_state;
   g.n_state = plan->n_state; g.n_obs = plan->n_obs; g.fast_math = (plan->flags & GJX_PLAN_FAST_MATH) != 0;
@@ -3342,8 +3347,7 @@ static std::string scan_plan_source(const gjx_scan_plan* plan, int impl, const c
   g.fused_tail = fused_tail;
   g.sc = plan->scopes.n_scopes > 0 ? &plan->scopes : nullptr;
   if (kname) *kname = g.kname();
-  std::string src = g.run();
-  if (tabs) *tabs = ts.reg.tables();
+  std::string src = gjx_jit::generated_source(g, tabs);
   if (block) *block = g.block;
   return src;
 }
@@ -3411,10 +3415,7 @@ int gjx_scan_run(gjx_scan_plan* p, const gjx_scan_io* io, gjx_stream s) {
   PlanTables tabs = c.tabs;
   void* args[] = {&k, &cols, &sa, &score, &logw, &mp, &row_e, &row_s, &tail, &tabs};
   const uint64_t rows = nrows_of(io->n);
-  if (hipModuleLaunchKernel(c.fn, (unsigned)(rows > 0x7fffffffull ? 0x7fffffffull : rows), 1, 1, (unsigned)c.block, 1, 1, 0, S(s), args,
-                            nullptr) != hipSuccess)
-    return GJX_ERR_LAUNCH;
-  return launch_status();
+  return launch_generated(c.fn, rows > 0x7fffffffull ? 0x7fffffffull : rows, 1, (unsigned)c.block, s, args);
 }
 
 // ---- bootstrap SMC for a user model: generated policy in the fused resample kernel -----------------
@@ -3666,7 +3667,6 @@ int gjx_jit_routes(uint64_t* child_compiles, uint64_t* inproc_compiles, uint64_t
 }
 
 static std::string smc_plan_source(const gjx_smc_plan* plan, int impl, PlanTables* tabs = nullptr, bool peers = false, bool cond = false) {
-  gjx_jit::TableScope ts;
   gjx_jit::GenSmc<CSite, CArg> g;
   g.peers = peers;
   if (cond) {  // (include/gjx_csmc.h; the caller has checked the plan: csmc_plan_status)
@@ -3679,9 +3679,7 @@ static std::string smc_plan_source(const gjx_smc_plan* plan, int impl, PlanTable
   g.sc_init = plan->init_scopes.n_scopes > 0 ? &plan->init_scopes : nullptr;
   g.sc_step = plan->step_scopes.n_scopes > 0 ? &plan->step_scopes : nullptr;
   g.n_params = plan->n_params;
-  std::string src = g.run();
-  if (tabs) *tabs = ts.reg.tables();
-  return src;
+  return gjx_jit::generated_source(g, tabs);
 }
 int gjx_smc_plan_source(const gjx_smc_plan* p, int impl, char* buf, size_t buf_len, size_t* needed) {
   if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
@@ -3775,8 +3773,7 @@ static int smc_plan_step(const gjx_smc_config* cfg, gjx_smc_plan* plan, gjx_jit:
     CsmcRet R = ret ? *ret : CsmcRet{};
     void* args[] = {&PA, &first, &nl, &em, &fb, &tabs, &prm_rows, &R};
     if (ret && plan->n_params == 0) args[6] = &R;  // (... the conditional kernels the path, behind it)
-    if (hipModuleLaunchKernel(cp->init, ntl * nf, 1, 1, kBlock, 1, 1, 0, S(s), args, nullptr) != hipSuccess) return GJX_ERR_LAUNCH;
-    return launch_status();
+    return launch_generated(cp->init, ntl * nf, 1, kBlock, s, args);
   }
   ResampleArgs A;
   int rc = smc_resample_args(cfg, t, prev, out, prev_e_out, prev_q_out, ctx, s, &A);
@@ -3793,8 +3790,7 @@ static int smc_plan_step(const gjx_smc_config* cfg, gjx_smc_plan* plan, gjx_jit:
   CsmcRet R = ret ? *ret : CsmcRet{};
   void* args[] = {&A, &PA, &tabs, &prm_rows, &R};
   if (ret && plan->n_params == 0) args[3] = &R;
-  if (hipModuleLaunchKernel(ad ? cp->step_adaptive : cp->step, ntl * nf, 1, 1, kBlock, 1, 1, 0, S(s), args, nullptr) != hipSuccess) return GJX_ERR_LAUNCH;
-  return launch_status();
+  return launch_generated(ad ? cp->step_adaptive : cp->step, ntl * nf, 1, kBlock, s, args);
 }
 
 int gjx_smc_plan_step(const gjx_smc_config* cfg, gjx_smc_plan* plan, int t, const float* obs_t, const gjx_smc_pop* prev,
@@ -4473,13 +4469,32 @@ constexpr unsigned kBacksimMaxGrid = 256 * 16;
 
 inline bool backsim_size_ok(uint64_t v) { return v >= 1 && v < (1ull << 31); }
 
+// What gjx_backsim_run and gjx_backmove_run ask of their io blocks alike (gjx_backsim_io / gjx_backmove_io name these fields
+// the same): sizes, generator and key lane, log-weights, observations, the strides of columns, paths and lineage, at least
+// one output, an 8-byte aligned workspace.  -> GJX_OK or GJX_ERR_INVALID (the workspace's SIZE is the caller's, checked after
+// everything here); *i32_mask: bit c = column c holds int32.
+template <class Io>
+int backward_io_check(const gjx_backsim_plan* p, const Io* io, const void* ws, uint32_t* i32_mask) {
+  if (!p || !io || io->n_steps < 1 || !backsim_size_ok(io->n) || !backsim_size_ok(io->m) || (io->impl != 0 && io->impl != 1) ||
+      (io->impl == 0 && io->key_lane != 0))
+    return GJX_ERR_INVALID;
+  if (!io->logw || io->logw_stride < io->n || io->logw_stride >= (1ull << 32) || (p->n_obs > 0 && !io->obs)) return GJX_ERR_INVALID;
+  bool any_out = io->lineage_out != nullptr;
+  if (io->lineage_out && (io->lineage_stride < io->m || io->lineage_stride >= (1ull << 32))) return GJX_ERR_INVALID;
+  *i32_mask = 0;
+  for (int c = 0; c < p->n_state; ++c) {
+    if (!io->cols[c] || io->col_stride[c] < io->n || io->col_stride[c] >= (1ull << 32)) return GJX_ERR_INVALID;
+    if (io->paths_out[c] && (io->paths_stride[c] < io->m || io->paths_stride[c] >= (1ull << 32))) return GJX_ERR_INVALID;
+    any_out = any_out || io->paths_out[c];
+    if (io->col_is_i32[c]) *i32_mask |= 1u << c;
+  }
+  return any_out && ((uintptr_t)ws & 7) == 0 ? GJX_OK : GJX_ERR_INVALID;
+}
+
 std::string backsim_source(const gjx_backsim_plan* p, int impl, PlanTables* tabs = nullptr) {
-  gjx_jit::TableScope ts;
   gjx_jit::GenBacksim<CSite, CArg> g;
   g.impl = impl; g.sites = p->sites; g.n_sites = p->n_sites; g.n_state = p->n_state;
-  std::string src = g.run();
-  if (tabs) *tabs = ts.reg.tables();
-  return src;
+  return gjx_jit::generated_source(g, tabs);
 }
 
 gjx_jit::CompiledBacksim* backsim_compiled(gjx_backsim_plan* p, int impl) {
@@ -4556,26 +4571,16 @@ size_t gjx_backsim_workspace_bytes(int32_t n_steps, uint64_t m) {
   return (size_t)n_steps * (size_t)m * sizeof(unsigned long long);
 }
 int gjx_backsim_run(gjx_backsim_plan* p, const gjx_backsim_io* io, void* ws, size_t ws_bytes, gjx_stream s) {
-  if (!p || !io || io->n_steps < 1 || !backsim_size_ok(io->n) || !backsim_size_ok(io->m) || (io->impl != 0 && io->impl != 1) ||
-      (io->impl == 0 && io->key_lane != 0))
-    return GJX_ERR_INVALID;
-  const uint32_t T = (uint32_t)io->n_steps, n = (uint32_t)io->n, m = (uint32_t)io->m;
-  if (!io->logw || io->logw_stride < io->n || io->logw_stride >= (1ull << 32) || (p->n_obs > 0 && !io->obs)) return GJX_ERR_INVALID;
-  bool any_out = io->lineage_out != nullptr;
-  if (io->lineage_out && (io->lineage_stride < io->m || io->lineage_stride >= (1ull << 32))) return GJX_ERR_INVALID;
-  BacksimFinishArgs F{};
   uint32_t i32_mask = 0;
+  if (int rc = backward_io_check(p, io, ws, &i32_mask)) return rc;
+  const uint32_t T = (uint32_t)io->n_steps, n = (uint32_t)io->n, m = (uint32_t)io->m;
+  BacksimFinishArgs F{};
   for (int c = 0; c < p->n_state; ++c) {
-    if (!io->cols[c] || io->col_stride[c] < io->n || io->col_stride[c] >= (1ull << 32)) return GJX_ERR_INVALID;
-    if (io->paths_out[c] && (io->paths_stride[c] < io->m || io->paths_stride[c] >= (1ull << 32))) return GJX_ERR_INVALID;
-    any_out = any_out || io->paths_out[c];
     F.col[c] = reinterpret_cast<const uint32_t*>(io->cols[c]);
     F.col_stride[c] = io->col_stride[c];
     F.paths[c] = reinterpret_cast<uint32_t*>(io->paths_out[c]);
     F.paths_stride[c] = io->paths_stride[c];
-    if (io->col_is_i32[c]) i32_mask |= 1u << c;
   }
-  if (!any_out || ((uintptr_t)ws & 7) != 0) return GJX_ERR_INVALID;
   if (!ws || ws_bytes < gjx_backsim_workspace_bytes(io->n_steps, io->m)) return GJX_ERR_WORKSPACE;
   if (!gjx_jit::enabled()) return GJX_ERR_UNSUPPORTED;  // generated kernels only, as guided plans
   gjx_jit::CompiledBacksim* k = backsim_compiled(p, io->impl);
@@ -4612,10 +4617,7 @@ int gjx_backsim_run(gjx_backsim_plan* p, const gjx_backsim_io* io, void* ws, siz
     A.n_chunks = n_chunks;
     PlanTables tabs = k->tabs;
     void* args[] = {&A, &tabs};
-    if (hipModuleLaunchKernel(last ? k->last : k->step, grid, 1, 1, kBlock, 1, 1, 0, S(s), args, nullptr) != hipSuccess) {
-      (void)hipGetLastError();
-      return GJX_ERR_LAUNCH;
-    }
+    if (int rc = launch_generated(last ? k->last : k->step, grid, 1, kBlock, s, args)) return rc;
   }
   F.best = best;
   F.lineage = io->lineage_out;
@@ -4638,12 +4640,9 @@ namespace {
 constexpr unsigned kBackmoveMaxGrid = 256 * 8;  // workgroups of 256 paths, grid-stride beyond (the LDS stage is per workgroup)
 
 std::string backmove_source(const gjx_backsim_plan* p, int impl, PlanTables* tabs = nullptr) {
-  gjx_jit::TableScope ts;
   gjx_jit::GenBackmove<CSite, CArg> g;
   g.impl = impl; g.sites = p->sites; g.n_sites = p->n_sites; g.n_state = p->n_state;
-  std::string src = g.run();
-  if (tabs) *tabs = ts.reg.tables();
-  return src;
+  return gjx_jit::generated_source(g, tabs);
 }
 
 gjx_jit::CompiledBacksim* backmove_compiled(gjx_backsim_plan* p, int impl) {
@@ -4701,23 +4700,13 @@ size_t gjx_backmove_workspace_bytes(int32_t n_steps, uint64_t n, uint64_t m) {
   return ~(size_t)0 - cv.left;
 }
 int gjx_backmove_run(gjx_backsim_plan* p, const gjx_backmove_io* io, void* ws, size_t ws_bytes, gjx_stream s) {
-  if (!p || !io || io->n_steps < 1 || !backsim_size_ok(io->n) || !backsim_size_ok(io->m) || (io->impl != 0 && io->impl != 1) ||
-      (io->impl == 0 && io->key_lane != 0) || io->n_moves < 0 || io->n_moves > GJX_BACKMOVE_MAX_MOVES)
-    return GJX_ERR_INVALID;
+  // (every refusal up to the workspace's size is GJX_ERR_INVALID: the shared checks first, then what this header adds)
+  uint32_t i32_mask = 0;
+  if (int rc = backward_io_check(p, io, ws, &i32_mask)) return rc;
+  if (io->n_moves < 0 || io->n_moves > GJX_BACKMOVE_MAX_MOVES) return GJX_ERR_INVALID;
   const uint32_t T = (uint32_t)io->n_steps, n = (uint32_t)io->n, m = (uint32_t)io->m, K = (uint32_t)io->n_moves;
   if ((uint64_t)m * (K ? K : 1u) >= (1ull << 31)) return GJX_ERR_INVALID;
-  if (!io->logw || io->logw_stride < io->n || io->logw_stride >= (1ull << 32) || (p->n_obs > 0 && !io->obs)) return GJX_ERR_INVALID;
   if (!io->ancestors || io->anc_stride < io->n || io->anc_stride >= (1ull << 32)) return GJX_ERR_INVALID;
-  bool any_out = io->lineage_out != nullptr;
-  if (io->lineage_out && (io->lineage_stride < io->m || io->lineage_stride >= (1ull << 32))) return GJX_ERR_INVALID;
-  uint32_t i32_mask = 0;
-  for (int c = 0; c < p->n_state; ++c) {
-    if (!io->cols[c] || io->col_stride[c] < io->n || io->col_stride[c] >= (1ull << 32)) return GJX_ERR_INVALID;
-    if (io->paths_out[c] && (io->paths_stride[c] < io->m || io->paths_stride[c] >= (1ull << 32))) return GJX_ERR_INVALID;
-    any_out = any_out || io->paths_out[c];
-    if (io->col_is_i32[c]) i32_mask |= 1u << c;
-  }
-  if (!any_out || ((uintptr_t)ws & 7) != 0) return GJX_ERR_INVALID;
   if (!ws || ws_bytes < gjx_backmove_workspace_bytes(io->n_steps, io->n, io->m)) return GJX_ERR_WORKSPACE;
   if (!gjx_jit::enabled()) return GJX_ERR_UNSUPPORTED;  // generated kernels only, as gjx_backsim_run
   gjx_jit::CompiledBacksim* k = backmove_compiled(p, io->impl);
@@ -4767,10 +4756,7 @@ int gjx_backmove_run(gjx_backsim_plan* p, const gjx_backmove_io* io, void* ws, s
     A.coarse = coarse;
     PlanTables tabs = k->tabs;
     void* args[] = {&A, &tabs};
-    if (hipModuleLaunchKernel(last ? k->last : k->step, grid, 1, 1, kBlock, 1, 1, 0, S(s), args, nullptr) != hipSuccess) {
-      (void)hipGetLastError();
-      return GJX_ERR_LAUNCH;
-    }
+    if (int rc = launch_generated(last ? k->last : k->step, grid, 1, kBlock, s, args)) return rc;
   }
   return launch_status();
 }
@@ -4798,12 +4784,9 @@ namespace {
 constexpr unsigned kTemperMaxGrid = 256 * 16;  // workgroups of 256 particles, grid-stride beyond
 
 std::string temper_source(const gjx_temper_plan* p, int impl, PlanTables* tabs = nullptr) {
-  gjx_jit::TableScope ts;
   gjx_jit::GenTemper<CSite, CArg> g;
   g.impl = impl; g.sites = p->sites; g.n_sites = p->n_sites;
-  std::string src = g.run();
-  if (tabs) *tabs = ts.reg.tables();
-  return src;
+  return gjx_jit::generated_source(g, tabs);
 }
 
 gjx_jit::CompiledTemper* temper_compiled(gjx_temper_plan* p, int impl) {
@@ -5021,11 +5004,7 @@ int gjx_temper_move(gjx_temper_plan* p, const gjx_temper_io* io, gjx_stream s) {
   PlanParams prm = p->prm;
   PlanTables tabs = k->tabs;
   void* args[] = {&A, &cols, &prm, &tabs};
-  if (hipModuleLaunchKernel(k->move, grid, 1, 1, kBlock, 1, 1, 0, S(s), args, nullptr) != hipSuccess) {
-    (void)hipGetLastError();
-    return GJX_ERR_LAUNCH;
-  }
-  return launch_status();
+  return launch_generated(k->move, grid, 1, kBlock, s, args);
 }
 
 uint32_t gjx_temper_ladder_blocks(uint64_t n) {

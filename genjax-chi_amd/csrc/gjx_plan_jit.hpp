@@ -513,22 +513,12 @@ struct SiteEmitter {
 };
 
 // bm_lds: the kernels of this source stage the Box-Muller tables in LDS (each calls bm_stage() at entry; gjx_device.hpp),
-// `block` threads per workgroup (a constant of the source: bm_stage forms its table addresses from it)
+// `block` threads per workgroup (a constant of the source: bm_stage forms its table addresses from it).  What the sites call
+// by name — jrow_lse, jcat_invcdf, jcat_invcdf_gb, jcat_gumbel ... — is in the device header, like every other fixed function.
 inline void emit_prelude(std::ostringstream& o, bool fast_math = false, bool bm_lds = false, int block = 0) {
   if (bm_lds) o << "#define GJX_BM_LDS 1\n#define GJX_BM_BLOCK " << block << "\n";
   if (fast_math) o << "#define GJX_FAST_MATH 1\n";  // gjx.h GJX_PLAN_FAST_MATH: hardware transcendentals (gjx_device.hpp d_exp / bm_pair)
   o << "#include \"gjx_device.hpp\"\nusing namespace gjx;\n";
-  o << "__device__ __forceinline__ float jrow_max(const float* l, uint32_t K){ float m=l[0]; for(uint32_t c=1;c<K;++c) m = l[c]>m?l[c]:m; return m; }\n";
-  o << "__device__ __forceinline__ float jrow_lse(const float* l, uint32_t K){ const float m=jrow_max(l,K); float acc=0.0f; for(uint32_t c=0;c<K;++c) acc = acc + m_exp(l[c]-m); return m + m_log(acc); }\n";
-  o << "__device__ __forceinline__ int32_t jcat_invcdf(const float* l, uint32_t K, uint32_t bits){ const float m=jrow_max(l,K); uint64_t Q=0; for(uint32_t c=0;c<K;++c) Q += cat_fix(l[c],m); const uint64_t thr=((uint64_t)bits*Q)>>32; uint64_t C=0; for(uint32_t c=0;c<K;++c){ C += cat_fix(l[c],m); if (C>thr) return (int32_t)c; } return (int32_t)(K-1); }\n";
-  // the guide bucket: one scattered 16-byte load per draw from a table of up to 2 MB (L2-resident).  As a BUFFER load
-  // (resource anchored 1 GiB below the first lane's address; every lane of the wave reads the same table, so all offsets
-  // are in range) the scan of the 256-state HMM runs 4.02 -> 2.39 ms per 5e8 particle-steps against the same load as
-  // global_load_dwordx4; the sc0 / sc1 bits make no further difference, a non-temporal global load is 2x slower and an
-  // agent-scope pair of 8-byte loads is even (profiles/r04_ab/README.md).
-  o << "typedef unsigned jv4u_t __attribute__((ext_vector_type(4)));\n__device__ __forceinline__ uint4 jguide_load(const uint4* p){ const uint64_t a=(uint64_t)(uintptr_t)p; const uint64_t first=((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a>>32))<<32)|(uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a); const uint64_t base=first-(1ull<<30); __amdgpu_buffer_rsrc_t rs=__builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)base,0,0x7fffffff,0x00020000); const jv4u_t v=__builtin_amdgcn_raw_buffer_load_b128(rs,(int)(uint32_t)(a-base),0,0); return make_uint4(v[0],v[1],v[2],v[3]); }\n";
-  o << "__device__ __forceinline__ int32_t jcat_invcdf_gb(const uint4* guide, const uint2* ent, uint32_t K, uint32_t bits, int sh, uint32_t& lpb){ const uint4 g=jguide_load(guide+(bits>>sh)); const uint32_t c0=g.y&511u, c1=(g.y>>9)&511u; if (bits<=g.x){ lpb=g.z; return (int32_t)c0; } if (!(g.y>>18)){ lpb=g.w; return (int32_t)c1; } const uint64_t thr=((uint64_t)bits*(uint64_t)ent[K-1].x)>>32; uint32_t c=c1; uint2 e=ent[c]; while (c<K-1 && (uint64_t)e.x<=thr){ ++c; e=ent[c]; } lpb=e.y; return (int32_t)c; }\n";
-  o << "template <int IMPL> __device__ __forceinline__ int32_t jcat_gumbel(const float* l, uint32_t K, const Stream<IMPL>& st){ int32_t best=0; float bv=-__builtin_inff(); for(uint32_t c=0;c<K;++c){ const float v = l[c] + gumbel_from_bits(st.bits32(c)); if (v>bv || c==0){ bv=v; best=(int32_t)c; } } return best; }\n";
 }
 
 // The sites of a lane that owns NP whole PAIRS of adjacent particles (suffixes A, B [, C, D]) under PHILOX: one cipher
@@ -1296,16 +1286,24 @@ struct GenSmc {
   }
 };
 
-// The kernels of a backward-simulation plan (include/gjx_backsim.h).  The transition table becomes ONE device function,
-// trans_lp(state of candidate i, next state of trajectory j) -> the f32 sum of the table's log-densities, emitted by
-// SiteEmitter exactly as an SMC step's weight is (mode 1: st_<k>, a.obs[]; nx_<c> for GJX_ARG_NEXT).  Around it:
-//   lanes over candidates, two adjacent ones per lane (8-byte loads of state and log-weight, once per work item);
-//   a work item = kBacksimBlock trajectories x one chunk of candidates: the trajectories' keys and next-state values are
-//   wave-uniform (scalar registers), each lane keeps (best value, best index) per trajectory and candidate order is
-//   ascending inside a lane, so `v > best || i == 0` is the oracle's own scan there;
-//   at the end of the item one DPP wave maximum per trajectory over the packed word (gjx_device.hpp backsim_pack) and one
-//   64-bit atomic maximum per wave and trajectory: order-free and exact.
-// A trajectory index past m is clamped to m - 1: its (identical) maxima change nothing.
+// The transition table of a backward pass as ONE device function, the static member of a generated struct:
+// GenTrans::trans_lp(a, tabs, state of candidate i, next state of trajectory j) -> the f32 sum of the table's log-densities,
+// emitted by SiteEmitter exactly as an SMC step's weight is (mode 1: st_<k>, a.obs[]; nx_<c> for GJX_ARG_NEXT).  `a` is the
+// kernel's argument block (BacksimArgs or BackmoveArgs: the walk reads a.obs[] alone).
+template <class CSiteT, class CArgT>
+inline void emit_trans_struct(std::ostringstream& o, int impl, const CSiteT* sites, int n_sites, int n_state) {
+  o << "struct GenTrans {\n  template <class Args>\n  static __device__ __forceinline__ float trans_lp(const Args& a, const PlanTables& tabs, const float (&st)["
+    << n_state << "], const float (&nx)[" << n_state << "]) {\n";
+  for (int k = 0; k < n_state; ++k) o << "    const float st_" << k << " = st[" << k << "], nx_" << k << " = nx[" << k << "];\n";
+  for (int k = 0; k < n_state; ++k) o << "    (void)st_" << k << "; (void)nx_" << k << ";\n";
+  o << "    float w = 0.0f, sc = 0.0f;\n";
+  SiteEmitter<CSiteT, CArgT> e{o, impl, 1, sites, n_sites, "    ", ""};
+  e.run();
+  o << "    (void)sc;\n    return w;\n  }\n};\n";
+}
+
+// The kernels of a backward-simulation plan (include/gjx_backsim.h): the transition struct and two instantiations of
+// gjx_device.hpp backsim_body (the last step's has no next state).
 template <class CSiteT, class CArgT>
 struct GenBacksim {
   std::ostringstream o;
@@ -1315,88 +1313,20 @@ struct GenBacksim {
   int n_state;
 
   std::string run() {
-    const std::string I = std::to_string(impl);
     emit_prelude(o);
-    std::string st_params, st_args_a, st_args_b, nx_params, nx_args;
-    for (int k = 0; k < n_state; ++k) {
-      const std::string K = std::to_string(k);
-      st_params += ", float st_" + K;
-      nx_params += ", float nx_" + K;
-      st_args_a += ", sa[" + K + "]";
-      st_args_b += ", sb[" + K + "]";
-      nx_args += ", nx[u][" + K + "]";
-    }
-    o << "__device__ __forceinline__ float trans_lp(const BacksimArgs& a, const PlanTables& tabs" << st_params << nx_params << ") {\n";
-    for (int k = 0; k < n_state; ++k) o << "  (void)st_" << k << "; (void)nx_" << k << ";\n";
-    o << "  float w = 0.0f, sc = 0.0f;\n";
-    SiteEmitter<CSiteT, CArgT> e{o, impl, 1, sites, n_sites, "  ", ""};
-    e.run();
-    o << "  (void)sc;\n  return w;\n}\n";
-    o << "constexpr int D = " << n_state << ", JB = kBacksimBlock;\n";
-    o << "__device__ __forceinline__ float bs_col(uint32_t bits, bool is_i32) { return is_i32 ? (float)(int32_t)bits : u2f(bits); }\n";
-    o << "template <bool LAST>\n__device__ __forceinline__ void backsim_body(const BacksimArgs& a, const PlanTables& tabs) {\n";
-    o << "  const uint32_t n = a.n, m = a.m;\n";
-    o << "  const uint32_t n_tb = (m + JB - 1) / JB;\n";
-    o << "  const uint64_t items = (uint64_t)n_tb * a.n_chunks;\n";
-    o << "  for (uint64_t it = blockIdx.x; it < items; it += gridDim.x) {\n";
-    o << "    const uint32_t tb = (uint32_t)(it / a.n_chunks), cc = (uint32_t)(it - (uint64_t)tb * a.n_chunks);\n";
-    o << "    Key tk[JB];\n    float nx[JB][D];\n    uint32_t tj[JB];\n";
-    o << "#pragma unroll\n    for (int u = 0; u < JB; ++u) {\n";
-    o << "      const uint32_t j = tb * JB + u < m ? tb * JB + u : m - 1u;\n";
-    o << "      tj[u] = j;\n      tk[u] = split_at<" << I << ">(a.kt, (uint64_t)j);\n";
-    o << "      for (int c = 0; c < D; ++c) nx[u][c] = 0.0f;\n";
-    o << "      if (!LAST) {\n        const uint32_t w = backsim_index(a.best_next[j], n);\n";
-    o << "        for (int c = 0; c < D; ++c) nx[u][c] = bs_col(a.col_next[c][w], (a.i32_mask >> c) & 1u);\n      }\n";
-    o << "    }\n";
-    o << "    float bv[JB];\n    uint32_t bi[JB];\n";
-    o << "#pragma unroll\n    for (int u = 0; u < JB; ++u) { bv[u] = -__builtin_inff(); bi[u] = 0x7fffffffu; }\n";
-    o << "    const uint64_t c0 = (uint64_t)cc * a.chunk;\n";
-    o << "    const uint64_t c1 = c0 + a.chunk < n ? c0 + a.chunk : n;\n";
-    o << "    for (uint64_t i64 = c0 + 2u * threadIdx.x; i64 < c1; i64 += 2u * blockDim.x) {\n";
-    o << "      const uint32_t i = (uint32_t)i64;\n";
-    o << "      const bool hasb = i + 1u < n;\n";
-    o << "      float sa[D], sb[D], lwa, lwb;\n";
-    o << "      if (a.vec2 && hasb) {\n";
-    o << "        const uint2 l2 = *reinterpret_cast<const uint2*>(a.lw + i);\n        lwa = u2f(l2.x); lwb = u2f(l2.y);\n";
-    o << "        for (int c = 0; c < D; ++c) {\n          const uint2 v2 = *reinterpret_cast<const uint2*>(a.col[c] + i);\n";
-    o << "          sa[c] = bs_col(v2.x, (a.i32_mask >> c) & 1u); sb[c] = bs_col(v2.y, (a.i32_mask >> c) & 1u);\n        }\n";
-    o << "      } else {\n";
-    o << "        lwa = a.lw[i]; lwb = hasb ? a.lw[i + 1u] : -__builtin_inff();\n";
-    o << "        for (int c = 0; c < D; ++c) {\n          sa[c] = bs_col(a.col[c][i], (a.i32_mask >> c) & 1u);\n";
-    o << "          sb[c] = hasb ? bs_col(a.col[c][i + 1u], (a.i32_mask >> c) & 1u) : sa[c];\n        }\n";
-    o << "      }\n";
-    o << "      const bool first = i == 0u;\n";
-    o << "#pragma unroll\n      for (int u = 0; u < JB; ++u) {\n";
-    o << "        const Stream<" << I << "> ds(tk[u], false, 0u);\n";
-    o << "        const float la = LAST ? lwa : lwa + trans_lp(a, tabs" << st_args_a << nx_args << ");\n";
-    o << "        const float lb = LAST ? lwb : lwb + trans_lp(a, tabs" << st_args_b << nx_args << ");\n";
-    o << "        const float va = la + gumbel_from_bits(ds.bits32(i));\n";
-    o << "        const float vb = lb + gumbel_from_bits(ds.bits32(i + 1u));\n";
-    o << "        if (va > bv[u] || first) { bv[u] = va; bi[u] = i; }\n";
-    o << "        if (hasb && vb > bv[u]) { bv[u] = vb; bi[u] = i + 1u; }\n";
-    o << "      }\n    }\n";
-    o << "#pragma unroll\n    for (int u = 0; u < JB; ++u) {\n";
-    o << "      const unsigned long long w = wave_last_u64(wave_scan_u64(backsim_pack(bv[u], bi[u]), 0ull,\n";
-    o << "          [](uint64_t x, uint64_t y) { return x > y ? x : y; }));\n";
-    o << "      if ((threadIdx.x & 63u) == 0u) atomicMax(a.best + tj[u], w);\n";
-    o << "    }\n  }\n}\n";
-    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_backsim_step_kernel(BacksimArgs a, PlanTables tabs) { backsim_body<false>(a, tabs); }\n";
-    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_backsim_last_kernel(BacksimArgs a, PlanTables tabs) { backsim_body<true>(a, tabs); }\n";
+    emit_trans_struct<CSiteT, CArgT>(o, impl, sites, n_sites, n_state);
+    const std::string ID = "<" + std::to_string(impl) + ", " + std::to_string(n_state);
+    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_backsim_step_kernel(BacksimArgs a, PlanTables tabs) { backsim_body" << ID << ", GenTrans, false>(a, tabs); }\n";
+    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_backsim_last_kernel(BacksimArgs a, PlanTables tabs) { backsim_body" << ID << ", GenTrans, true>(a, tabs); }\n";
     return o.str();
   }
 };
 
-// The kernels of the MCMC backward sampler (include/gjx_backmove.h) over the SAME transition table: trans_lp is emitted as
-// GenBacksim emits it, around it a LATENCY kernel — one lane per path, and per move a CDF search (dependent reads), a random
-// gather of the proposal's state and one transition density.  None of that depends on the chain's state, so a path's moves
-// are issued in blocks of 4 / 2 / 1 INDEPENDENT chains (bm_moves<B>: the B searches advance in lockstep, one load each per
-// round, a wave-uniform trip count — a finished search repeats its last read and changes nothing); only the B
-// compare-and-select steps at the end of a block are serial.
-//   search   bm_search returns cdf_upper_bound's index (gjx_hip.hip): the same halving of [lo, hi], run ceil(log2(size))
-//            times.  Two levels when a.coarse: the CDF's tile ends (entry 1024 k + 1023, the last one for the ragged tile)
-//            staged in LDS once per workgroup, then at most 10 rounds inside one 8 KB tile.  The CDF is non-decreasing, so
-//            the first entry above thr lies in the first tile whose END is above thr (the last tile if none is).
-//   keys     a.pk / a.ak have lane 0: under PHILOX the cipher key of every proposal and every uniform is wave-uniform.
+// The kernels of the MCMC backward sampler (include/gjx_backmove.h) over the SAME transition table: the same struct, and
+// around it the helpers of gjx_device.hpp (backmove_score, backmove_stage, backmove_draw, backmove_moves<B>, backmove_store).
+// The two kernels' own loops over paths are still emitted here: inside a device function they lose what the compiler does
+// for a kernel function alone (the uniform-workgroup form of blockDim.x, the no-clobber marks of its argument loads), and
+// the machine code changes (profiles/fixed_bodies_summary.md).
 template <class CSiteT, class CArgT>
 struct GenBackmove {
   std::ostringstream o;
@@ -1406,82 +1336,31 @@ struct GenBackmove {
   int n_state;
 
   std::string run() {
-    const std::string I = std::to_string(impl);
     emit_prelude(o);
-    std::string st_params, nx_params, st_args, nx_args;
-    for (int k = 0; k < n_state; ++k) {
-      const std::string K = std::to_string(k);
-      st_params += ", float st_" + K;
-      nx_params += ", float nx_" + K;
-      st_args += ", st[" + K + "]";
-      nx_args += ", nx[" + K + "]";
-    }
-    o << "__device__ __forceinline__ float trans_lp(const BackmoveArgs& a, const PlanTables& tabs" << st_params << nx_params << ") {\n";
-    for (int k = 0; k < n_state; ++k) o << "  (void)st_" << k << "; (void)nx_" << k << ";\n";
-    o << "  float w = 0.0f, sc = 0.0f;\n";
-    SiteEmitter<CSiteT, CArgT> e{o, impl, 1, sites, n_sites, "  ", ""};
-    e.run();
-    o << "  (void)sc;\n  return w;\n}\n";
-    o << "constexpr int D = " << n_state << ";\n";
-    o << "__device__ __forceinline__ float bm_col(uint32_t bits, bool is_i32) { return is_i32 ? (float)(int32_t)bits : u2f(bits); }\n";
-    o << "__device__ __forceinline__ float bm_score(const BackmoveArgs& a, const PlanTables& tabs, uint32_t i, const float (&nx)[D]) {\n";
-    o << "  float st[D];\n  for (int c = 0; c < D; ++c) st[c] = bm_col(a.col[c][i], (a.i32_mask >> c) & 1u);\n";
-    o << "  return trans_lp(a, tabs" << st_args << nx_args << ");\n}\n";
-    o << "__device__ __forceinline__ int bm_steps(uint32_t size) { return size > 1u ? 32 - __builtin_clz(size - 1u) : 0; }\n";
-    o << "template <int B>\n__device__ __forceinline__ void bm_search(const uint64_t* c, uint32_t (&lo)[B], uint32_t (&hi)[B], const uint64_t (&thr)[B], int steps) {\n";
-    o << "  for (int it = 0; it < steps; ++it) {\n    uint32_t mid[B];\n    uint64_t v[B];\n";
-    o << "#pragma unroll\n    for (int u = 0; u < B; ++u) { mid[u] = lo[u] + ((hi[u] - lo[u]) >> 1); v[u] = c[mid[u]]; }\n";
-    o << "#pragma unroll\n    for (int u = 0; u < B; ++u)\n      if (lo[u] < hi[u]) { if (v[u] > thr[u]) hi[u] = mid[u]; else lo[u] = mid[u] + 1u; }\n";
-    o << "  }\n}\n";
-    o << "__device__ __forceinline__ uint32_t bm_tile_end(uint32_t k, uint32_t n) { const uint32_t e = (k + 1u) * kBackmoveTile; return (e < n ? e : n) - 1u; }\n";
-    o << "__device__ __forceinline__ void bm_stage(const BackmoveArgs& a, uint64_t* ends) {\n";
-    o << "  const uint32_t nt = (a.n + kBackmoveTile - 1u) / kBackmoveTile;\n";
-    o << "  for (uint32_t k = threadIdx.x; k < nt; k += blockDim.x) ends[k] = a.cdf[bm_tile_end(k, a.n)];\n  __syncthreads();\n}\n";
-    // elements e[u] of the multinomial draw under a.pk: out[u] = the first i with cdf[i] > mulhi64(bits64(e[u]), Q)
-    o << "template <int B>\n__device__ __forceinline__ void bm_draw(const BackmoveArgs& a, const uint64_t* ends, uint64_t Q, const uint32_t (&e)[B], uint32_t (&out)[B]) {\n";
-    o << "  const Stream<" << I << "> ps(a.pk, false, 0u);\n  const uint32_t n = a.n;\n  uint64_t thr[B];\n  uint32_t hi[B];\n";
-    o << "#pragma unroll\n  for (int u = 0; u < B; ++u) { thr[u] = __umul64hi(ps.bits64(e[u]), Q); out[u] = 0u; }\n";
-    o << "  if (a.coarse) {\n    const uint32_t nt = (n + kBackmoveTile - 1u) / kBackmoveTile;\n";
-    o << "#pragma unroll\n    for (int u = 0; u < B; ++u) hi[u] = nt - 1u;\n";
-    o << "    bm_search<B>(ends, out, hi, thr, bm_steps(nt));\n";
-    o << "#pragma unroll\n    for (int u = 0; u < B; ++u) { hi[u] = bm_tile_end(out[u], n); out[u] *= kBackmoveTile; }\n";
-    o << "    bm_search<B>(a.cdf, out, hi, thr, bm_steps(n < kBackmoveTile ? n : kBackmoveTile));\n";
-    o << "  } else {\n";
-    o << "#pragma unroll\n    for (int u = 0; u < B; ++u) hi[u] = n - 1u;\n";
-    o << "    bm_search<B>(a.cdf, out, hi, thr, bm_steps(n));\n  }\n}\n";
-    // moves r0 .. r0 + B - 1 of path j
-    o << "template <int B>\n__device__ __forceinline__ void bm_moves(const BackmoveArgs& a, const PlanTables& tabs, const uint64_t* ends, uint64_t Q, uint32_t j, uint32_t r0,\n";
-    o << "                                         const float (&nx)[D], uint32_t& cur, float& s_cur) {\n";
-    o << "  uint32_t e[B], pr[B];\n  float sp[B], lg[B];\n";
-    o << "#pragma unroll\n  for (int u = 0; u < B; ++u) e[u] = (r0 + (uint32_t)u) * a.m + j;\n";
-    o << "  bm_draw<B>(a, ends, Q, e, pr);\n";
-    o << "#pragma unroll\n  for (int u = 0; u < B; ++u) {\n    sp[u] = bm_score(a, tabs, pr[u], nx);\n";
-    o << "    const Stream<" << I << "> as(split_at<" << I << ">(a.ak, (uint64_t)e[u]), false, 0u);\n";
-    o << "    lg[u] = m_log(uniform01(as.bits32(0u)));\n  }\n";
-    o << "#pragma unroll\n  for (int u = 0; u < B; ++u) {\n    const float d = sp[u] - s_cur;\n";
-    o << "    if (d >= 0.0f || lg[u] < d) { cur = pr[u]; s_cur = sp[u]; }\n  }\n}\n";
-    o << "__device__ __forceinline__ void bm_store(const BackmoveArgs& a, uint32_t j, uint32_t i) {\n  a.lin[j] = (int32_t)i;\n";
-    o << "  for (int c = 0; c < D; ++c)\n    if (a.path[c]) a.path[c][j] = a.col[c][i];\n}\n";
+    emit_trans_struct<CSiteT, CArgT>(o, impl, sites, n_sites, n_state);
+    const std::string I = std::to_string(impl), D = std::to_string(n_state), IDT = "<" + I + ", " + D + ", GenTrans, ";
+    // step t < T - 1: path j starts at the ancestor of its row-(t + 1) particle and makes a.n_moves moves
     o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_backmove_step_kernel(BackmoveArgs a, PlanTables tabs) {\n";
     o << "  __shared__ uint64_t sh_ends[kBackmoveLdsTiles];\n";
     o << "  const uint32_t n = a.n, m = a.m, K = a.n_moves;\n  uint64_t Q = 0;\n";
-    o << "  if (K) {\n    Q = a.cdf[n - 1u];\n    if (a.coarse) bm_stage(a, sh_ends);\n  }\n";
+    o << "  if (K) {\n    Q = a.cdf[n - 1u];\n    if (a.coarse) backmove_stage(a, sh_ends);\n  }\n";
     o << "  for (uint64_t j64 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j64 < m; j64 += (uint64_t)gridDim.x * blockDim.x) {\n";
     o << "    const uint32_t j = (uint32_t)j64;\n";
     o << "    uint32_t nxt = (uint32_t)a.lin_next[j];\n    nxt = nxt < n ? nxt : n - 1u;\n";
-    o << "    float nx[D];\n    for (int c = 0; c < D; ++c) nx[c] = bm_col(a.col_next[c][nxt], (a.i32_mask >> c) & 1u);\n";
+    o << "    float nx[" << D << "];\n    for (int c = 0; c < " << D << "; ++c) nx[c] = backsim_col(a.col_next[c][nxt], (a.i32_mask >> c) & 1u);\n";
     o << "    uint32_t cur = (uint32_t)a.anc_next[nxt];\n    cur = cur < n ? cur : n - 1u;\n";
-    o << "    if (K) {\n      float s_cur = bm_score(a, tabs, cur, nx);\n      uint32_t r = 0;\n";
-    o << "      for (; r + 4u <= K; r += 4u) bm_moves<4>(a, tabs, sh_ends, Q, j, r, nx, cur, s_cur);\n";
-    o << "      if (K - r >= 2u) { bm_moves<2>(a, tabs, sh_ends, Q, j, r, nx, cur, s_cur); r += 2u; }\n";
-    o << "      if (K - r >= 1u) bm_moves<1>(a, tabs, sh_ends, Q, j, r, nx, cur, s_cur);\n    }\n";
-    o << "    bm_store(a, j, cur);\n  }\n}\n";
+    o << "    if (K) {\n      float s_cur = backmove_score<" << D << ", GenTrans>(a, tabs, cur, nx);\n      uint32_t r = 0;\n";
+    o << "      for (; r + 4u <= K; r += 4u) backmove_moves" << IDT << "4>(a, tabs, sh_ends, Q, j, r, nx, cur, s_cur);\n";
+    o << "      if (K - r >= 2u) { backmove_moves" << IDT << "2>(a, tabs, sh_ends, Q, j, r, nx, cur, s_cur); r += 2u; }\n";
+    o << "      if (K - r >= 1u) backmove_moves" << IDT << "1>(a, tabs, sh_ends, Q, j, r, nx, cur, s_cur);\n    }\n";
+    o << "    backmove_store<" << D << ">(a, j, cur);\n  }\n}\n";
+    // step T - 1: path j is one multinomial draw from the final weights
     o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_backmove_last_kernel(BackmoveArgs a, PlanTables tabs) {\n";
     o << "  __shared__ uint64_t sh_ends[kBackmoveLdsTiles];\n  (void)tabs;\n";
-    o << "  const uint64_t Q = a.cdf[a.n - 1u];\n  if (a.coarse) bm_stage(a, sh_ends);\n";
+    o << "  const uint64_t Q = a.cdf[a.n - 1u];\n  if (a.coarse) backmove_stage(a, sh_ends);\n";
     o << "  for (uint64_t j64 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j64 < a.m; j64 += (uint64_t)gridDim.x * blockDim.x) {\n";
-    o << "    const uint32_t e[1] = {(uint32_t)j64};\n    uint32_t i[1];\n    bm_draw<1>(a, sh_ends, Q, e, i);\n";
-    o << "    bm_store(a, e[0], i[0]);\n  }\n}\n";
+    o << "    const uint32_t e[1] = {(uint32_t)j64};\n    uint32_t i[1];\n    backmove_draw<" << I << ", 1>(a, sh_ends, Q, e, i);\n";
+    o << "    backmove_store<" << D << ">(a, e[0], i[0]);\n  }\n}\n";
     return o.str();
   }
 };
@@ -1576,6 +1455,16 @@ struct GenTemper {
     return o.str();
   }
 };
+
+// One source generation: the generator numbers the plan's device tables while it runs (TableScope); `tabs` (nullable) takes
+// their addresses, in that order — the kernel argument of every launch of the source.
+template <class G>
+inline std::string generated_source(G& g, gjx::PlanTables* tabs) {
+  TableScope ts;
+  std::string src = g.run();
+  if (tabs) *tabs = ts.reg.tables();
+  return src;
+}
 
 inline bool enabled() {
   const char* e = std::getenv("GJX_PLAN_JIT");

@@ -1003,7 +1003,31 @@ class SmcPopulation:
         return p
 
 
-class SmcPlan:
+class PlanHandle:
+    """A plan object of the library, owned: `ops`, `handle` and the symbol that destroys it (`_destroy`, per class)."""
+
+    _destroy: str
+
+    def _source(self, symbol: str, impl: int) -> str:
+        """A `*_source` call of the ABI: the size first, then the text."""
+        need = C.c_size_t()
+        self.ops.lib.call(symbol, self.handle, impl, None, 0, C.byref(need))
+        buf = C.create_string_buffer(need.value)
+        self.ops.lib.call(symbol, self.handle, impl, buf, need.value, None)
+        return buf.value.decode()
+
+    def __del__(self):
+        try:
+            if self.handle:
+                self.ops.lib.call(self._destroy, self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+class SmcPlan(PlanHandle):
+    _destroy = "gjx_smc_plan_destroy"
+
     def __init__(self, ops: "Ops", handle, n_state: int, n_obs: int, n_params: int = 0):
         self.ops, self.handle, self.n_state, self.n_obs, self.n_params = ops, handle, n_state, n_obs, n_params
 
@@ -1023,11 +1047,7 @@ class SmcPlan:
 
     def source(self, impl: int) -> str:
         """The HIP source of the plan's generated kernels (include/gjx_guided.h: gjx_smc_plan_source)."""
-        need = C.c_size_t()
-        self.ops.lib.call("gjx_smc_plan_source", self.handle, impl, None, 0, C.byref(need))
-        buf = C.create_string_buffer(need.value)
-        self.ops.lib.call("gjx_smc_plan_source", self.handle, impl, buf, need.value, None)
-        return buf.value.decode()
+        return self._source("gjx_smc_plan_source", impl)
 
     def csmc_compile_check(self, impl: int) -> int:
         """gjx_csmc_plan_compile_check (include/gjx_csmc.h): the status, not raised."""
@@ -1036,23 +1056,13 @@ class SmcPlan:
 
     def csmc_source(self, impl: int) -> str:
         """The HIP source of the plan's CONDITIONAL kernels (include/gjx_csmc.h: gjx_csmc_plan_source)."""
-        need = C.c_size_t()
-        self.ops.lib.call("gjx_csmc_plan_source", self.handle, impl, None, 0, C.byref(need))
-        buf = C.create_string_buffer(need.value)
-        self.ops.lib.call("gjx_csmc_plan_source", self.handle, impl, buf, need.value, None)
-        return buf.value.decode()
-
-    def __del__(self):
-        try:
-            if self.handle:
-                self.ops.lib.call("gjx_smc_plan_destroy", self.handle)
-                self.handle = None
-        except Exception:
-            pass
+        return self._source("gjx_csmc_plan_source", impl)
 
 
-class BacksimPlan:
+class BacksimPlan(PlanHandle):
     """A gjx_backsim_plan (include/gjx_backsim.h): the generated kernels of one transition table."""
+
+    _destroy = "gjx_backsim_plan_destroy"
 
     def __init__(self, ops: "Ops", handle, n_state: int, n_obs: int):
         self.ops, self.handle, self.n_state, self.n_obs = ops, handle, n_state, n_obs
@@ -1061,11 +1071,7 @@ class BacksimPlan:
         return self.ops.lib._gjx_backsim_plan_compile_check(self.handle, impl)
 
     def source(self, impl: int) -> str:
-        need = C.c_size_t()
-        self.ops.lib.call("gjx_backsim_plan_source", self.handle, impl, None, 0, C.byref(need))
-        buf = C.create_string_buffer(need.value)
-        self.ops.lib.call("gjx_backsim_plan_source", self.handle, impl, buf, need.value, None)
-        return buf.value.decode()
+        return self._source("gjx_backsim_plan_source", impl)
 
     def move_compile_check(self, impl: int) -> int:
         """gjx_backmove_plan_compile_check: the MCMC move kernels of the same table (include/gjx_backmove.h)."""
@@ -1073,23 +1079,13 @@ class BacksimPlan:
         return self.ops.lib._gjx_backmove_plan_compile_check(self.handle, impl)
 
     def move_source(self, impl: int) -> str:
-        need = C.c_size_t()
-        self.ops.lib.call("gjx_backmove_plan_source", self.handle, impl, None, 0, C.byref(need))
-        buf = C.create_string_buffer(need.value)
-        self.ops.lib.call("gjx_backmove_plan_source", self.handle, impl, buf, need.value, None)
-        return buf.value.decode()
-
-    def __del__(self):
-        try:
-            if self.handle:
-                self.ops.lib.call("gjx_backsim_plan_destroy", self.handle)
-                self.handle = None
-        except Exception:
-            pass
+        return self._source("gjx_backmove_plan_source", impl)
 
 
-class TemperPlan:
+class TemperPlan(PlanHandle):
     """A gjx_temper_plan (include/gjx_temper.h): the generated move kernel of one static model's site table."""
+
+    _destroy = "gjx_temper_plan_destroy"
 
     def __init__(self, ops: "Ops", handle, n_latents: int):
         self.ops, self.handle, self.n_latents = ops, handle, n_latents
@@ -1106,35 +1102,17 @@ class TemperPlan:
         return self.ops.lib._gjx_temper_plan_compile_check(self.handle, impl)
 
     def source(self, impl: int) -> str:
-        need = C.c_size_t()
-        self.ops.lib.call("gjx_temper_plan_source", self.handle, impl, None, 0, C.byref(need))
-        buf = C.create_string_buffer(need.value)
-        self.ops.lib.call("gjx_temper_plan_source", self.handle, impl, buf, need.value, None)
-        return buf.value.decode()
-
-    def __del__(self):
-        try:
-            if self.handle:
-                self.ops.lib.call("gjx_temper_plan_destroy", self.handle)
-                self.handle = None
-        except Exception:
-            pass
+        return self._source("gjx_temper_plan_source", impl)
 
 
-class ScanPlan:
+class ScanPlan(PlanHandle):
+    _destroy = "gjx_scan_plan_destroy"
+
     def __init__(self, ops: "Ops", handle, n_state: int, n_obs: int):
         self.ops, self.handle, self.n_state, self.n_obs = ops, handle, n_state, n_obs
 
     def compile_check(self, impl: int) -> int:
         return self.ops.lib._gjx_scan_plan_compile_check(self.handle, impl)
-
-    def __del__(self):
-        try:
-            if self.handle:
-                self.ops.lib.call("gjx_scan_plan_destroy", self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
 
 @dataclass
@@ -1149,7 +1127,9 @@ class RowStats:
     q_out: torch.Tensor | None = None  # int64[1] fixed-point sum of that fold
 
 
-class Plan:
+class Plan(PlanHandle):
+    _destroy = "gjx_plan_destroy"
+
     def __init__(self, ops: Ops, handle, n_sites: int):
         self.ops, self.handle, self.n_sites = ops, handle, n_sites
         self.params_owner = None
@@ -1163,14 +1143,6 @@ class Plan:
         self.ops.lib.call("gjx_plan_set_params", self.handle, C.c_void_p(v.ctypes.data) if v.size else None, int(v.size))
         self.params_owner = None  # (whoever set them may claim them afterwards: see ImportanceK._fast_estimate)
         return self
-
-    def __del__(self):
-        try:
-            if self.handle:
-                self.ops.lib.call("gjx_plan_destroy", self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
 
 class PreparedImportance:

@@ -58,6 +58,16 @@ def importance_source(ops, plan, impl):
     return buf.value.decode()
 
 
+def source_shape(src):
+    """-> (struct names, kernel names, the source without its one generated struct and without the prelude's #include):
+    what a generated source of the fixed-body kinds consists of (gjx_plan_jit.hpp: a generator emits what the table decides)."""
+    src = src.replace('#include "gjx_device.hpp"\n', "")
+    structs = re.findall(r"^struct (\w+) \{$", src, flags=re.M)
+    kernels = re.findall(r'^extern "C" __global__ __launch_bounds__\(256\) void (\w+)\(', src, flags=re.M)
+    rest = re.sub(r"^struct \w+ \{\n.*?^\};\n", "", src, flags=re.M | re.S)
+    return structs, kernels, rest
+
+
 def kernel_notes(src, tmp_path, name):
     """Compile `src` with the helper the library itself uses (the code object stays at tmp_path / f"{name}.co") and read its
     notes -> {kernel: {field: int}}, fields vgpr_count, agpr_count, sgpr_count, private_segment_fixed_size."""

@@ -17,7 +17,7 @@ from genjax._amd.abi import GjxError
 from genjax._amd.runtime import use_ops
 from genjax._amd.smc_plan import build_transition_table
 from genjax.inference.smc import BootstrapSMC, GuidedSMC, LinearGaussianSSM, StateSpaceModel
-from offline import ROOT, header_symbols, kernel_notes, ops  # noqa: F401
+from offline import ROOT, header_symbols, kernel_notes, ops, source_shape  # noqa: F401
 
 Y = [("y",)]
 SYMBOLS = {"gjx_backmove_version", "gjx_backmove_plan_source", "gjx_backmove_plan_compile_check", "gjx_backmove_workspace_bytes",
@@ -182,10 +182,30 @@ def test_generated_move_kernels_compile_offline(ops, oracle_ops):
             src = plan.move_source(impl)
             assert "gjx_backmove_step_kernel" in src and "gjx_backmove_last_kernel" in src and "trans_lp(" in src
             assert "gjx_backsim_step_kernel" not in src and "gjx_backmove" not in plan.source(impl)  # a module of its own
-            assert src.count("nx_") > 0 and f"Stream<{impl}>" in src
+            # the generator is baked into the source: both entry points instantiate their helpers for it, the other's streams are absent
+            entries = src.split('extern "C"')[1:]
+            assert src.count("nx_") > 0 and len(entries) == 2 and all(f"<{impl}," in e for e in entries)
+            assert f"Stream<{1 - impl}>" not in src
             assert plan.move_compile_check(impl) == 0, (name, impl)
     assert "logpdf_normal_pre(" in ops.backsim_plan_create(tables["lgssm"]).move_source(1)
     assert "logpdf_gamma(" in ops.backsim_plan_create(tables["gamma"]).move_source(1)
+
+
+def test_generated_move_source_is_the_table_walk_and_two_kernels(ops):
+    """The search, the draw, the blocks of moves and the stores are gjx_device.hpp's backmove_* templates.  The two kernels'
+    own loops over paths (and the LDS array they hand to backmove_stage) are still generated: moved into a device function
+    they compile to other machine code (profiles/fixed_bodies_summary.md), so outside the struct the source holds the two
+    entry points and nothing else — one grid-stride loop and one LDS array each, no search loop, no atomic."""
+    plan = ops.backsim_plan_create(_table(ops, B.lgssm_model()))
+    for impl in (0, 1):
+        structs, kernels, rest = source_shape(plan.move_source(impl))
+        assert structs == ["GenTrans"] and kernels == ["gjx_backmove_step_kernel", "gjx_backmove_last_kernel"]
+        assert "bm_" not in plan.move_source(impl)
+        assert rest.startswith("using namespace gjx;\nextern \"C\"") and "__device__" not in rest and "template" not in rest
+        assert "while (" not in rest and "atomic" not in rest
+        step, last = rest.split('extern "C"')[1:]
+        assert step.count("__shared__") == last.count("__shared__") == 1
+        assert step.count("for (") == 3 and last.count("for (") == 1  # paths; the next state's D columns; blocks of four moves
 
 
 def test_philox_lgssm_move_kernel_occupancy(ops, tmp_path):

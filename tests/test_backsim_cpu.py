@@ -21,7 +21,7 @@ from genjax._amd.runtime import use_ops
 from genjax._amd.smc_models import HmmFilter, LgssmFilter
 from genjax._amd.smc_plan import build_smc_plan, build_transition_table
 from genjax.inference.smc import BootstrapSMC, DiscreteHMM, LinearGaussianSSM, StateSpaceModel
-from offline import kernel_notes, llvm_tool, ops  # noqa: F401
+from offline import kernel_notes, llvm_tool, ops, source_shape  # noqa: F401
 
 Y = [("y",)]
 
@@ -298,12 +298,31 @@ def test_generated_kernels_compile_offline(ops, oracle_ops, tmp_path):
         for impl in (0, 1):
             src = plan.source(impl)
             assert "gjx_backsim_step_kernel" in src and "gjx_backsim_last_kernel" in src and "trans_lp(" in src
-            assert src.count("nx_") > 0 and f"Stream<{impl}>" in src
+            # the generator is baked into the source: both entry points instantiate their body for it, the other's streams are absent
+            entries = src.split('extern "C"')[1:]
+            assert src.count("nx_") > 0 and len(entries) == 2 and all(f"backsim_body<{impl}," in e for e in entries)
+            assert f"Stream<{1 - impl}>" not in src
             assert plan.compile_check(impl) == 0, (name, impl)
     # the lowered distributions are the spec's own device functions
     assert "logpdf_normal_pre(" in ops.backsim_plan_create(tables["lgssm"]).source(1)
     assert "logpdf_gamma(" in ops.backsim_plan_create(tables["gamma"]).source(1)
     assert "jrow_lse(" in ops.backsim_plan_create(tables["hmm"]).source(1)  # (offline: no derived table yet)
+
+
+def test_generated_source_is_the_table_walk_and_two_instantiations(ops):
+    plan = ops.backsim_plan_create(_table(ops, B.lgssm_model()))
+    for impl in (0, 1):
+        structs, kernels, rest = source_shape(plan.source(impl))
+        assert structs == ["GenTrans"] and kernels == ["gjx_backsim_step_kernel", "gjx_backsim_last_kernel"]
+        for fixed in ("for (", "while (", "__shared__", "atomic"):  # the fixed body is gjx_device.hpp backsim_body
+            assert fixed not in rest, (impl, fixed, rest)
+        assert rest.count("\n") == 3, rest  # `using namespace gjx;` and one line per entry point
+
+
+def test_the_device_header_compiles_without_a_body_user(ops):
+    """The fixed bodies are templates over device-only calls (wave scans, a 64-bit atomic maximum, LDS): a source that
+    instantiates none of them — every importance, scan and filter kernel — still compiles against the header."""
+    assert ops.lib._gjx_jit_compile_source(b'#include "gjx_device.hpp"\nextern "C" __global__ void k() {}\n') == 0
 
 
 def test_philox_lgssm_kernel_occupancy_and_inner_loop(ops, tmp_path):
