@@ -1747,6 +1747,15 @@ struct TemperArgs {
   uint32_t n_moves;
   uint32_t recompute;
 };
+// The data columns of a plated tempered plan (include/gjx_plate.h): one more by-value kernel argument, of plated plans only.
+// Every lane reads row d of a column at the same moment; the generated loop reads the columns through pointers to the
+// CONSTANT address space (the data is not written while the kernel runs), so a row block is one scalar load per column.
+constexpr int kPlateMaxCols = 16;
+struct PlateData {
+  const float* col[kPlateMaxCols];
+  uint32_t n_rows;
+};
+typedef const __attribute__((address_space(4))) float* PlateCol;
 
 // ---- the fixed device code of the backward-simulation and backward-move kernels ---------------------------------------
 // What the site table decides reaches it as template arguments: the generator, the number of carry components D, and a

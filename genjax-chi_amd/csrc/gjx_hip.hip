@@ -14,6 +14,7 @@
 #include "../../include/gjx_smc_params.h"
 #include "../../include/gjx_csmc.h"
 #include "../../include/gjx_temper.h"
+#include "../../include/gjx_plate.h"
 // The library's own kernels keep the Philox round's plain XOR chain (gjx_device.hpp xor3): with v_bitop3_b32 the one-filter
 // LGSSM step measured 0.5 % slower (8.96e10 against 9.01e10 particle-steps/s, three alternating runs each, parent's range
 // 0.1 %), while the generated kernels, which include the header on their own, gain 6 % (importance) and 12 % (LGSSM scan);
@@ -4778,6 +4779,16 @@ struct gjx_temper_plan {
   std::vector<void*> dev_owned;  // per-row tables of categorical (observed) sites
   std::mutex mu;
   gjx_jit::CompiledTemper jit[2];
+  // include/gjx_plate.h: PLATED sites (gjx_temper_plan_create_plated) and their data columns (gjx_temper_plan_set_data)
+  bool plated = false;
+  int max_data = -1;  // highest data column the table reads
+  bool has_data = false;
+  PlateData data;
+  struct ObsExprStore {
+    gjx_expr_op ops[GJX_MAX_SITES][GJX_MAX_EXPR_OPS];
+  };
+  ObsExprStore* obs_expr = nullptr;  // the programs of PLATED sites' observed values (a plan's own copy, as ExprStore)
+  ~gjx_temper_plan() { delete obs_expr; }
 };
 
 namespace {
@@ -4795,6 +4806,60 @@ gjx_jit::CompiledTemper* temper_compiled(gjx_temper_plan* p, int impl) {
     return c.load(temper_source(p, impl, &c.tabs), gjx_jit::PlanKind::temper, {"gjx_temper_move_kernel"}, {&c.move});
   });
   return ready ? &c : nullptr;
+}
+
+// ---- plated sites (include/gjx_plate.h) --------------------------------------------------------------------------------
+// One site of a table given to gjx_temper_plan_create_plated.  A site without DATA operands in mode 0 / 1 is converted as
+// gjx_temper_plan_create converts it.  A PLATED site is validated by convert_site over a copy in which every DATA operand
+// reads an input column instead (same index range, same places allowed) and the observed value is a literal; the converted
+// site then takes the caller's own arguments back.  Notes the highest data column in the plan.
+bool plated_convert_site(const gjx_site& st, int s, CSite& c, gjx_temper_plan* p) {
+  if (st.observed != 0 && st.observed != 1 && st.observed != GJX_SITE_PLATED) return false;
+  const bool two_args = st.dist != GJX_DIST_BERNOULLI && st.dist != GJX_DIST_CATEGORICAL;
+  gjx_site t = st;
+  gjx_expr_op prog[3][GJX_MAX_EXPR_OPS];
+  gjx_arg* as[3] = {&t.arg[0], &t.arg[1], &t.obs};
+  bool any = false, in_obs = false;
+  int mx = -1;
+  for (int k = 0; k < 3; ++k) {
+    if ((k == 1 && !two_args) || (k == 2 && !st.observed)) continue;  // (not read: as convert_site ignores them)
+    gjx_arg& a = *as[k];
+    bool here = false;
+    if (a.kind == GJX_ARG_DATA) {
+      if (a.ref < 0 || a.ref >= GJX_PLATE_MAX_COLS) return false;
+      if (a.ref > mx) mx = a.ref;
+      a.kind = GJX_ARG_INPUT;
+      here = true;
+    } else if (a.kind == GJX_ARG_EXPR) {
+      const gjx_expr_op* ops = reinterpret_cast<const gjx_expr_op*>(a.table);
+      if (!ops || a.ref < 1 || a.ref > GJX_MAX_EXPR_OPS) return false;
+      memcpy(prog[k], ops, sizeof(gjx_expr_op) * (size_t)a.ref);
+      for (int i = 0; i < a.ref; ++i)
+        if (prog[k][i].op == GJX_EXPR_DATA) {
+          if (prog[k][i].ref < 0 || prog[k][i].ref >= GJX_PLATE_MAX_COLS) return false;
+          if (prog[k][i].ref > mx) mx = prog[k][i].ref;
+          prog[k][i].op = GJX_EXPR_INPUT;
+          here = true;
+        }
+      a.table = reinterpret_cast<const float*>(prog[k]);
+    }
+    any = any || here;
+    if (k == 2) in_obs = here;
+  }
+  if (st.observed != GJX_SITE_PLATED) return !any && convert_site(st, s, c);
+  if (!in_obs || st.dist == GJX_DIST_CATEGORICAL) return false;
+  if (t.obs.kind == GJX_ARG_EXPR && !expr_ok(t.obs, s, -1, -1, false)) return false;
+  t.observed = 1;
+  if (t.obs.kind == GJX_ARG_EXPR) t.obs = gjx_arg{GJX_ARG_CONST, 0, 0.0f, 0.0f, nullptr};
+  if (!convert_site(t, s, c)) return false;
+  c.observed = GJX_SITE_PLATED;
+  c.a0 = carg(st.arg[0]);
+  if (two_args) c.a1 = carg(st.arg[1]);
+  c.obs = carg(st.obs);
+  p->plated = true;
+  if (mx > p->max_data) p->max_data = mx;
+  if (!p->obs_expr) p->obs_expr = new gjx_temper_plan::ObsExprStore;
+  return true;
 }
 
 // ---- the ESS ladder -------------------------------------------------------------------------------------------------
@@ -4905,22 +4970,20 @@ __global__ __launch_bounds__(kBlock) void k_temper_ladder(LadderArgs a) {
     __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
-}  // namespace
 
-extern "C" {
-
-int gjx_temper_version(int* major, int* minor) { return version_out(major, minor, GJX_TEMPER_VERSION_MAJOR, GJX_TEMPER_VERSION_MINOR); }
-int gjx_temper_plan_create(const gjx_site* sites, int n_sites, uint32_t flags, gjx_temper_plan** out) {
+// gjx_temper_plan_create (allow_plated = false) and gjx_temper_plan_create_plated (include/gjx_plate.h)
+int temper_plan_create(const gjx_site* sites, int n_sites, uint32_t flags, gjx_temper_plan** out, bool allow_plated) {
   if (!sites || !out || n_sites < 1 || n_sites > GJX_MAX_SITES || flags != 0u) return GJX_ERR_INVALID;
   gjx_temper_plan* p = new (std::nothrow) gjx_temper_plan;
   if (!p) return GJX_ERR_LAUNCH;
   p->n_sites = n_sites; p->n_latents = 0; p->n_params = 0; p->max_param = -1; p->max_input = -1;
   memset(&p->prm, 0, sizeof p->prm);
+  memset(&p->data, 0, sizeof p->data);
   int n_observed = 0;
   bool ok = true;
   for (int s = 0; ok && s < n_sites; ++s) {
     CSite& c = p->sites[s];
-    ok = convert_site(sites[s], s, c);
+    ok = allow_plated ? plated_convert_site(sites[s], s, c, p) : convert_site(sites[s], s, c);
     if (!ok) break;
     if (c.observed) ++n_observed;
     else if (c.dist > GJX_DIST_BETA) ok = false;  // an integer-valued latent has no random-walk move
@@ -4939,7 +5002,44 @@ int gjx_temper_plan_create(const gjx_site* sites, int n_sites, uint32_t flags, g
   const int mp = expr_max_ref(p->sites, n_sites, GJX_EXPR_PARAM), mi = expr_max_ref(p->sites, n_sites, GJX_EXPR_INPUT);
   if (mp > p->max_param) p->max_param = mp;
   if (mi > p->max_input) p->max_input = mi;
+  if (p->plated) {  // the observed values' programs: the plan's own copy; what they read besides data
+    for (int s = 0; s < n_sites; ++s) {
+      CArg& o = p->sites[s].obs;
+      if (p->sites[s].observed != GJX_SITE_PLATED || o.kind != GJX_ARG_EXPR) continue;
+      memcpy(p->obs_expr->ops[s], o.table, sizeof(gjx_expr_op) * (size_t)o.ref);
+      o.table = reinterpret_cast<const float*>(p->obs_expr->ops[s]);
+      for (int k = 0; k < o.ref; ++k) {
+        const gjx_expr_op& e = p->obs_expr->ops[s][k];
+        if (e.op == GJX_EXPR_PARAM && e.ref > p->max_param) p->max_param = e.ref;
+        if (e.op == GJX_EXPR_INPUT && e.ref > p->max_input) p->max_input = e.ref;
+      }
+    }
+  }
   *out = p;
+  return GJX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int gjx_temper_version(int* major, int* minor) { return version_out(major, minor, GJX_TEMPER_VERSION_MAJOR, GJX_TEMPER_VERSION_MINOR); }
+int gjx_temper_plan_create(const gjx_site* sites, int n_sites, uint32_t flags, gjx_temper_plan** out) {
+  return temper_plan_create(sites, n_sites, flags, out, false);
+}
+int gjx_plate_version(int* major, int* minor) { return version_out(major, minor, GJX_PLATE_VERSION_MAJOR, GJX_PLATE_VERSION_MINOR); }
+int gjx_temper_plan_create_plated(const gjx_site* sites, int n_sites, uint32_t flags, gjx_temper_plan** out) {
+  return temper_plan_create(sites, n_sites, flags, out, true);
+}
+int gjx_temper_plan_set_data(gjx_temper_plan* p, const float* const* cols, int n_cols, uint64_t n_rows) {
+  if (!p || !p->plated || !cols || n_cols < 1 || n_cols > GJX_PLATE_MAX_COLS || n_cols <= p->max_data || n_rows < 1 ||
+      n_rows >= (1ull << 31))
+    return GJX_ERR_INVALID;
+  for (int c = 0; c <= p->max_data; ++c)
+    if (!cols[c]) return GJX_ERR_INVALID;
+  memset(&p->data, 0, sizeof p->data);
+  for (int c = 0; c < n_cols; ++c) p->data.col[c] = cols[c];
+  p->data.n_rows = (uint32_t)n_rows;
+  p->has_data = true;
   return GJX_OK;
 }
 int gjx_temper_plan_destroy(gjx_temper_plan* p) {
@@ -4972,7 +5072,7 @@ int gjx_temper_move(gjx_temper_plan* p, const gjx_temper_io* io, gjx_stream s) {
   if (!io->lp_out || !io->ll_out || (!io->recompute && (!io->lp_in || !io->ll_in)) || (io->n_moves > 0 && !io->scales))
     return GJX_ERR_INVALID;
   if (io->n_input_cols < 0 || io->n_input_cols > 16 || io->n_input_cols <= p->max_input || (io->n_input_cols && !io->input_cols) ||
-      p->n_params <= p->max_param)
+      p->n_params <= p->max_param || (p->plated && !p->has_data))
     return GJX_ERR_INVALID;
   TemperArgs A;
   memset(&A, 0, sizeof A);
@@ -5003,7 +5103,8 @@ int gjx_temper_move(gjx_temper_plan* p, const gjx_temper_io* io, gjx_stream s) {
   if (io->max_workgroups && grid > io->max_workgroups) grid = io->max_workgroups;
   PlanParams prm = p->prm;
   PlanTables tabs = k->tabs;
-  void* args[] = {&A, &cols, &prm, &tabs};
+  PlateData pd = p->data;
+  void* args[] = {&A, &cols, &prm, &tabs, &pd};  // (the kernel of a plan without plated sites takes the first four)
   return launch_generated(k->move, grid, 1, kBlock, s, args);
 }
 

@@ -188,6 +188,8 @@ struct SiteEmitter {
         return "((" + flit(a.scale) + " * cols.in[" + std::to_string(a.ref) + "][li" + sfx + "]) + " + flit(a.offset) + ")";
       case GJX_ARG_STATE: return "((" + flit(a.scale) + " * st_" + std::to_string(a.ref) + sfx + ") + " + flit(a.offset) + ")";
       case GJX_ARG_OBS: return "((" + flit(a.scale) + " * a.obs[" + std::to_string(a.ref) + "]) + " + flit(a.offset) + ")";
+      // (include/gjx_plate.h: column `ref` at the row of the plated loop — dc<ref> is the row's value, defined by GenTemper)
+      case GJX_ARG_DATA: return "((" + flit(a.scale) + " * dc" + std::to_string(a.ref) + ") + " + flit(a.offset) + ")";
       case GJX_ARG_PARAM:
         // (an SMC plan's parameter as it stands is the row's value itself: no multiply by 1, no add of 0 — a uniform value
         // stays in its scalar register — and what gjx_smc_plan_set_params derives the site's constants from)
@@ -207,6 +209,7 @@ struct SiteEmitter {
             case GJX_EXPR_PARAM: st.push_back("prm.p[" + r + "]"); break;
             case GJX_EXPR_STATE: st.push_back("st_" + r + sfx); break;
             case GJX_EXPR_OBS: st.push_back("a.obs[" + r + "]"); break;
+            case GJX_EXPR_DATA: st.push_back("dc" + r); break;
             case GJX_EXPR_NEG: st.back() = "(-" + st.back() + ")"; break;
             case GJX_EXPR_EXP: st.back() = "e_exp(" + st.back() + ")"; break;
             case GJX_EXPR_LOG: st.back() = "m_log(" + st.back() + ")"; break;
@@ -298,7 +301,7 @@ struct SiteEmitter {
           float stk[8];
           int d = 0;
           for (int k = 0; k < a.ref; ++k) {
-            if (ops[k].op >= GJX_EXPR_SITE && ops[k].op <= GJX_EXPR_OBS) return arg(a);  // (not a constant)
+            if ((ops[k].op >= GJX_EXPR_SITE && ops[k].op <= GJX_EXPR_OBS) || ops[k].op == GJX_EXPR_DATA) return arg(a);  // (not a constant)
             if (ops[k].op == GJX_EXPR_CONST) { stk[d++] = ops[k].value; continue; }
             if (ops[k].op == GJX_EXPR_NEG) { stk[d - 1] = -stk[d - 1]; continue; }
             if (ops[k].op == GJX_EXPR_EXP) { stk[d - 1] = gjx::e_exp(stk[d - 1]); continue; }
@@ -343,7 +346,7 @@ struct SiteEmitter {
       }
       else if (st.obs.kind == GJX_ARG_OBS) ov = "a.obs[" + std::to_string(st.obs.ref) + "]";
       else if (st.obs.kind == GJX_ARG_NEXT) ov = "nx_" + std::to_string(st.obs.ref);  // (transition tables: gjx_backsim.h)
-      else if (st.obs.kind == GJX_ARG_PARAM) ov = arg(st.obs);
+      else if (st.obs.kind == GJX_ARG_PARAM || st.obs.kind == GJX_ARG_DATA || st.obs.kind == GJX_ARG_EXPR) ov = arg(st.obs);  // (DATA, EXPR: a plated site's)
       else ov = "cols.in[" + std::to_string(st.obs.ref) + "][li" + sfx + "]";
       if (is_int(st)) o << ind << "const int32_t vi" << Q << " = (int32_t)__builtin_rintf(" << ov << ");\n";
       else o << ind << "const float vf" << Q << " = " << ov << ";\n";
@@ -483,7 +486,7 @@ struct SiteEmitter {
       if (a.kind != GJX_ARG_EXPR) return false;
       const gjx_expr_op* ops = reinterpret_cast<const gjx_expr_op*>(a.table);
       for (int k = 0; k < a.ref; ++k)
-        if (ops[k].op >= GJX_EXPR_SITE && ops[k].op <= GJX_EXPR_OBS) return false;
+        if ((ops[k].op >= GJX_EXPR_SITE && ops[k].op <= GJX_EXPR_OBS) || ops[k].op == GJX_EXPR_DATA) return false;
       return true;
     };
     const bool all_const = st.observed == 1 && st.obs.kind == GJX_ARG_CONST && is_const(st.a0) &&
@@ -1377,6 +1380,10 @@ struct GenBackmove {
 //            for the lazy children of p_r.  Under PHILOX latents 2 k and 2 k + 1 read the same pair block (one cipher
 //            call after common-subexpression elimination).
 //   keys     fold_in(key, r) and its two children are wave-uniform: three cipher blocks per sweep on the scalar side.
+//   plated   a GJX_SITE_PLATED site (include/gjx_plate.h) is a loop over the data rows inside tm_assess (emit_plated): its
+//            arguments and value read the row of the data columns, its f32 log-densities enter ll through a float64 sum.  The
+//            columns and the row count are one more kernel argument (PlateData pd), of plated plans only: the source of a
+//            table without plated sites is what it was before they existed, byte for byte.
 // No LDS (the Box-Muller tables are read from the constant arrays: GJX_BM_LDS is not defined), no barrier.
 template <class CSiteT, class CArgT>
 struct GenTemper {
@@ -1385,12 +1392,62 @@ struct GenTemper {
   const CSiteT* sites;
   int n_sites;
 
+  // The data columns plated site q reads (a0, a1, obs; affine operands and program leaves), in ascending order.
+  static std::vector<int> plate_cols(const CSiteT& st) {
+    bool used[GJX_PLATE_MAX_COLS] = {};
+    for (const CArgT* a : {&st.a0, &st.a1, &st.obs}) {
+      if (a->kind == GJX_ARG_DATA) used[a->ref] = true;
+      if (a->kind != GJX_ARG_EXPR) continue;
+      const gjx_expr_op* ops = reinterpret_cast<const gjx_expr_op*>(a->table);
+      for (int k = 0; k < a->ref; ++k)
+        if (ops[k].op == GJX_EXPR_DATA) used[ops[k].ref] = true;
+    }
+    std::vector<int> cs;
+    for (int c = 0; c < GJX_PLATE_MAX_COLS; ++c)
+      if (used[c]) cs.push_back(c);
+    return cs;
+  }
+  // A PLATED site (include/gjx_plate.h) at its table position: the loop over the data rows.  The row index is a counter
+  // against a kernel argument and the columns are constant-address-space pointers out of the argument block, so every read
+  // is a wave-uniform SCALAR load; a block of kPlateBlock rows issues its loads (one s_load_dwordx4 per column) before its
+  // arithmetic, a remainder loop takes the last n_rows % kPlateBlock rows.  Rows enter the float64 sum in index order.
+  static constexpr int kPlateBlock = 4;
+  void emit_plated(int q, const CSiteT* tab) {
+    const std::vector<int> cs = plate_cols(tab[q]);
+    const std::string Q = std::to_string(q);
+    std::ostringstream body;  // one row: head (arguments and value from dc<c>), the log-density, the float64 accumulate
+    SiteEmitter<CSiteT, CArgT> e{body, impl, 0, tab, n_sites, "      ", ""};
+    e.head(q);
+    body << "      pacc" << Q << " = pacc" << Q << " + (double)(" << e.lp_of(q) << ");\n";
+    o << "  // site " << q << ": plated over pd.n_rows data rows\n";
+    for (int c : cs) o << "  const PlateCol pc" << Q << "_" << c << " = (PlateCol)pd.col[" << c << "];\n";
+    o << "  double pacc" << Q << " = 0.0;\n  uint32_t d" << Q << " = 0u;\n";
+    o << "  for (; d" << Q << " + " << kPlateBlock << "u <= pd.n_rows; d" << Q << " += " << kPlateBlock << "u) {\n";
+    for (int c : cs)
+      for (int j = 0; j < kPlateBlock; ++j)
+        o << "    const float r" << c << "_" << j << " = pc" << Q << "_" << c << "[d" << Q << " + " << j << "u];\n";
+    for (int j = 0; j < kPlateBlock; ++j) {
+      o << "    {\n";
+      for (int c : cs) o << "      const float dc" << c << " = r" << c << "_" << j << ";\n";
+      o << body.str() << "    }\n";
+    }
+    o << "  }\n  for (; d" << Q << " < pd.n_rows; ++d" << Q << ") {\n    {\n";
+    for (int c : cs) o << "      const float dc" << c << " = pc" << Q << "_" << c << "[d" << Q << "];\n";
+    o << body.str() << "    }\n  }\n";
+    o << "  ll = ll + (float)pacc" << Q << ";\n";
+  }
+
   std::string run() {
     const std::string I = std::to_string(impl);
     emit_prelude(o);
     std::vector<CSiteT> tab(sites, sites + n_sites);
     int L = 0;
+    bool plated = false;
     for (int q = 0; q < n_sites; ++q) {
+      if (sites[q].observed == GJX_SITE_PLATED) {  // (emitted as an observed site inside its loop over the data rows)
+        tab[q].observed = 1;
+        plated = true;
+      }
       if (sites[q].observed) continue;
       tab[q].observed = 1;
       tab[q].obs = CArgT{};
@@ -1404,10 +1461,14 @@ struct GenTemper {
       return t;
     };
     o << "__device__ __forceinline__ void tm_assess(const RunCols& cols, const PlanParams& prm, const PlanTables& tabs, uint32_t li"
-      << list(", float nx_") << ", float& lp_out, float& ll_out) {\n";
+      << list(", float nx_") << ", float& lp_out, float& ll_out" << (plated ? ", const PlateData& pd" : "") << ") {\n";
     o << "  (void)cols; (void)prm; (void)tabs; (void)li;\n  float lp = 0.0f, ll = 0.0f;\n";
     SiteEmitter<CSiteT, CArgT> e{o, impl, 0, tab.data(), n_sites, "  ", ""};
     for (int q = 0; q < n_sites; ++q) {
+      if (sites[q].observed == GJX_SITE_PLATED) {
+        emit_plated(q, tab.data());
+        continue;
+      }
       e.head(q);
       if (sites[q].observed) {
         o << "  ll = ll + " << e.lp_of(q) << ";\n";
@@ -1421,14 +1482,15 @@ struct GenTemper {
       else o << "  lp = lp + (" << in << " ? " << e.lp_of(q) << " : -__builtin_inff());\n";
     }
     o << "  lp_out = lp; ll_out = ll;\n}\n";
-    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_temper_move_kernel(TemperArgs a, RunCols cols, PlanParams prm, PlanTables tabs) {\n";
+    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_temper_move_kernel(TemperArgs a, RunCols cols, PlanParams prm, PlanTables tabs"
+      << (plated ? ", PlateData pd" : "") << ") {\n";
     o << "  const uint32_t n = a.n;\n";
     o << "  for (uint64_t i64 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i64 < n; i64 += (uint64_t)gridDim.x * blockDim.x) {\n";
     o << "    const uint32_t i = (uint32_t)i64;\n";
     o << "    uint32_t an = a.anc ? (uint32_t)a.anc[i] : i;\n    an = an < n ? an : n - 1u;\n";
     for (int l = 0; l < L; ++l) o << "    float x" << l << " = a.x_in[" << l << "][an];\n";
     o << "    float lp, ll;\n";
-    o << "    if (a.recompute) tm_assess(cols, prm, tabs, i" << list(", x") << ", lp, ll);\n";
+    o << "    if (a.recompute) tm_assess(cols, prm, tabs, i" << list(", x") << ", lp, ll" << (plated ? ", pd" : "") << ");\n";
     o << "    else { lp = a.lp_in[an]; ll = a.ll_in[an]; }\n";
     o << "    int32_t acc = 0;\n";
     o << "    for (uint32_t r = 0; r < a.n_moves; ++r) {\n";
@@ -1440,7 +1502,7 @@ struct GenTemper {
       o << "      const float t" << l << " = a.scales[" << l << "] * site_normal<" << I << ">(Stream<" << I << ">(pk, true, " << fold << "u));\n";
       o << "      const float y" << l << " = x" << l << " + t" << l << ";\n";
     }
-    o << "      float lpn, lln;\n      tm_assess(cols, prm, tabs, i" << list(", y") << ", lpn, lln);\n";
+    o << "      float lpn, lln;\n      tm_assess(cols, prm, tabs, i" << list(", y") << ", lpn, lln" << (plated ? ", pd" : "") << ");\n";
     o << "      const float bh = a.beta * ll;\n      const float h = lp + bh;\n";
     o << "      const float bn = a.beta * lln;\n      const float hn = lpn + bn;\n";
     o << "      const float d = hn - h;\n";

@@ -96,6 +96,10 @@ class TemperUnavailable(HeaderUnavailable):
     header, why = "gjx_temper.h", "the tempered move runs as a generated HIP kernel only"
 
 
+class PlateUnavailable(HeaderUnavailable):
+    header, why = "gjx_plate.h", "plated likelihoods run inside the generated tempered move kernel only"
+
+
 class Keys(C.Structure):
     _fields_ = [
         ("impl", C.c_int32),
@@ -640,6 +644,19 @@ TEMPER_PROTOTYPES = {
 }
 TEMPER_ABI_VERSION = (0, 1)
 
+# include/gjx_plate.h: a NINTH header, same arrangement — plated likelihoods of a tempered plan: one observed site looped over
+# the rows of device data columns (a site mode, an argument kind and a program leaf of its own, a creator and a setter)
+SITE_PLATED = 4          # gjx_plate.h: GJX_SITE_PLATED (gjx_site.observed)
+ARG_DATA = 9             # ... GJX_ARG_DATA (gjx_arg.kind; GJX_ARG_NEXT is 8)
+EXPR_DATA = 21           # ... GJX_EXPR_DATA (gjx_expr_op.op)
+PLATE_MAX_COLS = 16      # ... GJX_PLATE_MAX_COLS
+PLATE_PROTOTYPES = {
+    "gjx_plate_version": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gjx_temper_plan_create_plated": (C.c_int, [C.POINTER(Site), C.c_int, C.c_uint32, C.POINTER(_P)]),
+    "gjx_temper_plan_set_data": (C.c_int, [_P, C.POINTER(C.c_void_p), C.c_int, C.c_uint64]),
+}
+PLATE_ABI_VERSION = (0, 1)
+
 # The optional headers, in the order they are bound: every one is exported by libgjx_hip.so only and bound if present.
 class Header(collections.namedtuple("Header", "key header version_fn prototypes version_name unavailable")):
     @property
@@ -665,6 +682,7 @@ PLAN_HEADERS = {h.key: h for h in (
            SmcParamsUnavailable),
     Header("csmc", "gjx_csmc.h", "gjx_csmc_version", CSMC_PROTOTYPES, "CSMC_ABI_VERSION", CsmcUnavailable),
     Header("temper", "gjx_temper.h", "gjx_temper_version", TEMPER_PROTOTYPES, "TEMPER_ABI_VERSION", TemperUnavailable),
+    Header("plate", "gjx_plate.h", "gjx_plate_version", PLATE_PROTOTYPES, "PLATE_ABI_VERSION", PlateUnavailable),
 )}
 
 

@@ -580,12 +580,18 @@ class Ops:
     # ---- tempered SMC for static models (include/gjx_temper.h) -----------------------------------------
     def temper_plan_create(self, sites: list, keep=()) -> "TemperPlan":
         """A gjx_temper_plan over a flat importance-style site table.  Raises abi.TemperUnavailable on a library without
-        include/gjx_temper.h (the CPU oracle)."""
+        include/gjx_temper.h (the CPU oracle).  A table that holds a PLATED site (include/gjx_plate.h) goes to
+        gjx_temper_plan_create_plated (abi.PlateUnavailable without that header)."""
         self.lib.require("temper", "gjx_temper_plan_create")
+        plated = any(s.observed == abi.SITE_PLATED for s in sites)
+        creator = "gjx_temper_plan_create_plated" if plated else "gjx_temper_plan_create"
+        if plated:
+            self.lib.require("plate", creator)
         arr = (abi.Site * max(1, len(sites)))(*sites)
         handle = C.c_void_p()
-        self.lib.call("gjx_temper_plan_create", arr, len(sites), 0, C.byref(handle))
+        self.lib.call(creator, arr, len(sites), 0, C.byref(handle))
         plan = TemperPlan(self, handle, int(self.lib.call("gjx_temper_plan_n_latents", handle)))
+        plan.plated = plated
         plan._keep = keep  # device tables and programs the sites point into
         return plan
 
@@ -1096,6 +1102,18 @@ class TemperPlan(PlanHandle):
         v = np.ascontiguousarray(np.asarray(values, dtype=np.float32).reshape(-1))
         self.ops.lib.call("gjx_temper_plan_set_params", self.handle,
                           v.ctypes.data_as(C.POINTER(C.c_float)) if v.size else None, int(v.size))
+        return self
+
+    def set_data(self, cols: list) -> "TemperPlan":
+        """gjx_temper_plan_set_data (include/gjx_plate.h): the data columns of the launches that follow — float32 device
+        tensors of one length, BORROWED by the library (the plan keeps them alive)."""
+        self.ops.lib.require("plate", "gjx_temper_plan_set_data")
+        if not cols:
+            raise ValueError("set_data: at least one column")
+        n_rows = cols[0].numel()
+        ptrs = (C.c_void_p * len(cols))(*[self.ops._chk(t, torch.float32, n_rows, f"data[{i}]").value for i, t in enumerate(cols)])
+        self.ops.lib.call("gjx_temper_plan_set_data", self.handle, ptrs, len(cols), n_rows)
+        self._data = list(cols)
         return self
 
     def compile_check(self, impl: int) -> int:

@@ -171,6 +171,11 @@ class _Rows:
         self.tracer, self.table, self.idx = tracer, table, idx
 
 
+def is_data_tensor(v) -> bool:
+    """A 1-D floating, integer or bool tensor with two or more elements: what a tempered plan reads as a data column."""
+    return isinstance(v, torch.Tensor) and v.dim() == 1 and v.numel() >= 2 and not v.is_complex()
+
+
 class SymExpr:
     """A traced f32 value beyond one affine step — `w * x + b` over two sites, `(z - m) * (z - m)`, ... — as the postfix
     program of `abi.ARG_EXPR`: operands push a value, `+ - * /` pop two, unary minus one; every operator is one f32 rounding,
@@ -185,7 +190,7 @@ class SymExpr:
             raise PlanUnsupported("expression too long for a plan argument")
         depth = deepest = 0
         for op, _, _ in prog:
-            depth += 1 if op <= abi.EXPR_OBS else (0 if op in abi.EXPR_UNARY else (-2 if op == abi.EXPR_SELECT else -1))
+            depth += 1 if op <= abi.EXPR_OBS or op == abi.EXPR_DATA else (0 if op in abi.EXPR_UNARY else (-2 if op == abi.EXPR_SELECT else -1))
             deepest = max(deepest, depth)
         if deepest > abi.MAX_EXPR_DEPTH:
             raise PlanUnsupported("expression too deep for a plan argument")
@@ -215,6 +220,8 @@ class SymExpr:
             return tracer, [(abi.EXPR_PARAM, tracer.param_slot(x), 0.0)]
         if Sym._is_const(x):
             return tracer, [(abi.EXPR_CONST, 0, cls._f32(x))]
+        if is_data_tensor(x) and hasattr(tracer, "data_col"):  # (a tempered plan: a 1-D tensor is a data column, temper.py)
+            return tracer, [(abi.EXPR_DATA, tracer.data_col(x), 0.0)]
         raise PlanUnsupported("unsupported operand in an expression over traced site values")
 
     @classmethod

@@ -17,20 +17,102 @@ import torch
 from . import abi, prng
 from .choicemap import ChoiceMap
 from .inference import ParticleCollection, SMCAlgorithm, Target
-from .lang import split
-from .plan import PlanTracer, PlanUnsupported, _make_plan, _needs_eager
+from .lang import bernoulli, split
+from .plan import PlanTracer, PlanUnsupported, SymExpr, _DIST_IDS, _make_plan, _needs_eager, is_data_tensor
 from .runtime import get_ops
 
 LADDER = 32  # candidates per ladder launch
 
 
 class _TemperTracer(PlanTracer):
-    """PlanTracer that names the address of whatever a tempered plan cannot hold."""
+    """PlanTracer that names the address of whatever a tempered plan cannot hold.
+
+    PLATED sites (include/gjx_plate.h).  In a tempered plan a 1-D tensor with two or more elements is always DATA — a
+    column of the data table, never a per-particle column (PlanTracer's reading of a length-n tensor does not apply: a
+    tempered plan has none).  A tensor becomes a column the first time it meets a traced value (`w * xs`: a program with a
+    DATA leaf, plan.SymExpr.program_of) or a site (an argument or the observed value); columns are deduplicated by the
+    tensor's memory and version.  A site with a data-dependent argument or value is ONE plated site."""
+
+    def __init__(self, constraint, n, use_params=True):
+        super().__init__(constraint, n, use_params)
+        self.data: list = []      # the data columns, as the model handed them over (uploaded as f32 at every run)
+        self._data_keys: dict = {}
+        self.data_rows = None     # D: one length per plan
+
+    def data_col(self, t: torch.Tensor) -> int:
+        # (identity is the memory: the body sees its tensor arguments as SpecTensor views of the caller's)
+        key = (t.data_ptr(), t.numel(), t.stride(0), t.dtype, str(t.device), t._version)
+        c = self._data_keys.get(key)
+        if c is None:
+            c = self._data_keys[key] = len(self.data)
+            self.data.append(t)
+        return c
+
+    def _data_cols_of(self, v) -> set:
+        """The data columns the argument / value `v` reads (a raw data tensor is registered here)."""
+        if is_data_tensor(v):
+            return {self.data_col(v)}
+        if isinstance(v, SymExpr):
+            return {ref for op, ref, _ in v.prog if op == abi.EXPR_DATA}
+        return set()
+
+    def _arg(self, v) -> abi.Arg:
+        if is_data_tensor(v):
+            return abi.Arg(abi.ARG_DATA, self.data_col(v), 1.0, 0.0, None)
+        return super()._arg(v)
 
     def _call(self, addr, gen_fn, args):
         raise PlanUnsupported(f"TemperedSMC: nested generative function at address {addr!r}")
 
+    def _plated(self, addr, gen_fn, args, obs, cols: set):
+        """One PLATED site: `gen_fn(*args) @ addr` with data-dependent arguments and / or a data column as its value."""
+        if obs is None:
+            raise PlanUnsupported(f"TemperedSMC: the latent at address {addr!r} depends on data (a vector-valued latent)")
+        if not is_data_tensor(obs):
+            raise PlanUnsupported(f"TemperedSMC: the site at address {addr!r} has data-dependent arguments: its observed value "
+                                  "must be a 1-D tensor of the same length")
+        if id(gen_fn) in _DIST_IDS:
+            dist = _DIST_IDS[id(gen_fn)]
+            vals = list(args[:1 if dist == abi.DIST_BERNOULLI else 2])
+        elif gen_fn is bernoulli and args[0][0] == "probs":
+            dist, vals = abi.DIST_BERNOULLI, [args[0][1]]
+        else:
+            raise PlanUnsupported(f"TemperedSMC: a plated site at address {addr!r} must be normal, gamma, beta or flip "
+                                  "(a plated categorical has no table rows per datum)")
+        if len(self.sites) >= abi.MAX_SITES:
+            raise PlanUnsupported(f"TemperedSMC: too many sites at address {addr!r}")
+        cols = cols | {self.data_col(obs)}
+        lengths = {int(self.data[c].numel()) for c in cols} | ({self.data_rows} if self.data_rows is not None else set())
+        if len(lengths) != 1:
+            raise PlanUnsupported(f"TemperedSMC: data columns of different lengths {sorted(lengths)} at address {addr!r} "
+                                  "(one plate length per plan)")
+        if len(self.data) > abi.PLATE_MAX_COLS:
+            raise PlanUnsupported(f"TemperedSMC: {len(self.data)} data columns (at most {abi.PLATE_MAX_COLS}) at address {addr!r}")
+        self.data_rows = lengths.pop()
+        site = abi.Site()
+        site.dist, site.observed, site.out_col = dist, abi.SITE_PLATED, -1
+        for k, v in enumerate(vals):
+            site.arg[k] = self._arg(v)
+        site.obs = abi.Arg(abi.ARG_DATA, self.data_col(obs), 1.0, 0.0, None)
+        self.sites.append(site)
+        self.items.append(("site", len(self.sites) - 1))
+        self.meta.append(dict(addr=addr, gen_fn=gen_fn, args=args, obs=obs, out_col=-1, is_int=dist == abi.DIST_BERNOULLI,
+                              dtype=gen_fn.value_dtype, path=self.prefix + (addr if isinstance(addr, tuple) else (addr,)),
+                              plated=True))
+        self.record(addr, None)
+        return obs  # (a constrained value may feed later sites: it is data there too)
+
     def handle_trace(self, addr, gen_fn, args):
+        from .lang import Categorical, Distribution
+
+        if isinstance(gen_fn, Distribution):
+            a = addr if isinstance(addr, tuple) else (addr,)
+            obs = self.constraint.get_submap(*a).get_value()
+            flat = [x for v in args for x in (v if isinstance(v, tuple) else (v,))]
+            # (a categorical's 1-D tensor argument is its logits / probs vector, not data)
+            cols = set().union(*[self._data_cols_of(v) for v in flat]) if flat and not isinstance(gen_fn, Categorical) else set()
+            if cols or is_data_tensor(obs):
+                return self._plated(addr, gen_fn, args, obs, cols)
         try:
             out = super().handle_trace(addr, gen_fn, args)
         except PlanUnsupported as e:
@@ -52,7 +134,7 @@ def lower(target: Target, n: int):
 
     if not isinstance(target.p, StaticGenerativeFunction):
         raise PlanUnsupported("TemperedSMC: the target's model must be a static @gen function")
-    if any(_needs_eager(a) for a in target.args):
+    if any(_needs_eager(a) and not is_data_tensor(a) for a in target.args):  # (a 1-D tensor is a data column)
         raise PlanUnsupported("TemperedSMC: the target's arguments need the per-site path")
     constraint = target.constraint.merge(ChoiceMap.empty())
     last = None
@@ -73,12 +155,43 @@ def lower(target: Target, n: int):
             raise PlanUnsupported(f"TemperedSMC: no latent site among the addresses {addrs!r}")
         if all(m["obs"] is None for m in tracer.meta):
             raise PlanUnsupported(f"TemperedSMC: no observed site among the addresses {addrs!r}")
+        if len(tracer.data) > abi.PLATE_MAX_COLS:  # (columns met after the last plated site)
+            raise PlanUnsupported(f"TemperedSMC: {len(tracer.data)} data columns (at most {abi.PLATE_MAX_COLS}) at address {addrs[-1]!r}")
         n_lat = sum(m["obs"] is None for m in tracer.meta)
         if n_lat > abi.TEMPER_MAX_LATENTS:
             raise PlanUnsupported(f"TemperedSMC: {n_lat} latents (at most {abi.TEMPER_MAX_LATENTS}); the last is at address "
                                   f"{[m['addr'] for m in tracer.meta if m['obs'] is None][-1]!r}")
         return tracer
     raise last
+
+
+class _PriorTable:
+    """What plan._make_plan reads of a tracer: the table of a plated plan without its plated sites."""
+
+    def __init__(self, tracer, sites, expr_progs, keep):
+        self.sites, self.expr_progs, self.keep = sites, expr_progs, keep
+        self.scopes, self.params, self.n_out = tracer.scopes, tracer.params, tracer.n_out
+
+
+def prior_table(tracer) -> _PriorTable:
+    """The importance table that draws stage 0 of a plated plan: its sites in order, the plated ones left out, every
+    reference to an earlier site renumbered (no site reads a plated one: its value is data)."""
+    new_of, sites, progs, keep = {}, [], {}, list(tracer.keep)
+    for q, s in enumerate(tracer.sites):
+        if s.observed == abi.SITE_PLATED:
+            continue
+        new_of[q] = len(sites)
+        c = abi.Site.from_buffer_copy(s)
+        for k in range(2):
+            a = c.arg[k]
+            if a.kind in (abi.ARG_SITE, abi.ARG_TABLE):
+                a.ref = new_of[a.ref]
+            elif a.kind == abi.ARG_EXPR:
+                prog = [(op, new_of[ref] if op == abi.EXPR_SITE else ref, val) for op, ref, val in tracer.expr_progs[a.table]]
+                c.arg[k] = abi.expr_arg(prog, keep)
+                progs[c.arg[k].table] = tuple(prog)
+        sites.append(c)
+    return _PriorTable(tracer, sites, progs, keep)
 
 
 def ladder_deltas(beta: float, lo=None, hi=None):
@@ -186,7 +299,8 @@ class TemperedSMC(SMCAlgorithm):
         tracer = lower(self.target, self.n_particles)
         latents = [m for m in tracer.meta if m["obs"] is None]
         tplan = ops.temper_plan_create(tracer.sites, keep=(tracer.keep, tracer))
-        st = self._st = dict(ops=ops, tracer=tracer, latents=latents, tplan=tplan, ws=None)
+        prior = prior_table(tracer) if tracer.data else None
+        st = self._st = dict(ops=ops, tracer=tracer, latents=latents, tplan=tplan, ws=None, prior=prior)
         return st
 
     def _scales(self, st):
@@ -219,9 +333,13 @@ class TemperedSMC(SMCAlgorithm):
         st = self._state()
         ops, tracer, tplan = st["ops"], st["tracer"], st["tplan"]
         n, L, K = self.n_particles, len(st["latents"]), self.n_moves
-        plan = _make_plan(tracer)  # (sets the importance plan's launch parameters)
+        # (sets the importance plan's launch parameters; a plated plan draws from the table WITHOUT its plated sites: they
+        # draw nothing, and the importance kernels do not know the mode)
+        plan = _make_plan(st["prior"] if st["prior"] is not None else tracer)
         if tracer.params:
             tplan.set_params(tracer.params)
+        if tracer.data:  # uploaded at every run: an in-place update of a data tensor is seen
+            tplan.set_data([t.detach().to(device=ops.device(), dtype=torch.float32).contiguous() for t in tracer.data])
         dtypes = [torch.float32] * tracer.n_out
         vals = ops.importance_run(plan, prng.split_lazy(prng.fold_in(key, 0), n), n, [], dtypes, want_score=False,
                                   want_max_partials=False)[0]
@@ -280,6 +398,10 @@ class TemperedSMC(SMCAlgorithm):
     def run_smc(self, key) -> ParticleCollection:
         """The final population as a ParticleCollection: traces through `Target.importance` with the latent columns as
         constraints, every log-weight f32(log Z-hat), so that logsumexp - log n reproduces the estimate."""
+        if self._state()["tracer"].data:
+            m = next(m for m in self._state()["tracer"].meta if m.get("plated"))
+            raise PlanUnsupported(f"TemperedSMC.run_smc: the plated site at address {m['addr']!r} has no per-site trace; use run() "
+                                  "or log_marginal_likelihood_estimate()")
         res = self.run(key)
         n = self.n_particles
         sub_keys = split(prng.fold_in(key, 0x7fffffff), n)

@@ -29,6 +29,8 @@
  *               are TFP's, NaN below 0 and finite there for a Gamma(1, b).  ll = the sum, taken the same way, of the
  *               observed sites' log-densities as those entry points return them.  One rounding per add, never
  *               contracted; arguments (affine forms, postfix programs) evaluate as in an importance plan.
+ *               (A plan made by gjx_temper_plan_create_plated may hold sites evaluated once per row of a data table; what
+ *               such a site adds to ll is specified in include/gjx_plate.h.  No table this header's creator accepts has one.)
  *   start       a = ancestors ? min((uint32) ancestors[i], n - 1) : i — no address is formed from an unchecked word;
  *               x_l = x_in[l][a].  recompute != 0: (lp, ll) = assess(x); otherwise lp = lp_in[a], ll = ll_in[a].
  *   keys        k_r = fold_in(key, r); p_r = fold_in(k_r, 0) the PROPOSAL key, a_r = fold_in(k_r, 1) the ACCEPTANCE key
