@@ -1757,6 +1757,16 @@ struct PlateData {
 };
 typedef const __attribute__((address_space(4))) float* PlateCol;
 
+// Kernel argument block of the pointwise launch over a plated plan (include/gjx_pointwise.h; the kernel is generated from the
+// site table, gjx_plan_jit.hpp GenPointwise; the fold below is fixed).  The workspace holds five float64 planes [W][n_rows]:
+// m (an f32 value, widened), s, s1, s2, c — lanes are rows, so every plane is written and read coalesced.
+struct PointwiseArgs {
+  const float* x[kTemperMaxLatents];  // latent columns: read at wave-uniform indices (scalar loads)
+  double* part;                       // [5][W][n_rows]
+  uint32_t n, per, W;                 // particles, particles per chunk, chunks
+};
+constexpr int kPointwiseBlock = 4;  // particles a lane takes per round of scalar loads
+
 // ---- the fixed device code of the backward-simulation and backward-move kernels ---------------------------------------
 // What the site table decides reaches it as template arguments: the generator, the number of carry components D, and a
 // generated struct whose static member is the table's walk — Trans::trans_lp(a, tabs, st, nx), the f32 sum of the transition
@@ -1930,6 +1940,87 @@ GJX_DEV void backmove_store(const BackmoveArgs& a, uint32_t j, uint32_t i) {
   for (int c = 0; c < D; ++c)
     if (a.path[c]) a.path[c][j] = a.col[c][i];
 }
+
+// ---- the fixed device code of the pointwise kernels (include/gjx_pointwise.h) -------------------------------------------
+// A lane is a data ROW; the generated kernel (gjx_plan_jit.hpp GenPointwise) hands it the row's terms of a block of NB
+// consecutive particles.  Moments first, then the online log-sum-exp with the BLOCK's maximum: one rescale of s per block
+// at the most, and none — not even its exponential — in a block in which no lane of the wave raised its maximum (the branch
+// is wave-uniform; a lane that did not raise its own keeps s as it is either way, so skipping is exact).  After the first few
+// hundred particles of a chunk a new maximum is rare: one exponential per term is what remains.  -inf and NaN entries enter
+// s1 and s2 by IEEE rules and nothing else (`>` is false on NaN).
+struct PointwiseAcc {
+  float m;
+  double s, s1, s2;
+  uint32_t c;  // (an integer add per term; widened when stored: n < 2^31)
+};
+// m_exp at an argument that is never above 0 (a term minus a maximum it entered), without m_exp's branches: the same bits
+GJX_DEV float pointwise_exp(float x) {
+  const float e = m_exp_core(x >= -86.0f ? x : -86.0f);
+  return x >= -86.0f ? e : 0.0f;  // (false on NaN, as m_exp's own test)
+}
+GJX_DEV PointwiseAcc pointwise_start() { return PointwiseAcc{-__builtin_inff(), 0.0, 0.0, 0.0, 0u}; }
+template <int NB>
+GJX_DEV void pointwise_take(PointwiseAcc& q, const float (&t)[NB]) {
+  const float ninf = -__builtin_inff();
+  float bm = q.m;
+#pragma unroll
+  for (int j = 0; j < NB; ++j) {
+    const double td = (double)t[j];
+    const double sq = td * td;
+    q.s1 = q.s1 + td;
+    q.s2 = q.s2 + sq;
+    bm = t[j] > bm ? t[j] : bm;
+  }
+  if (__builtin_amdgcn_ballot_w64(bm > q.m) != 0ull) {
+    if (bm > q.m) {
+      q.s = q.s * (double)pointwise_exp(q.m - bm);
+      q.m = bm;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NB; ++j) {
+    const bool live = t[j] > ninf;
+    const double e = (double)pointwise_exp(t[j] - q.m);
+    q.s = live ? q.s + e : q.s;
+    q.c += live ? 1u : 0u;
+  }
+}
+// chunk `b` of row `d`: five plain vector stores
+GJX_DEV void pointwise_store(const PointwiseArgs& a, uint32_t n_rows, uint32_t b, uint32_t d, const PointwiseAcc& q) {
+  const size_t plane = (size_t)a.W * n_rows, at = (size_t)b * n_rows + d;
+  a.part[at] = (double)q.m;
+  a.part[plane + at] = q.s;
+  a.part[2 * plane + at] = q.s1;
+  a.part[3 * plane + at] = q.s2;
+  a.part[4 * plane + at] = (double)q.c;
+}
+#ifndef __HIPCC_RTC__
+// The fold (the library's own second launch): one lane per row, the W partials in chunk order, float64 throughout.
+GJX_DEV void pointwise_fold(const double* part, uint32_t W, uint32_t n_rows, uint32_t d, double* out) {
+  const size_t plane = (size_t)W * n_rows;
+  const double ninf = -(double)__builtin_inff();
+  double M = ninf;
+#pragma unroll 8
+  for (uint32_t k = 0; k < W; ++k) {
+    const double mk = part[(size_t)k * n_rows + d];
+    M = mk > M ? mk : M;
+  }
+  double S = 0.0, s1 = 0.0, s2 = 0.0, c = 0.0;
+#pragma unroll 4
+  for (uint32_t k = 0; k < W; ++k) {
+    const size_t at = (size_t)k * n_rows + d;
+    const double mk = part[at];
+    if (mk > ninf) S = S + part[plane + at] * exp(mk - M);
+    s1 = s1 + part[2 * plane + at];
+    s2 = s2 + part[3 * plane + at];
+    c = c + part[4 * plane + at];
+  }
+  out[d] = M > ninf ? M + log(S) : ninf;
+  out[(size_t)n_rows + d] = s1;
+  out[2 * (size_t)n_rows + d] = s2;
+  out[3 * (size_t)n_rows + d] = c;
+}
+#endif
 #endif  // __HIP_DEVICE_COMPILE__
 
 template <int N>

@@ -15,6 +15,7 @@
 #include "../../include/gjx_csmc.h"
 #include "../../include/gjx_temper.h"
 #include "../../include/gjx_plate.h"
+#include "../../include/gjx_pointwise.h"
 // The library's own kernels keep the Philox round's plain XOR chain (gjx_device.hpp xor3): with v_bitop3_b32 the one-filter
 // LGSSM step measured 0.5 % slower (8.96e10 against 9.01e10 particle-steps/s, three alternating runs each, parent's range
 // 0.1 %), while the generated kernels, which include the header on their own, gain 6 % (importance) and 12 % (LGSSM scan);
@@ -4788,6 +4789,7 @@ struct gjx_temper_plan {
     gjx_expr_op ops[GJX_MAX_SITES][GJX_MAX_EXPR_OPS];
   };
   ObsExprStore* obs_expr = nullptr;  // the programs of PLATED sites' observed values (a plan's own copy, as ExprStore)
+  gjx_jit::CompiledPointwise pw;     // include/gjx_pointwise.h: the pointwise kernel (one source, whatever the generator)
   ~gjx_temper_plan() { delete obs_expr; }
 };
 
@@ -4971,6 +4973,30 @@ __global__ __launch_bounds__(kBlock) void k_temper_ladder(LadderArgs a) {
   }
 }
 
+// ---- pointwise predictive densities over a plated plan (include/gjx_pointwise.h) -----------------------------------------
+constexpr uint64_t kPointwiseWorkgroups = 2048;  // tiles of 256 rows x chunks of particles: about this many, whatever D is
+// Has the plan a pointwise source?  A PLATED site, and no per-particle input column anywhere in the table (the io has none).
+bool pointwise_plan_ok(const gjx_temper_plan* p) { return p && p->plated && p->max_input < 0; }
+std::string pointwise_source(const gjx_temper_plan* p, PlanTables* tabs = nullptr) {
+  gjx_jit::GenPointwise<CSite, CArg> g;
+  g.sites = p->sites; g.n_sites = p->n_sites;
+  return gjx_jit::generated_source(g, tabs);
+}
+gjx_jit::CompiledPointwise* pointwise_compiled(gjx_temper_plan* p) {
+  gjx_jit::CompiledPointwise& c = p->pw;
+  const bool ready = compiled_once(p->mu, c, {{p->sites, p->n_sites}}, &p->dev_owned, [&] {
+    return c.load(pointwise_source(p, &c.tabs), gjx_jit::PlanKind::temper, {"gjx_pointwise_kernel"}, {&c.fn});
+  });
+  return ready ? &c : nullptr;
+}
+// the second launch: one lane per row folds the chunks' partials in chunk order (gjx_device.hpp pointwise_fold)
+__global__ __launch_bounds__(kBlock) void k_pointwise_fold(const double* part, uint32_t W, uint32_t n_rows, double* out) {
+#if defined(__HIP_DEVICE_COMPILE__)  // (the header's device-only section)
+  const uint32_t d = blockIdx.x * kBlock + threadIdx.x;
+  if (d < n_rows) pointwise_fold(part, W, n_rows, d, out);
+#endif
+}
+
 // gjx_temper_plan_create (allow_plated = false) and gjx_temper_plan_create_plated (include/gjx_plate.h)
 int temper_plan_create(const gjx_site* sites, int n_sites, uint32_t flags, gjx_temper_plan** out, bool allow_plated) {
   if (!sites || !out || n_sites < 1 || n_sites > GJX_MAX_SITES || flags != 0u) return GJX_ERR_INVALID;
@@ -5045,6 +5071,7 @@ int gjx_temper_plan_set_data(gjx_temper_plan* p, const float* const* cols, int n
 int gjx_temper_plan_destroy(gjx_temper_plan* p) {
   if (!p) return GJX_OK;
   for (auto& c : p->jit) c.release();
+  p->pw.release();
   free_owned(p->dev_owned);
   delete p;
   return GJX_OK;
@@ -5139,6 +5166,55 @@ int gjx_temper_ess_ladder(const float* ll, uint64_t n, const float* deltas, int3
   A.per = (uint32_t)((n + W - 1) / W);
   A.G = (uint32_t)n_deltas;
   k_temper_ladder<<<W, kBlock, 0, S(s)>>>(A);
+  return launch_status();
+}
+
+int gjx_pointwise_version(int* major, int* minor) {
+  return version_out(major, minor, GJX_POINTWISE_VERSION_MAJOR, GJX_POINTWISE_VERSION_MINOR);
+}
+uint32_t gjx_pointwise_chunks(uint64_t n, uint64_t n_rows) {
+  if (n < 1 || n >= (1ull << 31) || n_rows < 1 || n_rows >= (1ull << 31)) return 0;
+  const uint64_t tiles = nrows_of(n_rows), by_n = nrows_of(n);
+  const uint64_t by_grid = (kPointwiseWorkgroups + tiles - 1) / tiles;  // (>= 1)
+  return (uint32_t)(by_n < by_grid ? by_n : by_grid);
+}
+size_t gjx_pointwise_workspace_bytes(uint64_t n, uint64_t n_rows) {
+  return (size_t)gjx_pointwise_chunks(n, n_rows) * (size_t)n_rows * 5 * sizeof(double);
+}
+int gjx_pointwise_source(const gjx_temper_plan* p, char* buf, size_t buf_len, size_t* needed) {
+  if (!pointwise_plan_ok(p)) return GJX_ERR_INVALID;
+  return copy_source_out(pointwise_source(p), buf, buf_len, needed);
+}
+int gjx_pointwise_compile_check(const gjx_temper_plan* p) {
+  if (!pointwise_plan_ok(p)) return GJX_ERR_INVALID;
+  return gjx_jit::compile_only(pointwise_source(p), gjx_jit::PlanKind::temper) ? GJX_OK : GJX_ERR_UNSUPPORTED;
+}
+int gjx_temper_pointwise(gjx_temper_plan* p, const gjx_pointwise_io* io, gjx_stream s) {
+  if (!pointwise_plan_ok(p) || !io || !p->has_data || io->n < 1 || io->n >= (1ull << 31) || !io->out || p->n_params <= p->max_param ||
+      ((uintptr_t)io->ws & 7) != 0)
+    return GJX_ERR_INVALID;
+  PointwiseArgs A;
+  memset(&A, 0, sizeof A);
+  for (int l = 0; l < p->n_latents; ++l) {
+    if (!io->x[l]) return GJX_ERR_INVALID;
+    A.x[l] = io->x[l];
+  }
+  const uint32_t D = p->data.n_rows, W = gjx_pointwise_chunks(io->n, D);
+  if (!io->ws || io->ws_bytes < gjx_pointwise_workspace_bytes(io->n, D)) return GJX_ERR_WORKSPACE;
+  if (!gjx_jit::enabled()) return GJX_ERR_UNSUPPORTED;  // a generated kernel only
+  gjx_jit::CompiledPointwise* k = pointwise_compiled(p);
+  if (!k) return GJX_ERR_JIT;
+  A.part = static_cast<double*>(io->ws);
+  A.n = (uint32_t)io->n;
+  A.W = W;
+  A.per = (uint32_t)((io->n + W - 1) / W);
+  PlanParams prm = p->prm;
+  PlanTables tabs = k->tabs;
+  PlateData pd = p->data;
+  void* args[] = {&A, &prm, &tabs, &pd};
+  const uint64_t tiles = nrows_of(D);
+  if (int rc = launch_generated(k->fn, tiles, W, kBlock, s, args)) return rc;
+  k_pointwise_fold<<<(unsigned)tiles, kBlock, 0, S(s)>>>(A.part, W, D, io->out);
   return launch_status();
 }
 

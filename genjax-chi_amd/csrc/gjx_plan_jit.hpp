@@ -1518,6 +1518,92 @@ struct GenTemper {
   }
 };
 
+// The pointwise kernel of a plated tempered plan (include/gjx_pointwise.h): the TRANSPOSED loop of emit_plated.  The move
+// kernel puts particles on lanes and reads data rows through the scalar cache; the reduction here runs over the particles,
+// so lanes are ROWS and particles are wave-uniform:
+//   * a workgroup owns a tile of 256 rows (blockIdx.x) and one chunk of particles (blockIdx.y); a lane loads its row of the
+//     data columns the plated sites read ONCE, into registers (dc<c>, the names SiteEmitter gives a DATA operand);
+//   * the chunk's particles are walked in index order; the latent columns are read through constant-address-space pointers
+//     at the loop counter — scalar loads, issued for a block of kPointwiseBlock particles before the block's arithmetic, a
+//     remainder loop for the rest (no read past x_l[n - 1]);
+//   * pw_term is tm_assess without the sums it does not need: the unplated sites' heads define the values a plated site may
+//     refer to (a latent's is the function argument nx_<l>), the plated sites' log-densities add up in f32 in table order;
+//   * the accumulators and the stores are fixed device code (gjx_device.hpp pointwise_take / pointwise_store).
+// Lanes at or past n_rows leave at once and store nothing.  No LDS, no barrier, no draw: one source per plan, whatever impl.
+// The source holds no data value, no parameter value and neither n nor n_rows.  (A table that reads a per-particle input
+// column has no pointwise source: the entry points refuse it before this runs.)
+template <class CSiteT, class CArgT>
+struct GenPointwise {
+  std::ostringstream o;
+  const CSiteT* sites;
+  int n_sites;
+
+  std::string run() {
+    using GT = GenTemper<CSiteT, CArgT>;
+    constexpr int NB = gjx::kPointwiseBlock;
+    emit_prelude(o);
+    std::vector<CSiteT> tab(sites, sites + n_sites);
+    bool used[GJX_PLATE_MAX_COLS] = {};
+    int L = 0;
+    for (int q = 0; q < n_sites; ++q) {
+      if (sites[q].observed == GJX_SITE_PLATED) {
+        for (int c : GT::plate_cols(sites[q])) used[c] = true;
+        tab[q].observed = 1;
+      }
+      if (sites[q].observed) continue;
+      tab[q].observed = 1;  // (a latent: an observed site whose value is the argument nx_<l>, as in GenTemper)
+      tab[q].obs = CArgT{};
+      tab[q].obs.kind = GJX_ARG_NEXT;
+      tab[q].obs.ref = L++;
+      tab[q].obs.scale = 1.0f;
+    }
+    std::vector<int> cs;
+    for (int c = 0; c < GJX_PLATE_MAX_COLS; ++c)
+      if (used[c]) cs.push_back(c);
+    auto list = [&](const std::string& pre, const std::string& post = "") {
+      std::string t;
+      for (int l = 0; l < L; ++l) t += pre + std::to_string(l) + post;
+      return t;
+    };
+    std::string dcs_decl, dcs;
+    for (int c : cs) {
+      dcs_decl += ", float dc" + std::to_string(c);
+      dcs += ", dc" + std::to_string(c);
+    }
+    o << "__device__ __forceinline__ float pw_term(const PlanParams& prm, const PlanTables& tabs" << list(", float nx_") << dcs_decl << ") {\n";
+    o << "  (void)prm; (void)tabs;\n";
+    SiteEmitter<CSiteT, CArgT> e{o, 0, 0, tab.data(), n_sites, "  ", ""};
+    bool first = true;
+    for (int q = 0; q < n_sites; ++q) {
+      e.head(q);
+      if (sites[q].observed != GJX_SITE_PLATED) continue;
+      // (the sum starts at the first term: +0 + t differs from t in the sign of a zero only, which no output can tell)
+      o << (first ? "  float t = " : "  t = t + ") << e.lp_of(q) << ";\n";
+      first = false;
+    }
+    o << "  return t;\n}\n";
+    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_pointwise_kernel(PointwiseArgs a, PlanParams prm, PlanTables tabs, PlateData pd) {\n";
+    o << "  const uint32_t d = blockIdx.x * 256u + threadIdx.x;\n  if (d >= pd.n_rows) return;\n";
+    for (int c : cs) o << "  const float dc" << c << " = pd.col[" << c << "][d];\n";
+    for (int l = 0; l < L; ++l) o << "  const PlateCol xc" << l << " = (PlateCol)a.x[" << l << "];\n";
+    o << "  const uint64_t lo64 = (uint64_t)blockIdx.y * a.per;\n";
+    o << "  const uint32_t lo = lo64 < a.n ? (uint32_t)lo64 : a.n;\n";
+    o << "  const uint32_t hi = a.n - lo > a.per ? lo + a.per : a.n;\n";
+    o << "  PointwiseAcc q = pointwise_start();\n  uint32_t i = lo;\n";
+    o << "  for (; hi - i >= " << NB << "u; i += " << NB << "u) {\n";
+    for (int l = 0; l < L; ++l)
+      for (int j = 0; j < NB; ++j) o << "    const float x" << l << "_" << j << " = xc" << l << "[(size_t)i + " << j << "u];\n";
+    o << "    const float t[" << NB << "] = {";
+    for (int j = 0; j < NB; ++j) o << (j ? ", " : "") << "pw_term(prm, tabs" << list(", x", "_" + std::to_string(j)) << dcs << ")";
+    o << "};\n    pointwise_take<" << NB << ">(q, t);\n  }\n";
+    o << "  for (; i < hi; ++i) {\n";
+    o << "    const float t[1] = {pw_term(prm, tabs" << list(", xc", "[i]") << dcs << ")};\n";
+    o << "    pointwise_take<1>(q, t);\n  }\n";
+    o << "  pointwise_store(a, pd.n_rows, blockIdx.y, d, q);\n}\n";
+    return o.str();
+  }
+};
+
 // One source generation: the generator numbers the plan's device tables while it runs (TableScope); `tabs` (nullable) takes
 // their addresses, in that order — the kernel argument of every launch of the source.
 template <class G>
@@ -1894,6 +1980,9 @@ struct CompiledBacksim : Module {  // the two kernels of a backward pass
 };
 struct CompiledTemper : Module {  // the move kernel of a tempered sampler
   hipFunction_t move = nullptr;
+};
+struct CompiledPointwise : Module {  // the pointwise kernel of a plated tempered plan (include/gjx_pointwise.h)
+  hipFunction_t fn = nullptr;
 };
 
 }  // namespace gjx_jit

@@ -100,6 +100,10 @@ class PlateUnavailable(HeaderUnavailable):
     header, why = "gjx_plate.h", "plated likelihoods run inside the generated tempered move kernel only"
 
 
+class PointwiseUnavailable(HeaderUnavailable):
+    header, why = "gjx_pointwise.h", "pointwise predictive densities run as a generated HIP kernel over a plated plan only"
+
+
 class Keys(C.Structure):
     _fields_ = [
         ("impl", C.c_int32),
@@ -657,6 +661,29 @@ PLATE_PROTOTYPES = {
 }
 PLATE_ABI_VERSION = (0, 1)
 
+# include/gjx_pointwise.h: a TENTH header, same arrangement — the per-row log-likelihood table of a plated tempered plan reduced
+# over the particles (log-sum-exp, two moments, count): what lppd, WAIC and held-out scores are made of
+class PointwiseIO(C.Structure):
+    """gjx_pointwise_io (include/gjx_pointwise.h)."""
+    _fields_ = [
+        ("n", C.c_uint64),
+        ("x", C.c_void_p * TEMPER_MAX_LATENTS),
+        ("out", C.c_void_p),
+        ("ws", C.c_void_p),
+        ("ws_bytes", C.c_size_t),
+    ]
+
+
+POINTWISE_PROTOTYPES = {
+    "gjx_pointwise_version": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gjx_pointwise_chunks": (C.c_uint32, [C.c_uint64, C.c_uint64]),
+    "gjx_pointwise_workspace_bytes": (C.c_size_t, [C.c_uint64, C.c_uint64]),
+    "gjx_temper_pointwise": (C.c_int, [_P, C.POINTER(PointwiseIO), _P]),
+    "gjx_pointwise_source": (C.c_int, [_P, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gjx_pointwise_compile_check": (C.c_int, [_P]),
+}
+POINTWISE_ABI_VERSION = (0, 1)
+
 # The optional headers, in the order they are bound: every one is exported by libgjx_hip.so only and bound if present.
 class Header(collections.namedtuple("Header", "key header version_fn prototypes version_name unavailable")):
     @property
@@ -683,6 +710,8 @@ PLAN_HEADERS = {h.key: h for h in (
     Header("csmc", "gjx_csmc.h", "gjx_csmc_version", CSMC_PROTOTYPES, "CSMC_ABI_VERSION", CsmcUnavailable),
     Header("temper", "gjx_temper.h", "gjx_temper_version", TEMPER_PROTOTYPES, "TEMPER_ABI_VERSION", TemperUnavailable),
     Header("plate", "gjx_plate.h", "gjx_plate_version", PLATE_PROTOTYPES, "PLATE_ABI_VERSION", PlateUnavailable),
+    Header("pointwise", "gjx_pointwise.h", "gjx_pointwise_version", POINTWISE_PROTOTYPES, "POINTWISE_ABI_VERSION",
+           PointwiseUnavailable),
 )}
 
 
@@ -697,6 +726,8 @@ _NO_STATUS = {
     "gjx_temper_plan_n_latents",
     "gjx_temper_ladder_blocks",
     "gjx_temper_ladder_workspace_bytes",
+    "gjx_pointwise_chunks",
+    "gjx_pointwise_workspace_bytes",
     "gjx_backmove_workspace_bytes",
     "gjx_backsim_workspace_bytes",
     "gjx_paths_workspace_bytes",

@@ -656,6 +656,28 @@ class Ops:
                       int(d.size), self._p(out), self._p(ws), ws.numel(), self.stream())
         return out
 
+    def temper_pointwise(self, plan: "TemperPlan", x: list) -> torch.Tensor:
+        """gjx_temper_pointwise (include/gjx_pointwise.h): TWO launches -> float64[4, D] on the device over the plan's data
+        rows d — the log-sum-exp over the particles of the per-row log-likelihood t[d, i], its sum, its sum of squares and the
+        count of entries above -inf.  `x`: the L latent columns, float32[n].  Nothing is drawn."""
+        self.lib.require("pointwise", "gjx_temper_pointwise")
+        if not getattr(plan, "plated", False) or not plan.n_rows:
+            raise ValueError("temper_pointwise: the plan has no plated site, or no data (TemperPlan.set_data)")
+        L, n, D = plan.n_latents, x[0].numel(), plan.n_rows
+        if len(x) != L:
+            raise ValueError(f"temper_pointwise: the plan has {L} latents, got {len(x)} columns")
+        io = abi.PointwiseIO()
+        io.n = n
+        for l in range(L):
+            io.x[l] = self._chk(x[l], torch.float32, n, f"x[{l}]").value
+        nb = int(self.lib.call("gjx_pointwise_workspace_bytes", n, D))
+        # (per call: see workspace(); uninitialised: the first launch writes every entry the fold reads)
+        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=self._alloc_device)
+        out = self.empty(4 * D, torch.float64)
+        io.out, io.ws, io.ws_bytes = out.data_ptr(), ws.data_ptr(), ws.numel()
+        self.lib.call("gjx_temper_pointwise", plan.handle, C.byref(io), self.stream())
+        return out.view(4, D)
+
     def smc_config(self, impl, n_total, first, n_local, step_keys, resample_keys, ess_threshold: float = 0.0):
         """Config of a whole-run call or of the step-level entry points (`first`, `n_local`: a rank's own block).
         `step_keys` / `resample_keys`: [T, 2] for one filter, [F, T, 2] for F filters stepping in the same launches
@@ -1095,6 +1117,7 @@ class TemperPlan(PlanHandle):
 
     def __init__(self, ops: "Ops", handle, n_latents: int):
         self.ops, self.handle, self.n_latents = ops, handle, n_latents
+        self.n_rows = 0  # rows of the last set_data (include/gjx_plate.h)
 
     def set_params(self, values) -> "TemperPlan":
         import numpy as np
@@ -1114,7 +1137,21 @@ class TemperPlan(PlanHandle):
         ptrs = (C.c_void_p * len(cols))(*[self.ops._chk(t, torch.float32, n_rows, f"data[{i}]").value for i, t in enumerate(cols)])
         self.ops.lib.call("gjx_temper_plan_set_data", self.handle, ptrs, len(cols), n_rows)
         self._data = list(cols)
+        self.n_rows = n_rows
         return self
+
+    def pointwise_compile_check(self) -> int:
+        """gjx_pointwise_compile_check (include/gjx_pointwise.h): the status, not raised."""
+        self.ops.lib.require("pointwise", "gjx_pointwise_compile_check")
+        return self.ops.lib._gjx_pointwise_compile_check(self.handle)
+
+    def pointwise_source(self) -> str:
+        """The HIP source of the plan's generated pointwise kernel (one per plan: it draws nothing)."""
+        need = C.c_size_t()
+        self.ops.lib.call("gjx_pointwise_source", self.handle, None, 0, C.byref(need))
+        buf = C.create_string_buffer(need.value)
+        self.ops.lib.call("gjx_pointwise_source", self.handle, buf, need.value, None)
+        return buf.value.decode()
 
     def compile_check(self, impl: int) -> int:
         return self.ops.lib._gjx_temper_plan_compile_check(self.handle, impl)

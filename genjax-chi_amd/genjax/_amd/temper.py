@@ -247,6 +247,61 @@ class TemperedResult:
                 f"n={self.lp.numel()})")
 
 
+class PointwiseLikelihood:
+    """Per data row d of a plated site, over the n equally weighted particles of a population (include/gjx_pointwise.h):
+    `lppd` = log (1/n) sum_i p(y_d | x_i), `mean` and `var` the sample mean and (n - 1) variance of log p(y_d | x_i), `count`
+    the particles with a density above 0.  float64 tensors of length D on the device; the scalar properties read them
+    from the host ONCE.  WAIC as Watanabe 2010 / Gelman, Hwang & Vehtari 2014 write it: elpd_waic = sum_d (lppd_d - var_d)."""
+
+    def __init__(self, table: torch.Tensor, n: int):
+        """`table`: float64 [4, D] — the rows lse, s1, s2, c of gjx_temper_pointwise; `n`: the population size."""
+        if table.dim() != 2 or table.shape[0] != 4 or table.dtype != torch.float64:
+            raise ValueError("PointwiseLikelihood: a float64 [4, D] tensor expected")
+        self.n = int(n)
+        if self.n < 1:
+            raise ValueError("PointwiseLikelihood: n >= 1")
+        lse, s1, s2, self.count = table.unbind(0)
+        self.lppd = lse - math.log(self.n)
+        self.mean = s1 / self.n
+        self.var = (s2 - s1 * s1 / self.n) / (self.n - 1) if self.n > 1 else torch.zeros_like(s1)
+        self._host = None
+
+    def _scalars(self):
+        if self._host is None:
+            h = torch.stack([self.lppd, self.var]).cpu().numpy()  # (the one host read)
+            lppd, var = h[0], h[1]
+            with np.errstate(invalid="ignore"):
+                pw = lppd - var
+                D = len(pw)
+                se = math.sqrt(D * float(np.var(pw, ddof=1))) if D > 1 else float("nan")
+            self._host = dict(lpd=float(lppd.sum()), p_waic=float(var.sum()), elpd=float(pw.sum()), se=se)
+        return self._host
+
+    @property
+    def log_predictive_density(self) -> float:
+        return self._scalars()["lpd"]
+
+    @property
+    def p_waic(self) -> float:
+        return self._scalars()["p_waic"]
+
+    @property
+    def elpd_waic(self) -> float:
+        return self._scalars()["elpd"]
+
+    @property
+    def waic(self) -> float:
+        return -2.0 * self._scalars()["elpd"]
+
+    @property
+    def elpd_waic_se(self) -> float:
+        """sqrt(D * var_d(lppd_d - var_d)), the sample variance over the rows (NaN for one row)."""
+        return self._scalars()["se"]
+
+    def __repr__(self):
+        return f"PointwiseLikelihood(rows={self.lppd.numel()}, n={self.n})"
+
+
 class TemperedSMC(SMCAlgorithm):
     """Adaptive tempered SMC sampler for a static target (Neal 2001; Del Moral, Doucet & Jasra 2006; the adaptive schedule
     of Jasra et al. 2011).
@@ -410,6 +465,40 @@ class TemperedSMC(SMCAlgorithm):
         out = ParticleCollection(trs, lw, True)
         out.result = res
         return out
+
+    # -- pointwise predictive densities (include/gjx_pointwise.h) ------------------------------------------------
+    def pointwise(self, res, target: Target | None = None) -> PointwiseLikelihood:
+        """The per-row log-likelihood of the plated site(s) under the population `res` — a TemperedResult of `run`, or the L
+        latent columns (float32 [n]) in the plan's latent order — reduced over the particles in two launches.
+        `target=None` scores the rows the sampler was fitted to; a `Target` over the same model body with OTHER data
+        tensors scores held-out rows under the same population (same structure: the kernel comes out of the JIT cache)."""
+        st = self._state()
+        ops = st["ops"]
+        ops.lib.require("pointwise", "gjx_temper_pointwise")
+        cols = list(res.columns) if isinstance(res, TemperedResult) else list(res)
+        fitted = [m["addr"] for m in st["latents"]]
+        if target is None:
+            tracer, tplan = st["tracer"], st["tplan"]
+        else:
+            if not isinstance(target, Target):
+                raise TypeError("TemperedSMC.pointwise: target must be a Target")
+            tracer = lower(target, self.n_particles)
+            theirs = [m["addr"] for m in tracer.meta if m["obs"] is None]
+            if theirs != fitted:
+                raise ValueError(f"TemperedSMC.pointwise: the target's latent addresses {theirs!r} are not the fitted plan's {fitted!r}")
+            tplan = None
+        if not tracer.data:
+            raise PlanUnsupported(f"TemperedSMC.pointwise: no plated site among the addresses {[m['addr'] for m in tracer.meta]!r} "
+                                  "(pointwise densities are those of a site observed over a data column)")
+        if len(cols) != len(fitted):
+            raise ValueError(f"TemperedSMC.pointwise: {len(fitted)} latent columns expected ({fitted!r}), got {len(cols)}")
+        if tplan is None:
+            tplan = ops.temper_plan_create(tracer.sites, keep=(tracer.keep, tracer))
+        if tracer.params:
+            tplan.set_params(tracer.params)
+        tplan.set_data([t.detach().to(device=ops.device(), dtype=torch.float32).contiguous() for t in tracer.data])
+        x = [c.detach().to(device=ops.device(), dtype=torch.float32).contiguous() for c in cols]
+        return PointwiseLikelihood(ops.temper_pointwise(tplan, x), x[0].numel())
 
     def log_marginal_likelihood_estimate(self, key, target: Target | None = None):
         if target is not None:
