@@ -685,26 +685,39 @@ GJX_DEV void bm_stage() { bm_issue().bm_stage(); }
 #define GJX_BM_CS g_bm_cs
 #endif
 // Correctly rounded sqrtf for arguments that are zero or not tiny (here: -2 log u in {0} U [1e-7, 45]).  Same
-// result as __builtin_sqrtf bit for bit; on the device it is the hardware estimate (<= 1 ulp) stepped to the
-// correctly rounded neighbour by two exact residuals, without the scaling and class handling the general
-// lowering adds for tiny and special arguments (16 -> 9 instructions).
+// result as __builtin_sqrtf bit for bit, without the scaling and class handling the general lowering adds for tiny and
+// special arguments (16 -> 9 instructions), and without a compare or select: a compare feeding a select goes through
+// VCC at 3.55 cycles each against 2.4 for an fma (tools/README.md), and the transform has two of each per draw.
+//   y = the hardware's estimate of 1/sqrt(x) (<= 1 ulp); s = x y ~ sqrt(x), h = y/2 ~ 1/(2 sqrt(x));
+//   e = 1/2 - h s is the estimate's relative error (one fma: exact product), and s + s e, h + h e are one coupled
+//   Newton step of both: s is then within a fraction of an ulp of sqrt(x) and h good to ~2^-22;
+//   r = s + (x - s s) h: the residual x - s s is exact in one fma (s s is within 2^-22 of x, the difference fits 24 bits),
+//   so the last fma rounds sqrt(x) + O(2^-44 sqrt(x)) once — the correctly rounded root unless sqrt(x) lies that close to
+//   a rounding boundary, which no float of the domain does: tools/check_exact_cuts.cpp runs every float of [1e-7, 45]
+//   (240 992 364 of them) with y set to the correctly rounded 1/sqrt(x) and to its neighbours at -2, -1, +1 and +2 ulp, and
+//   finds no difference from sqrtf, so the result does not depend on which <= 1 ulp estimate the hardware returns.
+//   The one-step form (r from the unrefined s and h) does differ, at a few dozen arguments: it is not an option.
+// Zeros: the argument of the estimate is clamped to 1e-30 (1/sqrt(0) = inf would make s = 0 * inf), so s = +-0 * y keeps
+// the sign of the zero through every step: +0 -> +0 and -0 -> -0, as sqrtf.  Outside {+-0} U [1e-7, 45] (negative, tiny,
+// infinite, NaN) nothing is claimed: -DGJX_GENERAL_SQRT and the host path keep __builtin_sqrtf.
 GJX_HD float sqrt_pos(float x) {
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(GJX_GENERAL_SQRT)
-  const float s = __builtin_amdgcn_sqrtf(x);
-  const float dn = u2f(f2u(s) - 1u), up = u2f(f2u(s) + 1u);
-  const float e_dn = __builtin_fmaf(-dn, s, x), e_up = __builtin_fmaf(-up, s, x);
-  float r = e_dn <= 0.0f ? dn : s;
-  r = e_up > 0.0f ? up : r;
-  return r;
+  const float y = __builtin_amdgcn_rsqf(__builtin_fmaxf(x, 1e-30f));
+  float s = x * y, h = 0.5f * y;
+  const float e = __builtin_fmaf(-h, s, 0.5f);
+  h = __builtin_fmaf(h, e, h);
+  s = __builtin_fmaf(s, e, s);
+  return __builtin_fmaf(__builtin_fmaf(-s, s, x), h, s);
 #else
   return __builtin_sqrtf(x);
 #endif
 }
 GJX_HD void bm_pair(uint32_t w_radius, uint32_t w_angle, float& z_cos, float& z_sin) {
-  // radius: u in (0, 1] with full float resolution near 0 (tails to 6.6 sigma)
-  const float u = ((float)w_radius + 1.0f) * 2.3283064365386963e-10f;
+  // radius: u = (w + 1) 2^-32 in (0, 1] with full float resolution near 0 (tails to 6.6 sigma)
+  const float uw = (float)w_radius + 1.0f;  // 2^32 u, in [1, 2^32]
 #ifdef GJX_FAST_MATH_DEVICE
   {  // the same map from the same two words through the hardware functions (v_sin / v_cos take revolutions)
+    const float u = uw * 2.3283064365386963e-10f;
     const float rf = __builtin_amdgcn_sqrtf(-1.38629436111989062f * __builtin_amdgcn_logf(u));
     const float tf = (float)(w_angle >> 8) * 5.9604644775390625e-08f;
     z_cos = rf * __builtin_amdgcn_cosf(tf);
@@ -712,7 +725,10 @@ GJX_HD void bm_pair(uint32_t w_radius, uint32_t w_angle, float& z_cos, float& z_
     return;
   }
 #endif
-  const uint32_t t = f2u(u) - 0x3f3504f3u;
+  // u enters the table walk only through its bits, and the scaling by 2^-32 only lowers the exponent field by 32 (uw is in
+  // [1, 2^32]: the product is exact, never subnormal): the scaling is folded into the integer constant.  Same t for all 2^32
+  // words (tools/check_exact_cuts.cpp runs them).
+  const uint32_t t = f2u(uw) - (0x3f3504f3u + (32u << 23));
   const BmEnt lg = GJX_BM_LG[(t >> 17) & 63u];
   const float m = u2f((t & 0x007fffffu) + 0x3f3504f3u);
   const float fe = (float)((int32_t)t >> 23);
@@ -783,6 +799,25 @@ GJX_HD float logpdf_normal_pre(float x, float loc, float rs, float lognorm) {
 }
 GJX_HD float logpdf_normal(float x, float loc, float scale) {
   return logpdf_normal_pre(x, loc, normal_rs(scale), normal_lognorm(scale));
+}
+// Two cuts of logpdf_normal_pre with the same bits, for a site whose hoisted constants are LITERALS of the generated source
+// (gjx_plan_jit.hpp lp_of decides; run-time scales and every hand-written caller keep the three-operation form above).
+// The compiler cannot make either: -ffp-contract=off forbids the fusing, and it does not reason about exactness.
+//   normal_resid_pow2: rs = 2^k, k >= 0.  loc * rs is then exact (no low bits lost, nothing underflows), so x*rs - loc*rs
+//     rounds the exact difference once — what fma(-rs, loc, x*rs) does.  Domain: loc * rs does not overflow (an infinite or
+//     NaN loc is inside it): past that the product is an infinity where the fma still sees the finite value.
+//   normal_halfsq: lognorm a literal with |lognorm| >= 2^-100.  With d d >= 2^-125 halving commutes with the rounding
+//     (round(d d) / 2 is round(d d / 2): both normal), so (-d/2) d is -round(d d)/2, the exact product inside the fma.  Below,
+//     the term is under 2^-126, less than half an ulp of lognorm (>= 2^-123), and both forms round to -lognorm.  Domain:
+//     d d does not overflow (an infinite or NaN d is inside it): past that d d is an infinity where (-d/2) d is still finite.
+// Outside the two domains (magnitudes beyond 1e19) the forms can differ: where loc * rs overflows the three-operation
+// residual is infinite and the fused one may be finite; for |d| in [2^64, 2^64.5) the three-operation density is a finite
+// number near -2e38 and the fused one -inf.  tools/check_exact_cuts.cpp sweeps both domains.
+GJX_HD float normal_resid_pow2(float x, float loc, float rs) { return __builtin_fmaf(-rs, loc, x * rs); }
+GJX_HD float normal_halfsq(float d, float lognorm) { return __builtin_fmaf(d * d, -0.5f, -lognorm); }
+struct NormalExactCuts {};  // the generator's tag: both conditions hold at this site
+GJX_HD float logpdf_normal_pre(float x, float loc, float rs, float lognorm, NormalExactCuts) {
+  return normal_halfsq(normal_resid_pow2(x, loc, rs), lognorm);
 }
 // (m_log also in fast-math plans, for every log inside a log-density: a score is a sum whose terms cancel — a coefficient
 // shape - 1 of up to 1e4 multiplied the hardware log's last bit into 2 % of a score of 0.046 — and the hardware log flushes a

@@ -1826,6 +1826,23 @@ __global__ __launch_bounds__(kBlock) void k_map_f32(const float* x, float c, flo
     }
   }
 }
+
+// gjx_debug_sqrt_pos_sweep: sqrt_pos against the general (correctly rounded) square root at every float whose bits are
+// lo .. lo + count - 1; out[0] += the mismatches, out[1] = min(out[1], bits of a mismatching argument)
+__global__ __launch_bounds__(kBlock) void k_sqrt_pos_sweep(uint32_t lo, uint64_t count, unsigned long long* out) {
+  unsigned long long bad = 0, first = ~0ull;
+  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += (uint64_t)gridDim.x * kBlock) {
+    const uint32_t b = lo + (uint32_t)i;
+    if (f2u(sqrt_pos(u2f(b))) != f2u(__builtin_sqrtf(u2f(b)))) {
+      ++bad;
+      first = first < b ? first : b;
+    }
+  }
+  if (bad) {
+    atomicAdd(&out[0], bad);
+    atomicMin(&out[1], first);
+  }
+}
 }  // namespace
 
 // ================================================================================================
@@ -3649,6 +3666,16 @@ int gjx_smc_plan_destroy(gjx_smc_plan* p) {
 int gjx_jit_compile_source(const char* source) {
   if (!source) return GJX_ERR_INVALID;
   return gjx_jit::compile_only(source, gjx_jit::PlanKind::smc /* (no options of its own: the base list) */) ? GJX_OK : GJX_ERR_JIT;
+}
+// A debug entry outside every header (tests/test_gpu_exact_cuts.py binds it by name): the device's sqrt_pos swept against
+// the general square root over the floats with bits lo_bits .. hi_bits.  `out`: two device uint64 the caller has set to
+// {0, ~0}; after the launch out[0] is the number of arguments at which the two differ and out[1] the smallest of them.
+int gjx_debug_sqrt_pos_sweep(uint32_t lo_bits, uint32_t hi_bits, uint64_t* out, gjx_stream s) {
+  if (!out || hi_bits < lo_bits) return GJX_ERR_INVALID;
+  const uint64_t count = (uint64_t)hi_bits - lo_bits + 1;
+  const uint64_t blocks = (count + kBlock - 1) / kBlock;
+  k_sqrt_pos_sweep<<<(unsigned)(blocks < 2048 ? blocks : 2048), kBlock, 0, S(s)>>>(lo_bits, count, reinterpret_cast<unsigned long long*>(out));
+  return launch_status();
 }
 int gjx_jit_stats(uint64_t* compiles, uint64_t* cached_modules, uint64_t* evictions) {
   gjx_jit::ModuleCache& mc = gjx_jit::ModuleCache::get();

@@ -152,6 +152,7 @@ struct SiteEmitter {
   int cur_blk = -1;
   bool store_values = true;  // false: the caller stores (the paired kernel writes both particles at once)
   bool ext_bits = false;     // true: the caller defines bits<q><sfx> of one-word draws (SMC quads share a block)
+  bool exact_cuts = true;    // false: Normal log-densities keep the three-operation form everywhere (normal_exact_cuts)
   const ScopeInfo* sc = nullptr;  // nested calls: per-site key scope and fold (null: a flat body, the implicit numbering)
   // include/gjx_csmc.h (the conditional kernels only): ret_comp[q] >= 0 — sampled site q is carry component ret_comp[q]; its
   // draw is made as ever (named vd<q> / vj<q>) and its VALUE is `rsel<sfx> ? rv_<k> : the draw`: a select in front of every
@@ -444,6 +445,17 @@ struct SiteEmitter {
       o << ind << "reinterpret_cast<uint32_t*>(cols.out[" << st.out_col << "])[" << (mode == 2 ? "oi" : "i") << sfx << "] = "
         << (isint ? "(uint32_t)" + v : "f2u(" + v + ")") << ";\n";
   }
+  // A Normal site whose hoisted constants are literals of the source, the reciprocal scale a power of two 2^k with k >= 0 and
+  // the log-normaliser of magnitude >= 2^-100: its log-density is the fused overload of logpdf_normal_pre (gjx_device.hpp
+  // NormalExactCuts: two operations fewer, the same bits).  Both conditions or neither: a site is emitted in one of two forms.
+  // Constants derived from launch parameters (pre == 2) and scales read at run time keep the three-operation form, and so do
+  // the tempered plans (GenTemper, GenPointwise: tests/test_pointwise_cpu.py pins their generated move sources byte for byte).
+  bool normal_exact_cuts(const CSiteT& st) const {
+    if (!exact_cuts || st.dist != GJX_DIST_NORMAL || st.pre != 1) return false;
+    const uint32_t rs = gjx::f2u(st.pre0);
+    const bool pow2 = (rs & 0x807fffffu) == 0u && rs >= 0x3f800000u && rs < 0x7f800000u;  // positive, no mantissa bits, 2^0 .. 2^127
+    return pow2 && st.pre1 - st.pre1 == 0.0f && __builtin_fabsf(st.pre1) >= 7.8886090522101181e-31f;  // finite, >= 2^-100
+  }
   // the log-density of site q at its value, as an expression over the names head() and tail() have defined
   std::string lp_of(int q) const {
     const CSiteT& st = sites[q];
@@ -457,7 +469,7 @@ struct SiteEmitter {
     const std::string p1 = st.pre == 2 ? "prm.d[" + std::to_string(2 * q + 1) + "]" : flit(st.pre1);
     switch (st.dist) {
       case GJX_DIST_NORMAL:
-        lp = st.pre ? "logpdf_normal_pre(" + v + ", a0_" + Q + ", " + p0 + ", " + p1 + ")"
+        lp = st.pre ? "logpdf_normal_pre(" + v + ", a0_" + Q + ", " + p0 + ", " + p1 + (normal_exact_cuts(st) ? ", NormalExactCuts())" : ")")
                     : "logpdf_normal(" + v + ", a0_" + Q + ", a1_" + Q + ")";
         break;
       case GJX_DIST_GAMMA:
@@ -1417,6 +1429,7 @@ struct GenTemper {
     const std::string Q = std::to_string(q);
     std::ostringstream body;  // one row: head (arguments and value from dc<c>), the log-density, the float64 accumulate
     SiteEmitter<CSiteT, CArgT> e{body, impl, 0, tab, n_sites, "      ", ""};
+    e.exact_cuts = false;
     e.head(q);
     body << "      pacc" << Q << " = pacc" << Q << " + (double)(" << e.lp_of(q) << ");\n";
     o << "  // site " << q << ": plated over pd.n_rows data rows\n";
@@ -1464,6 +1477,7 @@ struct GenTemper {
       << list(", float nx_") << ", float& lp_out, float& ll_out" << (plated ? ", const PlateData& pd" : "") << ") {\n";
     o << "  (void)cols; (void)prm; (void)tabs; (void)li;\n  float lp = 0.0f, ll = 0.0f;\n";
     SiteEmitter<CSiteT, CArgT> e{o, impl, 0, tab.data(), n_sites, "  ", ""};
+    e.exact_cuts = false;
     for (int q = 0; q < n_sites; ++q) {
       if (sites[q].observed == GJX_SITE_PLATED) {
         emit_plated(q, tab.data());
@@ -1573,6 +1587,7 @@ struct GenPointwise {
     o << "__device__ __forceinline__ float pw_term(const PlanParams& prm, const PlanTables& tabs" << list(", float nx_") << dcs_decl << ") {\n";
     o << "  (void)prm; (void)tabs;\n";
     SiteEmitter<CSiteT, CArgT> e{o, 0, 0, tab.data(), n_sites, "  ", ""};
+    e.exact_cuts = false;
     bool first = true;
     for (int q = 0; q < n_sites; ++q) {
       e.head(q);
