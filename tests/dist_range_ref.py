@@ -94,26 +94,28 @@ def golden():
 # product, of c = a - 1 and of 1 - x (6e-8 relative each, the last one 6e-8 * |c| absolute), plus the roundings of the sums
 # (6e-8 of the partial sums): together below 1e-6 * (sum |other terms| + sum |their coefficients|).
 
-def gamma_tolerance(x, a, r):
-    from math import lgamma
+def _abs_lgamma(a):
+    """|lgamma(a)| in float64 for a number or an array (torch's: nothing here needs scipy)."""
+    return torch.lgamma(torch.as_tensor(np.asarray(a, dtype=np.float64))).abs().numpy()
 
-    x = np.asarray(x, dtype=np.float64)
+
+def gamma_tolerance(x, a, r):
+    """x, a, r: numbers or arrays that broadcast (the grid passes two numbers and the points; tests/temper_fuzz.py whole tables)."""
+    x, a, r = (np.asarray(v, dtype=np.float64) for v in (x, a, r))
     with np.errstate(all="ignore"):
         lx = np.where(x > 0, np.log(np.where(x > 0, x, 1.0)), 0.0)
-        terms = np.abs((a - 1.0) * lx) + np.abs(r * x) + abs(a * math.log(r))
-    return 1e-5 * max(1.0, abs(lgamma(a))) + 1e-6 * (terms + abs(a - 1.0) + abs(a))
+        terms = np.abs((a - 1.0) * lx) + np.abs(r * x) + np.abs(a * np.log(r))
+        return 1e-5 * np.maximum(1.0, _abs_lgamma(a)) + 1e-6 * (terms + np.abs(a - 1.0) + np.abs(a))
 
 
 def beta_tolerance(x, a, b):
-    from math import lgamma
-
-    x = np.asarray(x, dtype=np.float64)
+    x, a, b = (np.asarray(v, dtype=np.float64) for v in (x, a, b))
     with np.errstate(all="ignore"):
         lx = np.where(x > 0, np.log(np.where(x > 0, x, 1.0)), 0.0)
         l1x = np.where(x < 1, np.log1p(-np.where(x < 1, x, 0.0)), 0.0)
         terms = np.abs((a - 1.0) * lx) + np.abs((b - 1.0) * l1x)
-    lg = sum(1e-5 * max(1.0, abs(lgamma(v))) for v in (a, b, a + b))
-    return lg + 1e-6 * (terms + abs(a - 1.0) + abs(b - 1.0))
+        lg = sum(1e-5 * np.maximum(1.0, _abs_lgamma(v)) for v in (a, b, a + b))
+        return lg + 1e-6 * (terms + np.abs(a - 1.0) + np.abs(b - 1.0))
 
 
 def compare_logpdf(got, ref, tol, what):

@@ -28,6 +28,7 @@ def _expr(rng, reals, params, depth=0):
     if r < 0.4:
         return f"(-{_expr(rng, reals, params, depth + 1)})"
     if r < 0.52:  # what reference bodies write between sites: exp / log of a traced value, a division by (of) a number
+        # (tests/temper_fuzz.py _WHERE reads the text of the two `where` templates below: reword them there too)
         x = str(rng.choice(reals))
         lit = round(float(rng.uniform(0.3, 3.0)), 3)
         y = str(rng.choice(reals))

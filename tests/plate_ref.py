@@ -23,6 +23,13 @@ SPREAD_LOG_Z = 0.0706
 SPREAD_MEAN = (0.0148, 0.0154)
 SPREAD_SD = (0.0112, 0.0095)
 E2E_FACTOR = 4.0
+# The same spread for the TWO-PLATE regression (two_plate below; tests/test_gpu_temper_fuzz.py, tests/test_temper_fuzz_cpu.py):
+# restatement_errors over the same 24 seeds at n = 4096, K = 2, ESS target 0.5, D = 200 rows per plate (profiles/plate_summary.md):
+# log Z 0.1009 (errors between -0.257 and +0.199, mean +0.008; log Z = -17.939); posterior means of (w, b) 0.0214, 0.0181 posterior
+# deviations; posterior deviations 0.0166, 0.0156 relative (12 s for the 24 runs).
+TWO_PLATE_SPREAD_LOG_Z = 0.1009
+TWO_PLATE_SPREAD_MEAN = (0.0214, 0.0181)
+TWO_PLATE_SPREAD_SD = (0.0166, 0.0156)
 
 
 def _param_arg(a, lat, base, keep):
@@ -196,3 +203,29 @@ def restatement_errors(model, n, n_moves, seeds):
         em.append([(r["w"].mean() - model.post_mean[0]) / sd[0], (r["b"].mean() - model.post_mean[1]) / sd[1],
                    r["w"].std() / sd[0] - 1.0, r["b"].std() / sd[1] - 1.0])
     return np.asarray(ez), np.asarray(em)
+
+
+# ---- the two-plate regression: the second latent is declared BETWEEN the plates (temper.prior_table renumbers) -----------------
+TWO_PLATE = '''def model(xs, zs):
+    w = normal(0.0, 2.0) @ "w"
+    normal(w * xs, 0.2) @ "y1"
+    b = normal(0.0, 2.0) @ "b"
+    normal(w * zs + b, 0.3) @ "y2"
+'''
+
+
+def two_plate_data(D=200, seed=0):
+    """(xs, zs, y1, y2): f32 columns (the closed form is taken at exactly these numbers)."""
+    rng = np.random.default_rng(seed)
+    xs, zs = np.linspace(-1.0, 1.0, D), rng.uniform(-1.0, 1.0, D)
+    y1 = 0.7 * xs + 0.2 * rng.standard_normal(D)
+    y2 = 0.7 * zs - 0.3 + 0.3 * rng.standard_normal(D)
+    return tuple(np.asarray(c, dtype=np.float32) for c in (xs, zs, y1, y2))
+
+
+def two_plate(D=200, seed=0):
+    """The closed form of TWO_PLATE from the stacked design: rows (xs_d, 0) at noise 0.2, then (zs_d, 1) at noise 0.3."""
+    xs, zs, y1, y2 = (c.astype(np.float64) for c in two_plate_data(D, seed))
+    X = np.concatenate([np.stack([xs, np.zeros(D)], axis=1), np.stack([zs, np.ones(D)], axis=1)])
+    noise = np.concatenate([np.full(D, float(np.float32(0.2))), np.full(D, float(np.float32(0.3)))])
+    return R.DesignRegression(X, np.concatenate([y1, y2]), noise, prior_sd=2.0)

@@ -174,6 +174,29 @@ class Regression:
         return -0.5 * (r * r).sum(axis=1) / self.noise ** 2 - self.m * (0.5 * math.log(2 * math.pi) + math.log(self.noise))
 
 
+class DesignRegression:
+    """Regression's sibling over a design matrix and a noise vector: y_i ~ N(w X[i, 0] + b X[i, 1], noise_i), w, b ~ N(0,
+    prior_sd) — several plated sites over one pair of latents, stacked.  The same closed forms and the same interface
+    (tempered_f64 and plate_ref.restatement_errors take either)."""
+
+    def __init__(self, X, ys, noise, prior_sd=2.0):
+        self.X, self.ys = np.asarray(X, dtype=np.float64), np.asarray(ys, dtype=np.float64)
+        self.noise, self.prior_sd, self.m = np.asarray(noise, dtype=np.float64), prior_sd, len(self.ys)
+        Xw = self.X / self.noise[:, None] ** 2
+        prec = self.X.T @ Xw + np.eye(2) / prior_sd ** 2
+        self.post_cov = np.linalg.inv(prec)
+        self.post_mean = self.post_cov @ (Xw.T @ self.ys)
+        C = np.diag(self.noise ** 2) + prior_sd ** 2 * self.X @ self.X.T  # the marginal covariance of y
+        _, logdet = np.linalg.slogdet(C)
+        self.log_z = float(-0.5 * (self.m * math.log(2 * math.pi) + logdet + self.ys @ np.linalg.solve(C, self.ys)))
+
+    log_prior = Regression.log_prior
+
+    def log_lik(self, w, b):
+        r = (self.ys[None, :] - (w[:, None] * self.X[None, :, 0] + b[:, None] * self.X[None, :, 1])) / self.noise[None, :]
+        return -0.5 * (r * r).sum(axis=1) - (0.5 * math.log(2 * math.pi) * self.m + np.log(self.noise).sum())
+
+
 def systematic(rng, w):
     n = len(w)
     c = np.cumsum(w)
