@@ -16,6 +16,7 @@
 #include "../../include/gjx_temper.h"
 #include "../../include/gjx_plate.h"
 #include "../../include/gjx_pointwise.h"
+#include "../../include/gjx_temper_cov.h"
 // The library's own kernels keep the Philox round's plain XOR chain (gjx_device.hpp xor3): with v_bitop3_b32 the one-filter
 // LGSSM step measured 0.5 % slower (8.96e10 against 9.01e10 particle-steps/s, three alternating runs each, parent's range
 // 0.1 %), while the generated kernels, which include the header on their own, gain 6 % (importance) and 12 % (LGSSM scan);
@@ -4807,6 +4808,7 @@ struct gjx_temper_plan {
   std::vector<void*> dev_owned;  // per-row tables of categorical (observed) sites
   std::mutex mu;
   gjx_jit::CompiledTemper jit[2];
+  gjx_jit::CompiledTemper cov_jit[2];  // include/gjx_temper_cov.h: the covariance move kernel, per generator
   // include/gjx_plate.h: PLATED sites (gjx_temper_plan_create_plated) and their data columns (gjx_temper_plan_set_data)
   bool plated = false;
   int max_data = -1;  // highest data column the table reads
@@ -4823,9 +4825,9 @@ struct gjx_temper_plan {
 namespace {
 constexpr unsigned kTemperMaxGrid = 256 * 16;  // workgroups of 256 particles, grid-stride beyond
 
-std::string temper_source(const gjx_temper_plan* p, int impl, PlanTables* tabs = nullptr) {
+std::string temper_source(const gjx_temper_plan* p, int impl, PlanTables* tabs = nullptr, bool cov = false) {
   gjx_jit::GenTemper<CSite, CArg> g;
-  g.impl = impl; g.sites = p->sites; g.n_sites = p->n_sites;
+  g.impl = impl; g.sites = p->sites; g.n_sites = p->n_sites; g.cov = cov;
   return gjx_jit::generated_source(g, tabs);
 }
 
@@ -4833,6 +4835,13 @@ gjx_jit::CompiledTemper* temper_compiled(gjx_temper_plan* p, int impl) {
   gjx_jit::CompiledTemper& c = p->jit[impl];
   const bool ready = compiled_once(p->mu, c, {{p->sites, p->n_sites}}, &p->dev_owned, [&] {
     return c.load(temper_source(p, impl, &c.tabs), gjx_jit::PlanKind::temper, {"gjx_temper_move_kernel"}, {&c.move});
+  });
+  return ready ? &c : nullptr;
+}
+gjx_jit::CompiledTemper* temper_cov_compiled(gjx_temper_plan* p, int impl) {
+  gjx_jit::CompiledTemper& c = p->cov_jit[impl];
+  const bool ready = compiled_once(p->mu, c, {{p->sites, p->n_sites}}, &p->dev_owned, [&] {
+    return c.load(temper_source(p, impl, &c.tabs, true), gjx_jit::PlanKind::temper, {"gjx_temper_move_cov_kernel"}, {&c.move});
   });
   return ready ? &c : nullptr;
 }
@@ -5000,6 +5009,207 @@ __global__ __launch_bounds__(kBlock) void k_temper_ladder(LadderArgs a) {
   }
 }
 
+// ---- the weighted moments and the proposal factor (include/gjx_temper_cov.h) -----------------------------------------------
+constexpr int kMomMaxPairs = 1 + GJX_TEMPER_MAX_LATENTS + GJX_TEMPER_MAX_LATENTS * (GJX_TEMPER_MAX_LATENTS + 1) / 2;  // 153
+constexpr int kMomTri = GJX_TEMPER_MAX_LATENTS * (GJX_TEMPER_MAX_LATENTS + 1) / 2;                                  // 136
+static_assert(kMomMaxPairs <= kBlock, "one lane per sum in the fold");
+constexpr int kMomStride = kBlock + 1;  // a row of the staged tile, in doubles: lanes of different rows read different banks
+struct MomentsArgs {
+  const float* x[GJX_TEMPER_MAX_LATENTS];
+  const float* lw;         // nullable: equal weights
+  double* moments;         // [P]
+  float* factor;           // [L (L + 1) / 2]
+  float* scales;           // [L]
+  uint32_t* n_degenerate;  // [1]
+  uint32_t* ticket;        // zero between launches
+  float* mb;               // [W] block maxima
+  double* part;            // [W, P] block sums
+  double c;                // 2.38 / sqrt(L)
+  uint32_t n, per, W, L, P, Q;
+};
+struct MomentsScratch {
+  uint32_t* ticket;
+  float* mb;
+  double* part;
+};
+bool moments_carve(Carver& cv, uint32_t W, uint32_t P, MomentsScratch* out) {
+  out->ticket = cv.take<uint32_t>(2);
+  out->mb = cv.take<float>(W);
+  out->part = cv.take<double>((size_t)W * P);
+  return cv.ok;
+}
+// term p of the specification reads rows (u, v) of the staged tile: row L holds ones, so that every term is (e * u) * v
+GJX_DEV void moments_rows(uint32_t p, uint32_t L, uint32_t* u, uint32_t* v) {
+  *u = L; *v = L;
+  if (p >= 1u && p <= L) *u = p - 1u;
+  if (p > L) {
+    uint32_t t = p - 1u - L, l = 0;
+    while ((l + 1u) * (l + 2u) / 2u <= t) ++l;
+    *u = l;
+    *v = t - l * (l + 1u) / 2u;
+  }
+}
+__global__ __launch_bounds__(kBlock) void k_temper_moments(MomentsArgs a) {
+  __shared__ double sh_d[(GJX_TEMPER_MAX_LATENTS + 1) * kMomStride];  // rows 0 .. L-1: deviations; row L: ones
+  __shared__ double sh_e[kBlock];                                    // weights of the tile; the fold: f_b
+  __shared__ double sh_acc[kBlock];                                  // [Q][P] segment sums; the fold: T_p
+  __shared__ double sh_S[kMomTri], sh_G[kMomTri];
+  __shared__ double sh_x0[GJX_TEMPER_MAX_LATENTS];
+  __shared__ float sh_red[4];
+  __shared__ uint32_t sh_last;
+  const uint32_t L = a.L, P = a.P, Q = a.Q, seg = kBlock / Q, t = threadIdx.x;
+  const float ninf = -__builtin_inff();
+  const uint32_t p = t % P, q = t / P;
+  const bool active = q < Q;
+  uint32_t ru, rv;
+  moments_rows(p, L, &ru, &rv);
+  double x0[GJX_TEMPER_MAX_LATENTS];
+#pragma unroll
+  for (int l = 0; l < GJX_TEMPER_MAX_LATENTS; ++l) x0[l] = (uint32_t)l < L ? (double)a.x[l][0] : 0.0;
+  sh_d[L * kMomStride + t] = 1.0;
+#pragma unroll
+  for (int l = 0; l < GJX_TEMPER_MAX_LATENTS; ++l)  // (for the fold's lane 1 + l: no lane indexes a register array by t)
+    if (t == (uint32_t)l) sh_x0[l] = x0[l];
+  for (uint32_t b = blockIdx.x; b < a.W; b += gridDim.x) {
+    const uint64_t lo64 = (uint64_t)b * a.per;
+    const uint32_t lo = lo64 < a.n ? (uint32_t)lo64 : a.n;
+    const uint32_t hi = (uint64_t)lo + a.per < a.n ? lo + a.per : a.n;
+    float mb = 0.0f;
+    if (a.lw) {
+      float mx = ninf;
+      for (uint32_t i = lo + t; i < hi; i += kBlock) {
+        const float v = a.lw[i];
+        mx = v > mx ? v : mx;  // (a NaN is skipped)
+      }
+      mb = block_max(mx, sh_red);
+    }
+    double acc = 0.0;
+    for (uint32_t base = lo; base < hi; base += kBlock) {
+      const uint32_t i = base + t;
+      double e = 0.0;
+      if (i < hi) {
+        if (a.lw) {
+          const float v = a.lw[i];
+          if (v > ninf) e = (double)m_exp(v - mb);  // -inf, NaN: no contribution
+        } else {
+          e = 1.0;
+        }
+      }
+      // the tile's column loads in flight together, converted afterwards: no load waits behind a lane's own branch (a lane
+      // past the block's end re-reads its last entry; columns L .. 15 are column 0 again), taken in groups of 2, 2, 4 and 8
+      float xv[GJX_TEMPER_MAX_LATENTS];
+      const uint32_t ic = i < hi ? i : hi - 1u;
+#pragma unroll
+      for (int l = 0; l < GJX_TEMPER_MAX_LATENTS; ++l) xv[l] = 0.0f;
+      xv[0] = a.x[0][ic]; xv[1] = a.x[1][ic];
+      if (L > 2u) {
+        xv[2] = a.x[2][ic]; xv[3] = a.x[3][ic];
+        if (L > 4u) {
+#pragma unroll
+          for (int l = 4; l < 8; ++l) xv[l] = a.x[l][ic];
+          if (L > 8u) {
+#pragma unroll
+            for (int l = 8; l < GJX_TEMPER_MAX_LATENTS; ++l) xv[l] = a.x[l][ic];
+          }
+        }
+      }
+      __syncthreads();  // (the last tile's readers are done)
+      sh_e[t] = e;
+#pragma unroll
+      for (int l = 0; l < GJX_TEMPER_MAX_LATENTS; ++l)
+        if ((uint32_t)l < L) sh_d[l * kMomStride + t] = e > 0.0 ? (double)xv[l] - x0[l] : 0.0;
+      __syncthreads();
+      if (active) {
+        const double* du = sh_d + ru * kMomStride + q * seg;
+        const double* dv = sh_d + rv * kMomStride + q * seg;
+        const double* de = sh_e + q * seg;
+        for (uint32_t k = 0; k < seg; ++k) acc += (de[k] * du[k]) * dv[k];
+      }
+    }
+    __syncthreads();
+    sh_acc[t] = acc;
+    __syncthreads();
+    if (t < P) {
+      double s = sh_acc[t];
+      for (uint32_t k = 1; k < Q; ++k) s += sh_acc[k * P + t];
+      sh_acc[t] = s;  // (segment 0 of sum t: no other lane reads this entry)
+    }
+    __syncthreads();
+    // ONE wave stores the block's sums (out of LDS, ceil(P / 64) per lane) and its maximum: the wave whose lane 0 adds to the
+    // ticket below, so that the add's release waits for every store of the hand-off — a barrier waits for no store of
+    // another wave
+    if (t < (uint32_t)kWave) {
+      for (uint32_t k = t; k < P; k += kWave) a.part[(size_t)b * P + k] = sh_acc[k];
+      if (t == 0) a.mb[b] = mb;
+    }
+  }
+  // the ticket of k_temper_ladder: the writer wave's lane 0 releases its wave's stores with the add; the last arriver's
+  // workgroup acquires and folds
+  if (t == 0) sh_last = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u ? 1u : 0u;
+  __syncthreads();
+  if (!sh_last) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  const float mt = t < a.W ? a.mb[t] : ninf;  // (W <= 256: one block maximum per lane)
+  const float M = block_max(mt, sh_red);
+  sh_e[t] = mt > ninf ? exp((double)mt - (double)M) : 0.0;
+  __syncthreads();
+  if (t < P) {
+    double T = 0.0;
+    for (uint32_t k = 0; k < a.W; ++k) T += sh_e[k] * a.part[(size_t)k * P + t];  // in index order
+    sh_acc[t] = T;
+  }
+  __syncthreads();
+  const uint32_t tri = L * (L + 1u) / 2u;
+  if (!(M > ninf)) {  // no entry above -inf
+    if (t < P) a.moments[t] = 0.0;
+    if (t < tri) a.factor[t] = 0.0f;
+    if (t < L) a.scales[t] = 0.0f;
+    if (t == 0) {
+      a.n_degenerate[0] = L;
+      __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return;
+  }
+  const double T0 = sh_acc[0];
+  if (t == 0) a.moments[0] = T0;
+  if (t >= 1u && t <= L) a.moments[t] = sh_x0[t - 1u] + sh_acc[t] / T0;
+  if (t > L && t < P) {
+    const double S = sh_acc[t] / T0 - (sh_acc[1u + ru] / T0) * (sh_acc[1u + rv] / T0);
+    a.moments[t] = S;
+    sh_S[t - 1u - L] = S;
+  }
+  __syncthreads();
+  if (t < L) {
+    const double s = sh_S[t * (t + 1u) / 2u + t];
+    a.scales[t] = s > 0.0 ? (float)(a.c * sqrt(s)) : 0.0f;
+  }
+  if (t != 0) return;
+  uint32_t ndeg = 0;
+  for (uint32_t l = 0; l < L; ++l) {  // the Cholesky rule of the header, operation by operation (never contracted)
+    const uint32_t rl = l * (l + 1u) / 2u;
+    for (uint32_t j = 0; j < l; ++j) {
+      const uint32_t rj = j * (j + 1u) / 2u;
+      double s = 0.0;
+      for (uint32_t k = 0; k < j; ++k) s += sh_G[rl + k] * sh_G[rj + k];
+      const double g = sh_G[rj + j];
+      sh_G[rl + j] = g == 0.0 ? 0.0 : (sh_S[rl + j] - s) / g;
+    }
+    double s = 0.0;
+    for (uint32_t k = 0; k < l; ++k) s += sh_G[rl + k] * sh_G[rl + k];
+    const double Sll = sh_S[rl + l], pv = Sll - s;
+    if (!(pv > 0x1p-40 * Sll)) {
+      for (uint32_t j = 0; j < l; ++j) sh_G[rl + j] = 0.0;
+      sh_G[rl + l] = Sll > 0.0 && Sll < __builtin_inf() ? sqrt(Sll) : 0.0;
+      ++ndeg;
+    } else {
+      sh_G[rl + l] = sqrt(pv);
+    }
+  }
+  for (uint32_t k = 0; k < tri; ++k) a.factor[k] = (float)(a.c * sh_G[k]);
+  a.n_degenerate[0] = ndeg;
+  __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // ---- pointwise predictive densities over a plated plan (include/gjx_pointwise.h) -----------------------------------------
 constexpr uint64_t kPointwiseWorkgroups = 2048;  // tiles of 256 rows x chunks of particles: about this many, whatever D is
 // Has the plan a pointwise source?  A PLATED site, and no per-particle input column anywhere in the table (the io has none).
@@ -5098,6 +5308,7 @@ int gjx_temper_plan_set_data(gjx_temper_plan* p, const float* const* cols, int n
 int gjx_temper_plan_destroy(gjx_temper_plan* p) {
   if (!p) return GJX_OK;
   for (auto& c : p->jit) c.release();
+  for (auto& c : p->cov_jit) c.release();
   p->pw.release();
   free_owned(p->dev_owned);
   delete p;
@@ -5119,11 +5330,14 @@ int gjx_temper_plan_compile_check(const gjx_temper_plan* p, int impl) {
   if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
   return gjx_jit::compile_only(temper_source(p, impl), gjx_jit::PlanKind::temper) ? GJX_OK : GJX_ERR_UNSUPPORTED;
 }
-int gjx_temper_move(gjx_temper_plan* p, const gjx_temper_io* io, gjx_stream s) {
-  if (!p || !io || io->n < 1 || io->n >= (1ull << 31) || (io->impl != 0 && io->impl != 1) || (io->impl == 0 && io->key_lane != 0) ||
+}  // extern "C"
+namespace {
+// gjx_temper_move (factor == nullptr, cov == false) and gjx_temper_move_cov (include/gjx_temper_cov.h: scales are not read)
+int temper_move(gjx_temper_plan* p, const gjx_temper_io* io, bool cov, const float* factor, gjx_stream s) {
+  if (!p || !io || (cov && !factor) || io->n < 1 || io->n >= (1ull << 31) || (io->impl != 0 && io->impl != 1) || (io->impl == 0 && io->key_lane != 0) ||
       io->n_moves < 0 || io->n_moves > GJX_TEMPER_MAX_MOVES)
     return GJX_ERR_INVALID;
-  if (!io->lp_out || !io->ll_out || (!io->recompute && (!io->lp_in || !io->ll_in)) || (io->n_moves > 0 && !io->scales))
+  if (!io->lp_out || !io->ll_out || (!io->recompute && (!io->lp_in || !io->ll_in)) || (!cov && io->n_moves > 0 && !io->scales))
     return GJX_ERR_INVALID;
   if (io->n_input_cols < 0 || io->n_input_cols > 16 || io->n_input_cols <= p->max_input || (io->n_input_cols && !io->input_cols) ||
       p->n_params <= p->max_param || (p->plated && !p->has_data))
@@ -5134,7 +5348,7 @@ int gjx_temper_move(gjx_temper_plan* p, const gjx_temper_io* io, gjx_stream s) {
     if (!io->x_in[l] || !io->x_out[l]) return GJX_ERR_INVALID;
     A.x_in[l] = io->x_in[l];
     A.x_out[l] = io->x_out[l];
-    A.scales[l] = io->scales ? io->scales[l] : 0.0f;
+    A.scales[l] = !cov && io->scales ? io->scales[l] : 0.0f;
   }
   RunCols cols;
   memset(&cols, 0, sizeof cols);
@@ -5143,7 +5357,7 @@ int gjx_temper_move(gjx_temper_plan* p, const gjx_temper_io* io, gjx_stream s) {
     cols.in[c] = io->input_cols[c];
   }
   if (!gjx_jit::enabled()) return GJX_ERR_UNSUPPORTED;  // a generated kernel only
-  gjx_jit::CompiledTemper* k = temper_compiled(p, io->impl);
+  gjx_jit::CompiledTemper* k = cov ? temper_cov_compiled(p, io->impl) : temper_compiled(p, io->impl);
   if (!k) return GJX_ERR_JIT;
   A.lp_in = io->lp_in; A.ll_in = io->ll_in; A.lp_out = io->lp_out; A.ll_out = io->ll_out;
   A.anc = io->ancestors; A.n_accept = io->n_accept;
@@ -5159,8 +5373,12 @@ int gjx_temper_move(gjx_temper_plan* p, const gjx_temper_io* io, gjx_stream s) {
   PlanTables tabs = k->tabs;
   PlateData pd = p->data;
   void* args[] = {&A, &cols, &prm, &tabs, &pd};  // (the kernel of a plan without plated sites takes the first four)
-  return launch_generated(k->move, grid, 1, kBlock, s, args);
+  void* cov_args[] = {&A, &cols, &prm, &tabs, &factor, &pd};
+  return launch_generated(k->move, grid, 1, kBlock, s, cov ? cov_args : args);
 }
+}  // namespace
+extern "C" {
+int gjx_temper_move(gjx_temper_plan* p, const gjx_temper_io* io, gjx_stream s) { return temper_move(p, io, false, nullptr, s); }
 
 uint32_t gjx_temper_ladder_blocks(uint64_t n) {
   const uint64_t rows = nrows_of(n);
@@ -5194,6 +5412,58 @@ int gjx_temper_ess_ladder(const float* ll, uint64_t n, const float* deltas, int3
   A.G = (uint32_t)n_deltas;
   k_temper_ladder<<<W, kBlock, 0, S(s)>>>(A);
   return launch_status();
+}
+
+int gjx_temper_cov_version(int* major, int* minor) {
+  return version_out(major, minor, GJX_TEMPER_COV_VERSION_MAJOR, GJX_TEMPER_COV_VERSION_MINOR);
+}
+size_t gjx_temper_moments_workspace_bytes(uint64_t n, int32_t n_latents) {
+  if (n < 1 || n >= (1ull << 31) || n_latents < 1 || n_latents > GJX_TEMPER_MAX_LATENTS) return 0;
+  Carver cv{nullptr, ~(size_t)0};
+  MomentsScratch sc;
+  (void)moments_carve(cv, gjx_temper_ladder_blocks(n), (uint32_t)(1 + n_latents + n_latents * (n_latents + 1) / 2), &sc);
+  return ~(size_t)0 - cv.left;
+}
+int gjx_temper_moments(const gjx_temper_moments_io* io, gjx_stream s) {
+  if (!io || io->n < 1 || io->n >= (1ull << 31) || io->n_latents < 1 || io->n_latents > GJX_TEMPER_MAX_LATENTS || !io->moments ||
+      !io->factor || !io->scales || !io->n_degenerate || ((uintptr_t)io->ws & 7) != 0)
+    return GJX_ERR_INVALID;
+  MomentsArgs A;
+  memset(&A, 0, sizeof A);
+  const uint32_t L = (uint32_t)io->n_latents;
+  for (uint32_t l = 0; l < L; ++l) {
+    if (!io->x[l]) return GJX_ERR_INVALID;
+    A.x[l] = io->x[l];
+  }
+  for (uint32_t l = L; l < GJX_TEMPER_MAX_LATENTS; ++l) A.x[l] = A.x[0];  // (the kernel loads columns in groups: every pointer valid)
+  if (!io->ws || io->ws_bytes < gjx_temper_moments_workspace_bytes(io->n, io->n_latents)) return GJX_ERR_WORKSPACE;
+  const uint32_t W = gjx_temper_ladder_blocks(io->n), P = 1u + L + L * (L + 1u) / 2u;
+  Carver cv{(char*)io->ws, io->ws_bytes};
+  MomentsScratch sc;
+  if (!moments_carve(cv, W, P, &sc)) return GJX_ERR_WORKSPACE;
+  A.lw = io->lw; A.moments = io->moments; A.factor = io->factor; A.scales = io->scales; A.n_degenerate = io->n_degenerate;
+  A.ticket = sc.ticket; A.mb = sc.mb; A.part = sc.part;
+  A.c = 2.38 / sqrt((double)L);
+  A.n = (uint32_t)io->n;
+  A.per = (uint32_t)((io->n + W - 1) / W);
+  A.W = W; A.L = L; A.P = P;
+  A.Q = 1;
+  while (A.Q * 2u * P <= (uint32_t)kBlock) A.Q *= 2u;  // the largest power of two <= 256 / P
+  unsigned grid = W;
+  if (io->max_workgroups && grid > io->max_workgroups) grid = io->max_workgroups;
+  k_temper_moments<<<grid, kBlock, 0, S(s)>>>(A);
+  return launch_status();
+}
+int gjx_temper_move_cov(gjx_temper_plan* p, const gjx_temper_io* io, const float* factor, gjx_stream s) {
+  return temper_move(p, io, true, factor, s);
+}
+int gjx_temper_cov_source(const gjx_temper_plan* p, int impl, char* buf, size_t buf_len, size_t* needed) {
+  if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
+  return copy_source_out(temper_source(p, impl, nullptr, true), buf, buf_len, needed);
+}
+int gjx_temper_cov_compile_check(const gjx_temper_plan* p, int impl) {
+  if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
+  return gjx_jit::compile_only(temper_source(p, impl, nullptr, true), gjx_jit::PlanKind::temper) ? GJX_OK : GJX_ERR_UNSUPPORTED;
 }
 
 int gjx_pointwise_version(int* major, int* minor) {

@@ -1391,6 +1391,9 @@ struct GenBackmove {
 //   propose  x'_l = x_l + scales[l] * site_normal(Stream(split_at(p_r, i), fold of latent l)): what k_sample_normal computes
 //            for the lazy children of p_r.  Under PHILOX latents 2 k and 2 k + 1 read the same pair block (one cipher
 //            call after common-subexpression elimination).
+//   cov      the SECOND kernel of a plan (include/gjx_temper_cov.h; `cov`): gjx_temper_move_cov_kernel proposes
+//            x' = x + F eps through a packed lower triangle F, one more pointer argument (before PlateData).  It shares
+//            tm_assess and everything else; the source of the diagonal kernel does not change with it.
 //   keys     fold_in(key, r) and its two children are wave-uniform: three cipher blocks per sweep on the scalar side.
 //   plated   a GJX_SITE_PLATED site (include/gjx_plate.h) is a loop over the data rows inside tm_assess (emit_plated): its
 //            arguments and value read the row of the data columns, its f32 log-densities enter ll through a float64 sum.  The
@@ -1403,6 +1406,7 @@ struct GenTemper {
   int impl;
   const CSiteT* sites;
   int n_sites;
+  bool cov = false;  // the covariance move (include/gjx_temper_cov.h): gjx_temper_move_cov_kernel, x' = x + F eps
 
   // The data columns plated site q reads (a0, a1, obs; affine operands and program leaves), in ascending order.
   static std::vector<int> plate_cols(const CSiteT& st) {
@@ -1496,9 +1500,12 @@ struct GenTemper {
       else o << "  lp = lp + (" << in << " ? " << e.lp_of(q) << " : -__builtin_inff());\n";
     }
     o << "  lp_out = lp; ll_out = ll;\n}\n";
-    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_temper_move_kernel(TemperArgs a, RunCols cols, PlanParams prm, PlanTables tabs"
+    if (cov) o << "typedef const __attribute__((address_space(4))) float* FactorPtr;\n";
+    o << "extern \"C\" __global__ __launch_bounds__(256) void " << (cov ? "gjx_temper_move_cov_kernel" : "gjx_temper_move_kernel")
+      << "(TemperArgs a, RunCols cols, PlanParams prm, PlanTables tabs" << (cov ? ", const float* factor" : "")
       << (plated ? ", PlateData pd" : "") << ") {\n";
     o << "  const uint32_t n = a.n;\n";
+    if (cov) o << "  FactorPtr F = (FactorPtr)factor;\n";
     o << "  for (uint64_t i64 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i64 < n; i64 += (uint64_t)gridDim.x * blockDim.x) {\n";
     o << "    const uint32_t i = (uint32_t)i64;\n";
     o << "    uint32_t an = a.anc ? (uint32_t)a.anc[i] : i;\n    an = an < n ? an : n - 1u;\n";
@@ -1511,7 +1518,21 @@ struct GenTemper {
     o << "      const Key kr = fold_in<" << I << ">(a.key, r);\n";
     o << "      const Key pk = split_at<" << I << ">(fold_in<" << I << ">(kr, 0u), (uint64_t)i);\n";
     o << "      const Key ak = split_at<" << I << ">(fold_in<" << I << ">(kr, 1u), (uint64_t)i);\n";
-    for (int l = 0; l < L; ++l) {
+    // the covariance move: the L draws first (+0 + z: what gjx_sample_logpdf_normal returns at loc 0, scale 1), then row l of
+    // the packed triangle against them, every product and sum rounded once.  F is wave-uniform and read through the scalar
+    // cache; the empty asm makes the pointer a value of THIS sweep, so the L (L + 1) / 2 loads are not hoisted out of the
+    // sweep loop into scalar registers they would not fit next to the key and the pointers.
+    if (cov) o << "      asm volatile(\"\" : \"+s\"(F));\n";
+    for (int l = 0; cov && l < L; ++l) {
+      const uint32_t fold = impl == 0 ? (uint32_t)(l + 1) : (uint32_t)l;
+      o << "      const float e" << l << " = 0.0f + site_normal<" << I << ">(Stream<" << I << ">(pk, true, " << fold << "u));\n";
+    }
+    for (int l = 0; cov && l < L; ++l) {
+      o << "      float t" << l << " = F[" << l * (l + 1) / 2 << "] * e0;\n";
+      for (int j = 1; j <= l; ++j) o << "      t" << l << " = t" << l << " + F[" << l * (l + 1) / 2 + j << "] * e" << j << ";\n";
+      o << "      const float y" << l << " = x" << l << " + t" << l << ";\n";
+    }
+    for (int l = 0; !cov && l < L; ++l) {
       const uint32_t fold = impl == 0 ? (uint32_t)(l + 1) : (uint32_t)l;  // (SiteEmitter::fold_of for a table of L latents)
       o << "      const float t" << l << " = a.scales[" << l << "] * site_normal<" << I << ">(Stream<" << I << ">(pk, true, " << fold << "u));\n";
       o << "      const float y" << l << " = x" << l << " + t" << l << ";\n";
@@ -1993,7 +2014,7 @@ struct CompiledSmc : Module {  // the kernels of a filter (bootstrap or guided)
 struct CompiledBacksim : Module {  // the two kernels of a backward pass
   hipFunction_t step = nullptr, last = nullptr;
 };
-struct CompiledTemper : Module {  // the move kernel of a tempered sampler
+struct CompiledTemper : Module {  // the move kernel of a tempered sampler (diagonal, or the covariance move: a slot each)
   hipFunction_t move = nullptr;
 };
 struct CompiledPointwise : Module {  // the pointwise kernel of a plated tempered plan (include/gjx_pointwise.h)

@@ -104,6 +104,10 @@ class PointwiseUnavailable(HeaderUnavailable):
     header, why = "gjx_pointwise.h", "pointwise predictive densities run as a generated HIP kernel over a plated plan only"
 
 
+class TemperCovUnavailable(HeaderUnavailable):
+    header, why = "gjx_temper_cov.h", "the population moments and the covariance move run as HIP kernels only"
+
+
 class Keys(C.Structure):
     _fields_ = [
         ("impl", C.c_int32),
@@ -684,6 +688,35 @@ POINTWISE_PROTOTYPES = {
 }
 POINTWISE_ABI_VERSION = (0, 1)
 
+# include/gjx_temper_cov.h: an ELEVENTH header, same arrangement — full-covariance proposals for the tempered move: the one-launch
+# weighted moments of a population with the proposal factor built on the device, and the move through that factor
+class TemperMomentsIO(C.Structure):
+    """gjx_temper_moments_io (include/gjx_temper_cov.h)."""
+    _fields_ = [
+        ("n", C.c_uint64),
+        ("n_latents", C.c_int32),
+        ("x", C.c_void_p * TEMPER_MAX_LATENTS),
+        ("lw", C.c_void_p),
+        ("moments", C.c_void_p),
+        ("factor", C.c_void_p),
+        ("scales", C.c_void_p),
+        ("n_degenerate", C.c_void_p),
+        ("ws", C.c_void_p),
+        ("ws_bytes", C.c_size_t),
+        ("max_workgroups", C.c_uint32),
+    ]
+
+
+TEMPER_COV_PROTOTYPES = {
+    "gjx_temper_cov_version": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gjx_temper_moments_workspace_bytes": (C.c_size_t, [C.c_uint64, C.c_int32]),
+    "gjx_temper_moments": (C.c_int, [C.POINTER(TemperMomentsIO), _P]),
+    "gjx_temper_move_cov": (C.c_int, [_P, C.POINTER(TemperIO), _P, _P]),
+    "gjx_temper_cov_source": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gjx_temper_cov_compile_check": (C.c_int, [_P, C.c_int]),
+}
+TEMPER_COV_ABI_VERSION = (0, 1)
+
 # The optional headers, in the order they are bound: every one is exported by libgjx_hip.so only and bound if present.
 class Header(collections.namedtuple("Header", "key header version_fn prototypes version_name unavailable")):
     @property
@@ -713,11 +746,19 @@ PLAN_HEADERS = {h.key: h for h in (
     Header("pointwise", "gjx_pointwise.h", "gjx_pointwise_version", POINTWISE_PROTOTYPES, "POINTWISE_ABI_VERSION",
            PointwiseUnavailable),
 )}
+# Headers that add entry points over the plans of a PLAN_HEADERS header (gjx_temper_cov.h moves a gjx_temper_plan).  A table of
+# its own for the same reason again: the suites of the earlier headers pin the contents of the three tables above; bound
+# after them and looked up with them everywhere.
+MOVE_HEADERS = {h.key: h for h in (
+    Header("temper_cov", "gjx_temper_cov.h", "gjx_temper_cov_version", TEMPER_COV_PROTOTYPES, "TEMPER_COV_ABI_VERSION",
+           TemperCovUnavailable),
+)}
 
 
 def all_optional_headers():
-    """Every header next to gjx.h, in binding order: OPTIONAL_HEADERS, then EXTENSION_HEADERS, then PLAN_HEADERS."""
-    return (*OPTIONAL_HEADERS.values(), *EXTENSION_HEADERS.values(), *PLAN_HEADERS.values())
+    """Every header next to gjx.h, in binding order: OPTIONAL_HEADERS, then EXTENSION_HEADERS, then PLAN_HEADERS, then
+    MOVE_HEADERS."""
+    return (*OPTIONAL_HEADERS.values(), *EXTENSION_HEADERS.values(), *PLAN_HEADERS.values(), *MOVE_HEADERS.values())
 
 
 _HEADER_OF = {name: h for h in all_optional_headers() for name in h.prototypes}  # entry point -> its optional header
@@ -728,6 +769,7 @@ _NO_STATUS = {
     "gjx_temper_ladder_workspace_bytes",
     "gjx_pointwise_chunks",
     "gjx_pointwise_workspace_bytes",
+    "gjx_temper_moments_workspace_bytes",
     "gjx_backmove_workspace_bytes",
     "gjx_backsim_workspace_bytes",
     "gjx_paths_workspace_bytes",

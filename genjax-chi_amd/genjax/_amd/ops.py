@@ -600,12 +600,27 @@ class Ops:
         """gjx_temper_move: ONE launch — every particle loads its ancestor's latents `x` (L float32[n] columns) and
         `lp` / `ll`, makes `n_moves` Metropolis-Hastings sweeps against prior * likelihood^beta under the scalar `key` (a
         prng.PRNGKey) and writes fresh columns.  -> (x [L columns], lp, ll, n_accept int32[n] or None)."""
+        self.lib.require("temper", "gjx_temper_move")
+        return self._temper_move("temper_move", None, plan, key, x, lp, ll, beta, n_moves, scales, ancestors, recompute, input_cols,
+                                 want_accept, max_workgroups)
+
+    def temper_move_cov(self, plan: "TemperPlan", key, x: list, lp, ll, beta: float, n_moves: int, factor: torch.Tensor, *,
+                        ancestors=None, recompute: bool = False, input_cols=(), want_accept: bool = True, max_workgroups: int = 0):
+        """gjx_temper_move_cov (include/gjx_temper_cov.h): ONE launch — temper_move with the proposal x' = x + F eps.
+        `factor`: F as float32 [L (L + 1) / 2] on the device, lower-triangular, packed by rows (what temper_moments
+        returns); it is handed over as a pointer: no host read.  -> (x [L columns], lp, ll, n_accept int32[n] or None)."""
+        self.lib.require("temper_cov", "gjx_temper_move_cov")
+        L = plan.n_latents
+        return self._temper_move("temper_move_cov", self._chk(factor, torch.float32, L * (L + 1) // 2, "factor"), plan, key, x, lp, ll,
+                                 beta, n_moves, None, ancestors, recompute, input_cols, want_accept, max_workgroups)
+
+    def _temper_move(self, what, factor, plan, key, x, lp, ll, beta, n_moves, scales, ancestors, recompute, input_cols, want_accept,
+                     max_workgroups):
         import numpy as np
 
-        self.lib.require("temper", "gjx_temper_move")
         L, n = plan.n_latents, x[0].numel()
         if len(x) != L:
-            raise ValueError(f"temper_move: the plan has {L} latents, got {len(x)} columns")
+            raise ValueError(f"{what}: the plan has {L} latents, got {len(x)} columns")
         io = abi.TemperIO()
         io.impl, io.n_moves, io.recompute, io.beta, io.n = key.impl, int(n_moves), 1 if recompute else 0, float(beta), n
         io.key[0], io.key[1], io.key_lane = key.k0, key.k1, key.lane
@@ -622,7 +637,7 @@ class Ops:
         if scales is not None:
             sc = np.ascontiguousarray(np.asarray(scales, dtype=np.float32).reshape(-1))
             if sc.size != L:
-                raise ValueError(f"temper_move: {L} scales expected, got {sc.size}")
+                raise ValueError(f"{what}: {L} scales expected, got {sc.size}")
             io.scales = sc.ctypes.data_as(C.POINTER(C.c_float))
         ins = (C.c_void_p * max(1, len(input_cols)))()
         for i, t in enumerate(input_cols):
@@ -632,8 +647,45 @@ class Ops:
         if acc is not None:
             io.n_accept = acc.data_ptr()
         io.max_workgroups = int(max_workgroups)
-        self.lib.call("gjx_temper_move", plan.handle, C.byref(io), self.stream())
+        if factor is None:
+            self.lib.call("gjx_temper_move", plan.handle, C.byref(io), self.stream())
+        else:
+            self.lib.call("gjx_temper_move_cov", plan.handle, C.byref(io), factor, self.stream())
         return list(block[:L]), block[L], block[L + 1], acc
+
+    def temper_moments_workspace(self, n: int, n_latents: int) -> torch.Tensor:
+        """A zeroed workspace of gjx_temper_moments for populations of n with n_latents columns (its ticket stays zero from
+        call to call: calls that share it must be stream-ordered)."""
+        self.lib.require("temper_cov", "gjx_temper_moments_workspace_bytes")
+        nb = int(self.lib.call("gjx_temper_moments_workspace_bytes", int(n), int(n_latents)))
+        if nb == 0:
+            raise ValueError(f"temper_moments: n = {n} or {n_latents} latents out of range")
+        return torch.zeros(max(nb, 8), dtype=torch.uint8, device=self._alloc_device)
+
+    def temper_moments(self, x: list, lw: torch.Tensor | None, ws: torch.Tensor | None = None, *, max_workgroups: int = 0):
+        """gjx_temper_moments (include/gjx_temper_cov.h): ONE launch over the L float32[n] columns `x` and the log-weights
+        `lw` (None: equal weights) -> (moments float64[1 + L + L (L + 1) / 2]: the weight sum relative to the maximum, the
+        weighted means, the weighted covariance packed by rows; factor float32[L (L + 1) / 2]: 2.38 / sqrt(L) times its
+        Cholesky factor, packed; scales float32[L]: the diagonal rule; n_degenerate int32[1]) — all on the device."""
+        self.lib.require("temper_cov", "gjx_temper_moments")
+        L, n = len(x), x[0].numel()
+        if not 1 <= L <= abi.TEMPER_MAX_LATENTS:
+            raise ValueError(f"temper_moments: 1 .. {abi.TEMPER_MAX_LATENTS} columns expected, got {L}")
+        io = abi.TemperMomentsIO()
+        io.n, io.n_latents = n, L
+        for l in range(L):
+            io.x[l] = self._chk(x[l], torch.float32, n, f"x[{l}]").value
+        if lw is not None:
+            io.lw = self._chk(lw, torch.float32, n, "lw").value
+        ws = self.temper_moments_workspace(n, L) if ws is None else ws
+        tri = L * (L + 1) // 2
+        moments = self.empty(1 + L + tri, torch.float64)
+        f32 = self.empty(tri + L, torch.float32)
+        ndeg = self.empty(1, torch.int32)
+        io.moments, io.factor, io.scales, io.n_degenerate = moments.data_ptr(), f32.data_ptr(), f32[tri:].data_ptr(), ndeg.data_ptr()
+        io.ws, io.ws_bytes, io.max_workgroups = ws.data_ptr(), ws.numel(), int(max_workgroups)
+        self.lib.call("gjx_temper_moments", C.byref(io), self.stream())
+        return moments, f32[:tri], f32[tri:], ndeg
 
     def temper_ladder_workspace(self, n: int) -> torch.Tensor:
         """A zeroed workspace of gjx_temper_ess_ladder for populations of n and any ladder length (its ticket stays zero
@@ -1158,6 +1210,15 @@ class TemperPlan(PlanHandle):
 
     def source(self, impl: int) -> str:
         return self._source("gjx_temper_plan_source", impl)
+
+    def cov_compile_check(self, impl: int) -> int:
+        """gjx_temper_cov_compile_check (include/gjx_temper_cov.h): the covariance move kernel of the same table."""
+        self.ops.lib.require("temper_cov", "gjx_temper_cov_compile_check")
+        return self.ops.lib._gjx_temper_cov_compile_check(self.handle, impl)
+
+    def cov_source(self, impl: int) -> str:
+        self.ops.lib.require("temper_cov", "gjx_temper_cov_source")
+        return self._source("gjx_temper_cov_source", impl)
 
 
 class ScanPlan(PlanHandle):

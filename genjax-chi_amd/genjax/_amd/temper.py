@@ -236,11 +236,14 @@ def next_beta(beta: float, need: float, ess_fn):
 
 class TemperedResult:
     """What `TemperedSMC.run` returns.  `choices`: the final, equally weighted population's latent columns as a ChoiceMap;
-    `lp`, `ll`: its log-prior and log-likelihood columns (f32[n], on the device)."""
+    `lp`, `ll`: its log-prior and log-likelihood columns (f32[n], on the device).  Under `proposal="covariance"`, `factor`:
+    the last stage's proposal factor, f32 [L, L], lower-triangular, on the device; `n_degenerate`: per stage, the latents
+    whose row of the factor fell back to the diagonal rule (include/gjx_temper_cov.h).  Both None on the diagonal route."""
 
-    def __init__(self, log_marginal_likelihood, betas, ess, accept_rate, choices, lp, ll, columns):
+    def __init__(self, log_marginal_likelihood, betas, ess, accept_rate, choices, lp, ll, columns, factor=None, n_degenerate=None):
         self.log_marginal_likelihood, self.betas, self.ess, self.accept_rate = log_marginal_likelihood, betas, ess, accept_rate
         self.choices, self.lp, self.ll, self.columns = choices, lp, ll, columns
+        self.factor, self.n_degenerate = factor, n_degenerate
 
     def __repr__(self):
         return (f"TemperedResult(log_marginal_likelihood={self.log_marginal_likelihood:.6f}, stages={len(self.betas) - 1}, "
@@ -309,16 +312,20 @@ class TemperedSMC(SMCAlgorithm):
     `n_moves`: Metropolis-Hastings sweeps per stage; `ess_target`: the next temperature is the largest whose increment keeps
     the effective sample size at `ess_target * n_particles`; `betas`: a FIXED increasing schedule ending at 1 instead;
     `scale`: one proposal scale per latent (a number for all) instead of 2.38 / sqrt(L) times the weighted population
-    standard deviation.
+    standard deviation; `proposal`: "diagonal" (that random walk, one latent at a time) or "covariance" — x' = x + F eps with
+    F = 2.38 / sqrt(L) times the Cholesky factor of the weighted population covariance, built on the device by one launch
+    (include/gjx_temper_cov.h): the proposal for a posterior whose latents are correlated.
 
     The adaptive schedule depends on the particles, so the estimate of Z is consistent but NOT exactly unbiased (Beskos,
     Jasra, Kantas & Thiery 2016); a fixed `betas=` keeps it unbiased.
 
     Host reads per adaptive stage: the two ladders' results and the proposal scales — three (two at the last stage, where
     the first ladder already reaches beta = 1; one fewer each with `scale=`; none with `betas=` and `scale=`) — and one at
-    the end of the run for the accumulated normalising constants and accept counts."""
+    the end of the run for the accumulated normalising constants and accept counts.  Under `proposal="covariance"` the factor
+    never leaves the device: two per adaptive stage, none before the end of the run with `betas=`."""
 
-    def __init__(self, target: Target, n_particles: int, n_moves: int = 2, ess_target: float = 0.5, betas=None, scale=None):
+    def __init__(self, target: Target, n_particles: int, n_moves: int = 2, ess_target: float = 0.5, betas=None, scale=None,
+                 proposal: str = "diagonal"):
         if not isinstance(target, Target):
             raise TypeError("TemperedSMC: target must be a Target")
         self.target, self.n_particles, self.n_moves = target, int(n_particles), int(n_moves)
@@ -336,6 +343,11 @@ class TemperedSMC(SMCAlgorithm):
                 raise ValueError("TemperedSMC: betas must increase strictly from above 0 to exactly 1")
             self.betas = b
         self.scale = scale
+        if proposal not in ("diagonal", "covariance"):
+            raise ValueError(f'TemperedSMC: proposal must be "diagonal" or "covariance", got {proposal!r}')
+        if proposal == "covariance" and scale is not None:
+            raise ValueError('TemperedSMC: scale= sets the diagonal proposal; it cannot be combined with proposal="covariance"')
+        self.proposal = proposal
         self._st = None
 
     def get_num_particles(self):
@@ -351,11 +363,13 @@ class TemperedSMC(SMCAlgorithm):
         if st is not None and st["ops"] is ops:
             return st
         ops.lib.require("temper", "gjx_temper_plan_create")
+        if self.proposal == "covariance":
+            ops.lib.require("temper_cov", "gjx_temper_move_cov")
         tracer = lower(self.target, self.n_particles)
         latents = [m for m in tracer.meta if m["obs"] is None]
         tplan = ops.temper_plan_create(tracer.sites, keep=(tracer.keep, tracer))
         prior = prior_table(tracer) if tracer.data else None
-        st = self._st = dict(ops=ops, tracer=tracer, latents=latents, tplan=tplan, ws=None, prior=prior)
+        st = self._st = dict(ops=ops, tracer=tracer, latents=latents, tplan=tplan, ws=None, prior=prior, ws_cov=None)
         return st
 
     def _scales(self, st):
@@ -405,6 +419,10 @@ class TemperedSMC(SMCAlgorithm):
         ws = st["ws"]
         fixed_scales = self._scales(st)
         need = self.ess_target * n
+        cov = self.proposal == "covariance"
+        if cov and st["ws_cov"] is None:
+            st["ws_cov"] = ops.temper_moments_workspace(n, L)
+        factor, degenerate = None, []
 
         def ess_fn(deltas):
             out = ops.temper_ess_ladder(ll, deltas, ws).cpu().numpy()  # (one host read)
@@ -425,10 +443,15 @@ class TemperedSMC(SMCAlgorithm):
             delta = float(np.float32(np.float32(nb) - np.float32(beta)))
             lw = ll * delta  # f32: one rounding per particle
             anc, e_s, q_s = ops.resample("systematic", prng.fold_in(ks, 0).literal(), lw)
-            sc = fixed_scales
-            if sc is None and K > 0:
-                sc = self.population_scales(x, lw).cpu().numpy()  # (one host read)
-            x, lp, ll, acc = ops.temper_move(tplan, prng.fold_in(ks, 1), x, lp, ll, nb, K, sc, ancestors=anc)
+            if cov:  # the moments of the weighted population BEFORE resampling; the factor stays on the device
+                _, factor, _, nd = ops.temper_moments(x, lw, st["ws_cov"])
+                degenerate.append(nd)  # (read at the end of the run)
+                x, lp, ll, acc = ops.temper_move_cov(tplan, prng.fold_in(ks, 1), x, lp, ll, nb, K, factor, ancestors=anc)
+            else:
+                sc = fixed_scales
+                if sc is None and K > 0:
+                    sc = self.population_scales(x, lw).cpu().numpy()  # (one host read)
+                x, lp, ll, acc = ops.temper_move(tplan, prng.fold_in(ks, 1), x, lp, ll, nb, K, sc, ancestors=anc)
             pairs.append((e_s, q_s))
             accepts.append(acc.sum())
             beta = nb
@@ -436,7 +459,11 @@ class TemperedSMC(SMCAlgorithm):
         # one host read for the whole run: the exact (e, q) pair of every stage, the accept counts, fixed-schedule ESS sums
         e_all = torch.cat([p[0] for p in pairs]).cpu().numpy().astype(np.int64)
         q_all = torch.cat([p[1] for p in pairs]).cpu().numpy().astype(np.int64)
-        acc_all = torch.stack(accepts).cpu().numpy()
+        if cov:  # (the stages' degenerate counts ride along with the accept counts)
+            tail = torch.cat([torch.stack(accepts).to(torch.int64), torch.cat(degenerate).to(torch.int64)]).cpu().numpy()
+            acc_all, degenerate = tail[:len(accepts)], [int(v) for v in tail[len(accepts):]]
+        else:
+            acc_all = torch.stack(accepts).cpu().numpy()
         log_z = 0.0
         for e_s, q_s in zip(e_all, q_all):
             if q_s <= 0:
@@ -447,7 +474,12 @@ class TemperedSMC(SMCAlgorithm):
             ess = [float(ess_of(o[0], o[1])) for o in torch.stack(ess).cpu().numpy()]
         rate = [float(a) / (n * K) if K else 0.0 for a in acc_all]
         choices = ChoiceMap.from_mapping([(m["addr"], c) for m, c in zip(st["latents"], x)])
-        return TemperedResult(float(log_z), betas, ess, rate, choices, lp, ll, x)
+        if not cov:
+            return TemperedResult(float(log_z), betas, ess, rate, choices, lp, ll, x)
+        full = torch.zeros(L, L, dtype=torch.float32, device=factor.device)
+        rows, cols = torch.tril_indices(L, L, device=factor.device)  # (row-major: the packing of the header)
+        full[rows, cols] = factor
+        return TemperedResult(float(log_z), betas, ess, rate, choices, lp, ll, x, full, degenerate)
 
     # -- the SMCAlgorithm interface --------------------------------------------------------------------------------------------
     def run_smc(self, key) -> ParticleCollection:
