@@ -1069,7 +1069,8 @@ GJX_DEV int32_t jcat_invcdf(const float* l, uint32_t K, uint32_t bits) {
   const float m = jrow_max(l, K);
   uint64_t Q = 0;
   for (uint32_t c = 0; c < K; ++c) Q += cat_fix(l[c], m);
-  const uint64_t thr = ((uint64_t)bits * Q) >> 32;
+  // floor(bits Q / 2^32), exact for any Q: from 512 classes near the maximum on Q reaches 2^32 and bits * Q leaves 64 bits
+  const uint64_t thr = (uint64_t)bits * (Q >> 32) + (((uint64_t)bits * (Q & 0xffffffffu)) >> 32);
   uint64_t C = 0;
   for (uint32_t c = 0; c < K; ++c) {
     C += cat_fix(l[c], m);

@@ -390,8 +390,11 @@ def check_regression_r02(ops):
 
 def check_hmm_alias(ops, k):
     """The alias table of every transition row encodes the row's softmax: summing, over the K columns, the
-    accept mass of the column and the reject mass handed to its alias reproduces softmax(logits) to the table's
-    24-bit threshold resolution; thresholds are below 2^24 and aliases are valid states."""
+    accept mass of the column and the reject mass handed to its alias reproduces softmax(logits) class by class — within
+    2^-24 (1 + a_c) / K of w^_c / Q (a_c columns alias to c; the threshold roundings) and that within (e_c + p_c E) /
+    max(1, S - E) of the softmax (cat_fix's 2^-24 per class relative to the row MAXIMUM: up to K 2^-24 per row in total);
+    cat_range_ref.alias_check asserts those bounds on wide tables.  On this benign circulant table the two add up to less
+    than the 4e-7 below; thresholds are below 2^24 and aliases are valid states."""
     from genjax._amd import workloads as W
 
     tl, ol = W.hmm_tables(k)
