@@ -416,7 +416,9 @@ GJX_HD float m_exp(float x) {
   return m_exp_core(x);
 }
 // (the arithmetic of m_exp for -86 <= x <= 88: callers that have already clamped select around it without a branch)
-GJX_HD float m_exp_core(float x) {
+// (`k`: m_exp_core(x) 2^k, the scaling folded into the exponent add.  The same bits as the product wherever neither is
+// subnormal or overflows: y is in [0.7, 1.42] and the add only moves its exponent field.)
+GJX_HD float m_exp_core_shl(float x, int32_t k) {
   const float fx = __builtin_rintf(x * 1.44269504088896341f);
   x = __builtin_fmaf(fx, -0.693359375f, x);
   x = __builtin_fmaf(fx, 2.12194440e-4f, x);
@@ -429,8 +431,9 @@ GJX_HD float m_exp_core(float x) {
   p = __builtin_fmaf(p, x, 5.0000001201E-1f);
   const float y = __builtin_fmaf(p, z, x) + 1.0f;
   const int32_t n = (int32_t)fx;
-  return u2f(f2u(y) + ((uint32_t)n << 23));
+  return u2f(f2u(y) + ((uint32_t)(n + k) << 23));
 }
+GJX_HD float m_exp_core(float x) { return m_exp_core_shl(x, 0); }
 
 // exp as a model body writes it (GJX_EXPR_EXP, gjx_map_f32): m_exp over its whole domain — NaN stays NaN, the top of the
 // range (m_exp clamps at 88, flushes below -86) goes through exp(x / 2)^2: +inf / subnormals / 0 where exp has them.
@@ -712,16 +715,17 @@ GJX_HD float sqrt_pos(float x) {
   return __builtin_sqrtf(x);
 #endif
 }
-GJX_HD void bm_pair(uint32_t w_radius, uint32_t w_angle, float& z_cos, float& z_sin) {
+// The transform in parts: the radius r and the two angle factors, z_cos = r * t_cos and z_sin = r * t_sin.
+GJX_HD void bm_parts(uint32_t w_radius, uint32_t w_angle, float& r_out, float& t_cos, float& t_sin) {
   // radius: u = (w + 1) 2^-32 in (0, 1] with full float resolution near 0 (tails to 6.6 sigma)
   const float uw = (float)w_radius + 1.0f;  // 2^32 u, in [1, 2^32]
 #ifdef GJX_FAST_MATH_DEVICE
   {  // the same map from the same two words through the hardware functions (v_sin / v_cos take revolutions)
     const float u = uw * 2.3283064365386963e-10f;
-    const float rf = __builtin_amdgcn_sqrtf(-1.38629436111989062f * __builtin_amdgcn_logf(u));
+    r_out = __builtin_amdgcn_sqrtf(-1.38629436111989062f * __builtin_amdgcn_logf(u));
     const float tf = (float)(w_angle >> 8) * 5.9604644775390625e-08f;
-    z_cos = rf * __builtin_amdgcn_cosf(tf);
-    z_sin = rf * __builtin_amdgcn_sinf(tf);
+    t_cos = __builtin_amdgcn_cosf(tf);
+    t_sin = __builtin_amdgcn_sinf(tf);
     return;
   }
 #endif
@@ -744,8 +748,34 @@ GJX_HD void bm_pair(uint32_t w_radius, uint32_t w_angle, float& z_cos, float& z_
   const float sd = __builtin_fmaf(d2 * d, -0.166666672f, d);
   const float cd = __builtin_fmaf(d2, __builtin_fmaf(d2, 0.0416666679f, -0.5f), 1.0f);
   const float ca = u2f(cs.a), sa = u2f(cs.b);
-  z_cos = r * __builtin_fmaf(ca, cd, -(sa * sd));
-  z_sin = r * __builtin_fmaf(sa, cd, ca * sd);
+  r_out = r;
+  t_cos = __builtin_fmaf(ca, cd, -(sa * sd));
+  t_sin = __builtin_fmaf(sa, cd, ca * sd);
+}
+GJX_HD void bm_pair(uint32_t w_radius, uint32_t w_angle, float& z_cos, float& z_sin) {
+  float r, tc, ts;
+  bm_parts(w_radius, w_angle, r, tc, ts);
+  z_cos = r * tc;
+  z_sin = r * ts;
+}
+// The VALUES of a latent site normal(+0.0, 1.0), 0.0f + 1.0f * z (the generator's tag; gjx_plan_jit.hpp zero_loc_unit decides).
+// The multiply by 1 folds; the add of +0 does not (it turns a -0 into +0), but it fuses into the transform's last product:
+// fma(r, t, +0) is (r t) + (+0) bit for bit unless the exact product is nonzero and rounds to zero — and r is a zero or at
+// least 3.45e-4 (the radius of the words next to u = 1), a nonzero t at least 6.2e-11 in magnitude (the angle next to a
+// quarter turn): the smallest nonzero product is 2.2e-14, nowhere near 2^-126.  tools/check_row_cuts.cpp runs every angle
+// word against the edge radii and a seeded million; gjx_debug_zero_loc_sweep (gjx_hip.hip) the two smallest radii on the
+// device.  Either way the value is never -0: the sum of anything and +0 is not.  -DGJX_ZERO_LOC_PLAIN keeps the two operations.
+struct PlusZero {};
+GJX_HD void bm_pair(uint32_t w_radius, uint32_t w_angle, float& z_cos, float& z_sin, PlusZero) {
+  float r, tc, ts;
+  bm_parts(w_radius, w_angle, r, tc, ts);
+#if defined(GJX_ZERO_LOC_PLAIN) || defined(GJX_FAST_MATH_DEVICE)
+  z_cos = 0.0f + r * tc;
+  z_sin = 0.0f + r * ts;
+#else
+  z_cos = __builtin_fmaf(r, tc, 0.0f);
+  z_sin = __builtin_fmaf(r, ts, 0.0f);
+#endif
 }
 constexpr uint32_t kTagTwin = 0x54u;  // 'T': the angle word of a lane-0 key (it has no partner particle)
 // The standard normal of a Normal SITE (generic, one particle: both words of its pair are derived here;
@@ -1017,9 +1047,19 @@ GJX_HD uint64_t rowfix(float lw, int32_t e) {
     const float fe = (float)e;
     float d = __builtin_fmaf(-fe, 0.693359375f, lw);
     d = __builtin_fmaf(-fe, -2.12194440e-4f, d);
+#if defined(GJX_ROWFIX_PLAIN) || defined(GJX_FAST_MATH_DEVICE)
     d = d > 1.0f ? 1.0f : d;
     const bool live = e != kRowEmpty && lw > -__builtin_inff() && d >= -86.0f;
     const uint32_t q = (uint32_t)__builtin_rintf(d_exp_core(live ? d : 0.0f) * 1073741824.0f);
+#else
+    // Two trims, the same integer for every (lw, e) (tools/check_row_cuts.cpp runs every d of [-86, 1] and the dead cases):
+    // the clamp as one minimum instead of a compare and a select (d is a NaN only when lw is, and that weight is dead
+    // through `live` whichever way the clamp treats it), and the scaling by 2^30 inside m_exp_core's exponent add (d in
+    // [-86, 1]: the result is between 2^-95 and e 2^30, normal either way).  -DGJX_ROWFIX_PLAIN keeps the former text.
+    d = __builtin_fminf(d, 1.0f);
+    const bool live = e != kRowEmpty && lw > -__builtin_inff() && d >= -86.0f;
+    const uint32_t q = (uint32_t)__builtin_rintf(m_exp_core_shl(live ? d : 0.0f, 30));
+#endif
     return live ? q : 0u;
   }
 #endif
@@ -1190,6 +1230,40 @@ GJX_DEV float wave_max(float v) {
   const uint32_t r = wave_scan_u32(f2u(v), f2u(-__builtin_inff()),
                                    [](uint32_t a, uint32_t b) { return u2f(b) > u2f(a) ? b : a; });
   return u2f(wave_last_u32(r));
+}
+// The same maximum on order-preserving integer keys: a float's bits with the magnitude bits flipped under a set sign read
+// as int32 in the floats' own order (the map is its own inverse), and an integer maximum takes its DPP operand directly —
+// one instruction per scan step where the float form is a move, a compare and a select.  The scan's identity is INT32_MIN,
+// below every key (the key of -inf is 0x807fffff), and it never survives: every lane's own value enters its result.
+// DOMAIN: equal to wave_max for every set of lane values that does not hold both +0 and -0.  The keys order -0 below +0
+// where the float compare calls them equal and keeps whichever lane came first.  The callers' values (the log-weights of a
+// generated importance or scan kernel's row) are never -0: an accumulator starts at +0 or at a Normal log-density with a
+// nonzero literal log-normaliser (gjx_plan_jit.hpp first contribution), and a sum is -0 only if every term is.
+// tools/check_row_cuts.cpp runs a host model of the scan against the select chain.  -DGJX_WAVE_MAX_SELECT: wave_max.
+GJX_HD int32_t order_key(uint32_t bits) { return (int32_t)(bits ^ ((uint32_t)((int32_t)bits >> 31) & 0x7fffffffu)); }
+GJX_DEV float wave_max_ordered(float v) {
+#ifdef GJX_WAVE_MAX_SELECT
+  return wave_max(v);
+#else
+  v = v == v ? v : -__builtin_inff();
+  // (the lanes' keys: the mask is made opaque so that AND and XOR stay two plain instructions, 4.8 cycles of issue — fused
+  // into one three-input v_bitop3_b32 they cost 4.3 (tools/README.md), once per row, and the count of v_bitop3_b32 is what
+  // tests/test_exact_cuts_cpu.py and tests/test_philox_xor3_cpu.py recognise the cipher's rounds by)
+  uint32_t mask = (uint32_t)((int32_t)f2u(v) >> 31) & 0x7fffffffu;
+  asm volatile("" : "+v"(mask));
+  const uint32_t r = wave_scan_u32(f2u(v) ^ mask, 0x80000000u,
+                                   [](uint32_t a, uint32_t b) { return (uint32_t)((int32_t)b > (int32_t)a ? (int32_t)b : (int32_t)a); });
+  return u2f((uint32_t)order_key(wave_last_u32(r)));
+#endif
+}
+// The first contribution to an accumulator that would start at +0: 0.0f + lp is lp itself unless lp is -0, and the generator
+// asks only for log-densities that never are (gjx_plan_jit.hpp).  -DGJX_FIRST_ACC_PLAIN keeps the addition.
+GJX_HD float first_acc(float lp) {
+#ifdef GJX_FIRST_ACC_PLAIN
+  return 0.0f + lp;
+#else
+  return lp;
+#endif
 }
 GJX_DEV uint64_t wave_sum(uint64_t v) {
   return wave_last_u64(wave_scan_u64(v, 0, [](uint64_t a, uint64_t b) { return a + b; }));

@@ -1845,6 +1845,29 @@ __global__ __launch_bounds__(kBlock) void k_sqrt_pos_sweep(uint32_t lo, uint64_t
     atomicMin(&out[1], first);
   }
 }
+// gjx_debug_zero_loc_sweep: the two forms of a normal(+0, 1) site's value, (r t) + 0 and fma(r, t, 0) (gjx_device.hpp bm_pair,
+// PlusZero), over all 2^24 angle words (the transform reads the top 24 bits) at two radius words, both outputs each;
+// out[0] += the mismatches, out[1] = min(out[1], a mismatching angle index)
+__global__ __launch_bounds__(kBlock) void k_zero_loc_sweep(uint32_t wr0, uint32_t wr1, unsigned long long* out) {
+  unsigned long long bad = 0, first = ~0ull;
+  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < ((uint64_t)1 << 24); i += (uint64_t)gridDim.x * kBlock) {
+    const uint32_t wa = (uint32_t)i << 8;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      float zc, zs, pc, ps;
+      bm_pair(k ? wr1 : wr0, wa, zc, zs);
+      bm_pair(k ? wr1 : wr0, wa, pc, ps, PlusZero());
+      if (f2u(0.0f + zc) != f2u(pc) || f2u(0.0f + zs) != f2u(ps)) {
+        ++bad;
+        first = first < i ? first : i;
+      }
+    }
+  }
+  if (bad) {
+    atomicAdd(&out[0], bad);
+    atomicMin(&out[1], first);
+  }
+}
 }  // namespace
 
 // ================================================================================================
@@ -2122,6 +2145,8 @@ struct gjx_plan {
                                   // that passes a gjx_lse_out, so the default launches do not carry the fold's registers
   gjx_jit::Compiled jit_wt[2];  // the quad form with WRITE-THROUGH stores (gjx_jit::Gen::wt_stores), [1] with the fused fold:
                                 // built on the first launch of a single pass (the other forms have one kind of store)
+  gjx_jit::Compiled jit_full[2];  // the quad form of a launch that passes EVERY output (gjx_jit::Gen::full_outputs), [1] with
+                                  // write-through stores: built on the first such launch, or by gjx_plan_prepare
   std::vector<void*> dev_owned;  // per-row tables of categorical sites (specialised kernels)
   std::mutex jit_mu;
   ExprStore expr;      // GJX_ARG_EXPR programs (host; read by the code generator)
@@ -2398,32 +2423,36 @@ static int jit_form_pref() {  // GJX_JIT_FORM = one | pair | quad (test / tuning
 // A hinted build that spills more than 32 B is replaced by the unhinted one (plan_compiled).
 static int jit_waves_hint(int P) { return P == 2 ? 6 : 0; }
 // The importance generator of a plan.  `form`: particles per lane, 1, 2 (pairs) or 4 (quads); above 1 is PHILOX only.
-static void plan_gen_setup(gjx_jit::Gen<CSite, CArg>& g, const gjx_plan* p, int impl, int form, bool fused_tail, bool wt_stores, int min_waves) {
+static void plan_gen_setup(gjx_jit::Gen<CSite, CArg>& g, const gjx_plan* p, int impl, int form, bool fused_tail, bool wt_stores, int min_waves,
+                           bool full_outputs = false) {
   g.impl = impl; g.sites = p->host; g.n_sites = p->n_sites; g.laned = form >= 2; g.pairs_per_lane = form == 4 ? 2 : 1;
   g.sc = p->scopes.n_scopes > 0 ? &p->scopes : nullptr;
   g.fast_math = (p->flags & GJX_PLAN_FAST_MATH) != 0;
   g.fused_tail = fused_tail;
   g.wt_stores = wt_stores;
+  g.full_outputs = full_outputs;
   g.min_waves = min_waves;
 }
 int gjx_plan_specialized_source(const gjx_plan* p, int impl, char* buf, size_t buf_len, size_t* needed) {
   const bool fused_tail = (impl & GJX_SOURCE_FUSED_TAIL) != 0, wt_stores = (impl & GJX_SOURCE_WT_STORES) != 0;
-  impl &= ~(GJX_SOURCE_FUSED_TAIL | GJX_SOURCE_WT_STORES);
+  const bool full_outputs = (impl & GJX_SOURCE_FULL_OUTPUTS) != 0;
+  impl &= ~(GJX_SOURCE_FUSED_TAIL | GJX_SOURCE_WT_STORES | GJX_SOURCE_FULL_OUTPUTS);
   if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
   const int form = impl == 1 ? jit_form_pref() : 1;  // (GJX_JIT_FORM picks the PHILOX form shown)
   gjx_jit::Gen<CSite, CArg> g;
-  plan_gen_setup(g, p, impl, form, fused_tail, wt_stores, jit_waves_hint(form));  // the kernel that ships
+  plan_gen_setup(g, p, impl, form, fused_tail, wt_stores, jit_waves_hint(form), full_outputs);  // the kernel that ships
   gjx_jit::TableScope ts;
   return copy_source_out(g.run(), buf, buf_len, needed);
 }
 
 int gjx_plan_compile_check(const gjx_plan* p, int impl) {
   const bool fused_tail = (impl & GJX_SOURCE_FUSED_TAIL) != 0, wt_stores = (impl & GJX_SOURCE_WT_STORES) != 0;
-  impl &= ~(GJX_SOURCE_FUSED_TAIL | GJX_SOURCE_WT_STORES);
+  const bool full_outputs = (impl & GJX_SOURCE_FULL_OUTPUTS) != 0;
+  impl &= ~(GJX_SOURCE_FUSED_TAIL | GJX_SOURCE_WT_STORES | GJX_SOURCE_FULL_OUTPUTS);
   if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
   for (int form = 1; form <= (impl == 1 ? 4 : 1); form *= 2) {  // PHILOX: one particle per lane, pairs, quads
     gjx_jit::Gen<CSite, CArg> g;
-    plan_gen_setup(g, p, impl, form, fused_tail, wt_stores && form == 4, jit_waves_hint(form));
+    plan_gen_setup(g, p, impl, form, fused_tail, wt_stores && form == 4, jit_waves_hint(form), full_outputs && form == 4);
     gjx_jit::TableScope ts;
     if (!gjx_jit::compile_only(g.run(), gjx_jit::PlanKind::importance)) return GJX_ERR_UNSUPPORTED;
   }
@@ -2435,6 +2464,7 @@ int gjx_plan_destroy(gjx_plan* p) {
   for (auto& c : p->jit) c.release();  // the modules stay cached (bounded, LRU) for plans of the same structure
   for (auto& c : p->jit_tail) c.release();
   for (auto& c : p->jit_wt) c.release();
+  for (auto& c : p->jit_full) c.release();
   free_owned(p->dev_owned);
   delete p;
   return GJX_OK;
@@ -2444,7 +2474,10 @@ int gjx_plan_destroy(gjx_plan* p) {
 // `lane_particles`: how many adjacent particles a lane may own given n and the alignment of the output buffers (1, 2, 4).
 // `fused_tail`: the variant that folds the row sums inside the launch (launches that pass a gjx_lse_out).
 // `one_pass`: a launch of a single pass; the quad form then stores write-through (gjx_jit::Gen::wt_stores).
-static gjx_jit::Compiled& plan_compiled(gjx_plan* mp, const gjx_keys* pk, int lane_particles, bool fused_tail = false, bool one_pass = false) {
+// `all_outputs`: the launch passes score, logw, max_partials, row_e and row_s and no gjx_lse_out; the quad form then runs the
+// variant that asks nothing about them (gjx_jit::Gen::full_outputs).
+static gjx_jit::Compiled& plan_compiled(gjx_plan* mp, const gjx_keys* pk, int lane_particles, bool fused_tail = false, bool one_pass = false,
+                                        bool all_outputs = false) {
   // PHILOX children of a lane-0 key share one cipher key, and an even first index keeps particle pairs
   // (2i, 2i+1) together: the paired / quad kernel forms (gjx_plan_jit.hpp)
   const bool pairable = pk->impl == 1 && pk->mode == 1 && pk->parent_lane == 0 && (pk->first & 1) == 0;
@@ -2452,11 +2485,14 @@ static gjx_jit::Compiled& plan_compiled(gjx_plan* mp, const gjx_keys* pk, int la
   if (P == 3) P = 2;
   const bool laned = P >= 2;
   const bool wt_stores = one_pass && P == 4;
-  gjx_jit::Compiled& c = wt_stores ? mp->jit_wt[fused_tail ? 1 : 0] : (fused_tail ? mp->jit_tail : mp->jit)[P == 4 ? 3 : (laned ? 2 : pk->impl)];
+  const bool full_outputs = all_outputs && !fused_tail && P == 4;
+  gjx_jit::Compiled& c = full_outputs ? mp->jit_full[wt_stores ? 1 : 0]
+                         : wt_stores  ? mp->jit_wt[fused_tail ? 1 : 0]
+                                      : (fused_tail ? mp->jit_tail : mp->jit)[P == 4 ? 3 : (laned ? 2 : pk->impl)];
   compiled_once(mp->jit_mu, c, {{mp->host, mp->n_sites}}, &mp->dev_owned, [&] {
     auto build = [&](int min_waves) {
       gjx_jit::Gen<CSite, CArg> g;
-      plan_gen_setup(g, mp, pk->impl, P, fused_tail, wt_stores, min_waves);
+      plan_gen_setup(g, mp, pk->impl, P, fused_tail, wt_stores, min_waves, full_outputs);
       gjx_jit::TableScope ts;  // the source numbers the plan's device tables; the addresses travel as a kernel argument
       const std::string src = g.run();
       c.block = g.block;
@@ -2471,7 +2507,8 @@ static gjx_jit::Compiled& plan_compiled(gjx_plan* mp, const gjx_keys* pk, int la
     if (ok && std::getenv("GJX_PLAN_JIT_VERBOSE")) {  // what the loaded code object allocates (the VGPR column of a rocprofv3 kernel trace is HALF of this)
       int regs = 0;
       if (hipFuncGetAttribute(&regs, HIP_FUNC_ATTRIBUTE_NUM_REGS, c.fn) != hipSuccess) (void)hipGetLastError();
-      fprintf(stderr, "gjx jit: %d particle(s) per lane%s%s: %d registers per lane\n", P, fused_tail ? ", fused tail" : "", wt_stores ? ", write-through stores" : "", regs);
+      fprintf(stderr, "gjx jit: %d particle(s) per lane%s%s%s: %d registers per lane\n", P, fused_tail ? ", fused tail" : "", wt_stores ? ", write-through stores" : "",
+              full_outputs ? ", every output" : "", regs);
     }
     if (ok && hint > 0) {
       int scratch = 0;
@@ -2507,6 +2544,8 @@ int gjx_plan_prepare(gjx_plan* p, const gjx_keys* pk) {
   ok = plan_compiled(p, pk, 2).state == 1 && ok;
   ok = plan_compiled(p, pk, 4).state == 1 && ok;
   ok = plan_compiled(p, pk, 4, false, true).state == 1 && ok;  // (a single-pass launch: the quad form's other kind of store)
+  ok = plan_compiled(p, pk, 4, false, false, true).state == 1 && ok;  // (a launch with every output: the quad form that asks nothing)
+  ok = plan_compiled(p, pk, 4, false, true, true).state == 1 && ok;
   if (ok) return GJX_OK;
   return jit_fallback_allowed() && !p->has_expr ? plan_device_table(p) : GJX_ERR_JIT;
 }
@@ -2561,7 +2600,8 @@ static int importance_launch(const gjx_plan* p, const gjx_keys* pk, int32_t n_pa
     uintptr_t al = (uintptr_t)logw | (uintptr_t)score | (uintptr_t)(4 * pass_stride) | (uintptr_t)(4 * n);
     for (int c = 0; c < n_value_cols; ++c) al |= (uintptr_t)value_cols[c];
     const int lane_particles = (al & 15) == 0 ? 4 : ((al & 7) == 0 ? 2 : 1);
-    gjx_jit::Compiled& c = plan_compiled(const_cast<gjx_plan*>(p), pk, lane_particles, lse != nullptr, n_pass <= 1);
+    const bool all_outputs = score && logw && max_partials && row_e && row_s && !lse;
+    gjx_jit::Compiled& c = plan_compiled(const_cast<gjx_plan*>(p), pk, lane_particles, lse != nullptr, n_pass <= 1, all_outputs);
     if (c.state != 1 && (!jit_fallback_allowed() || p->has_expr || p->scopes.n_scopes > 0)) return GJX_ERR_JIT;  // loud: never a silent 7x slower route
     if (c.state == 1) {
       uint64_t nn = n;
@@ -3677,6 +3717,11 @@ int gjx_debug_sqrt_pos_sweep(uint32_t lo_bits, uint32_t hi_bits, uint64_t* out, 
   const uint64_t count = (uint64_t)hi_bits - lo_bits + 1;
   const uint64_t blocks = (count + kBlock - 1) / kBlock;
   k_sqrt_pos_sweep<<<(unsigned)(blocks < 2048 ? blocks : 2048), kBlock, 0, S(s)>>>(lo_bits, count, reinterpret_cast<unsigned long long*>(out));
+  return launch_status();
+}
+int gjx_debug_zero_loc_sweep(uint32_t w_radius0, uint32_t w_radius1, uint64_t* out, gjx_stream s) {
+  if (!out) return GJX_ERR_INVALID;
+  k_zero_loc_sweep<<<2048, kBlock, 0, S(s)>>>(w_radius0, w_radius1, reinterpret_cast<unsigned long long*>(out));
   return launch_status();
 }
 int gjx_jit_stats(uint64_t* compiles, uint64_t* cached_modules, uint64_t* evictions) {

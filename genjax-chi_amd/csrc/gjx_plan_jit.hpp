@@ -153,7 +153,23 @@ struct SiteEmitter {
   bool store_values = true;  // false: the caller stores (the paired kernel writes both particles at once)
   bool ext_bits = false;     // true: the caller defines bits<q><sfx> of one-word draws (SMC quads share a block)
   bool exact_cuts = true;    // false: Normal log-densities keep the three-operation form everywhere (normal_exact_cuts)
+  bool row_cuts = false;     // true (the pair / quad importance and scan kernels): the exact zero-add cuts below, each only where
+                             // its conditions hold.  Off everywhere else — the tempered plans' sources are pinned byte for byte
   const ScopeInfo* sc = nullptr;  // nested calls: per-site key scope and fold (null: a flat body, the implicit numbering)
+  // (a) A latent Normal site of the lane's own scope whose location is the literal +0.0f (not -0.0f: the add of -0 is the
+  // identity and folds by itself) and whose scale is the literal 1.0f: its value 0.0f + 1.0f * z is the transform's output
+  // itself under the PlusZero overload of bm_pair (gjx_device.hpp), which fuses the add into its last product.
+  bool zero_loc_unit(int q) const {
+    const CSiteT& st = sites[q];
+    return row_cuts && pairs_normals() && st.dist == GJX_DIST_NORMAL && st.observed == 0 && scope_of(q) == 0 && !retained(q) &&
+           st.a0.kind == GJX_ARG_CONST && gjx::f2u(st.a0.offset) == 0u && st.a1.kind == GJX_ARG_CONST && st.a1.offset == 1.0f;
+  }
+  // (b) A reference to such a site with literal scale 1.0f and offset +0.0f is the value itself: 1.0f * v folds, and v + 0.0f
+  // is v unless v is -0 — which a value produced by an fma (or an addition) with +0 never is.
+  bool identity_ref(const CArgT& a) const {
+    return a.kind == GJX_ARG_SITE && a.scale == 1.0f && gjx::f2u(a.offset) == 0u && a.ref_site >= 0 && a.ref_site < n_sites &&
+           zero_loc_unit(a.ref_site);
+  }
   // include/gjx_csmc.h (the conditional kernels only): ret_comp[q] >= 0 — sampled site q is carry component ret_comp[q]; its
   // draw is made as ever (named vd<q> / vj<q>) and its VALUE is `rsel<sfx> ? rv_<k> : the draw`: a select in front of every
   // log-density that reads it.  null: the source of the unconditional kernels, byte for byte.
@@ -184,7 +200,9 @@ struct SiteEmitter {
   std::string arg(const CArgT& a) const {
     switch (a.kind) {
       case GJX_ARG_CONST: return flit(a.offset);
-      case GJX_ARG_SITE: return "((" + flit(a.scale) + " * " + val_f32(a.ref_site) + ") + " + flit(a.offset) + ")";
+      case GJX_ARG_SITE:
+        if (identity_ref(a)) return nm("vf", a.ref_site);
+        return "((" + flit(a.scale) + " * " + val_f32(a.ref_site) + ") + " + flit(a.offset) + ")";
       case GJX_ARG_INPUT:
         return "((" + flit(a.scale) + " * cols.in[" + std::to_string(a.ref) + "][li" + sfx + "]) + " + flit(a.offset) + ")";
       case GJX_ARG_STATE: return "((" + flit(a.scale) + " * st_" + std::to_string(a.ref) + sfx + ") + " + flit(a.offset) + ")";
@@ -383,6 +401,10 @@ struct SiteEmitter {
       switch (st.dist) {
         case GJX_DIST_NORMAL: {
           std::string e = eps;
+          if (zero_loc_unit(q)) {  // (the caller drew eps through bm_pair's PlusZero overload: the value itself)
+            o << ind << "const float " << VF << " = " << e << ";\n";
+            break;
+          }
           if (e.empty())
             e = pairs_normals() ? "site_normal<1>(Stream<1>(" + K + ", true, " + std::to_string(fold) + "u))"
                                 : "std_normal(bits" + Q + ")";
@@ -546,10 +568,17 @@ inline void emit_prelude(std::ostringstream& o, bool fast_math = false, bool bm_
 template <class CSiteT, class CArgT>
 inline void emit_pair_lane_sites(std::ostringstream& o, std::vector<SiteEmitter<CSiteT, CArgT>>& em, const CSiteT* sites, int n_sites,
                                  int NP, const std::string& ind, const std::string& store_at, const std::string& sc_guard = "",
-                                 const std::string& ubase = "", const std::string& lane_bytes = "") {
+                                 const std::string& ubase = "", const std::string& lane_bytes = "", bool sc_known = false) {
   const char* sfx[4] = {"A", "B", "C", "D"};
   const int P = 2 * NP;
-int cur_pair_blk = -1;
+  int cur_pair_blk = -1;
+  // `sc_known` (Gen::full_outputs): the launch stores the scores — no question is asked at the sites
+  const std::string if_sc = sc_known ? "" : "if (" + sc_guard + ") ";
+  // (c) The first contribution to the lane's weights (and to its scores) initialises them where it is a NormalExactCuts
+  // density: that is fma(d d, -0.5, -L) with L a nonzero literal, never -0, so 0.0f + lp is lp (gjx_device.hpp first_acc).
+  // Any other first contribution is added to the +0 the accumulators are declared with.  Flat bodies only: a callee's totals
+  // reach the caller's accumulators through close_scopes.
+  bool w_open = false, sc_open = false;
   for (int q = 0; q < n_sites; ++q) {
     const CSiteT& st = sites[q];
     // `sc_guard` (the importance kernels: the name of the score pointer): the lane's weights and scores are brought up to
@@ -583,7 +612,7 @@ int cur_pair_blk = -1;
       for (int pi = 0; pi < NP; ++pi) {
         const std::string Z = Q + "_" + std::to_string(pi);
         o << ind << "float zc" << Z << ", zs" << Z << ";\n      bm_pair(bits" << Q << sfx[2 * pi] << ", bits" << Q << sfx[2 * pi + 1] << ", zc" << Z
-          << ", zs" << Z << ");\n";
+          << ", zs" << Z << (em[0].zero_loc_unit(q) ? ", PlusZero());\n" : ");\n");
       }
       for (int pi = 0; pi < NP; ++pi) {
         const std::string Z = Q + "_" + std::to_string(pi);
@@ -632,20 +661,27 @@ int cur_pair_blk = -1;
         }
         return t;
       };
+      const bool never_neg_zero = em[0].row_cuts && !em[0].sc && st.observed <= 1 && em[0].normal_exact_cuts(st);
+      auto acc_to = [&](const char* base, bool first, int u, const std::string& lp) {
+        const std::string a = std::string(base) + sfx[u];
+        return first ? a + " = first_acc(" + lp + "); " : a + " = " + a + " + " + lp + "; ";
+      };
       if (st.observed) {  // the log-density enters the weight (always needed) and the score
         for (int u = 0; u < P; ++u) o << ind << "const float lp" << Q << sfx[u] << " = " << em[u].lp_of(q) << ";\n";
         o << ind;
-        for (int u = 0; u < P; ++u) o << "w" << sfx[u] << " = w" << sfx[u] << " + lp" << Q << sfx[u] << "; ";
+        for (int u = 0; u < P; ++u) o << acc_to("w", !w_open && never_neg_zero, u, "lp" + Q + sfx[u]);
         o << pins("w") << "\n";
-        o << ind << "if (" << sc_guard << ") { ";
-        for (int u = 0; u < P; ++u) o << "sc" << sfx[u] << " = sc" << sfx[u] << " + lp" << Q << sfx[u] << "; ";
+        o << ind << if_sc << "{ ";
+        for (int u = 0; u < P; ++u) o << acc_to("sc", !sc_open && never_neg_zero, u, "lp" + Q + sfx[u]);
         o << pins("sc") << " }\n";
+        w_open = true;
       } else {  // a latent site's log-density is part of the score alone
-        o << ind << "if (" << sc_guard << ") {\n";
+        o << ind << if_sc << "{\n";
         for (int u = 0; u < P; ++u)
-          o << ind << "  { const float lp = " << em[u].lp_of(q) << "; sc" << sfx[u] << " = sc" << sfx[u] << " + lp; }\n";
+          o << ind << "  { const float lp = " << em[u].lp_of(q) << "; " << acc_to("sc", !sc_open && never_neg_zero, u, "lp") << "}\n";
         o << ind << " " << pins("sc") << "\n" << ind << "}\n";
       }
+      sc_open = true;
       for (int u = 0; u < P; ++u) em[u].defer_acc = false;
     }
     for (int u = 0; u < P; ++u) em[u].close_scopes(q + 1);
@@ -684,6 +720,10 @@ struct Gen {
   bool wt_stores = false;  // the quad form's 16-byte stores are write-through (launches of ONE pass) instead of plain.  A variant
                            // of its own: as a run-time flag every store was a uniform branch pair (88 scalar instructions per
                            // row of the 10-latent kernel) and a basic block of its own
+  bool full_outputs = false;  // the one-row quad form of a launch that passes score, logw, max_partials, row_e and row_s (and no
+                              // gjx_lse_out): all five are known non-null, so the source asks nothing about them — as run-time
+                              // questions they were 25 uniform branches and a compare per site in every row of the 10-latent
+                              // kernel, and cut the row into some 40 basic blocks.  Every other form ignores the flag
   int block = 256;    // threads per workgroup of the generated kernel
   int rows_per_block = 1;
   bool laned = false; // the paired form (see above)
@@ -742,6 +782,7 @@ struct Gen {
     // the quad form's stores: one wave-uniform base per column and row (scalar registers) plus ONE per-lane byte offset
     // (gjx_device.hpp store16_at); the four-row workgroup of the estimate-only kernel has no block-uniform row
     const bool ubase = NP == 2 && R == 1;
+    const bool full = full_outputs && ubase;  // (Gen::full_outputs)
     emit_prelude(o, fast_math, bm_lds(), block);
     emit_hint_default();
     o << "extern \"C\" __global__ " << bounds(block) << " void " << kname() << signature();
@@ -798,17 +839,18 @@ struct Gen {
       em.push_back(SiteEmitter<CSiteT, CArgT>{o, impl, 0, sites, n_sites, "      ", sfx[u]});
       em.back().store_values = false;
       em.back().ext_bits = true;  // the lane owns whole pairs: their single-word draws come from the pairs' blocks
+      em.back().row_cuts = true;
       em.back().sc = sc;
     }
     for (int u = 0; u < P; ++u) em[u].emit_scope_keys();
     o << "      const uint64_t pair0 = (lnA - 1u) >> 1;\n";
     if (NP == 2) o << "      const uint64_t pair1 = pair0 + 1u;\n";
-    emit_pair_lane_sites<CSiteT, CArgT>(o, em, sites, n_sites, NP, "      ", "po + iA", "score", ubase ? "ub" : "", "lb");
+    emit_pair_lane_sites<CSiteT, CArgT>(o, em, sites, n_sites, NP, "      ", "po + iA", "score", ubase ? "ub" : "", "lb", full);
     if (ubase) {
       std::string wb, sb;
       for (int u = 0; u < P; ++u) { wb += (u ? ", f2u(w" : "f2u(w") + std::string(sfx[u]) + ")"; sb += (u ? ", f2u(sc" : "f2u(sc") + std::string(sfx[u]) + ")"; }
-      o << "      if (logw) store16_at(logw + ub, lb, make_uint4(" << wb << "), wt_one_pass);\n";
-      o << "      if (score) store16_at(score + ub, lb, make_uint4(" << sb << "), wt_one_pass);\n";
+      o << "      " << (full ? "" : "if (logw) ") << "store16_at(logw + ub, lb, make_uint4(" << wb << "), wt_one_pass);\n";
+      o << "      " << (full ? "" : "if (score) ") << "store16_at(score + ub, lb, make_uint4(" << sb << "), wt_one_pass);\n";
     } else if (P == 4) {
       std::string wb, sb;
       for (int u = 0; u < P; ++u) { wb += (u ? ", f2u(w" : "f2u(w") + std::string(sfx[u]) + ")"; sb += (u ? ", f2u(sc" : "f2u(sc") + std::string(sfx[u]) + ")"; }
@@ -821,12 +863,13 @@ struct Gen {
       o << "      if (score) *reinterpret_cast<float" << P << "*>(score + po + iA) = make_float" << P << "(" << ss << ");\n";
     }
     o << "    }\n";
-    o << "    if (max_partials || row_e) {\n";
+    o << "    " << (full ? "" : "if (max_partials || row_e) ") << "{\n";
     o << "      const float ninf = -__builtin_inff();\n";
     {
       std::string mx = "wA";
       for (int u = 1; u < P; ++u) mx = "(" + mx + " > w" + sfx[u] + " ? " + mx + " : w" + sfx[u] + ")";
-      o << "      float bm = wave_max(ok ? " << mx << " : ninf);\n";
+      // (one wave per row: the maximum on integer keys — a generated kernel's log-weights are never -0, gjx_device.hpp)
+      o << "      float bm = " << (waves_per_row == 1 ? "wave_max_ordered" : "wave_max") << "(ok ? " << mx << " : ninf);\n";
     }
     if (waves_per_row > 1) {
       o << "      __syncthreads();\n      if ((threadIdx.x & 63) == 0) sh_red[wv] = bm;\n      __syncthreads();\n";
@@ -837,8 +880,8 @@ struct Gen {
     // (v_bitop3_b32 reads them in place, gjx_device.hpp xor3) the allocator spilled that pair to a 65th VGPR — one more than
     // eight waves per SIMD allow.  One v_cmp per row instead.
     const char* lane0 = ubase ? "lb == 0u" : "tr == 0";
-    o << "      if (max_partials && " << lane0 << " && live_row) max_partials[rrow] = bm;\n";
-    o << "      if (row_e) {\n";
+    o << "      if (" << (full ? "" : "max_partials && ") << lane0 << " && live_row) max_partials[rrow] = bm;\n";
+    o << "      " << (full ? "" : "if (row_e) ") << "{\n";
     o << "        const int32_t eb = row_anchor(bm);\n";
     {
       std::string sm;
@@ -964,6 +1007,7 @@ struct GenScan {
       em.push_back(SiteEmitter<CSiteT, CArgT>{o, impl, 2, sites, n_sites, "        ", sfx[u]});
       em.back().store_values = false;
       em.back().ext_bits = true;
+      em.back().row_cuts = true;
       em.back().sc = sc;
     }
     for (int u = 0; u < P; ++u) em[u].emit_scope_keys();
@@ -983,7 +1027,7 @@ struct GenScan {
     o << "    if (max_partials || row_e) {\n";
     o << "      const float ninf = -__builtin_inff();\n";
     o << "      const float m4 = ((wtA > wtB ? wtA : wtB) > wtC ? (wtA > wtB ? wtA : wtB) : wtC);\n";
-    o << "      const float bm = wave_max(ok ? (m4 > wtD ? m4 : wtD) : ninf);\n";
+    o << "      const float bm = wave_max_ordered(ok ? (m4 > wtD ? m4 : wtD) : ninf);  // (wt starts at +0: never -0)\n";
     o << "      if (max_partials && threadIdx.x == 0) max_partials[row] = bm;\n";
     o << "      if (row_e) {\n";
     o << "        const int32_t eb = row_anchor(bm);\n";

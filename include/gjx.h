@@ -287,9 +287,15 @@ int gjx_plan_set_params(gjx_plan* p, const float* params /*host*/, int n_params)
  * variant; `impl | GJX_SOURCE_FUSED_TAIL` asks for the other.
  * The kind of store is a variant too, of the four-particles-per-lane form: plain stores by default (launches of
  * several passes: the write-back overlaps the following passes), write-through stores for a launch of ONE pass (built
- * on the first such launch, or by gjx_plan_prepare).  `impl | GJX_SOURCE_WT_STORES` asks for the write-through variant; the flags combine. */
+ * on the first such launch, or by gjx_plan_prepare).  `impl | GJX_SOURCE_WT_STORES` asks for the write-through variant; the flags combine.
+ * So is the set of outputs, of the same form where it runs one row per workgroup: a launch that passes score, logw,
+ * max_partials, row_e and row_s and no gjx_lse_out runs a variant whose source knows all five to be non-null and asks
+ * nothing about them (built on the first such launch, or by gjx_plan_prepare); every other set of outputs runs the
+ * guarded source, which is what the diagnostics show without the flag.  `impl | GJX_SOURCE_FULL_OUTPUTS` asks for the
+ * variant; it combines with GJX_SOURCE_WT_STORES, and the other forms ignore it.  Same results either way. */
 #define GJX_SOURCE_FUSED_TAIL 0x100
 #define GJX_SOURCE_WT_STORES 0x200
+#define GJX_SOURCE_FULL_OUTPUTS 0x400
 int gjx_plan_specialized_source(const gjx_plan* p, int impl, char* buf, size_t buf_len, size_t* needed);
 /* Build (hiprtc) and load now the kernel gjx_importance_run would build on its first launch with
  * this key form, so that no launch pays the ~0.2 s compilation.  Optional; the oracle build returns
