@@ -2138,15 +2138,10 @@ struct gjx_plan {
   PlanParams prm;
   CSite host[GJX_MAX_SITES];
   CSite* dev;
-  // specialised kernels, built on first use: [0] THREEFRY, [1] PHILOX one particle per lane, [2] PHILOX pairs
-  // (two adjacent particles per lane), [3] PHILOX quads (four per lane: one wave per 256-particle row)
-  gjx_jit::Compiled jit[4];
-  gjx_jit::Compiled jit_tail[4];  // the same forms WITH the fused fold (gjx_jit::Gen::fused_tail): built on the first launch
-                                  // that passes a gjx_lse_out, so the default launches do not carry the fold's registers
-  gjx_jit::Compiled jit_wt[2];  // the quad form with WRITE-THROUGH stores (gjx_jit::Gen::wt_stores), [1] with the fused fold:
-                                // built on the first launch of a single pass (the other forms have one kind of store)
-  gjx_jit::Compiled jit_full[2];  // the quad form of a launch that passes EVERY output (gjx_jit::Gen::full_outputs), [1] with
-                                  // write-through stores: built on the first such launch, or by gjx_plan_prepare
+  // specialised kernels, one per variant a launch can take (gjx_jit::ImportanceVariant::slot), each built on the first launch
+  // that takes it or by gjx_plan_prepare: the default launches do not carry the fused fold's registers, and only the quad
+  // form has two kinds of store and a source that knows every output to be passed
+  gjx_jit::Compiled jit[gjx_jit::ImportanceVariant::kSlots];
   std::vector<void*> dev_owned;  // per-row tables of categorical sites (specialised kernels)
   std::mutex jit_mu;
   ExprStore expr;      // GJX_ARG_EXPR programs (host; read by the code generator)
@@ -2422,37 +2417,42 @@ static int jit_form_pref() {  // GJX_JIT_FORM = one | pair | quad (test / tuning
 //    GJX_JIT_DEFINE=GJX_WAVES_HINT=<k>).
 // A hinted build that spills more than 32 B is replaced by the unhinted one (plan_compiled).
 static int jit_waves_hint(int P) { return P == 2 ? 6 : 0; }
-// The importance generator of a plan.  `form`: particles per lane, 1, 2 (pairs) or 4 (quads); above 1 is PHILOX only.
-static void plan_gen_setup(gjx_jit::Gen<CSite, CArg>& g, const gjx_plan* p, int impl, int form, bool fused_tail, bool wt_stores, int min_waves,
-                           bool full_outputs = false) {
-  g.impl = impl; g.sites = p->host; g.n_sites = p->n_sites; g.laned = form >= 2; g.pairs_per_lane = form == 4 ? 2 : 1;
+// How many adjacent particles a lane of a launch may own: 4, 2 or 1.  PHILOX children of a lane-0 key share one cipher key,
+// and an even first index keeps particle pairs (2i, 2i+1) together: the paired / quad kernel forms (gjx_plan_jit.hpp).  Those
+// write the 2 / 4 particles of a lane with one 8- / 16-byte store: `al` is the OR of every address such a store goes to and of
+// every byte distance it is repeated at, 4 n among them (n a multiple of 2 / 4).
+static int lane_particles(const gjx_keys* pk, uintptr_t al) {
+  if (pk->impl != 1 || pk->mode != 1 || pk->parent_lane != 0 || (pk->first & 1) != 0) return 1;
+  return (al & 15) == 0 ? 4 : ((al & 7) == 0 ? 2 : 1);
+}
+// The fold's outputs as the generated kernels take them (null: the empty tail)
+static LseTail lse_tail_of(const gjx_lse_out* lse) {
+  if (!lse) return LseTail{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0f};
+  return LseTail{lse->e, lse->q, lse->lse, lse->record, lse->tickets, lse->lse_shifted, lse->shift};
+}
+// The importance generator of a plan for one variant.
+static void plan_gen_setup(gjx_jit::Gen<CSite, CArg>& g, const gjx_plan* p, const gjx_jit::ImportanceVariant& v, int min_waves) {
+  g.v = v; g.sites = p->host; g.n_sites = p->n_sites;
   g.sc = p->scopes.n_scopes > 0 ? &p->scopes : nullptr;
   g.fast_math = (p->flags & GJX_PLAN_FAST_MATH) != 0;
-  g.fused_tail = fused_tail;
-  g.wt_stores = wt_stores;
-  g.full_outputs = full_outputs;
   g.min_waves = min_waves;
 }
 int gjx_plan_specialized_source(const gjx_plan* p, int impl, char* buf, size_t buf_len, size_t* needed) {
-  const bool fused_tail = (impl & GJX_SOURCE_FUSED_TAIL) != 0, wt_stores = (impl & GJX_SOURCE_WT_STORES) != 0;
-  const bool full_outputs = (impl & GJX_SOURCE_FULL_OUTPUTS) != 0;
-  impl &= ~(GJX_SOURCE_FUSED_TAIL | GJX_SOURCE_WT_STORES | GJX_SOURCE_FULL_OUTPUTS);
-  if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
-  const int form = impl == 1 ? jit_form_pref() : 1;  // (GJX_JIT_FORM picks the PHILOX form shown)
+  const gjx_jit::ImportanceVariant v = gjx_jit::ImportanceVariant::of_source(impl, jit_form_pref());  // (GJX_JIT_FORM picks the PHILOX form shown)
+  if (!p || (v.impl != 0 && v.impl != 1)) return GJX_ERR_INVALID;
   gjx_jit::Gen<CSite, CArg> g;
-  plan_gen_setup(g, p, impl, form, fused_tail, wt_stores, jit_waves_hint(form), full_outputs);  // the kernel that ships
+  plan_gen_setup(g, p, v, jit_waves_hint(v.lane_particles));  // the kernel that ships
   gjx_jit::TableScope ts;
   return copy_source_out(g.run(), buf, buf_len, needed);
 }
 
 int gjx_plan_compile_check(const gjx_plan* p, int impl) {
-  const bool fused_tail = (impl & GJX_SOURCE_FUSED_TAIL) != 0, wt_stores = (impl & GJX_SOURCE_WT_STORES) != 0;
-  const bool full_outputs = (impl & GJX_SOURCE_FULL_OUTPUTS) != 0;
-  impl &= ~(GJX_SOURCE_FUSED_TAIL | GJX_SOURCE_WT_STORES | GJX_SOURCE_FULL_OUTPUTS);
-  if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
-  for (int form = 1; form <= (impl == 1 ? 4 : 1); form *= 2) {  // PHILOX: one particle per lane, pairs, quads
+  const int gen = gjx_jit::ImportanceVariant::of_source(impl, 1).impl;
+  if (!p || (gen != 0 && gen != 1)) return GJX_ERR_INVALID;
+  for (int form = 1; form <= (gen == 1 ? 4 : 1); form *= 2) {  // PHILOX: one particle per lane, pairs, quads
     gjx_jit::Gen<CSite, CArg> g;
-    plan_gen_setup(g, p, impl, form, fused_tail, wt_stores && form == 4, jit_waves_hint(form), full_outputs && form == 4);
+    // (the pair form is compiled as a launch runs it, plain stores: only gjx_plan_specialized_source shows its text under the write-through flag)
+    plan_gen_setup(g, p, gjx_jit::ImportanceVariant::of_source(form == 4 ? impl : impl & ~GJX_SOURCE_WT_STORES, form), jit_waves_hint(form));
     gjx_jit::TableScope ts;
     if (!gjx_jit::compile_only(g.run(), gjx_jit::PlanKind::importance)) return GJX_ERR_UNSUPPORTED;
   }
@@ -2462,53 +2462,35 @@ int gjx_plan_destroy(gjx_plan* p) {
   if (!p) return GJX_OK;
   if (p->dev) (void)hipFree(p->dev);
   for (auto& c : p->jit) c.release();  // the modules stay cached (bounded, LRU) for plans of the same structure
-  for (auto& c : p->jit_tail) c.release();
-  for (auto& c : p->jit_wt) c.release();
-  for (auto& c : p->jit_full) c.release();
   free_owned(p->dev_owned);
   delete p;
   return GJX_OK;
 }
 
-// The hiprtc-specialised kernel of a plan for this key form (compiled and loaded on first use).
-// `lane_particles`: how many adjacent particles a lane may own given n and the alignment of the output buffers (1, 2, 4).
-// `fused_tail`: the variant that folds the row sums inside the launch (launches that pass a gjx_lse_out).
-// `one_pass`: a launch of a single pass; the quad form then stores write-through (gjx_jit::Gen::wt_stores).
-// `all_outputs`: the launch passes score, logw, max_partials, row_e and row_s and no gjx_lse_out; the quad form then runs the
-// variant that asks nothing about them (gjx_jit::Gen::full_outputs).
-static gjx_jit::Compiled& plan_compiled(gjx_plan* mp, const gjx_keys* pk, int lane_particles, bool fused_tail = false, bool one_pass = false,
-                                        bool all_outputs = false) {
-  // PHILOX children of a lane-0 key share one cipher key, and an even first index keeps particle pairs
-  // (2i, 2i+1) together: the paired / quad kernel forms (gjx_plan_jit.hpp)
-  const bool pairable = pk->impl == 1 && pk->mode == 1 && pk->parent_lane == 0 && (pk->first & 1) == 0;
-  int P = pairable ? (lane_particles < jit_form_pref() ? lane_particles : jit_form_pref()) : 1;
-  if (P == 3) P = 2;
-  const bool laned = P >= 2;
-  const bool wt_stores = one_pass && P == 4;
-  const bool full_outputs = all_outputs && !fused_tail && P == 4;
-  gjx_jit::Compiled& c = full_outputs ? mp->jit_full[wt_stores ? 1 : 0]
-                         : wt_stores  ? mp->jit_wt[fused_tail ? 1 : 0]
-                                      : (fused_tail ? mp->jit_tail : mp->jit)[P == 4 ? 3 : (laned ? 2 : pk->impl)];
+// The hiprtc-specialised kernel of a plan for one variant (compiled and loaded on first use).
+static gjx_jit::Compiled& plan_compiled(gjx_plan* mp, const gjx_jit::ImportanceVariant& v) {
+  gjx_jit::Compiled& c = mp->jit[v.slot()];
   compiled_once(mp->jit_mu, c, {{mp->host, mp->n_sites}}, &mp->dev_owned, [&] {
+    const int P = v.lane_particles;
     auto build = [&](int min_waves) {
       gjx_jit::Gen<CSite, CArg> g;
-      plan_gen_setup(g, mp, pk->impl, P, fused_tail, wt_stores, min_waves, full_outputs);
+      plan_gen_setup(g, mp, v, min_waves);
       gjx_jit::TableScope ts;  // the source numbers the plan's device tables; the addresses travel as a kernel argument
       const std::string src = g.run();
       c.block = g.block;
       c.rows_per_block = g.rows_per_block;
       c.tabs = ts.reg.tables();
-      return c.load(src, gjx_jit::PlanKind::importance, {g.kname()}, {&c.fn});
+      return c.load(src, gjx_jit::PlanKind::importance, {v.kname()}, {&c.fn});
     };
     // (jit_waves_hint has the register counts and the waves per SIMD that follow from them.)  The hint is kept as long
     // as the allocator gets there with (next to) no spilling; otherwise the unconstrained build is used.
-    const int hint = laned ? jit_waves_hint(P) : 0;
+    const int hint = jit_waves_hint(P);
     bool ok = build(hint);
     if (ok && std::getenv("GJX_PLAN_JIT_VERBOSE")) {  // what the loaded code object allocates (the VGPR column of a rocprofv3 kernel trace is HALF of this)
       int regs = 0;
       if (hipFuncGetAttribute(&regs, HIP_FUNC_ATTRIBUTE_NUM_REGS, c.fn) != hipSuccess) (void)hipGetLastError();
-      fprintf(stderr, "gjx jit: %d particle(s) per lane%s%s%s: %d registers per lane\n", P, fused_tail ? ", fused tail" : "", wt_stores ? ", write-through stores" : "",
-              full_outputs ? ", every output" : "", regs);
+      fprintf(stderr, "gjx jit: %d particle(s) per lane%s%s%s: %d registers per lane\n", P, v.fused_tail ? ", fused tail" : "", v.wt_stores ? ", write-through stores" : "",
+              v.full_outputs ? ", every output" : "", regs);
     }
     if (ok && hint > 0) {
       int scratch = 0;
@@ -2523,7 +2505,7 @@ static gjx_jit::Compiled& plan_compiled(gjx_plan* mp, const gjx_keys* pk, int la
       (void)hipGetLastError();
       fprintf(stderr, "[gjx] plan specialisation FAILED (hiprtc compile or module load; impl %d, %d particle(s) per lane). "
                       "gjx_importance_run returns GJX_ERR_JIT; set GJX_PLAN_JIT_VERBOSE=1 for the compiler log, GJX_PLAN_JIT=0 "
-                      "or GJX_PLAN_JIT_FALLBACK=1 to run the (7x slower) table interpreter instead.\n", pk->impl, P);
+                      "or GJX_PLAN_JIT_FALLBACK=1 to run the (7x slower) table interpreter instead.\n", v.impl, P);
     }
     return ok;
   });
@@ -2539,13 +2521,15 @@ static bool jit_fallback_allowed() {
 int gjx_plan_prepare(gjx_plan* p, const gjx_keys* pk) {
   if (!p || !keys_ok(pk)) return GJX_ERR_INVALID;
   if (!gjx_jit::enabled()) return p->has_expr ? GJX_ERR_UNSUPPORTED : plan_device_table(p);
-  // every form a launch may take (which one depends on n and on buffer alignment)
-  bool ok = plan_compiled(p, pk, 1).state == 1;
-  ok = plan_compiled(p, pk, 2).state == 1 && ok;
-  ok = plan_compiled(p, pk, 4).state == 1 && ok;
-  ok = plan_compiled(p, pk, 4, false, true).state == 1 && ok;  // (a single-pass launch: the quad form's other kind of store)
-  ok = plan_compiled(p, pk, 4, false, false, true).state == 1 && ok;  // (a launch with every output: the quad form that asks nothing)
-  ok = plan_compiled(p, pk, 4, false, true, true).state == 1 && ok;
+  // every variant a launch with these keys may take, named by a launch that leads to it: the particles per lane that n and
+  // the buffer alignment allow, then a single pass (the quad form's other kind of store) and every output passed (the quad
+  // form that asks nothing)
+  static const struct { int lane_particles; bool one_pass, every_output; } kLaunches[] = {
+      {1, false, false}, {2, false, false}, {4, false, false}, {4, true, false}, {4, false, true}, {4, true, true}};
+  const int most = lane_particles(pk, 0), pref = most > 1 ? jit_form_pref() : 1;
+  bool ok = true;
+  for (const auto& l : kLaunches)
+    ok = plan_compiled(p, gjx_jit::ImportanceVariant::of_launch(pk->impl, l.lane_particles < most ? l.lane_particles : most, pref, false, l.one_pass, l.every_output)).state == 1 && ok;
   if (ok) return GJX_OK;
   return jit_fallback_allowed() && !p->has_expr ? plan_device_table(p) : GJX_ERR_JIT;
 }
@@ -2599,14 +2583,15 @@ static int importance_launch(const gjx_plan* p, const gjx_keys* pk, int32_t n_pa
     // of 2 / 4, columns (and the distance between passes) aligned alike
     uintptr_t al = (uintptr_t)logw | (uintptr_t)score | (uintptr_t)(4 * pass_stride) | (uintptr_t)(4 * n);
     for (int c = 0; c < n_value_cols; ++c) al |= (uintptr_t)value_cols[c];
-    const int lane_particles = (al & 15) == 0 ? 4 : ((al & 7) == 0 ? 2 : 1);
-    const bool all_outputs = score && logw && max_partials && row_e && row_s && !lse;
-    gjx_jit::Compiled& c = plan_compiled(const_cast<gjx_plan*>(p), pk, lane_particles, lse != nullptr, n_pass <= 1, all_outputs);
+    const bool every_output = score && logw && max_partials && row_e && row_s;
+    // (GJX_JIT_FORM is asked only where there is a choice: a launch whose keys or buffers allow one particle per lane reads no environment)
+    const int allowed = lane_particles(pk, al);
+    const auto v = gjx_jit::ImportanceVariant::of_launch(pk->impl, allowed, allowed > 1 ? jit_form_pref() : 1, lse != nullptr, n_pass <= 1, every_output);
+    gjx_jit::Compiled& c = plan_compiled(const_cast<gjx_plan*>(p), v);
     if (c.state != 1 && (!jit_fallback_allowed() || p->has_expr || p->scopes.n_scopes > 0)) return GJX_ERR_JIT;  // loud: never a silent 7x slower route
     if (c.state == 1) {
       uint64_t nn = n;
-      LseTail tail{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0f};
-      if (lse) tail = LseTail{lse->e, lse->q, lse->lse, lse->record, lse->tickets, lse->lse_shifted, lse->shift};
+      LseTail tail = lse_tail_of(lse);
       PassBatch bt;
       memset(&bt, 0, sizeof bt);
       bt.n_pass = (uint32_t)n_pass;
@@ -3349,8 +3334,7 @@ struct gjx_scan_plan {
   uint32_t flags;
   CSite step[GJX_MAX_SITES];
   CArg next_state[GJX_SMC_MAX_STATE];
-  gjx_jit::Compiled jit[3];  // THREEFRY, PHILOX one particle per lane, PHILOX four per lane (GenScan::quad)
-  gjx_jit::Compiled jit_tail[3];  // the same with the fused fold (GenScan::fused_tail): launches that pass a gjx_lse_out
+  gjx_jit::Compiled jit[gjx_jit::ScanVariant::kSlots];  // one per variant (gjx_jit::ScanVariant::slot), built on the first launch that takes it
   gjx_jit::ScopeInfo scopes;  // nested calls inside the step kernel (gjx_scan_plan_create_scoped)
   std::vector<void*> dev_owned;  // per-row tables of categorical sites
   std::mutex mu;
@@ -3394,31 +3378,28 @@ int gjx_scan_plan_create_scoped(const gjx_scan_model* m, const gjx_scope* scopes
 int gjx_scan_plan_destroy(gjx_scan_plan* p) {
   if (!p) return GJX_OK;
   for (auto& c : p->jit) c.release();
-  for (auto& c : p->jit_tail) c.release();
   free_owned(p->dev_owned);
   delete p;
   return GJX_OK;
 }
-static std::string scan_plan_source(const gjx_scan_plan* plan, int impl, const char** kname = nullptr, PlanTables* tabs = nullptr,
-                                    bool quad = false, int* block = nullptr, bool fused_tail = false) {
+// The source of one variant of a scan plan's kernel; `c` (nullable) takes what a launch of it needs: the plan's device tables
+// as the source numbers them, and the workgroup size.
+static std::string scan_plan_source(const gjx_scan_plan* plan, const gjx_jit::ScanVariant& v, gjx_jit::Compiled* c = nullptr) {
   gjx_jit::GenScan<CSite, CArg> g;
-  g.impl = impl; g.sites = plan->step; g.n_sites = plan->n_step; g.next_state = plan->next_state;
+  g.v = v; g.sites = plan->step; g.n_sites = plan->n_step; g.next_state = plan->next_state;
   g.n_state = plan->n_state; g.n_obs = plan->n_obs; g.fast_math = (plan->flags & GJX_PLAN_FAST_MATH) != 0;
-  g.quad = quad;
-  g.fused_tail = fused_tail;
   g.sc = plan->scopes.n_scopes > 0 ? &plan->scopes : nullptr;
-  if (kname) *kname = g.kname();
-  std::string src = gjx_jit::generated_source(g, tabs);
-  if (block) *block = g.block;
+  std::string src = gjx_jit::generated_source(g, c ? &c->tabs : nullptr);
+  if (c) c->block = g.block;
   return src;
 }
 int gjx_scan_plan_compile_check(const gjx_scan_plan* p, int impl) {
-  const bool ft = (impl & GJX_SOURCE_FUSED_TAIL) != 0;  // (the variant with the in-launch fold, as gjx_plan_compile_check)
-  impl &= ~GJX_SOURCE_FUSED_TAIL;
-  if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
-  if (std::getenv("GJX_PLAN_JIT_DUMP")) fprintf(stderr, "%s\n", scan_plan_source(p, impl, nullptr, nullptr, false, nullptr, ft).c_str());
-  if (impl == 1 && !gjx_jit::compile_only(scan_plan_source(p, impl, nullptr, nullptr, true, nullptr, ft), gjx_jit::PlanKind::scan)) return GJX_ERR_UNSUPPORTED;
-  return gjx_jit::compile_only(scan_plan_source(p, impl, nullptr, nullptr, false, nullptr, ft), gjx_jit::PlanKind::scan) ? GJX_OK : GJX_ERR_UNSUPPORTED;
+  // (impl | GJX_SOURCE_FUSED_TAIL: the variant with the in-launch fold, as gjx_plan_compile_check)
+  const gjx_jit::ScanVariant one = gjx_jit::ScanVariant::of(impl, false), quad = gjx_jit::ScanVariant::of(impl, true);
+  if (!p || (one.impl != 0 && one.impl != 1)) return GJX_ERR_INVALID;
+  if (std::getenv("GJX_PLAN_JIT_DUMP")) fprintf(stderr, "%s\n", scan_plan_source(p, one).c_str());
+  if (quad.quad && !gjx_jit::compile_only(scan_plan_source(p, quad), gjx_jit::PlanKind::scan)) return GJX_ERR_UNSUPPORTED;
+  return gjx_jit::compile_only(scan_plan_source(p, one), gjx_jit::PlanKind::scan) ? GJX_OK : GJX_ERR_UNSUPPORTED;
 }
 int gjx_scan_run(gjx_scan_plan* p, const gjx_scan_io* io, gjx_stream s) {
   if (!p || !io || !keys_ok(io->particle_keys) || io->particle_keys->has_fold || !io->logw || io->n_steps < 1 ||
@@ -3443,21 +3424,16 @@ int gjx_scan_run(gjx_scan_plan* p, const gjx_scan_io* io, gjx_stream s) {
   if (!gjx_jit::enabled()) return GJX_ERR_UNSUPPORTED;
   // PHILOX children of a lane-0 key from an even first index, n and every column a multiple of four elements: the quad form
   // (four adjacent particles per lane share two pair blocks and two Box-Muller transforms per site and step)
-  bool quad = false;
-  {
-    const gjx_keys* pk = io->particle_keys;
-    uintptr_t al = (uintptr_t)io->logw | (uintptr_t)io->score | (uintptr_t)(4 * io->col_stride) | (uintptr_t)(4 * io->n);
-    for (int c = 0; c < io->n_value_cols; ++c) al |= (uintptr_t)io->value_cols[c];
-    for (int d = 0; d < p->n_state; ++d) al |= io->carry_out ? (uintptr_t)io->carry_out[d] : 0;
-    quad = impl == 1 && pk->mode == 1 && pk->parent_lane == 0 && (pk->first & 1) == 0 && (al & 15) == 0;
-  }
-  const bool fused_tail = io->lse != nullptr;  // the in-launch fold: a variant of its own, built when first asked for
-  gjx_jit::Compiled& c = (fused_tail ? p->jit_tail : p->jit)[quad ? 2 : impl];
+  uintptr_t al = (uintptr_t)io->logw | (uintptr_t)io->score | (uintptr_t)(4 * io->col_stride) | (uintptr_t)(4 * io->n);
+  for (int c = 0; c < io->n_value_cols; ++c) al |= (uintptr_t)io->value_cols[c];
+  for (int d = 0; d < p->n_state; ++d) al |= io->carry_out ? (uintptr_t)io->carry_out[d] : 0;
+  // (the in-launch fold is a variant of its own, built when a launch first passes a gjx_lse_out)
+  const gjx_jit::ScanVariant v = gjx_jit::ScanVariant::of(impl | (io->lse ? GJX_SOURCE_FUSED_TAIL : 0), lane_particles(io->particle_keys, al) == 4);
+  gjx_jit::Compiled& c = p->jit[v.slot()];
   const bool ready = compiled_once(p->mu, c, {{p->step, p->n_step}}, &p->dev_owned, [&] {
-    const char* kname = nullptr;
-    const std::string src = scan_plan_source(p, impl, &kname, &c.tabs, quad, &c.block, fused_tail);
+    const std::string src = scan_plan_source(p, v, &c);
     if (std::getenv("GJX_PLAN_JIT_DUMP")) fprintf(stderr, "%s\n", src.c_str());
-    return c.load(src, gjx_jit::PlanKind::scan, {kname}, {&c.fn});
+    return c.load(src, gjx_jit::PlanKind::scan, {v.kname()}, {&c.fn});
   });
   if (!ready) return GJX_ERR_JIT;
   KeySrc k = key_src(io->particle_keys);
@@ -3469,8 +3445,7 @@ int gjx_scan_run(gjx_scan_plan* p, const gjx_scan_io* io, gjx_stream s) {
     sa.carry0_cols[d] = io->carry0_cols ? io->carry0_cols[d] : nullptr;
     sa.carry_out[d] = io->carry_out ? io->carry_out[d] : nullptr;
   }
-  LseTail tail{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0f};
-  if (io->lse) tail = LseTail{io->lse->e, io->lse->q, io->lse->lse, io->lse->record, io->lse->tickets, io->lse->lse_shifted, io->lse->shift};
+  LseTail tail = lse_tail_of(io->lse);
   float* score = io->score; float* logw = io->logw; float* mp = io->max_partials;
   int32_t* row_e = io->row_e; uint64_t* row_s = io->row_s;
   PlanTables tabs = c.tabs;

@@ -295,6 +295,13 @@ struct SiteEmitter {
   // SMC steps keep the single-draw inverse-CDF form (one latent per slot-step: a pair would cost two blocks).
   // Scan steps (mode 2) are importance walks under the step's chained key: same draws as mode 0.
   bool pairs_normals() const { return impl == 1 && mode != 1; }
+  // does the postfix program of `a` (a GJX_ARG_EXPR argument) read nothing but literals?
+  static bool literal_program(const CArgT& a) {
+    const gjx_expr_op* ops = reinterpret_cast<const gjx_expr_op*>(a.table);
+    for (int k = 0; k < a.ref; ++k)
+      if ((ops[k].op >= GJX_EXPR_SITE && ops[k].op <= GJX_EXPR_OBS) || ops[k].op == GJX_EXPR_DATA) return false;
+    return true;
+  }
 
   // Part 1 of site q: arguments, the observed value, or the draw word(s).
   void head(int q) {
@@ -316,11 +323,11 @@ struct SiteEmitter {
       auto carg = [&](const CArgT& a, int which) {
         float v = a.offset;
         if (a.kind == GJX_ARG_EXPR) {  // a program over literals only is a constant too: its value, by the program's own steps
+          if (!literal_program(a)) return arg(a);  // (not a constant)
           const gjx_expr_op* ops = reinterpret_cast<const gjx_expr_op*>(a.table);
           float stk[8];
           int d = 0;
           for (int k = 0; k < a.ref; ++k) {
-            if ((ops[k].op >= GJX_EXPR_SITE && ops[k].op <= GJX_EXPR_OBS) || ops[k].op == GJX_EXPR_DATA) return arg(a);  // (not a constant)
             if (ops[k].op == GJX_EXPR_CONST) { stk[d++] = ops[k].value; continue; }
             if (ops[k].op == GJX_EXPR_NEG) { stk[d - 1] = -stk[d - 1]; continue; }
             if (ops[k].op == GJX_EXPR_EXP) { stk[d - 1] = gjx::e_exp(stk[d - 1]); continue; }
@@ -516,12 +523,7 @@ struct SiteEmitter {
     // an observed site whose arguments and value are ALL compile-time constants has a compile-time log-density: opaque, so
     // that no overflow of valid constants (-inf, +inf) becomes a constant log-weight either
     auto is_const = [](const CArgT& a) {  // a literal, or a program over literals only
-      if (a.kind == GJX_ARG_CONST) return true;
-      if (a.kind != GJX_ARG_EXPR) return false;
-      const gjx_expr_op* ops = reinterpret_cast<const gjx_expr_op*>(a.table);
-      for (int k = 0; k < a.ref; ++k)
-        if ((ops[k].op >= GJX_EXPR_SITE && ops[k].op <= GJX_EXPR_OBS) || ops[k].op == GJX_EXPR_DATA) return false;
-      return true;
+      return a.kind == GJX_ARG_CONST || (a.kind == GJX_ARG_EXPR && literal_program(a));
     };
     const bool all_const = st.observed == 1 && st.obs.kind == GJX_ARG_CONST && is_const(st.a0) &&
                            (st.dist == GJX_DIST_BERNOULLI || st.dist == GJX_DIST_CATEGORICAL || is_const(st.a1));
@@ -557,6 +559,67 @@ inline void emit_prelude(std::ostringstream& o, bool fast_math = false, bool bm_
   if (fast_math) o << "#define GJX_FAST_MATH 1\n";  // gjx.h GJX_PLAN_FAST_MATH: hardware transcendentals (gjx_device.hpp d_exp / bm_pair)
   o << "#include \"gjx_device.hpp\"\nusing namespace gjx;\n";
 }
+// PHILOX Normal sites draw through the Box-Muller tables: the importance and scan kernels of such a source stage them in LDS
+// (gjx_device.hpp bm_stage)
+template <class CSiteT>
+inline bool bm_lds(int impl, bool fast_math, const CSiteT* sites, int n_sites) {
+  if (impl != 1 || fast_math) return false;
+  for (int q = 0; q < n_sites; ++q)
+    if (!sites[q].observed && sites[q].dist == GJX_DIST_NORMAL) return true;
+  return false;
+}
+
+// The 2 or 4 particles a lane owns (suffixes A, B [, C, D]): one SiteEmitter each, and the lists a generated source spells out
+// particle by particle.  The lane owns whole pairs / quads, so the single-word draws of its own scope come from cipher blocks
+// the group shares (ext_bits); whatever else differs from an emitter's defaults is set through each(), once for all particles.
+template <class CSiteT, class CArgT>
+struct LaneGroup {
+  using Emitter = SiteEmitter<CSiteT, CArgT>;
+  static constexpr const char* kSfx[4] = {"A", "B", "C", "D"};
+  std::vector<Emitter> em;
+  LaneGroup(std::ostringstream& o, int P, int impl, int mode, const CSiteT* sites, int n_sites, const char* ind) {
+    for (int u = 0; u < P; ++u) { em.push_back(Emitter{o, impl, mode, sites, n_sites, ind, kSfx[u]}); em.back().ext_bits = true; }
+  }
+  int size() const { return (int)em.size(); }
+  // f(u, the emitter of particle u), in particle order
+  template <class F> void each(F f) { for (int u = 0; u < size(); ++u) f(u, em[u]); }
+  // expr(the emitter of a particle) -> a string; those of all particles, comma-separated
+  template <class F> std::string join(F expr) const {
+    std::string t;
+    for (int u = 0; u < size(); ++u) t += (u ? ", " : "") + std::string(expr(em[u]));
+    return t;
+  }
+  std::string list(const std::string& pre, const std::string& post = "") const {  // pre<suffix>post of every particle
+    return join([&](const Emitter& e) { return pre + e.sfx + post; });
+  }
+};
+
+// The row sums of a kernel without the fused fold are read by a later launch: plain stores (lse_store_row's last argument).
+inline const char* tail_scope(bool fused_tail) { return fused_tail ? "tail.tickets != nullptr" : "false"; }
+// The closing braces of the row loop and of the kernel and, in the fused-tail variant, the in-launch fold of the row sums
+// between them (gjx_device.hpp lse_tail).  `ticket`: the workgroup's ticket and the count of all tickets, as lse_tail takes them.
+inline void emit_kernel_close(std::ostringstream& o, bool fused_tail, const char* ticket) {
+  o << "  }\n";
+  if (fused_tail) o << "  if (row_e) lse_tail(row_e, row_s, (n + 255) / 256, tail, " << ticket << ");\n";
+  o << "}\n";
+}
+// The end of a row and of the kernel where a lane owns ONE particle (the importance and scan kernels of that form): the row's
+// maximum and its row-anchored sum by four waves through LDS (block_max / block_sum over `tmax`, -inf in a lane that is not
+// `live`), written by thread 0 at index `row`.  The forms in which a lane owns 2 or 4 particles reduce by waves and keep their
+// own statistics (Gen::run_paired, GenScan::run_quad): nothing but the close is common to them — they differ in the
+// reduction, the writer lane, the known outputs and, between the two quad forms, in how the lane's maximum is taken, which
+// the compiler turns into different machine code.
+inline void emit_row_epilogue_per_lane(std::ostringstream& o, const char* row, bool fused_tail, const char* ticket) {
+  o << "    if (max_partials || row_e) {\n";
+  o << "      const float bm = block_max(tmax, sh_red);\n";
+  o << "      if (max_partials && threadIdx.x == 0) max_partials[" << row << "] = bm;\n";
+  o << "      if (row_e) {\n";
+  o << "        const int32_t eb = row_anchor(bm);\n";
+  o << "        const uint64_t sb = block_sum(live ? rowfix(tmax, eb) : 0, sh_sum);\n";
+  o << "        if (threadIdx.x == 0) lse_store_row(row_e, row_s, " << row << ", eb, sb, " << tail_scope(fused_tail) << ");\n";
+  o << "      }\n    }\n";
+  emit_kernel_close(o, fused_tail, ticket);
+}
 
 // The sites of a lane that owns NP whole PAIRS of adjacent particles (suffixes A, B [, C, D]) under PHILOX: one cipher
 // block per pair and two draws (pk0 / pk1: the cipher key; pair0 [, pair1]: the pairs' counter words — defined by the
@@ -564,15 +627,17 @@ inline void emit_prelude(std::ostringstream& o, bool fast_math = false, bool bm_
 // The quad kernels store write-through (sc1) when a launch holds ONE pass (store16_out, gjx_device.hpp): the kernel's end
 // no longer waits for the write-back of its 48 MB — 4.94e10 -> 5.47e10 particles/s at one pass per launch; with many
 // passes per launch the write-back overlaps the following passes and plain stores are 1 % faster, hence the two source
-// variants (Gen::wt_stores: `wt_one_pass` is a constant of the generated source).
+// variants (ImportanceVariant::wt_stores: `wt_one_pass` is a constant of the generated source).
 template <class CSiteT, class CArgT>
-inline void emit_pair_lane_sites(std::ostringstream& o, std::vector<SiteEmitter<CSiteT, CArgT>>& em, const CSiteT* sites, int n_sites,
-                                 int NP, const std::string& ind, const std::string& store_at, const std::string& sc_guard = "",
-                                 const std::string& ubase = "", const std::string& lane_bytes = "", bool sc_known = false) {
-  const char* sfx[4] = {"A", "B", "C", "D"};
-  const int P = 2 * NP;
+inline void emit_pair_lane_sites(std::ostringstream& o, LaneGroup<CSiteT, CArgT>& lanes, const std::string& ind, const std::string& store_at,
+                                 const std::string& sc_guard = "", const std::string& ubase = "", const std::string& lane_bytes = "",
+                                 bool sc_known = false) {
+  auto& em = lanes.em;
+  const auto& sfx = lanes.kSfx;
+  const CSiteT* sites = em[0].sites;
+  const int n_sites = em[0].n_sites, P = lanes.size(), NP = P / 2;
   int cur_pair_blk = -1;
-  // `sc_known` (Gen::full_outputs): the launch stores the scores — no question is asked at the sites
+  // `sc_known` (ImportanceVariant::full_outputs): the launch stores the scores — no question is asked at the sites
   const std::string if_sc = sc_known ? "" : "if (" + sc_guard + ") ";
   // (c) The first contribution to the lane's weights (and to its scores) initialises them where it is a NormalExactCuts
   // density: that is fma(d d, -0.5, -L) with L a nonzero literal, never -0, so 0.0f + lp is lp (gjx_device.hpp first_acc).
@@ -625,17 +690,13 @@ inline void emit_pair_lane_sites(std::ostringstream& o, std::vector<SiteEmitter<
       const std::string I = std::to_string(em[0].impl), PS = std::to_string(P);
       const uint32_t fold = em[0].fold_of(q);
       o << ind << "float vg0_" << Q << "[" << PS << "]" << (st.dist == GJX_DIST_BETA ? ", vg1_" + Q + "[" + PS + "]" : std::string()) << ";\n";
-      o << ind << "{\n" << ind << "  const Stream<" << I << "> gs[" << PS << "] = {";
-      for (int u = 0; u < P; ++u) o << (u ? ", " : "") << "Stream<" << I << ">(" << em[u].key_of(q) << ", true, " << fold << "u)";
-      o << "};\n";
-      o << ind << "  const float gc0[" << PS << "] = {";
-      for (int u = 0; u < P; ++u) o << (u ? ", " : "") << "a0_" << Q << sfx[u];
-      o << "};\n" << ind << "  std_gamma_multi<" << I << ", " << PS << ">(gs, 0, gc0, vg0_" << Q << ");\n";
-      if (st.dist == GJX_DIST_BETA) {
-        o << ind << "  const float gc1[" << PS << "] = {";
-        for (int u = 0; u < P; ++u) o << (u ? ", " : "") << "a1_" << Q << sfx[u];
-        o << "};\n" << ind << "  std_gamma_multi<" << I << ", " << PS << ">(gs, 1, gc1, vg1_" << Q << ");\n";
-      }
+      o << ind << "{\n" << ind << "  const Stream<" << I << "> gs[" << PS << "] = {"
+        << lanes.join([&](const auto& e) { return "Stream<" + I + ">(" + e.key_of(q) + ", true, " + std::to_string(fold) + "u)"; }) << "};\n";
+      o << ind << "  const float gc0[" << PS << "] = {" << lanes.list("a0_" + Q) << "};\n"
+        << ind << "  std_gamma_multi<" << I << ", " << PS << ">(gs, 0, gc0, vg0_" << Q << ");\n";
+      if (st.dist == GJX_DIST_BETA)
+        o << ind << "  const float gc1[" << PS << "] = {" << lanes.list("a1_" + Q) << "};\n"
+          << ind << "  std_gamma_multi<" << I << ", " << PS << ">(gs, 1, gc1, vg1_" << Q << ");\n";
       o << ind << "}\n";
       for (int u = 0; u < P; ++u) {
         if (st.dist == GJX_DIST_GAMMA)
@@ -687,9 +748,7 @@ inline void emit_pair_lane_sites(std::ostringstream& o, std::vector<SiteEmitter<
     for (int u = 0; u < P; ++u) em[u].close_scopes(q + 1);
     if (st.out_col >= 0) {  // the lane's particles are adjacent in the column: one 8- / 16-byte store per lane
       const bool isint = SiteEmitter<CSiteT, CArgT>::is_int(st);
-      std::string vals;
-      for (int u = 0; u < P; ++u)
-        vals += (u ? ", " : "") + (isint ? "(uint32_t)vi" + Q + sfx[u] : "f2u(vf" + Q + sfx[u] + ")");
+      const std::string vals = isint ? lanes.list("(uint32_t)vi" + Q) : lanes.list("f2u(vf" + Q, ")");
       if (P == 4 && !ubase.empty())  // (wave-uniform base + the lane's byte offset: gjx_device.hpp store16_at)
         o << ind << "store16_at(reinterpret_cast<uint32_t*>(cols.out[" << st.out_col << "]) + " << ubase << ", " << lane_bytes << ", make_uint4(" << vals << "), wt_one_pass);\n";
       else if (P == 4)
@@ -707,13 +766,14 @@ inline void emit_pair_lane_sites(std::ostringstream& o, std::vector<SiteEmitter<
 //    TWO ADJACENT PARTICLES per lane.  The lane derives both particles' words anyway, so every Normal site
 //    costs one shared Box-Muller transform for the pair, and the cipher key (the parent's) is uniform over
 //    the launch: the round keys live in scalar registers.
-template <class CSiteT, class CArgT>
-struct Gen {
-  std::ostringstream o;
-  int impl;
-  const CSiteT* sites;
-  int n_sites;
-  int min_waves = 0;  // __launch_bounds__ waves-per-SIMD hint (0 = none)
+//
+// Which of these kernels a source is — the value that travels from a launch (gjx_hip.hip importance_launch) to the generator,
+// and the index of the plan's slot for the compiled kernel.
+struct ImportanceVariant {
+  int impl = 0;            // the generator: 0 THREEFRY, 1 PHILOX
+  int lane_particles = 1;  // adjacent particles per lane: 1; 2 = the paired form (128-thread workgroup per 256-particle row);
+                           // 4 = two pairs: one WAVE owns the whole row, so the row statistics are wave reductions (DPP only:
+                           // no LDS, no barrier) and every column store is 16 bytes per lane.  Above 1 is PHILOX only
   bool fused_tail = false;  // the kernel folds the row sums itself (gjx_device.hpp lse_tail; launches that pass a gjx_lse_out).
                             // A variant of its own: inlined into every kernel, the fold cost 22 VGPRs — one wave per SIMD —
                             // on launches that never enter it (132 -> 110 in the 10-latent quad kernel)
@@ -724,39 +784,72 @@ struct Gen {
                               // gjx_lse_out): all five are known non-null, so the source asks nothing about them — as run-time
                               // questions they were 25 uniform branches and a compare per site in every row of the 10-latent
                               // kernel, and cut the row into some 40 basic blocks.  Every other form ignores the flag
+
+  // Which combinations a launch can take: pairs and quads under PHILOX only; the two kinds of store and the known outputs
+  // exist at four particles per lane only, the known outputs not together with the fused tail.
+  constexpr bool launched() const {
+    return (impl == 0 || impl == 1) && (lane_particles == 1 || ((lane_particles == 2 || lane_particles == 4) && impl == 1)) &&
+           (!wt_stores || lane_particles == 4) && (!full_outputs || (lane_particles == 4 && !fused_tail));
+  }
+  // The variant of a launch.  `allowed`: how many adjacent particles a lane may own given the keys, n and the alignment of
+  // the buffers (gjx_hip.hip lane_particles); `form_pref`: GJX_JIT_FORM, the most the caller wants (three become two).
+  static ImportanceVariant of_launch(int impl, int allowed, int form_pref, bool lse, bool one_pass, bool every_output) {
+    const int most = impl == 1 ? (allowed < form_pref ? allowed : form_pref) : 1, P = most >= 4 ? 4 : (most >= 2 ? 2 : 1);
+    return ImportanceVariant{impl, P, lse, one_pass && P == 4, every_output && !lse && P == 4};
+  }
+  // The variant the diagnostics name: `bits` = impl | GJX_SOURCE_*, `form` the particles per lane of a PHILOX source.  Any
+  // combination of the flags stands, full outputs with the fused tail too (no launch takes it; the source exists); what a
+  // form ignores is dropped: one particle per lane has one kind of store and asks about every output, and so does the pair
+  // form, which still says the kind of store in its text (`wt_one_pass`), so that flag stays with it.
+  static ImportanceVariant of_source(int bits, int form) {
+    const int impl = bits & ~(GJX_SOURCE_FUSED_TAIL | GJX_SOURCE_WT_STORES | GJX_SOURCE_FULL_OUTPUTS), P = impl == 1 ? form : 1;
+    return ImportanceVariant{impl, P, (bits & GJX_SOURCE_FUSED_TAIL) != 0, (bits & GJX_SOURCE_WT_STORES) != 0 && P >= 2,
+                             (bits & GJX_SOURCE_FULL_OUTPUTS) != 0 && P == 4};
+  }
+  // The plan's slot of a variant a launch can take: the six (form, fused tail) pairs below four particles per lane, then the
+  // six quad variants.  Dense: kSlots of them, no two alike (the static_assert below walks them all).
+  static constexpr int kSlots = 12;
+  constexpr int slot() const {
+    if (lane_particles < 4) return 2 * (lane_particles == 2 ? 2 : impl) + (fused_tail ? 1 : 0);
+    return 6 + (full_outputs ? 4 + (wt_stores ? 1 : 0) : 2 * (fused_tail ? 1 : 0) + (wt_stores ? 1 : 0));
+  }
+  const char* kname() const { return impl == 0 ? "gjx_plan_kernel_threefry" : "gjx_plan_kernel_philox"; }
+};
+constexpr bool importance_slots_distinct() {
+  bool seen[ImportanceVariant::kSlots] = {};
+  int n = 0;
+  for (int k = 0; k < 2 * 3 * 8; ++k) {  // every generator, form and flag combination
+    const ImportanceVariant v{k & 1, 1 << ((k >> 1) % 3), ((k / 6) & 1) != 0, ((k / 6) & 2) != 0, ((k / 6) & 4) != 0};
+    if (!v.launched()) continue;
+    if (v.slot() < 0 || v.slot() >= ImportanceVariant::kSlots || seen[v.slot()]) return false;
+    seen[v.slot()] = true, ++n;
+  }
+  return n == ImportanceVariant::kSlots;
+}
+static_assert(importance_slots_distinct(), "two importance variants a launch can take share a slot of gjx_plan::jit");
+
+template <class CSiteT, class CArgT>
+struct Gen {
+  std::ostringstream o;
+  ImportanceVariant v;
+  const CSiteT* sites;
+  int n_sites;
+  int min_waves = 0;  // __launch_bounds__ waves-per-SIMD hint (0 = none)
   int block = 256;    // threads per workgroup of the generated kernel
   int rows_per_block = 1;
-  bool laned = false; // the paired form (see above)
   bool fast_math = false;  // GJX_PLAN_FAST_MATH
   const ScopeInfo* sc = nullptr;  // nested calls (null: a flat body)
-  int pairs_per_lane = 1;  // paired form: 1 = two adjacent particles per lane (128-thread workgroup per 256-particle row);
-                           // 2 = FOUR adjacent particles per lane: one WAVE owns the whole row, so the row statistics are
-                           // wave reductions (DPP only: no LDS, no barrier) and every column store is 16 bytes per lane
 
   static const char* signature() {
     return "(KeySrc ks, RunCols cols, float* score, float* logw, uint64_t n, float* max_partials, int32_t* row_e, "
            "uint64_t* row_s, LseTail tail, PassBatch bt, PlanParams prm, PlanTables tabs) {\n";
   }
-  const char* kname() const { return impl == 0 ? "gjx_plan_kernel_threefry" : "gjx_plan_kernel_philox"; }
-  // PHILOX Normal sites draw through the Box-Muller tables: this source's kernels stage them in LDS (gjx_device.hpp bm_stage)
-  bool bm_lds() const {
-    if (impl != 1 || fast_math) return false;
-    for (int q = 0; q < n_sites; ++q)
-      if (!sites[q].observed && sites[q].dist == GJX_DIST_NORMAL) return true;
-    return false;
-  }
   // the waves-per-SIMD hint is a macro with the plan's choice as its default (0 = none), so that
   // GJX_JIT_DEFINE=GJX_WAVES_HINT=<k> builds the same kernel under another hint for an A/B (tools/ab_waves_hint.py)
   std::string bounds(int threads) const { return "__launch_bounds__(" + std::to_string(threads) + ", GJX_WAVES_HINT)"; }
   void emit_hint_default() { o << "#ifndef GJX_WAVES_HINT\n#define GJX_WAVES_HINT " << (min_waves > 0 ? min_waves : 0) << "\n#endif\n"; }
-  // the row sums of a kernel without the fused fold are read by a later launch: plain stores
-  const char* tail_scope() const { return fused_tail ? "tail.tickets != nullptr" : "false"; }
-  void emit_tail() {
-    o << "  }\n";
-    // (one ticket per workgroup of the two-dimensional grid: its linear id, x fastest, and the count of all of them)
-    if (fused_tail) o << "  if (row_e) lse_tail(row_e, row_s, (n + 255) / 256, tail, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);\n";
-    o << "}\n";
-  }
+  // (one ticket per workgroup of the two-dimensional grid: its linear id, x fastest, and the count of all of them)
+  static constexpr const char* kTicket = "blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y";
   // The grid is (rows of a pass / R, passes): a workgroup's pass is blockIdx.y and its first row blockIdx.x — known to the
   // dispatcher, so the kernel divides nothing, and the address of the pass's parent key (bt.parent[pass], in the kernel
   // argument block) is known at the first instruction: its load goes out with the other arguments'.  The loop over x is for
@@ -768,8 +861,9 @@ struct Gen {
 
   std::string run_paired() {
     // NP pairs of adjacent particles per lane; a 256-particle row is 128 / NP lanes.  R rows per workgroup.
-    const int NP = pairs_per_lane == 2 ? 2 : 1;
+    const int NP = v.lane_particles / 2;
     const int lanes_per_row = 128 / NP;
+    const bool lds = bm_lds(v.impl, fast_math, sites, n_sites);
     // rows per workgroup: 1 when the walk stores value columns (measured r02); a walk without any (an estimate of the
     // log-marginal alone: row sums out, nothing else) runs 4 one-wave rows per workgroup — 256 lanes fold the row sums in
     // the fused tail in one trip of loads instead of 8 by a single wave (host-API call 52.5 -> 47.6 us at 1e6 particles)
@@ -782,10 +876,10 @@ struct Gen {
     // the quad form's stores: one wave-uniform base per column and row (scalar registers) plus ONE per-lane byte offset
     // (gjx_device.hpp store16_at); the four-row workgroup of the estimate-only kernel has no block-uniform row
     const bool ubase = NP == 2 && R == 1;
-    const bool full = full_outputs && ubase;  // (Gen::full_outputs)
-    emit_prelude(o, fast_math, bm_lds(), block);
+    const bool full = v.full_outputs && ubase;  // (ImportanceVariant::full_outputs)
+    emit_prelude(o, fast_math, lds, block);
     emit_hint_default();
-    o << "extern \"C\" __global__ " << bounds(block) << " void " << kname() << signature();
+    o << "extern \"C\" __global__ " << bounds(block) << " void " << v.kname() << signature();
     if (waves_per_row > 1) o << "  __shared__ float sh_red[" << waves_per_row * R << "];\n  __shared__ uint64_t sh_sum[" << waves_per_row * R << "];\n";
     if (R == 1) o << "  const int wv = threadIdx.x >> 6, pr = 0, tr = threadIdx.x;  // (block-uniform row: the cipher key stays scalar)\n";
     else o << "  const int wv = threadIdx.x >> 6, pr = threadIdx.x / " << lanes_per_row << ", tr = threadIdx.x % " << lanes_per_row << ";\n";
@@ -793,10 +887,10 @@ struct Gen {
     // the Box-Muller tables' loads first (they wait for no argument: gjx_device.hpp bm_issue), then the kernel's scalar
     // arguments in ONE round of loads (gjx_device.hpp: resample_args_anchor has the measurement), the pass's parent key among
     // them: one wait for both
-    if (bm_lds()) o << "  const BmLoads bm_loads = bm_issue();\n";
+    if (lds) o << "  const BmLoads bm_loads = bm_issue();\n";
     emit_pass_key();
     o << "  asm volatile(\"\" :: \"s\"(n), \"s\"(score), \"s\"(logw), \"s\"(max_partials), \"s\"(row_e), \"s\"(row_s), \"s\"(bt.n_pass), \"s\"(bt.rows_per_pass), \"s\"(bt.pass_stride), \"s\"(bt.row_stride), \"s\"(ks.first), \"s\"(ks.parent.k0), \"s\"(ks.parent.k1), \"s\"(bk0), \"s\"(bk1), \"s\"(grid_x)"
-      << (fused_tail ? ", \"s\"(tail.tickets)" : "") << ");\n";
+      << (v.fused_tail ? ", \"s\"(tail.tickets)" : "") << ");\n";
     {
       bool seen[64] = {};  // ... and the value columns this plan stores (RunCols::out has 64)
       for (int q = 0; q < n_sites; ++q)
@@ -805,8 +899,9 @@ struct Gen {
           o << "  asm volatile(\"\" :: \"s\"(cols.out[" << sites[q].out_col << "]));\n";
         }
     }
-    if (bm_lds()) o << "  bm_loads.bm_stage();\n";
-    o << "  const bool wt_one_pass = " << (wt_stores ? "true" : "false") << "; (void)wt_one_pass;  // (Gen::wt_stores)\n";
+    if (lds) o << "  bm_loads.bm_stage();\n";
+    // (the text of the generated comment names the flag as it was called when it was a member of Gen: sources stay as they were)
+    o << "  const bool wt_one_pass = " << (v.wt_stores ? "true" : "false") << "; (void)wt_one_pass;  // (Gen::wt_stores)\n";
     o << "  const uint32_t pk0 = bt.n_pass > 1 ? bk0 : ks.parent.k0, pk1 = bt.n_pass > 1 ? bk1 : ks.parent.k1;\n";
     o << "  const uint64_t po = (uint64_t)pass * bt.pass_stride, ro = (uint64_t)pass * bt.row_stride;  // this pass's outputs\n";
     o << "  for (uint64_t g0 = (uint64_t)blockIdx.x * " << R << "; g0 < bt.rows_per_pass; g0 += (uint64_t)grid_x * " << R << ") {\n";
@@ -817,57 +912,47 @@ struct Gen {
     // scalar registers that was more than fit — a pair spilled to VGPR lanes and read back for every row.)
     o << "    uint64_t rrow = ro + row;\n";
     if (NP == 2 && R == 1) o << "    asm volatile(\"\" : \"+s\"(rrow));\n";
-    const char* sfx[4] = {"A", "B", "C", "D"};
     const int P = 2 * NP;  // particles per lane
+    LaneGroup<CSiteT, CArgT> lanes(o, P, v.impl, 0, sites, n_sites, "      ");
+    lanes.each([&](int, auto& e) { e.store_values = false; e.row_cuts = true; e.sc = sc; });  // (the lane stores its particles at once)
     o << "    const uint64_t iA = row * 256 + " << P << " * (uint64_t)tr;\n";
-    for (int u = 1; u < P; ++u) o << "    const uint64_t i" << sfx[u] << " = iA + " << u << ";\n";
+    lanes.each([&](int u, auto& e) { if (u) o << "    const uint64_t i" << e.sfx << " = iA + " << u << ";\n"; });
     // n is a multiple of P in this form (checked by the host): all particles of a lane exist or none
     o << "    const bool ok = live_row && iA < n;\n";
     // (the lane's offset is made opaque per row: folded into the columns' bases it would be hoisted out of the row loop
     // as one 64-bit address pair per column)
     if (ubase) o << "    const uint64_t ub = po + row * 256;\n    uint32_t lb = 16u * (uint32_t)tr;\n    asm volatile(\"\" : \"+v\"(lb));\n";
-    for (int u = 0; u < P; ++u) o << "    const uint64_t li" << sfx[u] << " = i" << sfx[u] << "; (void)li" << sfx[u] << ";\n";
-    for (int u = 0; u < P; ++u) o << "    float w" << sfx[u] << " = 0.0f, sc" << sfx[u] << " = 0.0f;\n";
+    lanes.each([&](int, auto& e) { o << "    const uint64_t li" << e.sfx << " = i" << e.sfx << "; (void)li" << e.sfx << ";\n"; });
+    lanes.each([&](int, auto& e) { o << "    float w" << e.sfx << " = 0.0f, sc" << e.sfx << " = 0.0f;\n"; });
     o << "    if (ok) {\n";
     o << "      const uint64_t lnA = ks.first + iA + 1u;\n";
-    for (int u = 0; u < P; ++u) {
-      if (u) o << "      const uint64_t ln" << sfx[u] << " = lnA + " << u << "u;\n";
-      o << "      const Key pkey" << sfx[u] << "{pk0, pk1, (uint32_t)ln" << sfx[u] << ", (uint32_t)(ln" << sfx[u] << " >> 32)}; (void)pkey" << sfx[u] << ";\n";
-    }
-    std::vector<SiteEmitter<CSiteT, CArgT>> em;
-    for (int u = 0; u < P; ++u) {
-      em.push_back(SiteEmitter<CSiteT, CArgT>{o, impl, 0, sites, n_sites, "      ", sfx[u]});
-      em.back().store_values = false;
-      em.back().ext_bits = true;  // the lane owns whole pairs: their single-word draws come from the pairs' blocks
-      em.back().row_cuts = true;
-      em.back().sc = sc;
-    }
-    for (int u = 0; u < P; ++u) em[u].emit_scope_keys();
+    lanes.each([&](int u, auto& e) {
+      if (u) o << "      const uint64_t ln" << e.sfx << " = lnA + " << u << "u;\n";
+      o << "      const Key pkey" << e.sfx << "{pk0, pk1, (uint32_t)ln" << e.sfx << ", (uint32_t)(ln" << e.sfx << " >> 32)}; (void)pkey" << e.sfx << ";\n";
+    });
+    lanes.each([&](int, auto& e) { e.emit_scope_keys(); });
     o << "      const uint64_t pair0 = (lnA - 1u) >> 1;\n";
     if (NP == 2) o << "      const uint64_t pair1 = pair0 + 1u;\n";
-    emit_pair_lane_sites<CSiteT, CArgT>(o, em, sites, n_sites, NP, "      ", "po + iA", "score", ubase ? "ub" : "", "lb", full);
-    if (ubase) {
-      std::string wb, sb;
-      for (int u = 0; u < P; ++u) { wb += (u ? ", f2u(w" : "f2u(w") + std::string(sfx[u]) + ")"; sb += (u ? ", f2u(sc" : "f2u(sc") + std::string(sfx[u]) + ")"; }
-      o << "      " << (full ? "" : "if (logw) ") << "store16_at(logw + ub, lb, make_uint4(" << wb << "), wt_one_pass);\n";
-      o << "      " << (full ? "" : "if (score) ") << "store16_at(score + ub, lb, make_uint4(" << sb << "), wt_one_pass);\n";
-    } else if (P == 4) {
-      std::string wb, sb;
-      for (int u = 0; u < P; ++u) { wb += (u ? ", f2u(w" : "f2u(w") + std::string(sfx[u]) + ")"; sb += (u ? ", f2u(sc" : "f2u(sc") + std::string(sfx[u]) + ")"; }
-      o << "      if (logw) store16_out(logw + po + iA, make_uint4(" << wb << "), wt_one_pass);\n";
-      o << "      if (score) store16_out(score + po + iA, make_uint4(" << sb << "), wt_one_pass);\n";
+    emit_pair_lane_sites(o, lanes, "      ", "po + iA", "score", ubase ? "ub" : "", "lb", full);
+    if (P == 4) {
+      const std::string wb = lanes.list("f2u(w", ")"), sb = lanes.list("f2u(sc", ")");
+      if (ubase) {
+        o << "      " << (full ? "" : "if (logw) ") << "store16_at(logw + ub, lb, make_uint4(" << wb << "), wt_one_pass);\n";
+        o << "      " << (full ? "" : "if (score) ") << "store16_at(score + ub, lb, make_uint4(" << sb << "), wt_one_pass);\n";
+      } else {
+        o << "      if (logw) store16_out(logw + po + iA, make_uint4(" << wb << "), wt_one_pass);\n";
+        o << "      if (score) store16_out(score + po + iA, make_uint4(" << sb << "), wt_one_pass);\n";
+      }
     } else {
-      std::string ws, ss;
-      for (int u = 0; u < P; ++u) { ws += (u ? ", w" : "w") + std::string(sfx[u]); ss += (u ? ", sc" : "sc") + std::string(sfx[u]); }
-      o << "      if (logw) *reinterpret_cast<float" << P << "*>(logw + po + iA) = make_float" << P << "(" << ws << ");\n";
-      o << "      if (score) *reinterpret_cast<float" << P << "*>(score + po + iA) = make_float" << P << "(" << ss << ");\n";
+      o << "      if (logw) *reinterpret_cast<float" << P << "*>(logw + po + iA) = make_float" << P << "(" << lanes.list("w") << ");\n";
+      o << "      if (score) *reinterpret_cast<float" << P << "*>(score + po + iA) = make_float" << P << "(" << lanes.list("sc") << ");\n";
     }
     o << "    }\n";
     o << "    " << (full ? "" : "if (max_partials || row_e) ") << "{\n";
     o << "      const float ninf = -__builtin_inff();\n";
     {
       std::string mx = "wA";
-      for (int u = 1; u < P; ++u) mx = "(" + mx + " > w" + sfx[u] + " ? " + mx + " : w" + sfx[u] + ")";
+      for (int u = 1; u < P; ++u) mx = "(" + mx + " > w" + lanes.kSfx[u] + " ? " + mx + " : w" + lanes.kSfx[u] + ")";
       // (one wave per row: the maximum on integer keys — a generated kernel's log-weights are never -0, gjx_device.hpp)
       o << "      float bm = " << (waves_per_row == 1 ? "wave_max_ordered" : "wave_max") << "(ok ? " << mx << " : ninf);\n";
     }
@@ -885,31 +970,32 @@ struct Gen {
     o << "        const int32_t eb = row_anchor(bm);\n";
     {
       std::string sm;
-      for (int u = 0; u < P; ++u) sm += (u ? " + rowfix(w" : "rowfix(w") + std::string(sfx[u]) + ", eb)";
+      for (int u = 0; u < P; ++u) sm += (u ? " + rowfix(w" : "rowfix(w") + std::string(lanes.kSfx[u]) + ", eb)";
       o << "        uint64_t sb = wave_sum_52(ok ? (" << sm << ") : 0);  // (at most four weights below 2^32)\n";
     }
     if (waves_per_row > 1) {
       o << "        __syncthreads();\n        if ((threadIdx.x & 63) == 0) sh_sum[wv] = sb;\n        __syncthreads();\n";
       o << "        sb = sh_sum[2 * pr] + sh_sum[2 * pr + 1];\n";
     }
-    o << "        if (" << lane0 << " && live_row) lse_store_row(row_e, row_s, rrow, eb, sb, " << tail_scope() << ");\n";
+    o << "        if (" << lane0 << " && live_row) lse_store_row(row_e, row_s, rrow, eb, sb, " << tail_scope(v.fused_tail) << ");\n";
     o << "      }\n    }\n";
-    emit_tail();
+    emit_kernel_close(o, v.fused_tail, kTicket);
     return o.str();
   }
 
   std::string run() {
-    if (laned && impl == 1) return run_paired();
-    const std::string I = std::to_string(impl);
-    emit_prelude(o, fast_math, bm_lds(), 256);
+    if (v.lane_particles >= 2 && v.impl == 1) return run_paired();
+    const int impl = v.impl;
+    const bool lds = bm_lds(impl, fast_math, sites, n_sites);
+    emit_prelude(o, fast_math, lds, 256);
     emit_hint_default();
     // One workgroup per 256-particle row (grid-stride): short blocks keep every SIMD's wave slots
     // full even at 1e6 particles (15 rows per lane), where a 4-row block would serialise its rows.
-    o << "extern \"C\" __global__ " << bounds(256) << " void " << kname() << signature();
+    o << "extern \"C\" __global__ " << bounds(256) << " void " << v.kname() << signature();
     o << "  __shared__ float sh_red[4];\n  __shared__ uint64_t sh_sum[4];\n";
     emit_pass_key();
     o << "  asm volatile(\"\" :: \"s\"(bk0), \"s\"(bk1), \"s\"(grid_x));\n";
-    if (bm_lds()) o << "  bm_stage();\n";
+    if (lds) o << "  bm_stage();\n";
     o << "  const uint64_t po = (uint64_t)pass * bt.pass_stride, ro = (uint64_t)pass * bt.row_stride;\n";
     o << "  KeySrc kp = ks;\n";
     o << "  if (bt.n_pass > 1) { kp.parent.k0 = bk0; kp.parent.k1 = bk1; }\n";
@@ -919,22 +1005,14 @@ struct Gen {
     o << "      const uint64_t li = row * 256 + threadIdx.x, i = po + li;\n";
     o << "      const bool ok = li < n;\n";
     o << "      if (ok) {\n";
-    o << "        const Key pkey = key_at<" << I << ">(kp, li);\n";
+    o << "        const Key pkey = key_at<" << impl << ">(kp, li);\n";
     o << "        float w = 0.0f, sc = 0.0f;\n";
     SiteEmitter<CSiteT, CArgT> em{o, impl, 0, sites, n_sites, "        "};
     em.sc = sc;
     em.run();
     o << "        if (logw) logw[i] = w;\n        if (score) score[i] = sc;\n        tmax = w;\n        live = true;\n";
     o << "      }\n    }\n";
-    o << "    if (max_partials || row_e) {\n";
-    o << "      const float bm = block_max(tmax, sh_red);\n";
-    o << "      if (max_partials && threadIdx.x == 0) max_partials[ro + row] = bm;\n";
-    o << "      if (row_e) {\n";
-    o << "        const int32_t eb = row_anchor(bm);\n";
-    o << "        const uint64_t sb = block_sum(live ? rowfix(tmax, eb) : 0, sh_sum);\n";
-    o << "        if (threadIdx.x == 0) lse_store_row(row_e, row_s, ro + row, eb, sb, " << tail_scope() << ");\n";
-    o << "      }\n    }\n";
-    emit_tail();
+    emit_row_epilogue_per_lane(o, "ro + row", v.fused_tail, kTicket);
     return o.str();
   }
 };
@@ -942,88 +1020,85 @@ struct Gen {
 // Importance over a Scan model (gjx_scan_run): one lane per particle walks all T steps — the key chain, the carry and
 // the running weight / score stay in registers, every step stores its sampled values as one coalesced row of the
 // time-major columns, and the epilogue is the importance kernel's (row maxima, row-anchored sums, in-launch fold).
+//
+// Which scan kernel a source is: the value that travels from gjx_scan_run to the generator, and the plan's slot.
+struct ScanVariant {
+  int impl = 0;       // the generator: 0 THREEFRY, 1 PHILOX
+  bool quad = false;  // PHILOX, the lazy children of a lane-0 key, n and the columns multiples of four: FOUR adjacent particles
+                      // per lane (one wave per 256-particle row).  A step's keys are lanes (scan_step_key_philox), so the
+                      // lane's two pairs share their cipher blocks and Box-Muller transforms exactly as in the importance
+                      // kernel's quad form; row statistics are wave reductions, every store is 16 bytes per lane.
+  bool fused_tail = false;  // as ImportanceVariant::fused_tail: the in-launch fold of the row sums is a variant of its own (inlined,
+                            // it took the one-particle-per-lane LGSSM kernel from 64 to 133 VGPRs, 7 -> 3 waves per SIMD)
+  // `bits` = impl | GJX_SOURCE_FUSED_TAIL (the diagnostics), or a launch's generator with its tail bit; THREEFRY has no quad form
+  static ScanVariant of(int bits, bool quad) {
+    return ScanVariant{bits & ~GJX_SOURCE_FUSED_TAIL, quad && (bits & ~GJX_SOURCE_FUSED_TAIL) == 1, (bits & GJX_SOURCE_FUSED_TAIL) != 0};
+  }
+  static constexpr int kSlots = 6;  // THREEFRY, PHILOX one particle per lane, PHILOX four per lane; then the same with the fused fold
+  constexpr int slot() const { return (quad ? 2 : impl) + (fused_tail ? 3 : 0); }
+  const char* kname() const { return impl == 0 ? "gjx_scan_kernel_threefry" : "gjx_scan_kernel_philox"; }
+};
+static_assert(ScanVariant{0, false, false}.slot() == 0 && ScanVariant{1, false, false}.slot() == 1 && ScanVariant{1, true, false}.slot() == 2 &&
+                  ScanVariant{0, false, true}.slot() == 3 && ScanVariant{1, false, true}.slot() == 4 && ScanVariant{1, true, true}.slot() == 5,
+              "the six scan variants (THREEFRY has no quad form) have a slot of gjx_scan_plan::jit each");
+
 template <class CSiteT, class CArgT>
 struct GenScan {
   std::ostringstream o;
-  int impl;
+  ScanVariant v;
   const CSiteT* sites;
   int n_sites;
   const CArgT* next_state;
   int n_state, n_obs;
   bool fast_math = false;
   const ScopeInfo* sc = nullptr;  // nested calls inside the step kernel (null: a flat body)
-  bool quad = false;  // PHILOX, the lazy children of a lane-0 key, n and the columns multiples of four: FOUR adjacent particles
-                      // per lane (one wave per 256-particle row).  A step's keys are lanes (scan_step_key_philox), so the
-                      // lane's two pairs share their cipher blocks and Box-Muller transforms exactly as in the importance
-                      // kernel's quad form; row statistics are wave reductions, every store is 16 bytes per lane.
   int block = 256;
-  bool fused_tail = false;  // as Gen::fused_tail: the in-launch fold of the row sums is a variant of its own (inlined, it took
-                            // the one-particle-per-lane LGSSM kernel from 64 to 133 VGPRs, 7 -> 3 waves per SIMD)
-  const char* tail_scope() const { return fused_tail ? "tail.tickets != nullptr" : "false"; }
-  void emit_tail() {
-    o << "  }\n";
-    if (fused_tail) o << "  if (row_e) lse_tail(row_e, row_s, (n + 255) / 256, tail, blockIdx.x, gridDim.x);\n";
-    o << "}\n";
-  }
-  const char* kname() const { return impl == 0 ? "gjx_scan_kernel_threefry" : "gjx_scan_kernel_philox"; }
-  // PHILOX Normal sites draw through the Box-Muller tables: this source's kernels stage them in LDS (gjx_device.hpp bm_stage)
-  bool bm_lds() const {
-    if (impl != 1 || fast_math) return false;
-    for (int q = 0; q < n_sites; ++q)
-      if (!sites[q].observed && sites[q].dist == GJX_DIST_NORMAL) return true;
-    return false;
-  }
+  static constexpr const char* kSignature =
+      "(KeySrc ks, RunCols cols, ScanArgs sa, float* score, float* logw, float* max_partials, int32_t* row_e, uint64_t* row_s, LseTail tail, PlanTables tabs) {\n";
+  static constexpr const char* kTicket = "blockIdx.x, gridDim.x";  // (a one-dimensional grid)
+
   std::string run_quad() {
     block = 64;
-    const char* sfx[4] = {"A", "B", "C", "D"};
-    const int P = 4;
-    emit_prelude(o, fast_math, bm_lds(), block);
+    const bool lds = bm_lds(v.impl, fast_math, sites, n_sites);
+    LaneGroup<CSiteT, CArgT> lanes(o, 4, v.impl, 2, sites, n_sites, "        ");
+    lanes.each([&](int, auto& e) { e.store_values = false; e.row_cuts = true; e.sc = sc; });
+    emit_prelude(o, fast_math, lds, block);
     o << "struct StepObs { const float* obs; };\n";
-    o << "extern \"C\" __global__ __launch_bounds__(64) void " << kname()
-      << "(KeySrc ks, RunCols cols, ScanArgs sa, float* score, float* logw, float* max_partials, int32_t* row_e, uint64_t* row_s, LseTail tail, PlanTables tabs) {\n";
-    if (bm_lds()) o << "  bm_stage();\n";
+    o << "extern \"C\" __global__ __launch_bounds__(64) void " << v.kname() << kSignature;
+    if (lds) o << "  bm_stage();\n";
     o << "  const uint64_t n = sa.n, rows_all = (n + 255) / 256;\n";
     o << "  const bool wt_one_pass = false; (void)wt_one_pass;  // (a scan's stores spread over its T steps)\n";
     o << "  const uint32_t pk0 = ks.parent.k0, pk1 = ks.parent.k1;\n";
     o << "  for (uint64_t row = blockIdx.x; row < rows_all; row += gridDim.x) {\n";
     o << "    const uint64_t iA = row * 256 + 4 * (uint64_t)threadIdx.x;\n";
     o << "    const bool ok = iA < n;  // (n is a multiple of four in this form: all particles of a lane exist or none)\n";
-    for (int u = 0; u < P; ++u) o << "    float wt" << sfx[u] << " = 0.0f, sct" << sfx[u] << " = 0.0f;\n";
+    lanes.each([&](int, auto& e) { o << "    float wt" << e.sfx << " = 0.0f, sct" << e.sfx << " = 0.0f;\n"; });
     o << "    if (ok) {\n";
     o << "      const uint64_t lnA = ks.first + iA + 1u;\n";
-    for (int u = 0; u < P; ++u)
-      for (int k = 0; k < n_state; ++k)
-        o << "      float st_" << k << sfx[u] << " = sa.carry0_cols[" << k << "] ? sa.carry0_cols[" << k << "][iA + " << u << "] : sa.carry0[" << k << "];\n";
+    lanes.each([&](int u, auto& e) {
+      for (int k = 0; k < n_state; ++k) o << "      float st_" << k << e.sfx << " = sa.carry0_cols[" << k << "] ? sa.carry0_cols[" << k << "][iA + " << u << "] : sa.carry0[" << k << "];\n";
+    });
     o << "      for (int32_t t = 0; t < sa.n_steps; ++t) {\n";
     o << "        const uint64_t lt = lnA + (((uint64_t)(uint32_t)t + 1u) << 40);  // the lanes of step t (scan_step_key_philox)\n";
-    for (int u = 0; u < P; ++u)
-      o << "        const Key pkey" << sfx[u] << "{pk0, pk1, (uint32_t)(lt + " << u << "u), (uint32_t)((lt + " << u << "u) >> 32)}; (void)pkey" << sfx[u] << ";\n";
+    lanes.each([&](int u, auto& e) { o << "        const Key pkey" << e.sfx << "{pk0, pk1, (uint32_t)(lt + " << u << "u), (uint32_t)((lt + " << u << "u) >> 32)}; (void)pkey" << e.sfx << ";\n"; });
     o << "        const uint64_t pair0 = (lt - 1u) >> 1, pair1 = pair0 + 1u;\n";
     o << "        StepObs a; a.obs = sa.obs + (size_t)t * " << n_obs << "; (void)a;\n";
     o << "        const uint64_t oiA = (uint64_t)t * sa.col_stride + iA; (void)oiA;\n";
-    for (int u = 0; u < P; ++u) o << "        float w" << sfx[u] << " = 0.0f, sc" << sfx[u] << " = 0.0f;\n";
-    std::vector<SiteEmitter<CSiteT, CArgT>> em;
-    for (int u = 0; u < P; ++u) {
-      em.push_back(SiteEmitter<CSiteT, CArgT>{o, impl, 2, sites, n_sites, "        ", sfx[u]});
-      em.back().store_values = false;
-      em.back().ext_bits = true;
-      em.back().row_cuts = true;
-      em.back().sc = sc;
-    }
-    for (int u = 0; u < P; ++u) em[u].emit_scope_keys();
-    emit_pair_lane_sites<CSiteT, CArgT>(o, em, sites, n_sites, 2, "        ", "oiA");
-    for (int u = 0; u < P; ++u)
-      for (int k = 0; k < n_state; ++k) o << "        const float nx_" << k << sfx[u] << " = " << em[u].arg(next_state[k]) << ";\n";
-    for (int u = 0; u < P; ++u)
-      for (int k = 0; k < n_state; ++k) o << "        st_" << k << sfx[u] << " = nx_" << k << sfx[u] << ";\n";
-    for (int u = 0; u < P; ++u) o << "        wt" << sfx[u] << " = wt" << sfx[u] << " + w" << sfx[u] << "; sct" << sfx[u] << " = sct" << sfx[u] << " + sc" << sfx[u] << ";\n";
+    lanes.each([&](int, auto& e) { o << "        float w" << e.sfx << " = 0.0f, sc" << e.sfx << " = 0.0f;\n"; });
+    lanes.each([&](int, auto& e) { e.emit_scope_keys(); });
+    emit_pair_lane_sites(o, lanes, "        ", "oiA");
+    for (auto& e : lanes.em)
+      for (int k = 0; k < n_state; ++k) o << "        const float nx_" << k << e.sfx << " = " << e.arg(next_state[k]) << ";\n";
+    for (auto& e : lanes.em)
+      for (int k = 0; k < n_state; ++k) o << "        st_" << k << e.sfx << " = nx_" << k << e.sfx << ";\n";
+    lanes.each([&](int, auto& e) { o << "        wt" << e.sfx << " = wt" << e.sfx << " + w" << e.sfx << "; sct" << e.sfx << " = sct" << e.sfx << " + sc" << e.sfx << ";\n"; });
     o << "      }\n";
     for (int k = 0; k < n_state; ++k)
-      o << "      if (sa.carry_out[" << k << "]) *reinterpret_cast<float4*>(sa.carry_out[" << k << "] + iA) = make_float4(st_" << k << "A, st_" << k
-        << "B, st_" << k << "C, st_" << k << "D);\n";
-    o << "      if (logw) *reinterpret_cast<float4*>(logw + iA) = make_float4(wtA, wtB, wtC, wtD);\n";
-    o << "      if (score) *reinterpret_cast<float4*>(score + iA) = make_float4(sctA, sctB, sctC, sctD);\n";
+      o << "      if (sa.carry_out[" << k << "]) *reinterpret_cast<float4*>(sa.carry_out[" << k << "] + iA) = make_float4(" << lanes.list("st_" + std::to_string(k)) << ");\n";
+    o << "      if (logw) *reinterpret_cast<float4*>(logw + iA) = make_float4(" << lanes.list("wt") << ");\n";
+    o << "      if (score) *reinterpret_cast<float4*>(score + iA) = make_float4(" << lanes.list("sct") << ");\n";
     o << "    }\n";
+    // (this form's own row statistics: see emit_row_epilogue_per_lane)
     o << "    if (max_partials || row_e) {\n";
     o << "      const float ninf = -__builtin_inff();\n";
     o << "      const float m4 = ((wtA > wtB ? wtA : wtB) > wtC ? (wtA > wtB ? wtA : wtB) : wtC);\n";
@@ -1032,26 +1107,26 @@ struct GenScan {
     o << "      if (row_e) {\n";
     o << "        const int32_t eb = row_anchor(bm);\n";
     o << "        const uint64_t sb = wave_sum(ok ? (rowfix(wtA, eb) + rowfix(wtB, eb) + rowfix(wtC, eb) + rowfix(wtD, eb)) : 0);\n";
-    o << "        if (threadIdx.x == 0) lse_store_row(row_e, row_s, row, eb, sb, " << tail_scope() << ");\n";
+    o << "        if (threadIdx.x == 0) lse_store_row(row_e, row_s, row, eb, sb, " << tail_scope(v.fused_tail) << ");\n";
     o << "      }\n    }\n";
-    emit_tail();
+    emit_kernel_close(o, v.fused_tail, kTicket);
     return o.str();
   }
   std::string run() {
-    if (quad && impl == 1) return run_quad();
-    const std::string I = std::to_string(impl);
-    emit_prelude(o, fast_math, bm_lds(), 256);
+    if (v.quad && v.impl == 1) return run_quad();
+    const int impl = v.impl;
+    const bool lds = bm_lds(impl, fast_math, sites, n_sites);
+    emit_prelude(o, fast_math, lds, 256);
     o << "struct StepObs { const float* obs; };\n";
-    o << "extern \"C\" __global__ __launch_bounds__(256) void " << kname()
-      << "(KeySrc ks, RunCols cols, ScanArgs sa, float* score, float* logw, float* max_partials, int32_t* row_e, uint64_t* row_s, LseTail tail, PlanTables tabs) {\n";
+    o << "extern \"C\" __global__ __launch_bounds__(256) void " << v.kname() << kSignature;
     o << "  __shared__ float sh_red[4];\n  __shared__ uint64_t sh_sum[4];\n";
-    if (bm_lds()) o << "  bm_stage();\n";
+    if (lds) o << "  bm_stage();\n";
     o << "  const uint64_t n = sa.n, rows_all = (n + 255) / 256;\n";
     o << "  for (uint64_t row = blockIdx.x; row < rows_all; row += gridDim.x) {\n";
     o << "    float tmax = -__builtin_inff();\n    bool live = false;\n";
     o << "    const uint64_t i = row * 256 + threadIdx.x;\n";
     o << "    if (i < n) {\n";
-    o << "      Key " << (impl == 0 ? "pkey" : "pkey0") << " = key_at<" << I << ">(ks, i);\n";
+    o << "      Key " << (impl == 0 ? "pkey" : "pkey0") << " = key_at<" << impl << ">(ks, i);\n";
     for (int k = 0; k < n_state; ++k)
       o << "      float st_" << k << " = sa.carry0_cols[" << k << "] ? sa.carry0_cols[" << k << "][i] : sa.carry0[" << k << "];\n";
     o << "      float wt = 0.0f, sct = 0.0f;\n";
@@ -1069,15 +1144,7 @@ struct GenScan {
     o << "        wt = wt + w;\n        sct = sct + sc;\n      }\n";
     for (int k = 0; k < n_state; ++k) o << "      if (sa.carry_out[" << k << "]) sa.carry_out[" << k << "][i] = st_" << k << ";\n";
     o << "      if (logw) logw[i] = wt;\n      if (score) score[i] = sct;\n      tmax = wt;\n      live = true;\n    }\n";
-    o << "    if (max_partials || row_e) {\n";
-    o << "      const float bm = block_max(tmax, sh_red);\n";
-    o << "      if (max_partials && threadIdx.x == 0) max_partials[row] = bm;\n";
-    o << "      if (row_e) {\n";
-    o << "        const int32_t eb = row_anchor(bm);\n";
-    o << "        const uint64_t sb = block_sum(live ? rowfix(tmax, eb) : 0, sh_sum);\n";
-    o << "        if (threadIdx.x == 0) lse_store_row(row_e, row_s, row, eb, sb, " << tail_scope() << ");\n";
-    o << "      }\n    }\n";
-    emit_tail();
+    emit_row_epilogue_per_lane(o, "row", v.fused_tail, kTicket);
     return o.str();
   }
 };
@@ -1176,15 +1243,12 @@ struct GenSmc {
     o << "  }\n";
   }
   void emit_quad_body(const CSiteT* sites, int n_sites, const CArgT* state_args, bool step, bool prefetched = false) {
-    const char* sf[4] = {"A", "B", "C", "D"};
     int pf_i = 0;
-    std::vector<SiteEmitter<CSiteT, CArgT>> em;
     const ScopeInfo* sc = step ? sc_step : sc_init;
-    for (int u = 0; u < 4; ++u) {
-      em.push_back(SiteEmitter<CSiteT, CArgT>{o, impl, 1, sites, n_sites, "    ", sf[u]});
-      em.back().ext_bits = true;
-      em.back().sc = sc;
-    }
+    LaneGroup<CSiteT, CArgT> lanes(o, 4, impl, 1, sites, n_sites, "    ");
+    lanes.each([&](int, auto& e) { e.sc = sc; });
+    auto& em = lanes.em;
+    const auto& sf = lanes.kSfx;
     o << "    const uint64_t g = (uint64_t)jq >> 2;\n";
     if (cond) {  // (the retained slot may be any word of its quad)
       for (int u = 0; u < 4; ++u) {
