@@ -1877,6 +1877,19 @@ struct PointwiseArgs {
 };
 constexpr int kPointwiseBlock = 4;  // particles a lane takes per round of scalar loads
 
+// Kernel argument block of the predictive launch over a plated plan (include/gjx_predictive.h; the kernel is generated from
+// the site table, gjx_plan_jit.hpp GenPredictive; the fold is fixed).  The workspace holds, per plated site, five float64
+// planes [W][n_rows]: s1, s2, below, equal, nan — every plane is written and read along the rows.
+struct PredictiveArgs {
+  const float* x[kTemperMaxLatents];  // latent columns: read at wave-uniform indices (scalar loads)
+  double* part;                       // [S][5][W][n_rows]
+  float* draws;                       // [S][m][n_rows], null when stride == 0
+  Key key;                            // the call's key: fold_in(key, i) is particle i's parent key (wave-uniform)
+  uint32_t n, per, W;                 // particles, particles per chunk, chunks
+  uint32_t stride, m;                 // every stride-th particle stores its draws (0: none; <= n), m = ceil(n / stride)
+};
+constexpr int kPredictiveBlock = 4;  // particles a lane takes per round of scalar loads
+
 // ---- the fixed device code of the backward-simulation and backward-move kernels ---------------------------------------
 // What the site table decides reaches it as template arguments: the generator, the number of carry components D, and a
 // generated struct whose static member is the table's walk — Trans::trans_lp(a, tabs, st, nx), the f32 sum of the transition
@@ -2129,6 +2142,98 @@ GJX_DEV void pointwise_fold(const double* part, uint32_t W, uint32_t n_rows, uin
   out[(size_t)n_rows + d] = s1;
   out[2 * (size_t)n_rows + d] = s2;
   out[3 * (size_t)n_rows + d] = c;
+}
+#endif
+
+// ---- the fixed device code of the predictive kernels (include/gjx_predictive.h) -----------------------------------------
+// A lane owns the data rows dA = 2r and dA + 1; the generated kernel (gjx_plan_jit.hpp GenPredictive) hands it, particle by
+// particle in index order, the draws of every plated site at its two rows.  What it keeps per row and site: two float64
+// sums and three integer counts (widened when stored: n < 2^31).  Every comparison is false on NaN.
+struct PredictiveAcc {
+  double s1, s2;
+  uint32_t below, equal, nan;
+};
+GJX_DEV PredictiveAcc predictive_start() { return PredictiveAcc{0.0, 0.0, 0u, 0u, 0u}; }
+// fold_in<IMPL>(key, i), the parent key of particle i's pass over the rows: key and i are wave-uniform, so the block belongs
+// on the SCALAR unit.  philox4x32 joins its round's three words with xor3 — a vector instruction (v_bitop3_b32) that has no
+// scalar form: through it the whole block, multiplies included, ran on the vector unit in every lane, 60 of the 160 vector
+// instructions per particle of a one-site Normal kernel.  The same rounds with the XOR chain (the same bits: xor3 says so)
+// compile to s_mul_i32 / s_mul_hi_u32 / s_xor_b32 (profiles/predictive_summary.md).
+template <int IMPL>
+GJX_DEV Key predictive_pass_key(Key key, uint32_t i) {
+  if (IMPL == 0) return fold_in<0>(key, i);
+  uint32_t c0 = key.l0, c1 = key.l1, c2 = i, c3 = kTagFold, k0 = key.k0, k1 = key.k1;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    c0 = n0;
+    c2 = n2;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return Key{c0, c1, 0u, 0u};
+}
+GJX_DEV void predictive_take(PredictiveAcc& q, float y, float obs) {
+  const double yd = (double)y;
+  const double sq = yd * yd;
+  q.s1 = q.s1 + yd;
+  q.s2 = q.s2 + sq;
+  q.below += y < obs ? 1u : 0u;
+  q.equal += y == obs ? 1u : 0u;
+  q.nan += y != y ? 1u : 0u;
+}
+// The particles whose draws are stored, i % stride == 0, met in index order: a counter instead of a division per particle.
+// `next` is the chunk's next such particle (never reached with stride 0: particle indices are below 2^31), `slot` its row
+// next / stride of the table; both wave-uniform.  stride <= n < 2^31: neither the rounding-up nor the step overflows.
+struct PredictiveKeep {
+  uint32_t next, slot;
+};
+GJX_DEV PredictiveKeep predictive_keep_start(const PredictiveArgs& a, uint32_t lo) {
+  if (a.stride == 0u) return PredictiveKeep{0xffffffffu, 0u};
+  const uint32_t slot = (lo + a.stride - 1u) / a.stride;
+  return PredictiveKeep{slot * a.stride, slot};
+}
+// particle i's draws yA[s], yB[s] of rows dA, dA + 1 (the second only where it exists): plain vector stores
+template <int S>
+GJX_DEV void predictive_keep_rows(const PredictiveArgs& a, PredictiveKeep& k, uint32_t i, uint32_t n_rows, uint32_t dA, bool hasB,
+                                  const float (&yA)[S], const float (&yB)[S]) {
+  if (i != k.next) return;
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    float* row = a.draws + ((size_t)s * a.m + k.slot) * n_rows;  // (slot = i / stride < m)
+    row[dA] = yA[s];
+    if (hasB) row[dA + 1u] = yB[s];
+  }
+  k.next += a.stride;
+  ++k.slot;
+}
+// chunk `b` of site `s` and row `d`: five plain vector stores
+GJX_DEV void predictive_store(const PredictiveArgs& a, uint32_t n_rows, uint32_t s, uint32_t b, uint32_t d, const PredictiveAcc& q) {
+  const size_t plane = (size_t)a.W * n_rows;
+  double* at = a.part + (size_t)s * 5 * plane + (size_t)b * n_rows + d;
+  at[0] = q.s1;
+  at[plane] = q.s2;
+  at[2 * plane] = (double)q.below;
+  at[3 * plane] = (double)q.equal;
+  at[4 * plane] = (double)q.nan;
+}
+#ifndef __HIPCC_RTC__
+// The fold (the library's own second launch): one lane per row and site, the W partials in chunk order, float64 from +0.
+GJX_DEV void predictive_fold(const double* part, uint32_t W, uint32_t n_rows, uint32_t s, uint32_t d, double* out) {
+  const size_t plane = (size_t)W * n_rows;
+  const double* at = part + (size_t)s * 5 * plane + d;
+  double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll 4
+  for (uint32_t k = 0; k < W; ++k)
+#pragma unroll
+    for (int j = 0; j < 5; ++j) acc[j] = acc[j] + at[(size_t)j * plane + (size_t)k * n_rows];
+#pragma unroll
+  for (int j = 0; j < 5; ++j) out[((size_t)s * 5 + j) * n_rows + d] = acc[j];
 }
 #endif
 #endif  // __HIP_DEVICE_COMPILE__

@@ -16,6 +16,7 @@
 #include "../../include/gjx_temper.h"
 #include "../../include/gjx_plate.h"
 #include "../../include/gjx_pointwise.h"
+#include "../../include/gjx_predictive.h"
 #include "../../include/gjx_temper_cov.h"
 // The library's own kernels keep the Philox round's plain XOR chain (gjx_device.hpp xor3): with v_bitop3_b32 the one-filter
 // LGSSM step measured 0.5 % slower (8.96e10 against 9.01e10 particle-steps/s, three alternating runs each, parent's range
@@ -4840,6 +4841,7 @@ struct gjx_temper_plan {
   };
   ObsExprStore* obs_expr = nullptr;  // the programs of PLATED sites' observed values (a plan's own copy, as ExprStore)
   gjx_jit::CompiledPointwise pw;     // include/gjx_pointwise.h: the pointwise kernel (one source, whatever the generator)
+  gjx_jit::CompiledPredictive pred[2];  // include/gjx_predictive.h: the predictive kernel, per generator
   ~gjx_temper_plan() { delete obs_expr; }
 };
 
@@ -5255,6 +5257,35 @@ __global__ __launch_bounds__(kBlock) void k_pointwise_fold(const double* part, u
 #endif
 }
 
+// ---- posterior predictive draws over a plated plan (include/gjx_predictive.h) --------------------------------------------
+constexpr uint64_t kPredictiveWorkgroups = 2048;  // tiles of 512 rows x chunks of particles: about this many, whatever D is
+constexpr uint64_t kPredictiveTile = 2 * kBlock;  // rows per workgroup: two per lane
+// Has the plan a predictive source?  What a pointwise source needs: a PLATED site and no per-particle input column.
+int predictive_n_plated(const gjx_temper_plan* p) {
+  int S = 0;
+  for (int q = 0; q < p->n_sites; ++q) S += p->sites[q].observed == GJX_SITE_PLATED ? 1 : 0;
+  return S;
+}
+std::string predictive_source(const gjx_temper_plan* p, int impl, PlanTables* tabs = nullptr) {
+  gjx_jit::GenPredictive<CSite, CArg> g;
+  g.impl = impl; g.sites = p->sites; g.n_sites = p->n_sites;
+  return gjx_jit::generated_source(g, tabs);
+}
+gjx_jit::CompiledPredictive* predictive_compiled(gjx_temper_plan* p, int impl) {
+  gjx_jit::CompiledPredictive& c = p->pred[impl];
+  const bool ready = compiled_once(p->mu, c, {{p->sites, p->n_sites}}, &p->dev_owned, [&] {
+    return c.load(predictive_source(p, impl, &c.tabs), gjx_jit::PlanKind::predictive, {"gjx_predictive_kernel"}, {&c.fn});
+  });
+  return ready ? &c : nullptr;
+}
+// the second launch: one lane per row (x) and plated site (y) folds the chunks' partials in chunk order (gjx_device.hpp predictive_fold)
+__global__ __launch_bounds__(kBlock) void k_predictive_fold(const double* part, uint32_t W, uint32_t n_rows, double* out) {
+#if defined(__HIP_DEVICE_COMPILE__)  // (the header's device-only section)
+  const uint32_t d = blockIdx.x * kBlock + threadIdx.x;
+  if (d < n_rows) predictive_fold(part, W, n_rows, blockIdx.y, d, out);
+#endif
+}
+
 // gjx_temper_plan_create (allow_plated = false) and gjx_temper_plan_create_plated (include/gjx_plate.h)
 int temper_plan_create(const gjx_site* sites, int n_sites, uint32_t flags, gjx_temper_plan** out, bool allow_plated) {
   if (!sites || !out || n_sites < 1 || n_sites > GJX_MAX_SITES || flags != 0u) return GJX_ERR_INVALID;
@@ -5331,6 +5362,7 @@ int gjx_temper_plan_destroy(gjx_temper_plan* p) {
   for (auto& c : p->jit) c.release();
   for (auto& c : p->cov_jit) c.release();
   p->pw.release();
+  for (auto& c : p->pred) c.release();
   free_owned(p->dev_owned);
   delete p;
   return GJX_OK;
@@ -5533,6 +5565,64 @@ int gjx_temper_pointwise(gjx_temper_plan* p, const gjx_pointwise_io* io, gjx_str
   const uint64_t tiles = nrows_of(D);
   if (int rc = launch_generated(k->fn, tiles, W, kBlock, s, args)) return rc;
   k_pointwise_fold<<<(unsigned)tiles, kBlock, 0, S(s)>>>(A.part, W, D, io->out);
+  return launch_status();
+}
+
+int gjx_predictive_version(int* major, int* minor) {
+  return version_out(major, minor, GJX_PREDICTIVE_VERSION_MAJOR, GJX_PREDICTIVE_VERSION_MINOR);
+}
+uint32_t gjx_predictive_chunks(uint64_t n, uint64_t n_rows) {
+  if (n < 1 || n >= (1ull << 31) || n_rows < 1 || n_rows >= (1ull << 31)) return 0;
+  const uint64_t tiles = (n_rows + kPredictiveTile - 1) / kPredictiveTile, by_n = nrows_of(n);
+  const uint64_t by_grid = (kPredictiveWorkgroups + tiles - 1) / tiles;  // (>= 1)
+  return (uint32_t)(by_n < by_grid ? by_n : by_grid);
+}
+size_t gjx_predictive_workspace_bytes(uint64_t n, uint64_t n_rows, int32_t n_plated) {
+  if (n_plated < 1 || n_plated > GJX_MAX_SITES) return 0;
+  return (size_t)gjx_predictive_chunks(n, n_rows) * (size_t)n_rows * (size_t)n_plated * 5 * sizeof(double);
+}
+int gjx_predictive_source(const gjx_temper_plan* p, int impl, char* buf, size_t buf_len, size_t* needed) {
+  if (!pointwise_plan_ok(p) || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
+  return copy_source_out(predictive_source(p, impl), buf, buf_len, needed);
+}
+int gjx_predictive_compile_check(const gjx_temper_plan* p, int impl) {
+  if (!pointwise_plan_ok(p) || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
+  return gjx_jit::compile_only(predictive_source(p, impl), gjx_jit::PlanKind::predictive) ? GJX_OK : GJX_ERR_UNSUPPORTED;
+}
+int gjx_temper_predictive(gjx_temper_plan* p, const gjx_keys* key, const gjx_predictive_io* io, gjx_stream s) {
+  // (ONE literal key: its fold_in children are the particles' pass keys; a batch or a stream fold has no meaning here)
+  if (!pointwise_plan_ok(p) || !io || !keys_ok(key) || key->mode != 2 || key->has_fold || !p->has_data || io->n < 1 ||
+      io->n >= (1ull << 31) || !io->out || p->n_params <= p->max_param || (io->draw_stride > 0 && !io->draws) ||
+      ((uintptr_t)io->ws & 7) != 0)
+    return GJX_ERR_INVALID;
+  PredictiveArgs A;
+  memset(&A, 0, sizeof A);
+  for (int l = 0; l < p->n_latents; ++l) {
+    if (!io->x[l]) return GJX_ERR_INVALID;
+    A.x[l] = io->x[l];
+  }
+  const int n_plated = predictive_n_plated(p);
+  const uint32_t D = p->data.n_rows, W = gjx_predictive_chunks(io->n, D);
+  if (!io->ws || io->ws_bytes < gjx_predictive_workspace_bytes(io->n, D, n_plated)) return GJX_ERR_WORKSPACE;
+  if (!gjx_jit::enabled()) return GJX_ERR_UNSUPPORTED;  // a generated kernel only
+  gjx_jit::CompiledPredictive* k = predictive_compiled(p, key->impl);
+  if (!k) return GJX_ERR_JIT;
+  A.part = static_cast<double*>(io->ws);
+  A.key = Key{key->parent[0], key->parent[1], (uint32_t)key->parent_lane, (uint32_t)(key->parent_lane >> 32)};
+  A.n = (uint32_t)io->n;
+  A.W = W;
+  A.per = (uint32_t)((io->n + W - 1) / W);
+  // (a stride of n or more stores particle 0 alone, as the stride n does: the kernel's counter stays below 2^32)
+  A.stride = (uint32_t)(io->draw_stride < io->n ? io->draw_stride : io->n);
+  A.m = A.stride ? (uint32_t)((io->n + A.stride - 1) / A.stride) : 0u;
+  A.draws = A.stride ? io->draws : nullptr;
+  PlanParams prm = p->prm;
+  PlanTables tabs = k->tabs;
+  PlateData pd = p->data;
+  void* args[] = {&A, &prm, &tabs, &pd};
+  const uint64_t tiles = (D + kPredictiveTile - 1) / kPredictiveTile;
+  if (int rc = launch_generated(k->fn, tiles, W, kBlock, s, args)) return rc;
+  k_predictive_fold<<<dim3((unsigned)nrows_of(D), (unsigned)n_plated), kBlock, 0, S(s)>>>(A.part, W, D, io->out);
   return launch_status();
 }
 

@@ -208,7 +208,8 @@ struct SiteEmitter {
       case GJX_ARG_STATE: return "((" + flit(a.scale) + " * st_" + std::to_string(a.ref) + sfx + ") + " + flit(a.offset) + ")";
       case GJX_ARG_OBS: return "((" + flit(a.scale) + " * a.obs[" + std::to_string(a.ref) + "]) + " + flit(a.offset) + ")";
       // (include/gjx_plate.h: column `ref` at the row of the plated loop — dc<ref> is the row's value, defined by GenTemper)
-      case GJX_ARG_DATA: return "((" + flit(a.scale) + " * dc" + std::to_string(a.ref) + ") + " + flit(a.offset) + ")";
+      // (with the emitter's suffix: GenPredictive holds two rows per lane, dc<ref>A and dc<ref>B)
+      case GJX_ARG_DATA: return "((" + flit(a.scale) + " * dc" + std::to_string(a.ref) + sfx + ") + " + flit(a.offset) + ")";
       case GJX_ARG_PARAM:
         // (an SMC plan's parameter as it stands is the row's value itself: no multiply by 1, no add of 0 — a uniform value
         // stays in its scalar register — and what gjx_smc_plan_set_params derives the site's constants from)
@@ -228,7 +229,7 @@ struct SiteEmitter {
             case GJX_EXPR_PARAM: st.push_back("prm.p[" + r + "]"); break;
             case GJX_EXPR_STATE: st.push_back("st_" + r + sfx); break;
             case GJX_EXPR_OBS: st.push_back("a.obs[" + r + "]"); break;
-            case GJX_EXPR_DATA: st.push_back("dc" + r); break;
+            case GJX_EXPR_DATA: st.push_back("dc" + r + sfx); break;
             case GJX_EXPR_NEG: st.back() = "(-" + st.back() + ")"; break;
             case GJX_EXPR_EXP: st.back() = "e_exp(" + st.back() + ")"; break;
             case GJX_EXPR_LOG: st.back() = "m_log(" + st.back() + ")"; break;
@@ -631,7 +632,7 @@ inline void emit_row_epilogue_per_lane(std::ostringstream& o, const char* row, b
 template <class CSiteT, class CArgT>
 inline void emit_pair_lane_sites(std::ostringstream& o, LaneGroup<CSiteT, CArgT>& lanes, const std::string& ind, const std::string& store_at,
                                  const std::string& sc_guard = "", const std::string& ubase = "", const std::string& lane_bytes = "",
-                                 bool sc_known = false) {
+                                 bool sc_known = false, const bool* skip = nullptr) {
   auto& em = lanes.em;
   const auto& sfx = lanes.kSfx;
   const CSiteT* sites = em[0].sites;
@@ -645,6 +646,7 @@ inline void emit_pair_lane_sites(std::ostringstream& o, LaneGroup<CSiteT, CArgT>
   // reach the caller's accumulators through close_scopes.
   bool w_open = false, sc_open = false;
   for (int q = 0; q < n_sites; ++q) {
+    if (skip && skip[q]) continue;  // (GenPredictive: a site the caller has emitted itself — nothing is drawn or summed at it)
     const CSiteT& st = sites[q];
     // `sc_guard` (the importance kernels: the name of the score pointer): the lane's weights and scores are brought up to
     // date AT the site, pair by pair (gjx_device.hpp pinned2), the scores only where the launch stores them — so w and sc
@@ -1748,6 +1750,149 @@ struct GenPointwise {
   }
 };
 
+// The predictive kernel of a plated tempered plan (include/gjx_predictive.h): GenPointwise's transposed loop — rows on lanes,
+// the particles of a chunk wave-uniform — with a DRAW where the pointwise kernel has a density.  The header defines the draws
+// as an importance pass over the data rows, so the sites are emitted by the importance kernel's own emitters:
+//   * a lane owns the rows dA = 2 r and dA + 1 — the "particles" A and B of a LaneGroup.  Under PHILOX the plated sites go
+//     through emit_pair_lane_sites (pair r of the pass: one cipher block per two single-word draws of both rows, one
+//     Box-Muller transform per Normal site, the gammas of both rows drawn together); under THREEFRY through the two
+//     emitters' head() / tail(), the one-particle form twice.  No sampler is written here;
+//   * the pass's parent key fold_in(a.key, i) is wave-uniform, the rows' keys are its lazy children d (split_at);
+//   * the table walked is the plan's own with the plated sites as LATENT ones (their draws) and everything else as
+//     GenPointwise has it: an unplated site only defines the value a plated site may refer to (a latent's is the argument
+//     nx_<l>), emitted here by head() and skipped by the pair emitter.  The draw numbering is the shadow table's — site s of
+//     the plated sites alone — handed to the emitters as a ScopeInfo of one scope;
+//   * a lane loads its two rows of the data columns once (dc<c>A, dc<c>B: SiteEmitter's names under the suffixes).  With an
+//     odd row count the last lane has row A only: B reads row A's data again, is summed into accumulators nobody stores and
+//     is never stored itself;
+//   * accumulators, the stored subset and the stores are fixed device code (gjx_device.hpp predictive_*).
+// Lanes past the last row leave at once.  No LDS (the Box-Muller tables are read from the constant arrays), no barrier, no
+// inline assembly in the generated text.  The source holds no data value, no parameter value and neither n nor n_rows.
+template <class CSiteT, class CArgT>
+struct GenPredictive {
+  std::ostringstream o;
+  int impl;
+  const CSiteT* sites;
+  int n_sites;
+
+  std::string run() {
+    using GT = GenTemper<CSiteT, CArgT>;
+    using Emitter = SiteEmitter<CSiteT, CArgT>;
+    constexpr int NB = gjx::kPredictiveBlock;
+    const std::string I = std::to_string(impl);
+    emit_prelude(o);
+    std::vector<CSiteT> tab(sites, sites + n_sites);
+    std::vector<int> plated;  // table positions of the plated sites: shadow site s is plated[s]
+    bool used[GJX_PLATE_MAX_COLS] = {}, skip[GJX_MAX_SITES] = {};
+    ScopeInfo si;
+    si.n_scopes = 0;
+    si.parent[0] = -1;
+    int L = 0;
+    for (int q = 0; q < n_sites; ++q) {
+      si.site_scope[q] = 0;
+      si.fold_t[q] = (uint32_t)plated.size() + 1u;  // (THREEFRY: the 1-based counter of the shadow table's sites)
+      si.fold_p[q] = (uint32_t)plated.size();       // (PHILOX: the 0-based index among its sampled sites — all of them)
+      if (sites[q].observed == GJX_SITE_PLATED) {
+        for (int c : GT::plate_cols(sites[q])) used[c] = true;
+        tab[q].observed = 0;
+        tab[q].out_col = -1;  // (the draws go where predictive_keep_rows puts them)
+        plated.push_back(q);
+        continue;
+      }
+      skip[q] = true;
+      if (sites[q].observed) continue;
+      tab[q].observed = 1;  // (a latent: an observed site whose value is the argument nx_<l>, as in GenTemper)
+      tab[q].obs = CArgT{};
+      tab[q].obs.kind = GJX_ARG_NEXT;
+      tab[q].obs.ref = L++;
+      tab[q].obs.scale = 1.0f;
+    }
+    const int S = (int)plated.size();
+    const std::string SS = std::to_string(S);
+    std::vector<int> cs;
+    for (int c = 0; c < GJX_PLATE_MAX_COLS; ++c)
+      if (used[c]) cs.push_back(c);
+    auto list = [&](const std::string& pre, const std::string& post = "") {
+      std::string t;
+      for (int l = 0; l < L; ++l) t += pre + std::to_string(l) + post;
+      return t;
+    };
+    std::string dcs_decl, dcs;
+    for (int c : cs) {
+      dcs_decl += ", float dc" + std::to_string(c) + "A, float dc" + std::to_string(c) + "B";
+      dcs += ", dc" + std::to_string(c) + "A, dc" + std::to_string(c) + "B";
+    }
+    // particle i at the lane's two rows: the draws of every plated site, into the accumulators and (every stride-th) the table
+    o << "__device__ __forceinline__ void pd_particle(const PredictiveArgs& a, const PlanParams& prm, const PlanTables& tabs, PredictiveKeep& kp, "
+         "uint32_t i, uint32_t n_rows, uint32_t dA, bool hasB" << list(", float nx_") << dcs_decl << ", PredictiveAcc (&qA)[" << SS
+      << "], PredictiveAcc (&qB)[" << SS << "]) {\n";
+    o << "  (void)prm; (void)tabs;\n";
+    o << "  const Key pk = predictive_pass_key<" << I << ">(a.key, i);  // (fold_in(a.key, i), wave-uniform: the parent key of this particle's pass over the rows)\n";
+    o << "  const Key pkeyA = split_at<" << I << ">(pk, (uint64_t)dA); (void)pkeyA;\n";
+    o << "  const Key pkeyB = split_at<" << I << ">(pk, (uint64_t)dA + 1u); (void)pkeyB;\n";
+    LaneGroup<CSiteT, CArgT> lanes(o, 2, impl, 0, tab.data(), n_sites, "  ");
+    lanes.each([&](int, Emitter& e) { e.store_values = false; e.sc = &si; e.ext_bits = impl == 1; e.defer_acc = true; });
+    for (int q = 0; q < n_sites; ++q)
+      if (skip[q]) lanes.each([&](int, Emitter& e) { e.head(q); });
+    if (impl == 1) {
+      o << "  const uint32_t pk0 = pk.k0, pk1 = pk.k1; (void)pk0; (void)pk1;\n";
+      o << "  const uint64_t pair0 = (uint64_t)(dA >> 1); (void)pair0;\n";
+      // (the pair emitter adds a latent site's log-density to the lane's scores: nothing reads them here — dead code)
+      o << "  float scA = 0.0f, scB = 0.0f;\n";
+      emit_pair_lane_sites(o, lanes, "  ", "", "", "", "", false, skip);
+      o << "  (void)scA; (void)scB;\n";
+    } else {
+      for (int q : plated) {
+        lanes.each([&](int, Emitter& e) { e.head(q); });
+        lanes.each([&](int, Emitter& e) { e.tail(q); });
+      }
+    }
+    auto values = [&](const Emitter& e) {
+      std::string t;
+      for (int s = 0; s < S; ++s) t += (s ? ", " : "") + e.val_f32(plated[s]);
+      return t;
+    };
+    // the observed values of gjx_plate.h at the two rows (a Bernoulli site's as 0 / 1), from the ORIGINAL sites' operands
+    auto observed = [&](const Emitter& e) {
+      std::string t;
+      for (int s = 0; s < S; ++s) {
+        const CSiteT& st = sites[plated[s]];
+        const std::string ov = e.arg(st.obs);
+        t += (s ? ", " : "") + (Emitter::is_int(st) ? "((int32_t)__builtin_rintf(" + ov + ") != 0 ? 1.0f : 0.0f)" : ov);
+      }
+      return t;
+    };
+    lanes.each([&](int, Emitter& e) {
+      o << "  const float y" << e.sfx << "[" << SS << "] = {" << values(e) << "};\n";
+      o << "  const float ob" << e.sfx << "[" << SS << "] = {" << observed(e) << "};\n";
+    });
+    o << "#pragma unroll\n  for (int s = 0; s < " << SS << "; ++s) {\n    predictive_take(qA[s], yA[s], obA[s]);\n    predictive_take(qB[s], yB[s], obB[s]);\n  }\n";
+    o << "  predictive_keep_rows<" << SS << ">(a, kp, i, n_rows, dA, hasB, yA, yB);\n}\n";
+
+    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_predictive_kernel(PredictiveArgs a, PlanParams prm, PlanTables tabs, PlateData pd) {\n";
+    o << "  const uint32_t dA = (blockIdx.x * 256u + threadIdx.x) * 2u;\n  if (dA >= pd.n_rows) return;\n";
+    o << "  const bool hasB = dA + 1u < pd.n_rows;\n  const uint32_t dB = hasB ? dA + 1u : dA;  // (an odd row count: row n_rows is never read)\n";
+    for (int c : cs) o << "  const float dc" << c << "A = pd.col[" << c << "][dA], dc" << c << "B = pd.col[" << c << "][dB];\n";
+    for (int l = 0; l < L; ++l) o << "  const PlateCol xc" << l << " = (PlateCol)a.x[" << l << "];\n";
+    o << "  const uint64_t lo64 = (uint64_t)blockIdx.y * a.per;\n";
+    o << "  const uint32_t lo = lo64 < a.n ? (uint32_t)lo64 : a.n;\n";
+    o << "  const uint32_t hi = a.n - lo > a.per ? lo + a.per : a.n;\n";
+    o << "  PredictiveAcc qA[" << SS << "], qB[" << SS << "];\n";
+    o << "#pragma unroll\n  for (int s = 0; s < " << SS << "; ++s) qA[s] = qB[s] = predictive_start();\n";
+    o << "  PredictiveKeep kp = predictive_keep_start(a, lo);\n  uint32_t i = lo;\n";
+    o << "  for (; hi - i >= " << NB << "u; i += " << NB << "u) {\n";
+    for (int l = 0; l < L; ++l)
+      for (int j = 0; j < NB; ++j) o << "    const float x" << l << "_" << j << " = xc" << l << "[(size_t)i + " << j << "u];\n";
+    for (int j = 0; j < NB; ++j)
+      o << "    pd_particle(a, prm, tabs, kp, i + " << j << "u, pd.n_rows, dA, hasB" << list(", x", "_" + std::to_string(j)) << dcs << ", qA, qB);\n";
+    o << "  }\n";
+    o << "  for (; i < hi; ++i) pd_particle(a, prm, tabs, kp, i, pd.n_rows, dA, hasB" << list(", xc", "[i]") << dcs << ", qA, qB);\n";
+    o << "#pragma unroll\n  for (int s = 0; s < " << SS << "; ++s) {\n    predictive_store(a, pd.n_rows, (uint32_t)s, blockIdx.y, dA, qA[s]);\n";
+    o << "    if (hasB) predictive_store(a, pd.n_rows, (uint32_t)s, blockIdx.y, dA + 1u, qB[s]);\n  }\n}\n";
+    return o.str();
+  }
+};
+
 // One source generation: the generator numbers the plan's device tables while it runs (TableScope); `tabs` (nullable) takes
 // their addresses, in that order — the kernel argument of every launch of the source.
 template <class G>
@@ -1803,7 +1948,7 @@ inline bool read_file(const std::string& path, std::string* out) {
   return true;
 }
 // The plan kinds that generate kernels.  Each has its own compiler option list (compile_options).
-enum class PlanKind { importance, scan, smc, backsim, temper };
+enum class PlanKind { importance, scan, smc, backsim, temper, predictive };
 // The options of one plan kind: four fixed ones, then the kind's own, then the A/B knobs (a later option wins).
 //  * importance: -fno-slp-vectorize.  The SLP vectoriser turns pairs of f32 operations into v_pk_* forms, which issue no
 //    faster per flop than two scalar ones (tools/README.md) but cost v_mov shuffles to build register pairs and hazard wait
@@ -1814,6 +1959,7 @@ enum class PlanKind { importance, scan, smc, backsim, temper };
 //    cycles per row and step with SLP and 1345.6 without (56 / 50 VGPRs: eight waves per SIMD either way).
 //  * smc, backsim: nothing of their own (not priced).
 //  * temper: nothing of its own (not priced): one particle per lane, nothing for the SLP vectoriser to pair.
+//  * predictive: nothing of its own (not priced; profiles/predictive_summary.md has its instruction counts).
 inline std::vector<std::string> compile_options(PlanKind kind) {
   std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"};
   if (kind == PlanKind::importance) opts.push_back("-fno-slp-vectorize");
@@ -2124,6 +2270,9 @@ struct CompiledBacksim : Module {  // the two kernels of a backward pass
 };
 struct CompiledTemper : Module {  // the move kernel of a tempered sampler (diagonal, or the covariance move: a slot each)
   hipFunction_t move = nullptr;
+};
+struct CompiledPredictive : Module {  // the predictive kernel of a plated tempered plan, per generator (include/gjx_predictive.h)
+  hipFunction_t fn = nullptr;
 };
 struct CompiledPointwise : Module {  // the pointwise kernel of a plated tempered plan (include/gjx_pointwise.h)
   hipFunction_t fn = nullptr;

@@ -104,6 +104,10 @@ class PointwiseUnavailable(HeaderUnavailable):
     header, why = "gjx_pointwise.h", "pointwise predictive densities run as a generated HIP kernel over a plated plan only"
 
 
+class PredictiveUnavailable(HeaderUnavailable):
+    header, why = "gjx_predictive.h", "posterior predictive draws run as a generated HIP kernel over a plated plan only"
+
+
 class TemperCovUnavailable(HeaderUnavailable):
     header, why = "gjx_temper_cov.h", "the population moments and the covariance move run as HIP kernels only"
 
@@ -688,6 +692,32 @@ POINTWISE_PROTOTYPES = {
 }
 POINTWISE_ABI_VERSION = (0, 1)
 
+# include/gjx_predictive.h: a TWELFTH header, same arrangement — posterior predictive draws of a plated tempered plan: per row
+# and plated site the moments of the replicated data over the particles, its position against the observed value, and a
+# strided subset of the draws themselves.  It builds on gjx_plate.h alone and is bound right after it.
+class PredictiveIO(C.Structure):
+    """gjx_predictive_io (include/gjx_predictive.h)."""
+    _fields_ = [
+        ("n", C.c_uint64),
+        ("x", C.c_void_p * TEMPER_MAX_LATENTS),
+        ("out", C.c_void_p),
+        ("draws", C.c_void_p),
+        ("draw_stride", C.c_uint64),
+        ("ws", C.c_void_p),
+        ("ws_bytes", C.c_size_t),
+    ]
+
+
+PREDICTIVE_PROTOTYPES = {
+    "gjx_predictive_version": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gjx_predictive_chunks": (C.c_uint32, [C.c_uint64, C.c_uint64]),
+    "gjx_predictive_workspace_bytes": (C.c_size_t, [C.c_uint64, C.c_uint64, C.c_int32]),
+    "gjx_temper_predictive": (C.c_int, [_P, C.POINTER(Keys), C.POINTER(PredictiveIO), _P]),
+    "gjx_predictive_source": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gjx_predictive_compile_check": (C.c_int, [_P, C.c_int]),
+}
+PREDICTIVE_ABI_VERSION = (0, 1)
+
 # include/gjx_temper_cov.h: an ELEVENTH header, same arrangement — full-covariance proposals for the tempered move: the one-launch
 # weighted moments of a population with the proposal factor built on the device, and the move through that factor
 class TemperMomentsIO(C.Structure):
@@ -743,6 +773,8 @@ PLAN_HEADERS = {h.key: h for h in (
     Header("csmc", "gjx_csmc.h", "gjx_csmc_version", CSMC_PROTOTYPES, "CSMC_ABI_VERSION", CsmcUnavailable),
     Header("temper", "gjx_temper.h", "gjx_temper_version", TEMPER_PROTOTYPES, "TEMPER_ABI_VERSION", TemperUnavailable),
     Header("plate", "gjx_plate.h", "gjx_plate_version", PLATE_PROTOTYPES, "PLATE_ABI_VERSION", PlateUnavailable),
+    Header("predictive", "gjx_predictive.h", "gjx_predictive_version", PREDICTIVE_PROTOTYPES, "PREDICTIVE_ABI_VERSION",
+           PredictiveUnavailable),
     Header("pointwise", "gjx_pointwise.h", "gjx_pointwise_version", POINTWISE_PROTOTYPES, "POINTWISE_ABI_VERSION",
            PointwiseUnavailable),
 )}
@@ -769,6 +801,8 @@ _NO_STATUS = {
     "gjx_temper_ladder_workspace_bytes",
     "gjx_pointwise_chunks",
     "gjx_pointwise_workspace_bytes",
+    "gjx_predictive_chunks",
+    "gjx_predictive_workspace_bytes",
     "gjx_temper_moments_workspace_bytes",
     "gjx_backmove_workspace_bytes",
     "gjx_backsim_workspace_bytes",

@@ -592,6 +592,7 @@ class Ops:
         self.lib.call(creator, arr, len(sites), 0, C.byref(handle))
         plan = TemperPlan(self, handle, int(self.lib.call("gjx_temper_plan_n_latents", handle)))
         plan.plated = plated
+        plan.n_plated = sum(s.observed == abi.SITE_PLATED for s in sites)
         plan._keep = keep  # device tables and programs the sites point into
         return plan
 
@@ -729,6 +730,37 @@ class Ops:
         io.out, io.ws, io.ws_bytes = out.data_ptr(), ws.data_ptr(), ws.numel()
         self.lib.call("gjx_temper_pointwise", plan.handle, C.byref(io), self.stream())
         return out.view(4, D)
+
+    def temper_predictive(self, plan: "TemperPlan", key, x: list, draw_stride: int = 0):
+        """gjx_temper_predictive (include/gjx_predictive.h): TWO launches -> (out float64[S, 5, D], draws float32[S, m, D] or
+        None) on the device.  Per plated site s and data row d, over the n particles of the columns `x` (the L latent
+        columns, float32[n]): the sum and the sum of squares of the replicated value y ~ p(y | x_i, data_d), and the counts
+        y < obs_d, y == obs_d, y != y.  `key`: ONE key (a PRNGKey, or its literal batch); particle i draws its pass over the
+        rows under fold_in(key, i).  `draw_stride = k >= 1` also returns the draws of particles 0, k, 2 k, ... (m = ceil(n / k))."""
+        self.lib.require("predictive", "gjx_temper_predictive")
+        if not getattr(plan, "plated", False) or not plan.n_rows:
+            raise ValueError("temper_predictive: the plan has no plated site, or no data (TemperPlan.set_data)")
+        L, n, D, S = plan.n_latents, x[0].numel(), plan.n_rows, plan.n_plated
+        if len(x) != L:
+            raise ValueError(f"temper_predictive: the plan has {L} latents, got {len(x)} columns")
+        k = int(draw_stride)
+        if k < 0:
+            raise ValueError("temper_predictive: draw_stride >= 0")
+        kb = key if isinstance(key, KeyBatch) else key.literal()
+        io = abi.PredictiveIO()
+        io.n = n
+        for l in range(L):
+            io.x[l] = self._chk(x[l], torch.float32, n, f"x[{l}]").value
+        nb = int(self.lib.call("gjx_predictive_workspace_bytes", n, D, S))
+        # (per call: see workspace(); uninitialised: the first launch writes every entry the fold reads)
+        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=self._alloc_device)
+        out = self.empty(S * 5 * D, torch.float64)
+        draws = self.empty(S * (-(-n // k)) * D, torch.float32) if k else None
+        io.out, io.ws, io.ws_bytes, io.draw_stride = out.data_ptr(), ws.data_ptr(), ws.numel(), k
+        if draws is not None:
+            io.draws = draws.data_ptr()
+        self.lib.call("gjx_temper_predictive", plan.handle, C.byref(self._keys(kb, 1)), C.byref(io), self.stream())
+        return out.view(S, 5, D), (draws.view(S, -1, D) if draws is not None else None)
 
     def smc_config(self, impl, n_total, first, n_local, step_keys, resample_keys, ess_threshold: float = 0.0):
         """Config of a whole-run call or of the step-level entry points (`first`, `n_local`: a rank's own block).
@@ -1204,6 +1236,16 @@ class TemperPlan(PlanHandle):
         buf = C.create_string_buffer(need.value)
         self.ops.lib.call("gjx_pointwise_source", self.handle, buf, need.value, None)
         return buf.value.decode()
+
+    def predictive_compile_check(self, impl: int) -> int:
+        """gjx_predictive_compile_check (include/gjx_predictive.h): the status, not raised."""
+        self.ops.lib.require("predictive", "gjx_predictive_compile_check")
+        return self.ops.lib._gjx_predictive_compile_check(self.handle, impl)
+
+    def predictive_source(self, impl: int) -> str:
+        """The HIP source of the plan's generated predictive kernel under generator `impl`."""
+        self.ops.lib.require("predictive", "gjx_predictive_source")
+        return self._source("gjx_predictive_source", impl)
 
     def compile_check(self, impl: int) -> int:
         return self.ops.lib._gjx_temper_plan_compile_check(self.handle, impl)

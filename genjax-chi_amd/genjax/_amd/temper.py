@@ -305,6 +305,58 @@ class PointwiseLikelihood:
         return f"PointwiseLikelihood(rows={self.lppd.numel()}, n={self.n})"
 
 
+class PosteriorPredictive:
+    """Replicated data of the plated site(s) under a population of n equally weighted particles
+    (include/gjx_predictive.h): y_rep[d, i] ~ p(y | x_i, data_d), one draw per particle and data row.  Every field is a dict
+    by the plated sites' addresses, except `index`.
+
+    `mean`, `var`: the sample mean and (n - 1) variance of y_rep over the particles (zeros at n = 1); `pit` =
+    (below + 0.5 equal) / n with `below`, `equal` the particles whose draw is below / equal to the observed value — the
+    randomisation-free mid-PIT, uniform on a calibrated continuous model; `nan_count`: the draws that are NaN (a latent outside
+    its site's parameter range) — they reach `mean` and `var` as NaN and count neither as below nor as equal.  float64 [D] on
+    the device.  `pit`, `below`, `equal` are None where there is nothing observed (`TemperedSMC.predictive(args=)`).
+
+    `draws`: float32 [m, D] per address — the draws of the particles `index` (int64 [m]: 0, k, 2 k, ...) — or None when none
+    were asked for."""
+
+    FIELDS = ("s1", "s2", "below", "equal", "nan")
+
+    def __init__(self, addrs, table: torch.Tensor, n: int, draws: torch.Tensor | None = None, draw_stride: int = 0,
+                 observed: bool = True):
+        """`table`: float64 [S, 5, D] — per plated site the rows s1, s2, below, equal, nan of gjx_temper_predictive; `n`: the
+        population size; `draws`: float32 [S, m, D] with m = ceil(n / draw_stride), or None."""
+        addrs = list(addrs)
+        if table.dim() != 3 or table.shape[0] != len(addrs) or table.shape[1] != 5 or table.dtype != torch.float64:
+            raise ValueError(f"PosteriorPredictive: a float64 [{len(addrs)}, 5, D] tensor expected")
+        self.n, self.addresses = int(n), addrs
+        if self.n < 1:
+            raise ValueError("PosteriorPredictive: n >= 1")
+        k = int(draw_stride)
+        if (draws is None) != (k == 0):
+            raise ValueError("PosteriorPredictive: draws come with a draw_stride >= 1, and only with one")
+        self.mean, self.var, self.nan_count = {}, {}, {}
+        self.pit, self.below, self.equal = ({}, {}, {}) if observed else (None, None, None)
+        for s, a in enumerate(addrs):
+            s1, s2, below, equal, nan = table[s].unbind(0)
+            self.mean[a] = s1 / self.n
+            self.var[a] = (s2 - s1 * s1 / self.n) / (self.n - 1) if self.n > 1 else torch.zeros_like(s1)
+            self.nan_count[a] = nan
+            if observed:
+                self.below[a], self.equal[a] = below, equal
+                self.pit[a] = (below + 0.5 * equal) / self.n
+        self.draws, self.index = None, None
+        if draws is not None:
+            m = -(-self.n // k)
+            if draws.dim() != 3 or tuple(draws.shape) != (len(addrs), m, table.shape[2]) or draws.dtype != torch.float32:
+                raise ValueError(f"PosteriorPredictive: draws must be float32 [{len(addrs)}, {m}, {table.shape[2]}]")
+            self.draws = {a: draws[s] for s, a in enumerate(addrs)}
+            self.index = torch.arange(0, self.n, k, dtype=torch.int64, device=draws.device)
+
+    def __repr__(self):
+        D = next(iter(self.mean.values())).numel()
+        return f"PosteriorPredictive(sites={self.addresses!r}, rows={D}, n={self.n}, draws={0 if self.index is None else self.index.numel()})"
+
+
 class TemperedSMC(SMCAlgorithm):
     """Adaptive tempered SMC sampler for a static target (Neal 2001; Del Moral, Doucet & Jasra 2006; the adaptive schedule
     of Jasra et al. 2011).
@@ -531,6 +583,79 @@ class TemperedSMC(SMCAlgorithm):
         tplan.set_data([t.detach().to(device=ops.device(), dtype=torch.float32).contiguous() for t in tracer.data])
         x = [c.detach().to(device=ops.device(), dtype=torch.float32).contiguous() for c in cols]
         return PointwiseLikelihood(ops.temper_pointwise(tplan, x), x[0].numel())
+
+    # -- posterior predictive draws (include/gjx_predictive.h) ---------------------------------------------------
+    def _unobserved_target(self, st, args) -> Target:
+        """The fitted model at the arguments `args` with nothing observed at its plated sites: every plated address is
+        constrained to zeros of the data length (a tensor of its own each: the columns of the table stay those of the fitted
+        plan), every other observed address keeps the fitted constraint."""
+        if not isinstance(args, tuple):
+            raise TypeError("TemperedSMC.predictive: args must be a tuple")
+        rows = {int(a.numel()) for a in args if is_data_tensor(a)}
+        if len(rows) != 1:
+            raise PlanUnsupported(f"TemperedSMC.predictive: args must hold data columns (1-D tensors) of one length, got lengths {sorted(rows)}")
+        D = rows.pop()
+        pairs = [(m["addr"], torch.zeros(D, dtype=torch.float32) if m.get("plated") else m["obs"])
+                 for m in st["tracer"].meta if m["obs"] is not None]
+        return Target(self.target.p, args, ChoiceMap.from_mapping(pairs))
+
+    def predictive(self, res, key, target: Target | None = None, args=None, n_draws: int | None = None,
+                   draw_stride: int | None = None) -> PosteriorPredictive:
+        """Replicated data of the plated site(s) under the population `res` — a TemperedResult of `run`, or the L latent
+        columns (float32 [n]) in the plan's latent order: one draw per particle and data row in two launches, summarised per
+        row (PosteriorPredictive).  A function of the columns, the data and `key`: particle i draws under fold_in(key, i).
+
+        `target=None` replicates the rows the sampler was fitted to; a `Target` over the same model body with OTHER data
+        tensors replicates held-out rows and places their observed values among the draws; `args=` (the model's arguments,
+        new inputs) predicts where nothing is observed — no `pit`.  Same structure: the kernel comes out of the JIT cache.
+        `draw_stride=k` also returns the draws of particles 0, k, 2 k, ...; `n_draws=m` is draw_stride = ceil(n / m): at most m
+        of them, spread over the population (after resampling, neighbours are copies of one ancestor)."""
+        st = self._state()
+        ops = st["ops"]
+        ops.lib.require("predictive", "gjx_temper_predictive")
+        if target is not None and args is not None:
+            raise ValueError("TemperedSMC.predictive: target= (held-out rows) or args= (new inputs, nothing observed), not both")
+        if n_draws is not None and draw_stride is not None:
+            raise ValueError("TemperedSMC.predictive: n_draws= or draw_stride=, not both")
+        cols = list(res.columns) if isinstance(res, TemperedResult) else list(res)
+        fitted = [m["addr"] for m in st["latents"]]
+        if len(cols) != len(fitted):
+            raise ValueError(f"TemperedSMC.predictive: {len(fitted)} latent columns expected ({fitted!r}), got {len(cols)}")
+        n = int(cols[0].numel())
+        if n_draws is not None:
+            if int(n_draws) < 1:
+                raise ValueError("TemperedSMC.predictive: n_draws >= 1")
+            k = -(-n // int(n_draws))
+        elif draw_stride is not None:
+            k = int(draw_stride)
+            if k < 1:
+                raise ValueError("TemperedSMC.predictive: draw_stride >= 1")
+        else:
+            k = 0
+        if args is not None:
+            target = self._unobserved_target(st, args)
+        if target is None:
+            tracer, tplan = st["tracer"], st["tplan"]
+        else:
+            if not isinstance(target, Target):
+                raise TypeError("TemperedSMC.predictive: target must be a Target")
+            tracer = lower(target, self.n_particles)
+            theirs = [m["addr"] for m in tracer.meta if m["obs"] is None]
+            if theirs != fitted:
+                raise ValueError(f"TemperedSMC.predictive: the target's latent addresses {theirs!r} are not the fitted plan's {fitted!r}")
+            tplan = None
+        if not tracer.data:
+            raise PlanUnsupported(f"TemperedSMC.predictive: no plated site among the addresses {[m['addr'] for m in tracer.meta]!r} "
+                                  "(replicated data are those of a site observed over a data column)")
+        if tplan is None:
+            tplan = ops.temper_plan_create(tracer.sites, keep=(tracer.keep, tracer))
+        if tracer.params:
+            tplan.set_params(tracer.params)
+        tplan.set_data([t.detach().to(device=ops.device(), dtype=torch.float32).contiguous() for t in tracer.data])
+        x = [c.detach().to(device=ops.device(), dtype=torch.float32).contiguous() for c in cols]
+        table, draws = ops.temper_predictive(tplan, key, x, k)
+        addrs = [m["addr"] for m in tracer.meta if m.get("plated")]
+        return PosteriorPredictive(addrs, table, n, draws, k, observed=args is None)
 
     def log_marginal_likelihood_estimate(self, key, target: Target | None = None):
         if target is not None:
