@@ -194,6 +194,27 @@ def prior_table(tracer) -> _PriorTable:
     return _PriorTable(tracer, sites, progs, keep)
 
 
+def _reads_value_of(base, other, addr):
+    """The address of the first plated site that reads the VALUE of the plated site at `addr` — its observed column itself, or a
+    data column computed from it — or None.  `base` and `other`: two lowerings of one body over the same arguments that differ
+    in the value observed at `addr` alone: a column that is no site's observed column and differs between them was computed
+    from that value."""
+    assert len(base.sites) == len(other.sites) and len(base.data) == len(other.data)
+    observed = {s.obs.ref: m["addr"] for s, m in zip(base.sites, base.meta) if s.observed == abi.SITE_PLATED}
+    tainted = {c for c, a in observed.items() if a == addr}
+    tainted |= {c for c, (t, u) in enumerate(zip(base.data, other.data)) if c not in observed and not torch.equal(t, u)}
+    for s, m in zip(base.sites, base.meta):
+        if s.observed != abi.SITE_PLATED or m["addr"] == addr:
+            continue
+        for k in range(2):
+            a = s.arg[k]
+            cols = ({a.ref} if a.kind == abi.ARG_DATA else
+                    {ref for op, ref, _ in base.expr_progs[a.table] if op == abi.EXPR_DATA} if a.kind == abi.ARG_EXPR else set())
+            if cols & tainted:
+                return m["addr"]
+    return None
+
+
 def ladder_deltas(beta: float, lo=None, hi=None):
     """The candidates of one ladder launch, float32.  Coarse (lo is None): delta_j = (1 - beta) 2^-(G - 1 - j); fine:
     delta_k = lo + (hi - lo) k / G."""
@@ -595,9 +616,27 @@ class TemperedSMC(SMCAlgorithm):
         if len(rows) != 1:
             raise PlanUnsupported(f"TemperedSMC.predictive: args must hold data columns (1-D tensors) of one length, got lengths {sorted(rows)}")
         D = rows.pop()
-        pairs = [(m["addr"], torch.zeros(D, dtype=torch.float32) if m.get("plated") else m["obs"])
-                 for m in st["tracer"].meta if m["obs"] is not None]
-        return Target(self.target.p, args, ChoiceMap.from_mapping(pairs))
+        meta = st["tracer"].meta
+
+        def fill(one=None):
+            pairs = [(m["addr"], torch.full((D,), 1.0 if m["addr"] == one else 0.0, dtype=torch.float32) if m.get("plated") else m["obs"])
+                     for m in meta if m["obs"] is not None]
+            return Target(self.target.p, args, ChoiceMap.from_mapping(pairs))
+
+        # A plated site's value that feeds a later site is data (gjx_plate.h) — and here there is none: the fill would be read
+        # as if it had been observed.  Found by lowering with another fill at one address at a time: a later site that reads
+        # that address's column, or a column computed from it (one that changes with the fill), is refused.
+        target = fill()
+        plated = [m["addr"] for m in meta if m.get("plated")]
+        if len(plated) > 1:
+            base = lower(target, self.n_particles)
+            for addr in plated:
+                reader = _reads_value_of(base, lower(fill(addr), self.n_particles), addr)
+                if reader is not None:
+                    raise PlanUnsupported(f"TemperedSMC.predictive: args= observes nothing, but the site at address {reader!r} reads the "
+                                          f"value of the plated site at address {addr!r} (a plated site's value that feeds a later site "
+                                          "is data); pass target= with observed values instead")
+        return target
 
     def predictive(self, res, key, target: Target | None = None, args=None, n_draws: int | None = None,
                    draw_stride: int | None = None) -> PosteriorPredictive:

@@ -6,7 +6,10 @@ two data columns swapped) is in the kernel and in the replay alike.  This module
 the lowering: `evaluate64` executes the body's source text with small distribution objects of its own over torch float64
 tensors — no PlanTracer, no SymExpr, no ABI, no oracle, no kernel — and `check64` compares with a tolerance DERIVED from the
 bounds the suite already pins for the spec's arithmetic and from the f32 rounding floor of the very case, measured on the
-reference alone.  Used by tests/test_temper_fuzz_cpu.py (oracle backend) and tests/test_gpu_temper_fuzz.py (HIP backend)."""
+reference alone.  Used by tests/test_temper_fuzz_cpu.py (oracle backend) and tests/test_gpu_temper_fuzz.py (HIP backend).
+The same execution gives the LAW of every replicated draw of a plated site (include/gjx_predictive.h): `predictive_laws` holds
+the draws of the predictive replay and kernels to it, at ssm_fuzz's derived bounds (tests/test_predictive_fuzz_cpu.py,
+tests/test_gpu_predictive_fuzz.py)."""
 
 import math
 import re
@@ -194,6 +197,7 @@ class Evaluation:
         self.lp, self.ll = torch.zeros(n, dtype=dtype), torch.zeros(n, dtype=dtype)
         self.tol_lp, self.tol_ll = np.zeros(n), np.zeros(n)
         self.tables, self.tol_tables, self.pit, self.order = {}, {}, {}, []
+        self.laws, self.kinds = {}, {}  # plated address: (kind, float64 arguments [n, D]); latent address: kind
 
     def terms(self):
         """[D, n]: the f32 sum, in table order, of the plated sites' tables (pointwise_ref.terms' composition), and the sum of
@@ -213,7 +217,10 @@ def evaluate64(source, latents, observed, args, dtype=torch.float64):
     looks its value up — a latent column as [n, 1], a scalar, a data column as [1, D] — adds its log-density (torch.distributions
     in `dtype`; Bernoulli as log p / log1p(-p)) to lp or ll, and returns the value.  The support rule of include/gjx_temper.h
     is restated: a latent Gamma value <= 0 or a Beta value outside (0, 1) gives the term -inf.  A distribution argument outside
-    its domain (scale, shape, rate <= 0, p outside [0, 1]) makes the reference NaN there: no truth to compare with."""
+    its domain (scale, shape, rate <= 0, p outside [0, 1]) makes the reference NaN there: no truth to compare with.
+    Per plated address `laws` keeps the site's kind and its arguments broadcast to [n, D]: the law of the replicated draw
+    y_rep[d, i] of include/gjx_predictive.h.  That header's SHADOW rule is restated by what `@` returns: a plated site that reads
+    an earlier plated site's value reads the OBSERVED column (the value returned here), never that site's replicated draw."""
     import torch.distributions as TD
 
     n = len(next(iter(latents.values())))
@@ -255,6 +262,10 @@ def evaluate64(source, latents, observed, args, dtype=torch.float64):
             tol = (normal_tolerance(xs_, *as_) if kind == "normal" else gamma_tolerance(xs_, *as_) if kind == "gamma" else
                    beta_tolerance(xs_, *as_) if kind == "beta" else bernoulli_tolerance(lp.numpy()))
             tol = np.nan_to_num(np.broadcast_to(tol, shape).astype(np.float64), nan=0.0, posinf=0.0, neginf=0.0)
+        if role == "latent":
+            ev.kinds[addr] = kind
+        elif role == "plated":
+            ev.laws[addr] = (kind, [np.broadcast_to(v.to(torch.float64).numpy(), shape) for v in a[:1 if kind == "flip" else 2]])
         if role == "latent":
             ev.lp = ev.lp + lp[:, 0]
             if want_tol:
@@ -352,6 +363,161 @@ def check64(got, source=None, latents=None, observed=None, args=None, what="ll",
         raise AssertionError(f"{what}: {int(bad.sum())} of {bad.size} entries miss the float64 reference; at {k}: got {got[k]!r}, "
                              f"reference {r[k]!r}, tol {tol[k]:.3g} (f32 floor {ref.floor[what]:.3g})\n{context}")
     return float(ratio.max()) if ratio.size else 0.0
+
+
+# ---- the law of every replicated draw (include/gjx_predictive.h) -------------------------------------------------------------
+LAW_MIN_SHARE = 0.9         # of a site's (live particle, row) entries must have a float64 law to be compared with
+LAW_MIN_DRAWS = 16384       # below this many draws per site the DKW bound (0.021 there) is too loose to mean anything
+
+
+def _law_domain(kind, a):
+    """bool [n, D]: the float64 arguments are finite and inside the domain on which the law below is defined (a flip with p of
+    exactly 0 or 1 has no standardised residual)."""
+    with np.errstate(invalid="ignore"):
+        fin = np.all([np.isfinite(v) for v in a], axis=0)
+        if kind == "normal":
+            return fin & (a[1] > 0)
+        if kind in ("gamma", "beta"):
+            return fin & (a[0] > 0) & (a[1] > 0)
+        return fin & (a[0] > 0) & (a[0] < 1)
+
+
+def law_coverage(source, latents, observed, args, ev=None):
+    """-> ({plated address: (kind, float64 arguments [n, D], bool [n, D] entries with a truth)}, live bool [n], reasons): an
+    entry has a truth when its particle lies inside the support of every latent (`inside`) and the site's float64 arguments,
+    from the source text, are finite and in their domain.  `reasons` names every site with a truth on less than
+    LAW_MIN_SHARE of its live entries: such a case leaves a generator's stream (as Reference.reasons does for the densities)."""
+    ev = evaluate64(source, latents, observed, args) if ev is None else ev
+    live = inside([(k, "latent", v) for k, v in ev.kinds.items()], latents)
+    out, reasons = {}, []
+    for addr, (kind, a) in ev.laws.items():
+        ok = _law_domain(kind, a) & live[:, None]
+        share = ok.sum() / max(1, live.sum() * ok.shape[1])
+        if share < LAW_MIN_SHARE:
+            reasons.append(f"law of {addr!r} ({kind}): arguments in their domain on {share:.2f} of the live entries")
+        out[addr] = (kind, a, ok)
+    return out, live, reasons
+
+
+def predictive_laws(source, latents, observed, args, draws):
+    """`draws` {plated address: f32 [n, D]}, y_rep[d, i] as [i, d] — of the replay or of the kernel — against the law the
+    body's SOURCE TEXT gives that address at (particle i, row d): -> samples for ssm_fuzz.check_laws, whose bounds are derived
+    (DKW at alpha = 1e-6 for a PIT, 5 standard errors for a summed residual).  Per kind:
+      Normal, Gamma  the probability-integral transform of each draw under its own float64 parameters (ssm_fuzz._law);
+      Beta           the PIT through scipy.special.betainc where scipy is importable (exchanged shapes a ~ b move the mean
+                     residual by nothing, the PIT by much), otherwise ssm_fuzz._law's standardised residual;
+      flip           the standardised residual r = (y - p) / sqrt(p (1 - p)).
+    A marginal law is blind to an error that averages to nothing over the case (a probability or a location read from the wrong
+    column of symmetric data; exchanged arguments a ~ b).  So every site is also held CONDITIONALLY: with r the standardised
+    residual (of a PIT u: sqrt(12) (u - 1/2), mean 0 and variance 1 under the law) and w a covariate centred and scaled to unit
+    mean square over the compared entries, sum r_i w_i / sqrt(N) is as standard as sum r_i / sqrt(N), whatever w is as long as
+    it is fixed before the draw — the same 5 standard errors bound it.  Covariates, under the key (address, name): the site's
+    own float64 arguments ("arg0", "arg1"; a flip's as its logit), every latent column ("latent", address), every data
+    argument of the body ("data", position) and every observed float column ("observed", address).
+    Entries without a truth (law_coverage) are left out; at least LAW_MIN_SHARE of a site's live entries must remain."""
+    import ssm_fuzz as S
+
+    cover, _, reasons = law_coverage(source, latents, observed, args)
+    assert not reasons, reasons
+    try:
+        from scipy.special import betainc
+    except ImportError:  # pragma: no cover - the CPU tests of this repository import scipy
+        betainc = None
+    n = len(next(iter(latents.values())))
+    wide = [(("latent", k), np.asarray(v, dtype=np.float64).reshape(n, 1)) for k, v in latents.items()]
+    wide += [(("data", k), np.asarray(v, dtype=np.float64).reshape(1, -1)) for k, v in enumerate(args) if np.ndim(v) == 1]
+    wide += [(("observed", k), np.asarray(v, dtype=np.float64).reshape(1, -1)) for k, v in observed.items()
+             if np.ndim(v) == 1 and np.asarray(v).dtype != bool]
+    out = {}
+    for addr, y in draws.items():
+        kind, a64, ok = cover[addr]
+        y = np.asarray(y, dtype=np.float32).astype(np.float64)
+        assert y.shape == ok.shape, (addr, y.shape, ok.shape)
+        x, a = torch.from_numpy(y[ok]), [torch.from_numpy(np.ascontiguousarray(v[ok])) for v in a64]
+        nan = np.where(np.isnan(x.numpy()), np.nan, 0.0)  # (a NaN draw where a truth exists fails check_laws)
+        if kind == "beta" and betainc is not None:
+            law, v = "pit", betainc(a[0].numpy(), a[1].numpy(), np.clip(x.numpy(), 0.0, 1.0))
+        else:
+            law, v = S._law(kind, a, x)
+            v = v.numpy()
+        out[addr] = (law, v + nan)
+        r = (math.sqrt(12.0) * (v - 0.5) if law == "pit" else v) + nan
+        with np.errstate(invalid="ignore", divide="ignore"):
+            own = [np.log(a64[0]) - np.log1p(-a64[0])] if kind == "flip" else list(a64)
+            covs = [((f"arg{k}",), np.broadcast_to(w, ok.shape)[ok]) for k, w in enumerate(own)]
+        covs += [(name, np.broadcast_to(w, ok.shape)[ok]) for name, w in wide if name != ("observed", addr)]
+        for name, w in covs:
+            w = w - w.mean()
+            ms = float(np.mean(w * w))
+            if np.isfinite(ms) and ms > 1e-24 * max(1.0, float(np.max(np.abs(w))) ** 2):
+                out[(addr,) + name] = ("z", r * w / math.sqrt(ms))
+    return out
+
+
+def check_predictive(source, latents, observed, args, draws, context=""):
+    """predictive_laws through ssm_fuzz.check_laws -> its worst ratios."""
+    import ssm_fuzz as S
+
+    return S.check_laws(predictive_laws(source, latents, observed, args, draws), context)
+
+
+def draws_by_address(addrs, y):
+    """Draws [S, n, D] in table order (the kernel's layout; the replay's y [S, D, n] transposed) -> {address: [n, D]}."""
+    assert len(addrs) == len(y)
+    return {a: np.asarray(y[s]) for s, a in enumerate(addrs)}
+
+
+# ---- the predictive cases of tests/test_predictive_fuzz_cpu.py and tests/test_gpu_predictive_fuzz.py --------------------------
+# ONE definition of the seeds, sizes, inputs and populations: the CPU suite proves them admissible on the replay (the laws hold,
+# the coverage is there), the GPU suite compares the kernel on the very same numbers.  Keys: genjax.random.key(PRED_KEY + ., impl).
+PRED_DS = (1, 2, 3, 127, 129, 513)   # a lone row, a pair, an odd tail behind a pair, both sides of a wave's 128 rows, one past a tile
+PRED_NS = (1, 5, 257)
+PRED_BIG = (1000, 129)               # W = 4 chunks
+PRED_OUTSIDE = (257, 65)
+PRED_API = (300, 65, 33)             # n, the fitted rows, the held-out rows
+PRED_SEEDS = (41, 42, 43, 44)
+PRED_PER_SEED = 25                   # generated bodies per seed on the CPU; the GPU suite takes the first kept ones of each stream
+PRED_RANDOM = (257, (65, 2))         # n and the two row counts of a random body: 257 * 65 = 16705 >= LAW_MIN_DRAWS
+PRED_KEY = 5100
+
+
+def interleaved_inputs():
+    """(args, observed) of INTERLEAVED over max(PRED_DS) rows; a case of D rows reads the first D."""
+    return random_inputs(np.random.default_rng(77), INTERLEAVED_SITES, max(PRED_DS))
+
+
+def heldout_inputs():
+    """(args, observed) of INTERLEAVED over PRED_API[2] OTHER rows."""
+    return random_inputs(np.random.default_rng(78), INTERLEAVED_SITES, PRED_API[2])
+
+
+def head_rows(args, obs, D):
+    """The first D rows of a case's columns."""
+    cut = lambda v: v[:D] if isinstance(v, np.ndarray) else v  # noqa: E731
+    return tuple(cut(a) for a in args), {k: cut(v) for k, v in obs.items()}
+
+
+def interleaved_latents(what, n):
+    """The population of one interleaved case: `what` a row count of the grid, "big", "outside", "api"."""
+    seed = 3100 + what if isinstance(what, int) else {"big": 3001, "outside": 3002, "api": 3003}[what]
+    return latent_columns(np.random.default_rng(seed), INTERLEAVED_SITES, n, outside=what == "outside")
+
+
+def predictive_stream(seed, count=PRED_PER_SEED):
+    """The first `count` bodies of a seed's stream: (index, source, sites, args, observed, latents, reasons) — inputs of
+    max(PRED_RANDOM[1]) rows, a population of PRED_RANDOM[0].  `reasons`, from the reference alone: empty for a body the
+    predictive suites compare, else why not ("no plated site", or law_coverage's at the larger row count)."""
+    n, (D, _) = PRED_RANDOM
+    rng = np.random.default_rng(seed)
+    for i in range(count):
+        src, sites = random_tempered_model(rng)
+        args, obs = random_inputs(rng, sites, D)
+        latents = latent_columns(rng, sites, n)
+        if not any(role == "plated" for _, role, _ in sites):
+            reasons = ["no plated site"]
+        else:
+            reasons = law_coverage(src, latents, obs, args)[2]
+        yield i, src, sites, args, obs, latents, reasons
 
 
 # ---- the project's side of a case (the only part that imports the package) ------------------------------------------------
