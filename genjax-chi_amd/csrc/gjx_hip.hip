@@ -4819,6 +4819,11 @@ int gjx_backmove_run(gjx_backsim_plan* p, const gjx_backmove_io* io, void* ws, s
 // Tempered SMC for static models (include/gjx_temper.h): the move kernel is generated from the site table
 // (gjx_plan_jit.hpp GenTemper); the ESS ladder is the fixed kernel below
 // =====================================================================================================================
+// The four generated kernels of a tempered plan: the move (include/gjx_temper.h), the covariance move
+// (include/gjx_temper_cov.h), the pointwise kernel (include/gjx_pointwise.h: one source, whatever the generator) and the
+// predictive kernel (include/gjx_predictive.h).  The last two exist for a plan that passes pointwise_plan_ok only
+// (kTemperKernels below has what else they differ in).
+enum TemperKernel { kTemperMove, kTemperCovMove, kTemperPointwise, kTemperPredictive, kTemperKernelCount };
 struct gjx_temper_plan {
   int n_sites, n_latents;
   int n_params;   // values set by gjx_temper_plan_set_params
@@ -4829,8 +4834,7 @@ struct gjx_temper_plan {
   ExprStore expr;
   std::vector<void*> dev_owned;  // per-row tables of categorical (observed) sites
   std::mutex mu;
-  gjx_jit::CompiledTemper jit[2];
-  gjx_jit::CompiledTemper cov_jit[2];  // include/gjx_temper_cov.h: the covariance move kernel, per generator
+  gjx_jit::CompiledKernel jit[kTemperKernelCount][2];  // by TemperKernel and generator (the pointwise kernel: [0] alone)
   // include/gjx_plate.h: PLATED sites (gjx_temper_plan_create_plated) and their data columns (gjx_temper_plan_set_data)
   bool plated = false;
   int max_data = -1;  // highest data column the table reads
@@ -4840,32 +4844,62 @@ struct gjx_temper_plan {
     gjx_expr_op ops[GJX_MAX_SITES][GJX_MAX_EXPR_OPS];
   };
   ObsExprStore* obs_expr = nullptr;  // the programs of PLATED sites' observed values (a plan's own copy, as ExprStore)
-  gjx_jit::CompiledPointwise pw;     // include/gjx_pointwise.h: the pointwise kernel (one source, whatever the generator)
-  gjx_jit::CompiledPredictive pred[2];  // include/gjx_predictive.h: the predictive kernel, per generator
   ~gjx_temper_plan() { delete obs_expr; }
 };
 
 namespace {
 constexpr unsigned kTemperMaxGrid = 256 * 16;  // workgroups of 256 particles, grid-stride beyond
 
-std::string temper_source(const gjx_temper_plan* p, int impl, PlanTables* tabs = nullptr, bool cov = false) {
+// What the four generated kernels of a tempered plan (TemperKernel) differ in on the host side.
+struct TemperKernelDesc {
+  const char* entry;
+  gjx_jit::PlanKind kind;
+  bool per_impl;     // a source and a slot per generator
+  bool plated_only;  // refused (GJX_ERR_INVALID) without a PLATED site or with a per-particle input column
+};
+constexpr TemperKernelDesc kTemperKernels[kTemperKernelCount] = {{"gjx_temper_move_kernel", gjx_jit::PlanKind::temper, true, false},
+                                                {"gjx_temper_move_cov_kernel", gjx_jit::PlanKind::temper, true, false},
+                                                {"gjx_pointwise_kernel", gjx_jit::PlanKind::temper, false, true},
+                                                {"gjx_predictive_kernel", gjx_jit::PlanKind::predictive, true, true}};
+// Has the plan a pointwise (and a predictive) source?  A PLATED site, and no per-particle input column anywhere in the table
+// (the io structs have none).
+bool pointwise_plan_ok(const gjx_temper_plan* p) { return p && p->plated && p->max_input < 0; }
+// the guard of the exported *_source / *_compile_check functions of kernel k
+bool temper_kernel_ok(const gjx_temper_plan* p, TemperKernel k, int impl) {
+  const TemperKernelDesc& d = kTemperKernels[k];
+  return p && (!d.plated_only || pointwise_plan_ok(p)) && (!d.per_impl || impl == 0 || impl == 1);
+}
+std::string temper_source(const gjx_temper_plan* p, TemperKernel k, int impl, PlanTables* tabs = nullptr) {
+  auto run = [&](auto& g) {
+    g.sites = p->sites; g.n_sites = p->n_sites;
+    return gjx_jit::generated_source(g, tabs);
+  };
+  if (k == kTemperPointwise) {
+    gjx_jit::GenPointwise<CSite, CArg> g;
+    return run(g);
+  }
+  if (k == kTemperPredictive) {
+    gjx_jit::GenPredictive<CSite, CArg> g;
+    g.impl = impl;
+    return run(g);
+  }
   gjx_jit::GenTemper<CSite, CArg> g;
-  g.impl = impl; g.sites = p->sites; g.n_sites = p->n_sites; g.cov = cov;
-  return gjx_jit::generated_source(g, tabs);
+  g.impl = impl; g.cov = k == kTemperCovMove;
+  return run(g);
 }
-
-gjx_jit::CompiledTemper* temper_compiled(gjx_temper_plan* p, int impl) {
-  gjx_jit::CompiledTemper& c = p->jit[impl];
-  const bool ready = compiled_once(p->mu, c, {{p->sites, p->n_sites}}, &p->dev_owned, [&] {
-    return c.load(temper_source(p, impl, &c.tabs), gjx_jit::PlanKind::temper, {"gjx_temper_move_kernel"}, {&c.move});
-  });
-  return ready ? &c : nullptr;
+int temper_source_out(const gjx_temper_plan* p, TemperKernel k, int impl, char* buf, size_t buf_len, size_t* needed) {
+  if (!temper_kernel_ok(p, k, impl)) return GJX_ERR_INVALID;
+  return copy_source_out(temper_source(p, k, impl), buf, buf_len, needed);
 }
-gjx_jit::CompiledTemper* temper_cov_compiled(gjx_temper_plan* p, int impl) {
-  gjx_jit::CompiledTemper& c = p->cov_jit[impl];
-  const bool ready = compiled_once(p->mu, c, {{p->sites, p->n_sites}}, &p->dev_owned, [&] {
-    return c.load(temper_source(p, impl, &c.tabs, true), gjx_jit::PlanKind::temper, {"gjx_temper_move_cov_kernel"}, {&c.move});
-  });
+int temper_compile_check(const gjx_temper_plan* p, TemperKernel k, int impl) {
+  if (!temper_kernel_ok(p, k, impl)) return GJX_ERR_INVALID;
+  return gjx_jit::compile_only(temper_source(p, k, impl), kTemperKernels[k].kind) ? GJX_OK : GJX_ERR_UNSUPPORTED;
+}
+gjx_jit::CompiledKernel* temper_compiled(gjx_temper_plan* p, TemperKernel k, int impl) {
+  const TemperKernelDesc& d = kTemperKernels[k];
+  gjx_jit::CompiledKernel& c = p->jit[k][d.per_impl ? impl : 0];
+  const bool ready = compiled_once(p->mu, c, {{p->sites, p->n_sites}}, &p->dev_owned,
+                                   [&] { return c.load(temper_source(p, k, impl, &c.tabs), d.kind, {d.entry}, {&c.fn}); });
   return ready ? &c : nullptr;
 }
 
@@ -5235,20 +5269,6 @@ __global__ __launch_bounds__(kBlock) void k_temper_moments(MomentsArgs a) {
 
 // ---- pointwise predictive densities over a plated plan (include/gjx_pointwise.h) -----------------------------------------
 constexpr uint64_t kPointwiseWorkgroups = 2048;  // tiles of 256 rows x chunks of particles: about this many, whatever D is
-// Has the plan a pointwise source?  A PLATED site, and no per-particle input column anywhere in the table (the io has none).
-bool pointwise_plan_ok(const gjx_temper_plan* p) { return p && p->plated && p->max_input < 0; }
-std::string pointwise_source(const gjx_temper_plan* p, PlanTables* tabs = nullptr) {
-  gjx_jit::GenPointwise<CSite, CArg> g;
-  g.sites = p->sites; g.n_sites = p->n_sites;
-  return gjx_jit::generated_source(g, tabs);
-}
-gjx_jit::CompiledPointwise* pointwise_compiled(gjx_temper_plan* p) {
-  gjx_jit::CompiledPointwise& c = p->pw;
-  const bool ready = compiled_once(p->mu, c, {{p->sites, p->n_sites}}, &p->dev_owned, [&] {
-    return c.load(pointwise_source(p, &c.tabs), gjx_jit::PlanKind::temper, {"gjx_pointwise_kernel"}, {&c.fn});
-  });
-  return ready ? &c : nullptr;
-}
 // the second launch: one lane per row folds the chunks' partials in chunk order (gjx_device.hpp pointwise_fold)
 __global__ __launch_bounds__(kBlock) void k_pointwise_fold(const double* part, uint32_t W, uint32_t n_rows, double* out) {
 #if defined(__HIP_DEVICE_COMPILE__)  // (the header's device-only section)
@@ -5260,23 +5280,10 @@ __global__ __launch_bounds__(kBlock) void k_pointwise_fold(const double* part, u
 // ---- posterior predictive draws over a plated plan (include/gjx_predictive.h) --------------------------------------------
 constexpr uint64_t kPredictiveWorkgroups = 2048;  // tiles of 512 rows x chunks of particles: about this many, whatever D is
 constexpr uint64_t kPredictiveTile = 2 * kBlock;  // rows per workgroup: two per lane
-// Has the plan a predictive source?  What a pointwise source needs: a PLATED site and no per-particle input column.
 int predictive_n_plated(const gjx_temper_plan* p) {
   int S = 0;
   for (int q = 0; q < p->n_sites; ++q) S += p->sites[q].observed == GJX_SITE_PLATED ? 1 : 0;
   return S;
-}
-std::string predictive_source(const gjx_temper_plan* p, int impl, PlanTables* tabs = nullptr) {
-  gjx_jit::GenPredictive<CSite, CArg> g;
-  g.impl = impl; g.sites = p->sites; g.n_sites = p->n_sites;
-  return gjx_jit::generated_source(g, tabs);
-}
-gjx_jit::CompiledPredictive* predictive_compiled(gjx_temper_plan* p, int impl) {
-  gjx_jit::CompiledPredictive& c = p->pred[impl];
-  const bool ready = compiled_once(p->mu, c, {{p->sites, p->n_sites}}, &p->dev_owned, [&] {
-    return c.load(predictive_source(p, impl, &c.tabs), gjx_jit::PlanKind::predictive, {"gjx_predictive_kernel"}, {&c.fn});
-  });
-  return ready ? &c : nullptr;
 }
 // the second launch: one lane per row (x) and plated site (y) folds the chunks' partials in chunk order (gjx_device.hpp predictive_fold)
 __global__ __launch_bounds__(kBlock) void k_predictive_fold(const double* part, uint32_t W, uint32_t n_rows, double* out) {
@@ -5359,10 +5366,8 @@ int gjx_temper_plan_set_data(gjx_temper_plan* p, const float* const* cols, int n
 }
 int gjx_temper_plan_destroy(gjx_temper_plan* p) {
   if (!p) return GJX_OK;
-  for (auto& c : p->jit) c.release();
-  for (auto& c : p->cov_jit) c.release();
-  p->pw.release();
-  for (auto& c : p->pred) c.release();
+  for (auto& slots : p->jit)
+    for (auto& c : slots) c.release();
   free_owned(p->dev_owned);
   delete p;
   return GJX_OK;
@@ -5376,13 +5381,9 @@ int gjx_temper_plan_set_params(gjx_temper_plan* p, const float* params, int n_pa
 }
 int gjx_temper_plan_n_latents(const gjx_temper_plan* p) { return p ? p->n_latents : GJX_ERR_INVALID; }
 int gjx_temper_plan_source(const gjx_temper_plan* p, int impl, char* buf, size_t buf_len, size_t* needed) {
-  if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
-  return copy_source_out(temper_source(p, impl), buf, buf_len, needed);
+  return temper_source_out(p, kTemperMove, impl, buf, buf_len, needed);
 }
-int gjx_temper_plan_compile_check(const gjx_temper_plan* p, int impl) {
-  if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
-  return gjx_jit::compile_only(temper_source(p, impl), gjx_jit::PlanKind::temper) ? GJX_OK : GJX_ERR_UNSUPPORTED;
-}
+int gjx_temper_plan_compile_check(const gjx_temper_plan* p, int impl) { return temper_compile_check(p, kTemperMove, impl); }
 }  // extern "C"
 namespace {
 // gjx_temper_move (factor == nullptr, cov == false) and gjx_temper_move_cov (include/gjx_temper_cov.h: scales are not read)
@@ -5410,7 +5411,7 @@ int temper_move(gjx_temper_plan* p, const gjx_temper_io* io, bool cov, const flo
     cols.in[c] = io->input_cols[c];
   }
   if (!gjx_jit::enabled()) return GJX_ERR_UNSUPPORTED;  // a generated kernel only
-  gjx_jit::CompiledTemper* k = cov ? temper_cov_compiled(p, io->impl) : temper_compiled(p, io->impl);
+  gjx_jit::CompiledKernel* k = temper_compiled(p, cov ? kTemperCovMove : kTemperMove, io->impl);
   if (!k) return GJX_ERR_JIT;
   A.lp_in = io->lp_in; A.ll_in = io->ll_in; A.lp_out = io->lp_out; A.ll_out = io->ll_out;
   A.anc = io->ancestors; A.n_accept = io->n_accept;
@@ -5427,7 +5428,47 @@ int temper_move(gjx_temper_plan* p, const gjx_temper_io* io, bool cov, const flo
   PlateData pd = p->data;
   void* args[] = {&A, &cols, &prm, &tabs, &pd};  // (the kernel of a plan without plated sites takes the first four)
   void* cov_args[] = {&A, &cols, &prm, &tabs, &factor, &pd};
-  return launch_generated(k->move, grid, 1, kBlock, s, cov ? cov_args : args);
+  return launch_generated(k->fn, grid, 1, kBlock, s, cov ? cov_args : args);
+}
+
+// The chunks of particles of a launch whose lanes are data rows (gjx_pointwise_chunks, gjx_predictive_chunks): workgroups of
+// `tile` rows x chunks, about `target` workgroups whatever n_rows is, and no chunk of fewer than 256 particles.
+uint32_t plated_chunks(uint64_t n, uint64_t n_rows, uint64_t tile, uint64_t target) {
+  if (n < 1 || n >= (1ull << 31) || n_rows < 1 || n_rows >= (1ull << 31)) return 0;
+  const uint64_t tiles = (n_rows + tile - 1) / tile, by_n = nrows_of(n);
+  const uint64_t by_grid = (target + tiles - 1) / tiles;  // (>= 1)
+  return (uint32_t)(by_n < by_grid ? by_n : by_grid);
+}
+// What gjx_temper_pointwise and gjx_temper_predictive share, up to and with the first launch: kernel k of the plan over the
+// rows x chunks grid, its argument block A (PointwiseArgs / PredictiveArgs: x, part, n, W, per are filled here, `fill` adds
+// the entry point's own fields).  `ok`: the entry point's own conditions (checked with the common ones: GJX_ERR_INVALID);
+// `planes`: float64 planes of [W][n_rows] in the workspace.  The checks run in the order INVALID, WORKSPACE, UNSUPPORTED, JIT.
+template <class Args, class IO, class Fill>
+int plated_launch(gjx_temper_plan* p, TemperKernel k, int impl, const IO* io, bool ok, uint64_t tile, uint64_t target, size_t planes,
+                  gjx_stream s, Args& A, Fill fill) {
+  if (!pointwise_plan_ok(p) || !io || !ok || !p->has_data || io->n < 1 || io->n >= (1ull << 31) || !io->out || p->n_params <= p->max_param ||
+      ((uintptr_t)io->ws & 7) != 0)
+    return GJX_ERR_INVALID;
+  memset(&A, 0, sizeof A);
+  for (int l = 0; l < p->n_latents; ++l) {
+    if (!io->x[l]) return GJX_ERR_INVALID;
+    A.x[l] = io->x[l];
+  }
+  const uint32_t D = p->data.n_rows, W = plated_chunks(io->n, D, tile, target);
+  if (!io->ws || io->ws_bytes < (size_t)W * (size_t)D * planes * sizeof(double)) return GJX_ERR_WORKSPACE;
+  if (!gjx_jit::enabled()) return GJX_ERR_UNSUPPORTED;  // a generated kernel only
+  gjx_jit::CompiledKernel* c = temper_compiled(p, k, impl);
+  if (!c) return GJX_ERR_JIT;
+  A.part = static_cast<double*>(io->ws);
+  A.n = (uint32_t)io->n;
+  A.W = W;
+  A.per = (uint32_t)((io->n + W - 1) / W);
+  fill(A);
+  PlanParams prm = p->prm;
+  PlanTables tabs = c->tabs;
+  PlateData pd = p->data;
+  void* args[] = {&A, &prm, &tabs, &pd};
+  return launch_generated(c->fn, (D + tile - 1) / tile, W, kBlock, s, args);
 }
 }  // namespace
 extern "C" {
@@ -5511,118 +5552,57 @@ int gjx_temper_move_cov(gjx_temper_plan* p, const gjx_temper_io* io, const float
   return temper_move(p, io, true, factor, s);
 }
 int gjx_temper_cov_source(const gjx_temper_plan* p, int impl, char* buf, size_t buf_len, size_t* needed) {
-  if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
-  return copy_source_out(temper_source(p, impl, nullptr, true), buf, buf_len, needed);
+  return temper_source_out(p, kTemperCovMove, impl, buf, buf_len, needed);
 }
-int gjx_temper_cov_compile_check(const gjx_temper_plan* p, int impl) {
-  if (!p || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
-  return gjx_jit::compile_only(temper_source(p, impl, nullptr, true), gjx_jit::PlanKind::temper) ? GJX_OK : GJX_ERR_UNSUPPORTED;
-}
+int gjx_temper_cov_compile_check(const gjx_temper_plan* p, int impl) { return temper_compile_check(p, kTemperCovMove, impl); }
 
 int gjx_pointwise_version(int* major, int* minor) {
   return version_out(major, minor, GJX_POINTWISE_VERSION_MAJOR, GJX_POINTWISE_VERSION_MINOR);
 }
-uint32_t gjx_pointwise_chunks(uint64_t n, uint64_t n_rows) {
-  if (n < 1 || n >= (1ull << 31) || n_rows < 1 || n_rows >= (1ull << 31)) return 0;
-  const uint64_t tiles = nrows_of(n_rows), by_n = nrows_of(n);
-  const uint64_t by_grid = (kPointwiseWorkgroups + tiles - 1) / tiles;  // (>= 1)
-  return (uint32_t)(by_n < by_grid ? by_n : by_grid);
-}
+uint32_t gjx_pointwise_chunks(uint64_t n, uint64_t n_rows) { return plated_chunks(n, n_rows, kBlock, kPointwiseWorkgroups); }
 size_t gjx_pointwise_workspace_bytes(uint64_t n, uint64_t n_rows) {
   return (size_t)gjx_pointwise_chunks(n, n_rows) * (size_t)n_rows * 5 * sizeof(double);
 }
 int gjx_pointwise_source(const gjx_temper_plan* p, char* buf, size_t buf_len, size_t* needed) {
-  if (!pointwise_plan_ok(p)) return GJX_ERR_INVALID;
-  return copy_source_out(pointwise_source(p), buf, buf_len, needed);
+  return temper_source_out(p, kTemperPointwise, 0, buf, buf_len, needed);
 }
-int gjx_pointwise_compile_check(const gjx_temper_plan* p) {
-  if (!pointwise_plan_ok(p)) return GJX_ERR_INVALID;
-  return gjx_jit::compile_only(pointwise_source(p), gjx_jit::PlanKind::temper) ? GJX_OK : GJX_ERR_UNSUPPORTED;
-}
+int gjx_pointwise_compile_check(const gjx_temper_plan* p) { return temper_compile_check(p, kTemperPointwise, 0); }
 int gjx_temper_pointwise(gjx_temper_plan* p, const gjx_pointwise_io* io, gjx_stream s) {
-  if (!pointwise_plan_ok(p) || !io || !p->has_data || io->n < 1 || io->n >= (1ull << 31) || !io->out || p->n_params <= p->max_param ||
-      ((uintptr_t)io->ws & 7) != 0)
-    return GJX_ERR_INVALID;
   PointwiseArgs A;
-  memset(&A, 0, sizeof A);
-  for (int l = 0; l < p->n_latents; ++l) {
-    if (!io->x[l]) return GJX_ERR_INVALID;
-    A.x[l] = io->x[l];
-  }
-  const uint32_t D = p->data.n_rows, W = gjx_pointwise_chunks(io->n, D);
-  if (!io->ws || io->ws_bytes < gjx_pointwise_workspace_bytes(io->n, D)) return GJX_ERR_WORKSPACE;
-  if (!gjx_jit::enabled()) return GJX_ERR_UNSUPPORTED;  // a generated kernel only
-  gjx_jit::CompiledPointwise* k = pointwise_compiled(p);
-  if (!k) return GJX_ERR_JIT;
-  A.part = static_cast<double*>(io->ws);
-  A.n = (uint32_t)io->n;
-  A.W = W;
-  A.per = (uint32_t)((io->n + W - 1) / W);
-  PlanParams prm = p->prm;
-  PlanTables tabs = k->tabs;
-  PlateData pd = p->data;
-  void* args[] = {&A, &prm, &tabs, &pd};
-  const uint64_t tiles = nrows_of(D);
-  if (int rc = launch_generated(k->fn, tiles, W, kBlock, s, args)) return rc;
-  k_pointwise_fold<<<(unsigned)tiles, kBlock, 0, S(s)>>>(A.part, W, D, io->out);
+  if (int rc = plated_launch(p, kTemperPointwise, 0, io, true, kBlock, kPointwiseWorkgroups, 5, s, A, [](PointwiseArgs&) {})) return rc;
+  const uint32_t D = p->data.n_rows;
+  k_pointwise_fold<<<(unsigned)nrows_of(D), kBlock, 0, S(s)>>>(A.part, A.W, D, io->out);
   return launch_status();
 }
 
 int gjx_predictive_version(int* major, int* minor) {
   return version_out(major, minor, GJX_PREDICTIVE_VERSION_MAJOR, GJX_PREDICTIVE_VERSION_MINOR);
 }
-uint32_t gjx_predictive_chunks(uint64_t n, uint64_t n_rows) {
-  if (n < 1 || n >= (1ull << 31) || n_rows < 1 || n_rows >= (1ull << 31)) return 0;
-  const uint64_t tiles = (n_rows + kPredictiveTile - 1) / kPredictiveTile, by_n = nrows_of(n);
-  const uint64_t by_grid = (kPredictiveWorkgroups + tiles - 1) / tiles;  // (>= 1)
-  return (uint32_t)(by_n < by_grid ? by_n : by_grid);
-}
+uint32_t gjx_predictive_chunks(uint64_t n, uint64_t n_rows) { return plated_chunks(n, n_rows, kPredictiveTile, kPredictiveWorkgroups); }
 size_t gjx_predictive_workspace_bytes(uint64_t n, uint64_t n_rows, int32_t n_plated) {
   if (n_plated < 1 || n_plated > GJX_MAX_SITES) return 0;
   return (size_t)gjx_predictive_chunks(n, n_rows) * (size_t)n_rows * (size_t)n_plated * 5 * sizeof(double);
 }
 int gjx_predictive_source(const gjx_temper_plan* p, int impl, char* buf, size_t buf_len, size_t* needed) {
-  if (!pointwise_plan_ok(p) || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
-  return copy_source_out(predictive_source(p, impl), buf, buf_len, needed);
+  return temper_source_out(p, kTemperPredictive, impl, buf, buf_len, needed);
 }
-int gjx_predictive_compile_check(const gjx_temper_plan* p, int impl) {
-  if (!pointwise_plan_ok(p) || (impl != 0 && impl != 1)) return GJX_ERR_INVALID;
-  return gjx_jit::compile_only(predictive_source(p, impl), gjx_jit::PlanKind::predictive) ? GJX_OK : GJX_ERR_UNSUPPORTED;
-}
+int gjx_predictive_compile_check(const gjx_temper_plan* p, int impl) { return temper_compile_check(p, kTemperPredictive, impl); }
 int gjx_temper_predictive(gjx_temper_plan* p, const gjx_keys* key, const gjx_predictive_io* io, gjx_stream s) {
   // (ONE literal key: its fold_in children are the particles' pass keys; a batch or a stream fold has no meaning here)
-  if (!pointwise_plan_ok(p) || !io || !keys_ok(key) || key->mode != 2 || key->has_fold || !p->has_data || io->n < 1 ||
-      io->n >= (1ull << 31) || !io->out || p->n_params <= p->max_param || (io->draw_stride > 0 && !io->draws) ||
-      ((uintptr_t)io->ws & 7) != 0)
-    return GJX_ERR_INVALID;
+  const bool ok = io && keys_ok(key) && key->mode == 2 && !key->has_fold && !(io->draw_stride > 0 && !io->draws);
+  const int n_plated = pointwise_plan_ok(p) ? predictive_n_plated(p) : 0;
   PredictiveArgs A;
-  memset(&A, 0, sizeof A);
-  for (int l = 0; l < p->n_latents; ++l) {
-    if (!io->x[l]) return GJX_ERR_INVALID;
-    A.x[l] = io->x[l];
-  }
-  const int n_plated = predictive_n_plated(p);
-  const uint32_t D = p->data.n_rows, W = gjx_predictive_chunks(io->n, D);
-  if (!io->ws || io->ws_bytes < gjx_predictive_workspace_bytes(io->n, D, n_plated)) return GJX_ERR_WORKSPACE;
-  if (!gjx_jit::enabled()) return GJX_ERR_UNSUPPORTED;  // a generated kernel only
-  gjx_jit::CompiledPredictive* k = predictive_compiled(p, key->impl);
-  if (!k) return GJX_ERR_JIT;
-  A.part = static_cast<double*>(io->ws);
-  A.key = Key{key->parent[0], key->parent[1], (uint32_t)key->parent_lane, (uint32_t)(key->parent_lane >> 32)};
-  A.n = (uint32_t)io->n;
-  A.W = W;
-  A.per = (uint32_t)((io->n + W - 1) / W);
-  // (a stride of n or more stores particle 0 alone, as the stride n does: the kernel's counter stays below 2^32)
-  A.stride = (uint32_t)(io->draw_stride < io->n ? io->draw_stride : io->n);
-  A.m = A.stride ? (uint32_t)((io->n + A.stride - 1) / A.stride) : 0u;
-  A.draws = A.stride ? io->draws : nullptr;
-  PlanParams prm = p->prm;
-  PlanTables tabs = k->tabs;
-  PlateData pd = p->data;
-  void* args[] = {&A, &prm, &tabs, &pd};
-  const uint64_t tiles = (D + kPredictiveTile - 1) / kPredictiveTile;
-  if (int rc = launch_generated(k->fn, tiles, W, kBlock, s, args)) return rc;
-  k_predictive_fold<<<dim3((unsigned)nrows_of(D), (unsigned)n_plated), kBlock, 0, S(s)>>>(A.part, W, D, io->out);
+  const int rc = plated_launch(p, kTemperPredictive, ok ? key->impl : 0, io, ok, kPredictiveTile, kPredictiveWorkgroups, (size_t)n_plated * 5, s, A,
+                               [&](PredictiveArgs& a) {
+    a.key = Key{key->parent[0], key->parent[1], (uint32_t)key->parent_lane, (uint32_t)(key->parent_lane >> 32)};
+    // (a stride of n or more stores particle 0 alone, as the stride n does: the kernel's counter stays below 2^32)
+    a.stride = (uint32_t)(io->draw_stride < io->n ? io->draw_stride : io->n);
+    a.m = a.stride ? (uint32_t)((io->n + a.stride - 1) / a.stride) : 0u;
+    a.draws = a.stride ? io->draws : nullptr;
+  });
+  if (rc) return rc;
+  const uint32_t D = p->data.n_rows;
+  k_predictive_fold<<<dim3((unsigned)nrows_of(D), (unsigned)n_plated), kBlock, 0, S(s)>>>(A.part, A.W, D, io->out);
   return launch_status();
 }
 

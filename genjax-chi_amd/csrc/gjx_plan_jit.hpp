@@ -1490,11 +1490,112 @@ struct GenBackmove {
   }
 };
 
+// The shadow table of the tempered family (GenTemper, GenPointwise, GenPredictive), built once from a plan's site table: a COPY
+// in which every latent site is an observed one whose value is the function argument nx_<l> — the register or the column
+// entry the caller holds (the GJX_ARG_NEXT form of the transition tables, ref l in table order, scale 1) — and a PLATED site
+// (include/gjx_plate.h) is re-moded for the emitters: an observed site inside its loop over the data rows, or, `drawn`, a
+// LATENT one whose value is drawn and goes to no output column (the draws go where predictive_keep_rows puts them).
+template <class CSiteT, class CArgT>
+struct TemperTable {
+  std::vector<CSiteT> tab;
+  int L = 0;                // latents
+  std::vector<int> plated;  // table positions of the plated sites: plated site s is plated[s]
+  std::vector<int> cs;      // the data columns the plated sites read between them, in ascending order
+
+  // The data columns plated site q reads (a0, a1, obs; affine operands and program leaves), in ascending order.
+  static std::vector<int> plate_cols(const CSiteT& st) {
+    bool used[GJX_PLATE_MAX_COLS] = {};
+    for (const CArgT* a : {&st.a0, &st.a1, &st.obs}) {
+      if (a->kind == GJX_ARG_DATA) used[a->ref] = true;
+      if (a->kind != GJX_ARG_EXPR) continue;
+      const gjx_expr_op* ops = reinterpret_cast<const gjx_expr_op*>(a->table);
+      for (int k = 0; k < a->ref; ++k)
+        if (ops[k].op == GJX_EXPR_DATA) used[ops[k].ref] = true;
+    }
+    return set_of(used);
+  }
+  static std::vector<int> set_of(const bool (&used)[GJX_PLATE_MAX_COLS]) {
+    std::vector<int> cs;
+    for (int c = 0; c < GJX_PLATE_MAX_COLS; ++c)
+      if (used[c]) cs.push_back(c);
+    return cs;
+  }
+  TemperTable(const CSiteT* sites, int n_sites, bool drawn = false) : tab(sites, sites + n_sites) {
+    bool used[GJX_PLATE_MAX_COLS] = {};
+    for (int q = 0; q < n_sites; ++q) {
+      if (sites[q].observed == GJX_SITE_PLATED) {
+        for (int c : plate_cols(sites[q])) used[c] = true;
+        tab[q].observed = drawn ? 0 : 1;
+        if (drawn) tab[q].out_col = -1;
+        plated.push_back(q);
+      }
+      if (sites[q].observed) continue;
+      tab[q].observed = 1;
+      tab[q].obs = CArgT{};
+      tab[q].obs.kind = GJX_ARG_NEXT;
+      tab[q].obs.ref = L++;
+      tab[q].obs.scale = 1.0f;
+    }
+    cs = set_of(used);
+  }
+  // pre0post pre1post ... pre<L-1>post: the latents as parameters or arguments
+  std::string list(const std::string& pre, const std::string& post = "") const {
+    std::string t;
+    for (int l = 0; l < L; ++l) t += pre + std::to_string(l) + post;
+    return t;
+  }
+  // pre<c>sfx for every data column c and every lane suffix: the rows' data values dc<c> (SiteEmitter's names of a DATA
+  // operand under the suffixes) as parameters or arguments
+  std::string data_list(const std::string& pre, std::initializer_list<const char*> sfx) const {
+    std::string t;
+    for (int c : cs)
+      for (const char* s : sfx) t += pre + std::to_string(c) + s;
+    return t;
+  }
+  // The numbering of the draws of a `drawn` table, as a ScopeInfo of one scope.  It numbers the PLATED sites alone, in table
+  // order — include/gjx_predictive.h defines the draws as an importance pass over a table of just those sites — so site q
+  // carries the count of plated sites before it: fold_t, THREEFRY's 1-based counter of that table's sites; fold_p, PHILOX's
+  // 0-based index among its sampled sites (all of them).  (The entries of the other sites are never read: they draw nothing.)
+  ScopeInfo draw_numbering() const {
+    ScopeInfo si;
+    si.n_scopes = 0;
+    si.parent[0] = -1;
+    uint32_t s = 0;
+    for (int q = 0; q < (int)tab.size(); ++q) {
+      si.site_scope[q] = 0;
+      si.fold_t[q] = s + 1u;
+      si.fold_p[q] = s;
+      if (s < plated.size() && plated[s] == q) ++s;
+    }
+    return si;
+  }
+};
+
+// The transposed particle loop of GenPointwise and GenPredictive: lanes are data ROWS, the particles of the workgroup's chunk
+// (blockIdx.y) are wave-uniform and walked in index order.  The latent columns are read through constant-address-space pointers
+// at the loop counter — scalar loads, issued for a block of NB particles (x<l>_<j>) before `block`, the block's statements; a
+// remainder loop runs `rest` (the loop's body, reading xc<l>[i]: no read past x_l[n - 1]).  `prologue` and `epilogue` are the
+// accumulators' lines around the two loops.
+template <class Table>
+inline void emit_particle_loop(std::ostream& o, const Table& t, int NB, const std::string& prologue, const std::string& block,
+                               const std::string& rest, const std::string& epilogue) {
+  for (int l = 0; l < t.L; ++l) o << "  const PlateCol xc" << l << " = (PlateCol)a.x[" << l << "];\n";
+  o << "  const uint64_t lo64 = (uint64_t)blockIdx.y * a.per;\n";
+  o << "  const uint32_t lo = lo64 < a.n ? (uint32_t)lo64 : a.n;\n";
+  o << "  const uint32_t hi = a.n - lo > a.per ? lo + a.per : a.n;\n";
+  o << prologue << "  uint32_t i = lo;\n";
+  o << "  for (; hi - i >= " << NB << "u; i += " << NB << "u) {\n";
+  for (int l = 0; l < t.L; ++l)
+    for (int j = 0; j < NB; ++j) o << "    const float x" << l << "_" << j << " = xc" << l << "[(size_t)i + " << j << "u];\n";
+  o << block << "  }\n";
+  o << "  for (; i < hi; ++i)" << rest << epilogue;
+}
+
 // The move kernel of a tempered SMC sampler (include/gjx_temper.h) over a flat importance-style site table: one lane per
 // particle, the chain's state (L latent values, lp, ll) in registers, K Metropolis-Hastings sweeps in a run-time loop.
 //   assess   tm_assess is the table's walk by SiteEmitter (mode 0: parameters, input columns and postfix programs as in an
-//            importance kernel) over a COPY of the table in which every latent site is an observed one whose value is the
-//            function argument nx_<l> — the register the chain holds (the GJX_ARG_NEXT form of the transition tables).
+//            importance kernel) over the TemperTable: every latent site is an observed one whose value is the function
+//            argument nx_<l> — the register the chain holds.
 //            Nothing is drawn in it; the latent sites' log-densities go to lp (-inf outside a Gamma's / Beta's open support:
 //            the density formulas are TFP's and do not say so themselves — a Gamma(1, b) is finite below 0), the observed
 //            sites' to ll.
@@ -1518,28 +1619,13 @@ struct GenTemper {
   int n_sites;
   bool cov = false;  // the covariance move (include/gjx_temper_cov.h): gjx_temper_move_cov_kernel, x' = x + F eps
 
-  // The data columns plated site q reads (a0, a1, obs; affine operands and program leaves), in ascending order.
-  static std::vector<int> plate_cols(const CSiteT& st) {
-    bool used[GJX_PLATE_MAX_COLS] = {};
-    for (const CArgT* a : {&st.a0, &st.a1, &st.obs}) {
-      if (a->kind == GJX_ARG_DATA) used[a->ref] = true;
-      if (a->kind != GJX_ARG_EXPR) continue;
-      const gjx_expr_op* ops = reinterpret_cast<const gjx_expr_op*>(a->table);
-      for (int k = 0; k < a->ref; ++k)
-        if (ops[k].op == GJX_EXPR_DATA) used[ops[k].ref] = true;
-    }
-    std::vector<int> cs;
-    for (int c = 0; c < GJX_PLATE_MAX_COLS; ++c)
-      if (used[c]) cs.push_back(c);
-    return cs;
-  }
   // A PLATED site (include/gjx_plate.h) at its table position: the loop over the data rows.  The row index is a counter
   // against a kernel argument and the columns are constant-address-space pointers out of the argument block, so every read
   // is a wave-uniform SCALAR load; a block of kPlateBlock rows issues its loads (one s_load_dwordx4 per column) before its
   // arithmetic, a remainder loop takes the last n_rows % kPlateBlock rows.  Rows enter the float64 sum in index order.
   static constexpr int kPlateBlock = 4;
   void emit_plated(int q, const CSiteT* tab) {
-    const std::vector<int> cs = plate_cols(tab[q]);
+    const std::vector<int> cs = TemperTable<CSiteT, CArgT>::plate_cols(tab[q]);
     const std::string Q = std::to_string(q);
     std::ostringstream body;  // one row: head (arguments and value from dc<c>), the log-density, the float64 accumulate
     SiteEmitter<CSiteT, CArgT> e{body, impl, 0, tab, n_sites, "      ", ""};
@@ -1567,34 +1653,17 @@ struct GenTemper {
   std::string run() {
     const std::string I = std::to_string(impl);
     emit_prelude(o);
-    std::vector<CSiteT> tab(sites, sites + n_sites);
-    int L = 0;
-    bool plated = false;
-    for (int q = 0; q < n_sites; ++q) {
-      if (sites[q].observed == GJX_SITE_PLATED) {  // (emitted as an observed site inside its loop over the data rows)
-        tab[q].observed = 1;
-        plated = true;
-      }
-      if (sites[q].observed) continue;
-      tab[q].observed = 1;
-      tab[q].obs = CArgT{};
-      tab[q].obs.kind = GJX_ARG_NEXT;
-      tab[q].obs.ref = L++;
-      tab[q].obs.scale = 1.0f;
-    }
-    auto list = [&](const std::string& pre) {  // pre0 pre1 ... pre<L-1>
-      std::string t;
-      for (int l = 0; l < L; ++l) t += pre + std::to_string(l);
-      return t;
-    };
+    const TemperTable<CSiteT, CArgT> t(sites, n_sites);
+    const int L = t.L;
+    const bool plated = !t.plated.empty();
     o << "__device__ __forceinline__ void tm_assess(const RunCols& cols, const PlanParams& prm, const PlanTables& tabs, uint32_t li"
-      << list(", float nx_") << ", float& lp_out, float& ll_out" << (plated ? ", const PlateData& pd" : "") << ") {\n";
+      << t.list(", float nx_") << ", float& lp_out, float& ll_out" << (plated ? ", const PlateData& pd" : "") << ") {\n";
     o << "  (void)cols; (void)prm; (void)tabs; (void)li;\n  float lp = 0.0f, ll = 0.0f;\n";
-    SiteEmitter<CSiteT, CArgT> e{o, impl, 0, tab.data(), n_sites, "  ", ""};
+    SiteEmitter<CSiteT, CArgT> e{o, impl, 0, t.tab.data(), n_sites, "  ", ""};
     e.exact_cuts = false;
     for (int q = 0; q < n_sites; ++q) {
       if (sites[q].observed == GJX_SITE_PLATED) {
-        emit_plated(q, tab.data());
+        emit_plated(q, t.tab.data());
         continue;
       }
       e.head(q);
@@ -1621,7 +1690,7 @@ struct GenTemper {
     o << "    uint32_t an = a.anc ? (uint32_t)a.anc[i] : i;\n    an = an < n ? an : n - 1u;\n";
     for (int l = 0; l < L; ++l) o << "    float x" << l << " = a.x_in[" << l << "][an];\n";
     o << "    float lp, ll;\n";
-    o << "    if (a.recompute) tm_assess(cols, prm, tabs, i" << list(", x") << ", lp, ll" << (plated ? ", pd" : "") << ");\n";
+    o << "    if (a.recompute) tm_assess(cols, prm, tabs, i" << t.list(", x") << ", lp, ll" << (plated ? ", pd" : "") << ");\n";
     o << "    else { lp = a.lp_in[an]; ll = a.ll_in[an]; }\n";
     o << "    int32_t acc = 0;\n";
     o << "    for (uint32_t r = 0; r < a.n_moves; ++r) {\n";
@@ -1647,7 +1716,7 @@ struct GenTemper {
       o << "      const float t" << l << " = a.scales[" << l << "] * site_normal<" << I << ">(Stream<" << I << ">(pk, true, " << fold << "u));\n";
       o << "      const float y" << l << " = x" << l << " + t" << l << ";\n";
     }
-    o << "      float lpn, lln;\n      tm_assess(cols, prm, tabs, i" << list(", y") << ", lpn, lln" << (plated ? ", pd" : "") << ");\n";
+    o << "      float lpn, lln;\n      tm_assess(cols, prm, tabs, i" << t.list(", y") << ", lpn, lln" << (plated ? ", pd" : "") << ");\n";
     o << "      const float bh = a.beta * ll;\n      const float h = lp + bh;\n";
     o << "      const float bn = a.beta * lln;\n      const float hn = lpn + bn;\n";
     o << "      const float d = hn - h;\n";
@@ -1668,11 +1737,10 @@ struct GenTemper {
 // so lanes are ROWS and particles are wave-uniform:
 //   * a workgroup owns a tile of 256 rows (blockIdx.x) and one chunk of particles (blockIdx.y); a lane loads its row of the
 //     data columns the plated sites read ONCE, into registers (dc<c>, the names SiteEmitter gives a DATA operand);
-//   * the chunk's particles are walked in index order; the latent columns are read through constant-address-space pointers
-//     at the loop counter — scalar loads, issued for a block of kPointwiseBlock particles before the block's arithmetic, a
-//     remainder loop for the rest (no read past x_l[n - 1]);
-//   * pw_term is tm_assess without the sums it does not need: the unplated sites' heads define the values a plated site may
-//     refer to (a latent's is the function argument nx_<l>), the plated sites' log-densities add up in f32 in table order;
+//   * the chunk's particles are walked by emit_particle_loop in blocks of kPointwiseBlock;
+//   * pw_term is tm_assess without the sums it does not need, over the same TemperTable: the unplated sites' heads define the
+//     values a plated site may refer to (a latent's is the function argument nx_<l>), the plated sites' log-densities add up
+//     in f32 in table order;
 //   * the accumulators and the stores are fixed device code (gjx_device.hpp pointwise_take / pointwise_store).
 // Lanes at or past n_rows leave at once and store nothing.  No LDS, no barrier, no draw: one source per plan, whatever impl.
 // The source holds no data value, no parameter value and neither n nor n_rows.  (A table that reads a per-particle input
@@ -1684,40 +1752,14 @@ struct GenPointwise {
   int n_sites;
 
   std::string run() {
-    using GT = GenTemper<CSiteT, CArgT>;
     constexpr int NB = gjx::kPointwiseBlock;
     emit_prelude(o);
-    std::vector<CSiteT> tab(sites, sites + n_sites);
-    bool used[GJX_PLATE_MAX_COLS] = {};
-    int L = 0;
-    for (int q = 0; q < n_sites; ++q) {
-      if (sites[q].observed == GJX_SITE_PLATED) {
-        for (int c : GT::plate_cols(sites[q])) used[c] = true;
-        tab[q].observed = 1;
-      }
-      if (sites[q].observed) continue;
-      tab[q].observed = 1;  // (a latent: an observed site whose value is the argument nx_<l>, as in GenTemper)
-      tab[q].obs = CArgT{};
-      tab[q].obs.kind = GJX_ARG_NEXT;
-      tab[q].obs.ref = L++;
-      tab[q].obs.scale = 1.0f;
-    }
-    std::vector<int> cs;
-    for (int c = 0; c < GJX_PLATE_MAX_COLS; ++c)
-      if (used[c]) cs.push_back(c);
-    auto list = [&](const std::string& pre, const std::string& post = "") {
-      std::string t;
-      for (int l = 0; l < L; ++l) t += pre + std::to_string(l) + post;
-      return t;
-    };
-    std::string dcs_decl, dcs;
-    for (int c : cs) {
-      dcs_decl += ", float dc" + std::to_string(c);
-      dcs += ", dc" + std::to_string(c);
-    }
-    o << "__device__ __forceinline__ float pw_term(const PlanParams& prm, const PlanTables& tabs" << list(", float nx_") << dcs_decl << ") {\n";
+    const TemperTable<CSiteT, CArgT> t(sites, n_sites);
+    const std::string dcs = t.data_list(", dc", {""});
+    o << "__device__ __forceinline__ float pw_term(const PlanParams& prm, const PlanTables& tabs" << t.list(", float nx_")
+      << t.data_list(", float dc", {""}) << ") {\n";
     o << "  (void)prm; (void)tabs;\n";
-    SiteEmitter<CSiteT, CArgT> e{o, 0, 0, tab.data(), n_sites, "  ", ""};
+    SiteEmitter<CSiteT, CArgT> e{o, 0, 0, t.tab.data(), n_sites, "  ", ""};
     e.exact_cuts = false;
     bool first = true;
     for (int q = 0; q < n_sites; ++q) {
@@ -1730,38 +1772,28 @@ struct GenPointwise {
     o << "  return t;\n}\n";
     o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_pointwise_kernel(PointwiseArgs a, PlanParams prm, PlanTables tabs, PlateData pd) {\n";
     o << "  const uint32_t d = blockIdx.x * 256u + threadIdx.x;\n  if (d >= pd.n_rows) return;\n";
-    for (int c : cs) o << "  const float dc" << c << " = pd.col[" << c << "][d];\n";
-    for (int l = 0; l < L; ++l) o << "  const PlateCol xc" << l << " = (PlateCol)a.x[" << l << "];\n";
-    o << "  const uint64_t lo64 = (uint64_t)blockIdx.y * a.per;\n";
-    o << "  const uint32_t lo = lo64 < a.n ? (uint32_t)lo64 : a.n;\n";
-    o << "  const uint32_t hi = a.n - lo > a.per ? lo + a.per : a.n;\n";
-    o << "  PointwiseAcc q = pointwise_start();\n  uint32_t i = lo;\n";
-    o << "  for (; hi - i >= " << NB << "u; i += " << NB << "u) {\n";
-    for (int l = 0; l < L; ++l)
-      for (int j = 0; j < NB; ++j) o << "    const float x" << l << "_" << j << " = xc" << l << "[(size_t)i + " << j << "u];\n";
-    o << "    const float t[" << NB << "] = {";
-    for (int j = 0; j < NB; ++j) o << (j ? ", " : "") << "pw_term(prm, tabs" << list(", x", "_" + std::to_string(j)) << dcs << ")";
-    o << "};\n    pointwise_take<" << NB << ">(q, t);\n  }\n";
-    o << "  for (; i < hi; ++i) {\n";
-    o << "    const float t[1] = {pw_term(prm, tabs" << list(", xc", "[i]") << dcs << ")};\n";
-    o << "    pointwise_take<1>(q, t);\n  }\n";
-    o << "  pointwise_store(a, pd.n_rows, blockIdx.y, d, q);\n}\n";
+    for (int c : t.cs) o << "  const float dc" << c << " = pd.col[" << c << "][d];\n";
+    std::string block = "    const float t[" + std::to_string(NB) + "] = {";
+    for (int j = 0; j < NB; ++j) block += std::string(j ? ", " : "") + "pw_term(prm, tabs" + t.list(", x", "_" + std::to_string(j)) + dcs + ")";
+    block += "};\n    pointwise_take<" + std::to_string(NB) + ">(q, t);\n";
+    emit_particle_loop(o, t, NB, "  PointwiseAcc q = pointwise_start();\n", block,
+                       " {\n    const float t[1] = {pw_term(prm, tabs" + t.list(", xc", "[i]") + dcs + ")};\n    pointwise_take<1>(q, t);\n  }\n",
+                       "  pointwise_store(a, pd.n_rows, blockIdx.y, d, q);\n}\n");
     return o.str();
   }
 };
 
-// The predictive kernel of a plated tempered plan (include/gjx_predictive.h): GenPointwise's transposed loop — rows on lanes,
-// the particles of a chunk wave-uniform — with a DRAW where the pointwise kernel has a density.  The header defines the draws
+// The predictive kernel of a plated tempered plan (include/gjx_predictive.h): the transposed loop of emit_particle_loop — rows
+// on lanes, the particles of a chunk wave-uniform — with a DRAW where the pointwise kernel has a density.  The header defines the draws
 // as an importance pass over the data rows, so the sites are emitted by the importance kernel's own emitters:
 //   * a lane owns the rows dA = 2 r and dA + 1 — the "particles" A and B of a LaneGroup.  Under PHILOX the plated sites go
 //     through emit_pair_lane_sites (pair r of the pass: one cipher block per two single-word draws of both rows, one
 //     Box-Muller transform per Normal site, the gammas of both rows drawn together); under THREEFRY through the two
 //     emitters' head() / tail(), the one-particle form twice.  No sampler is written here;
 //   * the pass's parent key fold_in(a.key, i) is wave-uniform, the rows' keys are its lazy children d (split_at);
-//   * the table walked is the plan's own with the plated sites as LATENT ones (their draws) and everything else as
-//     GenPointwise has it: an unplated site only defines the value a plated site may refer to (a latent's is the argument
-//     nx_<l>), emitted here by head() and skipped by the pair emitter.  The draw numbering is the shadow table's — site s of
-//     the plated sites alone — handed to the emitters as a ScopeInfo of one scope;
+//   * the table walked is the `drawn` TemperTable: the plated sites as LATENT ones (their draws), every other site only
+//     defines the value a plated site may refer to (a latent's is the argument nx_<l>), emitted here by head() and skipped by
+//     the pair emitter.  The draws are numbered by TemperTable::draw_numbering, handed to the emitters as their ScopeInfo;
 //   * a lane loads its two rows of the data columns once (dc<c>A, dc<c>B: SiteEmitter's names under the suffixes).  With an
 //     odd row count the last lane has row A only: B reads row A's data again, is summed into accumulators nobody stores and
 //     is never stored itself;
@@ -1776,61 +1808,26 @@ struct GenPredictive {
   int n_sites;
 
   std::string run() {
-    using GT = GenTemper<CSiteT, CArgT>;
     using Emitter = SiteEmitter<CSiteT, CArgT>;
     constexpr int NB = gjx::kPredictiveBlock;
     const std::string I = std::to_string(impl);
     emit_prelude(o);
-    std::vector<CSiteT> tab(sites, sites + n_sites);
-    std::vector<int> plated;  // table positions of the plated sites: shadow site s is plated[s]
-    bool used[GJX_PLATE_MAX_COLS] = {}, skip[GJX_MAX_SITES] = {};
-    ScopeInfo si;
-    si.n_scopes = 0;
-    si.parent[0] = -1;
-    int L = 0;
-    for (int q = 0; q < n_sites; ++q) {
-      si.site_scope[q] = 0;
-      si.fold_t[q] = (uint32_t)plated.size() + 1u;  // (THREEFRY: the 1-based counter of the shadow table's sites)
-      si.fold_p[q] = (uint32_t)plated.size();       // (PHILOX: the 0-based index among its sampled sites — all of them)
-      if (sites[q].observed == GJX_SITE_PLATED) {
-        for (int c : GT::plate_cols(sites[q])) used[c] = true;
-        tab[q].observed = 0;
-        tab[q].out_col = -1;  // (the draws go where predictive_keep_rows puts them)
-        plated.push_back(q);
-        continue;
-      }
-      skip[q] = true;
-      if (sites[q].observed) continue;
-      tab[q].observed = 1;  // (a latent: an observed site whose value is the argument nx_<l>, as in GenTemper)
-      tab[q].obs = CArgT{};
-      tab[q].obs.kind = GJX_ARG_NEXT;
-      tab[q].obs.ref = L++;
-      tab[q].obs.scale = 1.0f;
-    }
+    const TemperTable<CSiteT, CArgT> t(sites, n_sites, true);
+    const std::vector<int>& plated = t.plated;
+    const ScopeInfo si = t.draw_numbering();
+    bool skip[GJX_MAX_SITES] = {};  // the sites that draw nothing: emitted here by head(), skipped by the pair emitter
+    for (int q = 0; q < n_sites; ++q) skip[q] = t.tab[q].observed != 0;
     const int S = (int)plated.size();
-    const std::string SS = std::to_string(S);
-    std::vector<int> cs;
-    for (int c = 0; c < GJX_PLATE_MAX_COLS; ++c)
-      if (used[c]) cs.push_back(c);
-    auto list = [&](const std::string& pre, const std::string& post = "") {
-      std::string t;
-      for (int l = 0; l < L; ++l) t += pre + std::to_string(l) + post;
-      return t;
-    };
-    std::string dcs_decl, dcs;
-    for (int c : cs) {
-      dcs_decl += ", float dc" + std::to_string(c) + "A, float dc" + std::to_string(c) + "B";
-      dcs += ", dc" + std::to_string(c) + "A, dc" + std::to_string(c) + "B";
-    }
+    const std::string SS = std::to_string(S), dcs = t.data_list(", dc", {"A", "B"});
     // particle i at the lane's two rows: the draws of every plated site, into the accumulators and (every stride-th) the table
     o << "__device__ __forceinline__ void pd_particle(const PredictiveArgs& a, const PlanParams& prm, const PlanTables& tabs, PredictiveKeep& kp, "
-         "uint32_t i, uint32_t n_rows, uint32_t dA, bool hasB" << list(", float nx_") << dcs_decl << ", PredictiveAcc (&qA)[" << SS
+         "uint32_t i, uint32_t n_rows, uint32_t dA, bool hasB" << t.list(", float nx_") << t.data_list(", float dc", {"A", "B"}) << ", PredictiveAcc (&qA)[" << SS
       << "], PredictiveAcc (&qB)[" << SS << "]) {\n";
     o << "  (void)prm; (void)tabs;\n";
     o << "  const Key pk = predictive_pass_key<" << I << ">(a.key, i);  // (fold_in(a.key, i), wave-uniform: the parent key of this particle's pass over the rows)\n";
     o << "  const Key pkeyA = split_at<" << I << ">(pk, (uint64_t)dA); (void)pkeyA;\n";
     o << "  const Key pkeyB = split_at<" << I << ">(pk, (uint64_t)dA + 1u); (void)pkeyB;\n";
-    LaneGroup<CSiteT, CArgT> lanes(o, 2, impl, 0, tab.data(), n_sites, "  ");
+    LaneGroup<CSiteT, CArgT> lanes(o, 2, impl, 0, t.tab.data(), n_sites, "  ");
     lanes.each([&](int, Emitter& e) { e.store_values = false; e.sc = &si; e.ext_bits = impl == 1; e.defer_acc = true; });
     for (int q = 0; q < n_sites; ++q)
       if (skip[q]) lanes.each([&](int, Emitter& e) { e.head(q); });
@@ -1872,23 +1869,18 @@ struct GenPredictive {
     o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_predictive_kernel(PredictiveArgs a, PlanParams prm, PlanTables tabs, PlateData pd) {\n";
     o << "  const uint32_t dA = (blockIdx.x * 256u + threadIdx.x) * 2u;\n  if (dA >= pd.n_rows) return;\n";
     o << "  const bool hasB = dA + 1u < pd.n_rows;\n  const uint32_t dB = hasB ? dA + 1u : dA;  // (an odd row count: row n_rows is never read)\n";
-    for (int c : cs) o << "  const float dc" << c << "A = pd.col[" << c << "][dA], dc" << c << "B = pd.col[" << c << "][dB];\n";
-    for (int l = 0; l < L; ++l) o << "  const PlateCol xc" << l << " = (PlateCol)a.x[" << l << "];\n";
-    o << "  const uint64_t lo64 = (uint64_t)blockIdx.y * a.per;\n";
-    o << "  const uint32_t lo = lo64 < a.n ? (uint32_t)lo64 : a.n;\n";
-    o << "  const uint32_t hi = a.n - lo > a.per ? lo + a.per : a.n;\n";
-    o << "  PredictiveAcc qA[" << SS << "], qB[" << SS << "];\n";
-    o << "#pragma unroll\n  for (int s = 0; s < " << SS << "; ++s) qA[s] = qB[s] = predictive_start();\n";
-    o << "  PredictiveKeep kp = predictive_keep_start(a, lo);\n  uint32_t i = lo;\n";
-    o << "  for (; hi - i >= " << NB << "u; i += " << NB << "u) {\n";
-    for (int l = 0; l < L; ++l)
-      for (int j = 0; j < NB; ++j) o << "    const float x" << l << "_" << j << " = xc" << l << "[(size_t)i + " << j << "u];\n";
-    for (int j = 0; j < NB; ++j)
-      o << "    pd_particle(a, prm, tabs, kp, i + " << j << "u, pd.n_rows, dA, hasB" << list(", x", "_" + std::to_string(j)) << dcs << ", qA, qB);\n";
-    o << "  }\n";
-    o << "  for (; i < hi; ++i) pd_particle(a, prm, tabs, kp, i, pd.n_rows, dA, hasB" << list(", xc", "[i]") << dcs << ", qA, qB);\n";
-    o << "#pragma unroll\n  for (int s = 0; s < " << SS << "; ++s) {\n    predictive_store(a, pd.n_rows, (uint32_t)s, blockIdx.y, dA, qA[s]);\n";
-    o << "    if (hasB) predictive_store(a, pd.n_rows, (uint32_t)s, blockIdx.y, dA + 1u, qB[s]);\n  }\n}\n";
+    for (int c : t.cs) o << "  const float dc" << c << "A = pd.col[" << c << "][dA], dc" << c << "B = pd.col[" << c << "][dB];\n";
+    auto particle = [&](const std::string& i, const std::string& xs) {
+      return "pd_particle(a, prm, tabs, kp, " + i + ", pd.n_rows, dA, hasB" + xs + dcs + ", qA, qB);\n";
+    };
+    std::string block;
+    for (int j = 0; j < NB; ++j) block += "    " + particle("i + " + std::to_string(j) + "u", t.list(", x", "_" + std::to_string(j)));
+    emit_particle_loop(o, t, NB,
+                       "  PredictiveAcc qA[" + SS + "], qB[" + SS + "];\n#pragma unroll\n  for (int s = 0; s < " + SS +
+                           "; ++s) qA[s] = qB[s] = predictive_start();\n  PredictiveKeep kp = predictive_keep_start(a, lo);\n",
+                       block, " " + particle("i", t.list(", xc", "[i]")),
+                       "#pragma unroll\n  for (int s = 0; s < " + SS + "; ++s) {\n    predictive_store(a, pd.n_rows, (uint32_t)s, blockIdx.y, dA, qA[s]);\n"
+                       "    if (hasB) predictive_store(a, pd.n_rows, (uint32_t)s, blockIdx.y, dA + 1u, qB[s]);\n  }\n}\n");
     return o.str();
   }
 };
@@ -2257,8 +2249,10 @@ struct Module {
     return true;
   }
 };
-struct Compiled : Module {  // an importance or scan kernel
+struct CompiledKernel : Module {  // one generated kernel: each of the four slots of a tempered plan (gjx_hip.hip TemperKernel)
   hipFunction_t fn = nullptr;
+};
+struct Compiled : CompiledKernel {  // an importance or scan kernel
   int block = 256;  // threads per workgroup of the compiled kernel
   int rows_per_block = 1;  // 256-particle rows per workgroup
 };
@@ -2267,15 +2261,6 @@ struct CompiledSmc : Module {  // the kernels of a filter (bootstrap or guided)
 };
 struct CompiledBacksim : Module {  // the two kernels of a backward pass
   hipFunction_t step = nullptr, last = nullptr;
-};
-struct CompiledTemper : Module {  // the move kernel of a tempered sampler (diagonal, or the covariance move: a slot each)
-  hipFunction_t move = nullptr;
-};
-struct CompiledPredictive : Module {  // the predictive kernel of a plated tempered plan, per generator (include/gjx_predictive.h)
-  hipFunction_t fn = nullptr;
-};
-struct CompiledPointwise : Module {  // the pointwise kernel of a plated tempered plan (include/gjx_pointwise.h)
-  hipFunction_t fn = nullptr;
 };
 
 }  // namespace gjx_jit

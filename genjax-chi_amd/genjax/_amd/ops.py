@@ -709,25 +709,32 @@ class Ops:
                       int(d.size), self._p(out), self._p(ws), ws.numel(), self.stream())
         return out
 
+    def _plated_io(self, what: str, plan: "TemperPlan", x: list, io, ws_symbol: str, *ws_args):
+        """What temper_pointwise and temper_predictive begin with: the plan is plated and has data, `x` holds its L latent
+        columns (float32[n]) -> io.n, io.x, io.ws of `ws_symbol`(n, D, *ws_args) bytes; returns (n, D, the workspace)."""
+        self.lib.require(what, "gjx_temper_" + what)
+        if not getattr(plan, "plated", False) or not plan.n_rows:
+            raise ValueError(f"temper_{what}: the plan has no plated site, or no data (TemperPlan.set_data)")
+        L, n, D = plan.n_latents, x[0].numel(), plan.n_rows
+        if len(x) != L:
+            raise ValueError(f"temper_{what}: the plan has {L} latents, got {len(x)} columns")
+        io.n = n
+        for l in range(L):
+            io.x[l] = self._chk(x[l], torch.float32, n, f"x[{l}]").value
+        nb = int(self.lib.call(ws_symbol, n, D, *ws_args))
+        # (per call: see workspace(); uninitialised: the first launch writes every entry the fold reads)
+        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=self._alloc_device)
+        io.ws, io.ws_bytes = ws.data_ptr(), ws.numel()
+        return n, D, ws
+
     def temper_pointwise(self, plan: "TemperPlan", x: list) -> torch.Tensor:
         """gjx_temper_pointwise (include/gjx_pointwise.h): TWO launches -> float64[4, D] on the device over the plan's data
         rows d — the log-sum-exp over the particles of the per-row log-likelihood t[d, i], its sum, its sum of squares and the
         count of entries above -inf.  `x`: the L latent columns, float32[n].  Nothing is drawn."""
-        self.lib.require("pointwise", "gjx_temper_pointwise")
-        if not getattr(plan, "plated", False) or not plan.n_rows:
-            raise ValueError("temper_pointwise: the plan has no plated site, or no data (TemperPlan.set_data)")
-        L, n, D = plan.n_latents, x[0].numel(), plan.n_rows
-        if len(x) != L:
-            raise ValueError(f"temper_pointwise: the plan has {L} latents, got {len(x)} columns")
         io = abi.PointwiseIO()
-        io.n = n
-        for l in range(L):
-            io.x[l] = self._chk(x[l], torch.float32, n, f"x[{l}]").value
-        nb = int(self.lib.call("gjx_pointwise_workspace_bytes", n, D))
-        # (per call: see workspace(); uninitialised: the first launch writes every entry the fold reads)
-        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=self._alloc_device)
+        n, D, ws = self._plated_io("pointwise", plan, x, io, "gjx_pointwise_workspace_bytes")
         out = self.empty(4 * D, torch.float64)
-        io.out, io.ws, io.ws_bytes = out.data_ptr(), ws.data_ptr(), ws.numel()
+        io.out = out.data_ptr()
         self.lib.call("gjx_temper_pointwise", plan.handle, C.byref(io), self.stream())
         return out.view(4, D)
 
@@ -737,26 +744,15 @@ class Ops:
         columns, float32[n]): the sum and the sum of squares of the replicated value y ~ p(y | x_i, data_d), and the counts
         y < obs_d, y == obs_d, y != y.  `key`: ONE key (a PRNGKey, or its literal batch); particle i draws its pass over the
         rows under fold_in(key, i).  `draw_stride = k >= 1` also returns the draws of particles 0, k, 2 k, ... (m = ceil(n / k))."""
-        self.lib.require("predictive", "gjx_temper_predictive")
-        if not getattr(plan, "plated", False) or not plan.n_rows:
-            raise ValueError("temper_predictive: the plan has no plated site, or no data (TemperPlan.set_data)")
-        L, n, D, S = plan.n_latents, x[0].numel(), plan.n_rows, plan.n_plated
-        if len(x) != L:
-            raise ValueError(f"temper_predictive: the plan has {L} latents, got {len(x)} columns")
         k = int(draw_stride)
         if k < 0:
             raise ValueError("temper_predictive: draw_stride >= 0")
         kb = key if isinstance(key, KeyBatch) else key.literal()
-        io = abi.PredictiveIO()
-        io.n = n
-        for l in range(L):
-            io.x[l] = self._chk(x[l], torch.float32, n, f"x[{l}]").value
-        nb = int(self.lib.call("gjx_predictive_workspace_bytes", n, D, S))
-        # (per call: see workspace(); uninitialised: the first launch writes every entry the fold reads)
-        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=self._alloc_device)
+        io, S = abi.PredictiveIO(), getattr(plan, "n_plated", 0)
+        n, D, ws = self._plated_io("predictive", plan, x, io, "gjx_predictive_workspace_bytes", S)
         out = self.empty(S * 5 * D, torch.float64)
         draws = self.empty(S * (-(-n // k)) * D, torch.float32) if k else None
-        io.out, io.ws, io.ws_bytes, io.draw_stride = out.data_ptr(), ws.data_ptr(), ws.numel(), k
+        io.out, io.draw_stride = out.data_ptr(), k
         if draws is not None:
             io.draws = draws.data_ptr()
         self.lib.call("gjx_temper_predictive", plan.handle, C.byref(self._keys(kb, 1)), C.byref(io), self.stream())
@@ -1120,12 +1116,12 @@ class PlanHandle:
 
     _destroy: str
 
-    def _source(self, symbol: str, impl: int) -> str:
-        """A `*_source` call of the ABI: the size first, then the text."""
+    def _source(self, symbol: str, *impl: int) -> str:
+        """A `*_source` call of the ABI (without `impl`: a source that no generator enters): the size first, then the text."""
         need = C.c_size_t()
-        self.ops.lib.call(symbol, self.handle, impl, None, 0, C.byref(need))
+        self.ops.lib.call(symbol, self.handle, *impl, None, 0, C.byref(need))
         buf = C.create_string_buffer(need.value)
-        self.ops.lib.call(symbol, self.handle, impl, buf, need.value, None)
+        self.ops.lib.call(symbol, self.handle, *impl, buf, need.value, None)
         return buf.value.decode()
 
     def __del__(self):
@@ -1231,11 +1227,7 @@ class TemperPlan(PlanHandle):
 
     def pointwise_source(self) -> str:
         """The HIP source of the plan's generated pointwise kernel (one per plan: it draws nothing)."""
-        need = C.c_size_t()
-        self.ops.lib.call("gjx_pointwise_source", self.handle, None, 0, C.byref(need))
-        buf = C.create_string_buffer(need.value)
-        self.ops.lib.call("gjx_pointwise_source", self.handle, buf, need.value, None)
-        return buf.value.decode()
+        return self._source("gjx_pointwise_source")
 
     def predictive_compile_check(self, impl: int) -> int:
         """gjx_predictive_compile_check (include/gjx_predictive.h): the status, not raised."""

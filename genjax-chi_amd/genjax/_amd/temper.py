@@ -571,38 +571,46 @@ class TemperedSMC(SMCAlgorithm):
         out.result = res
         return out
 
-    # -- pointwise predictive densities (include/gjx_pointwise.h) ------------------------------------------------
-    def pointwise(self, res, target: Target | None = None) -> PointwiseLikelihood:
-        """The per-row log-likelihood of the plated site(s) under the population `res` — a TemperedResult of `run`, or the L
-        latent columns (float32 [n]) in the plan's latent order — reduced over the particles in two launches.
-        `target=None` scores the rows the sampler was fitted to; a `Target` over the same model body with OTHER data
-        tensors scores held-out rows under the same population (same structure: the kernel comes out of the JIT cache)."""
+    # -- a population against a plated table: what pointwise() and predictive() share ---------------------------------------------
+    def _population(self, what: str, noun: str, res, target: Target | None):
+        """`res` (a TemperedResult, or the L latent columns) and `target` (None: the fitted one) -> (tracer, the tempered plan
+        with its parameters and data set, the columns as float32 device tensors).  A `target` of its own gets a plan of its own
+        (same structure: its kernels come out of the JIT cache)."""
         st = self._state()
         ops = st["ops"]
-        ops.lib.require("pointwise", "gjx_temper_pointwise")
         cols = list(res.columns) if isinstance(res, TemperedResult) else list(res)
         fitted = [m["addr"] for m in st["latents"]]
         if target is None:
             tracer, tplan = st["tracer"], st["tplan"]
         else:
             if not isinstance(target, Target):
-                raise TypeError("TemperedSMC.pointwise: target must be a Target")
+                raise TypeError(f"TemperedSMC.{what}: target must be a Target")
             tracer = lower(target, self.n_particles)
             theirs = [m["addr"] for m in tracer.meta if m["obs"] is None]
             if theirs != fitted:
-                raise ValueError(f"TemperedSMC.pointwise: the target's latent addresses {theirs!r} are not the fitted plan's {fitted!r}")
+                raise ValueError(f"TemperedSMC.{what}: the target's latent addresses {theirs!r} are not the fitted plan's {fitted!r}")
             tplan = None
         if not tracer.data:
-            raise PlanUnsupported(f"TemperedSMC.pointwise: no plated site among the addresses {[m['addr'] for m in tracer.meta]!r} "
-                                  "(pointwise densities are those of a site observed over a data column)")
+            raise PlanUnsupported(f"TemperedSMC.{what}: no plated site among the addresses {[m['addr'] for m in tracer.meta]!r} "
+                                  f"({noun} are those of a site observed over a data column)")
         if len(cols) != len(fitted):
-            raise ValueError(f"TemperedSMC.pointwise: {len(fitted)} latent columns expected ({fitted!r}), got {len(cols)}")
+            raise ValueError(f"TemperedSMC.{what}: {len(fitted)} latent columns expected ({fitted!r}), got {len(cols)}")
         if tplan is None:
             tplan = ops.temper_plan_create(tracer.sites, keep=(tracer.keep, tracer))
         if tracer.params:
             tplan.set_params(tracer.params)
         tplan.set_data([t.detach().to(device=ops.device(), dtype=torch.float32).contiguous() for t in tracer.data])
-        x = [c.detach().to(device=ops.device(), dtype=torch.float32).contiguous() for c in cols]
+        return tracer, tplan, [c.detach().to(device=ops.device(), dtype=torch.float32).contiguous() for c in cols]
+
+    # -- pointwise predictive densities (include/gjx_pointwise.h; DESIGN.md §4l) ------------------------------------------------
+    def pointwise(self, res, target: Target | None = None) -> PointwiseLikelihood:
+        """The per-row log-likelihood of the plated site(s) under the population `res` — a TemperedResult of `run`, or the L
+        latent columns (float32 [n]) in the plan's latent order — reduced over the particles in two launches.
+        `target=None` scores the rows the sampler was fitted to; a `Target` over the same model body with OTHER data
+        tensors scores held-out rows under the same population (same structure: the kernel comes out of the JIT cache)."""
+        ops = self._state()["ops"]
+        ops.lib.require("pointwise", "gjx_temper_pointwise")
+        _, tplan, x = self._population("pointwise", "pointwise densities", res, target)
         return PointwiseLikelihood(ops.temper_pointwise(tplan, x), x[0].numel())
 
     # -- posterior predictive draws (include/gjx_predictive.h; DESIGN.md §4n) ---------------------------------------------------
@@ -650,49 +658,21 @@ class TemperedSMC(SMCAlgorithm):
         `draw_stride=k` also returns the draws of particles 0, k, 2 k, ...; `n_draws=m` is draw_stride = ceil(n / m): at most m
         of them, spread over the population (after resampling, neighbours are copies of one ancestor)."""
         st = self._state()
-        ops = st["ops"]
-        ops.lib.require("predictive", "gjx_temper_predictive")
+        st["ops"].lib.require("predictive", "gjx_temper_predictive")
         if target is not None and args is not None:
             raise ValueError("TemperedSMC.predictive: target= (held-out rows) or args= (new inputs, nothing observed), not both")
         if n_draws is not None and draw_stride is not None:
             raise ValueError("TemperedSMC.predictive: n_draws= or draw_stride=, not both")
-        cols = list(res.columns) if isinstance(res, TemperedResult) else list(res)
-        fitted = [m["addr"] for m in st["latents"]]
-        if len(cols) != len(fitted):
-            raise ValueError(f"TemperedSMC.predictive: {len(fitted)} latent columns expected ({fitted!r}), got {len(cols)}")
-        n = int(cols[0].numel())
-        if n_draws is not None:
-            if int(n_draws) < 1:
-                raise ValueError("TemperedSMC.predictive: n_draws >= 1")
-            k = -(-n // int(n_draws))
-        elif draw_stride is not None:
-            k = int(draw_stride)
-            if k < 1:
-                raise ValueError("TemperedSMC.predictive: draw_stride >= 1")
-        else:
-            k = 0
+        if n_draws is not None and int(n_draws) < 1:
+            raise ValueError("TemperedSMC.predictive: n_draws >= 1")
+        if draw_stride is not None and int(draw_stride) < 1:
+            raise ValueError("TemperedSMC.predictive: draw_stride >= 1")
         if args is not None:
             target = self._unobserved_target(st, args)
-        if target is None:
-            tracer, tplan = st["tracer"], st["tplan"]
-        else:
-            if not isinstance(target, Target):
-                raise TypeError("TemperedSMC.predictive: target must be a Target")
-            tracer = lower(target, self.n_particles)
-            theirs = [m["addr"] for m in tracer.meta if m["obs"] is None]
-            if theirs != fitted:
-                raise ValueError(f"TemperedSMC.predictive: the target's latent addresses {theirs!r} are not the fitted plan's {fitted!r}")
-            tplan = None
-        if not tracer.data:
-            raise PlanUnsupported(f"TemperedSMC.predictive: no plated site among the addresses {[m['addr'] for m in tracer.meta]!r} "
-                                  "(replicated data are those of a site observed over a data column)")
-        if tplan is None:
-            tplan = ops.temper_plan_create(tracer.sites, keep=(tracer.keep, tracer))
-        if tracer.params:
-            tplan.set_params(tracer.params)
-        tplan.set_data([t.detach().to(device=ops.device(), dtype=torch.float32).contiguous() for t in tracer.data])
-        x = [c.detach().to(device=ops.device(), dtype=torch.float32).contiguous() for c in cols]
-        table, draws = ops.temper_predictive(tplan, key, x, k)
+        tracer, tplan, x = self._population("predictive", "replicated data", res, target)
+        n = int(x[0].numel())
+        k = -(-n // int(n_draws)) if n_draws is not None else int(draw_stride or 0)
+        table, draws = st["ops"].temper_predictive(tplan, key, x, k)
         addrs = [m["addr"] for m in tracer.meta if m.get("plated")]
         return PosteriorPredictive(addrs, table, n, draws, k, observed=args is None)
 

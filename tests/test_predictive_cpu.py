@@ -52,6 +52,20 @@ PARENT_SOURCE_SHA256 = {
     ("gamma_rate", "cov", 1): "34d008a3af73f1ca5cb1f4fe6dd7973abc083e083a7cfc3d6026efa7834947fc",
     ("gamma_rate", "pointwise", 0): "1f98428135165709c54b0eb9f3c5bb5f6c41b52aea16d644a460f94af205240c",
 }
+# ... and of the predictive kernel per generator (TemperPlan.predictive_source(impl)), the two-plate body included, generated with
+# the build of the commit before the tempered generators shared one shadow table and one particle loop.
+PARENT_PREDICTIVE_SHA256 = {
+    ("normal", 0): "30b0bfe243f5861fc1a392fb4f0331f4c654440604f817f29c4ef633d7ca8839",
+    ("normal", 1): "90bdc0149df6eb7491e7faaf2a1466d267cebbc49c0af51c2530c970c311e58e",
+    ("hetero", 0): "bc0cc773b657815ba52591cd1a394c9156dbb35ae94ddbf35005b6319029f849",
+    ("hetero", 1): "7480b1e1d2daba8b0c222dfd0662cb4cc8c7a6c908a62b8a451f40eab7cdc1c4",
+    ("logistic", 0): "2579704f6634e51b410bdedd0acae46187f4bce949b40c6eb1c974abf06bae3b",
+    ("logistic", 1): "8213d9a9b8ce27f054dd936af25d8eb93a7e5498aeebf708d69fa0086b354d6b",
+    ("gamma_rate", 0): "188dbb3fa9d2c3e23f9c7d6e97428e19146f96fa95d029c245cc21b49fd122dd",
+    ("gamma_rate", 1): "e7fe2dc718e12f5c46babe59bdce1cca123bfd0913aca64ed29c418d7280ff8d",
+    ("two_plate", 0): "3c512c8b5fc8ec21101637a10ac22341ed16bed757336ebb91085f1b29afe203",
+    ("two_plate", 1): "9451d98b9bbd6b8b9a631fe9bb4f2f82eab07c5666d00de5d9e5d63380562e5a",
+}
 
 # Vector registers: at most 128 (four waves per SIMD out of 512).  ONE kernel does not meet it: `gamma_rate` under THREEFRY —
 # two interleaved Marsaglia-Tsang rejection loops, each with a cipher block of its own in flight — takes 139; it is held to
@@ -168,6 +182,11 @@ def test_existing_sources_are_the_parents(lowered):
         plan = lowered[name][2]
         src = plan.source(impl) if kind == "move" else plan.cov_source(impl) if kind == "cov" else plan.pointwise_source()
         assert hashlib.sha256(src.encode()).hexdigest() == want, (name, kind, impl)
+
+
+def test_predictive_sources_are_the_parents(lowered):
+    for (name, impl), want in PARENT_PREDICTIVE_SHA256.items():
+        assert hashlib.sha256(lowered[name][2].predictive_source(impl).encode()).hexdigest() == want, (name, impl)
 
 
 def test_chunks_and_workspace(ops):  # noqa: F811

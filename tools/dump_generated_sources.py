@@ -10,7 +10,8 @@ loads it, plans are host objects, and the models are the builders the CPU tests 
               getter: the sources are what gjx_scan_plan_compile_check hands the compiler, recorded by a stand-in for gjx_jitc
               (GJX_JITC) that keeps its input and compiles nothing
   smc ...     plain, guided, parameterised and conditional filters, backward simulation and its MCMC moves, tempered move
-              kernels (diagonal, covariance, plated) and pointwise kernels.  (The peer-transport step kernels have no source
+              kernels (diagonal, covariance, plated), pointwise kernels and predictive kernels under both generators (a plan
+              without one: "refused").  (The peer-transport step kernels have no source
               getter and no launch on one device: their text differs from the plain one in the constant kPeers alone.)
 
 --text       also compiles every distinct source with gjx_jitc under the shipped options of its plan kind (compile_options in
@@ -313,15 +314,20 @@ def dump_tempered(ops):
         for impl in (0, 1):
             LINES.append(("temper", name, impl, "-", 0, plan.source(impl)))
             LINES.append(("temper_cov", name, impl, "-", 0, plan.cov_source(impl)))
-        try:
-            LINES.append(("pointwise", name, "-", "-", 0, plan.pointwise_source()))
-        except abi.GjxError as e:
-            LINES.append(("pointwise", name, "-", "-", 0, f"refused: {type(e).__name__}"))
+        for kind, impl, get in (("pointwise", "-", plan.pointwise_source), ("predictive", 0, lambda: plan.predictive_source(0)),
+                                ("predictive", 1, lambda: plan.predictive_source(1))):
+            try:
+                LINES.append((kind, name, impl, "-", 0, get()))
+            except abi.GjxError as e:
+                LINES.append((kind, name, impl, "-", 0, f"refused: {type(e).__name__}"))
 
     with use_ops(ops):
         targets = dict(R.models())
         targets.update(correlated=V.correlated_target(), correlated_plated=V.correlated_target(plated=True), gaussian16=V.gaussian_chain_target(16))
         targets.update({"plate." + name: P.target(name, 20, 0)[0] for name in P.MODELS})
+        xs, zs, y1, y2 = P.two_plate_data(20, 0)
+        targets["two_plate"] = F.target_of(P.TWO_PLATE, (xs, zs), {"y1": y1, "y2": y2})
+        targets["interleaved"] = F.target_of(F.INTERLEAVED, *F.head_rows(*F.interleaved_inputs(), 9))
         rng = np.random.default_rng(11)
         for i in range(20):
             src, sites = F.random_tempered_model(rng)
