@@ -2347,6 +2347,42 @@ GJX_DEV void store16_at(void* ubase, uint32_t lane_bytes, uint4 v, bool wt) {
 #endif
   *reinterpret_cast<uint4*>(reinterpret_cast<char*>(ubase) + lane_bytes) = v;
 }
+// The two stores with the NON-TEMPORAL hint as well (`nt`), alone (`global_store_dwordx4 ... nt`) or on the write-through store
+// (aux bit 1: `buffer_store_dwordx4 ... offen sc1 nt`): the line is marked for early eviction — nothing in the launch reads it
+// again.  Overloads of their own, so that the code of every caller of the two-kind forms above stays what it was.  Both flags
+// are constants of the caller (a generated importance source's: ImportanceVariant::stores, gjx_plan_jit.hpp), so the choice
+// costs no instruction.  Measured at the importance batch's shape, 32 passes x 48 MB per launch into the same 1.5 GB:
+// tools/microbench/stream_store.hip, profiles/stream_store_summary.md.
+GJX_DEV void store16_at(void* ubase, uint32_t lane_bytes, uint4 v, bool wt, bool nt) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (nt) {
+    typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
+    v4u_t x;
+    x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+    if (wt) {
+      __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(ubase, 0, 0x7fffffff, 0x00020000);
+      __builtin_amdgcn_raw_buffer_store_b128(x, rs, (int)lane_bytes, 0, 18 /* sc1 nt */);
+    } else {
+      __builtin_nontemporal_store(x, reinterpret_cast<v4u_t*>(reinterpret_cast<char*>(ubase) + lane_bytes));
+    }
+    return;
+  }
+#endif
+  store16_at(ubase, lane_bytes, v, wt);
+}
+GJX_DEV void store16_out(void* p, uint4 v, bool wt, bool nt) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (nt) {  // (the first active lane's address is the wave-uniform base, the lane's distance from it the offset: lanes of one row)
+    const uint64_t a = (uint64_t)(uintptr_t)p;
+    const uint64_t first = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32)) << 32) |
+                           (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a);
+    const uint64_t base = first - (1ull << 30);
+    store16_at((void*)(uintptr_t)base, (uint32_t)(a - base), v, wt, true);
+    return;
+  }
+#endif
+  store16_out(p, v, wt);
+}
 // Ends the compiler's freedom to postpone an accumulator's update: the two running sums are needed HERE, as one register
 // pair.  Without it the generated importance kernels compute every site's log-density where the totals are stored, at the
 // end of the row, and keep all sampled values alive until then (40 VGPRs in the 10-latent quad kernel).  No instruction;

@@ -2407,6 +2407,21 @@ static int jit_form_pref() {  // GJX_JIT_FORM = one | pair | quad (test / tuning
   if (e && !strcmp(e, "pair")) return 2;
   return 4;  // quad; measured (tools/ab_importance.py, 1e6 particles): quad 13.1 / pair 13.6 / one 28.3 us per pass at 8 passes per launch
 }
+// The kind of store an escape forces on the quad form's launches, -1 without one: GJX_JIT_DEFINE=GJX_STORES_PLAIN | GJX_STORES_WT |
+// GJX_STORES_NT | GJX_STORES_NT_WT (as a -D the name means nothing to the generated source: it picks the source).  Any build
+// can be A/B-ed against itself that way (tools/ab_store_floor.py); read like GJX_JIT_FORM (getenv at each launch), where a launch
+// has the choice.  GJX_JIT_DEFINE holds ONE define, so a store-kind escape cannot be combined with another A/B knob
+// (GJX_WAVES_HINT=..., GJX_PHILOX_PLAIN_XOR), and like any value of it the name is passed as a -D to every generated kernel's
+// compilation and is part of its module's cache key: under an escape scan, SMC and tempered kernels are built anew as well.
+static int jit_stores_pref() {
+  const char* e = std::getenv("GJX_JIT_DEFINE");
+  if (!e || strncmp(e, "GJX_STORES_", 11) != 0) return -1;
+  using V = gjx_jit::ImportanceVariant;
+  static const struct { const char* name; int kind; } kEscapes[] = {{"PLAIN", V::kStorePlain}, {"WT", V::kStoreWt}, {"NT", V::kStoreNt}, {"NT_WT", V::kStoreNtWt}};
+  for (const auto& x : kEscapes)
+    if (!strcmp(e + 11, x.name)) return x.kind;
+  return -1;
+}
 // The waves-per-SIMD hint of a form (P particles per lane).  A SIMD's 512 VGPRs are shared in granules of 8: <= 128
 // registers is 4 waves, <= 96 5, <= 80 6, <= 72 7, <= 64 8 (allocated registers: the code object's .vgpr_count; a rocprofv3
 // trace's VGPR column is half of it).
@@ -2453,7 +2468,7 @@ int gjx_plan_compile_check(const gjx_plan* p, int impl) {
   for (int form = 1; form <= (gen == 1 ? 4 : 1); form *= 2) {  // PHILOX: one particle per lane, pairs, quads
     gjx_jit::Gen<CSite, CArg> g;
     // (the pair form is compiled as a launch runs it, plain stores: only gjx_plan_specialized_source shows its text under the write-through flag)
-    plan_gen_setup(g, p, gjx_jit::ImportanceVariant::of_source(form == 4 ? impl : impl & ~GJX_SOURCE_WT_STORES, form), jit_waves_hint(form));
+    plan_gen_setup(g, p, gjx_jit::ImportanceVariant::of_source(form == 4 ? impl : impl & ~(GJX_SOURCE_WT_STORES | GJX_SOURCE_NT_STORES), form), jit_waves_hint(form));
     gjx_jit::TableScope ts;
     if (!gjx_jit::compile_only(g.run(), gjx_jit::PlanKind::importance)) return GJX_ERR_UNSUPPORTED;
   }
@@ -2490,7 +2505,8 @@ static gjx_jit::Compiled& plan_compiled(gjx_plan* mp, const gjx_jit::ImportanceV
     if (ok && std::getenv("GJX_PLAN_JIT_VERBOSE")) {  // what the loaded code object allocates (the VGPR column of a rocprofv3 kernel trace is HALF of this)
       int regs = 0;
       if (hipFuncGetAttribute(&regs, HIP_FUNC_ATTRIBUTE_NUM_REGS, c.fn) != hipSuccess) (void)hipGetLastError();
-      fprintf(stderr, "gjx jit: %d particle(s) per lane%s%s%s: %d registers per lane\n", P, v.fused_tail ? ", fused tail" : "", v.wt_stores ? ", write-through stores" : "",
+      static const char* const kStores[] = {"", ", write-through stores", ", non-temporal stores", ", non-temporal write-through stores"};  // by ImportanceVariant::kStore*
+      fprintf(stderr, "gjx jit: %d particle(s) per lane%s%s%s: %d registers per lane\n", P, v.fused_tail ? ", fused tail" : "", kStores[v.stores & 3],
               v.full_outputs ? ", every output" : "", regs);
     }
     if (ok && hint > 0) {
@@ -2523,14 +2539,16 @@ int gjx_plan_prepare(gjx_plan* p, const gjx_keys* pk) {
   if (!p || !keys_ok(pk)) return GJX_ERR_INVALID;
   if (!gjx_jit::enabled()) return p->has_expr ? GJX_ERR_UNSUPPORTED : plan_device_table(p);
   // every variant a launch with these keys may take, named by a launch that leads to it: the particles per lane that n and
-  // the buffer alignment allow, then a single pass (the quad form's other kind of store) and every output passed (the quad
-  // form that asks nothing)
-  static const struct { int lane_particles; bool one_pass, every_output; } kLaunches[] = {
-      {1, false, false}, {2, false, false}, {4, false, false}, {4, true, false}, {4, false, true}, {4, true, true}};
-  const int most = lane_particles(pk, 0), pref = most > 1 ? jit_form_pref() : 1;
+  // the buffer alignment allow, then the quad form's kinds of store (a single pass; several passes; a batch of the
+  // benchmark's size or larger) and every output passed (the quad form that asks nothing).  Launches that lead to the
+  // same variant build it once.
+  static const struct { int lane_particles, n_pass; uint64_t bytes; bool every_output; } kLaunches[] = {
+      {1, 2, 0, false}, {2, 2, 0, false}, {4, 2, 0, false}, {4, 1, 0, false}, {4, 32, ~0ull, false},
+      {4, 2, 0, true},  {4, 1, 0, true},  {4, 32, ~0ull, true}};
+  const int most = lane_particles(pk, 0), pref = most > 1 ? jit_form_pref() : 1, stores = most >= 4 && pref >= 4 ? jit_stores_pref() : -1;
   bool ok = true;
   for (const auto& l : kLaunches)
-    ok = plan_compiled(p, gjx_jit::ImportanceVariant::of_launch(pk->impl, l.lane_particles < most ? l.lane_particles : most, pref, false, l.one_pass, l.every_output)).state == 1 && ok;
+    ok = plan_compiled(p, gjx_jit::ImportanceVariant::of_launch(pk->impl, l.lane_particles < most ? l.lane_particles : most, pref, false, l.n_pass, l.bytes, l.every_output, stores)).state == 1 && ok;
   if (ok) return GJX_OK;
   return jit_fallback_allowed() && !p->has_expr ? plan_device_table(p) : GJX_ERR_JIT;
 }
@@ -2586,8 +2604,13 @@ static int importance_launch(const gjx_plan* p, const gjx_keys* pk, int32_t n_pa
     for (int c = 0; c < n_value_cols; ++c) al |= (uintptr_t)value_cols[c];
     const bool every_output = score && logw && max_partials && row_e && row_s;
     // (GJX_JIT_FORM is asked only where there is a choice: a launch whose keys or buffers allow one particle per lane reads no environment)
-    const int allowed = lane_particles(pk, al);
-    const auto v = gjx_jit::ImportanceVariant::of_launch(pk->impl, allowed, allowed > 1 ? jit_form_pref() : 1, lse != nullptr, n_pass <= 1, every_output);
+    const int allowed = lane_particles(pk, al), pref = allowed > 1 ? jit_form_pref() : 1;
+    // what the launch's columns write: the rule of the kind of store asks it (ImportanceVariant::stores_of)
+    int n_cols = (score ? 1 : 0) + (logw ? 1 : 0);
+    for (int c = 0; c < n_value_cols; ++c) n_cols += value_cols[c] ? 1 : 0;
+    const uint64_t bytes = 4ull * n * (uint64_t)n_cols * (uint64_t)(n_pass > 1 ? n_pass : 1);
+    const auto v = gjx_jit::ImportanceVariant::of_launch(pk->impl, allowed, pref, lse != nullptr, n_pass, bytes, every_output,
+                                                         allowed >= 4 && pref >= 4 ? jit_stores_pref() : -1);
     gjx_jit::Compiled& c = plan_compiled(const_cast<gjx_plan*>(p), v);
     if (c.state != 1 && (!jit_fallback_allowed() || p->has_expr || p->scopes.n_scopes > 0)) return GJX_ERR_JIT;  // loud: never a silent 7x slower route
     if (c.state == 1) {

@@ -626,13 +626,15 @@ inline void emit_row_epilogue_per_lane(std::ostringstream& o, const char* row, b
 // block per pair and two draws (pk0 / pk1: the cipher key; pair0 [, pair1]: the pairs' counter words — defined by the
 // caller), one Box-Muller transform per pair and Normal site, every stored column one vector store at `store_at`.
 // The quad kernels store write-through (sc1) when a launch holds ONE pass (store16_out, gjx_device.hpp): the kernel's end
-// no longer waits for the write-back of its 48 MB — 4.94e10 -> 5.47e10 particles/s at one pass per launch; with many
-// passes per launch the write-back overlaps the following passes and plain stores are 1 % faster, hence the two source
-// variants (ImportanceVariant::wt_stores: `wt_one_pass` is a constant of the generated source).
+// no longer waits for the write-back of its 48 MB — 4.94e10 -> 5.47e10 particles/s at one pass per launch; a batch
+// of the benchmark's size takes the write-through store with the non-temporal hint as well, and several passes
+// that stay in the caches plain stores (ImportanceVariant::stores_of has the measurements), hence the source
+// variants (ImportanceVariant::stores: `wt_one_pass` is a constant of the generated source; `store_kind` is what a store
+// line passes for it — the non-temporal kinds add a second constant, `nt_stores`).
 template <class CSiteT, class CArgT>
 inline void emit_pair_lane_sites(std::ostringstream& o, LaneGroup<CSiteT, CArgT>& lanes, const std::string& ind, const std::string& store_at,
                                  const std::string& sc_guard = "", const std::string& ubase = "", const std::string& lane_bytes = "",
-                                 bool sc_known = false, const bool* skip = nullptr) {
+                                 bool sc_known = false, const bool* skip = nullptr, const std::string& store_kind = "wt_one_pass") {
   auto& em = lanes.em;
   const auto& sfx = lanes.kSfx;
   const CSiteT* sites = em[0].sites;
@@ -752,9 +754,9 @@ inline void emit_pair_lane_sites(std::ostringstream& o, LaneGroup<CSiteT, CArgT>
       const bool isint = SiteEmitter<CSiteT, CArgT>::is_int(st);
       const std::string vals = isint ? lanes.list("(uint32_t)vi" + Q) : lanes.list("f2u(vf" + Q, ")");
       if (P == 4 && !ubase.empty())  // (wave-uniform base + the lane's byte offset: gjx_device.hpp store16_at)
-        o << ind << "store16_at(reinterpret_cast<uint32_t*>(cols.out[" << st.out_col << "]) + " << ubase << ", " << lane_bytes << ", make_uint4(" << vals << "), wt_one_pass);\n";
+        o << ind << "store16_at(reinterpret_cast<uint32_t*>(cols.out[" << st.out_col << "]) + " << ubase << ", " << lane_bytes << ", make_uint4(" << vals << "), " << store_kind << ");\n";
       else if (P == 4)
-        o << ind << "store16_out(reinterpret_cast<uint32_t*>(cols.out[" << st.out_col << "]) + " << store_at << ", make_uint4(" << vals << "), wt_one_pass);\n";
+        o << ind << "store16_out(reinterpret_cast<uint32_t*>(cols.out[" << st.out_col << "]) + " << store_at << ", make_uint4(" << vals << "), " << store_kind << ");\n";
       else
         o << ind << "*reinterpret_cast<uint" << P << "*>(reinterpret_cast<uint32_t*>(cols.out[" << st.out_col << "]) + " << store_at << ") = make_uint" << P
           << "(" << vals << ");\n";
@@ -779,49 +781,70 @@ struct ImportanceVariant {
   bool fused_tail = false;  // the kernel folds the row sums itself (gjx_device.hpp lse_tail; launches that pass a gjx_lse_out).
                             // A variant of its own: inlined into every kernel, the fold cost 22 VGPRs — one wave per SIMD —
                             // on launches that never enter it (132 -> 110 in the 10-latent quad kernel)
-  bool wt_stores = false;  // the quad form's 16-byte stores are write-through (launches of ONE pass) instead of plain.  A variant
-                           // of its own: as a run-time flag every store was a uniform branch pair (88 scalar instructions per
-                           // row of the 10-latent kernel) and a basic block of its own
+  // The kinds of store: bit 0 write-through (sc1), bit 1 non-temporal (nt) — the two flags gjx_device.hpp store16_at takes.
+  enum : int { kStorePlain = 0, kStoreWt = 1, kStoreNt = 2, kStoreNtWt = 3 };
+  int stores = kStorePlain;  // the kind of the quad form's 16-byte stores.  A variant of its own: as a run-time flag every store was a
+                   // uniform branch pair (88 scalar instructions per row of the 10-latent kernel) and a basic block of its own
   bool full_outputs = false;  // the one-row quad form of a launch that passes score, logw, max_partials, row_e and row_s (and no
                               // gjx_lse_out): all five are known non-null, so the source asks nothing about them — as run-time
                               // questions they were 25 uniform branches and a compare per site in every row of the 10-latent
                               // kernel, and cut the row into some 40 basic blocks.  Every other form ignores the flag
 
-  // Which combinations a launch can take: pairs and quads under PHILOX only; the two kinds of store and the known outputs
+  // Which combinations a launch can take: pairs and quads under PHILOX only; the four kinds of store and the known outputs
   // exist at four particles per lane only, the known outputs not together with the fused tail.
   constexpr bool launched() const {
     return (impl == 0 || impl == 1) && (lane_particles == 1 || ((lane_particles == 2 || lane_particles == 4) && impl == 1)) &&
-           (!wt_stores || lane_particles == 4) && (!full_outputs || (lane_particles == 4 && !fused_tail));
+           stores >= kStorePlain && stores <= kStoreNtWt && (stores == kStorePlain || lane_particles == 4) && (!full_outputs || (lane_particles == 4 && !fused_tail));
   }
   // The variant of a launch.  `allowed`: how many adjacent particles a lane may own given the keys, n and the alignment of
   // the buffers (gjx_hip.hip lane_particles); `form_pref`: GJX_JIT_FORM, the most the caller wants (three become two).
-  static ImportanceVariant of_launch(int impl, int allowed, int form_pref, bool lse, bool one_pass, bool every_output) {
+  // `n_pass`, `bytes`: the passes of the launch and what its columns write in all; `stores_pref`: the kind of store an escape
+  // forces (GJX_JIT_DEFINE=GJX_STORES_*, gjx_hip.hip jit_stores_pref), -1 for the measured rule.
+  static constexpr ImportanceVariant of_launch(int impl, int allowed, int form_pref, bool lse, int n_pass, uint64_t bytes, bool every_output,
+                                               int stores_pref = -1) {
     const int most = impl == 1 ? (allowed < form_pref ? allowed : form_pref) : 1, P = most >= 4 ? 4 : (most >= 2 ? 2 : 1);
-    return ImportanceVariant{impl, P, lse, one_pass && P == 4, every_output && !lse && P == 4};
+    return ImportanceVariant{impl, P, lse, P == 4 ? (stores_pref >= 0 ? stores_pref : stores_of(n_pass, bytes)) : (int)kStorePlain, every_output && !lse && P == 4};
   }
+  // The kind of store of a quad launch: the measured rule (profiles/stream_store_summary.md; one MI355X, the 10-latent model,
+  // 1e6 particles, `python bench.py`, builds and kinds alternating in one job, five runs each).
+  //  * ONE pass: write-through — the kernel's end does not wait for the write-back of its 48 MB (4.94e10 -> 5.47e10
+  //    particles/s at one pass per launch).
+  //  * a batch of the size this was measured at (32 passes of 1e6 particles: 1.54 GB per launch, six times the Infinity
+  //    Cache) or larger: write-through AND non-temporal.  Against
+  //    the plain stores such a batch took before (parent 1.0072e11 particles/s, range 0.9999 .. 1.0097): write-through
+  //    +1.1 %, non-temporal +2.1 %, both +2.9 % (1.0343 .. 1.0504e11, every run above every run of the parent).  The launch
+  //    itself is 3 % shorter (0.308 -> 0.299 ms) and nothing is left dirty in the L2s for the boundary behind it.
+  //  * smaller batches: plain, as before.  Event-timed indications at 97 - 387 MB per launch favour write-through, not both
+  //    hints, and at 960 MB whole runs overlapped the parent's: nothing there went through the five-run protocol, so the
+  //    threshold is the measured size, not a crossover.
+  static constexpr uint64_t kStreamBytes = 1500000000ull;
+  static constexpr int stores_of(int n_pass, uint64_t bytes) { return n_pass <= 1 ? kStoreWt : (bytes >= kStreamBytes ? kStoreNtWt : kStorePlain); }
   // The variant the diagnostics name: `bits` = impl | GJX_SOURCE_*, `form` the particles per lane of a PHILOX source.  Any
   // combination of the flags stands, full outputs with the fused tail too (no launch takes it; the source exists); what a
   // form ignores is dropped: one particle per lane has one kind of store and asks about every output, and so does the pair
-  // form, which still says the kind of store in its text (`wt_one_pass`), so that flag stays with it.
+  // form, which still says the kind of store in its text (`wt_one_pass`), so that flag stays with it; the non-temporal bit
+  // exists at four particles per lane only.
   static ImportanceVariant of_source(int bits, int form) {
-    const int impl = bits & ~(GJX_SOURCE_FUSED_TAIL | GJX_SOURCE_WT_STORES | GJX_SOURCE_FULL_OUTPUTS), P = impl == 1 ? form : 1;
-    return ImportanceVariant{impl, P, (bits & GJX_SOURCE_FUSED_TAIL) != 0, (bits & GJX_SOURCE_WT_STORES) != 0 && P >= 2,
+    const int impl = bits & ~(GJX_SOURCE_FUSED_TAIL | GJX_SOURCE_WT_STORES | GJX_SOURCE_FULL_OUTPUTS | GJX_SOURCE_NT_STORES), P = impl == 1 ? form : 1;
+    return ImportanceVariant{impl, P, (bits & GJX_SOURCE_FUSED_TAIL) != 0,
+                             ((bits & GJX_SOURCE_WT_STORES) != 0 && P >= 2 ? kStoreWt : 0) | ((bits & GJX_SOURCE_NT_STORES) != 0 && P == 4 ? kStoreNt : 0),
                              (bits & GJX_SOURCE_FULL_OUTPUTS) != 0 && P == 4};
   }
   // The plan's slot of a variant a launch can take: the six (form, fused tail) pairs below four particles per lane, then the
-  // six quad variants.  Dense: kSlots of them, no two alike (the static_assert below walks them all).
-  static constexpr int kSlots = 12;
+  // twelve quad variants (guarded, fused tail, every output; four kinds of store each).  Dense: kSlots of them, no two alike
+  // (the static_assert below walks them all).
+  static constexpr int kSlots = 18;
   constexpr int slot() const {
     if (lane_particles < 4) return 2 * (lane_particles == 2 ? 2 : impl) + (fused_tail ? 1 : 0);
-    return 6 + (full_outputs ? 4 + (wt_stores ? 1 : 0) : 2 * (fused_tail ? 1 : 0) + (wt_stores ? 1 : 0));
+    return 6 + 4 * (full_outputs ? 2 : (fused_tail ? 1 : 0)) + stores;
   }
   const char* kname() const { return impl == 0 ? "gjx_plan_kernel_threefry" : "gjx_plan_kernel_philox"; }
 };
 constexpr bool importance_slots_distinct() {
   bool seen[ImportanceVariant::kSlots] = {};
   int n = 0;
-  for (int k = 0; k < 2 * 3 * 8; ++k) {  // every generator, form and flag combination
-    const ImportanceVariant v{k & 1, 1 << ((k >> 1) % 3), ((k / 6) & 1) != 0, ((k / 6) & 2) != 0, ((k / 6) & 4) != 0};
+  for (int k = 0; k < 2 * 3 * 16; ++k) {  // every generator, form, kind of store and flag combination
+    const ImportanceVariant v{k & 1, 1 << ((k >> 1) % 3), ((k / 6) & 1) != 0, ((k / 6) >> 2) & 3, ((k / 6) & 2) != 0};
     if (!v.launched()) continue;
     if (v.slot() < 0 || v.slot() >= ImportanceVariant::kSlots || seen[v.slot()]) return false;
     seen[v.slot()] = true, ++n;
@@ -903,7 +926,11 @@ struct Gen {
     }
     if (lds) o << "  bm_loads.bm_stage();\n";
     // (the text of the generated comment names the flag as it was called when it was a member of Gen: sources stay as they were)
-    o << "  const bool wt_one_pass = " << (v.wt_stores ? "true" : "false") << "; (void)wt_one_pass;  // (Gen::wt_stores)\n";
+    o << "  const bool wt_one_pass = " << ((v.stores & ImportanceVariant::kStoreWt) ? "true" : "false") << "; (void)wt_one_pass;  // (Gen::wt_stores)\n";
+    // the non-temporal kinds say so in a second constant, passed by every store line (the other sources keep their text)
+    const bool nt = (v.stores & ImportanceVariant::kStoreNt) != 0 && NP == 2;
+    if (nt) o << "  const bool nt_stores = true; (void)nt_stores;  // (ImportanceVariant::stores)\n";
+    const std::string kind = nt ? "wt_one_pass, nt_stores" : "wt_one_pass";
     o << "  const uint32_t pk0 = bt.n_pass > 1 ? bk0 : ks.parent.k0, pk1 = bt.n_pass > 1 ? bk1 : ks.parent.k1;\n";
     o << "  const uint64_t po = (uint64_t)pass * bt.pass_stride, ro = (uint64_t)pass * bt.row_stride;  // this pass's outputs\n";
     o << "  for (uint64_t g0 = (uint64_t)blockIdx.x * " << R << "; g0 < bt.rows_per_pass; g0 += (uint64_t)grid_x * " << R << ") {\n";
@@ -935,15 +962,15 @@ struct Gen {
     lanes.each([&](int, auto& e) { e.emit_scope_keys(); });
     o << "      const uint64_t pair0 = (lnA - 1u) >> 1;\n";
     if (NP == 2) o << "      const uint64_t pair1 = pair0 + 1u;\n";
-    emit_pair_lane_sites(o, lanes, "      ", "po + iA", "score", ubase ? "ub" : "", "lb", full);
+    emit_pair_lane_sites(o, lanes, "      ", "po + iA", "score", ubase ? "ub" : "", "lb", full, nullptr, kind);
     if (P == 4) {
       const std::string wb = lanes.list("f2u(w", ")"), sb = lanes.list("f2u(sc", ")");
       if (ubase) {
-        o << "      " << (full ? "" : "if (logw) ") << "store16_at(logw + ub, lb, make_uint4(" << wb << "), wt_one_pass);\n";
-        o << "      " << (full ? "" : "if (score) ") << "store16_at(score + ub, lb, make_uint4(" << sb << "), wt_one_pass);\n";
+        o << "      " << (full ? "" : "if (logw) ") << "store16_at(logw + ub, lb, make_uint4(" << wb << "), " << kind << ");\n";
+        o << "      " << (full ? "" : "if (score) ") << "store16_at(score + ub, lb, make_uint4(" << sb << "), " << kind << ");\n";
       } else {
-        o << "      if (logw) store16_out(logw + po + iA, make_uint4(" << wb << "), wt_one_pass);\n";
-        o << "      if (score) store16_out(score + po + iA, make_uint4(" << sb << "), wt_one_pass);\n";
+        o << "      if (logw) store16_out(logw + po + iA, make_uint4(" << wb << "), " << kind << ");\n";
+        o << "      if (score) store16_out(score + po + iA, make_uint4(" << sb << "), " << kind << ");\n";
       }
     } else {
       o << "      if (logw) *reinterpret_cast<float" << P << "*>(logw + po + iA) = make_float" << P << "(" << lanes.list("w") << ");\n";

@@ -292,10 +292,15 @@ int gjx_plan_set_params(gjx_plan* p, const float* params /*host*/, int n_params)
  * max_partials, row_e and row_s and no gjx_lse_out runs a variant whose source knows all five to be non-null and asks
  * nothing about them (built on the first such launch, or by gjx_plan_prepare); every other set of outputs runs the
  * guarded source, which is what the diagnostics show without the flag.  `impl | GJX_SOURCE_FULL_OUTPUTS` asks for the
- * variant; it combines with GJX_SOURCE_WT_STORES, and the other forms ignore it.  Same results either way. */
+ * variant; it combines with GJX_SOURCE_WT_STORES, and the other forms ignore it.  Same results either way.
+ * `impl | GJX_SOURCE_NT_STORES` asks for the four-particles-per-lane variant whose 16-byte stores carry the non-temporal
+ * hint; with GJX_SOURCE_WT_STORES as well, both hints on the write-through store.  Four kinds of store in all; which one a
+ * launch takes is a measured rule of the library (ImportanceVariant::of_launch), and GJX_JIT_DEFINE=GJX_STORES_PLAIN |
+ * GJX_STORES_WT | GJX_STORES_NT | GJX_STORES_NT_WT forces one for an A/B.  Below four particles per lane the bit is ignored. */
 #define GJX_SOURCE_FUSED_TAIL 0x100
 #define GJX_SOURCE_WT_STORES 0x200
 #define GJX_SOURCE_FULL_OUTPUTS 0x400
+#define GJX_SOURCE_NT_STORES 0x800
 int gjx_plan_specialized_source(const gjx_plan* p, int impl, char* buf, size_t buf_len, size_t* needed);
 /* Build (hiprtc) and load now the kernel gjx_importance_run would build on its first launch with
  * this key form, so that no launch pays the ~0.2 s compilation.  Optional; the oracle build returns

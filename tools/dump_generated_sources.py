@@ -5,7 +5,7 @@ A refactor of the generators (gjx_plan_jit.hpp) or of the layer that picks a var
 the change and diffs the two outputs: every line must be equal.  No GPU is needed: the library is loaded as tests/offline.py
 loads it, plans are host objects, and the models are the builders the CPU tests use, with fixed seeds.
 
-  importance  every model under both generators, GJX_JIT_FORM one / pair / quad and the eight combinations of GJX_SOURCE_*
+  importance  every model under both generators, GJX_JIT_FORM one / pair / quad and the sixteen combinations of GJX_SOURCE_*
   scan        five plans, both generators, one lane and quad, with and without the fused tail.  Scan plans have no source
               getter: the sources are what gjx_scan_plan_compile_check hands the compiler, recorded by a stand-in for gjx_jitc
               (GJX_JITC) that keeps its input and compiles nothing
@@ -47,7 +47,7 @@ from genjax._amd.ops import Ops  # noqa: E402
 from genjax._amd.runtime import use_ops  # noqa: E402
 from offline import DEVICE_HDR, HIP_LIB, JITC, OPTIONS, importance_source, llvm_tool  # noqa: E402
 
-FLAGS = (0, 0x100, 0x200, 0x300, 0x400, 0x500, 0x600, 0x700)  # include/gjx.h GJX_SOURCE_FUSED_TAIL | _WT_STORES | _FULL_OUTPUTS
+FLAGS = tuple(range(0, 0x1000, 0x100))  # include/gjx.h GJX_SOURCE_FUSED_TAIL | _WT_STORES | _FULL_OUTPUTS | _NT_STORES
 KIND_OPTIONS = {"importance": ["-fno-slp-vectorize"]}  # compile_options(PlanKind): the kind's own, after the four fixed ones
 A = abi.Arg
 LINES = []  # (kind, model, generator, form, flags, source)
