@@ -1890,6 +1890,23 @@ struct PredictiveArgs {
 };
 constexpr int kPredictiveBlock = 4;  // particles a lane takes per round of scalar loads
 
+// Kernel argument block of the PSIS launches over a plated plan (include/gjx_psis.h; the kernel is generated from the site
+// table, gjx_plan_jit.hpp GenPsis, and launched four times: mode 0 .. 2 are the passes of the radix select, mode 3 collects;
+// psis_select and psis_finish below are fixed).  Particles are on lanes, a workgroup's kPsisRows rows are wave-uniform.
+constexpr int kPsisRows = 4;         // rows per workgroup: 8 KB of LDS histogram each
+constexpr int kPsisBins = 2048;      // an 11-bit digit (the third pass uses the first 1024)
+constexpr int kPsisMaxTail = 4095;   // GJX_PSIS_MAX_TAIL: M + 1 keys sort inside one workgroup's LDS
+struct PsisArgs {
+  const float* x[kTemperMaxLatents];  // latent columns: one vector load per lane and particle
+  uint32_t* hist;                     // [n_rows][kPsisBins]: zero before pass 0, cleared by psis_select after every pass
+  uint32_t* state;                    // [n_rows][4]: key prefix (after pass 2: k(tT)), remaining rank, collected, bad
+  uint32_t* keys;                     // [n_rows][M + 1]: the keys below k(tT), in arrival order (mode 3)
+  double* part;                       // [W][n_rows]: the chunks' partials of G (mode 3)
+  uint32_t n, per, W;                 // particles, particles per chunk, chunks
+  uint32_t M;                         // tail_len
+  uint32_t mode;
+};
+
 // ---- the fixed device code of the backward-simulation and backward-move kernels ---------------------------------------
 // What the site table decides reaches it as template arguments: the generator, the number of carry components D, and a
 // generated struct whose static member is the table's walk — Trans::trans_lp(a, tabs, st, nx), the f32 sum of the transition
@@ -2234,6 +2251,239 @@ GJX_DEV void predictive_fold(const double* part, uint32_t W, uint32_t n_rows, ui
     for (int j = 0; j < 5; ++j) acc[j] = acc[j] + at[(size_t)j * plane + (size_t)k * n_rows];
 #pragma unroll
   for (int j = 0; j < 5; ++j) out[((size_t)s * 5 + j) * n_rows + d] = acc[j];
+}
+#endif
+
+// ---- the fixed device code of the PSIS kernels (include/gjx_psis.h) ------------------------------------------------------
+// The total order of the header: an integer key per f32 entry, every NaN last.  psis_unkey is its inverse on everything but
+// the NaNs (which all come back as 0x7FFFFFFF).
+GJX_DEV uint32_t psis_key(float t) {
+  const uint32_t b = f2u(t);
+  return t != t ? 0xffffffffu : b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+}
+GJX_DEV float psis_unkey(uint32_t k) { return u2f((k >> 31) ? k ^ 0x80000000u : ~k); }
+// Zero the workgroup's kPsisRows histograms (the select passes; the collect pass uses the same LDS for its reduction).
+GJX_DEV void psis_begin(const PsisArgs& a, uint32_t* sh) {
+  if (a.mode < 3u)
+    for (uint32_t b = threadIdx.x; b < (uint32_t)(kPsisRows * kPsisBins); b += 256u) sh[b] = 0u;
+  __syncthreads();
+}
+// The row's key prefix (passes 1, 2) or cutoff key k(tT) (the collect pass): wave-uniform.
+GJX_DEV uint32_t psis_row_key(const PsisArgs& a, uint32_t d) { return a.mode == 0u ? 0u : a.state[4u * (size_t)d]; }
+// One entry t of row d (h: the row's LDS histogram; rkey, tT: psis_row_key and its f32 value; on: the lane holds a particle
+// of the chunk and the row exists).
+//   modes 0 .. 2   count digit `mode` of the key (bits 31..21, 20..10, 9..0) where the higher digits equal the prefix's;
+//   mode 3         a key below k(tT) is appended to the row's buffer (exactly c_less <= M of them exist: the slot test
+//                  only keeps a corrupted workspace from writing past the buffer); every other FINITE entry adds
+//                  exp_f32(f32(tT - t)) to the lane's float64 sum; non-finite entries are counted.
+GJX_DEV void psis_take(const PsisArgs& a, uint32_t* h, uint32_t d, uint32_t rkey, float tT, bool on, float t, double& g, uint32_t& bad) {
+  const uint32_t k = psis_key(t);
+  if (a.mode < 3u) {
+    const uint32_t hs = a.mode == 1u ? 21u : 10u, ds = a.mode == 0u ? 21u : a.mode == 1u ? 10u : 0u;
+    const bool match = a.mode == 0u || (k >> hs) == (rkey >> hs);
+    // (One LDS atomic per lane.  The top digit of a row's entries is nearly constant, so in pass 0 most lanes of a wave add to
+    // one address; counting the first lane's digit once per wave — a ballot and a population count — was measured and is
+    // SLOWER, 1.46 against 1.11 ms per 1e9 entries: profiles/psis_summary.md.)
+    if (on && match) atomicAdd(&h[(k >> ds) & (a.mode == 2u ? 0x3ffu : 0x7ffu)], 1u);
+    return;
+  }
+  if (!on) return;
+  const bool finite = (f2u(t) & 0x7f800000u) != 0x7f800000u;
+  bad += finite ? 0u : 1u;
+  if (k < rkey) {
+    const uint32_t slot = atomicAdd(&a.state[4u * (size_t)d + 2u], 1u);
+    if (slot <= a.M) a.keys[(size_t)d * (a.M + 1u) + slot] = k;
+  } else if (finite) {
+    g = g + (double)pointwise_exp(tT - t);
+  }
+}
+// After the chunk: the select passes add the workgroup's histograms to the rows' global ones (integer atomics; a plain store
+// when the row has one chunk); the collect pass folds the lanes' sums by a fixed binary tree and stores one partial per
+// (chunk, row), and adds the lanes' non-finite counts to the row's (integer atomics).
+GJX_DEV void psis_flush(const PsisArgs& a, uint32_t* sh, uint32_t n_rows, uint32_t r0, const double (&g)[kPsisRows], const uint32_t (&bad)[kPsisRows]) {
+  __syncthreads();
+  if (a.mode < 3u) {
+    const uint32_t bins = a.mode == 2u ? (uint32_t)kPsisBins / 2u : (uint32_t)kPsisBins;
+#pragma unroll
+    for (int j = 0; j < kPsisRows; ++j) {
+      const uint32_t d = r0 + (uint32_t)j;
+      if (d >= n_rows) break;
+      for (uint32_t b = threadIdx.x; b < bins; b += 256u) {
+        const uint32_t v = sh[j * kPsisBins + b];
+        uint32_t* at = a.hist + (size_t)d * kPsisBins + b;
+        if (a.W == 1u) *at = v;
+        else if (v) atomicAdd(at, v);
+      }
+    }
+    return;
+  }
+  double* red = reinterpret_cast<double*>(sh);
+#pragma unroll
+  for (int j = 0; j < kPsisRows; ++j) {
+    const uint32_t d = r0 + (uint32_t)j;
+    red[threadIdx.x] = g[j];
+    __syncthreads();
+    for (uint32_t s = 128u; s > 0u; s >>= 1) {
+      if (threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
+      __syncthreads();
+    }
+    if (d < n_rows) {
+      if (threadIdx.x == 0u) a.part[(size_t)blockIdx.y * n_rows + d] = red[0];
+      if (bad[j]) atomicAdd(&a.state[4u * (size_t)d + 3u], bad[j]);
+    }
+    __syncthreads();
+  }
+}
+#ifndef __HIPCC_RTC__
+// Between the passes (the library's own launch, one WAVE per row, `shw`: 64 words of LDS of that wave; every wave of the
+// workgroup calls it, `live` says whether its row exists): the digit at which the cumulative count reaches the remaining rank
+// (M + 1 at pass 0) extends the prefix, the rank is reduced by the count below it, the histogram is cleared.  After pass 2 the
+// prefix is k(tT), M + 1 - rank is c_less, and the collect pass's two counters are zeroed.
+GJX_DEV void psis_select(uint32_t* hist, uint32_t* state, uint32_t d, bool live, uint32_t pass, uint32_t M, uint32_t* shw) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t per = (pass == 2u ? (uint32_t)kPsisBins / 2u : (uint32_t)kPsisBins) / 64u;
+  uint32_t* h = hist + (size_t)d * kPsisBins + lane * per;
+  uint32_t sum = 0u;
+  for (uint32_t q = 0; q < per; ++q) sum += h[q];
+  shw[lane] = sum;
+  __syncthreads();
+  uint32_t below = 0u;
+  for (uint32_t l = 0; l < lane; ++l) below += shw[l];
+  const uint32_t prefix = pass == 0u ? 0u : state[4u * (size_t)d], rank = pass == 0u ? M + 1u : state[4u * (size_t)d + 1u];
+  if (!live) return;
+  if (below < rank && rank - below <= sum) {  // this lane's bins hold the rank-th entry
+    uint32_t cum = below, q = 0u;
+    for (; q + 1u < per && cum + h[q] < rank; ++q) cum += h[q];
+    state[4u * (size_t)d] = prefix | ((lane * per + q) << (pass == 0u ? 21u : pass == 1u ? 10u : 0u));
+    state[4u * (size_t)d + 1u] = rank - cum;
+    if (pass == 2u) state[4u * (size_t)d + 2u] = state[4u * (size_t)d + 3u] = 0u;
+  }
+  for (uint32_t q = 0; q < per; ++q) h[q] = 0u;
+}
+
+// The sums and maxima of psis_finish: all 256 lanes call, a fixed binary tree in LDS, the result to every lane.
+GJX_DEV double psis_block_sum(double v, double* red) {
+  __syncthreads();
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (uint32_t s = 128u; s > 0u; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
+    __syncthreads();
+  }
+  return red[0];
+}
+GJX_DEV double psis_block_max(double v, double* red) {
+  __syncthreads();
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (uint32_t s = 128u; s > 0u; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x + s] > red[threadIdx.x] ? red[threadIdx.x + s] : red[threadIdx.x];
+    __syncthreads();
+  }
+  return red[0];
+}
+// The last launch, one workgroup of 256 per row d (include/gjx_psis.h: tail, fit, weights, estimate).  LDS: the row's keys
+// (sk: 4096 words), the exceedances and then the smoothed log-weights (sx: 4096 doubles), the tree (red: 256 doubles), the
+// candidates (cth, cl: 96 doubles each; Gn <= 30 + 63).  Every branch below is uniform over the workgroup.
+GJX_DEV void psis_finish(const PsisArgs& a, uint32_t n_rows, uint32_t d, double* out, float* tail, uint32_t* sk, double* sx, double* red,
+                         double* cth, double* cl) {
+  const uint32_t tid = threadIdx.x, M = a.M;
+  uint32_t P = 8u;
+  while (P < M + 1u) P <<= 1;  // (M <= 4095: P <= 4096)
+  const uint32_t kT = a.state[4u * (size_t)d], rank = a.state[4u * (size_t)d + 1u];
+  const uint32_t c_less = rank >= 1u && rank <= M + 1u ? M + 1u - rank : 0u;
+  // the collected keys, the cutoff in the slots that are left (the entries tied with it), the padding above everything
+  for (uint32_t i = tid; i < P; i += 256u) sk[i] = i < c_less ? a.keys[(size_t)d * (M + 1u) + i] : i <= M ? kT : 0xffffffffu;
+  for (uint32_t k = 2u; k <= P; k <<= 1)
+    for (uint32_t j = k >> 1; j > 0u; j >>= 1) {
+      __syncthreads();
+      for (uint32_t i = tid; i < P; i += 256u) {
+        const uint32_t o = i ^ j;
+        if (o > i) {
+          const uint32_t u = sk[i], v = sk[o];
+          if ((i & k) == 0u ? u > v : u < v) {
+            sk[i] = v;
+            sk[o] = u;
+          }
+        }
+      }
+    }
+  __syncthreads();
+  if (tail)
+    for (uint32_t i = tid; i <= M; i += 256u) tail[(size_t)d * (M + 1u) + i] = psis_unkey(sk[i]);
+  double G = 0.0;
+  for (uint32_t k = 0; k < a.W; ++k) G = G + a.part[(size_t)k * n_rows + d];
+  const double B = G - (double)(M - c_less), bad = (double)a.state[4u * (size_t)d + 3u];
+  const double sd = (double)psis_unkey(sk[0]), td = (double)psis_unkey(sk[M]);
+  const double inf = (double)__builtin_inff(), nan = (double)__builtin_nanf("");
+  double khat = inf, sigma = nan, elpd = nan;
+  if (bad == 0.0) {
+    const double e_cut = exp(sd - td), Md = (double)M;
+    for (uint32_t i = tid; i < M; i += 256u) sx[i] = exp(sd - (double)psis_unkey(sk[M - 1u - i])) - e_cut;  // x_{i + 1}
+    __syncthreads();
+    const double xM = sx[M - 1u], xstar = sx[(uint32_t)(Md / 4.0 + 0.5) - 1u];
+    const bool smooth = xM > 0.0 && xstar > 0.0;
+    if (smooth) {
+      const uint32_t Gn = 30u + (uint32_t)sqrt(Md);
+      for (uint32_t j = 1u; j <= Gn; ++j) {
+        const double th = 1.0 / xM + (1.0 - sqrt((double)Gn / ((double)j - 0.5))) / (3.0 * xstar);
+        double acc = 0.0;
+        for (uint32_t i = tid; i < M; i += 256u) acc = acc + log1p(-th * sx[i]);
+        const double kj = psis_block_sum(acc, red) / Md;
+        if (tid == 0u) {
+          cth[j - 1u] = th;
+          cl[j - 1u] = Md * (log(-th / kj) - kj - 1.0);
+        }
+      }
+      __syncthreads();
+      double tw = 0.0;
+      if (tid < Gn) {
+        double den = 0.0;
+        for (uint32_t l = 0; l < Gn; ++l) den = den + exp(cl[l] - cl[tid]);
+        tw = cth[tid] / den;
+      }
+      const double theta = psis_block_sum(tw, red);
+      double acc = 0.0;
+      for (uint32_t i = tid; i < M; i += 256u) acc = acc + log1p(-theta * sx[i]);
+      const double kk = psis_block_sum(acc, red) / Md;
+      sigma = -kk / theta;
+      khat = (kk * Md + 5.0) / (Md + 10.0);
+    }
+    __syncthreads();  // (sx: the exceedances have been read; the log-weights take their place)
+    for (uint32_t i = tid; i < M; i += 256u) {
+      double lw = sd - (double)psis_unkey(sk[M - 1u - i]);
+      if (smooth) {
+        const double lp = log1p(-((double)(i + 1u) - 0.5) / Md);
+        const double q = khat == 0.0 ? -sigma * lp : sigma * expm1(-khat * lp) / khat;
+        lw = log(q + e_cut);
+        lw = lw < 0.0 ? lw : 0.0;
+      }
+      sx[i] = lw;
+    }
+    __syncthreads();
+    double m1 = -inf, m2 = -inf;
+    for (uint32_t i = tid; i < M; i += 256u) {
+      const double e1 = sx[i] + (double)psis_unkey(sk[M - 1u - i]);
+      m1 = e1 > m1 ? e1 : m1;
+      m2 = sx[i] > m2 ? sx[i] : m2;
+    }
+    m1 = psis_block_max(m1, red);
+    m2 = psis_block_max(m2, red);
+    m1 = sd > m1 ? sd : m1;
+    m2 = sd - td > m2 ? sd - td : m2;
+    double s1 = 0.0, s2 = 0.0;
+    for (uint32_t i = tid; i < M; i += 256u) {
+      s1 = s1 + exp(sx[i] + (double)psis_unkey(sk[M - 1u - i]) - m1);
+      s2 = s2 + exp(sx[i] - m2);
+    }
+    s1 = psis_block_sum(s1, red) + (double)(a.n - M) * exp(sd - m1);
+    s2 = psis_block_sum(s2, red) + B * exp(sd - td - m2);
+    elpd = (m1 + log(s1)) - (m2 + log(s2));
+  }
+  if (tid == 0u) {
+    const double v[7] = {elpd, khat, sigma, sd, td, B, bad};
+    for (int q = 0; q < 7; ++q) out[(size_t)q * n_rows + d] = v[q];
+  }
 }
 #endif
 #endif  // __HIP_DEVICE_COMPILE__

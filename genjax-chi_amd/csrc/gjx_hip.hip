@@ -16,6 +16,7 @@
 #include "../../include/gjx_temper.h"
 #include "../../include/gjx_plate.h"
 #include "../../include/gjx_pointwise.h"
+#include "../../include/gjx_psis.h"
 #include "../../include/gjx_predictive.h"
 #include "../../include/gjx_temper_cov.h"
 // The library's own kernels keep the Philox round's plain XOR chain (gjx_device.hpp xor3): with v_bitop3_b32 the one-filter
@@ -4842,11 +4843,11 @@ int gjx_backmove_run(gjx_backsim_plan* p, const gjx_backmove_io* io, void* ws, s
 // Tempered SMC for static models (include/gjx_temper.h): the move kernel is generated from the site table
 // (gjx_plan_jit.hpp GenTemper); the ESS ladder is the fixed kernel below
 // =====================================================================================================================
-// The four generated kernels of a tempered plan: the move (include/gjx_temper.h), the covariance move
-// (include/gjx_temper_cov.h), the pointwise kernel (include/gjx_pointwise.h: one source, whatever the generator) and the
-// predictive kernel (include/gjx_predictive.h).  The last two exist for a plan that passes pointwise_plan_ok only
-// (kTemperKernels below has what else they differ in).
-enum TemperKernel { kTemperMove, kTemperCovMove, kTemperPointwise, kTemperPredictive, kTemperKernelCount };
+// The five generated kernels of a tempered plan: the move (include/gjx_temper.h), the covariance move
+// (include/gjx_temper_cov.h), the pointwise kernel (include/gjx_pointwise.h: one source, whatever the generator), the
+// predictive kernel (include/gjx_predictive.h) and the PSIS kernel (include/gjx_psis.h: one source too).  The last three exist
+// for a plan that passes pointwise_plan_ok only (kTemperKernels below has what else they differ in).
+enum TemperKernel { kTemperMove, kTemperCovMove, kTemperPointwise, kTemperPredictive, kTemperPsis, kTemperKernelCount };
 struct gjx_temper_plan {
   int n_sites, n_latents;
   int n_params;   // values set by gjx_temper_plan_set_params
@@ -4857,7 +4858,7 @@ struct gjx_temper_plan {
   ExprStore expr;
   std::vector<void*> dev_owned;  // per-row tables of categorical (observed) sites
   std::mutex mu;
-  gjx_jit::CompiledKernel jit[kTemperKernelCount][2];  // by TemperKernel and generator (the pointwise kernel: [0] alone)
+  gjx_jit::CompiledKernel jit[kTemperKernelCount][2];  // by TemperKernel and generator (the pointwise and PSIS kernels: [0] alone)
   // include/gjx_plate.h: PLATED sites (gjx_temper_plan_create_plated) and their data columns (gjx_temper_plan_set_data)
   bool plated = false;
   int max_data = -1;  // highest data column the table reads
@@ -4873,7 +4874,7 @@ struct gjx_temper_plan {
 namespace {
 constexpr unsigned kTemperMaxGrid = 256 * 16;  // workgroups of 256 particles, grid-stride beyond
 
-// What the four generated kernels of a tempered plan (TemperKernel) differ in on the host side.
+// What the five generated kernels of a tempered plan (TemperKernel) differ in on the host side.
 struct TemperKernelDesc {
   const char* entry;
   gjx_jit::PlanKind kind;
@@ -4883,8 +4884,9 @@ struct TemperKernelDesc {
 constexpr TemperKernelDesc kTemperKernels[kTemperKernelCount] = {{"gjx_temper_move_kernel", gjx_jit::PlanKind::temper, true, false},
                                                 {"gjx_temper_move_cov_kernel", gjx_jit::PlanKind::temper, true, false},
                                                 {"gjx_pointwise_kernel", gjx_jit::PlanKind::temper, false, true},
-                                                {"gjx_predictive_kernel", gjx_jit::PlanKind::predictive, true, true}};
-// Has the plan a pointwise (and a predictive) source?  A PLATED site, and no per-particle input column anywhere in the table
+                                                {"gjx_predictive_kernel", gjx_jit::PlanKind::predictive, true, true},
+                                                {"gjx_psis_kernel", gjx_jit::PlanKind::psis, false, true}};
+// Has the plan a pointwise (and a predictive, and a PSIS) source?  A PLATED site, and no per-particle input column anywhere in the table
 // (the io structs have none).
 bool pointwise_plan_ok(const gjx_temper_plan* p) { return p && p->plated && p->max_input < 0; }
 // the guard of the exported *_source / *_compile_check functions of kernel k
@@ -4904,6 +4906,10 @@ std::string temper_source(const gjx_temper_plan* p, TemperKernel k, int impl, Pl
   if (k == kTemperPredictive) {
     gjx_jit::GenPredictive<CSite, CArg> g;
     g.impl = impl;
+    return run(g);
+  }
+  if (k == kTemperPsis) {
+    gjx_jit::GenPsis<CSite, CArg> g;
     return run(g);
   }
   gjx_jit::GenTemper<CSite, CArg> g;
@@ -5316,6 +5322,37 @@ __global__ __launch_bounds__(kBlock) void k_predictive_fold(const double* part, 
 #endif
 }
 
+// ---- PSIS-LOO over a plated plan (include/gjx_psis.h) ---------------------------------------------------------------------
+constexpr uint64_t kPsisWorkgroups = 2048;  // blocks of kPsisRows rows x chunks of particles: about this many, whatever D is
+// between the select passes: one wave per row (gjx_device.hpp psis_select)
+__global__ __launch_bounds__(kBlock) void k_psis_select(uint32_t* hist, uint32_t* state, uint32_t n_rows, uint32_t pass, uint32_t M) {
+#if defined(__HIP_DEVICE_COMPILE__)  // (the header's device-only section)
+  __shared__ uint32_t shw[kBlock];
+  const uint32_t w = threadIdx.x >> 6, d = blockIdx.x * (kBlock / 64) + w;
+  psis_select(hist, state, d < n_rows ? d : n_rows - 1u, d < n_rows, pass, M, shw + 64u * w);
+#endif
+}
+// the last launch: one workgroup per row (gjx_device.hpp psis_finish)
+__global__ __launch_bounds__(kBlock) void k_psis_finish(PsisArgs a, uint32_t n_rows, double* out, float* tail) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __shared__ uint32_t sk[kPsisMaxTail + 1];
+  __shared__ double sx[kPsisMaxTail + 1], red[kBlock], cth[96], cl[96];
+  psis_finish(a, n_rows, blockIdx.x, out, tail, sk, sx, red, cth, cl);
+#endif
+}
+// The workspace of gjx_temper_psis: the rows' histograms, states and key buffers, the chunks' partials.
+struct PsisScratch {
+  uint32_t *hist, *state, *keys;
+  double* part;
+};
+bool psis_carve(Carver& cv, uint64_t n_rows, uint32_t W, uint32_t M, PsisScratch* sc) {
+  sc->hist = cv.take<uint32_t>((size_t)n_rows * kPsisBins);
+  sc->state = cv.take<uint32_t>((size_t)n_rows * 4);
+  sc->keys = cv.take<uint32_t>((size_t)n_rows * ((size_t)M + 1));
+  sc->part = cv.take<double>((size_t)W * n_rows);
+  return cv.ok;
+}
+
 // gjx_temper_plan_create (allow_plated = false) and gjx_temper_plan_create_plated (include/gjx_plate.h)
 int temper_plan_create(const gjx_site* sites, int n_sites, uint32_t flags, gjx_temper_plan** out, bool allow_plated) {
   if (!sites || !out || n_sites < 1 || n_sites > GJX_MAX_SITES || flags != 0u) return GJX_ERR_INVALID;
@@ -5462,13 +5499,13 @@ uint32_t plated_chunks(uint64_t n, uint64_t n_rows, uint64_t tile, uint64_t targ
   const uint64_t by_grid = (target + tiles - 1) / tiles;  // (>= 1)
   return (uint32_t)(by_n < by_grid ? by_n : by_grid);
 }
-// What gjx_temper_pointwise and gjx_temper_predictive share, up to and with the first launch: kernel k of the plan over the
-// rows x chunks grid, its argument block A (PointwiseArgs / PredictiveArgs: x, part, n, W, per are filled here, `fill` adds
-// the entry point's own fields).  `ok`: the entry point's own conditions (checked with the common ones: GJX_ERR_INVALID);
-// `planes`: float64 planes of [W][n_rows] in the workspace.  The checks run in the order INVALID, WORKSPACE, UNSUPPORTED, JIT.
-template <class Args, class IO, class Fill>
-int plated_launch(gjx_temper_plan* p, TemperKernel k, int impl, const IO* io, bool ok, uint64_t tile, uint64_t target, size_t planes,
-                  gjx_stream s, Args& A, Fill fill) {
+// What gjx_temper_pointwise, gjx_temper_predictive and gjx_temper_psis begin with: the checks in the order INVALID, WORKSPACE,
+// UNSUPPORTED, JIT, then kernel k of the plan (`c`) and the common fields of its argument block A (PointwiseArgs /
+// PredictiveArgs / PsisArgs: x, n, W, per) over the grid of `tile` rows x chunks.  `ok`: the entry point's own conditions
+// (checked with the common ones: GJX_ERR_INVALID); `need(W, D)`: the workspace bytes of the entry point.
+template <class Args, class IO, class Need>
+int plated_prepare(gjx_temper_plan* p, TemperKernel k, int impl, const IO* io, bool ok, uint64_t tile, uint64_t target, Need need, Args& A,
+                   gjx_jit::CompiledKernel** c) {
   if (!pointwise_plan_ok(p) || !io || !ok || !p->has_data || io->n < 1 || io->n >= (1ull << 31) || !io->out || p->n_params <= p->max_param ||
       ((uintptr_t)io->ws & 7) != 0)
     return GJX_ERR_INVALID;
@@ -5478,14 +5515,26 @@ int plated_launch(gjx_temper_plan* p, TemperKernel k, int impl, const IO* io, bo
     A.x[l] = io->x[l];
   }
   const uint32_t D = p->data.n_rows, W = plated_chunks(io->n, D, tile, target);
-  if (!io->ws || io->ws_bytes < (size_t)W * (size_t)D * planes * sizeof(double)) return GJX_ERR_WORKSPACE;
+  if (!io->ws || io->ws_bytes < need(W, D)) return GJX_ERR_WORKSPACE;
   if (!gjx_jit::enabled()) return GJX_ERR_UNSUPPORTED;  // a generated kernel only
-  gjx_jit::CompiledKernel* c = temper_compiled(p, k, impl);
-  if (!c) return GJX_ERR_JIT;
-  A.part = static_cast<double*>(io->ws);
+  *c = temper_compiled(p, k, impl);
+  if (!*c) return GJX_ERR_JIT;
   A.n = (uint32_t)io->n;
   A.W = W;
   A.per = (uint32_t)((io->n + W - 1) / W);
+  return GJX_OK;
+}
+// What gjx_temper_pointwise and gjx_temper_predictive share, up to and with the first launch: plated_prepare with a workspace
+// of `planes` float64 planes of [W][n_rows] (A.part), `fill` adds the entry point's own fields to A.
+template <class Args, class IO, class Fill>
+int plated_launch(gjx_temper_plan* p, TemperKernel k, int impl, const IO* io, bool ok, uint64_t tile, uint64_t target, size_t planes,
+                  gjx_stream s, Args& A, Fill fill) {
+  gjx_jit::CompiledKernel* c = nullptr;
+  if (int rc = plated_prepare(p, k, impl, io, ok, tile, target,
+                              [&](uint32_t W, uint32_t D) { return (size_t)W * (size_t)D * planes * sizeof(double); }, A, &c))
+    return rc;
+  const uint32_t D = p->data.n_rows, W = A.W;
+  A.part = static_cast<double*>(io->ws);
   fill(A);
   PlanParams prm = p->prm;
   PlanTables tabs = c->tabs;
@@ -5626,6 +5675,60 @@ int gjx_temper_predictive(gjx_temper_plan* p, const gjx_keys* key, const gjx_pre
   if (rc) return rc;
   const uint32_t D = p->data.n_rows;
   k_predictive_fold<<<dim3((unsigned)nrows_of(D), (unsigned)n_plated), kBlock, 0, S(s)>>>(A.part, A.W, D, io->out);
+  return launch_status();
+}
+
+int gjx_psis_version(int* major, int* minor) { return version_out(major, minor, GJX_PSIS_VERSION_MAJOR, GJX_PSIS_VERSION_MINOR); }
+uint32_t gjx_psis_tail_len(uint64_t n, double r_eff) {
+  if (n < 1 || n >= (1ull << 31) || !(r_eff > 0.0) || !(r_eff - r_eff == 0.0)) return 0;
+  const double by_n = floor(0.2 * (double)n), by_root = ceil(3.0 * sqrt((double)n / r_eff));
+  double m = by_n < by_root ? by_n : by_root;
+  if (m > (double)GJX_PSIS_MAX_TAIL) m = (double)GJX_PSIS_MAX_TAIL;
+  return m < 5.0 ? 0u : (uint32_t)m;
+}
+size_t gjx_psis_workspace_bytes(uint64_t n, uint64_t n_rows, uint32_t tail_len) {
+  const uint32_t W = plated_chunks(n, n_rows, kPsisRows, kPsisWorkgroups);
+  if (!W || tail_len < 5 || tail_len > GJX_PSIS_MAX_TAIL) return 0;
+  Carver cv{nullptr, ~(size_t)0};
+  PsisScratch sc;
+  (void)psis_carve(cv, n_rows, W, tail_len, &sc);
+  return ~(size_t)0 - cv.left;
+}
+int gjx_psis_source(const gjx_temper_plan* p, char* buf, size_t buf_len, size_t* needed) {
+  return temper_source_out(p, kTemperPsis, 0, buf, buf_len, needed);
+}
+int gjx_psis_compile_check(const gjx_temper_plan* p) { return temper_compile_check(p, kTemperPsis, 0); }
+int gjx_temper_psis(gjx_temper_plan* p, const gjx_psis_io* io, gjx_stream s) {
+  const bool ok = io && io->tail_len >= 5 && io->tail_len <= GJX_PSIS_MAX_TAIL && io->tail_len < io->n;
+  PsisArgs A;
+  gjx_jit::CompiledKernel* c = nullptr;
+  if (int rc = plated_prepare(p, kTemperPsis, 0, io, ok, kPsisRows, kPsisWorkgroups,
+                              [&](uint32_t, uint32_t D) { return gjx_psis_workspace_bytes(io->n, D, io->tail_len); }, A, &c))
+    return rc;
+  const uint32_t D = p->data.n_rows;
+  Carver cv{(char*)io->ws, io->ws_bytes};
+  PsisScratch sc;
+  if (!psis_carve(cv, D, A.W, io->tail_len, &sc)) return GJX_ERR_WORKSPACE;
+  A.hist = sc.hist; A.state = sc.state; A.keys = sc.keys; A.part = sc.part;
+  A.M = io->tail_len;
+  // (a row with one chunk stores its histogram; with more the workgroups add to it: zero before pass 0, cleared by psis_select after)
+  if (A.W > 1 && hipMemsetAsync(sc.hist, 0, (size_t)D * kPsisBins * sizeof(uint32_t), S(s)) != hipSuccess) {
+    (void)hipGetLastError();
+    return GJX_ERR_LAUNCH;
+  }
+  PlanParams prm = p->prm;
+  PlanTables tabs = c->tabs;
+  PlateData pd = p->data;
+  void* args[] = {&A, &prm, &tabs, &pd};
+  const unsigned blocks = (D + kPsisRows - 1) / kPsisRows;
+  for (uint32_t mode = 0; mode < 4; ++mode) {
+    A.mode = mode;
+    if (int rc = launch_generated(c->fn, blocks, A.W, kBlock, s, args)) return rc;
+    if (mode == 3) break;
+    k_psis_select<<<(D + kBlock / 64 - 1) / (kBlock / 64), kBlock, 0, S(s)>>>(sc.hist, sc.state, D, mode, A.M);
+    if (int rc = launch_status()) return rc;
+  }
+  k_psis_finish<<<D, kBlock, 0, S(s)>>>(A, D, io->out, io->tail);
   return launch_status();
 }
 

@@ -1772,6 +1772,26 @@ struct GenTemper {
 // Lanes at or past n_rows leave at once and store nothing.  No LDS, no barrier, no draw: one source per plan, whatever impl.
 // The source holds no data value, no parameter value and neither n nor n_rows.  (A table that reads a per-particle input
 // column has no pointwise source: the entry points refuse it before this runs.)
+// pw_term(prm, tabs, nx_<l>..., dc<c>...): the entry t[d, i] of include/gjx_pointwise.h as a device function of a particle's
+// latents and a row's data values — what GenPointwise and GenPsis (under `name`) reduce in their two orientations.
+template <class CSiteT, class CArgT>
+inline void emit_row_term(std::ostringstream& o, const TemperTable<CSiteT, CArgT>& t, const CSiteT* sites, int n_sites, const char* name = "pw_term") {
+  o << "__device__ __forceinline__ float " << name << "(const PlanParams& prm, const PlanTables& tabs" << t.list(", float nx_")
+    << t.data_list(", float dc", {""}) << ") {\n";
+  o << "  (void)prm; (void)tabs;\n";
+  SiteEmitter<CSiteT, CArgT> e{o, 0, 0, t.tab.data(), n_sites, "  ", ""};
+  e.exact_cuts = false;
+  bool first = true;
+  for (int q = 0; q < n_sites; ++q) {
+    e.head(q);
+    if (sites[q].observed != GJX_SITE_PLATED) continue;
+    // (the sum starts at the first term: +0 + t differs from t in the sign of a zero only, which no output can tell)
+    o << (first ? "  float t = " : "  t = t + ") << e.lp_of(q) << ";\n";
+    first = false;
+  }
+  o << "  return t;\n}\n";
+}
+
 template <class CSiteT, class CArgT>
 struct GenPointwise {
   std::ostringstream o;
@@ -1783,20 +1803,7 @@ struct GenPointwise {
     emit_prelude(o);
     const TemperTable<CSiteT, CArgT> t(sites, n_sites);
     const std::string dcs = t.data_list(", dc", {""});
-    o << "__device__ __forceinline__ float pw_term(const PlanParams& prm, const PlanTables& tabs" << t.list(", float nx_")
-      << t.data_list(", float dc", {""}) << ") {\n";
-    o << "  (void)prm; (void)tabs;\n";
-    SiteEmitter<CSiteT, CArgT> e{o, 0, 0, t.tab.data(), n_sites, "  ", ""};
-    e.exact_cuts = false;
-    bool first = true;
-    for (int q = 0; q < n_sites; ++q) {
-      e.head(q);
-      if (sites[q].observed != GJX_SITE_PLATED) continue;
-      // (the sum starts at the first term: +0 + t differs from t in the sign of a zero only, which no output can tell)
-      o << (first ? "  float t = " : "  t = t + ") << e.lp_of(q) << ";\n";
-      first = false;
-    }
-    o << "  return t;\n}\n";
+    emit_row_term(o, t, sites, n_sites);
     o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_pointwise_kernel(PointwiseArgs a, PlanParams prm, PlanTables tabs, PlateData pd) {\n";
     o << "  const uint32_t d = blockIdx.x * 256u + threadIdx.x;\n  if (d >= pd.n_rows) return;\n";
     for (int c : t.cs) o << "  const float dc" << c << " = pd.col[" << c << "][d];\n";
@@ -1806,6 +1813,59 @@ struct GenPointwise {
     emit_particle_loop(o, t, NB, "  PointwiseAcc q = pointwise_start();\n", block,
                        " {\n    const float t[1] = {pw_term(prm, tabs" + t.list(", xc", "[i]") + dcs + ")};\n    pointwise_take<1>(q, t);\n  }\n",
                        "  pointwise_store(a, pd.n_rows, blockIdx.y, d, q);\n}\n");
+    return o.str();
+  }
+};
+
+// The PSIS kernel of a plated tempered plan (include/gjx_psis.h): the orientation of emit_plated, not of emit_particle_loop —
+// PARTICLES on lanes, rows wave-uniform:
+//   * a workgroup owns a block of kPsisRows rows (blockIdx.x) and one contiguous chunk of particles (blockIdx.y); the rows'
+//     data values are read through constant-address-space pointers at indices derived from blockIdx (scalar loads, once); a
+//     row past the last one reads the last row's data again and is switched off (`on`);
+//   * a lane loads a particle's latents once per round of 256 particles and evaluates the kPsisRows terms with ps_term — the
+//     pointwise kernel's pw_term, emitted by the same function, so t[d, i] is the same f32 in both;
+//   * what happens to a term depends on a.mode (the three select passes, the collect pass) and is fixed device code
+//     (gjx_device.hpp psis_begin / psis_take / psis_flush), as are the launches between the passes.
+// The loop's trip count is uniform over the workgroup (a lane past the chunk's end reads the chunk's last particle and is
+// switched off), so the barriers of psis_begin and psis_flush are reached by every lane.  32 KB of LDS;
+// no draw: one source per plan, whatever impl.  The source holds no data value, no parameter value and neither n, n_rows
+// nor tail_len.
+template <class CSiteT, class CArgT>
+struct GenPsis {
+  std::ostringstream o;
+  const CSiteT* sites;
+  int n_sites;
+
+  std::string run() {
+    constexpr int R = gjx::kPsisRows;
+    emit_prelude(o);
+    const TemperTable<CSiteT, CArgT> t(sites, n_sites);
+    emit_row_term(o, t, sites, n_sites, "ps_term");
+    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_psis_kernel(PsisArgs a, PlanParams prm, PlanTables tabs, PlateData pd) {\n";
+    o << "  __shared__ double shd[kPsisRows * kPsisBins / 2];\n  uint32_t* sh = reinterpret_cast<uint32_t*>(shd);\n";
+    o << "  const uint32_t r0 = blockIdx.x * (uint32_t)kPsisRows;\n";
+    for (int c : t.cs) o << "  const PlateCol pc" << c << " = (PlateCol)pd.col[" << c << "];\n";
+    for (int j = 0; j < R; ++j) {
+      const std::string J = std::to_string(j);
+      o << "  const bool on" << J << " = r0 + " << J << "u < pd.n_rows;\n";
+      o << "  const uint32_t d" << J << " = on" << J << " ? r0 + " << J << "u : pd.n_rows - 1u;\n";
+      for (int c : t.cs) o << "  const float dc" << c << "_" << J << " = pc" << c << "[d" << J << "];\n";
+      o << "  const uint32_t key" << J << " = psis_row_key(a, d" << J << ");\n  const float tT" << J << " = psis_unkey(key" << J << ");\n";
+    }
+    o << "  double g[kPsisRows] = {};\n  uint32_t bad[kPsisRows] = {};\n";
+    o << "  const uint64_t lo64 = (uint64_t)blockIdx.y * a.per;\n";
+    o << "  const uint32_t lo = lo64 < a.n ? (uint32_t)lo64 : a.n;\n";
+    o << "  const uint32_t hi = a.n - lo > a.per ? lo + a.per : a.n;\n";
+    o << "  psis_begin(a, sh);\n";
+    o << "  for (uint32_t i0 = lo; i0 < hi; i0 += 256u) {\n";
+    o << "    const bool live = hi - i0 > threadIdx.x;\n    const uint32_t i = live ? i0 + threadIdx.x : hi - 1u;\n";
+    for (int l = 0; l < t.L; ++l) o << "    const float x" << l << " = a.x[" << l << "][i];\n";
+    for (int j = 0; j < R; ++j) {
+      const std::string J = std::to_string(j);
+      o << "    psis_take(a, sh + " << J << " * kPsisBins, d" << J << ", key" << J << ", tT" << J << ", live && on" << J << ", ps_term(prm, tabs"
+        << t.list(", x") << t.data_list(", dc", {("_" + J).c_str()}) << "), g[" << J << "], bad[" << J << "]);\n";
+    }
+    o << "  }\n  psis_flush(a, sh, pd.n_rows, r0, g, bad);\n}\n";
     return o.str();
   }
 };
@@ -1967,7 +2027,7 @@ inline bool read_file(const std::string& path, std::string* out) {
   return true;
 }
 // The plan kinds that generate kernels.  Each has its own compiler option list (compile_options).
-enum class PlanKind { importance, scan, smc, backsim, temper, predictive };
+enum class PlanKind { importance, scan, smc, backsim, temper, predictive, psis };
 // The options of one plan kind: four fixed ones, then the kind's own, then the A/B knobs (a later option wins).
 //  * importance: -fno-slp-vectorize.  The SLP vectoriser turns pairs of f32 operations into v_pk_* forms, which issue no
 //    faster per flop than two scalar ones (tools/README.md) but cost v_mov shuffles to build register pairs and hazard wait
@@ -1979,6 +2039,7 @@ enum class PlanKind { importance, scan, smc, backsim, temper, predictive };
 //  * smc, backsim: nothing of their own (not priced).
 //  * temper: nothing of its own (not priced): one particle per lane, nothing for the SLP vectoriser to pair.
 //  * predictive: nothing of its own (not priced; profiles/predictive_summary.md has its instruction counts).
+//  * psis: nothing of its own (not priced; profiles/psis_summary.md has its register counts).
 inline std::vector<std::string> compile_options(PlanKind kind) {
   std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"};
   if (kind == PlanKind::importance) opts.push_back("-fno-slp-vectorize");

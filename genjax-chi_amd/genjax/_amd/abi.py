@@ -104,6 +104,10 @@ class PointwiseUnavailable(HeaderUnavailable):
     header, why = "gjx_pointwise.h", "pointwise predictive densities run as a generated HIP kernel over a plated plan only"
 
 
+class PsisUnavailable(HeaderUnavailable):
+    header, why = "gjx_psis.h", "PSIS-LOO runs as a generated HIP kernel over a plated plan only"
+
+
 class PredictiveUnavailable(HeaderUnavailable):
     header, why = "gjx_predictive.h", "posterior predictive draws run as a generated HIP kernel over a plated plan only"
 
@@ -692,6 +696,36 @@ POINTWISE_PROTOTYPES = {
 }
 POINTWISE_ABI_VERSION = (0, 1)
 
+# include/gjx_psis.h: a THIRTEENTH header, same arrangement — Pareto-smoothed importance-sampling leave-one-out over the same
+# table: per row the M + 1 smallest entries over the particles selected exactly, the generalised-Pareto fit of that tail, its
+# shape k-hat and elpd_loo.  It builds on gjx_plate.h alone and is bound right before it (the suites of the later headers pin the
+# end of PLAN_HEADERS).
+PSIS_MAX_TAIL = 4095     # gjx_psis.h: GJX_PSIS_MAX_TAIL
+
+
+class PsisIO(C.Structure):
+    """gjx_psis_io (include/gjx_psis.h)."""
+    _fields_ = [
+        ("n", C.c_uint64),
+        ("x", C.c_void_p * TEMPER_MAX_LATENTS),
+        ("tail_len", C.c_uint32),
+        ("out", C.c_void_p),
+        ("tail", C.c_void_p),
+        ("ws", C.c_void_p),
+        ("ws_bytes", C.c_size_t),
+    ]
+
+
+PSIS_PROTOTYPES = {
+    "gjx_psis_version": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gjx_psis_tail_len": (C.c_uint32, [C.c_uint64, C.c_double]),
+    "gjx_psis_workspace_bytes": (C.c_size_t, [C.c_uint64, C.c_uint64, C.c_uint32]),
+    "gjx_temper_psis": (C.c_int, [_P, C.POINTER(PsisIO), _P]),
+    "gjx_psis_source": (C.c_int, [_P, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gjx_psis_compile_check": (C.c_int, [_P]),
+}
+PSIS_ABI_VERSION = (0, 1)
+
 # include/gjx_predictive.h: a TWELFTH header, same arrangement — posterior predictive draws of a plated tempered plan: per row
 # and plated site the moments of the replicated data over the particles, its position against the observed value, and a
 # strided subset of the draws themselves.  It builds on gjx_plate.h alone and is bound right after it.
@@ -772,6 +806,7 @@ PLAN_HEADERS = {h.key: h for h in (
            SmcParamsUnavailable),
     Header("csmc", "gjx_csmc.h", "gjx_csmc_version", CSMC_PROTOTYPES, "CSMC_ABI_VERSION", CsmcUnavailable),
     Header("temper", "gjx_temper.h", "gjx_temper_version", TEMPER_PROTOTYPES, "TEMPER_ABI_VERSION", TemperUnavailable),
+    Header("psis", "gjx_psis.h", "gjx_psis_version", PSIS_PROTOTYPES, "PSIS_ABI_VERSION", PsisUnavailable),
     Header("plate", "gjx_plate.h", "gjx_plate_version", PLATE_PROTOTYPES, "PLATE_ABI_VERSION", PlateUnavailable),
     Header("predictive", "gjx_predictive.h", "gjx_predictive_version", PREDICTIVE_PROTOTYPES, "PREDICTIVE_ABI_VERSION",
            PredictiveUnavailable),
@@ -802,6 +837,8 @@ _NO_STATUS = {
     "gjx_pointwise_chunks",
     "gjx_pointwise_workspace_bytes",
     "gjx_predictive_chunks",
+    "gjx_psis_tail_len",
+    "gjx_psis_workspace_bytes",
     "gjx_predictive_workspace_bytes",
     "gjx_temper_moments_workspace_bytes",
     "gjx_backmove_workspace_bytes",

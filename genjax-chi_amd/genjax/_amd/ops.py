@@ -738,6 +738,25 @@ class Ops:
         self.lib.call("gjx_temper_pointwise", plan.handle, C.byref(io), self.stream())
         return out.view(4, D)
 
+    def temper_psis(self, plan: "TemperPlan", x: list, tail_len: int, want_tail: bool = False):
+        """gjx_temper_psis (include/gjx_psis.h): PSIS-LOO of the plan's data rows under the n equally weighted particles of
+        the columns `x` (the L latent columns, float32[n]) -> (out float64[7, D]: elpd_loo, khat, sigma, s, tT, B, bad;
+        tail float32[D, tail_len + 1], each row's tail_len + 1 smallest entries in ascending order, or None) on the device.
+        `tail_len`: 5 .. 4095 and below n (gjx_psis_tail_len has the package's rule).  Nothing is drawn, nothing read back."""
+        M = int(tail_len)
+        n = x[0].numel() if x else 0
+        if not 5 <= M <= abi.PSIS_MAX_TAIL or M >= n:
+            raise ValueError(f"temper_psis: tail_len must be in 5 .. {abi.PSIS_MAX_TAIL} and below n = {n}, got {M}")
+        io = abi.PsisIO()
+        n, D, ws = self._plated_io("psis", plan, x, io, "gjx_psis_workspace_bytes", M)
+        out = self.empty(7 * D, torch.float64)
+        tail = self.empty(D * (M + 1), torch.float32) if want_tail else None
+        io.tail_len, io.out = M, out.data_ptr()
+        if tail is not None:
+            io.tail = tail.data_ptr()
+        self.lib.call("gjx_temper_psis", plan.handle, C.byref(io), self.stream())
+        return out.view(7, D), (tail.view(D, M + 1) if tail is not None else None)
+
     def temper_predictive(self, plan: "TemperPlan", key, x: list, draw_stride: int = 0):
         """gjx_temper_predictive (include/gjx_predictive.h): TWO launches -> (out float64[S, 5, D], draws float32[S, m, D] or
         None) on the device.  Per plated site s and data row d, over the n particles of the columns `x` (the L latent
@@ -1224,6 +1243,15 @@ class TemperPlan(PlanHandle):
         """gjx_pointwise_compile_check (include/gjx_pointwise.h): the status, not raised."""
         self.ops.lib.require("pointwise", "gjx_pointwise_compile_check")
         return self.ops.lib._gjx_pointwise_compile_check(self.handle)
+
+    def psis_compile_check(self) -> int:
+        """gjx_psis_compile_check (include/gjx_psis.h): the status, not raised."""
+        self.ops.lib.require("psis", "gjx_psis_compile_check")
+        return self.ops.lib._gjx_psis_compile_check(self.handle)
+
+    def psis_source(self) -> str:
+        """The HIP source of the plan's generated PSIS kernel (one per plan: it draws nothing)."""
+        return self._source("gjx_psis_source")
 
     def pointwise_source(self) -> str:
         """The HIP source of the plan's generated pointwise kernel (one per plan: it draws nothing)."""

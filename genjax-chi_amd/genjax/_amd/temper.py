@@ -326,6 +326,61 @@ class PointwiseLikelihood:
         return f"PointwiseLikelihood(rows={self.lppd.numel()}, n={self.n})"
 
 
+class PSISLOO:
+    """Pareto-smoothed importance-sampling leave-one-out cross-validation of a plated site's rows under a population of n
+    equally weighted particles (include/gjx_psis.h; Vehtari, Gelman & Gabry 2017).  Per data row d, float64 [D] on the device:
+    `elpd_loo` (NaN where the row has a non-finite entry), `khat` — the shape of the generalised Pareto fitted to the row's
+    `tail_len` largest importance ratios (+inf where nothing was smoothed: a tail tied with its cutoff, or a non-finite
+    entry), `sigma` its scale, `bad` the count of non-finite entries.  `pointwise`: the PointwiseLikelihood of the same
+    population (lppd, WAIC).  The scalar properties read the device ONCE: `elpd` = sum_d elpd_loo_d, `se` =
+    sqrt(D var_d(elpd_loo_d)), `looic` = -2 elpd, `p_loo` = sum_d (lppd_d - elpd_loo_d), `khat_threshold` =
+    min(1 - 1 / log10(n), 0.7) (Vehtari et al. 2024) and `n_high`, the rows whose khat is above it."""
+
+    def __init__(self, table: torch.Tensor, pointwise: PointwiseLikelihood, n: int, tail_len: int):
+        """`table`: float64 [7, D] — the rows elpd_loo, khat, sigma, s, tT, B, bad of gjx_temper_psis."""
+        if table.dim() != 2 or table.shape[0] != 7 or table.dtype != torch.float64:
+            raise ValueError("PSISLOO: a float64 [7, D] tensor expected")
+        self.n, self.tail_len, self.pointwise = int(n), int(tail_len), pointwise
+        if self.n < 2:
+            raise ValueError("PSISLOO: n >= 2")
+        self.elpd_loo, self.khat, self.sigma, self.bad = table[0], table[1], table[2], table[6]
+        self.khat_threshold = min(1.0 - 1.0 / math.log10(self.n), 0.7)
+        self._host = None
+
+    def _scalars(self):
+        if self._host is None:
+            h = torch.stack([self.elpd_loo, self.khat, self.pointwise.lppd]).cpu().numpy()  # (the one host read)
+            e, k, lppd = h[0], h[1], h[2]
+            D = len(e)
+            with np.errstate(invalid="ignore"):
+                se = math.sqrt(D * float(np.var(e, ddof=1))) if D > 1 else float("nan")
+                self._host = dict(elpd=float(e.sum()), se=se, p_loo=float((lppd - e).sum()), n_high=int((k > self.khat_threshold).sum()))
+        return self._host
+
+    @property
+    def elpd(self) -> float:
+        return self._scalars()["elpd"]
+
+    @property
+    def se(self) -> float:
+        return self._scalars()["se"]
+
+    @property
+    def looic(self) -> float:
+        return -2.0 * self._scalars()["elpd"]
+
+    @property
+    def p_loo(self) -> float:
+        return self._scalars()["p_loo"]
+
+    @property
+    def n_high(self) -> int:
+        return self._scalars()["n_high"]
+
+    def __repr__(self):
+        return f"PSISLOO(rows={self.elpd_loo.numel()}, n={self.n}, tail_len={self.tail_len})"
+
+
 class PosteriorPredictive:
     """Replicated data of the plated site(s) under a population of n equally weighted particles
     (include/gjx_predictive.h): y_rep[d, i] ~ p(y | x_i, data_d), one draw per particle and data row.  Every field is a dict
@@ -612,6 +667,24 @@ class TemperedSMC(SMCAlgorithm):
         ops.lib.require("pointwise", "gjx_temper_pointwise")
         _, tplan, x = self._population("pointwise", "pointwise densities", res, target)
         return PointwiseLikelihood(ops.temper_pointwise(tplan, x), x[0].numel())
+
+    # -- PSIS-LOO (include/gjx_psis.h) ------------------------------------------------------------------------------
+    def loo(self, res, r_eff: float = 1.0) -> PSISLOO:
+        """Pareto-smoothed importance-sampling leave-one-out over the rows the sampler was fitted to, under the population
+        `res` — a TemperedResult of `run`, or the L latent columns (float32 [n]) in the plan's latent order: per row elpd_loo
+        and the diagnostic k-hat (PSISLOO), and the pointwise densities of the same call.  `r_eff`: the relative efficiency of
+        the population; as in the `loo` package it enters the tail length min(0.2 n, 3 sqrt(n / r_eff)) alone (capped at 4095:
+        include/gjx_psis.h)."""
+        ops = self._state()["ops"]
+        ops.lib.require("psis", "gjx_temper_psis")
+        ops.lib.require("pointwise", "gjx_temper_pointwise")
+        _, tplan, x = self._population("loo", "leave-one-out densities", res, None)
+        n = int(x[0].numel())
+        M = int(ops.lib.call("gjx_psis_tail_len", n, float(r_eff)))
+        if M == 0:
+            raise ValueError(f"TemperedSMC.loo: a population of n = {n} at r_eff = {r_eff} has no tail to fit (n >= 25 and a positive finite r_eff)")
+        table, _ = ops.temper_psis(tplan, x, M)
+        return PSISLOO(table, PointwiseLikelihood(ops.temper_pointwise(tplan, x), n), n, M)
 
     # -- posterior predictive draws (include/gjx_predictive.h; DESIGN.md §4n) ---------------------------------------------------
     def _unobserved_target(self, st, args) -> Target:

@@ -6,9 +6,9 @@ from .._amd.inference import (ChangeTarget, Importance, ImportanceK, ParticleCol
                               stack_to_first_dim)
 from .._amd.smc_fused import (BootstrapSMC, DiscreteHMM, GuidedSMC, LinearGaussianSSM, ParticleGibbs, ParticleGibbsResult,
                               ParticleMH, SMCResult, StateSpaceModel, Trajectories)
-from .._amd.temper import PointwiseLikelihood, PosteriorPredictive, TemperedResult, TemperedSMC
+from .._amd.temper import PSISLOO, PointwiseLikelihood, PosteriorPredictive, TemperedResult, TemperedSMC
 
 __all__ = ["ChangeTarget", "Importance", "ImportanceK", "SMCAlgorithm", "ParticleCollection", "BootstrapSMC", "GuidedSMC",
            "LinearGaussianSSM", "DiscreteHMM", "StateSpaceModel", "SMCResult", "Trajectories", "stack_to_first_dim", "ParticleMH",
            "ParticleGibbs", "ParticleGibbsResult", "TemperedSMC", "TemperedResult",
-           "PointwiseLikelihood", "PosteriorPredictive"]
+           "PointwiseLikelihood", "PosteriorPredictive", "PSISLOO"]

@@ -10,7 +10,7 @@ loads it, plans are host objects, and the models are the builders the CPU tests 
               getter: the sources are what gjx_scan_plan_compile_check hands the compiler, recorded by a stand-in for gjx_jitc
               (GJX_JITC) that keeps its input and compiles nothing
   smc ...     plain, guided, parameterised and conditional filters, backward simulation and its MCMC moves, tempered move
-              kernels (diagonal, covariance, plated), pointwise kernels and predictive kernels under both generators (a plan
+              kernels (diagonal, covariance, plated), pointwise kernels, predictive kernels under both generators and PSIS kernels (a plan
               without one: "refused").  (The peer-transport step kernels have no source
               getter and no launch on one device: their text differs from the plain one in the constant kPeers alone.)
 
@@ -315,7 +315,7 @@ def dump_tempered(ops):
             LINES.append(("temper", name, impl, "-", 0, plan.source(impl)))
             LINES.append(("temper_cov", name, impl, "-", 0, plan.cov_source(impl)))
         for kind, impl, get in (("pointwise", "-", plan.pointwise_source), ("predictive", 0, lambda: plan.predictive_source(0)),
-                                ("predictive", 1, lambda: plan.predictive_source(1))):
+                                ("predictive", 1, lambda: plan.predictive_source(1)), ("psis", "-", plan.psis_source)):
             try:
                 LINES.append((kind, name, impl, "-", 0, get()))
             except abi.GjxError as e:
