@@ -6,7 +6,9 @@ specification restated in float64 numpy, written from the header and sharing not
 3. The body sum, the Zhang-Stephens fit, the smoothed weights and the estimate, with every sum in index order or, `rev`, in
    reversed order — the difference between the two is float64 reordering noise, which the tolerances below are a multiple of.
 4. The closed-form leave-one-out of the conjugate regression (plate_ref.conjugate): the posterior refitted without row d,
-   Gaussian predictive at row d."""
+   Gaussian predictive at row d.
+5. The launch GEOMETRY as the headers state it (chunks of particles, rounds of 256 per chunk, keys sorted per row), so that
+   the suites can assert which loops of the kernels a case runs more than once."""
 
 import math
 
@@ -32,6 +34,17 @@ REORDER_FACTOR = 2.0 ** 10
 REORDER_FLOOR = 1e-11
 MEASURED_REORDER = dict(khat=2.9e-14, sigma=3.1e-14, elpd=5.5e-14)
 TOL = {q: max(REORDER_FACTOR * v, REORDER_FLOOR) for q, v in MEASURED_REORDER.items()}
+# The same measurement on the cases of tests/test_gpu_psis_shapes.py (tail lengths up to 4095, n up to 526000), by reorder_noise
+# on the reference's terms of every case; tests/test_psis_cpu.py::test_recorded_noise_covers_a_fresh_measurement repeats it.
+# All three maxima come from ONE case, the `normal` model at n = 4200, M = 4095 (khat 1.9 .. 2.4: nearly the whole row is
+# "tail", 93 candidates whose weights are exponentials of 4095 times a mean): khat 2.45e-13, sigma 2.46e-13, elpd 1.76e-12.
+# Next: n = 4096, M = 4095 (9.9e-14, 9.9e-14, 2.0e-13) and M = 2047 (3.8e-14, 3.8e-14, 1.3e-13); the trip-count cases stay at
+# or below the old table (n = 4099, D = 1100: 3.7e-14, 3.9e-14, 5.9e-14; the others under 5e-15), the key-space cases under
+# 1e-14 (elpd 2.3e-14), the public call's population (n = 20000, M = 425, khat <= 0.15) under 3e-15.  So the table is LOOSER
+# than the old one at the longest tails — by the reference's own measure, not by the kernel's — and the old one is untouched.
+MEASURED_REORDER_LARGE = dict(khat=2.5e-13, sigma=2.5e-13, elpd=1.8e-12)
+MEASURED_REORDER_LARGE_CASE = dict(khat=("normal", 4200, 4095), sigma=("normal", 4200, 4095), elpd=("normal", 4200, 4095))
+TOL_LARGE = {q: max(REORDER_FACTOR * v, REORDER_FLOOR) for q, v in MEASURED_REORDER_LARGE.items()}
 
 # The end-to-end case (tests/test_gpu_psis.py::test_end_to_end): plate_ref.conjugate(40), n = 4096.  Four times this is the bound:
 # the root-mean-square error, bias included, of sum_d elpd_loo_d against the closed-form leave-one-out sum (closed_form_loo:
@@ -49,6 +62,9 @@ E2E_MAX_KHAT = 0.302
 # 5000 .. 5023): 0.0182 on a sum of 41.4803 (errors between -0.038 and +0.022, mean -0.0087; khat at most 0.23).
 SPREAD_ELPD_SUM = 0.0182
 CLOSED_FORM_FACTOR = 4.0
+# The same at n = 20000 (M = 425; tests/test_gpu_psis_shapes.py::test_public_call_at_a_production_tail), same model, same 24
+# seeds, closed_form_errors (4 s): 0.0104 (errors between -0.0266 and +0.0148, mean -0.0019; khat at most 0.314).
+SPREAD_ELPD_SUM_20000 = 0.0104
 
 # The two cases whose khat the GPU suite requires on both sides of the scale, chosen here on the CPU with this reference
 # (tests/test_gpu_psis.py::test_khat_range): the `normal` model, D = 64 rows of plate_ref.target(seed=1), n = 4096,
@@ -198,6 +214,50 @@ def reorder_noise(t, M):
         ok = np.isfinite(a["elpd"])
         de = np.abs(a["elpd"] - b["elpd"])[ok]
     return dict(khat=float(dk.max()) if dk.size else 0.0, sigma=float(ds.max()) if ds.size else 0.0, elpd=float(de.max()) if de.size else 0.0)
+
+
+# ---- 5. the launch geometry (include/gjx_psis.h "body", gjx_pointwise.h "chunks"), restated from the headers' text -------------
+def chunks(n, D):
+    """-> (W, per): tiles = ceil(D / 4) row blocks, W = min(ceil(n / 256), max(1, ceil(2048 / tiles))) chunks of per =
+    ceil(n / W) particles (the last ones shorter, or empty)."""
+    tiles = -(-D // 4)
+    W = min(-(-n // 256), max(1, -(-2048 // tiles)))
+    return W, -(-n // W)
+
+
+def chunk_sizes(n, D):
+    """The particles of chunk c = 0 .. W - 1: lo = min(c per, n) .. min(lo + per, n)."""
+    W, per = chunks(n, D)
+    return [min((c + 1) * per, n) - min(c * per, n) for c in range(W)]
+
+
+def trips(n, D):
+    """The largest number of rounds of 256 particles a workgroup walks (lane l takes lo + l, lo + l + 256, ...)."""
+    return max(-(-c // 256) for c in chunk_sizes(n, D))
+
+
+def empty_chunks(n, D):
+    return sum(c == 0 for c in chunk_sizes(n, D))
+
+
+def first_trip(n, D):
+    """bool [n]: the particles a workgroup reaches in its FIRST round of 256 — all of them exactly when trips(n, D) == 1."""
+    W, per = chunks(n, D)
+    i = np.arange(n)
+    return i - (i // per) * per < 256
+
+
+def sort_size(M):
+    """The power of two at or above M + 1, at least 8: the keys one workgroup sorts (M + 1 tail entries, then padding)."""
+    P = 8
+    while P < M + 1:
+        P *= 2
+    return P
+
+
+def candidates(M):
+    """Gn of the fit."""
+    return 30 + int(math.floor(math.sqrt(M)))
 
 
 # ---- 4. the closed form ----------------------------------------------------------------------------------------------------

@@ -2,7 +2,9 @@
 leave free, the C-side validation before any launch, the tail-length and workspace rules, the generated kernel compiled for
 gfx950 offline (one source per plan, no data in it, no scratch), the numpy reference against itself (split form / direct
 form) and against the closed-form leave-one-out of the conjugate regression, the cases the GPU suite takes its k-hat range
-from, and the host logic of PSISLOO."""
+from, the host logic of PSISLOO — and the launch geometry restated from the headers' text (psis_ref.chunks): every case of
+tests/test_gpu_psis.py walks its chunks in one round and sorts at most 256 keys, every case of tests/test_gpu_psis_shapes.py
+has the geometry, the key-space property and the recorded noise it is named for."""
 
 import ctypes as C
 import math
@@ -21,7 +23,8 @@ from genjax._amd.plan import PlanUnsupported
 from genjax._amd.runtime import use_ops
 from genjax.inference.smc import PSISLOO, PointwiseLikelihood, TemperedSMC
 from offline import header_symbols, kernel_notes, ops  # noqa: F401  (ops: a fixture)
-from test_gpu_psis import MODELS, case_data, lower_all, population
+import test_gpu_psis_shapes as T
+from test_gpu_psis import CASES, MODELS, case_data, lower_all, population
 
 INVALID, UNSUPPORTED, WORKSPACE = -1, -2, -3
 SYMBOLS = {"gjx_psis_version", "gjx_psis_tail_len", "gjx_psis_workspace_bytes", "gjx_temper_psis", "gjx_psis_source",
@@ -260,3 +263,139 @@ def test_loo_refusals(ops):  # noqa: F811
             alg.loo([torch.zeros(64)])
         with pytest.raises(TypeError):
             alg.loo([torch.zeros(64), torch.zeros(64)], target=target)  # LOO scores the fitted rows: there is no target=
+
+
+# ---- the geometry of the GPU suites (tests/test_gpu_psis.py, tests/test_gpu_psis_shapes.py) ------------------------------------
+# (n, D) of every case of tests/test_gpu_psis.py: the pins, then identical particles, the non-finite entries and the k-hat
+# range (4096 x 64), the end-to-end case (40 rows)
+OLD_SHAPES = sorted({(n, D) for _, n, D, _ in CASES} | {(4096, 5), (4096, 64), (4096, 40)})
+NEW_SHAPES = ([(n, D) for _, n, D, _ in T.TRIP_CASES] + [(n, T.TAIL_D) for n, _ in T.TAIL_CASES] + [(T.OUTSIDE_N, T.TAIL_D)]
+              + [(n, T.KEY_D) for n, _ in T.KEY_SIZES] + [(T.PUBLIC_N, T.PUBLIC_ROWS)])
+
+
+def _terms(oracle_ops, lowered, name, data, cols):
+    return W.terms(P.Assess(oracle_ops, lowered[name][0], data), cols)
+
+
+def test_chunk_rule_is_the_librarys(ops):  # noqa: F811
+    """psis_ref.chunks against the library through the last term of gjx_psis_workspace_bytes (8 W D bytes, padded), on every
+    shape of both GPU suites and on the shapes tools/time_psis.py times."""
+    pad = lambda b: (b + 255) & ~255
+    for n, D in OLD_SHAPES + NEW_SHAPES + [(10 ** 6, 64), (10 ** 6, 1000), (10 ** 6, 10000)]:
+        M = S.tail_len(n)
+        Wc, per = S.chunks(n, D)
+        fixed = pad(D * 2048 * 4) + pad(D * 16) + pad(D * (M + 1) * 4)
+        assert int(ops.lib.call("gjx_psis_workspace_bytes", n, D, M)) - fixed == pad(Wc * D * 8), (n, D)
+        sizes = S.chunk_sizes(n, D)
+        assert len(sizes) == Wc and sum(sizes) == n and max(sizes) == per and S.first_trip(n, D).sum() == sum(min(c, 256) for c in sizes)
+
+
+def test_existing_gpu_cases_run_every_loop_once():
+    """The gap tests/test_gpu_psis_shapes.py closes: no case of tests/test_gpu_psis.py has a chunk of more than 256 particles,
+    an empty chunk, or more than 256 keys to sort."""
+    assert OLD_SHAPES == [(25, 5), (25, 64), (25, 300), (4096, 5), (4096, 40), (4096, 64), (4096, 300), (4099, 5), (4099, 64)]
+    for n, D in OLD_SHAPES:
+        assert S.trips(n, D) == 1 and S.empty_chunks(n, D) == 0 and S.first_trip(n, D).all() and S.sort_size(S.tail_len(n)) <= 256, (n, D)
+    assert {S.chunks(n, D) for n, D in OLD_SHAPES} == {(1, 25), (16, 256), (17, 242)}
+    assert {S.tail_len(n) for n, _ in OLD_SHAPES} == {5, 192, 193}
+
+
+def test_new_gpu_cases_have_the_geometry_they_are_named_for():
+    for name, n, D, kind in T.TRIP_CASES:
+        g = T.TRIP_GEOMETRY[n, D]
+        sizes = S.chunk_sizes(n, D)
+        assert S.chunks(n, D) == (g["W"], g["per"]) and S.trips(n, D) == g["trips"] > 1 and S.empty_chunks(n, D) == g["empty"], (n, D)
+        assert g["per"] - 256 * (g["trips"] - 1) == g["last"] and [c for c in sizes if c][-1] == g["short"], (n, D)
+        assert S.tail_len(n) == g["M"] and S.sort_size(g["M"]) == g["P"] and not S.first_trip(n, D).all(), (n, D)
+    assert S.chunk_sizes(526000, 3)[-1] == 0 and 2047 * 257 >= 526000 and 3 % 4 != 0  # an empty chunk; a row of the block switched off
+    assert {g["last"] for g in T.TRIP_GEOMETRY.values()} >= {1} and max(g["P"] for g in T.TRIP_GEOMETRY.values()) == 4096
+    for (n, M), (Pk, padding, Gn) in T.TAIL_CASES.items():
+        assert M < n and S.sort_size(M) == Pk and Pk - (M + 1) == padding and S.candidates(M) == Gn, (n, M)
+    assert sorted(M for n, M in T.TAIL_CASES if n == T.TAIL_N) == [255, 256, 257, 1000, 2047, 2048, 4095] and (4096, 4095) in T.TAIL_CASES
+    assert [S.sort_size(M) for M in (255, 256, 257, 1000, 2047, 2048, 4095)] == [256, 512, 512, 1024, 2048, 4096, 4096]
+    assert S.sort_size(T.OUTSIDE_M) == 1024 and T.OUTSIDE_M < T.OUTSIDE_N
+    assert T.KEY_SIZES[0][1] == S.tail_len(T.KEY_SIZES[0][0]) == 192 and T.KEY_SIZES[1] == (6000, 1000)
+    assert S.tail_len(T.PUBLIC_N) == 425 and S.sort_size(425) == 512 and S.tail_len(7226) == 256  # (the rule passes 255 above n = 7225)
+    assert S.sort_size(5) == 8 and S.sort_size(7) == 8 and S.sort_size(8) == 16 and S.sort_size(S.MAX_TAIL) == 4096
+
+
+def _new_case_terms(oracle_ops, lowered):
+    """(label, t, M) of every case of tests/test_gpu_psis_shapes.py, from the oracle's replay."""
+    for case in T.TRIP_CASES:
+        name, n, D, _ = case
+        yield case, _terms(oracle_ops, lowered, name, case_data(lowered, name, D), T.trip_columns(case)), S.tail_len(n)
+    tails = {n: _terms(oracle_ops, lowered, "normal", case_data(lowered, "normal", T.TAIL_D), T.tail_columns(n)) for n in {n for n, _ in T.TAIL_CASES}}
+    for n, M in sorted(T.TAIL_CASES):
+        yield ("normal", n, M), tails[n], M
+    yield "outside", _terms(oracle_ops, lowered, "hetero", case_data(lowered, "hetero", T.TAIL_D), T.outside_columns()), T.OUTSIDE_M
+    for n, M in T.KEY_SIZES:
+        for kind in T.KEY_KINDS:
+            cols, data = T.key_case(lowered, kind, n, M)
+            yield (kind, n, M), _terms(oracle_ops, lowered, "normal", data, cols), M
+    model = P.conjugate(T.PUBLIC_ROWS)
+    given = [model.xs.astype(np.float32), model.ys.astype(np.float32)]
+    cols = W.posterior_columns(model, T.PUBLIC_N, T.PUBLIC_SEED)
+    yield "public", _terms(oracle_ops, lowered, "normal", [given[k] for k in lowered["normal"][2]], cols), S.tail_len(T.PUBLIC_N)
+
+
+@pytest.fixture(scope="module")
+def new_cases(ops, oracle_ops, lowered):  # noqa: F811
+    return list(_new_case_terms(oracle_ops, lowered))
+
+
+def test_new_cases_have_their_properties_on_the_reference(new_cases):
+    """On the reference's terms: the key-space classes (one bin twice, the sign boundary inside the tail, -inf entries on
+    fewer / more particles than the tail, a heavy tie across the cutoff), a smoothed row in every tail-length case, NaN keys
+    inside the tail of the `outside` case, no k-hat above 0.7 in the public call's population."""
+    seen = set()
+    for label, t, M in new_cases:
+        ref = S.psis(t, M)
+        if label in T.TRIP_CASES:
+            assert np.isfinite(t).all() and np.isfinite(ref["khat"]).any(), label
+        elif label == "outside":
+            assert np.all(np.isnan(ref["tail"][:, M])) and np.all(np.isnan(ref["tail"]).sum(axis=1) > 1) and np.all(ref["bad"] > 0)
+        elif label == "public":
+            assert ref["khat"].max() <= 0.7 and np.all(ref["bad"] == 0)
+        elif label[0] == "normal":
+            assert np.isfinite(ref["khat"]).any(), label  # (otherwise the fit at this tail length would not be compared)
+        else:
+            T.key_property(label[0], t, M)
+            seen.add(label[0])
+            assert np.all(np.isposinf(ref["khat"])) and np.isnan(ref["elpd"]).all() if label[0].startswith("ninf") else np.isfinite(ref["elpd"]).all()
+    assert seen == set(T.KEY_KINDS)
+
+
+def test_first_round_only_is_caught_by_the_new_cases_alone(oracle_ops, lowered, new_cases):  # noqa: F811
+    """What the trip-count cases are for, shown on the reference: a selection that saw only the particles of each chunk's
+    FIRST round of 256 is the true one on every shape of tests/test_gpu_psis.py (it sees everything) and has another tail
+    on every row of every trip-count case."""
+    for n, D in OLD_SHAPES:
+        assert S.first_trip(n, D).all()
+    for label, t, M in new_cases:
+        if label in T.TRIP_CASES:
+            seen = S.first_trip(label[1], label[2])
+            assert all(not np.array_equal(S.select(t[d][seen], M)[0], S.select(t[d], M)[0]) for d in range(len(t))), label
+
+
+def test_recorded_noise_covers_a_fresh_measurement(new_cases):
+    """psis_ref.MEASURED_REORDER_LARGE is no smaller than reorder_noise on every case of tests/test_gpu_psis_shapes.py, and
+    the case recorded as the largest is the largest; the new table does not touch the old one."""
+    worst = {q: (0.0, None) for q in S.MEASURED_REORDER_LARGE}
+    for label, t, M in new_cases:
+        r = S.reorder_noise(t, M)
+        worst = {q: max(worst[q], (r[q], label), key=lambda v: v[0]) for q in worst}
+    print("reorder noise over the new cases", worst)
+    for q, (v, label) in worst.items():
+        assert v <= S.MEASURED_REORDER_LARGE[q] and label == S.MEASURED_REORDER_LARGE_CASE[q], (q, v, label)
+        assert S.TOL_LARGE[q] == max(S.REORDER_FACTOR * S.MEASURED_REORDER_LARGE[q], S.REORDER_FLOOR)
+    assert S.MEASURED_REORDER == dict(khat=2.9e-14, sigma=3.1e-14, elpd=5.5e-14) and S.REORDER_FACTOR == 2.0 ** 10 and S.REORDER_FLOOR == 1e-11
+
+
+def test_reference_recovers_the_closed_form_at_20000():
+    """As test_reference_recovers_the_closed_form, at the public call's n = 20000: two seeds outside the 24 measured ones —
+    one of them the GPU case's own — within four times the recorded spread, no k-hat above the threshold."""
+    model = P.conjugate(T.PUBLIC_ROWS)
+    err = S.closed_form_errors(model, T.PUBLIC_N, (T.PUBLIC_SEED, T.PUBLIC_SEED + 1))
+    print("sum elpd_loo minus the closed form at n = 20000", err, "bound", S.CLOSED_FORM_FACTOR * S.SPREAD_ELPD_SUM_20000)
+    assert np.all(np.abs(err) <= S.CLOSED_FORM_FACTOR * S.SPREAD_ELPD_SUM_20000) and S.SPREAD_ELPD_SUM_20000 < S.SPREAD_ELPD_SUM
+    assert T.PUBLIC_SEED not in W.CLOSED_FORM_SEEDS and min(1.0 - 1.0 / math.log10(T.PUBLIC_N), 0.7) == 0.7
