@@ -914,6 +914,74 @@ GJX_DEV float std_gamma_log(const Stream<IMPL>& st, int which, float conc) {
   return l;
 }
 
+// --- count families (include/gjx_counts.h): Poisson(rate) and NegativeBinomial(total_count, probs), TFP's formulas.
+// `k` is the count as f32, `lf` = log k! (m_lgamma(k + 1) here; a plated site reads it from the data column after the observed
+// one).  An argument outside the domain gives NaN, a value that is not >= 0 gives -inf, in that order.
+GJX_HD float logpdf_poisson_lf(float k, float rate, float lf) {
+  if (!(rate >= 0.0f)) return __builtin_nanf("");
+  if (!(k >= 0.0f)) return -__builtin_inff();
+  return (xlogy(k, rate) - rate) - lf;
+}
+GJX_HD float logpdf_poisson(float k, float rate) { return logpdf_poisson_lf(k, rate, m_lgamma(k + 1.0f)); }
+GJX_HD float logpdf_negative_binomial_lf(float k, float r, float p, float lf) {
+  if (!(r > 0.0f) || !(p >= 0.0f && p <= 1.0f)) return __builtin_nanf("");
+  if (!(k >= 0.0f)) return -__builtin_inff();
+  return (((m_lgamma(k + r) - lf) - m_lgamma(r)) + xlogy(k, p)) + xlogy(r, 1.0f - p);
+}
+GJX_HD float logpdf_negative_binomial(float k, float r, float p) {
+  return logpdf_negative_binomial_lf(k, r, p, m_lgamma(k + 1.0f));
+}
+// The Poisson draw over sub-streams B .. B + 64 of `st` (bounded loops only).  rate < 10: inversion by sequential search over
+// w0 of words(B), at most 128 steps.  rate >= 10: Hörmann's PTRS, attempt att over words(B + 1 + att) (w0 -> U, w1 -> V), at
+// most 64 attempts, then (int) rate.  Not a rate >= 0 (NaN included): -1, outside the support.  rate > 2^30: 2^30, no word read.
+// Lanes of a wave mix the two branches: each is ONE loop the wave walks once, as gamma_dv's.
+template <int IMPL>
+GJX_DEV int32_t poisson_draw(const Stream<IMPL>& st, uint32_t B, float rate) {
+  if (!(rate >= 0.0f)) return -1;
+  if (rate == 0.0f) return 0;
+  if (rate > 1073741824.0f) return 1073741824;
+  uint32_t w0, w1;
+  if (rate < 10.0f) {
+    st.words(B, w0, w1);
+    const float u = uniform01(w0);
+    float p = m_exp(-rate), s = p;
+    int32_t k = 0;
+    while (u >= s && k < 128) {
+      k += 1;
+      p = (p * rate) / (float)k;
+      s = s + p;
+    }
+    return k;
+  }
+  const float slam = __builtin_sqrtf(rate), lrate = m_log(rate);
+  const float b = 0.931f + 2.53f * slam;
+  const float a = -0.059f + 0.02483f * b;
+  const float l_inv_alpha = m_log(1.1239f + 1.1328f / (b - 3.4f));
+  const float vr = 0.9277f - 3.6224f / (b - 2.0f);
+  int32_t k = (int32_t)rate;
+  for (int att = 0; att < 64; ++att) {
+    st.words(B + 1u + (uint32_t)att, w0, w1);
+    const float U = uniform01(w0) - 0.5f, V = uniform01(w1);
+    const float us = 0.5f - __builtin_fabsf(U);
+    const float kf = __builtin_floorf((((2.0f * a) / us + b) * U + rate) + 0.43f);
+    if (!(kf >= 0.0f && kf < 2147483648.0f)) continue;  // (negative, NaN, +inf)
+    if (us >= 0.07f && V <= vr) { k = (int32_t)kf; break; }
+    if (us < 0.013f && V > us) continue;
+    const float lhs = (m_log(V) + l_inv_alpha) - m_log(a / (us * us) + b);
+    const float rhs = (-rate + kf * lrate) - m_lgamma(kf + 1.0f);
+    if (lhs <= rhs) { k = (int32_t)kf; break; }
+  }
+  return k;
+}
+// NegativeBinomial(r, p) as the Poisson mixture over a Gamma(r, (1 - p) / p) rate: the gamma owns sub-streams 0 .. 128 of the
+// site's stream, the Poisson draw starts at 256.  Arguments outside the domain, and probs == 1 (no finite count): -1.
+template <int IMPL>
+GJX_DEV int32_t negative_binomial_draw(const Stream<IMPL>& st, float r, float p) {
+  if (!(r > 0.0f) || !(p >= 0.0f && p < 1.0f)) return -1;
+  const float g = std_gamma<IMPL>(st, 0, r) * (p / (1.0f - p));
+  return poisson_draw<IMPL>(st, 256u, g);
+}
+
 // --- Beta(a, b) from its two gammas: g1 / (g1 + g2) wherever that ratio is sound: a shape >= 1 (its gamma never
 // leaves the normal range, and the other one's underflow then rounds the ratio to the 0 or 1 it is next to), or both gammas
 // normal f32 numbers.  With BOTH shapes below 1 the boost u^(1/conc) flushes gammas to 0 (42 % of them at conc = 0.01): 0 / 0 was

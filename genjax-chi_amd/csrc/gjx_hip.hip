@@ -19,6 +19,7 @@
 #include "../../include/gjx_psis.h"
 #include "../../include/gjx_predictive.h"
 #include "../../include/gjx_temper_cov.h"
+#include "../../include/gjx_counts.h"
 // The library's own kernels keep the Philox round's plain XOR chain (gjx_device.hpp xor3): with v_bitop3_b32 the one-filter
 // LGSSM step measured 0.5 % slower (8.96e10 against 9.01e10 particle-steps/s, three alternating runs each, parent's range
 // 0.1 %), while the generated kernels, which include the header on their own, gain 6 % (importance) and 12 % (LGSSM scan);
@@ -215,6 +216,28 @@ __global__ __launch_bounds__(kBlock) void k_sample_bernoulli(KeySrc ks, Opnd pro
     if (score) score[i] = logpdf_bernoulli(e, p);
   }
 }
+// include/gjx_counts.h: the two count families (values int32)
+template <int IMPL>
+__global__ __launch_bounds__(kBlock) void k_sample_poisson(KeySrc ks, Opnd rate, int32_t* val, float* score, uint64_t n) {
+  GJX_TILE_LOOP(i, n) {
+    const Stream<IMPL> st(key_at<IMPL>(ks, i), ks.has_fold != 0, ks.fold);
+    const float r = rate.at(i);
+    const int32_t v = poisson_draw<IMPL>(st, 0u, r);
+    val[i] = v;
+    if (score) score[i] = logpdf_poisson((float)v, r);
+  }
+}
+template <int IMPL>
+__global__ __launch_bounds__(kBlock) void k_sample_negative_binomial(KeySrc ks, Opnd total, Opnd probs, int32_t* val,
+                                                                     float* score, uint64_t n) {
+  GJX_TILE_LOOP(i, n) {
+    const Stream<IMPL> st(key_at<IMPL>(ks, i), ks.has_fold != 0, ks.fold);
+    const float r = total.at(i), p = probs.at(i);
+    const int32_t v = negative_binomial_draw<IMPL>(st, r, p);
+    val[i] = v;
+    if (score) score[i] = logpdf_negative_binomial((float)v, r, p);
+  }
+}
 template <int IMPL>
 __global__ __launch_bounds__(kBlock) void k_sample_categorical(KeySrc ks, const float* logits,
                                                                uint64_t n_rows, uint32_t K,
@@ -245,6 +268,13 @@ __global__ __launch_bounds__(kBlock) void k_logpdf_beta(Opnd v, Opnd a, Opnd b, 
 __global__ __launch_bounds__(kBlock) void k_logpdf_bernoulli(const uint8_t* v, int vs, Opnd probs,
                                                              float* score, uint64_t n) {
   GJX_TILE_LOOP(i, n) score[i] = logpdf_bernoulli(v ? v[i] != 0 : vs != 0, probs.at(i));
+}
+__global__ __launch_bounds__(kBlock) void k_logpdf_poisson(const int32_t* v, int vs, Opnd rate, float* score, uint64_t n) {
+  GJX_TILE_LOOP(i, n) score[i] = logpdf_poisson((float)(v ? v[i] : vs), rate.at(i));
+}
+__global__ __launch_bounds__(kBlock) void k_logpdf_negative_binomial(const int32_t* v, int vs, Opnd total, Opnd probs,
+                                                                     float* score, uint64_t n) {
+  GJX_TILE_LOOP(i, n) score[i] = logpdf_negative_binomial((float)(v ? v[i] : vs), total.at(i), probs.at(i));
 }
 __global__ __launch_bounds__(kBlock) void k_logpdf_categorical(const int32_t* v, int vs,
                                                                const float* logits,
@@ -2011,6 +2041,35 @@ int gjx_logpdf_bernoulli(const uint8_t* value, int value_scalar, gjx_f32 probs, 
   k_logpdf_bernoulli<<<grid_for(n), kBlock, 0, S(s)>>>(value, value_scalar, opnd(probs), score_out, n);
   return launch_status();
 }
+// include/gjx_counts.h
+int gjx_counts_version(int* major, int* minor) { return version_out(major, minor, GJX_COUNTS_VERSION_MAJOR, GJX_COUNTS_VERSION_MINOR); }
+int gjx_logpdf_poisson(const int32_t* value, int value_scalar, gjx_f32 rate, float* score_out, uint64_t n, gjx_stream s) {
+  if (!score_out) return GJX_ERR_INVALID;
+  if (n == 0) return GJX_OK;
+  k_logpdf_poisson<<<grid_for(n), kBlock, 0, S(s)>>>(value, value_scalar, opnd(rate), score_out, n);
+  return launch_status();
+}
+int gjx_logpdf_negative_binomial(const int32_t* value, int value_scalar, gjx_f32 total_count, gjx_f32 probs, float* score_out,
+                                 uint64_t n, gjx_stream s) {
+  if (!score_out) return GJX_ERR_INVALID;
+  if (n == 0) return GJX_OK;
+  k_logpdf_negative_binomial<<<grid_for(n), kBlock, 0, S(s)>>>(value, value_scalar, opnd(total_count), opnd(probs), score_out, n);
+  return launch_status();
+}
+int gjx_sample_logpdf_poisson(const gjx_keys* k, gjx_f32 rate, int32_t* value_out, float* score_out, uint64_t n, gjx_stream s) {
+  if (!keys_ok(k) || !value_out) return GJX_ERR_INVALID;
+  if (n == 0) return GJX_OK;
+  GJX_DISPATCH_IMPL(k->impl, k_sample_poisson, <<<grid_for(n), kBlock, 0, S(s)>>>(key_src(k), opnd(rate), value_out, score_out, n));
+  return launch_status();
+}
+int gjx_sample_logpdf_negative_binomial(const gjx_keys* k, gjx_f32 total_count, gjx_f32 probs, int32_t* value_out,
+                                        float* score_out, uint64_t n, gjx_stream s) {
+  if (!keys_ok(k) || !value_out) return GJX_ERR_INVALID;
+  if (n == 0) return GJX_OK;
+  GJX_DISPATCH_IMPL(k->impl, k_sample_negative_binomial,
+                    <<<grid_for(n), kBlock, 0, S(s)>>>(key_src(k), opnd(total_count), opnd(probs), value_out, score_out, n));
+  return launch_status();
+}
 int gjx_logpdf_categorical(const int32_t* value, int value_scalar, const float* logits,
                            uint64_t n_rows, uint32_t n_cat, const int32_t* row_index,
                            float* score_out, uint64_t n, gjx_stream s) {
@@ -2206,11 +2265,12 @@ static CArg carg(const gjx_arg& a) { return CArg{a.kind, a.ref, 0, a.ref, a.scal
 // (include/gjx_guided.h); every other creator refuses observed > 1 (it used to read it as "observed").
 // `allow_next`: the tables of gjx_backsim_plan_create, where `obs` may also be {GJX_ARG_NEXT, a carry component, 1, 0}
 // (include/gjx_backsim.h); arg_ok knows no such kind, so it is refused everywhere else.
-static bool convert_site(const gjx_site& st, int s, CSite& c, int n_state = -1, int n_obs = -1,
-                         bool allow_state = false, bool allow_guided = false, bool allow_next = false, bool allow_param = false) {
+// The operand rules every family shares (convert_site below; convert_count_site for include/gjx_counts.h): the site mode, the
+// one or two arguments, the observed value or the guided partner.
+static bool site_operands_ok(const gjx_site& st, int s, bool two_args, int n_state = -1, int n_obs = -1, bool allow_state = false,
+                             bool allow_guided = false, bool allow_next = false, bool allow_param = false) {
   if (st.observed > (allow_guided ? GJX_SITE_GUIDED : 1)) return false;
-  bool ok = st.dist >= 0 && st.dist <= GJX_DIST_CATEGORICAL && arg_ok(st.arg[0], s, n_state, n_obs, allow_state, allow_param);
-  const bool two_args = st.dist != GJX_DIST_BERNOULLI && st.dist != GJX_DIST_CATEGORICAL;
+  bool ok = arg_ok(st.arg[0], s, n_state, n_obs, allow_state, allow_param);
   if (ok && two_args) ok = arg_ok(st.arg[1], s, n_state, n_obs, allow_state, allow_param);
   if (ok && st.observed == GJX_SITE_GUIDED) {  // (that the partner is a PROPOSED site of the same kind: smc_guided_pairs_ok)
     ok = st.obs.kind == GJX_ARG_SITE && st.obs.ref >= 0 && st.obs.ref < s && st.obs.scale == 1.0f && st.obs.offset == 0.0f;
@@ -2222,6 +2282,13 @@ static bool convert_site(const gjx_site& st, int s, CSite& c, int n_state = -1, 
               (allow_next && st.obs.kind == GJX_ARG_NEXT && st.obs.ref >= 0 && st.obs.ref < n_state && st.obs.scale == 1.0f &&
                st.obs.offset == 0.0f);
   }
+  return ok;
+}
+static bool convert_site(const gjx_site& st, int s, CSite& c, int n_state = -1, int n_obs = -1,
+                         bool allow_state = false, bool allow_guided = false, bool allow_next = false, bool allow_param = false) {
+  const bool two_args = st.dist != GJX_DIST_BERNOULLI && st.dist != GJX_DIST_CATEGORICAL;
+  bool ok = st.dist >= 0 && st.dist <= GJX_DIST_CATEGORICAL &&
+            site_operands_ok(st, s, two_args, n_state, n_obs, allow_state, allow_guided, allow_next, allow_param);
   if (ok && st.dist == GJX_DIST_CATEGORICAL)
     ok = st.logits && st.n_cat > 0 && st.n_rows > 0 && (st.cat_mode == 0 || st.cat_mode == 1) && st.arg[0].kind != GJX_ARG_EXPR;
   if (!ok) return false;
@@ -2245,6 +2312,19 @@ static bool convert_site(const gjx_site& st, int s, CSite& c, int n_state = -1, 
   } else if ((st.dist == GJX_DIST_NORMAL && u1) || ((st.dist == GJX_DIST_GAMMA || st.dist == GJX_DIST_BETA) && u0 && u1)) {
     c.pre = 2;  // the same constants, derived from the launch's parameters (plan_derive_params)
   }
+  return true;
+}
+
+// A Poisson / NegativeBinomial site of a tempered plan (include/gjx_counts.h): the shared operand rules, one or two arguments,
+// nothing hoisted (pre == 0: the emitter evaluates the density's functions at the site).
+static bool convert_count_site(const gjx_site& st, int s, CSite& c) {
+  const bool two_args = st.dist == GJX_DIST_NEGATIVE_BINOMIAL;
+  if ((st.dist != GJX_DIST_POISSON && !two_args) || !site_operands_ok(st, s, two_args)) return false;
+  memset(&c, 0, sizeof(c));
+  c.dist = st.dist; c.observed = st.observed; c.out_col = st.out_col;
+  c.slot = -1;
+  c.a0 = carg(st.arg[0]); c.a1 = carg(st.arg[1]); c.obs = carg(st.obs);
+  if (!two_args) c.a1.kind = GJX_ARG_CONST;
   return true;
 }
 
@@ -4937,9 +5017,15 @@ gjx_jit::CompiledKernel* temper_compiled(gjx_temper_plan* p, TemperKernel k, int
 // gjx_temper_plan_create converts it.  A PLATED site is validated by convert_site over a copy in which every DATA operand
 // reads an input column instead (same index range, same places allowed) and the observed value is a literal; the converted
 // site then takes the caller's own arguments back.  Notes the highest data column in the plan.
-bool plated_convert_site(const gjx_site& st, int s, CSite& c, gjx_temper_plan* p) {
+// include/gjx_counts.h (allow_counts: gjx_temper_plan_create_counts): a Poisson / NegativeBinomial site, observed or plated, is
+// converted by convert_count_site (the same operand rules, nothing hoisted).  Its plated form reads log k! from the data column
+// after the observed one.
+bool plated_convert_site(const gjx_site& st, int s, CSite& c, gjx_temper_plan* p, bool allow_counts) {
   if (st.observed != 0 && st.observed != 1 && st.observed != GJX_SITE_PLATED) return false;
-  const bool two_args = st.dist != GJX_DIST_BERNOULLI && st.dist != GJX_DIST_CATEGORICAL;
+  const bool count = st.dist == GJX_DIST_POISSON || st.dist == GJX_DIST_NEGATIVE_BINOMIAL;
+  if (count && (!allow_counts || st.observed == 0)) return false;  // (a count-valued latent has no random-walk move)
+  const bool two_args = st.dist != GJX_DIST_BERNOULLI && st.dist != GJX_DIST_CATEGORICAL && st.dist != GJX_DIST_POISSON;
+  auto convert = [&](const gjx_site& u) { return count ? convert_count_site(u, s, c) : convert_site(u, s, c); };
   gjx_site t = st;
   gjx_expr_op prog[3][GJX_MAX_EXPR_OPS];
   gjx_arg* as[3] = {&t.arg[0], &t.arg[1], &t.obs};
@@ -4970,12 +5056,18 @@ bool plated_convert_site(const gjx_site& st, int s, CSite& c, gjx_temper_plan* p
     any = any || here;
     if (k == 2) in_obs = here;
   }
-  if (st.observed != GJX_SITE_PLATED) return !any && convert_site(st, s, c);
+  if (st.observed != GJX_SITE_PLATED) {
+    return !any && convert(st);  // (the caller's own operands: t's programs live on this frame)
+  }
   if (!in_obs || st.dist == GJX_DIST_CATEGORICAL) return false;
+  if (count) {  // obs: a plain DATA operand, log k! in the column after it
+    if (st.obs.kind != GJX_ARG_DATA || st.obs.scale != 1.0f || st.obs.offset != 0.0f || st.obs.ref + 1 >= GJX_PLATE_MAX_COLS) return false;
+    if (st.obs.ref + 1 > mx) mx = st.obs.ref + 1;
+  }
   if (t.obs.kind == GJX_ARG_EXPR && !expr_ok(t.obs, s, -1, -1, false)) return false;
   t.observed = 1;
   if (t.obs.kind == GJX_ARG_EXPR) t.obs = gjx_arg{GJX_ARG_CONST, 0, 0.0f, 0.0f, nullptr};
-  if (!convert_site(t, s, c)) return false;
+  if (!convert(t)) return false;
   c.observed = GJX_SITE_PLATED;
   c.a0 = carg(st.arg[0]);
   if (two_args) c.a1 = carg(st.arg[1]);
@@ -5354,7 +5446,8 @@ bool psis_carve(Carver& cv, uint64_t n_rows, uint32_t W, uint32_t M, PsisScratch
 }
 
 // gjx_temper_plan_create (allow_plated = false) and gjx_temper_plan_create_plated (include/gjx_plate.h)
-int temper_plan_create(const gjx_site* sites, int n_sites, uint32_t flags, gjx_temper_plan** out, bool allow_plated) {
+int temper_plan_create(const gjx_site* sites, int n_sites, uint32_t flags, gjx_temper_plan** out, bool allow_plated,
+                       bool allow_counts = false) {
   if (!sites || !out || n_sites < 1 || n_sites > GJX_MAX_SITES || flags != 0u) return GJX_ERR_INVALID;
   gjx_temper_plan* p = new (std::nothrow) gjx_temper_plan;
   if (!p) return GJX_ERR_LAUNCH;
@@ -5365,7 +5458,7 @@ int temper_plan_create(const gjx_site* sites, int n_sites, uint32_t flags, gjx_t
   bool ok = true;
   for (int s = 0; ok && s < n_sites; ++s) {
     CSite& c = p->sites[s];
-    ok = allow_plated ? plated_convert_site(sites[s], s, c, p) : convert_site(sites[s], s, c);
+    ok = allow_plated ? plated_convert_site(sites[s], s, c, p, allow_counts) : convert_site(sites[s], s, c);
     if (!ok) break;
     if (c.observed) ++n_observed;
     else if (c.dist > GJX_DIST_BETA) ok = false;  // an integer-valued latent has no random-walk move
@@ -5411,6 +5504,9 @@ int gjx_temper_plan_create(const gjx_site* sites, int n_sites, uint32_t flags, g
 int gjx_plate_version(int* major, int* minor) { return version_out(major, minor, GJX_PLATE_VERSION_MAJOR, GJX_PLATE_VERSION_MINOR); }
 int gjx_temper_plan_create_plated(const gjx_site* sites, int n_sites, uint32_t flags, gjx_temper_plan** out) {
   return temper_plan_create(sites, n_sites, flags, out, true);
+}
+int gjx_temper_plan_create_counts(const gjx_site* sites, int n_sites, uint32_t flags, gjx_temper_plan** out) {
+  return temper_plan_create(sites, n_sites, flags, out, true, true);
 }
 int gjx_temper_plan_set_data(gjx_temper_plan* p, const float* const* cols, int n_cols, uint64_t n_rows) {
   if (!p || !p->plated || !cols || n_cols < 1 || n_cols > GJX_PLATE_MAX_COLS || n_cols <= p->max_data || n_rows < 1 ||

@@ -189,6 +189,8 @@ struct SiteEmitter {
   }
 
   static bool is_int(const CSiteT& s) { return s.dist >= GJX_DIST_BERNOULLI; }
+  // include/gjx_counts.h: Poisson / NegativeBinomial (tempered plans made by gjx_temper_plan_create_counts only)
+  static bool is_count(const CSiteT& s) { return s.dist == GJX_DIST_POISSON || s.dist == GJX_DIST_NEGATIVE_BINOMIAL; }
   static bool sampled(const CSiteT& s) { return sampled_mode(s.observed); }  // consumes randomness (latent or proposed)
   static bool proposed(const CSiteT& s) { return s.observed == GJX_SITE_PROPOSED; }
   static bool guided(const CSiteT& s) { return s.observed == GJX_SITE_GUIDED; }
@@ -352,12 +354,14 @@ struct SiteEmitter {
         bool ok = v - v == 0.0f;
         if (st.dist == GJX_DIST_NORMAL) ok = ok && (which == 0 || v > 0.0f);
         else if (st.dist == GJX_DIST_BERNOULLI) ok = ok && v >= 0.0f && v <= 1.0f;
+        else if (st.dist == GJX_DIST_POISSON) ok = ok && v >= 0.0f;
+        else if (st.dist == GJX_DIST_NEGATIVE_BINOMIAL && which == 1) ok = ok && v >= 0.0f && v < 1.0f;
         else ok = ok && v > 0.0f;
         if (a.kind == GJX_ARG_EXPR) return ok ? arg(a) : "opq(" + arg(a) + ")";
         return ok ? flit(v) : flit_opaque(v);
       };
       o << ind << "const float a0_" << Q << " = " << carg(st.a0, 0) << ";\n";
-      if (st.dist != GJX_DIST_BERNOULLI) o << ind << "const float a1_" << Q << " = " << carg(st.a1, 1) << ";\n";
+      if (st.dist != GJX_DIST_BERNOULLI && st.dist != GJX_DIST_POISSON) o << ind << "const float a1_" << Q << " = " << carg(st.a1, 1) << ";\n";
     }
     if (guided(st)) {  // the value its partner (an earlier proposed site) drew
       if (is_int(st)) o << ind << "const int32_t vi" << Q << " = " << val_i32(st.obs.ref_site) << ";\n";
@@ -368,14 +372,16 @@ struct SiteEmitter {
       std::string ov;
       if (st.obs.kind == GJX_ARG_CONST) {
         const float v = st.obs.offset;
-        const bool in_support = st.dist == GJX_DIST_GAMMA ? v > 0.0f : (st.dist == GJX_DIST_BETA ? (v > 0.0f && v < 1.0f) : true);
+        const bool in_support = st.dist == GJX_DIST_GAMMA ? v > 0.0f : (st.dist == GJX_DIST_BETA ? (v > 0.0f && v < 1.0f) : (is_count(st) ? v >= 0.0f : true));
         ov = in_support ? flit(v) : flit_opaque(v);
       }
       else if (st.obs.kind == GJX_ARG_OBS) ov = "a.obs[" + std::to_string(st.obs.ref) + "]";
       else if (st.obs.kind == GJX_ARG_NEXT) ov = "nx_" + std::to_string(st.obs.ref);  // (transition tables: gjx_backsim.h)
       else if (st.obs.kind == GJX_ARG_PARAM || st.obs.kind == GJX_ARG_DATA || st.obs.kind == GJX_ARG_EXPR) ov = arg(st.obs);  // (DATA, EXPR: a plated site's)
       else ov = "cols.in[" + std::to_string(st.obs.ref) + "][li" + sfx + "]";
-      if (is_int(st)) o << ind << "const int32_t vi" << Q << " = (int32_t)__builtin_rintf(" << ov << ");\n";
+      // (a count keeps its float too: the support test k >= 0 of gjx_counts.h is taken before any conversion to an integer)
+      if (is_count(st)) o << ind << "const float vk" << Q << " = __builtin_rintf(" << ov << ");\n" << ind << "const int32_t vi" << Q << " = (int32_t)vk" << Q << ";\n";
+      else if (is_int(st)) o << ind << "const int32_t vi" << Q << " = (int32_t)__builtin_rintf(" << ov << ");\n";
       else o << ind << "const float vf" << Q << " = " << ov << ";\n";
       return;
     }
@@ -435,6 +441,14 @@ struct SiteEmitter {
             o << ind << "const float " << VF << " = g1_" << Q << " / (g1_" << Q << " + g2_" << Q << ");\n";
           else
             o << ind << "const float " << VF << " = beta_from_gammas<" << I << ">(strm" << Q << ", a0_" << Q << ", a1_" << Q << ", g1_" << Q << ", g2_" << Q << ");\n";
+          break;
+        case GJX_DIST_POISSON:  // (gjx_device.hpp poisson_draw / negative_binomial_draw: the one-particle form under both ciphers)
+          o << ind << "const Stream<" << I << "> strm" << Q << "(" << K << ", true, " << fold << "u);\n";
+          o << ind << "const int32_t " << VI << " = poisson_draw<" << I << ">(strm" << Q << ", 0u, a0_" << Q << ");\n";
+          break;
+        case GJX_DIST_NEGATIVE_BINOMIAL:
+          o << ind << "const Stream<" << I << "> strm" << Q << "(" << K << ", true, " << fold << "u);\n";
+          o << ind << "const int32_t " << VI << " = negative_binomial_draw<" << I << ">(strm" << Q << ", a0_" << Q << ", a1_" << Q << ");\n";
           break;
         default:
           if (st.cat_mode == 0) {
@@ -511,6 +525,16 @@ struct SiteEmitter {
                     : "logpdf_beta(" + v + ", a0_" + Q + ", a1_" + Q + ")";
         break;
       case GJX_DIST_BERNOULLI: lp = "logpdf_bernoulli(" + v + " != 0, a0_" + Q + ")"; break;
+      case GJX_DIST_POISSON:
+      case GJX_DIST_NEGATIVE_BINOMIAL: {
+        // an observed value: its float vk<q> (head()); a plated one reads log k! from the data column after its own (dc<c + 1>:
+        // gjx_counts.h), a scalar one and a draw evaluate m_lgamma(k + 1)
+        const std::string fn = st.dist == GJX_DIST_POISSON ? "logpdf_poisson" : "logpdf_negative_binomial";
+        const std::string as = ", a0_" + Q + (st.dist == GJX_DIST_POISSON ? std::string() : ", a1_" + Q);
+        if (st.observed && st.obs.kind == GJX_ARG_DATA) lp = fn + "_lf(vk" + Q + as + ", dc" + std::to_string(st.obs.ref + 1) + sfx + ")";
+        else lp = fn + "(" + (st.observed ? "vk" + Q : "(float)" + v) + as + ")";
+        break;
+      }
       default:
         const bool lpb_drawn = st.cat_ent && sampled(st) && st.cat_mode != 0;
         if (lpb_drawn && !retained(q))
@@ -1532,6 +1556,8 @@ struct TemperTable {
   // The data columns plated site q reads (a0, a1, obs; affine operands and program leaves), in ascending order.
   static std::vector<int> plate_cols(const CSiteT& st) {
     bool used[GJX_PLATE_MAX_COLS] = {};
+    // (a count site's log k! column, the one after its observed column: include/gjx_counts.h)
+    if ((st.dist == GJX_DIST_POISSON || st.dist == GJX_DIST_NEGATIVE_BINOMIAL) && st.obs.kind == GJX_ARG_DATA) used[st.obs.ref + 1] = true;
     for (const CArgT* a : {&st.a0, &st.a1, &st.obs}) {
       if (a->kind == GJX_ARG_DATA) used[a->ref] = true;
       if (a->kind != GJX_ARG_EXPR) continue;
@@ -1942,7 +1968,8 @@ struct GenPredictive {
       for (int s = 0; s < S; ++s) {
         const CSiteT& st = sites[plated[s]];
         const std::string ov = e.arg(st.obs);
-        t += (s ? ", " : "") + (Emitter::is_int(st) ? "((int32_t)__builtin_rintf(" + ov + ") != 0 ? 1.0f : 0.0f)" : ov);
+        t += (s ? ", " : "") + (Emitter::is_count(st) ? "__builtin_rintf(" + ov + ")"  // (a count's observed value is rint(data) itself)
+                                : Emitter::is_int(st) ? "((int32_t)__builtin_rintf(" + ov + ") != 0 ? 1.0f : 0.0f)" : ov);
       }
       return t;
     };

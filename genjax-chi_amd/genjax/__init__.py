@@ -10,7 +10,7 @@ from ._amd.choicemap import (ChoiceMap, ChoiceMapBuilder as _CMB, ChoiceMapNoVal
                              SelectionBuilder, C as _C)
 from ._amd.lang import (AddressReuse, Distribution, GenerativeFunction, GenerativeFunctionClosure, MissingAddress,
                         StaticGenerativeFunction, Trace, bernoulli, beta, categorical, exact_density, flip, gamma,
-                        gen, normal, uniform)
+                        gen, negative_binomial, normal, poisson, uniform)
 from ._amd.combinators import Scan, Vmap, scan, vmap
 from ._amd.edit import (Diff, EditRequest, EmptyRequest, IndexRequest, NoChange, NotSupportedEditRequest, Regenerate, Rejuvenate, StaticRequest,
                         UnknownChange, Update)
@@ -42,7 +42,7 @@ __all__ = [
     "AddressReuse", "Algorithm", "ChoiceMap", "ChoiceMapBuilder", "ChoiceMapNoValueAtAddress", "Diff", "Distribution",
     "EditRequest", "EmptyRequest", "IndexRequest", "NoChange", "NotSupportedEditRequest", "Regenerate", "Rejuvenate", "StaticRequest", "UnknownChange", "Update", "GenerativeFunction", "GenerativeFunctionClosure", "Marginal", "Mask", "MissingAddress", "SampleDistribution", "Scan",
     "Selection", "SelectionBuilder", "StaticGenerativeFunction", "Target", "Trace", "bernoulli", "beta",
-    "categorical", "exact_density", "fast_math", "flip", "gamma", "gen", "inference", "jaxlike", "marginal", "normal", "random",
+    "categorical", "exact_density", "fast_math", "flip", "gamma", "gen", "inference", "jaxlike", "marginal", "negative_binomial", "normal", "poisson", "random",
     "scan", "uniform", "Vmap", "vmap",
 ]
 __version__ = "0.1.0"

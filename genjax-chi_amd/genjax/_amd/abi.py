@@ -112,6 +112,10 @@ class PredictiveUnavailable(HeaderUnavailable):
     header, why = "gjx_predictive.h", "posterior predictive draws run as a generated HIP kernel over a plated plan only"
 
 
+class CountsUnavailable(HeaderUnavailable):
+    header, why = "gjx_counts.h", "the Poisson and negative-binomial densities and samplers are HIP kernels only"
+
+
 class TemperCovUnavailable(HeaderUnavailable):
     header, why = "gjx_temper_cov.h", "the population moments and the covariance move run as HIP kernels only"
 
@@ -781,6 +785,23 @@ TEMPER_COV_PROTOTYPES = {
 }
 TEMPER_COV_ABI_VERSION = (0, 1)
 
+# include/gjx_counts.h: a FOURTEENTH header, same arrangement — the count families Poisson and NegativeBinomial: two
+# distribution ids, their stand-alone density and draw kernels, and the tempered creator that accepts them at observed and
+# plated sites.  Bound between "temper" and "psis": the one slot that keeps what the suites of the other headers pin.
+DIST_POISSON = 5             # gjx_counts.h: GJX_DIST_POISSON (a0 = rate)
+DIST_NEGATIVE_BINOMIAL = 6   # ... GJX_DIST_NEGATIVE_BINOMIAL (a0 = total_count, a1 = probs)
+COUNT_DISTS = (DIST_POISSON, DIST_NEGATIVE_BINOMIAL)
+COUNTS_MAX_OBSERVED = 1 << 24  # ... GJX_COUNTS_MAX_OBSERVED
+COUNTS_PROTOTYPES = {
+    "gjx_counts_version": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gjx_logpdf_poisson": (C.c_int, [_P, C.c_int, F32, _P, C.c_uint64, _P]),
+    "gjx_logpdf_negative_binomial": (C.c_int, [_P, C.c_int, F32, F32, _P, C.c_uint64, _P]),
+    "gjx_sample_logpdf_poisson": (C.c_int, [_KP, F32, _P, _P, C.c_uint64, _P]),
+    "gjx_sample_logpdf_negative_binomial": (C.c_int, [_KP, F32, F32, _P, _P, C.c_uint64, _P]),
+    "gjx_temper_plan_create_counts": (C.c_int, [C.POINTER(Site), C.c_int, C.c_uint32, C.POINTER(_P)]),
+}
+COUNTS_ABI_VERSION = (0, 1)
+
 # The optional headers, in the order they are bound: every one is exported by libgjx_hip.so only and bound if present.
 class Header(collections.namedtuple("Header", "key header version_fn prototypes version_name unavailable")):
     @property
@@ -806,6 +827,7 @@ PLAN_HEADERS = {h.key: h for h in (
            SmcParamsUnavailable),
     Header("csmc", "gjx_csmc.h", "gjx_csmc_version", CSMC_PROTOTYPES, "CSMC_ABI_VERSION", CsmcUnavailable),
     Header("temper", "gjx_temper.h", "gjx_temper_version", TEMPER_PROTOTYPES, "TEMPER_ABI_VERSION", TemperUnavailable),
+    Header("counts", "gjx_counts.h", "gjx_counts_version", COUNTS_PROTOTYPES, "COUNTS_ABI_VERSION", CountsUnavailable),
     Header("psis", "gjx_psis.h", "gjx_psis_version", PSIS_PROTOTYPES, "PSIS_ABI_VERSION", PsisUnavailable),
     Header("plate", "gjx_plate.h", "gjx_plate_version", PLATE_PROTOTYPES, "PLATE_ABI_VERSION", PlateUnavailable),
     Header("predictive", "gjx_predictive.h", "gjx_predictive_version", PREDICTIVE_PROTOTYPES, "PREDICTIVE_ABI_VERSION",

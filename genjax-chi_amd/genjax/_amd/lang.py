@@ -1235,6 +1235,78 @@ class Categorical(Distribution):
         return ops.logpdf_categorical(n, v, self._logits(args[0], n))
 
 
+class _CountDist(Distribution):
+    """The count families of include/gjx_counts.h: int32 values, one density and one draw kernel each.  Arguments given on
+    the unconstrained scale (`log_rate=`, `logits=`) are mapped through the spec's own functions (`exp`, `sigmoid` as
+    SpecTensor takes them), so a body computes the same bits whichever way it writes the rate."""
+    value_dtype = torch.int32
+    abi_name = ""
+
+    @staticmethod
+    def _mapped(kind, v):
+        if kind in ("rate", "probs", "total_count"):
+            return v
+        t = v if isinstance(v, torch.Tensor) else torch.as_tensor(v, dtype=torch.float32)
+        t = _spec_plain(t).to(torch.float32)
+        if kind == "log_rate":
+            return _spec_plain(get_ops().map_f32(abi.MAP_EXP, t))
+        return _spec_plain(_spec_sigmoid(t))  # logits
+
+    def _sample(self, pk, args):
+        cols = [_to_device_col(x, pk.n) for x in self._params(args)]
+        return get_ops().sample_logpdf(self.abi_name, pk.kb, pk.n, *cols)
+
+    def _logpdf(self, n, v, args):
+        ops = get_ops()
+        if isinstance(v, torch.Tensor) and v.dim() >= 1 and v.shape[0] == n and n > 1:
+            top = int(torch.round(v.max().double())) if v.is_floating_point() else int(v.max())  # (one host read per scored column)
+            if top > abi.COUNTS_MAX_OBSERVED:
+                raise ValueError(f"genjax.{self.name}: an observed count of {top} is above 2^24 (not exact in float32)")
+            v = torch.round(v).to(device=ops.device(), dtype=torch.int32).contiguous() if v.is_floating_point() else \
+                v.to(device=ops.device(), dtype=torch.int32).contiguous()
+        else:
+            v = int(round(float(v)))
+            if v > abi.COUNTS_MAX_OBSERVED:
+                raise ValueError(f"genjax.{self.name}: an observed count of {v} is above 2^24 (not exact in float32)")
+        return ops.logpdf(self.abi_name, n, v, *[_to_device_col(x, n) for x in self._params(args)])
+
+
+class Poisson(_CountDist):
+    """tfd.Poisson(rate=... | log_rate=...) — tensorflow_probability/__init__.py:264; a bare argument is the rate."""
+    name, abi_name, dist_id = "poisson", "poisson", abi.DIST_POISSON
+
+    def canonical_args(self, args, kwargs):
+        if len(args) == 1 and not kwargs:
+            return (("rate", args[0]),)
+        if len(kwargs) == 1 and not args and next(iter(kwargs)) in ("rate", "log_rate"):
+            return (next(iter(kwargs.items())),)
+        raise TypeError("genjax.poisson takes rate (positional or rate=) or log_rate=")
+
+    def _params(self, args):
+        kind, v = args[0] if isinstance(args[0], tuple) else ("rate", args[0])
+        return (self._mapped(kind, v),)
+
+
+class NegativeBinomial(_CountDist):
+    """tfd.NegativeBinomial(total_count, probs=... | logits=...) — tensorflow_probability/__init__.py:249: the number of
+    successes of probability `probs` before `total_count` failures; total_count real and positive."""
+    name, abi_name, dist_id = "negative_binomial", "negative_binomial", abi.DIST_NEGATIVE_BINOMIAL
+
+    def canonical_args(self, args, kwargs):
+        kwargs = dict(kwargs)
+        if len(args) == 2 and not kwargs:
+            return (args[0], ("probs", args[1]))
+        if len(args) == 0 and "total_count" in kwargs:
+            args = (kwargs.pop("total_count"),)
+        if len(args) == 1 and len(kwargs) == 1 and next(iter(kwargs)) in ("probs", "logits"):
+            return (args[0], next(iter(kwargs.items())))
+        raise TypeError("genjax.negative_binomial takes total_count and probs= or logits=")
+
+    def _params(self, args):
+        kind, v = args[1] if isinstance(args[1], tuple) else ("probs", args[1])
+        return (args[0], self._mapped(kind, v))
+
+
 class Uniform(_RealDist):
     """tfd.Uniform(low, high) — tensorflow_probability/__init__.py (`uniform`): `low + (high − low)·u`, u the 24-bit uniform
     of the site's one-word draw (the bits every one-word sampler takes); log-density `−log(high − low)` inside `[low, high]`.
@@ -1266,6 +1338,8 @@ beta = Beta()
 flip = Flip()
 bernoulli = Bernoulli()
 categorical = Categorical()
+poisson = Poisson()
+negative_binomial = NegativeBinomial()
 
 
 class ExactDensityFromCallables(Distribution):

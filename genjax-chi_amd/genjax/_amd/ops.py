@@ -149,6 +149,13 @@ class Ops:
             val = self.empty(n, torch.uint8)
             self.lib.call("gjx_sample_logpdf_bernoulli", k, self._f32(a, n, "probs"),
                           C.c_void_p(val.data_ptr()), sp, n, self.stream())
+        elif dist == "poisson":  # include/gjx_counts.h: int32 values
+            val = self.empty(n, torch.int32)
+            self.lib.call("gjx_sample_logpdf_poisson", k, self._f32(a, n, "rate"), C.c_void_p(val.data_ptr()), sp, n, self.stream())
+        elif dist == "negative_binomial":
+            val = self.empty(n, torch.int32)
+            self.lib.call("gjx_sample_logpdf_negative_binomial", k, self._f32(a, n, "total_count"), self._f32(b, n, "probs"),
+                          C.c_void_p(val.data_ptr()), sp, n, self.stream())
         else:
             raise ValueError(dist)
         return val, score
@@ -181,6 +188,13 @@ class Ops:
             else:
                 vp, vs = None, int(bool(value))
             self.lib.call("gjx_logpdf_bernoulli", vp, vs, self._f32(a, n, "probs"), sp, n, self.stream())
+        elif dist in ("poisson", "negative_binomial"):  # include/gjx_counts.h: an int32 column or a scalar
+            if isinstance(value, torch.Tensor) and value.numel() > 1:
+                vp, vs = self._chk(value, torch.int32, n, "value"), 0
+            else:
+                vp, vs = None, int(value)
+            args = [self._f32(a, n, "arg0")] + ([self._f32(b, n, "arg1")] if dist == "negative_binomial" else [])
+            self.lib.call(f"gjx_logpdf_{dist}", vp, vs, *args, sp, n, self.stream())
         else:
             raise ValueError(dist)
         return score
@@ -584,8 +598,11 @@ class Ops:
         gjx_temper_plan_create_plated (abi.PlateUnavailable without that header)."""
         self.lib.require("temper", "gjx_temper_plan_create")
         plated = any(s.observed == abi.SITE_PLATED for s in sites)
-        creator = "gjx_temper_plan_create_plated" if plated else "gjx_temper_plan_create"
-        if plated:
+        counts = any(s.dist in abi.COUNT_DISTS for s in sites)  # (include/gjx_counts.h: only such a table goes to its creator)
+        creator = "gjx_temper_plan_create_counts" if counts else "gjx_temper_plan_create_plated" if plated else "gjx_temper_plan_create"
+        if counts:
+            self.lib.require("counts", creator)
+        elif plated:
             self.lib.require("plate", creator)
         arr = (abi.Site * max(1, len(sites)))(*sites)
         handle = C.c_void_p()

@@ -17,8 +17,8 @@ import torch
 from . import abi, prng
 from .choicemap import ChoiceMap
 from .inference import ParticleCollection, SMCAlgorithm, Target
-from .lang import bernoulli, split
-from .plan import PlanTracer, PlanUnsupported, SymExpr, _DIST_IDS, _make_plan, _needs_eager, is_data_tensor
+from .lang import NegativeBinomial, Poisson, bernoulli, split
+from .plan import ParamVal, PlanTracer, PlanUnsupported, SymExpr, _DIST_IDS, _make_plan, _needs_eager, is_data_tensor
 from .runtime import get_ops
 
 LADDER = 32  # candidates per ladder launch
@@ -38,6 +38,10 @@ class _TemperTracer(PlanTracer):
         self.data: list = []      # the data columns, as the model handed them over (uploaded as f32 at every run)
         self._data_keys: dict = {}
         self.data_rows = None     # D: one length per plan
+        # COUNT sites (include/gjx_counts.h): the column after a plated count site's observed column holds log k!,
+        # float32 of the float64 lgamma(k + 1) — data, not arithmetic.  lf_cols: that column -> the observed one
+        self.lf_cols: dict = {}
+        self._count_keys: dict = {}
 
     def data_col(self, t: torch.Tensor) -> int:
         # (identity is the memory: the body sees its tensor arguments as SpecTensor views of the caller's)
@@ -47,6 +51,81 @@ class _TemperTracer(PlanTracer):
             c = self._data_keys[key] = len(self.data)
             self.data.append(t)
         return c
+
+    @staticmethod
+    def log_factorial(t: torch.Tensor, addr=None) -> torch.Tensor:
+        """float32 of the float64 lgamma(rint(k) + 1) of a column of observed counts; a count above 2^24 is refused."""
+        k = torch.round(t.detach().to(device="cpu", dtype=torch.float64))
+        if k.numel() and float(k.max()) > abi.COUNTS_MAX_OBSERVED:
+            at = "" if addr is None else f" at address {addr!r}"
+            raise PlanUnsupported(f"TemperedSMC: an observed count of {int(k.max())}{at} is above 2^24 (not exact in float32)")
+        return torch.lgamma(k.clamp_min(0.0) + 1.0).to(torch.float32)
+
+    def count_cols(self, obs: torch.Tensor, addr) -> int:
+        """The observed column of a plated count site, with its log k! column registered directly after it.  (A pair of its
+        own even where the tensor is a column already: that column's neighbour is taken.)"""
+        key = (obs.data_ptr(), obs.numel(), obs.stride(0), obs.dtype, str(obs.device), obs._version)
+        c = self._count_keys.get(key)
+        if c is None:
+            c = self._count_keys[key] = len(self.data)
+            self._data_keys.setdefault(key, c)
+            self.data.append(obs)
+            self.data.append(self.log_factorial(obs, addr))
+            self.lf_cols[c + 1] = c
+        return c
+
+    def data_columns(self, device) -> list:
+        """The columns as float32 device tensors, as they are NOW: read at every run, the log k! columns recomputed."""
+        cols = [(self.log_factorial(self.data[self.lf_cols[c]]) if c in self.lf_cols else t.detach()) for c, t in enumerate(self.data)]
+        return [t.to(device=device, dtype=torch.float32).contiguous() for t in cols]
+
+    def _lowered(self, kind, v):
+        """An argument of a count family on its unconstrained scale as the program the per-site route computes (lang._CountDist):
+        log_rate -> exp(v); logits -> 1 / (1 + exp(-v))."""
+        if kind in ("rate", "probs"):
+            return v
+        _, prog = SymExpr.program_of(v, self)
+        z = (0, 0.0)
+        if kind == "log_rate":
+            return SymExpr(self, prog + [(abi.EXPR_EXP, *z)])
+        return SymExpr(self, [(abi.EXPR_CONST, 0, 1.0)] + prog + [(abi.EXPR_NEG, *z), (abi.EXPR_EXP, *z), (abi.EXPR_CONST, 0, 1.0),
+                                                                   (abi.EXPR_ADD, *z), (abi.EXPR_DIV, *z)])
+
+    def _count_family(self, gen_fn, args):
+        """-> (dist id, [a0, a1]) of a Poisson / NegativeBinomial site (canonical arguments), or None."""
+        if isinstance(gen_fn, Poisson):
+            kind, v = args[0]
+            return abi.DIST_POISSON, [self._lowered(kind, v)]
+        if isinstance(gen_fn, NegativeBinomial):
+            kind, v = args[1]
+            return abi.DIST_NEGATIVE_BINOMIAL, [args[0], self._lowered(kind, v)]
+        return None
+
+    def _observed_count(self, addr, gen_fn, args, obs):
+        """A scalar OBSERVED count site (gjx_counts.h: log k! is evaluated in the kernel, once per particle and sweep)."""
+        if len(self.sites) >= abi.MAX_SITES:
+            raise PlanUnsupported(f"TemperedSMC: too many sites at address {addr!r}")
+        try:
+            k = float(obs)
+        except Exception:
+            raise PlanUnsupported(f"TemperedSMC: the observed count at address {addr!r} must be a number or a 1-D tensor") from None
+        if k > abi.COUNTS_MAX_OBSERVED:
+            raise PlanUnsupported(f"TemperedSMC: an observed count of {int(k)} at address {addr!r} is above 2^24 (not exact in float32)")
+        dist, vals = self._count_family(gen_fn, args)
+        site = abi.Site()
+        site.dist, site.observed, site.out_col = dist, 1, -1
+        for j, v in enumerate(vals):
+            site.arg[j] = self._arg(v)
+        if self.use_params:
+            site.obs = abi.Arg(abi.ARG_PARAM, self.param_slot(ParamVal(k)), 1.0, 0.0, None)
+        else:
+            site.obs = abi.Arg(abi.ARG_CONST, 0, 0.0, k, None)
+        self.sites.append(site)
+        self.items.append(("site", len(self.sites) - 1))
+        self.meta.append(dict(addr=addr, gen_fn=gen_fn, args=args, obs=obs, out_col=-1, is_int=True, dtype=gen_fn.value_dtype,
+                              path=self.prefix + (addr if isinstance(addr, tuple) else (addr,))))
+        self.record(addr, None)
+        return obs
 
     def _data_cols_of(self, v) -> set:
         """The data columns the argument / value `v` reads (a raw data tensor is registered here)."""
@@ -71,17 +150,22 @@ class _TemperTracer(PlanTracer):
         if not is_data_tensor(obs):
             raise PlanUnsupported(f"TemperedSMC: the site at address {addr!r} has data-dependent arguments: its observed value "
                                   "must be a 1-D tensor of the same length")
-        if id(gen_fn) in _DIST_IDS:
+        count = isinstance(gen_fn, (Poisson, NegativeBinomial))
+        if count:
+            dist, vals = self._count_family(gen_fn, args)
+        elif id(gen_fn) in _DIST_IDS:
             dist = _DIST_IDS[id(gen_fn)]
             vals = list(args[:1 if dist == abi.DIST_BERNOULLI else 2])
         elif gen_fn is bernoulli and args[0][0] == "probs":
             dist, vals = abi.DIST_BERNOULLI, [args[0][1]]
         else:
-            raise PlanUnsupported(f"TemperedSMC: a plated site at address {addr!r} must be normal, gamma, beta or flip "
-                                  "(a plated categorical has no table rows per datum)")
+            raise PlanUnsupported(f"TemperedSMC: a plated site at address {addr!r} must be normal, gamma, beta, flip, poisson or "
+                                  "negative_binomial (a plated categorical has no table rows per datum)")
         if len(self.sites) >= abi.MAX_SITES:
             raise PlanUnsupported(f"TemperedSMC: too many sites at address {addr!r}")
-        cols = cols | {self.data_col(obs)}
+        # (a count site's observed column brings its log k! column, directly after it: include/gjx_counts.h)
+        obs_col = self.count_cols(obs, addr) if count else self.data_col(obs)
+        cols = cols | {obs_col}
         lengths = {int(self.data[c].numel()) for c in cols} | ({self.data_rows} if self.data_rows is not None else set())
         if len(lengths) != 1:
             raise PlanUnsupported(f"TemperedSMC: data columns of different lengths {sorted(lengths)} at address {addr!r} "
@@ -93,10 +177,10 @@ class _TemperTracer(PlanTracer):
         site.dist, site.observed, site.out_col = dist, abi.SITE_PLATED, -1
         for k, v in enumerate(vals):
             site.arg[k] = self._arg(v)
-        site.obs = abi.Arg(abi.ARG_DATA, self.data_col(obs), 1.0, 0.0, None)
+        site.obs = abi.Arg(abi.ARG_DATA, obs_col, 1.0, 0.0, None)
         self.sites.append(site)
         self.items.append(("site", len(self.sites) - 1))
-        self.meta.append(dict(addr=addr, gen_fn=gen_fn, args=args, obs=obs, out_col=-1, is_int=dist == abi.DIST_BERNOULLI,
+        self.meta.append(dict(addr=addr, gen_fn=gen_fn, args=args, obs=obs, out_col=-1, is_int=dist >= abi.DIST_BERNOULLI,
                               dtype=gen_fn.value_dtype, path=self.prefix + (addr if isinstance(addr, tuple) else (addr,)),
                               plated=True))
         self.record(addr, None)
@@ -109,6 +193,13 @@ class _TemperTracer(PlanTracer):
             a = addr if isinstance(addr, tuple) else (addr,)
             obs = self.constraint.get_submap(*a).get_value()
             flat = [x for v in args for x in (v if isinstance(v, tuple) else (v,))]
+            if isinstance(gen_fn, (Poisson, NegativeBinomial)):
+                if obs is None:
+                    raise PlanUnsupported(f"TemperedSMC: count-valued latent at address {addr!r} (a random-walk move needs a float value)")
+                if not is_data_tensor(obs):
+                    if set().union(*[self._data_cols_of(v) for v in flat]):
+                        return self._plated(addr, gen_fn, args, obs, set())  # (refused there, naming the address)
+                    return self._observed_count(addr, gen_fn, args, obs)
             # (a categorical's 1-D tensor argument is its logits / probs vector, not data)
             cols = set().union(*[self._data_cols_of(v) for v in flat]) if flat and not isinstance(gen_fn, Categorical) else set()
             if cols or is_data_tensor(obs):
@@ -178,8 +269,8 @@ def prior_table(tracer) -> _PriorTable:
     reference to an earlier site renumbered (no site reads a plated one: its value is data)."""
     new_of, sites, progs, keep = {}, [], {}, list(tracer.keep)
     for q, s in enumerate(tracer.sites):
-        if s.observed == abi.SITE_PLATED:
-            continue
+        if s.observed == abi.SITE_PLATED or (s.observed and s.dist in abi.COUNT_DISTS):  # (nor an observed count site: the
+            continue                                                                      # importance kernels do not know the ids)
         new_of[q] = len(sites)
         c = abi.Site.from_buffer_copy(s)
         for k in range(2):
@@ -202,7 +293,9 @@ def _reads_value_of(base, other, addr):
     assert len(base.sites) == len(other.sites) and len(base.data) == len(other.data)
     observed = {s.obs.ref: m["addr"] for s, m in zip(base.sites, base.meta) if s.observed == abi.SITE_PLATED}
     tainted = {c for c, a in observed.items() if a == addr}
-    tainted |= {c for c, (t, u) in enumerate(zip(base.data, other.data)) if c not in observed and not torch.equal(t, u)}
+    # (a count site's log k! column belongs to its observed column: it is not "computed from the value" by the body)
+    tainted |= {c for c, (t, u) in enumerate(zip(base.data, other.data))
+                if c not in observed and c not in base.lf_cols and not torch.equal(t, u)}
     for s, m in zip(base.sites, base.meta):
         if s.observed != abi.SITE_PLATED or m["addr"] == addr:
             continue
@@ -496,7 +589,7 @@ class TemperedSMC(SMCAlgorithm):
         tracer = lower(self.target, self.n_particles)
         latents = [m for m in tracer.meta if m["obs"] is None]
         tplan = ops.temper_plan_create(tracer.sites, keep=(tracer.keep, tracer))
-        prior = prior_table(tracer) if tracer.data else None
+        prior = prior_table(tracer) if tracer.data or any(s.dist in abi.COUNT_DISTS for s in tracer.sites) else None
         st = self._st = dict(ops=ops, tracer=tracer, latents=latents, tplan=tplan, ws=None, prior=prior, ws_cov=None)
         return st
 
@@ -536,7 +629,7 @@ class TemperedSMC(SMCAlgorithm):
         if tracer.params:
             tplan.set_params(tracer.params)
         if tracer.data:  # uploaded at every run: an in-place update of a data tensor is seen
-            tplan.set_data([t.detach().to(device=ops.device(), dtype=torch.float32).contiguous() for t in tracer.data])
+            tplan.set_data(tracer.data_columns(ops.device()))
         dtypes = [torch.float32] * tracer.n_out
         vals = ops.importance_run(plan, prng.split_lazy(prng.fold_in(key, 0), n), n, [], dtypes, want_score=False,
                                   want_max_partials=False)[0]
@@ -654,7 +747,7 @@ class TemperedSMC(SMCAlgorithm):
             tplan = ops.temper_plan_create(tracer.sites, keep=(tracer.keep, tracer))
         if tracer.params:
             tplan.set_params(tracer.params)
-        tplan.set_data([t.detach().to(device=ops.device(), dtype=torch.float32).contiguous() for t in tracer.data])
+        tplan.set_data(tracer.data_columns(ops.device()))
         return tracer, tplan, [c.detach().to(device=ops.device(), dtype=torch.float32).contiguous() for c in cols]
 
     # -- pointwise predictive densities (include/gjx_pointwise.h) ------------------------------------------------
