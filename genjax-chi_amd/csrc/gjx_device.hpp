@@ -1934,6 +1934,21 @@ struct PlateData {
   uint32_t n_rows;
 };
 typedef const __attribute__((address_space(4))) float* PlateCol;
+// The grouped latents of a tempered plan (include/gjx_group.h): one more by-value kernel argument, of grouped plans only.
+// z_in / z_out are [G][n] columns (lane i reads and writes entry g * n + i: coalesced); the offsets and the proposal scales
+// are wave-uniform and read through pointers to the CONSTANT address space (neither is written while the kernel runs).
+constexpr int kGroupMaxSites = 4;
+struct GroupArgs {
+  const float* z_in[kGroupMaxSites];
+  float* z_out[kGroupMaxSites];
+  const float* z_scales[kGroupMaxSites];  // [G] per grouped site
+  const int32_t* off;                     // [G + 1]
+  int32_t* n_accept_z;                    // nullable
+  Key init_key;
+  uint32_t G;
+  uint32_t init;
+};
+typedef const __attribute__((address_space(4))) int32_t* GroupOff;
 
 // Kernel argument block of the pointwise launch over a plated plan (include/gjx_pointwise.h; the kernel is generated from the
 // site table, gjx_plan_jit.hpp GenPointwise; the fold below is fixed).  The workspace holds five float64 planes [W][n_rows]:

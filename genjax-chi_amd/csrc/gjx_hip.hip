@@ -20,6 +20,7 @@
 #include "../../include/gjx_predictive.h"
 #include "../../include/gjx_temper_cov.h"
 #include "../../include/gjx_counts.h"
+#include "../../include/gjx_group.h"
 // The library's own kernels keep the Philox round's plain XOR chain (gjx_device.hpp xor3): with v_bitop3_b32 the one-filter
 // LGSSM step measured 0.5 % slower (8.96e10 against 9.01e10 particle-steps/s, three alternating runs each, parent's range
 // 0.1 %), while the generated kernels, which include the header on their own, gain 6 % (importance) and 12 % (LGSSM scan);
@@ -4927,7 +4928,8 @@ int gjx_backmove_run(gjx_backsim_plan* p, const gjx_backmove_io* io, void* ws, s
 // (include/gjx_temper_cov.h), the pointwise kernel (include/gjx_pointwise.h: one source, whatever the generator), the
 // predictive kernel (include/gjx_predictive.h) and the PSIS kernel (include/gjx_psis.h: one source too).  The last three exist
 // for a plan that passes pointwise_plan_ok only (kTemperKernels below has what else they differ in).
-enum TemperKernel { kTemperMove, kTemperCovMove, kTemperPointwise, kTemperPredictive, kTemperPsis, kTemperKernelCount };
+// A plan with GROUPED sites (include/gjx_group.h) has ONE kernel, the grouped move, and none of the five.
+enum TemperKernel { kTemperMove, kTemperCovMove, kTemperPointwise, kTemperPredictive, kTemperPsis, kTemperGroupedMove, kTemperKernelCount };
 struct gjx_temper_plan {
   int n_sites, n_latents;
   int n_params;   // values set by gjx_temper_plan_set_params
@@ -4948,6 +4950,10 @@ struct gjx_temper_plan {
     gjx_expr_op ops[GJX_MAX_SITES][GJX_MAX_EXPR_OPS];
   };
   ObsExprStore* obs_expr = nullptr;  // the programs of PLATED sites' observed values (a plan's own copy, as ExprStore)
+  // include/gjx_group.h: GROUPED sites (gjx_temper_plan_create_grouped) and their groups (gjx_temper_plan_set_groups)
+  int n_grouped = 0;
+  const int32_t* group_off = nullptr;  // dev int32[n_groups + 1], borrowed
+  uint32_t n_groups = 0;
   ~gjx_temper_plan() { delete obs_expr; }
 };
 
@@ -4965,14 +4971,15 @@ constexpr TemperKernelDesc kTemperKernels[kTemperKernelCount] = {{"gjx_temper_mo
                                                 {"gjx_temper_move_cov_kernel", gjx_jit::PlanKind::temper, true, false},
                                                 {"gjx_pointwise_kernel", gjx_jit::PlanKind::temper, false, true},
                                                 {"gjx_predictive_kernel", gjx_jit::PlanKind::predictive, true, true},
-                                                {"gjx_psis_kernel", gjx_jit::PlanKind::psis, false, true}};
+                                                {"gjx_psis_kernel", gjx_jit::PlanKind::psis, false, true},
+                                                {"gjx_temper_move_grouped_kernel", gjx_jit::PlanKind::temper, true, false}};
 // Has the plan a pointwise (and a predictive, and a PSIS) source?  A PLATED site, and no per-particle input column anywhere in the table
 // (the io structs have none).
-bool pointwise_plan_ok(const gjx_temper_plan* p) { return p && p->plated && p->max_input < 0; }
+bool pointwise_plan_ok(const gjx_temper_plan* p) { return p && p->plated && p->max_input < 0 && p->n_grouped == 0; }
 // the guard of the exported *_source / *_compile_check functions of kernel k
 bool temper_kernel_ok(const gjx_temper_plan* p, TemperKernel k, int impl) {
   const TemperKernelDesc& d = kTemperKernels[k];
-  return p && (!d.plated_only || pointwise_plan_ok(p)) && (!d.per_impl || impl == 0 || impl == 1);
+  return p && (p->n_grouped > 0) == (k == kTemperGroupedMove) && (!d.plated_only || pointwise_plan_ok(p)) && (!d.per_impl || impl == 0 || impl == 1);
 }
 std::string temper_source(const gjx_temper_plan* p, TemperKernel k, int impl, PlanTables* tabs = nullptr) {
   auto run = [&](auto& g) {
@@ -4990,6 +4997,11 @@ std::string temper_source(const gjx_temper_plan* p, TemperKernel k, int impl, Pl
   }
   if (k == kTemperPsis) {
     gjx_jit::GenPsis<CSite, CArg> g;
+    return run(g);
+  }
+  if (k == kTemperGroupedMove) {
+    gjx_jit::GenTemperGrouped<CSite, CArg> g;
+    g.impl = impl;
     return run(g);
   }
   gjx_jit::GenTemper<CSite, CArg> g;
@@ -5020,7 +5032,9 @@ gjx_jit::CompiledKernel* temper_compiled(gjx_temper_plan* p, TemperKernel k, int
 // include/gjx_counts.h (allow_counts: gjx_temper_plan_create_counts): a Poisson / NegativeBinomial site, observed or plated, is
 // converted by convert_count_site (the same operand rules, nothing hoisted).  Its plated form reads log k! from the data column
 // after the observed one.
-bool plated_convert_site(const gjx_site& st, int s, CSite& c, gjx_temper_plan* p, bool allow_counts) {
+// include/gjx_group.h (n_group >= 0: gjx_temper_plan_create_grouped, n_group the grouped sites before this one): a GROUP operand
+// is validated as a DATA operand is, in a0 / a1 of a PLATED site only.
+bool plated_convert_site(const gjx_site& st, int s, CSite& c, gjx_temper_plan* p, bool allow_counts, int n_group = -1) {
   if (st.observed != 0 && st.observed != 1 && st.observed != GJX_SITE_PLATED) return false;
   const bool count = st.dist == GJX_DIST_POISSON || st.dist == GJX_DIST_NEGATIVE_BINOMIAL;
   if (count && (!allow_counts || st.observed == 0)) return false;  // (a count-valued latent has no random-walk move)
@@ -5029,7 +5043,7 @@ bool plated_convert_site(const gjx_site& st, int s, CSite& c, gjx_temper_plan* p
   gjx_site t = st;
   gjx_expr_op prog[3][GJX_MAX_EXPR_OPS];
   gjx_arg* as[3] = {&t.arg[0], &t.arg[1], &t.obs};
-  bool any = false, in_obs = false;
+  bool any = false, in_obs = false, grp = false;
   int mx = -1;
   for (int k = 0; k < 3; ++k) {
     if ((k == 1 && !two_args) || (k == 2 && !st.observed)) continue;  // (not read: as convert_site ignores them)
@@ -5040,6 +5054,11 @@ bool plated_convert_site(const gjx_site& st, int s, CSite& c, gjx_temper_plan* p
       if (a.ref > mx) mx = a.ref;
       a.kind = GJX_ARG_INPUT;
       here = true;
+    } else if (a.kind == GJX_ARG_GROUP) {
+      if (k == 2 || a.ref < 0 || a.ref >= n_group) return false;
+      a.kind = GJX_ARG_INPUT;
+      a.ref = 0;
+      grp = true;
     } else if (a.kind == GJX_ARG_EXPR) {
       const gjx_expr_op* ops = reinterpret_cast<const gjx_expr_op*>(a.table);
       if (!ops || a.ref < 1 || a.ref > GJX_MAX_EXPR_OPS) return false;
@@ -5050,6 +5069,11 @@ bool plated_convert_site(const gjx_site& st, int s, CSite& c, gjx_temper_plan* p
           if (prog[k][i].ref > mx) mx = prog[k][i].ref;
           prog[k][i].op = GJX_EXPR_INPUT;
           here = true;
+        } else if (prog[k][i].op == GJX_EXPR_GROUP) {
+          if (k == 2 || prog[k][i].ref < 0 || prog[k][i].ref >= n_group) return false;
+          prog[k][i].op = GJX_EXPR_INPUT;
+          prog[k][i].ref = 0;
+          grp = true;
         }
       a.table = reinterpret_cast<const float*>(prog[k]);
     }
@@ -5057,7 +5081,7 @@ bool plated_convert_site(const gjx_site& st, int s, CSite& c, gjx_temper_plan* p
     if (k == 2) in_obs = here;
   }
   if (st.observed != GJX_SITE_PLATED) {
-    return !any && convert(st);  // (the caller's own operands: t's programs live on this frame)
+    return !any && !grp && convert(st);  // (the caller's own operands: t's programs live on this frame)
   }
   if (!in_obs || st.dist == GJX_DIST_CATEGORICAL) return false;
   if (count) {  // obs: a plain DATA operand, log k! in the column after it
@@ -5445,9 +5469,33 @@ bool psis_carve(Carver& cv, uint64_t n_rows, uint32_t W, uint32_t M, PsisScratch
   return cv.ok;
 }
 
+// What a table with GROUPED sites must satisfy beyond its sites' own rules (include/gjx_group.h): no per-particle input
+// column; every site reference names a scalar latent (the device functions of the grouped kernel define those values alone);
+// at least one PLATED site reads a grouped value.
+bool grouped_table_ok(const gjx_temper_plan* p) {
+  if (p->max_input >= 0) return false;
+  bool any_reader = false;
+  for (int q = 0; q < p->n_sites; ++q) {
+    const CSite& c = p->sites[q];
+    for (const CArg* a : {&c.a0, &c.a1, &c.obs}) {
+      if (a == &c.obs && c.observed != GJX_SITE_PLATED) continue;
+      if ((a->kind == GJX_ARG_SITE || a->kind == GJX_ARG_TABLE) && p->sites[a->ref_site].observed != 0) return false;
+      if (a->kind == GJX_ARG_GROUP) any_reader = true;
+      if (a->kind != GJX_ARG_EXPR) continue;
+      const gjx_expr_op* ops = reinterpret_cast<const gjx_expr_op*>(a->table);
+      for (int k = 0; k < a->ref; ++k) {
+        if (ops[k].op == GJX_EXPR_SITE && p->sites[ops[k].ref].observed != 0) return false;
+        if (ops[k].op == GJX_EXPR_GROUP) any_reader = true;
+      }
+    }
+  }
+  return any_reader;
+}
+
 // gjx_temper_plan_create (allow_plated = false) and gjx_temper_plan_create_plated (include/gjx_plate.h)
+// and gjx_temper_plan_create_grouped (include/gjx_group.h: allow_grouped)
 int temper_plan_create(const gjx_site* sites, int n_sites, uint32_t flags, gjx_temper_plan** out, bool allow_plated,
-                       bool allow_counts = false) {
+                       bool allow_counts = false, bool allow_grouped = false) {
   if (!sites || !out || n_sites < 1 || n_sites > GJX_MAX_SITES || flags != 0u) return GJX_ERR_INVALID;
   gjx_temper_plan* p = new (std::nothrow) gjx_temper_plan;
   if (!p) return GJX_ERR_LAUNCH;
@@ -5458,13 +5506,23 @@ int temper_plan_create(const gjx_site* sites, int n_sites, uint32_t flags, gjx_t
   bool ok = true;
   for (int s = 0; ok && s < n_sites; ++s) {
     CSite& c = p->sites[s];
-    ok = allow_plated ? plated_convert_site(sites[s], s, c, p, allow_counts) : convert_site(sites[s], s, c);
+    if (allow_grouped && sites[s].observed == GJX_SITE_GROUPED) {  // a float-valued latent with G components: converted as a latent
+      gjx_site u = sites[s];
+      u.observed = 0;
+      ok = p->n_grouped < GJX_GROUP_MAX_SITES && u.dist >= 0 && u.dist <= GJX_DIST_BETA && convert_site(u, s, c);
+      if (!ok) break;
+      c.observed = GJX_SITE_GROUPED;
+      ++p->n_grouped;
+    } else {
+      ok = allow_plated ? plated_convert_site(sites[s], s, c, p, allow_counts, allow_grouped ? p->n_grouped : -1) : convert_site(sites[s], s, c);
+    }
     if (!ok) break;
-    if (c.observed) ++n_observed;
+    if (c.observed == GJX_SITE_GROUPED) {}
+    else if (c.observed) ++n_observed;
     else if (c.dist > GJX_DIST_BETA) ok = false;  // an integer-valued latent has no random-walk move
     else ++p->n_latents;
     for (const CArg* a : {&c.a0, &c.a1, &c.obs}) {
-      if (a == &c.obs && !c.observed) continue;
+      if (a == &c.obs && (!c.observed || c.observed == GJX_SITE_GROUPED)) continue;
       if (a->kind == GJX_ARG_PARAM && a->ref > p->max_param) p->max_param = a->ref;
       if (a->kind == GJX_ARG_INPUT && a->ref > p->max_input) p->max_input = a->ref;
     }
@@ -5490,6 +5548,10 @@ int temper_plan_create(const gjx_site* sites, int n_sites, uint32_t flags, gjx_t
       }
     }
   }
+  if (p->n_grouped > 0 && !grouped_table_ok(p)) {
+    delete p;
+    return GJX_ERR_INVALID;
+  }
   *out = p;
   return GJX_OK;
 }
@@ -5508,6 +5570,19 @@ int gjx_temper_plan_create_plated(const gjx_site* sites, int n_sites, uint32_t f
 int gjx_temper_plan_create_counts(const gjx_site* sites, int n_sites, uint32_t flags, gjx_temper_plan** out) {
   return temper_plan_create(sites, n_sites, flags, out, true, true);
 }
+int gjx_group_version(int* major, int* minor) { return version_out(major, minor, GJX_GROUP_VERSION_MAJOR, GJX_GROUP_VERSION_MINOR); }
+int gjx_temper_plan_create_grouped(const gjx_site* sites, int n_sites, uint32_t flags, gjx_temper_plan** out) {
+  bool grouped = false;
+  for (int s = 0; sites && s < n_sites && s < GJX_MAX_SITES; ++s) grouped = grouped || sites[s].observed == GJX_SITE_GROUPED;
+  return temper_plan_create(sites, n_sites, flags, out, true, grouped, grouped);
+}
+int gjx_temper_plan_set_groups(gjx_temper_plan* p, const int32_t* offsets, uint32_t G) {
+  if (!p || p->n_grouped == 0 || !offsets || G < 1 || G >= (uint32_t)GJX_GROUP_MAX_GROUPS) return GJX_ERR_INVALID;
+  p->group_off = offsets;
+  p->n_groups = G;
+  return GJX_OK;
+}
+int gjx_temper_plan_n_grouped(const gjx_temper_plan* p) { return p ? p->n_grouped : GJX_ERR_INVALID; }
 int gjx_temper_plan_set_data(gjx_temper_plan* p, const float* const* cols, int n_cols, uint64_t n_rows) {
   if (!p || !p->plated || !cols || n_cols < 1 || n_cols > GJX_PLATE_MAX_COLS || n_cols <= p->max_data || n_rows < 1 ||
       n_rows >= (1ull << 31))
@@ -5537,14 +5612,17 @@ int gjx_temper_plan_set_params(gjx_temper_plan* p, const float* params, int n_pa
 }
 int gjx_temper_plan_n_latents(const gjx_temper_plan* p) { return p ? p->n_latents : GJX_ERR_INVALID; }
 int gjx_temper_plan_source(const gjx_temper_plan* p, int impl, char* buf, size_t buf_len, size_t* needed) {
-  return temper_source_out(p, kTemperMove, impl, buf, buf_len, needed);
+  return temper_source_out(p, p && p->n_grouped ? kTemperGroupedMove : kTemperMove, impl, buf, buf_len, needed);
 }
-int gjx_temper_plan_compile_check(const gjx_temper_plan* p, int impl) { return temper_compile_check(p, kTemperMove, impl); }
+int gjx_temper_plan_compile_check(const gjx_temper_plan* p, int impl) {
+  return temper_compile_check(p, p && p->n_grouped ? kTemperGroupedMove : kTemperMove, impl);
+}
 }  // extern "C"
 namespace {
 // gjx_temper_move (factor == nullptr, cov == false) and gjx_temper_move_cov (include/gjx_temper_cov.h: scales are not read)
-int temper_move(gjx_temper_plan* p, const gjx_temper_io* io, bool cov, const float* factor, gjx_stream s) {
-  if (!p || !io || (cov && !factor) || io->n < 1 || io->n >= (1ull << 31) || (io->impl != 0 && io->impl != 1) || (io->impl == 0 && io->key_lane != 0) ||
+// and gjx_temper_move_grouped (include/gjx_group.h: gio, whose `t` is io)
+int temper_move(gjx_temper_plan* p, const gjx_temper_io* io, bool cov, const float* factor, gjx_stream s, const gjx_group_io* gio = nullptr) {
+  if (!p || !io || (p->n_grouped > 0) != (gio != nullptr) || (cov && !factor) || io->n < 1 || io->n >= (1ull << 31) || (io->impl != 0 && io->impl != 1) || (io->impl == 0 && io->key_lane != 0) ||
       io->n_moves < 0 || io->n_moves > GJX_TEMPER_MAX_MOVES)
     return GJX_ERR_INVALID;
   if (!io->lp_out || !io->ll_out || (!io->recompute && (!io->lp_in || !io->ll_in)) || (!cov && io->n_moves > 0 && !io->scales))
@@ -5566,8 +5644,19 @@ int temper_move(gjx_temper_plan* p, const gjx_temper_io* io, bool cov, const flo
     if (c <= p->max_input && !io->input_cols[c]) return GJX_ERR_INVALID;
     cols.in[c] = io->input_cols[c];
   }
+  GroupArgs ga;
+  memset(&ga, 0, sizeof ga);
+  if (gio) {
+    if (!p->group_off || (gio->init && io->impl == 0 && gio->init_key_lane != 0)) return GJX_ERR_INVALID;
+    for (int g = 0; g < p->n_grouped; ++g) {
+      if (!gio->z_out[g] || (!gio->init && !gio->z_in[g]) || (io->n_moves > 0 && !gio->z_scales[g])) return GJX_ERR_INVALID;
+      ga.z_in[g] = gio->z_in[g]; ga.z_out[g] = gio->z_out[g]; ga.z_scales[g] = gio->z_scales[g];
+    }
+    ga.off = p->group_off; ga.n_accept_z = gio->n_accept_z; ga.G = p->n_groups; ga.init = gio->init ? 1u : 0u;
+    ga.init_key = Key{gio->init_key[0], gio->init_key[1], (uint32_t)gio->init_key_lane, (uint32_t)(gio->init_key_lane >> 32)};
+  }
   if (!gjx_jit::enabled()) return GJX_ERR_UNSUPPORTED;  // a generated kernel only
-  gjx_jit::CompiledKernel* k = temper_compiled(p, cov ? kTemperCovMove : kTemperMove, io->impl);
+  gjx_jit::CompiledKernel* k = temper_compiled(p, gio ? kTemperGroupedMove : cov ? kTemperCovMove : kTemperMove, io->impl);
   if (!k) return GJX_ERR_JIT;
   A.lp_in = io->lp_in; A.ll_in = io->ll_in; A.lp_out = io->lp_out; A.ll_out = io->ll_out;
   A.anc = io->ancestors; A.n_accept = io->n_accept;
@@ -5584,7 +5673,8 @@ int temper_move(gjx_temper_plan* p, const gjx_temper_io* io, bool cov, const flo
   PlateData pd = p->data;
   void* args[] = {&A, &cols, &prm, &tabs, &pd};  // (the kernel of a plan without plated sites takes the first four)
   void* cov_args[] = {&A, &cols, &prm, &tabs, &factor, &pd};
-  return launch_generated(k->fn, grid, 1, kBlock, s, cov ? cov_args : args);
+  void* group_args[] = {&A, &cols, &prm, &tabs, &pd, &ga};
+  return launch_generated(k->fn, grid, 1, kBlock, s, gio ? group_args : cov ? cov_args : args);
 }
 
 // The chunks of particles of a launch whose lanes are data rows (gjx_pointwise_chunks, gjx_predictive_chunks): workgroups of
@@ -5641,6 +5731,9 @@ int plated_launch(gjx_temper_plan* p, TemperKernel k, int impl, const IO* io, bo
 }  // namespace
 extern "C" {
 int gjx_temper_move(gjx_temper_plan* p, const gjx_temper_io* io, gjx_stream s) { return temper_move(p, io, false, nullptr, s); }
+int gjx_temper_move_grouped(gjx_temper_plan* p, const gjx_group_io* io, gjx_stream s) {
+  return io ? temper_move(p, &io->t, false, nullptr, s, io) : GJX_ERR_INVALID;
+}
 
 uint32_t gjx_temper_ladder_blocks(uint64_t n) {
   const uint64_t rows = nrows_of(n);

@@ -212,6 +212,9 @@ struct SiteEmitter {
       // (include/gjx_plate.h: column `ref` at the row of the plated loop — dc<ref> is the row's value, defined by GenTemper)
       // (with the emitter's suffix: GenPredictive holds two rows per lane, dc<ref>A and dc<ref>B)
       case GJX_ARG_DATA: return "((" + flit(a.scale) + " * dc" + std::to_string(a.ref) + sfx + ") + " + flit(a.offset) + ")";
+      // (include/gjx_group.h: grouped site `ref` at the group of the row — gz_<ref> is the current group's value, an argument
+      // of the device functions GenTemperGrouped emits)
+      case GJX_ARG_GROUP: return "((" + flit(a.scale) + " * gz_" + std::to_string(a.ref) + sfx + ") + " + flit(a.offset) + ")";
       case GJX_ARG_PARAM:
         // (an SMC plan's parameter as it stands is the row's value itself: no multiply by 1, no add of 0 — a uniform value
         // stays in its scalar register — and what gjx_smc_plan_set_params derives the site's constants from)
@@ -232,6 +235,7 @@ struct SiteEmitter {
             case GJX_EXPR_STATE: st.push_back("st_" + r + sfx); break;
             case GJX_EXPR_OBS: st.push_back("a.obs[" + r + "]"); break;
             case GJX_EXPR_DATA: st.push_back("dc" + r + sfx); break;
+            case GJX_EXPR_GROUP: st.push_back("gz_" + r + sfx); break;
             case GJX_EXPR_NEG: st.back() = "(-" + st.back() + ")"; break;
             case GJX_EXPR_EXP: st.back() = "e_exp(" + st.back() + ")"; break;
             case GJX_EXPR_LOG: st.back() = "m_log(" + st.back() + ")"; break;
@@ -302,7 +306,7 @@ struct SiteEmitter {
   static bool literal_program(const CArgT& a) {
     const gjx_expr_op* ops = reinterpret_cast<const gjx_expr_op*>(a.table);
     for (int k = 0; k < a.ref; ++k)
-      if ((ops[k].op >= GJX_EXPR_SITE && ops[k].op <= GJX_EXPR_OBS) || ops[k].op == GJX_EXPR_DATA) return false;
+      if ((ops[k].op >= GJX_EXPR_SITE && ops[k].op <= GJX_EXPR_OBS) || ops[k].op == GJX_EXPR_DATA || ops[k].op == GJX_EXPR_GROUP) return false;
     return true;
   }
 
@@ -378,6 +382,7 @@ struct SiteEmitter {
       else if (st.obs.kind == GJX_ARG_OBS) ov = "a.obs[" + std::to_string(st.obs.ref) + "]";
       else if (st.obs.kind == GJX_ARG_NEXT) ov = "nx_" + std::to_string(st.obs.ref);  // (transition tables: gjx_backsim.h)
       else if (st.obs.kind == GJX_ARG_PARAM || st.obs.kind == GJX_ARG_DATA || st.obs.kind == GJX_ARG_EXPR) ov = arg(st.obs);  // (DATA, EXPR: a plated site's)
+      else if (st.obs.kind == GJX_ARG_GROUP) ov = "gz_" + std::to_string(st.obs.ref) + sfx;  // (a grouped site's own value: TemperTable)
       else ov = "cols.in[" + std::to_string(st.obs.ref) + "][li" + sfx + "]";
       // (a count keeps its float too: the support test k >= 0 of gjx_counts.h is taken before any conversion to an integer)
       if (is_count(st)) o << ind << "const float vk" << Q << " = __builtin_rintf(" << ov << ");\n" << ind << "const int32_t vi" << Q << " = (int32_t)vk" << Q << ";\n";
@@ -1552,6 +1557,19 @@ struct TemperTable {
   int L = 0;                // latents
   std::vector<int> plated;  // table positions of the plated sites: plated site s is plated[s]
   std::vector<int> cs;      // the data columns the plated sites read between them, in ascending order
+  std::vector<int> grouped;  // table positions of the grouped sites (include/gjx_group.h): grouped site s is grouped[s]
+
+  // Does site `st` read a grouped value (a GROUP operand in a0 / a1, directly or in a program)?
+  static bool reads_group(const CSiteT& st) {
+    for (const CArgT* a : {&st.a0, &st.a1}) {
+      if (a->kind == GJX_ARG_GROUP) return true;
+      if (a->kind != GJX_ARG_EXPR) continue;
+      const gjx_expr_op* ops = reinterpret_cast<const gjx_expr_op*>(a->table);
+      for (int k = 0; k < a->ref; ++k)
+        if (ops[k].op == GJX_EXPR_GROUP) return true;
+    }
+    return false;
+  }
 
   // The data columns plated site q reads (a0, a1, obs; affine operands and program leaves), in ascending order.
   static std::vector<int> plate_cols(const CSiteT& st) {
@@ -1581,6 +1599,16 @@ struct TemperTable {
         tab[q].observed = drawn ? 0 : 1;
         if (drawn) tab[q].out_col = -1;
         plated.push_back(q);
+      }
+      if (sites[q].observed == GJX_SITE_GROUPED) {  // (include/gjx_group.h) an observed site whose value is the argument gz_<s>
+        tab[q].observed = 1;
+        tab[q].out_col = -1;
+        tab[q].obs = CArgT{};
+        tab[q].obs.kind = GJX_ARG_GROUP;
+        tab[q].obs.ref = (int)grouped.size();
+        tab[q].obs.scale = 1.0f;
+        grouped.push_back(q);
+        continue;
       }
       if (sites[q].observed) continue;
       tab[q].observed = 1;
@@ -1703,6 +1731,28 @@ struct GenTemper {
     o << "  ll = ll + (float)pacc" << Q << ";\n";
   }
 
+  // `v` outside the OPEN support of a latent of family `dist` (a NaN included) has log-density -inf, whatever the density
+  // formula gives there: the test that guards `lp`, or "" for a Normal.
+  static std::string in_support(int dist, const std::string& v) {
+    return dist == GJX_DIST_GAMMA ? "(" + v + " > 0.0f)" : dist == GJX_DIST_BETA ? "(" + v + " > 0.0f && " + v + " < 1.0f)" : "";
+  }
+  // Site q of tm_assess, by emitter `e` (over `o` and the shadow table `tab`): a plated site's loop, an observed site's term
+  // into ll, a latent's into lp.
+  void emit_site(SiteEmitter<CSiteT, CArgT>& e, int q, const CSiteT* tab) {
+    if (sites[q].observed == GJX_SITE_PLATED) {
+      emit_plated(q, tab);
+      return;
+    }
+    e.head(q);
+    if (sites[q].observed) {
+      o << "  ll = ll + " << e.lp_of(q) << ";\n";
+      return;
+    }
+    const std::string in = in_support(sites[q].dist, e.nm("vf", q));
+    if (in.empty()) o << "  lp = lp + " << e.lp_of(q) << ";\n";
+    else o << "  lp = lp + (" << in << " ? " << e.lp_of(q) << " : -__builtin_inff());\n";
+  }
+
   std::string run() {
     const std::string I = std::to_string(impl);
     emit_prelude(o);
@@ -1714,23 +1764,7 @@ struct GenTemper {
     o << "  (void)cols; (void)prm; (void)tabs; (void)li;\n  float lp = 0.0f, ll = 0.0f;\n";
     SiteEmitter<CSiteT, CArgT> e{o, impl, 0, t.tab.data(), n_sites, "  ", ""};
     e.exact_cuts = false;
-    for (int q = 0; q < n_sites; ++q) {
-      if (sites[q].observed == GJX_SITE_PLATED) {
-        emit_plated(q, t.tab.data());
-        continue;
-      }
-      e.head(q);
-      if (sites[q].observed) {
-        o << "  ll = ll + " << e.lp_of(q) << ";\n";
-        continue;
-      }
-      // a latent outside its site's OPEN support (a NaN included) has log-density -inf, whatever the density formula gives there
-      const std::string v = e.nm("vf", q);
-      const std::string in = sites[q].dist == GJX_DIST_GAMMA ? "(" + v + " > 0.0f)"
-                             : sites[q].dist == GJX_DIST_BETA ? "(" + v + " > 0.0f && " + v + " < 1.0f)" : "";
-      if (in.empty()) o << "  lp = lp + " << e.lp_of(q) << ";\n";
-      else o << "  lp = lp + (" << in << " ? " << e.lp_of(q) << " : -__builtin_inff());\n";
-    }
+    for (int q = 0; q < n_sites; ++q) emit_site(e, q, t.tab.data());
     o << "  lp_out = lp; ll_out = ll;\n}\n";
     if (cov) o << "typedef const __attribute__((address_space(4))) float* FactorPtr;\n";
     o << "extern \"C\" __global__ __launch_bounds__(256) void " << (cov ? "gjx_temper_move_cov_kernel" : "gjx_temper_move_kernel")
@@ -1780,6 +1814,229 @@ struct GenTemper {
     o << "    }\n";
     for (int l = 0; l < L; ++l) o << "    a.x_out[" << l << "][i] = x" << l << ";\n";
     o << "    a.lp_out[i] = lp;\n    a.ll_out[i] = ll;\n    if (a.n_accept) a.n_accept[i] = acc;\n";
+    o << "  }\n}\n";
+    return o.str();
+  }
+};
+
+// The move kernel of a tempered plan with GROUPED latents (include/gjx_group.h): GenTemper's kernel with a [G][n] column per
+// grouped site next to the scalars in registers.  One lane per particle, no LDS, no barrier.
+//   tm_flat    tm_assess over the FLAT sites (GenTemper::emit_site): the scalar latents' terms and every observed or plated
+//              site that reads no grouped value.
+//   gz_lp      the f32 sum over the grouped sites of the log-density at the group's values gz_<s> (arguments of the function;
+//              SiteEmitter names a GROUP operand so), -inf outside the open support.
+//   gm_term    one data row: the group-reading plated sites' f32 log-densities into a float64 accumulator, in table order.
+//   gm_rows1 / gm_rows2   the rows lo .. hi - 1 of one group, at the group's values (and, gm_rows2, at the proposal's in the same
+//              pass: the two evaluations share the row's data registers).  The loop of GenTemper::emit_plated: the bounds are
+//              wave-uniform (read from the offsets through a constant-address-space pointer and clamped to n_rows), so the
+//              row reads are scalar loads issued for a block of kPlateBlock rows, then a remainder loop.
+//   gm_assess  LZ and A of the specification: the loop over the groups at the lane's own entries of z_out (coalesced loads).
+//   gi_draw    init: the grouped sites as the LATENT sites of a table of their own (SiteEmitter's draws, numbered among
+//              themselves) under the key split_at(fold_in(init_key, g), i).
+// The key folds of a group (fold_in(fold_in(k_r, 2), g) and its two children) are wave-uniform: scalar-side cipher blocks.
+// The grouped columns, offsets and scales are one more kernel argument (GroupArgs), of grouped plans only.
+template <class CSiteT, class CArgT>
+struct GenTemperGrouped {
+  std::ostringstream o;
+  int impl;
+  const CSiteT* sites;
+  int n_sites;
+
+  std::string run() {
+    using Table = TemperTable<CSiteT, CArgT>;
+    using Emitter = SiteEmitter<CSiteT, CArgT>;
+    constexpr int NB = GenTemper<CSiteT, CArgT>::kPlateBlock;
+    const std::string I = std::to_string(impl);
+    emit_prelude(o);
+    const Table t(sites, n_sites);
+    const int L = t.L, S = (int)t.grouped.size();
+    bool gread[GJX_MAX_SITES] = {}, flat[GJX_MAX_SITES] = {}, used[GJX_PLATE_MAX_COLS] = {};
+    for (int q = 0; q < n_sites; ++q) {
+      gread[q] = sites[q].observed == GJX_SITE_PLATED && Table::reads_group(sites[q]);
+      flat[q] = !gread[q] && sites[q].observed != GJX_SITE_GROUPED;
+      if (gread[q])
+        for (int c : Table::plate_cols(sites[q])) used[c] = true;
+    }
+    const std::vector<int> gcs = Table::set_of(used);  // the data columns the group-reading sites read
+    auto zl = [&](const std::string& pre, const std::string& post = "") {  // pre0post ... pre<S-1>post
+      std::string r;
+      for (int s = 0; s < S; ++s) r += pre + std::to_string(s) + post;
+      return r;
+    };
+    auto dl = [&](const std::string& pre, const std::string& post = "") {
+      std::string r;
+      for (int c : gcs) r += pre + std::to_string(c) + post;
+      return r;
+    };
+    const std::string head = "(const PlanParams& prm, const PlanTables& tabs", nxs = t.list(", float nx_"), gzs = zl(", float gz_");
+    auto latent_heads = [&](Emitter& e) {  // the scalar latents' values vf<q> = nx_<l>: what a later site's argument may name
+      for (int q = 0; q < n_sites; ++q)
+        if (sites[q].observed == 0) e.head(q);
+    };
+
+    // -- tm_flat ---------------------------------------------------------------------------------------------------------------
+    {
+      GenTemper<CSiteT, CArgT> g;
+      g.impl = impl; g.sites = sites; g.n_sites = n_sites;
+      Emitter e{g.o, impl, 0, t.tab.data(), n_sites, "  ", ""};
+      e.exact_cuts = false;
+      o << "__device__ __forceinline__ void tm_flat(const RunCols& cols, const PlanParams& prm, const PlanTables& tabs, uint32_t li" << nxs
+        << ", float& lp_out, float& ll_out, const PlateData& pd) {\n";
+      o << "  (void)cols; (void)prm; (void)tabs; (void)li; (void)pd;\n  float lp = 0.0f, ll = 0.0f;\n";
+      for (int q = 0; q < n_sites; ++q)
+        if (flat[q]) g.emit_site(e, q, t.tab.data());
+      o << g.o.str() << "  lp_out = lp; ll_out = ll;\n}\n";
+    }
+    // -- gz_lp -----------------------------------------------------------------------------------------------------------------
+    {
+      Emitter e{o, impl, 0, t.tab.data(), n_sites, "  ", ""};
+      e.exact_cuts = false;
+      o << "__device__ __forceinline__ float gz_lp" << head << nxs << gzs << ") {\n  (void)prm; (void)tabs;\n";
+      latent_heads(e);
+      o << "  float lp = 0.0f;\n";
+      for (int q : t.grouped) {
+        e.head(q);
+        const std::string in = GenTemper<CSiteT, CArgT>::in_support(sites[q].dist, e.nm("vf", q));
+        if (in.empty()) o << "  lp = lp + " << e.lp_of(q) << ";\n";
+        else o << "  lp = lp + (" << in << " ? " << e.lp_of(q) << " : -__builtin_inff());\n";
+      }
+      o << "  return lp;\n}\n";
+    }
+    // -- gm_term ---------------------------------------------------------------------------------------------------------------
+    {
+      Emitter e{o, impl, 0, t.tab.data(), n_sites, "  ", ""};
+      e.exact_cuts = false;
+      o << "__device__ __forceinline__ void gm_term" << head << nxs << gzs << dl(", float dc") << ", double& acc) {\n  (void)prm; (void)tabs;\n";
+      latent_heads(e);
+      for (int q = 0; q < n_sites; ++q) {
+        if (!gread[q]) continue;
+        e.head(q);
+        o << "  acc = acc + (double)(" << e.lp_of(q) << ");\n";
+      }
+      o << "}\n";
+    }
+    // -- gm_rows1, gm_rows2 ------------------------------------------------------------------------------------------------------
+    for (int two = 0; two < 2; ++two) {
+      o << "__device__ __forceinline__ void gm_rows" << (two ? 2 : 1) << head << ", const PlateData& pd, uint32_t lo, uint32_t hi" << nxs << gzs
+        << (two ? zl(", float gy_") : "") << ", double& acc" << (two ? ", double& accn" : "") << ") {\n";
+      for (int c : gcs) o << "  const PlateCol pc" << c << " = (PlateCol)pd.col[" << c << "];\n";
+      auto row = [&](const std::string& ind, const std::string& dcs) {
+        o << ind << "gm_term(prm, tabs" << t.list(", nx_") << zl(", gz_") << dcs << ", acc);\n";
+        if (two) o << ind << "gm_term(prm, tabs" << t.list(", nx_") << zl(", gy_") << dcs << ", accn);\n";
+      };
+      o << "  uint32_t d = lo;\n  for (; d + " << NB << "u <= hi; d += " << NB << "u) {\n";
+      for (int c : gcs)
+        for (int j = 0; j < NB; ++j) o << "    const float r" << c << "_" << j << " = pc" << c << "[d + " << j << "u];\n";
+      for (int j = 0; j < NB; ++j) row("    ", dl(", r", "_" + std::to_string(j)));
+      o << "  }\n  for (; d < hi; ++d) {\n";
+      for (int c : gcs) o << "    const float r" << c << " = pc" << c << "[d];\n";
+      row("    ", dl(", r"));
+      o << "  }\n}\n";
+    }
+    // -- gm_assess ---------------------------------------------------------------------------------------------------------------
+    auto bounds = [](const std::string& ind) {  // the rows of group g, each bound clamped to n_rows
+      return ind + "uint32_t lo = (uint32_t)off[g], hi = (uint32_t)off[g + 1u];\n" + ind + "lo = lo < pd.n_rows ? lo : pd.n_rows;\n" + ind +
+             "hi = hi < pd.n_rows ? hi : pd.n_rows;\n";
+    };
+    o << "__device__ __forceinline__ void gm_assess" << head << ", const PlateData& pd, const GroupArgs& ga, GroupOff off, uint32_t n, uint32_t i" << nxs
+      << ", double& lz_out, double& a_out) {\n  double LZ = 0.0, A = 0.0;\n  for (uint32_t g = 0; g < ga.G; ++g) {\n" << bounds("    ");
+    for (int s = 0; s < S; ++s) o << "    const float z" << s << " = ga.z_out[" << s << "][(size_t)g * n + i];\n";
+    o << "    LZ = LZ + (double)gz_lp(prm, tabs" << t.list(", nx_") << zl(", z") << ");\n";
+    o << "    double acc = 0.0;\n    gm_rows1(prm, tabs, pd, lo, hi" << t.list(", nx_") << zl(", z") << ", acc);\n    A = A + acc;\n  }\n";
+    o << "  lz_out = LZ; a_out = A;\n}\n";
+    // -- gi_draw -----------------------------------------------------------------------------------------------------------------
+    {
+      std::vector<CSiteT> drawn(t.tab);
+      ScopeInfo si;
+      si.n_scopes = 0;
+      si.parent[0] = -1;
+      for (int q = 0, s = 0; q < n_sites; ++q) {
+        si.site_scope[q] = 0;
+        si.fold_t[q] = (uint32_t)s + 1u;
+        si.fold_p[q] = (uint32_t)s;
+        if (s < S && t.grouped[s] == q) {
+          drawn[q].observed = 0;
+          ++s;
+        }
+      }
+      Emitter e{o, impl, 0, drawn.data(), n_sites, "  ", ""};
+      e.exact_cuts = false; e.store_values = false; e.defer_acc = true; e.sc = &si;
+      o << "__device__ __forceinline__ void gi_draw" << head << ", Key pkey" << nxs << ", float (&zv)[" << S << "]) {\n  (void)prm; (void)tabs; (void)pkey;\n";
+      latent_heads(e);
+      for (int s = 0; s < S; ++s) {
+        e.head(t.grouped[s]);
+        e.tail(t.grouped[s]);
+        o << "  zv[" << s << "] = " << e.nm("vf", t.grouped[s]) << ";\n";
+      }
+      o << "}\n";
+    }
+    // -- the kernel ----------------------------------------------------------------------------------------------------------------
+    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_temper_move_grouped_kernel(TemperArgs a, RunCols cols, PlanParams prm, "
+         "PlanTables tabs, PlateData pd, GroupArgs ga) {\n";
+    o << "  const uint32_t n = a.n;\n  const GroupOff off = (GroupOff)ga.off;\n";
+    for (int s = 0; s < S; ++s) o << "  const PlateCol zs" << s << " = (PlateCol)ga.z_scales[" << s << "];\n";
+    o << "  for (uint64_t i64 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i64 < n; i64 += (uint64_t)gridDim.x * blockDim.x) {\n";
+    o << "    const uint32_t i = (uint32_t)i64;\n";
+    o << "    uint32_t an = a.anc ? (uint32_t)a.anc[i] : i;\n    an = an < n ? an : n - 1u;\n";
+    for (int l = 0; l < L; ++l) o << "    float x" << l << " = a.x_in[" << l << "][an];\n";
+    o << "    if (ga.init) {\n      for (uint32_t g = 0; g < ga.G; ++g) {\n";
+    o << "        float zv[" << S << "];\n        gi_draw(prm, tabs, split_at<" << I << ">(fold_in<" << I << ">(ga.init_key, g), (uint64_t)i)" << t.list(", x") << ", zv);\n";
+    for (int s = 0; s < S; ++s) o << "        ga.z_out[" << s << "][(size_t)g * n + i] = zv[" << s << "];\n";
+    o << "      }\n    } else {\n      for (uint32_t g = 0; g < ga.G; ++g) {\n";
+    for (int s = 0; s < S; ++s) o << "        ga.z_out[" << s << "][(size_t)g * n + i] = ga.z_in[" << s << "][(size_t)g * n + an];\n";
+    o << "      }\n    }\n";
+    o << "    float lp, ll, lpf = 0.0f, llf = 0.0f;\n";
+    o << "    if (a.recompute || a.n_moves) tm_flat(cols, prm, tabs, i" << t.list(", x") << ", lpf, llf, pd);\n";
+    o << "    if (a.recompute) {\n      double LZ, A;\n      gm_assess(prm, tabs, pd, ga, off, n, i" << t.list(", x") << ", LZ, A);\n";
+    o << "      lp = lpf + (float)LZ; ll = llf + (float)A;\n    } else { lp = a.lp_in[an]; ll = a.ll_in[an]; }\n";
+    o << "    int32_t acc = 0, accz = 0;\n";
+    o << "    for (uint32_t r = 0; r < a.n_moves; ++r) {\n";
+    o << "      const Key kr = fold_in<" << I << ">(a.key, r);\n";
+    o << "      const Key pk = split_at<" << I << ">(fold_in<" << I << ">(kr, 0u), (uint64_t)i);\n";
+    o << "      const Key ak = split_at<" << I << ">(fold_in<" << I << ">(kr, 1u), (uint64_t)i);\n";
+    for (int l = 0; l < L; ++l) {
+      const uint32_t fold = impl == 0 ? (uint32_t)(l + 1) : (uint32_t)l;
+      o << "      const float t" << l << " = a.scales[" << l << "] * site_normal<" << I << ">(Stream<" << I << ">(pk, true, " << fold << "u));\n";
+      o << "      const float y" << l << " = x" << l << " + t" << l << ";\n";
+    }
+    o << "      {\n        float lpfn, llfn;\n        tm_flat(cols, prm, tabs, i" << t.list(", y") << ", lpfn, llfn, pd);\n";
+    o << "        double LZn, An;\n        gm_assess(prm, tabs, pd, ga, off, n, i" << t.list(", y") << ", LZn, An);\n";
+    o << "        const float lpn = lpfn + (float)LZn;\n        const float lln = llfn + (float)An;\n";
+    o << "        const float bh = a.beta * ll;\n        const float h = lp + bh;\n";
+    o << "        const float bn = a.beta * lln;\n        const float hn = lpn + bn;\n";
+    o << "        const float d = hn - h;\n";
+    o << "        const float lg = m_log(uniform01(Stream<" << I << ">(ak, false, 0u).bits32(0u)));\n";
+    o << "        if (d >= 0.0f || lg < d) {";
+    for (int l = 0; l < L; ++l) o << " x" << l << " = y" << l << ";";
+    o << " lp = lpn; ll = lln; lpf = lpfn; llf = llfn; ++acc; }\n      }\n";
+    // the group phase: Metropolis within Gibbs, one group at a time, against the group's own rows
+    o << "      const Key kz = fold_in<" << I << ">(kr, 2u);\n      double LZ = 0.0, A = 0.0;\n";
+    o << "      for (uint32_t g = 0; g < ga.G; ++g) {\n";
+    o << "        const Key kg = fold_in<" << I << ">(kz, g);\n";
+    o << "        const Key gpk = split_at<" << I << ">(fold_in<" << I << ">(kg, 0u), (uint64_t)i);\n";
+    o << "        const Key gak = split_at<" << I << ">(fold_in<" << I << ">(kg, 1u), (uint64_t)i);\n";
+    o << bounds("        ");
+    o << "        const size_t zi = (size_t)g * n + i;\n";
+    for (int s = 0; s < S; ++s) {
+      const uint32_t fold = impl == 0 ? (uint32_t)(s + 1) : (uint32_t)s;
+      o << "        const float zc" << s << " = ga.z_out[" << s << "][zi];\n";
+      o << "        const float zw" << s << " = zs" << s << "[g] * site_normal<" << I << ">(Stream<" << I << ">(gpk, true, " << fold << "u));\n";
+      o << "        const float zy" << s << " = zc" << s << " + zw" << s << ";\n";
+    }
+    o << "        const float lz = gz_lp(prm, tabs" << t.list(", x") << zl(", zc") << ");\n";
+    o << "        const float lzn = gz_lp(prm, tabs" << t.list(", x") << zl(", zy") << ");\n";
+    o << "        double ac = 0.0, acn = 0.0;\n";
+    o << "        gm_rows2(prm, tabs, pd, lo, hi" << t.list(", x") << zl(", zc") << zl(", zy") << ", ac, acn);\n";
+    o << "        const float dz = lzn - lz;\n        const float da = (float)(acn - ac);\n        const float bd = a.beta * da;\n";
+    o << "        const float d = dz + bd;\n";
+    o << "        const float lg = m_log(uniform01(Stream<" << I << ">(gak, false, 0u).bits32(0u)));\n";
+    o << "        const bool ok = d >= 0.0f || lg < d;\n        if (ok) {";
+    for (int s = 0; s < S; ++s) o << " ga.z_out[" << s << "][zi] = zy" << s << ";";
+    o << " ++accz; }\n";
+    o << "        LZ = LZ + (double)(ok ? lzn : lz);\n        A = A + (ok ? acn : ac);\n      }\n";
+    o << "      lp = lpf + (float)LZ;\n      ll = llf + (float)A;\n    }\n";
+    for (int l = 0; l < L; ++l) o << "    a.x_out[" << l << "][i] = x" << l << ";\n";
+    o << "    a.lp_out[i] = lp;\n    a.ll_out[i] = ll;\n    if (a.n_accept) a.n_accept[i] = acc;\n    if (ga.n_accept_z) ga.n_accept_z[i] = accz;\n";
     o << "  }\n}\n";
     return o.str();
   }

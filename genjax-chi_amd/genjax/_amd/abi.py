@@ -116,6 +116,10 @@ class CountsUnavailable(HeaderUnavailable):
     header, why = "gjx_counts.h", "the Poisson and negative-binomial densities and samplers are HIP kernels only"
 
 
+class GroupUnavailable(HeaderUnavailable):
+    header, why = "gjx_group.h", "grouped latents live in the generated tempered move kernel only"
+
+
 class TemperCovUnavailable(HeaderUnavailable):
     header, why = "gjx_temper_cov.h", "the population moments and the covariance move run as HIP kernels only"
 
@@ -802,6 +806,39 @@ COUNTS_PROTOTYPES = {
 }
 COUNTS_ABI_VERSION = (0, 1)
 
+# include/gjx_group.h: a FIFTEENTH header, same arrangement — grouped latents of a tempered plan: a site mode, an argument kind
+# and a program leaf of its own, a creator, the setter of the group offsets and the grouped move.  Bound before "temper": the
+# slots after it are pinned by the suites of the other headers.
+SITE_GROUPED = 5          # gjx_group.h: GJX_SITE_GROUPED (gjx_site.observed)
+ARG_GROUP = 10            # ... GJX_ARG_GROUP (gjx_arg.kind)
+EXPR_GROUP = 22           # ... GJX_EXPR_GROUP (gjx_expr_op.op)
+GROUP_MAX_SITES = 4       # ... GJX_GROUP_MAX_SITES
+GROUP_MAX_GROUPS = 1 << 24  # ... GJX_GROUP_MAX_GROUPS
+
+
+class GroupIO(C.Structure):
+    """gjx_group_io (include/gjx_group.h)."""
+    _fields_ = [
+        ("t", TemperIO),
+        ("z_in", C.c_void_p * GROUP_MAX_SITES),
+        ("z_out", C.c_void_p * GROUP_MAX_SITES),
+        ("z_scales", C.c_void_p * GROUP_MAX_SITES),
+        ("n_accept_z", C.c_void_p),
+        ("init", C.c_int32),
+        ("init_key", C.c_uint32 * 2),
+        ("init_key_lane", C.c_uint64),
+    ]
+
+
+GROUP_PROTOTYPES = {
+    "gjx_group_version": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gjx_temper_plan_create_grouped": (C.c_int, [C.POINTER(Site), C.c_int, C.c_uint32, C.POINTER(_P)]),
+    "gjx_temper_plan_set_groups": (C.c_int, [_P, _P, C.c_uint32]),
+    "gjx_temper_plan_n_grouped": (C.c_int, [_P]),
+    "gjx_temper_move_grouped": (C.c_int, [_P, C.POINTER(GroupIO), _P]),
+}
+GROUP_ABI_VERSION = (0, 1)
+
 # The optional headers, in the order they are bound: every one is exported by libgjx_hip.so only and bound if present.
 class Header(collections.namedtuple("Header", "key header version_fn prototypes version_name unavailable")):
     @property
@@ -826,6 +863,7 @@ PLAN_HEADERS = {h.key: h for h in (
     Header("smc_params", "gjx_smc_params.h", "gjx_smc_params_version", SMC_PARAMS_PROTOTYPES, "SMC_PARAMS_ABI_VERSION",
            SmcParamsUnavailable),
     Header("csmc", "gjx_csmc.h", "gjx_csmc_version", CSMC_PROTOTYPES, "CSMC_ABI_VERSION", CsmcUnavailable),
+    Header("group", "gjx_group.h", "gjx_group_version", GROUP_PROTOTYPES, "GROUP_ABI_VERSION", GroupUnavailable),
     Header("temper", "gjx_temper.h", "gjx_temper_version", TEMPER_PROTOTYPES, "TEMPER_ABI_VERSION", TemperUnavailable),
     Header("counts", "gjx_counts.h", "gjx_counts_version", COUNTS_PROTOTYPES, "COUNTS_ABI_VERSION", CountsUnavailable),
     Header("psis", "gjx_psis.h", "gjx_psis_version", PSIS_PROTOTYPES, "PSIS_ABI_VERSION", PsisUnavailable),
@@ -854,6 +892,7 @@ _HEADER_OF = {name: h for h in all_optional_headers() for name in h.prototypes} 
 
 _NO_STATUS = {
     "gjx_temper_plan_n_latents",
+    "gjx_temper_plan_n_grouped",
     "gjx_temper_ladder_blocks",
     "gjx_temper_ladder_workspace_bytes",
     "gjx_pointwise_chunks",

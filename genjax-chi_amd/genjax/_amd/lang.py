@@ -390,6 +390,10 @@ class GenerativeFunctionClosure:
     def _call_args(self):
         return self.gen_fn.canonical_args(self.args, self.kwargs)
 
+    def repeat(self, /, *, n: int):
+        """`gen_fn(*args).repeat(n=G)`: the closure of `gen_fn.repeat(n=G)` over the same arguments — G i.i.d. copies."""
+        return GenerativeFunctionClosure(self.gen_fn.repeat(n=n), self._call_args(), {})  # (the inner function's canonical arguments)
+
     def __call__(self, key, *more):
         return self.gen_fn.simulate(key, self._call_args()).get_retval()
 

@@ -599,8 +599,12 @@ class Ops:
         self.lib.require("temper", "gjx_temper_plan_create")
         plated = any(s.observed == abi.SITE_PLATED for s in sites)
         counts = any(s.dist in abi.COUNT_DISTS for s in sites)  # (include/gjx_counts.h: only such a table goes to its creator)
-        creator = "gjx_temper_plan_create_counts" if counts else "gjx_temper_plan_create_plated" if plated else "gjx_temper_plan_create"
-        if counts:
+        grouped = sum(s.observed == abi.SITE_GROUPED for s in sites)  # (include/gjx_group.h: likewise)
+        creator = ("gjx_temper_plan_create_grouped" if grouped else "gjx_temper_plan_create_counts" if counts else
+                   "gjx_temper_plan_create_plated" if plated else "gjx_temper_plan_create")
+        if grouped:
+            self.lib.require("group", creator)
+        elif counts:
             self.lib.require("counts", creator)
         elif plated:
             self.lib.require("plate", creator)
@@ -610,6 +614,7 @@ class Ops:
         plan = TemperPlan(self, handle, int(self.lib.call("gjx_temper_plan_n_latents", handle)))
         plan.plated = plated
         plan.n_plated = sum(s.observed == abi.SITE_PLATED for s in sites)
+        plan.n_grouped = grouped
         plan._keep = keep  # device tables and programs the sites point into
         return plan
 
@@ -632,14 +637,60 @@ class Ops:
         return self._temper_move("temper_move_cov", self._chk(factor, torch.float32, L * (L + 1) // 2, "factor"), plan, key, x, lp, ll,
                                  beta, n_moves, None, ancestors, recompute, input_cols, want_accept, max_workgroups)
 
+    def temper_move_grouped(self, plan: "TemperPlan", key, x: list, z, lp, ll, beta: float, n_moves: int, scales=None, z_scales=None, *,
+                            ancestors=None, recompute: bool = False, init_key=None, want_accept: bool = True, max_workgroups: int = 0):
+        """gjx_temper_move_grouped (include/gjx_group.h): ONE launch — temper_move for a plan with grouped latents.  `z`: the S
+        grouped columns, float32 [G, n] each (None with `init_key`: drawn from the grouped sites' priors under that key);
+        `z_scales`: float32 [S, G] on the device (or S tensors [G]) — handed over as pointers, no host read.
+        -> (x [L columns], z [S tensors [G, n]], lp, ll, n_accept int32[n] or None, n_accept_z int32[n] or None)."""
+        self.lib.require("group", "gjx_temper_move_grouped")
+        what, S, G, n = "temper_move_grouped", plan.n_grouped, plan.n_groups, x[0].numel()
+        if not S or not G:
+            raise ValueError(f"{what}: a plan with grouped sites and set_groups() expected")
+        if (z is None) == (init_key is None):
+            raise ValueError(f"{what}: z (the grouped columns) or init_key (draw them), not both")
+        io = abi.GroupIO()
+        block, acc, keep = self._temper_fill(io.t, what, plan, key, x, lp, ll, beta, n_moves, scales, ancestors, recompute, (), want_accept,
+                                             max_workgroups)
+        z_out = torch.empty((S, G, n), dtype=torch.float32, device=self._alloc_device)
+        for s in range(S):
+            if z is not None:
+                io.z_in[s] = self._chk(z[s], torch.float32, G * n, f"z[{s}]").value
+            io.z_out[s] = z_out[s].data_ptr()
+            if z_scales is not None:
+                io.z_scales[s] = self._chk(z_scales[s], torch.float32, G, f"z_scales[{s}]").value
+        if init_key is not None:
+            if init_key.impl != key.impl:
+                raise ValueError(f"{what}: key and init_key of one generator expected")
+            io.init, io.init_key[0], io.init_key[1], io.init_key_lane = 1, init_key.k0, init_key.k1, init_key.lane
+        accz = self.empty(n, torch.int32) if want_accept else None
+        if accz is not None:
+            io.n_accept_z = accz.data_ptr()
+        self.lib.call("gjx_temper_move_grouped", plan.handle, C.byref(io), self.stream())
+        L = plan.n_latents
+        return list(block[:L]), list(z_out.unbind(0)), block[L], block[L + 1], acc, accz
+
     def _temper_move(self, what, factor, plan, key, x, lp, ll, beta, n_moves, scales, ancestors, recompute, input_cols, want_accept,
                      max_workgroups):
+        io = abi.TemperIO()
+        block, acc, keep = self._temper_fill(io, what, plan, key, x, lp, ll, beta, n_moves, scales, ancestors, recompute, input_cols,
+                                             want_accept, max_workgroups)
+        L = plan.n_latents
+        if factor is None:
+            self.lib.call("gjx_temper_move", plan.handle, C.byref(io), self.stream())
+        else:
+            self.lib.call("gjx_temper_move_cov", plan.handle, C.byref(io), factor, self.stream())
+        return list(block[:L]), block[L], block[L + 1], acc
+
+    def _temper_fill(self, io, what, plan, key, x, lp, ll, beta, n_moves, scales, ancestors, recompute, input_cols, want_accept,
+                     max_workgroups):
+        """Fills the gjx_temper_io `io` of one move launch -> (the output block: L latent columns, lp, ll; the accept column or
+        None; the host arrays `io` points into: keep them alive over the call)."""
         import numpy as np
 
         L, n = plan.n_latents, x[0].numel()
         if len(x) != L:
             raise ValueError(f"{what}: the plan has {L} latents, got {len(x)} columns")
-        io = abi.TemperIO()
         io.impl, io.n_moves, io.recompute, io.beta, io.n = key.impl, int(n_moves), 1 if recompute else 0, float(beta), n
         io.key[0], io.key[1], io.key_lane = key.k0, key.k1, key.lane
         block = self.empty_columns(n, [torch.float32] * (L + 2))
@@ -665,11 +716,7 @@ class Ops:
         if acc is not None:
             io.n_accept = acc.data_ptr()
         io.max_workgroups = int(max_workgroups)
-        if factor is None:
-            self.lib.call("gjx_temper_move", plan.handle, C.byref(io), self.stream())
-        else:
-            self.lib.call("gjx_temper_move_cov", plan.handle, C.byref(io), factor, self.stream())
-        return list(block[:L]), block[L], block[L + 1], acc
+        return block, acc, (sc, ins)
 
     def temper_moments_workspace(self, n: int, n_latents: int) -> torch.Tensor:
         """A zeroed workspace of gjx_temper_moments for populations of n with n_latents columns (its ticket stays zero from
@@ -1234,6 +1281,8 @@ class TemperPlan(PlanHandle):
     def __init__(self, ops: "Ops", handle, n_latents: int):
         self.ops, self.handle, self.n_latents = ops, handle, n_latents
         self.n_rows = 0  # rows of the last set_data (include/gjx_plate.h)
+        self.n_grouped = 0  # grouped sites (include/gjx_group.h)
+        self.n_groups = 0  # G of the last set_groups
 
     def set_params(self, values) -> "TemperPlan":
         import numpy as np
@@ -1254,6 +1303,16 @@ class TemperPlan(PlanHandle):
         self.ops.lib.call("gjx_temper_plan_set_data", self.handle, ptrs, len(cols), n_rows)
         self._data = list(cols)
         self.n_rows = n_rows
+        return self
+
+    def set_groups(self, offsets: torch.Tensor) -> "TemperPlan":
+        """gjx_temper_plan_set_groups (include/gjx_group.h): `offsets` int32 [G + 1] on the device — group g owns the data rows
+        offsets[g] .. offsets[g + 1] - 1 — BORROWED by the library (the plan keeps it alive)."""
+        self.ops.lib.require("group", "gjx_temper_plan_set_groups")
+        G = offsets.numel() - 1
+        self.ops.lib.call("gjx_temper_plan_set_groups", self.handle, self.ops._chk(offsets, torch.int32, G + 1, "offsets"), G)
+        self._offsets = offsets
+        self.n_groups = G
         return self
 
     def pointwise_compile_check(self) -> int:

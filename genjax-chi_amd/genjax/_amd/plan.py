@@ -190,7 +190,7 @@ class SymExpr:
             raise PlanUnsupported("expression too long for a plan argument")
         depth = deepest = 0
         for op, _, _ in prog:
-            depth += 1 if op <= abi.EXPR_OBS or op == abi.EXPR_DATA else (0 if op in abi.EXPR_UNARY else (-2 if op == abi.EXPR_SELECT else -1))
+            depth += 1 if op <= abi.EXPR_OBS or op in (abi.EXPR_DATA, abi.EXPR_GROUP) else (0 if op in abi.EXPR_UNARY else (-2 if op == abi.EXPR_SELECT else -1))
             deepest = max(deepest, depth)
         if deepest > abi.MAX_EXPR_DEPTH:
             raise PlanUnsupported("expression too deep for a plan argument")

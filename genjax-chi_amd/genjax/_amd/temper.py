@@ -24,6 +24,35 @@ from .runtime import get_ops
 LADDER = 32  # candidates per ladder launch
 
 
+class _GroupVal:
+    """The traced value of a GROUPED site (include/gjx_group.h): G components.  It supports exactly one operation, indexing by
+    the group tensor — a 1-D integer tensor of the plate length, the group of every data row: `a[g]` is the component of
+    the row's group, a program leaf (abi.EXPR_GROUP) of a plated site's arguments."""
+
+    def __init__(self, tracer, ref: int, addr):
+        self.tracer, self.ref, self.addr = tracer, ref, addr
+
+    def __getitem__(self, idx):
+        if not (isinstance(idx, torch.Tensor) and idx.dim() == 1 and idx.numel() >= 2 and not idx.is_floating_point()
+                and not idx.is_complex() and idx.dtype != torch.bool):
+            raise PlanUnsupported(f"TemperedSMC: the grouped latent at address {self.addr!r} can only be indexed by a 1-D integer "
+                                  "tensor of the plate length (the group of every data row)")
+        self.tracer.group_tensor(idx, self.addr)
+        return SymExpr(self.tracer, [(abi.EXPR_GROUP, self.ref, 0.0)])
+
+    def _no(self, *a, **k):
+        raise PlanUnsupported(f"TemperedSMC: the grouped latent at address {self.addr!r} supports indexing by the group tensor "
+                              "only (a[g] inside a plated site)")
+
+    __add__ = __radd__ = __sub__ = __rsub__ = __mul__ = __rmul__ = __truediv__ = __rtruediv__ = __neg__ = __pow__ = _no
+    __lt__ = __le__ = __gt__ = __ge__ = __iter__ = __len__ = __float__ = __bool__ = _no
+    exp = log = sqrt = abs = sum = mean = _no
+
+    @classmethod
+    def __torch_function__(cls, func, types, args=(), kwargs=None):
+        next(a for a in args if isinstance(a, _GroupVal))._no()
+
+
 class _TemperTracer(PlanTracer):
     """PlanTracer that names the address of whatever a tempered plan cannot hold.
 
@@ -42,6 +71,11 @@ class _TemperTracer(PlanTracer):
         # float32 of the float64 lgamma(k + 1) — data, not arithmetic.  lf_cols: that column -> the observed one
         self.lf_cols: dict = {}
         self._count_keys: dict = {}
+        # GROUPED sites (include/gjx_group.h): the group tensor (one per plan: NOT a data column), its identity, G
+        self.group = None
+        self._group_key = None
+        self.n_groups = None
+        self.n_grouped = 0
 
     def data_col(self, t: torch.Tensor) -> int:
         # (identity is the memory: the body sees its tensor arguments as SpecTensor views of the caller's)
@@ -73,6 +107,78 @@ class _TemperTracer(PlanTracer):
             self.data.append(self.log_factorial(obs, addr))
             self.lf_cols[c + 1] = c
         return c
+
+    def group_tensor(self, t: torch.Tensor, addr):
+        """Registers the tensor the grouped values are indexed by: one per plan (identity is memory plus version, as data_col's)."""
+        key = (t.data_ptr(), t.numel(), t.stride(0), t.dtype, str(t.device), t._version)
+        if self._group_key is None:
+            self.group, self._group_key = t, key
+            self.group_offsets(addr)  # (validated here, and again at every run)
+        elif key != self._group_key:
+            raise PlanUnsupported(f"TemperedSMC: the grouped latent at address {addr!r} is indexed by another group tensor than "
+                                  "the one before it (one group tensor per plan)")
+        if self.data_rows is not None and self.data_rows != t.numel():
+            raise PlanUnsupported(f"TemperedSMC: the group tensor of the grouped latent at address {addr!r} has {t.numel()} entries, "
+                                  f"the plate {self.data_rows} rows")
+
+    def group_offsets(self, addr=None) -> torch.Tensor:
+        """The group tensor as it is NOW -> offsets int32 [G + 1] (host): group k owns the rows offsets[k] .. offsets[k + 1] - 1.
+        Refused unless non-decreasing with values in 0 .. G - 1; empty groups are legal."""
+        if addr is None:
+            addr = next(m["addr"] for m in self.meta if m.get("grouped"))
+        g = self.group.detach().to(device="cpu", dtype=torch.int64)
+        G = self.n_groups
+        if int(g.min()) < 0 or int(g.max()) >= G:
+            raise PlanUnsupported(f"TemperedSMC: the group tensor of the grouped latent at address {addr!r} has values outside 0 .. {G - 1}")
+        if bool((g[1:] < g[:-1]).any()):
+            raise PlanUnsupported(f"TemperedSMC: the group tensor of the grouped latent at address {addr!r} is not sorted (the rows of "
+                                  "a group must be contiguous: non-decreasing group indices)")
+        off = torch.zeros(G + 1, dtype=torch.int64)
+        off[1:] = torch.cumsum(torch.bincount(g, minlength=G), dim=0)
+        return off.to(torch.int32)
+
+    @staticmethod
+    def _reads_group(v) -> bool:
+        return isinstance(v, SymExpr) and any(op == abi.EXPR_GROUP for op, _, _ in v.prog)
+
+    def _grouped(self, addr, gen_fn, args, obs):
+        """One GROUPED site: `dist(*args).repeat(n=G) @ addr`, latent, G i.i.d. components given the scalar latents."""
+        inner, G = gen_fn.gen_fn, gen_fn.axis_size
+        dist = _DIST_IDS.get(id(inner))
+        if dist is None or dist > abi.DIST_BETA:
+            raise PlanUnsupported(f"TemperedSMC: the grouped site at address {addr!r} must be normal, gamma or beta (a random-walk "
+                                  "move needs a float value)")
+        if obs is not None:
+            raise PlanUnsupported(f"TemperedSMC: the grouped site at address {addr!r} is observed (a grouped site is a latent)")
+        vals = list(args)[:2]
+        for v in vals:
+            if isinstance(v, _GroupVal) or self._reads_group(v):
+                raise PlanUnsupported(f"TemperedSMC: an argument of the grouped site at address {addr!r} reads a grouped latent "
+                                      "(grouped sites that depend on each other are not supported)")
+            if self._data_cols_of(v) or (isinstance(v, torch.Tensor) and v.dim() >= 1 and v.numel() > 1):
+                raise PlanUnsupported(f"TemperedSMC: an argument of the grouped site at address {addr!r} reads data (its components "
+                                      "are i.i.d. given the scalar latents)")
+        if not isinstance(G, int) or not 1 <= G < abi.GROUP_MAX_GROUPS:
+            raise PlanUnsupported(f"TemperedSMC: the grouped site at address {addr!r} has G = {G!r} (1 <= G < 2^24)")
+        if self.n_groups is not None and G != self.n_groups:
+            raise PlanUnsupported(f"TemperedSMC: the grouped site at address {addr!r} has G = {G}, the one before it G = {self.n_groups} "
+                                  "(one G per plan)")
+        if self.n_grouped >= abi.GROUP_MAX_SITES:
+            raise PlanUnsupported(f"TemperedSMC: more than {abi.GROUP_MAX_SITES} grouped sites at address {addr!r}")
+        if len(self.sites) >= abi.MAX_SITES:
+            raise PlanUnsupported(f"TemperedSMC: too many sites at address {addr!r}")
+        self.n_groups = G
+        site = abi.Site()
+        site.dist, site.observed, site.out_col = dist, abi.SITE_GROUPED, -1
+        for k, v in enumerate(vals):
+            site.arg[k] = self._arg(v)
+        self.sites.append(site)
+        self.items.append(("site", len(self.sites) - 1))
+        self.meta.append(dict(addr=addr, gen_fn=gen_fn, args=args, obs=None, out_col=-1, is_int=False, dtype=inner.value_dtype,
+                              path=self.prefix + (addr if isinstance(addr, tuple) else (addr,)), grouped=True))
+        self.record(addr, None)
+        self.n_grouped += 1
+        return _GroupVal(self, self.n_grouped - 1, addr)
 
     def data_columns(self, device) -> list:
         """The columns as float32 device tensors, as they are NOW: read at every run, the log k! columns recomputed."""
@@ -138,6 +244,8 @@ class _TemperTracer(PlanTracer):
     def _arg(self, v) -> abi.Arg:
         if is_data_tensor(v):
             return abi.Arg(abi.ARG_DATA, self.data_col(v), 1.0, 0.0, None)
+        if isinstance(v, SymExpr) and len(v.prog) == 1 and v.prog[0][0] == abi.EXPR_GROUP:  # (`a[g]` itself: the affine operand)
+            return abi.Arg(abi.ARG_GROUP, v.prog[0][1], 1.0, 0.0, None)
         return super()._arg(v)
 
     def _call(self, addr, gen_fn, args):
@@ -167,6 +275,8 @@ class _TemperTracer(PlanTracer):
         obs_col = self.count_cols(obs, addr) if count else self.data_col(obs)
         cols = cols | {obs_col}
         lengths = {int(self.data[c].numel()) for c in cols} | ({self.data_rows} if self.data_rows is not None else set())
+        if self.group is not None:
+            lengths |= {int(self.group.numel())}
         if len(lengths) != 1:
             raise PlanUnsupported(f"TemperedSMC: data columns of different lengths {sorted(lengths)} at address {addr!r} "
                                   "(one plate length per plan)")
@@ -187,12 +297,21 @@ class _TemperTracer(PlanTracer):
         return obs  # (a constrained value may feed later sites: it is data there too)
 
     def handle_trace(self, addr, gen_fn, args):
+        from .combinators import Vmap
         from .lang import Categorical, Distribution
 
+        flat = [x for v in args for x in (v if isinstance(v, tuple) else (v,))]
+        if isinstance(gen_fn, Vmap) and gen_fn.in_axes is None and gen_fn.axis_size is not None and isinstance(gen_fn.gen_fn, Distribution):
+            a = addr if isinstance(addr, tuple) else (addr,)
+            sub = self.constraint.get_submap(*a)
+            return self._grouped(addr, gen_fn, args, None if sub.static_is_empty() and sub.get_value() is None else sub)
+        used = next((v for v in flat if isinstance(v, _GroupVal)), None)
+        if used is not None:
+            raise PlanUnsupported(f"TemperedSMC: the site at address {addr!r} takes the grouped latent at address {used.addr!r} whole; "
+                                  "a grouped value can only be read as a[g] inside a plated site")
         if isinstance(gen_fn, Distribution):
             a = addr if isinstance(addr, tuple) else (addr,)
             obs = self.constraint.get_submap(*a).get_value()
-            flat = [x for v in args for x in (v if isinstance(v, tuple) else (v,))]
             if isinstance(gen_fn, (Poisson, NegativeBinomial)):
                 if obs is None:
                     raise PlanUnsupported(f"TemperedSMC: count-valued latent at address {addr!r} (a random-walk move needs a float value)")
@@ -202,7 +321,7 @@ class _TemperTracer(PlanTracer):
                     return self._observed_count(addr, gen_fn, args, obs)
             # (a categorical's 1-D tensor argument is its logits / probs vector, not data)
             cols = set().union(*[self._data_cols_of(v) for v in flat]) if flat and not isinstance(gen_fn, Categorical) else set()
-            if cols or is_data_tensor(obs):
+            if cols or is_data_tensor(obs) or any(self._reads_group(v) for v in flat):
                 return self._plated(addr, gen_fn, args, obs, cols)
         try:
             out = super().handle_trace(addr, gen_fn, args)
@@ -242,16 +361,24 @@ def lower(target: Target, n: int):
             last = PlanUnsupported(f"TemperedSMC: the body is not plan-able ({type(e).__name__}: {e})")
             continue
         addrs = [m["addr"] for m in tracer.meta]
-        if not any(m["obs"] is None for m in tracer.meta):
-            raise PlanUnsupported(f"TemperedSMC: no latent site among the addresses {addrs!r}")
+        if not any(m["obs"] is None and not m.get("grouped") for m in tracer.meta):
+            raise PlanUnsupported(f"TemperedSMC: no {'scalar ' if tracer.n_grouped else ''}latent site among the addresses {addrs!r}")
+        if tracer.n_grouped and tracer.group is None:
+            at = next(m["addr"] for m in tracer.meta if m.get("grouped"))
+            raise PlanUnsupported(f"TemperedSMC: the grouped latent at address {at!r} is read by no plated site (a[g] in a site observed "
+                                  "over a data column)")
+        if tracer.n_grouped and tracer.data_rows != tracer.group.numel():
+            at = next(m["addr"] for m in tracer.meta if m.get("grouped"))
+            raise PlanUnsupported(f"TemperedSMC: the group tensor of the grouped latent at address {at!r} has {tracer.group.numel()} "
+                                  f"entries, the plate {tracer.data_rows} rows")
         if all(m["obs"] is None for m in tracer.meta):
             raise PlanUnsupported(f"TemperedSMC: no observed site among the addresses {addrs!r}")
         if len(tracer.data) > abi.PLATE_MAX_COLS:  # (columns met after the last plated site)
             raise PlanUnsupported(f"TemperedSMC: {len(tracer.data)} data columns (at most {abi.PLATE_MAX_COLS}) at address {addrs[-1]!r}")
-        n_lat = sum(m["obs"] is None for m in tracer.meta)
+        n_lat = sum(m["obs"] is None and not m.get("grouped") for m in tracer.meta)
         if n_lat > abi.TEMPER_MAX_LATENTS:
             raise PlanUnsupported(f"TemperedSMC: {n_lat} latents (at most {abi.TEMPER_MAX_LATENTS}); the last is at address "
-                                  f"{[m['addr'] for m in tracer.meta if m['obs'] is None][-1]!r}")
+                                  f"{[m['addr'] for m in tracer.meta if m['obs'] is None and not m.get('grouped')][-1]!r}")
         return tracer
     raise last
 
@@ -269,8 +396,8 @@ def prior_table(tracer) -> _PriorTable:
     reference to an earlier site renumbered (no site reads a plated one: its value is data)."""
     new_of, sites, progs, keep = {}, [], {}, list(tracer.keep)
     for q, s in enumerate(tracer.sites):
-        if s.observed == abi.SITE_PLATED or (s.observed and s.dist in abi.COUNT_DISTS):  # (nor an observed count site: the
-            continue                                                                      # importance kernels do not know the ids)
+        if s.observed in (abi.SITE_PLATED, abi.SITE_GROUPED) or (s.observed and s.dist in abi.COUNT_DISTS):  # (nor an observed count
+            continue                                          # site: the importance kernels do not know the ids; nor a grouped one)
         new_of[q] = len(sites)
         c = abi.Site.from_buffer_copy(s)
         for k in range(2):
@@ -358,6 +485,9 @@ class TemperedResult:
         self.log_marginal_likelihood, self.betas, self.ess, self.accept_rate = log_marginal_likelihood, betas, ess, accept_rate
         self.choices, self.lp, self.ll, self.columns = choices, lp, ll, columns
         self.factor, self.n_degenerate = factor, n_degenerate
+        # a plan with grouped latents (include/gjx_group.h): per stage, the accepted group moves over n * n_moves * G; the S
+        # grouped columns f32 [G, n] (also in `choices`, at their addresses).  None otherwise
+        self.accept_rate_groups, self.group_columns = None, None
 
     def __repr__(self):
         return (f"TemperedResult(log_marginal_likelihood={self.log_marginal_likelihood:.6f}, stages={len(self.betas) - 1}, "
@@ -587,11 +717,39 @@ class TemperedSMC(SMCAlgorithm):
         if self.proposal == "covariance":
             ops.lib.require("temper_cov", "gjx_temper_move_cov")
         tracer = lower(self.target, self.n_particles)
-        latents = [m for m in tracer.meta if m["obs"] is None]
+        latents = [m for m in tracer.meta if m["obs"] is None and not m.get("grouped")]
+        if tracer.n_grouped:
+            ops.lib.require("group", "gjx_temper_move_grouped")
+            if self.proposal == "covariance":
+                self._refuse_grouped(tracer, 'proposal="covariance"')
         tplan = ops.temper_plan_create(tracer.sites, keep=(tracer.keep, tracer))
         prior = prior_table(tracer) if tracer.data or any(s.dist in abi.COUNT_DISTS for s in tracer.sites) else None
         st = self._st = dict(ops=ops, tracer=tracer, latents=latents, tplan=tplan, ws=None, prior=prior, ws_cov=None)
         return st
+
+    @staticmethod
+    def _refuse_grouped(tracer, what: str):
+        m = next(m for m in tracer.meta if m.get("grouped"))
+        raise PlanUnsupported(f"TemperedSMC: {what} is not supported with the grouped latent at address {m['addr']!r} "
+                              "(include/gjx_group.h: the grouped move is the diagonal random walk of run())")
+
+    GROUP_SCALE_BYTES = 256 << 20  # the float64 working block of group_scales
+
+    @staticmethod
+    def group_scales(z: list, lw: torch.Tensor) -> torch.Tensor:
+        """2.38 / sqrt(S) times the weighted standard deviation of every component z[s][g][:] of the S grouped columns
+        (float32 [G, n] each): float64 on the device, rounded to float32 -> f32 [S, G], still on the device."""
+        w = torch.softmax(lw.double(), dim=0)
+        # a block of groups at a time: the float64 temporaries stay at GROUP_SCALE_BYTES whatever G is (a [G, n] float64
+        # copy of one site is 8 GB at G = 1000, n = 1e6); the weighted sums are matrix-vector products
+        rows = max(1, TemperedSMC.GROUP_SCALE_BYTES // (8 * max(1, lw.numel())))
+        out = torch.empty(len(z), z[0].shape[0], dtype=torch.float64, device=lw.device)
+        for s, col in enumerate(z):
+            for g0 in range(0, col.shape[0], rows):
+                c = col[g0:g0 + rows].double()
+                c -= (c @ w)[:, None]
+                out[s, g0:g0 + rows] = c.square_() @ w
+        return (2.38 / math.sqrt(len(z)) * torch.sqrt(out)).to(torch.float32).contiguous()
 
     def _scales(self, st):
         L = len(st["latents"])
@@ -634,7 +792,13 @@ class TemperedSMC(SMCAlgorithm):
         vals = ops.importance_run(plan, prng.split_lazy(prng.fold_in(key, 0), n), n, [], dtypes, want_score=False,
                                   want_max_partials=False)[0]
         x = [vals[m["out_col"]] for m in st["latents"]]
-        x, lp, ll, _ = ops.temper_move(tplan, key, x, None, None, 0.0, 0, None, recompute=True, want_accept=False)
+        grouped, z, accepts_z = tracer.n_grouped > 0, None, []
+        if grouped:  # the offsets from the group tensor as it is now; the grouped columns from their priors at the scalars drawn
+            tplan.set_groups(tracer.group_offsets().to(ops.device()))
+            x, z, lp, ll, _, _ = ops.temper_move_grouped(tplan, key, x, None, None, None, 0.0, 0, recompute=True,
+                                                         init_key=prng.fold_in(key, 0x7ffffffe), want_accept=False)
+        else:
+            x, lp, ll, _ = ops.temper_move(tplan, key, x, None, None, 0.0, 0, None, recompute=True, want_accept=False)
         if st["ws"] is None:
             st["ws"] = ops.temper_ladder_workspace(n)
         ws = st["ws"]
@@ -672,7 +836,12 @@ class TemperedSMC(SMCAlgorithm):
                 sc = fixed_scales
                 if sc is None and K > 0:
                     sc = self.population_scales(x, lw).cpu().numpy()  # (one host read)
-                x, lp, ll, acc = ops.temper_move(tplan, prng.fold_in(ks, 1), x, lp, ll, nb, K, sc, ancestors=anc)
+                if grouped:  # (the grouped scales never leave the device)
+                    zsc = self.group_scales(z, lw) if K > 0 else None
+                    x, z, lp, ll, acc, accz = ops.temper_move_grouped(tplan, prng.fold_in(ks, 1), x, z, lp, ll, nb, K, sc, zsc, ancestors=anc)
+                    accepts_z.append(accz.sum())
+                else:
+                    x, lp, ll, acc = ops.temper_move(tplan, prng.fold_in(ks, 1), x, lp, ll, nb, K, sc, ancestors=anc)
             pairs.append((e_s, q_s))
             accepts.append(acc.sum())
             beta = nb
@@ -683,8 +852,9 @@ class TemperedSMC(SMCAlgorithm):
         if cov:  # (the stages' degenerate counts ride along with the accept counts)
             tail = torch.cat([torch.stack(accepts).to(torch.int64), torch.cat(degenerate).to(torch.int64)]).cpu().numpy()
             acc_all, degenerate = tail[:len(accepts)], [int(v) for v in tail[len(accepts):]]
-        else:
-            acc_all = torch.stack(accepts).cpu().numpy()
+        else:  # (a grouped plan's group accept counts ride along)
+            acc_all = torch.stack(accepts + accepts_z).to(torch.int64).cpu().numpy()
+            acc_all, accz_all = acc_all[:len(accepts)], acc_all[len(accepts):]
         log_z = 0.0
         for e_s, q_s in zip(e_all, q_all):
             if q_s <= 0:
@@ -694,6 +864,14 @@ class TemperedSMC(SMCAlgorithm):
         if self.betas is not None:
             ess = [float(ess_of(o[0], o[1])) for o in torch.stack(ess).cpu().numpy()]
         rate = [float(a) / (n * K) if K else 0.0 for a in acc_all]
+        if grouped:  # in table order: the scalar columns f32 [n], the grouped ones f32 [G, n]
+            xs, zs = iter(x), iter(z)
+            pairs_ = [(m["addr"], next(zs) if m.get("grouped") else next(xs)) for m in tracer.meta if m["obs"] is None]
+            res = TemperedResult(float(log_z), betas, ess, rate, ChoiceMap.from_mapping(pairs_), lp, ll, x)
+            G = tracer.n_groups
+            res.accept_rate_groups = [float(a) / (n * K * G) if K else 0.0 for a in accz_all]
+            res.group_columns = z
+            return res
         choices = ChoiceMap.from_mapping([(m["addr"], c) for m, c in zip(st["latents"], x)])
         if not cov:
             return TemperedResult(float(log_z), betas, ess, rate, choices, lp, ll, x)
@@ -706,6 +884,8 @@ class TemperedSMC(SMCAlgorithm):
     def run_smc(self, key) -> ParticleCollection:
         """The final population as a ParticleCollection: traces through `Target.importance` with the latent columns as
         constraints, every log-weight f32(log Z-hat), so that logsumexp - log n reproduces the estimate."""
+        if self._state()["tracer"].n_grouped:
+            self._refuse_grouped(self._state()["tracer"], "run_smc")
         if self._state()["tracer"].data:
             m = next(m for m in self._state()["tracer"].meta if m.get("plated"))
             raise PlanUnsupported(f"TemperedSMC.run_smc: the plated site at address {m['addr']!r} has no per-site trace; use run() "
@@ -726,6 +906,8 @@ class TemperedSMC(SMCAlgorithm):
         (same structure: its kernels come out of the JIT cache)."""
         st = self._state()
         ops = st["ops"]
+        if st["tracer"].n_grouped:
+            self._refuse_grouped(st["tracer"], what)
         cols = list(res.columns) if isinstance(res, TemperedResult) else list(res)
         fitted = [m["addr"] for m in st["latents"]]
         if target is None:
@@ -824,6 +1006,8 @@ class TemperedSMC(SMCAlgorithm):
         `draw_stride=k` also returns the draws of particles 0, k, 2 k, ...; `n_draws=m` is draw_stride = ceil(n / m): at most m
         of them, spread over the population (after resampling, neighbours are copies of one ancestor)."""
         st = self._state()
+        if st["tracer"].n_grouped:
+            self._refuse_grouped(st["tracer"], "predictive")
         st["ops"].lib.require("predictive", "gjx_temper_predictive")
         if target is not None and args is not None:
             raise ValueError("TemperedSMC.predictive: target= (held-out rows) or args= (new inputs, nothing observed), not both")
