@@ -1949,6 +1949,30 @@ struct GroupArgs {
   uint32_t init;
 };
 typedef const __attribute__((address_space(4))) int32_t* GroupOff;
+// The grouped columns of the check kernels over a grouped plan (include/gjx_group_checks.h; gjx_plan_jit.hpp GenPointwise,
+// GenPsis and GenPredictive in their grouped mode): one more by-value kernel argument, after PlateData.  z[s] is the [G][n]
+// column of grouped site s (n: the argument block's own), read at g(d) * n + i with a 64-bit index; nothing is written.
+struct GroupCols {
+  const float* z[kGroupMaxSites];
+  const int32_t* off;  // [G + 1]
+  uint32_t G;
+};
+// g(d) of include/gjx_group_checks.h: the number of g' in 1 .. G-1 with off[g'] <= d — for non-decreasing offsets the group
+// that owns row d (empty groups are skipped: the LAST g' whose first row is at or before d).  A bounded binary search: at
+// most 24 steps (G < 2^24), it reads off[1 .. G-1] alone and returns a value in 0 .. G-1 whatever the words are.  With a
+// wave-uniform d (the PSIS kernel's rows) every read is a scalar load; with a row per lane (pointwise, predictive) the lanes
+// of a wave walk nearly the same path, the rows being sorted by group.
+#if defined(__HIP_DEVICE_COMPILE__)
+GJX_DEV uint32_t group_of_row(GroupOff off, uint32_t G, uint32_t d) {
+  uint32_t lo = 0u, hi = G - 1u;
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo + 1u) >> 1);  // lo < mid <= hi
+    if (off[mid] <= (int32_t)d) lo = mid;
+    else hi = mid - 1u;
+  }
+  return lo;
+}
+#endif
 
 // Kernel argument block of the pointwise launch over a plated plan (include/gjx_pointwise.h; the kernel is generated from the
 // site table, gjx_plan_jit.hpp GenPointwise; the fold below is fixed).  The workspace holds five float64 planes [W][n_rows]:

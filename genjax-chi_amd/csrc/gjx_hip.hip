@@ -21,6 +21,7 @@
 #include "../../include/gjx_temper_cov.h"
 #include "../../include/gjx_counts.h"
 #include "../../include/gjx_group.h"
+#include "../../include/gjx_group_checks.h"
 // The library's own kernels keep the Philox round's plain XOR chain (gjx_device.hpp xor3): with v_bitop3_b32 the one-filter
 // LGSSM step measured 0.5 % slower (8.96e10 against 9.01e10 particle-steps/s, three alternating runs each, parent's range
 // 0.1 %), while the generated kernels, which include the header on their own, gain 6 % (importance) and 12 % (LGSSM scan);
@@ -4928,8 +4929,10 @@ int gjx_backmove_run(gjx_backsim_plan* p, const gjx_backmove_io* io, void* ws, s
 // (include/gjx_temper_cov.h), the pointwise kernel (include/gjx_pointwise.h: one source, whatever the generator), the
 // predictive kernel (include/gjx_predictive.h) and the PSIS kernel (include/gjx_psis.h: one source too).  The last three exist
 // for a plan that passes pointwise_plan_ok only (kTemperKernels below has what else they differ in).
-// A plan with GROUPED sites (include/gjx_group.h) has ONE kernel, the grouped move, and none of the five.
-enum TemperKernel { kTemperMove, kTemperCovMove, kTemperPointwise, kTemperPredictive, kTemperPsis, kTemperGroupedMove, kTemperKernelCount };
+// A plan with GROUPED sites (include/gjx_group.h) has none of the five: it has the grouped move and the three check kernels
+// of include/gjx_group_checks.h — the pointwise, predictive and PSIS generators in their grouped mode.
+enum TemperKernel { kTemperMove, kTemperCovMove, kTemperPointwise, kTemperPredictive, kTemperPsis, kTemperGroupedMove,
+                    kTemperGroupedPointwise, kTemperGroupedPredictive, kTemperGroupedPsis, kTemperKernelCount };
 struct gjx_temper_plan {
   int n_sites, n_latents;
   int n_params;   // values set by gjx_temper_plan_set_params
@@ -4960,42 +4963,50 @@ struct gjx_temper_plan {
 namespace {
 constexpr unsigned kTemperMaxGrid = 256 * 16;  // workgroups of 256 particles, grid-stride beyond
 
-// What the five generated kernels of a tempered plan (TemperKernel) differ in on the host side.
+// What the generated kernels of a tempered plan (TemperKernel) differ in on the host side.
 struct TemperKernelDesc {
   const char* entry;
   gjx_jit::PlanKind kind;
   bool per_impl;     // a source and a slot per generator
   bool plated_only;  // refused (GJX_ERR_INVALID) without a PLATED site or with a per-particle input column
+  bool grouped;      // a kernel of plans WITH grouped sites (and of no other); the rest are kernels of plans without
 };
-constexpr TemperKernelDesc kTemperKernels[kTemperKernelCount] = {{"gjx_temper_move_kernel", gjx_jit::PlanKind::temper, true, false},
-                                                {"gjx_temper_move_cov_kernel", gjx_jit::PlanKind::temper, true, false},
-                                                {"gjx_pointwise_kernel", gjx_jit::PlanKind::temper, false, true},
-                                                {"gjx_predictive_kernel", gjx_jit::PlanKind::predictive, true, true},
-                                                {"gjx_psis_kernel", gjx_jit::PlanKind::psis, false, true},
-                                                {"gjx_temper_move_grouped_kernel", gjx_jit::PlanKind::temper, true, false}};
+constexpr TemperKernelDesc kTemperKernels[kTemperKernelCount] = {{"gjx_temper_move_kernel", gjx_jit::PlanKind::temper, true, false, false},
+                                                {"gjx_temper_move_cov_kernel", gjx_jit::PlanKind::temper, true, false, false},
+                                                {"gjx_pointwise_kernel", gjx_jit::PlanKind::temper, false, true, false},
+                                                {"gjx_predictive_kernel", gjx_jit::PlanKind::predictive, true, true, false},
+                                                {"gjx_psis_kernel", gjx_jit::PlanKind::psis, false, true, false},
+                                                {"gjx_temper_move_grouped_kernel", gjx_jit::PlanKind::temper, true, false, true},
+                                                {"gjx_pointwise_grouped_kernel", gjx_jit::PlanKind::temper, false, true, true},
+                                                {"gjx_predictive_grouped_kernel", gjx_jit::PlanKind::predictive, true, true, true},
+                                                {"gjx_psis_grouped_kernel", gjx_jit::PlanKind::psis, false, true, true}};
 // Has the plan a pointwise (and a predictive, and a PSIS) source?  A PLATED site, and no per-particle input column anywhere in the table
 // (the io structs have none).
 bool pointwise_plan_ok(const gjx_temper_plan* p) { return p && p->plated && p->max_input < 0 && p->n_grouped == 0; }
+// ... and the check kernels of include/gjx_group_checks.h?  A grouped plan (its creator has seen to a group-reading PLATED
+// site and to no input column).
+bool grouped_checks_plan_ok(const gjx_temper_plan* p) { return p && p->plated && p->max_input < 0 && p->n_grouped > 0; }
 // the guard of the exported *_source / *_compile_check functions of kernel k
 bool temper_kernel_ok(const gjx_temper_plan* p, TemperKernel k, int impl) {
   const TemperKernelDesc& d = kTemperKernels[k];
-  return p && (p->n_grouped > 0) == (k == kTemperGroupedMove) && (!d.plated_only || pointwise_plan_ok(p)) && (!d.per_impl || impl == 0 || impl == 1);
+  return p && (p->n_grouped > 0) == d.grouped && (!d.plated_only || (d.grouped ? grouped_checks_plan_ok(p) : pointwise_plan_ok(p))) &&
+         (!d.per_impl || impl == 0 || impl == 1);
 }
 std::string temper_source(const gjx_temper_plan* p, TemperKernel k, int impl, PlanTables* tabs = nullptr) {
   auto run = [&](auto& g) {
     g.sites = p->sites; g.n_sites = p->n_sites;
     return gjx_jit::generated_source(g, tabs);
   };
-  if (k == kTemperPointwise) {
+  if (k == kTemperPointwise || k == kTemperGroupedPointwise) {  // (the generators take their grouped mode from the table)
     gjx_jit::GenPointwise<CSite, CArg> g;
     return run(g);
   }
-  if (k == kTemperPredictive) {
+  if (k == kTemperPredictive || k == kTemperGroupedPredictive) {
     gjx_jit::GenPredictive<CSite, CArg> g;
     g.impl = impl;
     return run(g);
   }
-  if (k == kTemperPsis) {
+  if (k == kTemperPsis || k == kTemperGroupedPsis) {
     gjx_jit::GenPsis<CSite, CArg> g;
     return run(g);
   }
@@ -5689,12 +5700,25 @@ uint32_t plated_chunks(uint64_t n, uint64_t n_rows, uint64_t tile, uint64_t targ
 // UNSUPPORTED, JIT, then kernel k of the plan (`c`) and the common fields of its argument block A (PointwiseArgs /
 // PredictiveArgs / PsisArgs: x, n, W, per) over the grid of `tile` rows x chunks.  `ok`: the entry point's own conditions
 // (checked with the common ones: GJX_ERR_INVALID); `need(W, D)`: the workspace bytes of the entry point.
+// include/gjx_group_checks.h (kTemperKernels[k].grouped): `z` are the grouped columns, checked here and handed on as `gc`, the
+// kernel's last argument; the flat kernels take z == nullptr and leave gc alone.
 template <class Args, class IO, class Need>
 int plated_prepare(gjx_temper_plan* p, TemperKernel k, int impl, const IO* io, bool ok, uint64_t tile, uint64_t target, Need need, Args& A,
-                   gjx_jit::CompiledKernel** c) {
-  if (!pointwise_plan_ok(p) || !io || !ok || !p->has_data || io->n < 1 || io->n >= (1ull << 31) || !io->out || p->n_params <= p->max_param ||
-      ((uintptr_t)io->ws & 7) != 0)
+                   gjx_jit::CompiledKernel** c, const gjx_group_cols* z = nullptr, GroupCols* gc = nullptr) {
+  const bool grouped = kTemperKernels[k].grouped;
+  if (!(grouped ? grouped_checks_plan_ok(p) : pointwise_plan_ok(p)) || !io || !ok || !p->has_data || io->n < 1 || io->n >= (1ull << 31) || !io->out ||
+      p->n_params <= p->max_param || ((uintptr_t)io->ws & 7) != 0)
     return GJX_ERR_INVALID;
+  if (grouped) {
+    if (!z || !gc || !p->group_off) return GJX_ERR_INVALID;
+    memset(gc, 0, sizeof *gc);
+    for (int g = 0; g < p->n_grouped; ++g) {
+      if (!z->z[g]) return GJX_ERR_INVALID;
+      gc->z[g] = z->z[g];
+    }
+    gc->off = p->group_off;
+    gc->G = p->n_groups;
+  }
   memset(&A, 0, sizeof A);
   for (int l = 0; l < p->n_latents; ++l) {
     if (!io->x[l]) return GJX_ERR_INVALID;
@@ -5714,10 +5738,11 @@ int plated_prepare(gjx_temper_plan* p, TemperKernel k, int impl, const IO* io, b
 // of `planes` float64 planes of [W][n_rows] (A.part), `fill` adds the entry point's own fields to A.
 template <class Args, class IO, class Fill>
 int plated_launch(gjx_temper_plan* p, TemperKernel k, int impl, const IO* io, bool ok, uint64_t tile, uint64_t target, size_t planes,
-                  gjx_stream s, Args& A, Fill fill) {
+                  gjx_stream s, Args& A, Fill fill, const gjx_group_cols* z = nullptr) {
   gjx_jit::CompiledKernel* c = nullptr;
+  GroupCols gc = {};
   if (int rc = plated_prepare(p, k, impl, io, ok, tile, target,
-                              [&](uint32_t W, uint32_t D) { return (size_t)W * (size_t)D * planes * sizeof(double); }, A, &c))
+                              [&](uint32_t W, uint32_t D) { return (size_t)W * (size_t)D * planes * sizeof(double); }, A, &c, z, &gc))
     return rc;
   const uint32_t D = p->data.n_rows, W = A.W;
   A.part = static_cast<double*>(io->ws);
@@ -5725,7 +5750,7 @@ int plated_launch(gjx_temper_plan* p, TemperKernel k, int impl, const IO* io, bo
   PlanParams prm = p->prm;
   PlanTables tabs = c->tabs;
   PlateData pd = p->data;
-  void* args[] = {&A, &prm, &tabs, &pd};
+  void* args[] = {&A, &prm, &tabs, &pd, &gc};  // (a flat kernel takes the first four)
   return launch_generated(c->fn, (D + tile - 1) / tile, W, kBlock, s, args);
 }
 }  // namespace
@@ -5828,13 +5853,21 @@ int gjx_pointwise_source(const gjx_temper_plan* p, char* buf, size_t buf_len, si
   return temper_source_out(p, kTemperPointwise, 0, buf, buf_len, needed);
 }
 int gjx_pointwise_compile_check(const gjx_temper_plan* p) { return temper_compile_check(p, kTemperPointwise, 0); }
-int gjx_temper_pointwise(gjx_temper_plan* p, const gjx_pointwise_io* io, gjx_stream s) {
+}  // extern "C"
+namespace {
+// gjx_temper_pointwise (z == nullptr) and gjx_temper_pointwise_grouped (include/gjx_group_checks.h)
+int temper_pointwise(gjx_temper_plan* p, const gjx_pointwise_io* io, const gjx_group_cols* z, bool grouped, gjx_stream s) {
   PointwiseArgs A;
-  if (int rc = plated_launch(p, kTemperPointwise, 0, io, true, kBlock, kPointwiseWorkgroups, 5, s, A, [](PointwiseArgs&) {})) return rc;
+  if (int rc = plated_launch(p, grouped ? kTemperGroupedPointwise : kTemperPointwise, 0, io, true, kBlock, kPointwiseWorkgroups, 5, s, A,
+                             [](PointwiseArgs&) {}, z))
+    return rc;
   const uint32_t D = p->data.n_rows;
   k_pointwise_fold<<<(unsigned)nrows_of(D), kBlock, 0, S(s)>>>(A.part, A.W, D, io->out);
   return launch_status();
 }
+}  // namespace
+extern "C" {
+int gjx_temper_pointwise(gjx_temper_plan* p, const gjx_pointwise_io* io, gjx_stream s) { return temper_pointwise(p, io, nullptr, false, s); }
 
 int gjx_predictive_version(int* major, int* minor) {
   return version_out(major, minor, GJX_PREDICTIVE_VERSION_MAJOR, GJX_PREDICTIVE_VERSION_MINOR);
@@ -5848,23 +5881,31 @@ int gjx_predictive_source(const gjx_temper_plan* p, int impl, char* buf, size_t 
   return temper_source_out(p, kTemperPredictive, impl, buf, buf_len, needed);
 }
 int gjx_predictive_compile_check(const gjx_temper_plan* p, int impl) { return temper_compile_check(p, kTemperPredictive, impl); }
-int gjx_temper_predictive(gjx_temper_plan* p, const gjx_keys* key, const gjx_predictive_io* io, gjx_stream s) {
+}  // extern "C"
+namespace {
+// gjx_temper_predictive (z == nullptr) and gjx_temper_predictive_grouped (include/gjx_group_checks.h)
+int temper_predictive(gjx_temper_plan* p, const gjx_keys* key, const gjx_predictive_io* io, const gjx_group_cols* z, bool grouped, gjx_stream s) {
   // (ONE literal key: its fold_in children are the particles' pass keys; a batch or a stream fold has no meaning here)
   const bool ok = io && keys_ok(key) && key->mode == 2 && !key->has_fold && !(io->draw_stride > 0 && !io->draws);
-  const int n_plated = pointwise_plan_ok(p) ? predictive_n_plated(p) : 0;
+  const int n_plated = (grouped ? grouped_checks_plan_ok(p) : pointwise_plan_ok(p)) ? predictive_n_plated(p) : 0;
   PredictiveArgs A;
-  const int rc = plated_launch(p, kTemperPredictive, ok ? key->impl : 0, io, ok, kPredictiveTile, kPredictiveWorkgroups, (size_t)n_plated * 5, s, A,
-                               [&](PredictiveArgs& a) {
+  const int rc = plated_launch(p, grouped ? kTemperGroupedPredictive : kTemperPredictive, ok ? key->impl : 0, io, ok, kPredictiveTile,
+                               kPredictiveWorkgroups, (size_t)n_plated * 5, s, A, [&](PredictiveArgs& a) {
     a.key = Key{key->parent[0], key->parent[1], (uint32_t)key->parent_lane, (uint32_t)(key->parent_lane >> 32)};
     // (a stride of n or more stores particle 0 alone, as the stride n does: the kernel's counter stays below 2^32)
     a.stride = (uint32_t)(io->draw_stride < io->n ? io->draw_stride : io->n);
     a.m = a.stride ? (uint32_t)((io->n + a.stride - 1) / a.stride) : 0u;
     a.draws = a.stride ? io->draws : nullptr;
-  });
+  }, z);
   if (rc) return rc;
   const uint32_t D = p->data.n_rows;
   k_predictive_fold<<<dim3((unsigned)nrows_of(D), (unsigned)n_plated), kBlock, 0, S(s)>>>(A.part, A.W, D, io->out);
   return launch_status();
+}
+}  // namespace
+extern "C" {
+int gjx_temper_predictive(gjx_temper_plan* p, const gjx_keys* key, const gjx_predictive_io* io, gjx_stream s) {
+  return temper_predictive(p, key, io, nullptr, false, s);
 }
 
 int gjx_psis_version(int* major, int* minor) { return version_out(major, minor, GJX_PSIS_VERSION_MAJOR, GJX_PSIS_VERSION_MINOR); }
@@ -5887,12 +5928,16 @@ int gjx_psis_source(const gjx_temper_plan* p, char* buf, size_t buf_len, size_t*
   return temper_source_out(p, kTemperPsis, 0, buf, buf_len, needed);
 }
 int gjx_psis_compile_check(const gjx_temper_plan* p) { return temper_compile_check(p, kTemperPsis, 0); }
-int gjx_temper_psis(gjx_temper_plan* p, const gjx_psis_io* io, gjx_stream s) {
+}  // extern "C"
+namespace {
+// gjx_temper_psis (z == nullptr) and gjx_temper_psis_grouped (include/gjx_group_checks.h)
+int temper_psis(gjx_temper_plan* p, const gjx_psis_io* io, const gjx_group_cols* z, bool grouped, gjx_stream s) {
   const bool ok = io && io->tail_len >= 5 && io->tail_len <= GJX_PSIS_MAX_TAIL && io->tail_len < io->n;
   PsisArgs A;
   gjx_jit::CompiledKernel* c = nullptr;
-  if (int rc = plated_prepare(p, kTemperPsis, 0, io, ok, kPsisRows, kPsisWorkgroups,
-                              [&](uint32_t, uint32_t D) { return gjx_psis_workspace_bytes(io->n, D, io->tail_len); }, A, &c))
+  GroupCols gc = {};
+  if (int rc = plated_prepare(p, grouped ? kTemperGroupedPsis : kTemperPsis, 0, io, ok, kPsisRows, kPsisWorkgroups,
+                              [&](uint32_t, uint32_t D) { return gjx_psis_workspace_bytes(io->n, D, io->tail_len); }, A, &c, z, &gc))
     return rc;
   const uint32_t D = p->data.n_rows;
   Carver cv{(char*)io->ws, io->ws_bytes};
@@ -5908,7 +5953,7 @@ int gjx_temper_psis(gjx_temper_plan* p, const gjx_psis_io* io, gjx_stream s) {
   PlanParams prm = p->prm;
   PlanTables tabs = c->tabs;
   PlateData pd = p->data;
-  void* args[] = {&A, &prm, &tabs, &pd};
+  void* args[] = {&A, &prm, &tabs, &pd, &gc};  // (the flat kernel takes the first four)
   const unsigned blocks = (D + kPsisRows - 1) / kPsisRows;
   for (uint32_t mode = 0; mode < 4; ++mode) {
     A.mode = mode;
@@ -5919,6 +5964,42 @@ int gjx_temper_psis(gjx_temper_plan* p, const gjx_psis_io* io, gjx_stream s) {
   }
   k_psis_finish<<<D, kBlock, 0, S(s)>>>(A, D, io->out, io->tail);
   return launch_status();
+}
+}  // namespace
+extern "C" {
+int gjx_temper_psis(gjx_temper_plan* p, const gjx_psis_io* io, gjx_stream s) { return temper_psis(p, io, nullptr, false, s); }
+
+// ---- include/gjx_group_checks.h: the three calls over a plan with grouped latents ---------------------------------------
+int gjx_group_checks_version(int* major, int* minor) {
+  return version_out(major, minor, GJX_GROUP_CHECKS_VERSION_MAJOR, GJX_GROUP_CHECKS_VERSION_MINOR);
+}
+int gjx_temper_pointwise_grouped(gjx_temper_plan* p, const gjx_pointwise_io* io, const gjx_group_cols* z, gjx_stream s) {
+  return temper_pointwise(p, io, z, true, s);
+}
+int gjx_temper_psis_grouped(gjx_temper_plan* p, const gjx_psis_io* io, const gjx_group_cols* z, gjx_stream s) {
+  return temper_psis(p, io, z, true, s);
+}
+int gjx_temper_predictive_grouped(gjx_temper_plan* p, const gjx_keys* key, const gjx_predictive_io* io, const gjx_group_cols* z, gjx_stream s) {
+  return temper_predictive(p, key, io, z, true, s);
+}
+}  // extern "C"
+namespace {
+bool group_checks_kernel(int kernel, TemperKernel* k) {
+  if (kernel < 0 || kernel > 2) return false;
+  *k = kernel == 0 ? kTemperGroupedPointwise : kernel == 1 ? kTemperGroupedPsis : kTemperGroupedPredictive;
+  return true;
+}
+}  // namespace
+extern "C" {
+int gjx_group_checks_source(const gjx_temper_plan* p, int kernel, int impl, char* buf, size_t buf_len, size_t* needed) {
+  TemperKernel k;
+  if (!group_checks_kernel(kernel, &k)) return GJX_ERR_INVALID;
+  return temper_source_out(p, k, kernel == 2 ? impl : 0, buf, buf_len, needed);
+}
+int gjx_group_checks_compile_check(const gjx_temper_plan* p, int kernel, int impl) {
+  TemperKernel k;
+  if (!group_checks_kernel(kernel, &k)) return GJX_ERR_INVALID;
+  return temper_compile_check(p, k, kernel == 2 ? impl : 0);
 }
 
 }  // extern "C"

@@ -1633,6 +1633,14 @@ struct TemperTable {
       for (const char* s : sfx) t += pre + std::to_string(c) + s;
     return t;
   }
+  // pre<s>sfx for every grouped site s and every lane suffix: the values gz_<s> of the row's group (SiteEmitter's names of a
+  // GROUP operand under the suffixes) as parameters or arguments; empty for a table without grouped sites
+  std::string group_list(const std::string& pre, std::initializer_list<const char*> sfx) const {
+    std::string t;
+    for (int s = 0; s < (int)grouped.size(); ++s)
+      for (const char* x : sfx) t += pre + std::to_string(s) + x;
+    return t;
+  }
   // The numbering of the draws of a `drawn` table, as a ScopeInfo of one scope.  It numbers the PLATED sites alone, in table
   // order — include/gjx_predictive.h defines the draws as an importance pass over a table of just those sites — so site q
   // carries the count of plated sites before it: fold_t, THREEFRY's 1-based counter of that table's sites; fold_p, PHILOX's
@@ -2042,6 +2050,18 @@ struct GenTemperGrouped {
   }
 };
 
+// The GROUPED mode of the three check generators (include/gjx_group_checks.h), taken exactly when the table holds a grouped
+// site — the text of a table without one is what it was before the mode existed, byte for byte.  The row term also depends
+// on z[s][g(d)][i]: the kernels are named gjx_*_grouped_kernel and take one more argument (GroupCols gc), the term functions
+// take gz_<s> (SiteEmitter's name of a GROUP operand) between the latents and the data values, and g(d) is found once per
+// row by group_of_row (gjx_device.hpp), before the particle loop.  What differs per kernel is the orientation of the z loads:
+//   pointwise   a lane is a row: per block of kPointwiseBlock particles four dword loads of z[s][g(d) * n + i ..] per grouped
+//               site (4-byte alignment is all n guarantees); the lanes of a group read one address — rows are sorted by group;
+//   PSIS        a lane is a particle, the workgroup's four rows are wave-uniform: their groups are found on the scalar side
+//               and lane i reads z[s][g(row) * n + i], coalesced, once per round;
+//   predictive  a lane owns two rows: gA and gB once, pd_particle takes gz_<s>A and gz_<s>B; the samplers are untouched.
+// No LDS beyond the PSIS histogram, no barrier added, no scratch; the source holds neither G nor n.
+
 // The pointwise kernel of a plated tempered plan (include/gjx_pointwise.h): the TRANSPOSED loop of emit_plated.  The move
 // kernel puts particles on lanes and reads data rows through the scalar cache; the reduction here runs over the particles,
 // so lanes are ROWS and particles are wave-uniform:
@@ -2060,7 +2080,7 @@ struct GenTemperGrouped {
 template <class CSiteT, class CArgT>
 inline void emit_row_term(std::ostringstream& o, const TemperTable<CSiteT, CArgT>& t, const CSiteT* sites, int n_sites, const char* name = "pw_term") {
   o << "__device__ __forceinline__ float " << name << "(const PlanParams& prm, const PlanTables& tabs" << t.list(", float nx_")
-    << t.data_list(", float dc", {""}) << ") {\n";
+    << t.group_list(", float gz_", {""}) << t.data_list(", float dc", {""}) << ") {\n";
   o << "  (void)prm; (void)tabs;\n";
   SiteEmitter<CSiteT, CArgT> e{o, 0, 0, t.tab.data(), n_sites, "  ", ""};
   e.exact_cuts = false;
@@ -2085,16 +2105,27 @@ struct GenPointwise {
     constexpr int NB = gjx::kPointwiseBlock;
     emit_prelude(o);
     const TemperTable<CSiteT, CArgT> t(sites, n_sites);
+    const int S = (int)t.grouped.size();  // the grouped mode (see above): nothing below emits a character without it
     const std::string dcs = t.data_list(", dc", {""});
     emit_row_term(o, t, sites, n_sites);
-    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_pointwise_kernel(PointwiseArgs a, PlanParams prm, PlanTables tabs, PlateData pd) {\n";
+    o << "extern \"C\" __global__ __launch_bounds__(256) void " << (S ? "gjx_pointwise_grouped_kernel" : "gjx_pointwise_kernel")
+      << "(PointwiseArgs a, PlanParams prm, PlanTables tabs, PlateData pd" << (S ? ", GroupCols gc" : "") << ") {\n";
     o << "  const uint32_t d = blockIdx.x * 256u + threadIdx.x;\n  if (d >= pd.n_rows) return;\n";
     for (int c : t.cs) o << "  const float dc" << c << " = pd.col[" << c << "][d];\n";
-    std::string block = "    const float t[" + std::to_string(NB) + "] = {";
-    for (int j = 0; j < NB; ++j) block += std::string(j ? ", " : "") + "pw_term(prm, tabs" + t.list(", x", "_" + std::to_string(j)) + dcs + ")";
+    if (S) o << "  const size_t zb = (size_t)group_of_row((GroupOff)gc.off, gc.G, d) * a.n;  // (row g(d) of the [G][n] columns)\n";
+    for (int s = 0; s < S; ++s) o << "  const float* zp" << s << " = gc.z[" << s << "] + zb;\n";
+    std::string block;
+    for (int s = 0; s < S; ++s)  // (four dword loads: g(d) * n + i is 4-byte aligned and no more)
+      for (int j = 0; j < NB; ++j)
+        block += "    const float gz" + std::to_string(s) + "_" + std::to_string(j) + " = zp" + std::to_string(s) + "[(size_t)i + " + std::to_string(j) + "u];\n";
+    block += "    const float t[" + std::to_string(NB) + "] = {";
+    for (int j = 0; j < NB; ++j)
+      block += std::string(j ? ", " : "") + "pw_term(prm, tabs" + t.list(", x", "_" + std::to_string(j)) + t.group_list(", gz", {("_" + std::to_string(j)).c_str()}) + dcs + ")";
     block += "};\n    pointwise_take<" + std::to_string(NB) + ">(q, t);\n";
+    std::string zrest;
+    for (int s = 0; s < S; ++s) zrest += ", zp" + std::to_string(s) + "[i]";
     emit_particle_loop(o, t, NB, "  PointwiseAcc q = pointwise_start();\n", block,
-                       " {\n    const float t[1] = {pw_term(prm, tabs" + t.list(", xc", "[i]") + dcs + ")};\n    pointwise_take<1>(q, t);\n  }\n",
+                       " {\n    const float t[1] = {pw_term(prm, tabs" + t.list(", xc", "[i]") + zrest + dcs + ")};\n    pointwise_take<1>(q, t);\n  }\n",
                        "  pointwise_store(a, pd.n_rows, blockIdx.y, d, q);\n}\n");
     return o.str();
   }
@@ -2124,7 +2155,9 @@ struct GenPsis {
     emit_prelude(o);
     const TemperTable<CSiteT, CArgT> t(sites, n_sites);
     emit_row_term(o, t, sites, n_sites, "ps_term");
-    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_psis_kernel(PsisArgs a, PlanParams prm, PlanTables tabs, PlateData pd) {\n";
+    const int S = (int)t.grouped.size();  // the grouped mode
+    o << "extern \"C\" __global__ __launch_bounds__(256) void " << (S ? "gjx_psis_grouped_kernel" : "gjx_psis_kernel")
+      << "(PsisArgs a, PlanParams prm, PlanTables tabs, PlateData pd" << (S ? ", GroupCols gc" : "") << ") {\n";
     o << "  __shared__ double shd[kPsisRows * kPsisBins / 2];\n  uint32_t* sh = reinterpret_cast<uint32_t*>(shd);\n";
     o << "  const uint32_t r0 = blockIdx.x * (uint32_t)kPsisRows;\n";
     for (int c : t.cs) o << "  const PlateCol pc" << c << " = (PlateCol)pd.col[" << c << "];\n";
@@ -2134,6 +2167,8 @@ struct GenPsis {
       o << "  const uint32_t d" << J << " = on" << J << " ? r0 + " << J << "u : pd.n_rows - 1u;\n";
       for (int c : t.cs) o << "  const float dc" << c << "_" << J << " = pc" << c << "[d" << J << "];\n";
       o << "  const uint32_t key" << J << " = psis_row_key(a, d" << J << ");\n  const float tT" << J << " = psis_unkey(key" << J << ");\n";
+      // (d<J> is wave-uniform: the search runs on the scalar side)
+      if (S) o << "  const size_t zb" << J << " = (size_t)group_of_row((GroupOff)gc.off, gc.G, d" << J << ") * a.n;\n";
     }
     o << "  double g[kPsisRows] = {};\n  uint32_t bad[kPsisRows] = {};\n";
     o << "  const uint64_t lo64 = (uint64_t)blockIdx.y * a.per;\n";
@@ -2143,10 +2178,12 @@ struct GenPsis {
     o << "  for (uint32_t i0 = lo; i0 < hi; i0 += 256u) {\n";
     o << "    const bool live = hi - i0 > threadIdx.x;\n    const uint32_t i = live ? i0 + threadIdx.x : hi - 1u;\n";
     for (int l = 0; l < t.L; ++l) o << "    const float x" << l << " = a.x[" << l << "][i];\n";
+    for (int s = 0; s < S; ++s)
+      for (int j = 0; j < R; ++j) o << "    const float gz" << s << "_" << j << " = gc.z[" << s << "][zb" << j << " + i];\n";
     for (int j = 0; j < R; ++j) {
       const std::string J = std::to_string(j);
       o << "    psis_take(a, sh + " << J << " * kPsisBins, d" << J << ", key" << J << ", tT" << J << ", live && on" << J << ", ps_term(prm, tabs"
-        << t.list(", x") << t.data_list(", dc", {("_" + J).c_str()}) << "), g[" << J << "], bad[" << J << "]);\n";
+        << t.list(", x") << t.group_list(", gz", {("_" + J).c_str()}) << t.data_list(", dc", {("_" + J).c_str()}) << "), g[" << J << "], bad[" << J << "]);\n";
     }
     o << "  }\n  psis_flush(a, sh, pd.n_rows, r0, g, bad);\n}\n";
     return o.str();
@@ -2188,10 +2225,11 @@ struct GenPredictive {
     bool skip[GJX_MAX_SITES] = {};  // the sites that draw nothing: emitted here by head(), skipped by the pair emitter
     for (int q = 0; q < n_sites; ++q) skip[q] = t.tab[q].observed != 0;
     const int S = (int)plated.size();
+    const int Z = (int)t.grouped.size();  // the grouped mode
     const std::string SS = std::to_string(S), dcs = t.data_list(", dc", {"A", "B"});
     // particle i at the lane's two rows: the draws of every plated site, into the accumulators and (every stride-th) the table
     o << "__device__ __forceinline__ void pd_particle(const PredictiveArgs& a, const PlanParams& prm, const PlanTables& tabs, PredictiveKeep& kp, "
-         "uint32_t i, uint32_t n_rows, uint32_t dA, bool hasB" << t.list(", float nx_") << t.data_list(", float dc", {"A", "B"}) << ", PredictiveAcc (&qA)[" << SS
+         "uint32_t i, uint32_t n_rows, uint32_t dA, bool hasB" << t.list(", float nx_") << t.group_list(", float gz_", {"A", "B"}) << t.data_list(", float dc", {"A", "B"}) << ", PredictiveAcc (&qA)[" << SS
       << "], PredictiveAcc (&qB)[" << SS << "]) {\n";
     o << "  (void)prm; (void)tabs;\n";
     o << "  const Key pk = predictive_pass_key<" << I << ">(a.key, i);  // (fold_in(a.key, i), wave-uniform: the parent key of this particle's pass over the rows)\n";
@@ -2237,19 +2275,35 @@ struct GenPredictive {
     o << "#pragma unroll\n  for (int s = 0; s < " << SS << "; ++s) {\n    predictive_take(qA[s], yA[s], obA[s]);\n    predictive_take(qB[s], yB[s], obB[s]);\n  }\n";
     o << "  predictive_keep_rows<" << SS << ">(a, kp, i, n_rows, dA, hasB, yA, yB);\n}\n";
 
-    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_predictive_kernel(PredictiveArgs a, PlanParams prm, PlanTables tabs, PlateData pd) {\n";
+    o << "extern \"C\" __global__ __launch_bounds__(256) void " << (Z ? "gjx_predictive_grouped_kernel" : "gjx_predictive_kernel")
+      << "(PredictiveArgs a, PlanParams prm, PlanTables tabs, PlateData pd" << (Z ? ", GroupCols gc" : "") << ") {\n";
     o << "  const uint32_t dA = (blockIdx.x * 256u + threadIdx.x) * 2u;\n  if (dA >= pd.n_rows) return;\n";
     o << "  const bool hasB = dA + 1u < pd.n_rows;\n  const uint32_t dB = hasB ? dA + 1u : dA;  // (an odd row count: row n_rows is never read)\n";
     for (int c : t.cs) o << "  const float dc" << c << "A = pd.col[" << c << "][dA], dc" << c << "B = pd.col[" << c << "][dB];\n";
-    auto particle = [&](const std::string& i, const std::string& xs) {
-      return "pd_particle(a, prm, tabs, kp, " + i + ", pd.n_rows, dA, hasB" + xs + dcs + ", qA, qB);\n";
+    // (the groups of the lane's two rows, found once: rows g(dA), g(dB) of the [G][n] columns)
+    if (Z) o << "  const size_t zbA = (size_t)group_of_row((GroupOff)gc.off, gc.G, dA) * a.n, zbB = (size_t)group_of_row((GroupOff)gc.off, gc.G, dB) * a.n;\n";
+    for (int s = 0; s < Z; ++s) o << "  const float* zp" << s << "A = gc.z[" << s << "] + zbA;\n  const float* zp" << s << "B = gc.z[" << s << "] + zbB;\n";
+    auto particle = [&](const std::string& i, const std::string& xs, const std::string& zs) {
+      return "pd_particle(a, prm, tabs, kp, " + i + ", pd.n_rows, dA, hasB" + xs + zs + dcs + ", qA, qB);\n";
+    };
+    auto zat = [&](const std::string& at) {  // zp<s>A[at], zp<s>B[at] for every grouped site
+      std::string r;
+      for (int s = 0; s < Z; ++s) r += ", zp" + std::to_string(s) + "A[" + at + "], zp" + std::to_string(s) + "B[" + at + "]";
+      return r;
     };
     std::string block;
-    for (int j = 0; j < NB; ++j) block += "    " + particle("i + " + std::to_string(j) + "u", t.list(", x", "_" + std::to_string(j)));
+    for (int s = 0; s < Z; ++s)  // (the block's loads before its arithmetic: four dwords per row and grouped site)
+      for (int j = 0; j < NB; ++j)
+        for (const char* r : {"A", "B"})
+          block += "    const float gz" + std::to_string(s) + r + "_" + std::to_string(j) + " = zp" + std::to_string(s) + r + "[(size_t)i + " + std::to_string(j) + "u];\n";
+    for (int j = 0; j < NB; ++j) {
+      const std::string J = "_" + std::to_string(j);
+      block += "    " + particle("i + " + std::to_string(j) + "u", t.list(", x", J), t.group_list(", gz", {("A" + J).c_str(), ("B" + J).c_str()}));
+    }
     emit_particle_loop(o, t, NB,
                        "  PredictiveAcc qA[" + SS + "], qB[" + SS + "];\n#pragma unroll\n  for (int s = 0; s < " + SS +
                            "; ++s) qA[s] = qB[s] = predictive_start();\n  PredictiveKeep kp = predictive_keep_start(a, lo);\n",
-                       block, " " + particle("i", t.list(", xc", "[i]")),
+                       block, " " + particle("i", t.list(", xc", "[i]"), zat("i")),
                        "#pragma unroll\n  for (int s = 0; s < " + SS + "; ++s) {\n    predictive_store(a, pd.n_rows, (uint32_t)s, blockIdx.y, dA, qA[s]);\n"
                        "    if (hasB) predictive_store(a, pd.n_rows, (uint32_t)s, blockIdx.y, dA + 1u, qB[s]);\n  }\n}\n");
     return o.str();

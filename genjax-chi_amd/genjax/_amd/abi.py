@@ -120,6 +120,10 @@ class GroupUnavailable(HeaderUnavailable):
     header, why = "gjx_group.h", "grouped latents live in the generated tempered move kernel only"
 
 
+class GroupChecksUnavailable(HeaderUnavailable):
+    header, why = "gjx_group_checks.h", "the pointwise, PSIS and predictive kernels of a grouped plan are generated HIP kernels only"
+
+
 class TemperCovUnavailable(HeaderUnavailable):
     header, why = "gjx_temper_cov.h", "the population moments and the covariance move run as HIP kernels only"
 
@@ -839,6 +843,25 @@ GROUP_PROTOTYPES = {
 }
 GROUP_ABI_VERSION = (0, 1)
 
+# include/gjx_group_checks.h: a SIXTEENTH header, same arrangement — pointwise densities, PSIS-LOO and predictive draws of a
+# plan with grouped latents: the io structs of the flat headers plus the grouped columns.  Bound directly after "group".
+
+
+class GroupCols(C.Structure):
+    """gjx_group_cols (include/gjx_group_checks.h)."""
+    _fields_ = [("z", C.c_void_p * GROUP_MAX_SITES)]
+
+
+GROUP_CHECKS_PROTOTYPES = {
+    "gjx_group_checks_version": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gjx_temper_pointwise_grouped": (C.c_int, [_P, C.POINTER(PointwiseIO), C.POINTER(GroupCols), _P]),
+    "gjx_temper_psis_grouped": (C.c_int, [_P, C.POINTER(PsisIO), C.POINTER(GroupCols), _P]),
+    "gjx_temper_predictive_grouped": (C.c_int, [_P, C.POINTER(Keys), C.POINTER(PredictiveIO), C.POINTER(GroupCols), _P]),
+    "gjx_group_checks_source": (C.c_int, [_P, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gjx_group_checks_compile_check": (C.c_int, [_P, C.c_int, C.c_int]),
+}
+GROUP_CHECKS_ABI_VERSION = (0, 1)
+
 # The optional headers, in the order they are bound: every one is exported by libgjx_hip.so only and bound if present.
 class Header(collections.namedtuple("Header", "key header version_fn prototypes version_name unavailable")):
     @property
@@ -864,6 +887,8 @@ PLAN_HEADERS = {h.key: h for h in (
            SmcParamsUnavailable),
     Header("csmc", "gjx_csmc.h", "gjx_csmc_version", CSMC_PROTOTYPES, "CSMC_ABI_VERSION", CsmcUnavailable),
     Header("group", "gjx_group.h", "gjx_group_version", GROUP_PROTOTYPES, "GROUP_ABI_VERSION", GroupUnavailable),
+    Header("group_checks", "gjx_group_checks.h", "gjx_group_checks_version", GROUP_CHECKS_PROTOTYPES, "GROUP_CHECKS_ABI_VERSION",
+           GroupChecksUnavailable),
     Header("temper", "gjx_temper.h", "gjx_temper_version", TEMPER_PROTOTYPES, "TEMPER_ABI_VERSION", TemperUnavailable),
     Header("counts", "gjx_counts.h", "gjx_counts_version", COUNTS_PROTOTYPES, "COUNTS_ABI_VERSION", CountsUnavailable),
     Header("psis", "gjx_psis.h", "gjx_psis_version", PSIS_PROTOTYPES, "PSIS_ABI_VERSION", PsisUnavailable),

@@ -773,15 +773,29 @@ class Ops:
                       int(d.size), self._p(out), self._p(ws), ws.numel(), self.stream())
         return out
 
-    def _plated_io(self, what: str, plan: "TemperPlan", x: list, io, ws_symbol: str, *ws_args):
+    def _plated_io(self, what: str, plan: "TemperPlan", x: list, io, ws_symbol: str, *ws_args, z=None):
         """What temper_pointwise and temper_predictive begin with: the plan is plated and has data, `x` holds its L latent
-        columns (float32[n]) -> io.n, io.x, io.ws of `ws_symbol`(n, D, *ws_args) bytes; returns (n, D, the workspace)."""
+        columns (float32[n]) -> io.n, io.x, io.ws of `ws_symbol`(n, D, *ws_args) bytes; returns (n, D, the workspace, the
+        gjx_group_cols of `z` or None).  `z`: the S grouped columns (float32 [G, n]) of a plan with grouped latents
+        (include/gjx_group_checks.h: the call then goes to gjx_temper_<what>_grouped) — required for such a plan, refused for
+        any other."""
         self.lib.require(what, "gjx_temper_" + what)
         if not getattr(plan, "plated", False) or not plan.n_rows:
             raise ValueError(f"temper_{what}: the plan has no plated site, or no data (TemperPlan.set_data)")
         L, n, D = plan.n_latents, x[0].numel(), plan.n_rows
         if len(x) != L:
             raise ValueError(f"temper_{what}: the plan has {L} latents, got {len(x)} columns")
+        S, cols = getattr(plan, "n_grouped", 0), None
+        if (z is not None) != (S > 0):
+            raise ValueError(f"temper_{what}: z= (the grouped columns) goes with a plan with grouped sites, and only with one")
+        if S:
+            self.lib.require("group_checks", f"gjx_temper_{what}_grouped")
+            G = plan.n_groups
+            if not G or len(z) != S:
+                raise ValueError(f"temper_{what}: {S} grouped columns and set_groups() expected, got {len(z)} columns, G = {G}")
+            cols = abi.GroupCols()
+            for s in range(S):
+                cols.z[s] = self._chk(z[s], torch.float32, G * n, f"z[{s}]").value
         io.n = n
         for l in range(L):
             io.x[l] = self._chk(x[l], torch.float32, n, f"x[{l}]").value
@@ -789,56 +803,68 @@ class Ops:
         # (per call: see workspace(); uninitialised: the first launch writes every entry the fold reads)
         ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=self._alloc_device)
         io.ws, io.ws_bytes = ws.data_ptr(), ws.numel()
-        return n, D, ws
+        return n, D, ws, cols
 
-    def temper_pointwise(self, plan: "TemperPlan", x: list) -> torch.Tensor:
+    def temper_pointwise(self, plan: "TemperPlan", x: list, z=None) -> torch.Tensor:
         """gjx_temper_pointwise (include/gjx_pointwise.h): TWO launches -> float64[4, D] on the device over the plan's data
         rows d — the log-sum-exp over the particles of the per-row log-likelihood t[d, i], its sum, its sum of squares and the
-        count of entries above -inf.  `x`: the L latent columns, float32[n].  Nothing is drawn."""
+        count of entries above -inf.  `x`: the L latent columns, float32[n].  Nothing is drawn.
+        `z`: the grouped columns of a plan with grouped latents, float32 [G, n] each (gjx_temper_pointwise_grouped)."""
         io = abi.PointwiseIO()
-        n, D, ws = self._plated_io("pointwise", plan, x, io, "gjx_pointwise_workspace_bytes")
+        n, D, ws, cols = self._plated_io("pointwise", plan, x, io, "gjx_pointwise_workspace_bytes", z=z)
         out = self.empty(4 * D, torch.float64)
         io.out = out.data_ptr()
-        self.lib.call("gjx_temper_pointwise", plan.handle, C.byref(io), self.stream())
+        if cols is None:
+            self.lib.call("gjx_temper_pointwise", plan.handle, C.byref(io), self.stream())
+        else:
+            self.lib.call("gjx_temper_pointwise_grouped", plan.handle, C.byref(io), C.byref(cols), self.stream())
         return out.view(4, D)
 
-    def temper_psis(self, plan: "TemperPlan", x: list, tail_len: int, want_tail: bool = False):
+    def temper_psis(self, plan: "TemperPlan", x: list, tail_len: int, want_tail: bool = False, z=None):
         """gjx_temper_psis (include/gjx_psis.h): PSIS-LOO of the plan's data rows under the n equally weighted particles of
         the columns `x` (the L latent columns, float32[n]) -> (out float64[7, D]: elpd_loo, khat, sigma, s, tT, B, bad;
         tail float32[D, tail_len + 1], each row's tail_len + 1 smallest entries in ascending order, or None) on the device.
-        `tail_len`: 5 .. 4095 and below n (gjx_psis_tail_len has the package's rule).  Nothing is drawn, nothing read back."""
+        `tail_len`: 5 .. 4095 and below n (gjx_psis_tail_len has the package's rule).  Nothing is drawn, nothing read back.
+        `z`: the grouped columns of a plan with grouped latents, float32 [G, n] each (gjx_temper_psis_grouped)."""
         M = int(tail_len)
         n = x[0].numel() if x else 0
         if not 5 <= M <= abi.PSIS_MAX_TAIL or M >= n:
             raise ValueError(f"temper_psis: tail_len must be in 5 .. {abi.PSIS_MAX_TAIL} and below n = {n}, got {M}")
         io = abi.PsisIO()
-        n, D, ws = self._plated_io("psis", plan, x, io, "gjx_psis_workspace_bytes", M)
+        n, D, ws, cols = self._plated_io("psis", plan, x, io, "gjx_psis_workspace_bytes", M, z=z)
         out = self.empty(7 * D, torch.float64)
         tail = self.empty(D * (M + 1), torch.float32) if want_tail else None
         io.tail_len, io.out = M, out.data_ptr()
         if tail is not None:
             io.tail = tail.data_ptr()
-        self.lib.call("gjx_temper_psis", plan.handle, C.byref(io), self.stream())
+        if cols is None:
+            self.lib.call("gjx_temper_psis", plan.handle, C.byref(io), self.stream())
+        else:
+            self.lib.call("gjx_temper_psis_grouped", plan.handle, C.byref(io), C.byref(cols), self.stream())
         return out.view(7, D), (tail.view(D, M + 1) if tail is not None else None)
 
-    def temper_predictive(self, plan: "TemperPlan", key, x: list, draw_stride: int = 0):
+    def temper_predictive(self, plan: "TemperPlan", key, x: list, draw_stride: int = 0, z=None):
         """gjx_temper_predictive (include/gjx_predictive.h): TWO launches -> (out float64[S, 5, D], draws float32[S, m, D] or
         None) on the device.  Per plated site s and data row d, over the n particles of the columns `x` (the L latent
         columns, float32[n]): the sum and the sum of squares of the replicated value y ~ p(y | x_i, data_d), and the counts
         y < obs_d, y == obs_d, y != y.  `key`: ONE key (a PRNGKey, or its literal batch); particle i draws its pass over the
-        rows under fold_in(key, i).  `draw_stride = k >= 1` also returns the draws of particles 0, k, 2 k, ... (m = ceil(n / k))."""
+        rows under fold_in(key, i).  `draw_stride = k >= 1` also returns the draws of particles 0, k, 2 k, ... (m = ceil(n / k)).
+        `z`: the grouped columns of a plan with grouped latents, float32 [G, n] each (gjx_temper_predictive_grouped)."""
         k = int(draw_stride)
         if k < 0:
             raise ValueError("temper_predictive: draw_stride >= 0")
         kb = key if isinstance(key, KeyBatch) else key.literal()
         io, S = abi.PredictiveIO(), getattr(plan, "n_plated", 0)
-        n, D, ws = self._plated_io("predictive", plan, x, io, "gjx_predictive_workspace_bytes", S)
+        n, D, ws, cols = self._plated_io("predictive", plan, x, io, "gjx_predictive_workspace_bytes", S, z=z)
         out = self.empty(S * 5 * D, torch.float64)
         draws = self.empty(S * (-(-n // k)) * D, torch.float32) if k else None
         io.out, io.draw_stride = out.data_ptr(), k
         if draws is not None:
             io.draws = draws.data_ptr()
-        self.lib.call("gjx_temper_predictive", plan.handle, C.byref(self._keys(kb, 1)), C.byref(io), self.stream())
+        if cols is None:
+            self.lib.call("gjx_temper_predictive", plan.handle, C.byref(self._keys(kb, 1)), C.byref(io), self.stream())
+        else:
+            self.lib.call("gjx_temper_predictive_grouped", plan.handle, C.byref(self._keys(kb, 1)), C.byref(io), C.byref(cols), self.stream())
         return out.view(S, 5, D), (draws.view(S, -1, D) if draws is not None else None)
 
     def smc_config(self, impl, n_total, first, n_local, step_keys, resample_keys, ess_threshold: float = 0.0):
@@ -1314,6 +1340,19 @@ class TemperPlan(PlanHandle):
         self._offsets = offsets
         self.n_groups = G
         return self
+
+    GROUP_CHECK_KERNELS = {"pointwise": 0, "psis": 1, "predictive": 2}
+
+    def group_checks_source(self, kernel: str, impl: int = 0) -> str:
+        """The HIP source of a check kernel of a grouped plan (include/gjx_group_checks.h): kernel "pointwise", "psis" or
+        "predictive"; `impl` is read for "predictive" only."""
+        self.ops.lib.require("group_checks", "gjx_group_checks_source")
+        return self._source("gjx_group_checks_source", self.GROUP_CHECK_KERNELS[kernel], impl)
+
+    def group_checks_compile_check(self, kernel: str, impl: int = 0) -> int:
+        """gjx_group_checks_compile_check: the status, not raised."""
+        self.ops.lib.require("group_checks", "gjx_group_checks_compile_check")
+        return self.ops.lib._gjx_group_checks_compile_check(self.handle, self.GROUP_CHECK_KERNELS[kernel], impl)
 
     def pointwise_compile_check(self) -> int:
         """gjx_pointwise_compile_check (include/gjx_pointwise.h): the status, not raised."""

@@ -24,6 +24,12 @@ from .runtime import get_ops
 LADDER = 32  # candidates per ladder launch
 
 
+class GroupTensorRefused(PlanUnsupported):
+    """The group tensor of a grouped latent — the values it holds NOW — cannot be lowered: unsorted, out of 0 .. G-1, or not
+    of the plate's length.  A PlanUnsupported for `lower()` and `run()`; a held-out target's is reported as a ValueError
+    (TemperedSMC._lower_held_out catches this class, not a message)."""
+
+
 class _GroupVal:
     """The traced value of a GROUPED site (include/gjx_group.h): G components.  It supports exactly one operation, indexing by
     the group tensor — a 1-D integer tensor of the plate length, the group of every data row: `a[g]` is the component of
@@ -118,7 +124,7 @@ class _TemperTracer(PlanTracer):
             raise PlanUnsupported(f"TemperedSMC: the grouped latent at address {addr!r} is indexed by another group tensor than "
                                   "the one before it (one group tensor per plan)")
         if self.data_rows is not None and self.data_rows != t.numel():
-            raise PlanUnsupported(f"TemperedSMC: the group tensor of the grouped latent at address {addr!r} has {t.numel()} entries, "
+            raise GroupTensorRefused(f"TemperedSMC: the group tensor of the grouped latent at address {addr!r} has {t.numel()} entries, "
                                   f"the plate {self.data_rows} rows")
 
     def group_offsets(self, addr=None) -> torch.Tensor:
@@ -129,9 +135,9 @@ class _TemperTracer(PlanTracer):
         g = self.group.detach().to(device="cpu", dtype=torch.int64)
         G = self.n_groups
         if int(g.min()) < 0 or int(g.max()) >= G:
-            raise PlanUnsupported(f"TemperedSMC: the group tensor of the grouped latent at address {addr!r} has values outside 0 .. {G - 1}")
+            raise GroupTensorRefused(f"TemperedSMC: the group tensor of the grouped latent at address {addr!r} has values outside 0 .. {G - 1}")
         if bool((g[1:] < g[:-1]).any()):
-            raise PlanUnsupported(f"TemperedSMC: the group tensor of the grouped latent at address {addr!r} is not sorted (the rows of "
+            raise GroupTensorRefused(f"TemperedSMC: the group tensor of the grouped latent at address {addr!r} is not sorted (the rows of "
                                   "a group must be contiguous: non-decreasing group indices)")
         off = torch.zeros(G + 1, dtype=torch.int64)
         off[1:] = torch.cumsum(torch.bincount(g, minlength=G), dim=0)
@@ -369,7 +375,7 @@ def lower(target: Target, n: int):
                                   "over a data column)")
         if tracer.n_grouped and tracer.data_rows != tracer.group.numel():
             at = next(m["addr"] for m in tracer.meta if m.get("grouped"))
-            raise PlanUnsupported(f"TemperedSMC: the group tensor of the grouped latent at address {at!r} has {tracer.group.numel()} "
+            raise GroupTensorRefused(f"TemperedSMC: the group tensor of the grouped latent at address {at!r} has {tracer.group.numel()} "
                                   f"entries, the plate {tracer.data_rows} rows")
         if all(m["obs"] is None for m in tracer.meta):
             raise PlanUnsupported(f"TemperedSMC: no observed site among the addresses {addrs!r}")
@@ -733,6 +739,47 @@ class TemperedSMC(SMCAlgorithm):
         raise PlanUnsupported(f"TemperedSMC: {what} is not supported with the grouped latent at address {m['addr']!r} "
                               "(include/gjx_group.h: the grouped move is the diagonal random walk of run())")
 
+    # -- a population of a plan with grouped latents (include/gjx_group_checks.h) -----------------------------------------------
+    def _split_population(self, what: str, res):
+        """`res` -> (the L scalar columns, the S grouped columns [G, n] or None) as given, unchecked but for their count.  A plan
+        with grouped latents takes a TemperedResult of a grouped run (`columns` and `group_columns`) or the latent columns in
+        table order as `choices` holds them: scalars [n], grouped [G, n].  The L scalar columns alone are refused, naming the
+        first grouped address: its [G, n] column is missing.  Raised before anything is asked of the library."""
+        st = self._state()
+        tracer = st["tracer"]
+        if not tracer.n_grouped:
+            return (list(res.columns) if isinstance(res, TemperedResult) else list(res)), None
+        lat = [m for m in tracer.meta if m["obs"] is None]  # table order, scalar and grouped
+        first = next(m["addr"] for m in lat if m.get("grouped"))
+        if isinstance(res, TemperedResult):
+            if res.group_columns is None:
+                raise PlanUnsupported(f"TemperedSMC: {what} needs the [G, n] column of the grouped latent at address {first!r}: the "
+                                      "TemperedResult is not one of a run with grouped latents")
+            return list(res.columns), list(res.group_columns)
+        given = list(res)
+        if len(given) == len(st["latents"]):
+            raise PlanUnsupported(f"TemperedSMC: {what} got the {len(given)} scalar latent columns alone; the [G, n] column of the grouped "
+                                  f"latent at address {first!r} is missing (pass the TemperedResult, or the latent columns in table order as "
+                                  "`choices` holds them: scalars [n], grouped [G, n])")
+        if len(given) != len(lat):
+            raise ValueError(f"TemperedSMC.{what}: {len(lat)} latent columns expected ({[m['addr'] for m in lat]!r}), got {len(given)}")
+        return [c for m, c in zip(lat, given) if not m.get("grouped")], [c for m, c in zip(lat, given) if m.get("grouped")]
+
+    def _lower_held_out(self, what: str, target: Target):
+        """The lowering of a held-out target of a grouped plan: its own group tensor must be sorted with values in 0 .. G-1 and
+        the fitted G (ValueError otherwise: a group that was never fitted has no column)."""
+        fitted = self._state()["tracer"]
+        try:
+            tracer = lower(target, self.n_particles)
+        except GroupTensorRefused as e:
+            raise ValueError(f"TemperedSMC.{what}: {e} — the rows' groups must be sorted and among the {fitted.n_groups} fitted "
+                             "groups (a group that was never fitted has no column)") from None
+        if tracer.n_groups != fitted.n_groups:
+            at = next(m["addr"] for m in fitted.meta if m.get("grouped"))
+            raise ValueError(f"TemperedSMC.{what}: the target has G = {tracer.n_groups} groups, the grouped latent at address {at!r} was "
+                             f"fitted with G = {fitted.n_groups}")
+        return tracer
+
     GROUP_SCALE_BYTES = 256 << 20  # the float64 working block of group_scales
 
     @staticmethod
@@ -900,25 +947,33 @@ class TemperedSMC(SMCAlgorithm):
         return out
 
     # -- a population against a plated table: what pointwise() and predictive() share ---------------------------------------------
-    def _population(self, what: str, noun: str, res, target: Target | None):
-        """`res` (a TemperedResult, or the L latent columns) and `target` (None: the fitted one) -> (tracer, the tempered plan
-        with its parameters and data set, the columns as float32 device tensors).  A `target` of its own gets a plan of its own
-        (same structure: its kernels come out of the JIT cache)."""
+    def _population(self, what: str, noun: str, split, target: Target | None):
+        """`split` (_split_population of the caller's population) and `target` (None: the fitted one) -> (tracer, the tempered plan
+        with its parameters, data and groups set, the scalar columns as float32 device tensors, the grouped columns [G, n]
+        likewise or None).  A `target` of its own gets a plan of its own (same structure: its kernels come out of the JIT
+        cache)."""
         st = self._state()
         ops = st["ops"]
-        if st["tracer"].n_grouped:
-            self._refuse_grouped(st["tracer"], what)
-        cols = list(res.columns) if isinstance(res, TemperedResult) else list(res)
+        grouped = st["tracer"].n_grouped > 0
+        cols, zcols = split
         fitted = [m["addr"] for m in st["latents"]]
+        if grouped and len(cols) == len(fitted):  # (before anything is uploaded)
+            n, G = int(cols[0].numel()), st["tracer"].n_groups
+            for m, c in zip([m for m in st["tracer"].meta if m.get("grouped")], zcols):
+                if not isinstance(c, torch.Tensor) or c.dim() != 2 or tuple(c.shape) != (G, n):
+                    shape = tuple(c.shape) if isinstance(c, torch.Tensor) else type(c).__name__
+                    raise ValueError(f"TemperedSMC.{what}: the column of the grouped latent at address {m['addr']!r} must be [G, n] = "
+                                     f"[{G}, {n}] (the fitted G, the population's n), got {shape}")
         if target is None:
             tracer, tplan = st["tracer"], st["tplan"]
         else:
             if not isinstance(target, Target):
                 raise TypeError(f"TemperedSMC.{what}: target must be a Target")
-            tracer = lower(target, self.n_particles)
+            tracer = self._lower_held_out(what, target) if grouped else lower(target, self.n_particles)
             theirs = [m["addr"] for m in tracer.meta if m["obs"] is None]
-            if theirs != fitted:
-                raise ValueError(f"TemperedSMC.{what}: the target's latent addresses {theirs!r} are not the fitted plan's {fitted!r}")
+            ours = [m["addr"] for m in st["tracer"].meta if m["obs"] is None]
+            if theirs != ours:
+                raise ValueError(f"TemperedSMC.{what}: the target's latent addresses {theirs!r} are not the fitted plan's {ours!r}")
             tplan = None
         if not tracer.data:
             raise PlanUnsupported(f"TemperedSMC.{what}: no plated site among the addresses {[m['addr'] for m in tracer.meta]!r} "
@@ -930,18 +985,26 @@ class TemperedSMC(SMCAlgorithm):
         if tracer.params:
             tplan.set_params(tracer.params)
         tplan.set_data(tracer.data_columns(ops.device()))
-        return tracer, tplan, [c.detach().to(device=ops.device(), dtype=torch.float32).contiguous() for c in cols]
+        dev = lambda c: c.detach().to(device=ops.device(), dtype=torch.float32).contiguous()
+        if not grouped:
+            return tracer, tplan, [dev(c) for c in cols], None
+        tplan.set_groups(tracer.group_offsets().to(ops.device()))  # (the group tensor as it is now, next to the data)
+        return tracer, tplan, [dev(c) for c in cols], [dev(c) for c in zcols]
 
     # -- pointwise predictive densities (include/gjx_pointwise.h) ------------------------------------------------
     def pointwise(self, res, target: Target | None = None) -> PointwiseLikelihood:
         """The per-row log-likelihood of the plated site(s) under the population `res` — a TemperedResult of `run`, or the L
         latent columns (float32 [n]) in the plan's latent order — reduced over the particles in two launches.
         `target=None` scores the rows the sampler was fitted to; a `Target` over the same model body with OTHER data
-        tensors scores held-out rows under the same population (same structure: the kernel comes out of the JIT cache)."""
+        tensors scores held-out rows under the same population (same structure: the kernel comes out of the JIT cache).
+        A plan with grouped latents (include/gjx_group_checks.h) takes the TemperedResult of its run, or the latent columns
+        in table order as `choices` holds them (scalars [n], grouped [G, n]); row d is scored at the values of ITS group, and
+        a held-out target brings its own group tensor: sorted, with values in 0 .. G-1, the fitted G."""
         ops = self._state()["ops"]
+        split = self._split_population("pointwise", res)  # (a grouped plan's refusal of scalar columns alone comes first)
         ops.lib.require("pointwise", "gjx_temper_pointwise")
-        _, tplan, x = self._population("pointwise", "pointwise densities", res, target)
-        return PointwiseLikelihood(ops.temper_pointwise(tplan, x), x[0].numel())
+        _, tplan, x, z = self._population("pointwise", "pointwise densities", split, target)
+        return PointwiseLikelihood(ops.temper_pointwise(tplan, x, z=z), x[0].numel())
 
     # -- PSIS-LOO (include/gjx_psis.h; DESIGN.md §4o) ------------------------------------------------------------------------------
     def loo(self, res, r_eff: float = 1.0) -> PSISLOO:
@@ -949,17 +1012,18 @@ class TemperedSMC(SMCAlgorithm):
         `res` — a TemperedResult of `run`, or the L latent columns (float32 [n]) in the plan's latent order: per row elpd_loo
         and the diagnostic k-hat (PSISLOO), and the pointwise densities of the same call.  `r_eff`: the relative efficiency of
         the population; as in the `loo` package it enters the tail length min(0.2 n, 3 sqrt(n / r_eff)) alone (capped at 4095:
-        include/gjx_psis.h)."""
+        include/gjx_psis.h).  A plan with grouped latents: as `pointwise` (rows are left out one at a time, not groups)."""
         ops = self._state()["ops"]
+        split = self._split_population("loo", res)
         ops.lib.require("psis", "gjx_temper_psis")
         ops.lib.require("pointwise", "gjx_temper_pointwise")
-        _, tplan, x = self._population("loo", "leave-one-out densities", res, None)
+        _, tplan, x, z = self._population("loo", "leave-one-out densities", split, None)
         n = int(x[0].numel())
         M = int(ops.lib.call("gjx_psis_tail_len", n, float(r_eff)))
         if M == 0:
             raise ValueError(f"TemperedSMC.loo: a population of n = {n} at r_eff = {r_eff} has no tail to fit (n >= 25 and a positive finite r_eff)")
-        table, _ = ops.temper_psis(tplan, x, M)
-        return PSISLOO(table, PointwiseLikelihood(ops.temper_pointwise(tplan, x), n), n, M)
+        table, _ = ops.temper_psis(tplan, x, M, z=z)
+        return PSISLOO(table, PointwiseLikelihood(ops.temper_pointwise(tplan, x, z=z), n), n, M)
 
     # -- posterior predictive draws (include/gjx_predictive.h; DESIGN.md §4n) ---------------------------------------------------
     def _unobserved_target(self, st, args) -> Target:
@@ -1004,10 +1068,11 @@ class TemperedSMC(SMCAlgorithm):
         tensors replicates held-out rows and places their observed values among the draws; `args=` (the model's arguments,
         new inputs) predicts where nothing is observed — no `pit`.  Same structure: the kernel comes out of the JIT cache.
         `draw_stride=k` also returns the draws of particles 0, k, 2 k, ...; `n_draws=m` is draw_stride = ceil(n / m): at most m
-        of them, spread over the population (after resampling, neighbours are copies of one ancestor)."""
+        of them, spread over the population (after resampling, neighbours are copies of one ancestor).
+        A plan with grouped latents: `res` as `pointwise` takes it; `target=` and `args=` carry the new rows' group tensor,
+        whose groups must be among the fitted ones (a group that was never fitted has no column to draw from)."""
         st = self._state()
-        if st["tracer"].n_grouped:
-            self._refuse_grouped(st["tracer"], "predictive")
+        split = self._split_population("predictive", res)
         st["ops"].lib.require("predictive", "gjx_temper_predictive")
         if target is not None and args is not None:
             raise ValueError("TemperedSMC.predictive: target= (held-out rows) or args= (new inputs, nothing observed), not both")
@@ -1019,10 +1084,10 @@ class TemperedSMC(SMCAlgorithm):
             raise ValueError("TemperedSMC.predictive: draw_stride >= 1")
         if args is not None:
             target = self._unobserved_target(st, args)
-        tracer, tplan, x = self._population("predictive", "replicated data", res, target)
+        tracer, tplan, x, z = self._population("predictive", "replicated data", split, target)
         n = int(x[0].numel())
         k = -(-n // int(n_draws)) if n_draws is not None else int(draw_stride or 0)
-        table, draws = st["ops"].temper_predictive(tplan, key, x, k)
+        table, draws = st["ops"].temper_predictive(tplan, key, x, k, z=z)
         addrs = [m["addr"] for m in tracer.meta if m.get("plated")]
         return PosteriorPredictive(addrs, table, n, draws, k, observed=args is None)
 

@@ -17,6 +17,7 @@
 #include "gjx_temper_cov.h"
 #include "gjx_counts.h"
 #include "gjx_group.h"
+#include "gjx_group_checks.h"
 #include "gjx_device.hpp"
 
 #include <hip/hip_runtime.h>
