@@ -2013,6 +2013,28 @@ struct PsisArgs {
   uint32_t M;                         // tail_len
   uint32_t mode;
 };
+// Kernel argument block of the unit-sum launch of PSIS leave-one-group-out (include/gjx_psis_units.h; the kernel is generated
+// from the site table, gjx_plan_jit.hpp GenPsisUnits): one launch per batch of `Ub` units fills the table the fixed passes
+// below (psis_units_pass) read four times.
+struct PsisUnitArgs {
+  const float* x[kTemperMaxLatents];  // latent columns: one vector load per lane and particle
+  const int32_t* unit_off;            // [U + 1], every word clamped to 0 .. n_rows before use
+  float* table;                       // [Ub][pitch]: T[u0 + ul, i] at ul * pitch + i; the padding i >= n is never written
+  uint32_t* umax;                     // [Ub]: zeroed here, raised to the unit's largest key by pass 0
+  uint32_t n, pitch;                  // particles; n rounded up to a multiple of 4 (16-byte loads of a table row)
+  uint32_t u0;                        // the batch's first unit
+};
+// ... and of the table passes: the PsisArgs of the row kernel over the batch's LOCAL unit indices (hist, state, keys of Ub
+// units; part has the pitch U that k_psis_finish reads it with), plus what the units add.
+constexpr uint32_t kPsisUnitsChunk = 32768;  // particles per chunk of a table pass: the chunk count is a function of n alone
+struct PsisUnitsArgs {
+  PsisArgs a;
+  const float* table;
+  uint32_t* umax;
+  double* epart;   // [W][Ub]: the chunks' partials of the lse sum (pass 1)
+  double* lse;     // the batch's slice of out row 7
+  uint32_t pitch, nu, Ub, U;  // table pitch, units in this batch, units per batch, units in all (the pitch of a.part)
+};
 
 // ---- the fixed device code of the backward-simulation and backward-move kernels ---------------------------------------
 // What the site table decides reaches it as template arguments: the generator, the number of carry components D, and a
@@ -2590,6 +2612,108 @@ GJX_DEV void psis_finish(const PsisArgs& a, uint32_t n_rows, uint32_t d, double*
   if (tid == 0u) {
     const double v[7] = {elpd, khat, sigma, sd, td, B, bad};
     for (int q = 0; q < 7; ++q) out[(size_t)q * n_rows + d] = v[q];
+  }
+}
+
+// ---- the table passes of PSIS leave-one-group-out (include/gjx_psis_units.h) -------------------------------------------------
+// The row kernel's four modes over the cached table T of one batch instead of over terms: a workgroup takes kPsisRows units
+// (blk) x one chunk of kPsisUnitsChunk particles (blockIdx.x = blk * W + chunk: the chunk count can pass a grid's y limit), a
+// lane reads four adjacent entries of each unit per round with one 16-byte load (the chunk's first particle and the pitch
+// are multiples of four, and an entry at or past the chunk's end — the padding included — is loaded but never taken).
+// Entries go through psis_take: histograms, keys, the body sum g and `bad` are the row kernel's.  What the units add:
+//   pass 0   the unit's largest key (a lane maximum, an LDS tree, one integer atomic per workgroup: exact and order-free);
+//   pass 1   e = the lane's float64 sum of (double) exp_f32(f32(t - m)), m the unit's largest entry — the lse partial;
+//   pass 3   the workgroup of chunk 0 adds the W partials of pass 1 in chunk order: lse = (double) m + log(sum).
+// Lane l takes the entries lo + 4 l .. lo + 4 l + 3, then those 1024 further on, in that order; lanes are folded by the fixed
+// binary tree of psis_flush, chunks in index order: a function of n alone.
+GJX_DEV void psis_units_pass(const PsisUnitsArgs& q, uint32_t* sh) {
+  const PsisArgs& a = q.a;
+  const uint32_t blk = blockIdx.x / a.W, chunk = blockIdx.x - blk * a.W, r0 = blk * (uint32_t)kPsisRows, tid = threadIdx.x;
+  const uint64_t lo64 = (uint64_t)chunk * a.per;
+  const uint32_t lo = lo64 < a.n ? (uint32_t)lo64 : a.n;
+  const uint32_t hi = a.n - lo > a.per ? lo + a.per : a.n;
+  bool on[kPsisRows];
+  uint32_t dd[kPsisRows], key[kPsisRows], bad[kPsisRows] = {}, mx[kPsisRows] = {};
+  float tT[kPsisRows], m[kPsisRows];
+  double g[kPsisRows] = {}, e[kPsisRows] = {};
+#pragma unroll
+  for (int j = 0; j < kPsisRows; ++j) {
+    on[j] = r0 + (uint32_t)j < q.nu;
+    dd[j] = on[j] ? r0 + (uint32_t)j : q.nu - 1u;  // (a unit past the batch's last: that one again, switched off)
+    key[j] = psis_row_key(a, dd[j]);
+    tT[j] = psis_unkey(key[j]);
+    m[j] = a.mode == 1u ? psis_unkey(q.umax[dd[j]]) : 0.0f;
+  }
+  if (a.mode == 3u && chunk == 0u && tid < (uint32_t)kPsisRows && r0 + tid < q.nu) {
+    const uint32_t d = r0 + tid;
+    double s = 0.0;
+    for (uint32_t k = 0; k < a.W; ++k) s = s + q.epart[(size_t)k * q.Ub + d];
+    q.lse[d] = (double)psis_unkey(q.umax[d]) + log(s);
+  }
+  psis_begin(a, sh);
+  for (uint32_t i0 = lo; i0 < hi; i0 += 1024u) {
+    const uint32_t i = i0 + 4u * tid;  // (i0 < 2^31, so no wrap; a multiple of four)
+    const bool live = i < hi;
+#pragma unroll
+    for (int j = 0; j < kPsisRows; ++j) {
+      float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (live) {
+        const float4 w = *reinterpret_cast<const float4*>(q.table + (size_t)dd[j] * q.pitch + i);
+        v[0] = w.x; v[1] = w.y; v[2] = w.z; v[3] = w.w;
+      }
+#pragma unroll
+      for (uint32_t c = 0; c < 4u; ++c) {
+        const bool take = on[j] && live && hi - i > c;
+        psis_take(a, sh + j * kPsisBins, dd[j], key[j], tT[j], take, v[c], g[j], bad[j]);
+        if (a.mode == 0u && take) {
+          const uint32_t k = psis_key(v[c]);
+          mx[j] = k > mx[j] ? k : mx[j];
+        }
+        if (a.mode == 1u && take) e[j] = e[j] + (double)pointwise_exp(v[c] - m[j]);
+      }
+    }
+  }
+  __syncthreads();
+  if (a.mode < 3u) {
+    const uint32_t bins = a.mode == 2u ? (uint32_t)kPsisBins / 2u : (uint32_t)kPsisBins;
+#pragma unroll
+    for (int j = 0; j < kPsisRows; ++j) {
+      if (!on[j]) break;
+      for (uint32_t b = tid; b < bins; b += 256u) {
+        const uint32_t v = sh[j * kPsisBins + b];
+        uint32_t* at = a.hist + (size_t)dd[j] * kPsisBins + b;
+        if (a.W == 1u) *at = v;
+        else if (v) atomicAdd(at, v);
+      }
+    }
+    if (a.mode == 2u) return;
+    __syncthreads();  // (the histograms are out: the same LDS folds the lanes' maxima or sums)
+  }
+  double* red = reinterpret_cast<double*>(sh);
+#pragma unroll
+  for (int j = 0; j < kPsisRows; ++j) {
+    if (a.mode == 0u) {
+      sh[tid] = mx[j];
+      __syncthreads();
+      for (uint32_t s = 128u; s > 0u; s >>= 1) {
+        if (tid < s) sh[tid] = sh[tid + s] > sh[tid] ? sh[tid + s] : sh[tid];
+        __syncthreads();
+      }
+      if (on[j] && tid == 0u) atomicMax(&q.umax[dd[j]], sh[0]);
+    } else {
+      red[tid] = a.mode == 1u ? e[j] : g[j];
+      __syncthreads();
+      for (uint32_t s = 128u; s > 0u; s >>= 1) {
+        if (tid < s) red[tid] = red[tid] + red[tid + s];
+        __syncthreads();
+      }
+      if (on[j]) {
+        if (tid == 0u && a.mode == 1u) q.epart[(size_t)chunk * q.Ub + dd[j]] = red[0];
+        if (tid == 0u && a.mode == 3u) a.part[(size_t)chunk * q.U + dd[j]] = red[0];
+        if (a.mode == 3u && bad[j]) atomicAdd(&a.state[4u * (size_t)dd[j] + 3u], bad[j]);
+      }
+    }
+    __syncthreads();
   }
 }
 #endif

@@ -17,6 +17,7 @@
 #include "../../include/gjx_plate.h"
 #include "../../include/gjx_pointwise.h"
 #include "../../include/gjx_psis.h"
+#include "../../include/gjx_psis_units.h"
 #include "../../include/gjx_predictive.h"
 #include "../../include/gjx_temper_cov.h"
 #include "../../include/gjx_counts.h"
@@ -4932,7 +4933,8 @@ int gjx_backmove_run(gjx_backsim_plan* p, const gjx_backmove_io* io, void* ws, s
 // A plan with GROUPED sites (include/gjx_group.h) has none of the five: it has the grouped move and the three check kernels
 // of include/gjx_group_checks.h — the pointwise, predictive and PSIS generators in their grouped mode.
 enum TemperKernel { kTemperMove, kTemperCovMove, kTemperPointwise, kTemperPredictive, kTemperPsis, kTemperGroupedMove,
-                    kTemperGroupedPointwise, kTemperGroupedPredictive, kTemperGroupedPsis, kTemperKernelCount };
+                    kTemperGroupedPointwise, kTemperGroupedPredictive, kTemperGroupedPsis, kTemperPsisUnits, kTemperGroupedPsisUnits,
+                    kTemperKernelCount };  // (the last two: the unit-sum kernel of include/gjx_psis_units.h, flat and grouped)
 struct gjx_temper_plan {
   int n_sites, n_latents;
   int n_params;   // values set by gjx_temper_plan_set_params
@@ -4979,7 +4981,9 @@ constexpr TemperKernelDesc kTemperKernels[kTemperKernelCount] = {{"gjx_temper_mo
                                                 {"gjx_temper_move_grouped_kernel", gjx_jit::PlanKind::temper, true, false, true},
                                                 {"gjx_pointwise_grouped_kernel", gjx_jit::PlanKind::temper, false, true, true},
                                                 {"gjx_predictive_grouped_kernel", gjx_jit::PlanKind::predictive, true, true, true},
-                                                {"gjx_psis_grouped_kernel", gjx_jit::PlanKind::psis, false, true, true}};
+                                                {"gjx_psis_grouped_kernel", gjx_jit::PlanKind::psis, false, true, true},
+                                                {"gjx_psis_units_kernel", gjx_jit::PlanKind::psis, false, true, false},
+                                                {"gjx_psis_units_grouped_kernel", gjx_jit::PlanKind::psis, false, true, true}};
 // Has the plan a pointwise (and a predictive, and a PSIS) source?  A PLATED site, and no per-particle input column anywhere in the table
 // (the io structs have none).
 bool pointwise_plan_ok(const gjx_temper_plan* p) { return p && p->plated && p->max_input < 0 && p->n_grouped == 0; }
@@ -5008,6 +5012,10 @@ std::string temper_source(const gjx_temper_plan* p, TemperKernel k, int impl, Pl
   }
   if (k == kTemperPsis || k == kTemperGroupedPsis) {
     gjx_jit::GenPsis<CSite, CArg> g;
+    return run(g);
+  }
+  if (k == kTemperPsisUnits || k == kTemperGroupedPsisUnits) {
+    gjx_jit::GenPsisUnits<CSite, CArg> g;
     return run(g);
   }
   if (k == kTemperGroupedMove) {
@@ -6002,4 +6010,131 @@ int gjx_group_checks_compile_check(const gjx_temper_plan* p, int kernel, int imp
   return temper_compile_check(p, k, kernel == 2 ? impl : 0);
 }
 
+}  // extern "C"
+
+// ---- include/gjx_psis_units.h: PSIS leave-one-group-out over contiguous row units -------------------------------------------
+namespace {
+// one table pass: kPsisRows units x one chunk per workgroup (gjx_device.hpp psis_units_pass)
+__global__ __launch_bounds__(kBlock) void k_psis_units_pass(PsisUnitsArgs q) {
+#if defined(__HIP_DEVICE_COMPILE__)  // (the header's device-only section)
+  __shared__ double shd[kPsisRows * kPsisBins / 2];
+  psis_units_pass(q, reinterpret_cast<uint32_t*>(shd));
+#endif
+}
+constexpr uint64_t kPsisUnitsMaxBatch = 1u << 20;  // units per batch at most: the grids stay far below their limits
+// Units per batch: the largest multiple of kPsisRows whose table fits table_bytes (0: the default), no more than U rounded up
+// to one; 0 when not even kPsisRows units fit or an argument is out of range.
+uint32_t psis_units_batch(uint64_t n, uint64_t U, size_t table_bytes) {
+  if (n < 1 || n >= (1ull << 31) || U < 1 || U >= (1ull << 31)) return 0;
+  const uint64_t pitch = (n + 3) & ~3ull, bytes = table_bytes ? table_bytes : GJX_PSIS_UNITS_TABLE_BYTES;
+  uint64_t ub = bytes / (pitch * sizeof(float)) / kPsisRows * kPsisRows;
+  const uint64_t all = (U + kPsisRows - 1) / kPsisRows * kPsisRows;
+  ub = ub < all ? ub : all;
+  // (blocks of kPsisRows units x W <= 65536 chunks: at most 2^30 workgroups per pass)
+  const uint64_t by_grid = (1ull << 32) / ((n + kPsisUnitsChunk - 1) / kPsisUnitsChunk) / kPsisRows * kPsisRows;
+  ub = ub < by_grid ? ub : by_grid;
+  return (uint32_t)(ub < kPsisUnitsMaxBatch ? ub : kPsisUnitsMaxBatch);
+}
+// The workspace of gjx_temper_psis_units: the table of one batch (16-byte aligned inside a workspace that is 8-byte aligned),
+// the batch's histograms, states, key buffers, largest keys and lse partials, and the body partials at the pitch U that
+// k_psis_finish reads them with.
+struct PsisUnitsScratch {
+  PsisScratch ps;
+  float* table;
+  uint32_t* umax;
+  double* epart;
+};
+bool psis_units_carve(Carver& cv, uint64_t n, uint64_t U, uint32_t Ub, uint32_t W, uint32_t M, PsisUnitsScratch* sc) {
+  const uint64_t pitch = (n + 3) & ~3ull;
+  float* t = cv.take<float>((size_t)Ub * pitch + 4);
+  sc->table = reinterpret_cast<float*>(((uintptr_t)t + 15) & ~(uintptr_t)15);
+  sc->ps.hist = cv.take<uint32_t>((size_t)Ub * kPsisBins);
+  sc->ps.state = cv.take<uint32_t>((size_t)Ub * 4);
+  sc->ps.keys = cv.take<uint32_t>((size_t)Ub * ((size_t)M + 1));
+  sc->ps.part = cv.take<double>((size_t)W * U + Ub);
+  sc->umax = cv.take<uint32_t>(Ub);
+  sc->epart = cv.take<double>((size_t)W * Ub);
+  return cv.ok;
+}
+uint32_t psis_units_chunks(uint64_t n) { return (uint32_t)((n + kPsisUnitsChunk - 1) / kPsisUnitsChunk); }
+}  // namespace
+extern "C" {
+int gjx_psis_units_version(int* major, int* minor) {
+  return version_out(major, minor, GJX_PSIS_UNITS_VERSION_MAJOR, GJX_PSIS_UNITS_VERSION_MINOR);
+}
+size_t gjx_psis_units_workspace_bytes(uint64_t n, uint64_t U, uint32_t tail_len, size_t table_bytes) {
+  const uint32_t Ub = psis_units_batch(n, U, table_bytes);
+  if (!Ub || tail_len < 5 || tail_len > GJX_PSIS_MAX_TAIL) return 0;
+  Carver cv{nullptr, ~(size_t)0};
+  PsisUnitsScratch sc;
+  (void)psis_units_carve(cv, n, U, Ub, psis_units_chunks(n), tail_len, &sc);
+  return ~(size_t)0 - cv.left;
+}
+int gjx_psis_units_source(const gjx_temper_plan* p, char* buf, size_t buf_len, size_t* needed) {
+  return temper_source_out(p, p && p->n_grouped > 0 ? kTemperGroupedPsisUnits : kTemperPsisUnits, 0, buf, buf_len, needed);
+}
+int gjx_psis_units_compile_check(const gjx_temper_plan* p) {
+  return temper_compile_check(p, p && p->n_grouped > 0 ? kTemperGroupedPsisUnits : kTemperPsisUnits, 0);
+}
+int gjx_temper_psis_units(gjx_temper_plan* p, const gjx_psis_units_io* io, const int32_t* unit_offsets, uint64_t U, const gjx_group_cols* z,
+                          gjx_stream s) {
+  if (!p || !io) return GJX_ERR_INVALID;
+  const bool grouped = p->n_grouped > 0;
+  const gjx_psis_io* pio = &io->psis;
+  const uint32_t Ub = psis_units_batch(pio->n, U, io->table_bytes);
+  const bool ok = pio->tail_len >= 5 && pio->tail_len <= GJX_PSIS_MAX_TAIL && pio->tail_len < pio->n && unit_offsets && Ub && (grouped || !z);
+  PsisUnitsArgs Q;
+  memset(&Q, 0, sizeof Q);
+  gjx_jit::CompiledKernel* c = nullptr;
+  GroupCols gc = {};
+  if (int rc = plated_prepare(p, grouped ? kTemperGroupedPsisUnits : kTemperPsisUnits, 0, pio, ok, kPsisRows, kPsisWorkgroups,
+                              [&](uint32_t, uint32_t) { return gjx_psis_units_workspace_bytes(pio->n, U, pio->tail_len, io->table_bytes); }, Q.a, &c,
+                              z, &gc))
+    return rc;
+  const uint32_t n = (uint32_t)pio->n, M = pio->tail_len, W = psis_units_chunks(n), pitch = (n + 3u) & ~3u;
+  Carver cv{(char*)pio->ws, pio->ws_bytes};
+  PsisUnitsScratch sc;
+  if (!psis_units_carve(cv, n, U, Ub, W, M, &sc)) return GJX_ERR_WORKSPACE;
+  PsisArgs& A = Q.a;  // (x and n are set; the chunks are this header's, not the row kernel's)
+  A.hist = sc.ps.hist; A.state = sc.ps.state; A.keys = sc.ps.keys; A.part = sc.ps.part;
+  A.W = W; A.per = kPsisUnitsChunk; A.M = M;
+  Q.table = sc.table; Q.umax = sc.umax; Q.epart = sc.epart; Q.pitch = pitch; Q.Ub = Ub; Q.U = (uint32_t)U;
+  PsisUnitArgs T;
+  memset(&T, 0, sizeof T);
+  for (int l = 0; l < kTemperMaxLatents; ++l) T.x[l] = A.x[l];
+  T.unit_off = unit_offsets; T.table = sc.table; T.umax = sc.umax; T.n = n; T.pitch = pitch;
+  // (a unit with one chunk stores its histogram; with more the workgroups add to it: zero before the first pass 0, cleared by
+  // psis_select after every pass, so zero again when the next batch begins)
+  if (W > 1 && hipMemsetAsync(sc.ps.hist, 0, (size_t)Ub * kPsisBins * sizeof(uint32_t), S(s)) != hipSuccess) {
+    (void)hipGetLastError();
+    return GJX_ERR_LAUNCH;
+  }
+  PlanParams prm = p->prm;
+  PlanTables tabs = c->tabs;
+  PlateData pd = p->data;
+  void* args[] = {&T, &prm, &tabs, &pd, &gc};  // (the flat kernel takes the first four)
+  const int P = gjx_jit::GenPsisUnits<CSite, CArg>::lane_particles(p->n_latents, p->n_grouped);
+  const uint64_t rounds = (pio->n + (uint64_t)kBlock * P - 1) / ((uint64_t)kBlock * P);
+  const unsigned gy = (unsigned)(rounds < 65535 ? rounds : 65535);
+  for (uint64_t u0 = 0; u0 < U; u0 += Ub) {
+    const uint32_t nu = (uint32_t)(U - u0 < Ub ? U - u0 : Ub);
+    T.u0 = (uint32_t)u0;
+    if (int rc = launch_generated(c->fn, nu, gy, kBlock, s, args)) return rc;
+    Q.nu = nu;
+    Q.lse = pio->out + (size_t)7 * U + u0;
+    A.part = sc.ps.part + u0;  // (k_psis_finish reads part[k * U + d]: the batch's slice of a [W][U] plane)
+    const uint64_t blocks = (uint64_t)((nu + kPsisRows - 1) / kPsisRows) * W;
+    for (uint32_t mode = 0; mode < 4; ++mode) {
+      A.mode = mode;
+      k_psis_units_pass<<<(unsigned)blocks, kBlock, 0, S(s)>>>(Q);
+      if (int rc = launch_status()) return rc;
+      if (mode == 3) break;
+      k_psis_select<<<(nu + kBlock / 64 - 1) / (kBlock / 64), kBlock, 0, S(s)>>>(sc.ps.hist, sc.ps.state, nu, mode, M);
+      if (int rc = launch_status()) return rc;
+    }
+    k_psis_finish<<<nu, kBlock, 0, S(s)>>>(A, (uint32_t)U, pio->out + u0, pio->tail ? pio->tail + (size_t)u0 * (M + 1u) : nullptr);
+    if (int rc = launch_status()) return rc;
+  }
+  return GJX_OK;
+}
 }  // extern "C"

@@ -2190,6 +2190,113 @@ struct GenPsis {
   }
 };
 
+// The unit-sum kernel of PSIS leave-one-group-out (include/gjx_psis_units.h): T[u, i], the float64 sum over the rows of unit u
+// of the PSIS term at particle i, rounded to f32 once, into a table the fixed passes of gjx_device.hpp psis_units_pass read.
+// The row kernel evaluates the term inside each of its four passes; here the term is evaluated ONCE per (row, particle):
+//   * a work item is one unit (blockIdx.x, wave-uniform) x one round of 256 * P particles (blockIdx.y, grid-stride); a lane
+//     keeps P particles in registers — their latents, the values of the current group and one float64 accumulator each — at
+//     the indices i0 + 256 k + lane, so every load and the store are coalesced dwords;
+//   * the unit's rows are walked once for the P particles: us_rows takes single rows up to a row index that is a multiple
+//     of four, then blocks of four rows whose data values arrive in one scalar load per column (the loop of gm_rows), then
+//     the remainder.  Row bounds come from the unit offsets through a constant-address-space pointer, clamped to n_rows;
+//   * grouped mode: g of the unit's first row by group_of_row, once and on the scalar side; then g is advanced while the
+//     next group's first row is at or before d (never past G - 1), the rows up to the next boundary are one call of us_rows,
+//     and the lane's z[s][g * n + i] are reloaded at a boundary only;
+//   * us_term is ps_term under another name: emit_row_term's text.
+// P comes from the register count: a particle costs L + S + 2 VGPRs across the row loop, and 48 of them leave the term its
+// temporaries below 128 VGPRs (four waves per SIMD; DESIGN.md §4r has the counts the compiler reports).
+// No LDS, no barrier, no scratch; the source holds neither n, n_rows, U, G nor a data value.
+template <class CSiteT, class CArgT>
+struct GenPsisUnits {
+  std::ostringstream o;
+  const CSiteT* sites;
+  int n_sites;
+
+  static int lane_particles(int L, int S) {
+    const int p = 48 / (L + S + 2);
+    return p >= 4 ? 4 : p >= 2 ? 2 : 1;
+  }
+
+  std::string run() {
+    emit_prelude(o);
+    const TemperTable<CSiteT, CArgT> t(sites, n_sites);
+    emit_row_term(o, t, sites, n_sites, "us_term");
+    const int L = t.L, S = (int)t.grouped.size(), P = lane_particles(L, S);
+    const std::string PS = std::to_string(P);
+    const std::string state = std::string("const float (&x)[") + std::to_string(L ? L : 1) + "][" + PS + "]" +
+                              (S ? ", const float (&z)[" + std::to_string(S) + "][" + PS + "]" : "") + ", double (&acc)[" + PS + "]";
+    auto at = [&](const char* arr, int n, const std::string& k) {  // , arr[0][k], arr[1][k] ...
+      std::string r;
+      for (int j = 0; j < n; ++j) r += std::string(", ") + arr + "[" + std::to_string(j) + "][" + k + "]";
+      return r;
+    };
+    // one row at the lane's P particles (dc<c>: the row's data values, wave-uniform)
+    o << "__device__ __forceinline__ void us_row(const PlanParams& prm, const PlanTables& tabs, " << state << t.data_list(", float dc", {""}) << ") {\n";
+    o << "#pragma unroll\n  for (int k = 0; k < " << PS << "; ++k) acc[k] = acc[k] + (double)us_term(prm, tabs" << at("x", L, "k") << at("z", S, "k")
+      << t.data_list(", dc", {""}) << ");\n}\n";
+    // the rows lo .. hi - 1 (one group's, in grouped mode)
+    o << "__device__ __forceinline__ void us_rows(const PlanParams& prm, const PlanTables& tabs, const PlateData& pd, uint32_t lo, uint32_t hi, " << state
+      << ") {\n";
+    for (int c : t.cs) o << "  const PlateCol pc" << c << " = (PlateCol)pd.col[" << c << "];\n";
+    auto single = [&](const std::string& cond) {
+      o << "  for (; " << cond << "; ++d) {\n";
+      for (int c : t.cs) o << "    const float r" << c << " = pc" << c << "[d];\n";
+      o << "    us_row(prm, tabs, x" << (S ? ", z" : "") << ", acc" << t.data_list(", r", {""}) << ");\n  }\n";
+    };
+    o << "  uint32_t d = lo;\n";
+    single("d < hi && (d & 3u) != 0u");
+    o << "  for (; hi - d >= 4u; d += 4u) {\n";
+    for (int c : t.cs)
+      for (int j = 0; j < 4; ++j) o << "    const float r" << c << "_" << j << " = pc" << c << "[d + " << j << "u];\n";
+    for (int j = 0; j < 4; ++j)
+      o << "    us_row(prm, tabs, x" << (S ? ", z" : "") << ", acc" << t.data_list(", r", {("_" + std::to_string(j)).c_str()}) << ");\n";
+    o << "  }\n";
+    single("d < hi");
+    o << "}\n";
+
+    o << "extern \"C\" __global__ __launch_bounds__(256) void " << (S ? "gjx_psis_units_grouped_kernel" : "gjx_psis_units_kernel")
+      << "(PsisUnitArgs a, PlanParams prm, PlanTables tabs, PlateData pd" << (S ? ", GroupCols gc" : "") << ") {\n";
+    o << "  const uint32_t ul = blockIdx.x;  // (the unit, local to the batch: wave-uniform)\n";
+    o << "  const GroupOff uo = (GroupOff)a.unit_off;\n";
+    o << "  const int32_t w0 = uo[(size_t)a.u0 + ul], w1 = uo[(size_t)a.u0 + ul + 1u];\n";
+    o << "  const uint32_t lo = w0 < 0 ? 0u : (uint32_t)w0 < pd.n_rows ? (uint32_t)w0 : pd.n_rows;\n";
+    o << "  const uint32_t h1 = w1 < 0 ? 0u : (uint32_t)w1 < pd.n_rows ? (uint32_t)w1 : pd.n_rows;\n";
+    o << "  const uint32_t hi = h1 < lo ? lo : h1;  // (decreasing words: an empty unit, never a wrapped row count)\n";
+    o << "  if (blockIdx.y == 0u && threadIdx.x == 0u) a.umax[ul] = 0u;  // (the maximum key of the unit: pass 0 of this batch raises it)\n";
+    if (S) {
+      o << "  const GroupOff go = (GroupOff)gc.off;\n";
+      o << "  const uint32_t g0 = lo < hi ? group_of_row(go, gc.G, lo) : 0u;\n";
+    }
+    o << "  const uint32_t step = 256u * " << PS << "u;\n";
+    o << "  for (uint64_t i64 = (uint64_t)blockIdx.y * step; i64 < a.n; i64 += (uint64_t)gridDim.y * step) {\n";
+    o << "    const uint32_t i0 = (uint32_t)i64 + threadIdx.x;\n";
+    o << "    uint32_t ix[" << PS << "];\n    float x[" << (L ? L : 1) << "][" << PS << "];\n    double acc[" << PS << "];\n";
+    o << "#pragma unroll\n    for (int k = 0; k < " << PS << "; ++k) {\n";
+    o << "      const uint64_t ik = (uint64_t)i0 + 256u * (uint32_t)k;\n      ix[k] = ik < a.n ? (uint32_t)ik : a.n - 1u;  // (a lane past the end: the last particle again, never stored)\n";
+    o << "      acc[k] = 0.0;\n";
+    if (!L) o << "      x[0][k] = 0.0f;\n";
+    for (int l = 0; l < L; ++l) o << "      x[" << l << "][k] = a.x[" << l << "][ix[k]];\n";
+    o << "    }\n";
+    if (S) {
+      o << "    float z[" << S << "][" << PS << "];\n    uint32_t g = g0;\n";
+      o << "    for (uint32_t d = lo; d < hi;) {\n";
+      o << "      while (g + 1u < gc.G && go[g + 1u] <= (int32_t)d) ++g;\n";
+      o << "      uint32_t e = hi;\n      if (g + 1u < gc.G) {  // (go[g + 1] > d >= 0: the group's rows end there)\n";
+      o << "        const uint32_t nx = (uint32_t)go[g + 1u];\n        e = nx < hi ? nx : hi;\n      }\n";
+      o << "#pragma unroll\n      for (int k = 0; k < " << PS << "; ++k) {\n";
+      for (int s = 0; s < S; ++s) o << "        z[" << s << "][k] = gc.z[" << s << "][(size_t)g * a.n + ix[k]];\n";
+      o << "      }\n      us_rows(prm, tabs, pd, d, e, x, z, acc);\n      d = e;\n    }\n";
+    } else {
+      o << "    us_rows(prm, tabs, pd, lo, hi, x, acc);\n";
+    }
+    o << "#pragma unroll\n    for (int k = 0; k < " << PS << "; ++k) {\n";
+    o << "      const uint64_t ik = (uint64_t)i0 + 256u * (uint32_t)k;\n";
+    o << "      if (ik < a.n) a.table[(size_t)ul * a.pitch + (size_t)ik] = (float)acc[k];\n    }\n";
+    o << "  }\n}\n";
+    return o.str();
+  }
+};
+
 // The predictive kernel of a plated tempered plan (include/gjx_predictive.h): the transposed loop of emit_particle_loop — rows
 // on lanes, the particles of a chunk wave-uniform — with a DRAW where the pointwise kernel has a density.  The header defines the draws
 // as an importance pass over the data rows, so the sites are emitted by the importance kernel's own emitters:

@@ -124,6 +124,10 @@ class GroupChecksUnavailable(HeaderUnavailable):
     header, why = "gjx_group_checks.h", "the pointwise, PSIS and predictive kernels of a grouped plan are generated HIP kernels only"
 
 
+class PsisUnitsUnavailable(HeaderUnavailable):
+    header, why = "gjx_psis_units.h", "PSIS leave-one-group-out runs as a generated unit-sum kernel and fixed HIP table passes only"
+
+
 class TemperCovUnavailable(HeaderUnavailable):
     header, why = "gjx_temper_cov.h", "the population moments and the covariance move run as HIP kernels only"
 
@@ -862,6 +866,24 @@ GROUP_CHECKS_PROTOTYPES = {
 }
 GROUP_CHECKS_ABI_VERSION = (0, 1)
 
+# include/gjx_psis_units.h: a SEVENTEENTH header, same arrangement — PSIS leave-one-group-out over contiguous row units of a
+# flat or a grouped plan: the unit sums once into a cached table, then the radix select of gjx_psis.h over that table.
+
+
+class PsisUnitsIO(C.Structure):
+    """gjx_psis_units_io (include/gjx_psis_units.h)."""
+    _fields_ = [("psis", PsisIO), ("table_bytes", C.c_size_t)]
+
+
+PSIS_UNITS_PROTOTYPES = {
+    "gjx_psis_units_version": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gjx_psis_units_workspace_bytes": (C.c_size_t, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_size_t]),
+    "gjx_temper_psis_units": (C.c_int, [_P, C.POINTER(PsisUnitsIO), _P, C.c_uint64, C.POINTER(GroupCols), _P]),
+    "gjx_psis_units_source": (C.c_int, [_P, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gjx_psis_units_compile_check": (C.c_int, [_P]),
+}
+PSIS_UNITS_ABI_VERSION = (0, 1)
+
 # The optional headers, in the order they are bound: every one is exported by libgjx_hip.so only and bound if present.
 class Header(collections.namedtuple("Header", "key header version_fn prototypes version_name unavailable")):
     @property
@@ -907,13 +929,27 @@ MOVE_HEADERS = {h.key: h for h in (
 )}
 
 
+# Headers that add a reduction over the plans and io structs of the check headers (gjx_psis_units.h).  A table of its own, and
+# kept out of all_optional_headers(), for the same reason once more: the suites of the earlier headers pin that tuple's length
+# and its last entry.  bound_headers() is what a library is bound with.
+CHECK_HEADERS = {h.key: h for h in (
+    Header("psis_units", "gjx_psis_units.h", "gjx_psis_units_version", PSIS_UNITS_PROTOTYPES, "PSIS_UNITS_ABI_VERSION",
+           PsisUnitsUnavailable),
+)}
+
+
 def all_optional_headers():
     """Every header next to gjx.h, in binding order: OPTIONAL_HEADERS, then EXTENSION_HEADERS, then PLAN_HEADERS, then
     MOVE_HEADERS."""
     return (*OPTIONAL_HEADERS.values(), *EXTENSION_HEADERS.values(), *PLAN_HEADERS.values(), *MOVE_HEADERS.values())
 
 
-_HEADER_OF = {name: h for h in all_optional_headers() for name in h.prototypes}  # entry point -> its optional header
+def bound_headers():
+    """Every header a library is bound with, in binding order: all_optional_headers(), then CHECK_HEADERS."""
+    return (*all_optional_headers(), *CHECK_HEADERS.values())
+
+
+_HEADER_OF = {name: h for h in bound_headers() for name in h.prototypes}  # entry point -> its optional header
 
 _NO_STATUS = {
     "gjx_temper_plan_n_latents",
@@ -925,6 +961,7 @@ _NO_STATUS = {
     "gjx_predictive_chunks",
     "gjx_psis_tail_len",
     "gjx_psis_workspace_bytes",
+    "gjx_psis_units_workspace_bytes",
     "gjx_predictive_workspace_bytes",
     "gjx_temper_moments_workspace_bytes",
     "gjx_backmove_workspace_bytes",
@@ -972,7 +1009,7 @@ class GjxLib:
         # is "wrong version", not "missing symbol"
         self.has = {}
         major, minor = C.c_int(-1), C.c_int(-1)
-        for h in (_CORE_HEADER, *all_optional_headers()):
+        for h in (_CORE_HEADER, *bound_headers()):
             if h is not _CORE_HEADER:
                 self.has[h.key] = hasattr(self._dll, h.version_fn)
                 setattr(self, "has_" + h.key, self.has[h.key])
@@ -999,7 +1036,7 @@ class GjxLib:
     def require(self, key: str, fn_name: str):
         """Raise the header's *Unavailable, naming `fn_name`, on a library without the optional header `key`."""
         if not self.has[key]:
-            raise next(h for h in all_optional_headers() if h.key == key).unavailable(fn_name, self.name)
+            raise next(h for h in bound_headers() if h.key == key).unavailable(fn_name, self.name)
 
     def call(self, name: str, *args):
         h = _HEADER_OF.get(name)

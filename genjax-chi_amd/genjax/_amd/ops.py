@@ -799,7 +799,7 @@ class Ops:
         io.n = n
         for l in range(L):
             io.x[l] = self._chk(x[l], torch.float32, n, f"x[{l}]").value
-        nb = int(self.lib.call(ws_symbol, n, D, *ws_args))
+        nb = int(ws_symbol(n, D, *ws_args) if callable(ws_symbol) else self.lib.call(ws_symbol, n, D, *ws_args))
         # (per call: see workspace(); uninitialised: the first launch writes every entry the fold reads)
         ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=self._alloc_device)
         io.ws, io.ws_bytes = ws.data_ptr(), ws.numel()
@@ -842,6 +842,37 @@ class Ops:
         else:
             self.lib.call("gjx_temper_psis_grouped", plan.handle, C.byref(io), C.byref(cols), self.stream())
         return out.view(7, D), (tail.view(D, M + 1) if tail is not None else None)
+
+    def temper_psis_units(self, plan: "TemperPlan", x: list, unit_offsets: torch.Tensor, tail_len: int, want_tail: bool = False, z=None,
+                          table_bytes: int = 0):
+        """gjx_temper_psis_units (include/gjx_psis_units.h): PSIS leave-one-group-out — temper_psis over UNITS, contiguous blocks
+        of the plan's data rows, each particle's entry the float64 sum of the unit's row terms -> (out float64[8, U]: elpd, khat,
+        sigma, s, tT, B, bad, lse; tail float32[U, tail_len + 1] or None) on the device.  `unit_offsets`: int32 [U + 1] on the
+        device, unit u owns the rows unit_offsets[u] .. unit_offsets[u + 1] - 1.  `z`: the grouped columns of a plan with grouped
+        latents.  `table_bytes`: the bound of the cached table of unit sums (0: 256 MB); the results do not depend on it."""
+        self.lib.require("psis_units", "gjx_temper_psis_units")
+        M, U = int(tail_len), unit_offsets.numel() - 1
+        n = x[0].numel() if x else 0
+        if not 5 <= M <= abi.PSIS_MAX_TAIL or M >= n:
+            raise ValueError(f"temper_psis_units: tail_len must be in 5 .. {abi.PSIS_MAX_TAIL} and below n = {n}, got {M}")
+        if U < 1:
+            raise ValueError("temper_psis_units: unit_offsets holds U + 1 >= 2 words")
+        uio = abi.PsisUnitsIO()
+        io = uio.psis
+        # (the size function of this header: units and the table bound in the place of the row count)
+        size = lambda n, D, *a: self.lib.call("gjx_psis_units_workspace_bytes", n, U, *a)
+        n, _, ws, cols = self._plated_io("psis", plan, x, io, size, M, int(table_bytes), z=z)
+        if ws.numel() == 8:  # (the size function's 0; the real sizes are far above)
+            raise ValueError(f"temper_psis_units: table_bytes = {table_bytes} holds fewer than four units of n = {n} particles")
+        uio.table_bytes = int(table_bytes)
+        out = self.empty(8 * U, torch.float64)
+        tail = self.empty(U * (M + 1), torch.float32) if want_tail else None
+        io.tail_len, io.out = M, out.data_ptr()
+        if tail is not None:
+            io.tail = tail.data_ptr()
+        self.lib.call("gjx_temper_psis_units", plan.handle, C.byref(uio), self._chk(unit_offsets, torch.int32, U + 1, "unit_offsets"), U,
+                      C.byref(cols) if cols is not None else None, self.stream())
+        return out.view(8, U), (tail.view(U, M + 1) if tail is not None else None)
 
     def temper_predictive(self, plan: "TemperPlan", key, x: list, draw_stride: int = 0, z=None):
         """gjx_temper_predictive (include/gjx_predictive.h): TWO launches -> (out float64[S, 5, D], draws float32[S, m, D] or
@@ -1367,6 +1398,16 @@ class TemperPlan(PlanHandle):
     def psis_source(self) -> str:
         """The HIP source of the plan's generated PSIS kernel (one per plan: it draws nothing)."""
         return self._source("gjx_psis_source")
+
+    def psis_units_compile_check(self) -> int:
+        """gjx_psis_units_compile_check (include/gjx_psis_units.h): the status, not raised."""
+        self.ops.lib.require("psis_units", "gjx_psis_units_compile_check")
+        return self.ops.lib._gjx_psis_units_compile_check(self.handle)
+
+    def psis_units_source(self) -> str:
+        """The HIP source of the plan's generated unit-sum kernel (flat or grouped, as the plan is)."""
+        self.ops.lib.require("psis_units", "gjx_psis_units_source")
+        return self._source("gjx_psis_units_source")
 
     def pointwise_source(self) -> str:
         """The HIP source of the plan's generated pointwise kernel (one per plan: it draws nothing)."""

@@ -132,12 +132,16 @@ class _TemperTracer(PlanTracer):
         Refused unless non-decreasing with values in 0 .. G - 1; empty groups are legal."""
         if addr is None:
             addr = next(m["addr"] for m in self.meta if m.get("grouped"))
-        g = self.group.detach().to(device="cpu", dtype=torch.int64)
-        G = self.n_groups
+        return self.offsets_of(self.group, self.n_groups, f"the group tensor of the grouped latent at address {addr!r}")
+
+    @staticmethod
+    def offsets_of(t: torch.Tensor, G: int, what: str) -> torch.Tensor:
+        """An integer tensor of group (or unit) indices -> offsets int32 [G + 1] (host), or GroupTensorRefused naming `what`."""
+        g = t.detach().to(device="cpu", dtype=torch.int64)
         if int(g.min()) < 0 or int(g.max()) >= G:
-            raise GroupTensorRefused(f"TemperedSMC: the group tensor of the grouped latent at address {addr!r} has values outside 0 .. {G - 1}")
+            raise GroupTensorRefused(f"TemperedSMC: {what} has values outside 0 .. {G - 1}")
         if bool((g[1:] < g[:-1]).any()):
-            raise GroupTensorRefused(f"TemperedSMC: the group tensor of the grouped latent at address {addr!r} is not sorted (the rows of "
+            raise GroupTensorRefused(f"TemperedSMC: {what} is not sorted (the rows of "
                                   "a group must be contiguous: non-decreasing group indices)")
         off = torch.zeros(G + 1, dtype=torch.int64)
         off[1:] = torch.cumsum(torch.bincount(g, minlength=G), dim=0)
@@ -610,6 +614,51 @@ class PSISLOO:
         return f"PSISLOO(rows={self.elpd_loo.numel()}, n={self.n}, tail_len={self.tail_len})"
 
 
+class PSISLOGO:
+    """Pareto-smoothed importance-sampling leave-one-GROUP-out cross-validation (include/gjx_psis_units.h): PSISLOO where what is
+    left out is a unit — a contiguous block of the plated site's rows — and a particle's entry is the sum of the log-likelihood
+    terms of the unit's rows.  Per unit u, float64 [U] on the device: `elpd_logo`, `khat`, `sigma`, `bad` as PSISLOO has them
+    per row, and `lppd` = log mean_i exp(T[u, i]).  `rows`: int64 [U] on the host, the units' sizes.  An EMPTY unit predicts
+    nothing: its elpd_logo and lppd are 0, its khat is reported as NaN, and it is left out of `se` and `n_high`.  The scalar
+    properties read the device ONCE: `elpd` = sum_u elpd_logo_u, `se` = sqrt(U' var_u(elpd_logo_u)) over the U' non-empty
+    units, `looic` = -2 elpd, `p_logo` = sum_u (lppd_u - elpd_logo_u), `khat_threshold` = min(1 - 1 / log10(n), 0.7) and
+    `n_high`, the non-empty units whose khat is above it."""
+
+    def __init__(self, table: torch.Tensor, rows: torch.Tensor, n: int, tail_len: int):
+        """`table`: float64 [8, U] — the rows elpd, khat, sigma, s, tT, B, bad, lse of gjx_temper_psis_units."""
+        if table.dim() != 2 or table.shape[0] != 8 or table.dtype != torch.float64:
+            raise ValueError("PSISLOGO: a float64 [8, U] tensor expected")
+        self.n, self.tail_len, self.rows = int(n), int(tail_len), rows.to(device="cpu", dtype=torch.int64)
+        if self.n < 2 or self.rows.numel() != table.shape[1]:
+            raise ValueError("PSISLOGO: n >= 2 and one size per unit")
+        empty = (self.rows == 0).to(table.device)
+        self.elpd_logo, self.sigma, self.bad = table[0], table[2], table[6]
+        self.khat = torch.where(empty, torch.full_like(table[1], float("nan")), table[1])
+        self.lppd = torch.where(empty, torch.zeros_like(table[7]), table[7] - math.log(self.n))
+        self.khat_threshold = min(1.0 - 1.0 / math.log10(self.n), 0.7)
+        self._host = None
+
+    def _scalars(self):
+        if self._host is None:
+            h = torch.stack([self.elpd_logo, self.khat, self.lppd]).cpu().numpy()  # (the one host read)
+            full = self.rows.numpy() > 0
+            e, k, lppd = h[0], h[1][full], h[2]
+            U = int(full.sum())
+            with np.errstate(invalid="ignore"):
+                se = math.sqrt(U * float(np.var(e[full], ddof=1))) if U > 1 else float("nan")
+                self._host = dict(elpd=float(e.sum()), se=se, p_logo=float((lppd - e).sum()), n_high=int((k > self.khat_threshold).sum()))
+        return self._host
+
+    elpd = property(lambda self: self._scalars()["elpd"])
+    se = property(lambda self: self._scalars()["se"])
+    looic = property(lambda self: -2.0 * self._scalars()["elpd"])
+    p_logo = property(lambda self: self._scalars()["p_logo"])
+    n_high = property(lambda self: self._scalars()["n_high"])
+
+    def __repr__(self):
+        return f"PSISLOGO(units={self.elpd_logo.numel()}, n={self.n}, tail_len={self.tail_len})"
+
+
 class PosteriorPredictive:
     """Replicated data of the plated site(s) under a population of n equally weighted particles
     (include/gjx_predictive.h): y_rep[d, i] ~ p(y | x_i, data_d), one draw per particle and data row.  Every field is a dict
@@ -1024,6 +1073,37 @@ class TemperedSMC(SMCAlgorithm):
             raise ValueError(f"TemperedSMC.loo: a population of n = {n} at r_eff = {r_eff} has no tail to fit (n >= 25 and a positive finite r_eff)")
         table, _ = ops.temper_psis(tplan, x, M, z=z)
         return PSISLOO(table, PointwiseLikelihood(ops.temper_pointwise(tplan, x, z=z), n), n, M)
+
+    # -- PSIS leave-one-group-out (include/gjx_psis_units.h) --------------------------------------------------------
+    def logo(self, res, groups=None, r_eff: float = 1.0, max_table_bytes: int | None = None) -> PSISLOGO:
+        """Pareto-smoothed importance-sampling leave-one-GROUP-out over the rows the sampler was fitted to, under the population
+        `res` (as `loo` takes it): what is left out is a unit, a contiguous block of rows, and a particle's entry is the sum of
+        the unit's row terms.  `groups=None`: the units are the groups of a plan with grouped latents (a flat plan has none: an
+        error).  `groups=`: an integer tensor [D], non-decreasing with values in 0 .. U-1, on a flat and a grouped plan alike
+        — unit u is the rows with groups == u; units need not be the plan's groups.  `r_eff` as in `loo`.  `max_table_bytes`
+        bounds the cached table of unit sums (None: 256 MB); the units go through it in batches and the results do not
+        depend on it.  Empty units: see PSISLOGO."""
+        st = self._state()
+        ops, tracer = st["ops"], st["tracer"]
+        split = self._split_population("logo", res)
+        ops.lib.require("psis_units", "gjx_temper_psis_units")
+        D = tracer.data_rows
+        if groups is None:  # (everything below: before anything is uploaded)
+            if not tracer.n_grouped:
+                raise PlanUnsupported("TemperedSMC.logo: a plan without grouped latents has no groups to leave out; pass groups=, an "
+                                      "integer tensor [D] of non-decreasing unit indices")
+            off = tracer.group_offsets()
+        else:
+            if not isinstance(groups, torch.Tensor) or groups.dim() != 1 or groups.is_floating_point() or groups.numel() != D or D == 0:
+                raise GroupTensorRefused(f"TemperedSMC: logo's groups= must be an integer tensor of the plate's {D} rows")
+            off = tracer.offsets_of(groups, int(groups.max()) + 1 if int(groups.min()) >= 0 else 1, "logo's groups= tensor")
+        _, tplan, x, z = self._population("logo", "leave-one-group-out densities", split, None)
+        n = int(x[0].numel())
+        M = int(ops.lib.call("gjx_psis_tail_len", n, float(r_eff)))
+        if M == 0:
+            raise ValueError(f"TemperedSMC.logo: a population of n = {n} at r_eff = {r_eff} has no tail to fit (n >= 25 and a positive finite r_eff)")
+        table, _ = ops.temper_psis_units(tplan, x, off.to(ops.device()), M, z=z, table_bytes=int(max_table_bytes or 0))
+        return PSISLOGO(table, off[1:].to(torch.int64) - off[:-1].to(torch.int64), n, M)
 
     # -- posterior predictive draws (include/gjx_predictive.h; DESIGN.md §4n) ---------------------------------------------------
     def _unobserved_target(self, st, args) -> Target:
