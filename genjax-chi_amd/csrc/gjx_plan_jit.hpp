@@ -1667,16 +1667,18 @@ struct TemperTable {
 // accumulators' lines around the two loops.
 template <class Table>
 inline void emit_particle_loop(std::ostream& o, const Table& t, int NB, const std::string& prologue, const std::string& block,
-                               const std::string& rest, const std::string& epilogue) {
+                               const std::string& rest, const std::string& epilogue, bool blocked = true) {
   for (int l = 0; l < t.L; ++l) o << "  const PlateCol xc" << l << " = (PlateCol)a.x[" << l << "];\n";
   o << "  const uint64_t lo64 = (uint64_t)blockIdx.y * a.per;\n";
   o << "  const uint32_t lo = lo64 < a.n ? (uint32_t)lo64 : a.n;\n";
   o << "  const uint32_t hi = a.n - lo > a.per ? lo + a.per : a.n;\n";
   o << prologue << "  uint32_t i = lo;\n";
-  o << "  for (; hi - i >= " << NB << "u; i += " << NB << "u) {\n";
-  for (int l = 0; l < t.L; ++l)
-    for (int j = 0; j < NB; ++j) o << "    const float x" << l << "_" << j << " = xc" << l << "[(size_t)i + " << j << "u];\n";
-  o << block << "  }\n";
+  if (blocked) {  // (not blocked: the particles one by one, in the same order — the `rest` loop alone)
+    o << "  for (; hi - i >= " << NB << "u; i += " << NB << "u) {\n";
+    for (int l = 0; l < t.L; ++l)
+      for (int j = 0; j < NB; ++j) o << "    const float x" << l << "_" << j << " = xc" << l << "[(size_t)i + " << j << "u];\n";
+    o << block << "  }\n";
+  }
   o << "  for (; i < hi; ++i)" << rest << epilogue;
 }
 
@@ -2321,6 +2323,13 @@ struct GenPredictive {
   const CSiteT* sites;
   int n_sites;
 
+  // pd_particle is inlined once per particle of a block and once more for the rest loop: NB + 1 copies of every drawn site's
+  // sampler.  With more than four drawn sites — a Gamma, a Beta, a Poisson and a negative-binomial rejection loop among seven,
+  // two rows each — the THREEFRY kernel of such a table took all 512 VGPRs, 256 AGPRs and 176 bytes of scratch per lane; one
+  // copy takes 315 VGPRs and no scratch.  Such tables walk the particles one by one: the same particles in the same order,
+  // the same accumulators.  Tables of up to four drawn sites keep their source byte for byte.
+  static constexpr int kBlockedSites = 4;
+
   std::string run() {
     using Emitter = SiteEmitter<CSiteT, CArgT>;
     constexpr int NB = gjx::kPredictiveBlock;
@@ -2412,7 +2421,8 @@ struct GenPredictive {
                            "; ++s) qA[s] = qB[s] = predictive_start();\n  PredictiveKeep kp = predictive_keep_start(a, lo);\n",
                        block, " " + particle("i", t.list(", xc", "[i]"), zat("i")),
                        "#pragma unroll\n  for (int s = 0; s < " + SS + "; ++s) {\n    predictive_store(a, pd.n_rows, (uint32_t)s, blockIdx.y, dA, qA[s]);\n"
-                       "    if (hasB) predictive_store(a, pd.n_rows, (uint32_t)s, blockIdx.y, dA + 1u, qB[s]);\n  }\n}\n");
+                       "    if (hasB) predictive_store(a, pd.n_rows, (uint32_t)s, blockIdx.y, dA + 1u, qB[s]);\n  }\n}\n",
+                       S <= kBlockedSites);
     return o.str();
   }
 };

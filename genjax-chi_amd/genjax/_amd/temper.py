@@ -256,7 +256,29 @@ class _TemperTracer(PlanTracer):
             return abi.Arg(abi.ARG_DATA, self.data_col(v), 1.0, 0.0, None)
         if isinstance(v, SymExpr) and len(v.prog) == 1 and v.prog[0][0] == abi.EXPR_GROUP:  # (`a[g]` itself: the affine operand)
             return abi.Arg(abi.ARG_GROUP, v.prog[0][1], 1.0, 0.0, None)
+        affine = self._affine_group(v.prog) if isinstance(v, SymExpr) else None
+        if affine is not None:
+            return abi.Arg(abi.ARG_GROUP, *affine, None)
         return super()._arg(v)
+
+    @staticmethod
+    def _affine_group(prog):
+        """(ref, scale, offset) of a program that is ONE affine step over one grouped value — `c * a[g] + d`, `a[g] * c - d`,
+        `a[g] + d` — or None.  The operand scale * z + offset rounds where the program rounds (a multiply, then an add; `- d`
+        is `+ (-d)` exactly; 1 * z is z), as an affine read of a scalar latent is ARG_SITE.  A multiply ALONE stays a program:
+        the operand's `+ 0` would turn a product of -0 into +0."""
+        ops = [op for op, _, _ in prog]
+        C_, G_ = abi.EXPR_CONST, abi.EXPR_GROUP
+        scale = 1.0
+        if ops[:3] in ([G_, C_, abi.EXPR_MUL], [C_, G_, abi.EXPR_MUL]):
+            ref, scale, rest = prog[ops.index(G_)][1], prog[ops.index(C_)][2], prog[3:]
+        elif ops[:1] == [G_]:
+            ref, rest = prog[0][1], prog[1:]
+        else:
+            return None
+        if len(rest) != 2 or rest[0][0] != C_ or rest[1][0] not in (abi.EXPR_ADD, abi.EXPR_SUB):
+            return None
+        return ref, scale, rest[0][2] if rest[1][0] == abi.EXPR_ADD else -rest[0][2]
 
     def _call(self, addr, gen_fn, args):
         raise PlanUnsupported(f"TemperedSMC: nested generative function at address {addr!r}")

@@ -107,7 +107,13 @@ def nb_tolerance(k, r, p):
 F = np.float32
 
 
-def m_lgamma32(x):
+def _log32(x):
+    return np.log(x).astype(F)
+
+
+def m_lgamma32(x, log=_log32):
+    """`log`: the f32 logarithm, numpy's by default; a replay that must match a kernel bit for bit passes the spec's own
+    (gjx_map_f32 of the oracle: tests/group_ref.py)."""
     x = np.asarray(x, dtype=F).copy()
     p = np.ones_like(x)
     for _ in range(8):
@@ -120,32 +126,33 @@ def m_lgamma32(x):
     s = fma(xi2, F(7.9365079365e-4), F(-2.7777777778e-3))
     s = (s.astype(np.float64) * xi2.astype(np.float64) + np.float64(F(8.3333333333e-2))).astype(F)
     s = (s * xi).astype(F)
-    r = ((x - F(0.5)) * np.log(x).astype(F)).astype(F)
+    r = ((x - F(0.5)) * log(x)).astype(F)
     r = (r - x).astype(F)
     r = (r + F(0.91893853320467)).astype(F)
     r = (r + s).astype(F)
-    return (r - np.log(p).astype(F)).astype(F)
+    return (r - log(p)).astype(F)
 
 
-def xlogy32(a, y):
+def xlogy32(a, y, log=_log32):
     a, y = np.asarray(a, dtype=F), np.asarray(y, dtype=F)
     with np.errstate(all="ignore"):
-        return np.where(a == 0, F(0.0), (a * np.log(y).astype(F)).astype(F)).astype(F)
+        return np.where(a == 0, F(0.0), (a * log(y)).astype(F)).astype(F)
 
 
-def poisson_logpmf32(k, rate):
+def poisson_logpmf32(k, rate, lf=None, log=_log32):
+    """`lf`: log k! as a plated site reads it from its data column (None: m_lgamma(k + 1), a scalar site's and a draw's)."""
     k, rate = np.asarray(k, dtype=F), np.asarray(rate, dtype=F)
-    lf = m_lgamma32(k + F(1.0))
-    return ((xlogy32(k, rate) - rate).astype(F) - lf).astype(F)
+    lf = m_lgamma32(k + F(1.0), log) if lf is None else np.asarray(lf, dtype=F)
+    return ((xlogy32(k, rate, log) - rate).astype(F) - lf).astype(F)
 
 
-def nb_logpmf32(k, r, p):
+def nb_logpmf32(k, r, p, lf=None, log=_log32):
     k, r, p = (np.asarray(v, dtype=F) for v in (k, r, p))
-    lf = m_lgamma32(k + F(1.0))
-    t = (m_lgamma32((k + r).astype(F)) - lf).astype(F)
-    t = (t - m_lgamma32(r)).astype(F)
-    t = (t + xlogy32(k, p)).astype(F)
-    return (t + xlogy32(r, (F(1.0) - p).astype(F))).astype(F)
+    lf = m_lgamma32(k + F(1.0), log) if lf is None else np.asarray(lf, dtype=F)
+    t = (m_lgamma32((k + r).astype(F), log) - lf).astype(F)
+    t = (t - m_lgamma32(r, log)).astype(F)
+    t = (t + xlogy32(k, p, log)).astype(F)
+    return (t + xlogy32(r, (F(1.0) - p).astype(F), log)).astype(F)
 
 
 # ---- the host ciphers, vectorised (genjax/_amd/prng.py restates them for scalars), and a site's draw stream --------------------

@@ -159,6 +159,50 @@ def _support(dist, v, term):
     return term
 
 
+def _value_plan(oracle_ops, arg):
+    """A single-site oracle plan whose VALUE column is `arg` (mapped by _arg) as the oracle evaluates it: a latent Normal of
+    scale 0 — the oracle draws loc + 0 * eps with a finite eps, which is loc (up to the sign of a zero).  The programs of an
+    argument are evaluated by the oracle's own walk: nothing here interprets an expression."""
+    s = abi.Site()
+    s.dist, s.observed, s.out_col = abi.DIST_NORMAL, 0, 0
+    s.arg[0], s.arg[1] = arg, abi.Arg(abi.ARG_CONST, 0, 0.0, 0.0, None)
+    return oracle_ops.plan_create([s])
+
+
+class _CountSite:
+    """A plated Poisson / negative-binomial site (include/gjx_counts.h), which the oracle does not know: its arguments are
+    the oracle's (one _value_plan each), its density is counts_ref's numpy-f32 restatement of the header's formula — every
+    operator rounding once — with the oracle's own logarithm (gjx_map_f32) and log k! read from the column after the observed
+    one, as the kernel reads it."""
+
+    def __init__(self, oracle_ops, dist, args, obs_col):
+        self.ops, self.dist, self.obs_col = oracle_ops, dist, obs_col
+        self.plans = [_value_plan(oracle_ops, a) for a in args[:1 if dist == abi.DIST_POISSON else 2]]
+
+    def _log(self, x):
+        x = np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float32), np.shape(x)))
+        return self.ops.map_f32(abi.MAP_LOG, torch.from_numpy(x.copy())).numpy()
+
+    def term(self, assess, d, ins, n):
+        import counts_ref as K
+
+        a = []
+        for plan in self.plans:
+            plan.set_params(list(assess._tracer.params) + [float(c[d]) for c in assess.data])
+            kb = prng.split_lazy(prng.key(0, assess.impl), n)
+            a.append(assess.ops.importance_run(plan, kb, n, ins, [torch.float32], want_score=False, want_max_partials=False)[0][0].numpy().copy())
+        k = np.full(n, np.rint(assess.data[self.obs_col][d]), dtype=np.float32)
+        lf = np.full(n, assess.data[self.obs_col + 1][d], dtype=np.float32)
+        with np.errstate(all="ignore"):
+            if self.dist == abi.DIST_POISSON:
+                ok, t = a[0] >= 0, K.poisson_logpmf32(k, a[0], lf, self._log)
+            else:
+                ok, t = (a[0] > 0) & (a[1] >= 0) & (a[1] <= 1), K.nb_logpmf32(k, a[0], a[1], lf, self._log)
+            # (the header: an argument outside the domain gives NaN, a value that is not >= 0 gives -inf, in that order)
+            t = np.where(k >= 0, t, np.float32(-np.inf))
+            return np.where(ok, t, np.float32(np.nan)).astype(np.float32)
+
+
 class Assess:
     """assess(x, z) of a lowered grouped model from single-site oracle plans and numpy sums in the header's order."""
 
@@ -187,7 +231,12 @@ class Assess:
                 kind, c.obs = ("reader" if _reads_group(s) else "plated"), abi.Arg(abi.ARG_PARAM, base + s.obs.ref, s.obs.scale, s.obs.offset, None)
             else:
                 kind = "observed"
-            plan = oracle_ops.plan_create([c])
+            if s.dist in abi.COUNT_DISTS:
+                assert kind in ("plated", "reader"), "a scalar observed count site is not replayed here"
+                assert (s.obs.scale, s.obs.offset) == (1.0, 0.0) and tracer.lf_cols.get(s.obs.ref + 1) == s.obs.ref
+                plan = _CountSite(oracle_ops, s.dist, [c.arg[0], c.arg[1]], s.obs.ref)
+            else:
+                plan = oracle_ops.plan_create([c])
             if tracer.params and kind in ("latent", "observed", "grouped"):
                 plan.set_params(tracer.params)
             self.terms.append((kind, plan, s.dist))
@@ -202,6 +251,8 @@ class Assess:
         return [torch.from_numpy(np.ascontiguousarray(c, dtype=np.float32)) for c in list(x) + list(zg)]
 
     def _row(self, plan, d, ins, n):
+        if isinstance(plan, _CountSite):
+            return plan.term(self, d, ins, n)
         plan.set_params(list(self._tracer.params) + [float(c[d]) for c in self.data])
         return self._logw(plan, ins, n)
 
@@ -272,13 +323,22 @@ class Assess:
         return self.total(lpf, LZ), self.total(llf, A)
 
 
-def _arg_value(a, x, lat, params, n):
+def _arg_value(a, x, lat, params, n, oracle_ops=None):
     """The f32 value of a grouped site's argument at the particles' scalars: a literal, a parameter or an affine read of a
-    scalar latent (multiply, then add: one rounding each)."""
+    scalar latent (multiply, then add: one rounding each); a PROGRAM over those through a single-site oracle plan
+    (_value_plan: the oracle evaluates it)."""
     if a.kind == abi.ARG_CONST:
         return float(np.float32(a.offset))
     if a.kind == abi.ARG_PARAM:
         return float(np.float32(np.float32(a.scale) * np.float32(params[a.ref]) + np.float32(a.offset)))
+    if a.kind == abi.ARG_EXPR:
+        keep = []
+        plan = _value_plan(oracle_ops, _arg(a, lat, len(params), len(lat), keep))
+        if params:
+            plan.set_params(params)
+        ins = [torch.from_numpy(np.ascontiguousarray(c, dtype=np.float32)) for c in x]
+        return oracle_ops.importance_run(plan, prng.split_lazy(prng.key(0, 1), n), n, ins, [torch.float32], want_score=False,
+                                         want_max_partials=False)[0][0].clone()
     assert a.kind == abi.ARG_SITE, a.kind
     v = (np.float32(a.scale) * np.asarray(x[lat[a.ref]], dtype=np.float32)).astype(np.float32)
     return torch.from_numpy(np.ascontiguousarray((v + np.float32(a.offset)).astype(np.float32)))
@@ -292,11 +352,13 @@ def init_ref(oracle_ops, tracer, init_key, x, G):
     sites = [s for s in tracer.sites if s.observed == abi.SITE_GROUPED]
     names = {abi.DIST_NORMAL: "normal", abi.DIST_GAMMA: "gamma", abi.DIST_BETA: "beta"}
     z = [np.empty((G, n), dtype=np.float32) for _ in sites]
+    # (a grouped site's arguments read the scalars alone: one value per particle, the same for every group)
+    args = [[_arg_value(st.arg[k], x, lat, tracer.params, n, oracle_ops) for k in range(2)] for st in sites]
     for g in range(G):
         kg = prng.fold_in(init_key, g)
         for s, st in enumerate(sites):
             kb = KeyBatch(init_key.impl, 1, parent=(kg.k0, kg.k1), first=0, fold=(s + 1 if init_key.impl == 0 else s), parent_lane=kg.lane)
-            a0, a1 = (_arg_value(st.arg[k], x, lat, tracer.params, n) for k in range(2))
+            a0, a1 = args[s]
             z[s][g] = oracle_ops.sample_logpdf(names[st.dist], kb, n, a0, a1, want_score=False)[0].numpy()
     return z
 

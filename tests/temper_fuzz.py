@@ -17,6 +17,7 @@ import re
 import numpy as np
 import torch
 
+from counts_ref import nb_logpmf, nb_tolerance, poisson_logpmf, poisson_tolerance
 from dist_range_ref import beta_tolerance, gamma_tolerance
 from fuzz_models import _expr, _pos
 
@@ -198,6 +199,7 @@ class Evaluation:
         self.tol_lp, self.tol_ll = np.zeros(n), np.zeros(n)
         self.tables, self.tol_tables, self.pit, self.order = {}, {}, {}, []
         self.laws, self.kinds = {}, {}  # plated address: (kind, float64 arguments [n, D]); latent address: kind
+        self.group_laws = {}            # grouped address: (kind, float64 arguments [n, G]) (tests/group_fuzz.py)
 
     def terms(self):
         """[D, n]: the f32 sum, in table order, of the plated sites' tables (pointwise_ref.terms' composition), and the sum of
@@ -220,20 +222,31 @@ def evaluate64(source, latents, observed, args, dtype=torch.float64):
     its domain (scale, shape, rate <= 0, p outside [0, 1]) makes the reference NaN there: no truth to compare with.
     Per plated address `laws` keeps the site's kind and its arguments broadcast to [n, D]: the law of the replicated draw
     y_rep[d, i] of include/gjx_predictive.h.  That header's SHADOW rule is restated by what `@` returns: a plated site that reads
-    an earlier plated site's value reads the OBSERVED column (the value returned here), never that site's replicated draw."""
+    an earlier plated site's value reads the OBSERVED column (the value returned here), never that site's replicated draw.
+    Grouped bodies (tests/group_fuzz.py; include/gjx_group.h): a `latents` entry of shape [G, n] is the value of a GROUPED
+    address `dist(...).repeat(n=G) @ addr`; its log-density [n, G], with the same support rule (NaN included), is summed into
+    lp, and `@` returns an object whose `[g]` — g the int64 [D] group column, passed as an integer model argument — is the
+    [n, D] tensor z[g(d), i].  `poisson` and `negative_binomial` sites take genjax's parametrisations (rate / log_rate,
+    probs / logits); their float64 density and bounds are counts_ref's."""
     import torch.distributions as TD
 
-    n = len(next(iter(latents.values())))
+    n = int(np.shape(next(iter(latents.values())))[-1])
     ev = Evaluation(n, dtype)
     want_tol = dtype == torch.float64
+    n_groups = {np.shape(v)[0] for v in latents.values() if np.ndim(v) == 2}
+    assert len(n_groups) <= 1, n_groups
 
     def tensor(v):
         if isinstance(v, torch.Tensor):
             return v.to(dtype)
         return torch.as_tensor(np.asarray(v, dtype=np.float64)).to(dtype)
 
-    def site(kind, a, addr):
-        if addr in latents:
+    def site(kind, a, addr, repeat=None):
+        if addr in latents and np.ndim(latents[addr]) == 2:
+            # a GROUPED latent (include/gjx_group.h), its value a column [G, n]: G components, i.i.d. given the scalars
+            assert repeat == np.shape(latents[addr])[0], (addr, repeat)
+            role, x = "grouped", tensor(latents[addr]).T
+        elif addr in latents:
             role, x = "latent", tensor(latents[addr]).reshape(n, 1)
         else:
             v = np.asarray(observed[addr])
@@ -246,12 +259,14 @@ def evaluate64(source, latents, observed, args, dtype=torch.float64):
             lp = torch.where((a[0] > 0) & (a[1] > 0), TD.Gamma(a[0], a[1], validate_args=False).log_prob(x), nan)
         elif kind == "beta":
             lp = torch.where((a[0] > 0) & (a[1] > 0), TD.Beta(a[0], a[1], validate_args=False).log_prob(x), nan)
-        else:
+        elif kind == "flip":
             p = a[0]
             lp = torch.where((p >= 0) & (p <= 1), torch.where(x != 0, torch.log(p), torch.log1p(-p)), nan)
-        shape = (n, x.shape[1] if role == "plated" else 1)
+        else:
+            lp = _count_logpmf(kind, x, a, dtype)
+        shape = (n, x.shape[1] if role in ("plated", "grouped") else 1)
         lp = lp + torch.zeros(shape, dtype=dtype)
-        if role == "latent":
+        if role in ("latent", "grouped"):
             if kind == "gamma":
                 lp = torch.where(x > 0, lp, torch.full((), float("-inf"), dtype=dtype))
             elif kind == "beta":
@@ -260,12 +275,19 @@ def evaluate64(source, latents, observed, args, dtype=torch.float64):
         if want_tol:
             xs_, as_ = x.numpy(), [v.numpy() for v in a]
             tol = (normal_tolerance(xs_, *as_) if kind == "normal" else gamma_tolerance(xs_, *as_) if kind == "gamma" else
-                   beta_tolerance(xs_, *as_) if kind == "beta" else bernoulli_tolerance(lp.numpy()))
+                   beta_tolerance(xs_, *as_) if kind == "beta" else bernoulli_tolerance(lp.numpy()) if kind == "flip" else
+                   poisson_tolerance(xs_, *as_) if kind == "poisson" else nb_tolerance(xs_, *as_))
             tol = np.nan_to_num(np.broadcast_to(tol, shape).astype(np.float64), nan=0.0, posinf=0.0, neginf=0.0)
-        if role == "latent":
+        if role in ("latent", "grouped"):
             ev.kinds[addr] = kind
         elif role == "plated":
-            ev.laws[addr] = (kind, [np.broadcast_to(v.to(torch.float64).numpy(), shape) for v in a[:1 if kind == "flip" else 2]])
+            ev.laws[addr] = (kind, [np.broadcast_to(v.to(torch.float64).numpy(), shape) for v in a[:1 if kind in ("flip", "poisson") else 2]])
+        if role == "grouped":
+            ev.lp = ev.lp + lp.sum(dim=1)
+            ev.group_laws[addr] = (kind, [np.broadcast_to(v.to(torch.float64).numpy(), shape) for v in a[:2]])
+            if want_tol:
+                ev.tol_lp = ev.tol_lp + tol.sum(axis=1)
+            return _GroupValue(x)
         if role == "latent":
             ev.lp = ev.lp + lp[:, 0]
             if want_tol:
@@ -287,19 +309,63 @@ def evaluate64(source, latents, observed, args, dtype=torch.float64):
         return x
 
     class Dist:
-        def __init__(self, kind, a):
-            self.kind, self.a = kind, a
+        def __init__(self, kind, a, n_rep=None):
+            self.kind, self.a, self.n_rep = kind, a, n_rep
+
+        def repeat(self, n):
+            return Dist(self.kind, self.a, n)
 
         def __matmul__(self, addr):
-            return site(self.kind, self.a, addr)
+            return site(self.kind, self.a, addr, self.n_rep)
 
-    ns = {"torch": torch}
+    def poisson(rate=None, *, log_rate=None):  # (genjax.poisson: a rate, or log_rate on the unconstrained scale)
+        return Dist("poisson", (rate,) if log_rate is None else (torch.exp(tensor(log_rate)),))
+
+    def negative_binomial(total_count, probs=None, *, logits=None):
+        return Dist("negative_binomial", (total_count, probs if logits is None else torch.sigmoid(tensor(logits))))
+
+    ns = {"torch": torch, "poisson": poisson, "negative_binomial": negative_binomial}
+    if n_groups:
+        ns["G"] = n_groups.pop()
     for kind in ("normal", "gamma", "beta", "flip"):
         ns[kind] = (lambda k: lambda *a: Dist(k, a))(kind)
     exec(source, ns)  # noqa: S102 - the body under test, executed as written
     with torch.no_grad():
-        ns["model"](*[tensor(v).reshape(1, -1) if np.ndim(v) == 1 else float(v) for v in args])
+        ns["model"](*[torch.as_tensor(np.asarray(v), dtype=torch.int64) if np.ndim(v) == 1 and np.asarray(v).dtype.kind == "i" else
+                      tensor(v).reshape(1, -1) if np.ndim(v) == 1 else float(v) for v in args])
     return ev
+
+
+class _GroupValue:
+    """What `@` returns for a grouped site: `[g]`, g the int64 [D] group column, is the [n, D] tensor z[g(d), i]."""
+
+    def __init__(self, x):
+        self.x = x  # [n, G]
+
+    def __getitem__(self, g):
+        assert isinstance(g, torch.Tensor) and g.dtype == torch.int64 and g.dim() == 1, "a grouped value is indexed by the group column"
+        return self.x[:, g]
+
+
+def _count_logpmf(kind, k, a, dtype):
+    """Poisson(rate) / NegativeBinomial(total_count, probs) at the counts k (include/gjx_counts.h's parametrisation): in
+    float64 counts_ref's densities; in float32 (the rounding floor of a case) the same formulas in torch's f32.  NaN for an
+    argument outside the domain (rate < 0; total_count <= 0; probs outside [0, 1])."""
+    nan = torch.full((), float("nan"), dtype=dtype)
+    if kind == "poisson":
+        rate, ok = a[0], a[0] >= 0
+        if dtype == torch.float64:
+            lp = torch.from_numpy(np.asarray(poisson_logpmf(*np.broadcast_arrays(k.numpy(), rate.numpy()))))
+        else:
+            lp = torch.xlogy(k, rate) - rate - torch.lgamma(k + 1.0)
+    else:
+        r, p = a
+        ok = (r > 0) & (p >= 0) & (p <= 1)
+        if dtype == torch.float64:
+            lp = torch.from_numpy(np.asarray(nb_logpmf(*np.broadcast_arrays(k.numpy(), r.numpy(), p.numpy()))))
+        else:
+            lp = torch.lgamma(k + r) - torch.lgamma(k + 1.0) - torch.lgamma(r) + torch.xlogy(k, p) + r * torch.log1p(-p)
+    return torch.where(ok, lp.to(dtype), nan)
 
 
 class Reference:

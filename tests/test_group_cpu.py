@@ -107,6 +107,42 @@ def test_lowering(lowered):
     assert [s.observed for s in tr.sites] == [0, abi.SITE_PLATED, 0, abi.SITE_GROUPED, 1, abi.SITE_PLATED] and plan.n_latents == 2
 
 
+def test_affine_read_of_a_grouped_value_is_the_group_operand(ops):  # noqa: F811
+    """The header's operand `scale * z[ref][g(d)] + offset` was reachable from no body: every read but the bare `a[g]` was
+    lowered to a program.  ONE affine step over one grouped value — a multiply by a literal, then an add or subtract of one — is
+    the operand (the roundings are the program's: a multiply, then an add); a multiply alone, a literal on the left of the
+    add and anything longer stay programs."""
+    G = 3
+    xs, ys = torch.linspace(0.0, 1.0, 8), torch.rand(8) + 0.5
+    g = torch.tensor([0, 0, 0, 1, 1, 2, 2, 2])
+
+    def lowered(fn):
+        with use_ops(ops):
+            tr = temper.lower(Target(gen(fn), (xs, g), ChoiceMap.d({"y": ys})), 64)
+            assert ops.temper_plan_create(tr.sites, keep=(tr.keep, tr)).n_grouped == 2  # (the creator accepts the operand)
+        return tr.sites[-1]
+
+    def body(loc, scale):
+        def fn(xs, g):
+            mu = normal(0.0, 1.0) @ "mu"
+            a = normal(mu, 1.0).repeat(n=G) @ "a"
+            s = gamma(2.0, 2.0).repeat(n=G) @ "s"
+            normal(loc(a, s, g, xs), scale(a, s, g, xs)) @ "y"
+        return fn
+
+    arg = lambda a: (a.kind, a.ref, a.scale, a.offset)  # noqa: E731
+    f32 = lambda v: float(np.float32(v))  # noqa: E731
+    y = lowered(body(lambda a, s, g, xs: 2.0 * a[g] - 0.5, lambda a, s, g, xs: s[g] + 0.1))
+    assert arg(y.arg[0]) == (abi.ARG_GROUP, 0, 2.0, -0.5) and arg(y.arg[1]) == (abi.ARG_GROUP, 1, 1.0, f32(0.1))
+    y = lowered(body(lambda a, s, g, xs: a[g] * 0.3 + 0.7, lambda a, s, g, xs: s[g]))
+    assert arg(y.arg[0]) == (abi.ARG_GROUP, 0, f32(0.3), f32(0.7)) and arg(y.arg[1]) == (abi.ARG_GROUP, 1, 1.0, 0.0)
+    y = lowered(body(lambda a, s, g, xs: 2.0 * a[g], lambda a, s, g, xs: 0.1 + s[g]))
+    assert _prog(y.arg[0]) == [(abi.EXPR_CONST, 0), (abi.EXPR_GROUP, 0), (abi.EXPR_MUL, 0)]
+    assert _prog(y.arg[1]) == [(abi.EXPR_CONST, 0), (abi.EXPR_GROUP, 1), (abi.EXPR_ADD, 0)]
+    y = lowered(body(lambda a, s, g, xs: 2.0 * a[g] - 0.5 + xs, lambda a, s, g, xs: (s[g] + 0.1) * 2.0))
+    assert y.arg[0].kind == abi.ARG_EXPR and y.arg[1].kind == abi.ARG_EXPR
+
+
 def test_group_tensor_is_read_again_at_every_run(ops):  # noqa: F811
     with use_ops(ops):
         target, g, _ = GR.target("intercept", SIZES)
