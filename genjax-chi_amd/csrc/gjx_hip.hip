@@ -23,6 +23,7 @@
 #include "../../include/gjx_counts.h"
 #include "../../include/gjx_group.h"
 #include "../../include/gjx_group_checks.h"
+#include "../../include/gjx_group_cov.h"
 // The library's own kernels keep the Philox round's plain XOR chain (gjx_device.hpp xor3): with v_bitop3_b32 the one-filter
 // LGSSM step measured 0.5 % slower (8.96e10 against 9.01e10 particle-steps/s, three alternating runs each, parent's range
 // 0.1 %), while the generated kernels, which include the header on their own, gain 6 % (importance) and 12 % (LGSSM scan);
@@ -4934,7 +4935,8 @@ int gjx_backmove_run(gjx_backsim_plan* p, const gjx_backmove_io* io, void* ws, s
 // of include/gjx_group_checks.h — the pointwise, predictive and PSIS generators in their grouped mode.
 enum TemperKernel { kTemperMove, kTemperCovMove, kTemperPointwise, kTemperPredictive, kTemperPsis, kTemperGroupedMove,
                     kTemperGroupedPointwise, kTemperGroupedPredictive, kTemperGroupedPsis, kTemperPsisUnits, kTemperGroupedPsisUnits,
-                    kTemperKernelCount };  // (the last two: the unit-sum kernel of include/gjx_psis_units.h, flat and grouped)
+                    kTemperGroupedCovMove,  // (the two before: the unit-sum kernel of include/gjx_psis_units.h, flat and grouped;
+                    kTemperKernelCount };   // the last: the block move of include/gjx_group_cov.h)
 struct gjx_temper_plan {
   int n_sites, n_latents;
   int n_params;   // values set by gjx_temper_plan_set_params
@@ -4983,7 +4985,8 @@ constexpr TemperKernelDesc kTemperKernels[kTemperKernelCount] = {{"gjx_temper_mo
                                                 {"gjx_predictive_grouped_kernel", gjx_jit::PlanKind::predictive, true, true, true},
                                                 {"gjx_psis_grouped_kernel", gjx_jit::PlanKind::psis, false, true, true},
                                                 {"gjx_psis_units_kernel", gjx_jit::PlanKind::psis, false, true, false},
-                                                {"gjx_psis_units_grouped_kernel", gjx_jit::PlanKind::psis, false, true, true}};
+                                                {"gjx_psis_units_grouped_kernel", gjx_jit::PlanKind::psis, false, true, true},
+                                                {"gjx_temper_move_grouped_cov_kernel", gjx_jit::PlanKind::temper, true, false, true}};
 // Has the plan a pointwise (and a predictive, and a PSIS) source?  A PLATED site, and no per-particle input column anywhere in the table
 // (the io structs have none).
 bool pointwise_plan_ok(const gjx_temper_plan* p) { return p && p->plated && p->max_input < 0 && p->n_grouped == 0; }
@@ -5018,9 +5021,9 @@ std::string temper_source(const gjx_temper_plan* p, TemperKernel k, int impl, Pl
     gjx_jit::GenPsisUnits<CSite, CArg> g;
     return run(g);
   }
-  if (k == kTemperGroupedMove) {
+  if (k == kTemperGroupedMove || k == kTemperGroupedCovMove) {
     gjx_jit::GenTemperGrouped<CSite, CArg> g;
-    g.impl = impl;
+    g.impl = impl; g.block = k == kTemperGroupedCovMove;
     return run(g);
   }
   gjx_jit::GenTemper<CSite, CArg> g;
@@ -5431,6 +5434,190 @@ __global__ __launch_bounds__(kBlock) void k_temper_moments(MomentsArgs a) {
   __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---- the per-group moments and proposal factors of grouped latents (include/gjx_group_cov.h) ------------------------------
+// Launch 1, k_group_moments<S>: workgroup (x, y) owns the particle blocks b = x, x + gridDim.x, ... and of each the groups
+// g = y, y + gridDim.y, ...  Per block: one pass over lw for m_b, the block's e_i into LDS as f32 (dynamic: `per` floats),
+// then per group the lanes walk the block (lane t: entries lo + t, lo + t + 256, ...: coalesced rows of z[s][g]), P float64
+// sums per lane in registers, one xor butterfly per sum inside each wave and the four waves as (w0 + w1) + (w2 + w3): the
+// balanced tree of the header.  Launch 2, k_group_factor<S>: one lane per group folds part[g][0 .. W-1][P] in index order and
+// runs the factor recursion in registers (S is a template parameter: every array index is a constant after unrolling).
+constexpr uint64_t kGroupMomentsWorkgroups = 2048;  // blocks x group ranges: about this many, whatever G is
+struct GroupMomentsArgs {
+  const float* z[kGroupMaxSites];
+  const float* lw;         // nullable: equal weights
+  float* factor;           // [G][S (S + 1) / 2]
+  float* scales;           // [S][G]
+  uint32_t* n_degenerate;  // [1]
+  float* mb;               // [W] block maxima
+  double* part;            // [G][W][P] block sums
+  double c;                // 2.38 / sqrt(S)
+  uint32_t n, per, W, G;
+};
+struct GroupMomentsScratch {
+  float* mb;
+  double* part;
+};
+bool group_moments_carve(Carver& cv, uint32_t W, uint64_t G, uint32_t P, GroupMomentsScratch* out) {
+  out->mb = cv.take<float>(W);
+  out->part = cv.take<double>((size_t)G * W * P);
+  return cv.ok;
+}
+bool group_moments_shape_ok(uint64_t n, uint64_t G, int32_t S) {
+  return n >= 1 && n <= (uint64_t)kBlock * GJX_GROUP_MOMENTS_MAX_BLOCK && G >= 1 && G < GJX_GROUP_MAX_GROUPS && S >= 1 && S <= GJX_GROUP_MAX_SITES;
+}
+template <int S>
+__global__ __launch_bounds__(kBlock) void k_group_moments(GroupMomentsArgs a) {
+  constexpr int P = 1 + S + S * (S + 1) / 2;
+  extern __shared__ float sh_e[];  // [per]: the block's weights
+  __shared__ double sh_w[4][P];    // the four waves' sums
+  __shared__ float sh_red[4];
+  const uint32_t t = threadIdx.x;
+  const float ninf = -__builtin_inff();
+  if (blockIdx.x == 0 && blockIdx.y == 0 && t == 0) a.n_degenerate[0] = 0u;  // (launch 2 adds to it: stream order)
+  for (uint32_t b = blockIdx.x; b < a.W; b += gridDim.x) {
+    const uint64_t lo64 = (uint64_t)b * a.per;
+    const uint32_t lo = lo64 < a.n ? (uint32_t)lo64 : a.n;
+    const uint32_t hi = (uint64_t)lo + a.per < a.n ? lo + a.per : a.n;
+    const uint32_t len = hi - lo;  // <= per: the LDS array's length
+    float mb = 0.0f;
+    if (a.lw) {
+      float mx = ninf;
+      for (uint32_t k = t; k < len; k += kBlock) {
+        const float v = a.lw[lo + k];
+        mx = v > mx ? v : mx;  // (a NaN is skipped)
+      }
+      mb = block_max(mx, sh_red);
+    }
+    __syncthreads();  // (the last block's readers of sh_e are done)
+    for (uint32_t k = t; k < len; k += kBlock) {
+      float e = 1.0f;
+      if (a.lw) {
+        const float v = a.lw[lo + k];
+        e = v > ninf ? m_exp(v - mb) : 0.0f;  // -inf, NaN: no contribution
+      }
+      sh_e[k] = e;
+    }
+    if (blockIdx.y == 0 && t == 0) a.mb[b] = mb;
+    __syncthreads();
+    for (uint32_t g = blockIdx.y; g < a.G; g += gridDim.y) {
+      const size_t row = (size_t)g * a.n;
+      double z0[S], acc[P];
+#pragma unroll
+      for (int s = 0; s < S; ++s) z0[s] = (double)a.z[s][row];
+#pragma unroll
+      for (int p = 0; p < P; ++p) acc[p] = 0.0;
+      for (uint32_t k = t; k < len; k += kBlock) {
+        float zv[S];
+#pragma unroll
+        for (int s = 0; s < S; ++s) zv[s] = a.z[s][row + lo + k];  // (the S loads in flight together)
+        const double e = (double)sh_e[k];
+        if (e > 0.0) {
+          acc[0] += e;
+          double ed[S], d[S];
+#pragma unroll
+          for (int s = 0; s < S; ++s) {
+            d[s] = (double)zv[s] - z0[s];
+            ed[s] = e * d[s];
+            acc[1 + s] += ed[s];
+#pragma unroll
+            for (int j = 0; j <= s; ++j) acc[1 + S + s * (s + 1) / 2 + j] += ed[s] * d[j];
+          }
+        }
+      }
+#pragma unroll
+      for (int p = 0; p < P; ++p) {
+#pragma unroll
+        for (int m = 1; m < kWave; m <<= 1) acc[p] += __shfl_xor(acc[p], m, kWave);
+      }
+      __syncthreads();  // (the last group's readers of sh_w are done)
+      if ((t & 63u) == 0u) {
+#pragma unroll
+        for (int p = 0; p < P; ++p) sh_w[t >> 6][p] = acc[p];
+      }
+      __syncthreads();
+      if (t < (uint32_t)P) a.part[((size_t)g * a.W + b) * P + t] = (sh_w[0][t] + sh_w[1][t]) + (sh_w[2][t] + sh_w[3][t]);
+    }
+  }
+}
+template <int S>
+__global__ __launch_bounds__(kBlock) void k_group_factor(GroupMomentsArgs a) {
+  constexpr int P = 1 + S + S * (S + 1) / 2, TRI = S * (S + 1) / 2;
+  const uint32_t g = blockIdx.x * kBlock + threadIdx.x;
+  if (g >= a.G) return;
+  const float ninf = -__builtin_inff();
+  float M = ninf;
+  for (uint32_t b = 0; b < a.W; ++b) {
+    const float v = a.mb[b];
+    M = v > M ? v : M;
+  }
+  double T[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) T[p] = 0.0;
+  const double* part = a.part + (size_t)g * a.W * P;
+  for (uint32_t b = 0; b < a.W; ++b) {  // in index order
+    const float v = a.mb[b];
+    const double f = v > ninf ? exp((double)v - (double)M) : 0.0;
+#pragma unroll
+    for (int p = 0; p < P; ++p) T[p] += f * part[(size_t)b * P + p];
+  }
+  float* fo = a.factor + (size_t)g * TRI;
+  if (!(T[0] > 0.0)) {  // no entry above -inf
+#pragma unroll
+    for (int k = 0; k < TRI; ++k) fo[k] = 0.0f;
+#pragma unroll
+    for (int s = 0; s < S; ++s) a.scales[(size_t)s * a.G + g] = 0.0f;
+    atomicAdd(a.n_degenerate, (uint32_t)S);
+    return;
+  }
+  double m[S], C[TRI], Gm[TRI];
+#pragma unroll
+  for (int s = 0; s < S; ++s) m[s] = T[1 + s] / T[0];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+#pragma unroll
+    for (int j = 0; j <= s; ++j) C[s * (s + 1) / 2 + j] = T[1 + S + s * (s + 1) / 2 + j] / T[0] - m[s] * m[j];
+  }
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    const double v = C[s * (s + 1) / 2 + s];
+    a.scales[(size_t)s * a.G + g] = v > 0.0 ? (float)(a.c * sqrt(v)) : 0.0f;
+  }
+  uint32_t ndeg = 0;
+#pragma unroll
+  for (int l = 0; l < S; ++l) {  // the Cholesky rule of include/gjx_temper_cov.h, operation by operation (never contracted)
+    const int rl = l * (l + 1) / 2;
+#pragma unroll
+    for (int j = 0; j < l; ++j) {
+      const int rj = j * (j + 1) / 2;
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < j; ++k) s += Gm[rl + k] * Gm[rj + k];
+      const double d = Gm[rj + j];
+      Gm[rl + j] = d == 0.0 ? 0.0 : (C[rl + j] - s) / d;
+    }
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < l; ++k) s += Gm[rl + k] * Gm[rl + k];
+    const double Sll = C[rl + l], pv = Sll - s;
+    if (!(pv > 0x1p-40 * Sll)) {
+#pragma unroll
+      for (int j = 0; j < l; ++j) Gm[rl + j] = 0.0;
+      Gm[rl + l] = Sll > 0.0 && Sll < __builtin_inf() ? sqrt(Sll) : 0.0;
+      ++ndeg;
+    } else {
+      Gm[rl + l] = sqrt(pv);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < TRI; ++k) fo[k] = (float)(a.c * Gm[k]);
+  if (ndeg) atomicAdd(a.n_degenerate, ndeg);
+}
+template <int S>
+void group_moments_launch(const GroupMomentsArgs& A, dim3 grid, hipStream_t st) {
+  k_group_moments<S><<<grid, kBlock, (size_t)A.per * sizeof(float), st>>>(A);
+  k_group_factor<S><<<(A.G + kBlock - 1) / kBlock, kBlock, 0, st>>>(A);
+}
+
 // ---- pointwise predictive densities over a plated plan (include/gjx_pointwise.h) -----------------------------------------
 constexpr uint64_t kPointwiseWorkgroups = 2048;  // tiles of 256 rows x chunks of particles: about this many, whatever D is
 // the second launch: one lane per row folds the chunks' partials in chunk order (gjx_device.hpp pointwise_fold)
@@ -5639,12 +5826,15 @@ int gjx_temper_plan_compile_check(const gjx_temper_plan* p, int impl) {
 }  // extern "C"
 namespace {
 // gjx_temper_move (factor == nullptr, cov == false) and gjx_temper_move_cov (include/gjx_temper_cov.h: scales are not read)
-// and gjx_temper_move_grouped (include/gjx_group.h: gio, whose `t` is io)
-int temper_move(gjx_temper_plan* p, const gjx_temper_io* io, bool cov, const float* factor, gjx_stream s, const gjx_group_io* gio = nullptr) {
-  if (!p || !io || (p->n_grouped > 0) != (gio != nullptr) || (cov && !factor) || io->n < 1 || io->n >= (1ull << 31) || (io->impl != 0 && io->impl != 1) || (io->impl == 0 && io->key_lane != 0) ||
+// and gjx_temper_move_grouped (include/gjx_group.h: gio, whose `t` is io) and gjx_temper_move_grouped_cov
+// (include/gjx_group_cov.h: `block`, with `factor` the scalars' triangle or nullptr and factor_z the groups'; neither scales
+// are read where a factor stands in)
+int temper_move(gjx_temper_plan* p, const gjx_temper_io* io, bool cov, const float* factor, gjx_stream s, const gjx_group_io* gio = nullptr,
+                bool block = false, const float* factor_z = nullptr) {
+  if (!p || !io || (p->n_grouped > 0) != (gio != nullptr) || (cov && !factor) || (block && (!gio || (io->n_moves > 0 && !factor_z))) || io->n < 1 || io->n >= (1ull << 31) || (io->impl != 0 && io->impl != 1) || (io->impl == 0 && io->key_lane != 0) ||
       io->n_moves < 0 || io->n_moves > GJX_TEMPER_MAX_MOVES)
     return GJX_ERR_INVALID;
-  if (!io->lp_out || !io->ll_out || (!io->recompute && (!io->lp_in || !io->ll_in)) || (!cov && io->n_moves > 0 && !io->scales))
+  if (!io->lp_out || !io->ll_out || (!io->recompute && (!io->lp_in || !io->ll_in)) || (!cov && !(block && factor) && io->n_moves > 0 && !io->scales))
     return GJX_ERR_INVALID;
   if (io->n_input_cols < 0 || io->n_input_cols > 16 || io->n_input_cols <= p->max_input || (io->n_input_cols && !io->input_cols) ||
       p->n_params <= p->max_param || (p->plated && !p->has_data))
@@ -5668,14 +5858,14 @@ int temper_move(gjx_temper_plan* p, const gjx_temper_io* io, bool cov, const flo
   if (gio) {
     if (!p->group_off || (gio->init && io->impl == 0 && gio->init_key_lane != 0)) return GJX_ERR_INVALID;
     for (int g = 0; g < p->n_grouped; ++g) {
-      if (!gio->z_out[g] || (!gio->init && !gio->z_in[g]) || (io->n_moves > 0 && !gio->z_scales[g])) return GJX_ERR_INVALID;
+      if (!gio->z_out[g] || (!gio->init && !gio->z_in[g]) || (!block && io->n_moves > 0 && !gio->z_scales[g])) return GJX_ERR_INVALID;
       ga.z_in[g] = gio->z_in[g]; ga.z_out[g] = gio->z_out[g]; ga.z_scales[g] = gio->z_scales[g];
     }
     ga.off = p->group_off; ga.n_accept_z = gio->n_accept_z; ga.G = p->n_groups; ga.init = gio->init ? 1u : 0u;
     ga.init_key = Key{gio->init_key[0], gio->init_key[1], (uint32_t)gio->init_key_lane, (uint32_t)(gio->init_key_lane >> 32)};
   }
   if (!gjx_jit::enabled()) return GJX_ERR_UNSUPPORTED;  // a generated kernel only
-  gjx_jit::CompiledKernel* k = temper_compiled(p, gio ? kTemperGroupedMove : cov ? kTemperCovMove : kTemperMove, io->impl);
+  gjx_jit::CompiledKernel* k = temper_compiled(p, block ? kTemperGroupedCovMove : gio ? kTemperGroupedMove : cov ? kTemperCovMove : kTemperMove, io->impl);
   if (!k) return GJX_ERR_JIT;
   A.lp_in = io->lp_in; A.ll_in = io->ll_in; A.lp_out = io->lp_out; A.ll_out = io->ll_out;
   A.anc = io->ancestors; A.n_accept = io->n_accept;
@@ -5692,7 +5882,7 @@ int temper_move(gjx_temper_plan* p, const gjx_temper_io* io, bool cov, const flo
   PlateData pd = p->data;
   void* args[] = {&A, &cols, &prm, &tabs, &pd};  // (the kernel of a plan without plated sites takes the first four)
   void* cov_args[] = {&A, &cols, &prm, &tabs, &factor, &pd};
-  void* group_args[] = {&A, &cols, &prm, &tabs, &pd, &ga};
+  void* group_args[] = {&A, &cols, &prm, &tabs, &pd, &ga, &factor, &factor_z};  // (the diagonal grouped kernel takes the first six)
   return launch_generated(k->fn, grid, 1, kBlock, s, gio ? group_args : cov ? cov_args : args);
 }
 
@@ -5849,6 +6039,59 @@ int gjx_temper_cov_source(const gjx_temper_plan* p, int impl, char* buf, size_t 
   return temper_source_out(p, kTemperCovMove, impl, buf, buf_len, needed);
 }
 int gjx_temper_cov_compile_check(const gjx_temper_plan* p, int impl) { return temper_compile_check(p, kTemperCovMove, impl); }
+
+// ---- include/gjx_group_cov.h: per-group covariance proposals for grouped latents ---------------------------------------------
+int gjx_group_cov_version(int* major, int* minor) {
+  return version_out(major, minor, GJX_GROUP_COV_VERSION_MAJOR, GJX_GROUP_COV_VERSION_MINOR);
+}
+size_t gjx_group_moments_workspace_bytes(uint64_t n, uint32_t G, int32_t S) {
+  if (!group_moments_shape_ok(n, G, S)) return 0;
+  Carver cv{nullptr, ~(size_t)0};
+  GroupMomentsScratch sc;
+  (void)group_moments_carve(cv, gjx_temper_ladder_blocks(n), G, (uint32_t)(1 + S + S * (S + 1) / 2), &sc);
+  return ~(size_t)0 - cv.left;
+}
+int gjx_group_moments(const gjx_group_moments_io* io, gjx_stream s) {
+  if (!io || !group_moments_shape_ok(io->n, io->G, io->S) || !io->factor || !io->scales || !io->n_degenerate || ((uintptr_t)io->ws & 7) != 0)
+    return GJX_ERR_INVALID;
+  GroupMomentsArgs A;
+  memset(&A, 0, sizeof A);
+  for (int q = 0; q < io->S; ++q) {
+    if (!io->z[q]) return GJX_ERR_INVALID;
+    A.z[q] = io->z[q];
+  }
+  if (!io->ws || io->ws_bytes < gjx_group_moments_workspace_bytes(io->n, io->G, io->S)) return GJX_ERR_WORKSPACE;
+  const uint32_t W = gjx_temper_ladder_blocks(io->n), P = (uint32_t)(1 + io->S + io->S * (io->S + 1) / 2);
+  Carver cv{(char*)io->ws, io->ws_bytes};
+  GroupMomentsScratch sc;
+  if (!group_moments_carve(cv, W, io->G, P, &sc)) return GJX_ERR_WORKSPACE;
+  A.lw = io->lw; A.factor = io->factor; A.scales = io->scales; A.n_degenerate = io->n_degenerate;
+  A.mb = sc.mb; A.part = sc.part;
+  A.c = 2.38 / sqrt((double)io->S);
+  A.n = (uint32_t)io->n;
+  A.per = (uint32_t)((io->n + W - 1) / W);
+  A.W = W; A.G = io->G;
+  // blocks x group ranges: every block of its own when the knob allows, then as many ranges as fill the device
+  uint32_t gx = W, gy = (uint32_t)((kGroupMomentsWorkgroups + W - 1) / W);
+  if (io->max_workgroups && gx > io->max_workgroups) gx = io->max_workgroups;
+  if (io->max_workgroups && gy > io->max_workgroups / gx) gy = io->max_workgroups / gx;  // (>= 1: gx <= max_workgroups)
+  if (gy > io->G) gy = io->G;
+  const dim3 grid(gx, gy, 1);
+  switch (io->S) {
+    case 1: group_moments_launch<1>(A, grid, S(s)); break;
+    case 2: group_moments_launch<2>(A, grid, S(s)); break;
+    case 3: group_moments_launch<3>(A, grid, S(s)); break;
+    default: group_moments_launch<4>(A, grid, S(s)); break;
+  }
+  return launch_status();
+}
+int gjx_temper_move_grouped_cov(gjx_temper_plan* p, const gjx_group_io* io, const float* factor_x, const float* factor_z, gjx_stream s) {
+  return io ? temper_move(p, &io->t, false, factor_x, s, io, true, factor_z) : GJX_ERR_INVALID;
+}
+int gjx_group_cov_source(const gjx_temper_plan* p, int impl, char* buf, size_t buf_len, size_t* needed) {
+  return temper_source_out(p, kTemperGroupedCovMove, impl, buf, buf_len, needed);
+}
+int gjx_group_cov_compile_check(const gjx_temper_plan* p, int impl) { return temper_compile_check(p, kTemperGroupedCovMove, impl); }
 
 int gjx_pointwise_version(int* major, int* minor) {
   return version_out(major, minor, GJX_POINTWISE_VERSION_MAJOR, GJX_POINTWISE_VERSION_MINOR);

@@ -1845,12 +1845,19 @@ struct GenTemper {
 //              themselves) under the key split_at(fold_in(init_key, g), i).
 // The key folds of a group (fold_in(fold_in(k_r, 2), g) and its two children) are wave-uniform: scalar-side cipher blocks.
 // The grouped columns, offsets and scales are one more kernel argument (GroupArgs), of grouped plans only.
+//   block      the SECOND kernel of a grouped plan (include/gjx_group_cov.h; `block`): gjx_temper_move_grouped_cov_kernel takes two
+//              more pointers after GroupArgs.  The group phase proposes z' = z + Fg eps through the group's packed S x S triangle
+//              (row g of factor_z: at most 10 floats, wave-uniform, scalar loads off a pointer advanced on the scalar side);
+//              the scalar phase proposes through factor_x as GenTemper's cov kernel does when that pointer is given (a
+//              wave-uniform branch), through a.scales otherwise.  It shares every device function above; the source of the
+//              diagonal kernel does not change with it.
 template <class CSiteT, class CArgT>
 struct GenTemperGrouped {
   std::ostringstream o;
   int impl;
   const CSiteT* sites;
   int n_sites;
+  bool block = false;  // the block move (include/gjx_group_cov.h): gjx_temper_move_grouped_cov_kernel
 
   std::string run() {
     using Table = TemperTable<CSiteT, CArgT>;
@@ -1981,10 +1988,13 @@ struct GenTemperGrouped {
       o << "}\n";
     }
     // -- the kernel ----------------------------------------------------------------------------------------------------------------
-    o << "extern \"C\" __global__ __launch_bounds__(256) void gjx_temper_move_grouped_kernel(TemperArgs a, RunCols cols, PlanParams prm, "
-         "PlanTables tabs, PlateData pd, GroupArgs ga) {\n";
+    if (block) o << "typedef const __attribute__((address_space(4))) float* FactorPtr;\n";
+    o << "extern \"C\" __global__ __launch_bounds__(256) void " << (block ? "gjx_temper_move_grouped_cov_kernel" : "gjx_temper_move_grouped_kernel")
+      << "(TemperArgs a, RunCols cols, PlanParams prm, "
+         "PlanTables tabs, PlateData pd, GroupArgs ga" << (block ? ", const float* factor_x, const float* factor_z" : "") << ") {\n";
     o << "  const uint32_t n = a.n;\n  const GroupOff off = (GroupOff)ga.off;\n";
-    for (int s = 0; s < S; ++s) o << "  const PlateCol zs" << s << " = (PlateCol)ga.z_scales[" << s << "];\n";
+    for (int s = 0; !block && s < S; ++s) o << "  const PlateCol zs" << s << " = (PlateCol)ga.z_scales[" << s << "];\n";
+    if (block) o << "  FactorPtr F = (FactorPtr)factor_x;\n  const FactorPtr FZ = (FactorPtr)factor_z;\n";
     o << "  for (uint64_t i64 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i64 < n; i64 += (uint64_t)gridDim.x * blockDim.x) {\n";
     o << "    const uint32_t i = (uint32_t)i64;\n";
     o << "    uint32_t an = a.anc ? (uint32_t)a.anc[i] : i;\n    an = an < n ? an : n - 1u;\n";
@@ -2004,7 +2014,29 @@ struct GenTemperGrouped {
     o << "      const Key kr = fold_in<" << I << ">(a.key, r);\n";
     o << "      const Key pk = split_at<" << I << ">(fold_in<" << I << ">(kr, 0u), (uint64_t)i);\n";
     o << "      const Key ak = split_at<" << I << ">(fold_in<" << I << ">(kr, 1u), (uint64_t)i);\n";
-    for (int l = 0; l < L; ++l) {
+    // the block move: the L draws once (+0 + z, as GenTemper's cov kernel forms them), then either row l of factor_x against
+    // them or the diagonal rule — a wave-uniform branch on the pointer; the empty asm keeps the loads of F inside the sweep
+    if (block) {
+      for (int l = 0; l < L; ++l) {
+        const uint32_t fold = impl == 0 ? (uint32_t)(l + 1) : (uint32_t)l;
+        o << "      const float d" << l << " = site_normal<" << I << ">(Stream<" << I << ">(pk, true, " << fold << "u));\n";
+      }
+      for (int l = 0; l < L; ++l) o << "      float y" << l << ";\n";
+      o << "      if (F) {\n        asm volatile(\"\" : \"+s\"(F));\n";
+      for (int l = 0; l < L; ++l) o << "        const float e" << l << " = 0.0f + d" << l << ";\n";
+      for (int l = 0; l < L; ++l) {
+        o << "        float t" << l << " = F[" << l * (l + 1) / 2 << "] * e0;\n";
+        for (int j = 1; j <= l; ++j) o << "        t" << l << " = t" << l << " + F[" << l * (l + 1) / 2 + j << "] * e" << j << ";\n";
+        o << "        y" << l << " = x" << l << " + t" << l << ";\n";
+      }
+      o << "      } else {\n";
+      for (int l = 0; l < L; ++l) {
+        o << "        const float t" << l << " = a.scales[" << l << "] * d" << l << ";\n";
+        o << "        y" << l << " = x" << l << " + t" << l << ";\n";
+      }
+      o << "      }\n";
+    }
+    for (int l = 0; !block && l < L; ++l) {
       const uint32_t fold = impl == 0 ? (uint32_t)(l + 1) : (uint32_t)l;
       o << "      const float t" << l << " = a.scales[" << l << "] * site_normal<" << I << ">(Stream<" << I << ">(pk, true, " << fold << "u));\n";
       o << "      const float y" << l << " = x" << l << " + t" << l << ";\n";
@@ -2027,7 +2059,22 @@ struct GenTemperGrouped {
     o << "        const Key gak = split_at<" << I << ">(fold_in<" << I << ">(kg, 1u), (uint64_t)i);\n";
     o << bounds("        ");
     o << "        const size_t zi = (size_t)g * n + i;\n";
-    for (int s = 0; s < S; ++s) {
+    // the block move: the group's packed triangle off FZ + g * S (S + 1) / 2 (scalar loads: g is wave-uniform), the S draws
+    // (+0 + z), then row s against them, every product and sum rounded once
+    if (block) {
+      o << "        const FactorPtr Fg = FZ + (size_t)g * " << S * (S + 1) / 2 << "u;\n";
+      for (int s = 0; s < S; ++s) {
+        const uint32_t fold = impl == 0 ? (uint32_t)(s + 1) : (uint32_t)s;
+        o << "        const float zc" << s << " = ga.z_out[" << s << "][zi];\n";
+        o << "        const float ze" << s << " = 0.0f + site_normal<" << I << ">(Stream<" << I << ">(gpk, true, " << fold << "u));\n";
+      }
+      for (int s = 0; s < S; ++s) {
+        o << "        float zw" << s << " = Fg[" << s * (s + 1) / 2 << "] * ze0;\n";
+        for (int j = 1; j <= s; ++j) o << "        zw" << s << " = zw" << s << " + Fg[" << s * (s + 1) / 2 + j << "] * ze" << j << ";\n";
+        o << "        const float zy" << s << " = zc" << s << " + zw" << s << ";\n";
+      }
+    }
+    for (int s = 0; !block && s < S; ++s) {
       const uint32_t fold = impl == 0 ? (uint32_t)(s + 1) : (uint32_t)s;
       o << "        const float zc" << s << " = ga.z_out[" << s << "][zi];\n";
       o << "        const float zw" << s << " = zs" << s << "[g] * site_normal<" << I << ">(Stream<" << I << ">(gpk, true, " << fold << "u));\n";

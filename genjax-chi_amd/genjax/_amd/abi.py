@@ -132,6 +132,10 @@ class TemperCovUnavailable(HeaderUnavailable):
     header, why = "gjx_temper_cov.h", "the population moments and the covariance move run as HIP kernels only"
 
 
+class GroupCovUnavailable(HeaderUnavailable):
+    header, why = "gjx_group_cov.h", "the per-group moments and the block move of grouped latents run as HIP kernels only"
+
+
 class Keys(C.Structure):
     _fields_ = [
         ("impl", C.c_int32),
@@ -884,6 +888,38 @@ PSIS_UNITS_PROTOTYPES = {
 }
 PSIS_UNITS_ABI_VERSION = (0, 1)
 
+# include/gjx_group_cov.h: an EIGHTEENTH header, same arrangement — per-group covariance proposals for grouped latents: the
+# two-launch moments of every group's components with one proposal factor per group, and the grouped move through them.
+
+
+class GroupMomentsIO(C.Structure):
+    """gjx_group_moments_io (include/gjx_group_cov.h)."""
+    _fields_ = [
+        ("n", C.c_uint64),
+        ("G", C.c_uint32),
+        ("S", C.c_int32),
+        ("z", C.c_void_p * GROUP_MAX_SITES),
+        ("lw", C.c_void_p),
+        ("factor", C.c_void_p),
+        ("scales", C.c_void_p),
+        ("n_degenerate", C.c_void_p),
+        ("ws", C.c_void_p),
+        ("ws_bytes", C.c_size_t),
+        ("max_workgroups", C.c_uint32),
+    ]
+
+
+GROUP_MOMENTS_MAX_N = 256 * 16000  # 256 * GJX_GROUP_MOMENTS_MAX_BLOCK
+GROUP_COV_PROTOTYPES = {
+    "gjx_group_cov_version": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gjx_group_moments_workspace_bytes": (C.c_size_t, [C.c_uint64, C.c_uint32, C.c_int32]),
+    "gjx_group_moments": (C.c_int, [C.POINTER(GroupMomentsIO), _P]),
+    "gjx_temper_move_grouped_cov": (C.c_int, [_P, C.POINTER(GroupIO), _P, _P, _P]),
+    "gjx_group_cov_source": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gjx_group_cov_compile_check": (C.c_int, [_P, C.c_int]),
+}
+GROUP_COV_ABI_VERSION = (0, 1)
+
 # The optional headers, in the order they are bound: every one is exported by libgjx_hip.so only and bound if present.
 class Header(collections.namedtuple("Header", "key header version_fn prototypes version_name unavailable")):
     @property
@@ -929,12 +965,15 @@ MOVE_HEADERS = {h.key: h for h in (
 )}
 
 
-# Headers that add a reduction over the plans and io structs of the check headers (gjx_psis_units.h).  A table of its own, and
-# kept out of all_optional_headers(), for the same reason once more: the suites of the earlier headers pin that tuple's length
-# and its last entry.  bound_headers() is what a library is bound with.
+# Headers that add a reduction over the plans and io structs of the check headers (gjx_psis_units.h), or a move over the io
+# struct of a PLAN_HEADERS header (gjx_group_cov.h).  A table of its own, and kept out of all_optional_headers(), for the same
+# reason once more: the suites of the earlier headers pin that tuple's length and its last entry, and the contents of
+# MOVE_HEADERS.  bound_headers() is what a library is bound with.
 CHECK_HEADERS = {h.key: h for h in (
     Header("psis_units", "gjx_psis_units.h", "gjx_psis_units_version", PSIS_UNITS_PROTOTYPES, "PSIS_UNITS_ABI_VERSION",
            PsisUnitsUnavailable),
+    Header("group_cov", "gjx_group_cov.h", "gjx_group_cov_version", GROUP_COV_PROTOTYPES, "GROUP_COV_ABI_VERSION",
+           GroupCovUnavailable),
 )}
 
 
@@ -964,6 +1003,7 @@ _NO_STATUS = {
     "gjx_psis_units_workspace_bytes",
     "gjx_predictive_workspace_bytes",
     "gjx_temper_moments_workspace_bytes",
+    "gjx_group_moments_workspace_bytes",
     "gjx_backmove_workspace_bytes",
     "gjx_backsim_workspace_bytes",
     "gjx_paths_workspace_bytes",

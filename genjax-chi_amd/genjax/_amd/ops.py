@@ -644,7 +644,27 @@ class Ops:
         `z_scales`: float32 [S, G] on the device (or S tensors [G]) — handed over as pointers, no host read.
         -> (x [L columns], z [S tensors [G, n]], lp, ll, n_accept int32[n] or None, n_accept_z int32[n] or None)."""
         self.lib.require("group", "gjx_temper_move_grouped")
-        what, S, G, n = "temper_move_grouped", plan.n_grouped, plan.n_groups, x[0].numel()
+        return self._temper_move_grouped("temper_move_grouped", None, plan, key, x, z, lp, ll, beta, n_moves, scales, z_scales, ancestors,
+                                         recompute, init_key, want_accept, max_workgroups)
+
+    def temper_move_grouped_cov(self, plan: "TemperPlan", key, x: list, z, lp, ll, beta: float, n_moves: int, factor_z, factor_x=None,
+                                scales=None, *, ancestors=None, recompute: bool = False, init_key=None, want_accept: bool = True,
+                                max_workgroups: int = 0):
+        """gjx_temper_move_grouped_cov (include/gjx_group_cov.h): ONE launch — temper_move_grouped with block proposals.
+        `factor_z`: float32 [G, S (S + 1) / 2] on the device, one packed lower triangle per group (what temper_group_moments
+        returns; None with n_moves == 0); `factor_x`: float32 [L (L + 1) / 2], the scalars' packed triangle, or None for the
+        diagonal walk over the scalars with `scales`.  Both are handed over as pointers: no host read.
+        -> what temper_move_grouped returns."""
+        self.lib.require("group_cov", "gjx_temper_move_grouped_cov")
+        S, G, L = plan.n_grouped, plan.n_groups, plan.n_latents
+        fz = None if factor_z is None else self._chk(factor_z, torch.float32, G * S * (S + 1) // 2, "factor_z")
+        fx = None if factor_x is None else self._chk(factor_x, torch.float32, L * (L + 1) // 2, "factor_x")
+        return self._temper_move_grouped("temper_move_grouped_cov", (fx, fz), plan, key, x, z, lp, ll, beta, n_moves, scales, None, ancestors,
+                                         recompute, init_key, want_accept, max_workgroups)
+
+    def _temper_move_grouped(self, what, factors, plan, key, x, z, lp, ll, beta, n_moves, scales, z_scales, ancestors, recompute, init_key,
+                             want_accept, max_workgroups):
+        S, G, n = plan.n_grouped, plan.n_groups, x[0].numel()
         if not S or not G:
             raise ValueError(f"{what}: a plan with grouped sites and set_groups() expected")
         if (z is None) == (init_key is None):
@@ -666,7 +686,10 @@ class Ops:
         accz = self.empty(n, torch.int32) if want_accept else None
         if accz is not None:
             io.n_accept_z = accz.data_ptr()
-        self.lib.call("gjx_temper_move_grouped", plan.handle, C.byref(io), self.stream())
+        if factors is None:
+            self.lib.call("gjx_temper_move_grouped", plan.handle, C.byref(io), self.stream())
+        else:
+            self.lib.call("gjx_temper_move_grouped_cov", plan.handle, C.byref(io), factors[0], factors[1], self.stream())
         L = plan.n_latents
         return list(block[:L]), list(z_out.unbind(0)), block[L], block[L + 1], acc, accz
 
@@ -751,6 +774,39 @@ class Ops:
         io.ws, io.ws_bytes, io.max_workgroups = ws.data_ptr(), ws.numel(), int(max_workgroups)
         self.lib.call("gjx_temper_moments", C.byref(io), self.stream())
         return moments, f32[:tri], f32[tri:], ndeg
+
+    def temper_group_moments_workspace(self, n: int, G: int, S: int) -> torch.Tensor:
+        """A workspace of gjx_group_moments for populations of n with S grouped columns of G groups (no word of it has to be
+        zero; calls that share it must be stream-ordered)."""
+        self.lib.require("group_cov", "gjx_group_moments_workspace_bytes")
+        nb = int(self.lib.call("gjx_group_moments_workspace_bytes", int(n), int(G), int(S)))
+        if nb == 0:
+            raise ValueError(f"temper_group_moments: n = {n} (1 .. {abi.GROUP_MOMENTS_MAX_N}), G = {G} or S = {S} out of range")
+        return torch.empty(nb, dtype=torch.uint8, device=self._alloc_device)
+
+    def temper_group_moments(self, z: list, lw: torch.Tensor | None, ws: torch.Tensor | None = None, *, max_workgroups: int = 0):
+        """gjx_group_moments (include/gjx_group_cov.h): TWO launches over the S grouped columns `z` (float32 [G, n] each) and the
+        log-weights `lw` (None: equal weights) -> (factor float32 [G, S (S + 1) / 2]: per group, 2.38 / sqrt(S) times the
+        Cholesky factor of the weighted covariance of its S components, packed by rows; scales float32 [S, G]: the diagonal
+        rule; n_degenerate int32[1]: fallback rows summed over the groups) — all on the device."""
+        self.lib.require("group_cov", "gjx_group_moments")
+        S = len(z)
+        if not 1 <= S <= abi.GROUP_MAX_SITES or z[0].dim() != 2:
+            raise ValueError(f"temper_group_moments: 1 .. {abi.GROUP_MAX_SITES} columns [G, n] expected")
+        G, n = z[0].shape
+        io = abi.GroupMomentsIO()
+        io.n, io.G, io.S = n, G, S
+        for s in range(S):
+            io.z[s] = self._chk(z[s], torch.float32, G * n, f"z[{s}]").value
+        if lw is not None:
+            io.lw = self._chk(lw, torch.float32, n, "lw").value
+        ws = self.temper_group_moments_workspace(n, G, S) if ws is None else ws
+        tri = S * (S + 1) // 2
+        factor, scales, ndeg = self.empty((G, tri), torch.float32), self.empty((S, G), torch.float32), self.empty(1, torch.int32)
+        io.factor, io.scales, io.n_degenerate = factor.data_ptr(), scales.data_ptr(), ndeg.data_ptr()
+        io.ws, io.ws_bytes, io.max_workgroups = ws.data_ptr(), ws.numel(), int(max_workgroups)
+        self.lib.call("gjx_group_moments", C.byref(io), self.stream())
+        return factor, scales, ndeg
 
     def temper_ladder_workspace(self, n: int) -> torch.Tensor:
         """A zeroed workspace of gjx_temper_ess_ladder for populations of n and any ladder length (its ticket stays zero
@@ -1437,6 +1493,15 @@ class TemperPlan(PlanHandle):
     def cov_source(self, impl: int) -> str:
         self.ops.lib.require("temper_cov", "gjx_temper_cov_source")
         return self._source("gjx_temper_cov_source", impl)
+
+    def group_cov_compile_check(self, impl: int) -> int:
+        """gjx_group_cov_compile_check (include/gjx_group_cov.h): the block move kernel of a grouped plan; the status, not raised."""
+        self.ops.lib.require("group_cov", "gjx_group_cov_compile_check")
+        return self.ops.lib._gjx_group_cov_compile_check(self.handle, impl)
+
+    def group_cov_source(self, impl: int) -> str:
+        self.ops.lib.require("group_cov", "gjx_group_cov_source")
+        return self._source("gjx_group_cov_source", impl)
 
 
 class ScanPlan(PlanHandle):

@@ -511,7 +511,10 @@ class TemperedResult:
     """What `TemperedSMC.run` returns.  `choices`: the final, equally weighted population's latent columns as a ChoiceMap;
     `lp`, `ll`: its log-prior and log-likelihood columns (f32[n], on the device).  Under `proposal="covariance"`, `factor`:
     the last stage's proposal factor, f32 [L, L], lower-triangular, on the device; `n_degenerate`: per stage, the latents
-    whose row of the factor fell back to the diagonal rule (include/gjx_temper_cov.h).  Both None on the diagonal route."""
+    whose row of the factor fell back to the diagonal rule (include/gjx_temper_cov.h).  Both None on the diagonal route.
+    Under `proposal="block"` (a plan with grouped latents, include/gjx_group_cov.h) `factor` and `n_degenerate` are the
+    scalars', `group_factor` is the last stage's per-group factors, f32 [G, S, S], lower-triangular, on the device, and
+    `n_degenerate_groups` the fallback rows per stage summed over the groups."""
 
     def __init__(self, log_marginal_likelihood, betas, ess, accept_rate, choices, lp, ll, columns, factor=None, n_degenerate=None):
         self.log_marginal_likelihood, self.betas, self.ess, self.accept_rate = log_marginal_likelihood, betas, ess, accept_rate
@@ -520,6 +523,7 @@ class TemperedResult:
         # a plan with grouped latents (include/gjx_group.h): per stage, the accepted group moves over n * n_moves * G; the S
         # grouped columns f32 [G, n] (also in `choices`, at their addresses).  None otherwise
         self.accept_rate_groups, self.group_columns = None, None
+        self.group_factor, self.n_degenerate_groups = None, None  # proposal="block"
 
     def __repr__(self):
         return (f"TemperedResult(log_marginal_likelihood={self.log_marginal_likelihood:.6f}, stages={len(self.betas) - 1}, "
@@ -742,7 +746,10 @@ class TemperedSMC(SMCAlgorithm):
     `scale`: one proposal scale per latent (a number for all) instead of 2.38 / sqrt(L) times the weighted population
     standard deviation; `proposal`: "diagonal" (that random walk, one latent at a time) or "covariance" — x' = x + F eps with
     F = 2.38 / sqrt(L) times the Cholesky factor of the weighted population covariance, built on the device by one launch
-    (include/gjx_temper_cov.h): the proposal for a posterior whose latents are correlated.
+    (include/gjx_temper_cov.h): the proposal for a posterior whose latents are correlated; or "block", for a plan with grouped
+    latents (`dist.repeat`) only — block-diagonal: that L x L factor for the scalars and one S x S factor per group over the
+    group's S components (include/gjx_group_cov.h), all built on the device from the weighted population before resampling.
+    "covariance" stays ONE factor over all latents and refuses a grouped plan, for which it would be (L + S G)^2.
 
     The adaptive schedule depends on the particles, so the estimate of Z is consistent but NOT exactly unbiased (Beskos,
     Jasra, Kantas & Thiery 2016); a fixed `betas=` keeps it unbiased.
@@ -750,7 +757,8 @@ class TemperedSMC(SMCAlgorithm):
     Host reads per adaptive stage: the two ladders' results and the proposal scales — three (two at the last stage, where
     the first ladder already reaches beta = 1; one fewer each with `scale=`; none with `betas=` and `scale=`) — and one at
     the end of the run for the accumulated normalising constants and accept counts.  Under `proposal="covariance"` the factor
-    never leaves the device: two per adaptive stage, none before the end of the run with `betas=`."""
+    never leaves the device: two per adaptive stage, none before the end of the run with `betas=`; `proposal="block"` likewise
+    (neither population_scales nor group_scales is called)."""
 
     def __init__(self, target: Target, n_particles: int, n_moves: int = 2, ess_target: float = 0.5, betas=None, scale=None,
                  proposal: str = "diagonal"):
@@ -771,10 +779,10 @@ class TemperedSMC(SMCAlgorithm):
                 raise ValueError("TemperedSMC: betas must increase strictly from above 0 to exactly 1")
             self.betas = b
         self.scale = scale
-        if proposal not in ("diagonal", "covariance"):
-            raise ValueError(f'TemperedSMC: proposal must be "diagonal" or "covariance", got {proposal!r}')
-        if proposal == "covariance" and scale is not None:
-            raise ValueError('TemperedSMC: scale= sets the diagonal proposal; it cannot be combined with proposal="covariance"')
+        if proposal not in ("diagonal", "covariance", "block"):
+            raise ValueError(f'TemperedSMC: proposal must be "diagonal", "covariance" or "block", got {proposal!r}')
+        if proposal != "diagonal" and scale is not None:
+            raise ValueError(f'TemperedSMC: scale= sets the diagonal proposal; it cannot be combined with proposal="{proposal}"')
         self.proposal = proposal
         self._st = None
 
@@ -793,15 +801,21 @@ class TemperedSMC(SMCAlgorithm):
         ops.lib.require("temper", "gjx_temper_plan_create")
         if self.proposal == "covariance":
             ops.lib.require("temper_cov", "gjx_temper_move_cov")
+        if self.proposal == "block":
+            ops.lib.require("temper_cov", "gjx_temper_moments")
+            ops.lib.require("group_cov", "gjx_temper_move_grouped_cov")
         tracer = lower(self.target, self.n_particles)
         latents = [m for m in tracer.meta if m["obs"] is None and not m.get("grouped")]
         if tracer.n_grouped:
             ops.lib.require("group", "gjx_temper_move_grouped")
             if self.proposal == "covariance":
                 self._refuse_grouped(tracer, 'proposal="covariance"')
+        elif self.proposal == "block":
+            raise ValueError('TemperedSMC: proposal="block" is one factor per group of a plan with grouped latents (dist.repeat); this '
+                             'target has none: use proposal="covariance"')
         tplan = ops.temper_plan_create(tracer.sites, keep=(tracer.keep, tracer))
         prior = prior_table(tracer) if tracer.data or any(s.dist in abi.COUNT_DISTS for s in tracer.sites) else None
-        st = self._st = dict(ops=ops, tracer=tracer, latents=latents, tplan=tplan, ws=None, prior=prior, ws_cov=None)
+        st = self._st = dict(ops=ops, tracer=tracer, latents=latents, tplan=tplan, ws=None, prior=prior, ws_cov=None, ws_block=None)
         return st
 
     @staticmethod
@@ -923,9 +937,13 @@ class TemperedSMC(SMCAlgorithm):
         fixed_scales = self._scales(st)
         need = self.ess_target * n
         cov = self.proposal == "covariance"
-        if cov and st["ws_cov"] is None:
+        block = self.proposal == "block"
+        if (cov or block) and st["ws_cov"] is None:
             st["ws_cov"] = ops.temper_moments_workspace(n, L)
+        if block and st["ws_block"] is None:
+            st["ws_block"] = ops.temper_group_moments_workspace(n, tracer.n_groups, tracer.n_grouped)
         factor, degenerate = None, []
+        factor_z, degenerate_z = None, []
 
         def ess_fn(deltas):
             out = ops.temper_ess_ladder(ll, deltas, ws).cpu().numpy()  # (one host read)
@@ -950,6 +968,14 @@ class TemperedSMC(SMCAlgorithm):
                 _, factor, _, nd = ops.temper_moments(x, lw, st["ws_cov"])
                 degenerate.append(nd)  # (read at the end of the run)
                 x, lp, ll, acc = ops.temper_move_cov(tplan, prng.fold_in(ks, 1), x, lp, ll, nb, K, factor, ancestors=anc)
+            elif block:  # both sets of moments BEFORE resampling; every factor stays on the device, then ONE move launch
+                _, factor, _, nd = ops.temper_moments(x, lw, st["ws_cov"])
+                factor_z, _, ndz = ops.temper_group_moments(z, lw, st["ws_block"])
+                degenerate.append(nd)
+                degenerate_z.append(ndz)
+                x, z, lp, ll, acc, accz = ops.temper_move_grouped_cov(tplan, prng.fold_in(ks, 1), x, z, lp, ll, nb, K, factor_z, factor,
+                                                                      ancestors=anc)
+                accepts_z.append(accz.sum())
             else:
                 sc = fixed_scales
                 if sc is None and K > 0:
@@ -970,9 +996,12 @@ class TemperedSMC(SMCAlgorithm):
         if cov:  # (the stages' degenerate counts ride along with the accept counts)
             tail = torch.cat([torch.stack(accepts).to(torch.int64), torch.cat(degenerate).to(torch.int64)]).cpu().numpy()
             acc_all, degenerate = tail[:len(accepts)], [int(v) for v in tail[len(accepts):]]
-        else:  # (a grouped plan's group accept counts ride along)
-            acc_all = torch.stack(accepts + accepts_z).to(torch.int64).cpu().numpy()
-            acc_all, accz_all = acc_all[:len(accepts)], acc_all[len(accepts):]
+        else:  # (a grouped plan's group accept counts ride along, and the block route's degenerate counts)
+            tail = torch.cat([torch.stack(accepts + accepts_z).to(torch.int64), *(d.to(torch.int64) for d in degenerate + degenerate_z)])
+            tail = tail.cpu().numpy()
+            acc_all, accz_all = tail[:len(accepts)], tail[len(accepts):len(accepts) + len(accepts_z)]
+            counts = [int(v) for v in tail[len(accepts) + len(accepts_z):]]
+            degenerate, degenerate_z = counts[:len(degenerate)], counts[len(degenerate):]
         log_z = 0.0
         for e_s, q_s in zip(e_all, q_all):
             if q_s <= 0:
@@ -989,14 +1018,25 @@ class TemperedSMC(SMCAlgorithm):
             G = tracer.n_groups
             res.accept_rate_groups = [float(a) / (n * K * G) if K else 0.0 for a in accz_all]
             res.group_columns = z
+            if block:
+                S = tracer.n_grouped
+                res.factor, res.n_degenerate, res.n_degenerate_groups = self._unpack(factor, L), degenerate, degenerate_z
+                res.group_factor = torch.zeros(G, S, S, dtype=torch.float32, device=factor_z.device)
+                rows, cols = torch.tril_indices(S, S, device=factor_z.device)
+                res.group_factor[:, rows, cols] = factor_z
             return res
         choices = ChoiceMap.from_mapping([(m["addr"], c) for m, c in zip(st["latents"], x)])
         if not cov:
             return TemperedResult(float(log_z), betas, ess, rate, choices, lp, ll, x)
+        return TemperedResult(float(log_z), betas, ess, rate, choices, lp, ll, x, self._unpack(factor, L), degenerate)
+
+    @staticmethod
+    def _unpack(factor: torch.Tensor, L: int) -> torch.Tensor:
+        """The packed lower triangle of include/gjx_temper_cov.h as f32 [L, L], on the device."""
         full = torch.zeros(L, L, dtype=torch.float32, device=factor.device)
         rows, cols = torch.tril_indices(L, L, device=factor.device)  # (row-major: the packing of the header)
         full[rows, cols] = factor
-        return TemperedResult(float(log_z), betas, ess, rate, choices, lp, ll, x, full, degenerate)
+        return full
 
     # -- the SMCAlgorithm interface --------------------------------------------------------------------------------------------
     def run_smc(self, key) -> ParticleCollection:
