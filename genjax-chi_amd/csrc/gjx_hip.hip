@@ -24,6 +24,7 @@
 #include "../../include/gjx_group.h"
 #include "../../include/gjx_group_checks.h"
 #include "../../include/gjx_group_cov.h"
+#include "../../include/gjx_quantiles.h"
 // The library's own kernels keep the Philox round's plain XOR chain (gjx_device.hpp xor3): with v_bitop3_b32 the one-filter
 // LGSSM step measured 0.5 % slower (8.96e10 against 9.01e10 particle-steps/s, three alternating runs each, parent's range
 // 0.1 %), while the generated kernels, which include the header on their own, gain 6 % (importance) and 12 % (LGSSM scan);
@@ -6376,6 +6377,95 @@ int gjx_temper_psis_units(gjx_temper_plan* p, const gjx_psis_units_io* io, const
       if (int rc = launch_status()) return rc;
     }
     k_psis_finish<<<nu, kBlock, 0, S(s)>>>(A, (uint32_t)U, pio->out + u0, pio->tail ? pio->tail + (size_t)u0 * (M + 1u) : nullptr);
+    if (int rc = launch_status()) return rc;
+  }
+  return GJX_OK;
+}
+}  // extern "C"
+
+// =====================================================================================================================
+// Quantiles and moments of f32 columns in device memory (include/gjx_quantiles.h; kernels in gjx_quantiles.hpp)
+// =====================================================================================================================
+#include "gjx_quantiles.hpp"
+
+namespace {
+inline bool quant_shape_ok(uint64_t n, uint64_t n_cols, int32_t Q) {
+  return n >= 1 && n < (1ull << 31) && n_cols >= 1 && n_cols < (1ull << 31) && Q >= 1 && Q <= GJX_QUANTILES_MAX_PROBS;
+}
+// the arrays of one batch of `cols` columns
+bool quant_carve(Carver& cv, uint32_t cols, QArgs* A) {
+  A->hist0 = cv.take<uint32_t>((size_t)cols * kQBins);
+  A->hist = cv.take<uint32_t>((size_t)cols * kQMaxSlots * kQBins);
+  A->part = cv.take<double>((size_t)cols * 2 * kQMaxBlocks);
+  A->st = cv.take<QColState>(cols);
+  return cv.ok;
+}
+inline uint32_t quant_batch(uint64_t n_cols, uint32_t max_workgroups) {
+  uint32_t b = (uint32_t)(n_cols < GJX_QUANTILES_BATCH_COLS ? n_cols : GJX_QUANTILES_BATCH_COLS);
+  return max_workgroups && b > max_workgroups ? max_workgroups : b;
+}
+}  // namespace
+
+extern "C" {
+int gjx_quantiles_version(int* major, int* minor) {
+  return version_out(major, minor, GJX_QUANTILES_VERSION_MAJOR, GJX_QUANTILES_VERSION_MINOR);
+}
+size_t gjx_quantiles_workspace_bytes(uint64_t n, uint32_t n_cols, int32_t n_probs) {
+  if (!quant_shape_ok(n, n_cols, n_probs)) return 0;
+  Carver cv{nullptr, ~(size_t)0};
+  QArgs A;
+  (void)quant_carve(cv, quant_batch(n_cols, 0), &A);
+  return ~(size_t)0 - cv.left;
+}
+int gjx_column_quantiles(const gjx_column_quantiles_io* io, gjx_stream s) {
+  if (!io || !io->probs || !io->bracket || !io->quant || !io->stats || io->n_segments < 1 || io->n_segments > GJX_QUANTILES_MAX_SEGMENTS ||
+      ((uintptr_t)io->ws & 7) != 0)
+    return GJX_ERR_INVALID;
+  QArgs A;
+  memset(&A, 0, sizeof A);
+  uint64_t n_cols = 0;
+  for (int g = 0; g < io->n_segments; ++g) {
+    const gjx_column_segment& sg = io->seg[g];
+    if (!sg.base || ((uintptr_t)sg.base & 3) != 0 || sg.n_cols < 1 || (sg.n_cols > 1 && sg.stride < io->n) || n_cols >= (1ull << 31))
+      return GJX_ERR_INVALID;
+    A.base[g] = sg.base;
+    A.stride[g] = sg.stride;
+    A.first[g] = (uint32_t)n_cols;
+    n_cols += sg.n_cols;
+  }
+  if (!quant_shape_ok(io->n, n_cols, io->n_probs)) return GJX_ERR_INVALID;
+  for (int j = 0; j < io->n_probs; ++j) {
+    if (!(io->probs[j] >= 0.0 && io->probs[j] <= 1.0)) return GJX_ERR_INVALID;
+    A.probs[j] = io->probs[j];
+  }
+  if (!io->ws || io->ws_bytes < gjx_quantiles_workspace_bytes(io->n, (uint32_t)n_cols, io->n_probs)) return GJX_ERR_WORKSPACE;
+  // the split of include/gjx_quantiles.h: a function of (n, n_cols, max_workgroups) alone, the same for every batch
+  const uint32_t w = io->max_workgroups, batch = quant_batch(n_cols, w);
+  const uint64_t min_per = w ? 1024 : 16384, by_n = (io->n + min_per - 1) / min_per;
+  uint64_t B = (w ? w : 2048u) / batch;
+  B = B < 1 ? 1 : B;
+  B = B > by_n ? by_n : B;
+  B = B > kQMaxBlocks ? kQMaxBlocks : B;
+  Carver cv{(char*)io->ws, io->ws_bytes};
+  if (!quant_carve(cv, batch, &A)) return GJX_ERR_WORKSPACE;
+  A.n_seg = io->n_segments;
+  A.Q = io->n_probs;
+  A.n = (uint32_t)io->n;
+  A.per = (uint32_t)((io->n + B - 1) / B);
+  A.B = (uint32_t)((io->n + A.per - 1) / A.per);
+  A.bracket = io->bracket; A.quant = io->quant; A.stats = io->stats;
+  const uint32_t passes = (2u * (uint32_t)io->n_probs + kQSlots - 1) / kQSlots;
+  for (uint64_t c0 = 0; c0 < n_cols; c0 += batch) {
+    A.col0 = (uint32_t)c0;
+    A.cols = (uint32_t)(n_cols - c0 < batch ? n_cols - c0 : batch);
+    const dim3 grid(A.B, A.cols, 1);
+    k_quant_clear<<<A.cols * 4u, kBlock, 0, S(s)>>>(A);
+    k_quant_sweep<0><<<grid, kBlock, 0, S(s)>>>(A, 0u);
+    k_quant_pick<0><<<A.cols, kBlock, 0, S(s)>>>(A);
+    for (uint32_t p = 0; p < passes; ++p) k_quant_sweep<1><<<grid, kBlock, 0, S(s)>>>(A, p * kQSlots);
+    k_quant_pick<1><<<A.cols, kBlock, 0, S(s)>>>(A);
+    for (uint32_t p = 0; p < passes; ++p) k_quant_sweep<2><<<grid, kBlock, 0, S(s)>>>(A, p * kQSlots);
+    k_quant_pick<2><<<A.cols, kBlock, 0, S(s)>>>(A);
     if (int rc = launch_status()) return rc;
   }
   return GJX_OK;

@@ -136,6 +136,10 @@ class GroupCovUnavailable(HeaderUnavailable):
     header, why = "gjx_group_cov.h", "the per-group moments and the block move of grouped latents run as HIP kernels only"
 
 
+class QuantilesUnavailable(HeaderUnavailable):
+    header, why = "gjx_quantiles.h", "the radix select over columns in device memory and its moments are HIP kernels only"
+
+
 class Keys(C.Structure):
     _fields_ = [
         ("impl", C.c_int32),
@@ -920,6 +924,41 @@ GROUP_COV_PROTOTYPES = {
 }
 GROUP_COV_ABI_VERSION = (0, 1)
 
+# include/gjx_quantiles.h: a NINETEENTH header, same arrangement — exact quantiles and moments of f32 columns in device memory:
+# a three-sweep radix select for several ranks at once, the posterior summary of a tempered plan's latents.
+QUANTILES_MAX_PROBS = 8
+QUANTILES_MAX_SEGMENTS = 32
+
+
+class ColumnSegment(C.Structure):
+    """gjx_column_segment (include/gjx_quantiles.h)."""
+    _fields_ = [("base", C.c_void_p), ("n_cols", C.c_uint32), ("stride", C.c_uint64)]
+
+
+class ColumnQuantilesIO(C.Structure):
+    """gjx_column_quantiles_io (include/gjx_quantiles.h)."""
+    _fields_ = [
+        ("n", C.c_uint64),
+        ("n_segments", C.c_int32),
+        ("seg", ColumnSegment * QUANTILES_MAX_SEGMENTS),
+        ("n_probs", C.c_int32),
+        ("probs", C.POINTER(C.c_double)),
+        ("bracket", C.c_void_p),
+        ("quant", C.c_void_p),
+        ("stats", C.c_void_p),
+        ("ws", C.c_void_p),
+        ("ws_bytes", C.c_size_t),
+        ("max_workgroups", C.c_uint32),
+    ]
+
+
+QUANTILES_PROTOTYPES = {
+    "gjx_quantiles_version": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gjx_quantiles_workspace_bytes": (C.c_size_t, [C.c_uint64, C.c_uint32, C.c_int32]),
+    "gjx_column_quantiles": (C.c_int, [C.POINTER(ColumnQuantilesIO), _P]),
+}
+QUANTILES_ABI_VERSION = (0, 1)
+
 # The optional headers, in the order they are bound: every one is exported by libgjx_hip.so only and bound if present.
 class Header(collections.namedtuple("Header", "key header version_fn prototypes version_name unavailable")):
     @property
@@ -977,6 +1016,14 @@ CHECK_HEADERS = {h.key: h for h in (
 )}
 
 
+# Headers that summarise columns in device memory and know no plan at all (gjx_quantiles.h).  A table of its own once more:
+# the suites of the earlier headers pin the contents of every table above and the last entry of bound_headers().
+SUMMARY_HEADERS = {h.key: h for h in (
+    Header("quantiles", "gjx_quantiles.h", "gjx_quantiles_version", QUANTILES_PROTOTYPES, "QUANTILES_ABI_VERSION",
+           QuantilesUnavailable),
+)}
+
+
 def all_optional_headers():
     """Every header next to gjx.h, in binding order: OPTIONAL_HEADERS, then EXTENSION_HEADERS, then PLAN_HEADERS, then
     MOVE_HEADERS."""
@@ -984,8 +1031,9 @@ def all_optional_headers():
 
 
 def bound_headers():
-    """Every header a library is bound with, in binding order: all_optional_headers(), then CHECK_HEADERS."""
-    return (*all_optional_headers(), *CHECK_HEADERS.values())
+    """Every header a library is bound with, in binding order: all_optional_headers(), then SUMMARY_HEADERS, then
+    CHECK_HEADERS."""
+    return (*all_optional_headers(), *SUMMARY_HEADERS.values(), *CHECK_HEADERS.values())
 
 
 _HEADER_OF = {name: h for h in bound_headers() for name in h.prototypes}  # entry point -> its optional header
@@ -1004,6 +1052,7 @@ _NO_STATUS = {
     "gjx_predictive_workspace_bytes",
     "gjx_temper_moments_workspace_bytes",
     "gjx_group_moments_workspace_bytes",
+    "gjx_quantiles_workspace_bytes",
     "gjx_backmove_workspace_bytes",
     "gjx_backsim_workspace_bytes",
     "gjx_paths_workspace_bytes",

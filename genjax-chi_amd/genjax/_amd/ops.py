@@ -808,6 +808,40 @@ class Ops:
         self.lib.call("gjx_group_moments", C.byref(io), self.stream())
         return factor, scales, ndeg
 
+    def column_quantiles(self, segments: list, probs, ws: torch.Tensor | None = None, *, max_workgroups: int = 0):
+        """gjx_column_quantiles (include/gjx_quantiles.h): exact order statistics, quantiles and moments of every column of
+        `segments` — float32 tensors [n] (one column) or [C, n] (C columns at stride n), all of one n — at the probabilities
+        `probs` (1 .. 8 numbers in [0, 1]) -> (bracket float32 [n_cols, Q, 2]: the lo-th and hi-th order statistic; quant
+        float64 [n_cols, Q]: the linear-rule quantile; stats float64 [n_cols, 5]: NaN count, mean, sample variance, min,
+        max) — all on the device, columns numbered through the segments in order."""
+        import numpy as np
+
+        self.lib.require("quantiles", "gjx_column_quantiles")
+        p = np.ascontiguousarray(np.asarray(probs, dtype=np.float64).reshape(-1))
+        if not 1 <= p.size <= abi.QUANTILES_MAX_PROBS or not np.all((p >= 0.0) & (p <= 1.0)):
+            raise ValueError(f"column_quantiles: 1 .. {abi.QUANTILES_MAX_PROBS} probabilities in [0, 1] expected, got {probs!r}")
+        if not 1 <= len(segments) <= abi.QUANTILES_MAX_SEGMENTS or any(c.dim() not in (1, 2) for c in segments):
+            raise ValueError(f"column_quantiles: 1 .. {abi.QUANTILES_MAX_SEGMENTS} segments [n] or [C, n] expected")
+        n = int(segments[0].shape[-1])
+        io = abi.ColumnQuantilesIO()
+        io.n, io.n_segments, io.n_probs, io.probs = n, len(segments), int(p.size), p.ctypes.data_as(C.POINTER(C.c_double))
+        n_cols = 0
+        for k, c in enumerate(segments):
+            cols = int(c.shape[0]) if c.dim() == 2 else 1
+            io.seg[k].base = self._chk(c, torch.float32, cols * n, f"segments[{k}]").value
+            io.seg[k].n_cols, io.seg[k].stride = cols, n
+            n_cols += cols
+        nb = int(self.lib.call("gjx_quantiles_workspace_bytes", n, n_cols, int(p.size)))
+        if nb == 0:
+            raise ValueError(f"column_quantiles: n = {n} or {n_cols} columns out of range")
+        ws = torch.empty(nb, dtype=torch.uint8, device=self._alloc_device) if ws is None else ws
+        bracket = self.empty((n_cols, p.size, 2), torch.float32)
+        quant, stats = self.empty((n_cols, p.size), torch.float64), self.empty((n_cols, 5), torch.float64)
+        io.bracket, io.quant, io.stats = bracket.data_ptr(), quant.data_ptr(), stats.data_ptr()
+        io.ws, io.ws_bytes, io.max_workgroups = ws.data_ptr(), ws.numel(), int(max_workgroups)
+        self.lib.call("gjx_column_quantiles", C.byref(io), self.stream())
+        return bracket, quant, stats
+
     def temper_ladder_workspace(self, n: int) -> torch.Tensor:
         """A zeroed workspace of gjx_temper_ess_ladder for populations of n and any ladder length (its ticket stays zero
         from call to call: calls that share it must be stream-ordered)."""

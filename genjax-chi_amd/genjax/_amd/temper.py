@@ -530,6 +530,27 @@ class TemperedResult:
                 f"n={self.lp.numel()})")
 
 
+class PosteriorSummary:
+    """What `TemperedSMC.summary` returns (include/gjx_quantiles.h): dictionaries keyed by latent address, every value float64
+    on the device — `mean`, `sd`, `var` (divisor m - 1), `min`, `max`, `nan_count` of shape [] for a scalar latent and [G]
+    for a grouped one, `quantiles` of shape [Q] / [G, Q] at `probs`, and `brackets` (float32 [Q, 2] / [G, Q, 2]): the two
+    exact order statistics each quantile interpolates.  Everything is over the m = n - nan_count entries that are not NaN.
+    Views of three tensors the one library call wrote: nothing is read from the host."""
+
+    def __init__(self, rows: dict, probs, quant: torch.Tensor, stats: torch.Tensor, bracket: torch.Tensor):
+        """`rows`: address -> (first column, columns, grouped) into quant [C, Q], stats [C, 5] and bracket [C, Q, 2]."""
+        self.probs = tuple(probs)
+        cut = lambda t, a: t[rows[a][0]:rows[a][0] + rows[a][1]] if rows[a][2] else t[rows[a][0]]
+        stat = lambda j: {a: cut(stats[:, j], a) for a in rows}
+        self.nan_count, self.mean, self.var, self.min, self.max = (stat(j) for j in range(5))
+        self.sd = {a: torch.sqrt(v) for a, v in self.var.items()}
+        self.quantiles = {a: cut(quant, a) for a in rows}
+        self.brackets = {a: cut(bracket, a) for a in rows}
+
+    def __repr__(self):
+        return f"PosteriorSummary(addresses={list(self.mean)!r}, probs={self.probs!r})"
+
+
 class PointwiseLikelihood:
     """Per data row d of a plated site, over the n equally weighted particles of a population (include/gjx_pointwise.h):
     `lppd` = log (1/n) sum_i p(y_d | x_i), `mean` and `var` the sample mean and (n - 1) variance of log p(y_d | x_i), `count`
@@ -1232,6 +1253,44 @@ class TemperedSMC(SMCAlgorithm):
         table, draws = st["ops"].temper_predictive(tplan, key, x, k, z=z)
         addrs = [m["addr"] for m in tracer.meta if m.get("plated")]
         return PosteriorPredictive(addrs, table, n, draws, k, observed=args is None)
+
+    # -- the posterior summary (include/gjx_quantiles.h) ----------------------------------------------------------
+    def summary(self, res, probs=(0.05, 0.5, 0.95)) -> PosteriorSummary:
+        """Mean, standard deviation, extremes and exact quantiles of every latent under the equally weighted population `res` — a
+        TemperedResult of `run`, or the latent columns in table order as `choices` holds them (scalars [n], grouped [G, n]).
+        `probs`: 1 .. 8 probabilities in [0, 1]; the quantiles follow the linear rule (numpy's default) between two exact
+        order statistics.  ONE library call for all latents — a scalar is a segment of one column, a grouped latent a segment
+        of G columns — with no host read and no torch arithmetic on the [G, n] columns (PosteriorSummary)."""
+        try:
+            p = [float(v) for v in probs]
+        except TypeError:
+            p = []
+        if not 1 <= len(p) <= abi.QUANTILES_MAX_PROBS or not all(0.0 <= v <= 1.0 for v in p):
+            raise ValueError(f"TemperedSMC.summary: probs must be 1 .. {abi.QUANTILES_MAX_PROBS} probabilities in [0, 1], got {probs!r}")
+        st = self._state()
+        ops, tracer = st["ops"], st["tracer"]
+        x, z = self._split_population("summary", res)
+        ops.lib.require("quantiles", "gjx_column_quantiles")
+        if len(x) != len(st["latents"]):
+            raise ValueError(f"TemperedSMC.summary: {len(st['latents'])} latent columns expected "
+                             f"({[m['addr'] for m in st['latents']]!r}), got {len(x)}")
+        dev = lambda c: c.detach().to(device=ops.device(), dtype=torch.float32).contiguous()
+        x, z = [dev(c) for c in x], [dev(c) for c in z or []]
+        n = int((x + z)[0].shape[-1])
+        grouped = [m for m in tracer.meta if m.get("grouped")]
+        for m, c in [*zip(st["latents"], x), *zip(grouped, z)]:
+            want = (tracer.n_groups, n) if m.get("grouped") else (n,)
+            if tuple(c.shape) != want:
+                raise ValueError(f"TemperedSMC.summary: the column of the latent at address {m['addr']!r} must have shape "
+                                 f"{list(want)}, got {list(c.shape)}")
+        bracket, quant, stats = ops.column_quantiles(x + z, p)
+        rows, at = {}, 0
+        for m, c in [*zip(st["latents"], x), *zip(grouped, z)]:
+            k = c.shape[0] if c.dim() == 2 else 1
+            rows[m["addr"]] = (at, k, c.dim() == 2)
+            at += k
+        order = [m["addr"] for m in tracer.meta if m["obs"] is None]  # table order, as `choices`
+        return PosteriorSummary({a: rows[a] for a in order}, p, quant, stats, bracket)
 
     def log_marginal_likelihood_estimate(self, key, target: Target | None = None):
         if target is not None:
