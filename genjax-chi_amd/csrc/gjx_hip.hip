@@ -6471,3 +6471,99 @@ int gjx_column_quantiles(const gjx_column_quantiles_io* io, gjx_stream s) {
   return GJX_OK;
 }
 }  // extern "C"
+
+// ---- weighted columns: the same select on histograms of mass ------------------------------------------------------------
+namespace {
+inline uint64_t wquant_mass_stride(uint64_t n) { return (n + 7) & ~(uint64_t)3; }  // a row, its phase (<= 3), whole quads
+// the arrays of one batch of `cols` columns weighed by V weight columns
+bool wquant_carve(Carver& cv, uint64_t n, uint32_t cols, uint32_t V, WQArgs* A) {
+  A->hist0 = cv.take<uint64_t>((size_t)cols * kWQBins0);
+  A->hist = cv.take<uint64_t>((size_t)cols * kWQMaxSlots * kWQBins);
+  A->part = cv.take<double>((size_t)cols * 3 * kQMaxBlocks);
+  A->st = cv.take<WQColState>(cols);
+  A->wmax = cv.take<uint32_t>(cols);
+  A->mass = cv.take<uint32_t>((size_t)(V < cols ? V : cols) * wquant_mass_stride(n));
+  return cv.ok;
+}
+}  // namespace
+
+extern "C" {
+size_t gjx_weighted_quantiles_workspace_bytes(uint64_t n, uint32_t n_cols, uint32_t n_weight_cols, int32_t n_probs) {
+  if (!quant_shape_ok(n, n_cols, n_probs) || n_weight_cols < 1 || n_weight_cols > n_cols) return 0;
+  Carver cv{nullptr, ~(size_t)0};
+  WQArgs A;
+  (void)wquant_carve(cv, n, quant_batch(n_cols, 0), n_weight_cols, &A);
+  return ~(size_t)0 - cv.left;
+}
+int gjx_weighted_column_quantiles(const gjx_weighted_quantiles_io* io, gjx_stream s) {
+  if (!io || !io->probs || !io->quant || !io->stats || !io->logw || io->n_segments < 1 || io->n_segments > GJX_QUANTILES_MAX_SEGMENTS ||
+      ((uintptr_t)io->ws & 7) != 0 || ((uintptr_t)io->logw & 3) != 0)
+    return GJX_ERR_INVALID;
+  WQArgs A;
+  memset(&A, 0, sizeof A);
+  uint64_t n_cols = 0;
+  for (int g = 0; g < io->n_segments; ++g) {
+    const gjx_column_segment& sg = io->seg[g];
+    if (!sg.base || ((uintptr_t)sg.base & 3) != 0 || sg.n_cols < 1 || (sg.n_cols > 1 && sg.stride < io->n) || n_cols >= (1ull << 31))
+      return GJX_ERR_INVALID;
+    A.base[g] = sg.base;
+    A.stride[g] = sg.stride;
+    A.first[g] = (uint32_t)n_cols;
+    n_cols += sg.n_cols;
+  }
+  const uint32_t V = io->n_weight_cols;
+  if (!quant_shape_ok(io->n, n_cols, io->n_probs) || V < 1 || V > n_cols || (V > 1 && io->logw_stride < io->n)) return GJX_ERR_INVALID;
+  for (int j = 0; j < io->n_probs; ++j) {
+    if (!(io->probs[j] >= 0.0 && io->probs[j] <= 1.0)) return GJX_ERR_INVALID;
+    A.probs[j] = io->probs[j];
+  }
+  if (!io->ws || io->ws_bytes < gjx_weighted_quantiles_workspace_bytes(io->n, (uint32_t)n_cols, V, io->n_probs)) return GJX_ERR_WORKSPACE;
+  // the split of include/gjx_quantiles.h, as gjx_column_quantiles takes it
+  const uint32_t w = io->max_workgroups, batch = quant_batch(n_cols, w);
+  const uint64_t min_per = w ? 1024 : 16384, by_n = (io->n + min_per - 1) / min_per;
+  uint64_t B = (w ? w : 2048u) / batch;
+  B = B < 1 ? 1 : B;
+  B = B > by_n ? by_n : B;
+  B = B > kQMaxBlocks ? kQMaxBlocks : B;
+  Carver cv{(char*)io->ws, io->ws_bytes};
+  if (!wquant_carve(cv, io->n, batch, V, &A)) return GJX_ERR_WORKSPACE;
+  A.n_seg = io->n_segments;
+  A.Q = io->n_probs;
+  A.n = (uint32_t)io->n;
+  A.per = (uint32_t)((io->n + B - 1) / B);
+  A.B = (uint32_t)((io->n + A.per - 1) / A.per);
+  A.logw = io->logw;
+  A.logw_stride = io->logw_stride;
+  A.V = V;
+  A.by_v = V <= batch;
+  A.frac = frac_bits(io->n) < 31 ? frac_bits(io->n) : 31;
+  A.mstride = wquant_mass_stride(io->n);
+  A.phased = 1u;
+  A.mass_by_v = A.by_v;
+  if (io->mass_out) {  // the caller's table: dense rows [V][n], every batch reads the rows it wrote there
+    A.mass = io->mass_out;
+    A.mstride = io->n;
+    A.phased = 0u;
+    A.mass_by_v = 1u;
+  }
+  A.quant = io->quant; A.stats = io->stats;
+  const uint32_t passes = ((uint32_t)io->n_probs + kQSlots - 1) / kQSlots;
+  for (uint64_t c0 = 0; c0 < n_cols; c0 += batch) {
+    A.col0 = (uint32_t)c0;
+    A.cols = (uint32_t)(n_cols - c0 < batch ? n_cols - c0 : batch);
+    A.rows = A.by_v ? V : A.cols;
+    const dim3 grid(A.B, A.cols, 1), rows(A.B, A.rows, 1);
+    k_wquant_clear<<<A.cols * 4u, kBlock, 0, S(s)>>>(A);
+    k_wquant_mass<0><<<rows, kBlock, 0, S(s)>>>(A);
+    k_wquant_mass<1><<<rows, kBlock, 0, S(s)>>>(A);
+    k_wquant_sweep<0><<<grid, kBlock, 0, S(s)>>>(A, 0u);
+    k_wquant_pick<0><<<A.cols, kBlock, 0, S(s)>>>(A);
+    for (uint32_t p = 0; p < passes; ++p) k_wquant_sweep<1><<<grid, kBlock, 0, S(s)>>>(A, p * kQSlots);
+    k_wquant_pick<1><<<A.cols, kBlock, 0, S(s)>>>(A);
+    for (uint32_t p = 0; p < passes; ++p) k_wquant_sweep<2><<<grid, kBlock, 0, S(s)>>>(A, p * kQSlots);
+    k_wquant_pick<2><<<A.cols, kBlock, 0, S(s)>>>(A);
+    if (int rc = launch_status()) return rc;
+  }
+  return GJX_OK;
+}
+}  // extern "C"

@@ -952,10 +952,32 @@ class ColumnQuantilesIO(C.Structure):
     ]
 
 
+class WeightedQuantilesIO(C.Structure):
+    """gjx_weighted_quantiles_io (include/gjx_quantiles.h, GJX_QUANTILES_WEIGHTED)."""
+    _fields_ = [
+        ("n", C.c_uint64),
+        ("n_segments", C.c_int32),
+        ("seg", ColumnSegment * QUANTILES_MAX_SEGMENTS),
+        ("logw", C.c_void_p),
+        ("n_weight_cols", C.c_uint32),
+        ("logw_stride", C.c_uint64),
+        ("n_probs", C.c_int32),
+        ("probs", C.POINTER(C.c_double)),
+        ("quant", C.c_void_p),
+        ("stats", C.c_void_p),
+        ("mass_out", C.c_void_p),
+        ("ws", C.c_void_p),
+        ("ws_bytes", C.c_size_t),
+        ("max_workgroups", C.c_uint32),
+    ]
+
+
 QUANTILES_PROTOTYPES = {
     "gjx_quantiles_version": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "gjx_quantiles_workspace_bytes": (C.c_size_t, [C.c_uint64, C.c_uint32, C.c_int32]),
     "gjx_column_quantiles": (C.c_int, [C.POINTER(ColumnQuantilesIO), _P]),
+    "gjx_weighted_quantiles_workspace_bytes": (C.c_size_t, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int32]),
+    "gjx_weighted_column_quantiles": (C.c_int, [C.POINTER(WeightedQuantilesIO), _P]),
 }
 QUANTILES_ABI_VERSION = (0, 1)
 
@@ -1053,6 +1075,7 @@ _NO_STATUS = {
     "gjx_temper_moments_workspace_bytes",
     "gjx_group_moments_workspace_bytes",
     "gjx_quantiles_workspace_bytes",
+    "gjx_weighted_quantiles_workspace_bytes",
     "gjx_backmove_workspace_bytes",
     "gjx_backsim_workspace_bytes",
     "gjx_paths_workspace_bytes",

@@ -842,6 +842,53 @@ class Ops:
         self.lib.call("gjx_column_quantiles", C.byref(io), self.stream())
         return bracket, quant, stats
 
+    def _rows(self, t: torch.Tensor, n: int, name: str):
+        """-> (data_ptr, rows, row stride) of float32 rows [n] or [R, n]; the rows themselves dense, their stride free."""
+        if t.device.type != self.device_type or t.dtype != torch.float32:
+            raise TypeError(f"{name}: expected a float32 {self.device_type} tensor, got {t.dtype} on {t.device}")
+        if t.dim() not in (1, 2) or t.shape[-1] != n or (n > 1 and t.stride(-1) != 1):
+            raise ValueError(f"{name}: rows [{n}] or [R, {n}] with unit element stride expected, got {list(t.shape)}")
+        rows = int(t.shape[0]) if t.dim() == 2 else 1
+        stride = int(t.stride(0)) if rows > 1 else n
+        if rows > 1 and stride < n:
+            raise ValueError(f"{name}: rows overlap (stride {stride} < {n})")
+        return t.data_ptr(), rows, stride
+
+    def weighted_column_quantiles(self, segments: list, log_weights: torch.Tensor, probs, ws: torch.Tensor | None = None, *,
+                                  max_workgroups: int = 0, want_mass: bool = False):
+        """gjx_weighted_column_quantiles (include/gjx_quantiles.h): exact inverted-CDF quantiles and weighted moments of every
+        column of `segments` (as `column_quantiles`; the rows of a [C, n] segment may be strided) under `log_weights` —
+        float32 [n], or [V, n] with rows possibly strided: data column c is weighed by row c % V — at `probs` -> (quant
+        float32 [n_cols, Q]: an entry of the column; stats float64 [n_cols, 6]: NaN count, mean, population variance, min,
+        max, ess[, mass int32 [V, n] holding the u32 bits of the fixed-point masses]) — all on the device."""
+        import numpy as np
+
+        self.lib.require("quantiles", "gjx_weighted_column_quantiles")
+        p = np.ascontiguousarray(np.asarray(probs, dtype=np.float64).reshape(-1))
+        if not 1 <= p.size <= abi.QUANTILES_MAX_PROBS or not np.all((p >= 0.0) & (p <= 1.0)):
+            raise ValueError(f"weighted_column_quantiles: 1 .. {abi.QUANTILES_MAX_PROBS} probabilities in [0, 1] expected, got {probs!r}")
+        if not 1 <= len(segments) <= abi.QUANTILES_MAX_SEGMENTS:
+            raise ValueError(f"weighted_column_quantiles: 1 .. {abi.QUANTILES_MAX_SEGMENTS} segments [n] or [C, n] expected")
+        n = int(segments[0].shape[-1])
+        io = abi.WeightedQuantilesIO()
+        io.n, io.n_segments, io.n_probs, io.probs = n, len(segments), int(p.size), p.ctypes.data_as(C.POINTER(C.c_double))
+        n_cols = 0
+        for k, c in enumerate(segments):
+            io.seg[k].base, io.seg[k].n_cols, io.seg[k].stride = self._rows(c, n, f"segments[{k}]")
+            n_cols += io.seg[k].n_cols
+        io.logw, V, io.logw_stride = self._rows(log_weights, n, "log_weights")
+        io.n_weight_cols = V
+        nb = int(self.lib.call("gjx_weighted_quantiles_workspace_bytes", n, n_cols, V, int(p.size)))
+        if nb == 0:
+            raise ValueError(f"weighted_column_quantiles: n = {n}, {n_cols} columns or {V} weight columns out of range")
+        ws = torch.empty(nb, dtype=torch.uint8, device=self._alloc_device) if ws is None else ws
+        quant, stats = self.empty((n_cols, p.size), torch.float32), self.empty((n_cols, 6), torch.float64)
+        mass = self.empty((V, n), torch.int32) if want_mass else None  # (u32 bits: torch has no arithmetic on uint32)
+        io.quant, io.stats, io.mass_out = quant.data_ptr(), stats.data_ptr(), mass.data_ptr() if want_mass else None
+        io.ws, io.ws_bytes, io.max_workgroups = ws.data_ptr(), ws.numel(), int(max_workgroups)
+        self.lib.call("gjx_weighted_column_quantiles", C.byref(io), self.stream())
+        return (quant, stats, mass) if want_mass else (quant, stats)
+
     def temper_ladder_workspace(self, n: int) -> torch.Tensor:
         """A zeroed workspace of gjx_temper_ess_ladder for populations of n and any ladder length (its ticket stays zero
         from call to call: calls that share it must be stream-ordered)."""

@@ -90,6 +90,70 @@ class SMCResult:
                             paths[n_state] if with_log_weights else None, out["sum"][:n_state], out["sumsq"][:n_state],
                             [c.dtype == torch.float32 for c in cols[:n_state]])
 
+    def summary(self, probs=(0.05, 0.5, 0.95)) -> "StateSummary":
+        """The FILTERING summary of every step: mean, sd, extremes, effective sample size and exact weighted quantiles of
+        x_t | y_1:t under `history[t]` weighted by `log_weight_history[t]` — ONE library call over all f32 carry components
+        (gjx_weighted_column_quantiles: K segments of T columns against T weight columns), no host read.  Needs
+        `record_history=True`.  The quantiles follow the inverted-CDF rule: each is a particle of the step."""
+        p = _summary_probs("SMCResult.summary", probs)
+        if self.history is None or self.log_weight_history is None:
+            raise ValueError("summary() needs the per-step states: run the filter with BootstrapSMC(..., record_history=True)")
+        cols = list(self.history) if isinstance(self.history, tuple) else [self.history]
+        is_f32 = [c.dtype == torch.float32 for c in cols]
+        seg = [c for c, f in zip(cols, is_f32) if f]
+        quant = stats = None
+        if seg:
+            quant, stats = get_ops().weighted_column_quantiles(seg, self.log_weight_history, p)
+        return _state_summary(p, "inverted_cdf", is_f32, isinstance(self.history, tuple), quant, stats)
+
+
+@dataclass
+class StateSummary:
+    """What `SMCResult.summary` (filtering) and `Trajectories.summary` (smoothing) return.  Per f32 carry component — the
+    tensor itself for a one-column carry, a tuple for a multi-component one, None for an integer column — float64 [T] on
+    the device: `mean`, `sd`, `var`, `min`, `max`, `ess`, `nan_count`; and `quantiles` [T, Q] at `probs`.  All are views of
+    the library call's outputs.  `rule`: "inverted_cdf" — weighted populations: a quantile is the first entry whose
+    cumulative mass reaches p W, float32, and `var` is the population form — or "linear" — equally weighted paths: numpy's
+    default rule in float64, the sample variance, and `ess` is None."""
+    probs: tuple
+    rule: str
+    mean: torch.Tensor | tuple | None
+    sd: torch.Tensor | tuple | None
+    var: torch.Tensor | tuple | None
+    min: torch.Tensor | tuple | None
+    max: torch.Tensor | tuple | None
+    ess: torch.Tensor | tuple | None
+    nan_count: torch.Tensor | tuple | None
+    quantiles: torch.Tensor | tuple | None
+
+
+def _summary_probs(who: str, probs) -> list:
+    try:
+        p = [float(v) for v in probs]
+    except TypeError:
+        p = []
+    if not 1 <= len(p) <= abi.QUANTILES_MAX_PROBS or not all(0.0 <= v <= 1.0 for v in p):
+        raise ValueError(f"{who}: probs must be 1 .. {abi.QUANTILES_MAX_PROBS} probabilities in [0, 1], got {probs!r}")
+    return p
+
+
+def _state_summary(p, rule, is_f32, multi, quant, stats) -> StateSummary:
+    """Cut the outputs of one library call ([K' T, Q] and [K' T, 5 or 6], K' the f32 components in order) per component."""
+    kf = sum(is_f32)
+    if kf:
+        stats, quant = stats.view(kf, -1, stats.shape[-1]), quant.view(kf, -1, len(p))
+    at = iter(range(kf))
+    rows = [next(at) if f else None for f in is_f32]
+
+    def pick(f):
+        outs = [None if k is None else f(k) for k in rows]
+        return tuple(outs) if multi else outs[0]
+
+    stat = lambda j: pick(lambda k: stats[k, :, j])
+    has_ess = kf and stats.shape[-1] == 6
+    return StateSummary(tuple(p), rule, stat(1), pick(lambda k: torch.sqrt(stats[k, :, 2])), stat(2), stat(3), stat(4),
+                        stat(5) if has_ess else pick(lambda k: None), stat(0), pick(lambda k: quant[k]))
+
 
 @dataclass
 class Trajectories:
@@ -123,6 +187,20 @@ class Trajectories:
     def var(self):
         """float64[T] per f32 component: sumsq / m - mean^2, evaluated in float64 on the host."""
         return self._pick(self._moments()[1])
+
+    def summary(self, probs=(0.05, 0.5, 0.95)) -> StateSummary:
+        """The SMOOTHING summary of every step, one library call over all f32 components and no host read.  Weighted paths
+        (no key): gjx_weighted_column_quantiles against the final `log_weights`, rule "inverted_cdf".  Equally weighted
+        paths: gjx_column_quantiles, rule "linear"."""
+        p = _summary_probs("Trajectories.summary", probs)
+        multi = isinstance(self.paths, tuple)
+        seg = [c.contiguous() for c, f in zip(self.paths if multi else [self.paths], self._is_f32) if f]
+        quant = stats = None
+        if seg and self.log_weights is not None:
+            quant, stats = get_ops().weighted_column_quantiles(seg, self.log_weights.contiguous(), p)
+        elif seg:
+            _, quant, stats = get_ops().column_quantiles(seg, p)
+        return _state_summary(p, "linear" if self.log_weights is None else "inverted_cdf", self._is_f32, multi, quant, stats)
 
 
 def _columns(cols):

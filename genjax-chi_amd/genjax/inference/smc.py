@@ -5,11 +5,12 @@ Importance, ImportanceK, SMCAlgorithm), plus what the north star adds on top of 
 from .._amd.inference import (ChangeTarget, Importance, ImportanceK, ParticleCollection, SMCAlgorithm,
                               stack_to_first_dim)
 from .._amd.smc_fused import (BootstrapSMC, DiscreteHMM, GuidedSMC, LinearGaussianSSM, ParticleGibbs, ParticleGibbsResult,
-                              ParticleMH, SMCResult, StateSpaceModel, Trajectories)
+                              ParticleMH, SMCResult, StateSpaceModel, StateSummary, Trajectories)
 from .._amd.temper import (PSISLOGO, PSISLOO, PointwiseLikelihood, PosteriorPredictive, PosteriorSummary, TemperedResult,
                            TemperedSMC)
 
 __all__ = ["ChangeTarget", "Importance", "ImportanceK", "SMCAlgorithm", "ParticleCollection", "BootstrapSMC", "GuidedSMC",
            "LinearGaussianSSM", "DiscreteHMM", "StateSpaceModel", "SMCResult", "Trajectories", "stack_to_first_dim", "ParticleMH",
            "ParticleGibbs", "ParticleGibbsResult", "TemperedSMC", "TemperedResult",
-           "PointwiseLikelihood", "PosteriorPredictive", "PSISLOO", "PSISLOGO", "PosteriorSummary"]
+           "PointwiseLikelihood", "PosteriorPredictive", "PSISLOO", "PSISLOGO", "PosteriorSummary",
+           "StateSummary"]

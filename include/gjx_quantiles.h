@@ -49,6 +49,42 @@
  * 2 Q) and, after the last sweep, writes the outputs.  Sweeps 1 and 2 histogram only the entries whose prefix is one of the
  * column's slots, GJX_QUANTILES_SLOTS_PER_LAUNCH slots per launch (one LDS histogram each), and run again per four slots:
  * ceil(2 Q / 4) launches each, of which a column with fewer slots leaves all but the first at once.
+ *
+ * WEIGHTED COLUMNS (GJX_QUANTILES_WEIGHTED; the version stays 0.1: the addition changes no declaration and no struct layout
+ * above, a C client detects it by the macro).  gjx_weighted_column_quantiles weighs entry i of data column c by the
+ * log-weight logw[(c % V) * logw_stride + i], V = n_weight_cols: V = 1 is one weight vector for all columns (the weighted
+ * paths of a trace-back), V = T with K segments of T columns a K-component carry's history against its T rows of
+ * log-weights.  What SMCResult.summary and Trajectories.summary ask of the library.  The radix select above counts entries;
+ * this one accumulates MASS, the max-anchored fixed-point weight of gjx.h — an integer, so a histogram of masses is
+ * order-independent.  Specification (exact; per data column c with its weight column v = c % V):
+ *
+ *   mass      m_v = the maximum over the non-NaN log-weights of column v (as gjx_max_f32 skips NaNs; -inf if there is none),
+ *             q_i = fixw(lw_i, m_v, F), F = min(gjx_frac_bits(n), 31): rint(exp(lw_i - m_v) 2^F) in the f32 arithmetic of
+ *             gjx.h, exactly 2^F where lw_i == m_v.  q_i <= 2^31 fits a u32 and a column's total stays below 2^62.  A NaN,
+ *             a -inf (also where it is the maximum) and anything more than 80 below the maximum weigh 0.  mass_out, where
+ *             given, receives q as u32 [V][n].
+ *   valid     an entry counts if its x is not NaN; nan = the number of NaN entries; W = the sum of q_i over the valid entries,
+ *             an exact u64.
+ *   target    T_j = min(max(ceil(p_j * (double) W), 1), W): one conversion, one float64 product, one ceil.
+ *   quant     quant[c][j] = the f32 value, bit for bit, of the first entry, ascending in the key above, whose inclusive
+ *             cumulative mass reaches T_j (entries of equal key are interchangeable): the inverted-CDF rule.  An entry of
+ *             mass 0 is never returned.  W = 0: NaN (0x7FC00000).
+ *   stats     stats[c][0 .. 5], f64: nan, mean, variance, min, max, ess; all but nan are NaN for W = 0.  min / max are over the
+ *             valid entries of positive mass, so p = 0 returns min and p = 1 max.  With the sums over the valid entries of
+ *             positive mass (a zero mass adds nothing, also before an infinite x):
+ *               S1 = sum (double) q_i * (double) x_i,                     mean = S1 / (double) W
+ *               S2 = sum (double) q_i * (((double) x_i - mean)^2),        variance = S2 / (double) W  (the population form: a
+ *                    weighted sample has no m - 1), taken in a later sweep
+ *               S0 = sum (double) q_i * (double) q_i,                     ess = (double) W * (double) W / S0
+ *             every product and sum rounding once, no FMA, in the fixed order above: blocks (the same B), head / quads /
+ *             tail by the DATA column's base, lanes, balanced tree, fold in index order.
+ *   No floating-point atomics: quant, nan, min, max and mass_out are bit-equal whatever max_workgroups is; mean, variance and
+ *   ess at equal max_workgroups.
+ *
+ * LAUNCHES, per batch: the clear, a PROLOGUE of two kernels — each weight column's maximum, then the u32 mass table (in the
+ * workspace, or in mass_out) so that a mass is evaluated once and a sweep streams 8 bytes per entry — and three sweeps on
+ * 12 / 10 / 10 key bits with u64 bins (4096 bins, then four slots of 1024: 32 KiB of LDS each), a pick kernel after each.
+ * There is one target per probability: at most Q slots, ceil(Q / 4) launches of sweeps 1 and 2.
  */
 #ifndef GJX_QUANTILES_H
 #define GJX_QUANTILES_H
@@ -66,6 +102,7 @@ extern "C" {
 #define GJX_QUANTILES_MAX_SEGMENTS 32
 #define GJX_QUANTILES_SLOTS_PER_LAUNCH 4
 #define GJX_QUANTILES_BATCH_COLS 256 /* columns of one batch: the workspace does not grow beyond them */
+#define GJX_QUANTILES_WEIGHTED 1     /* gjx_weighted_column_quantiles and its size function are declared below */
 
 typedef struct {
   const float* base; /* dev f32: column j of the segment starts at base + j * stride */
@@ -97,6 +134,31 @@ size_t gjx_quantiles_workspace_bytes(uint64_t n, uint32_t n_cols, int32_t n_prob
  * or NaN, ws not 8-byte aligned.
  * GJX_ERR_WORKSPACE: ws NULL or smaller than gjx_quantiles_workspace_bytes(n, n_cols, n_probs). */
 int gjx_column_quantiles(const gjx_column_quantiles_io* io, gjx_stream s);
+
+typedef struct {
+  uint64_t n;                                          /* as gjx_column_quantiles_io */
+  int32_t n_segments;
+  gjx_column_segment seg[GJX_QUANTILES_MAX_SEGMENTS];
+  const float* logw;                                   /* dev f32: weight column v starts at logw + v * logw_stride */
+  uint32_t n_weight_cols;                              /* V: 1 .. n_cols; data column c is weighed by weight column c % V */
+  uint64_t logw_stride;                                /* elements; >= n where V > 1 */
+  int32_t n_probs;                                     /* Q: 1 .. GJX_QUANTILES_MAX_PROBS */
+  const double* probs;                                 /* HOST f64[Q], each in [0, 1] */
+  float* quant;                                        /* dev f32[n_cols][Q]: an ENTRY of the column, bit for bit */
+  double* stats;                                       /* dev f64[n_cols][6]: nan, mean, variance, min, max, ess */
+  uint32_t* mass_out;                                  /* dev u32[V][n], nullable: the masses q_i every sum is over */
+  void* ws;                                            /* dev, 8-byte aligned; no word of it has to be zero */
+  size_t ws_bytes;
+  uint32_t max_workgroups;                             /* as gjx_column_quantiles_io */
+} gjx_weighted_quantiles_io;
+
+/* 0 for whatever gjx_weighted_column_quantiles refuses by its shape: as gjx_quantiles_workspace_bytes, and n_weight_cols
+ * outside 1 .. n_cols.  No growth beyond GJX_QUANTILES_BATCH_COLS columns. */
+size_t gjx_weighted_quantiles_workspace_bytes(uint64_t n, uint32_t n_cols, uint32_t n_weight_cols, int32_t n_probs);
+/* Per batch 7 + 2 ceil(Q / 4) launches on stream s.
+ * GJX_ERR_INVALID (nothing launched): what gjx_column_quantiles refuses, a NULL logw, n_weight_cols outside 1 .. n_cols,
+ * logw_stride < n where n_weight_cols > 1.  GJX_ERR_WORKSPACE: ws NULL or smaller than the size function's answer. */
+int gjx_weighted_column_quantiles(const gjx_weighted_quantiles_io* io, gjx_stream s);
 
 #ifdef __cplusplus
 }
