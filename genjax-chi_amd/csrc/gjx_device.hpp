@@ -1997,6 +1997,18 @@ struct PredictiveArgs {
 };
 constexpr int kPredictiveBlock = 4;  // particles a lane takes per round of scalar loads
 
+// Kernel argument block of the two launches of gjx_plate_loglik (include/gjx_plate_loglik.h; both kernels are generated from
+// the site table, gjx_plan_jit.hpp GenPlateLoglik).  Particles are on lanes; the rows of a workgroup's chunk (blockIdx.y of
+// the first launch) are wave-uniform.  The workspace holds one float64 plane [C][n] per plated site: lane i writes and reads
+// entry c * n + i, so every access is coalesced.
+struct PlateLoglikArgs {
+  const float* x[kTemperMaxLatents];  // latent columns: one vector load per lane and column
+  double* part;                       // [S][C][n]
+  float* lp_out;                      // nullable
+  float* ll_out;
+  uint32_t n, R, C;                   // particles, rows per chunk (a multiple of 4), chunks: (C - 1) R < n_rows <= C R
+};
+
 // Kernel argument block of the PSIS launches over a plated plan (include/gjx_psis.h; the kernel is generated from the site
 // table, gjx_plan_jit.hpp GenPsis, and launched four times: mode 0 .. 2 are the passes of the radix select, mode 3 collects;
 // psis_select and psis_finish below are fixed).  Particles are on lanes, a workgroup's kPsisRows rows are wave-uniform.
@@ -2382,6 +2394,28 @@ GJX_DEV void predictive_fold(const double* part, uint32_t W, uint32_t n_rows, ui
   for (int j = 0; j < 5; ++j) out[((size_t)s * 5 + j) * n_rows + d] = acc[j];
 }
 #endif
+
+// ---- the fixed device code of the row-split log-likelihood kernels (include/gjx_plate_loglik.h) -------------------------------
+// The rows lo .. hi - 1 of chunk c: c R .. min((c + 1) R, n_rows) - 1.  (C - 1) R < n_rows < 2^31, so c R does not wrap for a
+// chunk of the grid; a chunk past the last one (never launched) would come out empty.  Wave-uniform: c is blockIdx.y.
+GJX_DEV void plate_loglik_chunk(const PlateLoglikArgs& a, uint32_t n_rows, uint32_t c, uint32_t& lo, uint32_t& hi) {
+  const uint64_t lo64 = (uint64_t)c * a.R;
+  lo = lo64 < n_rows ? (uint32_t)lo64 : n_rows;
+  hi = n_rows - lo > a.R ? lo + a.R : n_rows;
+}
+// partial_c of plated site s and particle i: one plain vector store, consecutive lanes to consecutive doubles
+GJX_DEV void plate_loglik_store(const PlateLoglikArgs& a, uint32_t s, uint32_t c, uint32_t i, double v) {
+  a.part[((size_t)s * a.C + c) * a.n + i] = v;
+}
+// acc of plated site s and particle i: the C partials in chunk order, float64 from +0.0 (the header's fold).  The loads of a
+// round of four are independent of the adds before them; the adds stay in order.
+GJX_DEV double plate_loglik_fold(const PlateLoglikArgs& a, uint32_t s, uint32_t i) {
+  const double* at = a.part + (size_t)s * a.C * a.n + i;
+  double acc = 0.0;
+#pragma unroll 4
+  for (uint32_t c = 0; c < a.C; ++c) acc = acc + at[(size_t)c * a.n];
+  return acc;
+}
 
 // ---- the fixed device code of the PSIS kernels (include/gjx_psis.h) ------------------------------------------------------
 // The total order of the header: an integer key per f32 entry, every NaN last.  psis_unkey is its inverse on everything but

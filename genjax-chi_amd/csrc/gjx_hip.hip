@@ -15,6 +15,7 @@
 #include "../../include/gjx_csmc.h"
 #include "../../include/gjx_temper.h"
 #include "../../include/gjx_plate.h"
+#include "../../include/gjx_plate_loglik.h"
 #include "../../include/gjx_pointwise.h"
 #include "../../include/gjx_psis.h"
 #include "../../include/gjx_psis_units.h"
@@ -4937,7 +4938,9 @@ int gjx_backmove_run(gjx_backsim_plan* p, const gjx_backmove_io* io, void* ws, s
 enum TemperKernel { kTemperMove, kTemperCovMove, kTemperPointwise, kTemperPredictive, kTemperPsis, kTemperGroupedMove,
                     kTemperGroupedPointwise, kTemperGroupedPredictive, kTemperGroupedPsis, kTemperPsisUnits, kTemperGroupedPsisUnits,
                     kTemperGroupedCovMove,  // (the two before: the unit-sum kernel of include/gjx_psis_units.h, flat and grouped;
-                    kTemperKernelCount };   // the last: the block move of include/gjx_group_cov.h)
+                                            // this one: the block move of include/gjx_group_cov.h)
+                    kTemperLoglikRows, kTemperLoglikFold,  // the two launches of include/gjx_plate_loglik.h
+                    kTemperKernelCount };
 struct gjx_temper_plan {
   int n_sites, n_latents;
   int n_params;   // values set by gjx_temper_plan_set_params
@@ -4987,7 +4990,9 @@ constexpr TemperKernelDesc kTemperKernels[kTemperKernelCount] = {{"gjx_temper_mo
                                                 {"gjx_psis_grouped_kernel", gjx_jit::PlanKind::psis, false, true, true},
                                                 {"gjx_psis_units_kernel", gjx_jit::PlanKind::psis, false, true, false},
                                                 {"gjx_psis_units_grouped_kernel", gjx_jit::PlanKind::psis, false, true, true},
-                                                {"gjx_temper_move_grouped_cov_kernel", gjx_jit::PlanKind::temper, true, false, true}};
+                                                {"gjx_temper_move_grouped_cov_kernel", gjx_jit::PlanKind::temper, true, false, true},
+                                                {"gjx_plate_loglik_rows_kernel", gjx_jit::PlanKind::temper, true, false, false},
+                                                {"gjx_plate_loglik_fold_kernel", gjx_jit::PlanKind::temper, true, false, false}};
 // Has the plan a pointwise (and a predictive, and a PSIS) source?  A PLATED site, and no per-particle input column anywhere in the table
 // (the io structs have none).
 bool pointwise_plan_ok(const gjx_temper_plan* p) { return p && p->plated && p->max_input < 0 && p->n_grouped == 0; }
@@ -5025,6 +5030,11 @@ std::string temper_source(const gjx_temper_plan* p, TemperKernel k, int impl, Pl
   if (k == kTemperGroupedMove || k == kTemperGroupedCovMove) {
     gjx_jit::GenTemperGrouped<CSite, CArg> g;
     g.impl = impl; g.block = k == kTemperGroupedCovMove;
+    return run(g);
+  }
+  if (k == kTemperLoglikRows || k == kTemperLoglikFold) {
+    gjx_jit::GenPlateLoglik<CSite, CArg> g;
+    g.impl = impl; g.fold = k == kTemperLoglikFold;
     return run(g);
   }
   gjx_jit::GenTemper<CSite, CArg> g;
@@ -6093,6 +6103,93 @@ int gjx_group_cov_source(const gjx_temper_plan* p, int impl, char* buf, size_t b
   return temper_source_out(p, kTemperGroupedCovMove, impl, buf, buf_len, needed);
 }
 int gjx_group_cov_compile_check(const gjx_temper_plan* p, int impl) { return temper_compile_check(p, kTemperGroupedCovMove, impl); }
+}  // extern "C"
+
+// ---- the row-split log-likelihood of a plated plan (include/gjx_plate_loglik.h) ----------------------------------------------
+namespace {
+// R of the header's rule (0: arguments out of range).  C = ceil(n_rows / R).
+uint32_t loglik_rows_per_chunk(uint64_t n, uint64_t n_rows, uint32_t rows_per_chunk) {
+  if (n < 1 || n >= (1ull << 31) || n_rows < 1 || n_rows >= (1ull << 31) || (rows_per_chunk & 3u) != 0u) return 0;
+  auto up4 = [](uint64_t v) { return (v + 3) / 4 * 4; };
+  uint64_t R = rows_per_chunk;
+  if (R == 0) {
+    const uint64_t tiles = nrows_of(n), want = (GJX_PLATE_LOGLIK_TARGET_WORKGROUPS + tiles - 1) / tiles;
+    R = up4((n_rows + want - 1) / want);
+    if (R < GJX_PLATE_LOGLIK_MIN_ROWS) R = GJX_PLATE_LOGLIK_MIN_ROWS;
+  }
+  if ((n_rows + R - 1) / R > GJX_PLATE_LOGLIK_MAX_CHUNKS) R = up4((n_rows + GJX_PLATE_LOGLIK_MAX_CHUNKS - 1) / GJX_PLATE_LOGLIK_MAX_CHUNKS);
+  return (uint32_t)R;  // (< 2^31 + 4)
+}
+// the plans gjx_plate_loglik and its source / compile_check serve, and their kernel by index
+bool loglik_plan_ok(const gjx_temper_plan* p) { return p && p->plated && p->n_grouped == 0; }
+int loglik_n_plated(const gjx_temper_plan* p) {
+  int S = 0;
+  for (int q = 0; q < p->n_sites; ++q) S += p->sites[q].observed == GJX_SITE_PLATED;
+  return S;
+}
+}  // namespace
+extern "C" {
+int gjx_plate_loglik_version(int* major, int* minor) {
+  return version_out(major, minor, GJX_PLATE_LOGLIK_VERSION_MAJOR, GJX_PLATE_LOGLIK_VERSION_MINOR);
+}
+uint32_t gjx_plate_loglik_chunks(uint64_t n, uint64_t n_rows, uint32_t rows_per_chunk) {
+  const uint64_t R = loglik_rows_per_chunk(n, n_rows, rows_per_chunk);
+  return R ? (uint32_t)((n_rows + R - 1) / R) : 0u;
+}
+size_t gjx_plate_loglik_workspace_bytes(uint64_t n, uint64_t n_rows, uint32_t rows_per_chunk, int32_t n_plated) {
+  if (n_plated < 1 || n_plated > GJX_MAX_SITES) return 0;
+  return (size_t)gjx_plate_loglik_chunks(n, n_rows, rows_per_chunk) * (size_t)n * (size_t)n_plated * sizeof(double);
+}
+int gjx_temper_plan_n_plated(const gjx_temper_plan* p) { return p ? loglik_n_plated(p) : GJX_ERR_INVALID; }
+int gjx_plate_loglik_source(const gjx_temper_plan* p, int kernel, int impl, char* buf, size_t buf_len, size_t* needed) {
+  if (!loglik_plan_ok(p) || (kernel != 0 && kernel != 1)) return GJX_ERR_INVALID;
+  return temper_source_out(p, kernel ? kTemperLoglikFold : kTemperLoglikRows, impl, buf, buf_len, needed);
+}
+int gjx_plate_loglik_compile_check(const gjx_temper_plan* p, int kernel, int impl) {
+  if (!loglik_plan_ok(p) || (kernel != 0 && kernel != 1)) return GJX_ERR_INVALID;
+  return temper_compile_check(p, kernel ? kTemperLoglikFold : kTemperLoglikRows, impl);
+}
+int gjx_plate_loglik(gjx_temper_plan* p, const gjx_plate_loglik_io* io, void* ws, size_t ws_bytes, gjx_stream s) {
+  if (!loglik_plan_ok(p) || !io || !p->has_data || io->n < 1 || io->n >= (1ull << 31) || (io->impl != 0 && io->impl != 1) || !io->ll_out ||
+      (io->rows_per_chunk & 3u) != 0u || ((uintptr_t)ws & 7) != 0)
+    return GJX_ERR_INVALID;
+  if (io->n_input_cols < 0 || io->n_input_cols > 16 || io->n_input_cols <= p->max_input || (io->n_input_cols && !io->input_cols) ||
+      p->n_params <= p->max_param)
+    return GJX_ERR_INVALID;
+  PlateLoglikArgs A;
+  memset(&A, 0, sizeof A);
+  for (int l = 0; l < p->n_latents; ++l) {
+    if (!io->x_in[l]) return GJX_ERR_INVALID;
+    A.x[l] = io->x_in[l];
+  }
+  RunCols cols;
+  memset(&cols, 0, sizeof cols);
+  for (int c = 0; c < io->n_input_cols; ++c) {
+    if (c <= p->max_input && !io->input_cols[c]) return GJX_ERR_INVALID;
+    cols.in[c] = io->input_cols[c];
+  }
+  const uint32_t D = p->data.n_rows;
+  A.n = (uint32_t)io->n;
+  A.R = loglik_rows_per_chunk(io->n, D, io->rows_per_chunk);
+  A.C = (uint32_t)(((uint64_t)D + A.R - 1) / A.R);
+  if (!ws || ws_bytes < gjx_plate_loglik_workspace_bytes(io->n, D, io->rows_per_chunk, loglik_n_plated(p))) return GJX_ERR_WORKSPACE;
+  if (!gjx_jit::enabled()) return GJX_ERR_UNSUPPORTED;  // generated kernels only
+  gjx_jit::CompiledKernel* rows = temper_compiled(p, kTemperLoglikRows, io->impl);
+  gjx_jit::CompiledKernel* fold = rows ? temper_compiled(p, kTemperLoglikFold, io->impl) : nullptr;
+  if (!rows || !fold) return GJX_ERR_JIT;
+  A.part = static_cast<double*>(ws);
+  A.lp_out = io->lp_out; A.ll_out = io->ll_out;
+  const uint64_t tiles = nrows_of(io->n);
+  unsigned grid = (unsigned)(tiles < kTemperMaxGrid ? tiles : kTemperMaxGrid);
+  if (io->max_workgroups && grid > io->max_workgroups) grid = io->max_workgroups;
+  PlanParams prm = p->prm;
+  PlateData pd = p->data;
+  PlanTables rows_tabs = rows->tabs, fold_tabs = fold->tabs;
+  void* rows_args[] = {&A, &cols, &prm, &rows_tabs, &pd};
+  if (int rc = launch_generated(rows->fn, grid, A.C, kBlock, s, rows_args)) return rc;
+  void* fold_args[] = {&A, &cols, &prm, &fold_tabs};
+  return launch_generated(fold->fn, grid, 1, kBlock, s, fold_args);
+}
 
 int gjx_pointwise_version(int* major, int* minor) {
   return version_out(major, minor, GJX_POINTWISE_VERSION_MAJOR, GJX_POINTWISE_VERSION_MINOR);

@@ -1714,8 +1714,9 @@ struct GenTemper {
   // against a kernel argument and the columns are constant-address-space pointers out of the argument block, so every read
   // is a wave-uniform SCALAR load; a block of kPlateBlock rows issues its loads (one s_load_dwordx4 per column) before its
   // arithmetic, a remainder loop takes the last n_rows % kPlateBlock rows.  Rows enter the float64 sum in index order.
+  // (GenPlateLoglik walks a chunk of the rows instead: `lo` .. `hi` - 1, hi <= pd.n_rows, and hands the sum to `finish`.)
   static constexpr int kPlateBlock = 4;
-  void emit_plated(int q, const CSiteT* tab) {
+  void emit_plated(int q, const CSiteT* tab, const char* lo = "0u", const char* hi = "pd.n_rows", const std::string& finish = "") {
     const std::vector<int> cs = TemperTable<CSiteT, CArgT>::plate_cols(tab[q]);
     const std::string Q = std::to_string(q);
     std::ostringstream body;  // one row: head (arguments and value from dc<c>), the log-density, the float64 accumulate
@@ -1725,20 +1726,24 @@ struct GenTemper {
     body << "      pacc" << Q << " = pacc" << Q << " + (double)(" << e.lp_of(q) << ");\n";
     o << "  // site " << q << ": plated over pd.n_rows data rows\n";
     for (int c : cs) o << "  const PlateCol pc" << Q << "_" << c << " = (PlateCol)pd.col[" << c << "];\n";
-    o << "  double pacc" << Q << " = 0.0;\n  uint32_t d" << Q << " = 0u;\n";
-    o << "  for (; d" << Q << " + " << kPlateBlock << "u <= pd.n_rows; d" << Q << " += " << kPlateBlock << "u) {\n";
+    o << "  double pacc" << Q << " = 0.0;\n  uint32_t d" << Q << " = " << lo << ";\n";
+    o << "  for (; d" << Q << " + " << kPlateBlock << "u <= " << hi << "; d" << Q << " += " << kPlateBlock << "u) {\n";
+    // (a chunk's counter starts at an unknown row: its 32-bit `d + j` could wrap for all the compiler knows, and four loads
+    // whose addresses need not be consecutive stay four s_load_dword; the widened index cannot wrap)
+    const char* wide = finish.empty() ? "" : "(size_t)";
     for (int c : cs)
       for (int j = 0; j < kPlateBlock; ++j)
-        o << "    const float r" << c << "_" << j << " = pc" << Q << "_" << c << "[d" << Q << " + " << j << "u];\n";
+        o << "    const float r" << c << "_" << j << " = pc" << Q << "_" << c << "[" << wide << "d" << Q << " + " << j << "u];\n";
     for (int j = 0; j < kPlateBlock; ++j) {
       o << "    {\n";
       for (int c : cs) o << "      const float dc" << c << " = r" << c << "_" << j << ";\n";
       o << body.str() << "    }\n";
     }
-    o << "  }\n  for (; d" << Q << " < pd.n_rows; ++d" << Q << ") {\n    {\n";
+    o << "  }\n  for (; d" << Q << " < " << hi << "; ++d" << Q << ") {\n    {\n";
     for (int c : cs) o << "      const float dc" << c << " = pc" << Q << "_" << c << "[d" << Q << "];\n";
     o << body.str() << "    }\n  }\n";
-    o << "  ll = ll + (float)pacc" << Q << ";\n";
+    if (finish.empty()) o << "  ll = ll + (float)pacc" << Q << ";\n";
+    else o << finish;
   }
 
   // `v` outside the OPEN support of a latent of family `dist` (a NaN included) has log-density -inf, whatever the density
@@ -1824,6 +1829,78 @@ struct GenTemper {
     o << "    }\n";
     for (int l = 0; l < L; ++l) o << "    a.x_out[" << l << "][i] = x" << l << ";\n";
     o << "    a.lp_out[i] = lp;\n    a.ll_out[i] = ll;\n    if (a.n_accept) a.n_accept[i] = acc;\n";
+    o << "  }\n}\n";
+    return o.str();
+  }
+};
+
+// The two kernels of gjx_plate_loglik (include/gjx_plate_loglik.h): tm_assess of a plated plan cut in two along the ROWS.  The
+// move kernel gives a particle to a lane and every row to that lane; at n = 4096 that is 64 waves on a device with room
+// for thousands, whatever the number of rows.  Here the grid is 2-D:
+//   rows   (fold == false) gjx_plate_loglik_rows_kernel: workgroup (x, y) owns the particle tiles x, x + gridDim.x, ... and
+//          row chunk y.  A lane holds its particle's latents in registers and walks the chunk's rows with the loop of
+//          GenTemper::emit_plated between the chunk's bounds — the same wave-uniform scalar loads in blocks of kPlateBlock
+//          rows, the same remainder loop (a chunk's last 1 .. 3 rows are read one by one: nothing past pd.n_rows), the same
+//          float64 sum in row order.  The unplated sites contribute their heads alone: the values a plated site may refer to.
+//          One float64 store per plated site, lane i to entry i of the chunk's plane: coalesced.
+//   fold   (fold == true) gjx_plate_loglik_fold_kernel: tm_assess itself, one lane per particle, with every plated site's row
+//          loop replaced by the sum of its C partials in chunk order (gjx_device.hpp plate_loglik_fold); lp, the unplated
+//          observed sites' terms and the adds into ll are GenTemper::emit_site's text.
+// Neither kernel has LDS or a barrier: a row's data reach every lane through the scalar cache, and lanes share nothing else.
+// Neither source holds a data value, a parameter value, n, n_rows, R or C.
+template <class CSiteT, class CArgT>
+struct GenPlateLoglik {
+  int impl;
+  const CSiteT* sites;
+  int n_sites;
+  bool fold = false;
+
+  std::string run() {
+    GenTemper<CSiteT, CArgT> g;  // (its stream and its emitters of a site and of a plated site's loop)
+    g.impl = impl; g.sites = sites; g.n_sites = n_sites;
+    std::ostringstream& o = g.o;
+    emit_prelude(o);
+    const TemperTable<CSiteT, CArgT> t(sites, n_sites);
+    const std::string head = "(const PlateLoglikArgs& a, const RunCols& cols, const PlanParams& prm, const PlanTables& tabs, uint32_t li, uint32_t i" +
+                             t.list(", float nx_");
+    SiteEmitter<CSiteT, CArgT> e{o, impl, 0, t.tab.data(), n_sites, "  ", ""};
+    e.exact_cuts = false;
+    if (fold) {
+      o << "__device__ __forceinline__ void pl_fold" << head << ", float& lp_out, float& ll_out) {\n";
+      o << "  (void)a; (void)cols; (void)prm; (void)tabs; (void)li; (void)i;\n  float lp = 0.0f, ll = 0.0f;\n";
+      for (int q = 0, s = 0; q < n_sites; ++q) {
+        if (sites[q].observed != GJX_SITE_PLATED) {
+          g.emit_site(e, q, t.tab.data());
+          continue;
+        }
+        o << "  // site " << q << ": plated — its chunks' partial sums, in chunk order\n";
+        o << "  ll = ll + (float)plate_loglik_fold(a, " << s++ << "u, i);\n";
+      }
+      o << "  lp_out = lp; ll_out = ll;\n}\n";
+    } else {
+      o << "__device__ __forceinline__ void pl_rows" << head << ", const PlateData& pd, uint32_t c, uint32_t lo, uint32_t hi) {\n";
+      o << "  (void)a; (void)cols; (void)prm; (void)tabs; (void)li; (void)i;\n";
+      for (int q = 0, s = 0; q < n_sites; ++q) {
+        if (sites[q].observed != GJX_SITE_PLATED) {
+          e.head(q);
+          continue;
+        }
+        g.emit_plated(q, t.tab.data(), "lo", "hi", "  plate_loglik_store(a, " + std::to_string(s++) + "u, c, i, pacc" + std::to_string(q) + ");\n");
+      }
+      o << "}\n";
+    }
+    o << "extern \"C\" __global__ __launch_bounds__(256) void " << (fold ? "gjx_plate_loglik_fold_kernel" : "gjx_plate_loglik_rows_kernel")
+      << "(PlateLoglikArgs a, RunCols cols, PlanParams prm, PlanTables tabs" << (fold ? "" : ", PlateData pd") << ") {\n";
+    if (!fold) o << "  uint32_t lo, hi;\n  plate_loglik_chunk(a, pd.n_rows, blockIdx.y, lo, hi);\n";
+    o << "  for (uint64_t i64 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i64 < a.n; i64 += (uint64_t)gridDim.x * blockDim.x) {\n";
+    o << "    const uint32_t i = (uint32_t)i64;\n";
+    for (int l = 0; l < t.L; ++l) o << "    const float x" << l << " = a.x[" << l << "][i];\n";
+    if (fold) {
+      o << "    float lp, ll;\n    pl_fold(a, cols, prm, tabs, i, i" << t.list(", x") << ", lp, ll);\n";
+      o << "    if (a.lp_out) a.lp_out[i] = lp;\n    a.ll_out[i] = ll;\n";
+    } else {
+      o << "    pl_rows(a, cols, prm, tabs, i, i" << t.list(", x") << ", pd, blockIdx.y, lo, hi);\n";
+    }
     o << "  }\n}\n";
     return o.str();
   }

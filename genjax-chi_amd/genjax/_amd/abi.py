@@ -140,6 +140,10 @@ class QuantilesUnavailable(HeaderUnavailable):
     header, why = "gjx_quantiles.h", "the radix select over columns in device memory and its moments are HIP kernels only"
 
 
+class PlateLoglikUnavailable(HeaderUnavailable):
+    header, why = "gjx_plate_loglik.h", "the row-split log-likelihood of a plated plan runs as two generated HIP kernels only"
+
+
 class Keys(C.Structure):
     _fields_ = [
         ("impl", C.c_int32),
@@ -981,6 +985,39 @@ QUANTILES_PROTOTYPES = {
 }
 QUANTILES_ABI_VERSION = (0, 1)
 
+# include/gjx_plate_loglik.h: a TWENTIETH header, same arrangement — the log-likelihood of a plated tempered plan over a
+# population with the work split over data rows as well as particles: two generated launches, float64 partials per row chunk.
+PLATE_LOGLIK_TARGET_WORKGROUPS = 1024  # gjx_plate_loglik.h: GJX_PLATE_LOGLIK_TARGET_WORKGROUPS
+PLATE_LOGLIK_MAX_CHUNKS = 1024         # GJX_PLATE_LOGLIK_MAX_CHUNKS
+PLATE_LOGLIK_MIN_ROWS = 64             # GJX_PLATE_LOGLIK_MIN_ROWS
+
+
+class PlateLoglikIO(C.Structure):
+    """gjx_plate_loglik_io (include/gjx_plate_loglik.h)."""
+    _fields_ = [
+        ("impl", C.c_int32),
+        ("rows_per_chunk", C.c_uint32),
+        ("n", C.c_uint64),
+        ("x_in", C.c_void_p * TEMPER_MAX_LATENTS),
+        ("input_cols", C.POINTER(C.c_void_p)),
+        ("n_input_cols", C.c_int32),
+        ("max_workgroups", C.c_uint32),
+        ("ll_out", C.c_void_p),
+        ("lp_out", C.c_void_p),
+    ]
+
+
+PLATE_LOGLIK_PROTOTYPES = {
+    "gjx_plate_loglik_version": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gjx_plate_loglik_chunks": (C.c_uint32, [C.c_uint64, C.c_uint64, C.c_uint32]),
+    "gjx_plate_loglik_workspace_bytes": (C.c_size_t, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int32]),
+    "gjx_temper_plan_n_plated": (C.c_int, [_P]),
+    "gjx_plate_loglik": (C.c_int, [_P, C.POINTER(PlateLoglikIO), _P, C.c_size_t, _P]),
+    "gjx_plate_loglik_source": (C.c_int, [_P, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gjx_plate_loglik_compile_check": (C.c_int, [_P, C.c_int, C.c_int]),
+}
+PLATE_LOGLIK_ABI_VERSION = (0, 1)
+
 # The optional headers, in the order they are bound: every one is exported by libgjx_hip.so only and bound if present.
 class Header(collections.namedtuple("Header", "key header version_fn prototypes version_name unavailable")):
     @property
@@ -1046,6 +1083,15 @@ SUMMARY_HEADERS = {h.key: h for h in (
 )}
 
 
+# Headers that evaluate a plated plan for a sampler other than the tempered one (gjx_plate_loglik.h: importance weights).  A
+# table of its own, and kept out of bound_headers(), once more: the suites of the earlier headers pin that tuple whole.
+# library_headers() is what a library is bound with.
+LOGLIK_HEADERS = {h.key: h for h in (
+    Header("plate_loglik", "gjx_plate_loglik.h", "gjx_plate_loglik_version", PLATE_LOGLIK_PROTOTYPES, "PLATE_LOGLIK_ABI_VERSION",
+           PlateLoglikUnavailable),
+)}
+
+
 def all_optional_headers():
     """Every header next to gjx.h, in binding order: OPTIONAL_HEADERS, then EXTENSION_HEADERS, then PLAN_HEADERS, then
     MOVE_HEADERS."""
@@ -1058,7 +1104,12 @@ def bound_headers():
     return (*all_optional_headers(), *SUMMARY_HEADERS.values(), *CHECK_HEADERS.values())
 
 
-_HEADER_OF = {name: h for h in bound_headers() for name in h.prototypes}  # entry point -> its optional header
+def library_headers():
+    """Every header a library is bound with, in binding order: bound_headers(), then LOGLIK_HEADERS."""
+    return (*bound_headers(), *LOGLIK_HEADERS.values())
+
+
+_HEADER_OF = {name: h for h in library_headers() for name in h.prototypes}  # entry point -> its optional header
 
 _NO_STATUS = {
     "gjx_temper_plan_n_latents",
@@ -1067,6 +1118,9 @@ _NO_STATUS = {
     "gjx_temper_ladder_workspace_bytes",
     "gjx_pointwise_chunks",
     "gjx_pointwise_workspace_bytes",
+    "gjx_plate_loglik_chunks",
+    "gjx_plate_loglik_workspace_bytes",
+    "gjx_temper_plan_n_plated",
     "gjx_predictive_chunks",
     "gjx_psis_tail_len",
     "gjx_psis_workspace_bytes",
@@ -1121,7 +1175,7 @@ class GjxLib:
         # is "wrong version", not "missing symbol"
         self.has = {}
         major, minor = C.c_int(-1), C.c_int(-1)
-        for h in (_CORE_HEADER, *bound_headers()):
+        for h in (_CORE_HEADER, *library_headers()):
             if h is not _CORE_HEADER:
                 self.has[h.key] = hasattr(self._dll, h.version_fn)
                 setattr(self, "has_" + h.key, self.has[h.key])
@@ -1148,7 +1202,7 @@ class GjxLib:
     def require(self, key: str, fn_name: str):
         """Raise the header's *Unavailable, naming `fn_name`, on a library without the optional header `key`."""
         if not self.has[key]:
-            raise next(h for h in bound_headers() if h.key == key).unavailable(fn_name, self.name)
+            raise next(h for h in library_headers() if h.key == key).unavailable(fn_name, self.name)
 
     def call(self, name: str, *args):
         h = _HEADER_OF.get(name)

@@ -375,6 +375,12 @@ class ImportanceK(SMCAlgorithm):
         return self.target
 
     def run_smc(self, key):
+        if self._plated_state() is not None:
+            from .plan import PlanUnsupported
+
+            m = next(m for m in self._plated_state()["tracer"].meta if m.get("plated"))
+            raise PlanUnsupported(f"ImportanceK.run_smc: the plated site at address {m['addr']!r} has no per-site trace; use "
+                                  "weighted_population() or log_marginal_likelihood_estimate()")
         key, sub_key = split(key)
         sub_keys = split(sub_key, self.get_num_particles())
         if self.q is not None:
@@ -466,11 +472,95 @@ class ImportanceK(SMCAlgorithm):
             raise
         return out
 
+    # -- a PLATED target: one observed site over device data columns of any length D (`normal(w * xs + b, s) @ "y"` with xs,
+    # ys of D rows), no proposal.  The importance plans know no plated site and the per-site route has no [K] x [D] broadcast;
+    # a tempered plan holds such a body (temper.lower).  The latents are drawn from the prior by the plan of the body WITHOUT
+    # its plated sites (temper.prior_table: what stage 0 of TemperedSMC.run draws from), and the weights are the
+    # log-likelihood column of gjx_plate_loglik (include/gjx_plate_loglik.h) — a prior proposal cancels lp.
+    def _plated_state(self):
+        """-> the lowered target (a dict) when this route serves it, None when another route does.  PlanUnsupported for a
+        plated target with grouped latents (grouped plans are out of scope of include/gjx_plate_loglik.h)."""
+        ops = get_ops()
+        states = self.__dict__.setdefault("_plated", {})
+        tid = threading.get_ident()  # (one state per host thread: a tempered plan takes its parameters set-then-run)
+        st = states.get(tid)
+        if st is not None and st["ops"] is ops:
+            return st["lowered"]
+        from . import temper
+        from .lang import StaticGenerativeFunction
+        from .plan import PlanUnsupported, is_data_tensor
+
+        states[tid] = st = dict(ops=ops, lowered=None)
+        n = self.get_num_particles()
+        if self.q is not None or not isinstance(self.target.p, StaticGenerativeFunction):
+            return None
+        rows = {t.numel() for t in list(self.target.args) + [v for _, v in self.target.constraint.leaves()] if is_data_tensor(t)}
+        # (no data column: another route's target.  D == K: the per-site route takes such a tensor for a column over the
+        # particles today, and keeps it)
+        if not rows or n in rows or not all(ops.lib.has.get(h) for h in ("temper", "plate", "plate_loglik")):
+            return None
+        try:
+            tracer = temper.lower(self.target, n)
+        except PlanUnsupported:
+            return None
+        if not tracer.data:
+            return None
+        if tracer.n_grouped:
+            at = next(m["addr"] for m in tracer.meta if m.get("grouped"))
+            del states[tid]  # (refused at every call)
+            raise PlanUnsupported(f"ImportanceK: the grouped latent at address {at!r} is not supported (include/gjx_plate_loglik.h: "
+                                  "grouped plans are out of scope); use TemperedSMC")
+        st["lowered"] = dict(ops=ops, tracer=tracer, n=n, latents=[m for m in tracer.meta if m["obs"] is None],
+                             tplan=ops.temper_plan_create(tracer.sites, keep=(tracer.keep, tracer)), prior=temper.prior_table(tracer),
+                             ladder_ws=None)
+        return st["lowered"]
+
+    def _plated_population(self, st, key):
+        """-> (the latent columns in latent order, ll f32[K]): the prior draw under the key batch run_smc derives inside
+        log_marginal_likelihood_estimate(key) — split_lazy(split_at(split_at(key, 1), 1), K) — and the two launches of
+        gjx_plate_loglik.  Data and parameters are set at every call: an in-place update of a data tensor is seen."""
+        from .plan import _make_plan
+
+        if type(key) is not prng.PRNGKey:
+            raise TypeError("expected a scalar PRNG key")
+        ops, tracer, tplan, n = st["ops"], st["tracer"], st["tplan"], st["n"]
+        plan = _make_plan(st["prior"])  # (sets the importance plan's launch parameters)
+        if tracer.params:
+            tplan.set_params(tracer.params)
+        tplan.set_data(tracer.data_columns(ops.device()))
+        kb = prng.split_lazy(prng.split_at(prng.split_at(key, 1), 1), n)
+        vals = ops.importance_run(plan, kb, n, [], [torch.float32] * tracer.n_out, want_score=False, want_max_partials=False)[0]
+        x = [vals[m["out_col"]] for m in st["latents"]]
+        ll, _ = ops.plate_loglik(tplan, x, impl=key.impl, want_lp=False)
+        return x, ll
+
+    def weighted_population(self, key):
+        """The weighted population of a plated target under a prior proposal -> (choices, log_weights, ess): the latent columns
+        by address (a ChoiceMap of f32[K] device tensors), the f32[K] log-weights (the log-likelihood of every particle) and
+        the effective sample size (sum w)^2 / sum w^2 as a float64 scalar on the device (gjx_temper_ess_ladder at delta = 1: no
+        torch reduction).  The population is the one log_marginal_likelihood_estimate(key) weighs: the same key derivation."""
+        from .plan import PlanUnsupported
+
+        st = self._plated_state()
+        if st is None:
+            raise PlanUnsupported("ImportanceK.weighted_population: the target has no plated site (an observed site over data "
+                                  "columns, no proposal); run_smc() returns the population of every other target")
+        x, ll = self._plated_population(st, key)
+        if st["ladder_ws"] is None:
+            st["ladder_ws"] = st["ops"].temper_ladder_workspace(st["n"])
+        sums = st["ops"].temper_ess_ladder(ll, [1.0], st["ladder_ws"])  # f64 [S1, S2, max]
+        choices = ChoiceMap.from_mapping([(m["addr"], c) for m, c in zip(st["latents"], x)])
+        return choices, ll, sums[0] * sums[0] / sums[1]
+
     def log_marginal_likelihood_estimate(self, key, target: Target | None = None):
         if target is None:
             fast = self._fast_estimate(key)
             if fast is not None:
                 return fast
+            st = self._plated_state()
+            if st is not None:  # the exact fixed-point log-sum-exp of ll (gjx_logsumexp_f32), minus log K: an f32 device scalar
+                _, ll = self._plated_population(st, key)
+                return st["ops"].logsumexp(ll)[0][0] - math.log(st["n"])
         return super().log_marginal_likelihood_estimate(key, target)
 
     def random_weighted_batch(self, keys, *args):

@@ -957,6 +957,38 @@ class Ops:
             self.lib.call("gjx_temper_pointwise_grouped", plan.handle, C.byref(io), C.byref(cols), self.stream())
         return out.view(4, D)
 
+    def plate_loglik(self, plan: "TemperPlan", x: list, *, impl: int = 1, rows_per_chunk: int = 0, input_cols=(), want_lp: bool = True,
+                     max_workgroups: int = 0, ws: torch.Tensor | None = None):
+        """gjx_plate_loglik (include/gjx_plate_loglik.h): TWO launches -> (ll, lp or None), float32[n] on the device — `assess`
+        of the plated plan at the L latent columns `x` (float32[n]), the plated sites' rows summed in float64 per chunk of
+        `rows_per_chunk` rows (0: the library's rule) and the chunks in order.  Nothing is drawn, nothing read back.
+        `ws`: a uint8 device tensor of at least plate_loglik_workspace_bytes(plan, n, rows_per_chunk) bytes (None: per call)."""
+        self.lib.require("plate_loglik", "gjx_plate_loglik")
+        if not getattr(plan, "plated", False) or not plan.n_rows:
+            raise ValueError("plate_loglik: the plan has no plated site, or no data (TemperPlan.set_data)")
+        L, n = plan.n_latents, x[0].numel()
+        if len(x) != L:
+            raise ValueError(f"plate_loglik: the plan has {L} latents, got {len(x)} columns")
+        io = abi.PlateLoglikIO()
+        io.impl, io.rows_per_chunk, io.n, io.max_workgroups = int(impl), int(rows_per_chunk), n, int(max_workgroups)
+        for l in range(L):
+            io.x_in[l] = self._chk(x[l], torch.float32, n, f"x[{l}]").value
+        ins = (C.c_void_p * max(1, len(input_cols)))()
+        for i, t in enumerate(input_cols):
+            ins[i] = self._chk(t, torch.float32, n, f"input_cols[{i}]").value
+        io.input_cols, io.n_input_cols = ins, len(input_cols)
+        out = self.empty_columns(n, [torch.float32] * (2 if want_lp else 1))
+        io.ll_out, io.lp_out = out[0].data_ptr(), out[1].data_ptr() if want_lp else None
+        if ws is None:  # (uninitialised: the first launch writes every entry the second reads)
+            ws = torch.empty(max(self.plate_loglik_workspace_bytes(plan, n, rows_per_chunk), 8), dtype=torch.uint8, device=self._alloc_device)
+        self.lib.call("gjx_plate_loglik", plan.handle, C.byref(io), ws.data_ptr(), ws.numel(), self.stream())
+        return out[0], (out[1] if want_lp else None)
+
+    def plate_loglik_workspace_bytes(self, plan: "TemperPlan", n: int, rows_per_chunk: int = 0) -> int:
+        """gjx_plate_loglik_workspace_bytes for the plan's data rows and plated sites (0: arguments out of range)."""
+        self.lib.require("plate_loglik", "gjx_plate_loglik_workspace_bytes")
+        return int(self.lib.call("gjx_plate_loglik_workspace_bytes", int(n), int(plan.n_rows), int(rows_per_chunk), int(plan.n_plated)))
+
     def temper_psis(self, plan: "TemperPlan", x: list, tail_len: int, want_tail: bool = False, z=None):
         """gjx_temper_psis (include/gjx_psis.h): PSIS-LOO of the plan's data rows under the n equally weighted particles of
         the columns `x` (the L latent columns, float32[n]) -> (out float64[7, D]: elpd_loo, khat, sigma, s, tT, B, bad;
@@ -1549,6 +1581,18 @@ class TemperPlan(PlanHandle):
     def pointwise_source(self) -> str:
         """The HIP source of the plan's generated pointwise kernel (one per plan: it draws nothing)."""
         return self._source("gjx_pointwise_source")
+
+    LOGLIK_KERNELS = {"rows": 0, "fold": 1}
+
+    def loglik_source(self, kernel: str, impl: int) -> str:
+        """The HIP source of a generated kernel of gjx_plate_loglik (include/gjx_plate_loglik.h): "rows" or "fold"."""
+        self.ops.lib.require("plate_loglik", "gjx_plate_loglik_source")
+        return self._source("gjx_plate_loglik_source", self.LOGLIK_KERNELS[kernel], impl)
+
+    def loglik_compile_check(self, kernel: str, impl: int) -> int:
+        """gjx_plate_loglik_compile_check: the status, not raised."""
+        self.ops.lib.require("plate_loglik", "gjx_plate_loglik_compile_check")
+        return self.ops.lib._gjx_plate_loglik_compile_check(self.handle, self.LOGLIK_KERNELS[kernel], impl)
 
     def predictive_compile_check(self, impl: int) -> int:
         """gjx_predictive_compile_check (include/gjx_predictive.h): the status, not raised."""
